@@ -9,6 +9,12 @@ synthetic 128-phoneme utterances per GPU (BASELINE.json configs[2]; SURVEY.md §
 already resident in HBM, durations pinned to 3,3,3,4 (F = 422 frames = 10.55 s of audio each).
 Ranks hold different utterances (weak scaling); the only collective is the one-time
 broadcast of the weight blob.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else it can measure
+(roofline of the dominant kernel from per-launch events, CPU baseline, free-running and host-buffer
+steps, the other precisions, batch-1 latency, serving leg, `--detail`) runs with `--full` only.
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs) for output-for-output
+comparisons of two builds.
 """
 from __future__ import annotations
 
@@ -25,6 +31,9 @@ sys.path.insert(0, ROOT)
 
 PEAK_F32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
 PEAK_F16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: BF16/F16 MFMA, dense (no sparsity)
+DUMP_LIMIT_BYTES = 60 << 20    # --dump-outputs stays under 64 MB in all
+# the secondary measurements and their values under --full (a plain run has them all off)
+FULL_DEFAULTS = {"cpu_utts": 12, "free_run": 1, "pcie": 1, "reduced": 1, "serve": 1, "latency_b1": 50}
 _T0 = time.perf_counter()
 
 
@@ -40,6 +49,54 @@ def synthetic_ids(B: int, n_phonemes: int, seed: int) -> np.ndarray:
     ids = rng.integers(1, 178, size=(B, n_phonemes), dtype=np.int64)
     z = np.zeros((B, 1), np.int64)
     return np.concatenate([z, ids, z], axis=1)
+
+
+def synthetic_blob() -> str:
+    """Path of the seeded synthetic weight file, created on first use.  Where the package keeps it (build/ of the tree, or
+    KOKOROX_AMD_CACHE) when that directory can be written or already holds it; otherwise (a checkout the benchmarking user
+    cannot write) the user's cache directory, then the temporary directory.  Written under a temporary name and renamed,
+    so that an interrupted run leaves no truncated file behind."""
+    import shutil
+    import tempfile
+    from kokorox_amd import weights as W
+    path = W.default_blob_path()
+    name = os.path.basename(path)
+    cache = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+    dirs = [os.path.dirname(path), os.path.join(cache, "kokorox_amd"),
+            os.path.join(tempfile.gettempdir(), f"kokorox_amd-{os.getuid()}")]
+    for d in dirs:
+        if os.path.exists(os.path.join(d, name)):
+            return os.path.join(d, name)
+    for d in dirs:
+        try:
+            os.makedirs(d, exist_ok=True)
+            tmp = tempfile.mkdtemp(dir=d)
+        except OSError:
+            continue
+        try:
+            os.replace(W.ensure_synthetic_blob(os.path.join(tmp, name)), os.path.join(d, name))
+        finally:
+            shutil.rmtree(tmp, ignore_errors=True)
+        return os.path.join(d, name)
+    raise SystemExit(f"bench.py: no writable directory for the synthetic weight file {name} among {dirs}")
+
+
+def dump_outputs(out_dir: str, audio: np.ndarray, frames: np.ndarray):
+    """Write what a caller of the timed path receives after its last step: `audio.npy` = the waveform rows [n, ld]
+    (float32; the samples past 600 * frames of a row are not the caller's and are written as 0), `frames.npy` = the frame
+    count of every utterance (float64).  When all rows exceed DUMP_LIMIT_BYTES, a fixed seeded sample of whole rows is
+    written; `audio_rows.npy` names the rows that `audio.npy` holds."""
+    B, ld = audio.shape
+    k = min(B, DUMP_LIMIT_BYTES // (4 * ld))
+    if k < 1:
+        raise SystemExit(f"--dump-outputs: one waveform row ({4 * ld} bytes) exceeds the {DUMP_LIMIT_BYTES}-byte limit")
+    rows = np.arange(B) if k == B else np.sort(np.random.default_rng(0).choice(B, size=k, replace=False))
+    out = np.array(audio[rows], dtype=np.float32)
+    out[np.arange(ld)[None, :] >= 600 * frames[rows, None]] = 0.0
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "audio.npy"), out)
+    np.save(os.path.join(out_dir, "frames.npy"), frames.astype(np.float64))
+    np.save(os.path.join(out_dir, "audio_rows.npy"), rows.astype(np.float64))
 
 
 def usable_cores() -> int:
@@ -321,7 +378,7 @@ def replicas_main(a):
     if max(dev_ids) >= torch.cuda.device_count():
         raise SystemExit(f"--replicas {N} but only {torch.cuda.device_count()} GPU(s) visible")
     progress("preparing synthetic weight blob")
-    blob_path = W.ensure_synthetic_blob()
+    blob_path = synthetic_blob()
     t0 = time.perf_counter()
     models = hk.HipKoko.replicas(blob_path, dev_ids)
     t_fan = time.perf_counter() - t0
@@ -353,7 +410,7 @@ def replicas_main(a):
             for _ in range(a.warmup):
                 m.infer_device(ids.data_ptr(), T, lens, styles.data_ptr(), speeds, audio.data_ptr(), audio_ld, frames.data_ptr(), seed=2)
                 m.sync()
-            if r == 0:
+            if r == 0 and a.full:
                 m.profile_enable(True)  # (replica 0's per-launch HIP events: the roofline block, as rank 0's in the torchrun form)
             bar.wait()  # start of the timed region
             for _ in range(a.steps):
@@ -382,15 +439,19 @@ def replicas_main(a):
         raise SystemExit(f"replica failed: {errs[0] if errs else 'barrier broken'}")
     for (m, ids, styles, audio, frames) in state:
         assert (frames.cpu().numpy() == F).all()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, state[0][3].cpu().numpy(), state[0][4].cpu().numpy())
     finite = all(bool(torch.isfinite(s[3][:, : 600 * F]).all().item()) for s in state)
     audio_s_per_step = N * B * F * 600 / 24000.0
     # the dominant kernel's roofline from replica 0's own launches (HIP events on its stream), as rank 0 reports it under torchrun
     m0 = models[0]
-    n_launch, conv_ms, conv_flops = m0.profile_read()
-    det = m0.profile_detail()
-    conv_bytes = float(det[:, 9].sum()) if len(det) else 0.0
-    m0.profile_enable(False)
-    rl = roofline(m0.get_conv_mode() in (1, 4, 5, 6), conv_flops, conv_ms, n_launch, a.steps, wall, B, T, F, conv_bytes, f8=m0.get_conv_mode() == 6)
+    rl = None
+    if a.full:
+        n_launch, conv_ms, conv_flops = m0.profile_read()
+        det = m0.profile_detail()
+        conv_bytes = float(det[:, 9].sum()) if len(det) else 0.0
+        m0.profile_enable(False)
+        rl = roofline(m0.get_conv_mode() in (1, 4, 5, 6), conv_flops, conv_ms, n_launch, a.steps, wall, B, T, F, conv_bytes, f8=m0.get_conv_mode() == 6)
     if rl is not None:
         rl["measured_on"] = f"replica 0 of {N} (device {dev_ids[0]}" + (f", CU partition 0 of {dev_ids.count(dev_ids[0])}" if dev_ids.count(dev_ids[0]) > 1 else "") + ")"
     out = {
@@ -407,7 +468,7 @@ def replicas_main(a):
         "utterances_per_s": N * B * a.steps / wall, "audio_s_per_step": audio_s_per_step, "finite": finite,
         "weight_broadcast_s": t_fan, "replicas_times_ms": dict(zip(("file_read", "blob_resident_everywhere", "models_built"), hk.HipKoko.replicas_times())),
         "roofline": rl,
-        "cpu_baseline": None, "cpu_baseline_note": "the CPU restatement is timed at N = 1 only (python bench.py); see BENCH_r*.json",
+        "cpu_baseline": None, "cpu_baseline_note": "the CPU restatement is timed at N = 1 only (python bench.py --full); see BENCH_r*.json",
         "serve": serve_leg(models) if a.serve else None,
     }
     print(json.dumps(out), flush=True)
@@ -422,23 +483,38 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=64, help="utterances per GPU")
     ap.add_argument("--phonemes", type=int, default=128)
-    ap.add_argument("--cpu-utts", type=int, default=12, help="utterances in the CPU baseline sample (0 = skip)")
-    ap.add_argument("--detail", default="", help="write a per-shape table of the conv launches to this file")
-    ap.add_argument("--free-run", type=int, default=1, help="also time one step with predicted durations")
-    ap.add_argument("--pcie", type=int, default=1, help="also time one step through the host-buffer boundary (N=1)")
-    ap.add_argument("--reduced", type=int, default=1,
-                    help="also time the opt-in reduced-precision mode (one f16 MFMA per product) as a secondary block (N=1)")
-    ap.add_argument("--serve", type=int, default=1, help="also run the 32-client serving leg (configs[4]) on rank 0 at N=1")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (roofline from per-launch events in the timed steps, CPU baseline, "
+                         "free-running and host-buffer steps, other precisions, batch-1 latency, serving leg); the options below "
+                         "marked (--full) tune them")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (rank / replica 0; bench.dump_outputs)")
+    ap.add_argument("--cpu-utts", type=int, default=None, help="(--full) utterances in the CPU baseline sample (0 = skip)")
+    ap.add_argument("--detail", default="", help="(--full) write a per-shape table of the conv launches to this file")
+    ap.add_argument("--free-run", type=int, default=None, help="(--full) also time one step with predicted durations")
+    ap.add_argument("--pcie", type=int, default=None, help="(--full) also time one step through the host-buffer boundary (N=1)")
+    ap.add_argument("--reduced", type=int, default=None,
+                    help="(--full) also time the opt-in reduced-precision mode (one f16 MFMA per product) as a secondary block (N=1)")
+    ap.add_argument("--serve", type=int, default=None, help="(--full) also run the 32-client serving leg (configs[4]) on rank 0 at N=1")
     ap.add_argument("--durations", default="pinned", choices=["pinned", "free"],
                     help="free = the timed steps run on the predicted (ragged) durations: a profiling mode (rocprof of the "
                          "ragged step, tools/ragged_profile.sh); the headline is the pinned workload")
     ap.add_argument("--serve-models", type=int, default=1,
                     help="models per GPU behind the serving leg's dispatcher: n > 1 = n CU-partitioned models (kx_create_replicas with the "
                          "device id given n times: each confined to 1 / n of the CUs, forwards side by side; DESIGN.md section 7)")
-    ap.add_argument("--latency-b1", type=int, default=50, help="batch-1 calls timed for the latency_b1 block (configs[1]; 0 = skip)")
+    ap.add_argument("--latency-b1", type=int, default=None, help="(--full) batch-1 calls timed for the latency_b1 block (configs[1]; 0 = skip)")
     ap.add_argument("--replicas", type=int, default=0,
                     help="single-process form: N models from kx_create_replicas, one host thread each (instead of torchrun)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.detail and not a.full:
+        ap.error("--detail needs --full")
+    for name, default in FULL_DEFAULTS.items():
+        v = getattr(a, name)
+        if v and not a.full:
+            ap.error(f"--{name.replace('_', '-')} {v} needs --full")
+        setattr(a, name, (default if v is None else v) if a.full else 0)
     if a.replicas > 0:
         return replicas_main(a)
 
@@ -471,7 +547,7 @@ def main():
 
     # ---- weights: rank 0 owns the file, everyone else gets it over RCCL/xGMI once ----------
     progress("preparing synthetic weight blob")
-    blob_path = W.ensure_synthetic_blob() if rank == 0 else ""
+    blob_path = synthetic_blob() if rank == 0 else ""
     t0 = time.perf_counter()
     blob = kd.broadcast_blob(blob_path, dev, rank, world)
     torch.cuda.synchronize()
@@ -522,38 +598,42 @@ def main():
         model.sync()
         progress(f"warmup step {i + 1}/{a.warmup} done")
     fence()
-    model.profile_enable(True)
+    if a.full:
+        model.profile_enable(True)
     t0 = time.perf_counter()
     for _ in range(a.steps):
         step()
     fence()
     wall = time.perf_counter() - t0
     progress(f"{a.steps} timed steps: {wall:.3f} s")
-    n_launch, conv_ms, conv_flops = model.profile_read()
-    stats_launches, stats_bytes = model.profile_aux()
     conv_mode = model.get_conv_mode()
-    f16x3 = conv_mode in (1, 4, 5, 6)  # all run the 16-bit matrix pipe (modes 4 / 5 = the opt-in reduced precision, labelled as such)
-    det = model.profile_detail()
-    conv_bytes = float(det[:, 9].sum()) if len(det) else 0.0
-    if a.detail and rank == 0:
-        per = len(det) // max(a.steps, 1)
-        agg = {}
-        for r in det[-per:]:
-            key = tuple(int(v) for v in r[:6])
-            t = agg.setdefault(key, [0, 0.0, 0.0, 0.0])
-            t[0] += 1; t[1] += r[7]; t[2] += r[8]; t[3] += r[9]
-        with open(a.detail, "w") as f:
-            f.write("rows Cin taps dil stride store launches GFLOP ms TFLOP/s alg_GB alg_GB/s\n")
-            for key, (n, fl, ms, by) in sorted(agg.items(), key=lambda kv: -kv[1][2]):
-                f.write(" ".join(f"{v:5d}" for v in key) + f" {n:4d} {fl / 1e9:10.1f} {ms:9.3f} {fl / ms / 1e9:8.1f}"
-                        f" {by / 1e9:8.2f} {by / ms / 1e6:8.0f}\n")
-    model.profile_enable(False)
+    if a.full:
+        n_launch, conv_ms, conv_flops = model.profile_read()
+        stats_launches, stats_bytes = model.profile_aux()
+        f16x3 = conv_mode in (1, 4, 5, 6)  # all run the 16-bit matrix pipe (modes 4 / 5 = the opt-in reduced precision, labelled as such)
+        det = model.profile_detail()
+        conv_bytes = float(det[:, 9].sum()) if len(det) else 0.0
+        if a.detail and rank == 0:
+            per = len(det) // max(a.steps, 1)
+            agg = {}
+            for r in det[-per:]:
+                key = tuple(int(v) for v in r[:6])
+                t = agg.setdefault(key, [0, 0.0, 0.0, 0.0])
+                t[0] += 1; t[1] += r[7]; t[2] += r[8]; t[3] += r[9]
+            with open(a.detail, "w") as f:
+                f.write("rows Cin taps dil stride store launches GFLOP ms TFLOP/s alg_GB alg_GB/s\n")
+                for key, (n, fl, ms, by) in sorted(agg.items(), key=lambda kv: -kv[1][2]):
+                    f.write(" ".join(f"{v:5d}" for v in key) + f" {n:4d} {fl / 1e9:10.1f} {ms:9.3f} {fl / ms / 1e9:8.1f}"
+                            f" {by / 1e9:8.2f} {by / ms / 1e6:8.0f}\n")
+        model.profile_enable(False)
     wall_t = torch.tensor([wall], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
     if world > 1:
         dist.all_reduce(wall_t, op=dist.ReduceOp.MAX)
     wall = float(wall_t.item())
 
     fr = frames.cpu().numpy()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, audio.cpu().numpy(), fr)
     if free_main:
         finite = all(bool(torch.isfinite(audio[b, : 600 * int(fr[b])]).all().item()) for b in range(B))
         audio_s_per_step = world * float(fr.sum()) * 600 / 24000.0  # (rank 0's frames stand for every rank's)
@@ -751,10 +831,12 @@ def main():
             "finite": finite,
             "weight_broadcast_s": t_bcast,
             "model_tflops": flops_per_utt * world * B * a.steps / wall / 1e12,
-            "roofline": roofline(f16x3, conv_flops, conv_ms, n_launch, a.steps, wall, B, T, F, conv_bytes, f8=conv_mode == 6),
+            "roofline": roofline(f16x3, conv_flops, conv_ms, n_launch, a.steps, wall, B, T, F, conv_bytes, f8=conv_mode == 6)
+                        if a.full else None,
             # unfused InstanceNorm statistics passes of the timed steps: each reads its tensor once (the known byte
             # count tools/summarize_pmc.py checks FETCH_SIZE against)
-            "in_stats": {"launches_per_step": stats_launches / max(a.steps, 1), "bytes_per_step": stats_bytes / max(a.steps, 1)},
+            "in_stats": {"launches_per_step": stats_launches / max(a.steps, 1), "bytes_per_step": stats_bytes / max(a.steps, 1)}
+                        if a.full else None,
             "free_running": free,
             "latency_b1": lat_b1,
             "pcie_inclusive": pcie,

@@ -11,7 +11,7 @@ def main(prof_dir, bench_json, out, cmd=""):
     rows = list(csv.DictReader(open(stats)))
     tot = sum(float(r["TotalDurationNs"]) for r in rows)
     lines = [f"# rocprofv3 --kernel-trace --stats summary ({os.path.basename(prof_dir)})",
-             "# command: rocprofv3 --kernel-trace --stats --output-format csv -- " + (cmd or "python3 bench.py --steps 3 --warmup 1 "
+             "# command: rocprofv3 --kernel-trace --stats --output-format csv -- " + (cmd or "python3 bench.py --full --steps 3 --warmup 1 "
                                                                                       "--cpu-utts 0 --free-run 0 --pcie 0 --serve 0 --reduced 0"),
              f"# total GPU kernel time {tot / 1e6:.2f} ms", "",
              f"{'kernel':88s} {'calls':>6s} {'total_ms':>10s} {'avg_us':>10s} {'pct':>7s}"]
