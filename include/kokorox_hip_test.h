@@ -13,7 +13,9 @@ extern "C" {
  * 1 leaky(slope), 2 snake(alpha[Cin]); norm = optional [3,B,Cin] (mean, scale, shift);
  * mode as in kx_set_conv_mode, plus 2 = f16x3 on the LDS-DMA kernel forms only (conv_f16x3.hip: what the direct-A
  * kernels are compared with bit for bit) and 3 = f16x3 through the direct-A kernel whatever the grid; + 0x100 (modes 1 and 3,
- * here and in the other conv hooks) = the input staged through a pre-split image (conv_f16x3_pre.hip) whatever the row count. */
+ * here and in the other conv hooks) = the input staged through a pre-split image (conv_f16x3_pre.hip) whatever the row count;
+ * + 0x200 = f16f8 (the layer carries the 8-bit cross image of its weights); + 0x400 = the direct-A conv's 256-column tile with
+ * the 4 x 1 wave layout too (not the 2 x 2 one); + 0x800 = no 16x16x32 form. */
 int kx_test_conv1d(int device_id, const float* x, int B, int Cin, int L, const float* w,
                    const float* bias, int Cout, int k, int stride, int pad, int dil,
                    int transposed, int act, float slope, const float* alpha,
@@ -45,6 +47,13 @@ int kx_test_conv1d_full(int device_id, const float* x, int B, int Cin, int L, co
                         const float* w, const float* bias, int Cout, int k, int pad, int dil, int act, float slope,
                         const float* alpha, const float* norm, const float* resid, int accumulate, float out_mul,
                         float out_div, float* y, float* stats_out, int mode, char* err, size_t err_len);
+
+/* The launch plan of one conv (kokorox_amd/csrc/conv_plan.hip: kernel form, tile, statistics slots, flat tile list, pre-split
+ * input), computed on the host without a device.  in[25] = the fields of kx::ConvLaunch in declaration order (mode, prec1, f8, BM,
+ * rows, n_chunks16, K, dil, stride, pad, act, in_up2, store, accum, epi, norm, stats, image, merge_T, x_bs, x_ld, B, cols, cus,
+ * force), out[17] = those of kx::ConvPlan (form, bm, act, kt, wm, wn, vt, pf, p1, bf, bn, cols, merged, pre, stat_cols,
+ * stat_tiles, flat_bn). */
+int kx_test_conv_plan(const int64_t* in, int n_in, int64_t* out, int n_out, char* err, size_t err_len);
 
 /* Stand-alone bidirectional LSTM (hidden 256): x [B,L,n_in] -> y [B,L,512]. */
 int kx_test_lstm(int device_id, const float* x, int B, int L, int n_in, const float* w_ih,

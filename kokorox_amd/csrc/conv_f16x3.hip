@@ -369,11 +369,6 @@ void conv1d_f16x3_kernel(const ConvArgs a) {
     }
 }
 
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 int conv16_cu_count() {  // of the CURRENT device (cached per device: models on several GPUs launch from several threads)
     if (const int part = cu_count_override()) return part;  // (a CU-partitioned model is launching: its share)
     static std::atomic<int> n[KX_MAX_DEVICES];
@@ -397,9 +392,7 @@ static void launch_inst16_pf(const ConvArgs& a, int B, int max_cols, hipStream_t
     const int XW = (BN - 1) * a.stride + (a.K - 1) * a.dil + 1;
     const int XWp = PF ? ((VT > 1) ? 128 : BN + 128) : ((XW + 3) & ~3);  // (as in the kernel)
     KX_REQUIRE(!PF || (a.stride == 1 && XW <= XWp), "conv1d f16x3: the prefetching build needs stride 1 and a window <= BN + 128");
-    static const int lds_pad = env_int("KX_LDS_PAD", 0);  // diagnostic: extra LDS to force one workgroup per CU
-    size_t lds = 16 * ((size_t)2 * TK * 4 * BM + (size_t)VT * 4 * XWp);
-    if (lds + lds_pad <= 160 * 1024) lds += lds_pad;
+    const size_t lds = 16 * ((size_t)2 * TK * 4 * BM + (size_t)VT * 4 * XWp);
     KX_REQUIRE(lds <= 160 * 1024, "conv1d f16x3: LDS tile too large for this k/stride");
     KX_REQUIRE(VT == 1 || (a.K == 1 && a.stride == 1 && XW <= 128), "conv1d f16x3: virtual taps need a k=1 GEMM");
     lds_limit.ensure(reinterpret_cast<const void*>(kern), lds);
@@ -412,146 +405,107 @@ static void launch_inst16_pf(const ConvArgs& a, int B, int max_cols, hipStream_t
     KX_HIP(hipGetLastError());
 }
 
-
-template <int BM, int BN, int WM, int WN, int ACT, int TK>
-static void launch_inst16_act(const ConvArgs& a, int B, int max_cols, hipStream_t s) {
-    static const int pf_env = env_int("KX_PF", 1);
-    const int XW = (BN - 1) * a.stride + (a.K - 1) * a.dil + 1;
-    if (pf_env && a.stride == 1 && XW <= BN + 128)
-        launch_inst16_pf<BM, BN, WM, WN, ACT, TK, true>(a, B, max_cols, s);
+// (weight pieces of 1 and 2 taps were measured too: no faster than 3 anywhere, so only TK = 3 is built)
+template <int BM, int BN, int WM, int WN, int ACT>
+static void launch_inst16_act(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s) {
+    if (p.pf)
+        launch_inst16_pf<BM, BN, WM, WN, ACT, 3, true>(a, B, p.cols, s);
     else
-        launch_inst16_pf<BM, BN, WM, WN, ACT, TK, false>(a, B, max_cols, s);
-}
-
-template <int BM, int BN, int WM, int WN, int TK>
-static void launch_inst16_tk(const ConvArgs& a, int B, int max_cols, hipStream_t s) {
-    if (a.act == ACT_SNAKE)
-        launch_inst16_act<BM, BN, WM, WN, ACT_SNAKE, TK>(a, B, max_cols, s);
-    else if (a.act == ACT_LEAKY)
-        launch_inst16_act<BM, BN, WM, WN, ACT_LEAKY, TK>(a, B, max_cols, s);
-    else
-        launch_inst16_act<BM, BN, WM, WN, ACT_NONE, TK>(a, B, max_cols, s);
+        launch_inst16_pf<BM, BN, WM, WN, ACT, 3, false>(a, B, p.cols, s);
 }
 
 template <int BM, int BN, int WM, int WN>
-static void launch_inst16(const ConvArgs& a, int B, int max_cols, hipStream_t s) {
-    // (weight pieces of 1 and 2 taps were measured too: no faster than 3 anywhere, so only TK = 3 is built)
-#ifndef KX_TK
-#define KX_TK 3
-#endif
-    launch_inst16_tk<BM, BN, WM, WN, KX_TK>(a, B, max_cols, s);
+static void launch_inst16(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s) {
+    if (p.act == ACT_SNAKE)
+        launch_inst16_act<BM, BN, WM, WN, ACT_SNAKE>(p, a, B, s);
+    else if (p.act == ACT_LEAKY)
+        launch_inst16_act<BM, BN, WM, WN, ACT_LEAKY>(p, a, B, s);
+    else
+        launch_inst16_act<BM, BN, WM, WN, ACT_NONE>(p, a, B, s);
 }
 
-// Tile of a launch: BN columns per workgroup, WN = waves side by side along the columns.
-//   128-row weights: 256 x (2 x 2 waves) by default; 128 x (2 x 2) for short sequences; and for small grids (batch 1:
-//   256-column tiles would not even give every CU one workgroup) 128 x (4 x 1): half the tile, but each wave still
-//   spans 128 columns, so the fused InstanceNorm partial sums cover the same column groups in the same order as with
-//   the 256-wide tile and results stay bit-identical across batch sizes.
-// stats: the launch fuses InstanceNorm partial sums into its epilogue.  Their slots must then be 128 columns wide whatever the
-// launch geometry (an utterance's sums are added in the same order alone and beside a longer one: batch invariance), so the
-// 2 x 2-wave tile of short sequences (64-column slots) is not taken.
-void conv16_pick_tile(int BM, int max_cols, int B, int Cout, int K, int dil, int stride, int* bn, int* wn, int ws_force, bool stats,
-                      int act, int n_chunks16, int pmode) {
-    static const int force = env_int("KX_BN", 0);
-    if (ws_force != 1 && act >= 0 && conv16_da_s16_shape(BM, K, dil, stride, act, n_chunks16, false, pmode)) {
-        // the S16 form of the direct-A conv: 192 columns on chip-filling grids, 128 on small ones; three / two 64-column slots
-        const bool small = (long)((max_cols + 255) / 256) * ((Cout + 127) / 128) * B < 256 && ws_force != 2;
-        *bn = small ? 128 : 192;
-        *wn = small ? 2 : 3;
+// The LDS-DMA forms (FORM_LDS).  (An 8-wave x 128-register form of the 128x256 tile was tried: it spills and is 6 % slower; a
+// 128x192 tile for 3 workgroups per CU: the 168-register cap spills in the main loop, 1.7x slower.)
+static void launch_lds(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s) {
+    if (p.vt > 1) {
+        // k = 1 GEMMs: vt 16-channel chunks staged together and walked as vt taps of one super-chunk (the one kernel whose
+        // epilogue carries gelu_new).  Two chunks: 48 KiB of LDS instead of 73.7, so three workgroups fit a CU and the 1040 - 1170
+        // workgroups of the ALBERT GEMMs at batch 64 run in two rounds of 768 instead of three rounds of 512.
+        KX_REQUIRE(p.bm == 128 && p.bn == 128 && p.pf && p.act != ACT_SNAKE && (p.vt == 2 || p.vt == 3), "conv1d f16x3: no such virtual-tap form");
+        if (p.vt == 3) {
+            if (p.act == ACT_LEAKY)
+                launch_inst16_pf<128, 128, 2, 2, ACT_LEAKY, 3, true, 3>(a, B, p.cols, s);
+            else
+                launch_inst16_pf<128, 128, 2, 2, ACT_NONE, 3, true, 3>(a, B, p.cols, s);
+        } else {
+            if (p.act == ACT_LEAKY)
+                launch_inst16_pf<128, 128, 2, 2, ACT_LEAKY, 2, true, 2>(a, B, p.cols, s);
+            else
+                launch_inst16_pf<128, 128, 2, 2, ACT_NONE, 2, true, 2>(a, B, p.cols, s);
+        }
         return;
     }
-    if (ws_force == 2 && conv16_da_eligible(BM, K, dil, stride, 0)) {  // test hook: the direct-A kernel whatever the grid
-        *bn = 256; *wn = 2;
+    const int bm = p.bm, bn = p.bn, wm = p.wm, wn = p.wn;
+    if (bm == 128 && bn == 128 && wm == 4 && wn == 1)
+        launch_inst16<128, 128, 4, 1>(p, a, B, s);
+    else if (bm == 128 && bn == 128 && wm == 2 && wn == 2)
+        launch_inst16<128, 128, 2, 2>(p, a, B, s);
+    else if (bm == 128 && bn == 256 && wm == 2 && wn == 2)
+        launch_inst16<128, 256, 2, 2>(p, a, B, s);
+    else if (bm == 64 && bn == 256 && wm == 1 && wn == 4)
+        launch_inst16<64, 256, 1, 4>(p, a, B, s);
+    else if (bm == 32 && bn == 256 && wm == 1 && wn == 4)
+        launch_inst16<32, 256, 1, 4>(p, a, B, s);
+    else
+        throw Error(1, "conv1d f16x3: no such LDS-DMA form");
+}
+
+void launch_conv(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s) {
+    if (p.form == FORM_F32) {
+        launch_conv1d(a, p.bm, B, p.cols, s);
         return;
     }
-    if (BM != 128) {
-        *bn = 256; *wn = 4;
-    } else if ((force == 128 || max_cols <= 160) && !stats) {
-        *bn = 128; *wn = 2;
-    } else if ((long)((max_cols + 255) / 256) * ((Cout + 127) / 128) * B < 256 && force != 256) {
-        *bn = 128; *wn = 1;
-    } else {
-        *bn = 256; *wn = 2;
-    }
-}
-
-// The tile width of the launch below when it goes to a kernel that can take a flat tile list (the direct-A conv family), else
-// 0.  Must mirror launch_conv1d_f16x3's dispatch exactly (launch_da_inst checks the width the host assumed).
-int conv16_flat_bn(const ConvArgs& a, int BM, int B, int max_cols) {
-    static const int on = env_int("KX_FLAT", 1);
-    if (!on || BM != 128 || B < 2 || max_cols <= 0 || a.merge_T > 0 || a.ws_force == 1 || a.stamps) return 0;
-    if (a.K == 1 && a.stride == 1 && !a.stat_part && !a.in_up2 && a.n_chunks16 >= 3 && a.act != ACT_SNAKE) return 0;  // k = 1 GEMM forms
-    int bn, wn;
-    conv16_pick_tile(BM, max_cols, B, a.Cout, a.K, a.dil, a.stride, &bn, &wn, a.ws_force, a.stat_part != nullptr, a.act, a.n_chunks16,
-                     conv16_pmode(a));
-    if (conv16_da_s16_shape(BM, a.K, a.dil, a.stride, a.act, a.n_chunks16, a.merge_T > 0, conv16_pmode(a))) return bn;  // 192 / 128
-    if (bn == 128 && wn == 1) return conv16_use_da(BM, a.K, a.dil, a.stride, a.merge_T > 0) ? 128 : 0;
-    if (bn == 128) return 0;
-    return conv16_use_da(BM, a.K, a.dil, a.stride, a.merge_T > 0) ? 256 : 0;
-}
-
-void launch_conv1d_f16x3(const ConvArgs& a, int BM, int B, int max_cols, hipStream_t s) {
-#ifdef KX_ONLY_MAIN  // (compile-time probe builds: just the dominant instantiation, ~10 s instead of ~3 min)
-    launch_inst16_pf<128, 256, 2, 2, ACT_SNAKE, 3, true>(a, B, max_cols, s);
-    return;
-#else
     KX_REQUIRE(a.n_chunks16 == (a.Cin + CK16 - 1) / CK16 && a.w16 != nullptr, "conv1d f16x3: weights not packed");
-    KX_REQUIRE(BM == 128 || a.epi != EPI_GELU_NEW, "conv1d f16x3: gelu epilogue needs the 128-row tile");
-    if (max_cols <= 0) return;
-    if (BM == 128) {
-        // (an 8-wave x 128-register form of the 128x256 tile was tried: it spills and is 6 % slower)
-        // (also tried: a 128x192 tile for 3 workgroups per CU: the 168-register cap spills in the main loop, 1.7x slower)
-        // k = 1 GEMMs (ALBERT, projections, LSTM input products) take the virtual-tap form; it is also the one
-        // kernel whose epilogue carries gelu_new
-        if (a.K == 1 && a.stride == 1 && !a.stat_part && !a.in_up2 && a.n_chunks16 >= 3 && a.act != ACT_SNAKE) {
-            // (test hook mode 2 keeps the virtual-tap form below, so that the two can be compared bit for bit)
-            if (a.ws_force != 1 && conv16_use_dag(a, BM)) {
-                launch_conv1d_f16x3_dag(a, B, max_cols, s);
+    KX_REQUIRE(a.epi != EPI_GELU_NEW || p.vt > 1 || p.form == FORM_DAG || p.form == FORM_DAGN,
+               "conv1d f16x3: gelu epilogue exists only for k=1 GEMMs with >= 48 input channels");
+    KX_REQUIRE(p.merged == (a.merge_T > 0), "conv1d f16x3: merged columns do not match the plan");
+    if (p.cols <= 0) return;
+    switch (p.form) {
+        case FORM_LDS: launch_lds(p, a, B, s); return;
+        case FORM_DAG:
+        case FORM_DAGN: launch_conv1d_f16x3_dag(p, a, B, s); return;
+        case FORM_DAPN: launch_conv1d_f16x3_dapn(a, B, p.cols, s); return;
+        case FORM_DA_PRE: launch_conv16_da_pre(p, a, B, s); return;
+        case FORM_DA_S16: launch_conv16_da_s16(p, a, B, s); return;
+        case FORM_DA_F8: launch_conv16_da_f8(p, a, B, s); return;
+        case FORM_DA:
+            if (p.p1) {
+                launch_conv16_da_p1(p, a, B, s);
                 return;
             }
-            // Two 16-channel chunks per super-chunk instead of three: 48 KiB of LDS instead of 73.7, so three workgroups
-            // fit a CU (the registers always allowed three) and the 1040 - 1170 workgroups of the ALBERT GEMMs at batch 64
-            // run in two rounds of 768 instead of three rounds of 512.  (KX_GEMM_VT=3: the former form.)
-            // (small grids -- batch 1 -- keep three: fewer barriers per unit of work, and every workgroup is resident anyway)
-            static const int vt_env = env_int("KX_GEMM_VT", 0);
-            const long wgs = (long)((max_cols + 127) / 128) * ((a.Cout + 127) / 128);
-            const int vt = vt_env ? vt_env : (wgs > 2L * conv16_cu_count() ? 2 : 3);
-            if (vt == 3) {
-                if (a.act == ACT_LEAKY)
-                    launch_inst16_pf<128, 128, 2, 2, ACT_LEAKY, 3, true, 3>(a, B, max_cols, s);
-                else
-                    launch_inst16_pf<128, 128, 2, 2, ACT_NONE, 3, true, 3>(a, B, max_cols, s);
-            } else {
-                if (a.act == ACT_LEAKY)
-                    launch_inst16_pf<128, 128, 2, 2, ACT_LEAKY, 2, true, 2>(a, B, max_cols, s);
-                else
-                    launch_inst16_pf<128, 128, 2, 2, ACT_NONE, 2, true, 2>(a, B, max_cols, s);
+            [[fallthrough]];
+        case FORM_DA_W2: {
+            static const int dephase = getenv("KX_DEPHASE") ? atoi(getenv("KX_DEPHASE")) : 0;  // permille of a tile's estimated time
+            static const int dephase_mode = getenv("KX_DEPHASE_MODE") ? atoi(getenv("KX_DEPHASE_MODE")) : 1;
+            ConvArgs d;
+            const ConvArgs* ap = &a;
+            if (dephase > 0 && p.bn == 256) {  // (diagnostic, profiles/r03_lanes_dephase.txt: no effect)
+                d = a;
+                const long grid_n = (long)((p.cols + 255) / 256) * ((a.Cout + 127) / 128) * B;
+                // a tile: n_chunks x K x 8 column tiles x 3 MFMAs of 32 cycles, two waves per SIMD, ~80 % pipe use; + the epilogue
+                const double tile_cycles = (double)a.n_chunks16 * a.K * 8 * 96 * 2.5 + 50000.0;
+                d.dephase_cycles = grid_n >= 1024 ? (int)(tile_cycles * dephase / 1000.0) : 0;
+                d.dephase_mode = dephase_mode;
+                ap = &d;
             }
+            if (p.form == FORM_DA_W2)
+                launch_conv16_da_w2(p, *ap, B, s);
+            else
+                launch_conv16_da(p, *ap, B, s);
             return;
         }
-        KX_REQUIRE(a.epi != EPI_GELU_NEW, "conv1d f16x3: gelu epilogue exists only for k=1 GEMMs with >= 48 input channels");
-        int bn, wn;
-        conv16_pick_tile(BM, max_cols, B, a.Cout, a.K, a.dil, a.stride, &bn, &wn, a.ws_force, a.stat_part != nullptr, a.act, a.n_chunks16,
-                         conv16_pmode(a));
-        if (a.ws_force != 1 && conv16_da_s16_shape(BM, a.K, a.dil, a.stride, a.act, a.n_chunks16, a.merge_T > 0, conv16_pmode(a)))
-            launch_conv1d_f16x3_da(a, B, max_cols, s, bn);  // (bn = 192 or 128: the S16 form's tiles)
-        else if (bn == 128 && wn == 1 && conv16_use_da(BM, a.K, a.dil, a.stride, a.merge_T > 0) && a.ws_force != 1)
-            launch_conv1d_f16x3_da(a, B, max_cols, s, 128);  // (test hook mode 2 keeps the LDS-DMA form for comparison)
-        else if (bn == 128 && wn == 1)
-            launch_inst16<128, 128, 4, 1>(a, B, max_cols, s);
-        else if (bn == 128)
-            launch_inst16<128, 128, 2, 2>(a, B, max_cols, s);
-        else if (conv16_use_da(BM, a.K, a.dil, a.stride, a.merge_T > 0) && a.ws_force != 1)
-            launch_conv1d_f16x3_da(a, B, max_cols, s);
-        else
-            launch_inst16<128, 256, 2, 2>(a, B, max_cols, s);
-    } else if (BM == 64)
-        launch_inst16<64, 256, 1, 4>(a, B, max_cols, s);
-    else if (BM == 32)
-        launch_inst16<32, 256, 1, 4>(a, B, max_cols, s);
-    else
-        throw Error(1, "conv1d f16x3: unsupported BM");
-#endif
+    }
+    throw Error(1, "conv1d: unknown kernel form");
 }
 
 // ---- weight repacking into split-f16 fragment images -------------------------------------------------

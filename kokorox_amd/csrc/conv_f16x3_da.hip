@@ -24,7 +24,7 @@
 //     below with a_hi b_hi on v_mfma_f32_16x16x32_f16 and the two cross terms of 16 channels x 4 taps on ONE
 //     v_mfma_scale_f32_16x16x128_f8f6f4 -- two MFMA-equivalents per product instead of three, ~2^-17 per product instead of 2^-22
 //     (see "S16 form, f16f8"); rings and input prefetch are buffer loads, the snake takes sin^2 from v_cos_f32;
-//   * S16 (f16x3 mode: snake convs with 11 taps and the un-dilated 7-tap ones; KX_DA_S16=0 switches it off): v_mfma_f32_16x16x32_f16
+//   * S16 (f16x3 mode: snake convs with 11 taps and the un-dilated 7-tap ones; the test override FORCE_NO_S16 keeps them off it): v_mfma_f32_16x16x32_f16
 //     with K = 16 channels x two
 //     taps, on a 128 x 192 tile (128 x 128 on small grids) with 64-column statistics slots; the one form whose results are not
 //     bit-identical to the others (one instruction sums 32 products) -- its two tile widths are identical to each other;
@@ -32,7 +32,7 @@
 //     B fragment read feeds six MFMAs instead of three and the MFMAs of a tile alternate between two accumulators; two ring
 //     slots of 16 registers, every vector load unconditional and every wait a compile-time constant (see "W2 form" below;
 //     profiles/r03_w2_form.txt).  Bit-identical to the 4 x 1 forms below, which remain for the 128-column tile (small grids),
-//     the reduced-precision mode and KX_DA_W2=0;
+//     the reduced-precision mode and the test override FORCE_DA_4X1;
 //   * compile-time tap count (KT = 3, 7, 11: the resblock convs, 85 % of the conv time): a chunk's KT steps are unrolled and
 //     the NEXT chunk's input transform (AdaIN affine + snake + f16 split, ~600 vector instructions per wave and chunk) is
 //     dealt out in 24 pieces between the MFMAs of the chunk's column tiles, where the matrix pipe hides it; done in one
@@ -64,16 +64,6 @@ __device__ __forceinline__ void static_for(F&& f) {
         static_for<I + 1, N>(f);
     }
 }
-
-#if !defined(KX_DA_P1) && !defined(KX_DA_W2) && !defined(KX_DA_S16) && !defined(KX_DA_PRE)
-bool conv16_da_eligible(int BM, int K, int dil, int stride, int merged) {
-    return BM == 128 && stride == 1 && !merged && (K - 1) * dil + 256 <= 384;
-}
-bool conv16_use_da(int BM, int K, int dil, int stride, int merged) {
-    static const int on = getenv("KX_DA") ? atoi(getenv("KX_DA")) : 1;
-    return on && conv16_da_eligible(BM, K, dil, stride, merged);
-}
-#endif
 
 // P1: the opt-in reduced-precision form (KOKOROX_CONV=f16, BASELINE configs[2] "bf16" / the reference's model_fp16
 // variants, hf_cache.rs:135-144): ONE v_mfma_f32_32x32x16_f16 per product on the high halves only (weights and activations
@@ -1497,39 +1487,17 @@ __global__ __launch_bounds__(256, (NTT == 8 || S16) ? 2 : 3) void conv1d_f16x3_d
 #endif
 }
 
-// The launchers below exist twice: this translation unit instantiates the f16x3 kernels (P1 = false); conv_f16x3_da_p1.hip
-// defines KX_DA_P1 and includes this file for the reduced-precision ones, so that the two sets compile side by side.
-#ifdef KX_DA_P1
-constexpr bool DA_P1 = true;
-#else
-constexpr bool DA_P1 = false;
-#endif
-
-#ifdef KX_DA_W2
-constexpr bool DA_W2 = true;
-#else
-constexpr bool DA_W2 = false;
-#endif
-
-#ifdef KX_DA_S16
-constexpr bool DA_S16 = true;
-#else
-constexpr bool DA_S16 = false;
-#endif
-
-#ifdef KX_DA_F8
-constexpr bool DA_F8 = true;
-#else
-constexpr bool DA_F8 = false;
-#endif
-
-template <int ACT, int KT, int NTT, bool W2X = DA_W2, bool PREX = false, bool BFX = false>
+// Launchers.  Every direct-A unit includes this file for the kernel; each instantiates only its own forms, through its one entry
+// point (launch_conv16_da* in kx_common.h), which carries out the plan of conv_plan.hip: this file's for the f16x3 forms of the
+// 4 x 1 layout, conv_f16x3_da_{p1,w2,s16,f8,pre}.hip theirs.
+template <int ACT, int KT, int NTT, bool P1 = false, bool W2 = false, bool S16 = false, bool PRE = false, bool BF = false, bool F8 = false>
 static void launch_da_inst(const ConvArgs& a, int B, int max_cols, hipStream_t s) {
-    auto kern = conv1d_f16x3_da_kernel<ACT, KT, NTT, DA_P1, W2X, DA_S16, PREX, BFX, DA_F8>;
+    auto kern = conv1d_f16x3_da_kernel<ACT, KT, NTT, P1, W2, S16, PRE, BF, F8>;
     constexpr int BN = 32 * NTT;
     // two input buffers (48 / 32 KiB), and never less than the statistics scratch of the epilogue (4 waves x 8.25 KiB)
     constexpr size_t lds_x = 16 * (size_t)2 * 4 * (BN + 128), lds_scr = 4 * 32 * 33 * sizeof(float2);
     constexpr size_t lds = lds_x > lds_scr ? lds_x : lds_scr;
+    KX_REQUIRE(a.stride == 1 && a.merge_T == 0 && (a.K - 1) * a.dil + 256 <= 384, "conv1d f16x3 da: launch not eligible");
     dim3 grid((max_cols + BN - 1) / BN, (a.Cout + 127) / 128, B);
     KX_REQUIRE(grid.x > 0 && grid.y > 0 && grid.y < 65536 && B > 0 && B < 65536, "conv1d f16x3 da: bad grid");
     if (a.tile_prefix) {  // flat tile list: the host counted the live column tiles for THIS tile width (a.flat_tiles_host)
@@ -1542,200 +1510,39 @@ static void launch_da_inst(const ConvArgs& a, int B, int max_cols, hipStream_t s
     KX_HIP(hipGetLastError());
 }
 
-#ifdef KX_DA_PRE
-// The PRE forms (conv_f16x3_da_pre.hip defines KX_DA_PRE and includes this file): the input is a pre-split image (a.x16).  Which
-// launches get one is decided from the layer's shape alone (conv16_pre_shape, conv_f16x3_pre.hip), never from the batch.
-void launch_conv1d_f16x3_da_pre(const ConvArgs& a, int B, int max_cols, hipStream_t s, int bn) {
-    KX_REQUIRE(a.x16 != nullptr && a.x16_ld > 0 && !a.in_up2 && !a.prec1 && a.stride == 1 && a.merge_T == 0,
-               "conv1d f16x3 da pre: launch not eligible");
-    KX_REQUIRE(bn == 256 || bn == 128, "conv1d f16x3 da pre: tile of 256 or 128 columns");
-    // the chunk term of the image offsets is a 32-bit scalar: n_chunks x four planes x x16_ld x 16 B per utterance
-    KX_REQUIRE((long)a.n_chunks16 * 64 * a.x16_ld < (1L << 31), "conv1d f16x3 da pre: image of one utterance beyond 2 GiB");
-    // small grids (the 128-column tile was chosen): the narrow form without staging, 32 rows x 128 columns per workgroup
-    if (bn == 128 && conv16_dapn_eligible(a)) {
-        launch_conv1d_f16x3_dapn(a, B, max_cols, s);
-        return;
-    }
-    const bool w64 = a.K == 3 && (a.K - 1) * a.dil <= 64;  // the unrolled 3-tap forms (W2 on the 256-column tile); else run-time taps
-    if (bn == 256) {
-        if (w64) launch_da_inst<ACT_NONE, 3, 8, true, true>(a, B, max_cols, s);
-        else launch_da_inst<ACT_NONE, 0, 8, false, true>(a, B, max_cols, s);
-    } else {
-        if (w64) launch_da_inst<ACT_NONE, 3, 4, false, true>(a, B, max_cols, s);
-        else launch_da_inst<ACT_NONE, 0, 4, false, true>(a, B, max_cols, s);
-    }
-}
-#elif defined(KX_DA_F8)
-// The f16f8 forms of the S16 loop (conv_f16x3_da_f8.hip defines KX_DA_S16 and KX_DA_F8 and includes this file): the S16 shapes
-// whose tap count is 3 mod 4 (11, 7 and 3: all of them), when the layer carries an 8-bit cross image (ConvArgs::w8x, CONV_F16F8).
-// (the 3-tap snake convs are bound by their transform, not by the matrix pipe; on this form they still gain 6 % -- 12.8 -> 12.0 ms
-// over the six shapes -- from the hardware cosine, the shorter MFMA stream and the 16 x 16 shapes' clock; KX_F8_K3=0: the 2 x 2 f16x3 form)
-static bool f8_k3() {
-    static const int on = getenv("KX_F8_K3") ? atoi(getenv("KX_F8_K3")) : 1;
-    return on != 0;
-}
-bool conv16_da_f8_shape(int K, int dil) { return (K == 11 || K == 7 || (K == 3 && f8_k3())) && (K - 1) * dil <= 64; }
-void launch_conv1d_f16x3_da_f8(const ConvArgs& a, int B, int max_cols, hipStream_t s, int bn) {
-    KX_REQUIRE(a.w8x != nullptr && conv16_da_f8_shape(a.K, a.dil) && a.act == ACT_SNAKE && a.stride == 1 && a.merge_T == 0 && !a.prec1 &&
-                   a.n_chunks16 >= 2 && (a.n_chunks16 & 1) == 0,
-               "conv1d f16x3 da f8: launch not eligible");
-    KX_REQUIRE(bn == 192 || bn == 128, "conv1d f16x3 da f8: tile of 192 or 128 columns");
-    KX_REQUIRE((long)a.Cin * a.x_ld * 4 < (1L << 32), "conv1d f16x3 da f8: input tensor of one utterance beyond 4 GiB");
-    if (a.K == 11) {
-        if (bn == 192) launch_da_inst<ACT_SNAKE, 11, 6>(a, B, max_cols, s);
-        else launch_da_inst<ACT_SNAKE, 11, 4>(a, B, max_cols, s);
-    } else if (a.K == 7) {
-        if (bn == 192) launch_da_inst<ACT_SNAKE, 7, 6>(a, B, max_cols, s);
-        else launch_da_inst<ACT_SNAKE, 7, 4>(a, B, max_cols, s);
-    } else {
-        if (bn == 192) launch_da_inst<ACT_SNAKE, 3, 6>(a, B, max_cols, s);
-        else launch_da_inst<ACT_SNAKE, 3, 4>(a, B, max_cols, s);
-    }
-}
-#elif defined(KX_DA_S16)
-// The S16 forms (conv_f16x3_da_s16.hip defines KX_DA_S16 and includes this file).
-// Shapes the S16 form takes (and conv16_pick_tile gives 64-column statistics slots): snake resblock convs with 11 taps and an even
-// number of 16-channel chunks, and (round 4) the un-dilated 7-tap ones.  KX_DA_S16=0 switches the form off, 2 keeps it to 11 taps.
-bool conv16_da_s16_shape(int BM, int K, int dil, int stride, int act, int n_chunks16, bool merged, int pmode) {
-    static const int on = getenv("KX_DA_S16") ? atoi(getenv("KX_DA_S16")) : 1;
-    static const int da = getenv("KX_DA") ? atoi(getenv("KX_DA")) : 1;
-    static const int st = getenv("KX_DA_STATIC") ? atoi(getenv("KX_DA_STATIC")) : 1;
-    // 11 taps: always.  7 taps: the un-dilated launches only (measured: the big 7-tap launches gain 3 % on this form, the
-    // dilated ones lose 3 %: profiles/r03_s16_form.txt; KX_DA_S16=2 keeps the 7-tap convs off it).  The choice depends on the
-    // layer's shape alone, never on the batch, so an utterance's bits do not depend on what it is batched with.
-    // pmode: 0 = f16x3, 1 = a reduced-precision launch (never this form), 2 = f16f8 (the layer carries an 8-bit cross image: every
-    // 7-tap conv takes the form -- with two MFMA-equivalents per product the dilated ones gain 18 % on it instead of losing 3 %)
-    const bool taps = K == 11 || (K == 7 && dil == 1 && on == 1) || (K == 7 && pmode == 2) || (K == 3 && pmode == 2 && conv16_da_f8_shape(3, dil));
-    return on && da && st && BM == 128 && stride == 1 && !merged && pmode != 1 && act == ACT_SNAKE && taps && (K - 1) * dil <= 64 &&
-           n_chunks16 >= 2 && (n_chunks16 & 1) == 0;
-}
-void launch_conv1d_f16x3_da_s16(const ConvArgs& a, int B, int max_cols, hipStream_t s, int bn) {
-    KX_REQUIRE(conv16_da_s16_shape(128, a.K, a.dil, a.stride, a.act, a.n_chunks16, a.merge_T > 0, conv16_pmode(a)), "conv1d f16x3 da s16: launch not eligible");
-    KX_REQUIRE(bn == 192 || bn == 128, "conv1d f16x3 da s16: tile of 192 or 128 columns");
-    if (a.K == 11) {
-        if (bn == 192) launch_da_inst<ACT_SNAKE, 11, 6>(a, B, max_cols, s);
-        else launch_da_inst<ACT_SNAKE, 11, 4>(a, B, max_cols, s);
-    } else {
-        if (bn == 192) launch_da_inst<ACT_SNAKE, 7, 6>(a, B, max_cols, s);
-        else launch_da_inst<ACT_SNAKE, 7, 4>(a, B, max_cols, s);
-    }
-}
-#elif defined(KX_DA_W2)
-// The W2 forms (conv_f16x3_da_w2.hip defines KX_DA_W2 and includes this file): the unrolled forms of the 256-column tile;
-// launch_da_ntt<8> of the main translation unit forwards here.  Results are bit-identical to the forms they replace.
-// (The reduced-precision mode keeps the 4 x 1 layout: its W2 instantiations measured 78.2 against 78.4 ms per step -- that mode is
-// bound by the transform's vector work, not by the operand reads -- and are not built.)
-bool conv16_da_w2_has(int act, int K) { return (act == ACT_SNAKE && (K == 3 || K == 7 || K == 11)) || (act == ACT_LEAKY && K == 3); }
-void launch_conv1d_f16x3_da_w2(const ConvArgs& a, int B, int max_cols, hipStream_t s) {
-    KX_REQUIRE(conv16_da_w2_has(a.act, a.K) && (a.K - 1) * a.dil <= 64 && !a.prec1, "conv1d f16x3 da w2: launch not eligible");
-#ifdef KX_DA_AUDIT
-    launch_da_inst<ACT_SNAKE, 11, 8>(a, B, max_cols, s);
-    return;
-#endif
-    if (a.act == ACT_LEAKY) launch_da_inst<ACT_LEAKY, 3, 8>(a, B, max_cols, s);
-    else if (a.K == 11) launch_da_inst<ACT_SNAKE, 11, 8>(a, B, max_cols, s);
-    else if (a.K == 7) launch_da_inst<ACT_SNAKE, 7, 8>(a, B, max_cols, s);
-    else launch_da_inst<ACT_SNAKE, 3, 8>(a, B, max_cols, s);
-}
-#else
-bool conv16_da_w2_has(int act, int K);                                                          // conv_f16x3_da_w2.hip
-void launch_conv1d_f16x3_da_w2(const ConvArgs& a, int B, int max_cols, hipStream_t s);  // conv_f16x3_da_w2.hip
-void launch_conv1d_f16x3_da_s16(const ConvArgs& a, int B, int max_cols, hipStream_t s, int bn);  // conv_f16x3_da_s16.hip
-
-template <int NTT, bool BFX = false>
-static void launch_da_ntt(const ConvArgs& a, int B, int max_cols, hipStream_t s) {
+// The 4 x 1 forms (FORM_DA) of one tile width: compile-time tap counts for the resblock convs (kt = 11, 7, 3: the transform dealt
+// out between the MFMAs), run-time ones (kt = 0) for the rest.  P1: the reduced-precision forms (conv_f16x3_da_p1.hip).
+template <int NTT, bool P1, bool BF>
+static void launch_da_4x1(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s) {
 #ifdef KX_DA_AUDIT  // (tests/test_asm_audit_cpu.py: the early return keeps the build short; every instantiation is still emitted)
-    if (a.act == ACT_SNAKE) launch_da_inst<ACT_SNAKE, 11, 8>(a, B, max_cols, s);
-    else launch_da_inst<ACT_LEAKY, 0, 4>(a, B, max_cols, s);
+    if (p.act == ACT_SNAKE) launch_da_inst<ACT_SNAKE, 11, 8, P1, false, false, false, BF>(a, B, p.cols, s);
+    else launch_da_inst<ACT_LEAKY, 0, 4, P1, false, false, false, BF>(a, B, p.cols, s);
     return;
 #endif
-    // the resblock tap counts get the unrolled form with the transform between the MFMAs (KX_DA_STATIC=0: run-time form)
-    static const int st = getenv("KX_DA_STATIC") ? atoi(getenv("KX_DA_STATIC")) : 1;
-    // (the unrolled forms stage a window of BN + 64 columns: (K - 1) dil <= 64, true of every resblock conv of the graph)
-    const bool w64 = (a.K - 1) * a.dil <= 64;
-#ifndef KX_DA_P1
-    // the 256-column tile's unrolled forms: the 2 x 2 wave layout (KX_DA_W2=0: 4 x 1; bit-identical either way)
-    static const int w2 = getenv("KX_DA_W2") ? atoi(getenv("KX_DA_W2")) : 1;
-    if (w2 && st && w64 && NTT == 8 && conv16_da_w2_has(a.act, a.K)) {
-        launch_conv1d_f16x3_da_w2(a, B, max_cols, s);
-        return;
-    }
-#endif
-    if (a.act == ACT_SNAKE) {
-        if (st && w64 && a.K == 11) launch_da_inst<ACT_SNAKE, 11, NTT, DA_W2, false, BFX>(a, B, max_cols, s);
-        else if (st && w64 && a.K == 7) launch_da_inst<ACT_SNAKE, 7, NTT, DA_W2, false, BFX>(a, B, max_cols, s);
-        else if (st && w64 && a.K == 3) launch_da_inst<ACT_SNAKE, 3, NTT, DA_W2, false, BFX>(a, B, max_cols, s);
-        else launch_da_inst<ACT_SNAKE, 0, NTT, DA_W2, false, BFX>(a, B, max_cols, s);
-    } else if (a.act == ACT_LEAKY) {
-        if (st && w64 && a.K == 3) launch_da_inst<ACT_LEAKY, 3, NTT, DA_W2, false, BFX>(a, B, max_cols, s);
-        else launch_da_inst<ACT_LEAKY, 0, NTT, DA_W2, false, BFX>(a, B, max_cols, s);
+    KX_REQUIRE(p.kt == 0 || (a.K == p.kt && (a.K - 1) * a.dil <= 64), "conv1d f16x3 da: compile-time taps do not match the launch");
+    if (p.act == ACT_SNAKE) {
+        if (p.kt == 11) launch_da_inst<ACT_SNAKE, 11, NTT, P1, false, false, false, BF>(a, B, p.cols, s);
+        else if (p.kt == 7) launch_da_inst<ACT_SNAKE, 7, NTT, P1, false, false, false, BF>(a, B, p.cols, s);
+        else if (p.kt == 3) launch_da_inst<ACT_SNAKE, 3, NTT, P1, false, false, false, BF>(a, B, p.cols, s);
+        else launch_da_inst<ACT_SNAKE, 0, NTT, P1, false, false, false, BF>(a, B, p.cols, s);
+    } else if (p.act == ACT_LEAKY) {
+        if (p.kt == 3) launch_da_inst<ACT_LEAKY, 3, NTT, P1, false, false, false, BF>(a, B, p.cols, s);
+        else launch_da_inst<ACT_LEAKY, 0, NTT, P1, false, false, false, BF>(a, B, p.cols, s);
     } else
-        launch_da_inst<ACT_NONE, 0, NTT, DA_W2, false, BFX>(a, B, max_cols, s);
+        launch_da_inst<ACT_NONE, 0, NTT, P1, false, false, false, BF>(a, B, p.cols, s);
 }
 
-#endif  // KX_DA_W2
-
-#if defined(KX_DA_W2) || defined(KX_DA_S16) || defined(KX_DA_PRE)
-#elif defined(KX_DA_P1)
-// bn: 256 or 128, as launch_conv1d_f16x3_da (which forwards here when a.prec1 is set)
-void launch_conv1d_f16x3_da_p1(const ConvArgs& a, int B, int max_cols, hipStream_t s, int bn) {
-    if (a.prec1 == 2) {  // bf16 operands: the bf16 form of the weight image
-        KX_REQUIRE(a.w16b != nullptr, "conv1d f16x3 da p1: no bf16 weight image");
-        ConvArgs b16 = a;
-        b16.w16 = a.w16b;
-        if (bn == 256) launch_da_ntt<8, true>(b16, B, max_cols, s);
-        else launch_da_ntt<4, true>(b16, B, max_cols, s);
-        return;
-    }
-    if (bn == 256)
-        launch_da_ntt<8>(a, B, max_cols, s);
-    else
-        launch_da_ntt<4>(a, B, max_cols, s);
+template <bool P1, bool BF>
+static void launch_da_4x1_bn(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s) {
+    KX_REQUIRE(p.bn == 256 || p.bn == 128, "conv1d f16x3 da: tile of 256 or 128 columns");
+    if (p.bn == 256) launch_da_4x1<8, P1, BF>(p, a, B, s);
+    else launch_da_4x1<4, P1, BF>(p, a, B, s);
 }
-#else
-void launch_conv1d_f16x3_da_p1(const ConvArgs& a, int B, int max_cols, hipStream_t s, int bn);  // conv_f16x3_da_p1.hip
-void launch_conv1d_f16x3_da_pre(const ConvArgs& a, int B, int max_cols, hipStream_t s, int bn);  // conv_f16x3_da_pre.hip
 
-// bn: 256 (chip-filling launches) or 128 (small grids); the statistics slots are 128 columns wide either way
-void launch_conv1d_f16x3_da(const ConvArgs& a, int B, int max_cols, hipStream_t s, int bn) {
-    KX_REQUIRE(conv16_da_eligible(128, a.K, a.dil, a.stride, a.merge_T > 0), "conv1d f16x3 da: launch not eligible");
-    KX_REQUIRE(a.n_chunks16 == (a.Cin + CK16 - 1) / CK16 && a.w16 != nullptr, "conv1d f16x3 da: weights not packed");
-    KX_REQUIRE(a.epi != EPI_GELU_NEW, "conv1d f16x3 da: no gelu epilogue");
-    KX_REQUIRE(bn == 256 || bn == 128 || bn == 192, "conv1d f16x3 da: tile of 256, 192 or 128 columns");
-    if (max_cols <= 0) return;
-    if (a.x16) {  // pre-split input image (conv_f16x3_pre.hip decides which layers get one)
-        KX_REQUIRE(bn != 192, "conv1d f16x3 da: no pre-split form of the 192-column tile");
-        launch_conv1d_f16x3_da_pre(a, B, max_cols, s, bn);
-        return;
-    }
-    // 7 / 11-tap snake convs: the 16x16x32 form on its 192- or 128-column tile (conv16_pick_tile chose bn and the 64-column
-    // statistics slots for it by the same predicate)
-    if (conv16_da_s16_shape(128, a.K, a.dil, a.stride, a.act, a.n_chunks16, a.merge_T > 0, conv16_pmode(a))) {
-        if (a.w8x && conv16_da_f8_shape(a.K, a.dil)) launch_conv1d_f16x3_da_f8(a, B, max_cols, s, bn == 128 ? 128 : 192);  // (CONV_F16F8)
-        else launch_conv1d_f16x3_da_s16(a, B, max_cols, s, bn == 128 ? 128 : 192);
-        return;
-    }
-    KX_REQUIRE(bn != 192, "conv1d f16x3 da: the 192-column tile exists in the S16 form only");
-    if (a.prec1) {
-        launch_conv1d_f16x3_da_p1(a, B, max_cols, s, bn);
-        return;
-    }
-    static const int dephase = getenv("KX_DEPHASE") ? atoi(getenv("KX_DEPHASE")) : 0;  // permille of a tile's estimated time
-    static const int dephase_mode = getenv("KX_DEPHASE_MODE") ? atoi(getenv("KX_DEPHASE_MODE")) : 1;
-    if (dephase > 0 && bn == 256) {  // (diagnostic, profiles/r03_lanes_dephase.txt: no effect)
-        ConvArgs d = a;
-        const long grid_n = (long)((max_cols + 255) / 256) * ((a.Cout + 127) / 128) * B;
-        // a tile: n_chunks x K x 8 column tiles x 3 MFMAs of 32 cycles, two waves per SIMD, ~80 % pipe use; + the epilogue
-        const double tile_cycles = (double)a.n_chunks16 * a.K * 8 * 96 * 2.5 + 50000.0;
-        d.dephase_cycles = grid_n >= 1024 ? (int)(tile_cycles * dephase / 1000.0) : 0;
-        d.dephase_mode = dephase_mode;
-        launch_da_ntt<8>(d, B, max_cols, s);
-        return;
-    }
-    if (bn == 256)
-        launch_da_ntt<8>(a, B, max_cols, s);
-    else
-        launch_da_ntt<4>(a, B, max_cols, s);
+#ifndef KX_DA_UNIT  // (the other direct-A units define it before including this file: their entry points are their own)
+void launch_conv16_da(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s) {
+    KX_REQUIRE(p.form == FORM_DA && !p.p1 && !a.prec1, "conv1d f16x3 da: not an f16x3 form of the 4 x 1 layout");
+    launch_da_4x1_bn<false, false>(p, a, B, s);
 }
 #endif
 

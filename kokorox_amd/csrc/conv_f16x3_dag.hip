@@ -27,15 +27,6 @@ __device__ __forceinline__ void static_for_g(F&& f) {
     }
 }
 
-bool conv16_dag_eligible(const ConvArgs& a, int BM) {
-    return BM == 128 && a.K == 1 && a.stride == 1 && !a.stat_part && !a.in_up2 && a.n_chunks16 >= 3 && a.act != ACT_SNAKE &&
-           a.nmean == nullptr && a.store != ST_UPSCATTER;
-}
-bool conv16_use_dag(const ConvArgs& a, int BM) {
-    static const int on = getenv("KX_DAG") ? atoi(getenv("KX_DAG")) : 1;
-    return on && conv16_dag_eligible(a, BM);
-}
-
 template <int ACT>
 __global__ __launch_bounds__(256, 3) void conv1d_f16x3_dag_kernel(const ConvArgs a) {
     constexpr int BM = 128, BN = 128, NT = 4, VT = 3;
@@ -410,31 +401,28 @@ static void launch_dag_inst(const ConvArgs& a, int B, int max_cols, hipStream_t 
     KX_HIP(hipGetLastError());
 }
 
-void launch_conv1d_f16x3_dag(const ConvArgs& a, int B, int max_cols, hipStream_t s) {
-    KX_REQUIRE(conv16_dag_eligible(a, 128), "conv1d f16x3 dag: launch not eligible");
+// FORM_DAG, or FORM_DAGN on small grids (results are bit-identical either way)
+void launch_conv1d_f16x3_dag(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s) {
+    KX_REQUIRE(a.K == 1 && a.stride == 1 && !a.stat_part && !a.in_up2 && a.n_chunks16 >= 3 && a.act != ACT_SNAKE && a.nmean == nullptr &&
+                   a.store != ST_UPSCATTER,
+               "conv1d f16x3 dag: launch not eligible");
     KX_REQUIRE(a.n_chunks16 == (a.Cin + CK16 - 1) / CK16 && a.w16 != nullptr, "conv1d f16x3 dag: weights not packed");
     KX_REQUIRE(a.pad == 0, "conv1d f16x3 dag: a 1-tap GEMM has no padding");
-    if (max_cols <= 0) return;
-    // at most half as many 128 x 128 tiles as CUs: the narrow form (KX_DAGN=0: never, 2: always; results are bit-identical either
-    // way).  Measured by batch, off / on: 1: 11.85 / 10.55 ms, 4: 16.74 / 15.73, 16: 36.6 / 36.5; at 32 and 64 no launch qualifies
-    // (forced everywhere it costs 3 - 5 %: four times the weight traffic and the split repeated by four waves; on the 390-tile grids of the
-    // 768-row GEMMs at batch 64 alone it is twice as slow as the 128 x 128 form: 3.09 against 1.59 ms for 12 launches).
-    static const int narrow = getenv("KX_DAGN") ? atoi(getenv("KX_DAGN")) : 1;
-    const long wgs = (long)((max_cols + 127) / 128) * ((a.Cout + 127) / 128) * (a.merge_T > 0 ? 1 : B);
-    // (the narrow form: 32-bit byte offsets into the input)
-    const long x_span = ((long)a.x_bs * (a.merge_T > 0 ? a.merge_B : B) + (long)CK16 * a.x_ld) * 4;
-    const bool narrow_ok = x_span < (1L << 31);
-    if (narrow_ok && (narrow == 2 || (narrow && 2 * wgs <= conv16_cu_count()))) {
+    if (p.cols <= 0) return;
+    if (p.form == FORM_DAGN) {
+        // (the narrow form: 32-bit byte offsets into the input)
+        const long x_span = ((long)a.x_bs * (a.merge_T > 0 ? a.merge_B : B) + (long)CK16 * a.x_ld) * 4;
+        KX_REQUIRE(x_span < (1L << 31), "conv1d f16x3 dag narrow: input beyond 2 GiB");
         if (a.act == ACT_LEAKY)
-            launch_dagn_inst<ACT_LEAKY>(a, B, max_cols, s);
+            launch_dagn_inst<ACT_LEAKY>(a, B, p.cols, s);
         else
-            launch_dagn_inst<ACT_NONE>(a, B, max_cols, s);
+            launch_dagn_inst<ACT_NONE>(a, B, p.cols, s);
         return;
     }
     if (a.act == ACT_LEAKY)
-        launch_dag_inst<ACT_LEAKY>(a, B, max_cols, s);
+        launch_dag_inst<ACT_LEAKY>(a, B, p.cols, s);
     else
-        launch_dag_inst<ACT_NONE>(a, B, max_cols, s);
+        launch_dag_inst<ACT_NONE>(a, B, p.cols, s);
 }
 
 }  // namespace kx

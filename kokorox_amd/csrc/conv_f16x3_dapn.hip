@@ -24,9 +24,8 @@ __device__ __forceinline__ void static_for_n(F&& f) {
     }
 }
 
-bool conv16_dapn_eligible(const ConvArgs& a) {
-    static const int on = getenv("KX_DAPN") ? atoi(getenv("KX_DAPN")) : 1;
-    return on && a.x16 != nullptr && a.x16_ld > 0 && !a.in_up2 && !a.prec1 && a.stride == 1 && a.merge_T == 0 && a.Cout % 32 == 0 &&
+static bool dapn_eligible(const ConvArgs& a) {
+    return a.x16 != nullptr && a.x16_ld > 0 && !a.in_up2 && !a.prec1 && a.stride == 1 && a.merge_T == 0 && a.Cout % 32 == 0 &&
            a.K >= 1 && a.K <= 12 && a.epi == EPI_NONE && (a.store == ST_NORMAL || a.store == ST_UPSCATTER) &&
            !(a.stat_part && (a.store != ST_NORMAL || a.accum)) && (long)a.n_chunks16 * a.K < 5000;
 }
@@ -199,7 +198,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_f16x3_dapn_kernel(const ConvArg
 }
 
 void launch_conv1d_f16x3_dapn(const ConvArgs& a, int B, int max_cols, hipStream_t s) {
-    KX_REQUIRE(conv16_dapn_eligible(a), "conv1d f16x3 dapn: launch not eligible");
+    KX_REQUIRE(dapn_eligible(a), "conv1d f16x3 dapn: launch not eligible");
     KX_REQUIRE(a.n_chunks16 == (a.Cin + CK16 - 1) / CK16 && a.w16 != nullptr, "conv1d f16x3 dapn: weights not packed");
     KX_REQUIRE((long)a.n_chunks16 * 64 * a.x16_ld < (1L << 31), "conv1d f16x3 dapn: image of one utterance beyond 2 GiB");
     if (max_cols <= 0) return;

@@ -6,7 +6,8 @@
 // upsamplers, whose run-time-tap form cannot even hide it between its MFMAs.  For those layers the transform is done ONCE here,
 // by an elementwise pass that writes the image in the very layout the kernels keep in LDS; staging a chunk is then five or six
 // 16-byte loads and LDS writes per lane.  The pass costs one read and one write of the tensor (HBM-bound, these tensors are
-// F or 2F or 20F columns long); the rule below takes the layers where that is cheaper than the repeated transform.
+// F or 2F or 20F columns long); the plan (conv_plan.hip) gives an image to the layers where that is cheaper than the repeated
+// transform, by their shape alone.
 //
 // Same arithmetic, operation for operation, as emit8 / xform_* of conv_f16x3_da.hip (fma of (x - mean) with scale and shift,
 // activation, one multiply by the pre-scale, split_pair): a layer's bits do not depend on which path staged it (tested:
@@ -14,22 +15,6 @@
 #include "conv_f16x3_common.h"
 
 namespace kx {
-
-static int pre_env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
-// Which layers get a pre-split image: by the layer's shape alone (never by the batch, so an utterance's bits do not depend on
-// what it is batched with -- and the arithmetic is the same either way).  KX_PRE_ROWS: smallest row count (0 = never).
-bool conv16_pre_shape(int BM, int rows, int K, int dil, int stride, int act, int in_up2) {
-    // >= 4 row tiles per window.  At batch 64 the 512-row layers (the predictor's F0 / N convs, decode.3) gain from it what their six
-    // extra passes cost (profiles/r05_experiments_not_kept.txt: 113.32 vs 113.28 ms); at batch 1 they then take the narrow form
-    // (conv_f16x3_dapn.hip: 64 workgroups instead of 16 on the forward's critical path), which is what the rule is set by.
-    static const int min_rows = pre_env_int("KX_PRE_ROWS", 512);
-    return min_rows > 0 && BM == 128 && rows >= min_rows && stride == 1 && K >= 2 && !in_up2 && act != ACT_SNAKE &&
-           conv16_da_eligible(BM, K, dil, stride, 0) && conv16_use_da(BM, K, dil, stride, 0);
-}
 
 size_t conv16_pre_image_bytes(int Cin, int x_ld) { return (size_t)((Cin + CK16 - 1) / CK16) * 64 * (size_t)x_ld; }
 

@@ -141,26 +141,65 @@ struct ConvArgs {
     int x16_ld;
 };
 
+// ---- the launch plan of a conv (conv_plan.hip): kernel form, tile, statistics slots, flat tile list, input staging ----------
+enum ConvMode { CONV_F32 = 0, CONV_F16X3 = 1, CONV_F16X3_LDS = 2, CONV_F16X3_DA = 3, CONV_F16 = 4, CONV_BF16 = 5, CONV_F16F8 = 6 };  // (2, 3: test hook only: f16x3 kept on the LDS-DMA kernel forms of conv_f16x3.hip / forced through conv_f16x3_da.hip)
+enum ConvForm {
+    FORM_F32 = 0,  // conv1d_mfma_kernel<bm, ..> (conv_mfma.hip: the f32 mode)
+    FORM_LDS,      // conv1d_f16x3_kernel<bm, bn, wm, wn, act, vt == 1 ? 3 : vt, pf, vt> (conv_f16x3.hip: weights by LDS-DMA; vt > 1: k = 1 GEMMs)
+    FORM_DAG,      // conv1d_f16x3_dag_kernel<act> (conv_f16x3_dag.hip: k = 1 GEMMs, 128 x 128 tiles)
+    FORM_DAGN,     // conv1d_f16x3_dagn_kernel<act> (the same on small grids: 128 x 32 tiles)
+    FORM_DA,       // conv1d_f16x3_da_kernel<act, kt, bn / 32, p1, .., bf>, 4 x 1 waves (conv_f16x3_da.hip; p1: conv_f16x3_da_p1.hip)
+    FORM_DA_W2,    // its 2 x 2-wave forms of the 256-column tile (conv_f16x3_da_w2.hip)
+    FORM_DA_S16,   // its 16x16x32 forms: 11 / 7 taps, 192 / 128 columns (conv_f16x3_da_s16.hip)
+    FORM_DA_F8,    // their f16f8 forms: 11 / 7 / 3 taps (conv_f16x3_da_f8.hip)
+    FORM_DA_PRE,   // its forms that stage a pre-split input image (conv_f16x3_da_pre.hip)
+    FORM_DAPN,     // the narrow pre-split form for small grids: 32 rows x 128 columns, no staging (conv_f16x3_dapn.hip)
+};
+// ConvArgs::ws_force, the test hooks' overrides (0 in the model): the low two bits hold 1 = the LDS-DMA forms only or 2 = the
+// direct-A forms whatever the grid; FORCE_DA_4X1 = the 4 x 1 wave layout on the 256-column tile too, FORCE_NO_S16 = no 16x16x32 form
+enum ConvForce { FORCE_LDS = 1, FORCE_DA = 2, FORCE_DA_4X1 = 4, FORCE_NO_S16 = 8 };
+
+struct ConvLaunch {  // what the plan of a conv launch depends on
+    int mode;          // ConvMode: CONV_F32, CONV_F16X3, CONV_F16, CONV_BF16 or CONV_F16F8
+    int prec1;         // ConvArgs::prec1 (1: one f16 MFMA per product; 2: one bf16 MFMA, on the layer's bf16 image)
+    int f8;            // the launch carries the layer's 8-bit cross image (ConvArgs::w8x)
+    int BM, rows, n_chunks16, K, dil, stride, pad, act, in_up2, store, accum, epi;
+    int norm;          // AdaIN affine on the input
+    int stats;         // InstanceNorm partial sums of the output requested
+    int image;         // pre-split input image: 0 = none can be made, 1 = by the layer's shape, 2 = wherever the layer has that form
+    int merge_T;       // > 0: input and output share one plain length array and this longest length (the columns may be merged)
+    long x_bs;         // input floats per utterance
+    int x_ld;
+    int B, cols;       // batch; columns of the launch (the longest output; ST_UPSCATTER: the longest input + 1)
+    int cus;           // CUs of the device, or of the model's CU partition
+    int force;         // ConvArgs::ws_force
+};
+struct ConvPlan {
+    int form;                           // ConvForm
+    int bm, act, kt, wm, wn, vt, pf, p1, bf;  // the form's template parameters (kt: the direct-A forms' compile-time taps, 0 = run time)
+    int bn;                             // tile width: columns per workgroup
+    int cols;                           // columns of the launch (merged: B x merge_T)
+    int merged;                         // one merged column space for the batch (ConvArgs::merge_T, merge_B)
+    int pre;                            // the input is written as a pre-split image first (ConvArgs::x16)
+    int stat_cols, stat_tiles;          // fused InstanceNorm partial sums: slot width, slots per row (0: not fused)
+    int flat_bn;                        // tile width of the flat tile list of a ragged batch (= bn), 0 = the form takes none
+};
+ConvPlan conv_plan(const ConvLaunch& c);
+bool conv16_f8_layer(int BM, int rows, int K, int n_chunks16);  // layers that get an 8-bit cross image in f16f8 mode (dilation 1)
+// carries the plan out: one launch, a conv1d_mfma / conv1d_f16x3 / direct-A kernel (conv_f16x3.hip)
+void launch_conv(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s);
+int conv16_cu_count();  // CUs of the current device, or of the launching model's CU partition (conv_f16x3.hip)
+int cu_count_override(); // model.hip: the CU partition of the model that is launching on this thread (0 = none)
+
 // pre-split images (conv_f16x3_pre.hip)
-bool conv16_pre_shape(int BM, int rows, int K, int dil, int stride, int act, int in_up2);  // which layers get one: by shape alone
 size_t conv16_pre_image_bytes(int Cin, int x_ld);  // per utterance
 // writes the image of a.x (a's norm parameters, activation, slope, pre-scale) for B utterances of at most Lmax columns
-// the narrow pre-split form for small grids (conv_f16x3_dapn.hip): 32 rows x 128 columns per workgroup, B fragments straight from the image
-bool conv16_dapn_eligible(const ConvArgs& a);
-void launch_conv1d_f16x3_dapn(const ConvArgs& a, int B, int max_cols, hipStream_t s);
 void launch_split_image(const ConvArgs& a, int B, int Lmax, void* img, long img_bs, hipStream_t s);
 
 // tile_prefix of a LenMap for `bn`-column tiles (+ `extra` columns per utterance: the polyphase convs' L + 1), on the device
 void launch_tile_prefix(LenMap len, int extra, int bn, int B, int* out, hipStream_t s);
-// the launch geometry launch_conv1d_f16x3 will choose for these arguments if it can take a flat tile list: the tile width
-// (128 / 192 / 256 columns), or 0 when the launch goes to a kernel without the flat form
-int conv16_flat_bn(const ConvArgs& a, int BM, int B, int max_cols);
 
-struct ConvShape {
-    int BM;  // 128, 64 or 32
-};
 inline int conv_pick_bm(int rows) { return rows >= 128 ? 128 : (rows > 32 ? 64 : 32); }
-inline int conv_bn(int BM) { return BM == 128 ? 128 : 256; }
 
 void launch_conv1d(const ConvArgs& a, int BM, int B, int max_cols, hipStream_t s);
 
@@ -174,27 +213,19 @@ void launch_pack_conv(const PackSrc& src, float* dst, int Cout, int Cin, int K, 
 void launch_pack_convT(const float* w, float* dst, int Cin, int Cout, int s, int BM, hipStream_t s_);
 size_t packed_conv_floats(int rows, int Cin, int K, int BM);
 
-// f16x3 split path
-enum ConvMode { CONV_F32 = 0, CONV_F16X3 = 1, CONV_F16X3_LDS = 2, CONV_F16X3_DA = 3, CONV_F16 = 4, CONV_BF16 = 5, CONV_F16F8 = 6 };  // (2, 3: test hook only: f16x3 kept on the LDS-DMA kernel forms of conv_f16x3.hip / forced through conv_f16x3_da.hip)
-void launch_conv1d_f16x3(const ConvArgs& a, int BM, int B, int max_cols, hipStream_t s);
-// precision class of a launch, as the shape rules see it: 0 = f16x3, 1 = reduced precision (one MFMA per product), 2 = f16f8 (the
-// layer carries an 8-bit cross image)
-inline int conv16_pmode(const ConvArgs& a) { return a.prec1 ? 1 : (a.w8x ? 2 : 0); }
-// (act / n_chunks16 / pmode: given, the shapes of the direct-A S16 form get its tiles: 192 or 128 columns, 64-column statistics slots)
-void conv16_pick_tile(int BM, int max_cols, int B, int Cout, int K, int dil, int stride, int* bn, int* wn,
-                      int ws_force = 0, bool stats = false, int act = -1, int n_chunks16 = 0, int pmode = 0);  // (conv_f16x3.hip)
-// conv_f16x3_da.hip: the 128 x 256 tile with the weight fragments loaded from global memory straight into registers
-bool conv16_use_da(int BM, int K, int dil, int stride, int merged);       // eligible AND switched on (default; KX_DA=0 turns it off)
-bool conv16_da_eligible(int BM, int K, int dil, int stride, int merged);  // shape fits the kernel
-void launch_conv1d_f16x3_da(const ConvArgs& a, int B, int max_cols, hipStream_t s, int bn = 256);
-// conv_f16x3_dag.hip: k = 1 GEMMs (incl. the merged token-axis form) in the direct-A form, 128 x 128 tile
-bool conv16_use_dag(const ConvArgs& a, int BM);       // eligible AND switched on (default; KX_DAG=0 turns it off)
-bool conv16_dag_eligible(const ConvArgs& a, int BM);
-void launch_conv1d_f16x3_dag(const ConvArgs& a, int B, int max_cols, hipStream_t s);
-int conv16_cu_count();  // CUs of the current device, or of the launching model's CU partition (conv_f16x3.hip)
-int cu_count_override(); // model.hip: the CU partition of the model that is launching on this thread (0 = none)
-// shapes that take the 16x16x32 form of the direct-A conv (conv_f16x3_da_s16.hip): 192 / 128-column tiles, 64-column statistics slots
-bool conv16_da_s16_shape(int BM, int K, int dil, int stride, int act, int n_chunks16, bool merged, int pmode);
+// f16x3 split path: the launchers of the plan's forms (launch_conv calls them)
+// direct-A conv units, one entry each: conv_f16x3_da.hip (FORM_DA, f16x3), _p1.hip (FORM_DA, reduced precision), _w2.hip,
+// _s16.hip, _f8.hip, _pre.hip
+void launch_conv16_da(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s);
+void launch_conv16_da_p1(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s);
+void launch_conv16_da_w2(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s);
+void launch_conv16_da_s16(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s);
+void launch_conv16_da_f8(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s);
+void launch_conv16_da_pre(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s);
+// the narrow pre-split form (conv_f16x3_dapn.hip): 32 rows x 128 columns per workgroup, B fragments straight from the image
+void launch_conv1d_f16x3_dapn(const ConvArgs& a, int B, int max_cols, hipStream_t s);
+// k = 1 GEMMs (incl. the merged token-axis form) in the direct-A form (conv_f16x3_dag.hip): FORM_DAG / FORM_DAGN
+void launch_conv1d_f16x3_dag(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s);
 size_t packed_conv16_halves(int rows, int Cin, int K, int BM);
 float device_absmax(const float* p, long n, hipStream_t s);
 int pick_weight_shift(float absmax);
@@ -211,8 +242,6 @@ void launch_image_to_bf16(const void* w16, void* dst, size_t n_halves, hipStream
 // (split_pair_f8, conv_f16x3_common.h); the products of a slot carry 2^7 (undone by the instruction's block scale).
 size_t packed_conv8x_bytes(int rows, int Cin, int K);
 void launch_pack_conv8x(const void* w16, void* dst, int rows, int Cin, int K, hipStream_t s);
-bool conv16_da_f8_shape(int K, int dil);  // which of the S16 form's shapes have an f16f8 kernel (conv_f16x3_da_f8.hip)
-void launch_conv1d_f16x3_da_f8(const ConvArgs& a, int B, int max_cols, hipStream_t s, int bn);
 
 // ---- everything else (kernels_misc.hip) ----------------------------------------------
 void launch_vec_add(const float* a, const float* b, float* out, int n, hipStream_t s);

@@ -590,11 +590,44 @@ struct Model::LaneScope {
 };
 
 void Model::conv(const ConvW& w, const T& in, const T& out, const ConvOpts& o) {
-    // Layers whose input window many row tiles stage get a pre-split image of the input (conv_f16x3_pre.hip): planned in the
-    // dry run like every other buffer of the back half; the rule looks at the layer's shape only.
+    // reduced-precision mode (opt-in): the decoder and generator convs that take the direct-A kernel run one f16 MFMA
+    // per product; everything upstream of the F0 / N curves (duration head, prosody predictor) and every kernel that is
+    // not the direct-A conv (harmonic source, STFT pair, k = 1 GEMMs, conv_post) stays f32-class (SURVEY.md section 7, hard part 3)
+    const int prec1 = (conv_mode == CONV_F16 && p1_region_) ? 1 : ((conv_mode == CONV_BF16 && p1_region_ && w.w16b) ? 2 : 0);
+    // f16f8 mode (the default): the layers that carry an 8-bit cross image run two MFMA-equivalents per product instead of three
+    const void* w8x = conv_mode == CONV_F16F8 ? w.w8x : nullptr;
+    // The plan of the launch (conv_plan.hip): also in the dry run, which plans the pre-split input images like every other buffer
+    // of the back half
+    ConvLaunch c{};
+    c.mode = conv_mode;
+    c.prec1 = prec1;
+    c.f8 = w8x != nullptr;
+    c.BM = w.BM;
+    c.rows = w.rows;
+    c.n_chunks16 = w.n_chunks16;
+    c.K = w.K;
+    c.dil = o.dil;
+    c.stride = o.stride;
+    c.pad = o.pad;
+    c.act = o.act;
+    c.in_up2 = o.in_up2;
+    c.store = o.store;
+    c.accum = o.accum;
+    c.epi = o.epi;
+    c.norm = o.nmean != nullptr;
+    c.stats = o.stat_part != nullptr;
+    c.image = img_arena_ ? 1 : 0;
+    const bool plain_lens = in.len.mul == 1 && in.len.add == 0 && out.len.lens == in.len.lens && out.len.mul == 1 && out.len.add == 0;
+    c.merge_T = plain_lens ? in.Lmax : 0;
+    c.x_bs = in.bs;
+    c.x_ld = in.ld;
+    c.B = B_;
+    c.cols = (o.store == ST_UPSCATTER) ? in.Lmax + 1 : out.Lmax;
+    c.cus = dry_ ? 0 : conv16_cu_count();  // (the dry run needs the image only, which does not depend on it)
+    const ConvPlan plan = conv_plan(c);
     void* x16 = nullptr;
     long x16_bs = 0;
-    if ((conv_mode == CONV_F16X3 || conv_mode == CONV_F16F8) && img_arena_ && conv16_pre_shape(w.BM, w.rows, w.K, o.dil, o.stride, o.act, o.in_up2)) {
+    if (plan.pre) {
         x16_bs = (long)conv16_pre_image_bytes(w.Cin, in.ld);
         x16 = img_arena_->alloc((size_t)B_ * x16_bs);
     }
@@ -645,15 +678,11 @@ void Model::conv(const ConvW& w, const T& in, const T& out, const ConvOpts& o) {
     a.up_off = o.up_off;
     a.up_reflect = o.up_reflect;
     a.up_cout = w.up_cout ? w.up_cout : 1;
-    const bool f16 = conv_mode == CONV_F16X3 || conv_mode == CONV_F16 || conv_mode == CONV_BF16 || conv_mode == CONV_F16F8;
-    // reduced-precision mode (opt-in): the decoder and generator convs that take the direct-A kernel run one f16 MFMA
-    // per product; everything upstream of the F0 / N curves (duration head, prosody predictor) and every kernel that is
-    // not the direct-A conv (harmonic source, STFT pair, k = 1 GEMMs, conv_post) stays f32-class (SURVEY.md section 7, hard part 3)
-    a.prec1 = (conv_mode == CONV_F16 && p1_region_) ? 1 : ((conv_mode == CONV_BF16 && p1_region_ && w.w16b) ? 2 : 0);
+    const bool f16 = plan.form != FORM_F32;
+    a.prec1 = prec1;
     a.w16 = w.w16;
     a.w16b = w.w16b;
-    // f16f8 mode (opt-in): the layers that carry an 8-bit cross image run two MFMA-equivalents per product instead of three
-    a.w8x = conv_mode == CONV_F16F8 ? w.w8x : nullptr;
+    a.w8x = w8x;
     // outputs that no cache can hold until the next layer reads them (> 512 MB: L2 is 32 MB, MALL 256 MB) are streamed by the direct-A
     // kernels' interior stores (non-temporal stores and residual loads); smaller ones (small batches, the token axis, the decoder)
     // stay cacheable
@@ -670,45 +699,29 @@ void Model::conv(const ConvW& w, const T& in, const T& out, const ConvOpts& o) {
         diag_recs_.push_back(DiagRec{w.name, w.rows, w.Cin, w.K, w.act_shift, 0.0, 0.0, 0.0});
     }
     parts_.erase(out.p);  // whatever statistics were known for this tensor are stale now
-    static const bool fuse_stats = !(getenv("KX_FUSE_STATS") && atoi(getenv("KX_FUSE_STATS")) == 0);
-    if (fuse_stats && o.stat_part && o.store == ST_NORMAL && !o.accum) {
-        const int max_c = out.Lmax;
-        int bn, wn;
-        if (f16) {
-            conv16_pick_tile(w.BM, max_c, B_, w.rows, w.K, o.dil, o.stride, &bn, &wn, 0, true, o.act, w.n_chunks16, conv16_pmode(a));
-        } else {
-            bn = conv_bn(w.BM);
-            wn = w.BM == 128 ? 2 : 4;
-        }
+    if (plan.stat_cols) {  // InstanceNorm partial sums in the epilogue
         a.stat_part = o.stat_part;
-        a.stat_tiles = ((max_c + bn - 1) / bn) * wn;
-        parts_[out.p] = PartInfo{o.stat_part, a.stat_tiles, bn / wn, w.rows};
+        a.stat_tiles = plan.stat_tiles;
+        parts_[out.p] = PartInfo{o.stat_part, a.stat_tiles, plan.stat_cols, w.rows};
     }
     static const int dbg_env = getenv("KX_DBG") ? atoi(getenv("KX_DBG")) : 0;
     a.dbg = dbg_env;
-    int max_cols = (o.store == ST_UPSCATTER) ? in.Lmax + 1 : out.Lmax;
-    static const bool merge_env = !(getenv("KX_MERGE") && atoi(getenv("KX_MERGE")) == 0);
-    if (merge_env && f16 && B_ > 1 && w.K == 1 && o.stride == 1 && o.pad == 0 && !o.in_up2 && !o.nmean &&
-        o.store != ST_UPSCATTER && !o.stat_part && in.Lmax <= 512 && in.len.mul == 1 && in.len.add == 0 &&
-        out.len.lens == in.len.lens && out.len.mul == 1 && out.len.add == 0) {
-        a.merge_T = in.Lmax;  // k = 1 GEMM on a short axis: one merged column space for the whole batch
+    const int max_cols = plan.cols;
+    if (plan.merged) {  // k = 1 GEMM on a short axis: one merged column space for the whole batch
+        a.merge_T = in.Lmax;
         a.merge_B = B_;
-        max_cols = B_ * in.Lmax;
     }
     // ragged batch: the direct-A kernels take a flat list of the live tiles instead of a (longest length) x B grid
-    if (f16 && B_ > 1) {
-        const int fbn = conv16_flat_bn(a, w.BM, B_, max_cols);
-        if (fbn) {
-            const LenMap& lm = (o.store == ST_UPSCATTER) ? a.in_len : a.out_len;
-            const int extra = o.store == ST_UPSCATTER ? 1 : 0;
-            int total = 0;
-            a.tile_prefix = tile_prefix_for(lm, extra, fbn, &total);
-            a.flat_ny = (w.rows + 127) / 128;
-            a.flat_B = B_;
-            a.flat_tiles_host = total;
-            a.flat_bn_host = fbn;
-            if (total <= 0) return;  // (nothing to compute)
-        }
+    if (plan.flat_bn) {
+        const LenMap& lm = (o.store == ST_UPSCATTER) ? a.in_len : a.out_len;
+        const int extra = o.store == ST_UPSCATTER ? 1 : 0;
+        int total = 0;
+        a.tile_prefix = tile_prefix_for(lm, extra, plan.flat_bn, &total);
+        a.flat_ny = (w.rows + 127) / 128;
+        a.flat_B = B_;
+        a.flat_tiles_host = total;
+        a.flat_bn_host = plan.flat_bn;
+        if (total <= 0) return;  // (nothing to compute)
     }
     // diagnostic: KX_STAMP=<file> dumps per-workgroup timestamps of the first 128->128 k=11 launch
     static const char* stamp_path = getenv("KX_STAMP");
@@ -762,13 +775,11 @@ void Model::conv(const ConvW& w, const T& in, const T& out, const ConvOpts& o) {
             }
         }
         KX_HIP(hipEventRecord(ev_[ev_used_], stream_));
-        if (f16) launch_conv1d_f16x3(a, w.BM, B_, max_cols, stream_);
-        else launch_conv1d(a, w.BM, B_, max_cols, stream_);
+    }
+    launch_conv(plan, a, B_, stream_);
+    if (prof_on_ && w.BM == 128) {
         KX_HIP(hipEventRecord(ev_[ev_used_ + 1], stream_));
         ev_used_ += 2;
-    } else {
-        if (f16) launch_conv1d_f16x3(a, w.BM, B_, max_cols, stream_);
-        else launch_conv1d(a, w.BM, B_, max_cols, stream_);
     }
     if (d_stamps) {
         stamped = true;
@@ -1031,8 +1042,7 @@ void Model::set_conv_mode(int mode) {
         KX_HIP(hipSetDevice(device));
         for (auto& kv : convs_) {
             ConvW& c = kv.second;
-            const bool taps = c.K == 7 || c.K == 11 || (c.K == 3 && c.rows <= 256 && conv16_da_f8_shape(3, 1));
-            if (c.w8x || !c.w16 || c.BM != 128 || c.up_s || !taps || c.n_chunks16 < 2 || (c.n_chunks16 & 1)) continue;
+            if (c.w8x || !c.w16 || c.up_s || !conv16_f8_layer(c.BM, c.rows, c.K, c.n_chunks16)) continue;
             void* p = nullptr;
             KX_HIP(hipMalloc(&p, packed_conv8x_bytes(c.rows, c.Cin, c.K)));
             owned_.push_back(p);

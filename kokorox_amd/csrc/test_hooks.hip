@@ -96,11 +96,13 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         const bool pre = (mode & 0x100) != 0;
         // bit 9: f16f8 -- the layer gets the 8-bit cross image of its weights (the S16 form's shapes then run the f16f8 kernel)
         const bool f8 = (mode & 0x200) != 0;
+        // bits 10, 11: the 4 x 1 wave layout on the direct-A conv's 256-column tile too; no 16x16x32 form (ConvForce)
+        const int force_bits = (mode & 0x400 ? kx::FORCE_DA_4X1 : 0) | (mode & 0x800 ? kx::FORCE_NO_S16 : 0);
         mode &= 0xff;
         KX_REQUIRE(mode >= kx::CONV_F32 && mode <= kx::CONV_F16X3_DA, "test_conv1d: mode must be 0, 1, 2 or 3");
         KX_REQUIRE(!pre || mode == kx::CONV_F16X3 || mode == kx::CONV_F16X3_DA, "test_conv1d: pre-split images exist for the direct-A kernels only");
         kx::ConvArgs a{};
-        a.ws_force = mode == kx::CONV_F16X3_LDS ? 1 : (mode == kx::CONV_F16X3_DA ? 2 : 0);
+        a.ws_force = (mode == kx::CONV_F16X3_LDS ? kx::FORCE_LDS : (mode == kx::CONV_F16X3_DA ? kx::FORCE_DA : 0)) | force_bits;
         // row strides: the caller's dense rows, or (pad_ld) the model's: a multiple of 32 floats, input padding poisoned
         const int Ly = Lout + ex.up_off;  // columns of y (Lout: the conv's own output length)
         KX_REQUIRE(ex.up_off == 0 || (transposed && ex.up_off == 1 && !ex.pad_ld), "test_conv1d: an output offset comes with transposed convs");
@@ -201,19 +203,34 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
             a.r_bs = (long)Cout * y_ld;
             a.r_ld = y_ld;
         }
+        // the plan of the launch (conv_plan.hip), as the model makes it: the hook's modes 2 and 3 are f16x3 with an override
+        kx::ConvLaunch c{};
+        c.mode = mode == kx::CONV_F32 ? kx::CONV_F32 : (f8 ? kx::CONV_F16F8 : kx::CONV_F16X3);
+        c.f8 = f8;
+        c.BM = BM;
+        c.rows = rows;
+        c.n_chunks16 = (Cin + 15) / 16;
+        c.K = a.K;
+        c.dil = a.dil;
+        c.stride = a.stride;
+        c.pad = a.pad;
+        c.act = act;
+        c.norm = norm != nullptr;
+        c.store = a.store;
+        c.accum = ex.accum;
+        c.stats = ex.stats_out != nullptr;
+        c.image = pre ? 2 : 0;
+        c.x_bs = a.x_bs;
+        c.x_ld = x_ld;
+        c.B = B;
+        c.cols = transposed ? L + 1 : Lout;
+        c.cus = mode == kx::CONV_F32 ? 0 : kx::conv16_cu_count();
+        c.force = a.ws_force;
+        const kx::ConvPlan plan = kx::conv_plan(c);
         float2* d_part = nullptr;
-        int cols_per_tile = 0;
         if (ex.stats_out) {
-            KX_REQUIRE(!transposed && !ex.accum, "test_conv1d: fused statistics come with plain, non-accumulating stores");
-            int bn, wn;
-            if (mode != kx::CONV_F32) {
-                kx::conv16_pick_tile(BM, Lout, B, rows, a.K, a.dil, a.stride, &bn, &wn, a.ws_force, true, a.act, (Cin + 15) / 16, f8 ? 2 : 0);
-            } else {
-                bn = kx::conv_bn(BM);
-                wn = BM == 128 ? 2 : 4;
-            }
-            a.stat_tiles = ((Lout + bn - 1) / bn) * wn;
-            cols_per_tile = bn / wn;
+            KX_REQUIRE(!transposed && !ex.accum && plan.stat_cols > 0, "test_conv1d: fused statistics come with plain, non-accumulating stores");
+            a.stat_tiles = plan.stat_tiles;
             d_part = dm.get<float2>((size_t)B * rows * a.stat_tiles);
             KX_HIP(hipMemset(d_part, 0, (size_t)B * rows * a.stat_tiles * sizeof(float2)));
             a.stat_part = d_part;
@@ -240,28 +257,23 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
             a.w_unscale = std::ldexp(1.0f, -ws);
             a.x_prescale = 1.0f;
             a.xcd_swizzle = 1;
-            const int max_cols = transposed ? L + 1 : Lout;
-            if (ex.flat && B > 1) {
-                const int fbn = kx::conv16_flat_bn(a, BM, B, max_cols);
-                if (fbn) {
-                    const kx::LenMap lm = transposed ? a.in_len : a.out_len;
-                    int* d_pre = dm.get<int>((size_t)B + 1);
-                    kx::launch_tile_prefix(lm, transposed ? 1 : 0, fbn, B, d_pre, nullptr);
-                    int total = 0;
-                    for (int b = 0; b < B; ++b) {
-                        const int cols = lens[b] * lm.mul + lm.add + (transposed ? 1 : 0);
-                        total += cols > 0 ? (cols + fbn - 1) / fbn : 0;
-                    }
-                    a.tile_prefix = d_pre;
-                    a.flat_ny = (rows + 127) / 128;
-                    a.flat_B = B;
-                    a.flat_tiles_host = total;
-                    a.flat_bn_host = fbn;
+            if (ex.flat && plan.flat_bn) {
+                const kx::LenMap lm = transposed ? a.in_len : a.out_len;
+                int* d_pre = dm.get<int>((size_t)B + 1);
+                kx::launch_tile_prefix(lm, transposed ? 1 : 0, plan.flat_bn, B, d_pre, nullptr);
+                int total = 0;
+                for (int b = 0; b < B; ++b) {
+                    const int cols = lens[b] * lm.mul + lm.add + (transposed ? 1 : 0);
+                    total += cols > 0 ? (cols + plan.flat_bn - 1) / plan.flat_bn : 0;
                 }
+                a.tile_prefix = d_pre;
+                a.flat_ny = (rows + 127) / 128;
+                a.flat_B = B;
+                a.flat_tiles_host = total;
+                a.flat_bn_host = plan.flat_bn;
             }
             if (pre) {
-                KX_REQUIRE(BM == 128 && a.K >= 2 && a.act != kx::ACT_SNAKE && kx::conv16_da_eligible(BM, a.K, a.dil, a.stride, 0),
-                           "test_conv1d: this layer has no pre-split form");
+                KX_REQUIRE(plan.pre, "test_conv1d: this layer has no pre-split form");
                 const long img_bs = (long)kx::conv16_pre_image_bytes(Cin, x_ld);
                 unsigned char* img = dm.get<unsigned char>((size_t)B * img_bs);
                 KX_HIP(hipMemset(img, 0xff, (size_t)B * img_bs));  // (NaN halves wherever the pass does not write)
@@ -270,10 +282,8 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
                 a.x16_bs = img_bs;
                 a.x16_ld = x_ld;
             }
-            kx::launch_conv1d_f16x3(a, BM, B, max_cols, nullptr);
-        } else {
-            kx::launch_conv1d(a, BM, B, transposed ? L + 1 : Lout, nullptr);
         }
+        kx::launch_conv(plan, a, B, nullptr);
         KX_HIP(hipDeviceSynchronize());
         if (ex.pad_ld) {
             std::vector<float> yp((size_t)B * Cout * y_ld);
@@ -288,7 +298,7 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         if (ex.stats_out) {
             std::vector<float2> part((size_t)B * rows * a.stat_tiles);
             KX_HIP(hipMemcpy(part.data(), d_part, part.size() * sizeof(float2), hipMemcpyDeviceToHost));
-            const int used = (Lout + cols_per_tile - 1) / cols_per_tile;
+            const int used = (Lout + plan.stat_cols - 1) / plan.stat_cols;
             for (size_t br = 0; br < (size_t)B * rows; ++br) {
                 double sm = 0.0, sq = 0.0;
                 for (int t = 0; t < used && t < a.stat_tiles; ++t) {
@@ -352,6 +362,26 @@ int kx_test_conv1d_full(int device_id, const float* x, int B, int Cin, int L, co
     const int Lout = L + 2 * pad - dil * (k - 1);
     return test_conv1d_impl(device_id, x, B, Cin, L, w, bias, Cout, k, 1, pad, dil, 0, act, slope, alpha, norm, y, Lout, mode, ex,
                             err, err_len);
+}
+
+int kx_test_conv_plan(const int64_t* in, int n_in, int64_t* out, int n_out, char* err, size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        KX_REQUIRE(in && out && n_in == 25 && n_out == 17, "test_conv_plan: 25 launch fields in, 17 plan fields out");
+        kx::ConvLaunch c{};
+        int* f[] = {&c.mode, &c.prec1, &c.f8, &c.BM, &c.rows, &c.n_chunks16, &c.K, &c.dil, &c.stride, &c.pad, &c.act, &c.in_up2,
+                    &c.store, &c.accum, &c.epi, &c.norm, &c.stats, &c.image, &c.merge_T};
+        for (int i = 0; i < 19; ++i) *f[i] = (int)in[i];
+        c.x_bs = (long)in[19];
+        c.x_ld = (int)in[20];
+        c.B = (int)in[21];
+        c.cols = (int)in[22];
+        c.cus = (int)in[23];
+        c.force = (int)in[24];
+        const kx::ConvPlan p = kx::conv_plan(c);
+        const int v[] = {p.form, p.bm, p.act, p.kt, p.wm, p.wn, p.vt, p.pf, p.p1, p.bf, p.bn, p.cols, p.merged, p.pre, p.stat_cols,
+                         p.stat_tiles, p.flat_bn};
+        for (int i = 0; i < 17; ++i) out[i] = v[i];
+    });
 }
 
 int kx_test_lstm(int device_id, const float* x, int B, int L, int n_in, const float* w_ih, const float* w_hh,

@@ -157,6 +157,7 @@ def load_test_library() -> C.CDLL:
         "kx_test_conv1d_epilogue": (i32, [i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, i32, f32, f32, vp, vp,
                                           i32, cp, sz]),
         "kx_test_lstm_parts": (i32, [i32]),
+        "kx_test_conv_plan": (i32, [vp, i32, vp, i32, cp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -167,7 +168,7 @@ def load_test_library() -> C.CDLL:
 
 
 TEST_ABI_SYMBOLS = ["kx_test_conv1d", "kx_test_lstm", "kx_test_source", "kx_test_attention", "kx_test_conv1d_epilogue", "kx_test_conv1d_full",
-                    "kx_test_conv_transpose", "kx_test_lstm_fault", "kx_test_lstm_parts"]
+                    "kx_test_conv_transpose", "kx_test_lstm_fault", "kx_test_lstm_parts", "kx_test_conv_plan"]
 
 ABI_SYMBOLS = [
     "kx_version", "kx_init", "kx_create", "kx_import_onnx", "kx_create_from_device_blob", "kx_create_replicas", "kx_replicas_times", "kx_create_partition", "kx_destroy",
@@ -633,6 +634,28 @@ def conv1d(x, w, bias=None, stride=1, pad=0, dil=1, transposed=False, act=0, slo
     _err_call(lib.kx_test_conv1d, device, _ptr(x), B, Cin, L, _ptr(w), _ptr(bias), Cout, k, stride, pad, dil,
               1 if transposed else 0, act, float(slope), _ptr(alpha), _ptr(norm), _ptr(y), Lout, mode | (0x100 if pre else 0))
     return y
+
+
+# kx::ConvLaunch and kx::ConvPlan (kokorox_amd/csrc/kx_common.h), field by field in declaration order
+CONV_LAUNCH_FIELDS = ("mode", "prec1", "f8", "BM", "rows", "n_chunks16", "K", "dil", "stride", "pad", "act", "in_up2", "store", "accum",
+                      "epi", "norm", "stats", "image", "merge_T", "x_bs", "x_ld", "B", "cols", "cus", "force")
+CONV_PLAN_FIELDS = ("form", "bm", "act", "kt", "wm", "wn", "vt", "pf", "p1", "bf", "bn", "cols", "merged", "pre", "stat_cols",
+                    "stat_tiles", "flat_bn")
+CONV_FORMS = ("F32", "LDS", "DAG", "DAGN", "DA", "DA_W2", "DA_S16", "DA_F8", "DA_PRE", "DAPN")  # kx::ConvForm
+
+
+def conv_plan(**launch):
+    """The launch plan of one conv (conv_plan.hip) for the kx::ConvLaunch fields given (the others 0), computed on the host: a
+    dict of the kx::ConvPlan fields, with "form" as its ConvForm name.  Needs no GPU."""
+    lib = load_test_library()
+    unknown = set(launch) - set(CONV_LAUNCH_FIELDS)
+    assert not unknown, unknown
+    src = np.array([int(launch.get(f, 0)) for f in CONV_LAUNCH_FIELDS], dtype=np.int64)
+    out = np.zeros(len(CONV_PLAN_FIELDS), dtype=np.int64)
+    _err_call(lib.kx_test_conv_plan, _ptr(src), len(src), _ptr(out), len(out))
+    plan = dict(zip(CONV_PLAN_FIELDS, (int(v) for v in out)))
+    plan["form"] = CONV_FORMS[plan["form"]]
+    return plan
 
 
 def conv_transpose(x, w, bias=None, stride=6, act=1, slope=0.1, resid=None, up_off=0, mode=1, pre=False, device=0):

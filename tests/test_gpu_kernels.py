@@ -237,7 +237,7 @@ def _sweep_cases(n, seed):
     """Random conv shapes concentrated on tile borders: columns around multiples of 128 / 256, output channels
     around the 32 / 64 / 128-row tiles, every kernel width and dilation the graph uses, with and without the fused
     AdaIN affine + leaky / snake input transform (act 2 with k = 11 and an even number of 16-channel chunks is the
-    16x16x32 form of the direct-A kernel, conv16_da_s16_shape)."""
+    16x16x32 form of the direct-A kernel: conv_plan.hip, s16_shape)."""
     rng = np.random.default_rng(seed)
     cases = []
     for _ in range(n):
@@ -293,7 +293,7 @@ def test_conv1d_tile_border_sweep(B, Cin, Cout, L, k, p, d, act):
 
 
 def _s16_border_cases():
-    """The 16x16x32 form's predicate (conv_f16x3_da.hip, conv16_da_s16_shape: snake, 11 taps, (k-1) dil <= 64, an even
+    """The 16x16x32 form's predicate (conv_plan.hip, s16_shape: snake, 11 taps, (k-1) dil <= 64, an even
     number >= 2 of 16-channel chunks, 128-row weight tiles) admits partial chunks (Cin 17..32, 49..64), Cout != n 128 and
     any length: every (Cin, Cout) pair of the lists below meets every length once over the three dilations."""
     cins, couts, lens, dils = [24, 32, 56, 128], [22, 128, 130, 256], [1, 63, 65, 191, 193, 257, 517], [1, 3, 5]
@@ -592,33 +592,23 @@ def test_direct_a_kernel_is_bit_identical_under_load(B, Cin, Cout, L, k, d):
 
 
 @pytest.mark.gpu
-def test_direct_a_4x1_layout_of_the_256_column_tile_is_still_bit_identical():
+def test_direct_a_4x1_layout_of_the_256_column_tile_by_hook_mode_is_still_bit_identical():
     """The 256-column tile's unrolled forms default to the 2 x 2 wave layout (conv_f16x3_da_w2.hip), which the test above
-    exercises; the 4 x 1 forms stay in the library (KX_DA_W2=0, read once per process, hence the child process) as the A/B
+    exercises; the 4 x 1 forms stay in the library (hook mode bit 0x400: the 4 x 1 layout on the 256-column tile too) as the A/B
     reference and must keep producing the same bits: mode 3 against the LDS-DMA kernel (mode 2) for 7 and 11 taps."""
-    import subprocess
-    import sys
-    code = (
-        "import numpy as np\n"
-        "from kokorox_amd import hip_koko as hk\n"
-        "rng = np.random.default_rng(3)\n"
-        "for (B, C, L, k, d) in ((4, 128, 16000, 11, 3), (4, 256, 5000, 7, 1)):\n"
-        "    x = rng.standard_normal((B, C, L), dtype=np.float32)\n"
-        "    w = (rng.standard_normal((C, C, k), dtype=np.float32) / np.sqrt(C * k)).astype(np.float32)\n"
-        "    b = rng.standard_normal(C, dtype=np.float32)\n"
-        "    alpha = (0.5 + rng.random(C)).astype(np.float32)\n"
-        "    norm = rng.standard_normal((B, 3, C), dtype=np.float32)\n"
-        "    kw = dict(pad=d * (k - 1) // 2, dil=d, act=2, alpha=alpha, norm=norm)\n"
-        "    y2 = hk.conv1d(x, w, b, mode=2, **kw)\n"
-        "    y3 = hk.conv1d(x, w, b, mode=3, **kw)\n"
-        "    assert np.isfinite(y3).all() and np.array_equal(y2, y3), (k, float(np.abs(y2 - y3).max()))\n"
-        "print('same bits')\n")
-    import os
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    # (KX_DA_S16=0: the 11-tap case would otherwise take the 16x16x32 form, which is not bit-identical by construction)
-    r = subprocess.run([sys.executable, "-c", code], cwd=root, env=dict(os.environ, KX_DA_W2="0", KX_DA_S16="0"), capture_output=True,
-                       text=True, timeout=600)
-    assert r.returncode == 0 and "same bits" in r.stdout, r.stderr[-2000:]
+    from kokorox_amd import hip_koko as hk
+    rng = np.random.default_rng(3)
+    for (B, C, L, k, d) in ((4, 128, 16000, 11, 3), (4, 256, 5000, 7, 1)):
+        x = rng.standard_normal((B, C, L), dtype=np.float32)
+        w = (rng.standard_normal((C, C, k), dtype=np.float32) / np.sqrt(C * k)).astype(np.float32)
+        b = rng.standard_normal(C, dtype=np.float32)
+        alpha = (0.5 + rng.random(C)).astype(np.float32)
+        norm = rng.standard_normal((B, 3, C), dtype=np.float32)
+        kw = dict(pad=d * (k - 1) // 2, dil=d, act=2, alpha=alpha, norm=norm)
+        y2 = hk.conv1d(x, w, b, mode=2, **kw)
+        # (bit 0x800, no 16x16x32 form: the 11-tap case would otherwise take it, which is not bit-identical by construction)
+        y3 = hk.conv1d(x, w, b, mode=3 | 0x400 | 0x800, **kw)
+        assert np.isfinite(y3).all() and np.array_equal(y2, y3), (k, float(np.abs(y2 - y3).max()))
 
 
 @pytest.mark.gpu
