@@ -48,6 +48,34 @@ int kx_test_conv1d_full(int device_id, const float* x, int B, int Cin, int L, co
                         const float* alpha, const float* norm, const float* resid, int accumulate, float out_mul,
                         float out_div, float* y, float* stats_out, int mode, char* err, size_t err_len);
 
+/* kx_test_conv1d_full plus what Model::conv sets on top of it.  opts[8] = in_up2 (the conv reads x[p >> 1]: x [B,Cin,L] stands for
+ * 2 L columns, lens[] are stored lengths), epi (kx::ConvEpi: 1 = gelu_new), merged (offer the plan ConvLaunch::merge_T = L as the
+ * model does for every conv whose input and output share one plain length array; the plan decides, ConvArgs::merge_T / merge_B
+ * follow it), tmajor (ST_TMAJOR: y is [B,Lout,Cout]; with pad_ld & 1 its rows of Cout values end in a checked margin), prec1 (0, or
+ * 1 / 2 = one f16 / bf16 MFMA per product, 2 on the bf16 weight image built as Model::set_conv_mode builds it), act_shift
+ * (x_prescale = 2^act_shift, w_unscale its inverse, as kx_set_act_prescale sets them), epi_stream (ConvArgs::epi_stream), up_stride
+ * (s > 0: the polyphase transposed conv of kx_test_conv_transpose instead, w [Cin,Cout,2 s], dense rows, Lout = (L-1) s - 2 (s/2) + 2 s).
+ * norm_gb [B,2 Cout] (gamma | beta) with norm_out [3,B,Cout]: the conv's own fused partial sums go through launch_stats_finalize
+ * and come back as the next conv's (mean, scale, shift) planes.  plan_out[17]: the kx::ConvPlan that was launched, fields as in
+ * kx_test_conv_plan.  Lout = (in_up2 ? 2 L : L) + 2 pad - dil (k-1). */
+int kx_test_conv1d_opts(int device_id, const float* x, int B, int Cin, int L, const int32_t* lens, int pad_ld, const float* w,
+                        const float* bias, int Cout, int k, int pad, int dil, int act, float slope, const float* alpha,
+                        const float* norm, const float* resid, int accumulate, float out_mul, float out_div, float* y,
+                        float* stats_out, int mode, const int32_t* opts, int n_opts, const float* norm_gb, float* norm_out,
+                        int64_t* plan_out, char* err, size_t err_len);
+
+/* Stand-alone channel layer norm (launch_layernorm_ch) of x [B,C,T] over C, on rows padded to 32 floats (input padding NaN, output
+ * padding checked): mode 0 plain, 1 affine (g, be [C]), 2 adaptive ((1 + g) xhat + be, g, be [B,C]); leaky != 0: leaky ReLU on the
+ * result.  y [B,C,T]: columns >= lens[b] come back as -12345.5 (never written). */
+int kx_test_layernorm(int device_id, const float* x, int B, int C, int T, const int32_t* lens, float eps, int mode, const float* g,
+                      const float* be, float leaky, float* y, char* err, size_t err_len);
+
+/* Stand-alone InstanceNorm statistics of x [B,C,L] (padded rows, NaN padding), gb [B,2 C] (gamma | beta) -> out [3,3,B,C]:
+ * (mean, scale = (1 + gamma) rstd, shift = beta) from launch_in_stats alone, from launch_in_stats that also leaves its raw sums, and
+ * from those raw sums through launch_stats_finalize. */
+int kx_test_instance_norm(int device_id, const float* x, int B, int C, int L, const int32_t* lens, const float* gb, float* out,
+                          char* err, size_t err_len);
+
 /* The launch plan of one conv (kokorox_amd/csrc/conv_plan.hip: kernel form, tile, statistics slots, flat tile list, pre-split
  * input), computed on the host without a device.  in[25] = the fields of kx::ConvLaunch in declaration order (mode, prec1, f8, BM,
  * rows, n_chunks16, K, dil, stride, pad, act, in_up2, store, accum, epi, norm, stats, image, merge_T, x_bs, x_ld, B, cols, cus,

@@ -165,6 +165,7 @@ static void launch_inst(const ConvArgs& a, int B, int max_cols, hipStream_t s) {
 
 void launch_conv1d(const ConvArgs& a, int BM, int B, int max_cols, hipStream_t s) {
     KX_REQUIRE(a.n_chunks == (a.Cin + CONV_CK - 1) / CONV_CK, "conv1d: n_chunks mismatch");
+    KX_REQUIRE(a.epi != EPI_GELU_NEW || BM == 128, "conv1d: gelu epilogue exists only for 128-row weight tiles");
     if (max_cols <= 0) return;
     if (BM == 128)
         launch_inst<128, 128, 2, 2>(a, B, max_cols, s);

@@ -381,7 +381,9 @@ __global__ __launch_bounds__(64) void stats_finalize_kernel(const float2* part, 
                                                             float* scale, float* shift, int n_bs) {
     const int c = blockIdx.x, b = blockIdx.y;
     const int L = len_of(len, b);
-    const int used = ((L + cols_per_tile - 1) / cols_per_tile);  // slots written by workgroups that did not exit early
+    // slots written by workgroups that did not exit early; STAT_RAW_TILES: the tiles are the parts of ONE pair of sums (in_stats_kernel's
+    // raw_out), all of them count whatever the length (counted by columns, a row of one column lost the low parts of its sums)
+    const int used = cols_per_tile == STAT_RAW_TILES ? tiles : ((L + cols_per_tile - 1) / cols_per_tile);
     const float2* p = part + ((long)b * C + c) * tiles;
     double s = 0.0, q = 0.0;
     for (int i = threadIdx.x; i < used && i < tiles; i += 64) {

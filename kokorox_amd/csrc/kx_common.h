@@ -274,6 +274,8 @@ void launch_style_fc(const FcDesc* d_desc, int n_desc, const float* styles, floa
 
 // instance-norm statistics of [B][C][ld] rows -> mean, scale = rstd*(1+gamma), shift = beta
 // finalize fused statistics: partials [B][C][tiles] -> mean, scale, shift (same outputs as launch_in_stats)
+// cols_per_tile = STAT_RAW_TILES: the tiles are the high and low parts of launch_in_stats' raw_out, summed whatever the length
+constexpr int STAT_RAW_TILES = 0;
 void launch_stats_finalize(const float2* part, int tiles, int cols_per_tile, int C, LenMap len, int B, const float* gb,
                            long gb_bs, float* mean, float* scale, float* shift, int n_bs, hipStream_t s);
 void launch_in_stats(const float* x, long bs, int ld, int C, LenMap len, int B, const float* gb, long gb_bs,

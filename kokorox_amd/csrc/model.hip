@@ -846,8 +846,8 @@ void Model::stats(const T& x, const std::string& fc_key) {
     }
     launch_in_stats(x.p, x.bs, x.ld, x.C, x.len, B_, gb_ + fc_off(fc_key), gb_total_, nmean_, nscale_, nshift_, n_bs_,
                     raw, stream_);
-    // (two "tiles" of one column each: the high and the low part of the f64 sums)
-    if (raw) parts_[x.p] = PartInfo{raw, 2, 1, x.C};
+    // (two "tiles": the high and the low part of the f64 sums, both read back whatever the length)
+    if (raw) parts_[x.p] = PartInfo{raw, 2, STAT_RAW_TILES, x.C};
 }
 
 void Model::tap(const char* name, const T& t) {

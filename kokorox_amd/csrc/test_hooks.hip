@@ -79,6 +79,17 @@ struct ConvTestExtra {  // epilogue forms beyond bias: residual, accumulate into
     int pad_ld = 0;              // rows padded to a multiple of 32 floats as in the model (x padding = NaN, y padding checked)
     int flat = 0;                // ragged batches: the flat tile list the model gives the direct-A kernels (ConvArgs::tile_prefix)
     int up_off = 0, up_reflect = 0;  // transposed: the output starts at column up_off of y (and column 0 = reflection of column 1)
+    // what Model::conv sets beyond that (kx_test_conv1d_opts)
+    int in_up2 = 0;              // the conv reads x[p >> 1]: L stored columns stand for 2 L
+    int epi = kx::EPI_NONE;
+    int merged = 0;              // offer the plan one merged column space for the batch (ConvLaunch::merge_T), as Model::conv does
+    int tmajor = 0;              // ST_TMAJOR: y is [B][Lout][Cout]
+    int prec1 = 0;               // 1 / 2: one f16 / bf16 MFMA per product (2: on the bf16 image Model::set_conv_mode builds)
+    int act_shift = 0;           // x_prescale = 2^act_shift, w_unscale carries its inverse
+    int epi_stream = 0;
+    const float* norm_gb = nullptr;  // [B][2 Cout] (gamma | beta): finalize the conv's own partial sums into ...
+    float* norm_out = nullptr;       // ... [3][B][Cout] = mean, scale, shift (launch_stats_finalize)
+    int64_t* plan_out = nullptr;     // [17] the ConvPlan that was launched, fields as kx_test_conv_plan returns them
 };
 }  // namespace
 
@@ -106,7 +117,17 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         // row strides: the caller's dense rows, or (pad_ld) the model's: a multiple of 32 floats, input padding poisoned
         const int Ly = Lout + ex.up_off;  // columns of y (Lout: the conv's own output length)
         KX_REQUIRE(ex.up_off == 0 || (transposed && ex.up_off == 1 && !ex.pad_ld), "test_conv1d: an output offset comes with transposed convs");
-        const int x_ld = ex.pad_ld ? (L + 31) & ~31 : L, y_ld = ex.pad_ld ? (Lout + 31) & ~31 : Ly;
+        // (time-major stores: a row of y is one column's Cout values; padded, it ends in a 32-float margin)
+        const int yr = ex.tmajor ? Lout : Cout, yc = ex.tmajor ? Cout : Lout;  // rows per utterance and columns of y as stored
+        const int x_ld = ex.pad_ld ? (L + 31) & ~31 : L;
+        const int y_ld = ex.tmajor ? (ex.pad_ld ? ((Cout + 31) & ~31) + 32 : Cout) : (ex.pad_ld ? (Lout + 31) & ~31 : Ly);
+        const int Lv = ex.in_up2 ? 2 * L : L;  // the input length the conv sees
+        const bool want_stats = ex.stats_out != nullptr || ex.norm_out != nullptr;
+        KX_REQUIRE(!ex.tmajor || (!transposed && !ex.resid && !ex.accum && !want_stats), "test_conv1d: time-major stores are plain stores");
+        KX_REQUIRE(!ex.in_up2 || !transposed, "test_conv1d: in_up2 with plain convs only");
+        KX_REQUIRE(!ex.merged || (!transposed && Lout == L), "test_conv1d: merged columns need input and output of one length");
+        KX_REQUIRE((ex.norm_out != nullptr) == (ex.norm_gb != nullptr), "test_conv1d: norm planes come with gamma / beta");
+        KX_REQUIRE(ex.act_shift >= -24 && ex.act_shift <= 24 && ex.prec1 >= 0 && ex.prec1 <= 2, "test_conv1d: bad act_shift / prec1");
         const float poison = std::nanf(""), sentinel = -12345.5f;
         auto padded = [&](const float* src, int rows_total, int len, int ld, float fill) {
             std::vector<float> v((size_t)rows_total * ld, fill);
@@ -121,16 +142,21 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         a.x_bs = (long)Cin * x_ld;
         a.x_ld = x_ld;
         a.Cin = Cin;
-        if (ex.lens) {  // ragged batch: utterance b is lens[b] columns long (stride-1 convs: the output shrinks by L - Lout)
+        const int up = ex.in_up2 ? 2 : 1;
+        // (the merged kernels read the length array itself: a merged launch always carries real lengths)
+        const bool ragged = ex.lens != nullptr || ex.merged;
+        if (ex.lens) {  // ragged batch: utterance b is lens[b] columns long (stride-1 convs: the output shrinks by Lv - Lout)
             KX_REQUIRE(!transposed && stride == 1, "test_conv1d: ragged lengths with stride-1 convs only");
             for (int b = 0; b < B; ++b) {
-                KX_REQUIRE(ex.lens[b] >= 1 && ex.lens[b] <= L && ex.lens[b] + (Lout - L) >= 1, "test_conv1d: lens out of range");
+                KX_REQUIRE(ex.lens[b] >= 1 && ex.lens[b] <= L && up * ex.lens[b] + (Lout - Lv) >= 1, "test_conv1d: lens out of range");
                 lens[b] = ex.lens[b];
             }
-        }
+        } else if (ex.merged)
+            lens.assign(B, L);
         int* d_one = dm.up(lens.data(), B);
-        a.in_len = ex.lens ? kx::LenMap{d_one, 1, 0} : kx::LenMap{d_one, 0, L};
-        a.out_len = ex.lens ? kx::LenMap{d_one, 1, Lout - L} : kx::LenMap{d_one, 0, Lout};
+        a.in_len = ragged ? kx::LenMap{d_one, up, 0} : kx::LenMap{d_one, 0, Lv};
+        a.out_len = ragged ? kx::LenMap{d_one, up, Lout - Lv} : kx::LenMap{d_one, 0, Lout};
+        a.in_up2 = ex.in_up2;
         a.n_chunks = (Cin + kx::CONV_CK - 1) / kx::CONV_CK;
         const float* dw = dm.up(w, (size_t)Cout * Cin * k);
         int BM, rows;
@@ -145,7 +171,7 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
             a.stride = stride;
             a.pad = pad;
             a.dil = dil;
-            a.store = kx::ST_NORMAL;
+            a.store = ex.tmajor ? kx::ST_TMAJOR : kx::ST_NORMAL;
             a.up_cout = 1;
         } else {
             KX_REQUIRE(k == 2 * stride && pad == (k - stride) / 2 && dil == 1, "test_conv1d: transposed needs k=2s, pad=(k-s)/2");
@@ -178,18 +204,20 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         a.slope = slope;
         a.alpha = alpha ? dm.up(alpha, (size_t)Cin) : nullptr;
         KX_REQUIRE(act != kx::ACT_SNAKE || alpha, "test_conv1d: snake needs alpha");
-        float* dy = dm.get<float>((size_t)B * Cout * y_ld);
+        float* dy = dm.get<float>((size_t)B * yr * y_ld);
         if (ex.pad_ld) {  // y holds the running sum (accumulate) or zeros; the row padding holds a sentinel nobody may touch
-            std::vector<float> y0((size_t)B * Cout * Lout, 0.f);
-            const std::vector<float> yp = padded(ex.accum ? y : y0.data(), B * Cout, Lout, y_ld, sentinel);
+            std::vector<float> y0((size_t)B * yr * yc, 0.f);
+            const std::vector<float> yp = padded(ex.accum ? y : y0.data(), B * yr, yc, y_ld, sentinel);
             KX_HIP(hipMemcpy(dy, yp.data(), yp.size() * 4, hipMemcpyHostToDevice));
         } else if (ex.accum)
             KX_HIP(hipMemcpy(dy, y, (size_t)B * Cout * Lout * 4, hipMemcpyHostToDevice));  // y holds the running sum
         else
-            KX_HIP(hipMemset(dy, 0, (size_t)B * Cout * Ly * 4));
+            KX_HIP(hipMemset(dy, 0, (size_t)B * yr * y_ld * 4));
         a.y = dy;
-        a.y_bs = (long)Cout * y_ld;
+        a.y_bs = (long)yr * y_ld;
         a.y_ld = y_ld;
+        a.epi = ex.epi;
+        a.epi_stream = ex.epi_stream;
         a.out_mul = ex.out_mul;
         a.out_div = ex.out_div;
         a.accum = ex.accum;
@@ -218,8 +246,12 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         c.norm = norm != nullptr;
         c.store = a.store;
         c.accum = ex.accum;
-        c.stats = ex.stats_out != nullptr;
+        c.stats = want_stats;
         c.image = pre ? 2 : 0;
+        c.prec1 = ex.prec1;
+        c.in_up2 = ex.in_up2;
+        c.epi = ex.epi;
+        c.merge_T = ex.merged ? L : 0;  // (Model::conv: input and output share one plain length array)
         c.x_bs = a.x_bs;
         c.x_ld = x_ld;
         c.B = B;
@@ -227,8 +259,17 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         c.cus = mode == kx::CONV_F32 ? 0 : kx::conv16_cu_count();
         c.force = a.ws_force;
         const kx::ConvPlan plan = kx::conv_plan(c);
+        if (ex.plan_out) {
+            const int v[] = {plan.form, plan.bm, plan.act, plan.kt, plan.wm, plan.wn, plan.vt, plan.pf, plan.p1, plan.bf, plan.bn, plan.cols,
+                             plan.merged, plan.pre, plan.stat_cols, plan.stat_tiles, plan.flat_bn};
+            for (int i = 0; i < 17; ++i) ex.plan_out[i] = v[i];
+        }
+        if (plan.merged) {
+            a.merge_T = L;
+            a.merge_B = B;
+        }
         float2* d_part = nullptr;
-        if (ex.stats_out) {
+        if (want_stats) {
             KX_REQUIRE(!transposed && !ex.accum && plan.stat_cols > 0, "test_conv1d: fused statistics come with plain, non-accumulating stores");
             a.stat_tiles = plan.stat_tiles;
             d_part = dm.get<float2>((size_t)B * rows * a.stat_tiles);
@@ -254,8 +295,16 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
                 a.w8x = p8;
             }
             a.n_chunks16 = (Cin + 15) / 16;
-            a.w_unscale = std::ldexp(1.0f, -ws);
-            a.x_prescale = 1.0f;
+            a.prec1 = ex.prec1;
+            if (ex.prec1 == 2) {  // the bf16 form of the image, as Model::set_conv_mode builds it
+                KX_REQUIRE(BM == 128, "test_conv1d: bf16 images exist for 128-row tiles");
+                const size_t nh = kx::packed_conv16_halves(rows, Cin, Kp, BM);
+                void* pb = dm.get<unsigned short>(nh);
+                kx::launch_image_to_bf16(p16, pb, nh, nullptr);
+                a.w16b = pb;
+            }
+            a.x_prescale = std::ldexp(1.0f, ex.act_shift);
+            a.w_unscale = std::ldexp(std::ldexp(1.0f, -ws), -ex.act_shift);  // (Model::conv: exact, both are powers of two)
             a.xcd_swizzle = 1;
             if (ex.flat && plan.flat_bn) {
                 const kx::LenMap lm = transposed ? a.in_len : a.out_len;
@@ -286,15 +335,23 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         kx::launch_conv(plan, a, B, nullptr);
         KX_HIP(hipDeviceSynchronize());
         if (ex.pad_ld) {
-            std::vector<float> yp((size_t)B * Cout * y_ld);
+            std::vector<float> yp((size_t)B * yr * y_ld);
             KX_HIP(hipMemcpy(yp.data(), dy, yp.size() * 4, hipMemcpyDeviceToHost));
-            for (int r = 0; r < B * Cout; ++r) {
-                std::memcpy(y + (size_t)r * Lout, &yp[(size_t)r * y_ld], (size_t)Lout * 4);
-                for (int c = Lout; c < y_ld; ++c)
+            for (int r = 0; r < B * yr; ++r) {
+                std::memcpy(y + (size_t)r * yc, &yp[(size_t)r * y_ld], (size_t)yc * 4);
+                for (int c = yc; c < y_ld; ++c)
                     if (yp[(size_t)r * y_ld + c] != sentinel) throw Error(KX_ERR_STATE, "test_conv1d: the kernel wrote into the row padding");
             }
         } else
-            KX_HIP(hipMemcpy(y, dy, (size_t)B * Cout * Ly * 4, hipMemcpyDeviceToHost));
+            KX_HIP(hipMemcpy(y, dy, (size_t)B * yr * y_ld * 4, hipMemcpyDeviceToHost));
+        if (ex.norm_out) {  // the model's route from the partial sums to the next conv's AdaIN planes (Model::stats)
+            const float* d_gb = dm.up(ex.norm_gb, (size_t)B * 2 * rows);
+            float* d_pl = dm.get<float>((size_t)3 * B * rows);
+            kx::launch_stats_finalize(d_part, a.stat_tiles, plan.stat_cols, rows, a.out_len, B, d_gb, 2L * rows, d_pl, d_pl + (size_t)B * rows,
+                                      d_pl + (size_t)2 * B * rows, rows, nullptr);
+            KX_HIP(hipDeviceSynchronize());
+            KX_HIP(hipMemcpy(ex.norm_out, d_pl, (size_t)3 * B * rows * 4, hipMemcpyDeviceToHost));
+        }
         if (ex.stats_out) {
             std::vector<float2> part((size_t)B * rows * a.stat_tiles);
             KX_HIP(hipMemcpy(part.data(), d_part, part.size() * sizeof(float2), hipMemcpyDeviceToHost));
@@ -362,6 +419,101 @@ int kx_test_conv1d_full(int device_id, const float* x, int B, int Cin, int L, co
     const int Lout = L + 2 * pad - dil * (k - 1);
     return test_conv1d_impl(device_id, x, B, Cin, L, w, bias, Cout, k, 1, pad, dil, 0, act, slope, alpha, norm, y, Lout, mode, ex,
                             err, err_len);
+}
+
+int kx_test_conv1d_opts(int device_id, const float* x, int B, int Cin, int L, const int32_t* lens, int pad_ld, const float* w,
+                        const float* bias, int Cout, int k, int pad, int dil, int act, float slope, const float* alpha,
+                        const float* norm, const float* resid, int accumulate, float out_mul, float out_div, float* y,
+                        float* stats_out, int mode, const int32_t* opts, int n_opts, const float* norm_gb, float* norm_out,
+                        int64_t* plan_out, char* err, size_t err_len) {
+    ConvTestExtra ex;
+    if (!opts || n_opts != 8 || !plan_out || opts[7] < 0)
+        return guarded_free(err, err_len, [] { throw Error(KX_ERR_INVALID, "test_conv1d_opts: 8 options in, 17 plan fields out"); });
+    ex.resid = resid;
+    ex.accum = accumulate;
+    ex.out_mul = out_mul;
+    ex.out_div = out_div;
+    ex.stats_out = stats_out;
+    ex.lens = lens;
+    ex.pad_ld = pad_ld & 1;
+    ex.flat = (pad_ld >> 1) & 1;
+    ex.in_up2 = opts[0] != 0;
+    ex.epi = opts[1];
+    ex.merged = opts[2] != 0;
+    ex.tmajor = opts[3] != 0;
+    ex.prec1 = opts[4];
+    ex.act_shift = opts[5];
+    ex.epi_stream = opts[6] != 0;
+    ex.norm_gb = norm_gb;
+    ex.norm_out = norm_out;
+    ex.plan_out = plan_out;
+    if (const int s = opts[7]) {  // a polyphase transposed conv (kx_test_conv_transpose: k = 2 s, pad = s / 2, w [Cin,Cout,k]) with these options
+        const int pd = (k - s) / 2;
+        return test_conv1d_impl(device_id, x, B, Cin, L, w, bias, Cout, k, s, pd, 1, 1, act, slope, alpha, norm, y, (L - 1) * s - 2 * pd + k,
+                                mode, ex, err, err_len);
+    }
+    const int Lout = (ex.in_up2 ? 2 * L : L) + 2 * pad - dil * (k - 1);
+    return test_conv1d_impl(device_id, x, B, Cin, L, w, bias, Cout, k, 1, pad, dil, 0, act, slope, alpha, norm, y, Lout, mode, ex,
+                            err, err_len);
+}
+
+int kx_test_layernorm(int device_id, const float* x, int B, int C, int T, const int32_t* lens, float eps, int mode, const float* g,
+                      const float* be, float leaky, float* y, char* err, size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        check_device(device_id);
+        KX_REQUIRE(x && y && lens && B > 0 && C > 0 && T > 0 && mode >= kx::LN_PLAIN && mode <= kx::LN_ADA, "test_layernorm: bad argument");
+        KX_REQUIRE(mode == kx::LN_PLAIN || (g && be), "test_layernorm: the affine forms need gamma and beta");
+        for (int b = 0; b < B; ++b) KX_REQUIRE(lens[b] >= 1 && lens[b] <= T, "test_layernorm: lens out of range");
+        KX_HIP(hipSetDevice(device_id));
+        DevMem dm;
+        const int ld = (T + 31) & ~31;  // rows padded as in the model; the input padding is NaN, the output holds a sentinel throughout
+        const float sentinel = -12345.5f;
+        std::vector<float> xp((size_t)B * C * ld, std::nanf(""));
+        for (size_t r = 0; r < (size_t)B * C; ++r) std::memcpy(&xp[r * ld], x + r * T, (size_t)T * 4);
+        const float* dx = dm.up(xp.data(), xp.size());
+        std::vector<float> yp((size_t)B * C * ld, sentinel);
+        float* dy = dm.up(yp.data(), yp.size());
+        const int* d_len = dm.up(lens, B);
+        const size_t ng = mode == kx::LN_ADA ? (size_t)B * C : (size_t)C;
+        const float* dg = mode == kx::LN_PLAIN ? nullptr : dm.up(g, ng);
+        const float* db = mode == kx::LN_PLAIN ? nullptr : dm.up(be, ng);
+        kx::launch_layernorm_ch(dx, dy, (long)C * ld, ld, C, kx::LenMap{d_len, 1, 0}, B, T, eps, mode, dg, db, C, leaky, nullptr);
+        KX_HIP(hipDeviceSynchronize());
+        KX_HIP(hipMemcpy(yp.data(), dy, yp.size() * 4, hipMemcpyDeviceToHost));
+        for (size_t r = 0; r < (size_t)B * C; ++r) {
+            std::memcpy(y + r * T, &yp[r * ld], (size_t)T * 4);  // (columns past lens[b] come back as the sentinel: the caller checks them)
+            for (int c = T; c < ld; ++c)
+                if (yp[r * ld + c] != sentinel) throw Error(KX_ERR_STATE, "test_layernorm: the kernel wrote into the row padding");
+        }
+    });
+}
+
+int kx_test_instance_norm(int device_id, const float* x, int B, int C, int L, const int32_t* lens, const float* gb, float* out,
+                          char* err, size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        check_device(device_id);
+        KX_REQUIRE(x && lens && gb && out && B > 0 && C > 0 && L > 0, "test_instance_norm: bad argument");
+        for (int b = 0; b < B; ++b) KX_REQUIRE(lens[b] >= 1 && lens[b] <= L, "test_instance_norm: lens out of range");
+        KX_HIP(hipSetDevice(device_id));
+        DevMem dm;
+        const int ld = (L + 31) & ~31;
+        std::vector<float> xp((size_t)B * C * ld, std::nanf(""));
+        for (size_t r = 0; r < (size_t)B * C; ++r) std::memcpy(&xp[r * ld], x + r * L, (size_t)L * 4);
+        const float* dx = dm.up(xp.data(), xp.size());
+        const int* d_len = dm.up(lens, B);
+        const float* d_gb = dm.up(gb, (size_t)B * 2 * C);
+        const size_t n = (size_t)B * C;
+        float* pl = dm.get<float>(9 * n);
+        float2* raw = dm.get<float2>(2 * n);
+        const kx::LenMap lm{d_len, 1, 0};
+        // out[0]: the pass alone; out[1]: the pass that also leaves its raw sums (Model::stats, first AdaIN of a tensor); out[2]: those
+        // raw sums finalized (its later AdaINs)
+        kx::launch_in_stats(dx, (long)C * ld, ld, C, lm, B, d_gb, 2L * C, pl, pl + n, pl + 2 * n, C, nullptr, nullptr);
+        kx::launch_in_stats(dx, (long)C * ld, ld, C, lm, B, d_gb, 2L * C, pl + 3 * n, pl + 4 * n, pl + 5 * n, C, raw, nullptr);
+        kx::launch_stats_finalize(raw, 2, kx::STAT_RAW_TILES, C, lm, B, d_gb, 2L * C, pl + 6 * n, pl + 7 * n, pl + 8 * n, C, nullptr);
+        KX_HIP(hipDeviceSynchronize());
+        KX_HIP(hipMemcpy(out, pl, 9 * n * 4, hipMemcpyDeviceToHost));
+    });
 }
 
 int kx_test_conv_plan(const int64_t* in, int n_in, int64_t* out, int n_out, char* err, size_t err_len) {

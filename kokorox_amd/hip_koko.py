@@ -158,6 +158,10 @@ def load_test_library() -> C.CDLL:
                                           i32, cp, sz]),
         "kx_test_lstm_parts": (i32, [i32]),
         "kx_test_conv_plan": (i32, [vp, i32, vp, i32, cp, sz]),
+        "kx_test_conv1d_opts": (i32, [i32, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, i32, f32,
+                                      f32, vp, vp, i32, vp, i32, vp, vp, vp, cp, sz]),
+        "kx_test_layernorm": (i32, [i32, vp, i32, i32, i32, vp, f32, i32, vp, vp, f32, vp, cp, sz]),
+        "kx_test_instance_norm": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, cp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -168,7 +172,8 @@ def load_test_library() -> C.CDLL:
 
 
 TEST_ABI_SYMBOLS = ["kx_test_conv1d", "kx_test_lstm", "kx_test_source", "kx_test_attention", "kx_test_conv1d_epilogue", "kx_test_conv1d_full",
-                    "kx_test_conv_transpose", "kx_test_lstm_fault", "kx_test_lstm_parts", "kx_test_conv_plan"]
+                    "kx_test_conv_transpose", "kx_test_lstm_fault", "kx_test_lstm_parts", "kx_test_conv_plan", "kx_test_conv1d_opts",
+                    "kx_test_layernorm", "kx_test_instance_norm"]
 
 ABI_SYMBOLS = [
     "kx_version", "kx_init", "kx_create", "kx_import_onnx", "kx_create_from_device_blob", "kx_create_replicas", "kx_replicas_times", "kx_create_partition", "kx_destroy",
@@ -707,6 +712,75 @@ def conv1d_full(x, w, bias=None, pad=0, dil=1, act=0, slope=0.0, alpha=None, nor
               Cout, k, pad, dil, act, float(slope), _ptr(_f32(alpha)), _ptr(_f32(norm)), _ptr(_f32(resid)),
               0 if y_init is None else 1, float(out_mul), float(out_div), _ptr(y), _ptr(st), mode | (0x100 if pre else 0))
     return (y, st) if want_stats else y
+
+
+def conv1d_opts(x, w, bias=None, pad=0, dil=1, act=0, slope=0.0, alpha=None, norm=None, resid=None, y_init=None,
+                out_mul=1.0, out_div=1.0, want_stats=False, lens=None, pad_ld=False, flat=False, mode=1, device=0, pre=False,
+                in_up2=False, epi=0, merged=False, tmajor=False, prec1=0, act_shift=0, epi_stream=False, want_norm=None,
+                up_stride=0):
+    """conv1d_full plus the launch options Model::conv sets (include/kokorox_hip_test.h, kx_test_conv1d_opts): in_up2 (x [B,Cin,L]
+    read as 2 L columns), epi (1 = gelu_new), merged (the plan may merge the batch's columns), tmajor (y [B,Lout,Cout]), prec1,
+    act_shift, epi_stream, up_stride (s > 0: the polyphase transposed conv instead, w [Cin,Cout,2 s]); want_norm = gb [B,2 Cout]: the fused partial sums finalized into (mean, scale, shift) [3,B,Cout].
+    Returns a dict: y, plan (the ConvPlan that ran, as conv_plan returns it), and stats / norm when asked for."""
+    lib = load_test_library()
+    x, w = _f32(x), _f32(w)
+    B, Cin, L = x.shape
+    Cout, _, k = w.shape
+    Lout = (2 * L if in_up2 else L) + 2 * pad - dil * (k - 1)
+    if up_stride:
+        Cout = w.shape[1]
+        assert k == 2 * up_stride
+        Lout = (L - 1) * up_stride - 2 * ((k - up_stride) // 2) + k
+    shape = (B, Lout, Cout) if tmajor else (B, Cout, Lout)
+    y = np.zeros(shape, dtype=np.float32) if y_init is None else _f32(y_init).copy()
+    st = np.zeros((B, Cout, 2), dtype=np.float32) if want_stats else None
+    ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+    opts = np.array([in_up2, epi, merged, tmajor, prec1, act_shift, epi_stream, up_stride], dtype=np.int32)
+    gb = _f32(want_norm)
+    planes = None if gb is None else np.zeros((3, B, Cout), dtype=np.float32)
+    assert gb is None or gb.shape == (B, 2 * Cout)
+    plan = np.zeros(len(CONV_PLAN_FIELDS), dtype=np.int64)
+    _err_call(lib.kx_test_conv1d_opts, device, _ptr(x), B, Cin, L, _ptr(ln), (1 if pad_ld else 0) | (2 if flat else 0), _ptr(w),
+              _ptr(_f32(bias)), Cout, k, pad, dil, act, float(slope), _ptr(_f32(alpha)), _ptr(_f32(norm)), _ptr(_f32(resid)),
+              0 if y_init is None else 1, float(out_mul), float(out_div), _ptr(y), _ptr(st), mode | (0x100 if pre else 0), _ptr(opts),
+              len(opts), _ptr(gb), _ptr(planes), _ptr(plan))
+    pl = dict(zip(CONV_PLAN_FIELDS, (int(v) for v in plan)))
+    pl["form"] = CONV_FORMS[pl["form"]]
+    return {"y": y, "plan": pl, "stats": st, "norm": planes}
+
+
+LN_PLAIN, LN_AFFINE, LN_ADA = 0, 1, 2
+
+
+def layernorm(x, lens, eps=1e-5, mode=LN_PLAIN, g=None, be=None, leaky=0.0, device=0):
+    """Channel layer norm of x [B,C,T] over C (launch_layernorm_ch) on the model's padded rows.  g, be: [C] (LN_AFFINE) or [B,C]
+    (LN_ADA: (1 + g) xhat + be).  Columns >= lens[b] come back as LN_SENTINEL."""
+    lib = load_test_library()
+    x = _f32(x)
+    B, C, T = x.shape
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    g, be = _f32(g), _f32(be)
+    if mode != LN_PLAIN:
+        assert g.shape == be.shape == ((B, C) if mode == LN_ADA else (C,))
+    y = np.zeros((B, C, T), dtype=np.float32)
+    _err_call(lib.kx_test_layernorm, device, _ptr(x), B, C, T, _ptr(ln), float(eps), mode, _ptr(g), _ptr(be), float(leaky), _ptr(y))
+    return y
+
+
+LN_SENTINEL = np.float32(-12345.5)
+
+
+def instance_norm(x, lens, gb, device=0):
+    """InstanceNorm statistics of x [B,C,L] with gb [B,2 C] (gamma | beta) -> [3 routes, 3, B, C]: (mean, scale, shift) from
+    launch_in_stats alone, from launch_in_stats leaving raw sums, and from those raw sums through launch_stats_finalize."""
+    lib = load_test_library()
+    x, gb = _f32(x), _f32(gb)
+    B, C, L = x.shape
+    assert gb.shape == (B, 2 * C)
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    out = np.zeros((3, 3, B, C), dtype=np.float32)
+    _err_call(lib.kx_test_instance_norm, device, _ptr(x), B, C, L, _ptr(ln), _ptr(gb), _ptr(out))
+    return out
 
 
 def lstm(x, params, device=0):

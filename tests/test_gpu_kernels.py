@@ -90,7 +90,8 @@ def test_conv_transpose_polyphase(Cin, Cout, L, s, mode):
 
 @pytest.mark.parametrize("L,n_in", [(19, 72), (1, 640), (130, 512)])
 def test_bilstm(L, n_in):
-    """(the input projection runs on the f32 MFMA kernel in this hook)"""
+    """(the input projection runs on the f32 MFMA kernel in this hook; its time-major store on the f16x3 kernels a forward runs it on:
+    tests/test_gpu_conv_options.py, test_time_major_store_of_the_lstm_input_projection)"""
     from kokorox_amd import hip_koko as hk
     torch.manual_seed(L)
     m = torch.nn.LSTM(n_in, 256, 1, batch_first=True, bidirectional=True).double()
