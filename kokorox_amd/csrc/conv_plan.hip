@@ -1,7 +1,7 @@
 // The launch plan of a conv: which kernel form, tile, statistics slots, flat tile list and input staging a launch gets.  Decided
 // here once, on the host, from the layer's shape and options, the precision mode, the batch, the column count and the CU count;
-// Model::conv and the test hooks size their buffers from the plan and hand it to launch_conv (conv_f16x3.hip), whose launchers
-// carry it out.  No HIP calls: the plan is a pure function of its inputs (tests/test_conv_plan_cpu.py runs it without a GPU).
+// conv_call (conv_call.hip) fills its input and builds the kernel arguments to match; Model::conv and the test hooks size their
+// buffers from the plan and hand it to launch_conv (conv_f16x3.hip), whose launchers carry it out.  No HIP calls: the plan is a pure function of its inputs (tests/test_conv_plan_cpu.py runs it without a GPU).
 //
 // What decides an utterance's bits must not depend on the batch or the lengths: the MFMA family of a layer (the 16x16x32 forms
 // by shape alone), whether its input goes through a pre-split image (by shape alone) and the width of its statistics slots

@@ -1,6 +1,7 @@
 // Host-side model object behind the C ABI (include/kokorox_hip.h).
 #pragma once
 #include <atomic>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -90,6 +91,65 @@ struct ConvOpts {
     LenMap up_len{nullptr, 1, 0};  // ST_UPSCATTER: un-shifted output length
     float2* stat_part = nullptr;   // fuse InstanceNorm partial sums of the output into the epilogue
 };
+
+// ---- conv launch assembly (conv_call.hip): the weight images of a layer and the arguments of a launch, built in one place for
+// Model and for the kernel hooks of tests/ -------------------------------------------------------------------------------------
+using DevAlloc = std::function<void*(size_t bytes)>;  // device memory that lives as long as the weights (Model: owned_)
+// a complete ConvW (f32 pack, weight shift, split-f16 image; no bias) from canonical device weights: one to three
+// row-concatenated [rows_i][Cin][K] sources, or a ConvTranspose1d weight [Cin][Cout][2 stride] as a polyphase two-tap GEMM
+ConvW pack_conv(const PackSrc& src, int Cin, int K, hipStream_t s, const DevAlloc& alloc);
+ConvW pack_convT(const float* w, int Cin, int Cout, int stride, hipStream_t s, const DevAlloc& alloc);
+// the bf16 image (128-row tiles) / the 8-bit cross image (conv16_f8_layer shapes of plain convs), where the layer qualifies
+// and does not have it yet
+void add_bf16_image(ConvW& c, hipStream_t s, const DevAlloc& alloc);
+void add_f8_image(ConvW& c, hipStream_t s, const DevAlloc& alloc);
+
+struct ConvCtx {  // what a conv launch takes from its caller beyond layer, tensors and options
+    int mode = CONV_F16F8;   // ConvMode
+    bool p1_region = false;  // inside the part of the forward whose direct-A convs may run reduced precision (CONV_F16 / CONV_BF16)
+    int B = 0;
+    int cus = 0;             // ConvLaunch::cus
+    int n_bs = 0;            // row stride of the AdaIN parameter planes
+    // the test hooks' overrides
+    int force = 0;           // ConvForce bits (ConvArgs::ws_force)
+    int image = 0;           // ConvLaunch::image (the model: 1 while the back half is issued)
+    int epi_stream = -1;     // ConvArgs::epi_stream; -1 = by the size of the output
+    bool offer_merge = true; // merged columns wherever the length maps allow them
+    bool flat = true;        // false: a ragged batch on the dense grid (the plan's flat tile list is not taken)
+    bool stats = false;      // statistics are wanted and the slots come later, sized from the plan (the model: ConvOpts::stat_part)
+};
+
+// Plan and kernel arguments of one launch.  Three things need a resource of the caller's, who is told by the plan: the
+// pre-split image (plan.pre), the flat tile table (plan.flat_bn) and, under ConvCtx::stats, the statistics slots
+// (plan.stat_cols); the setters fill in what depends on them.
+struct ConvCall {
+    ConvPlan plan;
+    ConvArgs a;
+    int B;
+    size_t image_bytes() const { return conv16_pre_image_bytes(a.Cin, a.x_ld); }  // per utterance
+    void set_image(const void* img, long img_bs) {  // (written by launch_split_image(a, ..))
+        a.x16 = img;
+        a.x16_bs = img_bs;
+        a.x16_ld = a.x_ld;
+    }
+    // the flat tile list runs over these columns per utterance: flat_len() + flat_extra()
+    const LenMap& flat_len() const { return a.store == ST_UPSCATTER ? a.in_len : a.out_len; }
+    int flat_extra() const { return a.store == ST_UPSCATTER ? 1 : 0; }
+    void set_flat(const int* tile_prefix, int tiles_host) {  // launch_tile_prefix's table and conv_tile_count of the same lengths
+        a.tile_prefix = tile_prefix;
+        a.flat_ny = (a.Cout + 127) / 128;
+        a.flat_B = B;
+        a.flat_tiles_host = tiles_host;
+        a.flat_bn_host = plan.flat_bn;
+    }
+    void set_stats(float2* part) {  // [B][rows][plan.stat_tiles]
+        a.stat_part = part;
+        a.stat_tiles = plan.stat_tiles;
+    }
+};
+ConvCall conv_call(const ConvW& w, const T& in, const T& out, const ConvOpts& o, const ConvCtx& ctx);
+// column tiles of `bn` columns over a batch whose host lengths are h_lens (tile_prefix[B] as the host counts it)
+int conv_tile_count(const int* h_lens, int B, const LenMap& lm, int extra, int bn);
 
 // the KXHIPW01 image behind `path`: the container itself (header checked), or built from the `.onnx` the reference passes
 // *variant (optional): what the file was -- 0 KXHIPW01 container, 1 fp32 ONNX, 2 fp16 / bf16 ONNX, 3 8-bit quantised ONNX,
@@ -188,7 +248,7 @@ class Model {
     const TensorInfo& info(const std::string& name) const;
     bool has(const std::string& name) const { return table_.count(name) != 0; }
     float* dev_alloc(size_t floats);
-    void pack16(ConvW& c, const PackSrc& src, const float* wT, int n_src_floats[3]);
+    DevAlloc owned_alloc();  // hipMalloc'd, freed with the model
     ConvW make_conv(const std::string& name, bool bias = true);
     ConvW make_conv_cat(const std::vector<std::string>& names);
     ConvW make_convT(const std::string& name, int stride);
@@ -197,6 +257,10 @@ class Model {
     long fc_off(const std::string& key) const;
 
     void conv(const ConvW& w, const T& in, const T& out, const ConvOpts& o);
+    void prof_begin(const ConvW& w, const T& in, const T& out, const ConvOpts& o);  // profile mode: the bracket around a timed launch
+    void prof_end();
+    long stamp_begin(const ConvW& w, ConvCall& call);  // KX_STAMP diagnostic
+    void stamp_dump(unsigned long long* d_stamps, long n_wg);
     void stats(const T& x, const std::string& fc_key);
     void adain_resblk(const std::string& name, const T& x, const T& out, bool upsample, float* ws_a, float* ws_b,
                       float* ws_c);

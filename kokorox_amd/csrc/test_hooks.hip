@@ -1,5 +1,7 @@
 // Stand-alone kernel hooks for tests/ (include/kokorox_hip_test.h): libkokorox_hip_test.so, a library of its own that links
-// against libkokorox_hip.so -- the production library exports none of them.
+// against libkokorox_hip.so -- the production library exports none of them.  The conv hooks take their weight images, launch
+// plan and kernel arguments from conv_call.hip, the code Model runs; what is theirs is the buffers, the tensor views over them
+// and the checks around the launch.
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -79,12 +81,12 @@ struct ConvTestExtra {  // epilogue forms beyond bias: residual, accumulate into
     int pad_ld = 0;              // rows padded to a multiple of 32 floats as in the model (x padding = NaN, y padding checked)
     int flat = 0;                // ragged batches: the flat tile list the model gives the direct-A kernels (ConvArgs::tile_prefix)
     int up_off = 0, up_reflect = 0;  // transposed: the output starts at column up_off of y (and column 0 = reflection of column 1)
-    // what Model::conv sets beyond that (kx_test_conv1d_opts)
+    // the launch options a forward sets beyond that (kx_test_conv1d_opts)
     int in_up2 = 0;              // the conv reads x[p >> 1]: L stored columns stand for 2 L
     int epi = kx::EPI_NONE;
-    int merged = 0;              // offer the plan one merged column space for the batch (ConvLaunch::merge_T), as Model::conv does
+    int merged = 0;              // input and output share one plain length array: conv_call offers the plan merged columns (ConvLaunch::merge_T)
     int tmajor = 0;              // ST_TMAJOR: y is [B][Lout][Cout]
-    int prec1 = 0;               // 1 / 2: one f16 / bf16 MFMA per product (2: on the bf16 image Model::set_conv_mode builds)
+    int prec1 = 0;               // 1 / 2: one f16 / bf16 MFMA per product (the hook runs CONV_F16 / CONV_BF16 inside the reduced-precision region; 2: on add_bf16_image's image)
     int act_shift = 0;           // x_prescale = 2^act_shift, w_unscale carries its inverse
     int epi_stream = 0;
     const float* norm_gb = nullptr;  // [B][2 Cout] (gamma | beta): finalize the conv's own partial sums into ...
@@ -92,6 +94,13 @@ struct ConvTestExtra {  // epilogue forms beyond bias: residual, accumulate into
     int64_t* plan_out = nullptr;     // [17] the ConvPlan that was launched, fields as kx_test_conv_plan returns them
 };
 }  // namespace
+
+// a ConvPlan as the 17 integers kx_test_conv_plan and kx_test_conv1d_opts return
+static void plan_fields(const kx::ConvPlan& p, int64_t* out) {
+    const int v[] = {p.form, p.bm, p.act, p.kt, p.wm, p.wn, p.vt, p.pf, p.p1, p.bf, p.bn, p.cols, p.merged, p.pre, p.stat_cols,
+                     p.stat_tiles, p.flat_bn};
+    for (int i = 0; i < 17; ++i) out[i] = v[i];
+}
 
 static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L, const float* w, const float* bias, int Cout,
                             int k, int stride, int pad, int dil, int transposed, int act, float slope, const float* alpha,
@@ -112,8 +121,6 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         mode &= 0xff;
         KX_REQUIRE(mode >= kx::CONV_F32 && mode <= kx::CONV_F16X3_DA, "test_conv1d: mode must be 0, 1, 2 or 3");
         KX_REQUIRE(!pre || mode == kx::CONV_F16X3 || mode == kx::CONV_F16X3_DA, "test_conv1d: pre-split images exist for the direct-A kernels only");
-        kx::ConvArgs a{};
-        a.ws_force = (mode == kx::CONV_F16X3_LDS ? kx::FORCE_LDS : (mode == kx::CONV_F16X3_DA ? kx::FORCE_DA : 0)) | force_bits;
         // row strides: the caller's dense rows, or (pad_ld) the model's: a multiple of 32 floats, input padding poisoned
         const int Ly = Lout + ex.up_off;  // columns of y (Lout: the conv's own output length)
         KX_REQUIRE(ex.up_off == 0 || (transposed && ex.up_off == 1 && !ex.pad_ld), "test_conv1d: an output offset comes with transposed convs");
@@ -128,20 +135,43 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         KX_REQUIRE(!ex.merged || (!transposed && Lout == L), "test_conv1d: merged columns need input and output of one length");
         KX_REQUIRE((ex.norm_out != nullptr) == (ex.norm_gb != nullptr), "test_conv1d: norm planes come with gamma / beta");
         KX_REQUIRE(ex.act_shift >= -24 && ex.act_shift <= 24 && ex.prec1 >= 0 && ex.prec1 <= 2, "test_conv1d: bad act_shift / prec1");
+        KX_REQUIRE(!transposed || (k == 2 * stride && pad == (k - stride) / 2 && dil == 1), "test_conv1d: transposed needs k=2s, pad=(k-s)/2");
+        KX_REQUIRE(act != kx::ACT_SNAKE || alpha, "test_conv1d: snake needs alpha");
         const float poison = std::nanf(""), sentinel = -12345.5f;
         auto padded = [&](const float* src, int rows_total, int len, int ld, float fill) {
             std::vector<float> v((size_t)rows_total * ld, fill);
             for (int r = 0; r < rows_total; ++r) std::memcpy(&v[(size_t)r * ld], src + (size_t)r * len, (size_t)len * 4);
             return v;
         };
+        const kx::DevAlloc alloc = [&dm](size_t bytes) -> void* { return dm.get<unsigned char>(bytes); };
+
+        // the layer: its weight images from the model's packers (conv_call.hip), bias and pre-scale as Model keeps them
+        const float* dw = dm.up(w, (size_t)Cout * Cin * k);
+        kx::ConvW cw = transposed ? kx::pack_convT(dw, Cin, Cout, stride, nullptr, alloc)
+                                  : kx::pack_conv(kx::PackSrc{{dw, nullptr, nullptr}, {Cout, 0, 0}}, Cin, k, nullptr, alloc);
+        cw.bias = bias ? dm.up(bias, (size_t)Cout) : nullptr;
+        cw.act_shift = ex.act_shift;
+        const int rows = cw.rows;
+        if (f8 && mode != kx::CONV_F32) {
+            kx::add_f8_image(cw, nullptr, alloc);
+            KX_REQUIRE(cw.w8x, "test_conv1d: f16f8 images exist for the 128-row tiles of plain 3-, 7- and 11-tap convs");
+        }
+        if (ex.prec1 == 2 && mode != kx::CONV_F32) {
+            kx::add_bf16_image(cw, nullptr, alloc);
+            KX_REQUIRE(cw.w16b, "test_conv1d: bf16 images exist for 128-row tiles");
+        }
+
+        // the input and output views: dense = every utterance L columns ({lens, 0, L}), ragged = its own length
+        kx::T in, out, res;
         if (ex.pad_ld) {
             const std::vector<float> xp = padded(x, B * Cin, L, x_ld, poison);
-            a.x = dm.up(xp.data(), xp.size());
+            in.p = dm.up(xp.data(), xp.size());
         } else
-            a.x = dm.up(x, (size_t)B * Cin * L);
-        a.x_bs = (long)Cin * x_ld;
-        a.x_ld = x_ld;
-        a.Cin = Cin;
+            in.p = dm.up(x, (size_t)B * Cin * L);
+        in.bs = (long)Cin * x_ld;
+        in.ld = x_ld;
+        in.C = Cin;
+        in.Lmax = L;
         const int up = ex.in_up2 ? 2 : 1;
         // (the merged kernels read the length array itself: a merged launch always carries real lengths)
         const bool ragged = ex.lens != nullptr || ex.merged;
@@ -154,56 +184,7 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         } else if (ex.merged)
             lens.assign(B, L);
         int* d_one = dm.up(lens.data(), B);
-        a.in_len = ragged ? kx::LenMap{d_one, up, 0} : kx::LenMap{d_one, 0, Lv};
-        a.out_len = ragged ? kx::LenMap{d_one, up, Lout - Lv} : kx::LenMap{d_one, 0, Lout};
-        a.in_up2 = ex.in_up2;
-        a.n_chunks = (Cin + kx::CONV_CK - 1) / kx::CONV_CK;
-        const float* dw = dm.up(w, (size_t)Cout * Cin * k);
-        int BM, rows;
-        float* packed;
-        if (!transposed) {
-            rows = Cout;
-            BM = kx::conv_pick_bm(rows);
-            packed = dm.get<float>(kx::packed_conv_floats(rows, Cin, k, BM));
-            kx::PackSrc src{{dw, nullptr, nullptr}, {Cout, 0, 0}};
-            kx::launch_pack_conv(src, packed, Cout, Cin, k, BM, nullptr);
-            a.K = k;
-            a.stride = stride;
-            a.pad = pad;
-            a.dil = dil;
-            a.store = ex.tmajor ? kx::ST_TMAJOR : kx::ST_NORMAL;
-            a.up_cout = 1;
-        } else {
-            KX_REQUIRE(k == 2 * stride && pad == (k - stride) / 2 && dil == 1, "test_conv1d: transposed needs k=2s, pad=(k-s)/2");
-            rows = stride * Cout;
-            BM = kx::conv_pick_bm(rows);
-            packed = dm.get<float>(kx::packed_conv_floats(rows, Cin, 2, BM));
-            kx::launch_pack_convT(dw, packed, Cin, Cout, stride, BM, nullptr);
-            a.K = 2;
-            a.stride = 1;
-            a.pad = 1;
-            a.dil = 1;
-            a.store = kx::ST_UPSCATTER;
-            a.up_s = stride;
-            a.up_pad = pad;
-            a.up_cout = Cout;
-            a.up_off = ex.up_off;
-            a.up_reflect = ex.up_reflect;
-        }
-        a.Cout = rows;
-        a.w = packed;
-        a.bias = bias ? dm.up(bias, (size_t)Cout) : nullptr;
-        if (norm) {
-            const float* dn = dm.up(norm, (size_t)3 * B * Cin);
-            a.nmean = dn;
-            a.nscale = dn + (size_t)B * Cin;
-            a.nshift = dn + (size_t)2 * B * Cin;
-            a.n_bs = Cin;
-        }
-        a.act = act;
-        a.slope = slope;
-        a.alpha = alpha ? dm.up(alpha, (size_t)Cin) : nullptr;
-        KX_REQUIRE(act != kx::ACT_SNAKE || alpha, "test_conv1d: snake needs alpha");
+        in.len = ragged ? kx::LenMap{d_one, 1, 0} : kx::LenMap{d_one, 0, L};  // (the stored columns: in_up2 doubles them in the launch)
         float* dy = dm.get<float>((size_t)B * yr * y_ld);
         if (ex.pad_ld) {  // y holds the running sum (accumulate) or zeros; the row padding holds a sentinel nobody may touch
             std::vector<float> y0((size_t)B * yr * yc, 0.f);
@@ -213,124 +194,91 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
             KX_HIP(hipMemcpy(dy, y, (size_t)B * Cout * Lout * 4, hipMemcpyHostToDevice));  // y holds the running sum
         else
             KX_HIP(hipMemset(dy, 0, (size_t)B * yr * y_ld * 4));
-        a.y = dy;
-        a.y_bs = (long)yr * y_ld;
-        a.y_ld = y_ld;
-        a.epi = ex.epi;
-        a.epi_stream = ex.epi_stream;
-        a.out_mul = ex.out_mul;
-        a.out_div = ex.out_div;
-        a.accum = ex.accum;
+        out.p = dy;
+        out.bs = (long)yr * y_ld;
+        out.ld = y_ld;
+        out.C = rows;
+        out.Lmax = Lout;
+        out.len = ragged ? kx::LenMap{d_one, up, Lout - Lv} : kx::LenMap{d_one, 0, Lout};
+
+        kx::ConvOpts o;
+        if (transposed) {  // the polyphase two-tap GEMM, scattered to the up-sampled axis
+            o.pad = 1;
+            o.store = kx::ST_UPSCATTER;
+            o.up_pad = pad;
+            o.up_off = ex.up_off;
+            o.up_reflect = ex.up_reflect;
+            o.up_len = out.len;
+        } else {
+            o.stride = stride;
+            o.pad = pad;
+            o.dil = dil;
+            o.store = ex.tmajor ? kx::ST_TMAJOR : kx::ST_NORMAL;
+        }
+        if (norm) {
+            const float* dn = dm.up(norm, (size_t)3 * B * Cin);
+            o.nmean = dn;
+            o.nscale = dn + (size_t)B * Cin;
+            o.nshift = dn + (size_t)2 * B * Cin;
+        }
+        o.act = act;
+        o.slope = slope;
+        o.alpha = alpha ? dm.up(alpha, (size_t)Cin) : nullptr;
+        o.in_up2 = ex.in_up2;
+        o.epi = ex.epi;
+        o.out_mul = ex.out_mul;
+        o.out_div = ex.out_div;
+        o.accum = ex.accum;
         if (ex.resid) {
             KX_REQUIRE(!transposed || !ex.pad_ld, "test_conv1d: residual of a transposed conv on dense rows only");
             if (ex.pad_ld) {
                 const std::vector<float> rp = padded(ex.resid, B * Cout, Lout, y_ld, poison);
-                a.resid = dm.up(rp.data(), rp.size());
+                res.p = dm.up(rp.data(), rp.size());
             } else
-                a.resid = dm.up(ex.resid, (size_t)B * Cout * Ly);
-            a.r_bs = (long)Cout * y_ld;
-            a.r_ld = y_ld;
+                res.p = dm.up(ex.resid, (size_t)B * Cout * Ly);
+            res.bs = (long)Cout * y_ld;
+            res.ld = y_ld;
+            o.resid = &res;
         }
-        // the plan of the launch (conv_plan.hip), as the model makes it: the hook's modes 2 and 3 are f16x3 with an override
-        kx::ConvLaunch c{};
-        c.mode = mode == kx::CONV_F32 ? kx::CONV_F32 : (f8 ? kx::CONV_F16F8 : kx::CONV_F16X3);
-        c.f8 = f8;
-        c.BM = BM;
-        c.rows = rows;
-        c.n_chunks16 = (Cin + 15) / 16;
-        c.K = a.K;
-        c.dil = a.dil;
-        c.stride = a.stride;
-        c.pad = a.pad;
-        c.act = act;
-        c.norm = norm != nullptr;
-        c.store = a.store;
-        c.accum = ex.accum;
-        c.stats = want_stats;
-        c.image = pre ? 2 : 0;
-        c.prec1 = ex.prec1;
-        c.in_up2 = ex.in_up2;
-        c.epi = ex.epi;
-        c.merge_T = ex.merged ? L : 0;  // (Model::conv: input and output share one plain length array)
-        c.x_bs = a.x_bs;
-        c.x_ld = x_ld;
-        c.B = B;
-        c.cols = transposed ? L + 1 : Lout;
-        c.cus = mode == kx::CONV_F32 ? 0 : kx::conv16_cu_count();
-        c.force = a.ws_force;
-        const kx::ConvPlan plan = kx::conv_plan(c);
-        if (ex.plan_out) {
-            const int v[] = {plan.form, plan.bm, plan.act, plan.kt, plan.wm, plan.wn, plan.vt, plan.pf, plan.p1, plan.bf, plan.bn, plan.cols,
-                             plan.merged, plan.pre, plan.stat_cols, plan.stat_tiles, plan.flat_bn};
-            for (int i = 0; i < 17; ++i) ex.plan_out[i] = v[i];
-        }
-        if (plan.merged) {
-            a.merge_T = L;
-            a.merge_B = B;
-        }
+
+        // the launch as the model assembles it: the hook's modes 2 and 3 are f16x3 with an override, prec1 is the f16 / bf16
+        // mode inside its region
+        kx::ConvCtx ctx;
+        ctx.mode = mode == kx::CONV_F32 ? kx::CONV_F32
+                                        : (ex.prec1 == 1 ? kx::CONV_F16 : (ex.prec1 == 2 ? kx::CONV_BF16 : (f8 ? kx::CONV_F16F8 : kx::CONV_F16X3)));
+        ctx.p1_region = true;
+        ctx.B = B;
+        ctx.cus = mode == kx::CONV_F32 ? 0 : kx::conv16_cu_count();
+        ctx.n_bs = norm ? Cin : 0;
+        ctx.force = (mode == kx::CONV_F16X3_LDS ? kx::FORCE_LDS : (mode == kx::CONV_F16X3_DA ? kx::FORCE_DA : 0)) | force_bits;
+        ctx.image = pre ? 2 : 0;
+        ctx.epi_stream = ex.epi_stream;
+        ctx.offer_merge = ex.merged != 0;
+        ctx.flat = ex.flat != 0;
+        ctx.stats = want_stats;
+        kx::ConvCall call = kx::conv_call(cw, in, out, o, ctx);
+        const kx::ConvPlan& plan = call.plan;
+        const kx::ConvArgs& a = call.a;
+        if (ex.plan_out) plan_fields(plan, ex.plan_out);
         float2* d_part = nullptr;
         if (want_stats) {
             KX_REQUIRE(!transposed && !ex.accum && plan.stat_cols > 0, "test_conv1d: fused statistics come with plain, non-accumulating stores");
-            a.stat_tiles = plan.stat_tiles;
-            d_part = dm.get<float2>((size_t)B * rows * a.stat_tiles);
-            KX_HIP(hipMemset(d_part, 0, (size_t)B * rows * a.stat_tiles * sizeof(float2)));
-            a.stat_part = d_part;
+            d_part = dm.get<float2>((size_t)B * rows * plan.stat_tiles);
+            KX_HIP(hipMemset(d_part, 0, (size_t)B * rows * plan.stat_tiles * sizeof(float2)));
+            call.set_stats(d_part);
         }
-        if (mode != kx::CONV_F32) {
-            const float amax = kx::device_absmax(dw, (long)Cout * Cin * k, nullptr);
-            const int ws = kx::pick_weight_shift(amax);
-            const int Kp = transposed ? 2 : k;
-            void* p16 = dm.get<unsigned short>(kx::packed_conv16_halves(rows, Cin, Kp, BM));
-            if (transposed)
-                kx::launch_pack_convT16(dw, p16, Cin, Cout, stride, BM, std::ldexp(1.0f, ws), nullptr);
-            else {
-                kx::PackSrc src{{dw, nullptr, nullptr}, {Cout, 0, 0}};
-                kx::launch_pack_conv16(src, p16, Cout, Cin, k, BM, std::ldexp(1.0f, ws), nullptr);
-            }
-            a.w16 = p16;
-            if (f8) {
-                KX_REQUIRE(!transposed && BM == 128, "test_conv1d: f16f8 images exist for 128-row tiles of plain convs");
-                void* p8 = dm.get<unsigned char>(kx::packed_conv8x_bytes(rows, Cin, k));
-                kx::launch_pack_conv8x(p16, p8, rows, Cin, k, nullptr);
-                a.w8x = p8;
-            }
-            a.n_chunks16 = (Cin + 15) / 16;
-            a.prec1 = ex.prec1;
-            if (ex.prec1 == 2) {  // the bf16 form of the image, as Model::set_conv_mode builds it
-                KX_REQUIRE(BM == 128, "test_conv1d: bf16 images exist for 128-row tiles");
-                const size_t nh = kx::packed_conv16_halves(rows, Cin, Kp, BM);
-                void* pb = dm.get<unsigned short>(nh);
-                kx::launch_image_to_bf16(p16, pb, nh, nullptr);
-                a.w16b = pb;
-            }
-            a.x_prescale = std::ldexp(1.0f, ex.act_shift);
-            a.w_unscale = std::ldexp(std::ldexp(1.0f, -ws), -ex.act_shift);  // (Model::conv: exact, both are powers of two)
-            a.xcd_swizzle = 1;
-            if (ex.flat && plan.flat_bn) {
-                const kx::LenMap lm = transposed ? a.in_len : a.out_len;
-                int* d_pre = dm.get<int>((size_t)B + 1);
-                kx::launch_tile_prefix(lm, transposed ? 1 : 0, plan.flat_bn, B, d_pre, nullptr);
-                int total = 0;
-                for (int b = 0; b < B; ++b) {
-                    const int cols = lens[b] * lm.mul + lm.add + (transposed ? 1 : 0);
-                    total += cols > 0 ? (cols + plan.flat_bn - 1) / plan.flat_bn : 0;
-                }
-                a.tile_prefix = d_pre;
-                a.flat_ny = (rows + 127) / 128;
-                a.flat_B = B;
-                a.flat_tiles_host = total;
-                a.flat_bn_host = plan.flat_bn;
-            }
-            if (pre) {
-                KX_REQUIRE(plan.pre, "test_conv1d: this layer has no pre-split form");
-                const long img_bs = (long)kx::conv16_pre_image_bytes(Cin, x_ld);
-                unsigned char* img = dm.get<unsigned char>((size_t)B * img_bs);
-                KX_HIP(hipMemset(img, 0xff, (size_t)B * img_bs));  // (NaN halves wherever the pass does not write)
-                kx::launch_split_image(a, B, L, img, img_bs, nullptr);
-                a.x16 = img;
-                a.x16_bs = img_bs;
-                a.x16_ld = x_ld;
-            }
+        if (plan.flat_bn) {
+            int* d_pre = dm.get<int>((size_t)B + 1);
+            kx::launch_tile_prefix(call.flat_len(), call.flat_extra(), plan.flat_bn, B, d_pre, nullptr);
+            call.set_flat(d_pre, kx::conv_tile_count(lens.data(), B, call.flat_len(), call.flat_extra(), plan.flat_bn));
+        }
+        if (pre) {
+            KX_REQUIRE(plan.pre, "test_conv1d: this layer has no pre-split form");
+            const long img_bs = (long)call.image_bytes();
+            unsigned char* img = dm.get<unsigned char>((size_t)B * img_bs);
+            KX_HIP(hipMemset(img, 0xff, (size_t)B * img_bs));  // (NaN halves wherever the pass does not write)
+            kx::launch_split_image(a, B, L, img, img_bs, nullptr);
+            call.set_image(img, img_bs);
         }
         kx::launch_conv(plan, a, B, nullptr);
         KX_HIP(hipDeviceSynchronize());
@@ -529,10 +477,7 @@ int kx_test_conv_plan(const int64_t* in, int n_in, int64_t* out, int n_out, char
         c.cols = (int)in[22];
         c.cus = (int)in[23];
         c.force = (int)in[24];
-        const kx::ConvPlan p = kx::conv_plan(c);
-        const int v[] = {p.form, p.bm, p.act, p.kt, p.wm, p.wn, p.vt, p.pf, p.p1, p.bf, p.bn, p.cols, p.merged, p.pre, p.stat_cols,
-                         p.stat_tiles, p.flat_bn};
-        for (int i = 0; i < 17; ++i) out[i] = v[i];
+        plan_fields(kx::conv_plan(c), out);
     });
 }
 
@@ -550,17 +495,10 @@ int kx_test_lstm(int device_id, const float* x, int B, int L, int n_in, const fl
                 for (int c = 0; c < n_in; ++c) xc[((size_t)b * n_in + c) * L + t] = x[((size_t)b * L + t) * n_in + c];
         std::vector<int> lens(B, L);
         int* d_len = dm.up(lens.data(), B);
-        kx::ConvArgs a{};
-        a.x = dm.up(xc.data(), xc.size());
-        a.x_bs = (long)n_in * L;
-        a.x_ld = L;
-        a.Cin = n_in;
-        a.in_len = kx::LenMap{d_len, 1, 0};
-        a.out_len = a.in_len;
-        a.n_chunks = (n_in + kx::CONV_CK - 1) / kx::CONV_CK;
-        float* packed = dm.get<float>(kx::packed_conv_floats(2048, n_in, 1, 128));
-        kx::PackSrc src{{dm.up(w_ih, (size_t)1024 * n_in), dm.up(w_ih_r, (size_t)1024 * n_in), nullptr}, {1024, 1024, 0}};
-        kx::launch_pack_conv(src, packed, 2048, n_in, 1, 128, nullptr);
+        // the input GEMM's weights as Model::make_lstm packs them; launched here on the f32 kernel, which is what this test pins
+        const kx::DevAlloc alloc = [&dm](size_t bytes) -> void* { return dm.get<unsigned char>(bytes); };
+        const kx::PackSrc src{{dm.up(w_ih, (size_t)1024 * n_in), dm.up(w_ih_r, (size_t)1024 * n_in), nullptr}, {1024, 1024, 0}};
+        const kx::ConvW ih = kx::pack_conv(src, n_in, 1, nullptr, alloc);
         float* bias = dm.get<float>(2048);
         kx::launch_vec_add(dm.up(b_ih, 1024), dm.up(b_hh, 1024), bias, 1024, nullptr);
         kx::launch_vec_add(dm.up(b_ih_r, 1024), dm.up(b_hh_r, 1024), bias + 1024, 1024, nullptr);
@@ -568,17 +506,25 @@ int kx_test_lstm(int device_id, const float* x, int B, int L, int n_in, const fl
         kx::launch_transpose_whh(dm.up(w_hh, 1024 * 256), whhT, nullptr);
         kx::launch_transpose_whh(dm.up(w_hh_r, 1024 * 256), whhT + 256 * 1024, nullptr);
         float* gx = dm.get<float>((size_t)B * L * 2048);
-        a.w = packed;
+        kx::ConvArgs a{};
+        a.x = dm.up(xc.data(), xc.size());
+        a.x_bs = (long)n_in * L;
+        a.x_ld = L;
+        a.Cin = n_in;
+        a.in_len = kx::LenMap{d_len, 1, 0};
+        a.out_len = a.in_len;
+        a.n_chunks = ih.n_chunks;
+        a.w = ih.w;
         a.bias = bias;
         a.K = 1; a.dil = 1; a.stride = 1; a.pad = 0;
-        a.Cout = 2048;
+        a.Cout = ih.rows;
         a.y = gx;
         a.y_bs = (long)L * 2048;
         a.y_ld = 2048;
         a.out_mul = 1.f; a.out_div = 1.f;
         a.store = kx::ST_TMAJOR;
         a.up_cout = 1;
-        kx::launch_conv1d(a, 128, B, L, nullptr);
+        kx::launch_conv1d(a, ih.BM, B, L, nullptr);
         float* dy = dm.get<float>((size_t)B * 512 * L);
         // (the hook runs the product's two-CU recurrence: exchange buffer + sticky error word as Model holds them)
         unsigned long long* xchg = dm.get<unsigned long long>(kx::lstm_exchange_bytes(B) / sizeof(unsigned long long));
