@@ -269,12 +269,25 @@ int kx_set_act_prescale(kx_model* m, const char* conv_name, int log2_scale);
  * sum_k row_k * (weights[k] * 0.1), in order, un-normalised; entries with voice id < 0 are skipped. */
 int kx_set_voice_table(kx_model* m, const float* table, int n_voices);
 
-/* Output forms of the reference: 0 = f32 mono (ort_koko.rs:80-87), 1 = f32 stereo with every sample written
- * twice (koko.rs:1239-1246), 2 = 16-bit PCM `(s.clamp(-1,1) * 32767) as i16` (kokorox-websocket/src/lib.rs:701-704).
+/* Output forms of the reference (kx_infer_packed, kx_infer_voices and kx_dispatcher_submit_ex take these three):
+ * 0 = f32 mono (ort_koko.rs:80-87), 1 = f32 stereo with every sample written twice (koko.rs:1239-1246), 2 = 16-bit PCM
+ * `(s.clamp(-1,1) * 32767) as i16` (kokorox-websocket/src/lib.rs:701-704).
  * Packed on the GPU, so only the packed bytes cross PCIe. */
 #define KX_PACK_F32_MONO 0
 #define KX_PACK_F32_STEREO 1
 #define KX_PACK_PCM16_MONO 2
+/* The bodies the reference's servers send, mono at 24 000 Hz (kx_infer_requests and kx_dispatcher_submit_request only):
+ * 3 = the HTTP body (kokorox-openai/src/lib.rs:416-425): the 44 bytes of `WavHeader::new(1, 24000, 32).write_header`
+ *     (kokorox/src/utils/wav.rs:18-50: IEEE float, both size fields the reference's 0xFFFFFFFF placeholders) followed by the
+ *     samples as f32 little-endian bit copies (a NaN keeps its payload); 44 + 4 S bytes.
+ * 4 = the WebSocket chunk (`encode_audio`, kokorox-websocket/src/lib.rs:696-736): standard-alphabet base64 with `=` padding,
+ *     no line breaks, no NUL, of a 16-bit WAV file: 44-byte header with its true sizes (36 + 2 S and 2 S), then
+ *     `(s.clamp(-1.0, 1.0) * 32767.0) as i16` per sample with Rust's meaning (NaN -> 0, +-inf -> +-32767, the product rounded
+ *     to f32 and truncated toward zero); 4 * ceil((44 + 2 S) / 3) characters, always ending in exactly one `=`, as S is a
+ *     multiple of 600.  A request of more than 0xFFFFFFFF - 36 data bytes is refused with KX_ERR_INVALID.
+ * (Form 2, as it has been since it was added, clamps with fmax / fmin, which drop a NaN: a NaN sample becomes -32767 there.) */
+#define KX_PACK_WAV_F32 3
+#define KX_PACK_WAV16_BASE64 4
 
 /* kx_infer with device-side style lookup/mix and packed output.  *out = library-owned bytes of the B utterances back
  * to back (kx_free_packed); out_bytes[b] / out_samples[b] per utterance. */
@@ -286,6 +299,20 @@ int kx_infer_packed(kx_model* m, const int64_t* ids, int64_t t_stride, const int
                     const float* speeds, int n_speed, uint64_t seed, uint32_t flags, int format, void** out,
                     int64_t* out_bytes, int64_t* out_samples);
 void kx_free_packed(void* p);
+
+/* The chunk loop of `TTSKoko::tts_raw_audio` (kokorox/src/tts/koko.rs:947-1191: a text is split into chunks of at most 500
+ * tokens, run one after the other, the waveforms appended with no cross-fade) as ONE forward with the bodies packed on the
+ * GPU.  Rows are chunks; request r owns chunks_per_request[r] consecutive rows (every entry >= 1, their sum = B, otherwise
+ * KX_ERR_INVALID).  The voice is per row: `styles` [B,256], or NULL with `voice_ids` / `weights` [B,max_mix] as
+ * kx_infer_voices (the row of a voice is lens[b] - 2 of each chunk, koko.rs:1166).  Row b draws the noise stream
+ * (seed, utterance base + b) exactly as kx_infer.  `formats` [n_format], n_format = 1 (shared) or R, values KX_PACK_* 0..4.
+ * *out = one pooled page-locked buffer (kx_free_packed) holding the R requests back to back: request r is the header of its
+ * form, if any, then its chunks' samples in order with nothing between chunks; out_bytes[r], out_samples[r] (= 600 x the sum
+ * of its chunks' frames) per request.  Forms 0..2 give the bytes of kx_infer_packed. */
+int kx_infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                      const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                      const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                      const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples);
 
 /* ---- request dispatcher ----------------------------------------------------
  * Replaces the reference's one-request-at-a-time `Mutex<Session>` (kokorox/src/onn/ort_koko.rs:78; callers
@@ -326,6 +353,19 @@ int kx_dispatcher_submit(kx_dispatcher* d, const int64_t* ids, int n_tokens, con
 int kx_dispatcher_submit_ex(kx_dispatcher* d, const int64_t* ids, int n_tokens, const float* style,
                             const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed,
                             int format, void** out, int64_t* out_bytes, int64_t* out_samples, char* err, size_t err_len);
+/* A request of 1 .. max_batch chunks (the chunk loop of koko.rs:947-1191 as one submit): `ids` holds the chunks back to back,
+ * chunk c has chunk_tokens[c] ids incl. its own two 0 pads; `styles` = n_chunks rows of 256 floats, or NULL with ONE voice
+ * spec for the request as in kx_dispatcher_submit_ex (the row of the voice is chunk_tokens[c] - 2 per chunk); `format` is a
+ * KX_PACK_* form 0..4.  Checked completely at submit with the rules of kx_dispatcher_submit_ex per chunk.  The chunks run as
+ * rows of ONE batched forward (a request is never split over batches or models; batches are sized in rows), chunk c draws
+ * the noise stream (seed, c), and *out is the request's one region: header of the form, if any, then the chunks' samples in
+ * order.  The bytes equal kx_infer_requests (R = 1, same seed, utterance base 0) whatever the request was batched with and
+ * on whichever model.  Release *out with kx_free_packed / kx_free_audio only. */
+int kx_dispatcher_submit_request(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                 const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
+                                 float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
+                                 int64_t* out_samples, char* err, size_t err_len);
+/* n_requests counts requests, max_batch_seen the largest batch in ROWS (a request of n chunks is n rows). */
 int kx_dispatcher_stats(kx_dispatcher* d, int64_t* n_requests, int64_t* n_batches, int64_t* max_batch_seen);
 /* batches each model (worker) has run so far: per_model[n_models] */
 int kx_dispatcher_model_batches(kx_dispatcher* d, int64_t* per_model, int n_models);

@@ -73,9 +73,72 @@ class HipKoko {
         return wav;
     }
 
+    // The chunk loop of TTSKoko::tts_raw_audio (koko.rs:947-1191) as one forward (kx_infer_requests): tokens = the chunks (each
+    // 0-wrapped), request r owns chunks_per_request[r] consecutive ones, styles = one row per chunk, format = a KX_PACK_* form
+    // 0..4 for every request.  Returns each request's body: header of the form, if any, then its chunks' samples in order
+    // (KX_PACK_WAV_F32: the HTTP body; KX_PACK_WAV16_BASE64: the WebSocket chunk's base64 text).
+    std::vector<std::string> infer_requests(const std::vector<std::vector<int64_t>>& tokens,
+                                            const std::vector<int32_t>& chunks_per_request,
+                                            const std::vector<std::vector<float>>& styles, float speed, uint64_t seed,
+                                            int format) const {
+        if (tokens.empty() || styles.size() != tokens.size()) throw std::invalid_argument("infer_requests: one style row per chunk");
+        const int B = (int)tokens.size(), R = (int)chunks_per_request.size();
+        size_t stride = 1;
+        for (const auto& t : tokens) stride = t.size() > stride ? t.size() : stride;
+        std::vector<int64_t> ids((size_t)B * stride, 0);
+        std::vector<int32_t> tl(B);
+        std::vector<float> st((size_t)B * KX_STYLE_DIM);
+        for (int b = 0; b < B; ++b) {
+            tl[b] = (int32_t)tokens[b].size();
+            for (size_t i = 0; i < tokens[b].size(); ++i) ids[(size_t)b * stride + i] = tokens[b][i];
+            if (styles[b].size() != KX_STYLE_DIM) throw std::invalid_argument("infer_requests: style rows need 256 floats");
+            for (int k = 0; k < KX_STYLE_DIM; ++k) st[(size_t)b * KX_STYLE_DIM + k] = styles[b][k];
+        }
+        void* out = nullptr;
+        std::vector<int64_t> nb(R > 0 ? R : 1), ns(R > 0 ? R : 1);
+        const int32_t fmt = format;
+        const int rc = kx_infer_requests(h_, ids.data(), (int64_t)stride, tl.data(), B, chunks_per_request.data(), R, st.data(),
+                                         nullptr, nullptr, 0, &speed, 1, seed, 0, &fmt, 1, &out, nb.data(), ns.data());
+        if (rc != KX_OK) {
+            char msg[512];
+            kx_last_error_copy(h_, msg, sizeof(msg));
+            throw std::runtime_error(std::string("kokorox_hip error: ") + msg);
+        }
+        std::vector<std::string> bodies;
+        const char* p = static_cast<const char*>(out);
+        for (int r = 0; r < R; ++r) {
+            bodies.emplace_back(p, p + nb[r]);
+            p += nb[r];
+        }
+        kx_free_packed(out);
+        return bodies;
+    }
+
   private:
     explicit HipKoko(kx_model* adopted) : h_(adopted) {}
     kx_model* h_ = nullptr;
 };
+
+// A request of 1 .. max_batch chunks through a dispatcher (kx_dispatcher_submit_request): ids = the chunks back to back, each
+// with its own two 0 pads, styles = one 256-float row per chunk; returns the body in the given KX_PACK_* form (0..4).
+inline std::string submit_request(kx_dispatcher* d, const std::vector<std::vector<int64_t>>& chunks,
+                                  const std::vector<float>& styles, float speed, uint64_t seed, int format) {
+    std::vector<int64_t> ids;
+    std::vector<int32_t> lens;
+    for (const auto& c : chunks) {
+        ids.insert(ids.end(), c.begin(), c.end());
+        lens.push_back((int32_t)c.size());
+    }
+    if (styles.size() != chunks.size() * KX_STYLE_DIM) throw std::invalid_argument("submit_request: one style row per chunk");
+    void* out = nullptr;
+    int64_t nb = 0, ns = 0;
+    char err[256] = {0};
+    if (kx_dispatcher_submit_request(d, ids.data(), lens.data(), (int)lens.size(), styles.data(), nullptr, nullptr, 0, speed, seed,
+                                     format, &out, &nb, &ns, err, sizeof(err)) != KX_OK)
+        throw std::runtime_error(std::string("kokorox_hip error: ") + err);
+    std::string body(static_cast<const char*>(out), (size_t)nb);
+    kx_free_packed(out);
+    return body;
+}
 
 }  // namespace kokorox

@@ -30,6 +30,10 @@ pub const KX_FLAG_NOISE_OFF: u32 = 1;
 pub const KX_PACK_F32_MONO: c_int = 0;
 pub const KX_PACK_F32_STEREO: c_int = 1;
 pub const KX_PACK_PCM16_MONO: c_int = 2;
+/// The HTTP body: 44-byte float WAV header + f32 samples (kokorox-openai/src/lib.rs:416-425); requests only.
+pub const KX_PACK_WAV_F32: c_int = 3;
+/// The WebSocket chunk: base64 of a 16-bit WAV file (`encode_audio`, kokorox-websocket/src/lib.rs:696-736); requests only.
+pub const KX_PACK_WAV16_BASE64: c_int = 4;
 
 #[repr(C)]
 pub struct KxModel {
@@ -92,6 +96,11 @@ extern "C" {
                        styles: *const f32, speeds: *const f32, n_speed: c_int, seed: u64, flags: u32,
                        format: c_int, out: *mut *mut c_void, out_bytes: *mut i64, out_samples: *mut i64) -> c_int;
     fn kx_free_packed(p: *mut c_void);
+    fn kx_infer_requests(m: *mut KxModel, ids: *const i64, t_stride: i64, lens: *const i32, b: c_int,
+                         chunks_per_request: *const i32, r: c_int, styles: *const f32, voice_ids: *const i32,
+                         weights: *const f32, max_mix: c_int, speeds: *const f32, n_speed: c_int, seed: u64, flags: u32,
+                         formats: *const i32, n_format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                         out_samples: *mut i64) -> c_int;
     fn kx_dispatcher_create(models: *mut *mut KxModel, n_models: c_int, max_batch: c_int, max_wait_us: c_int,
                             err: *mut c_char, err_len: usize) -> *mut KxDispatcher;
     fn kx_dispatcher_create_warm(models: *mut *mut KxModel, n_models: c_int, max_batch: c_int, max_wait_us: c_int,
@@ -103,6 +112,10 @@ extern "C" {
                                voice_ids: *const i32, weights: *const f32, n_mix: c_int, speed: f32, seed: u64,
                                format: c_int, out: *mut *mut c_void, out_bytes: *mut i64, out_samples: *mut i64,
                                err: *mut c_char, err_len: usize) -> c_int;
+    fn kx_dispatcher_submit_request(d: *mut KxDispatcher, ids: *const i64, chunk_tokens: *const i32, n_chunks: c_int,
+                                    styles: *const f32, voice_ids: *const i32, weights: *const f32, n_mix: c_int,
+                                    speed: f32, seed: u64, format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                                    out_samples: *mut i64, err: *mut c_char, err_len: usize) -> c_int;
     fn kx_dispatcher_stats(d: *mut KxDispatcher, n_requests: *mut i64, n_batches: *mut i64,
                            max_batch_seen: *mut i64) -> c_int;
     fn kx_dispatcher_failures(d: *mut KxDispatcher, n_replayed: *mut i64, n_retried: *mut i64) -> c_int;
@@ -359,6 +372,37 @@ impl HipKoko {
         Ok((v, nbytes))
     }
 
+    /// The chunk loop of `TTSKoko::tts_raw_audio` (koko.rs:947-1191) as one forward: `tokens` are the chunks, request r owns
+    /// `chunks_per_request[r]` consecutive ones, `styles` holds one row per chunk, `formats` one KX_PACK_* form (0..4) for
+    /// all requests or one per request.  Returns each request's body: header of its form, if any, then its chunks' samples
+    /// in order with nothing between them.
+    pub fn infer_requests(&self, tokens: &[Vec<i64>], chunks_per_request: &[i32], styles: &[Vec<f32>], speeds: &[f32],
+                          seed: u64, formats: &[c_int]) -> Result<Vec<Vec<u8>>, Box<dyn Error>> {
+        if tokens.is_empty() || styles.len() != tokens.len() || styles.iter().any(|s| s.len() != KX_STYLE_DIM) {
+            return Err("infer_requests: one style row of 256 floats per chunk is required".into());
+        }
+        let (b, r) = (tokens.len(), chunks_per_request.len());
+        let (ids, lens, stride) = Self::flatten(tokens);
+        let st: Vec<f32> = styles.iter().flatten().copied().collect();
+        let mut out: *mut c_void = ptr::null_mut();
+        let (mut nbytes, mut nsamp) = (vec![0i64; r.max(1)], vec![0i64; r.max(1)]);
+        let rc = unsafe {
+            kx_infer_requests(self.h, ids.as_ptr(), stride as i64, lens.as_ptr(), b as c_int, chunks_per_request.as_ptr(),
+                              r as c_int, st.as_ptr(), ptr::null(), ptr::null(), 0, speeds.as_ptr(), speeds.len() as c_int,
+                              seed, 0, formats.as_ptr(), formats.len() as c_int, &mut out, nbytes.as_mut_ptr(),
+                              nsamp.as_mut_ptr())
+        };
+        self.check(rc)?;
+        let mut bodies = Vec::with_capacity(r);
+        let mut at = 0usize;
+        for n in nbytes.iter().take(r) {
+            bodies.push(unsafe { std::slice::from_raw_parts((out as *const u8).add(at), *n as usize) }.to_vec());
+            at += *n as usize;
+        }
+        unsafe { kx_free_packed(out) };
+        Ok(bodies)
+    }
+
     /// Raw device-pointer form (inputs and output stay in HBM).
     ///
     /// # Safety
@@ -583,6 +627,56 @@ impl HipKokoDispatcher {
         Ok((v, ns))
     }
 
+    /// A request of 1 .. max_batch chunks (`chunks`: the 0-wrapped id lists of the chunk loop, koko.rs:947-1191) as rows of one
+    /// batched forward; `Voice::Row` carries one 256-float row per chunk, back to back.  Returns the request's body in the given
+    /// KX_PACK_* form (0..4) and its sample count; the bytes equal `HipKoko::infer_requests` of the request alone.
+    pub fn submit_request(&self, chunks: &[Vec<i64>], voice: Voice, speed: f32, seed: u64, format: i32)
+                          -> Result<(Vec<u8>, i64), Box<dyn Error>> {
+        let ids: Vec<i64> = chunks.iter().flatten().copied().collect();
+        let lens: Vec<i32> = chunks.iter().map(|c| c.len() as i32).collect();
+        let (mut vid, mut w): (Vec<i32>, Vec<f32>) = (Vec::new(), Vec::new());
+        let (style_p, vid_p, w_p, n_mix) = match voice {
+            Voice::Row(s) => {
+                if s.len() != KX_STYLE_DIM * chunks.len() {
+                    return Err("submit_request: one style row of 256 floats per chunk is required".into());
+                }
+                (s.as_ptr(), ptr::null(), ptr::null(), 0)
+            }
+            Voice::Single(id) => {
+                vid.push(id);
+                (ptr::null(), vid.as_ptr(), ptr::null(), 1)
+            }
+            Voice::Mix(parts) => {
+                for (id, p) in parts {
+                    vid.push(*id);
+                    w.push(*p);
+                }
+                (ptr::null(), vid.as_ptr(), w.as_ptr(), vid.len() as c_int)
+            }
+        };
+        let mut out: *mut c_void = ptr::null_mut();
+        let (mut nb, mut ns) = (0i64, 0i64);
+        let mut err = vec![0 as c_char; 256];
+        let rc = unsafe {
+            kx_dispatcher_submit_request(self.d, ids.as_ptr(), lens.as_ptr(), lens.len() as c_int, style_p, vid_p, w_p, n_mix,
+                                         speed, seed, format, &mut out, &mut nb, &mut ns, err.as_mut_ptr(), err.len())
+        };
+        if rc != KX_OK {
+            return Err(format!("kokorox_hip error {}: {}", rc, cstr_buf(&err)).into());
+        }
+        let v = unsafe { std::slice::from_raw_parts(out as *const u8, nb as usize) }.to_vec();
+        unsafe { kx_free_packed(out) };
+        Ok((v, ns))
+    }
+
+    /// The WebSocket chunk of `encode_audio` (kokorox-websocket/src/lib.rs:696-736) for a request: base64 of its 16-bit WAV
+    /// file, encoded on the GPU, as the `String` the server puts into its JSON message.
+    pub fn submit_request_base64(&self, chunks: &[Vec<i64>], voice: Voice, speed: f32, seed: u64)
+                                 -> Result<String, Box<dyn Error>> {
+        let (bytes, _) = self.submit_request(chunks, voice, speed, seed, KX_PACK_WAV16_BASE64)?;
+        Ok(String::from_utf8(bytes)?) // (base64 is ASCII: this never fails on what the library returns)
+    }
+
     /// Batches each model (GPU) has run so far.
     pub fn model_batches(&self) -> Vec<i64> {
         let mut v = vec![0i64; self._models.len()];
@@ -597,7 +691,7 @@ impl HipKokoDispatcher {
         (a, b)
     }
 
-    /// (requests, batches, largest batch) so far.
+    /// (requests, batches, largest batch in rows: a request of n chunks is n rows) so far.
     pub fn stats(&self) -> (i64, i64, i64) {
         let (mut a, mut b, mut c) = (0i64, 0i64, 0i64);
         unsafe { kx_dispatcher_stats(self.d, &mut a, &mut b, &mut c) };

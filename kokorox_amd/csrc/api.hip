@@ -279,6 +279,27 @@ int kx_infer_packed(kx_model* m, const int64_t* ids, int64_t t_stride, const int
     });
 }
 
+int kx_infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                      const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                      const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                      const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples) {
+    return guarded(m, [&](Model& M) {
+        KX_REQUIRE(chunks_per_request && formats && R >= 1, "infer_requests: null argument");
+        KX_REQUIRE((styles != nullptr) != (voice_ids != nullptr), "infer_requests: give the style rows OR voice ids, not both");
+        KX_REQUIRE(styles || weights, "infer_requests: null argument");
+        Model::HostCall hc;
+        hc.styles = styles;
+        hc.voice_ids = voice_ids;
+        hc.weights = weights;
+        hc.max_mix = voice_ids ? max_mix : 0;
+        hc.chunks_per_request = chunks_per_request;
+        hc.n_requests = R;
+        hc.req_formats = formats;
+        hc.n_req_formats = n_format;
+        M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples);
+    });
+}
+
 int kx_infer_device(kx_model* m, const int64_t* d_ids, int64_t t_stride, const int32_t* lens_host, int B,
                     const float* d_styles, const float* speeds_host, int n_speed, uint64_t seed, uint32_t flags,
                     float* d_audio, int64_t audio_ld, int32_t* d_frames, int64_t* need_ld) {

@@ -19,44 +19,58 @@ using kx::dispatch::Request;
 struct ModelBackend {
     using Handle = kx_model;
     struct Out {
-        void* buf = nullptr;  // the packed batch in one pooled page-locked buffer (utterances back to back)
+        void* buf = nullptr;  // the packed batch in one pooled page-locked buffer (requests back to back); per REQUEST:
         std::vector<int64_t> bytes, samples;
     };
     static int n_voices(kx_model* h) { return h->m->n_voices(); }
     static int n_vocab(kx_model* h) { return h->m->n_vocab(); }
     static void free_out(void* p) { kx::host_out_free(p); }
+    // Rows are chunks: a request of n chunks is n consecutive rows, each with the request's seed as its noise key and its chunk
+    // index as the utterance of that key's stream, and comes out of the forward as ONE region (HostCall::chunks_per_request).
     static int forward(kx_model* h, std::vector<Request*>& batch, Out& o) {
-        const int B = (int)batch.size();
+        const int R = (int)batch.size();
+        int B = 0;
         size_t stride = 0;
         int mm = 1;
-        bool any_voice = false, mixed_format = false;
+        // plain = every request is one row in form 0..2: the single-utterance traffic of submit / submit_ex, which keeps the
+        // per-utterance packing it has always had (pack_audio_kernel); anything else goes through the request packer
+        bool any_voice = false, plain = true;
         for (Request* r : batch) {
-            stride = r->ids.size() > stride ? r->ids.size() : stride;
+            plain = plain && r->rows() == 1 && r->format <= KX_PACK_PCM16_MONO;
+            B += r->rows();
+            for (int c = 0; c < r->rows(); ++c) stride = (size_t)r->chunk_len(c) > stride ? (size_t)r->chunk_len(c) : stride;
             mm = r->n_mix > mm ? r->n_mix : mm;
             any_voice = any_voice || r->kind != 0;
-            mixed_format = mixed_format || r->format != batch[0]->format;
         }
         std::vector<int64_t> ids((size_t)B * stride, 0);
-        std::vector<int32_t> lens(B), kinds(B), formats(B), vids((size_t)B * mm, -1);
+        std::vector<int32_t> lens(B), kinds(B), chunks(R), formats(R), vids((size_t)B * mm, -1);
         std::vector<float> styles((size_t)B * KX_STYLE_DIM, 0.f), speeds(B), weights((size_t)B * mm, 0.f);
         std::vector<uint64_t> seeds(B);
-        for (int b = 0; b < B; ++b) {
-            const Request& r = *batch[b];
-            lens[b] = (int32_t)r.ids.size();
-            memcpy(&ids[(size_t)b * stride], r.ids.data(), r.ids.size() * 8);
-            kinds[b] = r.kind;
-            formats[b] = r.format;
-            if (r.kind == 0) memcpy(&styles[(size_t)b * KX_STYLE_DIM], r.style.data(), KX_STYLE_DIM * 4);
-            for (int k = 0; k < r.n_mix; ++k) {
-                vids[(size_t)b * mm + k] = r.voice_ids[k];
-                weights[(size_t)b * mm + k] = r.weights[k];
+        std::vector<uint32_t> uidx(B);
+        int b = 0;
+        for (int q = 0; q < R; ++q) {
+            const Request& r = *batch[(size_t)q];
+            chunks[q] = r.rows();
+            formats[q] = r.format;
+            size_t at = 0;
+            for (int c = 0; c < r.rows(); ++c, ++b) {
+                lens[b] = (int32_t)r.chunk_len(c);
+                memcpy(&ids[(size_t)b * stride], r.ids.data() + at, (size_t)lens[b] * 8);
+                at += (size_t)lens[b];
+                kinds[b] = r.kind;
+                if (r.kind == 0) memcpy(&styles[(size_t)b * KX_STYLE_DIM], r.style.data() + (size_t)c * KX_STYLE_DIM, KX_STYLE_DIM * 4);
+                for (int k = 0; k < r.n_mix; ++k) {
+                    vids[(size_t)b * mm + k] = r.voice_ids[k];
+                    weights[(size_t)b * mm + k] = r.weights[k];
+                }
+                speeds[b] = r.speed;
+                seeds[b] = r.seed;
+                uidx[b] = (uint32_t)c;
             }
-            speeds[b] = r.speed;
-            seeds[b] = r.seed;
         }
         o.buf = nullptr;
-        o.bytes.assign(B, 0);
-        o.samples.assign(B, 0);
+        o.bytes.assign(R, 0);
+        o.samples.assign(R, 0);
         int rc = KX_ERR_DEVICE;
         std::string err;
         {
@@ -65,8 +79,17 @@ struct ModelBackend {
             try {
                 kx::Model::HostCall hc;
                 hc.utt_seeds = seeds.data();
-                hc.format = batch[0]->format;
-                if (mixed_format) hc.formats = formats.data();
+                if (plain) {  // (R = B: chunk 0 of every request is utterance 0 of its key's stream, the default)
+                    hc.format = batch[0]->format;
+                    for (int q = 1; q < R && !hc.formats; ++q)
+                        if (formats[q] != formats[0]) hc.formats = formats.data();  // (per utterance only where they differ)
+                } else {
+                    hc.utt_index = uidx.data();
+                    hc.chunks_per_request = chunks.data();
+                    hc.n_requests = R;
+                    hc.req_formats = formats.data();
+                    hc.n_req_formats = R;
+                }
                 if (any_voice) {
                     hc.voice_ids = vids.data();
                     hc.weights = weights.data();
@@ -92,9 +115,10 @@ struct ModelBackend {
         }
         return rc;
     }
-    // Every request gets a pointer INTO the batch's page-locked buffer (no per-request malloc + copy of a megabyte each: that
-    // was ~5 ms per batch of host time); the buffer goes back to the pool when the last of them has been freed
-    // (kx_free_audio / kx_free_packed -> host_out_free).
+    // Every request gets ONE pointer INTO the batch's page-locked buffer, for its whole region (no per-request malloc + copy of a
+    // megabyte each: that was ~5 ms per batch of host time); the buffer goes back to the pool when the last of them has been
+    // freed (kx_free_audio / kx_free_packed -> host_out_free).  The owners counted here and by the copy-out path below are
+    // requests, not rows.
     static void distribute(std::vector<Request*>& batch, Out& o) {
         const int B = (int)batch.size();
         std::vector<void*> parts((size_t)B);
@@ -218,6 +242,18 @@ int kx_dispatcher_submit_ex(kx_dispatcher* d, const int64_t* ids, int n_tokens, 
     }
     return d->submit_ex(ids, n_tokens, style, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes, out_samples, err,
                         err_len);
+}
+
+int kx_dispatcher_submit_request(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                 const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
+                                 float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
+                                 int64_t* out_samples, char* err, size_t err_len) {
+    if (!d) {
+        if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null dispatcher");
+        return KX_ERR_INVALID;
+    }
+    return d->submit_request(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
+                             out_samples, err, err_len);
 }
 
 int kx_dispatcher_stats(kx_dispatcher* d, int64_t* n_requests, int64_t* n_batches, int64_t* max_batch_seen) {

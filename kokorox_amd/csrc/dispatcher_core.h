@@ -8,12 +8,17 @@
 // queue and run them as one batched forward:
 //   * a worker whose model is free and that finds work waits at most `max_wait_us` after the oldest request's arrival for
 //     company (unless the queue already holds a full batch for every free model), then takes its SHARE of the queue:
-//     ceil(queued / free models), at most `max_batch`.  32 requests waiting in front of 8 idle GPUs become 8 batches of 4, not one batch
+//     ceil(queued rows / free models), at most `max_batch` rows.  32 requests waiting in front of 8 idle GPUs become 8 batches of 4, not one batch
 //     of 32 on one GPU beside seven idle ones; a single worker that frees up while the others are busy takes up to a
 //     whole batch (the reference's config 5: kokorox-openai, 32 clients over 8 GPUs).
 //   * a request names its voice either as the 256-float style row (what `mix_styles` returns, koko.rs:1255-1306) or as
 //     (voice id, weight) pairs into the device voice table, single voice or mix, and its output form (f32 mono / f32
-//     stereo, koko.rs:1239-1246 / PCM16, kokorox-websocket/src/lib.rs:696-736); requests of every kind share one batch.
+//     stereo, koko.rs:1239-1246 / PCM16, kokorox-websocket/src/lib.rs:696-736; a request of chunks also the two bodies the
+//     servers send, float WAV and base64 of a 16-bit WAV file); requests of every kind share one batch.
+//   * a request is 1 .. max_batch CHUNKS (the chunk loop of koko.rs:947-1191 as one submit): its chunks are consecutive rows
+//     of one forward and its result is one region.  Batches are sized in ROWS; a request is never split over batches or
+//     models, and a worker always takes the request at the head of the queue, so a request of max_batch chunks cannot starve
+//     behind a stream of small ones.  Replay, retry and re-queue move whole requests.
 //   * every request carries its own noise seed, applied per utterance, so a request's bytes are identical whether it
 //     ran alone or inside any batch on any of the models.
 //   * a request is checked COMPLETELY when it is submitted (token ids, token count, speed, format, voice ids against the
@@ -62,9 +67,13 @@ namespace dispatch {
 constexpr int MAX_MIX = 16;
 
 struct Request {
-    std::vector<int64_t> ids;
-    int kind = 0;  // 0 = style row, 1 = single voice, 2 = mix
-    std::vector<float> style;
+    std::vector<int64_t> ids;  // the chunks' ids back to back
+    // tokens of each chunk; empty = ONE chunk of ids.size() tokens (the single-utterance submits)
+    std::vector<int32_t> chunk_lens;
+    int rows() const { return chunk_lens.empty() ? 1 : (int)chunk_lens.size(); }
+    int chunk_len(int c) const { return chunk_lens.empty() ? (int)ids.size() : (int)chunk_lens[(size_t)c]; }
+    int kind = 0;  // 0 = style rows, 1 = single voice, 2 = mix
+    std::vector<float> style;  // kind 0: rows() x 256 floats, one row per chunk
     int32_t voice_ids[MAX_MIX];
     float weights[MAX_MIX];
     int n_mix = 0;
@@ -90,6 +99,7 @@ struct Core {
     std::mutex mu;
     std::condition_variable cv_work, cv_quiet;
     std::deque<Request*> queue;
+    long queued_rows = 0;  // rows (chunks) of the requests in `queue`: what shares and batch sizes are counted in
     bool stop = false;
     static constexpr int WORKERS_PER_MODEL = 2;
     std::vector<char> busy;  // per model: a forward is running (its GPU phase); 0 = a worker may start the next batch
@@ -143,7 +153,7 @@ struct Core {
                     // work is here and this model is free: give others a short chance to join, unless every free model
                     // already has a full batch waiting
                     bool go = true;
-                    while (!stop && !failed[m] && !queue.empty() && !busy[m] && (long)queue.size() < (long)max_batch * free_models()) {
+                    while (!stop && !failed[m] && !queue.empty() && !busy[m] && queued_rows < (long)max_batch * free_models()) {
                         const auto deadline = queue.front()->t_submit + std::chrono::microseconds(max_wait_us);
                         const auto now = std::chrono::steady_clock::now();
                         if (now >= deadline) break;
@@ -161,17 +171,22 @@ struct Core {
                 }
                 // this model's share of what is waiting (the other free models' workers wake up on the same notify)
                 const long fm = free_models();
-                long take = ((long)queue.size() + fm - 1) / fm;
+                long take = (queued_rows + fm - 1) / fm;
                 take = take > max_batch ? max_batch : take;
-                while (!queue.empty() && (long)batch.size() < take) {
+                // whole requests, in order, while they fit the share; the head of the queue always goes (it has at most
+                // max_batch rows: submit checks that), so a large request cannot starve behind small ones
+                long rows = 0;
+                while (!queue.empty() && (batch.empty() || rows + queue.front()->rows() <= take)) {
+                    rows += queue.front()->rows();
                     batch.push_back(queue.front());
                     queue.pop_front();
                 }
+                queued_rows -= rows;
                 busy[m] = true;
                 n_batches += 1;
                 per_model_batches[m] += 1;
                 n_requests += (int64_t)batch.size();
-                if ((int64_t)batch.size() > max_seen_batch) max_seen_batch = (int64_t)batch.size();
+                if ((int64_t)rows > max_seen_batch) max_seen_batch = (int64_t)rows;
                 more = !queue.empty();
             }
             if (more) cv_work.notify_all();  // (what is left is for the other free models)
@@ -179,7 +194,7 @@ struct Core {
             int rc = forward_retrying(h, batch, out);
             const bool replay = rc == KX_ERR_INVALID && batch.size() > 1;
             if (replay) {
-                // per-request isolation: only the requests that fail alone report the failure
+                // per-request isolation (a request with all its chunks): only the requests that fail alone report the failure
                 for (Request* r : batch) {
                     std::vector<Request*> one{r};
                     typename Backend::Out o1;
@@ -198,7 +213,10 @@ struct Core {
                     if (!failed[m]) n_model_failures += 1;
                     failed[m] = 1;
                     if (healthy_models() > 0) {
-                        for (auto it = batch.rbegin(); it != batch.rend(); ++it) queue.push_front(*it);
+                        for (auto it = batch.rbegin(); it != batch.rend(); ++it) {
+                            queue.push_front(*it);
+                            queued_rows += (*it)->rows();
+                        }
                         n_requeued += (int64_t)batch.size();
                         requeued = true;
                     } else {
@@ -208,6 +226,7 @@ struct Core {
                             finish(r);
                         }
                         queue.clear();
+                        queued_rows = 0;
                     }
                 }
             }
@@ -264,6 +283,7 @@ struct Core {
             }
             ++inside;
             queue.push_back(&r);
+            queued_rows += r.rows();
             cv_work.notify_all();
             r.cv.wait(lk, [&] { return r.done; });
             if (--inside == 0) cv_quiet.notify_all();
@@ -290,9 +310,9 @@ struct Core {
     }
 
     bool check_common(const int64_t* ids, int n_tokens, float speed, int format, const char* who, char* err,
-                      size_t err_len) {
-        if (!ids || n_tokens < 1 || n_tokens > KX_MAX_TOKENS || !(speed > 0.f) || format < 0 || format > 2) {
-            if (err && err_len) snprintf(err, err_len, "%s: bad argument (1..512 tokens, speed > 0, format 0..2)", who);
+                      size_t err_len, int max_format = KX_PACK_PCM16_MONO) {
+        if (!ids || n_tokens < 1 || n_tokens > KX_MAX_TOKENS || !(speed > 0.f) || format < 0 || format > max_format) {
+            if (err && err_len) snprintf(err, err_len, "%s: bad argument (1..512 tokens, speed > 0, format 0..%d)", who, max_format);
             return false;
         }
         const int nv = vocab_everywhere();  // (from the models' embedding tables: vocab.rs:5-20 has 178 rows, a checkpoint may differ)
@@ -312,6 +332,42 @@ struct Core {
             n = (n < 0 || v < n) ? v : n;
         }
         return n < 0 ? 0 : n;
+    }
+
+    // The voice of a request named into the device voice table, for both submit forms: `voice_ids[n_mix]` with weights = null and
+    // n_mix = 1 (a single voice: row copy) or with `weights[n_mix]` (a mix; ids < 0 are skipped parts, koko.rs:1283).  min_tokens
+    // = the shortest chunk: the row of a voice is tokens - 2, so the two 0 pads must be there.  Fills r.kind / n_mix / voice_ids /
+    // weights; the ids are checked against the voice tables NOW: inside a batch a bad id would fail every request it was batched with.
+    bool set_voices(Request& r, const int32_t* voice_ids, const float* weights, int n_mix, int min_tokens, const char* who, char* err,
+                    size_t err_len) {
+        if (!voice_ids || n_mix < 1 || n_mix > MAX_MIX || min_tokens < 2 || (!weights && n_mix != 1)) {
+            if (err && err_len)
+                snprintf(err, err_len, "%s: voices need 1..16 ids (one id when weights is null: a single voice) and the two 0 pads "
+                                       "among the tokens", who);
+            return false;
+        }
+        const int nv = voices_everywhere();
+        bool any = false;
+        for (int k = 0; k < n_mix; ++k) {
+            if (voice_ids[k] >= nv) {
+                if (err && err_len)
+                    snprintf(err, err_len, "%s: voice id %d outside the table of %d voices%s", who, (int)voice_ids[k], nv,
+                             nv ? "" : " (kx_set_voice_table was not called on every model)");
+                return false;
+            }
+            any = any || voice_ids[k] >= 0;
+        }
+        if (!any || (!weights && voice_ids[0] < 0)) {
+            if (err && err_len) snprintf(err, err_len, "%s: no voice given", who);
+            return false;
+        }
+        r.kind = weights ? 2 : 1;
+        r.n_mix = n_mix;
+        for (int k = 0; k < n_mix; ++k) {
+            r.voice_ids[k] = voice_ids[k];
+            r.weights[k] = weights ? weights[k] : 0.f;
+        }
+        return true;
     }
 
     int submit_row(const int64_t* ids, int n_tokens, const float* style, float speed, uint64_t seed, float** out,
@@ -348,37 +404,57 @@ struct Core {
             }
             r.kind = 0;
             r.style.assign(style, style + KX_STYLE_DIM);
-        } else {
-            if (!voice_ids || n_mix < 1 || n_mix > MAX_MIX || n_tokens < 2 || (!weights && n_mix != 1)) {
-                if (err && err_len)
-                    snprintf(err, err_len, "dispatcher_submit_ex: voices need 1..16 ids (one id when weights is null: a single "
-                                           "voice) and the two 0 pads among the tokens");
-                return KX_ERR_INVALID;
-            }
-            // ids against the voice tables NOW: inside a batch a bad id would fail every request it was batched with
-            const int nv = voices_everywhere();
-            bool any = false;
-            for (int k = 0; k < n_mix; ++k) {
-                if (voice_ids[k] >= nv) {
-                    if (err && err_len)
-                        snprintf(err, err_len, "dispatcher_submit_ex: voice id %d outside the table of %d voices%s", (int)voice_ids[k], nv,
-                                 nv ? "" : " (kx_set_voice_table was not called on every model)");
-                    return KX_ERR_INVALID;
-                }
-                any = any || voice_ids[k] >= 0;
-            }
-            if (!any || (!weights && voice_ids[0] < 0)) {  // (negative ids are skipped parts of a mix, koko.rs:1283)
-                if (err && err_len) snprintf(err, err_len, "dispatcher_submit_ex: no voice given");
-                return KX_ERR_INVALID;
-            }
-            r.kind = weights ? 2 : 1;
-            r.n_mix = n_mix;
-            for (int k = 0; k < n_mix; ++k) {
-                r.voice_ids[k] = voice_ids[k];
-                r.weights[k] = weights ? weights[k] : 0.f;
-            }
+        } else if (!set_voices(r, voice_ids, weights, n_mix, n_tokens, "dispatcher_submit_ex", err, err_len)) {
+            return KX_ERR_INVALID;
         }
         r.ids.assign(ids, ids + n_tokens);
+        r.format = format;
+        r.speed = speed;
+        r.seed = seed;
+        return submit(r, out, out_bytes, out_samples, err, err_len);
+    }
+
+    // A request of n_chunks chunks: ids = the chunks back to back (chunk c has chunk_tokens[c] ids incl. its two 0 pads);
+    // styles = n_chunks rows of 256 floats, or null with ONE voice spec for the whole request as in submit_ex (the row of the
+    // voice is chunk_tokens[c] - 2 per chunk, koko.rs:1166); format 0 .. 4.  Every chunk is checked with submit_ex's rules.
+    int submit_request(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
+                       const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
+                       void** out, int64_t* out_bytes, int64_t* out_samples, char* err, size_t err_len) {
+        const char* who = "dispatcher_submit_request";
+        if (!out || !out_bytes || !out_samples) {
+            if (err && err_len) snprintf(err, err_len, "%s: null output argument", who);
+            return KX_ERR_INVALID;
+        }
+        if (!ids || !chunk_tokens || n_chunks < 1 || n_chunks > max_batch) {
+            if (err && err_len) snprintf(err, err_len, "%s: a request has 1..%d chunks (max_batch)", who, max_batch);
+            return KX_ERR_INVALID;
+        }
+        if ((styles != nullptr) == (voice_ids != nullptr)) {
+            if (err && err_len) snprintf(err, err_len, "%s: give the style rows OR voice ids, not both", who);
+            return KX_ERR_INVALID;
+        }
+        size_t total = 0;
+        int min_tokens = KX_MAX_TOKENS;
+        for (int c = 0; c < n_chunks; ++c) {
+            // (the count first: check_common reads chunk_tokens[c] ids)
+            if (chunk_tokens[c] < (voice_ids ? 2 : 1) || chunk_tokens[c] > KX_MAX_TOKENS) {
+                if (err && err_len)
+                    snprintf(err, err_len, "%s: chunk %d: 1..512 tokens (with a voice: at least the two 0 pads)", who, c);
+                return KX_ERR_INVALID;
+            }
+            if (!check_common(ids + total, chunk_tokens[c], speed, format, who, err, err_len, KX_PACK_WAV16_BASE64)) return KX_ERR_INVALID;
+            total += (size_t)chunk_tokens[c];
+            min_tokens = chunk_tokens[c] < min_tokens ? chunk_tokens[c] : min_tokens;
+        }
+        Request r;
+        if (styles) {
+            r.kind = 0;
+            r.style.assign(styles, styles + (size_t)n_chunks * KX_STYLE_DIM);
+        } else if (!set_voices(r, voice_ids, weights, n_mix, min_tokens, who, err, err_len)) {
+            return KX_ERR_INVALID;
+        }
+        r.ids.assign(ids, ids + total);
+        r.chunk_lens.assign(chunk_tokens, chunk_tokens + n_chunks);
         r.format = format;
         r.speed = speed;
         r.seed = seed;

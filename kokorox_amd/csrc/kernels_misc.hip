@@ -450,7 +450,15 @@ void launch_style_mix(const float* table, int n_voices, const int* voice_ids, co
 
 // ---- output packing on device ------------------------------------------------------------------------
 // f32 stereo = every sample written twice (koko.rs:1239-1246); PCM16 = (s.clamp(-1,1) * 32767) as i16,
-// i.e. truncation toward zero, NaN -> 0 (kokorox-websocket/src/lib.rs:701-704).
+// i.e. truncation toward zero (kokorox-websocket/src/lib.rs:701-704; a NaN: see pcm16_sample).
+// `(s.clamp(-1.0, 1.0) * 32767.0) as i16`: the product rounded to f32, truncated toward zero.  nan_to_zero = Rust's meaning
+// (clamp keeps a NaN and the cast turns it into 0: form 4); without it the fmaxf / fminf clamp drops the NaN and the sample
+// becomes -32767, which is what form 2 has always given (left as it is).
+__device__ __forceinline__ int pcm16_sample(float s, bool nan_to_zero) {
+    if (nan_to_zero && s != s) return 0;
+    const float c = fminf(fmaxf(s, -1.0f), 1.0f);
+    return __float2int_rz(__fmul_rn(c, 32767.0f));
+}
 __global__ void pack_audio_kernel(const float* audio, long audio_ld, const int* frames, int format, const int* formats,
                                   void* out, long out_stride_bytes, const long* out_off) {
     const long j = blockIdx.x * (long)blockDim.x + threadIdx.x;
@@ -463,8 +471,7 @@ __global__ void pack_audio_kernel(const float* audio, long audio_ld, const int* 
     if (format == 1) {
         reinterpret_cast<float2*>(ob)[j] = make_float2(sv, sv);
     } else if (format == 2) {
-        const float c = fminf(fmaxf(sv, -1.0f), 1.0f);
-        reinterpret_cast<short*>(ob)[j] = (short)__float2int_rz(__fmul_rn(c, 32767.0f));
+        reinterpret_cast<short*>(ob)[j] = (short)pcm16_sample(sv, false);
     } else {
         reinterpret_cast<float*>(ob)[j] = sv;
     }
@@ -473,6 +480,204 @@ void launch_pack_audio(const float* audio, long audio_ld, const int* frames, int
                        long out_stride_bytes, const long* out_off, hipStream_t s, const int* formats) {
     hipLaunchKernelGGL(pack_audio_kernel, dim3((600 * Fmax + 255) / 256, B), dim3(256), 0, s, audio, audio_ld, frames,
                        format, formats, out, out_stride_bytes, out_off);
+    KX_HIP(hipGetLastError());
+}
+
+// ---- requests of several chunks, packed as the bytes a server sends ---------------------------------------------
+// A request's region is a function of a VIRTUAL BYTE STREAM: the header of its form, then the sample bytes of its rows in
+// order (the chunk loop of koko.rs:947-1191 appends the waveforms with no cross-fade).  Forms 0..2 are launch_pack_audio's;
+// 3 = `WavHeader::new(1, 24000, 32).write_header` + `to_le_bytes` of every sample (kokorox/src/utils/wav.rs:18-50,
+// kokorox-openai/src/lib.rs:416-425: both size fields are the reference's 0xFFFFFFFF placeholders); 4 = standard base64 of a
+// 16-bit WAV file (`encode_audio`, kokorox-websocket/src/lib.rs:696-736), whose output group g is stream bytes 3g .. 3g + 2.
+//
+// One lane writes one 16-byte unit of the output, aligned in the compact buffer (a region starts on a multiple of 4, so its
+// first and last unit may be partial: those lanes store single dwords).  A workgroup first copies the window of the
+// request's sample stream that its 256 units need into LDS, lanes along time, looking up the row of every sample in the
+// batch's prefix table: the conversion then never sees a row boundary, and nothing at or past 600 * frames[b] of a row is
+// ever read.  (44 + 1200 k) mod 3 = 2: every chunk boundary of form 4 falls inside a base64 group.
+constexpr int PACK_THREADS = 256;
+constexpr int PACK_LDS = 2048 + 8;  // samples a workgroup's 4096 output bytes can need: 2048 (PCM16), 1536 + 2 (base64)
+
+__device__ __forceinline__ uint32_t wav_header_dword(int form, long S, int j) {
+    const bool f32 = form == 3;
+    switch (j) {
+        case 0: return 0x46464952u;                                   // "RIFF"
+        case 1: return f32 ? 0xFFFFFFFFu : (uint32_t)(36 + 2 * S);   // file size - 8 (placeholder in the float form)
+        case 2: return 0x45564157u;                                   // "WAVE"
+        case 3: return 0x20746d66u;                                   // "fmt "
+        case 4: return 16u;
+        case 5: return (f32 ? 3u : 1u) | (1u << 16);                  // format tag (3 = IEEE float, 1 = PCM), 1 channel
+        case 6: return 24000u;
+        case 7: return f32 ? 96000u : 48000u;                         // bytes per second
+        case 8: return f32 ? (4u | (32u << 16)) : (2u | (16u << 16));  // block align, bits per sample
+        case 9: return 0x61746164u;                                   // "data"
+        default: return f32 ? 0xFFFFFFFFu : (uint32_t)(2 * S);
+    }
+}
+__device__ __forceinline__ uint32_t base64_char(uint32_t v) {
+    return v < 26u ? 65u + v : (v < 52u ? 71u + v : (v < 62u ? v - 4u : (v == 62u ? 43u : 47u)));
+}
+
+__global__ __launch_bounds__(PACK_THREADS) void pack_requests_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                     const PackReq* __restrict__ reqs,
+                                                                     const long* __restrict__ cum, char* __restrict__ out) {
+    __shared__ float smp[PACK_LDS];
+    const PackReq rq = reqs[blockIdx.y];
+    const long mis = rq.out_off & 15;  // the region starts `mis` bytes into its first 16-byte unit
+    const long blk_lo = (long)blockIdx.x * (PACK_THREADS * 16) - mis;
+    if (blk_lo >= rq.out_bytes) return;  // (uniform: the grid covers the largest region of the batch)
+    const long p_lo = blk_lo < 0 ? 0 : blk_lo;
+    const long p_hi = blk_lo + PACK_THREADS * 16 < rq.out_bytes ? blk_lo + PACK_THREADS * 16 : rq.out_bytes;
+    const long S = rq.n_samples;
+    // samples of the request's stream that output bytes [p_lo, p_hi) depend on
+    long s_lo, s_hi;
+    if (rq.form == 0) {
+        s_lo = p_lo >> 2, s_hi = p_hi >> 2;
+    } else if (rq.form == 1) {
+        s_lo = p_lo >> 3, s_hi = (p_hi + 7) >> 3;
+    } else if (rq.form == 2) {
+        s_lo = p_lo >> 1, s_hi = p_hi >> 1;
+    } else if (rq.form == 3) {
+        s_lo = (p_lo < 44 ? 0 : p_lo - 44) >> 2, s_hi = (p_hi < 44 ? 0 : p_hi - 44) >> 2;
+    } else {
+        const long k_lo = (p_lo >> 2) * 3, k_hi = (p_hi >> 2) * 3;  // stream bytes of its groups
+        s_lo = (k_lo < 44 ? 0 : k_lo - 44) >> 1, s_hi = (k_hi < 44 ? 0 : k_hi - 43) >> 1;
+    }
+    s_hi = s_hi > S ? S : s_hi;
+    {
+        const long g0 = cum[rq.first_row];
+        const int row_end = rq.first_row + rq.n_rows;
+        long i = s_lo + threadIdx.x;
+        if (i < s_hi) {
+            int lo = rq.first_row, hi = row_end - 1;  // the row of the lane's first sample: cum[row] <= g0 + i < cum[row + 1]
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (cum[mid] <= g0 + i) lo = mid; else hi = mid - 1;
+            }
+            int row = lo;
+            for (; i < s_hi; i += PACK_THREADS) {
+                while (row + 1 < row_end && cum[row + 1] <= g0 + i) ++row;
+                smp[i - s_lo] = audio[(long)row * audio_ld + (g0 + i - cum[row])];
+            }
+        }
+    }
+    __syncthreads();
+    const long u_lo = blk_lo + (long)threadIdx.x * 16;  // the lane's unit, as a byte offset in the region (may start before it)
+    if (u_lo >= rq.out_bytes) return;
+    auto sample = [&](long i) { return smp[i - s_lo]; };
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long p = u_lo + 4 * j;
+        uint32_t v = 0;
+        if (p >= 0 && p < rq.out_bytes) {
+            if (rq.form == 0) {
+                v = __float_as_uint(sample(p >> 2));
+            } else if (rq.form == 1) {
+                v = __float_as_uint(sample(p >> 3));
+            } else if (rq.form == 2) {
+                v = ((uint32_t)pcm16_sample(sample(p >> 1), false) & 0xFFFFu) | ((uint32_t)pcm16_sample(sample((p >> 1) + 1), false) << 16);
+            } else if (rq.form == 3) {
+                v = p < 44 ? wav_header_dword(3, S, (int)(p >> 2)) : __float_as_uint(sample((p - 44) >> 2));
+            } else {
+                const long k = (p >> 2) * 3, L = 44 + 2 * S;  // group p / 4 = stream bytes k .. k + 2 of L
+                uint32_t b[3];
+#pragma unroll
+                for (int t = 0; t < 3; ++t) {
+                    const long kk = k + t;
+                    if (kk >= L) {
+                        b[t] = 0;
+                    } else if (kk < 44) {
+                        b[t] = (wav_header_dword(4, S, (int)(kk >> 2)) >> (8 * (int)(kk & 3))) & 255u;
+                    } else {
+                        const long d = kk - 44;
+                        b[t] = ((uint32_t)pcm16_sample(sample(d >> 1), true) >> (8 * (int)(d & 1))) & 255u;
+                    }
+                }
+                const long n = L - k;  // bytes of this group: 3, or 2 / 1 in the last one ('=' padding)
+                const uint32_t c0 = base64_char(b[0] >> 2), c1 = base64_char(((b[0] & 3u) << 4) | (b[1] >> 4));
+                const uint32_t c2 = n < 2 ? 61u : base64_char(((b[1] & 15u) << 2) | (b[2] >> 6));
+                const uint32_t c3 = n < 3 ? 61u : base64_char(b[2] & 63u);
+                v = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
+            }
+        }
+        w[j] = v;
+    }
+    char* o = out + rq.out_off + u_lo;  // 16-byte aligned: out_off + u_lo = 16 * (unit index) - mis + out_off
+    if (u_lo >= 0 && u_lo + 16 <= rq.out_bytes) {
+        *reinterpret_cast<uint4*>(o) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long p = u_lo + 4 * j;
+            if (p >= 0 && p < rq.out_bytes) *reinterpret_cast<uint32_t*>(o + 4 * j) = w[j];
+        }
+    }
+}
+
+long pack_request_bytes(int form, long n_samples) {
+    switch (form) {
+        case 0: return 4 * n_samples;
+        case 1: return 8 * n_samples;
+        case 2: return 2 * n_samples;
+        case 3: return 44 + 4 * n_samples;
+        case 4:
+            KX_REQUIRE(36 + 2 * n_samples <= 0xFFFFFFFFL, "pack: a 16-bit WAV file cannot hold that many samples (size field of 32 bits)");
+            return 4 * ((44 + 2 * n_samples + 2) / 3);
+        default: KX_REQUIRE(false, "infer: unknown output format");
+    }
+    return 0;
+}
+
+size_t pack_requests_bound(const int* formats, int n_format, int R, size_t n_samples) {
+    // per sample: 8 (stereo), 4 (f32, float WAV), 3 >= 8 / 3 (base64 of 16 bits), 2 (PCM16); per request: the 44-byte header,
+    // or its 60 base64 characters and the last group's padding -- what a one-frame request needs beyond its samples
+    size_t per_sample = 0;
+    for (int i = 0; i < n_format; ++i) {
+        const int f = formats[i];
+        const size_t w = f == 1 ? 8 : (f == 2 ? 2 : (f == 4 ? 3 : 4));
+        per_sample = w > per_sample ? w : per_sample;
+    }
+    return n_samples * per_sample + (size_t)R * 64 + 16;
+}
+
+void build_pack_plan(const int* frames, int B, const int* chunks_per_request, int R, const int* formats, int n_format,
+                     PackPlan& plan) {
+    KX_REQUIRE(frames && formats && B >= 1 && R >= 1 && (n_format == 1 || n_format == R), "pack: bad argument");
+    plan.cum.assign((size_t)B + 1, 0);
+    for (int b = 0; b < B; ++b) {
+        KX_REQUIRE(frames[b] >= 0, "pack: negative frame count");
+        plan.cum[(size_t)b + 1] = plan.cum[(size_t)b] + 600L * frames[b];
+    }
+    plan.req.assign((size_t)R, PackReq{});
+    plan.total_bytes = 0;
+    plan.max_units = 0;
+    int row = 0;
+    for (int r = 0; r < R; ++r) {
+        const int n = chunks_per_request ? chunks_per_request[r] : 1;
+        KX_REQUIRE(n >= 1 && n <= B - row, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
+        PackReq& q = plan.req[(size_t)r];
+        q.first_row = row;
+        q.n_rows = n;
+        q.form = formats[n_format == 1 ? 0 : r];
+        q.pad_ = 0;
+        q.n_samples = plan.cum[(size_t)(row + n)] - plan.cum[(size_t)row];
+        q.out_off = plan.total_bytes;
+        q.out_bytes = pack_request_bytes(q.form, q.n_samples);
+        plan.total_bytes += q.out_bytes;
+        const long units = ((q.out_off & 15) + q.out_bytes + 15) / 16;
+        plan.max_units = units > plan.max_units ? units : plan.max_units;
+        row += n;
+    }
+    KX_REQUIRE(row == B, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
+}
+
+void launch_pack_requests(const float* audio, long audio_ld, const PackReq* d_req, const long* d_cum, int R, long max_units,
+                          void* out, hipStream_t s) {
+    if (max_units <= 0) return;
+    KX_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0 && R <= 65535, "pack: unaligned output or too many requests");
+    hipLaunchKernelGGL(pack_requests_kernel, dim3((unsigned)((max_units + PACK_THREADS - 1) / PACK_THREADS), (unsigned)R),
+                       dim3(PACK_THREADS), 0, s, audio, audio_ld, d_req, d_cum, static_cast<char*>(out));
     KX_HIP(hipGetLastError());
 }
 
@@ -1101,8 +1306,8 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 
 __global__ void source_sample_kernel(const float* f0, long f0_bs, const int* frames, const float* phase, int L2max,
                                      const float* lin_w, const float* lin_b, uint32_t k0, uint32_t k1,
-                                     uint64_t utt_base, const uint64_t* utt_seeds, int noise_off, float* har,
-                                     long har_bs) {
+                                     uint64_t utt_base, const uint64_t* utt_seeds, const uint32_t* utt_index,
+                                     int noise_off, float* har, long har_bs) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     const int n2 = 2 * frames[b];
     if (j >= 300 * n2) return;
@@ -1115,12 +1320,12 @@ __global__ void source_sample_kernel(const float* f0, long f0_bs, const int* fra
     const float l1 = __fsub_rn(src, (float)i0), l0 = __fsub_rn(1.0f, l1);
     const int i1 = i0 + (i0 < n2 - 1 ? 1 : 0);
     const float amp = uv ? 0.003f : (0.1f / 3.0f);
-    // per-utterance keys (dispatcher): stream (seed_b, utterance 0); otherwise (seed, utt_base + b)
+    // per-utterance keys (dispatcher): stream (seed_b, utt_index[b], or utterance 0 without one); otherwise (seed, utt_base + b)
     uint32_t utt = (uint32_t)(utt_base + (uint64_t)b);
     if (utt_seeds) {
         k0 = (uint32_t)(utt_seeds[b] & 0xFFFFFFFFu);
         k1 = (uint32_t)(utt_seeds[b] >> 32);
-        utt = 0u;
+        utt = utt_index ? utt_index[b] : 0u;
     }
     float acc = 0.f;
 #pragma unroll
@@ -1144,14 +1349,14 @@ __global__ void source_sample_kernel(const float* f0, long f0_bs, const int* fra
 }
 
 void launch_source(const float* f0, long f0_bs, const int* frames, int B, int Fmax, const float* lin_w,
-                   const float* lin_b, uint64_t seed, uint64_t utt_base, const uint64_t* utt_seeds, int noise_off,
-                   float* phase_ws, float* har, long har_bs, hipStream_t s) {
+                   const float* lin_b, uint64_t seed, uint64_t utt_base, const uint64_t* utt_seeds,
+                   const uint32_t* utt_index, int noise_off, float* phase_ws, float* har, long har_bs, hipStream_t s) {
     const int L2max = 2 * Fmax;
     hipLaunchKernelGGL(source_phase_kernel, dim3(B), dim3(256), 0, s, f0, f0_bs, frames, phase_ws, L2max);
     KX_HIP(hipGetLastError());
     hipLaunchKernelGGL(source_sample_kernel, dim3((600 * Fmax + 255) / 256, B), dim3(256), 0, s, f0, f0_bs, frames,
                        phase_ws, L2max, lin_w, lin_b, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32),
-                       utt_base, utt_seeds, noise_off, har, har_bs);
+                       utt_base, utt_seeds, utt_index, noise_off, har, har_bs);
     KX_HIP(hipGetLastError());
 }
 

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include <atomic>
 #include <mutex>
@@ -290,6 +291,33 @@ void launch_style_mix(const float* table, int n_voices, const int* voice_ids, co
                       const int* rows, const int* kinds, float* styles, int B, hipStream_t s);
 void launch_pack_audio(const float* audio, long audio_ld, const int* frames, int B, int Fmax, int format, void* out,
                        long out_stride_bytes, const long* out_off, hipStream_t s, const int* formats = nullptr);
+
+// ---- requests of several chunks, packed as the bytes a server sends (kernels_misc.hip: pack_requests_kernel) ----------
+// A request is n_rows consecutive rows of the audio slab; its output is a function of a virtual byte stream: the header of
+// its form (if any), then the sample bytes of its rows in order with nothing between them.  Forms 0..2 as launch_pack_audio,
+// 3 = 44-byte float WAV header + f32 bit copies, 4 = base64 of a 16-bit WAV file (include/kokorox_hip.h, KX_PACK_*).
+struct PackReq {
+    int first_row, n_rows, form, pad_;
+    long out_off;    // byte offset of the request's region in the compact output (a multiple of 4)
+    long out_bytes;  // size of the region (a multiple of 4 in every form)
+    long n_samples;  // 600 * the sum of its rows' frames
+};
+struct PackPlan {
+    std::vector<PackReq> req;
+    std::vector<long> cum;  // [B + 1] samples of the rows before row b, over the whole batch
+    long total_bytes = 0;
+    long max_units = 0;     // 16-byte units of the largest region (the launch's grid)
+};
+long pack_request_bytes(int form, long n_samples);  // throws KX_ERR_INVALID: unknown form, 16-bit WAV past 4 GiB
+// Worst case of a batch's compact output before the frame counts are known: R requests, n_samples samples in all, every
+// request in the widest of the given forms (the per-request header and the base64 padding do not scale with the samples).
+size_t pack_requests_bound(const int* formats, int n_format, int R, size_t n_samples);
+// chunks_per_request [R] (null: every row a request of its own, R = B), formats [n_format], n_format = 1 or R
+void build_pack_plan(const int* frames, int B, const int* chunks_per_request, int R, const int* formats, int n_format,
+                     PackPlan& plan);
+// d_req [R], d_cum [B + 1]: device copies of the plan; out: 16-byte aligned, plan.total_bytes long
+void launch_pack_requests(const float* audio, long audio_ld, const PackReq* d_req, const long* d_cum, int R, long max_units,
+                          void* out, hipStream_t s);
 // Host output buffers of the kx_infer* calls: page-locked and pooled (one asynchronous D2H copy at PCIe rate instead
 // of per-utterance pageable copies); host_out_free also accepts plain malloc'd pointers (dispatcher results).
 void* host_out_alloc(size_t bytes);
@@ -326,8 +354,9 @@ void launch_pool_up2(const float* x, long xbs, int xld, int C, const float* mean
                      long ybs, int yld, LenMap in_len, int B, int Lmax_in, hipStream_t s);
 
 void launch_source(const float* f0, long f0_bs, const int* frames, int B, int Fmax, const float* lin_w,
-                   const float* lin_b, uint64_t seed, uint64_t utt_base, const uint64_t* utt_seeds, int noise_off,
-                   float* phase_ws,
+                   const float* lin_b, uint64_t seed, uint64_t utt_base, const uint64_t* utt_seeds,
+                   const uint32_t* utt_index,  // beside utt_seeds: row b draws (utt_seeds[b], utt_index[b]); null = utterance 0
+                   int noise_off, float* phase_ws,
                    float* har, long har_bs, hipStream_t s);
 enum StftVariant { STFT_ONNX = 0, STFT_TORCH = 1 };  // (kernels_misc.hip: the two STFT / iSTFT pairs)
 void launch_stft(const float* har_src, long hs_bs, float* har, long bs, int ld, const int* frames, int B,

@@ -190,6 +190,14 @@ class Model {
         // per-utterance forms (the dispatcher's mixed batches); null = the batch-wide fields above
         const int32_t* kinds = nullptr;      // host [B]: 0 = row of `styles`, 1 = single voice (copy), 2 = mix
         const int32_t* formats = nullptr;    // host [B]
+        // requests of several chunks (kx_infer_requests, the dispatcher): rows are chunks, request r owns chunks_per_request[r]
+        // consecutive rows and comes out as ONE region (header of its form, then its rows' samples with nothing between them);
+        // out_bytes / out_samples of the call then have n_requests entries and `format` / `formats` are not used
+        const int32_t* chunks_per_request = nullptr;  // host [n_requests], every entry >= 1, sum = B
+        int n_requests = 0;
+        const int32_t* req_formats = nullptr;         // host [n_req_formats], values 0..4 (KX_PACK_*)
+        int n_req_formats = 0;                        // 1 (shared) or n_requests
+        const uint32_t* utt_index = nullptr;          // host [B] beside utt_seeds: row b draws (utt_seeds[b], utt_index[b])
     };
     void infer_host_ex(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
                        int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out, int64_t* out_bytes,
@@ -312,6 +320,7 @@ class Model {
 
     Arena arenaT_, arenaF_, arenaIO_;
     const uint64_t* d_utt_seeds_ = nullptr;  // per-utterance noise keys of the running call (dispatcher)
+    const uint32_t* d_utt_index_ = nullptr;  // beside them: the utterance index of each row's stream (chunk c of a dispatched request)
     float* d_voices_ = nullptr;  // [n_voices_][511][256]
     std::atomic<int> n_voices_{0};
     int* d_pinned_ = nullptr;
@@ -334,6 +343,7 @@ class Model {
     int64_t n_lstm_timeouts_ = 0, n_rerun_ = 0;
     void infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds, int n_speed,
                          uint64_t seed, uint32_t flags, const HostCall& hc, void** out, int64_t* out_bytes, int64_t* out_samples);
+    PackPlan pack_plan_;               // request table + sample prefixes of the running call (same lifetime rule as h_off_)
     std::vector<long> h_off_;          // host staging that asynchronous copies read / write: outlives the calling frame
     unsigned h_bad_id_ = 0;
     unsigned* d_dev_err_ = nullptr;

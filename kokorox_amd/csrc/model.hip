@@ -1384,7 +1384,7 @@ void Model::infer_device(const int64_t* d_ids, int64_t t_stride, const int32_t* 
             float* phase = A.f((size_t)B * 9 * 2 * Fmax);
             if (!dry_)
                 launch_source(curves.p, curves.bs, dF_, B, Fmax, wt(G + "m_source.l_linear.weight"),
-                              wt(G + "m_source.l_linear.bias"), seed, utt_base, d_utt_seeds_, noise_off, phase, har_src, hs_ld, stream_);
+                              wt(G + "m_source.l_linear.bias"), seed, utt_base, d_utt_seeds_, d_utt_index_, noise_off, phase, har_src, hs_ld, stream_);
             if (taps_on_ && !dry_) {
                 T hs;
                 hs.p = har_src; hs.bs = hs_ld; hs.ld = (int)hs_ld; hs.C = 1; hs.len = LenMap{dF_, 600, 0}; hs.Lmax = 600 * Fmax;
@@ -1622,7 +1622,21 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     *out = nullptr;
     KX_REQUIRE(B >= 1, "infer: empty batch");
     KX_REQUIRE(ids && lens && speeds, "infer: null argument");
-    KX_REQUIRE(hc.format >= 0 && hc.format <= 2, "infer: unknown output format");
+    const bool grouped = hc.chunks_per_request != nullptr;  // (then `format` / `formats` are not used)
+    KX_REQUIRE(grouped || (hc.format >= 0 && hc.format <= 2), "infer: unknown output format");
+    const int R = grouped ? hc.n_requests : B;
+    if (grouped) {
+        KX_REQUIRE(R >= 1 && hc.req_formats && (hc.n_req_formats == 1 || hc.n_req_formats == R), "infer: requests need 1 or R output formats");
+        long rows = 0;
+        for (int r = 0; r < R; ++r) {
+            KX_REQUIRE(hc.chunks_per_request[r] >= 1, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
+            rows += hc.chunks_per_request[r];
+        }
+        KX_REQUIRE(rows == B, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
+        for (int i = 0; i < hc.n_req_formats; ++i)
+            KX_REQUIRE(hc.req_formats[i] >= 0 && hc.req_formats[i] <= 4, "infer: unknown output format");
+    }
+    KX_REQUIRE(!hc.utt_index || hc.utt_seeds, "infer: utterance indices go with per-row seeds");
     const bool by_voice = hc.voice_ids != nullptr;
     KX_REQUIRE(by_voice || hc.styles, "infer: styles or voice ids are required");
     KX_REQUIRE(!hc.kinds || (by_voice && hc.styles), "infer: per-utterance kinds need both styles and voice ids");
@@ -1638,7 +1652,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             const int64_t id = ids[b * t_stride + t];
             KX_REQUIRE(id >= 0 && id < n_vocab_, "infer: token id outside 0..177");
         }
-        KX_REQUIRE(kind_of(b) >= 0 && kind_of(b) <= 2 && format_of(b) >= 0 && format_of(b) <= 2, "infer: unknown kind / output format");
+        KX_REQUIRE(kind_of(b) >= 0 && kind_of(b) <= 2 && (grouped || (format_of(b) >= 0 && format_of(b) <= 2)), "infer: unknown kind / output format");
         if (kind_of(b) != 0) {
             KX_REQUIRE(lens[b] >= 2, "infer: voice rows need the two 0 pads (row = tokens - 2)");
             bool any = false;
@@ -1656,30 +1670,46 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     float* d_styles;
     int* d_fr;
     uint64_t* d_seeds;
-    int *d_vid, *d_rows, *d_kinds, *d_formats;
+    uint32_t* d_uidx;
+    PackReq* d_req = nullptr;
+    long* d_cum = nullptr;
+    int *d_vid, *d_rows, *d_kinds, *d_formats = nullptr;
     float* d_w;
     void* d_packed;
-    long* d_off;
+    long* d_off = nullptr;
     struct SeedGuard {  // the per-utterance key pointer is valid only during this call
         const uint64_t*& p;
         ~SeedGuard() { p = nullptr; }
     } seed_guard{d_utt_seeds_};
+    struct IndexGuard {
+        const uint32_t*& p;
+        ~IndexGuard() { p = nullptr; }
+    } index_guard{d_utt_index_};
     const int mm = by_voice ? hc.max_mix : 1;
-    int bytes_per_sample = 0;  // (the widest form of the batch sizes the packed buffer)
-    for (int b = 0; b < B; ++b) bytes_per_sample = bps_of(b) > bytes_per_sample ? bps_of(b) : bytes_per_sample;
+    int bytes_per_sample = 0;  // (per-utterance packing: the widest form of the batch sizes the packed buffer)
+    for (int b = 0; b < B && !grouped; ++b) bytes_per_sample = bps_of(b) > bytes_per_sample ? bps_of(b) : bytes_per_sample;
     auto planIO = [&](Arena& A, size_t audio_floats) {
         A.off = 0;
         d_ids = static_cast<int64_t*>(A.alloc((size_t)B * t_stride * 8));
         d_seeds = static_cast<uint64_t*>(A.alloc((size_t)B * 8));
+        d_uidx = static_cast<uint32_t*>(A.alloc((size_t)B * 4));
         d_styles = A.f((size_t)B * 256);
         d_fr = A.i(B);
         d_vid = A.i((size_t)B * mm);
         d_rows = A.i(B);
         d_kinds = A.i(B);
-        d_formats = A.i(B);
         d_w = A.f((size_t)B * mm);
-        d_off = static_cast<long*>(A.alloc((size_t)B * 8));
-        d_packed = A.alloc(audio_floats * bytes_per_sample);  // compact output: utterances back to back
+        if (grouped) {
+            // (the per-request header and the base64 padding do not scale with the samples: one frame per request is where a
+            // per-sample estimate falls short)
+            d_req = static_cast<PackReq*>(A.alloc((size_t)R * sizeof(PackReq)));
+            d_cum = static_cast<long*>(A.alloc(((size_t)B + 1) * 8));
+            d_packed = A.alloc(pack_requests_bound(hc.req_formats, hc.n_req_formats, R, audio_floats));
+        } else {
+            d_formats = A.i(B);
+            d_off = static_cast<long*>(A.alloc((size_t)B * 8));
+            d_packed = A.alloc(audio_floats * bytes_per_sample);  // compact output: utterances back to back
+        }
         return A.f(audio_floats);
     };
     // worst case length is 50 frames per token; start from a typical 8 and retry once if short
@@ -1715,6 +1745,11 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             KX_HIP(hipMemcpyAsync(d_seeds, hc.utt_seeds, (size_t)B * 8, hipMemcpyHostToDevice, stream_));
             d_utt_seeds_ = d_seeds;
         }
+        d_utt_index_ = nullptr;
+        if (hc.utt_index) {
+            KX_HIP(hipMemcpyAsync(d_uidx, hc.utt_index, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+            d_utt_index_ = d_uidx;
+        }
         int64_t need_ld = 0;
         try {
             infer_device(d_ids, t_stride, lens, B, d_styles, speeds, n_speed, seed, flags, d_audio, ld, d_fr, &need_ld);
@@ -1727,22 +1762,36 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         }
         // frame counts are known (the forward's one host sync): pack the B waveforms back to back on the GPU in the
         // requested sample format, then ONE asynchronous copy into a page-locked host buffer
-        std::vector<long>& off = h_off_;
-        off.assign(B, 0);
         int64_t total = 0;
-        for (int b = 0; b < B; ++b) {
-            out_samples[b] = (int64_t)600 * hF_[b];
-            out_bytes[b] = out_samples[b] * bps_of(b);
-            off[b] = (long)total;
-            total += out_bytes[b];
+        if (grouped) {
+            // the request table and the rows' sample prefixes, then ONE launch for every request of the batch, whatever its form
+            PackPlan& plan = pack_plan_;
+            build_pack_plan(hF_.data(), B, hc.chunks_per_request, R, hc.req_formats, hc.n_req_formats, plan);
+            for (int r = 0; r < R; ++r) {
+                out_samples[r] = plan.req[(size_t)r].n_samples;
+                out_bytes[r] = plan.req[(size_t)r].out_bytes;
+            }
+            total = plan.total_bytes;
+            KX_HIP(hipMemcpyAsync(d_req, plan.req.data(), (size_t)R * sizeof(PackReq), hipMemcpyHostToDevice, stream_));
+            KX_HIP(hipMemcpyAsync(d_cum, plan.cum.data(), ((size_t)B + 1) * 8, hipMemcpyHostToDevice, stream_));
+            launch_pack_requests(d_audio, ld, d_req, d_cum, R, plan.max_units, d_packed, stream_);
+        } else {
+            std::vector<long>& off = h_off_;
+            off.assign(B, 0);
+            for (int b = 0; b < B; ++b) {
+                out_samples[b] = (int64_t)600 * hF_[b];
+                out_bytes[b] = out_samples[b] * bps_of(b);
+                off[b] = (long)total;
+                total += out_bytes[b];
+            }
+            KX_HIP(hipMemcpyAsync(d_off, off.data(), (size_t)B * 8, hipMemcpyHostToDevice, stream_));
+            if (hc.formats) {
+                int* st = stage_ints((size_t)3 * B) + 2 * (size_t)B;
+                memcpy(st, hc.formats, (size_t)B * 4);
+                KX_HIP(hipMemcpyAsync(d_formats, st, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+            }
+            launch_pack_audio(d_audio, ld, dF_, B, Fmax_, hc.format, d_packed, 0, d_off, stream_, hc.formats ? d_formats : nullptr);
         }
-        KX_HIP(hipMemcpyAsync(d_off, off.data(), (size_t)B * 8, hipMemcpyHostToDevice, stream_));
-        if (hc.formats) {
-            int* st = stage_ints((size_t)3 * B) + 2 * (size_t)B;
-            memcpy(st, hc.formats, (size_t)B * 4);
-            KX_HIP(hipMemcpyAsync(d_formats, st, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
-        }
-        launch_pack_audio(d_audio, ld, dF_, B, Fmax_, hc.format, d_packed, 0, d_off, stream_, hc.formats ? d_formats : nullptr);
         char* host = static_cast<char*>(host_out_alloc((size_t)(total > 0 ? total : 1)));
         hipError_t e = hipMemcpyAsync(host, d_packed, (size_t)total, hipMemcpyDeviceToHost, stream_);
         if (e == hipSuccess) e = hipStreamSynchronize(stream_);

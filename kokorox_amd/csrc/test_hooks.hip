@@ -588,9 +588,37 @@ int kx_test_source(int device_id, const float* f0, int B, int F2, const float* l
         const float* d_b = dm.up(&lin_b, 1);
         float* phase = dm.get<float>((size_t)B * 9 * F2);
         float* har = dm.get<float>((size_t)B * 600 * F);
-        kx::launch_source(d_f0, F2, d_fr, B, F, d_w, d_b, seed, utt_base, nullptr, noise_off, phase, har, (long)600 * F, nullptr);
+        kx::launch_source(d_f0, F2, d_fr, B, F, d_w, d_b, seed, utt_base, nullptr, nullptr, noise_off, phase, har, (long)600 * F, nullptr);
         KX_HIP(hipDeviceSynchronize());
         KX_HIP(hipMemcpy(out, har, (size_t)B * 600 * F * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int kx_test_pack_requests(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames,
+                          const int32_t* chunks_per_request, int R, const int32_t* formats, void* out, int64_t out_cap,
+                          int64_t* out_bytes, char* err, size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        check_device(device_id);
+        KX_REQUIRE(audio && frames && chunks_per_request && formats && out && out_bytes && B > 0 && R > 0, "test_pack_requests: bad argument");
+        for (int b = 0; b < B; ++b) KX_REQUIRE(frames[b] >= 0 && 600L * frames[b] <= audio_ld, "test_pack_requests: a row is shorter than its frames");
+        kx::PackPlan plan;  // the table builder of Model::infer_host_once
+        kx::build_pack_plan(frames, B, chunks_per_request, R, formats, R, plan);
+        for (int r = 0; r < R; ++r) out_bytes[r] = plan.req[(size_t)r].out_bytes;
+        KX_REQUIRE(plan.total_bytes <= out_cap, "test_pack_requests: out_cap is too small");
+        KX_HIP(hipSetDevice(device_id));
+        DevMem dm;
+        const float* d_audio = dm.up(audio, (size_t)B * (size_t)audio_ld);
+        const kx::PackReq* d_req = dm.up(plan.req.data(), (size_t)R);
+        const long* d_cum = dm.up(plan.cum.data(), (size_t)B + 1);
+        // a sentinel after the last region: the kernel must not write past what the plan says
+        char* d_out = dm.get<char>((size_t)plan.total_bytes + 64);
+        KX_HIP(hipMemset(d_out, 0xA5, (size_t)plan.total_bytes + 64));
+        kx::launch_pack_requests(d_audio, (long)audio_ld, d_req, d_cum, R, plan.max_units, d_out, nullptr);
+        KX_HIP(hipDeviceSynchronize());
+        std::vector<unsigned char> tail(64);
+        KX_HIP(hipMemcpy(out, d_out, (size_t)plan.total_bytes, hipMemcpyDeviceToHost));
+        KX_HIP(hipMemcpy(tail.data(), d_out + plan.total_bytes, 64, hipMemcpyDeviceToHost));
+        for (unsigned char c : tail) KX_REQUIRE(c == 0xA5, "test_pack_requests: the kernel wrote past the last region");
     });
 }
 

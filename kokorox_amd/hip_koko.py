@@ -21,6 +21,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libkokorox_hip.so")
 
 PACK_F32_MONO, PACK_F32_STEREO, PACK_PCM16_MONO = 0, 1, 2
+PACK_WAV_F32, PACK_WAV16_BASE64 = 3, 4  # the servers' bodies (infer_requests / submit_request only): float WAV, base64 of a 16-bit WAV
 KX_OK, KX_ERR_INVALID, KX_ERR_IO, KX_ERR_DEVICE, KX_ERR_STATE = 0, 1, 2, 3, 4  # include/kokorox_hip.h
 KX_FLAG_NOISE_OFF = 1
 KX_FLAG_TAPS = 2
@@ -107,6 +108,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "kx_infer_voices": (i32, [vp, vp, i64, vp, i32, vp, vp, i32, vp, i32, u64, u32, i32, C.POINTER(vp), vp, vp]),
         "kx_infer_packed": (i32, [vp, vp, i64, vp, i32, vp, vp, i32, u64, u32, i32, C.POINTER(vp), vp, vp]),
         "kx_free_packed": (None, [vp]),
+        "kx_infer_requests": (i32, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, u64, u32, vp, i32, C.POINTER(vp), vp, vp]),
+        "kx_dispatcher_submit_request": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
+                                               C.POINTER(i64), cp, sz]),
         "kx_dispatcher_create": (vp, [vp, i32, i32, i32, cp, sz]),
         "kx_dispatcher_create_warm": (vp, [vp, i32, i32, i32, i32, i32, cp, sz]),
         "kx_dispatcher_submit": (i32, [vp, vp, i32, vp, f32, u64, C.POINTER(C.POINTER(f32)), C.POINTER(i64), cp, sz]),
@@ -162,6 +166,7 @@ def load_test_library() -> C.CDLL:
                                       f32, vp, vp, i32, vp, i32, vp, vp, vp, cp, sz]),
         "kx_test_layernorm": (i32, [i32, vp, i32, i32, i32, vp, f32, i32, vp, vp, f32, vp, cp, sz]),
         "kx_test_instance_norm": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, cp, sz]),
+        "kx_test_pack_requests": (i32, [i32, vp, i32, i64, vp, vp, i32, vp, vp, i64, vp, cp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -173,7 +178,7 @@ def load_test_library() -> C.CDLL:
 
 TEST_ABI_SYMBOLS = ["kx_test_conv1d", "kx_test_lstm", "kx_test_source", "kx_test_attention", "kx_test_conv1d_epilogue", "kx_test_conv1d_full",
                     "kx_test_conv_transpose", "kx_test_lstm_fault", "kx_test_lstm_parts", "kx_test_conv_plan", "kx_test_conv1d_opts",
-                    "kx_test_layernorm", "kx_test_instance_norm"]
+                    "kx_test_layernorm", "kx_test_instance_norm", "kx_test_pack_requests"]
 
 ABI_SYMBOLS = [
     "kx_version", "kx_init", "kx_create", "kx_import_onnx", "kx_create_from_device_blob", "kx_create_replicas", "kx_replicas_times", "kx_create_partition", "kx_destroy",
@@ -181,7 +186,7 @@ ABI_SYMBOLS = [
     "kx_free_audio", "kx_infer_device", "kx_sync", "kx_set_pinned_durations", "kx_warmup", "kx_arena_bytes", "kx_call_times", "kx_model_status", "kx_model_info", "kx_dispatcher_health", "kx_set_utterance_base", "kx_set_lanes",
     "kx_set_conv_mode", "kx_get_conv_mode", "kx_set_stft_variant", "kx_get_stft_variant",
     "kx_profile_enable", "kx_profile_read", "kx_profile_detail", "kx_profile_aux", "kx_diag_enable", "kx_diag_count", "kx_diag_get", "kx_set_act_prescale", "kx_set_voice_table", "kx_infer_voices",
-    "kx_infer_packed", "kx_free_packed", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
+    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
     "kx_dispatcher_stats", "kx_dispatcher_failures", "kx_dispatcher_destroy", "kx_debug_tap",
 ]
 
@@ -192,6 +197,16 @@ def _ptr(a: Optional[np.ndarray]):
 
 def _f32(a) -> Optional[np.ndarray]:
     return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _decode_packed(raw: bytes, fmt: int):
+    """A request's region as Python hands it out: samples as an array for forms 0..2, the body as bytes for forms 3 and 4."""
+    if fmt in (PACK_WAV_F32, PACK_WAV16_BASE64):
+        return raw
+    if fmt == PACK_PCM16_MONO:
+        return np.frombuffer(raw, dtype=np.int16).copy()
+    a = np.frombuffer(raw, dtype=np.float32).copy()
+    return a.reshape(-1, 2) if fmt == PACK_F32_STEREO else a
 
 
 class HipKoko:
@@ -357,6 +372,42 @@ class HipKoko:
         self._check(self._lib.kx_infer_packed(self._h, _ptr(ids), ids.shape[1], _ptr(lens), B, _ptr(st), _ptr(sp),
                                               sp.shape[0], seed, flags, fmt, C.byref(out), _ptr(nbytes), _ptr(nsamp)))
         return self._unpack(out, nbytes, nsamp, B, fmt)
+
+    def infer_requests(self, tokens, chunks_per_request, styles=None, voice_ids=None, weights=None, speeds=(1.0,), seed: int = 0,
+                       flags: int = 0, fmt=0):
+        """Several requests of several chunks in one forward (kx_infer_requests): `tokens` are the B chunks (each 0-wrapped),
+        request r owns chunks_per_request[r] consecutive ones.  The voice is per chunk: `styles` [B, 256], or `voice_ids` /
+        `weights` [B, max_mix] as infer_voices.  `fmt` = one PACK_* form for all, or one per request.  Returns one entry per
+        request: its chunks' samples back to back as an array for forms 0..2 (float32, [n, 2] float32, int16), the body as
+        `bytes` for PACK_WAV_F32 and PACK_WAV16_BASE64."""
+        ids, lens = self._ids_lens(tokens)
+        B = len(tokens)
+        cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32).reshape(-1)
+        R = cpr.shape[0]
+        fm = np.ascontiguousarray(fmt, dtype=np.int32).reshape(-1)
+        st = v = w = None
+        mm = 0
+        if styles is not None:
+            st = _f32(np.asarray(styles, dtype=np.float32).reshape(B, STYLE_DIM))
+        if voice_ids is not None:
+            v = np.ascontiguousarray(np.asarray(voice_ids, dtype=np.int32).reshape(B, -1))
+            w = _f32(np.asarray(weights, dtype=np.float32).reshape(B, -1))
+            mm = v.shape[1]
+        sp = _f32(np.asarray(speeds, dtype=np.float32).reshape(-1))
+        out = C.c_void_p()
+        nbytes, nsamp = np.zeros(max(R, 1), np.int64), np.zeros(max(R, 1), np.int64)
+        self._check(self._lib.kx_infer_requests(self._h, _ptr(ids), ids.shape[1], _ptr(lens), B, _ptr(cpr), R, _ptr(st), _ptr(v),
+                                                _ptr(w), mm, _ptr(sp), sp.shape[0], seed, flags, _ptr(fm), fm.shape[0],
+                                                C.byref(out), _ptr(nbytes), _ptr(nsamp)))
+        total = int(nbytes[:R].sum())
+        raw = C.string_at(out, total) if total else b""
+        self._lib.kx_free_packed(out)
+        res, o = [], 0
+        for r in range(R):
+            part = raw[o: o + int(nbytes[r])]
+            o += int(nbytes[r])
+            res.append(_decode_packed(part, int(fm[r if fm.shape[0] > 1 else 0])))
+        return res
 
     def infer_device(self, d_ids: int, t_stride: int, lens_host: np.ndarray, d_styles: int, speeds_host: np.ndarray,
                      d_audio: int, audio_ld: int, d_frames: int, seed: int = 0, flags: int = 0) -> int:
@@ -568,6 +619,40 @@ class Dispatcher:
             return np.frombuffer(raw, dtype=np.int16).copy()
         arr = np.frombuffer(raw, dtype=np.float32).copy()
         return arr.reshape(-1, 2) if fmt == 1 else arr
+
+    def submit_request(self, chunks: Sequence[Sequence[int]], styles=None, voices=None, speed: float = 1.0, seed: int = 0,
+                       fmt: int = 0):
+        """A request of 1 .. max_batch chunks (kx_dispatcher_submit_request): `chunks` = the 0-wrapped id lists; `styles` = one
+        256-float row per chunk, OR `voices` as in submit_ex (one voice spec for the request); `fmt` = a PACK_* form 0..4.
+        Returns what HipKoko.infer_requests returns for one request: an array (forms 0..2) or the body as bytes (3, 4)."""
+        lens = np.array([len(c) for c in chunks], dtype=np.int32)
+        a = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.int64).reshape(-1) for c in chunks])
+                                 if len(chunks) else np.zeros(0, np.int64))
+        st = vid = w = None
+        n_mix = 0
+        if styles is not None:
+            st = _f32(np.asarray(styles, dtype=np.float32).reshape(-1))
+            if st.shape[0] != STYLE_DIM * len(chunks):
+                raise ValueError(f"one style row of {STYLE_DIM} floats per chunk is required")
+        elif voices is None:
+            raise ValueError("submit_request: give styles (one row per chunk) or voices")
+        elif isinstance(voices, (int, np.integer)):
+            vid, n_mix = np.array([voices], dtype=np.int32), 1
+        else:
+            vid = np.array([v for v, _ in voices], dtype=np.int32)
+            w = np.array([x for _, x in voices], dtype=np.float32)
+            n_mix = len(vid)
+        out, nb, ns = C.c_void_p(), C.c_int64(0), C.c_int64(0)
+        err = C.create_string_buffer(256)
+        rc = self._lib.kx_dispatcher_submit_request(self._d, _ptr(a), _ptr(lens), len(chunks), _ptr(st), _ptr(vid), _ptr(w), n_mix,
+                                                    float(speed), seed, fmt, C.byref(out), C.byref(nb), C.byref(ns), err, len(err))
+        if rc != 0:
+            raise KokoroxHipError(rc, err.value.decode())
+        try:
+            raw = C.string_at(out, nb.value)
+        finally:
+            self._lib.kx_free_packed(out)
+        return _decode_packed(raw, fmt)
 
     def stats(self):
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
@@ -816,3 +901,25 @@ def harmonic_source(f0, lin_w, lin_b, seed=0, utt_base=0, noise_off=False, devic
     _err_call(lib.kx_test_source, device, _ptr(f0), B, F2, _ptr(lin_w), float(lin_b), seed, utt_base,
               1 if noise_off else 0, _ptr(out))
     return out
+
+
+def pack_requests(audio, frames, chunks_per_request, formats, device=0):
+    """The request packer alone (kx_test_pack_requests): audio [B, audio_ld] with row b valid for 600 * frames[b] samples,
+    request r = chunks_per_request[r] consecutive rows in form formats[r].  Returns the R regions as bytes."""
+    lib = load_test_library()
+    audio = _f32(audio)
+    B, ld = audio.shape
+    fr = np.ascontiguousarray(frames, dtype=np.int32)
+    cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32)
+    fm = np.ascontiguousarray(formats, dtype=np.int32)
+    R = cpr.shape[0]
+    assert fr.shape == (B,) and fm.shape == (R,)
+    cap = 8 * 600 * int(fr.sum()) + 64 * R
+    out = np.zeros(cap, dtype=np.uint8)
+    nb = np.zeros(R, dtype=np.int64)
+    _err_call(lib.kx_test_pack_requests, device, _ptr(audio), B, ld, _ptr(fr), _ptr(cpr), R, _ptr(fm), _ptr(out), cap, _ptr(nb))
+    raw, res, o = out.tobytes(), [], 0
+    for r in range(R):
+        res.append(raw[o: o + int(nb[r])])
+        o += int(nb[r])
+    return res

@@ -7,11 +7,15 @@ Reference (paths under /root/reference/kokorox/src/tts/):
   * `tokenize_with_variant` tokenize.rs:35-67  — char -> id, unknown chars dropped
   * padding                 koko.rs:1161-1175  — optional id-30 prefix, 0 at both ends
   * chunk loop              koko.rs:947-1191   — one forward per <= 500-token chunk, waveforms appended
+  * float WAV body          utils/wav.rs:18-50, kokorox-openai/src/lib.rs:416-425  — `wav_f32_body`
+  * base64 16-bit WAV       kokorox-websocket/src/lib.rs:696-736 (`encode_audio`)   — `wav16_base64`
 These stay on the host (north_star: "the voice-style mixer ... stay identical"); the GPU
 only ever sees ids and one 256-float row per utterance.
 """
 from __future__ import annotations
 
+import base64
+import struct
 from typing import Dict, List, Sequence
 
 import numpy as np
@@ -101,3 +105,56 @@ def tts_chunks(model, styles: Dict[str, np.ndarray], style_name: str, chunk_toke
         return np.zeros(0, dtype=np.float32)
     outs = model.infer_batch(toks, np.asarray(rows, dtype=np.float32), [float(speed)], seed=seed)
     return np.concatenate([np.asarray(o, dtype=np.float32) for o in outs])
+
+
+SAMPLE_RATE = 24000
+
+
+def wav_f32_body(samples) -> bytes:
+    """The HTTP body of kokorox-openai/src/lib.rs:416-425: the 44 bytes of `WavHeader::new(1, 24000, 32).write_header`
+    (utils/wav.rs:18-50: IEEE float, both size fields the reference's 0xFFFFFFFF placeholders), then `to_le_bytes` of
+    every sample: bit copies, a NaN keeps its payload."""
+    s = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+    hdr = struct.pack("<4sI4s4sIHHIIHH4sI", b"RIFF", 0xFFFFFFFF, b"WAVE", b"fmt ", 16, 3, 1, SAMPLE_RATE, SAMPLE_RATE * 4, 4, 32,
+                      b"data", 0xFFFFFFFF)
+    return hdr + s.astype("<f4", copy=False).tobytes()
+
+
+def pcm16(samples) -> np.ndarray:
+    """`(s.clamp(-1.0, 1.0) * 32767.0) as i16` with Rust's meaning: clamp keeps a NaN and the cast turns it into 0, +-inf
+    clamp to +-1, the product is rounded to f32 and then truncated toward zero."""
+    s = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+    nan = np.isnan(s)
+    c = np.clip(np.where(nan, np.float32(0), s), np.float32(-1.0), np.float32(1.0)).astype(np.float32)
+    return np.trunc(c * np.float32(32767.0)).astype(np.int16)
+
+
+def wav16_base64(samples) -> bytes:
+    """The WebSocket chunk of `encode_audio` (kokorox-websocket/src/lib.rs:696-736): standard base64 (`=` padding, no line
+    breaks) of a 16-bit mono WAV file at 24 kHz, header with its true sizes, samples through `pcm16`."""
+    pcm = pcm16(samples)
+    n = 2 * pcm.shape[0]
+    if 36 + n > 0xFFFFFFFF:
+        raise ValueError("wav16_base64: a 16-bit WAV file cannot hold that many samples")
+    hdr = struct.pack("<4sI4s4sIHHIIHH4sI", b"RIFF", 36 + n, b"WAVE", b"fmt ", 16, 1, 1, SAMPLE_RATE, SAMPLE_RATE * 2, 2, 16,
+                      b"data", n)
+    return base64.b64encode(hdr + pcm.astype("<i2", copy=False).tobytes())
+
+
+def tts_request(model, styles: Dict[str, np.ndarray], style_name: str, chunk_tokens: Sequence[Sequence[int]],
+                speed: float = 1.0, initial_silence: int = 0, seed: int = 0, fmt: int = 0):
+    """`tts_chunks` through `model.infer_requests`: the chunks of one text as ONE request of one batched forward, its body
+    (header of the form, then the chunks' samples with nothing between them) packed on the GPU.  `fmt` is a PACK_* form of
+    hip_koko: 0..2 give the samples as an array, 3 (`wav_f32_body`) and 4 (`wav16_base64`) the bytes a server sends.  An
+    empty chunk list and an empty chunk are errors (a request has at least one chunk)."""
+    toks, rows = [], []
+    for ch in chunk_tokens:
+        t = [30] * int(initial_silence) + [int(v) for v in ch]
+        if not t:
+            raise ValueError("tts_request: empty chunk")
+        rows.append(mix_styles(styles, style_name, len(t))[0])
+        toks.append([0] + t + [0])
+    if not toks:
+        raise ValueError("tts_request: a request has at least one chunk")
+    return model.infer_requests(toks, [len(toks)], styles=np.asarray(rows, dtype=np.float32), speeds=[float(speed)], seed=seed,
+                                fmt=fmt)[0]

@@ -1,0 +1,27 @@
+"""Three packed calls of the bench batch (64 x 130 tokens, durations pinned 3,3,3,4 -> 422 frames each) in the form given on
+the command line: 'old2' = kx_infer_packed form 2 (pack_audio_kernel), '2' / '3' / '4' = kx_infer_requests in that form, every
+row a request of its own (pack_requests_kernel).  Meant to run under the profiler, one form per run:
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o t -- python tools/pack_profile.py 4
+profiles/pack_kernels_stats.txt holds the rows of the kernel_stats.csv files."""
+import os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch  # noqa
+from kokorox_amd import hip_koko as hk, weights as W
+from oracle import kokoro_ref as R
+which = sys.argv[1]
+m = hk.HipKoko.new(W.ensure_synthetic_blob())
+B = 64
+toks = [list(int(v) for v in R.synthetic_inputs(1, 128, seed=40 + b)[0]) for b in range(B)]
+rows = [W.synthetic_voices(1)[0, 128, 0]] * B
+m.set_pinned_durations([3, 3, 3, 4])
+for it in range(3):
+    if which == "old2":
+        out = m.infer_packed(toks, rows, fmt=2)
+        n = sum(o.nbytes for o in out)
+    else:
+        out = m.infer_requests(toks, [1] * B, styles=rows, fmt=int(which))
+        n = sum(len(o) if isinstance(o, bytes) else o.nbytes for o in out)
+print("form", which, "bytes", n, "frames", len(toks[0]))
+m.close()
