@@ -187,12 +187,10 @@ ConvCall conv_call(const ConvW& w, const T& in, const T& out, const ConvOpts& o,
     // outputs that no cache can hold until the next layer reads them (> 512 MB: L2 is 32 MB, MALL 256 MB) are streamed by the direct-A
     // kernels' interior stores (non-temporal stores and residual loads); smaller ones (small batches, the token axis, the decoder)
     // stay cacheable
-    static const long stream_mb = getenv("KX_EPI_STREAM_MB") ? atol(getenv("KX_EPI_STREAM_MB")) : 512;
+    constexpr double EPI_STREAM_BYTES = 512.0 * 1048576.0;
     a.epi_stream = ctx.epi_stream >= 0 ? ctx.epi_stream
-                                       : plan.form != FORM_F32 && stream_mb >= 0 &&
-                                             (double)ctx.B * w.rows * out.ld * 4.0 > (double)stream_mb * 1048576.0;
-    static const int xcd_swz = getenv("KX_XCD_SWIZZLE") ? atoi(getenv("KX_XCD_SWIZZLE")) : 1;
-    a.xcd_swizzle = xcd_swz;
+                                       : plan.form != FORM_F32 && (double)ctx.B * w.rows * out.ld * 4.0 > EPI_STREAM_BYTES;
+    a.xcd_swizzle = 1;
     a.x_prescale = std::ldexp(1.0f, w.act_shift);
     a.w_unscale = std::ldexp(w.unscale, -w.act_shift);  // (exact: both are powers of two)
     if (plan.merged) {  // k = 1 GEMM on a short axis: one merged column space for the whole batch

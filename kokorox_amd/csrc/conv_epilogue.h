@@ -97,7 +97,7 @@ __device__ __forceinline__ void conv_store_rmw(const ConvArgs& a, f32x16 (&acc)[
     constexpr bool ACCUM = LOADS >= 2;  // (whether the y read-back buffers exist)
     const int cmax = ncols - 1, rmax = a.Cout - 1;
     const bool merged = a.merge_T > 0;
-    // row strides in bytes (timing ablations, results wrong: KX_DBG bit 32 stores every row of the tensor over row 0,
+    // row strides in bytes (timing ablations, results wrong: ConvArgs::dbg bit 32 stores every row of the tensor over row 0,
     // bit 64 reads the residual / running sum from row 0 -- same instruction stream, no HBM traffic behind it)
     const unsigned yrs = (a.dbg & 32) ? 0u : 4u * (tmaj ? 1u : (unsigned)a.y_ld);
     const unsigned rrs = (a.dbg & 64) ? 0u : 4u * (unsigned)a.r_ld;

@@ -484,26 +484,12 @@ void launch_conv(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s) {
                 return;
             }
             [[fallthrough]];
-        case FORM_DA_W2: {
-            static const int dephase = getenv("KX_DEPHASE") ? atoi(getenv("KX_DEPHASE")) : 0;  // permille of a tile's estimated time
-            static const int dephase_mode = getenv("KX_DEPHASE_MODE") ? atoi(getenv("KX_DEPHASE_MODE")) : 1;
-            ConvArgs d;
-            const ConvArgs* ap = &a;
-            if (dephase > 0 && p.bn == 256) {  // (diagnostic, profiles/r03_lanes_dephase.txt: no effect)
-                d = a;
-                const long grid_n = (long)((p.cols + 255) / 256) * ((a.Cout + 127) / 128) * B;
-                // a tile: n_chunks x K x 8 column tiles x 3 MFMAs of 32 cycles, two waves per SIMD, ~80 % pipe use; + the epilogue
-                const double tile_cycles = (double)a.n_chunks16 * a.K * 8 * 96 * 2.5 + 50000.0;
-                d.dephase_cycles = grid_n >= 1024 ? (int)(tile_cycles * dephase / 1000.0) : 0;
-                d.dephase_mode = dephase_mode;
-                ap = &d;
-            }
+        case FORM_DA_W2:
             if (p.form == FORM_DA_W2)
-                launch_conv16_da_w2(p, *ap, B, s);
+                launch_conv16_da_w2(p, a, B, s);
             else
-                launch_conv16_da(p, *ap, B, s);
+                launch_conv16_da(p, a, B, s);
             return;
-        }
     }
     throw Error(1, "conv1d: unknown kernel form");
 }

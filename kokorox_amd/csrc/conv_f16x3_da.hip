@@ -1,8 +1,8 @@
 // conv1d f16x3, "direct A" form of the 128 x 256 tile: the weight fragments go from global memory (L2) straight into
 // the registers the MFMAs read them from; LDS holds only the transformed input window (double-buffered).
 //
-// Why (profiles/r02_weight_stream_ablations.txt): in conv1d_f16x3_kernel the weights reach LDS by LDS-DMA
-// (global_load_lds), 24 one-KiB copy instructions per 3-tap piece and workgroup.  Removing those copies (KX_DBG bit 2)
+// Why (profiles/r02_weight_stream_ablations.txt, the timing ablations it records as bits): in conv1d_f16x3_kernel the weights
+// reach LDS by LDS-DMA (global_load_lds), 24 one-KiB copy instructions per 3-tap piece and workgroup.  Removing those copies (bit 2)
 // takes the 128 -> 128, k = 11 launches from 25.7 to 18.0 ms per step; keeping every copy INSTRUCTION but pointing them
 // all at one hot KiB (bit 256) leaves 24.8 ms: the cost is the copy instructions, not their bytes.  A CU moves
 // ~12 B/clk through LDS-DMA while the fragment reads keep the LDS busy (the producers of a wave-specialised form that was built and dropped in round 2 measured
@@ -467,14 +467,6 @@ __global__ __launch_bounds__(256, (NTT == 8 || S16) ? 2 : 3) void conv1d_f16x3_d
     // exactly its own duration (7.2 of 24.8 ms on the k = 11 launches; dropping it, loads kept: 17.7 ms): the partner
     // workgroup's MFMAs do not fill the gap (two co-resident workgroups that start together stay in phase).  A wave's own
     // MFMAs do: the matrix pipe runs an MFMA for 32 cycles while the wave's vector instructions keep issuing.
-#ifdef KX_DA_NO_XFORM
-    auto keep_elem = [&](const int hh) __attribute__((always_inline)) {
-        const int U = hh / 2, half = hh & 1;
-        const bool split = SPLIT && U >= 4 * NJF;
-        const int j = split ? NJF : U % NJF, cr = split ? 2 * (U - 4 * NJF) + half : 2 * (U / NJF) + half;
-        asm volatile("" ::"v"(raw[j][cr]), "v"(praw[0]), "v"(praw[1]), "v"(praw[2]), "v"(praw[3]));
-    };
-#endif
     float al_rcp_x = 1.f;  // (alpha | 1 / alpha by lane, set by the first part of a chunk's transform)
     float y_carry = 0.f;   // (first element of a pair, from half 0 to half 1)
     float xt_ = 0.f, xz_ = 0.f;  // (state of the element in flight: the affine value, then z = r^2 / sin^2)
@@ -636,13 +628,6 @@ __global__ __launch_bounds__(256, (NTT == 8 || S16) ? 2 : 3) void conv1d_f16x3_d
     // Three-deep A ring with STATIC slots: step s uses slot s % 3 and refills it for step s + 3 as soon as its MFMAs are
     // issued, so a fragment is requested two whole steps before its use and nothing ever moves between registers.  The
     // (chunk, tap) walk is flattened and unrolled by three for that.
-#ifdef KX_DA_STAMPS  // diagnostic build only (tools/stamp_timeline.py): per-workgroup phase stamps; nothing reads them back
-    unsigned long long st0 = 0, st1 = 0, st2 = 0, cyc0 = 0, acc_bar = 0, acc_wait = 0;
-    if (a.stamps) {
-        st0 = __builtin_amdgcn_s_memrealtime();
-        cyc0 = __builtin_readcyclecounter();
-    }
-#endif
     u32x4 ah0 = {0, 0, 0, 0}, al0 = {0, 0, 0, 0}, ah1 = {0, 0, 0, 0}, al1 = {0, 0, 0, 0}, ah2 = {0, 0, 0, 0}, al2 = {0, 0, 0, 0};
     u32x4 a2h[2][2] = {}, a2l[2][2] = {};  // W2 / S16: [slot][row block]
     if constexpr (W2) load_A2(0, a2h[1], a2l[1]);  // (a chunk's first step arrives in slot 1, see below)
@@ -662,9 +647,6 @@ __global__ __launch_bounds__(256, (NTT == 8 || S16) ? 2 : 3) void conv1d_f16x3_d
     stage_from_raw(Xs, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (once: the ages below start from an empty queue)
     __syncthreads();
-#ifdef KX_DA_STAMPS
-    if (a.stamps) st1 = __builtin_amdgcn_s_memrealtime();
-#endif
     int age0 = 0, age1 = 0, age2 = 0;
     if (n_chunks > 1 && !(a.dbg & 1)) {
         load_raw(1);
@@ -690,16 +672,6 @@ __global__ __launch_bounds__(256, (NTT == 8 || S16) ? 2 : 3) void conv1d_f16x3_d
         // Per accumulator: cross terms of a group, then the pair's a_hi b_hi; groups and taps ascending.
         static_assert(W64, "S16: the 64-column window of the unrolled forms");
         constexpr int NB = 2 * NT, HS = (KT - 1) / 2, TB = KT * NB, NA = HS * NB, SB0 = (HS + 1) * NB;
-#ifdef KX_DA_STAMPS  // diagnostic build: 10 ns ticks a wave spends in the loop's barriers (o[7]) and in its ring waits (o[6])
-        unsigned long long tb0 = 0;
-#define F8_BAR_T0 if (a.stamps) tb0 = __builtin_amdgcn_s_memrealtime();
-#define F8_BAR_T1 if (a.stamps) acc_bar += __builtin_amdgcn_s_memrealtime() - tb0;
-#define F8_WAIT_T1 if (a.stamps) acc_wait += __builtin_amdgcn_s_memrealtime() - tb0;
-#else
-#define F8_BAR_T0
-#define F8_BAR_T1
-#define F8_WAIT_T1
-#endif
 #ifndef KX_F8_RH
 #define KX_F8_RH ((KT - 1) % 3 != 0 ? 3 : 4)
 #endif
@@ -800,21 +772,15 @@ __global__ __launch_bounds__(256, (NTT == 8 || S16) ? 2 : 3) void conv1d_f16x3_d
                 constexpr int c = FS::cross_of(p), xsl = c >= 0 ? c % RC : 0;
                 if constexpr (nb == 0) {
                     if constexpr (p == HS) {
-                        F8_BAR_T0
                         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // barrier 1
-                        F8_BAR_T1
                         load_raw(ch0 + 2 < n_chunks ? ch0 + 2 : n_chunks - 1);
                         load_blk_h(p, 0, fh[e]);
                     }
                     if constexpr (p == HS + 1) {
-                        F8_BAR_T0
                         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // barrier 2
-                        F8_BAR_T1
                     }
                     constexpr int ag_h = FS::age(0, p), ag_x = c >= 0 ? FS::age(1, c) : 63;
-                    F8_BAR_T0
                     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ag_h < ag_x ? ag_h : ag_x) : "memory");
-                    F8_WAIT_T1
                     __builtin_amdgcn_sched_barrier(0);
                     asm volatile("" : "+v"(hs[sl][0]), "+v"(hs[sl][1]));
                     if constexpr (c >= 0) asm volatile("" : "+v"(xs[xsl][0]), "+v"(xs[xsl][1]), "+v"(xs[xsl][2]), "+v"(xs[xsl][3]));
@@ -826,11 +792,7 @@ __global__ __launch_bounds__(256, (NTT == 8 || S16) ? 2 : 3) void conv1d_f16x3_d
                     if constexpr (FS::cross_of(ip / NB) >= 0) load_blk_x(FS::cross_of(ip / NB), ip % NB, fx[e ^ 1]);
                 }
                 if constexpr (i % G == 0) __builtin_amdgcn_sched_barrier(0);
-#ifdef KX_F8_NO_CROSS  // (diagnostic build: the cross-term MFMAs dropped, results wrong: timing only)
-                if constexpr (false) {
-#else
                 if constexpr (c >= 0) {
-#endif
                     const v8i x0 = v8i{(int)xs[xsl][0][0], (int)xs[xsl][0][1], (int)xs[xsl][0][2], (int)xs[xsl][0][3],
                                        (int)xs[xsl][1][0], (int)xs[xsl][1][1], (int)xs[xsl][1][2], (int)xs[xsl][1][3]};
                     const v8i x1 = v8i{(int)xs[xsl][2][0], (int)xs[xsl][2][1], (int)xs[xsl][2][2], (int)xs[xsl][2][3],
@@ -849,11 +811,6 @@ __global__ __launch_bounds__(256, (NTT == 8 || S16) ? 2 : 3) void conv1d_f16x3_d
                 constexpr int h1 = (inA || inB) ? FS::hu_before(NB, NA, HU, first, I0, rel + 1) : 0;
                 static_assert(h1 - h0 <= 2, "at most two half-units per block");
                 uint4* Xdst = Xs + (inA ? 1 : 0) * XBUF;
-#ifdef KX_DA_NO_XFORM  // (diagnostic build: the transform's vector work and LDS writes dropped, image stale: timing only)
-                if constexpr (h1 > h0) keep_elem(h0);
-                if constexpr (h1 > h0 + 1) keep_elem(h0 + 1);
-                (void)Xdst;
-#else
                 if constexpr (h1 > h0) {
                     xform_a(h0 / 2, h0 & 1, 0);
                     xform_b();
@@ -864,7 +821,6 @@ __global__ __launch_bounds__(256, (NTT == 8 || S16) ? 2 : 3) void conv1d_f16x3_d
                     xform_b();
                     xform_c((h0 + 1) / 2, (h0 + 1) & 1, Xdst, 0);
                 }
-#endif
                 if constexpr (i % G == G - 1) {  // the pipeline of the region: its half-units spread over its MFMAs by their duration
                     constexpr int ig = i - (G - 1);
                     constexpr bool gA = ig < NA, gB = ig >= SB0;
@@ -899,9 +855,7 @@ __global__ __launch_bounds__(256, (NTT == 8 || S16) ? 2 : 3) void conv1d_f16x3_d
                     }
                 }
             });
-            F8_BAR_T0
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // barrier 3
-            F8_BAR_T1
             load_raw(ch0 + 3 < n_chunks ? ch0 + 3 : n_chunks - 1);
             load_blk_h(0, 0, fh[0]);
             load_blk_x(0, 0, fx[0]);
@@ -1267,27 +1221,16 @@ __global__ __launch_bounds__(256, (NTT == 8 || S16) ? 2 : 3) void conv1d_f16x3_d
                 constexpr int h1 = i + 1 > I0 ? ((i + 1 - I0) * HUX) / (TILES - I0) : 0;
                 // (no run-time condition around them: a branch would put them in a block of their own, behind the MFMAs
                 // instead of between them)
-#ifdef KX_DA_NO_XFORM  // (diagnostic build: the transform's vector work and LDS writes dropped, image stale: compare CYCLES, not time)
-                constexpr bool do_xform = false;
-#else
-                constexpr bool do_xform = true;
-#endif
-#ifdef KX_DA_NO_XFORM
-                // (the loads stay alive and counted -- the hand-counted ring waits assume every prefetch batch -- only the vector
-                // work and the LDS writes go)
-                if constexpr (h1 > h0) keep_elem(h0);
-                if constexpr (h1 > h0 + 1) keep_elem(h0 + 1);
-#endif
                 if constexpr (PRE) {
                     if constexpr (h1 > h0) pre_unit(h0, Xs + (cur ^ 1) * XBUF);
                     if constexpr (h1 > h0 + 1) pre_unit(h0 + 1, Xs + (cur ^ 1) * XBUF);
                 } else {
-                if constexpr (do_xform && h1 > h0) {
+                if constexpr (h1 > h0) {
                     xform_a(h0 / 2, h0 & 1, ch + 1);
                     xform_b();
                     xform_c(h0 / 2, h0 & 1, Xs + (cur ^ 1) * XBUF, ch + 1);
                 }
-                if constexpr (do_xform && h1 > h0 + 1) {
+                if constexpr (h1 > h0 + 1) {
                     xform_a((h0 + 1) / 2, (h0 + 1) & 1, ch + 1);
                     xform_b();
                     xform_c((h0 + 1) / 2, (h0 + 1) & 1, Xs + (cur ^ 1) * XBUF, ch + 1);
@@ -1341,14 +1284,7 @@ __global__ __launch_bounds__(256, (NTT == 8 || S16) ? 2 : 3) void conv1d_f16x3_d
                 }
             });
             if (more) {
-#ifdef KX_DA_STAMPS
-                unsigned long long tb0 = 0;
-                if (a.stamps) tb0 = __builtin_amdgcn_s_memrealtime();
-#endif
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#ifdef KX_DA_STAMPS
-                if (a.stamps) acc_bar += __builtin_amdgcn_s_memrealtime() - tb0;
-#endif
                 cur ^= 1;
                 if (ch + 2 < n_chunks && !(a.dbg & 1)) {
                     load_raw(ch + 2);
@@ -1443,9 +1379,6 @@ __global__ __launch_bounds__(256, (NTT == 8 || S16) ? 2 : 3) void conv1d_f16x3_d
     }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (belt and braces: no hand-counted load is in flight past this point)
-#ifdef KX_DA_STAMPS
-    if (a.stamps) st2 = __builtin_amdgcn_s_memrealtime();
-#endif
     if (a.dbg & 8) return;
     // the statistics scratch of the epilogue lives in the input buffers: everybody must be done reading them
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -1472,19 +1405,6 @@ __global__ __launch_bounds__(256, (NTT == 8 || S16) ? 2 : 3) void conv1d_f16x3_d
     } else {
         conv_store_group<EPI_ROWS>(a, acc, a.w_unscale, b, ct * BM + wave * 32, t0, r, h, ncols, Lout, tile_x, stat_scr, wide_scr);
     }
-#ifdef KX_DA_STAMPS
-    if (a.stamps && tid == 0) {
-        const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-        unsigned long long* o = a.stamps + (unsigned long long)lin * 8;
-        o[0] = st0; o[1] = st1; o[2] = st2;
-        __builtin_amdgcn_s_waitcnt(0);
-        o[3] = __builtin_amdgcn_s_memrealtime();
-        o[4] = __builtin_amdgcn_s_getreg(63492);  // HW_REG_HW_ID
-        o[5] = __builtin_readcyclecounter() - cyc0;
-        o[6] = F8 ? acc_wait : __builtin_amdgcn_s_getreg(63508);  // HW_REG_XCC_ID; F8 forms: 10 ns ticks in the ring waits of the main loop (wave 0)
-        o[7] = acc_bar;  // 10 ns ticks spent in the chunk barriers of the main loop (wave 0)
-    }
-#endif
 }
 
 // Launchers.  Every direct-A unit includes this file for the kernel; each instantiates only its own forms, through its one entry

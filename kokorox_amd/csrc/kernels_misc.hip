@@ -744,81 +744,8 @@ void launch_copy_rows(const float* src, long sbs, int sld, float* dst, long dbs,
 }
 
 // ---- bidirectional LSTM recurrence (hidden 256) -------------------------------------------
-// gx [B][L][2048] holds W_ih x + b_ih + b_hh for both directions (conv kernel, time-major store).  One workgroup of
-// 1024 threads per (utterance, direction): thread r owns gate row r and walks W_hh^T[k][r] against h in LDS, then
-// the first 256 threads apply the cell update.  A step is bound by how fast one CU can pull the 1 MB of W_hh^T
-// through its L1 (~60 B/clk); the first LSTM_LDS_K of the 256 k-rows therefore stay in LDS for the whole sequence
-// (36 x 4 KB = 144 KB) and the next LSTM_REG_K in registers, the rest streams from L2 every step.  The image is
-// [k/4][row][4 k], so every thread moves 16-byte pieces (a quarter of the load instructions of a [k][row] image:
-// the step got 20 % shorter; with 4-byte loads, more than 32 register rows made it 35-50 % longer).
-constexpr int LSTM_LDS_K = 36;
-constexpr int LSTM_REG_K = 64;
-__global__ __launch_bounds__(1024) void lstm_kernel(const float* gx, long gx_bs, int gx_ld, const float* whhT,
-                                                    float* y, long y_bs, int y_ld, LenMap len) {
-    extern __shared__ __attribute__((aligned(16))) float lstm_smem[];
-    float* hs = lstm_smem;                                          // [256]
-    float* gates = hs + 256;                                        // [1024]
-    float4* wl = reinterpret_cast<float4*>(gates + 1024);           // [LSTM_LDS_K / 4][1024] x 4 k
-    const int b = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x;
-    const int L = len_of(len, b);
-    // image [k4][row][4 k]: thread = row, every access is one 16-byte piece, coalesced across the workgroup
-    const float4* W4 = reinterpret_cast<const float4*>(whhT + (long)dir * 256 * 1024) + tid;
-    float c = 0.f;
-    if (tid < 256) hs[tid] = 0.f;
-#pragma unroll
-    for (int k4 = 0; k4 < LSTM_LDS_K / 4; ++k4) wl[k4 * 1024 + tid] = W4[(long)k4 * 1024];
-    // ... and the next LSTM_REG_K k-rows in registers
-    float4 wreg[LSTM_REG_K / 4];
-#pragma unroll
-    for (int k4 = 0; k4 < LSTM_REG_K / 4; ++k4) wreg[k4] = W4[(long)(LSTM_LDS_K / 4 + k4) * 1024];
-    __syncthreads();
-    for (int step = 0; step < L; ++step) {
-        const int t = dir ? (L - 1 - step) : step;
-        float acc = gx[b * gx_bs + (long)t * gx_ld + dir * 1024 + tid];
-        const float4* h4 = reinterpret_cast<const float4*>(hs);
-        // streamed part first in program order: its loads are in flight while the resident parts are summed
-        float acc2 = 0.f;
-#pragma unroll 4
-        for (int k4 = (LSTM_LDS_K + LSTM_REG_K) / 4; k4 < 64; ++k4) {
-            const float4 hv = h4[k4];
-            const float4 w = W4[(long)k4 * 1024];
-            acc2 = fmaf(w.x, hv.x, acc2);
-            acc2 = fmaf(w.y, hv.y, acc2);
-            acc2 = fmaf(w.z, hv.z, acc2);
-            acc2 = fmaf(w.w, hv.w, acc2);
-        }
-#pragma unroll
-        for (int k4 = 0; k4 < LSTM_LDS_K / 4; ++k4) {
-            const float4 hv = h4[k4];
-            const float4 w = wl[k4 * 1024 + tid];
-            acc = fmaf(w.x, hv.x, acc);
-            acc = fmaf(w.y, hv.y, acc);
-            acc = fmaf(w.z, hv.z, acc);
-            acc = fmaf(w.w, hv.w, acc);
-        }
-#pragma unroll
-        for (int k4 = 0; k4 < LSTM_REG_K / 4; ++k4) {
-            const float4 hv = h4[LSTM_LDS_K / 4 + k4];
-            acc = fmaf(wreg[k4].x, hv.x, acc);
-            acc = fmaf(wreg[k4].y, hv.y, acc);
-            acc = fmaf(wreg[k4].z, hv.z, acc);
-            acc = fmaf(wreg[k4].w, hv.w, acc);
-        }
-        gates[tid] = acc + acc2;
-        __syncthreads();
-        if (tid < 256) {
-            const float ig = 1.0f / (1.0f + expf(-gates[tid]));
-            const float fg = 1.0f / (1.0f + expf(-gates[256 + tid]));
-            const float gg = tanhf(gates[512 + tid]);
-            const float og = 1.0f / (1.0f + expf(-gates[768 + tid]));
-            c = fg * c + ig * gg;
-            const float hn = og * tanhf(c);
-            hs[tid] = hn;
-            y[b * y_bs + (long)(dir * 256 + tid) * y_ld + t] = hn;
-        }
-        __syncthreads();
-    }
-}
+// gx [B][L][2048] holds W_ih x + b_ih + b_hh for both directions (conv kernel, time-major store); W_hh^T is the image
+// [k/4][row][4 k], so every thread moves 16-byte pieces.
 // One unit's cell update from its four gate pre-activations (PyTorch order i, f, g, o); returns h.  ONE definition for every
 // recurrence kernel, with the multiply-add spelled out: left to -ffp-contract the same expression was fused in one kernel and
 // not in another, and the resident-weights forms and their streaming fall-back must agree bit for bit.
@@ -833,8 +760,8 @@ __device__ __forceinline__ float lstm_cell(float pi, float pf, float pg, float p
 }
 
 // ---- the same recurrence with W_hh fully resident: two CUs per (utterance, direction) -------------------------------
-// One CU cannot hold the 1 MiB of W_hh (512 KiB of registers + 160 KiB of LDS), which is why lstm_kernel streams 60 % of
-// it from L2 on every step (5.5 us per step, bound by the CU's L1 fill rate).  Here the recurrence of one (utterance,
+// One CU cannot hold the 1 MiB of W_hh (512 KiB of registers + 160 KiB of LDS): a one-workgroup recurrence (lstm_stream_kernel
+// below) streams 62 % of it from L2 on every step (~6 us per step, bound by the CU's L1 fill rate).  Here the recurrence of one (utterance,
 // direction) runs on TWO workgroups = two CUs.  Half hf owns hidden units [128 hf, 128 hf + 128) with all four of their
 // gate rows (512 rows x 256 k = 512 KiB: 96 registers per thread + 128 KiB of LDS), so it updates its own cells locally
 // and the only traffic per step is the exchange of the 128 new h values each way: 8-byte {h, tag} granules written with
@@ -988,8 +915,7 @@ __global__ __launch_bounds__(LstmParts<NQ>::THREADS) void lstm_pair_kernel(const
 // runs after a hand-off of the resident-weights forms timed out (a recurrence's partner starved behind other work on the GPU;
 // DESIGN.md section 7), and since round 5 it gives the SAME BITS as they do: a lane is (row pair, K quarter) of the two-CU
 // form and walks half 0's rows, then half 1's, with the same order of sums ((q0 + q1) + (q2 + q3) over the quad) and the same
-// cell update -- so a model may switch between the forms at any call without its results changing (lstm_kernel above, whose
-// lanes own whole rows, agrees with them to rounding only; it stays as KX_LSTM_PAIR=0's reference form).
+// cell update -- so a model may switch between the forms at any call without its results changing.
 // Half 0's first 8 pieces (of 16 per row) live in registers, its next 4 in LDS (128 KiB); the other 4 and all of half 1
 // (62 % of the 1 MiB) come from L2 on every step: ~6 us per step against 1.6 - 2.5 us resident.
 constexpr int LSTMS_REG = 16, LSTMS_LDS = 8;  // float4 pieces (2 j + row A / B) of half 0 in registers / in LDS
@@ -1082,21 +1008,15 @@ __global__ __launch_bounds__(1024) void lstm_stream_kernel(const float* gx, long
 static std::atomic<int> lstm_test_fault{0};
 void lstm_set_test_fault(int nth) { lstm_test_fault.store(nth > 0 ? nth : 0); }
 
-// 0 = by batch size, 2 / 4 = that many workgroups per (utterance, direction), 1 = the streaming fall-back (KX_LSTM_PARTS; kx_test_lstm_parts)
-static std::atomic<int> lstm_parts_force{getenv("KX_LSTM_PARTS") ? atoi(getenv("KX_LSTM_PARTS")) : 0};
+// 0 = by batch size, 2 / 4 = that many workgroups per (utterance, direction), 1 = the streaming fall-back (kx_test_lstm_parts)
+static std::atomic<int> lstm_parts_force{0};
 void lstm_set_parts(int n) { lstm_parts_force.store(n == 1 || n == 2 || n == 4 ? n : 0); }  // (1 = the streaming fall-back)
-
-static bool lstm_use_pair() {
-    static const int v = getenv("KX_LSTM_PAIR") ? atoi(getenv("KX_LSTM_PAIR")) : 1;
-    return v != 0;
-}
 
 size_t lstm_exchange_bytes(int B) { return (size_t)B * 2 * 2 * 2 * 128 * sizeof(unsigned long long); }
 
 void launch_lstm(const float* gx, long gx_bs, int gx_ld, const float* whhT, float* y, long y_bs, int y_ld,
                  LenMap len, int B, unsigned long long* xchg, unsigned* err_word, hipStream_t s, unsigned* epoch_state) {
-    static_assert(LSTM_LDS_K % 4 == 0 && LSTM_REG_K % 4 == 0, "whole float4 groups of h");
-    if (lstm_use_pair() && xchg && err_word && lstm_parts_force.load() != 1) {
+    if (xchg && err_word && lstm_parts_force.load() != 1) {
         // The tag's epoch is 16 bits wide and counted PER exchange buffer (epoch_state; the test hook's one-shot buffer has
         // none): when it wraps the buffer is cleared in stream order, so a granule of 65535 launches ago can never carry
         // the tag of a live step.  (0 is what a cleared buffer holds and is never used as an epoch.)
@@ -1120,7 +1040,7 @@ void launch_lstm(const float* gx, long gx_bs, int gx_ld, const float* whhT, floa
         }
         // Four parts per (utterance, direction) while that leaves no CU without work: 8 B workgroups of 512 threads, each of which
         // needs a CU's whole register file (256 registers per lane).  Same bits either way (see lstm_pair_kernel).
-        // KX_LSTM_PARTS = 2 / 4 forces a form.
+        // lstm_set_parts(2 / 4) forces a form.
         const int parts = lstm_parts_force.load();
         const bool four = parts ? parts == 4 : 8 * B <= conv16_cu_count();
         const int spin = fault ? (1 << 10) : (1 << 19);
@@ -1140,18 +1060,11 @@ void launch_lstm(const float* gx, long gx_bs, int gx_ld, const float* whhT, floa
         KX_HIP(hipGetLastError());
         return;
     }
-    if (lstm_use_pair()) {  // the fall-back of a model whose hand-off timed out (xchg = null): same bits as the resident forms
-        const size_t lds = sizeof(float) * (4 * LSTMP_HP + 1024 + (size_t)LSTMS_LDS * 1024 * 4);
-        static DynLdsLimit stream_limit;
-        stream_limit.ensure(reinterpret_cast<const void*>(lstm_stream_kernel), lds);
-        hipLaunchKernelGGL(lstm_stream_kernel, dim3(B, 2), dim3(1024), lds, s, gx, gx_bs, gx_ld, whhT, y, y_bs, y_ld, len);
-        KX_HIP(hipGetLastError());
-        return;
-    }
-    const size_t lds = sizeof(float) * (256 + 1024 + (size_t)LSTM_LDS_K * 1024);
-    static DynLdsLimit one_limit;
-    one_limit.ensure(reinterpret_cast<const void*>(lstm_kernel), lds);
-    hipLaunchKernelGGL(lstm_kernel, dim3(B, 2), dim3(1024), lds, s, gx, gx_bs, gx_ld, whhT, y, y_bs, y_ld, len);
+    // the fall-back of a model whose hand-off timed out (xchg = null): same bits as the resident forms
+    const size_t lds = sizeof(float) * (4 * LSTMP_HP + 1024 + (size_t)LSTMS_LDS * 1024 * 4);
+    static DynLdsLimit stream_limit;
+    stream_limit.ensure(reinterpret_cast<const void*>(lstm_stream_kernel), lds);
+    hipLaunchKernelGGL(lstm_stream_kernel, dim3(B, 2), dim3(1024), lds, s, gx, gx_bs, gx_ld, whhT, y, y_bs, y_ld, len);
     KX_HIP(hipGetLastError());
 }
 

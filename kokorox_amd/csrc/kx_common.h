@@ -117,13 +117,13 @@ struct ConvArgs {
     int merge_B;
     float2* stat_part;  // optional [B][Cout][stat_tiles] partial (sum, sum of squares) of the stored values
     int stat_tiles;
-    int xcd_swizzle;               // one-role f16x3 kernel: contiguous column tiles per XCD (1 unless KX_XCD_SWIZZLE=0)
+    int xcd_swizzle;               // XCD-aware tile order of the f16x3 kernels: always 1 (conv_call.hip)
     int ws_force;                  // test hook: 1 = the LDS-DMA kernel forms only (no direct-A kernel), 2 = the direct-A kernel whatever the grid
-    unsigned long long* stamps;  // diagnostic build only: per-workgroup {t0,t1,t2,t3,hw_id,xcc_id,0,0}
+    unsigned long long* stamps;  // retired diagnostic, never set (null); its run-time tests are open work: DESIGN.md section 3
     int prec1;  // direct-A conv: the reduced-precision forms, opt-in: 1 = one f16 MFMA per product (KOKOROX_CONV=f16), 2 = one bf16
                 // MFMA per product on a bf16 weight image (KOKOROX_CONV=bf16)
-    int dephase_cycles, dephase_mode;  // direct-A conv: start delay of half of the first round of workgroups (0 = off)
-    int dbg;  // timing ablations (env KX_DBG): 1 skip input staging, 2 skip weight copies, 4 skip MFMA, 8 skip epilogue
+    int dephase_cycles, dephase_mode;  // retired diagnostic, never set (0)
+    int dbg;  // retired timing ablations, never set (0)
     // Flat tile list of a ragged batch (direct-A kernels): tile_prefix[b] = column tiles of the utterances before b (so
     // tile_prefix[B] = all of them); the grid is then ONE dimension of tile_prefix[B] * flat_ny workgroups, none of them
     // dead, and the XCD-aware order runs over the whole list.  null = the (max_cols / BN) x row tiles x B grid with

@@ -267,8 +267,6 @@ class Model {
     void conv(const ConvW& w, const T& in, const T& out, const ConvOpts& o);
     void prof_begin(const ConvW& w, const T& in, const T& out, const ConvOpts& o);  // profile mode: the bracket around a timed launch
     void prof_end();
-    long stamp_begin(const ConvW& w, ConvCall& call);  // KX_STAMP diagnostic
-    void stamp_dump(unsigned long long* d_stamps, long n_wg);
     void stats(const T& x, const std::string& fc_key);
     void adain_resblk(const std::string& name, const T& x, const T& out, bool upsample, float* ws_a, float* ws_b,
                       float* ws_c);

@@ -556,8 +556,6 @@ void Model::conv(const ConvW& w, const T& in, const T& out, const ConvOpts& o) {
     }
     parts_.erase(out.p);  // whatever statistics were known for this tensor are stale now
     if (plan.stat_cols) parts_[out.p] = PartInfo{o.stat_part, plan.stat_tiles, plan.stat_cols, w.rows};
-    static const int dbg_env = getenv("KX_DBG") ? atoi(getenv("KX_DBG")) : 0;
-    call.a.dbg = dbg_env;
     // ragged batch: the direct-A kernels take a flat list of the live tiles instead of a (longest length) x B grid
     if (plan.flat_bn) {
         int total = 0;
@@ -565,7 +563,6 @@ void Model::conv(const ConvW& w, const T& in, const T& out, const ConvOpts& o) {
         call.set_flat(prefix, total);
         if (total <= 0) return;  // (nothing to compute)
     }
-    const long stamp_wgs = stamp_begin(w, call);
     if (x16) {
         // (outside the timed interval of the profile mode: that one is the conv kernel's own duration, which the rocprofv3
         // summary of the same kernel name must reproduce; the pass shows up under its own name there and in ms_per_step)
@@ -578,7 +575,6 @@ void Model::conv(const ConvW& w, const T& in, const T& out, const ConvOpts& o) {
     if (timed) prof_begin(w, in, out, o);
     launch_conv(plan, call.a, B_, stream_);
     if (timed) prof_end();
-    if (stamp_wgs) stamp_dump(call.a.stamps, stamp_wgs);
 }
 
 // profile mode: FLOPs and algorithmic HBM bytes of a launch, and the first of the two events around it
@@ -615,44 +611,6 @@ void Model::prof_begin(const ConvW& w, const T& in, const T& out, const ConvOpts
 void Model::prof_end() {
     KX_HIP(hipEventRecord(ev_[ev_used_ + 1], stream_));
     ev_used_ += 2;
-}
-
-// diagnostic: KX_STAMP=<file> dumps per-workgroup timestamps of the first 128->128 k=11 launch (KX_STAMP_ROWS, KX_STAMP_K: of
-// another shape; KX_STAMP_SKIP: matching launches to pass over first).  stamp_begin gives the launch its stamp buffer and
-// returns its workgroup count (0: not this launch), stamp_dump writes the file after the launch.
-static const char* stamp_path() {
-    static const char* path = getenv("KX_STAMP");
-    return path;
-}
-static bool stamped = false;
-
-long Model::stamp_begin(const ConvW& w, ConvCall& call) {
-    static const int stamp_rows = getenv("KX_STAMP_ROWS") ? atoi(getenv("KX_STAMP_ROWS")) : 128;
-    static const int stamp_k = getenv("KX_STAMP_K") ? atoi(getenv("KX_STAMP_K")) : 11;
-    static int stamp_skip = getenv("KX_STAMP_SKIP") ? atoi(getenv("KX_STAMP_SKIP")) : 0;
-    if (!stamp_path() || stamped || call.plan.form == FORM_F32 || w.K != stamp_k || w.rows != stamp_rows || B_ < 8) return 0;
-    if (stamp_skip > 0) {
-        --stamp_skip;
-        return 0;
-    }
-    const long n_wg = (long)((call.plan.cols + 127) / 128) * ((w.rows + 127) / 128) * (call.a.merge_T > 0 ? 1 : B_);
-    unsigned long long* d_stamps = nullptr;
-    KX_HIP(hipMalloc((void**)&d_stamps, n_wg * 64));
-    KX_HIP(hipMemsetAsync(d_stamps, 0, n_wg * 64, stream_));
-    call.a.stamps = d_stamps;
-    return n_wg;
-}
-
-void Model::stamp_dump(unsigned long long* d_stamps, long n_wg) {
-    stamped = true;
-    KX_HIP(hipStreamSynchronize(stream_));
-    std::vector<unsigned long long> hst(n_wg * 8);
-    KX_HIP(hipMemcpy(hst.data(), d_stamps, n_wg * 64, hipMemcpyDeviceToHost));
-    KX_HIP(hipFree(d_stamps));
-    if (FILE* f = fopen(stamp_path(), "wb")) {
-        fwrite(hst.data(), 8, hst.size(), f);
-        fclose(f);
-    }
 }
 
 // The device prefix table of (length map, extra columns, tile width) for the running call: built once per call and key by a

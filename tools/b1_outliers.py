@@ -40,7 +40,7 @@ for i in range(n + 5):
     if i >= 5:
         rows.append([(t2 - t) * 1e3, (t1 - t) * 1e3] + m.call_times())
 a = np.array(rows)
-print(f"{n} calls (gc {'on' if gc.isenabled() else 'off'}, KX_LSTM_PARTS={os.environ.get('KX_LSTM_PARTS', '0')}): median {np.median(a[:, 0]):.3f} ms, p99 {np.sort(a[:, 0])[int(n * 0.99)]:.3f}, max {a[:, 0].max():.3f}; status {m.status()}")
+print(f"{n} calls (gc {'on' if gc.isenabled() else 'off'}): median {np.median(a[:, 0]):.3f} ms, p99 {np.sort(a[:, 0])[int(n * 0.99)]:.3f}, max {a[:, 0].max():.3f}; status {m.status()}")
 for r in a[np.argsort(-a[:, 0])[:4]]:
     print("   total %.2f  returned %.2f | front queued %.2f  front done %.2f  back planned %.2f  back queued %.2f" % tuple(r))
 m.close()
