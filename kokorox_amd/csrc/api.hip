@@ -15,22 +15,11 @@ using kx::Model;
 
 #include "kx_handle.h"
 
+#include "check_device.h"
 #include "api_guard.h"  // the exception fence + the per-thread last-error text (HIP-free: sanitizer-tested on the CPU)
 using kx::guarded;
 using kx::guarded_free;
 using kx::set_err;
-
-static void check_device(int device_id) {
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) throw Error(KX_ERR_DEVICE, "no HIP device is visible (the HIP path has no CPU fallback)");
-    if (device_id < 0 || device_id >= n) throw Error(KX_ERR_INVALID, "device id out of range");
-    hipDeviceProp_t p;
-    KX_HIP(hipGetDeviceProperties(&p, device_id));
-    if (strncmp(p.gcnArchName, "gfx950", 6) != 0)
-        throw Error(KX_ERR_DEVICE, std::string("device is ") + p.gcnArchName + ", this library is built for gfx950 only");
-}
-
 
 extern "C" {
 
@@ -54,18 +43,9 @@ kx_model* kx_create(const char* weights_path, int device_id, char* err, size_t e
 int kx_import_onnx(const char* onnx_path, const char* out_path, char* err, size_t err_len) {
     return guarded_free(err, err_len, [&] {
         KX_REQUIRE(onnx_path && *onnx_path && out_path && *out_path, "kx_import_onnx: two paths");
-        FILE* f = fopen(onnx_path, "rb");
-        if (!f) throw Error(KX_ERR_IO, std::string("cannot open weight file: ") + onnx_path);
-        std::vector<unsigned char> in;
-        unsigned char buf[1 << 16];
-        size_t got;
-        while ((got = fread(buf, 1, sizeof buf, f)) > 0) in.insert(in.end(), buf, buf + got);
-        fclose(f);
+        const std::vector<unsigned char> in = kx::read_file(onnx_path, "weight file");
         const std::vector<unsigned char> blob = kx::import_onnx_bytes(in.data(), in.size());
-        FILE* o = fopen(out_path, "wb");
-        if (!o) throw Error(KX_ERR_IO, std::string("cannot write ") + out_path);
-        const bool ok = fwrite(blob.data(), 1, blob.size(), o) == blob.size();
-        if (fclose(o) != 0 || !ok) throw Error(KX_ERR_IO, std::string("short write on ") + out_path);
+        kx::write_file_atomic(out_path, blob.data(), blob.size());
     });
 }
 
@@ -119,6 +99,7 @@ int kx_create_replicas(const char* weights_path, const int* device_ids, int n, k
         int variant = -2;
         const std::vector<unsigned char> host = kx::read_weight_file(weights_path, &variant);  // the ONE file read
         const size_t nb = host.size();
+        (void)kx::kxw_table(host.data(), nb, nb);  // refused here, before n copies of it are made (every model checks its own again)
         t_ms[0] = ms_since(t0);
         blobs.assign(n, nullptr);
         blob_dev.assign(device_ids, device_ids + n);

@@ -8,14 +8,9 @@
 #include <vector>
 
 #include "kx_common.h"
+#include "kxw_file.h"
 
 namespace kx {
-
-struct TensorInfo {
-    size_t offset = 0, nbytes = 0;
-    int ndim = 0;
-    int dims[4] = {0, 0, 0, 0};
-};
 
 struct ConvW {
     const float* w = nullptr;     // packed [co_tile][chunk][k][8][BM]
@@ -151,12 +146,6 @@ ConvCall conv_call(const ConvW& w, const T& in, const T& out, const ConvOpts& o,
 // column tiles of `bn` columns over a batch whose host lengths are h_lens (tile_prefix[B] as the host counts it)
 int conv_tile_count(const int* h_lens, int B, const LenMap& lm, int extra, int bn);
 
-// the KXHIPW01 image behind `path`: the container itself (header checked), or built from the `.onnx` the reference passes
-// *variant (optional): what the file was -- 0 KXHIPW01 container, 1 fp32 ONNX, 2 fp16 / bf16 ONNX, 3 8-bit quantised ONNX,
-// 4 4-bit quantised ONNX (3, 4: weights de-quantised), -1 a cached conversion (KOKOROX_KXW_CACHE=1)
-std::vector<unsigned char> read_weight_file(const char* path, int* variant = nullptr);
-std::vector<unsigned char> import_onnx_bytes(const unsigned char* data, size_t n, int* variant = nullptr);  // ImportError -> Error(KX_ERR_IO)
-
 // (KX_ERR_DEVICE class) a part of a resident-weights LSTM recurrence timed out waiting for its partner: the call is invalid,
 // the model has switched to the streaming recurrence; host entry points re-run the call once
 struct LstmTimeout : Error {
@@ -251,7 +240,7 @@ class Model {
     int device;
 
   private:
-    void build();  // parse table, pack weights, style-fc descriptors
+    void build();  // pack weights, style-fc descriptors (table_ and blob_ are in place)
     const float* wt(const std::string& name) const;
     const TensorInfo& info(const std::string& name) const;
     bool has(const std::string& name) const { return table_.count(name) != 0; }
@@ -306,7 +295,7 @@ class Model {
     hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
     char* blob_ = nullptr;
     size_t blob_bytes_ = 0;
-    std::map<std::string, TensorInfo> table_;
+    TensorTable table_;
     std::vector<void*> owned_;
     std::map<std::string, ConvW> convs_;
     std::map<std::string, LstmW> lstms_;

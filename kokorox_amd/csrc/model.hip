@@ -4,13 +4,8 @@
 #include <chrono>
 #include "model.h"
 
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include <cstdlib>
 #include <cstring>
-
-#include "onnx_import.h"
 
 namespace kx {
 
@@ -142,139 +137,12 @@ Model::~Model() {
     T("done");
 }
 
-// ---- weight container ------------------------------------------------------------------------
-static void parse_table(const unsigned char* hdr, size_t hdr_bytes, size_t total,
-                        std::map<std::string, TensorInfo>& table) {
-    uint32_t n;
-    memcpy(&n, hdr + 8, 4);
-    if (64 + (size_t)n * 128 > hdr_bytes) throw Error(2, "weight blob: truncated tensor table");
-    for (uint32_t i = 0; i < n; ++i) {
-        const unsigned char* e = hdr + 64 + (size_t)i * 128;
-        char name[89];
-        memcpy(name, e, 88);
-        name[88] = 0;
-        uint32_t dt, nd, dims[4];
-        uint64_t off, nb;
-        memcpy(&dt, e + 88, 4);
-        memcpy(&nd, e + 92, 4);
-        memcpy(dims, e + 96, 16);
-        memcpy(&off, e + 112, 8);
-        memcpy(&nb, e + 120, 8);
-        if (dt != 0 || nd > 4 || off + nb > total || (off & 255)) throw Error(2, std::string("weight blob: bad entry ") + name);
-        TensorInfo ti;
-        ti.offset = off;
-        ti.nbytes = nb;
-        ti.ndim = (int)nd;
-        size_t cnt = 1;
-        for (int k = 0; k < (int)nd; ++k) {
-            ti.dims[k] = (int)dims[k];
-            cnt *= dims[k];
-        }
-        if (cnt * 4 != nb) throw Error(2, std::string("weight blob: size mismatch ") + name);
-        table[name] = ti;
-    }
-}
-
-static size_t check_header(const unsigned char* h, size_t have) {
-    if (have < 64 || memcmp(h, "KXHIPW01", 8) != 0) throw Error(2, "weight blob: bad magic (expected KXHIPW01)");
-    uint64_t total;
-    memcpy(&total, h + 24, 8);
-    return (size_t)total;
-}
-
-static std::vector<unsigned char> read_all(const char* path, const char* what) {
-    FILE* f = fopen(path, "rb");
-    if (!f) throw Error(2, std::string("cannot open ") + what + ": " + path);
-    fseek(f, 0, SEEK_END);
-    const long sz = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    if (sz < 0) {
-        fclose(f);
-        throw Error(2, std::string("cannot size ") + what + ": " + path);
-    }
-    std::vector<unsigned char> host((size_t)sz);
-    const size_t got = host.empty() ? 0 : fread(host.data(), 1, host.size(), f);
-    fclose(f);
-    if (got != host.size()) throw Error(2, std::string("short read on ") + what + ": " + path);
-    return host;
-}
-
-std::vector<unsigned char> import_onnx_bytes(const unsigned char* data, size_t n, int* variant) {
-    try {
-        ImportInfo info;
-        std::vector<unsigned char> blob = onnx_to_kxw(data, n, &info);
-        if (variant) *variant = info.variant();
-        return blob;
-    } catch (const ImportError& e) {
-        throw Error(2, std::string("weight file is not a KXHIPW01 blob (bad magic) and not a readable ONNX model: ") + e.what());
-    }
-}
-
-// The KXHIPW01 image behind `path`.  The path is either the library's own container or — what the reference passes to
-// OrtKoko::new (koko.rs:570-573, hf_cache.rs:128-158) — the `.onnx` file, which is converted in memory
-// (onnx_import.cpp).  `<path>.kxw` beside an .onnx is used instead when it is at least as new as the .onnx and whole;
-// it is written only when KOKOROX_KXW_CACHE=1 (a library should not drop files into a model cache unasked).
-std::vector<unsigned char> read_weight_file(const char* path, int* variant) {
-    KX_REQUIRE(path && *path, "kx_create: empty weights path");
-    if (variant) *variant = 0;
-    std::vector<unsigned char> host = read_all(path, "weight file");
-    if (is_kxw_magic(host.data(), host.size())) {
-        const size_t total = check_header(host.data(), host.size());
-        if (total != host.size()) throw Error(2, "weight blob: file size does not match header");
-        return host;
-    }
-    // The converted image may be cached beside the source -- ONLY when KOKOROX_KXW_CACHE=1 says so (a file the library never wrote
-    // is never trusted), and only while the cache's stamp names exactly this source: its size, its modification time to the
-    // nanosecond and the importer's version (cp -p / mv / a re-pointed Hugging Face blob symlink keep an older mtime: a "not
-    // older than the source" test would load the former variant's weights).
-    const std::string cache = std::string(path) + ".kxw", stamp_path = cache + ".src";
-    const char* ce = getenv("KOKOROX_KXW_CACHE");
-    const bool use_cache = ce && strcmp(ce, "1") == 0;
-    struct stat so;
-    std::string stamp;
-    if (use_cache && stat(path, &so) == 0) {
-        stamp = "kxw-cache 1 importer " + std::to_string(KX_IMPORTER_VERSION) + " size " + std::to_string((long long)so.st_size) + " mtime " +
-                std::to_string((long long)so.st_mtim.tv_sec) + "." + std::to_string((long)so.st_mtim.tv_nsec) + "\n";
-        try {
-            const std::vector<unsigned char> st = read_all(stamp_path.c_str(), "weight cache stamp");
-            if (std::string(st.begin(), st.end()) == stamp) {
-                std::vector<unsigned char> c = read_all(cache.c_str(), "weight cache");
-                if (is_kxw_magic(c.data(), c.size()) && check_header(c.data(), c.size()) == c.size()) {
-                    if (variant) *variant = -1;  // (a cached conversion: the source's kind was not looked at again)
-                    return c;
-                }
-            }
-        } catch (const Error&) {  // no cache, or an unreadable one, is not an error: convert
-        }
-    }
-    int var = 1;
-    std::vector<unsigned char> blob = import_onnx_bytes(host.data(), host.size(), &var);
-    if (variant) *variant = var;
-    if (var >= 3)
-        fprintf(stderr,
-                "kokorox-hip: %s is a %d-bit quantised ONNX variant: its weights are de-quantised at load and the model runs f32-class "
-                "arithmetic, which is NOT what ONNX Runtime computes for this file (it quantises the activations at run time: "
-                "DynamicQuantizeLinear -> MatMulInteger / ConvInteger / MatMulNBits).  Parity with the reference is claimed for "
-                "onnx/model.onnx only.\n",
-                path, var == 3 ? 8 : 4);
-    if (use_cache && !stamp.empty()) {
-        const std::string tmp = cache + ".tmp." + std::to_string((long)getpid());
-        if (FILE* f = fopen(tmp.c_str(), "wb")) {
-            const bool ok = fwrite(blob.data(), 1, blob.size(), f) == blob.size();
-            if (fclose(f) != 0 || !ok || rename(tmp.c_str(), cache.c_str()) != 0) (void)remove(tmp.c_str());
-            else if (FILE* g = fopen((stamp_path + ".tmp").c_str(), "wb")) {  // (the stamp last: a cache without it is ignored)
-                const bool ok2 = fwrite(stamp.data(), 1, stamp.size(), g) == stamp.size();
-                if (fclose(g) != 0 || !ok2 || rename((stamp_path + ".tmp").c_str(), stamp_path.c_str()) != 0) (void)remove((stamp_path + ".tmp").c_str());
-            }
-        }
-    }
-    return blob;
-}
-
+// ---- weight container: read and checked on the host (kxw_file.cpp); here it reaches the device --------------------------
+// (in both loaders the table is accepted before the blob is allocated and before build() launches anything)
 void Model::load_file(const char* path) {
     const std::vector<unsigned char> host = read_weight_file(path, &source_variant_);
     const size_t n = host.size();
-    parse_table(host.data(), n, n, table_);
+    table_ = kxw_table(host.data(), n, n);
     KX_HIP(hipSetDevice(device));
     KX_HIP(hipMalloc((void**)&blob_, n));
     blob_bytes_ = n;
@@ -283,19 +151,15 @@ void Model::load_file(const char* path) {
 }
 
 void Model::load_device_blob(const void* d_blob, size_t n, bool adopt) {
-    KX_REQUIRE(d_blob && n >= 64, "kx_create_from_device_blob: empty blob");
+    KX_REQUIRE(d_blob && n >= KXW_HEADER_BYTES, "kx_create_from_device_blob: empty blob");
     KX_HIP(hipSetDevice(device));
-    unsigned char h64[64];
-    KX_HIP(hipMemcpy(h64, d_blob, 64, hipMemcpyDeviceToHost));
-    const size_t total = check_header(h64, 64);
-    if (total != n) throw Error(2, "weight blob: size does not match header");
-    uint32_t nt;
-    memcpy(&nt, h64 + 8, 4);
-    const size_t hdr_bytes = 64 + (size_t)nt * 128;
-    if (hdr_bytes > n) throw Error(2, "weight blob: truncated tensor table");
-    std::vector<unsigned char> hdr(hdr_bytes);
-    KX_HIP(hipMemcpy(hdr.data(), d_blob, hdr_bytes, hipMemcpyDeviceToHost));
-    parse_table(hdr.data(), hdr_bytes, total, table_);
+    unsigned char h64[KXW_HEADER_BYTES];
+    KX_HIP(hipMemcpy(h64, d_blob, sizeof h64, hipMemcpyDeviceToHost));
+    const KxwHeader h = kxw_header(h64, sizeof h64);
+    if (h.total_bytes != n) throw Error(2, "weight blob: size does not match header");
+    std::vector<unsigned char> hdr(h.table_bytes);  // (not beyond the blob: kxw_header)
+    KX_HIP(hipMemcpy(hdr.data(), d_blob, hdr.size(), hipMemcpyDeviceToHost));
+    table_ = kxw_table(hdr.data(), hdr.size(), n);
     blob_bytes_ = n;
     if (adopt) {  // the caller hands over a hipMalloc'd blob on this device (kx_create_replicas): no second copy
         blob_ = static_cast<char*>(const_cast<void*>(d_blob));

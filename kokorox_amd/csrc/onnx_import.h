@@ -19,7 +19,7 @@
 
 namespace kx {
 
-// bumped whenever the placement rules change what the importer writes for the same .onnx (it stamps the opt-in cache: model.hip)
+// bumped whenever the placement rules change what the importer writes for the same .onnx (it stamps the opt-in cache: kxw_file.cpp)
 constexpr int KX_IMPORTER_VERSION = 1;
 
 struct ImportError : std::runtime_error {

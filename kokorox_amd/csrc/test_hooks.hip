@@ -16,21 +16,11 @@ using kx::Model;
 
 #include "kx_handle.h"
 
+#include "check_device.h"
 #include "api_guard.h"
 using kx::guarded;
 using kx::guarded_free;
 using kx::set_err;
-
-static void check_device(int device_id) {
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) throw Error(KX_ERR_DEVICE, "no HIP device is visible (the HIP path has no CPU fallback)");
-    if (device_id < 0 || device_id >= n) throw Error(KX_ERR_INVALID, "device id out of range");
-    hipDeviceProp_t p;
-    KX_HIP(hipGetDeviceProperties(&p, device_id));
-    if (strncmp(p.gcnArchName, "gfx950", 6) != 0)
-        throw Error(KX_ERR_DEVICE, std::string("device is ") + p.gcnArchName + ", this library is built for gfx950 only");
-}
 
 namespace {
 struct DevMem {

@@ -7,8 +7,9 @@ There is no network here, so the model is exercised with *synthetic* weights of 
 architecture, scaled so that activations, durations, F0 and the
 output waveform stay in realistic ranges.
 
-Blob format "KXHIPW01" (little endian), consumed by kokorox_amd/csrc/weights.cpp and by
-the oracle's own reader:
+Blob format "KXHIPW01" (little endian), read and checked by kokorox_amd/csrc/kxw_file.cpp
+(which also requires every tensor of tensor_spec() with exactly its shape) and by the
+oracle's own reader:
 
     0   char[8]  magic "KXHIPW01"
     8   u32      n_tensors

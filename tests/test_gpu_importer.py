@@ -235,3 +235,57 @@ def test_four_replicas_on_one_gpu_build_fail_and_destroy(blob_path, monkeypatch)
     torch.cuda.synchronize()
     free1 = torch.cuda.mem_get_info()[0]
     assert free0 - free1 < 64 << 20, f"{(free0 - free1) >> 20} MiB of device memory did not come back"
+
+
+# ---- a container whose table is sound but is not the model's is refused on the host (csrc/kxw_file.cpp: kxw_table) -------------
+def _table_cases():
+    p = os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_kxw_file_cpu.py")
+    spec = importlib.util.spec_from_file_location("_kxw_table_cases", p)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.fixture(scope="module")
+def shrunk_blob(blob_path):
+    """The synthetic blob with ONE table entry patched in memory: `predictor.lstm.bias_ih_l0` as [1023] / 4092 bytes, offset and
+    data untouched.  The tensor's 256-byte padding covers the four bytes a 1024-float read would take, so not even a build
+    that accepts the file reads out of bounds with it: the cases below check only that it is refused, and before any launch."""
+    a = np.fromfile(blob_path, dtype=np.uint8)
+    _table_cases().shrink_lstm_bias(a)
+    return a
+
+
+def _refused_and_session_model_unharmed(ei, hip_model):
+    """(kx_create and kx_create_from_device_blob return a handle or NULL: their status does not cross the ABI, the message does.
+    "weight blob: shape mismatch" is kxw_table's, thrown as KX_ERR_IO -- the status itself is asserted on the CPU, where
+    tests/test_kxw_file_cpu.py feeds this same patched table to the stand-alone driver, and below through kx_create_replicas.)"""
+    C = _table_cases()
+    msg = str(ei.value)
+    assert "weight blob: shape mismatch " + C.LSTM_BIAS in msg and "[1023]" in msg and "[1024]" in msg, msg
+    audio = hip_model.infer([[0, 5, 6, 0]], [[0.0] * 256], 1.0)
+    assert audio.shape[0] > 0 and audio.shape[0] % 600 == 0
+
+
+def test_file_whose_table_is_not_the_models_is_refused(hip_model, shrunk_blob, tmp_path):
+    import ctypes
+    from kokorox_amd import hip_koko as hk
+    p = str(tmp_path / "shrunk.kxw")
+    shrunk_blob.tofile(p)
+    with pytest.raises(RuntimeError) as ei:
+        hk.HipKoko.new(p)
+    # the entry point that does return its status: refused on the host copy, before any device has been handed a byte
+    dev, out, err = (ctypes.c_int * 1)(0), (ctypes.c_void_p * 1)(), ctypes.create_string_buffer(512)
+    assert hk.load_library().kx_create_replicas(os.fsencode(p), dev, 1, out, err, len(err)) == hk.KX_ERR_IO
+    assert not out[0] and err.value.decode() in str(ei.value)
+    _refused_and_session_model_unharmed(ei, hip_model)
+
+
+def test_device_blob_whose_table_is_not_the_models_is_refused(hip_model, shrunk_blob):
+    import torch
+    from kokorox_amd import hip_koko as hk
+    buf = torch.from_numpy(shrunk_blob).cuda()
+    with pytest.raises(RuntimeError) as ei:
+        hk.HipKoko.from_device_blob(buf.data_ptr(), buf.numel(), 0)
+    del buf
+    _refused_and_session_model_unharmed(ei, hip_model)
