@@ -1,0 +1,154 @@
+// The argument checks of the two inference entries and the layout of their compact output (host_request.h).  No HIP.
+#include "host_request.h"
+
+namespace kx {
+
+// ---- refusals of the host entry (Model::infer_host_once) ---------------------------------------------------------------------
+void check_host_call(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds, const HostCall& hc,
+                     void** out, const int64_t* out_bytes, const int64_t* out_samples, int n_vocab, int n_voices,
+                     bool have_voice_table) {
+    KX_REQUIRE(out && out_bytes && out_samples, "infer: null output argument");
+    *out = nullptr;
+    KX_REQUIRE(B >= 1, "infer: empty batch");
+    KX_REQUIRE(ids && lens && speeds, "infer: null argument");
+    const bool grouped = hc.grouped();  // (then `format` / `formats` are not used)
+    KX_REQUIRE(grouped || (hc.format >= 0 && hc.format <= 2), "infer: unknown output format");
+    if (grouped) {
+        const int R = hc.n_requests;
+        KX_REQUIRE(R >= 1 && hc.req_formats && (hc.n_req_formats == 1 || hc.n_req_formats == R), "infer: requests need 1 or R output formats");
+        long rows = 0;
+        for (int r = 0; r < R; ++r) {
+            KX_REQUIRE(hc.chunks_per_request[r] >= 1, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
+            rows += hc.chunks_per_request[r];
+        }
+        KX_REQUIRE(rows == B, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
+        for (int i = 0; i < hc.n_req_formats; ++i)
+            KX_REQUIRE(hc.req_formats[i] >= 0 && hc.req_formats[i] <= 4, "infer: unknown output format");
+    }
+    KX_REQUIRE(!hc.utt_index || hc.utt_seeds, "infer: utterance indices go with per-row seeds");
+    const bool by_voice = hc.by_voice();
+    KX_REQUIRE(by_voice || hc.styles, "infer: styles or voice ids are required");
+    KX_REQUIRE(!hc.kinds || (by_voice && hc.styles), "infer: per-utterance kinds need both styles and voice ids");
+    if (by_voice) {
+        KX_REQUIRE(have_voice_table && hc.weights && hc.max_mix >= 1 && hc.max_mix <= 16, "infer: voice table not set or bad mix");
+    }
+    for (int b = 0; b < B; ++b) {
+        KX_REQUIRE(lens[b] >= 1 && lens[b] <= 512 && lens[b] <= t_stride, "infer: token count must be 1..512");
+        for (int t = 0; t < lens[b]; ++t) {
+            const int64_t id = ids[b * t_stride + t];
+            KX_REQUIRE(id >= 0 && id < n_vocab, "infer: token id outside 0..177");
+        }
+        const int kind = hc.kind_of(b);
+        KX_REQUIRE(kind >= 0 && kind <= 2 && (grouped || (hc.format_of(b) >= 0 && hc.format_of(b) <= 2)), "infer: unknown kind / output format");
+        if (kind != 0) {
+            KX_REQUIRE(lens[b] >= 2, "infer: voice rows need the two 0 pads (row = tokens - 2)");
+            bool any = false;
+            for (int k = 0; k < hc.max_mix; ++k) {
+                const int v = hc.voice_ids[(size_t)b * hc.max_mix + k];
+                KX_REQUIRE(v < n_voices, "infer: voice id outside the table");
+                any = any || v >= 0;
+            }
+            KX_REQUIRE(any && (kind != 1 || hc.voice_ids[(size_t)b * hc.max_mix] >= 0), "infer: no voice given");
+        }
+    }
+}
+
+// ---- refusals of the device entry (Model::infer_device) ----------------------------------------------------------------------
+int check_device_call(const void* d_ids, int64_t t_stride, const int32_t* lens_host, int B, const void* d_styles,
+                      const float* speeds_host, int n_speed) {
+    KX_REQUIRE(B >= 1 && B <= 4096, "infer: batch must be 1..4096 (empty input is an error)");
+    KX_REQUIRE(d_ids && lens_host && d_styles && speeds_host, "infer: null argument");
+    KX_REQUIRE(n_speed == 1 || n_speed == B, "infer: n_speed must be 1 or B");
+    int Tmax = 0;
+    for (int b = 0; b < B; ++b) {
+        KX_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= 512, "infer: token count must be 1..512");
+        KX_REQUIRE((int64_t)lens_host[b] <= t_stride, "infer: lens[b] exceeds the row stride");
+        if (lens_host[b] > Tmax) Tmax = lens_host[b];
+    }
+    for (int i = 0; i < n_speed; ++i) KX_REQUIRE(speeds_host[i] > 0.f, "infer: speed must be > 0");
+    return Tmax;
+}
+
+// ---- layout of the compact output ----------------------------------------------------------------------------------------------
+void utt_layout(const int* frames, int B, int format, const int* formats, UttLayout& L) {
+    L.sample_bytes.assign((size_t)B, 0);
+    L.samples.assign((size_t)B, 0);
+    L.bytes.assign((size_t)B, 0);
+    L.off.assign((size_t)B, 0);
+    L.total_bytes = 0;
+    for (int b = 0; b < B; ++b) {
+        L.sample_bytes[(size_t)b] = format_sample_bytes(formats ? formats[b] : format);
+        L.samples[(size_t)b] = (int64_t)600 * frames[b];
+        L.bytes[(size_t)b] = L.samples[(size_t)b] * L.sample_bytes[(size_t)b];
+        L.off[(size_t)b] = (long)L.total_bytes;
+        L.total_bytes += L.bytes[(size_t)b];
+    }
+}
+
+size_t packed_bytes_bound(const HostCall& hc, int B, size_t n_samples) {
+    // (the per-request header and the base64 padding do not scale with the samples: one frame per request is where a
+    // per-sample estimate falls short)
+    if (hc.grouped()) return pack_requests_bound(hc.req_formats, hc.n_req_formats, hc.n_requests, n_samples);
+    int widest = 0;  // (per-utterance packing: the widest form of the batch sizes the packed buffer)
+    for (int b = 0; b < B; ++b) widest = format_sample_bytes(hc.format_of(b)) > widest ? format_sample_bytes(hc.format_of(b)) : widest;
+    return n_samples * (size_t)widest;
+}
+
+long pack_request_bytes(int form, long n_samples) {
+    switch (form) {
+        case 0: return 4 * n_samples;
+        case 1: return 8 * n_samples;
+        case 2: return 2 * n_samples;
+        case 3: return 44 + 4 * n_samples;
+        case 4:
+            KX_REQUIRE(36 + 2 * n_samples <= 0xFFFFFFFFL, "pack: a 16-bit WAV file cannot hold that many samples (size field of 32 bits)");
+            return 4 * ((44 + 2 * n_samples + 2) / 3);
+        default: KX_REQUIRE(false, "infer: unknown output format");
+    }
+    return 0;
+}
+
+size_t pack_requests_bound(const int* formats, int n_format, int R, size_t n_samples) {
+    // per sample: 8 (stereo), 4 (f32, float WAV), 3 >= 8 / 3 (base64 of 16 bits), 2 (PCM16); per request: the 44-byte header,
+    // or its 60 base64 characters and the last group's padding -- what a one-frame request needs beyond its samples
+    size_t per_sample = 0;
+    for (int i = 0; i < n_format; ++i) {
+        const int f = formats[i];
+        const size_t w = f == 1 ? 8 : (f == 2 ? 2 : (f == 4 ? 3 : 4));
+        per_sample = w > per_sample ? w : per_sample;
+    }
+    return n_samples * per_sample + (size_t)R * 64 + 16;
+}
+
+void build_pack_plan(const int* frames, int B, const int* chunks_per_request, int R, const int* formats, int n_format,
+                     PackPlan& plan) {
+    KX_REQUIRE(frames && formats && B >= 1 && R >= 1 && (n_format == 1 || n_format == R), "pack: bad argument");
+    plan.cum.assign((size_t)B + 1, 0);
+    for (int b = 0; b < B; ++b) {
+        KX_REQUIRE(frames[b] >= 0, "pack: negative frame count");
+        plan.cum[(size_t)b + 1] = plan.cum[(size_t)b] + 600L * frames[b];
+    }
+    plan.req.assign((size_t)R, PackReq{});
+    plan.total_bytes = 0;
+    plan.max_units = 0;
+    int row = 0;
+    for (int r = 0; r < R; ++r) {
+        const int n = chunks_per_request ? chunks_per_request[r] : 1;
+        KX_REQUIRE(n >= 1 && n <= B - row, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
+        PackReq& q = plan.req[(size_t)r];
+        q.first_row = row;
+        q.n_rows = n;
+        q.form = formats[n_format == 1 ? 0 : r];
+        q.pad_ = 0;
+        q.n_samples = plan.cum[(size_t)(row + n)] - plan.cum[(size_t)row];
+        q.out_off = plan.total_bytes;
+        q.out_bytes = pack_request_bytes(q.form, q.n_samples);
+        plan.total_bytes += q.out_bytes;
+        const long units = ((q.out_off & 15) + q.out_bytes + 15) / 16;
+        plan.max_units = units > plan.max_units ? units : plan.max_units;
+        row += n;
+    }
+    KX_REQUIRE(row == B, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
+}
+
+}  // namespace kx

@@ -615,63 +615,6 @@ __global__ __launch_bounds__(PACK_THREADS) void pack_requests_kernel(const float
     }
 }
 
-long pack_request_bytes(int form, long n_samples) {
-    switch (form) {
-        case 0: return 4 * n_samples;
-        case 1: return 8 * n_samples;
-        case 2: return 2 * n_samples;
-        case 3: return 44 + 4 * n_samples;
-        case 4:
-            KX_REQUIRE(36 + 2 * n_samples <= 0xFFFFFFFFL, "pack: a 16-bit WAV file cannot hold that many samples (size field of 32 bits)");
-            return 4 * ((44 + 2 * n_samples + 2) / 3);
-        default: KX_REQUIRE(false, "infer: unknown output format");
-    }
-    return 0;
-}
-
-size_t pack_requests_bound(const int* formats, int n_format, int R, size_t n_samples) {
-    // per sample: 8 (stereo), 4 (f32, float WAV), 3 >= 8 / 3 (base64 of 16 bits), 2 (PCM16); per request: the 44-byte header,
-    // or its 60 base64 characters and the last group's padding -- what a one-frame request needs beyond its samples
-    size_t per_sample = 0;
-    for (int i = 0; i < n_format; ++i) {
-        const int f = formats[i];
-        const size_t w = f == 1 ? 8 : (f == 2 ? 2 : (f == 4 ? 3 : 4));
-        per_sample = w > per_sample ? w : per_sample;
-    }
-    return n_samples * per_sample + (size_t)R * 64 + 16;
-}
-
-void build_pack_plan(const int* frames, int B, const int* chunks_per_request, int R, const int* formats, int n_format,
-                     PackPlan& plan) {
-    KX_REQUIRE(frames && formats && B >= 1 && R >= 1 && (n_format == 1 || n_format == R), "pack: bad argument");
-    plan.cum.assign((size_t)B + 1, 0);
-    for (int b = 0; b < B; ++b) {
-        KX_REQUIRE(frames[b] >= 0, "pack: negative frame count");
-        plan.cum[(size_t)b + 1] = plan.cum[(size_t)b] + 600L * frames[b];
-    }
-    plan.req.assign((size_t)R, PackReq{});
-    plan.total_bytes = 0;
-    plan.max_units = 0;
-    int row = 0;
-    for (int r = 0; r < R; ++r) {
-        const int n = chunks_per_request ? chunks_per_request[r] : 1;
-        KX_REQUIRE(n >= 1 && n <= B - row, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
-        PackReq& q = plan.req[(size_t)r];
-        q.first_row = row;
-        q.n_rows = n;
-        q.form = formats[n_format == 1 ? 0 : r];
-        q.pad_ = 0;
-        q.n_samples = plan.cum[(size_t)(row + n)] - plan.cum[(size_t)row];
-        q.out_off = plan.total_bytes;
-        q.out_bytes = pack_request_bytes(q.form, q.n_samples);
-        plan.total_bytes += q.out_bytes;
-        const long units = ((q.out_off & 15) + q.out_bytes + 15) / 16;
-        plan.max_units = units > plan.max_units ? units : plan.max_units;
-        row += n;
-    }
-    KX_REQUIRE(row == B, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
-}
-
 void launch_pack_requests(const float* audio, long audio_ld, const PackReq* d_req, const long* d_cum, int R, long max_units,
                           void* out, hipStream_t s) {
     if (max_units <= 0) return;

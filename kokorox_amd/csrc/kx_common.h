@@ -13,6 +13,7 @@
 #include <atomic>
 #include <mutex>
 
+#include "host_request.h"
 #include "kx_error.h"
 
 namespace kx {
@@ -46,11 +47,6 @@ struct DynLdsLimit {
         if (e_ != hipSuccess)                                                              \
             throw kx::Error(3, std::string(#expr) + ": " + hipGetErrorString(e_) + " (" +  \
                                    __FILE__ + ":" + std::to_string(__LINE__) + ")");       \
-    } while (0)
-
-#define KX_REQUIRE(cond, msg)                                 \
-    do {                                                      \
-        if (!(cond)) throw kx::Error(1, std::string(msg));    \
     } while (0)
 
 // Valid length of utterance b for a tensor = lens[b] * mul + add (lens = tokens or frames).
@@ -190,7 +186,7 @@ bool conv16_f8_layer(int BM, int rows, int K, int n_chunks16);  // layers that g
 // carries the plan out: one launch, a conv1d_mfma / conv1d_f16x3 / direct-A kernel (conv_f16x3.hip)
 void launch_conv(const ConvPlan& p, const ConvArgs& a, int B, hipStream_t s);
 int conv16_cu_count();  // CUs of the current device, or of the launching model's CU partition (conv_f16x3.hip)
-int cu_count_override(); // model.hip: the CU partition of the model that is launching on this thread (0 = none)
+int cu_count_override(); // model_forward.hip: the CU partition of the model that is launching on this thread (0 = none)
 
 // pre-split images (conv_f16x3_pre.hip)
 size_t conv16_pre_image_bytes(int Cin, int x_ld);  // per utterance
@@ -292,29 +288,7 @@ void launch_style_mix(const float* table, int n_voices, const int* voice_ids, co
 void launch_pack_audio(const float* audio, long audio_ld, const int* frames, int B, int Fmax, int format, void* out,
                        long out_stride_bytes, const long* out_off, hipStream_t s, const int* formats = nullptr);
 
-// ---- requests of several chunks, packed as the bytes a server sends (kernels_misc.hip: pack_requests_kernel) ----------
-// A request is n_rows consecutive rows of the audio slab; its output is a function of a virtual byte stream: the header of
-// its form (if any), then the sample bytes of its rows in order with nothing between them.  Forms 0..2 as launch_pack_audio,
-// 3 = 44-byte float WAV header + f32 bit copies, 4 = base64 of a 16-bit WAV file (include/kokorox_hip.h, KX_PACK_*).
-struct PackReq {
-    int first_row, n_rows, form, pad_;
-    long out_off;    // byte offset of the request's region in the compact output (a multiple of 4)
-    long out_bytes;  // size of the region (a multiple of 4 in every form)
-    long n_samples;  // 600 * the sum of its rows' frames
-};
-struct PackPlan {
-    std::vector<PackReq> req;
-    std::vector<long> cum;  // [B + 1] samples of the rows before row b, over the whole batch
-    long total_bytes = 0;
-    long max_units = 0;     // 16-byte units of the largest region (the launch's grid)
-};
-long pack_request_bytes(int form, long n_samples);  // throws KX_ERR_INVALID: unknown form, 16-bit WAV past 4 GiB
-// Worst case of a batch's compact output before the frame counts are known: R requests, n_samples samples in all, every
-// request in the widest of the given forms (the per-request header and the base64 padding do not scale with the samples).
-size_t pack_requests_bound(const int* formats, int n_format, int R, size_t n_samples);
-// chunks_per_request [R] (null: every row a request of its own, R = B), formats [n_format], n_format = 1 or R
-void build_pack_plan(const int* frames, int B, const int* chunks_per_request, int R, const int* formats, int n_format,
-                     PackPlan& plan);
+// ---- requests of several chunks (host_request.h: PackReq, PackPlan, build_pack_plan): pack_requests_kernel ----------
 // d_req [R], d_cum [B + 1]: device copies of the plan; out: 16-byte aligned, plan.total_bytes long
 void launch_pack_requests(const float* audio, long audio_ld, const PackReq* d_req, const long* d_cum, int R, long max_units,
                           void* out, hipStream_t s);

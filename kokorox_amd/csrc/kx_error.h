@@ -12,3 +12,8 @@ struct Error : std::runtime_error {
 };
 
 }  // namespace kx
+
+#define KX_REQUIRE(cond, msg)                                 \
+    do {                                                      \
+        if (!(cond)) throw kx::Error(1, std::string(msg));    \
+    } while (0)

@@ -1,6 +1,6 @@
 // The KXHIPW01 weight container on the host: the one reader of weight files, the one place a tensor table is accepted, and
-// the opt-in cache of converted `.onnx` files.  Plain C++17, no HIP: Model (model.hip) keeps only the device side, and the
-// CPU suite builds this unit with g++ -fsanitize=address,undefined (tests/cpp/kxw_fuzz.cpp).
+// the opt-in cache of converted `.onnx` files.  Plain C++17, no HIP: Model keeps only the device side (model.hip:
+// load_file, load_device_blob), and the CPU suite builds this unit with g++ -fsanitize=address,undefined (tests/cpp/kxw_fuzz.cpp).
 //
 // Layout (little endian; written by kokorox_amd/weights.py and onnx_import.cpp):
 //     0   char[8] magic "KXHIPW01"      8  u32 n_tensors      12  u32 n_tensors * 128

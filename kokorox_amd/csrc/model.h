@@ -1,6 +1,7 @@
 // Host-side model object behind the C ABI (include/kokorox_hip.h).
 #pragma once
 #include <atomic>
+#include <chrono>
 #include <functional>
 #include <map>
 #include <mutex>
@@ -61,6 +62,12 @@ struct T {
     int C = 0;
     LenMap len{nullptr, 1, 0};
     int Lmax = 0;
+    // C rows of ld floats per utterance; bs: floats from one utterance to the next where that is not C * ld
+    static T of(float* p, int C, int ld, LenMap len, int Lmax, long bs = -1) {
+        T t;
+        t.p = p; t.bs = bs >= 0 ? bs : (long)C * ld; t.ld = ld; t.C = C; t.len = len; t.Lmax = Lmax;
+        return t;
+    }
     T rows(int r0, int n) const {
         T t = *this;
         t.p = p + (long)r0 * ld;
@@ -152,6 +159,16 @@ struct LstmTimeout : Error {
     explicit LstmTimeout(const std::string& m) : Error(3, m) {}
 };
 
+// sets a variable for a scope and puts its earlier value back on every way out
+template <class V>
+struct Restore {
+    V& ref;
+    V saved;
+    Restore(V& r, V now) : ref(r), saved(r) { ref = now; }
+    ~Restore() { ref = saved; }
+    Restore(const Restore&) = delete;
+};
+
 class Model {
   public:
     Model(int device, int part = 0, int n_parts = 1);  // n_parts > 1: confined to CUs [part, part + 1) x CUs / n_parts
@@ -164,30 +181,13 @@ class Model {
 
     void infer_device(const int64_t* d_ids, int64_t t_stride, const int32_t* lens_host, int B,
                       const float* d_styles, const float* speeds_host, int n_speed, uint64_t seed, uint32_t flags,
-                      float* d_audio, int64_t audio_ld, int32_t* d_frames, int64_t* need_ld);
+                      float* d_audio, int64_t audio_ld, int32_t* d_frames, int64_t* need_ld,
+                      // device [B] each, valid for this call only: the host entries' per-row noise keys and stream indices
+                      const uint64_t* d_utt_seeds = nullptr, const uint32_t* d_utt_index = nullptr);
     void infer_host(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* styles,
                     const float* speeds, int n_speed, uint64_t seed, uint32_t flags, float** out,
                     int64_t* out_lens, const uint64_t* utt_seeds = nullptr);
-    // general host entry behind kx_infer / kx_infer_voices / kx_infer_packed
-    struct HostCall {
-        const float* styles = nullptr;       // host [B][256], or
-        const int32_t* voice_ids = nullptr;  // host [B][max_mix] into the device voice table
-        const float* weights = nullptr;      // host [B][max_mix]
-        int max_mix = 0;
-        const uint64_t* utt_seeds = nullptr;
-        int format = 0;                      // 0 f32 mono, 1 f32 stereo, 2 pcm16 mono
-        // per-utterance forms (the dispatcher's mixed batches); null = the batch-wide fields above
-        const int32_t* kinds = nullptr;      // host [B]: 0 = row of `styles`, 1 = single voice (copy), 2 = mix
-        const int32_t* formats = nullptr;    // host [B]
-        // requests of several chunks (kx_infer_requests, the dispatcher): rows are chunks, request r owns chunks_per_request[r]
-        // consecutive rows and comes out as ONE region (header of its form, then its rows' samples with nothing between them);
-        // out_bytes / out_samples of the call then have n_requests entries and `format` / `formats` are not used
-        const int32_t* chunks_per_request = nullptr;  // host [n_requests], every entry >= 1, sum = B
-        int n_requests = 0;
-        const int32_t* req_formats = nullptr;         // host [n_req_formats], values 0..4 (KX_PACK_*)
-        int n_req_formats = 0;                        // 1 (shared) or n_requests
-        const uint32_t* utt_index = nullptr;          // host [B] beside utt_seeds: row b draws (utt_seeds[b], utt_index[b])
-    };
+    using HostCall = kx::HostCall;  // (host_request.h)
     void infer_host_ex(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
                        int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out, int64_t* out_bytes,
                        int64_t* out_samples);
@@ -211,7 +211,7 @@ class Model {
     void arena_bytes(int64_t out[3]) const { out[0] = (int64_t)arenaT_.cap; out[1] = (int64_t)arenaF_.cap; out[2] = (int64_t)arenaIO_.cap; }
     // host-side milestones of the last infer_device call, ms from its entry: front half queued, front half done on the GPU (the
     // one host wait), back half planned, back half queued (= the call's return)
-    void call_times(double out[4]) const { for (int i = 0; i < 4; ++i) out[i] = call_ms_[i]; }
+    void call_times(double out[4]) const { for (int i = 0; i < 4; ++i) out[i] = call_.ms[i]; }
     void profile_enable(bool on);
     void profile_read(int64_t* launches, double* ms, double* flops);
     struct ProfRec { int rows, Cin, K, dil, stride, store; double cols, flops; float ms; double bytes; };
@@ -276,13 +276,11 @@ class Model {
     };
     Lane lanes_[N_LANES];
     int lanes_cfg_ = 0;  // 0 = by batch size (4 up to 32 utterances, else 1), 1..4 = fixed (KX_LANES, kx_set_lanes)
-    int n_lanes_ = 1;    // lanes of the running call
     std::vector<hipEvent_t> lane_ev_;
-    size_t lane_ev_used_ = 0;
     hipEvent_t record_here();               // a pooled event recorded on the current stream (null in the sizing pass)
     void wait_here(hipEvent_t e);           // the current stream waits for it
-    struct LaneScope;                       // issue on lane k until the scope ends (model.hip)
-    struct DeviceTurn;                      // one forward at a time per GPU across models (model.hip)
+    struct LaneScope;                       // issue on lane k until the scope ends (model_forward.hip)
+    struct DeviceTurn;                      // one forward at a time per GPU across models (model_forward.hip)
     void sync_lanes();
 
     int part_ = 0, n_parts_ = 1, cu_count_ = 0;  // cu_count_ = 0: the whole device
@@ -306,32 +304,82 @@ class Model {
     int n_vocab_ = 178;  // rows of the two embedding tables (vocab.rs:5-20)
 
     Arena arenaT_, arenaF_, arenaIO_;
-    const uint64_t* d_utt_seeds_ = nullptr;  // per-utterance noise keys of the running call (dispatcher)
-    const uint32_t* d_utt_index_ = nullptr;  // beside them: the utterance index of each row's stream (chunk c of a dispatched request)
     float* d_voices_ = nullptr;  // [n_voices_][511][256]
     std::atomic<int> n_voices_{0};
     int* d_pinned_ = nullptr;
-    Arena* stats_arena_ = nullptr;  // where stats() keeps the raw sums of tensors it had to read (frame-axis arena)
-    Arena* img_arena_ = nullptr;    // where conv() puts pre-split input images; non-null only while the back half is issued
     int n_pinned_ = 0;
 
-    // per-call state
-    int B_ = 0, Tmax_ = 0, Fmax_ = 0;
-    std::vector<int> hT_, hF_;
-    int *dT_ = nullptr, *dF_ = nullptr;
+    // ---- per-call state: value-initialised when a forward starts (start_call), read until the next one does -----------
+    struct PartInfo { const float2* part; int tiles, cols_per_tile, C; };
+    // a flat tile list (ConvArgs::tile_prefix), one per (length map, tile width, stream)
+    struct PrefixKey { const int* lens; int mul, add, bn; hipStream_t stream; const int* dev; };
+    struct CallState {
+        int B = 0, Tmax = 0, Fmax = 0;
+        std::vector<int> hT, hF;           // host copies of the token / frame counts
+        int *dT = nullptr, *dF = nullptr;  // the device's
+        bool taps_on = false;
+        bool dry = false;        // sizing pass: allocate (count) but launch nothing
+        bool p1_region = false;  // inside the part of the forward whose direct-A convs may run reduced precision
+        std::map<const float*, PartInfo> parts;  // output tensor -> fused statistics partials of its producer
+        std::vector<PrefixKey> prefix_keys;      // the flat tile lists belong to one call's lengths
+        size_t prefix_used = 0;
+        size_t lane_ev_used = 0;
+        int n_lanes = 1;
+        const uint64_t* d_utt_seeds = nullptr;  // per-utterance noise keys (infer_device's argument)
+        const uint32_t* d_utt_index = nullptr;  // beside them: the utterance index of each row's stream (chunk c of a dispatched request)
+        Arena* stats_arena = nullptr;  // where stats() keeps the raw sums of tensors it had to read (frame-axis arena)
+        Arena* img_arena = nullptr;    // where conv() puts pre-split input images; non-null only while the back half is issued
+        std::chrono::steady_clock::time_point t_enter;
+        double ms[4] = {0, 0, 0, 0};   // call_times()
+        void mark(int i) { ms[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count(); }
+    };
+    CallState call_;
+    // the three steps of infer_device (model_forward.hip)
+    void start_call(std::chrono::steady_clock::time_point t_enter, const int32_t* lens_host, int B, int Tmax, uint32_t flags,
+                    const uint64_t* d_utt_seeds, const uint32_t* d_utt_index);
+    struct Front {  // what the back half reads of the front half
+        T dcat, t_en;
+        const int* idx; int idx_ld, Tp;
+        uint64_t seed; int noise_off;
+        float* d_audio; int64_t audio_ld;
+    };
+    Front front_half(const int64_t* d_ids, int64_t t_stride, const int32_t* lens_host, const float* d_styles,
+                     const float* speeds_host, int n_speed, uint64_t seed, uint32_t flags, float* d_audio, int64_t audio_ld,
+                     int32_t* d_frames, int64_t* need_ld);
+    void back_half(const Front& f, Arena& A);
+    // host lengths behind a length map of the running call, and their sum in columns (+ extra per utterance)
+    const std::vector<int>& host_lens(const LenMap& lm) const { return lm.lens == call_.dT ? call_.hT : call_.hF; }
+    double host_cols(const LenMap& lm, int extra = 0) const {
+        double cols = 0;
+        for (int b = 0; b < call_.B; ++b) cols += (double)host_lens(lm)[b] * lm.mul + lm.add + extra;
+        return cols;
+    }
+    // Sizes an arena by running `plan` on it in measure mode (dry: as a sizing pass of the launch sequence, nothing is
+    // launched), grows it, then runs `plan` for real and returns what that returns.
+    template <class Plan>
+    auto plan_arena(Arena& A, bool dry, Plan&& plan) {
+        {
+            Restore<bool> measure(A.measure, true), dry_pass(call_.dry, dry);
+            A.off = 0;
+            plan(A);
+        }
+        ensure_arena(A, A.off);
+        A.off = 0;
+        return plan(A);
+    }
     // two-CU LSTM: exchange buffers (one for the main stream, one for the TextEncoder branch that runs beside it) and the
     // sticky device error word (bit 1: a half never saw its partner) checked at every host synchronisation
     unsigned long long* d_xchg_[2] = {nullptr, nullptr};
     size_t xchg_cap_ = 0;
     unsigned xchg_epoch_[2] = {0, 0};  // launches on each exchange buffer since it was last cleared (16-bit tag epoch)
-    bool p1_region_ = false;           // inside the part of the forward whose direct-A convs may run reduced precision
     bool lstm_pair_ok_ = true;         // false after a hand-off time-out: the streaming recurrence until lstm_rearm_in_ forwards were clean
     int lstm_rearm_in_ = 0;
     int64_t n_lstm_timeouts_ = 0, n_rerun_ = 0;
     void infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds, int n_speed,
                          uint64_t seed, uint32_t flags, const HostCall& hc, void** out, int64_t* out_bytes, int64_t* out_samples);
-    PackPlan pack_plan_;               // request table + sample prefixes of the running call (same lifetime rule as h_off_)
-    std::vector<long> h_off_;          // host staging that asynchronous copies read / write: outlives the calling frame
+    // host staging that asynchronous copies read / write: outlives the calling frame
+    PackPlan pack_plan_;               // request table + sample prefixes of the running call
+    UttLayout utt_layout_;             // per-utterance offsets of the running call
     unsigned h_bad_id_ = 0;
     unsigned* d_dev_err_ = nullptr;
     unsigned* h_words_ = nullptr;    // page-locked: [0] the device error word as read back
@@ -346,21 +394,12 @@ class Model {
     float* gb_ = nullptr;  // [B][gb_total_]
     float *nmean_ = nullptr, *nscale_ = nullptr, *nshift_ = nullptr;
     int n_bs_ = 0;
-    bool taps_on_ = false;
-    bool dry_ = false;  // sizing pass: allocate (count) but launch nothing
     std::map<std::string, Tap> taps_;
 
-    // flat tile lists of the running call (ConvArgs::tile_prefix), one per (length map, tile width, stream)
-    struct PrefixKey { const int* lens; int mul, add, bn; hipStream_t stream; const int* dev; };
-    std::vector<PrefixKey> prefix_keys_;
-    int* d_prefix_ = nullptr;
-    size_t prefix_cap_ = 0, prefix_used_ = 0;
+    int* d_prefix_ = nullptr;  // device block of the flat tile lists (CallState::prefix_keys)
+    size_t prefix_cap_ = 0;
     const int* tile_prefix_for(const LenMap& lm, int extra, int bn, int* total);
 
-    struct PartInfo { const float2* part; int tiles, cols_per_tile, C; };
-    std::map<const float*, PartInfo> parts_;  // output tensor -> fused statistics partials of its producer
-
-    double call_ms_[4] = {0, 0, 0, 0};
     bool diag_on_ = false;
     std::vector<DiagRec> diag_recs_;
     float* d_diag_ = nullptr;  // [diag_cap_][3]

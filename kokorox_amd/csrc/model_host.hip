@@ -1,0 +1,278 @@
+// The host side of a call: staging of a batch's inputs, the forward, the packed result in a pooled page-locked buffer.
+// What a call is refused for and where its bytes go is decided without HIP (host_request.cpp, host_pool.cpp).
+#include "model.h"
+
+#include <cstdlib>
+#include <cstring>
+
+#include "host_pool.h"
+
+namespace kx {
+
+void Model::warmup(int B, int n_tokens, int frames_per_token) {
+    KX_REQUIRE(B >= 1 && B <= 4096 && n_tokens >= 2 && n_tokens <= 512 && frames_per_token >= 1 && frames_per_token <= 50,
+               "warmup: 1..4096 utterances of 2..512 tokens at 1..50 frames per token");
+    // (the caller's pinned pattern, if any, is put back afterwards)
+    std::vector<int32_t> saved((size_t)n_pinned_);
+    if (n_pinned_) {
+        KX_HIP(hipSetDevice(device));
+        KX_HIP(hipStreamSynchronize(stream_));
+        KX_HIP(hipMemcpy(saved.data(), d_pinned_, saved.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    const int32_t fpt = frames_per_token;
+    set_pinned(&fpt, 1);
+    struct Restore {
+        Model& m;
+        std::vector<int32_t>& s;
+        ~Restore() {
+            try {
+                m.set_pinned(s.empty() ? nullptr : s.data(), (int)s.size());
+            } catch (...) {
+            }
+        }
+    } restore{*this, saved};
+    std::vector<int64_t> ids((size_t)B * n_tokens, 1);
+    for (int b = 0; b < B; ++b) ids[(size_t)b * n_tokens] = ids[(size_t)b * n_tokens + n_tokens - 1] = 0;  // the two pads
+    std::vector<int32_t> lens((size_t)B, n_tokens);
+    std::vector<float> styles((size_t)B * 256, 0.f);
+    const float speed = 1.f;
+    HostCall hc;
+    hc.styles = styles.data();
+    void* out = nullptr;
+    std::vector<int64_t> bytes((size_t)B), samples((size_t)B);
+    infer_host_ex(ids.data(), n_tokens, lens.data(), B, &speed, 1, 0, 1u /* noise off */, hc, &out, bytes.data(), samples.data());
+    host_out_free(out);
+}
+
+// page-locked scratch for the small per-call host arrays (grown when a larger batch arrives; the stream is idle then: a
+// call's copies out of it are followed by that call's synchronisations)
+int* Model::stage_ints(size_t n) {
+    if (n > h_stage_cap_) {
+        KX_HIP(hipStreamSynchronize(stream_));
+        if (h_stage_) KX_HIP(hipHostFree(h_stage_));
+        h_stage_ = nullptr;
+        h_stage_cap_ = 0;
+        const size_t want = n < 1024 ? 1024 : 2 * n;
+        KX_HIP(hipHostMalloc((void**)&h_stage_, want * sizeof(int), hipHostMallocDefault));
+        h_stage_cap_ = want;
+    }
+    return h_stage_;
+}
+
+// kx_infer_device: d_ids / d_styles were written by the caller, typically on the legacy null stream (torch's default);
+// the model's stream is non-blocking, so that order is made explicit here (an event on the null stream, no host wait).
+void Model::order_after_null_stream() {
+    KX_HIP(hipSetDevice(device));
+    KX_HIP(hipEventRecord(ev_null_, nullptr));
+    KX_HIP(hipStreamWaitEvent(stream_, ev_null_, 0));
+}
+
+// ... and on the way out: the model's streams are non-blocking, so work the caller queues on the legacy null stream AFTER
+// kx_infer_device returns (torch's default stream reading d_audio, or overwriting d_ids / d_styles for the next request) would
+// race with the back half that is still queued.  The null stream waits, on the GPU, for the end of this forward: a caller on
+// the null stream is ordered as it was when the model's stream was a blocking one; no host stall.  (Callers on other streams
+// must use kx_sync: the header says so.)
+void Model::order_null_stream_after() {
+    if (!ev_done_) KX_HIP(hipEventCreateWithFlags(&ev_done_, hipEventDisableTiming));
+    KX_HIP(hipEventRecord(ev_done_, main_stream_));
+    KX_HIP(hipStreamWaitEvent(nullptr, ev_done_, 0));
+}
+
+void Model::set_voice_table(const float* table, int n_voices) {
+    KX_REQUIRE(table && n_voices >= 1 && n_voices <= 4096, "voice table: 1..4096 voices of [511][256] floats");
+    KX_HIP(hipSetDevice(device));
+    KX_HIP(hipStreamSynchronize(stream_));
+    if (d_voices_) {
+        for (auto it = owned_.begin(); it != owned_.end(); ++it)
+            if (*it == d_voices_) {
+                owned_.erase(it);
+                break;
+            }
+        KX_HIP(hipFree(d_voices_));
+        d_voices_ = nullptr;
+    }
+    const size_t n = (size_t)n_voices * 511 * 256;
+    d_voices_ = dev_alloc(n);
+    KX_HIP(hipMemcpy(d_voices_, table, n * sizeof(float), hipMemcpyHostToDevice));
+    n_voices_.store(n_voices, std::memory_order_release);
+}
+
+void Model::infer_host(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* styles,
+                       const float* speeds, int n_speed, uint64_t seed, uint32_t flags, float** out,
+                       int64_t* out_lens, const uint64_t* utt_seeds) {
+    KX_REQUIRE(out && out_lens, "infer: null output argument");
+    HostCall hc;
+    hc.styles = styles;
+    hc.utt_seeds = utt_seeds;
+    KX_REQUIRE(styles, "infer: null argument");
+    void* p = nullptr;
+    *out = nullptr;
+    std::vector<int64_t> bytes(B > 0 ? B : 1);
+    infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, &p, bytes.data(), out_lens);
+    *out = static_cast<float*>(p);
+}
+
+// A hand-off time-out of the resident-weights recurrence invalidates the call it happened in, not the request: the host entry
+// points run the call once more, now on the streaming recurrence (same bits), and the caller sees a result, not an error.
+void Model::infer_host_ex(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
+                          int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out,
+                          int64_t* out_bytes, int64_t* out_samples) {
+    try {
+        infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples);
+    } catch (const LstmTimeout&) {
+        n_rerun_ += 1;
+        infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples);
+    }
+    note_clean_forward();
+}
+
+void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
+                            int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out,
+                            int64_t* out_bytes, int64_t* out_samples) {
+    check_host_call(ids, t_stride, lens, B, speeds, hc, out, out_bytes, out_samples, n_vocab_, n_voices_, d_voices_ != nullptr);
+    const bool grouped = hc.grouped(), by_voice = hc.by_voice();
+    const int R = grouped ? hc.n_requests : B;
+    KX_HIP(hipSetDevice(device));
+    // I/O staging lives in its own arena: ids, styles, frames, noise keys, voice picks, audio, packed audio
+    int64_t* d_ids;
+    float* d_styles;
+    int* d_fr;
+    uint64_t* d_seeds;
+    uint32_t* d_uidx;
+    PackReq* d_req = nullptr;
+    long* d_cum = nullptr;
+    int *d_vid, *d_rows, *d_kinds, *d_formats = nullptr;
+    float* d_w;
+    void* d_packed;
+    long* d_off = nullptr;
+    const int mm = by_voice ? hc.max_mix : 1;
+    auto planIO = [&](Arena& A, size_t audio_floats) {
+        d_ids = static_cast<int64_t*>(A.alloc((size_t)B * t_stride * 8));
+        d_seeds = static_cast<uint64_t*>(A.alloc((size_t)B * 8));
+        d_uidx = static_cast<uint32_t*>(A.alloc((size_t)B * 4));
+        d_styles = A.f((size_t)B * 256);
+        d_fr = A.i(B);
+        d_vid = A.i((size_t)B * mm);
+        d_rows = A.i(B);
+        d_kinds = A.i(B);
+        d_w = A.f((size_t)B * mm);
+        if (grouped) {
+            d_req = static_cast<PackReq*>(A.alloc((size_t)R * sizeof(PackReq)));
+            d_cum = static_cast<long*>(A.alloc(((size_t)B + 1) * 8));
+        } else {
+            d_formats = A.i(B);
+            d_off = static_cast<long*>(A.alloc((size_t)B * 8));
+        }
+        d_packed = A.alloc(packed_bytes_bound(hc, B, audio_floats));  // compact output: utterances / requests back to back
+        return A.f(audio_floats);
+    };
+    // worst case length is 50 frames per token; start from a typical 8 and retry once if short
+    int Tmax = 0;
+    for (int b = 0; b < B; ++b) Tmax = lens[b] > Tmax ? lens[b] : Tmax;
+    int64_t ld = (int64_t)600 * Tmax * 8;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        float* d_audio = plan_arena(arenaIO_, false, [&](Arena& A) { return planIO(A, (size_t)B * ld); });
+        KX_HIP(hipMemcpyAsync(d_ids, ids, (size_t)B * t_stride * 8, hipMemcpyHostToDevice, stream_));
+        if (hc.styles)  // (explicit rows first: the mix kernel then fills the rows of the utterances that name voices)
+            KX_HIP(hipMemcpyAsync(d_styles, hc.styles, (size_t)B * 256 * 4, hipMemcpyHostToDevice, stream_));
+        if (by_voice) {
+            std::vector<int> rows(B);
+            for (int b = 0; b < B; ++b) rows[b] = lens[b] >= 2 ? lens[b] - 2 : 0;  // tokens before the 0 padding (koko.rs:1161-1166)
+            KX_HIP(hipMemcpyAsync(d_vid, hc.voice_ids, (size_t)B * mm * 4, hipMemcpyHostToDevice, stream_));
+            KX_HIP(hipMemcpyAsync(d_w, hc.weights, (size_t)B * mm * 4, hipMemcpyHostToDevice, stream_));
+            int* st = stage_ints((size_t)3 * B);  // page-locked: rows | kinds | formats, copied on the model's own stream
+            memcpy(st, rows.data(), (size_t)B * 4);
+            KX_HIP(hipMemcpyAsync(d_rows, st, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+            if (hc.kinds) {
+                memcpy(st + B, hc.kinds, (size_t)B * 4);
+                KX_HIP(hipMemcpyAsync(d_kinds, st + B, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+            }
+            launch_style_mix(d_voices_, n_voices_, d_vid, d_w, mm, d_rows, hc.kinds ? d_kinds : nullptr, d_styles, B, stream_);
+        }
+        // (the per-row noise keys are this call's: the call state keeps pointing at them, into arenaIO_, until the next call
+        // resets it, and nothing may read them in between)
+        if (hc.utt_seeds) KX_HIP(hipMemcpyAsync(d_seeds, hc.utt_seeds, (size_t)B * 8, hipMemcpyHostToDevice, stream_));
+        if (hc.utt_index) KX_HIP(hipMemcpyAsync(d_uidx, hc.utt_index, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+        int64_t need_ld = 0;
+        try {
+            infer_device(d_ids, t_stride, lens, B, d_styles, speeds, n_speed, seed, flags, d_audio, ld, d_fr, &need_ld,
+                         hc.utt_seeds ? d_seeds : nullptr, hc.utt_index ? d_uidx : nullptr);
+        } catch (const Error& e) {
+            if (attempt == 0 && need_ld > ld) {
+                ld = need_ld;
+                continue;
+            }
+            throw;
+        }
+        // frame counts are known (the forward's one host sync): pack the B waveforms back to back on the GPU in the
+        // requested sample format, then ONE asynchronous copy into a page-locked host buffer
+        int64_t total = 0;
+        if (grouped) {
+            // the request table and the rows' sample prefixes, then ONE launch for every request of the batch, whatever its form
+            PackPlan& plan = pack_plan_;
+            build_pack_plan(call_.hF.data(), B, hc.chunks_per_request, R, hc.req_formats, hc.n_req_formats, plan);
+            for (int r = 0; r < R; ++r) {
+                out_samples[r] = plan.req[(size_t)r].n_samples;
+                out_bytes[r] = plan.req[(size_t)r].out_bytes;
+            }
+            total = plan.total_bytes;
+            KX_HIP(hipMemcpyAsync(d_req, plan.req.data(), (size_t)R * sizeof(PackReq), hipMemcpyHostToDevice, stream_));
+            KX_HIP(hipMemcpyAsync(d_cum, plan.cum.data(), ((size_t)B + 1) * 8, hipMemcpyHostToDevice, stream_));
+            launch_pack_requests(d_audio, ld, d_req, d_cum, R, plan.max_units, d_packed, stream_);
+        } else {
+            UttLayout& lay = utt_layout_;
+            utt_layout(call_.hF.data(), B, hc.format, hc.formats, lay);
+            memcpy(out_samples, lay.samples.data(), (size_t)B * 8);
+            memcpy(out_bytes, lay.bytes.data(), (size_t)B * 8);
+            total = lay.total_bytes;
+            KX_HIP(hipMemcpyAsync(d_off, lay.off.data(), (size_t)B * 8, hipMemcpyHostToDevice, stream_));
+            if (hc.formats) {
+                int* st = stage_ints((size_t)3 * B) + 2 * (size_t)B;
+                memcpy(st, hc.formats, (size_t)B * 4);
+                KX_HIP(hipMemcpyAsync(d_formats, st, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+            }
+            launch_pack_audio(d_audio, ld, call_.dF, B, call_.Fmax, hc.format, d_packed, 0, d_off, stream_, hc.formats ? d_formats : nullptr);
+        }
+        char* host = static_cast<char*>(host_out_alloc((size_t)(total > 0 ? total : 1)));
+        hipError_t e = hipMemcpyAsync(host, d_packed, (size_t)total, hipMemcpyDeviceToHost, stream_);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+        if (e != hipSuccess) {
+            host_out_free(host);
+            throw Error(3, std::string("infer: D2H copy failed: ") + hipGetErrorString(e));
+        }
+        // the sticky device error word once more: kernels of the back half (the frame-axis LSTM) can raise it after the
+        // forward's mid-way check, and the audio of THIS call would be garbage -- it must fail here, not in the next call
+        try {
+            check_dev_err();
+        } catch (...) {
+            host_out_free(host);
+            throw;
+        }
+        *out = host;
+        return;
+    }
+}
+
+// ---- pooled page-locked host buffers for the results (host_pool.cpp): the process-wide pool on hipHostMalloc ---------------
+namespace {
+void* pinned_alloc(size_t bytes) {
+    void* p = nullptr;
+    if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess || !p) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return p;
+}
+void pinned_free(void* p) { (void)hipHostFree(p); }
+HostPool& host_pool() {
+    static HostPool* p = new HostPool(pinned_alloc, pinned_free, size_t(1) << 30);  // (leaked on purpose: buffers may outlive static destruction order)
+    return *p;
+}
+}  // namespace
+
+void* host_out_alloc(size_t bytes) { return host_pool().alloc(bytes); }
+void host_out_share(void* base, void* const* parts, int n) { host_pool().share(base, parts, n); }
+size_t host_out_live_bytes() { return host_pool().live_bytes(); }
+void host_out_free(void* p) { host_pool().free(p); }
+
+}  // namespace kx

@@ -7,7 +7,9 @@ workers and condition variables (kokorox_amd/csrc/dispatcher_core.h), the except
 of the C ABI (api_guard.h) — and both headers are HIP-free so that tests/cpp/host_sanitize.cpp can drive them against a stub
 model: 64 client threads, mixed voices and output formats, batches failing as a whole (INVALID -> replayed one by one,
 DEVICE -> one retry), a model that stays broken, requests refused at submit, destroy-while-queued.
-Not covered here: the pooled page-locked buffers (HIP allocations, model.hip) — they are exercised by the GPU suite only.
+The pooled page-locked result buffers (kokorox_amd/csrc/host_pool.cpp, HIP-free as well: model_host.hip hands it hipHostMalloc
+and hipHostFree) are driven by tests/cpp/host_pool_sanitize.cpp with a counting allocator: the re-use rule, one reference per
+distinct part of a shared buffer in every order of release, the idle cap, the malloc fall-back, eight threads on one pool.
 """
 import os
 import subprocess
@@ -17,11 +19,14 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.parametrize("name,flags,env", [
+SANITIZERS = [
     ("thread", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1:second_deadlock_stack=1"}),
     ("address", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
      {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=1", "UBSAN_OPTIONS": "halt_on_error=1"}),
-])
+]
+
+
+@pytest.mark.parametrize("name,flags,env", SANITIZERS)
 def test_dispatcher_and_api_guard_under_sanitizers(tmp_path, name, flags, env):
     exe = str(tmp_path / f"host_{name}")
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", *flags, "-I", os.path.join(ROOT, "kokorox_amd", "csrc"),
@@ -29,6 +34,18 @@ def test_dispatcher_and_api_guard_under_sanitizers(tmp_path, name, flags, env):
     for _ in range(3):  # (thread interleavings differ from run to run)
         r = subprocess.run([exe], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0 and "scenarios passed" in r.stdout, r.stdout[-1000:] + r.stderr[-6000:]
+        assert "WARNING: ThreadSanitizer" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr
+
+
+@pytest.mark.parametrize("name,flags,env", SANITIZERS)
+def test_result_buffer_pool_under_sanitizers(tmp_path, name, flags, env):
+    exe = str(tmp_path / f"pool_{name}")
+    csrc = os.path.join(ROOT, "kokorox_amd", "csrc")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", *flags, "-I", csrc, os.path.join(ROOT, "tests", "cpp", "host_pool_sanitize.cpp"),
+                    os.path.join(csrc, "host_pool.cpp"), "-o", exe, "-lpthread"], check=True)
+    for _ in range(3):  # (thread interleavings differ from run to run)
+        r = subprocess.run([exe], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0 and "host pool: all scenarios passed" in r.stdout, r.stdout[-1000:] + r.stderr[-6000:]
         assert "WARNING: ThreadSanitizer" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr
 
 
