@@ -276,7 +276,8 @@ int kx_set_voice_table(kx_model* m, const float* table, int n_voices);
 #define KX_PACK_F32_MONO 0
 #define KX_PACK_F32_STEREO 1
 #define KX_PACK_PCM16_MONO 2
-/* The bodies the reference's servers send, mono at 24 000 Hz (kx_infer_requests and kx_dispatcher_submit_request only):
+/* The bodies the reference's servers send, mono, at 24 000 Hz unless the format word says otherwise (kx_infer_requests and
+ * kx_dispatcher_submit_request only):
  * 3 = the HTTP body (kokorox-openai/src/lib.rs:416-425): the 44 bytes of `WavHeader::new(1, 24000, 32).write_header`
  *     (kokorox/src/utils/wav.rs:18-50: IEEE float, both size fields the reference's 0xFFFFFFFF placeholders) followed by the
  *     samples as f32 little-endian bit copies (a NaN keeps its payload); 44 + 4 S bytes.
@@ -288,6 +289,51 @@ int kx_set_voice_table(kx_model* m, const float* table, int n_voices);
  * (Form 2, as it has been since it was added, clamps with fmax / fmin, which drop a NaN: a NaN sample becomes -32767 there.) */
 #define KX_PACK_WAV_F32 3
 #define KX_PACK_WAV16_BASE64 4
+/* Raw G.711, one byte per sample, no header (kx_infer_requests and kx_dispatcher_submit_request only): the 16-bit-input
+ * algorithms that CPython's audioop.lin2ulaw / lin2alaw (width 2) implement, applied to form 4's 16-bit sample v (NaN -> 0).
+ * 8 = mu-law: p = v >> 2 (arithmetic); p < 0: p = -p, mask 0x7F, else mask 0xFF; p = min(p, 8159) + 33; seg = the first index
+ *     with p <= {0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF, 0x1FFF}; none: byte = 0x7F ^ mask; else
+ *     byte = ((seg << 4) | ((p >> (seg + 1)) & 15)) ^ mask.
+ * 9 = A-law: v >= 0: mask 0xD5, m = v, else mask 0x55, m = -v - 1; p = m >> 3; seg = the first index with
+ *     p <= {0x1F, 0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF}; mantissa = (p >> 1) & 15 for seg 0 and 1, (p >> seg) & 15 above;
+ *     byte = ((seg << 4) | mantissa) ^ mask.
+ * Forms 5, 6 and 7 do not exist and are refused ("infer: unknown output format"). */
+#define KX_PACK_MULAW 8
+#define KX_PACK_ALAW 9
+
+/* The `format` / `formats[]` value of kx_infer_requests and kx_dispatcher_submit_request is a WORD: bits 0..7 = the form above
+ * (0..4, 8, 9), bits 8..11 = the output sample rate, every other bit zero (else "infer: unknown output format").  Rate code 0 =
+ * 24 000 Hz, the model's own rate: the bytes of the plain forms, unchanged.  Codes 4..15 are refused with KX_ERR_INVALID,
+ * "infer: unknown output sample rate".  Every form combines with every rate.  (kx_infer, kx_infer_packed, kx_infer_voices,
+ * kx_dispatcher_submit and kx_dispatcher_submit_ex keep taking the forms 0..2 and nothing else.)
+ *
+ * With a rate code the request's stream x[0..S) -- its chunks' samples appended, S a multiple of 600 -- is resampled on the GPU
+ * as a whole before its form is applied (a chunk boundary is invisible to the filter); out_samples[r] then counts samples at
+ * the OUTPUT rate, S L / M, the WAV headers of forms 3 and 4 carry that rate and its byte rate (rate x 4, rate x 2), and form
+ * 4's text ends in zero, one or two `=` ((44 + 2 S L / M) mod 3 takes all three values; its 4 GiB refusal counts output samples).
+ *
+ *   code   rate     (L, M)   Q = max(L, M)   C = 24 Q   N = 2 C + 1 taps
+ *    1     8000     (1, 3)        3             72          145
+ *    2    16000     (2, 3)        3             72          145
+ *    3    48000     (2, 1)        2             48           97
+ *
+ * Taps: h[i] = sinc((i - C) / Q) * kaiser_N(i; beta = 10.0) in float64 (sinc(t) = sin(pi t) / (pi t)), scaled so that their sum
+ * is L, rounded once to float32 (committed as bit patterns: kx_resample_filter hands them out).  With x[j] = 0 outside the stream,
+ *     y[n] = f32( sum_j f64(h[n M - j L + C]) * f64(x[j]) ),   n in [0, S L / M),
+ * over every j in [0, S) with 0 <= n M - j L + C < N, in ASCENDING j, the accumulator a float64 that starts at +0, one addition
+ * per term, then one round-to-nearest-even conversion to f32.  A product of two float32 values is exact in float64, so a fused
+ * multiply-add and a separate multiply and add give the same bits: a host loop in that order reproduces the GPU bit for bit
+ * (subnormal and infinite inputs aside).  Pass band to 0.85 of the smaller Nyquist frequency within 2e-5, -6 dB at it, below
+ * -99 dB from 1.15 of it. */
+#define KX_PACK_RATE_24000 0x000
+#define KX_PACK_RATE_8000 0x100
+#define KX_PACK_RATE_16000 0x200
+#define KX_PACK_RATE_48000 0x300
+#define KX_RESAMPLE_MAX_TAPS 145
+/* The filter of a format word's rate code, from the library's one table; host only, touches no GPU.  Any of L, M, n_taps, taps
+ * may be NULL; taps receives n_taps floats (cap = its capacity in floats, KX_RESAMPLE_MAX_TAPS always suffices).  Rate code 0
+ * gives L = M = 1 and no taps.  An unknown word is refused as by kx_infer_requests. */
+int kx_resample_filter(int format_word, int32_t* L, int32_t* M, int32_t* n_taps, float* taps, int cap);
 
 /* kx_infer with device-side style lookup/mix and packed output.  *out = library-owned bytes of the B utterances back
  * to back (kx_free_packed); out_bytes[b] / out_samples[b] per utterance. */
@@ -305,10 +351,11 @@ void kx_free_packed(void* p);
  * GPU.  Rows are chunks; request r owns chunks_per_request[r] consecutive rows (every entry >= 1, their sum = B, otherwise
  * KX_ERR_INVALID).  The voice is per row: `styles` [B,256], or NULL with `voice_ids` / `weights` [B,max_mix] as
  * kx_infer_voices (the row of a voice is lens[b] - 2 of each chunk, koko.rs:1166).  Row b draws the noise stream
- * (seed, utterance base + b) exactly as kx_infer.  `formats` [n_format], n_format = 1 (shared) or R, values KX_PACK_* 0..4.
+ * (seed, utterance base + b) exactly as kx_infer.  `formats` [n_format], n_format = 1 (shared) or R: format words (a KX_PACK_*
+ * form, optionally | KX_PACK_RATE_*).
  * *out = one pooled page-locked buffer (kx_free_packed) holding the R requests back to back: request r is the header of its
  * form, if any, then its chunks' samples in order with nothing between chunks; out_bytes[r], out_samples[r] (= 600 x the sum
- * of its chunks' frames) per request.  Forms 0..2 give the bytes of kx_infer_packed. */
+ * of its chunks' frames, x L / M with a rate code) per request.  Forms 0..2 at rate code 0 give the bytes of kx_infer_packed. */
 int kx_infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
                       const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
                       const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
@@ -356,7 +403,7 @@ int kx_dispatcher_submit_ex(kx_dispatcher* d, const int64_t* ids, int n_tokens, 
 /* A request of 1 .. max_batch chunks (the chunk loop of koko.rs:947-1191 as one submit): `ids` holds the chunks back to back,
  * chunk c has chunk_tokens[c] ids incl. its own two 0 pads; `styles` = n_chunks rows of 256 floats, or NULL with ONE voice
  * spec for the request as in kx_dispatcher_submit_ex (the row of the voice is chunk_tokens[c] - 2 per chunk); `format` is a
- * KX_PACK_* form 0..4.  Checked completely at submit with the rules of kx_dispatcher_submit_ex per chunk.  The chunks run as
+ * format word (a KX_PACK_* form, optionally | KX_PACK_RATE_*).  Checked completely at submit with the rules of kx_dispatcher_submit_ex per chunk.  The chunks run as
  * rows of ONE batched forward (a request is never split over batches or models; batches are sized in rows), chunk c draws
  * the noise stream (seed, c), and *out is the request's one region: header of the form, if any, then the chunks' samples in
  * order.  The bytes equal kx_infer_requests (R = 1, same seed, utterance base 0) whatever the request was batched with and

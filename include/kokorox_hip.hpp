@@ -12,6 +12,28 @@
 
 namespace kokorox {
 
+// The format word of infer_requests / submit_request: a form, optionally or'ed with an output rate (kokorox_hip.h, KX_PACK_*).
+constexpr int PACK_F32_MONO = KX_PACK_F32_MONO, PACK_F32_STEREO = KX_PACK_F32_STEREO, PACK_PCM16_MONO = KX_PACK_PCM16_MONO,
+              PACK_WAV_F32 = KX_PACK_WAV_F32, PACK_WAV16_BASE64 = KX_PACK_WAV16_BASE64, PACK_MULAW = KX_PACK_MULAW,
+              PACK_ALAW = KX_PACK_ALAW;
+constexpr int PACK_RATE_24000 = KX_PACK_RATE_24000, PACK_RATE_8000 = KX_PACK_RATE_8000, PACK_RATE_16000 = KX_PACK_RATE_16000,
+              PACK_RATE_48000 = KX_PACK_RATE_48000;
+
+// The resampler behind a format word's rate code (kx_resample_filter; host only): output rate / 24 000 = L / M and the taps.
+struct ResampleFilter {
+    int32_t L = 1, M = 1;
+    std::vector<float> taps;
+};
+inline ResampleFilter resample_filter(int format_word) {
+    ResampleFilter f;
+    int32_t n = 0;
+    f.taps.resize(KX_RESAMPLE_MAX_TAPS);
+    if (kx_resample_filter(format_word, &f.L, &f.M, &n, f.taps.data(), (int)f.taps.size()) != KX_OK)
+        throw std::invalid_argument("resample_filter: unknown output format or sample rate");
+    f.taps.resize((size_t)n);
+    return f;
+}
+
 class HipKoko {
   public:
     explicit HipKoko(const std::string& model_path, int device = 0) {
@@ -74,8 +96,8 @@ class HipKoko {
     }
 
     // The chunk loop of TTSKoko::tts_raw_audio (koko.rs:947-1191) as one forward (kx_infer_requests): tokens = the chunks (each
-    // 0-wrapped), request r owns chunks_per_request[r] consecutive ones, styles = one row per chunk, format = a KX_PACK_* form
-    // 0..4 for every request.  Returns each request's body: header of the form, if any, then its chunks' samples in order
+    // 0-wrapped), request r owns chunks_per_request[r] consecutive ones, styles = one row per chunk, format = a format word
+    // (a KX_PACK_* form, optionally | KX_PACK_RATE_*) for every request.  Returns each request's body: header of the form, if any, then its chunks' samples in order
     // (KX_PACK_WAV_F32: the HTTP body; KX_PACK_WAV16_BASE64: the WebSocket chunk's base64 text).
     std::vector<std::string> infer_requests(const std::vector<std::vector<int64_t>>& tokens,
                                             const std::vector<int32_t>& chunks_per_request,
@@ -120,7 +142,7 @@ class HipKoko {
 };
 
 // A request of 1 .. max_batch chunks through a dispatcher (kx_dispatcher_submit_request): ids = the chunks back to back, each
-// with its own two 0 pads, styles = one 256-float row per chunk; returns the body in the given KX_PACK_* form (0..4).
+// with its own two 0 pads, styles = one 256-float row per chunk; returns the body in the given format word (a KX_PACK_* form, optionally | a rate).
 inline std::string submit_request(kx_dispatcher* d, const std::vector<std::vector<int64_t>>& chunks,
                                   const std::vector<float>& styles, float speed, uint64_t seed, int format) {
     std::vector<int64_t> ids;

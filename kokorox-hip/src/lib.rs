@@ -34,6 +34,15 @@ pub const KX_PACK_PCM16_MONO: c_int = 2;
 pub const KX_PACK_WAV_F32: c_int = 3;
 /// The WebSocket chunk: base64 of a 16-bit WAV file (`encode_audio`, kokorox-websocket/src/lib.rs:696-736); requests only.
 pub const KX_PACK_WAV16_BASE64: c_int = 4;
+/// Raw G.711 mu-law / A-law of the 16-bit sample, one byte per sample, no header; requests only.
+pub const KX_PACK_MULAW: c_int = 8;
+pub const KX_PACK_ALAW: c_int = 9;
+/// The output sample rate, or'ed into a request's form (bits 8..11 of the format word; 0 = the model's 24 000 Hz).
+pub const KX_PACK_RATE_24000: c_int = 0x000;
+pub const KX_PACK_RATE_8000: c_int = 0x100;
+pub const KX_PACK_RATE_16000: c_int = 0x200;
+pub const KX_PACK_RATE_48000: c_int = 0x300;
+pub const KX_RESAMPLE_MAX_TAPS: usize = 145;
 
 #[repr(C)]
 pub struct KxModel {
@@ -49,6 +58,7 @@ extern "C" {
     fn kx_init(device_id: c_int, err: *mut c_char, err_len: usize) -> c_int;
     fn kx_create(weights_path: *const c_char, device_id: c_int, err: *mut c_char, err_len: usize) -> *mut KxModel;
     fn kx_import_onnx(onnx_path: *const c_char, out_path: *const c_char, err: *mut c_char, err_len: usize) -> c_int;
+    fn kx_resample_filter(format_word: c_int, l: *mut i32, m: *mut i32, n_taps: *mut i32, taps: *mut f32, cap: c_int) -> c_int;
     fn kx_create_from_device_blob(d_blob: *const c_void, n_bytes: usize, device_id: c_int, err: *mut c_char,
                                   err_len: usize) -> *mut KxModel;
     fn kx_create_replicas(weights_path: *const c_char, device_ids: *const c_int, n: c_int,
@@ -148,6 +158,21 @@ pub fn import_onnx(onnx_path: &str, out_path: &str) -> Result<(), String> {
     match unsafe { kx_import_onnx(a.as_ptr(), b.as_ptr(), err.as_mut_ptr(), err.len()) } {
         KX_OK => Ok(()),
         _ => Err(cstr_buf(&err)),
+    }
+}
+
+/// Host only: `(L, M, taps)` of the resampler behind a format word's rate code, from the library's one table (`L / M` = output
+/// rate / 24 000, the float32 taps of the FIR; rate code 0 gives `(1, 1, [])`).  What a host-side check of a resampled body
+/// needs: output n is the f32 rounding of the float64 sum, over ascending j, of `taps[n * M - j * L + C] * x[j]`.
+pub fn resample_filter(format_word: i32) -> Result<(i32, i32, Vec<f32>), String> {
+    let (mut l, mut m, mut n) = (0i32, 0i32, 0i32);
+    let mut taps = vec![0f32; KX_RESAMPLE_MAX_TAPS];
+    match unsafe { kx_resample_filter(format_word, &mut l, &mut m, &mut n, taps.as_mut_ptr(), taps.len() as c_int) } {
+        KX_OK => {
+            taps.truncate(n as usize);
+            Ok((l, m, taps))
+        }
+        _ => Err("unknown output format or sample rate".to_string()),
     }
 }
 
@@ -373,7 +398,7 @@ impl HipKoko {
     }
 
     /// The chunk loop of `TTSKoko::tts_raw_audio` (koko.rs:947-1191) as one forward: `tokens` are the chunks, request r owns
-    /// `chunks_per_request[r]` consecutive ones, `styles` holds one row per chunk, `formats` one KX_PACK_* form (0..4) for
+    /// `chunks_per_request[r]` consecutive ones, `styles` holds one row per chunk, `formats` one format word (a KX_PACK_* form, optionally | KX_PACK_RATE_*) for
     /// all requests or one per request.  Returns each request's body: header of its form, if any, then its chunks' samples
     /// in order with nothing between them.
     pub fn infer_requests(&self, tokens: &[Vec<i64>], chunks_per_request: &[i32], styles: &[Vec<f32>], speeds: &[f32],
@@ -629,7 +654,8 @@ impl HipKokoDispatcher {
 
     /// A request of 1 .. max_batch chunks (`chunks`: the 0-wrapped id lists of the chunk loop, koko.rs:947-1191) as rows of one
     /// batched forward; `Voice::Row` carries one 256-float row per chunk, back to back.  Returns the request's body in the given
-    /// KX_PACK_* form (0..4) and its sample count; the bytes equal `HipKoko::infer_requests` of the request alone.
+    /// format word (a KX_PACK_* form, optionally | KX_PACK_RATE_*) and its sample count at that rate; the bytes equal
+    /// `HipKoko::infer_requests` of the request alone.
     pub fn submit_request(&self, chunks: &[Vec<i64>], voice: Voice, speed: f32, seed: u64, format: i32)
                           -> Result<(Vec<u8>, i64), Box<dyn Error>> {
         let ids: Vec<i64> = chunks.iter().flatten().copied().collect();
@@ -675,6 +701,12 @@ impl HipKokoDispatcher {
                                  -> Result<String, Box<dyn Error>> {
         let (bytes, _) = self.submit_request(chunks, voice, speed, seed, KX_PACK_WAV16_BASE64)?;
         Ok(String::from_utf8(bytes)?) // (base64 is ASCII: this never fails on what the library returns)
+    }
+
+    /// A request as telephony wants it: raw G.711 mu-law bytes at 8 kHz, resampled and encoded on the GPU.
+    pub fn submit_request_mulaw_8k(&self, chunks: &[Vec<i64>], voice: Voice, speed: f32, seed: u64) -> Result<Vec<u8>, Box<dyn Error>> {
+        let (bytes, _) = self.submit_request(chunks, voice, speed, seed, KX_PACK_MULAW | KX_PACK_RATE_8000)?;
+        Ok(bytes)
     }
 
     /// Batches each model (GPU) has run so far.

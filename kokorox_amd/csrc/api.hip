@@ -49,6 +49,27 @@ int kx_import_onnx(const char* onnx_path, const char* out_path, char* err, size_
     });
 }
 
+int kx_resample_filter(int format_word, int32_t* L, int32_t* M, int32_t* n_taps, float* taps, int cap) {
+    return guarded_free(nullptr, 0, [&] {
+        kx::check_format_word(format_word);
+        const int code = kx::format_rate(format_word);
+        if (code == 0) {  // 24 000 Hz: the samples as they are
+            if (L) *L = 1;
+            if (M) *M = 1;
+            if (n_taps) *n_taps = 0;
+            return;
+        }
+        const kx::ResampleFilter& f = kx::resample_filter(code);
+        if (L) *L = f.L;
+        if (M) *M = f.M;
+        if (n_taps) *n_taps = f.n_taps;
+        if (taps) {
+            KX_REQUIRE(cap >= f.n_taps, "resample_filter: cap is smaller than the number of taps");
+            std::memcpy(taps, f.taps, (size_t)f.n_taps * sizeof(float));
+        }
+    });
+}
+
 kx_model* kx_create_from_device_blob(const void* d_blob, size_t n_bytes, int device_id, char* err, size_t err_len) {
     kx_model* h = nullptr;
     int rc = guarded_free(err, err_len, [&] {

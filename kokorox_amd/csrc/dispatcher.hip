@@ -33,7 +33,8 @@ struct ModelBackend {
         size_t stride = 0;
         int mm = 1;
         // plain = every request is one row in form 0..2: the single-utterance traffic of submit / submit_ex, which keeps the
-        // per-utterance packing it has always had (pack_audio_kernel); anything else goes through the request packer
+        // per-utterance packing it has always had (pack_audio_kernel); anything else (several chunks, forms 3 / 4 / 8 / 9, a rate
+        // code: all of them words above 2) goes through the request packer
         bool any_voice = false, plain = true;
         for (Request* r : batch) {
             plain = plain && r->rows() == 1 && r->format <= KX_PACK_PCM16_MONO;

@@ -14,7 +14,8 @@
 //   * a request names its voice either as the 256-float style row (what `mix_styles` returns, koko.rs:1255-1306) or as
 //     (voice id, weight) pairs into the device voice table, single voice or mix, and its output form (f32 mono / f32
 //     stereo, koko.rs:1239-1246 / PCM16, kokorox-websocket/src/lib.rs:696-736; a request of chunks also the two bodies the
-//     servers send, float WAV and base64 of a 16-bit WAV file); requests of every kind share one batch.
+//     servers send, float WAV and base64 of a 16-bit WAV file, G.711 bytes, and any of them at 8, 16 or 48 kHz); requests of
+//     every kind, form and rate share one batch.
 //   * a request is 1 .. max_batch CHUNKS (the chunk loop of koko.rs:947-1191 as one submit): its chunks are consecutive rows
 //     of one forward and its result is one region.  Batches are sized in ROWS; a request is never split over batches or
 //     models, and a worker always takes the request at the head of the queue, so a request of max_batch chunks cannot starve
@@ -309,10 +310,20 @@ struct Core {
         return n < 0 ? 0 : n;
     }
 
+    // format_word: `format` is the word of the request entries (include/kokorox_hip.h: a form 0..4, 8 or 9 in bits 0..7, a
+    // rate code 0..3 in bits 8..11, nothing else); otherwise one of the three forms 0..2 of the single-utterance submits
     bool check_common(const int64_t* ids, int n_tokens, float speed, int format, const char* who, char* err,
-                      size_t err_len, int max_format = KX_PACK_PCM16_MONO) {
-        if (!ids || n_tokens < 1 || n_tokens > KX_MAX_TOKENS || !(speed > 0.f) || format < 0 || format > max_format) {
-            if (err && err_len) snprintf(err, err_len, "%s: bad argument (1..512 tokens, speed > 0, format 0..%d)", who, max_format);
+                      size_t err_len, bool format_word = false) {
+        const int form = format_word ? (format & 0xFF) : format;
+        const bool form_ok = format_word ? (format >= 0 && (format & ~0xFFF) == 0 && (form <= KX_PACK_WAV16_BASE64 || form == KX_PACK_MULAW || form == KX_PACK_ALAW))
+                                         : (format >= 0 && format <= KX_PACK_PCM16_MONO);
+        if (!ids || n_tokens < 1 || n_tokens > KX_MAX_TOKENS || !(speed > 0.f) || !form_ok) {
+            if (err && err_len)
+                snprintf(err, err_len, "%s: bad argument (1..512 tokens, speed > 0, format %s)", who, format_word ? "0..4, 8, 9 | rate code << 8" : "0..2");
+            return false;
+        }
+        if (format_word && ((format >> 8) & 15) > 3) {
+            if (err && err_len) snprintf(err, err_len, "%s: unknown output sample rate (rate codes 0..3)", who);
             return false;
         }
         const int nv = vocab_everywhere();  // (from the models' embedding tables: vocab.rs:5-20 has 178 rows, a checkpoint may differ)
@@ -416,7 +427,7 @@ struct Core {
 
     // A request of n_chunks chunks: ids = the chunks back to back (chunk c has chunk_tokens[c] ids incl. its two 0 pads);
     // styles = n_chunks rows of 256 floats, or null with ONE voice spec for the whole request as in submit_ex (the row of the
-    // voice is chunk_tokens[c] - 2 per chunk, koko.rs:1166); format 0 .. 4.  Every chunk is checked with submit_ex's rules.
+    // voice is chunk_tokens[c] - 2 per chunk, koko.rs:1166); format = a format word.  Every chunk is checked with submit_ex's rules.
     int submit_request(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
                        const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
                        void** out, int64_t* out_bytes, int64_t* out_samples, char* err, size_t err_len) {
@@ -442,7 +453,7 @@ struct Core {
                     snprintf(err, err_len, "%s: chunk %d: 1..512 tokens (with a voice: at least the two 0 pads)", who, c);
                 return KX_ERR_INVALID;
             }
-            if (!check_common(ids + total, chunk_tokens[c], speed, format, who, err, err_len, KX_PACK_WAV16_BASE64)) return KX_ERR_INVALID;
+            if (!check_common(ids + total, chunk_tokens[c], speed, format, who, err, err_len, true)) return KX_ERR_INVALID;
             total += (size_t)chunk_tokens[c];
             min_tokens = chunk_tokens[c] < min_tokens ? chunk_tokens[c] : min_tokens;
         }

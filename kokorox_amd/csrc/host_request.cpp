@@ -1,7 +1,51 @@
 // The argument checks of the two inference entries and the layout of their compact output (host_request.h).  No HIP.
 #include "host_request.h"
 
+#include <cstring>
+
+#include "resample_taps.h"
+
 namespace kx {
+
+// ---- the format word and the resampler's tables ------------------------------------------------------------------------------
+void check_format_word(int word) {
+    const int form = format_form(word);
+    KX_REQUIRE(word >= 0 && (word & ~0xFFF) == 0 && (form <= 4 || form == 8 || form == 9), "infer: unknown output format");
+    KX_REQUIRE(format_rate(word) <= 3, "infer: unknown output sample rate");
+}
+
+namespace {
+// (the tables are committed as bit patterns: what the library computes with is what the generator rounded)
+const uint32_t kBits8000[KX_RESAMPLE_NTAPS_8000] = {KX_RESAMPLE_TAPS_8000};
+const uint32_t kBits16000[KX_RESAMPLE_NTAPS_16000] = {KX_RESAMPLE_TAPS_16000};
+const uint32_t kBits48000[KX_RESAMPLE_NTAPS_48000] = {KX_RESAMPLE_TAPS_48000};
+struct FilterTables {
+    float taps[3][KX_RESAMPLE_NTAPS_8000];
+    ResampleFilter f[3];
+    FilterTables() {
+        static_assert(sizeof(float) == 4 && KX_RESAMPLE_NTAPS_16000 <= KX_RESAMPLE_NTAPS_8000 && KX_RESAMPLE_NTAPS_48000 <= KX_RESAMPLE_NTAPS_8000,
+                      "float32 bit patterns, the 8000 Hz table the longest");
+        std::memcpy(taps[0], kBits8000, sizeof kBits8000);
+        std::memcpy(taps[1], kBits16000, sizeof kBits16000);
+        std::memcpy(taps[2], kBits48000, sizeof kBits48000);
+        f[0] = ResampleFilter{1, 3, 72, KX_RESAMPLE_NTAPS_8000, taps[0]};
+        f[1] = ResampleFilter{2, 3, 72, KX_RESAMPLE_NTAPS_16000, taps[1]};
+        f[2] = ResampleFilter{2, 1, 48, KX_RESAMPLE_NTAPS_48000, taps[2]};
+    }
+};
+}  // namespace
+
+const ResampleFilter& resample_filter(int rate_code) {
+    KX_REQUIRE(rate_code >= 1 && rate_code <= 3, "infer: unknown output sample rate");
+    static const FilterTables tables;
+    return tables.f[rate_code - 1];
+}
+
+long resampled_samples(int rate_code, long n_samples) {
+    if (rate_code == 0) return n_samples;
+    const ResampleFilter& f = resample_filter(rate_code);
+    return n_samples * f.L / f.M;
+}
 
 // ---- refusals of the host entry (Model::infer_host_once) ---------------------------------------------------------------------
 void check_host_call(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds, const HostCall& hc,
@@ -22,8 +66,7 @@ void check_host_call(const int64_t* ids, int64_t t_stride, const int32_t* lens, 
             rows += hc.chunks_per_request[r];
         }
         KX_REQUIRE(rows == B, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
-        for (int i = 0; i < hc.n_req_formats; ++i)
-            KX_REQUIRE(hc.req_formats[i] >= 0 && hc.req_formats[i] <= 4, "infer: unknown output format");
+        for (int i = 0; i < hc.n_req_formats; ++i) check_format_word(hc.req_formats[i]);
     }
     KX_REQUIRE(!hc.utt_index || hc.utt_seeds, "infer: utterance indices go with per-row seeds");
     const bool by_voice = hc.by_voice();
@@ -95,29 +138,42 @@ size_t packed_bytes_bound(const HostCall& hc, int B, size_t n_samples) {
 }
 
 long pack_request_bytes(int form, long n_samples) {
-    switch (form) {
-        case 0: return 4 * n_samples;
-        case 1: return 8 * n_samples;
-        case 2: return 2 * n_samples;
-        case 3: return 44 + 4 * n_samples;
+    check_format_word(form);
+    const long n = resampled_samples(format_rate(form), n_samples);  // samples at the output rate
+    switch (format_form(form)) {
+        case 0: return 4 * n;
+        case 1: return 8 * n;
+        case 2: return 2 * n;
+        case 3: return 44 + 4 * n;
         case 4:
-            KX_REQUIRE(36 + 2 * n_samples <= 0xFFFFFFFFL, "pack: a 16-bit WAV file cannot hold that many samples (size field of 32 bits)");
-            return 4 * ((44 + 2 * n_samples + 2) / 3);
-        default: KX_REQUIRE(false, "infer: unknown output format");
+            KX_REQUIRE(36 + 2 * n <= 0xFFFFFFFFL, "pack: a 16-bit WAV file cannot hold that many samples (size field of 32 bits)");
+            return 4 * ((44 + 2 * n + 2) / 3);
+        default: return n;  // 8, 9: one G.711 byte per sample
     }
-    return 0;
 }
 
 size_t pack_requests_bound(const int* formats, int n_format, int R, size_t n_samples) {
-    // per sample: 8 (stereo), 4 (f32, float WAV), 3 >= 8 / 3 (base64 of 16 bits), 2 (PCM16); per request: the 44-byte header,
-    // or its 60 base64 characters and the last group's padding -- what a one-frame request needs beyond its samples
+    // per sample: 8 (stereo), 4 (f32, float WAV), 3 >= 8 / 3 (base64 of 16 bits), 2 (PCM16), 1 (G.711), twice that at 48 000 Hz
+    // (the lower rates are counted as 24 000 Hz); per request: the 44-byte header, or its 60 base64 characters and the last
+    // group's padding -- what a one-frame request needs beyond its samples
     size_t per_sample = 0;
     for (int i = 0; i < n_format; ++i) {
-        const int f = formats[i];
-        const size_t w = f == 1 ? 8 : (f == 2 ? 2 : (f == 4 ? 3 : 4));
+        const int f = format_form(formats[i]);
+        size_t w = f == 1 ? 8 : (f == 2 ? 2 : (f == 4 ? 3 : (f >= 8 ? 1 : 4)));
+        if (format_rate(formats[i]) == 3) w *= 2;
         per_sample = w > per_sample ? w : per_sample;
     }
     return n_samples * per_sample + (size_t)R * 64 + 16;
+}
+
+size_t resample_floats_bound(const int* formats, int n_format, size_t n_samples) {
+    size_t per_sample = 0;  // (every request at the batch's highest ratio: 2 at 48 000 Hz, below 1 otherwise)
+    for (int i = 0; i < n_format; ++i) {
+        const int c = format_rate(formats[i]);
+        const size_t w = c == 0 ? 0 : (c == 3 ? 2 : 1);
+        per_sample = w > per_sample ? w : per_sample;
+    }
+    return n_samples * per_sample;
 }
 
 void build_pack_plan(const int* frames, int B, const int* chunks_per_request, int R, const int* formats, int n_format,
@@ -131,6 +187,8 @@ void build_pack_plan(const int* frames, int B, const int* chunks_per_request, in
     plan.req.assign((size_t)R, PackReq{});
     plan.total_bytes = 0;
     plan.max_units = 0;
+    plan.y_floats = 0;
+    plan.max_resampled = 0;
     int row = 0;
     for (int r = 0; r < R; ++r) {
         const int n = chunks_per_request ? chunks_per_request[r] : 1;
@@ -138,11 +196,20 @@ void build_pack_plan(const int* frames, int B, const int* chunks_per_request, in
         PackReq& q = plan.req[(size_t)r];
         q.first_row = row;
         q.n_rows = n;
-        q.form = formats[n_format == 1 ? 0 : r];
-        q.pad_ = 0;
-        q.n_samples = plan.cum[(size_t)(row + n)] - plan.cum[(size_t)row];
+        const int word = formats[n_format == 1 ? 0 : r];
+        check_format_word(word);
+        q.form = format_form(word);
+        q.pad_ = format_rate(word);
+        q.src_samples = plan.cum[(size_t)(row + n)] - plan.cum[(size_t)row];
+        q.n_samples = resampled_samples(q.pad_, q.src_samples);
+        q.y_off = 0;
+        if (q.pad_) {
+            q.y_off = plan.y_floats;
+            plan.y_floats += q.n_samples;
+            plan.max_resampled = q.n_samples > plan.max_resampled ? q.n_samples : plan.max_resampled;
+        }
         q.out_off = plan.total_bytes;
-        q.out_bytes = pack_request_bytes(q.form, q.n_samples);
+        q.out_bytes = pack_request_bytes(word, q.src_samples);
         plan.total_bytes += q.out_bytes;
         const long units = ((q.out_off & 15) + q.out_bytes + 15) / 16;
         plan.max_units = units > plan.max_units ? units : plan.max_units;

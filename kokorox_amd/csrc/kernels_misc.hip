@@ -9,6 +9,7 @@
 #include <atomic>
 
 #include "kx_common.h"
+#include "resample_taps.h"
 
 namespace kx {
 
@@ -495,11 +496,17 @@ void launch_pack_audio(const float* audio, long audio_ld, const int* frames, int
 // request's sample stream that its 256 units need into LDS, lanes along time, looking up the row of every sample in the
 // batch's prefix table: the conversion then never sees a row boundary, and nothing at or past 600 * frames[b] of a row is
 // ever read.  (44 + 1200 k) mod 3 = 2: every chunk boundary of form 4 falls inside a base64 group.
+//
+// A request with a rate code (PackReq::pad_) was resampled as a whole by resample_requests_kernel below: its stream is then
+// ONE run of n_samples floats at y + y_off, which the staging step copies instead of looking rows up; the forms apply to it
+// exactly as to the model's samples, and the WAV headers carry the chosen rate.  Forms 8 / 9 are G.711 of form 4's 16-bit
+// sample, one byte each.
 constexpr int PACK_THREADS = 256;
-constexpr int PACK_LDS = 2048 + 8;  // samples a workgroup's 4096 output bytes can need: 2048 (PCM16), 1536 + 2 (base64)
+constexpr int PACK_LDS = 4096 + 8;  // samples a workgroup's 4096 output bytes can need: 4096 (G.711), 2048 (PCM16), 1536 + 2 (base64)
 
-__device__ __forceinline__ uint32_t wav_header_dword(int form, long S, int j) {
+__device__ __forceinline__ uint32_t wav_header_dword(int form, long S, int j, int rate_code) {
     const bool f32 = form == 3;
+    const uint32_t hz = rate_code == 0 ? 24000u : (rate_code == 1 ? 8000u : (rate_code == 2 ? 16000u : 48000u));
     switch (j) {
         case 0: return 0x46464952u;                                   // "RIFF"
         case 1: return f32 ? 0xFFFFFFFFu : (uint32_t)(36 + 2 * S);   // file size - 8 (placeholder in the float form)
@@ -507,8 +514,8 @@ __device__ __forceinline__ uint32_t wav_header_dword(int form, long S, int j) {
         case 3: return 0x20746d66u;                                   // "fmt "
         case 4: return 16u;
         case 5: return (f32 ? 3u : 1u) | (1u << 16);                  // format tag (3 = IEEE float, 1 = PCM), 1 channel
-        case 6: return 24000u;
-        case 7: return f32 ? 96000u : 48000u;                         // bytes per second
+        case 6: return hz;
+        case 7: return f32 ? 4u * hz : 2u * hz;                       // bytes per second
         case 8: return f32 ? (4u | (32u << 16)) : (2u | (16u << 16));  // block align, bits per sample
         case 9: return 0x61746164u;                                   // "data"
         default: return f32 ? 0xFFFFFFFFu : (uint32_t)(2 * S);
@@ -518,9 +525,29 @@ __device__ __forceinline__ uint32_t base64_char(uint32_t v) {
     return v < 26u ? 65u + v : (v < 52u ? 71u + v : (v < 62u ? v - 4u : (v == 62u ? 43u : 47u)));
 }
 
+// G.711 of a 16-bit sample, the 16-bit-input algorithms of CPython's audioop.lin2ulaw / lin2alaw (include/kokorox_hip.h)
+__device__ __forceinline__ uint32_t g711_mulaw(int v) {
+    int p = v >> 2;
+    const uint32_t mask = p < 0 ? 0x7Fu : 0xFFu;
+    p = p < 0 ? -p : p;
+    p = (p > 8159 ? 8159 : p) + 33;
+    int seg = 0;
+    while (seg < 8 && p > (0x40 << seg) - 1) ++seg;  // first segment end 0x3F, 0x7F .. 0x1FFF that holds p
+    if (seg == 8) return 0x7Fu ^ mask;
+    return (uint32_t)((seg << 4) | ((p >> (seg + 1)) & 15)) ^ mask;
+}
+__device__ __forceinline__ uint32_t g711_alaw(int v) {
+    const uint32_t mask = v >= 0 ? 0xD5u : 0x55u;
+    const int p = (v >= 0 ? v : -v - 1) >> 3;
+    int seg = 0;
+    while (seg < 7 && p > (0x20 << seg) - 1) ++seg;  // (p <= 0xFFF: segment 7 holds whatever is left)
+    return (uint32_t)((seg << 4) | ((p >> (seg < 2 ? 1 : seg)) & 15)) ^ mask;
+}
+
 __global__ __launch_bounds__(PACK_THREADS) void pack_requests_kernel(const float* __restrict__ audio, long audio_ld,
                                                                      const PackReq* __restrict__ reqs,
-                                                                     const long* __restrict__ cum, char* __restrict__ out) {
+                                                                     const long* __restrict__ cum,
+                                                                     const float* __restrict__ y, char* __restrict__ out) {
     __shared__ float smp[PACK_LDS];
     const PackReq rq = reqs[blockIdx.y];
     const long mis = rq.out_off & 15;  // the region starts `mis` bytes into its first 16-byte unit
@@ -539,12 +566,17 @@ __global__ __launch_bounds__(PACK_THREADS) void pack_requests_kernel(const float
         s_lo = p_lo >> 1, s_hi = p_hi >> 1;
     } else if (rq.form == 3) {
         s_lo = (p_lo < 44 ? 0 : p_lo - 44) >> 2, s_hi = (p_hi < 44 ? 0 : p_hi - 44) >> 2;
-    } else {
+    } else if (rq.form == 4) {
         const long k_lo = (p_lo >> 2) * 3, k_hi = (p_hi >> 2) * 3;  // stream bytes of its groups
         s_lo = (k_lo < 44 ? 0 : k_lo - 44) >> 1, s_hi = (k_hi < 44 ? 0 : k_hi - 43) >> 1;
+    } else {
+        s_lo = p_lo, s_hi = p_hi;
     }
     s_hi = s_hi > S ? S : s_hi;
-    {
+    if (rq.pad_) {  // (uniform) a resampled request: one contiguous run
+        const float* __restrict__ src = y + rq.y_off;
+        for (long i = s_lo + threadIdx.x; i < s_hi; i += PACK_THREADS) smp[i - s_lo] = src[i];
+    } else {
         const long g0 = cum[rq.first_row];
         const int row_end = rq.first_row + rq.n_rows;
         long i = s_lo + threadIdx.x;
@@ -578,7 +610,13 @@ __global__ __launch_bounds__(PACK_THREADS) void pack_requests_kernel(const float
             } else if (rq.form == 2) {
                 v = ((uint32_t)pcm16_sample(sample(p >> 1), false) & 0xFFFFu) | ((uint32_t)pcm16_sample(sample((p >> 1) + 1), false) << 16);
             } else if (rq.form == 3) {
-                v = p < 44 ? wav_header_dword(3, S, (int)(p >> 2)) : __float_as_uint(sample((p - 44) >> 2));
+                v = p < 44 ? wav_header_dword(3, S, (int)(p >> 2), rq.pad_) : __float_as_uint(sample((p - 44) >> 2));
+            } else if (rq.form >= 8) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {  // (a region of G.711 bytes is a multiple of 4 long: p + 3 is inside it)
+                    const int pcm = pcm16_sample(sample(p + t), true);
+                    v |= (rq.form == 8 ? g711_mulaw(pcm) : g711_alaw(pcm)) << (8 * t);
+                }
             } else {
                 const long k = (p >> 2) * 3, L = 44 + 2 * S;  // group p / 4 = stream bytes k .. k + 2 of L
                 uint32_t b[3];
@@ -588,7 +626,7 @@ __global__ __launch_bounds__(PACK_THREADS) void pack_requests_kernel(const float
                     if (kk >= L) {
                         b[t] = 0;
                     } else if (kk < 44) {
-                        b[t] = (wav_header_dword(4, S, (int)(kk >> 2)) >> (8 * (int)(kk & 3))) & 255u;
+                        b[t] = (wav_header_dword(4, S, (int)(kk >> 2), rq.pad_) >> (8 * (int)(kk & 3))) & 255u;
                     } else {
                         const long d = kk - 44;
                         b[t] = ((uint32_t)pcm16_sample(sample(d >> 1), true) >> (8 * (int)(d & 1))) & 255u;
@@ -615,12 +653,91 @@ __global__ __launch_bounds__(PACK_THREADS) void pack_requests_kernel(const float
     }
 }
 
-void launch_pack_requests(const float* audio, long audio_ld, const PackReq* d_req, const long* d_cum, int R, long max_units,
-                          void* out, hipStream_t s) {
-    if (max_units <= 0) return;
+// ---- output sample rates: a request's whole stream through a polyphase FIR, before the packer -----------------------------
+// For rate code c the ratio is L / M ((1, 3), (2, 3), (2, 1)), C = 24 max(L, M), N = 2 C + 1 taps h (resample_taps.h), and
+//     y[n] = f32( sum over j ascending, 0 <= j < S, 0 <= n M - j L + C < N, of f64(h[n M - j L + C]) * f64(x[j]) )
+// with a float64 accumulator from +0, one addition per term and one round-to-nearest-even conversion at the end: a product
+// of two float32 values is exact in float64, so a fused multiply-add and a multiply and an add give the same bits, and a
+// host loop in the same order reproduces y bit for bit (kokorox_amd/voices.py: resample_stream).  x is the request's stream
+// as the packer defines it: a chunk boundary is invisible, and nothing at or past 600 * frames[b] of a row is read.
+//
+// A workgroup owns RS_WINDOW consecutive outputs of one request, lane t the outputs n0 + t + 256 k.  It stages the inputs
+// those outputs touch into LDS with the packer's row lookup, and the taps as float64; every lane then runs its chains out
+// of LDS.  Neighbouring lanes read inputs 3 (8 kHz), 1 or 2 (16 kHz) and 0 or 1 (48 kHz) dwords apart: conflict-free, at
+// most two-way, and pairwise broadcast; the taps are one address per phase.
+constexpr int RS_THREADS = 256;
+constexpr int RS_WINDOW = 1024;
+constexpr int RS_MAX_TAPS = KX_RESAMPLE_NTAPS_8000;
+// inputs of a window: floor(((n0 + 1023) M + C) / L) - ceil((n0 M - C) / L) + 1 <= (1023 M + 2 C) / L + 1 = 3214 at 8 kHz
+constexpr int RS_LDS = 3 * (RS_WINDOW - 1) + (RS_MAX_TAPS - 1) + 1 + 2;
+static_assert(KX_RESAMPLE_NTAPS_16000 <= RS_MAX_TAPS && KX_RESAMPLE_NTAPS_48000 <= RS_MAX_TAPS, "the 8 kHz table is the longest");
+__device__ const uint32_t resample_tap_bits[3][RS_MAX_TAPS] = {{KX_RESAMPLE_TAPS_8000}, {KX_RESAMPLE_TAPS_16000}, {KX_RESAMPLE_TAPS_48000}};
+
+__global__ __launch_bounds__(RS_THREADS) void resample_requests_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                        const PackReq* __restrict__ reqs,
+                                                                        const long* __restrict__ cum, float* __restrict__ y) {
+    __shared__ float xs[RS_LDS];
+    __shared__ double hs[RS_MAX_TAPS];
+    const PackReq rq = reqs[blockIdx.y];
+    if (rq.pad_ == 0) return;  // (uniform) a request at 24 kHz: the packer reads the model's slab
+    const long n0 = (long)blockIdx.x * RS_WINDOW;
+    if (n0 >= rq.n_samples) return;  // (uniform: the grid covers the longest resampled request)
+    const long n1 = n0 + RS_WINDOW < rq.n_samples ? n0 + RS_WINDOW : rq.n_samples;
+    const int L = rq.pad_ == 1 ? 1 : 2, M = rq.pad_ == 3 ? 1 : 3, C = rq.pad_ == 3 ? 48 : 72, N = 2 * C + 1;
+    const long S = rq.src_samples;
+    // inputs some output of [n0, n1) touches: ceil((n0 M - C) / L) .. floor(((n1 - 1) M + C) / L), inside the stream
+    const long a_lo = n0 * M - C;
+    const long j_lo = a_lo <= 0 ? 0 : (a_lo + L - 1) / L;
+    long j_hi = ((n1 - 1) * M + C) / L + 1;
+    j_hi = j_hi > S ? S : j_hi;
+    for (int t = threadIdx.x; t < N; t += RS_THREADS) hs[t] = (double)__uint_as_float(resample_tap_bits[rq.pad_ - 1][t]);
+    {
+        const long g0 = cum[rq.first_row];
+        const int row_end = rq.first_row + rq.n_rows;
+        long i = j_lo + threadIdx.x;
+        if (i < j_hi) {
+            int lo = rq.first_row, hi = row_end - 1;  // the row of the lane's first sample: cum[row] <= g0 + i < cum[row + 1]
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (cum[mid] <= g0 + i) lo = mid; else hi = mid - 1;
+            }
+            int row = lo;
+            for (; i < j_hi; i += RS_THREADS) {
+                while (row + 1 < row_end && cum[row + 1] <= g0 + i) ++row;
+                xs[i - j_lo] = audio[(long)row * audio_ld + (g0 + i - cum[row])];
+            }
+        }
+    }
+    __syncthreads();
+    float* __restrict__ dst = y + rq.y_off;
+    for (long n = n0 + threadIdx.x; n < n1; n += RS_THREADS) {
+        const long a = n * M - C;
+        const long jl = a <= 0 ? 0 : (a + L - 1) / L;  // >= j_lo, as n >= n0
+        long jh = (n * M + C) / L;                      // < j_hi, as n < n1
+        jh = jh > S - 1 ? S - 1 : jh;
+        int idx = (int)(n * M - jl * L) + C;            // <= 2 C, as jl L >= n M - C; stays >= 0 down to j = jh
+        const float* xp = xs + (jl - j_lo);
+        double acc = 0.0;
+        for (long j = jl; j <= jh; ++j, idx -= L) acc += hs[idx] * (double)*xp++;
+        dst[n] = (float)acc;
+    }
+}
+
+// The one way a plan's kernels are launched, for the model and for the test hook: the resampler when some request carries a
+// rate code, then the packer.  d_req [R], d_cum [B + 1]: device copies of the plan; d_y: plan.y_floats floats (may be null
+// when that is 0); out: 16-byte aligned, plan.total_bytes long.
+void launch_pack_plan(const float* audio, long audio_ld, const PackReq* d_req, const long* d_cum, int R, const PackPlan& plan,
+                      float* d_y, void* out, hipStream_t s) {
+    if (plan.max_units <= 0) return;
     KX_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0 && R <= 65535, "pack: unaligned output or too many requests");
-    hipLaunchKernelGGL(pack_requests_kernel, dim3((unsigned)((max_units + PACK_THREADS - 1) / PACK_THREADS), (unsigned)R),
-                       dim3(PACK_THREADS), 0, s, audio, audio_ld, d_req, d_cum, static_cast<char*>(out));
+    if (plan.y_floats > 0) {
+        KX_REQUIRE(d_y != nullptr, "pack: no buffer for the resampled streams");
+        hipLaunchKernelGGL(resample_requests_kernel, dim3((unsigned)((plan.max_resampled + RS_WINDOW - 1) / RS_WINDOW), (unsigned)R),
+                           dim3(RS_THREADS), 0, s, audio, audio_ld, d_req, d_cum, d_y);
+        KX_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(pack_requests_kernel, dim3((unsigned)((plan.max_units + PACK_THREADS - 1) / PACK_THREADS), (unsigned)R),
+                       dim3(PACK_THREADS), 0, s, audio, audio_ld, d_req, d_cum, d_y, static_cast<char*>(out));
     KX_HIP(hipGetLastError());
 }
 

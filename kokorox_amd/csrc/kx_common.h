@@ -289,9 +289,10 @@ void launch_pack_audio(const float* audio, long audio_ld, const int* frames, int
                        long out_stride_bytes, const long* out_off, hipStream_t s, const int* formats = nullptr);
 
 // ---- requests of several chunks (host_request.h: PackReq, PackPlan, build_pack_plan): pack_requests_kernel ----------
-// d_req [R], d_cum [B + 1]: device copies of the plan; out: 16-byte aligned, plan.total_bytes long
-void launch_pack_requests(const float* audio, long audio_ld, const PackReq* d_req, const long* d_cum, int R, long max_units,
-                          void* out, hipStream_t s);
+// and, for requests with a rate code, resample_requests_kernel before it.  d_req [R], d_cum [B + 1]: device copies of the plan;
+// d_y: plan.y_floats floats for the resampled streams (null when 0); out: 16-byte aligned, plan.total_bytes long
+void launch_pack_plan(const float* audio, long audio_ld, const PackReq* d_req, const long* d_cum, int R, const PackPlan& plan,
+                      float* d_y, void* out, hipStream_t s);
 // Host output buffers of the kx_infer* calls: page-locked and pooled (one asynchronous D2H copy at PCIe rate instead
 // of per-utterance pageable copies); host_out_free also accepts plain malloc'd pointers (dispatcher results).
 void* host_out_alloc(size_t bytes);

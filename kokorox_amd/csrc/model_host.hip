@@ -141,6 +141,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     uint32_t* d_uidx;
     PackReq* d_req = nullptr;
     long* d_cum = nullptr;
+    float* d_y = nullptr;  // the resampled streams of the requests with a rate code, back to back
     int *d_vid, *d_rows, *d_kinds, *d_formats = nullptr;
     float* d_w;
     void* d_packed;
@@ -159,6 +160,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         if (grouped) {
             d_req = static_cast<PackReq*>(A.alloc((size_t)R * sizeof(PackReq)));
             d_cum = static_cast<long*>(A.alloc(((size_t)B + 1) * 8));
+            d_y = A.f(resample_floats_bound(hc.req_formats, hc.n_req_formats, audio_floats));
         } else {
             d_formats = A.i(B);
             d_off = static_cast<long*>(A.alloc((size_t)B * 8));
@@ -209,6 +211,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         int64_t total = 0;
         if (grouped) {
             // the request table and the rows' sample prefixes, then ONE launch for every request of the batch, whatever its form
+            // (and one before it, the resampler, when a request asks for another rate)
             PackPlan& plan = pack_plan_;
             build_pack_plan(call_.hF.data(), B, hc.chunks_per_request, R, hc.req_formats, hc.n_req_formats, plan);
             for (int r = 0; r < R; ++r) {
@@ -218,7 +221,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             total = plan.total_bytes;
             KX_HIP(hipMemcpyAsync(d_req, plan.req.data(), (size_t)R * sizeof(PackReq), hipMemcpyHostToDevice, stream_));
             KX_HIP(hipMemcpyAsync(d_cum, plan.cum.data(), ((size_t)B + 1) * 8, hipMemcpyHostToDevice, stream_));
-            launch_pack_requests(d_audio, ld, d_req, d_cum, R, plan.max_units, d_packed, stream_);
+            launch_pack_plan(d_audio, ld, d_req, d_cum, R, plan, d_y, d_packed, stream_);
         } else {
             UttLayout& lay = utt_layout_;
             utt_layout(call_.hF.data(), B, hc.format, hc.formats, lay);

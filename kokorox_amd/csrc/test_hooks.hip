@@ -603,12 +603,19 @@ int kx_test_pack_requests(int device_id, const float* audio, int B, int64_t audi
         // a sentinel after the last region: the kernel must not write past what the plan says
         char* d_out = dm.get<char>((size_t)plan.total_bytes + 64);
         KX_HIP(hipMemset(d_out, 0xA5, (size_t)plan.total_bytes + 64));
-        kx::launch_pack_requests(d_audio, (long)audio_ld, d_req, d_cum, R, plan.max_units, d_out, nullptr);
+        // (the same sentinel after the resampled streams)
+        float* d_y = plan.y_floats > 0 ? dm.get<float>((size_t)plan.y_floats + 16) : nullptr;
+        if (d_y) KX_HIP(hipMemset(d_y + plan.y_floats, 0xA5, 64));
+        kx::launch_pack_plan(d_audio, (long)audio_ld, d_req, d_cum, R, plan, d_y, d_out, nullptr);
         KX_HIP(hipDeviceSynchronize());
         std::vector<unsigned char> tail(64);
         KX_HIP(hipMemcpy(out, d_out, (size_t)plan.total_bytes, hipMemcpyDeviceToHost));
         KX_HIP(hipMemcpy(tail.data(), d_out + plan.total_bytes, 64, hipMemcpyDeviceToHost));
         for (unsigned char c : tail) KX_REQUIRE(c == 0xA5, "test_pack_requests: the kernel wrote past the last region");
+        if (d_y) {
+            KX_HIP(hipMemcpy(tail.data(), d_y + plan.y_floats, 64, hipMemcpyDeviceToHost));
+            for (unsigned char c : tail) KX_REQUIRE(c == 0xA5, "test_pack_requests: the resampler wrote past the last stream");
+        }
     });
 }
 

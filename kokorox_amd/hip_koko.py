@@ -22,6 +22,11 @@ LIB_PATH = os.path.join(_HERE, "lib", "libkokorox_hip.so")
 
 PACK_F32_MONO, PACK_F32_STEREO, PACK_PCM16_MONO = 0, 1, 2
 PACK_WAV_F32, PACK_WAV16_BASE64 = 3, 4  # the servers' bodies (infer_requests / submit_request only): float WAV, base64 of a 16-bit WAV
+PACK_MULAW, PACK_ALAW = 8, 9  # raw G.711, one byte per sample (infer_requests / submit_request only)
+# the output sample rate, or'ed into the form of infer_requests / submit_request (the format word of include/kokorox_hip.h)
+PACK_RATE_24000, PACK_RATE_8000, PACK_RATE_16000, PACK_RATE_48000 = 0x000, 0x100, 0x200, 0x300
+RATE_HZ = {0: 24000, 1: 8000, 2: 16000, 3: 48000}  # by rate code (bits 8..11 of the word)
+RESAMPLE_MAX_TAPS = 145
 KX_OK, KX_ERR_INVALID, KX_ERR_IO, KX_ERR_DEVICE, KX_ERR_STATE = 0, 1, 2, 3, 4  # include/kokorox_hip.h
 KX_FLAG_NOISE_OFF = 1
 KX_FLAG_TAPS = 2
@@ -72,6 +77,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "kx_init": (i32, [i32, cp, sz]),
         "kx_create": (vp, [cp, i32, cp, sz]),
         "kx_import_onnx": (i32, [cp, cp, cp, sz]),
+        "kx_resample_filter": (i32, [i32, vp, vp, vp, vp, i32]),
         "kx_warmup": (i32, [vp, i32, i32, i32]),
         "kx_arena_bytes": (i32, [vp, C.POINTER(i64)]),
         "kx_call_times": (i32, [vp, C.POINTER(C.c_double)]),
@@ -181,7 +187,7 @@ TEST_ABI_SYMBOLS = ["kx_test_conv1d", "kx_test_lstm", "kx_test_source", "kx_test
                     "kx_test_layernorm", "kx_test_instance_norm", "kx_test_pack_requests"]
 
 ABI_SYMBOLS = [
-    "kx_version", "kx_init", "kx_create", "kx_import_onnx", "kx_create_from_device_blob", "kx_create_replicas", "kx_replicas_times", "kx_create_partition", "kx_destroy",
+    "kx_version", "kx_init", "kx_create", "kx_import_onnx", "kx_resample_filter", "kx_create_from_device_blob", "kx_create_replicas", "kx_replicas_times", "kx_create_partition", "kx_destroy",
     "kx_last_error", "kx_last_error_copy", "kx_infer",
     "kx_free_audio", "kx_infer_device", "kx_sync", "kx_set_pinned_durations", "kx_warmup", "kx_arena_bytes", "kx_call_times", "kx_model_status", "kx_model_info", "kx_dispatcher_health", "kx_set_utterance_base", "kx_set_lanes",
     "kx_set_conv_mode", "kx_get_conv_mode", "kx_set_stft_variant", "kx_get_stft_variant",
@@ -199,10 +205,26 @@ def _f32(a) -> Optional[np.ndarray]:
     return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
 
 
+def resample_filter(word: int):
+    """(L, M, taps) of a format word's rate code from the library's one table (kx_resample_filter; host only, no GPU): the
+    ratio of output to input rate and the float32 taps of the FIR.  Rate code 0 gives (1, 1, no taps)."""
+    lib = load_library()
+    L, M, n = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    taps = np.zeros(RESAMPLE_MAX_TAPS, dtype=np.float32)
+    rc = lib.kx_resample_filter(int(word), C.byref(L), C.byref(M), C.byref(n), _ptr(taps), taps.shape[0])
+    if rc != KX_OK:
+        raise KokoroxHipError(rc, "unknown output format or sample rate")
+    return L.value, M.value, taps[: n.value].copy()
+
+
 def _decode_packed(raw: bytes, fmt: int):
-    """A request's region as Python hands it out: samples as an array for forms 0..2, the body as bytes for forms 3 and 4."""
+    """A request's region as Python hands it out: samples as an array for forms 0..2 and 8 / 9 (uint8), the body as bytes for
+    forms 3 and 4; at the output rate of the word."""
+    fmt = int(fmt) & 0xFF
     if fmt in (PACK_WAV_F32, PACK_WAV16_BASE64):
         return raw
+    if fmt in (PACK_MULAW, PACK_ALAW):
+        return np.frombuffer(raw, dtype=np.uint8).copy()
     if fmt == PACK_PCM16_MONO:
         return np.frombuffer(raw, dtype=np.int16).copy()
     a = np.frombuffer(raw, dtype=np.float32).copy()
@@ -374,12 +396,14 @@ class HipKoko:
         return self._unpack(out, nbytes, nsamp, B, fmt)
 
     def infer_requests(self, tokens, chunks_per_request, styles=None, voice_ids=None, weights=None, speeds=(1.0,), seed: int = 0,
-                       flags: int = 0, fmt=0):
+                       flags: int = 0, fmt=0, with_samples: bool = False):
         """Several requests of several chunks in one forward (kx_infer_requests): `tokens` are the B chunks (each 0-wrapped),
         request r owns chunks_per_request[r] consecutive ones.  The voice is per chunk: `styles` [B, 256], or `voice_ids` /
-        `weights` [B, max_mix] as infer_voices.  `fmt` = one PACK_* form for all, or one per request.  Returns one entry per
-        request: its chunks' samples back to back as an array for forms 0..2 (float32, [n, 2] float32, int16), the body as
-        `bytes` for PACK_WAV_F32 and PACK_WAV16_BASE64."""
+        `weights` [B, max_mix] as infer_voices.  `fmt` = one format word (a PACK_* form, optionally | PACK_RATE_*) for all, or one
+        per request.  Returns one entry per request: its chunks' samples back to back, at the word's rate, as an array for forms
+        0..2 (float32, [n, 2] float32, int16) and the G.711 forms (uint8), the body as `bytes` for PACK_WAV_F32 and
+        PACK_WAV16_BASE64.  with_samples: also the library's own sample count of every request (out_samples, at the output
+        rate), as a second list."""
         ids, lens = self._ids_lens(tokens)
         B = len(tokens)
         cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32).reshape(-1)
@@ -407,7 +431,7 @@ class HipKoko:
             part = raw[o: o + int(nbytes[r])]
             o += int(nbytes[r])
             res.append(_decode_packed(part, int(fm[r if fm.shape[0] > 1 else 0])))
-        return res
+        return (res, [int(v) for v in nsamp[:R]]) if with_samples else res
 
     def infer_device(self, d_ids: int, t_stride: int, lens_host: np.ndarray, d_styles: int, speeds_host: np.ndarray,
                      d_audio: int, audio_ld: int, d_frames: int, seed: int = 0, flags: int = 0) -> int:
@@ -623,8 +647,9 @@ class Dispatcher:
     def submit_request(self, chunks: Sequence[Sequence[int]], styles=None, voices=None, speed: float = 1.0, seed: int = 0,
                        fmt: int = 0):
         """A request of 1 .. max_batch chunks (kx_dispatcher_submit_request): `chunks` = the 0-wrapped id lists; `styles` = one
-        256-float row per chunk, OR `voices` as in submit_ex (one voice spec for the request); `fmt` = a PACK_* form 0..4.
-        Returns what HipKoko.infer_requests returns for one request: an array (forms 0..2) or the body as bytes (3, 4)."""
+        256-float row per chunk, OR `voices` as in submit_ex (one voice spec for the request); `fmt` = a format word (a PACK_*
+        form, optionally | PACK_RATE_*).  Returns what HipKoko.infer_requests returns for one request: an array (forms 0..2, 8, 9)
+        or the body as bytes (3, 4)."""
         lens = np.array([len(c) for c in chunks], dtype=np.int32)
         a = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.int64).reshape(-1) for c in chunks])
                                  if len(chunks) else np.zeros(0, np.int64))
@@ -905,7 +930,8 @@ def harmonic_source(f0, lin_w, lin_b, seed=0, utt_base=0, noise_off=False, devic
 
 def pack_requests(audio, frames, chunks_per_request, formats, device=0):
     """The request packer alone (kx_test_pack_requests): audio [B, audio_ld] with row b valid for 600 * frames[b] samples,
-    request r = chunks_per_request[r] consecutive rows in form formats[r].  Returns the R regions as bytes."""
+    request r = chunks_per_request[r] consecutive rows in the format word formats[r] (the resampler runs first where a word
+    has a rate code).  Returns the R regions as bytes."""
     lib = load_test_library()
     audio = _f32(audio)
     B, ld = audio.shape
@@ -914,7 +940,7 @@ def pack_requests(audio, frames, chunks_per_request, formats, device=0):
     fm = np.ascontiguousarray(formats, dtype=np.int32)
     R = cpr.shape[0]
     assert fr.shape == (B,) and fm.shape == (R,)
-    cap = 8 * 600 * int(fr.sum()) + 64 * R
+    cap = 16 * 600 * int(fr.sum()) + 64 * R  # (stereo f32 at 48 kHz: 16 bytes per sample of the model)
     out = np.zeros(cap, dtype=np.uint8)
     nb = np.zeros(R, dtype=np.int64)
     _err_call(lib.kx_test_pack_requests, device, _ptr(audio), B, ld, _ptr(fr), _ptr(cpr), R, _ptr(fm), _ptr(out), cap, _ptr(nb))

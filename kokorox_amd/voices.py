@@ -9,6 +9,8 @@ Reference (paths under /root/reference/kokorox/src/tts/):
   * chunk loop              koko.rs:947-1191   — one forward per <= 500-token chunk, waveforms appended
   * float WAV body          utils/wav.rs:18-50, kokorox-openai/src/lib.rs:416-425  — `wav_f32_body`
   * base64 16-bit WAV       kokorox-websocket/src/lib.rs:696-736 (`encode_audio`)   — `wav16_base64`
+Beyond the reference: `resample_stream`, `mulaw_bytes`, `alaw_bytes` mirror the output rates and the G.711 forms of the
+request packer (include/kokorox_hip.h, KX_PACK_RATE_*, KX_PACK_MULAW / KX_PACK_ALAW).
 These stay on the host (north_star: "the voice-style mixer ... stay identical"); the GPU
 only ever sees ids and one 256-float row per utterance.
 """
@@ -110,12 +112,12 @@ def tts_chunks(model, styles: Dict[str, np.ndarray], style_name: str, chunk_toke
 SAMPLE_RATE = 24000
 
 
-def wav_f32_body(samples) -> bytes:
+def wav_f32_body(samples, rate: int = SAMPLE_RATE) -> bytes:
     """The HTTP body of kokorox-openai/src/lib.rs:416-425: the 44 bytes of `WavHeader::new(1, 24000, 32).write_header`
     (utils/wav.rs:18-50: IEEE float, both size fields the reference's 0xFFFFFFFF placeholders), then `to_le_bytes` of
-    every sample: bit copies, a NaN keeps its payload."""
+    every sample: bit copies, a NaN keeps its payload.  `rate`: the header's sample rate (the samples are taken as given)."""
     s = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
-    hdr = struct.pack("<4sI4s4sIHHIIHH4sI", b"RIFF", 0xFFFFFFFF, b"WAVE", b"fmt ", 16, 3, 1, SAMPLE_RATE, SAMPLE_RATE * 4, 4, 32,
+    hdr = struct.pack("<4sI4s4sIHHIIHH4sI", b"RIFF", 0xFFFFFFFF, b"WAVE", b"fmt ", 16, 3, 1, rate, rate * 4, 4, 32,
                       b"data", 0xFFFFFFFF)
     return hdr + s.astype("<f4", copy=False).tobytes()
 
@@ -129,23 +131,80 @@ def pcm16(samples) -> np.ndarray:
     return np.trunc(c * np.float32(32767.0)).astype(np.int16)
 
 
-def wav16_base64(samples) -> bytes:
+def wav16_base64(samples, rate: int = SAMPLE_RATE) -> bytes:
     """The WebSocket chunk of `encode_audio` (kokorox-websocket/src/lib.rs:696-736): standard base64 (`=` padding, no line
-    breaks) of a 16-bit mono WAV file at 24 kHz, header with its true sizes, samples through `pcm16`."""
+    breaks) of a 16-bit mono WAV file at 24 kHz (or `rate`: the header's, the samples are taken as given), header with its
+    true sizes, samples through `pcm16`."""
     pcm = pcm16(samples)
     n = 2 * pcm.shape[0]
     if 36 + n > 0xFFFFFFFF:
         raise ValueError("wav16_base64: a 16-bit WAV file cannot hold that many samples")
-    hdr = struct.pack("<4sI4s4sIHHIIHH4sI", b"RIFF", 36 + n, b"WAVE", b"fmt ", 16, 1, 1, SAMPLE_RATE, SAMPLE_RATE * 2, 2, 16,
+    hdr = struct.pack("<4sI4s4sIHHIIHH4sI", b"RIFF", 36 + n, b"WAVE", b"fmt ", 16, 1, 1, rate, rate * 2, 2, 16,
                       b"data", n)
     return base64.b64encode(hdr + pcm.astype("<i2", copy=False).tobytes())
+
+
+def resample_stream(x, word: int) -> np.ndarray:
+    """A request's stream at the output rate of a format word, as resample_requests_kernel computes it (include/kokorox_hip.h):
+    with (L, M) and the float32 taps h of the word's rate code from the library's table (N = 2 C + 1 of them),
+        y[n] = f32(sum over j ascending, 0 <= j < S, 0 <= n M - j L + C < N, of f64(h[n M - j L + C]) * f64(x[j])),
+    a float64 accumulator from +0, one addition per term, one rounding at the end.  The products are exact in float64, so
+    this loop -- the k-th term of every output at once -- gives the GPU's bits.  Rate code 0 returns the stream as it is."""
+    from . import hip_koko as hk
+    x32 = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    L, M, h32 = hk.resample_filter(word)
+    if h32.shape[0] == 0:
+        return x32
+    S, N = x32.shape[0], h32.shape[0]
+    C = (N - 1) // 2
+    if (S * L) % M:
+        raise ValueError("resample_stream: the stream's length must give a whole number of output samples")
+    h, xd = h32.astype(np.float64), x32.astype(np.float64)
+    n = np.arange(S * L // M, dtype=np.int64)
+    a = n * M - C
+    jl = np.where(a <= 0, 0, (a + L - 1) // L)      # first j with n M - j L + C <= N - 1, inside the stream
+    jh = np.minimum((n * M + C) // L, S - 1)        # last j with n M - j L + C >= 0, inside the stream
+    acc = np.zeros(n.shape[0], dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(int((jh - jl).max()) + 1 if n.shape[0] else 0):
+            j = jl + k
+            live = j <= jh
+            jj = np.where(live, j, 0)
+            acc = np.where(live, acc + h[np.where(live, n * M - jj * L + C, 0)] * xd[jj], acc)
+        return acc.astype(np.float32)
+
+
+def mulaw_bytes(pcm) -> np.ndarray:
+    """G.711 mu-law of 16-bit samples: the 16-bit-input algorithm of CPython's `audioop.lin2ulaw(_, 2)` (form 8)."""
+    v = np.asarray(pcm).astype(np.int32).reshape(-1)
+    p = v >> 2
+    mask = np.where(p < 0, 0x7F, 0xFF)
+    p = np.minimum(np.abs(p), 8159) + 33
+    seg = np.zeros_like(p)
+    for k in range(8):  # the first segment end 0x3F, 0x7F .. 0x1FFF that holds p; 8 = none
+        seg += p > (0x40 << k) - 1
+    byte = np.where(seg >= 8, 0x7F, (seg << 4) | ((p >> (seg + 1)) & 15)) ^ mask
+    return byte.astype(np.uint8)
+
+
+def alaw_bytes(pcm) -> np.ndarray:
+    """G.711 A-law of 16-bit samples: the 16-bit-input algorithm of CPython's `audioop.lin2alaw(_, 2)` (form 9)."""
+    v = np.asarray(pcm).astype(np.int32).reshape(-1)
+    mask = np.where(v >= 0, 0xD5, 0x55)
+    p = np.where(v >= 0, v, -v - 1) >> 3
+    seg = np.zeros_like(p)
+    for k in range(7):  # the first segment end 0x1F, 0x3F .. 0xFFF that holds p (p <= 0xFFF)
+        seg += p > (0x20 << k) - 1
+    byte = ((seg << 4) | ((p >> np.where(seg < 2, 1, seg)) & 15)) ^ mask
+    return byte.astype(np.uint8)
 
 
 def tts_request(model, styles: Dict[str, np.ndarray], style_name: str, chunk_tokens: Sequence[Sequence[int]],
                 speed: float = 1.0, initial_silence: int = 0, seed: int = 0, fmt: int = 0):
     """`tts_chunks` through `model.infer_requests`: the chunks of one text as ONE request of one batched forward, its body
-    (header of the form, then the chunks' samples with nothing between them) packed on the GPU.  `fmt` is a PACK_* form of
-    hip_koko: 0..2 give the samples as an array, 3 (`wav_f32_body`) and 4 (`wav16_base64`) the bytes a server sends.  An
+    (header of the form, then the chunks' samples with nothing between them) packed on the GPU.  `fmt` is a format word of
+    hip_koko (a PACK_* form, optionally | PACK_RATE_*): 0..2 and 8 / 9 give the samples as an array, 3 (`wav_f32_body`) and 4
+    (`wav16_base64`) the bytes a server sends.  An
     empty chunk list and an empty chunk are errors (a request has at least one chunk)."""
     toks, rows = [], []
     for ch in chunk_tokens:

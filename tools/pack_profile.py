@@ -1,6 +1,8 @@
 """Three packed calls of the bench batch (64 x 130 tokens, durations pinned 3,3,3,4 -> 422 frames each) in the form given on
 the command line: 'old2' = kx_infer_packed form 2 (pack_audio_kernel), '2' / '3' / '4' = kx_infer_requests in that form, every
-row a request of its own (pack_requests_kernel).  Meant to run under the profiler, one form per run:
+row a request of its own (pack_requests_kernel); a format word with a rate code, written as the header does ('0x108' = G.711
+mu-law at 8 kHz, '0x303' = float WAV at 48 kHz), adds resample_requests_kernel in front of it.  Meant to run under the
+profiler, one word per run:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o t -- python tools/pack_profile.py 4
 profiles/pack_kernels_stats.txt holds the rows of the kernel_stats.csv files."""
 import os, sys
@@ -21,7 +23,7 @@ for it in range(3):
         out = m.infer_packed(toks, rows, fmt=2)
         n = sum(o.nbytes for o in out)
     else:
-        out = m.infer_requests(toks, [1] * B, styles=rows, fmt=int(which))
+        out = m.infer_requests(toks, [1] * B, styles=rows, fmt=int(which, 0))
         n = sum(len(o) if isinstance(o, bytes) else o.nbytes for o in out)
 print("form", which, "bytes", n, "frames", len(toks[0]))
 m.close()
