@@ -361,6 +361,32 @@ int kx_infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, const i
                       const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
                       const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples);
 
+/* ---- token marks: where each input token sits in a request's stream -------------------------------------------------------
+ * The duration head decides how many 600-sample frames every token occupies; the marks give that as sample offsets in the
+ * request's own stream, at the request's own output rate, across its chunks.
+ *   Request r has chunks c = 0 .. n-1; chunk c has T_c tokens, its two 0 pads included.  d_c[t] are the durations the forward
+ *   USED, in frames: after kx_set_pinned_durations if a pattern is set, after the division by the speed and the clamp to >= 1.
+ *   The request's format word has the rate (L, M); K = 600 L / M (600 at 24 000 Hz, 200 at 8000, 400 at 16 000, 1200 at
+ *   48 000).  F_c = sum over t of d_c[t].  The marks of request r are, chunk after chunk, T_c + 1 int64 values per chunk:
+ *       m_c[t] = K * ( sum over c' < c of F_c'  +  sum over t' < t of d_c[t'] ),   t = 0 .. T_c
+ * Token t of chunk c occupies the output samples [m_c[t], m_c[t+1]) of the request's stream.  m_0[0] = 0;
+ * m_c[T_c] = m_{c+1}[0] (the chunk boundary is stored twice on purpose: every chunk indexes on its own); the last value equals
+ * out_samples[r]; request r has sum over c of (T_c + 1) marks.
+ * Marks count SAMPLES of the stream, not bytes, and do not depend on the form: a stereo pair counts once, a WAV header and
+ * base64 are not counted.  The resampler's filter is symmetric about its tap C (kx_resample_filter), so output sample n sits
+ * at time n / rate with no delay: that is why scaling a 24 000 Hz offset by L / M is exact.
+ *
+ * kx_infer_requests with marks for every request.  *out, out_bytes, out_samples: exactly those of kx_infer_requests (same
+ * bytes, sizes, layout).  *out_marks points INTO the buffer of *out (8-byte aligned, behind the bodies) and holds the marks of
+ * the R requests back to back, out_n_marks[r] values for request r; it is never freed on its own and stays valid until *out is
+ * released with kx_free_packed.  A null out_marks or out_n_marks: KX_ERR_INVALID "infer: null marks argument"; everything
+ * kx_infer_requests refuses is refused here the same way with the same text. */
+int kx_infer_requests_marks(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                            const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                            const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                            const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                            int64_t** out_marks, int64_t* out_n_marks);
+
 /* ---- request dispatcher ----------------------------------------------------
  * Replaces the reference's one-request-at-a-time `Mutex<Session>` (kokorox/src/onn/ort_koko.rs:78; callers
  * kokorox-openai/src/lib.rs:370-439, kokorox-websocket/src/lib.rs:657-668).  Any number of threads submit
@@ -412,6 +438,17 @@ int kx_dispatcher_submit_request(kx_dispatcher* d, const int64_t* ids, const int
                                  const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
                                  float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
                                  int64_t* out_samples, char* err, size_t err_len);
+/* kx_dispatcher_submit_request with the request's token marks (see "token marks" above): *out_marks points INTO the allocation
+ * of *out, 8-byte aligned behind the body, *out_n_marks values = the sum over the chunks of chunk_tokens[c] + 1; it is never
+ * freed on its own and lives until *out is released (kx_free_packed / kx_free_audio).  Body and marks equal those of
+ * kx_infer_requests_marks (R = 1, same seed, utterance base 0) whatever the request was batched with -- requests with and
+ * without marks share batches -- on whichever model and recurrence form.  A null out_marks or out_n_marks: KX_ERR_INVALID
+ * "dispatcher_submit_request: null marks argument"; every other refusal as kx_dispatcher_submit_request. */
+int kx_dispatcher_submit_request_marks(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                       const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
+                                       float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
+                                       int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, char* err,
+                                       size_t err_len);
 /* n_requests counts requests, max_batch_seen the largest batch in ROWS (a request of n chunks is n rows). */
 int kx_dispatcher_stats(kx_dispatcher* d, int64_t* n_requests, int64_t* n_batches, int64_t* max_batch_seen);
 /* batches each model (worker) has run so far: per_model[n_models] */

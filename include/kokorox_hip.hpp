@@ -136,6 +136,50 @@ class HipKoko {
         return bodies;
     }
 
+    // infer_requests with the token marks of every request (kx_infer_requests_marks; "token marks" in kokorox_hip.h): marks[r]
+    // = per chunk of request r its tokens + 1 sample offsets in the request's stream, at the request's output rate.
+    std::vector<std::string> infer_requests_marks(const std::vector<std::vector<int64_t>>& tokens,
+                                                  const std::vector<int32_t>& chunks_per_request,
+                                                  const std::vector<std::vector<float>>& styles, float speed, uint64_t seed,
+                                                  int format, std::vector<std::vector<int64_t>>& marks) const {
+        if (tokens.empty() || styles.size() != tokens.size()) throw std::invalid_argument("infer_requests: one style row per chunk");
+        const int B = (int)tokens.size(), R = (int)chunks_per_request.size();
+        size_t stride = 1;
+        for (const auto& t : tokens) stride = t.size() > stride ? t.size() : stride;
+        std::vector<int64_t> ids((size_t)B * stride, 0);
+        std::vector<int32_t> tl(B);
+        std::vector<float> st((size_t)B * KX_STYLE_DIM);
+        for (int b = 0; b < B; ++b) {
+            tl[b] = (int32_t)tokens[b].size();
+            for (size_t i = 0; i < tokens[b].size(); ++i) ids[(size_t)b * stride + i] = tokens[b][i];
+            if (styles[b].size() != KX_STYLE_DIM) throw std::invalid_argument("infer_requests: style rows need 256 floats");
+            for (int k = 0; k < KX_STYLE_DIM; ++k) st[(size_t)b * KX_STYLE_DIM + k] = styles[b][k];
+        }
+        void* out = nullptr;
+        int64_t* mk = nullptr;
+        std::vector<int64_t> nb(R > 0 ? R : 1), ns(R > 0 ? R : 1), nm(R > 0 ? R : 1);
+        const int32_t fmt = format;
+        const int rc = kx_infer_requests_marks(h_, ids.data(), (int64_t)stride, tl.data(), B, chunks_per_request.data(), R, st.data(),
+                                               nullptr, nullptr, 0, &speed, 1, seed, 0, &fmt, 1, &out, nb.data(), ns.data(), &mk,
+                                               nm.data());
+        if (rc != KX_OK) {
+            char msg[512];
+            kx_last_error_copy(h_, msg, sizeof(msg));
+            throw std::runtime_error(std::string("kokorox_hip error: ") + msg);
+        }
+        std::vector<std::string> bodies;
+        marks.clear();
+        const char* p = static_cast<const char*>(out);
+        for (int r = 0; r < R; ++r) {  // (the marks live in the buffer of `out`: copied before it is released)
+            bodies.emplace_back(p, p + nb[r]);
+            p += nb[r];
+            marks.emplace_back(mk, mk + nm[r]);
+            mk += nm[r];
+        }
+        kx_free_packed(out);
+        return bodies;
+    }
+
   private:
     explicit HipKoko(kx_model* adopted) : h_(adopted) {}
     kx_model* h_ = nullptr;
@@ -159,6 +203,30 @@ inline std::string submit_request(kx_dispatcher* d, const std::vector<std::vecto
                                      format, &out, &nb, &ns, err, sizeof(err)) != KX_OK)
         throw std::runtime_error(std::string("kokorox_hip error: ") + err);
     std::string body(static_cast<const char*>(out), (size_t)nb);
+    kx_free_packed(out);
+    return body;
+}
+
+// ... and with the request's token marks (kx_dispatcher_submit_request_marks)
+inline std::string submit_request_marks(kx_dispatcher* d, const std::vector<std::vector<int64_t>>& chunks,
+                                        const std::vector<float>& styles, float speed, uint64_t seed, int format,
+                                        std::vector<int64_t>& marks) {
+    std::vector<int64_t> ids;
+    std::vector<int32_t> lens;
+    for (const auto& c : chunks) {
+        ids.insert(ids.end(), c.begin(), c.end());
+        lens.push_back((int32_t)c.size());
+    }
+    if (styles.size() != chunks.size() * KX_STYLE_DIM) throw std::invalid_argument("submit_request: one style row per chunk");
+    void* out = nullptr;
+    int64_t* mk = nullptr;
+    int64_t nb = 0, ns = 0, nm = 0;
+    char err[256] = {0};
+    if (kx_dispatcher_submit_request_marks(d, ids.data(), lens.data(), (int)lens.size(), styles.data(), nullptr, nullptr, 0, speed,
+                                           seed, format, &out, &nb, &ns, &mk, &nm, err, sizeof(err)) != KX_OK)
+        throw std::runtime_error(std::string("kokorox_hip error: ") + err);
+    std::string body(static_cast<const char*>(out), (size_t)nb);
+    marks.assign(mk, mk + nm);  // (inside the allocation of `out`: copied before it is released)
     kx_free_packed(out);
     return body;
 }

@@ -107,6 +107,16 @@ int kx_test_pack_requests(int device_id, const float* audio, int B, int64_t audi
                           const int32_t* chunks_per_request, int R, const int32_t* formats, void* out, int64_t out_cap,
                           int64_t* out_bytes, char* err, size_t err_len);
 
+/* The token marks alone (token_marks_kernel through build_pack_plan and build_mark_plan, the host-side table builders the model
+ * uses; no audio): dur [B][512] frames per token with row b valid for lens[b] entries (whatever lies beyond must not reach the
+ * result), request r = chunks_per_request[r] consecutive rows in the format word formats[r] ([R]; only its rate matters),
+ * want [R] = which requests get marks, NULL = all.  frames[b] is taken as the sum of the row's valid durations.  out_marks
+ * receives the wanted requests' marks back to back (out_cap values available), out_n_marks[r] their counts (0 where not
+ * wanted).  The definition of the marks: include/kokorox_hip.h, "token marks". */
+int kx_test_token_marks(int device_id, const int32_t* dur, const int32_t* lens, int B, const int32_t* chunks_per_request, int R,
+                        const int32_t* formats, const uint8_t* want, int64_t* out_marks, int64_t out_cap, int64_t* out_n_marks,
+                        char* err, size_t err_len);
+
 /* Fault injection for the two-CU LSTM recurrence (process-wide, test only): nth > 0 makes the nth following launch of
  * the pair kernel, and every later one, lose the second half of each pair and poll with a short limit, so the call it
  * belongs to must fail with KX_ERR_DEVICE (the bounded wait's error path) and the model must fall back to the one-CU

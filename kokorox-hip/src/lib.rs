@@ -111,6 +111,11 @@ extern "C" {
                          weights: *const f32, max_mix: c_int, speeds: *const f32, n_speed: c_int, seed: u64, flags: u32,
                          formats: *const i32, n_format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
                          out_samples: *mut i64) -> c_int;
+    fn kx_infer_requests_marks(m: *mut KxModel, ids: *const i64, t_stride: i64, lens: *const i32, b: c_int,
+                               chunks_per_request: *const i32, r: c_int, styles: *const f32, voice_ids: *const i32,
+                               weights: *const f32, max_mix: c_int, speeds: *const f32, n_speed: c_int, seed: u64, flags: u32,
+                               formats: *const i32, n_format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                               out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64) -> c_int;
     fn kx_dispatcher_create(models: *mut *mut KxModel, n_models: c_int, max_batch: c_int, max_wait_us: c_int,
                             err: *mut c_char, err_len: usize) -> *mut KxDispatcher;
     fn kx_dispatcher_create_warm(models: *mut *mut KxModel, n_models: c_int, max_batch: c_int, max_wait_us: c_int,
@@ -126,6 +131,11 @@ extern "C" {
                                     styles: *const f32, voice_ids: *const i32, weights: *const f32, n_mix: c_int,
                                     speed: f32, seed: u64, format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
                                     out_samples: *mut i64, err: *mut c_char, err_len: usize) -> c_int;
+    fn kx_dispatcher_submit_request_marks(d: *mut KxDispatcher, ids: *const i64, chunk_tokens: *const i32, n_chunks: c_int,
+                                          styles: *const f32, voice_ids: *const i32, weights: *const f32, n_mix: c_int,
+                                          speed: f32, seed: u64, format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                                          out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64,
+                                          err: *mut c_char, err_len: usize) -> c_int;
     fn kx_dispatcher_stats(d: *mut KxDispatcher, n_requests: *mut i64, n_batches: *mut i64,
                            max_batch_seen: *mut i64) -> c_int;
     fn kx_dispatcher_failures(d: *mut KxDispatcher, n_replayed: *mut i64, n_retried: *mut i64) -> c_int;
@@ -428,6 +438,40 @@ impl HipKoko {
         Ok(bodies)
     }
 
+    /// `infer_requests` with the token marks of every request ("token marks" in kokorox_hip.h): per request its body and, per
+    /// chunk, tokens + 1 sample offsets in the request's stream at the request's output rate, the chunks back to back.
+    pub fn infer_requests_marks(&self, tokens: &[Vec<i64>], chunks_per_request: &[i32], styles: &[Vec<f32>], speeds: &[f32],
+                                seed: u64, formats: &[c_int]) -> Result<Vec<(Vec<u8>, Vec<i64>)>, Box<dyn Error>> {
+        if tokens.is_empty() || styles.len() != tokens.len() || styles.iter().any(|s| s.len() != KX_STYLE_DIM) {
+            return Err("infer_requests: one style row of 256 floats per chunk is required".into());
+        }
+        let (b, r) = (tokens.len(), chunks_per_request.len());
+        let (ids, lens, stride) = Self::flatten(tokens);
+        let st: Vec<f32> = styles.iter().flatten().copied().collect();
+        let mut out: *mut c_void = ptr::null_mut();
+        let mut mk: *mut i64 = ptr::null_mut();
+        let (mut nbytes, mut nsamp, mut nmarks) = (vec![0i64; r.max(1)], vec![0i64; r.max(1)], vec![0i64; r.max(1)]);
+        let rc = unsafe {
+            kx_infer_requests_marks(self.h, ids.as_ptr(), stride as i64, lens.as_ptr(), b as c_int, chunks_per_request.as_ptr(),
+                                    r as c_int, st.as_ptr(), ptr::null(), ptr::null(), 0, speeds.as_ptr(), speeds.len() as c_int,
+                                    seed, 0, formats.as_ptr(), formats.len() as c_int, &mut out, nbytes.as_mut_ptr(),
+                                    nsamp.as_mut_ptr(), &mut mk, nmarks.as_mut_ptr())
+        };
+        self.check(rc)?;
+        let mut res = Vec::with_capacity(r);
+        let (mut at, mut mat) = (0usize, 0usize);
+        for i in 0..r {
+            // (the marks live in the buffer of `out`: copied before it is released)
+            let body = unsafe { std::slice::from_raw_parts((out as *const u8).add(at), nbytes[i] as usize) }.to_vec();
+            let marks = unsafe { std::slice::from_raw_parts((mk as *const i64).add(mat), nmarks[i] as usize) }.to_vec();
+            at += nbytes[i] as usize;
+            mat += nmarks[i] as usize;
+            res.push((body, marks));
+        }
+        unsafe { kx_free_packed(out) };
+        Ok(res)
+    }
+
     /// Raw device-pointer form (inputs and output stay in HBM).
     ///
     /// # Safety
@@ -693,6 +737,33 @@ impl HipKokoDispatcher {
         let v = unsafe { std::slice::from_raw_parts(out as *const u8, nb as usize) }.to_vec();
         unsafe { kx_free_packed(out) };
         Ok((v, ns))
+    }
+
+    /// `submit_request` with the request's token marks ("token marks" in kokorox_hip.h): body, marks, sample count.
+    pub fn submit_request_marks(&self, chunks: &[Vec<i64>], styles: &[f32], speed: f32, seed: u64, format: i32)
+                                -> Result<(Vec<u8>, Vec<i64>, i64), Box<dyn Error>> {
+        if styles.len() != KX_STYLE_DIM * chunks.len() {
+            return Err("submit_request: one style row of 256 floats per chunk is required".into());
+        }
+        let ids: Vec<i64> = chunks.iter().flatten().copied().collect();
+        let lens: Vec<i32> = chunks.iter().map(|c| c.len() as i32).collect();
+        let mut out: *mut c_void = ptr::null_mut();
+        let mut mk: *mut i64 = ptr::null_mut();
+        let (mut nb, mut ns, mut nm) = (0i64, 0i64, 0i64);
+        let mut err = vec![0 as c_char; 256];
+        let rc = unsafe {
+            kx_dispatcher_submit_request_marks(self.d, ids.as_ptr(), lens.as_ptr(), lens.len() as c_int, styles.as_ptr(), ptr::null(),
+                                               ptr::null(), 0, speed, seed, format, &mut out, &mut nb, &mut ns, &mut mk, &mut nm,
+                                               err.as_mut_ptr(), err.len())
+        };
+        if rc != KX_OK {
+            return Err(format!("kokorox_hip error {}: {}", rc, cstr_buf(&err)).into());
+        }
+        let v = unsafe { std::slice::from_raw_parts(out as *const u8, nb as usize) }.to_vec();
+        // (inside the allocation of `out`: copied before it is released)
+        let marks = unsafe { std::slice::from_raw_parts(mk as *const i64, nm as usize) }.to_vec();
+        unsafe { kx_free_packed(out) };
+        Ok((v, marks, ns))
     }
 
     /// The WebSocket chunk of `encode_audio` (kokorox-websocket/src/lib.rs:696-736) for a request: base64 of its 16-bit WAV

@@ -281,10 +281,12 @@ int kx_infer_packed(kx_model* m, const int64_t* ids, int64_t t_stride, const int
     });
 }
 
-int kx_infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
-                      const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
-                      const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
-                      const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples) {
+// kx_infer_requests and kx_infer_requests_marks are one call: the first asks for no marks
+static int infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                          const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                          const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                          const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                          bool marks, int64_t** out_marks, int64_t* out_n_marks) {
     return guarded(m, [&](Model& M) {
         KX_REQUIRE(chunks_per_request && formats && R >= 1, "infer_requests: null argument");
         KX_REQUIRE((styles != nullptr) != (voice_ids != nullptr), "infer_requests: give the style rows OR voice ids, not both");
@@ -298,8 +300,30 @@ int kx_infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, const i
         hc.n_requests = R;
         hc.req_formats = formats;
         hc.n_req_formats = n_format;
-        M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples);
+        std::vector<uint8_t> want;
+        if (marks) {  // (every request of the call)
+            want.assign((size_t)R, 1);
+            hc.req_marks = want.data();
+        }
+        M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks);
     });
+}
+
+int kx_infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                      const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                      const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                      const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples) {
+    return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
+                          flags, formats, n_format, out, out_bytes, out_samples, false, nullptr, nullptr);
+}
+
+int kx_infer_requests_marks(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                            const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                            const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                            const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                            int64_t** out_marks, int64_t* out_n_marks) {
+    return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
+                          flags, formats, n_format, out, out_bytes, out_samples, true, out_marks, out_n_marks);
 }
 
 int kx_infer_device(kx_model* m, const int64_t* d_ids, int64_t t_stride, const int32_t* lens_host, int B,

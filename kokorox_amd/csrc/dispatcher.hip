@@ -21,6 +21,9 @@ struct ModelBackend {
     struct Out {
         void* buf = nullptr;  // the packed batch in one pooled page-locked buffer (requests back to back); per REQUEST:
         std::vector<int64_t> bytes, samples;
+        // the token marks of the requests that want them: one block in the same buffer, behind the bodies (null: nobody asked)
+        int64_t* marks = nullptr;
+        std::vector<int64_t> n_marks;
     };
     static int n_voices(kx_model* h) { return h->m->n_voices(); }
     static int n_vocab(kx_model* h) { return h->m->n_vocab(); }
@@ -35,9 +38,10 @@ struct ModelBackend {
         // plain = every request is one row in form 0..2: the single-utterance traffic of submit / submit_ex, which keeps the
         // per-utterance packing it has always had (pack_audio_kernel); anything else (several chunks, forms 3 / 4 / 8 / 9, a rate
         // code: all of them words above 2) goes through the request packer
-        bool any_voice = false, plain = true;
+        bool any_voice = false, plain = true, any_marks = false;
         for (Request* r : batch) {
-            plain = plain && r->rows() == 1 && r->format <= KX_PACK_PCM16_MONO;
+            plain = plain && r->rows() == 1 && r->format <= KX_PACK_PCM16_MONO && !r->want_marks;  // (marks come with the request path)
+            any_marks = any_marks || r->want_marks;
             B += r->rows();
             for (int c = 0; c < r->rows(); ++c) stride = (size_t)r->chunk_len(c) > stride ? (size_t)r->chunk_len(c) : stride;
             mm = r->n_mix > mm ? r->n_mix : mm;
@@ -48,11 +52,13 @@ struct ModelBackend {
         std::vector<float> styles((size_t)B * KX_STYLE_DIM, 0.f), speeds(B), weights((size_t)B * mm, 0.f);
         std::vector<uint64_t> seeds(B);
         std::vector<uint32_t> uidx(B);
+        std::vector<uint8_t> want(R);
         int b = 0;
         for (int q = 0; q < R; ++q) {
             const Request& r = *batch[(size_t)q];
             chunks[q] = r.rows();
             formats[q] = r.format;
+            want[q] = r.want_marks ? 1 : 0;
             size_t at = 0;
             for (int c = 0; c < r.rows(); ++c, ++b) {
                 lens[b] = (int32_t)r.chunk_len(c);
@@ -72,6 +78,8 @@ struct ModelBackend {
         o.buf = nullptr;
         o.bytes.assign(R, 0);
         o.samples.assign(R, 0);
+        o.marks = nullptr;
+        o.n_marks.assign(R, 0);
         int rc = KX_ERR_DEVICE;
         std::string err;
         {
@@ -90,6 +98,7 @@ struct ModelBackend {
                     hc.n_requests = R;
                     hc.req_formats = formats.data();
                     hc.n_req_formats = R;
+                    if (any_marks) hc.req_marks = want.data();
                 }
                 if (any_voice) {
                     hc.voice_ids = vids.data();
@@ -101,7 +110,7 @@ struct ModelBackend {
                     hc.styles = styles.data();
                 }
                 M.infer_host_ex(ids.data(), (int64_t)stride, lens.data(), B, speeds.data(), B, 0, 0, hc, &o.buf, o.bytes.data(),
-                                o.samples.data());
+                                o.samples.data(), &o.marks, o.n_marks.data());
                 rc = KX_OK;
             } catch (const kx::Error& e) {
                 rc = e.code;
@@ -123,10 +132,13 @@ struct ModelBackend {
     static void distribute(std::vector<Request*>& batch, Out& o) {
         const int B = (int)batch.size();
         std::vector<void*> parts((size_t)B);
-        int64_t off = 0;
+        std::vector<int64_t*> marks((size_t)B, nullptr);  // a request's marks go with its body: one owner, one pointer to release
+        int64_t off = 0, moff = 0;
         for (int b = 0; b < B; ++b) {
             parts[(size_t)b] = static_cast<char*>(o.buf) + off;
             off += o.bytes[(size_t)b];
+            if (o.marks && o.n_marks[(size_t)b] > 0) marks[(size_t)b] = o.marks + moff;
+            moff += o.n_marks[(size_t)b];
         }
         // A client that keeps (caches, leaks) one result keeps its whole batch's buffer page-locked.  Beyond KX_PINNED_LIVE_CAP_MB
         // (default 4096) of such buffers still held, a batch's results are copied out into plain allocations instead -- the ~5 ms of
@@ -137,16 +149,25 @@ struct ModelBackend {
             std::vector<void*> copies;
             copies.reserve((size_t)B);
             bool ok = true;
+            std::vector<int64_t*> mcopies((size_t)B, nullptr);
             for (int b = 0; b < B && ok; ++b) {
-                void* q = malloc((size_t)(o.bytes[(size_t)b] > 0 ? o.bytes[(size_t)b] : 1));
+                // body and marks in ONE plain allocation, the marks 8-aligned behind the body: still one pointer to release
+                const size_t body = (size_t)o.bytes[(size_t)b], mbytes = marks[(size_t)b] ? (size_t)o.n_marks[(size_t)b] * 8 : 0;
+                const size_t mat = (body + 7) & ~size_t(7);
+                void* q = malloc(mbytes ? mat + mbytes : (body > 0 ? body : 1));
                 ok = q != nullptr;
                 if (ok) {
-                    memcpy(q, parts[(size_t)b], (size_t)o.bytes[(size_t)b]);
+                    memcpy(q, parts[(size_t)b], body);
+                    if (mbytes) {
+                        mcopies[(size_t)b] = reinterpret_cast<int64_t*>(static_cast<char*>(q) + mat);
+                        memcpy(mcopies[(size_t)b], marks[(size_t)b], mbytes);
+                    }
                     copies.push_back(q);
                 }
             }
             if (ok) {
                 parts = copies;
+                marks = mcopies;
                 kx::host_out_free(o.buf);
             } else {  // (out of pageable memory: share after all)
                 for (void* q : copies) free(q);
@@ -160,8 +181,11 @@ struct ModelBackend {
             r->out = parts[(size_t)b];
             r->out_bytes = o.bytes[(size_t)b];
             r->out_samples = o.samples[(size_t)b];
+            r->marks = r->want_marks ? marks[(size_t)b] : nullptr;
+            r->n_marks = r->want_marks ? o.n_marks[(size_t)b] : 0;
         }
         o.buf = nullptr;
+        o.marks = nullptr;
     }
 };
 
@@ -255,6 +279,19 @@ int kx_dispatcher_submit_request(kx_dispatcher* d, const int64_t* ids, const int
     }
     return d->submit_request(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
                              out_samples, err, err_len);
+}
+
+int kx_dispatcher_submit_request_marks(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                       const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
+                                       float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
+                                       int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, char* err,
+                                       size_t err_len) {
+    if (!d) {
+        if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null dispatcher");
+        return KX_ERR_INVALID;
+    }
+    return d->submit_request_marks(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
+                                   out_bytes, out_samples, out_marks, out_n_marks, err, err_len);
 }
 
 int kx_dispatcher_stats(kx_dispatcher* d, int64_t* n_requests, int64_t* n_batches, int64_t* max_batch_seen) {

@@ -44,6 +44,7 @@
 //   static int forward(Handle*, std::vector<dispatch::Request*>&, Out&);  the batched forward: fills rc / err of EVERY request
 //                                                                         (and Out on success), returns the batch's status
 //   static void distribute(std::vector<dispatch::Request*>&, Out&);       gives every request its out / out_bytes / out_samples
+//                                                                         (and marks / n_marks where want_marks is set)
 //   static int n_voices(Handle*);                                         rows of the model's voice table (0 = none)
 //   static int n_vocab(Handle*);                                          rows of its embedding tables (token ids are 0 .. n_vocab - 1)
 //   static void free_out(void*);                                          releases a request's `out` (what distribute handed out)
@@ -81,9 +82,12 @@ struct Request {
     int format = 0;
     float speed = 1.f;
     uint64_t seed = 0;
+    bool want_marks = false;  // the token marks of the request beside its body (submit_request_marks); a batch may mix both kinds
     // result
     void* out = nullptr;
     int64_t out_bytes = 0, out_samples = 0;
+    int64_t* marks = nullptr;  // want_marks: into the allocation of `out`, 8-byte aligned behind the body; released with `out`
+    int64_t n_marks = 0;
     int rc = -1;
     std::string err;
     bool done = false;
@@ -431,9 +435,28 @@ struct Core {
     int submit_request(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
                        const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
                        void** out, int64_t* out_bytes, int64_t* out_samples, char* err, size_t err_len) {
+        return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
+                                  out_samples, false, nullptr, nullptr, err, err_len);
+    }
+    // ... and with the request's token marks: *out_marks points into the allocation of *out
+    int submit_request_marks(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
+                             const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
+                             void** out, int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
+                             char* err, size_t err_len) {
+        return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
+                                  out_samples, true, out_marks, out_n_marks, err, err_len);
+    }
+    int submit_request_any(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
+                           const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
+                           void** out, int64_t* out_bytes, int64_t* out_samples, bool want_marks, int64_t** out_marks,
+                           int64_t* out_n_marks, char* err, size_t err_len) {
         const char* who = "dispatcher_submit_request";
         if (!out || !out_bytes || !out_samples) {
             if (err && err_len) snprintf(err, err_len, "%s: null output argument", who);
+            return KX_ERR_INVALID;
+        }
+        if (want_marks && (!out_marks || !out_n_marks)) {
+            if (err && err_len) snprintf(err, err_len, "%s: null marks argument", who);
             return KX_ERR_INVALID;
         }
         if (!ids || !chunk_tokens || n_chunks < 1 || n_chunks > max_batch) {
@@ -469,7 +492,13 @@ struct Core {
         r.format = format;
         r.speed = speed;
         r.seed = seed;
-        return submit(r, out, out_bytes, out_samples, err, err_len);
+        r.want_marks = want_marks;
+        const int rc = submit(r, out, out_bytes, out_samples, err, err_len);
+        if (rc == KX_OK && want_marks) {
+            *out_marks = r.marks;
+            *out_n_marks = r.n_marks;
+        }
+        return rc;
     }
 };
 

@@ -96,6 +96,12 @@ void check_host_call(const int64_t* ids, int64_t t_stride, const int32_t* lens, 
     }
 }
 
+void check_marks_call(const HostCall& hc, int64_t** out_marks, int64_t* out_n_marks) {
+    KX_REQUIRE(out_marks && out_n_marks, "infer: null marks argument");
+    *out_marks = nullptr;
+    KX_REQUIRE(hc.grouped(), "infer: marks are for requests (chunks_per_request)");
+}
+
 // ---- refusals of the device entry (Model::infer_device) ----------------------------------------------------------------------
 int check_device_call(const void* d_ids, int64_t t_stride, const int32_t* lens_host, int B, const void* d_styles,
                       const float* speeds_host, int n_speed) {
@@ -128,10 +134,18 @@ void utt_layout(const int* frames, int B, int format, const int* formats, UttLay
     }
 }
 
-size_t packed_bytes_bound(const HostCall& hc, int B, size_t n_samples) {
+size_t packed_bytes_bound(const HostCall& hc, int B, size_t n_samples, const int32_t* lens) {
     // (the per-request header and the base64 padding do not scale with the samples: one frame per request is where a
     // per-sample estimate falls short)
-    if (hc.grouped()) return pack_requests_bound(hc.req_formats, hc.n_req_formats, hc.n_requests, n_samples);
+    if (hc.grouped()) {
+        size_t n = pack_requests_bound(hc.req_formats, hc.n_req_formats, hc.n_requests, n_samples);
+        if (hc.req_marks) {
+            KX_REQUIRE(lens, "infer: marks need the token counts");
+            n += 8;
+            for (int b = 0; b < B; ++b) n += 8 * ((size_t)lens[b] + 1);
+        }
+        return n;
+    }
     int widest = 0;  // (per-utterance packing: the widest form of the batch sizes the packed buffer)
     for (int b = 0; b < B; ++b) widest = format_sample_bytes(hc.format_of(b)) > widest ? format_sample_bytes(hc.format_of(b)) : widest;
     return n_samples * (size_t)widest;
@@ -216,6 +230,40 @@ void build_pack_plan(const int* frames, int B, const int* chunks_per_request, in
         row += n;
     }
     KX_REQUIRE(row == B, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
+}
+
+void build_mark_plan(const PackPlan& plan, const int* lens, const int* chunks_per_request, int R, const int* formats,
+                     int n_format, const uint8_t* req_marks, MarkPlan& mp) {
+    const int B = (int)plan.cum.size() - 1;
+    KX_REQUIRE(lens && formats && B >= 1 && R >= 1 && (int)plan.req.size() == R && (n_format == 1 || n_format == R), "marks: bad argument");
+    mp.row.assign((size_t)B, MarkRow{-1, 0, 0});
+    mp.count.assign((size_t)R, 0);
+    mp.first.assign((size_t)R, 0);
+    mp.marks_off = (plan.total_bytes + 7) & ~7L;
+    mp.n_marks = 0;
+    int row = 0;
+    for (int r = 0; r < R; ++r) {
+        const int n = chunks_per_request ? chunks_per_request[r] : 1;
+        const PackReq& q = plan.req[(size_t)r];
+        KX_REQUIRE(q.first_row == row && q.n_rows == n && n <= B - row, "marks: the grouping is not the plan's");
+        const int word = formats[n_format == 1 ? 0 : r];
+        check_format_word(word);
+        const long K = frame_samples(format_rate(word));
+        mp.first[(size_t)r] = mp.n_marks;
+        for (int b = row; b < row + n; ++b) {
+            KX_REQUIRE(lens[b] >= 1 && lens[b] <= 512, "infer: token count must be 1..512");
+            MarkRow& m = mp.row[(size_t)b];
+            m.K = K;
+            m.base = (plan.cum[(size_t)b] - plan.cum[(size_t)row]) / 600 * K;  // (cum counts 600 samples per frame)
+            if (req_marks && req_marks[r]) {
+                m.first = mp.n_marks;
+                mp.n_marks += lens[b] + 1;
+            }
+        }
+        mp.count[(size_t)r] = mp.n_marks - mp.first[(size_t)r];
+        row += n;
+    }
+    KX_REQUIRE(row == B, "marks: the grouping is not the plan's");
 }
 
 }  // namespace kx

@@ -30,6 +30,8 @@ struct HostCall {
     const int32_t* req_formats = nullptr;         // host [n_req_formats], format words (form | rate code << 8: check_format_word)
     int n_req_formats = 0;                        // 1 (shared) or n_requests
     const uint32_t* utt_index = nullptr;          // host [B] beside utt_seeds: row b draws (utt_seeds[b], utt_index[b])
+    // token timing marks (include/kokorox_hip.h, "token marks"): request r wants them when req_marks[r] != 0; null = none
+    const uint8_t* req_marks = nullptr;           // host [n_requests]
 
     bool grouped() const { return chunks_per_request != nullptr; }
     bool by_voice() const { return voice_ids != nullptr; }
@@ -44,6 +46,9 @@ struct HostCall {
 void check_host_call(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds, const HostCall& hc,
                      void** out, const int64_t* out_bytes, const int64_t* out_samples, int n_vocab, int n_voices,
                      bool have_voice_table);
+// The entries that return token marks (HostCall::req_marks set): their two extra output arguments, checked after everything
+// above; *out_marks is cleared.  throws KX_ERR_INVALID: "infer: null marks argument"
+void check_marks_call(const HostCall& hc, int64_t** out_marks, int64_t* out_n_marks);
 // Everything Model::infer_device refuses before hipSetDevice; returns the longest token count.
 int check_device_call(const void* d_ids, int64_t t_stride, const int32_t* lens_host, int B, const void* d_styles,
                       const float* speeds_host, int n_speed);
@@ -113,8 +118,33 @@ size_t resample_floats_bound(const int* formats, int n_format, size_t n_samples)
 void build_pack_plan(const int* frames, int B, const int* chunks_per_request, int R, const int* formats, int n_format,
                      PackPlan& plan);
 
+// ---- token timing marks behind the bodies (kernels_misc.hip: token_marks_kernel) ------------------------------------------
+// The marks of a request (include/kokorox_hip.h has the definition): per chunk its tokens + 1 int64 sample offsets at the
+// request's output rate.  They live in a block of their own in the packed buffer, at plan.total_bytes rounded up to 8, the
+// requests that want them back to back in request order, so body and marks leave the device in one copy.  One MarkRow per
+// ROW of the batch; the packer's and the resampler's table (PackReq) does not know about marks.
+struct MarkRow {
+    long first;  // index (in int64 values) of the row's first mark in the marks block; -1: its request wants none
+    long base;   // K x the frames of the request's earlier rows: the row's first mark
+    long K;      // output samples per frame: 600 L / M of the request's rate (600, 200, 400, 1200)
+};
+struct MarkPlan {
+    std::vector<MarkRow> row;  // [B]
+    std::vector<long> count;   // [R] marks of request r: the sum over its rows of lens + 1, or 0 when it wants none
+    std::vector<long> first;   // [R] index of request r's first mark in the block
+    long marks_off = 0;        // byte offset of the block in the packed buffer (a multiple of 8, >= plan.total_bytes)
+    long n_marks = 0;          // int64 values of the block
+    long end_bytes() const { return marks_off + 8 * n_marks; }  // bytes of body + marks: what one copy brings to the host
+};
+inline long frame_samples(int rate_code) { return rate_code == 1 ? 200 : (rate_code == 2 ? 400 : (rate_code == 3 ? 1200 : 600)); }
+// plan: build_pack_plan's result for the same rows and grouping; lens [B] tokens per row; formats [n_format] as there;
+// req_marks [R], null = no request wants marks (the block is then empty)
+void build_mark_plan(const PackPlan& plan, const int* lens, const int* chunks_per_request, int R, const int* formats,
+                     int n_format, const uint8_t* req_marks, MarkPlan& out);
+
 // Bytes of the packed buffer of a call of B rows before its forward has run, for n_samples samples in all: the requests' bound
-// when the call is grouped, else every sample in the widest form of the batch.
-size_t packed_bytes_bound(const HostCall& hc, int B, size_t n_samples);
+// when the call is grouped, else every sample in the widest form of the batch.  With marks asked for (hc.req_marks; lens [B]
+// then required) 8 + 8 x the sum over the rows of lens + 1 more: the alignment gap and a block in which every request wants them.
+size_t packed_bytes_bound(const HostCall& hc, int B, size_t n_samples, const int32_t* lens = nullptr);
 
 }  // namespace kx

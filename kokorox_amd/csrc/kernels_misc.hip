@@ -741,6 +741,47 @@ void launch_pack_plan(const float* audio, long audio_ld, const PackReq* d_req, c
     KX_HIP(hipGetLastError());
 }
 
+// ---- token timing marks (include/kokorox_hip.h has the definition; host_request.h: MarkRow, build_mark_plan) ----------------
+// One workgroup of 512 per row: lane t holds the duration of token t (0 at and beyond lens[b]: the front half leaves those
+// entries of `dur` unwritten, they are never loaded), an exclusive scan in 64 bits, and lane t stores base + K x scan[t] as one
+// 8-byte value, coalesced along t; the lane of the last token stores entry T, the row's end, as well.  The scan is one
+// __shfl_up ladder inside each wave64 and ONE exchange of the eight wave totals through LDS (one barrier).
+constexpr int MARK_THREADS = 512;
+__global__ __launch_bounds__(MARK_THREADS) void token_marks_kernel(const int* __restrict__ dur, const int* __restrict__ lens,
+                                                                   const MarkRow* __restrict__ rows,
+                                                                   long long* __restrict__ marks) {
+    __shared__ long long wave_total[MARK_THREADS / 64];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const MarkRow mr = rows[b];
+    if (mr.first < 0) return;  // (the whole workgroup: its request wants no marks)
+    const int T = min(lens[b], MARK_THREADS);
+    const long long d = t < T ? (long long)dur[(long)b * 512 + t] : 0;
+    const int lane = t & 63, wave = t >> 6;
+    long long incl = d;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long v = __shfl_up(incl, o);
+        if (lane >= o) incl += v;
+    }
+    if (lane == 63) wave_total[wave] = incl;
+    __syncthreads();
+    long long before = 0;
+#pragma unroll
+    for (int w = 0; w < MARK_THREADS / 64; ++w) before += w < wave ? wave_total[w] : 0;
+    incl += before;
+    if (t < T) {
+        marks[mr.first + t] = mr.base + mr.K * (incl - d);
+        if (t == T - 1) marks[mr.first + T] = mr.base + mr.K * incl;
+    }
+}
+// dur [B][512], lens [B], rows [B]: device; marks: the marks block (8-byte aligned), MarkPlan::n_marks values long
+void launch_token_marks(const int* dur, const int* lens, const MarkRow* d_rows, int B, void* marks, hipStream_t s) {
+    KX_REQUIRE(dur && lens && d_rows && marks && B >= 1 && (reinterpret_cast<uintptr_t>(marks) & 7) == 0, "marks: bad launch argument");
+    hipLaunchKernelGGL(token_marks_kernel, dim3((unsigned)B), dim3(MARK_THREADS), 0, s, dur, lens, d_rows,
+                       static_cast<long long*>(marks));
+    KX_HIP(hipGetLastError());
+}
+
 // ---- diagnostics: magnitude of a conv input after its AdaIN affine ---------------------------------------------
 __global__ void diag_stats_kernel(const float* x, long bs, int ld, int C, LenMap len, const float* nmean,
                                   const float* nscale, const float* nshift, int n_bs, float* out3) {

@@ -293,6 +293,9 @@ void launch_pack_audio(const float* audio, long audio_ld, const int* frames, int
 // d_y: plan.y_floats floats for the resampled streams (null when 0); out: 16-byte aligned, plan.total_bytes long
 void launch_pack_plan(const float* audio, long audio_ld, const PackReq* d_req, const long* d_cum, int R, const PackPlan& plan,
                       float* d_y, void* out, hipStream_t s);
+// token timing marks of the rows whose MarkRow::first is >= 0 (host_request.h: build_mark_plan): dur [B][512] as duration_kernel
+// wrote it, lens [B], d_rows [B] on the device; marks = the marks block, 8-byte aligned
+void launch_token_marks(const int* dur, const int* lens, const MarkRow* d_rows, int B, void* marks, hipStream_t s);
 // Host output buffers of the kx_infer* calls: page-locked and pooled (one asynchronous D2H copy at PCIe rate instead
 // of per-utterance pageable copies); host_out_free also accepts plain malloc'd pointers (dispatcher results).
 void* host_out_alloc(size_t bytes);

@@ -190,7 +190,7 @@ class Model {
     using HostCall = kx::HostCall;  // (host_request.h)
     void infer_host_ex(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
                        int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out, int64_t* out_bytes,
-                       int64_t* out_samples);
+                       int64_t* out_samples, int64_t** out_marks = nullptr, int64_t* out_n_marks = nullptr);
     // [0] recurrence in use: 0 = resident weights (two / four workgroups), 1 = the streaming fall-back; [1] hand-off time-outs so
     // far; [2] clean forwards left until the resident forms return (0 when they are in use); [3] calls re-run transparently
     void status(int64_t out[4]) const;
@@ -317,6 +317,7 @@ class Model {
         int B = 0, Tmax = 0, Fmax = 0;
         std::vector<int> hT, hF;           // host copies of the token / frame counts
         int *dT = nullptr, *dF = nullptr;  // the device's
+        const int* d_dur = nullptr;        // [B][512] frames per token as the forward used them (token-axis arena: alive until the next call)
         bool taps_on = false;
         bool dry = false;        // sizing pass: allocate (count) but launch nothing
         bool p1_region = false;  // inside the part of the forward whose direct-A convs may run reduced precision
@@ -376,9 +377,11 @@ class Model {
     int lstm_rearm_in_ = 0;
     int64_t n_lstm_timeouts_ = 0, n_rerun_ = 0;
     void infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds, int n_speed,
-                         uint64_t seed, uint32_t flags, const HostCall& hc, void** out, int64_t* out_bytes, int64_t* out_samples);
+                         uint64_t seed, uint32_t flags, const HostCall& hc, void** out, int64_t* out_bytes, int64_t* out_samples,
+                         int64_t** out_marks, int64_t* out_n_marks);
     // host staging that asynchronous copies read / write: outlives the calling frame
     PackPlan pack_plan_;               // request table + sample prefixes of the running call
+    MarkPlan mark_plan_;               // per-row table of the token marks of the running call
     UttLayout utt_layout_;             // per-utterance offsets of the running call
     unsigned h_bad_id_ = 0;
     unsigned* d_dev_err_ = nullptr;

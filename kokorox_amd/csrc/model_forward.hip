@@ -390,6 +390,7 @@ Model::Front Model::front_half(const int64_t* d_ids, int64_t t_stride, const int
         d_bad_id_ = reinterpret_cast<unsigned*>(A.i(1));
         d_speeds = A.f(B);
         dur = A.i((size_t)B * 512);
+        call_.d_dur = dur;
         idx = A.i((size_t)B * idx_ld);
         gb_ = A.f((size_t)B * gb_total_);
         nmean_ = A.f((size_t)B * n_bs_);

@@ -116,21 +116,23 @@ void Model::infer_host(const int64_t* ids, int64_t t_stride, const int32_t* lens
 // points run the call once more, now on the streaming recurrence (same bits), and the caller sees a result, not an error.
 void Model::infer_host_ex(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
                           int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out,
-                          int64_t* out_bytes, int64_t* out_samples) {
+                          int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks) {
     try {
-        infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples);
+        infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks);
     } catch (const LstmTimeout&) {
         n_rerun_ += 1;
-        infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples);
+        infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks);
     }
     note_clean_forward();
 }
 
 void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
                             int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out,
-                            int64_t* out_bytes, int64_t* out_samples) {
+                            int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks) {
     check_host_call(ids, t_stride, lens, B, speeds, hc, out, out_bytes, out_samples, n_vocab_, n_voices_, d_voices_ != nullptr);
+    if (hc.req_marks) check_marks_call(hc, out_marks, out_n_marks);
     const bool grouped = hc.grouped(), by_voice = hc.by_voice();
+    const bool marks = hc.req_marks != nullptr;  // (grouped then: check_marks_call)
     const int R = grouped ? hc.n_requests : B;
     KX_HIP(hipSetDevice(device));
     // I/O staging lives in its own arena: ids, styles, frames, noise keys, voice picks, audio, packed audio
@@ -140,6 +142,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     uint64_t* d_seeds;
     uint32_t* d_uidx;
     PackReq* d_req = nullptr;
+    MarkRow* d_mrow = nullptr;
     long* d_cum = nullptr;
     float* d_y = nullptr;  // the resampled streams of the requests with a rate code, back to back
     int *d_vid, *d_rows, *d_kinds, *d_formats = nullptr;
@@ -161,11 +164,12 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             d_req = static_cast<PackReq*>(A.alloc((size_t)R * sizeof(PackReq)));
             d_cum = static_cast<long*>(A.alloc(((size_t)B + 1) * 8));
             d_y = A.f(resample_floats_bound(hc.req_formats, hc.n_req_formats, audio_floats));
+            if (marks) d_mrow = static_cast<MarkRow*>(A.alloc((size_t)B * sizeof(MarkRow)));
         } else {
             d_formats = A.i(B);
             d_off = static_cast<long*>(A.alloc((size_t)B * 8));
         }
-        d_packed = A.alloc(packed_bytes_bound(hc, B, audio_floats));  // compact output: utterances / requests back to back
+        d_packed = A.alloc(packed_bytes_bound(hc, B, audio_floats, lens));  // compact output: utterances / requests back to back
         return A.f(audio_floats);
     };
     // worst case length is 50 frames per token; start from a typical 8 and retry once if short
@@ -209,6 +213,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         // frame counts are known (the forward's one host sync): pack the B waveforms back to back on the GPU in the
         // requested sample format, then ONE asynchronous copy into a page-locked host buffer
         int64_t total = 0;
+        int64_t marks_off = 0, n_marks = 0;
         if (grouped) {
             // the request table and the rows' sample prefixes, then ONE launch for every request of the batch, whatever its form
             // (and one before it, the resampler, when a request asks for another rate)
@@ -222,6 +227,20 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             KX_HIP(hipMemcpyAsync(d_req, plan.req.data(), (size_t)R * sizeof(PackReq), hipMemcpyHostToDevice, stream_));
             KX_HIP(hipMemcpyAsync(d_cum, plan.cum.data(), ((size_t)B + 1) * 8, hipMemcpyHostToDevice, stream_));
             launch_pack_plan(d_audio, ld, d_req, d_cum, R, plan, d_y, d_packed, stream_);
+            if (marks) {
+                // the token marks of the requests that want them, in a block of their own behind the bodies (8-aligned): one
+                // more launch on this stream, and the call's one copy to the host brings both
+                MarkPlan& mp = mark_plan_;
+                build_mark_plan(plan, lens, hc.chunks_per_request, R, hc.req_formats, hc.n_req_formats, hc.req_marks, mp);
+                for (int r = 0; r < R; ++r) out_n_marks[r] = mp.count[(size_t)r];
+                marks_off = mp.marks_off;
+                n_marks = mp.n_marks;
+                if (n_marks > 0) {
+                    KX_HIP(hipMemcpyAsync(d_mrow, mp.row.data(), (size_t)B * sizeof(MarkRow), hipMemcpyHostToDevice, stream_));
+                    launch_token_marks(call_.d_dur, call_.dT, d_mrow, B, static_cast<char*>(d_packed) + marks_off, stream_);
+                    total = mp.end_bytes();
+                }
+            }
         } else {
             UttLayout& lay = utt_layout_;
             utt_layout(call_.hF.data(), B, hc.format, hc.formats, lay);
@@ -252,6 +271,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             throw;
         }
         *out = host;
+        if (marks) *out_marks = n_marks > 0 ? reinterpret_cast<int64_t*>(host + marks_off) : nullptr;
         return;
     }
 }

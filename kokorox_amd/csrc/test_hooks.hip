@@ -619,4 +619,46 @@ int kx_test_pack_requests(int device_id, const float* audio, int B, int64_t audi
     });
 }
 
+int kx_test_token_marks(int device_id, const int32_t* dur, const int32_t* lens, int B, const int32_t* chunks_per_request, int R,
+                        const int32_t* formats, const uint8_t* want, int64_t* out_marks, int64_t out_cap, int64_t* out_n_marks,
+                        char* err, size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        check_device(device_id);
+        KX_REQUIRE(dur && lens && chunks_per_request && formats && out_marks && out_n_marks && B > 0 && R > 0, "test_token_marks: bad argument");
+        std::vector<int> frames((size_t)B, 0);  // what duration_kernel would have summed: the row's valid durations
+        for (int b = 0; b < B; ++b) {
+            KX_REQUIRE(lens[b] >= 1 && lens[b] <= 512, "test_token_marks: lens out of range");
+            long f = 0;
+            for (int t = 0; t < lens[b]; ++t) {
+                KX_REQUIRE(dur[(size_t)b * 512 + t] >= 0, "test_token_marks: negative duration");
+                f += dur[(size_t)b * 512 + t];
+            }
+            KX_REQUIRE(f <= 0x7FFFFFFF / 600, "test_token_marks: too many frames in a row");
+            frames[(size_t)b] = (int)f;
+        }
+        kx::PackPlan plan;  // the two table builders of Model::infer_host_once
+        kx::build_pack_plan(frames.data(), B, chunks_per_request, R, formats, R, plan);
+        std::vector<uint8_t> all((size_t)R, 1);  // want = null: every request
+        kx::MarkPlan mp;
+        kx::build_mark_plan(plan, lens, chunks_per_request, R, formats, R, want ? want : all.data(), mp);
+        for (int r = 0; r < R; ++r) out_n_marks[r] = mp.count[(size_t)r];
+        KX_REQUIRE(mp.n_marks <= out_cap, "test_token_marks: out_cap is too small");
+        if (mp.n_marks == 0) return;
+        KX_HIP(hipSetDevice(device_id));
+        DevMem dm;
+        const int* d_dur = dm.up(dur, (size_t)B * 512);
+        const int* d_len = dm.up(lens, (size_t)B);
+        const kx::MarkRow* d_rows = dm.up(mp.row.data(), (size_t)B);
+        // a sentinel after the last mark: the kernel must not write past what the plan says
+        char* d_out = dm.get<char>((size_t)mp.n_marks * 8 + 64);
+        KX_HIP(hipMemset(d_out, 0xA5, (size_t)mp.n_marks * 8 + 64));
+        kx::launch_token_marks(d_dur, d_len, d_rows, B, d_out, nullptr);
+        KX_HIP(hipDeviceSynchronize());
+        std::vector<unsigned char> tail(64);
+        KX_HIP(hipMemcpy(out_marks, d_out, (size_t)mp.n_marks * 8, hipMemcpyDeviceToHost));
+        KX_HIP(hipMemcpy(tail.data(), d_out + mp.n_marks * 8, 64, hipMemcpyDeviceToHost));
+        for (unsigned char c : tail) KX_REQUIRE(c == 0xA5, "test_token_marks: the kernel wrote past the last mark");
+    });
+}
+
 }  // extern "C"

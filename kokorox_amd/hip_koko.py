@@ -117,6 +117,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "kx_infer_requests": (i32, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, u64, u32, vp, i32, C.POINTER(vp), vp, vp]),
         "kx_dispatcher_submit_request": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
                                                C.POINTER(i64), cp, sz]),
+        "kx_infer_requests_marks": (i32, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, u64, u32, vp, i32, C.POINTER(vp), vp, vp,
+                                          C.POINTER(vp), vp]),
+        "kx_dispatcher_submit_request_marks": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
+                                                     C.POINTER(i64), C.POINTER(vp), C.POINTER(i64), cp, sz]),
         "kx_dispatcher_create": (vp, [vp, i32, i32, i32, cp, sz]),
         "kx_dispatcher_create_warm": (vp, [vp, i32, i32, i32, i32, i32, cp, sz]),
         "kx_dispatcher_submit": (i32, [vp, vp, i32, vp, f32, u64, C.POINTER(C.POINTER(f32)), C.POINTER(i64), cp, sz]),
@@ -173,6 +177,7 @@ def load_test_library() -> C.CDLL:
         "kx_test_layernorm": (i32, [i32, vp, i32, i32, i32, vp, f32, i32, vp, vp, f32, vp, cp, sz]),
         "kx_test_instance_norm": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, cp, sz]),
         "kx_test_pack_requests": (i32, [i32, vp, i32, i64, vp, vp, i32, vp, vp, i64, vp, cp, sz]),
+        "kx_test_token_marks": (i32, [i32, vp, vp, i32, vp, i32, vp, vp, vp, i64, vp, cp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -184,7 +189,7 @@ def load_test_library() -> C.CDLL:
 
 TEST_ABI_SYMBOLS = ["kx_test_conv1d", "kx_test_lstm", "kx_test_source", "kx_test_attention", "kx_test_conv1d_epilogue", "kx_test_conv1d_full",
                     "kx_test_conv_transpose", "kx_test_lstm_fault", "kx_test_lstm_parts", "kx_test_conv_plan", "kx_test_conv1d_opts",
-                    "kx_test_layernorm", "kx_test_instance_norm", "kx_test_pack_requests"]
+                    "kx_test_layernorm", "kx_test_instance_norm", "kx_test_pack_requests", "kx_test_token_marks"]
 
 ABI_SYMBOLS = [
     "kx_version", "kx_init", "kx_create", "kx_import_onnx", "kx_resample_filter", "kx_create_from_device_blob", "kx_create_replicas", "kx_replicas_times", "kx_create_partition", "kx_destroy",
@@ -192,7 +197,7 @@ ABI_SYMBOLS = [
     "kx_free_audio", "kx_infer_device", "kx_sync", "kx_set_pinned_durations", "kx_warmup", "kx_arena_bytes", "kx_call_times", "kx_model_status", "kx_model_info", "kx_dispatcher_health", "kx_set_utterance_base", "kx_set_lanes",
     "kx_set_conv_mode", "kx_get_conv_mode", "kx_set_stft_variant", "kx_get_stft_variant",
     "kx_profile_enable", "kx_profile_read", "kx_profile_detail", "kx_profile_aux", "kx_diag_enable", "kx_diag_count", "kx_diag_get", "kx_set_act_prescale", "kx_set_voice_table", "kx_infer_voices",
-    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
+    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
     "kx_dispatcher_stats", "kx_dispatcher_failures", "kx_dispatcher_destroy", "kx_debug_tap",
 ]
 
@@ -404,6 +409,19 @@ class HipKoko:
         0..2 (float32, [n, 2] float32, int16) and the G.711 forms (uint8), the body as `bytes` for PACK_WAV_F32 and
         PACK_WAV16_BASE64.  with_samples: also the library's own sample count of every request (out_samples, at the output
         rate), as a second list."""
+        res, _, nsamp = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, False)
+        return (res, nsamp) if with_samples else res
+
+    def infer_requests_marks(self, tokens, chunks_per_request, styles=None, voice_ids=None, weights=None, speeds=(1.0,),
+                             seed: int = 0, flags: int = 0, fmt=0, with_samples: bool = False):
+        """infer_requests with the token marks of every request (kx_infer_requests_marks; the definition is in
+        include/kokorox_hip.h, the numpy form voices.token_marks).  Returns (bodies, marks): bodies exactly as infer_requests,
+        marks one int64 array per request -- per chunk its tokens + 1 sample offsets in the request's stream at the request's
+        output rate, the chunks back to back (voices.token_spans splits them).  with_samples: out_samples as a third entry."""
+        res, marks, nsamp = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, True)
+        return (res, marks, nsamp) if with_samples else (res, marks)
+
+    def _infer_requests(self, tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, want_marks):
         ids, lens = self._ids_lens(tokens)
         B = len(tokens)
         cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32).reshape(-1)
@@ -420,18 +438,30 @@ class HipKoko:
         sp = _f32(np.asarray(speeds, dtype=np.float32).reshape(-1))
         out = C.c_void_p()
         nbytes, nsamp = np.zeros(max(R, 1), np.int64), np.zeros(max(R, 1), np.int64)
-        self._check(self._lib.kx_infer_requests(self._h, _ptr(ids), ids.shape[1], _ptr(lens), B, _ptr(cpr), R, _ptr(st), _ptr(v),
-                                                _ptr(w), mm, _ptr(sp), sp.shape[0], seed, flags, _ptr(fm), fm.shape[0],
-                                                C.byref(out), _ptr(nbytes), _ptr(nsamp)))
+        args = (self._h, _ptr(ids), ids.shape[1], _ptr(lens), B, _ptr(cpr), R, _ptr(st), _ptr(v), _ptr(w), mm, _ptr(sp), sp.shape[0],
+                seed, flags, _ptr(fm), fm.shape[0], C.byref(out), _ptr(nbytes), _ptr(nsamp))
+        marks = None
+        if want_marks:
+            mk, n_mk = C.c_void_p(), np.zeros(max(R, 1), np.int64)
+            self._check(self._lib.kx_infer_requests_marks(*args, C.byref(mk), _ptr(n_mk)))
+        else:
+            self._check(self._lib.kx_infer_requests(*args))
         total = int(nbytes[:R].sum())
         raw = C.string_at(out, total) if total else b""
+        if want_marks:  # (they live in the buffer of `out`: read before it is released)
+            if (mk.value or 0) % 8 != 0 or not (out.value <= mk.value):
+                self._lib.kx_free_packed(out)
+                raise KokoroxHipError(3, "marks are not 8-byte aligned inside the packed buffer")
+            flat = np.frombuffer(C.string_at(mk, 8 * int(n_mk[:R].sum())), dtype=np.int64).copy()
+            cuts = np.cumsum(n_mk[:R])[:-1]
+            marks = [m.copy() for m in np.split(flat, cuts)]
         self._lib.kx_free_packed(out)
         res, o = [], 0
         for r in range(R):
             part = raw[o: o + int(nbytes[r])]
             o += int(nbytes[r])
             res.append(_decode_packed(part, int(fm[r if fm.shape[0] > 1 else 0])))
-        return (res, [int(v) for v in nsamp[:R]]) if with_samples else res
+        return res, marks, [int(v) for v in nsamp[:R]]
 
     def infer_device(self, d_ids: int, t_stride: int, lens_host: np.ndarray, d_styles: int, speeds_host: np.ndarray,
                      d_audio: int, audio_ld: int, d_frames: int, seed: int = 0, flags: int = 0) -> int:
@@ -645,11 +675,12 @@ class Dispatcher:
         return arr.reshape(-1, 2) if fmt == 1 else arr
 
     def submit_request(self, chunks: Sequence[Sequence[int]], styles=None, voices=None, speed: float = 1.0, seed: int = 0,
-                       fmt: int = 0):
+                       fmt: int = 0, marks: bool = False):
         """A request of 1 .. max_batch chunks (kx_dispatcher_submit_request): `chunks` = the 0-wrapped id lists; `styles` = one
         256-float row per chunk, OR `voices` as in submit_ex (one voice spec for the request); `fmt` = a format word (a PACK_*
         form, optionally | PACK_RATE_*).  Returns what HipKoko.infer_requests returns for one request: an array (forms 0..2, 8, 9)
-        or the body as bytes (3, 4)."""
+        or the body as bytes (3, 4).  marks=True (kx_dispatcher_submit_request_marks): returns (body, marks), marks = the
+        request's token marks as one int64 array (HipKoko.infer_requests_marks)."""
         lens = np.array([len(c) for c in chunks], dtype=np.int32)
         a = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.int64).reshape(-1) for c in chunks])
                                  if len(chunks) else np.zeros(0, np.int64))
@@ -669,15 +700,24 @@ class Dispatcher:
             n_mix = len(vid)
         out, nb, ns = C.c_void_p(), C.c_int64(0), C.c_int64(0)
         err = C.create_string_buffer(256)
-        rc = self._lib.kx_dispatcher_submit_request(self._d, _ptr(a), _ptr(lens), len(chunks), _ptr(st), _ptr(vid), _ptr(w), n_mix,
-                                                    float(speed), seed, fmt, C.byref(out), C.byref(nb), C.byref(ns), err, len(err))
+        args = (self._d, _ptr(a), _ptr(lens), len(chunks), _ptr(st), _ptr(vid), _ptr(w), n_mix, float(speed), seed, fmt, C.byref(out),
+                C.byref(nb), C.byref(ns))
+        mk, n_mk = C.c_void_p(), C.c_int64(0)
+        if marks:
+            rc = self._lib.kx_dispatcher_submit_request_marks(*args, C.byref(mk), C.byref(n_mk), err, len(err))
+        else:
+            rc = self._lib.kx_dispatcher_submit_request(*args, err, len(err))
         if rc != 0:
             raise KokoroxHipError(rc, err.value.decode())
         try:
             raw = C.string_at(out, nb.value)
+            if marks:  # (inside the allocation of `out`, 8-byte aligned behind the body: read before it is released)
+                if (mk.value or 0) % 8 != 0 or (mk.value or 0) < out.value + nb.value:
+                    raise KokoroxHipError(3, "marks are not 8-byte aligned behind the body")
+                m = np.frombuffer(C.string_at(mk, 8 * n_mk.value), dtype=np.int64).copy()
         finally:
             self._lib.kx_free_packed(out)
-        return _decode_packed(raw, fmt)
+        return (_decode_packed(raw, fmt), m) if marks else _decode_packed(raw, fmt)
 
     def stats(self):
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
@@ -949,3 +989,23 @@ def pack_requests(audio, frames, chunks_per_request, formats, device=0):
         res.append(raw[o: o + int(nb[r])])
         o += int(nb[r])
     return res
+
+
+def token_marks(dur, lens, chunks_per_request, formats, want=None, device=0):
+    """The token marks alone (kx_test_token_marks): dur [B, 512] int32 frames per token, row b valid for lens[b] entries,
+    request r = chunks_per_request[r] consecutive rows in the format word formats[r]; want [R] = which requests get marks
+    (None: all).  Returns one int64 array per request (empty where not wanted): voices.token_marks of the same durations."""
+    lib = load_test_library()
+    dur = np.ascontiguousarray(dur, dtype=np.int32)
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32)
+    fm = np.ascontiguousarray(formats, dtype=np.int32)
+    B, R = ln.shape[0], cpr.shape[0]
+    assert dur.shape == (B, 512) and fm.shape == (R,)
+    wt = None if want is None else np.ascontiguousarray(want, dtype=np.uint8)
+    assert wt is None or wt.shape == (R,)
+    cap = int(ln.sum()) + B
+    out = np.zeros(cap, dtype=np.int64)
+    n = np.zeros(R, dtype=np.int64)
+    _err_call(lib.kx_test_token_marks, device, _ptr(dur), _ptr(ln), B, _ptr(cpr), R, _ptr(fm), _ptr(wt), _ptr(out), cap, _ptr(n))
+    return [m.copy() for m in np.split(out[: int(n.sum())], np.cumsum(n)[:-1])]

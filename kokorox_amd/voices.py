@@ -199,6 +199,62 @@ def alaw_bytes(pcm) -> np.ndarray:
     return byte.astype(np.uint8)
 
 
+_RATE_LM = {0: (1, 1), 1: (1, 3), 2: (2, 3), 3: (2, 1)}  # rate code of a format word -> (L, M): 24 000, 8000, 16 000, 48 000 Hz
+
+
+def token_marks(durations_per_chunk: Sequence[Sequence[int]], word: int = 0) -> np.ndarray:
+    """The token marks of ONE request (the definition of include/kokorox_hip.h, "token marks", in numpy int64):
+    `durations_per_chunk[c][t]` = frames the forward used for token t of chunk c (the two 0 pads included), `word` the request's
+    format word (only its rate code matters).  With K = 600 L / M, chunk after chunk T_c + 1 values
+        m_c[t] = K * (frames of the chunks before c + sum of d_c[t'] for t' < t),   t = 0 .. T_c;
+    token t of chunk c occupies the output samples [m_c[t], m_c[t + 1]) of the request's stream, the last value is the
+    request's sample count."""
+    code = (int(word) >> 8) & 15
+    if code not in _RATE_LM or not durations_per_chunk:
+        raise ValueError("token_marks: unknown output sample rate, or a request without chunks")
+    L, M = _RATE_LM[code]
+    K = 600 * L // M
+    out, base = [], 0
+    for d in durations_per_chunk:
+        d = np.asarray(d, dtype=np.int64).reshape(-1)
+        if d.shape[0] < 1:
+            raise ValueError("token_marks: empty chunk")
+        out.append(K * (base + np.concatenate([np.zeros(1, np.int64), np.cumsum(d, dtype=np.int64)])))
+        base += int(d.sum())
+    return np.concatenate(out).astype(np.int64)
+
+
+def token_spans(marks, chunk_tokens: Sequence[int]):
+    """A request's marks as one (start, end) pair of int64 arrays per chunk: token t of chunk c occupies samples
+    [start[t], end[t]) of the request's stream.  `chunk_tokens[c]` = tokens of chunk c (its two pads included); chunk c has
+    chunk_tokens[c] + 1 marks.  start[0] is where the chunk begins in the body; the first and the last span are the spans of
+    the two pad tokens: the chunk's lead-in and tail."""
+    m = np.asarray(marks, dtype=np.int64).reshape(-1)
+    if m.shape[0] != sum(int(t) + 1 for t in chunk_tokens):
+        raise ValueError("token_spans: a request has the sum over its chunks of tokens + 1 marks")
+    spans, o = [], 0
+    for t in chunk_tokens:
+        t = int(t)
+        spans.append((m[o: o + t].copy(), m[o + 1: o + t + 1].copy()))
+        o += t + 1
+    return spans
+
+
+def word_spans(spans, words: Sequence[Sequence[int]]):
+    """(start, end) samples of words given as token index ranges: `spans` = (start, end) arrays of ONE chunk (token_spans),
+    `words` = (first token, last token) pairs, both inclusive, indices into the chunk's tokens with the pads counted.  A word
+    starts where its first token starts and ends where its last token ends.  (Which tokens make a word is the text
+    front-end's knowledge: it stays outside this library.)"""
+    start, end = spans
+    out = []
+    for a, b in words:
+        a, b = int(a), int(b)
+        if not 0 <= a <= b < len(start):
+            raise ValueError("word_spans: token range outside the chunk")
+        out.append((int(start[a]), int(end[b])))
+    return out
+
+
 def tts_request(model, styles: Dict[str, np.ndarray], style_name: str, chunk_tokens: Sequence[Sequence[int]],
                 speed: float = 1.0, initial_silence: int = 0, seed: int = 0, fmt: int = 0):
     """`tts_chunks` through `model.infer_requests`: the chunks of one text as ONE request of one batched forward, its body
