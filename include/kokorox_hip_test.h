@@ -101,7 +101,8 @@ int kx_test_source(int device_id, const float* f0, int B, int F2, const float* l
 
 /* The request packer alone (pack_requests_kernel through build_pack_plan, the host-side table builder the model uses), host
  * arrays in, host bytes out: audio [B, audio_ld] with row b valid for 600 frames[b] samples (whatever lies beyond must not
- * reach the result), request r = chunks_per_request[r] consecutive rows in the format word formats[r] (a KX_PACK_* form, optionally | KX_PACK_RATE_*; [R]).  out receives
+ * reach the result), request r = chunks_per_request[r] consecutive rows (null: every row a request of its own, R = B) in the
+ * format word formats[r] (a KX_PACK_* form, optionally | KX_PACK_RATE_*; [R]).  out receives
  * the R regions back to back (out_cap bytes available), out_bytes[r] their sizes. */
 int kx_test_pack_requests(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames,
                           const int32_t* chunks_per_request, int R, const int32_t* formats, void* out, int64_t out_cap,

@@ -15,7 +15,7 @@ namespace {
 
 using kx::dispatch::Request;
 
-// One batched forward on a model: requests of every kind / format in one HostCall (per-utterance kinds, formats, keys).
+// One batched forward on a model: requests of every kind / format in one HostCall (per-row kinds and keys, per-request formats).
 struct ModelBackend {
     using Handle = kx_model;
     struct Out {
@@ -35,12 +35,8 @@ struct ModelBackend {
         int B = 0;
         size_t stride = 0;
         int mm = 1;
-        // plain = every request is one row in form 0..2: the single-utterance traffic of submit / submit_ex, which keeps the
-        // per-utterance packing it has always had (pack_audio_kernel); anything else (several chunks, forms 3 / 4 / 8 / 9, a rate
-        // code: all of them words above 2) goes through the request packer
-        bool any_voice = false, plain = true, any_marks = false;
+        bool any_voice = false, any_marks = false;
         for (Request* r : batch) {
-            plain = plain && r->rows() == 1 && r->format <= KX_PACK_PCM16_MONO && !r->want_marks;  // (marks come with the request path)
             any_marks = any_marks || r->want_marks;
             B += r->rows();
             for (int c = 0; c < r->rows(); ++c) stride = (size_t)r->chunk_len(c) > stride ? (size_t)r->chunk_len(c) : stride;
@@ -88,18 +84,15 @@ struct ModelBackend {
             try {
                 kx::Model::HostCall hc;
                 hc.utt_seeds = seeds.data();
-                if (plain) {  // (R = B: chunk 0 of every request is utterance 0 of its key's stream, the default)
-                    hc.format = batch[0]->format;
-                    for (int q = 1; q < R && !hc.formats; ++q)
-                        if (formats[q] != formats[0]) hc.formats = formats.data();  // (per utterance only where they differ)
-                } else {
-                    hc.utt_index = uidx.data();
-                    hc.chunks_per_request = chunks.data();
-                    hc.n_requests = R;
-                    hc.req_formats = formats.data();
-                    hc.n_req_formats = R;
-                    if (any_marks) hc.req_marks = want.data();
-                }
+                // every batch is a call of R requests, the single-utterance traffic of submit / submit_ex included: its rows
+                // carry utterance index 0, which source_sample_kernel reads exactly as it reads a null utt_index (utterance 0
+                // of the key's stream), so their noise, and with it their audio, is what a call without indices gives
+                hc.utt_index = uidx.data();
+                hc.chunks_per_request = chunks.data();
+                hc.n_requests = R;
+                hc.req_formats = formats.data();
+                hc.n_req_formats = R;
+                if (any_marks) hc.req_marks = want.data();
                 if (any_voice) {
                     hc.voice_ids = vids.data();
                     hc.weights = weights.data();

@@ -55,7 +55,7 @@ void check_host_call(const int64_t* ids, int64_t t_stride, const int32_t* lens, 
     *out = nullptr;
     KX_REQUIRE(B >= 1, "infer: empty batch");
     KX_REQUIRE(ids && lens && speeds, "infer: null argument");
-    const bool grouped = hc.grouped();  // (then `format` / `formats` are not used)
+    const bool grouped = hc.grouped();  // (then `format` is not used)
     KX_REQUIRE(grouped || (hc.format >= 0 && hc.format <= 2), "infer: unknown output format");
     if (grouped) {
         const int R = hc.n_requests;
@@ -82,7 +82,7 @@ void check_host_call(const int64_t* ids, int64_t t_stride, const int32_t* lens, 
             KX_REQUIRE(id >= 0 && id < n_vocab, "infer: token id outside 0..177");
         }
         const int kind = hc.kind_of(b);
-        KX_REQUIRE(kind >= 0 && kind <= 2 && (grouped || (hc.format_of(b) >= 0 && hc.format_of(b) <= 2)), "infer: unknown kind / output format");
+        KX_REQUIRE(kind >= 0 && kind <= 2, "infer: unknown kind / output format");
         if (kind != 0) {
             KX_REQUIRE(lens[b] >= 2, "infer: voice rows need the two 0 pads (row = tokens - 2)");
             bool any = false;
@@ -119,36 +119,14 @@ int check_device_call(const void* d_ids, int64_t t_stride, const int32_t* lens_h
 }
 
 // ---- layout of the compact output ----------------------------------------------------------------------------------------------
-void utt_layout(const int* frames, int B, int format, const int* formats, UttLayout& L) {
-    L.sample_bytes.assign((size_t)B, 0);
-    L.samples.assign((size_t)B, 0);
-    L.bytes.assign((size_t)B, 0);
-    L.off.assign((size_t)B, 0);
-    L.total_bytes = 0;
-    for (int b = 0; b < B; ++b) {
-        L.sample_bytes[(size_t)b] = format_sample_bytes(formats ? formats[b] : format);
-        L.samples[(size_t)b] = (int64_t)600 * frames[b];
-        L.bytes[(size_t)b] = L.samples[(size_t)b] * L.sample_bytes[(size_t)b];
-        L.off[(size_t)b] = (long)L.total_bytes;
-        L.total_bytes += L.bytes[(size_t)b];
-    }
-}
-
 size_t packed_bytes_bound(const HostCall& hc, int B, size_t n_samples, const int32_t* lens) {
-    // (the per-request header and the base64 padding do not scale with the samples: one frame per request is where a
-    // per-sample estimate falls short)
-    if (hc.grouped()) {
-        size_t n = pack_requests_bound(hc.req_formats, hc.n_req_formats, hc.n_requests, n_samples);
-        if (hc.req_marks) {
-            KX_REQUIRE(lens, "infer: marks need the token counts");
-            n += 8;
-            for (int b = 0; b < B; ++b) n += 8 * ((size_t)lens[b] + 1);
-        }
-        return n;
+    size_t n = pack_requests_bound(hc.words(), hc.n_words(), hc.regions(B), n_samples);
+    if (hc.req_marks) {
+        KX_REQUIRE(lens, "infer: marks need the token counts");
+        n += 8;
+        for (int b = 0; b < B; ++b) n += 8 * ((size_t)lens[b] + 1);
     }
-    int widest = 0;  // (per-utterance packing: the widest form of the batch sizes the packed buffer)
-    for (int b = 0; b < B; ++b) widest = format_sample_bytes(hc.format_of(b)) > widest ? format_sample_bytes(hc.format_of(b)) : widest;
-    return n_samples * (size_t)widest;
+    return n;
 }
 
 long pack_request_bytes(int form, long n_samples) {

@@ -460,33 +460,11 @@ __device__ __forceinline__ int pcm16_sample(float s, bool nan_to_zero) {
     const float c = fminf(fmaxf(s, -1.0f), 1.0f);
     return __float2int_rz(__fmul_rn(c, 32767.0f));
 }
-__global__ void pack_audio_kernel(const float* audio, long audio_ld, const int* frames, int format, const int* formats,
-                                  void* out, long out_stride_bytes, const long* out_off) {
-    const long j = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    const int b = blockIdx.y;
-    if (j >= 600L * frames[b]) return;
-    if (formats) format = formats[b];  // (per utterance: requests of one dispatched batch may differ)
-    const float sv = audio[b * audio_ld + j];
-    // out_off: byte offset of utterance b in a compact output (utterances back to back); else a fixed stride
-    char* ob = static_cast<char*>(out) + (out_off ? out_off[b] : b * out_stride_bytes);
-    if (format == 1) {
-        reinterpret_cast<float2*>(ob)[j] = make_float2(sv, sv);
-    } else if (format == 2) {
-        reinterpret_cast<short*>(ob)[j] = (short)pcm16_sample(sv, false);
-    } else {
-        reinterpret_cast<float*>(ob)[j] = sv;
-    }
-}
-void launch_pack_audio(const float* audio, long audio_ld, const int* frames, int B, int Fmax, int format, void* out,
-                       long out_stride_bytes, const long* out_off, hipStream_t s, const int* formats) {
-    hipLaunchKernelGGL(pack_audio_kernel, dim3((600 * Fmax + 255) / 256, B), dim3(256), 0, s, audio, audio_ld, frames,
-                       format, formats, out, out_stride_bytes, out_off);
-    KX_HIP(hipGetLastError());
-}
 
 // ---- requests of several chunks, packed as the bytes a server sends ---------------------------------------------
 // A request's region is a function of a VIRTUAL BYTE STREAM: the header of its form, then the sample bytes of its rows in
-// order (the chunk loop of koko.rs:947-1191 appends the waveforms with no cross-fade).  Forms 0..2 are launch_pack_audio's;
+// order (the chunk loop of koko.rs:947-1191 appends the waveforms with no cross-fade).  Forms 0..2 are the bare samples above
+// (the per-utterance entries kx_infer / kx_infer_packed / kx_infer_voices are single-row requests in those forms);
 // 3 = `WavHeader::new(1, 24000, 32).write_header` + `to_le_bytes` of every sample (kokorox/src/utils/wav.rs:18-50,
 // kokorox-openai/src/lib.rs:416-425: both size fields are the reference's 0xFFFFFFFF placeholders); 4 = standard base64 of a
 // 16-bit WAV file (`encode_audio`, kokorox-websocket/src/lib.rs:696-736), whose output group g is stream bytes 3g .. 3g + 2.

@@ -285,8 +285,6 @@ void launch_diag_stats(const float* x, long bs, int ld, int C, LenMap len, int B
 
 void launch_style_mix(const float* table, int n_voices, const int* voice_ids, const float* weights, int max_mix,
                       const int* rows, const int* kinds, float* styles, int B, hipStream_t s);
-void launch_pack_audio(const float* audio, long audio_ld, const int* frames, int B, int Fmax, int format, void* out,
-                       long out_stride_bytes, const long* out_off, hipStream_t s, const int* formats = nullptr);
 
 // ---- requests of several chunks (host_request.h: PackReq, PackPlan, build_pack_plan): pack_requests_kernel ----------
 // and, for requests with a rate code, resample_requests_kernel before it.  d_req [R], d_cum [B + 1]: device copies of the plan;

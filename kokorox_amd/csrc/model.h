@@ -382,7 +382,6 @@ class Model {
     // host staging that asynchronous copies read / write: outlives the calling frame
     PackPlan pack_plan_;               // request table + sample prefixes of the running call
     MarkPlan mark_plan_;               // per-row table of the token marks of the running call
-    UttLayout utt_layout_;             // per-utterance offsets of the running call
     unsigned h_bad_id_ = 0;
     unsigned* d_dev_err_ = nullptr;
     unsigned* h_words_ = nullptr;    // page-locked: [0] the device error word as read back

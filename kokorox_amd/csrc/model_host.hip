@@ -131,9 +131,11 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
                             int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks) {
     check_host_call(ids, t_stride, lens, B, speeds, hc, out, out_bytes, out_samples, n_vocab_, n_voices_, d_voices_ != nullptr);
     if (hc.req_marks) check_marks_call(hc, out_marks, out_n_marks);
-    const bool grouped = hc.grouped(), by_voice = hc.by_voice();
-    const bool marks = hc.req_marks != nullptr;  // (grouped then: check_marks_call)
-    const int R = grouped ? hc.n_requests : B;
+    const bool by_voice = hc.by_voice();
+    const bool marks = hc.req_marks != nullptr;  // (with chunks_per_request then: check_marks_call)
+    // one way to lay the output out and pack it: a call without chunks_per_request is R = B single-row requests in hc.format
+    const int R = hc.regions(B), n_words = hc.n_words();
+    const int32_t* words = hc.words();
     KX_HIP(hipSetDevice(device));
     // I/O staging lives in its own arena: ids, styles, frames, noise keys, voice picks, audio, packed audio
     int64_t* d_ids;
@@ -145,10 +147,9 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     MarkRow* d_mrow = nullptr;
     long* d_cum = nullptr;
     float* d_y = nullptr;  // the resampled streams of the requests with a rate code, back to back
-    int *d_vid, *d_rows, *d_kinds, *d_formats = nullptr;
+    int *d_vid, *d_rows, *d_kinds;
     float* d_w;
     void* d_packed;
-    long* d_off = nullptr;
     const int mm = by_voice ? hc.max_mix : 1;
     auto planIO = [&](Arena& A, size_t audio_floats) {
         d_ids = static_cast<int64_t*>(A.alloc((size_t)B * t_stride * 8));
@@ -160,16 +161,11 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         d_rows = A.i(B);
         d_kinds = A.i(B);
         d_w = A.f((size_t)B * mm);
-        if (grouped) {
-            d_req = static_cast<PackReq*>(A.alloc((size_t)R * sizeof(PackReq)));
-            d_cum = static_cast<long*>(A.alloc(((size_t)B + 1) * 8));
-            d_y = A.f(resample_floats_bound(hc.req_formats, hc.n_req_formats, audio_floats));
-            if (marks) d_mrow = static_cast<MarkRow*>(A.alloc((size_t)B * sizeof(MarkRow)));
-        } else {
-            d_formats = A.i(B);
-            d_off = static_cast<long*>(A.alloc((size_t)B * 8));
-        }
-        d_packed = A.alloc(packed_bytes_bound(hc, B, audio_floats, lens));  // compact output: utterances / requests back to back
+        d_req = static_cast<PackReq*>(A.alloc((size_t)R * sizeof(PackReq)));
+        d_cum = static_cast<long*>(A.alloc(((size_t)B + 1) * 8));
+        d_y = A.f(resample_floats_bound(words, n_words, audio_floats));  // (0 floats when no word carries a rate code)
+        if (marks) d_mrow = static_cast<MarkRow*>(A.alloc((size_t)B * sizeof(MarkRow)));
+        d_packed = A.alloc(packed_bytes_bound(hc, B, audio_floats, lens));  // compact output: the requests back to back
         return A.f(audio_floats);
     };
     // worst case length is 50 frames per token; start from a typical 8 and retry once if short
@@ -186,7 +182,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             for (int b = 0; b < B; ++b) rows[b] = lens[b] >= 2 ? lens[b] - 2 : 0;  // tokens before the 0 padding (koko.rs:1161-1166)
             KX_HIP(hipMemcpyAsync(d_vid, hc.voice_ids, (size_t)B * mm * 4, hipMemcpyHostToDevice, stream_));
             KX_HIP(hipMemcpyAsync(d_w, hc.weights, (size_t)B * mm * 4, hipMemcpyHostToDevice, stream_));
-            int* st = stage_ints((size_t)3 * B);  // page-locked: rows | kinds | formats, copied on the model's own stream
+            int* st = stage_ints((size_t)2 * B);  // page-locked: rows | kinds, copied on the model's own stream
             memcpy(st, rows.data(), (size_t)B * 4);
             KX_HIP(hipMemcpyAsync(d_rows, st, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
             if (hc.kinds) {
@@ -210,50 +206,33 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             }
             throw;
         }
-        // frame counts are known (the forward's one host sync): pack the B waveforms back to back on the GPU in the
-        // requested sample format, then ONE asynchronous copy into a page-locked host buffer
-        int64_t total = 0;
+        // frame counts are known (the forward's one host sync): the request table and the rows' sample prefixes, then ONE
+        // launch packs every request of the batch back to back on the GPU, whatever its form (and one before it, the
+        // resampler, when a request asks for another rate), then ONE asynchronous copy into a page-locked host buffer
+        PackPlan& plan = pack_plan_;
+        build_pack_plan(call_.hF.data(), B, hc.chunks_per_request, R, words, n_words, plan);
+        for (int r = 0; r < R; ++r) {
+            out_samples[r] = plan.req[(size_t)r].n_samples;
+            out_bytes[r] = plan.req[(size_t)r].out_bytes;
+        }
+        int64_t total = plan.total_bytes;
         int64_t marks_off = 0, n_marks = 0;
-        if (grouped) {
-            // the request table and the rows' sample prefixes, then ONE launch for every request of the batch, whatever its form
-            // (and one before it, the resampler, when a request asks for another rate)
-            PackPlan& plan = pack_plan_;
-            build_pack_plan(call_.hF.data(), B, hc.chunks_per_request, R, hc.req_formats, hc.n_req_formats, plan);
-            for (int r = 0; r < R; ++r) {
-                out_samples[r] = plan.req[(size_t)r].n_samples;
-                out_bytes[r] = plan.req[(size_t)r].out_bytes;
+        KX_HIP(hipMemcpyAsync(d_req, plan.req.data(), (size_t)R * sizeof(PackReq), hipMemcpyHostToDevice, stream_));
+        KX_HIP(hipMemcpyAsync(d_cum, plan.cum.data(), ((size_t)B + 1) * 8, hipMemcpyHostToDevice, stream_));
+        launch_pack_plan(d_audio, ld, d_req, d_cum, R, plan, d_y, d_packed, stream_);
+        if (marks) {
+            // the token marks of the requests that want them, in a block of their own behind the bodies (8-aligned): one
+            // more launch on this stream, and the call's one copy to the host brings both
+            MarkPlan& mp = mark_plan_;
+            build_mark_plan(plan, lens, hc.chunks_per_request, R, words, n_words, hc.req_marks, mp);
+            for (int r = 0; r < R; ++r) out_n_marks[r] = mp.count[(size_t)r];
+            marks_off = mp.marks_off;
+            n_marks = mp.n_marks;
+            if (n_marks > 0) {
+                KX_HIP(hipMemcpyAsync(d_mrow, mp.row.data(), (size_t)B * sizeof(MarkRow), hipMemcpyHostToDevice, stream_));
+                launch_token_marks(call_.d_dur, call_.dT, d_mrow, B, static_cast<char*>(d_packed) + marks_off, stream_);
+                total = mp.end_bytes();
             }
-            total = plan.total_bytes;
-            KX_HIP(hipMemcpyAsync(d_req, plan.req.data(), (size_t)R * sizeof(PackReq), hipMemcpyHostToDevice, stream_));
-            KX_HIP(hipMemcpyAsync(d_cum, plan.cum.data(), ((size_t)B + 1) * 8, hipMemcpyHostToDevice, stream_));
-            launch_pack_plan(d_audio, ld, d_req, d_cum, R, plan, d_y, d_packed, stream_);
-            if (marks) {
-                // the token marks of the requests that want them, in a block of their own behind the bodies (8-aligned): one
-                // more launch on this stream, and the call's one copy to the host brings both
-                MarkPlan& mp = mark_plan_;
-                build_mark_plan(plan, lens, hc.chunks_per_request, R, hc.req_formats, hc.n_req_formats, hc.req_marks, mp);
-                for (int r = 0; r < R; ++r) out_n_marks[r] = mp.count[(size_t)r];
-                marks_off = mp.marks_off;
-                n_marks = mp.n_marks;
-                if (n_marks > 0) {
-                    KX_HIP(hipMemcpyAsync(d_mrow, mp.row.data(), (size_t)B * sizeof(MarkRow), hipMemcpyHostToDevice, stream_));
-                    launch_token_marks(call_.d_dur, call_.dT, d_mrow, B, static_cast<char*>(d_packed) + marks_off, stream_);
-                    total = mp.end_bytes();
-                }
-            }
-        } else {
-            UttLayout& lay = utt_layout_;
-            utt_layout(call_.hF.data(), B, hc.format, hc.formats, lay);
-            memcpy(out_samples, lay.samples.data(), (size_t)B * 8);
-            memcpy(out_bytes, lay.bytes.data(), (size_t)B * 8);
-            total = lay.total_bytes;
-            KX_HIP(hipMemcpyAsync(d_off, lay.off.data(), (size_t)B * 8, hipMemcpyHostToDevice, stream_));
-            if (hc.formats) {
-                int* st = stage_ints((size_t)3 * B) + 2 * (size_t)B;
-                memcpy(st, hc.formats, (size_t)B * 4);
-                KX_HIP(hipMemcpyAsync(d_formats, st, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
-            }
-            launch_pack_audio(d_audio, ld, call_.dF, B, call_.Fmax, hc.format, d_packed, 0, d_off, stream_, hc.formats ? d_formats : nullptr);
         }
         char* host = static_cast<char*>(host_out_alloc((size_t)(total > 0 ? total : 1)));
         hipError_t e = hipMemcpyAsync(host, d_packed, (size_t)total, hipMemcpyDeviceToHost, stream_);

@@ -589,9 +589,9 @@ int kx_test_pack_requests(int device_id, const float* audio, int B, int64_t audi
                           int64_t* out_bytes, char* err, size_t err_len) {
     return guarded_free(err, err_len, [&] {
         check_device(device_id);
-        KX_REQUIRE(audio && frames && chunks_per_request && formats && out && out_bytes && B > 0 && R > 0, "test_pack_requests: bad argument");
+        KX_REQUIRE(audio && frames && formats && out && out_bytes && B > 0 && R > 0, "test_pack_requests: bad argument");
         for (int b = 0; b < B; ++b) KX_REQUIRE(frames[b] >= 0 && 600L * frames[b] <= audio_ld, "test_pack_requests: a row is shorter than its frames");
-        kx::PackPlan plan;  // the table builder of Model::infer_host_once
+        kx::PackPlan plan;  // the table builder of Model::infer_host_once (null chunks_per_request: R = B single-row requests)
         kx::build_pack_plan(frames, B, chunks_per_request, R, formats, R, plan);
         for (int r = 0; r < R; ++r) out_bytes[r] = plan.req[(size_t)r].out_bytes;
         KX_REQUIRE(plan.total_bytes <= out_cap, "test_pack_requests: out_cap is too small");

@@ -374,9 +374,10 @@ class HipKoko:
         return ids, lens
 
     def infer_voices(self, tokens, voice_ids, weights, speeds=(1.0,), seed: int = 0, flags: int = 0,
-                     fmt: int = 0) -> List[np.ndarray]:
+                     fmt: int = 0, with_samples: bool = False):
         """Style rows are looked up / mixed on the GPU: voice_ids [B, max_mix] (-1 = unused), weights [B, max_mix]
-        (the number after the dot in "af_sky.4+af_nicole.5"); max_mix == 1 is the single-voice copy."""
+        (the number after the dot in "af_sky.4+af_nicole.5"); max_mix == 1 is the single-voice copy.  with_samples: also the
+        library's own sample count of every utterance (out_samples), as a second list."""
         ids, lens = self._ids_lens(tokens)
         B = len(tokens)
         v = np.ascontiguousarray(np.asarray(voice_ids, dtype=np.int32).reshape(B, -1))
@@ -387,9 +388,10 @@ class HipKoko:
         self._check(self._lib.kx_infer_voices(self._h, _ptr(ids), ids.shape[1], _ptr(lens), B, _ptr(v), _ptr(w),
                                               v.shape[1], _ptr(sp), sp.shape[0], seed, flags, fmt, C.byref(out),
                                               _ptr(nbytes), _ptr(nsamp)))
-        return self._unpack(out, nbytes, nsamp, B, fmt)
+        res = self._unpack(out, nbytes, nsamp, B, fmt)
+        return (res, [int(n) for n in nsamp]) if with_samples else res
 
-    def infer_packed(self, tokens, styles, speeds=(1.0,), seed: int = 0, flags: int = 0, fmt: int = 0):
+    def infer_packed(self, tokens, styles, speeds=(1.0,), seed: int = 0, flags: int = 0, fmt: int = 0, with_samples: bool = False):
         ids, lens = self._ids_lens(tokens)
         B = len(tokens)
         st = _f32(np.asarray(styles, dtype=np.float32).reshape(B, STYLE_DIM))
@@ -398,7 +400,8 @@ class HipKoko:
         nbytes, nsamp = np.zeros(B, np.int64), np.zeros(B, np.int64)
         self._check(self._lib.kx_infer_packed(self._h, _ptr(ids), ids.shape[1], _ptr(lens), B, _ptr(st), _ptr(sp),
                                               sp.shape[0], seed, flags, fmt, C.byref(out), _ptr(nbytes), _ptr(nsamp)))
-        return self._unpack(out, nbytes, nsamp, B, fmt)
+        res = self._unpack(out, nbytes, nsamp, B, fmt)
+        return (res, [int(n) for n in nsamp]) if with_samples else res
 
     def infer_requests(self, tokens, chunks_per_request, styles=None, voice_ids=None, weights=None, speeds=(1.0,), seed: int = 0,
                        flags: int = 0, fmt=0, with_samples: bool = False):
@@ -971,14 +974,19 @@ def harmonic_source(f0, lin_w, lin_b, seed=0, utt_base=0, noise_off=False, devic
 def pack_requests(audio, frames, chunks_per_request, formats, device=0):
     """The request packer alone (kx_test_pack_requests): audio [B, audio_ld] with row b valid for 600 * frames[b] samples,
     request r = chunks_per_request[r] consecutive rows in the format word formats[r] (the resampler runs first where a word
-    has a rate code).  Returns the R regions as bytes."""
+    has a rate code).  chunks_per_request = None: every row a request of its own (a null pointer to the plan builder, as the
+    per-utterance entries of the model pass it); one word in `formats` then serves all rows.  Returns the R regions as bytes."""
     lib = load_test_library()
     audio = _f32(audio)
     B, ld = audio.shape
     fr = np.ascontiguousarray(frames, dtype=np.int32)
-    cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32)
     fm = np.ascontiguousarray(formats, dtype=np.int32)
-    R = cpr.shape[0]
+    if chunks_per_request is None:
+        cpr, R = None, B
+        fm = np.repeat(fm, B) if fm.shape == (1,) else fm
+    else:
+        cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32)
+        R = cpr.shape[0]
     assert fr.shape == (B,) and fm.shape == (R,)
     cap = 16 * 600 * int(fr.sum()) + 64 * R  # (stereo f32 at 48 kHz: 16 bytes per sample of the model)
     out = np.zeros(cap, dtype=np.uint8)

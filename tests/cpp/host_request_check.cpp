@@ -1,7 +1,7 @@
 // Driver for the argument checks and the output layout of the inference entries (kokorox_amd/csrc/host_request.cpp), built by
 // tests/test_host_request_cpu.py with g++ -fsanitize=address,undefined.  No device, nothing loaded into python.
 //   host_request_check refusals   one line per case: "<entry>.<case>\t<code>\t<message>" or "<entry>.<case>\taccepted"
-//   host_request_check layout     per-utterance layout, request plans and the packed buffer's bound, checked here against
+//   host_request_check layout     the per-utterance calls' plans, request plans and the packed buffer's bound, checked here against
 //                                 sums written out independently; prints what it covered, exits 1 at the first difference
 #include <cstdint>
 #include <cstdio>
@@ -39,7 +39,7 @@ struct HostArgs {
     std::vector<int32_t> lens{3, 8, 2};
     std::vector<float> speeds{1.f};
     std::vector<float> styles = std::vector<float>(3 * 256, 0.f);
-    std::vector<int32_t> voice_ids, kinds, formats, cpr, req_formats;
+    std::vector<int32_t> voice_ids, kinds, cpr, req_formats;
     std::vector<float> weights;
     std::vector<uint64_t> seeds{1, 2, 3};
     std::vector<uint32_t> index{0, 1, 2};
@@ -134,7 +134,6 @@ static void refusals() {
     host_case("id_minus_1", [](A& a) { a.ids[8 + 3] = -1; });
     host_case("id_n_vocab", [](A& a) { a.ids[2 * 8 + 1] = A::N_VOCAB; });
     host_case("kind_3", [](A& a) { a.voices(1, {0, 1, 2}); a.hc.styles = a.styles.data(); a.kinds = {0, 3, 1}; a.hc.kinds = a.kinds.data(); });
-    host_case("format_3_per_utterance", [](A& a) { a.formats = {0, 1, 3}; a.hc.formats = a.formats.data(); });
     host_case("voice_row_of_one_token", [](A& a) { a.voices(1, {0, 1, 2}); a.lens[2] = 1; });
     host_case("voice_id_n_voices", [](A& a) { a.voices(2, {0, 1, 2, A::N_VOICES, 3, -1}); });
     host_case("all_voice_ids_negative", [](A& a) { a.voices(2, {0, 1, -1, -1, 3, -1}); });
@@ -163,8 +162,13 @@ static void refusals() {
         a.hc.styles = a.styles.data();
         a.kinds = {0, 1, 2};
         a.hc.kinds = a.kinds.data();
-        a.formats = {0, 1, 2};
-        a.hc.formats = a.formats.data();
+    });
+    host_case("ok_ungrouped_each_form", [](A& a) {
+        for (int form = 0; form <= 2; ++form) {
+            a.hc.format = form;
+            a.result = reinterpret_cast<void*>(0x10);
+            a.check();
+        }
     });
     host_case("ok_grouped_shared_format", [](A& a) { a.grouped({1, 2}, {4}); a.hc.format = 9; /* (not used then) */ });
     host_case("ok_grouped_formats_per_request", [](A& a) { a.grouped({2, 1}, {3, 4}); });
@@ -197,33 +201,53 @@ static long form_bytes(int form, long n) {  // include/kokorox_hip.h, KX_PACK_*
 }
 
 static void utterance_layout() {
+    // what kx_infer / kx_infer_packed / kx_infer_voices ask of the plan builder: null chunks, one shared form 0..2, R = B
     const int B = 5;
     const int frames[B] = {1, 7, 422, 1, 3};
     static const int width[3] = {4, 8, 2};
-    const int mixed[B] = {0, 1, 2, 2, 1};
+    const int mixed[B] = {0, 1, 2, 2, 1};  // (as a grouped call of single-row requests: the dispatcher's mixed batches)
+    const int ones[B] = {1, 1, 1, 1, 1};
     for (int c = 0; c < 4; ++c) {
-        kx::UttLayout L;
-        L.total_bytes = 77;  // (stale contents must not survive)
-        L.off.assign(9, 5);
-        kx::utt_layout(frames, B, c < 3 ? c : 0, c < 3 ? nullptr : mixed, L);
-        CHECK(L.sample_bytes.size() == (size_t)B && L.samples.size() == (size_t)B && L.bytes.size() == (size_t)B && L.off.size() == (size_t)B);
-        int64_t sum = 0;
-        int widest = 0;
+        kx::PackPlan plan;
+        plan.total_bytes = 77;  // (stale contents must not survive)
+        plan.max_units = 77;
+        plan.req.resize(9);
+        plan.cum.assign(3, 5);
+        const int form = c < 3 ? c : 0;
         kx::HostCall hc;
-        hc.format = c < 3 ? c : 0;
-        hc.formats = c < 3 ? nullptr : mixed;
+        hc.format = form;
+        if (c == 3) {
+            hc.chunks_per_request = ones;
+            hc.n_requests = B;
+            hc.req_formats = mixed;
+            hc.n_req_formats = B;
+        }
+        CHECK(hc.regions(B) == B && hc.n_words() == (c < 3 ? 1 : B));
+        kx::build_pack_plan(frames, B, hc.chunks_per_request, B, hc.words(), hc.n_words(), plan);
+        CHECK(plan.req.size() == (size_t)B && plan.cum.size() == (size_t)B + 1);
+        long sum = 0, n = 0;
         for (int b = 0; b < B; ++b) {
             const int w = width[c < 3 ? c : mixed[b]];
-            CHECK(L.sample_bytes[(size_t)b] == w);
-            CHECK(L.samples[(size_t)b] == 600 * (int64_t)frames[b]);
-            CHECK(L.bytes[(size_t)b] == 600 * (int64_t)frames[b] * w);
-            CHECK(L.off[(size_t)b] == sum);
-            sum += L.bytes[(size_t)b];
-            widest = w > widest ? w : widest;
+            const kx::PackReq& q = plan.req[(size_t)b];
+            CHECK(q.first_row == b && q.n_rows == 1 && q.form == (c < 3 ? c : mixed[b]) && q.pad_ == 0);
+            CHECK(q.n_samples == 600L * frames[b]);
+            CHECK(q.out_bytes == 600L * frames[b] * w);
+            CHECK(q.out_off == sum);
+            sum += q.out_bytes;
+            n += 600L * frames[b];
         }
-        CHECK(L.total_bytes == sum);
-        // before the forward the packed buffer is sized for every sample in the widest form of the batch
-        CHECK(kx::packed_bytes_bound(hc, B, 1000) == (size_t)1000 * (size_t)widest);
+        CHECK(plan.total_bytes == sum && plan.y_floats == 0);
+        // before the forward the packed buffer is sized by the requests' bound over the call's words, and holds the plan:
+        // for these frames, and for B rows of one frame each
+        const int* words = c < 3 ? &form : mixed;
+        const int n_words = c < 3 ? 1 : B;
+        CHECK(kx::packed_bytes_bound(hc, B, 1000) == kx::pack_requests_bound(words, n_words, B, 1000));
+        CHECK(kx::packed_bytes_bound(hc, B, (size_t)n) == kx::pack_requests_bound(words, n_words, B, (size_t)n));
+        CHECK(kx::packed_bytes_bound(hc, B, (size_t)n) >= (size_t)plan.total_bytes);
+        kx::build_pack_plan(ones, B, hc.chunks_per_request, B, hc.words(), hc.n_words(), plan);
+        CHECK(plan.total_bytes == (c < 3 ? 600L * B * width[c] : 600L * (4 + 8 + 2 + 2 + 8)));
+        CHECK(kx::packed_bytes_bound(hc, B, (size_t)600 * B) >= (size_t)plan.total_bytes);
+        CHECK(kx::resample_floats_bound(hc.words(), hc.n_words(), 1000) == 0);  // (24 kHz: nothing to resample)
     }
     printf("utterance layout: 4 assignments of forms over %d utterances\n", B);
 }

@@ -130,7 +130,9 @@ void bounds() {
     // the ungrouped entries do not know marks: their bound does not move
     kx::HostCall hc;
     hc.format = 1;
-    CHECK(kx::packed_bytes_bound(hc, 3, 1800) == 1800 * 8);
+    const int stereo = 1, three[3] = {1, 1, 1};
+    CHECK(kx::packed_bytes_bound(hc, 3, 1800) == kx::pack_requests_bound(&stereo, 1, 3, 1800));
+    CHECK(kx::packed_bytes_bound(hc, 3, 1800, three) == kx::packed_bytes_bound(hc, 3, 1800));
     printf("bounds: %d batches of one frame per token\n", n);
 }
 

@@ -93,6 +93,22 @@ def test_hook_packs_every_form_and_grouping(grouping):
                 _expect_and_compare(got[r], streams[r], forms[r])
 
 
+def test_hook_null_grouping_is_one_request_per_row():
+    """chunks_per_request = null is what kx_infer / kx_infer_packed / kx_infer_voices hand to the plan builder: R = B single-row
+    requests sharing one form 0..2.  Row 0 of one frame, rows of unequal length (workgroups past a short region exit) and the
+    last row, against the numpy mirrors and against the same rows grouped explicitly."""
+    from kokorox_amd import hip_koko as hk
+    B = len(FRAMES)
+    for rot in range(0, 15, 3):
+        a = _slab(rot)
+        for f in (0, 1, 2):
+            got = hk.pack_requests(a, FRAMES, None, [f])
+            assert len(got) == B
+            for b in range(B):
+                _expect_and_compare(got[b], a[b, : 600 * FRAMES[b]], f)
+            assert got == hk.pack_requests(a, FRAMES, [1] * B, [f] * B)
+
+
 def test_hook_known_answer_of_the_fixture():
     from kokorox_amd import hip_koko as hk
     with open(os.path.join(ROOT, "tests", "golden", "wire_formats.json"), encoding="utf-8") as f:
@@ -289,6 +305,53 @@ def _dispatcher_scenario(model):
 
 def test_dispatcher_requests_equal_their_solo_runs(hip_model):
     _dispatcher_scenario(hip_model)
+
+
+def test_dispatcher_single_row_requests_beside_each_other_and_beside_chunks(hip_model):
+    """The single-utterance traffic in forms 0, 1, 2 goes through the same packer as every other request: one batch of three
+    such requests (submit_ex), then three more (submit_request) beside a two-chunk form-4 request.  Every result equals its
+    solo run -- kx_infer_packed for the single rows, kx_infer_requests for the chunks -- byte for byte."""
+    from kokorox_amd import hip_koko as hk
+    from kokorox_amd import weights as W
+    toks = _chunks()
+    rows = [W.synthetic_voices(1)[0, len(t) - 2, 0] for t in toks]
+    hip_model.set_utterance_base(0)
+    hip_model.set_pinned_durations(None)
+    d = hk.Dispatcher([hip_model], max_batch=8, max_wait_us=100000)
+    first, second, errs = [None] * 3, [None] * 4, []
+
+    def one(i):
+        try:
+            first[i] = d.submit_ex(toks[i], style=rows[i], seed=800 + i, fmt=i)
+        except Exception as e:  # pragma: no cover
+            errs.append(e)
+
+    def two(i):
+        try:
+            if i < 3:
+                second[i] = d.submit_request([toks[i]], styles=[rows[i]], seed=810 + i, fmt=(i + 1) % 3)
+            else:
+                second[i] = d.submit_request(toks[3:5], styles=rows[3:5], seed=820, fmt=4)
+        except Exception as e:  # pragma: no cover
+            errs.append(e)
+
+    try:
+        for target, n in ((one, 3), (two, 4)):
+            th = [threading.Thread(target=target, args=(i,)) for i in range(n)]
+            for t in th:
+                t.start()
+            for t in th:
+                t.join(timeout=300)
+        st = d.stats()
+    finally:
+        d.close()
+    assert not errs, errs
+    for i in range(3):
+        _same(first[i], hip_model.infer_packed([toks[i]], [rows[i]], [1.0], seed=800 + i, fmt=i)[0])
+        _same(second[i], hip_model.infer_packed([toks[i]], [rows[i]], [1.0], seed=810 + i, fmt=(i + 1) % 3)[0])
+    _same(second[3], hip_model.infer_requests(toks[3:5], [2], styles=rows[3:5], speeds=[1.0], seed=820, fmt=4)[0])
+    # (as above, this rests on the threads' submits reaching the queue within max_wait_us of each other)
+    assert st["requests"] == 7 and st["batches"] < st["requests"], st
 
 
 def test_dispatcher_copy_out_path_in_a_fresh_process():

@@ -1,5 +1,5 @@
 """CPU: what a call is refused for before it touches the device, and where its output bytes go
-(kokorox_amd/csrc/host_request.cpp: check_host_call, check_device_call, utt_layout, build_pack_plan, pack_requests_bound,
+(kokorox_amd/csrc/host_request.cpp: check_host_call, check_device_call, build_pack_plan, pack_requests_bound,
 packed_bytes_bound).
 
 Model::infer_host_once and Model::infer_device take their argument checks and the layout of the compact output from that unit,
@@ -39,7 +39,7 @@ HOST_REFUSALS = {
     "voices_without_table": MIX, "voices_without_weights": MIX, "max_mix_0": MIX, "max_mix_17": MIX,
     "lens_0": TOKENS, "lens_513": TOKENS, "lens_above_stride": TOKENS,
     "id_minus_1": TOKEN_ID, "id_n_vocab": TOKEN_ID,
-    "kind_3": KIND_FORMAT, "format_3_per_utterance": KIND_FORMAT,
+    "kind_3": KIND_FORMAT,
     "voice_row_of_one_token": "infer: voice rows need the two 0 pads (row = tokens - 2)",
     "voice_id_n_voices": "infer: voice id outside the table",
     "all_voice_ids_negative": NO_VOICE, "kind_1_negative_first_id": NO_VOICE,
@@ -51,7 +51,7 @@ BAD_GROUPINGS = {
     "grouped_1_2_formats_0_1_2": "infer: requests need 1 or R output formats",
 }
 HOST_ACCEPTED = ["ok_style_rows", "ok_style_rows_seeds_and_index", "ok_single_voice", "ok_mix", "ok_per_utterance_kinds",
-                 "ok_grouped_shared_format", "ok_grouped_formats_per_request"]
+                 "ok_ungrouped_each_form", "ok_grouped_shared_format", "ok_grouped_formats_per_request"]
 DEVICE_REFUSALS = {
     "B_0": BATCH, "B_4097": BATCH,
     "null_ids": NULL_ARG, "null_styles": NULL_ARG,
@@ -118,7 +118,8 @@ def test_device_entry_refusals_keep_their_own_wording(outcomes):
 
 
 def test_layout_request_plans_and_the_packed_bound(driver):
-    """Per-utterance layout (B = 5, frames 1 7 422 1 3, forms all 0 / 1 / 2 and mixed), the request plan of every composition
+    """The plan of a per-utterance call (B = 5 single-row requests, frames 1 7 422 1 3, forms all 0 / 1 / 2 through a null
+    grouping and mixed through a grouped call), the request plan of every composition
     of 6 rows with each form shared and one mixed assignment, the bound of 1..64 one-frame requests in every form, and the
     sample count from which a 16-bit WAV file is refused: the driver compares with sums written out on its own."""
     out = driver("layout")
