@@ -387,6 +387,54 @@ int kx_infer_requests_marks(kx_model* m, const int64_t* ids, int64_t t_stride, c
                             const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
                             int64_t** out_marks, int64_t* out_n_marks);
 
+/* ---- joins: shaping the seams of a request on the GPU ------------------------------------------------------------------------
+ * Every chunk carries a 0 pad token at both ends and the duration head gives each pad some frames: a request of several chunks
+ * has a lead-in, a tail and inner silences whose lengths the model chose.  A join spec trims those pad spans, puts a pause of
+ * the caller's choice between consecutive chunks and fades the trimmed edges, before the request is resampled and packed.
+ * Everything is defined at 24 000 Hz, before resampling: 1 ms is 24 samples.
+ *
+ * Chunk c (row b) has T tokens, used durations d[0..T) (the ones the marks use: after pinning, after the speed, after the
+ * clamp), F = sum of d, valid samples x[0..600 F).
+ *   Which edges are trimmed.  The head edge of a row is SELECTED if the row has T >= 3 and either (it is the request's first
+ *   row and HEAD is set) or (it is not the first row and INNER is set); the tail edge symmetrically, with TAIL and INNER.  Rows
+ *   with T < 3 are never trimmed: their one or two tokens are both pads, a lead span and a tail span would overlap.
+ *   Per row, with k = 24 keep_ms:  skip = max(0, 600 d[0] - k) if the head is selected, else 0;
+ *   cut = max(0, 600 d[T-1] - k) if the tail is selected, else 0;  keep = 600 F - skip - cut (>= 600: the middle tokens have
+ *   d >= 1);  gap = 24 pause_ms for every row but the request's last, else 0.
+ *   Fades, with n = 24 fade_ms (2 n <= 576 < 600: the two never overlap).  If the head is selected and n > 0, sample i < n of
+ *   the kept segment is f32(f64(x) * (f64(2 i + 1) / f64(2 n))); if the tail is selected and n > 0, sample keep - 1 - i, i < n,
+ *   gets the same expression: one float64 division, one float64 product, one round-to-nearest-even conversion.  A NaN stays a
+ *   NaN.
+ *   The request's stream: for each chunk in order, x[skip .. skip + keep) with its fades, then gap zeros (+0.0f).  Its length
+ *   is S' = sum of (keep + gap); every term is a multiple of 24, so S' L / M is exact at all four rates.  The stream is then
+ *   resampled as a whole -- the zeros and the cuts are invisible to the filter, exactly as chunk boundaries are -- and packed
+ *   in its form exactly as a plain request: the WAV headers, the `=` count, out_samples[r] = S' L / M and the 4 GiB refusal of
+ *   form 4 all follow S'.
+ *   Marks of a joined request.  With P_c = sum over c' < c of (keep_c' + gap_c') and u = 600 x sum over t' < t of d_c[t']:
+ *       m_c[t] = (P_c + clamp(u - skip_c, 0, keep_c)) L / M,   t = 0 .. T_c
+ *   A cut part of a pad collapses onto the edge; m_c[T_c] <= m_{c+1}[0], the difference is the pause and belongs to no token;
+ *   the last value equals out_samples[r]; all values are multiples of 24 before scaling, so they are exact integers.
+ *   A spec of all zeros gives the bytes and marks of kx_infer_requests_marks. */
+#define KX_JOIN_TRIM_HEAD  1u  /* the request's lead-in: the first pad of its first chunk            */
+#define KX_JOIN_TRIM_TAIL  2u  /* the request's tail: the last pad of its last chunk                 */
+#define KX_JOIN_TRIM_INNER 4u  /* at every boundary between two chunks: the last pad of the earlier
+                                  chunk and the first pad of the later one                           */
+typedef struct kx_join {
+    uint32_t flags;     /* the three bits above, every other bit zero            */
+    int32_t  keep_ms;   /* 0..1000: of a trimmed pad span at most this much stays */
+    int32_t  pause_ms;  /* 0..5000: zeros inserted between consecutive chunks     */
+    int32_t  fade_ms;   /* 0..12: linear fade at every trimmed edge               */
+} kx_join;
+/* kx_infer_requests_marks with a join spec per request: joins [n_join], n_join = 1 (shared) or R.  out_marks / out_n_marks may
+ * BOTH be NULL (no marks); exactly one NULL: "infer: null marks argument".  Refused with KX_ERR_INVALID before any device work:
+ * a null `joins` ("infer: null join argument"), n_join not 1 or R ("infer: bad join count"), a stray flag bit or a field outside
+ * its range ("infer: bad join"); everything kx_infer_requests refuses is refused the same way with the same text. */
+int kx_infer_requests_joined(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                             const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                             const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                             const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                             int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join);
+
 /* ---- request dispatcher ----------------------------------------------------
  * Replaces the reference's one-request-at-a-time `Mutex<Session>` (kokorox/src/onn/ort_koko.rs:78; callers
  * kokorox-openai/src/lib.rs:370-439, kokorox-websocket/src/lib.rs:657-668).  Any number of threads submit
@@ -449,6 +497,16 @@ int kx_dispatcher_submit_request_marks(kx_dispatcher* d, const int64_t* ids, con
                                        float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
                                        int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, char* err,
                                        size_t err_len);
+/* kx_dispatcher_submit_request_marks with the request's join spec (see "joins" above; one request, one spec).  out_marks and
+ * out_n_marks are both NULL (no marks) or both set, else "dispatcher_submit_request: null marks argument"; a null `join`, a
+ * stray flag bit or a field outside its range: "dispatcher_submit_request: bad join".  Joined and plain requests, with and
+ * without marks, share batches; body and marks equal those of kx_infer_requests_joined (R = 1, same seed, utterance base 0)
+ * whatever the request was batched with. */
+int kx_dispatcher_submit_request_joined(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                        const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
+                                        float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
+                                        int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
+                                        char* err, size_t err_len);
 /* n_requests counts requests, max_batch_seen the largest batch in ROWS (a request of n chunks is n rows). */
 int kx_dispatcher_stats(kx_dispatcher* d, int64_t* n_requests, int64_t* n_batches, int64_t* max_batch_seen);
 /* batches each model (worker) has run so far: per_model[n_models] */

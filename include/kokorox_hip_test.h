@@ -118,6 +118,18 @@ int kx_test_token_marks(int device_id, const int32_t* dur, const int32_t* lens, 
                         const int32_t* formats, const uint8_t* want, int64_t* out_marks, int64_t out_cap, int64_t* out_n_marks,
                         char* err, size_t err_len);
 
+/* Joined requests alone (include/kokorox_hip.h, "joins"): the joined form of the packer, the resampler and the marks kernel
+ * through build_join_plan / build_mark_plan and launch_pack_plan, as the model runs them.  audio [B, audio_ld] as
+ * kx_test_pack_requests takes it, or NULL for the marks alone (no audio is read, out may be NULL with out_cap 0); dur [B][512]
+ * and lens [B] as kx_test_token_marks takes them: frames[b] = the sum of the row's valid durations, its edge durations dur[b][0]
+ * and dur[b][lens[b] - 1], all derived on the host.  formats [R], joins [R], want [R] = which requests get marks (NULL = none).
+ * out receives the R bodies back to back (out_cap bytes available), out_bytes[r] / out_samples[r] their sizes, out_marks the
+ * wanted requests' marks back to back (marks_cap values available), out_n_marks[r] their counts. */
+int kx_test_join_requests(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* dur, const int32_t* lens,
+                          const int32_t* chunks_per_request, int R, const int32_t* formats, const kx_join* joins,
+                          const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes, int64_t* out_samples,
+                          int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks, char* err, size_t err_len);
+
 /* Fault injection for the two-CU LSTM recurrence (process-wide, test only): nth > 0 makes the nth following launch of
  * the pair kernel, and every later one, lose the second half of each pair and poll with a short limit, so the call it
  * belongs to must fail with KX_ERR_DEVICE (the bounded wait's error path) and the model must fall back to the one-CU

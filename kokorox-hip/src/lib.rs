@@ -43,6 +43,21 @@ pub const KX_PACK_RATE_8000: c_int = 0x100;
 pub const KX_PACK_RATE_16000: c_int = 0x200;
 pub const KX_PACK_RATE_48000: c_int = 0x300;
 pub const KX_RESAMPLE_MAX_TAPS: usize = 145;
+/// Join flags ("joins" in kokorox_hip.h): trim the request's lead-in, its tail, the pad spans at every boundary between chunks.
+pub const KX_JOIN_TRIM_HEAD: u32 = 1;
+pub const KX_JOIN_TRIM_TAIL: u32 = 2;
+pub const KX_JOIN_TRIM_INNER: u32 = 4;
+
+/// How a request's seams are shaped on the GPU (`kx_join`): of a trimmed pad span at most `keep_ms` stays (0..1000),
+/// `pause_ms` of zeros between consecutive chunks (0..5000), a linear fade of `fade_ms` at every trimmed edge (0..12).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct KxJoin {
+    pub flags: u32,
+    pub keep_ms: i32,
+    pub pause_ms: i32,
+    pub fade_ms: i32,
+}
 
 #[repr(C)]
 pub struct KxModel {
@@ -116,6 +131,12 @@ extern "C" {
                                weights: *const f32, max_mix: c_int, speeds: *const f32, n_speed: c_int, seed: u64, flags: u32,
                                formats: *const i32, n_format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
                                out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64) -> c_int;
+    fn kx_infer_requests_joined(m: *mut KxModel, ids: *const i64, t_stride: i64, lens: *const i32, b: c_int,
+                                chunks_per_request: *const i32, r: c_int, styles: *const f32, voice_ids: *const i32,
+                                weights: *const f32, max_mix: c_int, speeds: *const f32, n_speed: c_int, seed: u64, flags: u32,
+                                formats: *const i32, n_format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                                out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64, joins: *const KxJoin,
+                                n_join: c_int) -> c_int;
     fn kx_dispatcher_create(models: *mut *mut KxModel, n_models: c_int, max_batch: c_int, max_wait_us: c_int,
                             err: *mut c_char, err_len: usize) -> *mut KxDispatcher;
     fn kx_dispatcher_create_warm(models: *mut *mut KxModel, n_models: c_int, max_batch: c_int, max_wait_us: c_int,
@@ -136,6 +157,11 @@ extern "C" {
                                           speed: f32, seed: u64, format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
                                           out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64,
                                           err: *mut c_char, err_len: usize) -> c_int;
+    fn kx_dispatcher_submit_request_joined(d: *mut KxDispatcher, ids: *const i64, chunk_tokens: *const i32, n_chunks: c_int,
+                                           styles: *const f32, voice_ids: *const i32, weights: *const f32, n_mix: c_int,
+                                           speed: f32, seed: u64, format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                                           out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64,
+                                           join: *const KxJoin, err: *mut c_char, err_len: usize) -> c_int;
     fn kx_dispatcher_stats(d: *mut KxDispatcher, n_requests: *mut i64, n_batches: *mut i64,
                            max_batch_seen: *mut i64) -> c_int;
     fn kx_dispatcher_failures(d: *mut KxDispatcher, n_replayed: *mut i64, n_retried: *mut i64) -> c_int;
@@ -472,6 +498,40 @@ impl HipKoko {
         Ok(res)
     }
 
+    /// `infer_requests_marks` with the seams of every request shaped on the GPU ("joins" in kokorox_hip.h): `joins` holds one
+    /// spec for all requests or one per request.
+    pub fn infer_requests_joined(&self, tokens: &[Vec<i64>], chunks_per_request: &[i32], styles: &[Vec<f32>], speeds: &[f32],
+                                 seed: u64, formats: &[c_int], joins: &[KxJoin]) -> Result<Vec<(Vec<u8>, Vec<i64>)>, Box<dyn Error>> {
+        if tokens.is_empty() || styles.len() != tokens.len() || styles.iter().any(|s| s.len() != KX_STYLE_DIM) {
+            return Err("infer_requests: one style row of 256 floats per chunk is required".into());
+        }
+        let (b, r) = (tokens.len(), chunks_per_request.len());
+        let (ids, lens, stride) = Self::flatten(tokens);
+        let st: Vec<f32> = styles.iter().flatten().copied().collect();
+        let mut out: *mut c_void = ptr::null_mut();
+        let mut mk: *mut i64 = ptr::null_mut();
+        let (mut nbytes, mut nsamp, mut nmarks) = (vec![0i64; r.max(1)], vec![0i64; r.max(1)], vec![0i64; r.max(1)]);
+        let rc = unsafe {
+            kx_infer_requests_joined(self.h, ids.as_ptr(), stride as i64, lens.as_ptr(), b as c_int, chunks_per_request.as_ptr(),
+                                     r as c_int, st.as_ptr(), ptr::null(), ptr::null(), 0, speeds.as_ptr(), speeds.len() as c_int,
+                                     seed, 0, formats.as_ptr(), formats.len() as c_int, &mut out, nbytes.as_mut_ptr(),
+                                     nsamp.as_mut_ptr(), &mut mk, nmarks.as_mut_ptr(), joins.as_ptr(), joins.len() as c_int)
+        };
+        self.check(rc)?;
+        let mut res = Vec::with_capacity(r);
+        let (mut at, mut mat) = (0usize, 0usize);
+        for i in 0..r {
+            // (the marks live in the buffer of `out`: copied before it is released)
+            let body = unsafe { std::slice::from_raw_parts((out as *const u8).add(at), nbytes[i] as usize) }.to_vec();
+            let marks = unsafe { std::slice::from_raw_parts((mk as *const i64).add(mat), nmarks[i] as usize) }.to_vec();
+            at += nbytes[i] as usize;
+            mat += nmarks[i] as usize;
+            res.push((body, marks));
+        }
+        unsafe { kx_free_packed(out) };
+        Ok(res)
+    }
+
     /// Raw device-pointer form (inputs and output stay in HBM).
     ///
     /// # Safety
@@ -755,6 +815,33 @@ impl HipKokoDispatcher {
             kx_dispatcher_submit_request_marks(self.d, ids.as_ptr(), lens.as_ptr(), lens.len() as c_int, styles.as_ptr(), ptr::null(),
                                                ptr::null(), 0, speed, seed, format, &mut out, &mut nb, &mut ns, &mut mk, &mut nm,
                                                err.as_mut_ptr(), err.len())
+        };
+        if rc != KX_OK {
+            return Err(format!("kokorox_hip error {}: {}", rc, cstr_buf(&err)).into());
+        }
+        let v = unsafe { std::slice::from_raw_parts(out as *const u8, nb as usize) }.to_vec();
+        // (inside the allocation of `out`: copied before it is released)
+        let marks = unsafe { std::slice::from_raw_parts(mk as *const i64, nm as usize) }.to_vec();
+        unsafe { kx_free_packed(out) };
+        Ok((v, marks, ns))
+    }
+
+    /// `submit_request_marks` with the request's join spec ("joins" in kokorox_hip.h): body, marks, sample count.
+    pub fn submit_request_joined(&self, chunks: &[Vec<i64>], styles: &[f32], speed: f32, seed: u64, format: i32, join: KxJoin)
+                                 -> Result<(Vec<u8>, Vec<i64>, i64), Box<dyn Error>> {
+        if styles.len() != KX_STYLE_DIM * chunks.len() {
+            return Err("submit_request: one style row of 256 floats per chunk is required".into());
+        }
+        let ids: Vec<i64> = chunks.iter().flatten().copied().collect();
+        let lens: Vec<i32> = chunks.iter().map(|c| c.len() as i32).collect();
+        let mut out: *mut c_void = ptr::null_mut();
+        let mut mk: *mut i64 = ptr::null_mut();
+        let (mut nb, mut ns, mut nm) = (0i64, 0i64, 0i64);
+        let mut err = vec![0 as c_char; 256];
+        let rc = unsafe {
+            kx_dispatcher_submit_request_joined(self.d, ids.as_ptr(), lens.as_ptr(), lens.len() as c_int, styles.as_ptr(), ptr::null(),
+                                                ptr::null(), 0, speed, seed, format, &mut out, &mut nb, &mut ns, &mut mk, &mut nm,
+                                                &join, err.as_mut_ptr(), err.len())
         };
         if rc != KX_OK {
             return Err(format!("kokorox_hip error {}: {}", rc, cstr_buf(&err)).into());

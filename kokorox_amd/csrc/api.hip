@@ -281,12 +281,20 @@ int kx_infer_packed(kx_model* m, const int64_t* ids, int64_t t_stride, const int
     });
 }
 
-// kx_infer_requests and kx_infer_requests_marks are one call: the first asks for no marks
+static_assert(sizeof(kx_join) == sizeof(kx::JoinSpec) && offsetof(kx_join, flags) == offsetof(kx::JoinSpec, flags) &&
+                  offsetof(kx_join, keep_ms) == offsetof(kx::JoinSpec, keep_ms) && offsetof(kx_join, pause_ms) == offsetof(kx::JoinSpec, pause_ms) &&
+                  offsetof(kx_join, fade_ms) == offsetof(kx::JoinSpec, fade_ms) && KX_JOIN_TRIM_HEAD == kx::JOIN_TRIM_HEAD &&
+                  KX_JOIN_TRIM_TAIL == kx::JOIN_TRIM_TAIL && KX_JOIN_TRIM_INNER == kx::JOIN_TRIM_INNER,
+              "kx_join is the layout of kx::JoinSpec");
+
+// kx_infer_requests, kx_infer_requests_marks and kx_infer_requests_joined are one call: the first asks for no marks, the first
+// two for no joins
 static int infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
                           const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
                           const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
                           const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
-                          bool marks, int64_t** out_marks, int64_t* out_n_marks) {
+                          bool marks, int64_t** out_marks, int64_t* out_n_marks, bool joined = false, const kx_join* joins = nullptr,
+                          int n_join = 0) {
     return guarded(m, [&](Model& M) {
         KX_REQUIRE(chunks_per_request && formats && R >= 1, "infer_requests: null argument");
         KX_REQUIRE((styles != nullptr) != (voice_ids != nullptr), "infer_requests: give the style rows OR voice ids, not both");
@@ -304,6 +312,11 @@ static int infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, con
         if (marks) {  // (every request of the call)
             want.assign((size_t)R, 1);
             hc.req_marks = want.data();
+        }
+        if (joined) {  // (a null `joins` is refused with the call's other arguments: check_join_call)
+            hc.join_call = true;
+            hc.req_joins = reinterpret_cast<const kx::JoinSpec*>(joins);
+            hc.n_req_joins = n_join;
         }
         M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks);
     });
@@ -324,6 +337,16 @@ int kx_infer_requests_marks(kx_model* m, const int64_t* ids, int64_t t_stride, c
                             int64_t** out_marks, int64_t* out_n_marks) {
     return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
                           flags, formats, n_format, out, out_bytes, out_samples, true, out_marks, out_n_marks);
+}
+
+int kx_infer_requests_joined(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                             const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                             const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                             const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                             int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join) {
+    return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
+                          flags, formats, n_format, out, out_bytes, out_samples, out_marks || out_n_marks, out_marks, out_n_marks, true,
+                          joins, n_join);
 }
 
 int kx_infer_device(kx_model* m, const int64_t* d_ids, int64_t t_stride, const int32_t* lens_host, int B,

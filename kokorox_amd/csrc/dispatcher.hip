@@ -35,9 +35,10 @@ struct ModelBackend {
         int B = 0;
         size_t stride = 0;
         int mm = 1;
-        bool any_voice = false, any_marks = false;
+        bool any_voice = false, any_marks = false, any_join = false;
         for (Request* r : batch) {
             any_marks = any_marks || r->want_marks;
+            any_join = any_join || r->joined();
             B += r->rows();
             for (int c = 0; c < r->rows(); ++c) stride = (size_t)r->chunk_len(c) > stride ? (size_t)r->chunk_len(c) : stride;
             mm = r->n_mix > mm ? r->n_mix : mm;
@@ -49,12 +50,14 @@ struct ModelBackend {
         std::vector<uint64_t> seeds(B);
         std::vector<uint32_t> uidx(B);
         std::vector<uint8_t> want(R);
+        std::vector<kx::JoinSpec> joins(R);  // (a plain request beside a joined one: the all-zero spec, the plain bytes)
         int b = 0;
         for (int q = 0; q < R; ++q) {
             const Request& r = *batch[(size_t)q];
             chunks[q] = r.rows();
             formats[q] = r.format;
             want[q] = r.want_marks ? 1 : 0;
+            joins[q] = kx::JoinSpec{r.join.flags, r.join.keep_ms, r.join.pause_ms, r.join.fade_ms};
             size_t at = 0;
             for (int c = 0; c < r.rows(); ++c, ++b) {
                 lens[b] = (int32_t)r.chunk_len(c);
@@ -93,6 +96,10 @@ struct ModelBackend {
                 hc.req_formats = formats.data();
                 hc.n_req_formats = R;
                 if (any_marks) hc.req_marks = want.data();
+                if (any_join) {
+                    hc.req_joins = joins.data();
+                    hc.n_req_joins = R;
+                }
                 if (any_voice) {
                     hc.voice_ids = vids.data();
                     hc.weights = weights.data();
@@ -285,6 +292,19 @@ int kx_dispatcher_submit_request_marks(kx_dispatcher* d, const int64_t* ids, con
     }
     return d->submit_request_marks(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
                                    out_bytes, out_samples, out_marks, out_n_marks, err, err_len);
+}
+
+int kx_dispatcher_submit_request_joined(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                        const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
+                                        float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
+                                        int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
+                                        char* err, size_t err_len) {
+    if (!d) {
+        if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null dispatcher");
+        return KX_ERR_INVALID;
+    }
+    return d->submit_request_joined(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
+                                    out_bytes, out_samples, out_marks, out_n_marks, join, err, err_len);
 }
 
 int kx_dispatcher_stats(kx_dispatcher* d, int64_t* n_requests, int64_t* n_batches, int64_t* max_batch_seen) {

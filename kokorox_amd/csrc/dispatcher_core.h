@@ -44,7 +44,8 @@
 //   static int forward(Handle*, std::vector<dispatch::Request*>&, Out&);  the batched forward: fills rc / err of EVERY request
 //                                                                         (and Out on success), returns the batch's status
 //   static void distribute(std::vector<dispatch::Request*>&, Out&);       gives every request its out / out_bytes / out_samples
-//                                                                         (and marks / n_marks where want_marks is set)
+//                                                                         (and marks / n_marks where want_marks is set);
+//                                                                         Request::join shapes a request's seams
 //   static int n_voices(Handle*);                                         rows of the model's voice table (0 = none)
 //   static int n_vocab(Handle*);                                          rows of its embedding tables (token ids are 0 .. n_vocab - 1)
 //   static void free_out(void*);                                          releases a request's `out` (what distribute handed out)
@@ -82,6 +83,8 @@ struct Request {
     int format = 0;
     float speed = 1.f;
     uint64_t seed = 0;
+    kx_join join = {0, 0, 0, 0};  // how its seams are shaped (submit_request_joined); all zeros = the chunks appended
+    bool joined() const { return join.flags || join.keep_ms || join.pause_ms || join.fade_ms; }
     bool want_marks = false;  // the token marks of the request beside its body (submit_request_marks); a batch may mix both kinds
     // result
     void* out = nullptr;
@@ -446,10 +449,23 @@ struct Core {
         return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
                                   out_samples, true, out_marks, out_n_marks, err, err_len);
     }
+    // ... and with its join spec; both marks arguments null = no marks
+    int submit_request_joined(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
+                              const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
+                              void** out, int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
+                              const kx_join* join, char* err, size_t err_len) {
+        if (!join || (join->flags & ~7u) || join->keep_ms < 0 || join->keep_ms > 1000 || join->pause_ms < 0 || join->pause_ms > 5000 ||
+            join->fade_ms < 0 || join->fade_ms > 12) {
+            if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: bad join");
+            return KX_ERR_INVALID;
+        }
+        return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
+                                  out_samples, out_marks || out_n_marks, out_marks, out_n_marks, err, err_len, join);
+    }
     int submit_request_any(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
                            const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
                            void** out, int64_t* out_bytes, int64_t* out_samples, bool want_marks, int64_t** out_marks,
-                           int64_t* out_n_marks, char* err, size_t err_len) {
+                           int64_t* out_n_marks, char* err, size_t err_len, const kx_join* join = nullptr) {
         const char* who = "dispatcher_submit_request";
         if (!out || !out_bytes || !out_samples) {
             if (err && err_len) snprintf(err, err_len, "%s: null output argument", who);
@@ -493,6 +509,7 @@ struct Core {
         r.speed = speed;
         r.seed = seed;
         r.want_marks = want_marks;
+        if (join) r.join = *join;
         const int rc = submit(r, out, out_bytes, out_samples, err, err_len);
         if (rc == KX_OK && want_marks) {
             *out_marks = r.marks;

@@ -102,6 +102,12 @@ void check_marks_call(const HostCall& hc, int64_t** out_marks, int64_t* out_n_ma
     KX_REQUIRE(hc.grouped(), "infer: marks are for requests (chunks_per_request)");
 }
 
+void check_join_call(const HostCall& hc) {
+    KX_REQUIRE(hc.req_joins, "infer: null join argument");
+    KX_REQUIRE(hc.grouped() && (hc.n_req_joins == 1 || hc.n_req_joins == hc.n_requests), "infer: bad join count");
+    for (int i = 0; i < hc.n_req_joins; ++i) KX_REQUIRE(join_spec_ok(hc.req_joins[i]), "infer: bad join");
+}
+
 // ---- refusals of the device entry (Model::infer_device) ----------------------------------------------------------------------
 int check_device_call(const void* d_ids, int64_t t_stride, const int32_t* lens_host, int B, const void* d_styles,
                       const float* speeds_host, int n_speed) {
@@ -119,7 +125,16 @@ int check_device_call(const void* d_ids, int64_t t_stride, const int32_t* lens_h
 }
 
 // ---- layout of the compact output ----------------------------------------------------------------------------------------------
+size_t join_pause_samples(const int* chunks_per_request, int R, const JoinSpec* joins, int n_join) {
+    size_t n = 0;
+    if (!joins || !chunks_per_request) return n;
+    for (int r = 0; r < R; ++r)
+        if (chunks_per_request[r] > 1) n += (size_t)24 * (size_t)joins[n_join == 1 ? 0 : r].pause_ms * (size_t)(chunks_per_request[r] - 1);
+    return n;
+}
+
 size_t packed_bytes_bound(const HostCall& hc, int B, size_t n_samples, const int32_t* lens) {
+    n_samples += join_pause_samples(hc.chunks_per_request, hc.n_requests, hc.req_joins, hc.n_req_joins);
     size_t n = pack_requests_bound(hc.words(), hc.n_words(), hc.regions(B), n_samples);
     if (hc.req_marks) {
         KX_REQUIRE(lens, "infer: marks need the token counts");
@@ -168,14 +183,9 @@ size_t resample_floats_bound(const int* formats, int n_format, size_t n_samples)
     return n_samples * per_sample;
 }
 
-void build_pack_plan(const int* frames, int B, const int* chunks_per_request, int R, const int* formats, int n_format,
-                     PackPlan& plan) {
-    KX_REQUIRE(frames && formats && B >= 1 && R >= 1 && (n_format == 1 || n_format == R), "pack: bad argument");
-    plan.cum.assign((size_t)B + 1, 0);
-    for (int b = 0; b < B; ++b) {
-        KX_REQUIRE(frames[b] >= 0, "pack: negative frame count");
-        plan.cum[(size_t)b + 1] = plan.cum[(size_t)b] + 600L * frames[b];
-    }
+namespace {
+// plan.cum is in place (the prefix over what every row contributes to its request's stream): the request table over it
+void fill_pack_requests(int B, const int* chunks_per_request, int R, const int* formats, int n_format, PackPlan& plan) {
     plan.req.assign((size_t)R, PackReq{});
     plan.total_bytes = 0;
     plan.max_units = 0;
@@ -209,11 +219,62 @@ void build_pack_plan(const int* frames, int B, const int* chunks_per_request, in
     }
     KX_REQUIRE(row == B, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
 }
+}  // namespace
+
+void build_pack_plan(const int* frames, int B, const int* chunks_per_request, int R, const int* formats, int n_format,
+                     PackPlan& plan) {
+    KX_REQUIRE(frames && formats && B >= 1 && R >= 1 && (n_format == 1 || n_format == R), "pack: bad argument");
+    plan.cum.assign((size_t)B + 1, 0);
+    for (int b = 0; b < B; ++b) {
+        KX_REQUIRE(frames[b] >= 0, "pack: negative frame count");
+        plan.cum[(size_t)b + 1] = plan.cum[(size_t)b] + 600L * frames[b];
+    }
+    fill_pack_requests(B, chunks_per_request, R, formats, n_format, plan);
+}
+
+void build_join_plan(const int* frames, const int* lens, const int* edges, int B, const int* chunks_per_request, int R,
+                     const int* formats, int n_format, const JoinSpec* joins, int n_join, PackPlan& plan, JoinPlan& join) {
+    KX_REQUIRE(frames && lens && edges && formats && joins && B >= 1 && R >= 1 && (n_format == 1 || n_format == R) &&
+                   (n_join == 1 || n_join == R), "join: bad argument");
+    join.row.assign((size_t)B, JoinRow{});
+    join.any = false;
+    plan.cum.assign((size_t)B + 1, 0);
+    int row = 0;
+    for (int r = 0; r < R; ++r) {
+        const int n = chunks_per_request ? chunks_per_request[r] : 1;
+        KX_REQUIRE(n >= 1 && n <= B - row, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
+        const JoinSpec& js = joins[n_join == 1 ? 0 : r];
+        KX_REQUIRE(join_spec_ok(js), "infer: bad join");
+        join.any = join.any || !join_spec_plain(js);
+        const long k = 24L * js.keep_ms, fade = 24L * js.fade_ms;
+        for (int b = row; b < row + n; ++b) {
+            KX_REQUIRE(frames[b] >= 0 && edges[2 * b] >= 0 && edges[2 * b + 1] >= 0, "pack: negative frame count");
+            const bool first = b == row, last = b == row + n - 1, long_enough = lens[b] >= 3;  // (shorter rows are pads only)
+            const bool head = long_enough && (js.flags & (first ? JOIN_TRIM_HEAD : JOIN_TRIM_INNER)) != 0;
+            const bool tail = long_enough && (js.flags & (last ? JOIN_TRIM_TAIL : JOIN_TRIM_INNER)) != 0;
+            JoinRow& j = join.row[(size_t)b];
+            const long lead = 600L * edges[2 * b] - k, trail = 600L * edges[2 * b + 1] - k;
+            j.skip = head && lead > 0 ? lead : 0;
+            const long cut = tail && trail > 0 ? trail : 0;
+            j.keep = 600L * frames[b] - j.skip - cut;
+            j.gap = last ? 0 : 24L * js.pause_ms;
+            j.fade_head = head ? (int)fade : 0;
+            j.fade_tail = tail ? (int)fade : 0;
+            // (the middle tokens of a trimmed row have at least one frame each: 600 samples, more than the two fades' 576)
+            KX_REQUIRE(j.keep >= 0 && j.keep >= (long)j.fade_head + j.fade_tail, "join: a row's edge durations exceed its frames");
+            plan.cum[(size_t)b + 1] = plan.cum[(size_t)b] + j.keep + j.gap;
+        }
+        row += n;
+    }
+    KX_REQUIRE(row == B, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
+    fill_pack_requests(B, chunks_per_request, R, formats, n_format, plan);
+}
 
 void build_mark_plan(const PackPlan& plan, const int* lens, const int* chunks_per_request, int R, const int* formats,
-                     int n_format, const uint8_t* req_marks, MarkPlan& mp) {
+                     int n_format, const uint8_t* req_marks, MarkPlan& mp, const JoinPlan* join) {
     const int B = (int)plan.cum.size() - 1;
-    KX_REQUIRE(lens && formats && B >= 1 && R >= 1 && (int)plan.req.size() == R && (n_format == 1 || n_format == R), "marks: bad argument");
+    KX_REQUIRE(lens && formats && B >= 1 && R >= 1 && (int)plan.req.size() == R && (n_format == 1 || n_format == R) &&
+                   (!join || (int)join->row.size() == B), "marks: bad argument");
     mp.row.assign((size_t)B, MarkRow{-1, 0, 0});
     mp.count.assign((size_t)R, 0);
     mp.first.assign((size_t)R, 0);
@@ -232,7 +293,10 @@ void build_mark_plan(const PackPlan& plan, const int* lens, const int* chunks_pe
             KX_REQUIRE(lens[b] >= 1 && lens[b] <= 512, "infer: token count must be 1..512");
             MarkRow& m = mp.row[(size_t)b];
             m.K = K;
-            m.base = (plan.cum[(size_t)b] - plan.cum[(size_t)row]) / 600 * K;  // (cum counts 600 samples per frame)
+            m.src_base = plan.cum[(size_t)b] - plan.cum[(size_t)row];
+            m.base = m.src_base * K / 600;  // (exact: cum counts multiples of 24 samples, 600 per frame in a plain plan)
+            m.skip = join ? join->row[(size_t)b].skip : 0;
+            m.keep = join ? join->row[(size_t)b].keep : plan.cum[(size_t)b + 1] - plan.cum[(size_t)b];
             if (req_marks && req_marks[r]) {
                 m.first = mp.n_marks;
                 mp.n_marks += lens[b] + 1;

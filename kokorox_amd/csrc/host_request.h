@@ -11,6 +11,20 @@
 
 namespace kx {
 
+// A request's join spec: the layout of kx_join (include/kokorox_hip.h, "joins"; api.hip asserts the two agree).
+struct JoinSpec {
+    uint32_t flags;    // JOIN_TRIM_* bits, every other bit zero
+    int32_t keep_ms;   // 0..1000
+    int32_t pause_ms;  // 0..5000
+    int32_t fade_ms;   // 0..12
+};
+constexpr uint32_t JOIN_TRIM_HEAD = 1u, JOIN_TRIM_TAIL = 2u, JOIN_TRIM_INNER = 4u;
+inline bool join_spec_ok(const JoinSpec& j) {
+    return (j.flags & ~7u) == 0 && j.keep_ms >= 0 && j.keep_ms <= 1000 && j.pause_ms >= 0 && j.pause_ms <= 5000 && j.fade_ms >= 0 &&
+           j.fade_ms <= 12;
+}
+inline bool join_spec_plain(const JoinSpec& j) { return j.flags == 0 && j.keep_ms == 0 && j.pause_ms == 0 && j.fade_ms == 0; }
+
 // general host entry behind kx_infer / kx_infer_voices / kx_infer_packed / kx_infer_requests (Model::infer_host_ex)
 struct HostCall {
     const float* styles = nullptr;       // host [B][256], or
@@ -31,6 +45,10 @@ struct HostCall {
     const uint32_t* utt_index = nullptr;          // host [B] beside utt_seeds: row b draws (utt_seeds[b], utt_index[b])
     // token timing marks (include/kokorox_hip.h, "token marks"): request r wants them when req_marks[r] != 0; null = none
     const uint8_t* req_marks = nullptr;           // host [n_requests]
+    // joins (include/kokorox_hip.h, "joins"): request r is shaped by req_joins[n_req_joins == 1 ? 0 : r]; null = none
+    bool join_call = false;                       // the entry that takes joins: req_joins must then be there (check_join_call)
+    const JoinSpec* req_joins = nullptr;          // host [n_req_joins]
+    int n_req_joins = 0;                          // 1 (shared) or n_requests
 
     bool grouped() const { return chunks_per_request != nullptr; }
     bool by_voice() const { return voice_ids != nullptr; }
@@ -51,6 +69,11 @@ void check_host_call(const int64_t* ids, int64_t t_stride, const int32_t* lens, 
 // The entries that return token marks (HostCall::req_marks set): their two extra output arguments, checked after everything
 // above; *out_marks is cleared.  throws KX_ERR_INVALID: "infer: null marks argument"
 void check_marks_call(const HostCall& hc, int64_t** out_marks, int64_t* out_n_marks);
+// The entry that takes joins (HostCall::join_call; req_joins / n_req_joins as the caller gave them, a null pointer included),
+// checked after check_host_call.  throws KX_ERR_INVALID: "infer: null join argument", "infer: bad join count" (not 1 or R),
+// "infer: bad join" (a stray flag bit or a field outside its range).  Its marks arguments may both be null (no marks); exactly
+// one null is check_marks_call's refusal.
+void check_join_call(const HostCall& hc);
 // Everything Model::infer_device refuses before hipSetDevice; returns the longest token count.
 int check_device_call(const void* d_ids, int64_t t_stride, const int32_t* lens_host, int B, const void* d_styles,
                       const float* speeds_host, int n_speed);
@@ -114,8 +137,11 @@ void build_pack_plan(const int* frames, int B, const int* chunks_per_request, in
 // ROW of the batch; the packer's and the resampler's table (PackReq) does not know about marks.
 struct MarkRow {
     long first;  // index (in int64 values) of the row's first mark in the marks block; -1: its request wants none
-    long base;   // K x the frames of the request's earlier rows: the row's first mark
+    long base;   // the row's first mark: the samples of the request's earlier rows (their pauses included) x L / M
     long K;      // output samples per frame: 600 L / M of the request's rate (600, 200, 400, 1200)
+    // what the joined form of the kernel clamps with (a plain row: skip = 0, keep = 600 x its frames), at 24 000 Hz
+    long src_base = 0;  // samples of the request's stream before the row: base = src_base x L / M
+    long skip = 0, keep = 0;
 };
 struct MarkPlan {
     std::vector<MarkRow> row;  // [B]
@@ -128,12 +154,34 @@ struct MarkPlan {
 inline long frame_samples(int rate_code) { return rate_code == 1 ? 200 : (rate_code == 2 ? 400 : (rate_code == 3 ? 1200 : 600)); }
 // plan: build_pack_plan's result for the same rows and grouping; lens [B] tokens per row; formats [n_format] as there;
 // req_marks [R], null = no request wants marks (the block is then empty)
+// join: the join plan the pack plan was built with (build_join_plan), null = rows appended
+struct JoinPlan;
 void build_mark_plan(const PackPlan& plan, const int* lens, const int* chunks_per_request, int R, const int* formats,
-                     int n_format, const uint8_t* req_marks, MarkPlan& out);
+                     int n_format, const uint8_t* req_marks, MarkPlan& out, const JoinPlan* join = nullptr);
+
+// ---- joins: a kept segment of each row, then a run of zeros (include/kokorox_hip.h, "joins") -------------------------------
+// Row b of a request contributes x[skip .. skip + keep) of its 600 frames[b] valid samples, the first fade_head and the last
+// fade_tail of them faded, then gap zeros.  The packer's and the resampler's staging step read this table beside the prefix
+// table, which in a joined plan runs over keep + gap (PackPlan::cum), so PackReq's sizes follow the joined stream S'.
+struct JoinRow {
+    long skip, keep, gap;      // samples at 24 000 Hz, multiples of 24
+    int fade_head, fade_tail;  // 24 fade_ms where that edge is trimmed, else 0
+};
+struct JoinPlan {
+    std::vector<JoinRow> row;  // [B]
+    bool any = false;          // some request's spec is not all zeros: the joined form of the kernels is launched
+};
+// frames [B], lens [B], edges [B][2] = the used durations of each row's first and last token (frames), joins [n_join] with
+// n_join = 1 or R; everything else as build_pack_plan, whose plan it fills for the joined streams.
+void build_join_plan(const int* frames, const int* lens, const int* edges, int B, const int* chunks_per_request, int R,
+                     const int* formats, int n_format, const JoinSpec* joins, int n_join, PackPlan& plan, JoinPlan& join);
+// samples (at 24 000 Hz) the pauses add to a call before its frame counts are known: 24 pause_ms (rows_r - 1) per request
+size_t join_pause_samples(const int* chunks_per_request, int R, const JoinSpec* joins, int n_join);
 
 // Bytes of the packed buffer of a call of B rows before its forward has run, for n_samples samples in all: pack_requests_bound
 // over the call's words and regions.  With marks asked for (hc.req_marks; lens [B]
 // then required) 8 + 8 x the sum over the rows of lens + 1 more: the alignment gap and a block in which every request wants them.
+// With joins (hc.req_joins) n_samples grows by the pauses (join_pause_samples); trimming only shrinks.
 size_t packed_bytes_bound(const HostCall& hc, int B, size_t n_samples, const int32_t* lens = nullptr);
 
 }  // namespace kx

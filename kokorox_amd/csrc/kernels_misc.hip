@@ -522,10 +522,54 @@ __device__ __forceinline__ uint32_t g711_alaw(int v) {
     return (uint32_t)((seg << 4) | ((p >> (seg < 2 ? 1 : seg)) & 15)) ^ mask;
 }
 
-__global__ __launch_bounds__(PACK_THREADS) void pack_requests_kernel(const float* __restrict__ audio, long audio_ld,
-                                                                     const PackReq* __restrict__ reqs,
-                                                                     const long* __restrict__ cum,
-                                                                     const float* __restrict__ y, char* __restrict__ out) {
+// The staging step of the packer and of the resampler: samples [lo, hi) of a request's stream into dst[0 .. hi - lo), lanes
+// along time.  Every lane finds the row of its first sample in the batch's prefix table (cum[row] <= g0 + i < cum[row + 1])
+// and walks on from there.  Plain: the rows appended, sample o of row b is audio[b ld + o].  JOINED (include/kokorox_hip.h,
+// "joins"; host_request.h: JoinRow): cum runs over keep + gap, and offset o of row b is its kept sample skip + o -- times its
+// gain when o lies in one of the two fades, which never overlap -- while o < keep, and +0 in the pause behind it.  A fade is
+// one float64 division, one float64 product and one rounding, computed here: it needs no storage.  Either way nothing at or
+// past 600 * frames[b] of a row is read (skip + keep <= 600 frames[b]), and nothing of a cut region.
+__device__ __forceinline__ float join_fade(float v, long i, int n) {
+    return (float)((double)v * ((double)(2 * i + 1) / (double)(2 * n)));
+}
+template <bool JOINED, int THREADS>
+__device__ __forceinline__ void stage_stream(float* __restrict__ dst, const float* __restrict__ audio, long audio_ld,
+                                             const long* __restrict__ cum, const JoinRow* __restrict__ jrows, int first_row,
+                                             int n_rows, long lo_i, long hi_i) {
+    const long g0 = cum[first_row];
+    const int row_end = first_row + n_rows;
+    long i = lo_i + threadIdx.x;
+    if (i < hi_i) {
+        int lo = first_row, hi = row_end - 1;  // the row of the lane's first sample: cum[row] <= g0 + i < cum[row + 1]
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (cum[mid] <= g0 + i) lo = mid; else hi = mid - 1;
+        }
+        int row = lo;
+        for (; i < hi_i; i += THREADS) {
+            while (row + 1 < row_end && cum[row + 1] <= g0 + i) ++row;
+            const long o = g0 + i - cum[row];
+            if (!JOINED) {
+                dst[i - lo_i] = audio[(long)row * audio_ld + o];
+            } else {
+                const JoinRow jr = jrows[row];
+                float v = 0.0f;
+                if (o < jr.keep) {
+                    v = audio[(long)row * audio_ld + jr.skip + o];
+                    if (o < jr.fade_head) v = join_fade(v, o, jr.fade_head);
+                    else if (jr.keep - 1 - o < jr.fade_tail) v = join_fade(v, jr.keep - 1 - o, jr.fade_tail);
+                }
+                dst[i - lo_i] = v;
+            }
+        }
+    }
+}
+
+template <bool JOINED>
+__device__ __forceinline__ void pack_requests_body(const float* __restrict__ audio, long audio_ld,
+                                                   const PackReq* __restrict__ reqs, const long* __restrict__ cum,
+                                                   const JoinRow* __restrict__ jrows, const float* __restrict__ y,
+                                                   char* __restrict__ out) {
     __shared__ float smp[PACK_LDS];
     const PackReq rq = reqs[blockIdx.y];
     const long mis = rq.out_off & 15;  // the region starts `mis` bytes into its first 16-byte unit
@@ -555,21 +599,7 @@ __global__ __launch_bounds__(PACK_THREADS) void pack_requests_kernel(const float
         const float* __restrict__ src = y + rq.y_off;
         for (long i = s_lo + threadIdx.x; i < s_hi; i += PACK_THREADS) smp[i - s_lo] = src[i];
     } else {
-        const long g0 = cum[rq.first_row];
-        const int row_end = rq.first_row + rq.n_rows;
-        long i = s_lo + threadIdx.x;
-        if (i < s_hi) {
-            int lo = rq.first_row, hi = row_end - 1;  // the row of the lane's first sample: cum[row] <= g0 + i < cum[row + 1]
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (cum[mid] <= g0 + i) lo = mid; else hi = mid - 1;
-            }
-            int row = lo;
-            for (; i < s_hi; i += PACK_THREADS) {
-                while (row + 1 < row_end && cum[row + 1] <= g0 + i) ++row;
-                smp[i - s_lo] = audio[(long)row * audio_ld + (g0 + i - cum[row])];
-            }
-        }
+        stage_stream<JOINED, PACK_THREADS>(smp, audio, audio_ld, cum, jrows, rq.first_row, rq.n_rows, s_lo, s_hi);
     }
     __syncthreads();
     const long u_lo = blk_lo + (long)threadIdx.x * 16;  // the lane's unit, as a byte offset in the region (may start before it)
@@ -630,6 +660,20 @@ __global__ __launch_bounds__(PACK_THREADS) void pack_requests_kernel(const float
         }
     }
 }
+// (two kernels, not one with a flag: the plain form keeps its name, its arguments and its registers)
+__global__ __launch_bounds__(PACK_THREADS) void pack_requests_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                     const PackReq* __restrict__ reqs,
+                                                                     const long* __restrict__ cum,
+                                                                     const float* __restrict__ y, char* __restrict__ out) {
+    pack_requests_body<false>(audio, audio_ld, reqs, cum, nullptr, y, out);
+}
+__global__ __launch_bounds__(PACK_THREADS) void pack_requests_joined_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                            const PackReq* __restrict__ reqs,
+                                                                            const long* __restrict__ cum,
+                                                                            const JoinRow* __restrict__ jrows,
+                                                                            const float* __restrict__ y, char* __restrict__ out) {
+    pack_requests_body<true>(audio, audio_ld, reqs, cum, jrows, y, out);
+}
 
 // ---- output sample rates: a request's whole stream through a polyphase FIR, before the packer -----------------------------
 // For rate code c the ratio is L / M ((1, 3), (2, 3), (2, 1)), C = 24 max(L, M), N = 2 C + 1 taps h (resample_taps.h), and
@@ -651,9 +695,10 @@ constexpr int RS_LDS = 3 * (RS_WINDOW - 1) + (RS_MAX_TAPS - 1) + 1 + 2;
 static_assert(KX_RESAMPLE_NTAPS_16000 <= RS_MAX_TAPS && KX_RESAMPLE_NTAPS_48000 <= RS_MAX_TAPS, "the 8 kHz table is the longest");
 __device__ const uint32_t resample_tap_bits[3][RS_MAX_TAPS] = {{KX_RESAMPLE_TAPS_8000}, {KX_RESAMPLE_TAPS_16000}, {KX_RESAMPLE_TAPS_48000}};
 
-__global__ __launch_bounds__(RS_THREADS) void resample_requests_kernel(const float* __restrict__ audio, long audio_ld,
-                                                                        const PackReq* __restrict__ reqs,
-                                                                        const long* __restrict__ cum, float* __restrict__ y) {
+template <bool JOINED>
+__device__ __forceinline__ void resample_requests_body(const float* __restrict__ audio, long audio_ld,
+                                                       const PackReq* __restrict__ reqs, const long* __restrict__ cum,
+                                                       const JoinRow* __restrict__ jrows, float* __restrict__ y) {
     __shared__ float xs[RS_LDS];
     __shared__ double hs[RS_MAX_TAPS];
     const PackReq rq = reqs[blockIdx.y];
@@ -669,23 +714,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_requests_kernel(const flo
     long j_hi = ((n1 - 1) * M + C) / L + 1;
     j_hi = j_hi > S ? S : j_hi;
     for (int t = threadIdx.x; t < N; t += RS_THREADS) hs[t] = (double)__uint_as_float(resample_tap_bits[rq.pad_ - 1][t]);
-    {
-        const long g0 = cum[rq.first_row];
-        const int row_end = rq.first_row + rq.n_rows;
-        long i = j_lo + threadIdx.x;
-        if (i < j_hi) {
-            int lo = rq.first_row, hi = row_end - 1;  // the row of the lane's first sample: cum[row] <= g0 + i < cum[row + 1]
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (cum[mid] <= g0 + i) lo = mid; else hi = mid - 1;
-            }
-            int row = lo;
-            for (; i < j_hi; i += RS_THREADS) {
-                while (row + 1 < row_end && cum[row + 1] <= g0 + i) ++row;
-                xs[i - j_lo] = audio[(long)row * audio_ld + (g0 + i - cum[row])];
-            }
-        }
-    }
+    stage_stream<JOINED, RS_THREADS>(xs, audio, audio_ld, cum, jrows, rq.first_row, rq.n_rows, j_lo, j_hi);
     __syncthreads();
     float* __restrict__ dst = y + rq.y_off;
     for (long n = n0 + threadIdx.x; n < n1; n += RS_THREADS) {
@@ -700,22 +729,43 @@ __global__ __launch_bounds__(RS_THREADS) void resample_requests_kernel(const flo
         dst[n] = (float)acc;
     }
 }
+__global__ __launch_bounds__(RS_THREADS) void resample_requests_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                        const PackReq* __restrict__ reqs,
+                                                                        const long* __restrict__ cum, float* __restrict__ y) {
+    resample_requests_body<false>(audio, audio_ld, reqs, cum, nullptr, y);
+}
+__global__ __launch_bounds__(RS_THREADS) void resample_requests_joined_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                               const PackReq* __restrict__ reqs,
+                                                                               const long* __restrict__ cum,
+                                                                               const JoinRow* __restrict__ jrows,
+                                                                               float* __restrict__ y) {
+    resample_requests_body<true>(audio, audio_ld, reqs, cum, jrows, y);
+}
 
 // The one way a plan's kernels are launched, for the model and for the test hook: the resampler when some request carries a
 // rate code, then the packer.  d_req [R], d_cum [B + 1]: device copies of the plan; d_y: plan.y_floats floats (may be null
-// when that is 0); out: 16-byte aligned, plan.total_bytes long.
+// when that is 0); out: 16-byte aligned, plan.total_bytes long.  d_join [B]: the device copy of a join plan's rows when the
+// batch has a joined request (JoinPlan::any; the plan was then built by build_join_plan), else null: the plain kernels.
 void launch_pack_plan(const float* audio, long audio_ld, const PackReq* d_req, const long* d_cum, int R, const PackPlan& plan,
-                      float* d_y, void* out, hipStream_t s) {
+                      float* d_y, void* out, hipStream_t s, const JoinRow* d_join) {
     if (plan.max_units <= 0) return;
     KX_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0 && R <= 65535, "pack: unaligned output or too many requests");
     if (plan.y_floats > 0) {
         KX_REQUIRE(d_y != nullptr, "pack: no buffer for the resampled streams");
-        hipLaunchKernelGGL(resample_requests_kernel, dim3((unsigned)((plan.max_resampled + RS_WINDOW - 1) / RS_WINDOW), (unsigned)R),
-                           dim3(RS_THREADS), 0, s, audio, audio_ld, d_req, d_cum, d_y);
+        const dim3 grid((unsigned)((plan.max_resampled + RS_WINDOW - 1) / RS_WINDOW), (unsigned)R);
+        if (d_join)
+            hipLaunchKernelGGL(resample_requests_joined_kernel, grid, dim3(RS_THREADS), 0, s, audio, audio_ld, d_req, d_cum, d_join, d_y);
+        else
+            hipLaunchKernelGGL(resample_requests_kernel, grid, dim3(RS_THREADS), 0, s, audio, audio_ld, d_req, d_cum, d_y);
         KX_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(pack_requests_kernel, dim3((unsigned)((plan.max_units + PACK_THREADS - 1) / PACK_THREADS), (unsigned)R),
-                       dim3(PACK_THREADS), 0, s, audio, audio_ld, d_req, d_cum, d_y, static_cast<char*>(out));
+    const dim3 grid((unsigned)((plan.max_units + PACK_THREADS - 1) / PACK_THREADS), (unsigned)R);
+    if (d_join)
+        hipLaunchKernelGGL(pack_requests_joined_kernel, grid, dim3(PACK_THREADS), 0, s, audio, audio_ld, d_req, d_cum, d_join, d_y,
+                           static_cast<char*>(out));
+    else
+        hipLaunchKernelGGL(pack_requests_kernel, grid, dim3(PACK_THREADS), 0, s, audio, audio_ld, d_req, d_cum, d_y,
+                           static_cast<char*>(out));
     KX_HIP(hipGetLastError());
 }
 
@@ -724,10 +774,13 @@ void launch_pack_plan(const float* audio, long audio_ld, const PackReq* d_req, c
 // entries of `dur` unwritten, they are never loaded), an exclusive scan in 64 bits, and lane t stores base + K x scan[t] as one
 // 8-byte value, coalesced along t; the lane of the last token stores entry T, the row's end, as well.  The scan is one
 // __shfl_up ladder inside each wave64 and ONE exchange of the eight wave totals through LDS (one barrier).
+// JOINED (a batch with a joined request): the value is (src_base + clamp(600 x scan - skip, 0, keep)) L / M, written as x K / 600
+// -- every term is a multiple of 24 and K of 200, so the division is exact; a plain row (skip 0, keep 600 x its frames) gives
+// base + K x scan as before.
 constexpr int MARK_THREADS = 512;
-__global__ __launch_bounds__(MARK_THREADS) void token_marks_kernel(const int* __restrict__ dur, const int* __restrict__ lens,
-                                                                   const MarkRow* __restrict__ rows,
-                                                                   long long* __restrict__ marks) {
+template <bool JOINED>
+__device__ __forceinline__ void token_marks_body(const int* __restrict__ dur, const int* __restrict__ lens,
+                                                 const MarkRow* __restrict__ rows, long long* __restrict__ marks) {
     __shared__ long long wave_total[MARK_THREADS / 64];
     const int b = blockIdx.x, t = threadIdx.x;
     const MarkRow mr = rows[b];
@@ -747,16 +800,49 @@ __global__ __launch_bounds__(MARK_THREADS) void token_marks_kernel(const int* __
 #pragma unroll
     for (int w = 0; w < MARK_THREADS / 64; ++w) before += w < wave ? wave_total[w] : 0;
     incl += before;
+    auto mark = [&](long long scan) -> long long {
+        if (!JOINED) return mr.base + mr.K * scan;
+        long long u = 600 * scan - mr.skip;
+        u = u < 0 ? 0 : (u > mr.keep ? mr.keep : u);
+        return (mr.src_base + u) * mr.K / 600;
+    };
     if (t < T) {
-        marks[mr.first + t] = mr.base + mr.K * (incl - d);
-        if (t == T - 1) marks[mr.first + T] = mr.base + mr.K * incl;
+        marks[mr.first + t] = mark(incl - d);
+        if (t == T - 1) marks[mr.first + T] = mark(incl);
     }
 }
+__global__ __launch_bounds__(MARK_THREADS) void token_marks_kernel(const int* __restrict__ dur, const int* __restrict__ lens,
+                                                                   const MarkRow* __restrict__ rows,
+                                                                   long long* __restrict__ marks) {
+    token_marks_body<false>(dur, lens, rows, marks);
+}
+__global__ __launch_bounds__(MARK_THREADS) void token_marks_joined_kernel(const int* __restrict__ dur, const int* __restrict__ lens,
+                                                                          const MarkRow* __restrict__ rows,
+                                                                          long long* __restrict__ marks) {
+    token_marks_body<true>(dur, lens, rows, marks);
+}
 // dur [B][512], lens [B], rows [B]: device; marks: the marks block (8-byte aligned), MarkPlan::n_marks values long
-void launch_token_marks(const int* dur, const int* lens, const MarkRow* d_rows, int B, void* marks, hipStream_t s) {
+// joined: the batch has a joined request (the rows' skip / keep / src_base then matter)
+void launch_token_marks(const int* dur, const int* lens, const MarkRow* d_rows, int B, void* marks, hipStream_t s, bool joined) {
     KX_REQUIRE(dur && lens && d_rows && marks && B >= 1 && (reinterpret_cast<uintptr_t>(marks) & 7) == 0, "marks: bad launch argument");
-    hipLaunchKernelGGL(token_marks_kernel, dim3((unsigned)B), dim3(MARK_THREADS), 0, s, dur, lens, d_rows,
-                       static_cast<long long*>(marks));
+    hipLaunchKernelGGL(joined ? token_marks_joined_kernel : token_marks_kernel, dim3((unsigned)B), dim3(MARK_THREADS), 0, s, dur,
+                       lens, d_rows, static_cast<long long*>(marks));
+    KX_HIP(hipGetLastError());
+}
+
+// ---- joins: the used durations of every row's first and last token, for the host's join plan ---------------------------------
+// edges[b] = {dur[b][0], dur[b][lens[b] - 1]}: eight bytes per row behind the duration head, copied to the host beside the
+// frame counts before the forward's one host wait.
+__global__ void edge_durations_kernel(const int* __restrict__ dur, const int* __restrict__ lens, int2* __restrict__ edges, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int T = min(max(lens[b], 1), 512);
+    edges[b] = make_int2(dur[(long)b * 512], dur[(long)b * 512 + T - 1]);
+}
+void launch_edge_durations(const int* dur, const int* lens, int* edges, int B, hipStream_t s) {
+    KX_REQUIRE(dur && lens && edges && B >= 1 && (reinterpret_cast<uintptr_t>(edges) & 7) == 0, "join: bad launch argument");
+    hipLaunchKernelGGL(edge_durations_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, dur, lens,
+                       reinterpret_cast<int2*>(edges), B);
     KX_HIP(hipGetLastError());
 }
 

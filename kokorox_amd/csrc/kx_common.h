@@ -289,11 +289,16 @@ void launch_style_mix(const float* table, int n_voices, const int* voice_ids, co
 // ---- requests of several chunks (host_request.h: PackReq, PackPlan, build_pack_plan): pack_requests_kernel ----------
 // and, for requests with a rate code, resample_requests_kernel before it.  d_req [R], d_cum [B + 1]: device copies of the plan;
 // d_y: plan.y_floats floats for the resampled streams (null when 0); out: 16-byte aligned, plan.total_bytes long
+// d_join [B]: the rows of a join plan (host_request.h: build_join_plan, which then also built `plan`) when the batch has a joined
+// request: the joined form of the two kernels; null: the plain kernels
 void launch_pack_plan(const float* audio, long audio_ld, const PackReq* d_req, const long* d_cum, int R, const PackPlan& plan,
-                      float* d_y, void* out, hipStream_t s);
+                      float* d_y, void* out, hipStream_t s, const JoinRow* d_join = nullptr);
 // token timing marks of the rows whose MarkRow::first is >= 0 (host_request.h: build_mark_plan): dur [B][512] as duration_kernel
 // wrote it, lens [B], d_rows [B] on the device; marks = the marks block, 8-byte aligned
-void launch_token_marks(const int* dur, const int* lens, const MarkRow* d_rows, int B, void* marks, hipStream_t s);
+// joined: the batch has a joined request (token_marks_joined_kernel: the clamp to every row's kept segment)
+void launch_token_marks(const int* dur, const int* lens, const MarkRow* d_rows, int B, void* marks, hipStream_t s, bool joined = false);
+// edges [B][2] = {dur[b][0], dur[b][lens[b] - 1]} (8-byte aligned): what the host's join plan needs beside the frame counts
+void launch_edge_durations(const int* dur, const int* lens, int* edges, int B, hipStream_t s);
 // Host output buffers of the kx_infer* calls: page-locked and pooled (one asynchronous D2H copy at PCIe rate instead
 // of per-utterance pageable copies); host_out_free also accepts plain malloc'd pointers (dispatcher results).
 void* host_out_alloc(size_t bytes);

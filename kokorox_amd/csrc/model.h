@@ -382,6 +382,9 @@ class Model {
     // host staging that asynchronous copies read / write: outlives the calling frame
     PackPlan pack_plan_;               // request table + sample prefixes of the running call
     MarkPlan mark_plan_;               // per-row table of the token marks of the running call
+    JoinPlan join_plan_;               // per-row kept segments and pauses of the running call (a call with joins)
+    bool want_edges_ = false;          // the running host call has joins: front_half brings the rows' edge durations back
+    std::vector<int> h_edge_;          // [B][2] used durations of every row's first and last token (valid when want_edges_)
     unsigned h_bad_id_ = 0;
     unsigned* d_dev_err_ = nullptr;
     unsigned* h_words_ = nullptr;    // page-locked: [0] the device error word as read back

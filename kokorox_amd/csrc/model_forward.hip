@@ -383,10 +383,11 @@ Model::Front Model::front_half(const int64_t* d_ids, int64_t t_stride, const int
     const int Tp = up4(Tmax);
     const int idx_ld = Tmax * 50;
     float *emb, *h, *qkv, *ctx, *av, *ff, *dcat, *gxT, *gxT2, *xl, *logits, *te0, *te1, *t_en, *d_speeds;
-    int *dur, *idx;
+    int *dur, *idx, *d_edge = nullptr;
     plan_arena(arenaT_, false, [&](Arena& A) {
         call_.dT = A.i(B);
         call_.dF = A.i(B);
+        if (want_edges_) d_edge = A.i((size_t)2 * B);  // (a call with joins: every row's two edge durations)
         d_bad_id_ = reinterpret_cast<unsigned*>(A.i(1));
         d_speeds = A.f(B);
         dur = A.i((size_t)B * 512);
@@ -508,6 +509,13 @@ Model::Front Model::front_half(const int64_t* d_ids, int64_t t_stride, const int
     launch_duration(logits, t_logits.bs, Tp, d_speeds, n_speed, call_.dT, d_pinned_, n_pinned_, dur, call_.dF, idx, idx_ld, B,
                     stream_);
     KX_HIP(hipMemcpyAsync(call_.hF.data(), call_.dF, B * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    if (want_edges_) {
+        // a call with joins sizes its regions from the used durations of every row's two pad tokens as well: a gather of
+        // eight bytes per row and one more copy in front of the same host wait
+        h_edge_.assign((size_t)2 * B, 0);
+        launch_edge_durations(dur, call_.dT, d_edge, B, stream_);
+        KX_HIP(hipMemcpyAsync(h_edge_.data(), d_edge, (size_t)2 * B * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    }
     h_bad_id_ = 0;
     KX_HIP(hipMemcpyAsync(&h_bad_id_, d_bad_id_, sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
 

@@ -130,7 +130,9 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
                             int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out,
                             int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks) {
     check_host_call(ids, t_stride, lens, B, speeds, hc, out, out_bytes, out_samples, n_vocab_, n_voices_, d_voices_ != nullptr);
+    if (hc.join_call) check_join_call(hc);
     if (hc.req_marks) check_marks_call(hc, out_marks, out_n_marks);
+    const bool joins = hc.req_joins != nullptr;
     const bool by_voice = hc.by_voice();
     const bool marks = hc.req_marks != nullptr;  // (with chunks_per_request then: check_marks_call)
     // one way to lay the output out and pack it: a call without chunks_per_request is R = B single-row requests in hc.format
@@ -145,6 +147,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     uint32_t* d_uidx;
     PackReq* d_req = nullptr;
     MarkRow* d_mrow = nullptr;
+    JoinRow* d_jrow = nullptr;
     long* d_cum = nullptr;
     float* d_y = nullptr;  // the resampled streams of the requests with a rate code, back to back
     int *d_vid, *d_rows, *d_kinds;
@@ -163,7 +166,10 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         d_w = A.f((size_t)B * mm);
         d_req = static_cast<PackReq*>(A.alloc((size_t)R * sizeof(PackReq)));
         d_cum = static_cast<long*>(A.alloc(((size_t)B + 1) * 8));
-        d_y = A.f(resample_floats_bound(words, n_words, audio_floats));  // (0 floats when no word carries a rate code)
+        // (the pauses of a call with joins lengthen the streams; trimming only shortens them)
+        const size_t pauses = join_pause_samples(hc.chunks_per_request, R, hc.req_joins, hc.n_req_joins);
+        d_y = A.f(resample_floats_bound(words, n_words, audio_floats + pauses));  // (0 floats when no word carries a rate code)
+        if (joins) d_jrow = static_cast<JoinRow*>(A.alloc((size_t)B * sizeof(JoinRow)));
         if (marks) d_mrow = static_cast<MarkRow*>(A.alloc((size_t)B * sizeof(MarkRow)));
         d_packed = A.alloc(packed_bytes_bound(hc, B, audio_floats, lens));  // compact output: the requests back to back
         return A.f(audio_floats);
@@ -196,6 +202,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         if (hc.utt_seeds) KX_HIP(hipMemcpyAsync(d_seeds, hc.utt_seeds, (size_t)B * 8, hipMemcpyHostToDevice, stream_));
         if (hc.utt_index) KX_HIP(hipMemcpyAsync(d_uidx, hc.utt_index, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
         int64_t need_ld = 0;
+        Restore<bool> edges(want_edges_, joins);  // (the forward brings every row's two edge durations back with its frame counts)
         try {
             infer_device(d_ids, t_stride, lens, B, d_styles, speeds, n_speed, seed, flags, d_audio, ld, d_fr, &need_ld,
                          hc.utt_seeds ? d_seeds : nullptr, hc.utt_index ? d_uidx : nullptr);
@@ -210,7 +217,10 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         // launch packs every request of the batch back to back on the GPU, whatever its form (and one before it, the
         // resampler, when a request asks for another rate), then ONE asynchronous copy into a page-locked host buffer
         PackPlan& plan = pack_plan_;
-        build_pack_plan(call_.hF.data(), B, hc.chunks_per_request, R, words, n_words, plan);
+        JoinPlan& jp = join_plan_;
+        if (joins) build_join_plan(call_.hF.data(), lens, h_edge_.data(), B, hc.chunks_per_request, R, words, n_words, hc.req_joins, hc.n_req_joins, plan, jp);
+        else build_pack_plan(call_.hF.data(), B, hc.chunks_per_request, R, words, n_words, plan);
+        const bool joined = joins && jp.any;  // (all-zero specs: the plain kernels, the plain bytes)
         for (int r = 0; r < R; ++r) {
             out_samples[r] = plan.req[(size_t)r].n_samples;
             out_bytes[r] = plan.req[(size_t)r].out_bytes;
@@ -219,18 +229,19 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         int64_t marks_off = 0, n_marks = 0;
         KX_HIP(hipMemcpyAsync(d_req, plan.req.data(), (size_t)R * sizeof(PackReq), hipMemcpyHostToDevice, stream_));
         KX_HIP(hipMemcpyAsync(d_cum, plan.cum.data(), ((size_t)B + 1) * 8, hipMemcpyHostToDevice, stream_));
-        launch_pack_plan(d_audio, ld, d_req, d_cum, R, plan, d_y, d_packed, stream_);
+        if (joined) KX_HIP(hipMemcpyAsync(d_jrow, jp.row.data(), (size_t)B * sizeof(JoinRow), hipMemcpyHostToDevice, stream_));
+        launch_pack_plan(d_audio, ld, d_req, d_cum, R, plan, d_y, d_packed, stream_, joined ? d_jrow : nullptr);
         if (marks) {
             // the token marks of the requests that want them, in a block of their own behind the bodies (8-aligned): one
             // more launch on this stream, and the call's one copy to the host brings both
             MarkPlan& mp = mark_plan_;
-            build_mark_plan(plan, lens, hc.chunks_per_request, R, words, n_words, hc.req_marks, mp);
+            build_mark_plan(plan, lens, hc.chunks_per_request, R, words, n_words, hc.req_marks, mp, joins ? &jp : nullptr);
             for (int r = 0; r < R; ++r) out_n_marks[r] = mp.count[(size_t)r];
             marks_off = mp.marks_off;
             n_marks = mp.n_marks;
             if (n_marks > 0) {
                 KX_HIP(hipMemcpyAsync(d_mrow, mp.row.data(), (size_t)B * sizeof(MarkRow), hipMemcpyHostToDevice, stream_));
-                launch_token_marks(call_.d_dur, call_.dT, d_mrow, B, static_cast<char*>(d_packed) + marks_off, stream_);
+                launch_token_marks(call_.d_dur, call_.dT, d_mrow, B, static_cast<char*>(d_packed) + marks_off, stream_, joined);
                 total = mp.end_bytes();
             }
         }

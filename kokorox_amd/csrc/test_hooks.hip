@@ -661,4 +661,78 @@ int kx_test_token_marks(int device_id, const int32_t* dur, const int32_t* lens, 
     });
 }
 
+int kx_test_join_requests(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* dur, const int32_t* lens,
+                          const int32_t* chunks_per_request, int R, const int32_t* formats, const kx_join* joins,
+                          const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes, int64_t* out_samples,
+                          int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks, char* err, size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        check_device(device_id);
+        KX_REQUIRE(dur && lens && chunks_per_request && formats && joins && out_bytes && out_samples && out_n_marks && B > 0 && R > 0 &&
+                       (audio ? out != nullptr : out_cap == 0), "test_join_requests: bad argument");
+        // what the forward would have brought back: the rows' frame counts and the durations of their two edge tokens
+        std::vector<int> frames((size_t)B, 0), edges((size_t)2 * B, 0);
+        for (int b = 0; b < B; ++b) {
+            KX_REQUIRE(lens[b] >= 1 && lens[b] <= 512, "test_join_requests: lens out of range");
+            long f = 0;
+            for (int t = 0; t < lens[b]; ++t) {
+                KX_REQUIRE(dur[(size_t)b * 512 + t] >= 0, "test_join_requests: negative duration");
+                f += dur[(size_t)b * 512 + t];
+            }
+            KX_REQUIRE(f <= 0x7FFFFFFF / 600 && (!audio || 600L * f <= audio_ld), "test_join_requests: a row is shorter than its frames");
+            frames[(size_t)b] = (int)f;
+            edges[(size_t)2 * b] = dur[(size_t)b * 512];
+            edges[(size_t)2 * b + 1] = dur[(size_t)b * 512 + lens[b] - 1];
+        }
+        for (int r = 0; r < R; ++r) KX_REQUIRE(kx::join_spec_ok(kx::JoinSpec{joins[r].flags, joins[r].keep_ms, joins[r].pause_ms, joins[r].fade_ms}), "infer: bad join");
+        kx::PackPlan plan;  // the three table builders of Model::infer_host_once
+        kx::JoinPlan jp;
+        kx::build_join_plan(frames.data(), lens, edges.data(), B, chunks_per_request, R, formats, R,
+                            reinterpret_cast<const kx::JoinSpec*>(joins), R, plan, jp);
+        std::vector<uint8_t> none((size_t)R, 0);  // want = null: no request
+        kx::MarkPlan mp;
+        kx::build_mark_plan(plan, lens, chunks_per_request, R, formats, R, want ? want : none.data(), mp, &jp);
+        for (int r = 0; r < R; ++r) {
+            out_bytes[r] = plan.req[(size_t)r].out_bytes;
+            out_samples[r] = plan.req[(size_t)r].n_samples;
+            out_n_marks[r] = mp.count[(size_t)r];
+        }
+        KX_REQUIRE(mp.n_marks <= marks_cap && (mp.n_marks == 0 || out_marks), "test_join_requests: marks_cap is too small");
+        KX_REQUIRE(!audio || plan.total_bytes <= out_cap, "test_join_requests: out_cap is too small");
+        KX_HIP(hipSetDevice(device_id));
+        DevMem dm;
+        const kx::JoinRow* d_join = jp.any ? dm.up(jp.row.data(), (size_t)B) : nullptr;
+        std::vector<unsigned char> tail(64);
+        if (audio) {  // (null: the marks alone, as kx_test_token_marks runs them)
+            const float* d_audio = dm.up(audio, (size_t)B * (size_t)audio_ld);
+            const kx::PackReq* d_req = dm.up(plan.req.data(), (size_t)R);
+            const long* d_cum = dm.up(plan.cum.data(), (size_t)B + 1);
+            // a sentinel after the last region and after the resampled streams: the kernels must not write past the plan
+            char* d_out = dm.get<char>((size_t)plan.total_bytes + 64);
+            KX_HIP(hipMemset(d_out, 0xA5, (size_t)plan.total_bytes + 64));
+            float* d_y = plan.y_floats > 0 ? dm.get<float>((size_t)plan.y_floats + 16) : nullptr;
+            if (d_y) KX_HIP(hipMemset(d_y + plan.y_floats, 0xA5, 64));
+            kx::launch_pack_plan(d_audio, (long)audio_ld, d_req, d_cum, R, plan, d_y, d_out, nullptr, d_join);
+            KX_HIP(hipDeviceSynchronize());
+            KX_HIP(hipMemcpy(out, d_out, (size_t)plan.total_bytes, hipMemcpyDeviceToHost));
+            KX_HIP(hipMemcpy(tail.data(), d_out + plan.total_bytes, 64, hipMemcpyDeviceToHost));
+            for (unsigned char c : tail) KX_REQUIRE(c == 0xA5, "test_join_requests: the kernel wrote past the last region");
+            if (d_y) {
+                KX_HIP(hipMemcpy(tail.data(), d_y + plan.y_floats, 64, hipMemcpyDeviceToHost));
+                for (unsigned char c : tail) KX_REQUIRE(c == 0xA5, "test_join_requests: the resampler wrote past the last stream");
+            }
+        }
+        if (mp.n_marks == 0) return;
+        const int* d_dur = dm.up(dur, (size_t)B * 512);
+        const int* d_len = dm.up(lens, (size_t)B);
+        const kx::MarkRow* d_rows = dm.up(mp.row.data(), (size_t)B);
+        char* d_mk = dm.get<char>((size_t)mp.n_marks * 8 + 64);
+        KX_HIP(hipMemset(d_mk, 0xA5, (size_t)mp.n_marks * 8 + 64));
+        kx::launch_token_marks(d_dur, d_len, d_rows, B, d_mk, nullptr, jp.any);
+        KX_HIP(hipDeviceSynchronize());
+        KX_HIP(hipMemcpy(out_marks, d_mk, (size_t)mp.n_marks * 8, hipMemcpyDeviceToHost));
+        KX_HIP(hipMemcpy(tail.data(), d_mk + mp.n_marks * 8, 64, hipMemcpyDeviceToHost));
+        for (unsigned char c : tail) KX_REQUIRE(c == 0xA5, "test_join_requests: the kernel wrote past the last mark");
+    });
+}
+
 }  // extern "C"

@@ -27,6 +27,10 @@ PACK_MULAW, PACK_ALAW = 8, 9  # raw G.711, one byte per sample (infer_requests /
 PACK_RATE_24000, PACK_RATE_8000, PACK_RATE_16000, PACK_RATE_48000 = 0x000, 0x100, 0x200, 0x300
 RATE_HZ = {0: 24000, 1: 8000, 2: 16000, 3: 48000}  # by rate code (bits 8..11 of the word)
 RESAMPLE_MAX_TAPS = 145
+# joins (include/kokorox_hip.h, "joins"): a spec is (flags, keep_ms, pause_ms, fade_ms), the layout of kx_join
+JOIN_TRIM_HEAD, JOIN_TRIM_TAIL, JOIN_TRIM_INNER = 1, 2, 4
+JOIN_DTYPE = np.dtype([("flags", "<u4"), ("keep_ms", "<i4"), ("pause_ms", "<i4"), ("fade_ms", "<i4")])
+JOIN_NONE = (0, 0, 0, 0)
 KX_OK, KX_ERR_INVALID, KX_ERR_IO, KX_ERR_DEVICE, KX_ERR_STATE = 0, 1, 2, 3, 4  # include/kokorox_hip.h
 KX_FLAG_NOISE_OFF = 1
 KX_FLAG_TAPS = 2
@@ -121,6 +125,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                           C.POINTER(vp), vp]),
         "kx_dispatcher_submit_request_marks": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
                                                      C.POINTER(i64), C.POINTER(vp), C.POINTER(i64), cp, sz]),
+        "kx_infer_requests_joined": (i32, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, u64, u32, vp, i32, C.POINTER(vp), vp, vp,
+                                           vp, vp, vp, i32]),
+        "kx_dispatcher_submit_request_joined": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
+                                                      C.POINTER(i64), vp, vp, vp, cp, sz]),
         "kx_dispatcher_create": (vp, [vp, i32, i32, i32, cp, sz]),
         "kx_dispatcher_create_warm": (vp, [vp, i32, i32, i32, i32, i32, cp, sz]),
         "kx_dispatcher_submit": (i32, [vp, vp, i32, vp, f32, u64, C.POINTER(C.POINTER(f32)), C.POINTER(i64), cp, sz]),
@@ -178,6 +186,7 @@ def load_test_library() -> C.CDLL:
         "kx_test_instance_norm": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, cp, sz]),
         "kx_test_pack_requests": (i32, [i32, vp, i32, i64, vp, vp, i32, vp, vp, i64, vp, cp, sz]),
         "kx_test_token_marks": (i32, [i32, vp, vp, i32, vp, i32, vp, vp, vp, i64, vp, cp, sz]),
+        "kx_test_join_requests": (i32, [i32, vp, i32, i64, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, cp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -189,7 +198,7 @@ def load_test_library() -> C.CDLL:
 
 TEST_ABI_SYMBOLS = ["kx_test_conv1d", "kx_test_lstm", "kx_test_source", "kx_test_attention", "kx_test_conv1d_epilogue", "kx_test_conv1d_full",
                     "kx_test_conv_transpose", "kx_test_lstm_fault", "kx_test_lstm_parts", "kx_test_conv_plan", "kx_test_conv1d_opts",
-                    "kx_test_layernorm", "kx_test_instance_norm", "kx_test_pack_requests", "kx_test_token_marks"]
+                    "kx_test_layernorm", "kx_test_instance_norm", "kx_test_pack_requests", "kx_test_token_marks", "kx_test_join_requests"]
 
 ABI_SYMBOLS = [
     "kx_version", "kx_init", "kx_create", "kx_import_onnx", "kx_resample_filter", "kx_create_from_device_blob", "kx_create_replicas", "kx_replicas_times", "kx_create_partition", "kx_destroy",
@@ -197,7 +206,7 @@ ABI_SYMBOLS = [
     "kx_free_audio", "kx_infer_device", "kx_sync", "kx_set_pinned_durations", "kx_warmup", "kx_arena_bytes", "kx_call_times", "kx_model_status", "kx_model_info", "kx_dispatcher_health", "kx_set_utterance_base", "kx_set_lanes",
     "kx_set_conv_mode", "kx_get_conv_mode", "kx_set_stft_variant", "kx_get_stft_variant",
     "kx_profile_enable", "kx_profile_read", "kx_profile_detail", "kx_profile_aux", "kx_diag_enable", "kx_diag_count", "kx_diag_get", "kx_set_act_prescale", "kx_set_voice_table", "kx_infer_voices",
-    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
+    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
     "kx_dispatcher_stats", "kx_dispatcher_failures", "kx_dispatcher_destroy", "kx_debug_tap",
 ]
 
@@ -208,6 +217,21 @@ def _ptr(a: Optional[np.ndarray]):
 
 def _f32(a) -> Optional[np.ndarray]:
     return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+
+
+def join_specs(joins, n=None) -> np.ndarray:
+    """Join specs as the array of kx_join the library takes: one (flags, keep_ms, pause_ms, fade_ms) tuple, a list of them, or
+    an array of JOIN_DTYPE already.  n: the count expected (a single tuple is repeated)."""
+    if isinstance(joins, np.ndarray) and joins.dtype == JOIN_DTYPE:
+        a = np.ascontiguousarray(joins).reshape(-1)
+    else:
+        j = list(joins)
+        if len(j) == 4 and all(isinstance(v, (int, np.integer)) for v in j):
+            j = [tuple(j)] * (n if n is not None else 1)
+        a = np.array([tuple(int(v) for v in t) for t in j], dtype=JOIN_DTYPE)
+    if n is not None and a.shape[0] != n:
+        raise ValueError(f"{n} join specs are required")
+    return a
 
 
 def resample_filter(word: int):
@@ -424,7 +448,19 @@ class HipKoko:
         res, marks, nsamp = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, True)
         return (res, marks, nsamp) if with_samples else (res, marks)
 
-    def _infer_requests(self, tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, want_marks):
+    def infer_requests_joined(self, tokens, chunks_per_request, joins, styles=None, voice_ids=None, weights=None, speeds=(1.0,),
+                              seed: int = 0, flags: int = 0, fmt=0, marks: bool = False, with_samples: bool = False):
+        """infer_requests with the seams of every request shaped on the GPU (kx_infer_requests_joined; the definition is in
+        include/kokorox_hip.h, "joins", the numpy form voices.join_stream / voices.joined_marks): `joins` = one spec
+        (flags, keep_ms, pause_ms, fade_ms) for all requests, or a list of one per request.  Returns the bodies as
+        infer_requests does; marks=True: (bodies, marks) as infer_requests_marks.  with_samples: out_samples as a last entry."""
+        j = join_specs(joins)
+        res, mk, nsamp = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, marks, j)
+        out = (res, mk) if marks else (res,)
+        out = out + (nsamp,) if with_samples else out
+        return out if len(out) > 1 else out[0]
+
+    def _infer_requests(self, tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, want_marks, joins=None):
         ids, lens = self._ids_lens(tokens)
         B = len(tokens)
         cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32).reshape(-1)
@@ -446,6 +482,10 @@ class HipKoko:
         marks = None
         if want_marks:
             mk, n_mk = C.c_void_p(), np.zeros(max(R, 1), np.int64)
+        if joins is not None:
+            self._check(self._lib.kx_infer_requests_joined(*args, C.byref(mk) if want_marks else None, _ptr(n_mk) if want_marks else None,
+                                                           _ptr(joins), joins.shape[0]))
+        elif want_marks:
             self._check(self._lib.kx_infer_requests_marks(*args, C.byref(mk), _ptr(n_mk)))
         else:
             self._check(self._lib.kx_infer_requests(*args))
@@ -678,12 +718,13 @@ class Dispatcher:
         return arr.reshape(-1, 2) if fmt == 1 else arr
 
     def submit_request(self, chunks: Sequence[Sequence[int]], styles=None, voices=None, speed: float = 1.0, seed: int = 0,
-                       fmt: int = 0, marks: bool = False):
+                       fmt: int = 0, marks: bool = False, join=None):
         """A request of 1 .. max_batch chunks (kx_dispatcher_submit_request): `chunks` = the 0-wrapped id lists; `styles` = one
         256-float row per chunk, OR `voices` as in submit_ex (one voice spec for the request); `fmt` = a format word (a PACK_*
         form, optionally | PACK_RATE_*).  Returns what HipKoko.infer_requests returns for one request: an array (forms 0..2, 8, 9)
         or the body as bytes (3, 4).  marks=True (kx_dispatcher_submit_request_marks): returns (body, marks), marks = the
-        request's token marks as one int64 array (HipKoko.infer_requests_marks)."""
+        request's token marks as one int64 array (HipKoko.infer_requests_marks).  join = (flags, keep_ms, pause_ms, fade_ms)
+        (kx_dispatcher_submit_request_joined): the request's seams shaped as HipKoko.infer_requests_joined shapes them."""
         lens = np.array([len(c) for c in chunks], dtype=np.int32)
         a = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.int64).reshape(-1) for c in chunks])
                                  if len(chunks) else np.zeros(0, np.int64))
@@ -706,7 +747,11 @@ class Dispatcher:
         args = (self._d, _ptr(a), _ptr(lens), len(chunks), _ptr(st), _ptr(vid), _ptr(w), n_mix, float(speed), seed, fmt, C.byref(out),
                 C.byref(nb), C.byref(ns))
         mk, n_mk = C.c_void_p(), C.c_int64(0)
-        if marks:
+        if join is not None:
+            j = join_specs(join, 1)
+            rc = self._lib.kx_dispatcher_submit_request_joined(*args, C.byref(mk) if marks else None, C.byref(n_mk) if marks else None,
+                                                               _ptr(j), err, len(err))
+        elif marks:
             rc = self._lib.kx_dispatcher_submit_request_marks(*args, C.byref(mk), C.byref(n_mk), err, len(err))
         else:
             rc = self._lib.kx_dispatcher_submit_request(*args, err, len(err))
@@ -1017,3 +1062,41 @@ def token_marks(dur, lens, chunks_per_request, formats, want=None, device=0):
     n = np.zeros(R, dtype=np.int64)
     _err_call(lib.kx_test_token_marks, device, _ptr(dur), _ptr(ln), B, _ptr(cpr), R, _ptr(fm), _ptr(wt), _ptr(out), cap, _ptr(n))
     return [m.copy() for m in np.split(out[: int(n.sum())], np.cumsum(n)[:-1])]
+
+
+def join_requests(audio, dur, lens, chunks_per_request, formats, joins, want=None, device=0):
+    """Joined requests alone (kx_test_join_requests): audio [B, audio_ld] (None: the marks alone), dur [B, 512] int32 frames per
+    token with row b valid for lens[b] entries and 600 * their sum samples of audio, request r = chunks_per_request[r]
+    consecutive rows in the format word formats[r] with the join spec joins[r]; want [R] = which requests get marks (None:
+    none).  Returns (bodies as bytes, out_samples, marks): voices.join_stream -> resample_stream -> the form mirrors, and
+    voices.joined_marks (an empty array where not wanted)."""
+    lib = load_test_library()
+    dur = np.ascontiguousarray(dur, dtype=np.int32)
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32)
+    fm = np.ascontiguousarray(formats, dtype=np.int32)
+    B, R = ln.shape[0], cpr.shape[0]
+    assert dur.shape == (B, 512) and fm.shape == (R,)
+    j = join_specs(joins, R)
+    wt = None if want is None else np.ascontiguousarray(want, dtype=np.uint8)
+    assert wt is None or wt.shape == (R,)
+    ld, cap = 0, 0
+    if audio is not None:
+        audio = _f32(audio)
+        assert audio.shape[0] == B
+        ld = audio.shape[1]
+        frames = int(sum(int(dur[b, : ln[b]].sum()) for b in range(B)))
+        pauses = sum(24 * int(j["pause_ms"][r]) * (int(cpr[r]) - 1) for r in range(R))
+        cap = 16 * (600 * frames + pauses) + 64 * R  # (stereo f32 at 48 kHz: 16 bytes per sample of the model)
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    mcap = int(ln.sum()) + B
+    mk = np.zeros(mcap, dtype=np.int64)
+    nb, ns, nm = np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int64)
+    _err_call(lib.kx_test_join_requests, device, _ptr(audio), B, ld, _ptr(dur), _ptr(ln), _ptr(cpr), R, _ptr(fm), _ptr(j), _ptr(wt),
+              _ptr(out) if audio is not None else None, cap, _ptr(nb), _ptr(ns), _ptr(mk), mcap, _ptr(nm))
+    raw, res, o = out.tobytes(), [], 0
+    for r in range(R):
+        res.append(raw[o: o + int(nb[r])] if audio is not None else b"")
+        o += int(nb[r])
+    marks = [m.copy() for m in np.split(mk[: int(nm.sum())], np.cumsum(nm)[:-1])]
+    return res, [int(v) for v in ns], marks

@@ -224,6 +224,99 @@ def token_marks(durations_per_chunk: Sequence[Sequence[int]], word: int = 0) -> 
     return np.concatenate(out).astype(np.int64)
 
 
+JOIN_TRIM_HEAD, JOIN_TRIM_TAIL, JOIN_TRIM_INNER = 1, 2, 4
+
+
+def _join_fields(join):
+    flags, keep_ms, pause_ms, fade_ms = (int(v) for v in (join if join is not None else (0, 0, 0, 0)))
+    if flags & ~7 or not (0 <= keep_ms <= 1000 and 0 <= pause_ms <= 5000 and 0 <= fade_ms <= 12):
+        raise ValueError("join: flags 0..7, keep_ms 0..1000, pause_ms 0..5000, fade_ms 0..12")
+    return flags, keep_ms, pause_ms, fade_ms
+
+
+def join_rows(durations_per_chunk: Sequence[Sequence[int]], join):
+    """Per chunk of ONE request (skip, keep, gap, fade at the head, fade at the tail) in samples at 24 kHz, by the definition of
+    include/kokorox_hip.h, "joins": `join` = (flags, keep_ms, pause_ms, fade_ms).  A head edge is selected when the chunk has at
+    least 3 tokens and is the request's first with JOIN_TRIM_HEAD or a later one with JOIN_TRIM_INNER; a tail edge symmetrically
+    with JOIN_TRIM_TAIL / JOIN_TRIM_INNER; of a selected pad span at most 24 keep_ms samples stay."""
+    flags, keep_ms, pause_ms, fade_ms = _join_fields(join)
+    n, rows = len(durations_per_chunk), []
+    for c, d in enumerate(durations_per_chunk):
+        d = [int(v) for v in np.asarray(d).reshape(-1)]
+        if not d:
+            raise ValueError("join_rows: empty chunk")
+        head = len(d) >= 3 and bool(flags & (JOIN_TRIM_HEAD if c == 0 else JOIN_TRIM_INNER))
+        tail = len(d) >= 3 and bool(flags & (JOIN_TRIM_TAIL if c == n - 1 else JOIN_TRIM_INNER))
+        skip = max(0, 600 * d[0] - 24 * keep_ms) if head else 0
+        cut = max(0, 600 * d[-1] - 24 * keep_ms) if tail else 0
+        rows.append((skip, 600 * sum(d) - skip - cut, 0 if c == n - 1 else 24 * pause_ms, 24 * fade_ms if head else 0,
+                     24 * fade_ms if tail else 0))
+    return rows
+
+
+def join_stream(chunks_samples, durations_per_chunk: Sequence[Sequence[int]], join) -> np.ndarray:
+    """The stream of ONE joined request at 24 kHz, float32: for each chunk in order its kept samples x[skip .. skip + keep) --
+    sample i < n of a faded head and sample keep - 1 - i of a faded tail as f32(f64(x) * (f64(2 i + 1) / f64(2 n))) -- then gap
+    zeros.  `chunks_samples[c]` = the chunk's samples (at least 600 x its frames; what lies beyond is not used)."""
+    parts = []
+    for x, d, (skip, keep, gap, fh, ft) in zip(chunks_samples, durations_per_chunk, join_rows(durations_per_chunk, join)):
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        if x.shape[0] < 600 * int(np.sum(np.asarray(d, dtype=np.int64))):
+            raise ValueError("join_stream: a chunk is shorter than its frames")
+        seg = x[skip: skip + keep].copy()
+        with np.errstate(invalid="ignore", over="ignore"):
+            if fh:
+                g = (2 * np.arange(fh, dtype=np.float64) + 1) / np.float64(2 * fh)
+                seg[:fh] = (seg[:fh].astype(np.float64) * g).astype(np.float32)
+            if ft:
+                g = (2 * np.arange(ft, dtype=np.float64) + 1) / np.float64(2 * ft)
+                seg[keep - ft:] = (seg[keep - ft:].astype(np.float64) * g[::-1]).astype(np.float32)
+        parts.append(seg)
+        parts.append(np.zeros(gap, dtype=np.float32))
+    return np.concatenate(parts) if parts else np.zeros(0, dtype=np.float32)
+
+
+def joined_marks(durations_per_chunk: Sequence[Sequence[int]], word: int, join) -> np.ndarray:
+    """The token marks of ONE joined request in int64: m_c[t] = (P_c + clamp(600 x sum of d_c[t'] for t' < t - skip_c, 0,
+    keep_c)) L / M with P_c the kept samples and pauses of the chunks before c.  The all-zero spec gives `token_marks`."""
+    code = (int(word) >> 8) & 15
+    if code not in _RATE_LM or not durations_per_chunk:
+        raise ValueError("joined_marks: unknown output sample rate, or a request without chunks")
+    L, M = _RATE_LM[code]
+    out, base = [], 0
+    for d, (skip, keep, gap, _, _) in zip(durations_per_chunk, join_rows(durations_per_chunk, join)):
+        u = 600 * np.concatenate([np.zeros(1, np.int64), np.cumsum(np.asarray(d, dtype=np.int64).reshape(-1), dtype=np.int64)])
+        out.append((base + np.clip(u - skip, 0, keep)) * L // M)
+        base += keep + gap
+    return np.concatenate(out).astype(np.int64)
+
+
+def joined_body(chunks_samples, durations_per_chunk: Sequence[Sequence[int]], word: int, join) -> bytes:
+    """The body of ONE joined request in the format word `word`, as bytes: join_stream, resample_stream, then the form."""
+    return stream_body(resample_stream(join_stream(chunks_samples, durations_per_chunk, join), word), word)
+
+
+def stream_body(y, word: int) -> bytes:
+    """The form of a format word applied to a request's stream `y`, which is at the word's rate already, as bytes."""
+    y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1)
+    form, rate = int(word) & 0xFF, {0: 24000, 1: 8000, 2: 16000, 3: 48000}[(int(word) >> 8) & 15]
+    if form == 0:
+        return y.astype("<f4").tobytes()
+    if form == 1:
+        return np.repeat(y, 2).astype("<f4").tobytes()
+    if form == 2:
+        # (form 2 clamps with fmax / fmin, which drop a NaN: -32767 there, include/kokorox_hip.h)
+        c = np.where(np.isnan(y), np.float32(-1.0), np.clip(y, np.float32(-1.0), np.float32(1.0))).astype(np.float32)
+        return np.trunc(c * np.float32(32767.0)).astype("<i2").tobytes()
+    if form == 3:
+        return wav_f32_body(y, rate)
+    if form == 4:
+        return wav16_base64(y, rate)
+    if form in (8, 9):
+        return (mulaw_bytes if form == 8 else alaw_bytes)(pcm16(y)).tobytes()
+    raise ValueError("stream_body: unknown output format")
+
+
 def token_spans(marks, chunk_tokens: Sequence[int]):
     """A request's marks as one (start, end) pair of int64 arrays per chunk: token t of chunk c occupies samples
     [start[t], end[t]) of the request's stream.  `chunk_tokens[c]` = tokens of chunk c (its two pads included); chunk c has
@@ -256,11 +349,12 @@ def word_spans(spans, words: Sequence[Sequence[int]]):
 
 
 def tts_request(model, styles: Dict[str, np.ndarray], style_name: str, chunk_tokens: Sequence[Sequence[int]],
-                speed: float = 1.0, initial_silence: int = 0, seed: int = 0, fmt: int = 0):
+                speed: float = 1.0, initial_silence: int = 0, seed: int = 0, fmt: int = 0, join=None):
     """`tts_chunks` through `model.infer_requests`: the chunks of one text as ONE request of one batched forward, its body
     (header of the form, then the chunks' samples with nothing between them) packed on the GPU.  `fmt` is a format word of
     hip_koko (a PACK_* form, optionally | PACK_RATE_*): 0..2 and 8 / 9 give the samples as an array, 3 (`wav_f32_body`) and 4
-    (`wav16_base64`) the bytes a server sends.  An
+    (`wav16_base64`) the bytes a server sends.  `join` = (flags, keep_ms, pause_ms, fade_ms): the seams shaped on the GPU
+    (`model.infer_requests_joined`; trim the pads' silence, pause between sentences, fade the cut edges).  An
     empty chunk list and an empty chunk are errors (a request has at least one chunk)."""
     toks, rows = [], []
     for ch in chunk_tokens:
@@ -271,5 +365,8 @@ def tts_request(model, styles: Dict[str, np.ndarray], style_name: str, chunk_tok
         toks.append([0] + t + [0])
     if not toks:
         raise ValueError("tts_request: a request has at least one chunk")
+    if join is not None:
+        return model.infer_requests_joined(toks, [len(toks)], join, styles=np.asarray(rows, dtype=np.float32), speeds=[float(speed)],
+                                           seed=seed, fmt=fmt)[0]
     return model.infer_requests(toks, [len(toks)], styles=np.asarray(rows, dtype=np.float32), speeds=[float(speed)], seed=seed,
                                 fmt=fmt)[0]

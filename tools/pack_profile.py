@@ -5,7 +5,11 @@ the command line; an optional second argument is the batch (1 = one utterance). 
     '2' / '3' / '4'      kx_infer_requests in that form, every row a request of its own (pack_requests_kernel); a format word
                          with a rate code, written as the header does ('0x108' = G.711 mu-law at 8 kHz, '0x303' = float WAV at
                          48 kHz), adds resample_requests_kernel in front of it;
-    a word and 'm'       ('2m') kx_infer_requests_marks in that word, which adds token_marks_kernel behind the packer.
+    a word and 'm'       ('2m') kx_infer_requests_marks in that word, which adds token_marks_kernel behind the packer;
+    a word and 'j'       ('2j', '0x108j') kx_infer_requests_joined with marks, the batch as BATCH / 4 requests of 4 chunks, every
+                         request with the spec {HEAD | TAIL | INNER, keep 20 ms, pause 150 ms, fade 5 ms}: the joined forms of the
+                         three kernels (pack_requests_joined_kernel, resample_requests_joined_kernel, token_marks_joined_kernel);
+    a word and 'g'       ('2g') the same grouping without joins (kx_infer_requests_marks): the plain kernels on the same batch.
 Meant to run under the profiler, one mode per run (kernel trace only, no counters in the same run):
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o t -- python tools/pack_profile.py p2
 profiles/pack_kernels_stats.txt holds the rows of the kernel_stats.csv files."""
@@ -27,6 +31,18 @@ for it in range(3):
         out = m.infer_batch(toks, rows, [1.0])
     elif which in ("p0", "p1", "p2"):
         out = m.infer_packed(toks, rows, fmt=int(which[1]))
+    elif which[-1] in "jg":
+        word = int(which[:-1], 0)
+        L, M, _ = hk.resample_filter(word)
+        if which[-1] == "j":
+            join = (hk.JOIN_TRIM_HEAD | hk.JOIN_TRIM_TAIL | hk.JOIN_TRIM_INNER, 20, 150, 5)
+            out, marks = m.infer_requests_joined(toks, [4] * (B // 4), join, styles=rows, fmt=word, marks=True)
+            # per chunk 422 frames less its two 3-frame pads but for 20 ms of each; three pauses of 150 ms per request
+            assert all(int(k[-1]) == (4 * (422 * 600 - 2 * (1800 - 480)) + 3 * 3600) * L // M for k in marks)
+        else:
+            out, marks = m.infer_requests_marks(toks, [4] * (B // 4), styles=rows, fmt=word)
+            assert all(int(k[-1]) == 4 * 422 * 600 * L // M for k in marks)
+        assert all(k.shape[0] == 4 * 131 for k in marks)
     elif which.endswith("m"):
         word = int(which[:-1], 0)
         out, marks = m.infer_requests_marks(toks, [1] * B, styles=rows, fmt=word)
