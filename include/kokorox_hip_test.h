@@ -99,36 +99,21 @@ int kx_test_source(int device_id, const float* f0, int B, int F2, const float* l
                    float lin_b, uint64_t seed, uint64_t utt_base, int noise_off, float* out,
                    char* err, size_t err_len);
 
-/* The request packer alone (pack_requests_kernel through build_pack_plan, the host-side table builder the model uses), host
- * arrays in, host bytes out: audio [B, audio_ld] with row b valid for 600 frames[b] samples (whatever lies beyond must not
- * reach the result), request r = chunks_per_request[r] consecutive rows (null: every row a request of its own, R = B) in the
- * format word formats[r] (a KX_PACK_* form, optionally | KX_PACK_RATE_*; [R]).  out receives
- * the R regions back to back (out_cap bytes available), out_bytes[r] their sizes. */
-int kx_test_pack_requests(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames,
-                          const int32_t* chunks_per_request, int R, const int32_t* formats, void* out, int64_t out_cap,
-                          int64_t* out_bytes, char* err, size_t err_len);
-
-/* The token marks alone (token_marks_kernel through build_pack_plan and build_mark_plan, the host-side table builders the model
- * uses; no audio): dur [B][512] frames per token with row b valid for lens[b] entries (whatever lies beyond must not reach the
- * result), request r = chunks_per_request[r] consecutive rows in the format word formats[r] ([R]; only its rate matters),
- * want [R] = which requests get marks, NULL = all.  frames[b] is taken as the sum of the row's valid durations.  out_marks
- * receives the wanted requests' marks back to back (out_cap values available), out_n_marks[r] their counts (0 where not
- * wanted).  The definition of the marks: include/kokorox_hip.h, "token marks". */
-int kx_test_token_marks(int device_id, const int32_t* dur, const int32_t* lens, int B, const int32_t* chunks_per_request, int R,
-                        const int32_t* formats, const uint8_t* want, int64_t* out_marks, int64_t out_cap, int64_t* out_n_marks,
-                        char* err, size_t err_len);
-
-/* Joined requests alone (include/kokorox_hip.h, "joins"): the joined form of the packer, the resampler and the marks kernel
- * through build_join_plan / build_mark_plan and launch_pack_plan, as the model runs them.  audio [B, audio_ld] as
- * kx_test_pack_requests takes it, or NULL for the marks alone (no audio is read, out may be NULL with out_cap 0); dur [B][512]
- * and lens [B] as kx_test_token_marks takes them: frames[b] = the sum of the row's valid durations, its edge durations dur[b][0]
- * and dur[b][lens[b] - 1], all derived on the host.  formats [R], joins [R], want [R] = which requests get marks (NULL = none).
- * out receives the R bodies back to back (out_cap bytes available), out_bytes[r] / out_samples[r] their sizes, out_marks the
- * wanted requests' marks back to back (marks_cap values available), out_n_marks[r] their counts. */
-int kx_test_join_requests(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* dur, const int32_t* lens,
-                          const int32_t* chunks_per_request, int R, const int32_t* formats, const kx_join* joins,
-                          const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes, int64_t* out_samples,
-                          int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks, char* err, size_t err_len);
+/* The output stage of a call alone (include/kokorox_hip.h: the KX_PACK_* forms and rates, "token marks", "joins"): the packer,
+ * the resampler and the marks kernel through build_output_plan and launch_output_plan, the planner and the launcher the model
+ * runs, host arrays in, host bytes out.  audio [B, audio_ld] with row b valid for 600 frames[b] samples (whatever lies beyond
+ * must not reach the result), or NULL for the marks alone (no audio is read, out may be NULL with out_cap 0).  The frame counts
+ * are either given (frames [B]; dur and lens NULL, and then neither marks nor joins) or derived on the host from dur [B][512]
+ * frames per token with row b valid for lens[b] entries (frames NULL): frames[b] = the sum of the row's valid durations, its
+ * edge durations dur[b][0] and dur[b][lens[b] - 1].  Request r = chunks_per_request[r] consecutive rows (NULL: every row a
+ * request of its own, R = B) in the format word formats[r] (a KX_PACK_* form, optionally | KX_PACK_RATE_*; [R]), shaped by
+ * joins[r] ([R], NULL = rows appended as they are), with marks when want[r] != 0 ([R], NULL = none).  out receives the R bodies
+ * back to back (out_cap bytes available), out_bytes[r] / out_samples[r] their sizes, out_marks the wanted requests' marks back
+ * to back (marks_cap values available), out_n_marks[r] their counts (0 where not wanted). */
+int kx_test_output_plan(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames, const int32_t* dur,
+                        const int32_t* lens, const int32_t* chunks_per_request, int R, const int32_t* formats, const kx_join* joins,
+                        const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes, int64_t* out_samples,
+                        int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks, char* err, size_t err_len);
 
 /* Fault injection for the two-CU LSTM recurrence (process-wide, test only): nth > 0 makes the nth following launch of
  * the pair kernel, and every later one, lose the second half of each pair and poll with a short limit, so the call it

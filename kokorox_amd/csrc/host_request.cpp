@@ -125,23 +125,31 @@ int check_device_call(const void* d_ids, int64_t t_stride, const int32_t* lens_h
 }
 
 // ---- layout of the compact output ----------------------------------------------------------------------------------------------
-size_t join_pause_samples(const int* chunks_per_request, int R, const JoinSpec* joins, int n_join) {
-    size_t n = 0;
-    if (!joins || !chunks_per_request) return n;
-    for (int r = 0; r < R; ++r)
-        if (chunks_per_request[r] > 1) n += (size_t)24 * (size_t)joins[n_join == 1 ? 0 : r].pause_ms * (size_t)(chunks_per_request[r] - 1);
-    return n;
-}
-
-size_t packed_bytes_bound(const HostCall& hc, int B, size_t n_samples, const int32_t* lens) {
-    n_samples += join_pause_samples(hc.chunks_per_request, hc.n_requests, hc.req_joins, hc.n_req_joins);
-    size_t n = pack_requests_bound(hc.words(), hc.n_words(), hc.regions(B), n_samples);
-    if (hc.req_marks) {
-        KX_REQUIRE(lens, "infer: marks need the token counts");
-        n += 8;
-        for (int b = 0; b < B; ++b) n += 8 * ((size_t)lens[b] + 1);
+OutputBounds output_bounds(const RequestLayout& lay, int B, size_t n_samples, const int32_t* lens) {
+    if (lay.joins && lay.chunks_per_request)
+        for (int r = 0; r < lay.R; ++r)
+            if (lay.chunks_per_request[r] > 1)
+                n_samples += (size_t)24 * (size_t)lay.joins[lay.n_join == 1 ? 0 : r].pause_ms * (size_t)(lay.chunks_per_request[r] - 1);
+    // bytes per sample: 8 (stereo), 4 (f32, float WAV), 3 >= 8 / 3 (base64 of 16 bits), 2 (PCM16), 1 (G.711), twice that at 48 000 Hz
+    // (the lower rates are counted as 24 000 Hz); per request: the 44-byte header, or its 60 base64 characters and the last
+    // group's padding -- what a one-frame request needs beyond its samples.  Resampled floats per sample: every request at the
+    // batch's highest ratio, 2 at 48 000 Hz, below 1 otherwise
+    size_t per_sample = 0, y_per_sample = 0;
+    for (int i = 0; i < lay.n_format; ++i) {
+        const int f = format_form(lay.formats[i]), c = format_rate(lay.formats[i]);
+        size_t w = f == 1 ? 8 : (f == 2 ? 2 : (f == 4 ? 3 : (f >= 8 ? 1 : 4)));
+        if (c == 3) w *= 2;
+        const size_t y = c == 0 ? 0 : (c == 3 ? 2 : 1);
+        per_sample = w > per_sample ? w : per_sample;
+        y_per_sample = y > y_per_sample ? y : y_per_sample;
     }
-    return n;
+    OutputBounds bound{n_samples * per_sample + (size_t)lay.R * 64 + 16, n_samples * y_per_sample};
+    if (lay.marks) {
+        KX_REQUIRE(lens, "infer: marks need the token counts");
+        bound.packed_bytes += 8;
+        for (int b = 0; b < B; ++b) bound.packed_bytes += 8 * ((size_t)lens[b] + 1);
+    }
+    return bound;
 }
 
 long pack_request_bytes(int form, long n_samples) {
@@ -159,103 +167,35 @@ long pack_request_bytes(int form, long n_samples) {
     }
 }
 
-size_t pack_requests_bound(const int* formats, int n_format, int R, size_t n_samples) {
-    // per sample: 8 (stereo), 4 (f32, float WAV), 3 >= 8 / 3 (base64 of 16 bits), 2 (PCM16), 1 (G.711), twice that at 48 000 Hz
-    // (the lower rates are counted as 24 000 Hz); per request: the 44-byte header, or its 60 base64 characters and the last
-    // group's padding -- what a one-frame request needs beyond its samples
-    size_t per_sample = 0;
-    for (int i = 0; i < n_format; ++i) {
-        const int f = format_form(formats[i]);
-        size_t w = f == 1 ? 8 : (f == 2 ? 2 : (f == 4 ? 3 : (f >= 8 ? 1 : 4)));
-        if (format_rate(formats[i]) == 3) w *= 2;
-        per_sample = w > per_sample ? w : per_sample;
-    }
-    return n_samples * per_sample + (size_t)R * 64 + 16;
-}
-
-size_t resample_floats_bound(const int* formats, int n_format, size_t n_samples) {
-    size_t per_sample = 0;  // (every request at the batch's highest ratio: 2 at 48 000 Hz, below 1 otherwise)
-    for (int i = 0; i < n_format; ++i) {
-        const int c = format_rate(formats[i]);
-        const size_t w = c == 0 ? 0 : (c == 3 ? 2 : 1);
-        per_sample = w > per_sample ? w : per_sample;
-    }
-    return n_samples * per_sample;
-}
-
-namespace {
-// plan.cum is in place (the prefix over what every row contributes to its request's stream): the request table over it
-void fill_pack_requests(int B, const int* chunks_per_request, int R, const int* formats, int n_format, PackPlan& plan) {
-    plan.req.assign((size_t)R, PackReq{});
-    plan.total_bytes = 0;
-    plan.max_units = 0;
-    plan.y_floats = 0;
-    plan.max_resampled = 0;
-    int row = 0;
-    for (int r = 0; r < R; ++r) {
-        const int n = chunks_per_request ? chunks_per_request[r] : 1;
-        KX_REQUIRE(n >= 1 && n <= B - row, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
-        PackReq& q = plan.req[(size_t)r];
-        q.first_row = row;
-        q.n_rows = n;
-        const int word = formats[n_format == 1 ? 0 : r];
-        check_format_word(word);
-        q.form = format_form(word);
-        q.pad_ = format_rate(word);
-        q.src_samples = plan.cum[(size_t)(row + n)] - plan.cum[(size_t)row];
-        q.n_samples = resampled_samples(q.pad_, q.src_samples);
-        q.y_off = 0;
-        if (q.pad_) {
-            q.y_off = plan.y_floats;
-            plan.y_floats += q.n_samples;
-            plan.max_resampled = q.n_samples > plan.max_resampled ? q.n_samples : plan.max_resampled;
-        }
-        q.out_off = plan.total_bytes;
-        q.out_bytes = pack_request_bytes(word, q.src_samples);
-        plan.total_bytes += q.out_bytes;
-        const long units = ((q.out_off & 15) + q.out_bytes + 15) / 16;
-        plan.max_units = units > plan.max_units ? units : plan.max_units;
-        row += n;
-    }
-    KX_REQUIRE(row == B, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
-}
-}  // namespace
-
-void build_pack_plan(const int* frames, int B, const int* chunks_per_request, int R, const int* formats, int n_format,
-                     PackPlan& plan) {
-    KX_REQUIRE(frames && formats && B >= 1 && R >= 1 && (n_format == 1 || n_format == R), "pack: bad argument");
-    plan.cum.assign((size_t)B + 1, 0);
-    for (int b = 0; b < B; ++b) {
-        KX_REQUIRE(frames[b] >= 0, "pack: negative frame count");
-        plan.cum[(size_t)b + 1] = plan.cum[(size_t)b] + 600L * frames[b];
-    }
-    fill_pack_requests(B, chunks_per_request, R, formats, n_format, plan);
-}
-
-void build_join_plan(const int* frames, const int* lens, const int* edges, int B, const int* chunks_per_request, int R,
-                     const int* formats, int n_format, const JoinSpec* joins, int n_join, PackPlan& plan, JoinPlan& join) {
-    KX_REQUIRE(frames && lens && edges && formats && joins && B >= 1 && R >= 1 && (n_format == 1 || n_format == R) &&
-                   (n_join == 1 || n_join == R), "join: bad argument");
-    join.row.assign((size_t)B, JoinRow{});
-    join.any = false;
+void build_output_plan(const int* frames, const int* lens, const int* edges, int B, const RequestLayout& lay, OutputPlan& plan) {
+    const int R = lay.R;
+    KX_REQUIRE(frames && lay.formats && B >= 1 && R >= 1 && (lay.n_format == 1 || lay.n_format == R) &&
+                   (!lay.joins || (edges && (lay.n_join == 1 || lay.n_join == R))) && (lens || (!lay.marks && !lay.joins)),
+               "plan: bad argument");
+    auto rows_of = [&](int r) { return lay.chunks_per_request ? lay.chunks_per_request[r] : 1; };
+    // the rows: what each contributes to its request's stream, and the prefix over it.  (A pass of its own: the refusals of the
+    // rows speak before those of the request table below, whichever request they are in, and callers match on the text.)
+    const JoinSpec as_it_is{};
+    plan.join.assign((size_t)B, JoinRow{});
+    plan.joined = false;
     plan.cum.assign((size_t)B + 1, 0);
     int row = 0;
     for (int r = 0; r < R; ++r) {
-        const int n = chunks_per_request ? chunks_per_request[r] : 1;
+        const int n = rows_of(r);
         KX_REQUIRE(n >= 1 && n <= B - row, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
-        const JoinSpec& js = joins[n_join == 1 ? 0 : r];
+        const JoinSpec& js = lay.joins ? lay.joins[lay.n_join == 1 ? 0 : r] : as_it_is;
         KX_REQUIRE(join_spec_ok(js), "infer: bad join");
-        join.any = join.any || !join_spec_plain(js);
+        plan.joined = plan.joined || !join_spec_plain(js);
         const long k = 24L * js.keep_ms, fade = 24L * js.fade_ms;
         for (int b = row; b < row + n; ++b) {
-            KX_REQUIRE(frames[b] >= 0 && edges[2 * b] >= 0 && edges[2 * b + 1] >= 0, "pack: negative frame count");
-            const bool first = b == row, last = b == row + n - 1, long_enough = lens[b] >= 3;  // (shorter rows are pads only)
+            KX_REQUIRE(frames[b] >= 0 && (!lay.joins || (edges[2 * b] >= 0 && edges[2 * b + 1] >= 0)), "pack: negative frame count");
+            const bool first = b == row, last = b == row + n - 1, long_enough = js.flags != 0 && lens[b] >= 3;  // (shorter rows are pads only)
             const bool head = long_enough && (js.flags & (first ? JOIN_TRIM_HEAD : JOIN_TRIM_INNER)) != 0;
             const bool tail = long_enough && (js.flags & (last ? JOIN_TRIM_TAIL : JOIN_TRIM_INNER)) != 0;
-            JoinRow& j = join.row[(size_t)b];
-            const long lead = 600L * edges[2 * b] - k, trail = 600L * edges[2 * b + 1] - k;
-            j.skip = head && lead > 0 ? lead : 0;
-            const long cut = tail && trail > 0 ? trail : 0;
+            JoinRow& j = plan.join[(size_t)b];
+            const long lead = head ? 600L * edges[2 * b] - k : 0, trail = tail ? 600L * edges[2 * b + 1] - k : 0;
+            j.skip = lead > 0 ? lead : 0;
+            const long cut = trail > 0 ? trail : 0;
             j.keep = 600L * frames[b] - j.skip - cut;
             j.gap = last ? 0 : 24L * js.pause_ms;
             j.fade_head = head ? (int)fade : 0;
@@ -267,45 +207,58 @@ void build_join_plan(const int* frames, const int* lens, const int* edges, int B
         row += n;
     }
     KX_REQUIRE(row == B, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
-    fill_pack_requests(B, chunks_per_request, R, formats, n_format, plan);
-}
-
-void build_mark_plan(const PackPlan& plan, const int* lens, const int* chunks_per_request, int R, const int* formats,
-                     int n_format, const uint8_t* req_marks, MarkPlan& mp, const JoinPlan* join) {
-    const int B = (int)plan.cum.size() - 1;
-    KX_REQUIRE(lens && formats && B >= 1 && R >= 1 && (int)plan.req.size() == R && (n_format == 1 || n_format == R) &&
-                   (!join || (int)join->row.size() == B), "marks: bad argument");
-    mp.row.assign((size_t)B, MarkRow{-1, 0, 0});
-    mp.count.assign((size_t)R, 0);
-    mp.first.assign((size_t)R, 0);
-    mp.marks_off = (plan.total_bytes + 7) & ~7L;
-    mp.n_marks = 0;
-    int row = 0;
+    // the requests: the table of the packer and the resampler over that prefix, and the rows' marks behind the bodies
+    plan.req.assign((size_t)R, PackReq{});
+    plan.total_bytes = plan.max_units = plan.y_floats = plan.max_resampled = 0;
+    plan.mark.assign(lens ? (size_t)B : 0, MarkRow{-1, 0, 0});
+    plan.count.assign((size_t)R, 0);
+    plan.first.assign((size_t)R, 0);
+    plan.n_marks = 0;
+    row = 0;
     for (int r = 0; r < R; ++r) {
-        const int n = chunks_per_request ? chunks_per_request[r] : 1;
-        const PackReq& q = plan.req[(size_t)r];
-        KX_REQUIRE(q.first_row == row && q.n_rows == n && n <= B - row, "marks: the grouping is not the plan's");
-        const int word = formats[n_format == 1 ? 0 : r];
+        const int n = rows_of(r);
+        PackReq& q = plan.req[(size_t)r];
+        q.first_row = row;
+        q.n_rows = n;
+        const int word = lay.formats[lay.n_format == 1 ? 0 : r];
         check_format_word(word);
-        const long K = frame_samples(format_rate(word));
-        mp.first[(size_t)r] = mp.n_marks;
-        for (int b = row; b < row + n; ++b) {
-            KX_REQUIRE(lens[b] >= 1 && lens[b] <= 512, "infer: token count must be 1..512");
-            MarkRow& m = mp.row[(size_t)b];
-            m.K = K;
-            m.src_base = plan.cum[(size_t)b] - plan.cum[(size_t)row];
-            m.base = m.src_base * K / 600;  // (exact: cum counts multiples of 24 samples, 600 per frame in a plain plan)
-            m.skip = join ? join->row[(size_t)b].skip : 0;
-            m.keep = join ? join->row[(size_t)b].keep : plan.cum[(size_t)b + 1] - plan.cum[(size_t)b];
-            if (req_marks && req_marks[r]) {
-                m.first = mp.n_marks;
-                mp.n_marks += lens[b] + 1;
+        q.form = format_form(word);
+        q.rate = format_rate(word);
+        q.src_samples = plan.cum[(size_t)(row + n)] - plan.cum[(size_t)row];
+        q.n_samples = resampled_samples(q.rate, q.src_samples);
+        q.y_off = 0;
+        if (q.rate) {
+            q.y_off = plan.y_floats;
+            plan.y_floats += q.n_samples;
+            plan.max_resampled = q.n_samples > plan.max_resampled ? q.n_samples : plan.max_resampled;
+        }
+        q.out_off = plan.total_bytes;
+        q.out_bytes = pack_request_bytes(word, q.src_samples);
+        plan.total_bytes += q.out_bytes;
+        const long units = ((q.out_off & 15) + q.out_bytes + 15) / 16;
+        plan.max_units = units > plan.max_units ? units : plan.max_units;
+        plan.first[(size_t)r] = plan.n_marks;
+        if (lens) {
+            const long K = frame_samples(q.rate);
+            for (int b = row; b < row + n; ++b) {
+                KX_REQUIRE(lens[b] >= 1 && lens[b] <= 512, "infer: token count must be 1..512");
+                MarkRow& m = plan.mark[(size_t)b];
+                m.K = K;
+                m.src_base = plan.cum[(size_t)b] - plan.cum[(size_t)row];
+                m.base = m.src_base * K / 600;  // (exact: cum counts multiples of 24 samples)
+                m.skip = plan.join[(size_t)b].skip;
+                m.keep = plan.join[(size_t)b].keep;
+                if (lay.marks && lay.marks[r]) {
+                    m.first = plan.n_marks;
+                    plan.n_marks += lens[b] + 1;
+                }
             }
         }
-        mp.count[(size_t)r] = mp.n_marks - mp.first[(size_t)r];
+        plan.count[(size_t)r] = plan.n_marks - plan.first[(size_t)r];
         row += n;
     }
-    KX_REQUIRE(row == B, "marks: the grouping is not the plan's");
+    plan.marks_off = (plan.total_bytes + 7) & ~7L;
 }
 
 }  // namespace kx
+

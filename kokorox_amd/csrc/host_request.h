@@ -25,6 +25,18 @@ inline bool join_spec_ok(const JoinSpec& j) {
 }
 inline bool join_spec_plain(const JoinSpec& j) { return j.flags == 0 && j.keep_ms == 0 && j.pause_ms == 0 && j.fade_ms == 0; }
 
+// What a call asks of the output stage (a view: the arrays are the caller's): how its rows group into requests, and each
+// request's format word, wish for token marks and join spec.  build_output_plan and output_bounds take it.
+struct RequestLayout {
+    const int32_t* chunks_per_request;  // [R] rows of each request; null: every row a request of its own, and R = B
+    int R;
+    const int32_t* formats;             // [n_format] format words (check_format_word), n_format = 1 (shared) or R
+    int n_format;
+    const uint8_t* marks;               // [R] request r wants token marks when marks[r] != 0; null: none does
+    const JoinSpec* joins;              // [n_join] with n_join = 1 (shared) or R; null: the rows are appended as they are
+    int n_join;
+};
+
 // general host entry behind kx_infer / kx_infer_voices / kx_infer_packed / kx_infer_requests (Model::infer_host_ex)
 struct HostCall {
     const float* styles = nullptr;       // host [B][256], or
@@ -53,10 +65,11 @@ struct HostCall {
     bool grouped() const { return chunks_per_request != nullptr; }
     bool by_voice() const { return voice_ids != nullptr; }
     int kind_of(int b) const { return kinds ? kinds[b] : (by_voice() ? (max_mix == 1 ? 1 : 2) : 0); }
-    // the call as build_pack_plan takes it: a call without chunks_per_request is B single-row requests sharing `format`
-    int regions(int B) const { return grouped() ? n_requests : B; }
-    const int32_t* words() const { return grouped() ? req_formats : &format; }
-    int n_words() const { return grouped() ? n_req_formats : 1; }
+    // what the call asks of the output stage: a call without chunks_per_request is B single-row requests sharing `format`
+    RequestLayout layout(int B) const {
+        if (!grouped()) return RequestLayout{nullptr, B, &format, 1, nullptr, nullptr, 0};
+        return RequestLayout{chunks_per_request, n_requests, req_formats, n_req_formats, req_marks, req_joins, n_req_joins};
+    }
 };
 
 // ---- the refusals, side by side.  The two entries word some of them differently (a row longer than the stride, for one):
@@ -96,92 +109,77 @@ struct ResampleFilter {
 const ResampleFilter& resample_filter(int rate_code);  // throws KX_ERR_INVALID outside 1..3
 long resampled_samples(int rate_code, long n_samples);  // n_samples L / M (exact for whole frames); code 0: n_samples
 
-// ---- requests of several chunks, packed as the bytes a server sends (kernels_misc.hip: pack_requests_kernel) ----------
+// ---- the output stage of a call: every request packed as the bytes a server sends (request_kernels.hip) ----------------------
 // A request is n_rows consecutive rows of the audio slab; its output is a function of a virtual byte stream: the header of
 // its form (if any), then the sample bytes of its rows in order with nothing between them.  Forms 0..2 are the bare samples
-// (f32, f32 written twice, PCM16: kernels_misc.hip, pcm16_sample), 3 = 44-byte float WAV header + f32 bit copies, 4 = base64
+// (f32, f32 written twice, PCM16: request_kernels.hip, pcm16_sample), 3 = 44-byte float WAV header + f32 bit copies, 4 = base64
 // of a 16-bit WAV file, 8 / 9 = G.711 bytes (include/kokorox_hip.h, KX_PACK_*).  With a rate code the stream is first resampled as a whole (resample_requests_kernel) into a buffer of
 // plan.y_floats floats, and the packer reads the request as ONE row of that buffer.
 struct PackReq {
-    int first_row, n_rows, form, pad_;  // form = bits 0..7 of the word; pad_ = its rate code
+    int first_row, n_rows, form, rate;  // form = bits 0..7 of the word; rate = its rate code
     long out_off;      // byte offset of the request's region in the compact output (a multiple of 4)
     long out_bytes;    // size of the region (a multiple of 4 in every form)
-    long n_samples;    // samples of the region, at the output rate: 600 * the sum of its rows' frames * L / M
-    long src_samples;  // 600 * the sum of its rows' frames
+    long n_samples;    // samples of the region, at the output rate: the samples of its stream * L / M
+    long src_samples;  // samples of its stream at 24 000 Hz: 600 * the sum of its rows' frames when nothing joins them
     long y_off;        // rate code != 0: floats before the request's resampled stream in the intermediate buffer
 };
-struct PackPlan {
-    std::vector<PackReq> req;
-    std::vector<long> cum;  // [B + 1] samples of the rows before row b, over the whole batch
-    long total_bytes = 0;
-    long max_units = 0;     // 16-byte units of the largest region (the launch's grid)
-    long y_floats = 0;      // floats of the intermediate buffer: the resampled streams back to back (0: nothing to resample)
-    long max_resampled = 0;  // most output samples of one resampled request (the resampler's grid)
-};
-// `form` = a format word, n_samples at 24 000 Hz.  throws KX_ERR_INVALID: unknown word, 16-bit WAV past 4 GiB
-long pack_request_bytes(int form, long n_samples);
-// Worst case of a batch's compact output before the frame counts are known: R requests, n_samples samples (at 24 000 Hz) in
-// all, every request in the widest of the given words (48 000 Hz doubles the samples; the per-request header and the base64
-// padding do not scale with the samples).
-size_t pack_requests_bound(const int* formats, int n_format, int R, size_t n_samples);
-// ... and of the intermediate buffer of the resampled streams, in floats: 0 when no word carries a rate code
-size_t resample_floats_bound(const int* formats, int n_format, size_t n_samples);
-// chunks_per_request [R] (null: every row a request of its own, R = B), formats [n_format] (words), n_format = 1 or R
-void build_pack_plan(const int* frames, int B, const int* chunks_per_request, int R, const int* formats, int n_format,
-                     PackPlan& plan);
-
-// ---- token timing marks behind the bodies (kernels_misc.hip: token_marks_kernel) ------------------------------------------
-// The marks of a request (include/kokorox_hip.h has the definition): per chunk its tokens + 1 int64 sample offsets at the
-// request's output rate.  They live in a block of their own in the packed buffer, at plan.total_bytes rounded up to 8, the
-// requests that want them back to back in request order, so body and marks leave the device in one copy.  One MarkRow per
-// ROW of the batch; the packer's and the resampler's table (PackReq) does not know about marks.
-struct MarkRow {
-    long first;  // index (in int64 values) of the row's first mark in the marks block; -1: its request wants none
-    long base;   // the row's first mark: the samples of the request's earlier rows (their pauses included) x L / M
-    long K;      // output samples per frame: 600 L / M of the request's rate (600, 200, 400, 1200)
-    // what the joined form of the kernel clamps with (a plain row: skip = 0, keep = 600 x its frames), at 24 000 Hz
-    long src_base = 0;  // samples of the request's stream before the row: base = src_base x L / M
-    long skip = 0, keep = 0;
-};
-struct MarkPlan {
-    std::vector<MarkRow> row;  // [B]
-    std::vector<long> count;   // [R] marks of request r: the sum over its rows of lens + 1, or 0 when it wants none
-    std::vector<long> first;   // [R] index of request r's first mark in the block
-    long marks_off = 0;        // byte offset of the block in the packed buffer (a multiple of 8, >= plan.total_bytes)
-    long n_marks = 0;          // int64 values of the block
-    long end_bytes() const { return marks_off + 8 * n_marks; }  // bytes of body + marks: what one copy brings to the host
-};
-inline long frame_samples(int rate_code) { return rate_code == 1 ? 200 : (rate_code == 2 ? 400 : (rate_code == 3 ? 1200 : 600)); }
-// plan: build_pack_plan's result for the same rows and grouping; lens [B] tokens per row; formats [n_format] as there;
-// req_marks [R], null = no request wants marks (the block is then empty)
-// join: the join plan the pack plan was built with (build_join_plan), null = rows appended
-struct JoinPlan;
-void build_mark_plan(const PackPlan& plan, const int* lens, const int* chunks_per_request, int R, const int* formats,
-                     int n_format, const uint8_t* req_marks, MarkPlan& out, const JoinPlan* join = nullptr);
-
-// ---- joins: a kept segment of each row, then a run of zeros (include/kokorox_hip.h, "joins") -------------------------------
-// Row b of a request contributes x[skip .. skip + keep) of its 600 frames[b] valid samples, the first fade_head and the last
-// fade_tail of them faded, then gap zeros.  The packer's and the resampler's staging step read this table beside the prefix
-// table, which in a joined plan runs over keep + gap (PackPlan::cum), so PackReq's sizes follow the joined stream S'.
+// Joins: a kept segment of each row, then a run of zeros (include/kokorox_hip.h, "joins").  Row b of a request contributes
+// x[skip .. skip + keep) of its 600 frames[b] valid samples, the first fade_head and the last fade_tail of them faded, then gap
+// zeros.  The staging step of the joined packer and resampler reads this table beside the prefix table, which runs over
+// keep + gap (OutputPlan::cum), so PackReq's sizes follow the joined stream S'.  A row nothing shapes: {0, 600 frames[b], 0, 0, 0}.
 struct JoinRow {
     long skip, keep, gap;      // samples at 24 000 Hz, multiples of 24
     int fade_head, fade_tail;  // 24 fade_ms where that edge is trimmed, else 0
 };
-struct JoinPlan {
-    std::vector<JoinRow> row;  // [B]
-    bool any = false;          // some request's spec is not all zeros: the joined form of the kernels is launched
+// Token timing marks behind the bodies (request_kernels.hip: token_marks_kernel; include/kokorox_hip.h has the definition):
+// per chunk its tokens + 1 int64 sample offsets at the request's output rate.  They live in a block of their own in the packed
+// buffer, at total_bytes rounded up to 8, the requests that want them back to back in request order, so body and marks leave
+// the device in one copy.  One MarkRow per ROW of the batch; the packer's and the resampler's table (PackReq) does not know
+// about marks.
+struct MarkRow {
+    long first;  // index (in int64 values) of the row's first mark in the marks block; -1: its request wants none
+    long base;   // the row's first mark: the samples of the request's earlier rows (their pauses included) x L / M
+    long K;      // output samples per frame: 600 L / M of the request's rate (600, 200, 400, 1200)
+    // what the joined form of the kernel clamps with (the row's JoinRow), at 24 000 Hz
+    long src_base = 0;  // samples of the request's stream before the row: base = src_base x L / M
+    long skip = 0, keep = 0;
 };
-// frames [B], lens [B], edges [B][2] = the used durations of each row's first and last token (frames), joins [n_join] with
-// n_join = 1 or R; everything else as build_pack_plan, whose plan it fills for the joined streams.
-void build_join_plan(const int* frames, const int* lens, const int* edges, int B, const int* chunks_per_request, int R,
-                     const int* formats, int n_format, const JoinSpec* joins, int n_join, PackPlan& plan, JoinPlan& join);
-// samples (at 24 000 Hz) the pauses add to a call before its frame counts are known: 24 pause_ms (rows_r - 1) per request
-size_t join_pause_samples(const int* chunks_per_request, int R, const JoinSpec* joins, int n_join);
+inline long frame_samples(int rate_code) { return rate_code == 1 ? 200 : (rate_code == 2 ? 400 : (rate_code == 3 ? 1200 : 600)); }
 
-// Bytes of the packed buffer of a call of B rows before its forward has run, for n_samples samples in all: pack_requests_bound
-// over the call's words and regions.  With marks asked for (hc.req_marks; lens [B]
-// then required) 8 + 8 x the sum over the rows of lens + 1 more: the alignment gap and a block in which every request wants them.
-// With joins (hc.req_joins) n_samples grows by the pauses (join_pause_samples); trimming only shrinks.
-size_t packed_bytes_bound(const HostCall& hc, int B, size_t n_samples, const int32_t* lens = nullptr);
+// Everything the output stage of one call is launched with (kx_common.h: launch_output_plan), from build_output_plan.
+struct OutputPlan {
+    std::vector<PackReq> req;  // [R]
+    std::vector<long> cum;     // [B + 1] samples (keep + gap) of the rows before row b, over the whole batch
+    long total_bytes = 0;
+    long max_units = 0;      // 16-byte units of the largest region (the packer's grid)
+    long y_floats = 0;       // floats of the intermediate buffer: the resampled streams back to back (0: nothing to resample)
+    long max_resampled = 0;  // most output samples of one resampled request (the resampler's grid)
+    std::vector<JoinRow> join;  // [B]
+    bool joined = false;        // some request's spec is not all zeros: the joined form of the kernels is launched
+    std::vector<MarkRow> mark;  // [B]; empty when the token counts were not given
+    std::vector<long> count;    // [R] marks of request r: the sum over its rows of lens + 1, or 0 when it wants none
+    std::vector<long> first;    // [R] index of request r's first mark in the block
+    long marks_off = 0;         // byte offset of the block in the packed buffer (a multiple of 8, >= total_bytes)
+    long n_marks = 0;           // int64 values of the block
+    long end_bytes() const { return marks_off + 8 * n_marks; }  // bytes of body + marks: what one copy brings to the host
+};
+// `form` = a format word, n_samples at 24 000 Hz.  throws KX_ERR_INVALID: unknown word, 16-bit WAV past 4 GiB
+long pack_request_bytes(int form, long n_samples);
+// The plan of a call whose frame counts are known.  frames [B]; lens [B] tokens per row (may be null when the layout has
+// neither marks nor joins); edges [B][2] = the used durations of each row's first and last token, in frames (may be null when
+// it has no joins).  A layout without joins is the plain case of the same walk (JoinRow above), and so is a spec of all zeros:
+// plan.joined stays false and the plain kernels run.
+void build_output_plan(const int* frames, const int* lens, const int* edges, int B, const RequestLayout& layout, OutputPlan& plan);
+
+// What a call of B rows needs before its forward has run, for n_samples samples (at 24 000 Hz) in all -- with joins the pauses
+// come on top, 24 pause_ms (rows_r - 1) per request; trimming only shrinks.  packed_bytes: R requests, every one in the widest
+// of the layout's words (48 000 Hz doubles the samples; the per-request header and the base64 padding do not scale with the
+// samples); with marks (lens [B] then required) 8 + 8 x the sum over the rows of lens + 1 more: the alignment gap and a block
+// in which every request wants them.  y_floats: the intermediate buffer of the resampled streams, 0 when no word carries a
+// rate code.
+struct OutputBounds {
+    size_t packed_bytes, y_floats;
+};
+OutputBounds output_bounds(const RequestLayout& layout, int B, size_t n_samples, const int32_t* lens);
 
 }  // namespace kx

@@ -286,17 +286,25 @@ void launch_diag_stats(const float* x, long bs, int ld, int C, LenMap len, int B
 void launch_style_mix(const float* table, int n_voices, const int* voice_ids, const float* weights, int max_mix,
                       const int* rows, const int* kinds, float* styles, int B, hipStream_t s);
 
-// ---- requests of several chunks (host_request.h: PackReq, PackPlan, build_pack_plan): pack_requests_kernel ----------
-// and, for requests with a rate code, resample_requests_kernel before it.  d_req [R], d_cum [B + 1]: device copies of the plan;
-// d_y: plan.y_floats floats for the resampled streams (null when 0); out: 16-byte aligned, plan.total_bytes long
-// d_join [B]: the rows of a join plan (host_request.h: build_join_plan, which then also built `plan`) when the batch has a joined
-// request: the joined form of the two kernels; null: the plain kernels
-void launch_pack_plan(const float* audio, long audio_ld, const PackReq* d_req, const long* d_cum, int R, const PackPlan& plan,
-                      float* d_y, void* out, hipStream_t s, const JoinRow* d_join = nullptr);
-// token timing marks of the rows whose MarkRow::first is >= 0 (host_request.h: build_mark_plan): dur [B][512] as duration_kernel
-// wrote it, lens [B], d_rows [B] on the device; marks = the marks block, 8-byte aligned
-// joined: the batch has a joined request (token_marks_joined_kernel: the clamp to every row's kept segment)
-void launch_token_marks(const int* dur, const int* lens, const MarkRow* d_rows, int B, void* marks, hipStream_t s, bool joined = false);
+// ---- the output stage of a call (request_kernels.hip; host_request.h: OutputPlan, build_output_plan) ----------------------
+// Device memory for a plan's tables, which the launchers copy the plan into: req [R], cum [B + 1], join [B] (used by a joined
+// plan only), mark [B] (used when a request wants marks only)
+struct OutputTables {
+    PackReq* req;
+    long* cum;
+    JoinRow* join;
+    MarkRow* mark;
+};
+// Everything between "the plan is built" and "copy to the host", for the model and for the test hook: the resampler when
+// plan.y_floats > 0 (d_y: that many floats, null when 0), the packer into d_packed (16-byte aligned, plan.total_bytes long), and
+// when plan.n_marks > 0 the token marks at d_packed + plan.marks_off.  audio [B][audio_ld]; dur [B][512] as duration_kernel
+// wrote it and lens [B], both on the device.  The joined form of the kernels runs only when plan.joined.
+void launch_output_plan(const float* audio, long audio_ld, const int* dur, const int* lens, const OutputPlan& plan,
+                        const OutputTables& t, float* d_y, void* d_packed, hipStream_t s);
+// its two halves: the bodies, and the marks (n_marks > 0) into a block of their own, 8-byte aligned
+void launch_pack_plan(const float* audio, long audio_ld, const OutputPlan& plan, const OutputTables& t, float* d_y, void* out,
+                      hipStream_t s);
+void launch_token_marks(const int* dur, const int* lens, const OutputPlan& plan, const OutputTables& t, void* marks, hipStream_t s);
 // edges [B][2] = {dur[b][0], dur[b][lens[b] - 1]} (8-byte aligned): what the host's join plan needs beside the frame counts
 void launch_edge_durations(const int* dur, const int* lens, int* edges, int B, hipStream_t s);
 // Host output buffers of the kx_infer* calls: page-locked and pooled (one asynchronous D2H copy at PCIe rate instead

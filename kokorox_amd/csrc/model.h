@@ -380,9 +380,7 @@ class Model {
                          uint64_t seed, uint32_t flags, const HostCall& hc, void** out, int64_t* out_bytes, int64_t* out_samples,
                          int64_t** out_marks, int64_t* out_n_marks);
     // host staging that asynchronous copies read / write: outlives the calling frame
-    PackPlan pack_plan_;               // request table + sample prefixes of the running call
-    MarkPlan mark_plan_;               // per-row table of the token marks of the running call
-    JoinPlan join_plan_;               // per-row kept segments and pauses of the running call (a call with joins)
+    OutputPlan output_plan_;           // the tables of the running call's output stage: requests, prefixes, joins, marks
     bool want_edges_ = false;          // the running host call has joins: front_half brings the rows' edge durations back
     std::vector<int> h_edge_;          // [B][2] used durations of every row's first and last token (valid when want_edges_)
     unsigned h_bad_id_ = 0;

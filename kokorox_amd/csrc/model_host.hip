@@ -132,12 +132,12 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     check_host_call(ids, t_stride, lens, B, speeds, hc, out, out_bytes, out_samples, n_vocab_, n_voices_, d_voices_ != nullptr);
     if (hc.join_call) check_join_call(hc);
     if (hc.req_marks) check_marks_call(hc, out_marks, out_n_marks);
-    const bool joins = hc.req_joins != nullptr;
     const bool by_voice = hc.by_voice();
-    const bool marks = hc.req_marks != nullptr;  // (with chunks_per_request then: check_marks_call)
     // one way to lay the output out and pack it: a call without chunks_per_request is R = B single-row requests in hc.format
-    const int R = hc.regions(B), n_words = hc.n_words();
-    const int32_t* words = hc.words();
+    const RequestLayout layout = hc.layout(B);
+    const int R = layout.R;
+    const bool joins = layout.joins != nullptr;
+    const bool marks = layout.marks != nullptr;  // (with chunks_per_request then: check_marks_call)
     KX_HIP(hipSetDevice(device));
     // I/O staging lives in its own arena: ids, styles, frames, noise keys, voice picks, audio, packed audio
     int64_t* d_ids;
@@ -145,10 +145,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     int* d_fr;
     uint64_t* d_seeds;
     uint32_t* d_uidx;
-    PackReq* d_req = nullptr;
-    MarkRow* d_mrow = nullptr;
-    JoinRow* d_jrow = nullptr;
-    long* d_cum = nullptr;
+    OutputTables tables{};
     float* d_y = nullptr;  // the resampled streams of the requests with a rate code, back to back
     int *d_vid, *d_rows, *d_kinds;
     float* d_w;
@@ -164,14 +161,13 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         d_rows = A.i(B);
         d_kinds = A.i(B);
         d_w = A.f((size_t)B * mm);
-        d_req = static_cast<PackReq*>(A.alloc((size_t)R * sizeof(PackReq)));
-        d_cum = static_cast<long*>(A.alloc(((size_t)B + 1) * 8));
-        // (the pauses of a call with joins lengthen the streams; trimming only shortens them)
-        const size_t pauses = join_pause_samples(hc.chunks_per_request, R, hc.req_joins, hc.n_req_joins);
-        d_y = A.f(resample_floats_bound(words, n_words, audio_floats + pauses));  // (0 floats when no word carries a rate code)
-        if (joins) d_jrow = static_cast<JoinRow*>(A.alloc((size_t)B * sizeof(JoinRow)));
-        if (marks) d_mrow = static_cast<MarkRow*>(A.alloc((size_t)B * sizeof(MarkRow)));
-        d_packed = A.alloc(packed_bytes_bound(hc, B, audio_floats, lens));  // compact output: the requests back to back
+        tables.req = static_cast<PackReq*>(A.alloc((size_t)R * sizeof(PackReq)));
+        tables.cum = static_cast<long*>(A.alloc(((size_t)B + 1) * 8));
+        const OutputBounds bound = output_bounds(layout, B, audio_floats, lens);
+        d_y = A.f(bound.y_floats);  // (0 floats when no word carries a rate code)
+        if (joins) tables.join = static_cast<JoinRow*>(A.alloc((size_t)B * sizeof(JoinRow)));
+        if (marks) tables.mark = static_cast<MarkRow*>(A.alloc((size_t)B * sizeof(MarkRow)));
+        d_packed = A.alloc(bound.packed_bytes);  // compact output: the requests back to back, then the marks
         return A.f(audio_floats);
     };
     // worst case length is 50 frames per token; start from a typical 8 and retry once if short
@@ -213,38 +209,20 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             }
             throw;
         }
-        // frame counts are known (the forward's one host sync): the request table and the rows' sample prefixes, then ONE
-        // launch packs every request of the batch back to back on the GPU, whatever its form (and one before it, the
-        // resampler, when a request asks for another rate), then ONE asynchronous copy into a page-locked host buffer
-        PackPlan& plan = pack_plan_;
-        JoinPlan& jp = join_plan_;
-        if (joins) build_join_plan(call_.hF.data(), lens, h_edge_.data(), B, hc.chunks_per_request, R, words, n_words, hc.req_joins, hc.n_req_joins, plan, jp);
-        else build_pack_plan(call_.hF.data(), B, hc.chunks_per_request, R, words, n_words, plan);
-        const bool joined = joins && jp.any;  // (all-zero specs: the plain kernels, the plain bytes)
+        // frame counts are known (the forward's one host sync): the plan of the output stage, then ONE launch packs every
+        // request of the batch back to back on the GPU, whatever its form (one before it, the resampler, when a request asks
+        // for another rate; one behind it, the token marks, when a request wants them), then ONE asynchronous copy of bodies
+        // and marks into a page-locked host buffer.  (All-zero join specs: the plain kernels, the plain bytes.)
+        OutputPlan& plan = output_plan_;
+        build_output_plan(call_.hF.data(), lens, joins ? h_edge_.data() : nullptr, B, layout, plan);
         for (int r = 0; r < R; ++r) {
             out_samples[r] = plan.req[(size_t)r].n_samples;
             out_bytes[r] = plan.req[(size_t)r].out_bytes;
+            if (marks) out_n_marks[r] = plan.count[(size_t)r];
         }
-        int64_t total = plan.total_bytes;
-        int64_t marks_off = 0, n_marks = 0;
-        KX_HIP(hipMemcpyAsync(d_req, plan.req.data(), (size_t)R * sizeof(PackReq), hipMemcpyHostToDevice, stream_));
-        KX_HIP(hipMemcpyAsync(d_cum, plan.cum.data(), ((size_t)B + 1) * 8, hipMemcpyHostToDevice, stream_));
-        if (joined) KX_HIP(hipMemcpyAsync(d_jrow, jp.row.data(), (size_t)B * sizeof(JoinRow), hipMemcpyHostToDevice, stream_));
-        launch_pack_plan(d_audio, ld, d_req, d_cum, R, plan, d_y, d_packed, stream_, joined ? d_jrow : nullptr);
-        if (marks) {
-            // the token marks of the requests that want them, in a block of their own behind the bodies (8-aligned): one
-            // more launch on this stream, and the call's one copy to the host brings both
-            MarkPlan& mp = mark_plan_;
-            build_mark_plan(plan, lens, hc.chunks_per_request, R, words, n_words, hc.req_marks, mp, joins ? &jp : nullptr);
-            for (int r = 0; r < R; ++r) out_n_marks[r] = mp.count[(size_t)r];
-            marks_off = mp.marks_off;
-            n_marks = mp.n_marks;
-            if (n_marks > 0) {
-                KX_HIP(hipMemcpyAsync(d_mrow, mp.row.data(), (size_t)B * sizeof(MarkRow), hipMemcpyHostToDevice, stream_));
-                launch_token_marks(call_.d_dur, call_.dT, d_mrow, B, static_cast<char*>(d_packed) + marks_off, stream_, joined);
-                total = mp.end_bytes();
-            }
-        }
+        launch_output_plan(d_audio, ld, call_.d_dur, call_.dT, plan, tables, d_y, d_packed, stream_);
+        const int64_t marks_off = plan.marks_off, n_marks = plan.n_marks;
+        const int64_t total = n_marks > 0 ? plan.end_bytes() : plan.total_bytes;
         char* host = static_cast<char*>(host_out_alloc((size_t)(total > 0 ? total : 1)));
         hipError_t e = hipMemcpyAsync(host, d_packed, (size_t)total, hipMemcpyDeviceToHost, stream_);
         if (e == hipSuccess) e = hipStreamSynchronize(stream_);

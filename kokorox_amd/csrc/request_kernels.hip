@@ -1,0 +1,420 @@
+// The output stage of a call (gfx950): every request of the batch packed as the bytes a server sends -- the packer and its
+// forms (samples, WAV, base64, G.711), the output-rate resampler before it, the token timing marks behind the bodies and the
+// edge durations the host's join plan needs.  host_request.h has the tables these kernels read and the planner that fills
+// them (build_output_plan); launch_output_plan below is the one way they are launched, for the model and for the test hook.
+#include "kx_common.h"
+#include "resample_taps.h"
+
+namespace kx {
+
+// ---- output packing on device ------------------------------------------------------------------------
+// f32 stereo = every sample written twice (koko.rs:1239-1246); PCM16 = (s.clamp(-1,1) * 32767) as i16,
+// i.e. truncation toward zero (kokorox-websocket/src/lib.rs:701-704; a NaN: see pcm16_sample).
+// `(s.clamp(-1.0, 1.0) * 32767.0) as i16`: the product rounded to f32, truncated toward zero.  nan_to_zero = Rust's meaning
+// (clamp keeps a NaN and the cast turns it into 0: form 4); without it the fmaxf / fminf clamp drops the NaN and the sample
+// becomes -32767, which is what form 2 has always given (left as it is).
+__device__ __forceinline__ int pcm16_sample(float s, bool nan_to_zero) {
+    if (nan_to_zero && s != s) return 0;
+    const float c = fminf(fmaxf(s, -1.0f), 1.0f);
+    return __float2int_rz(__fmul_rn(c, 32767.0f));
+}
+
+// ---- requests of several chunks, packed as the bytes a server sends ---------------------------------------------
+// A request's region is a function of a VIRTUAL BYTE STREAM: the header of its form, then the sample bytes of its rows in
+// order (the chunk loop of koko.rs:947-1191 appends the waveforms with no cross-fade).  Forms 0..2 are the bare samples above
+// (the per-utterance entries kx_infer / kx_infer_packed / kx_infer_voices are single-row requests in those forms);
+// 3 = `WavHeader::new(1, 24000, 32).write_header` + `to_le_bytes` of every sample (kokorox/src/utils/wav.rs:18-50,
+// kokorox-openai/src/lib.rs:416-425: both size fields are the reference's 0xFFFFFFFF placeholders); 4 = standard base64 of a
+// 16-bit WAV file (`encode_audio`, kokorox-websocket/src/lib.rs:696-736), whose output group g is stream bytes 3g .. 3g + 2.
+//
+// One lane writes one 16-byte unit of the output, aligned in the compact buffer (a region starts on a multiple of 4, so its
+// first and last unit may be partial: those lanes store single dwords).  A workgroup first copies the window of the
+// request's sample stream that its 256 units need into LDS, lanes along time, looking up the row of every sample in the
+// batch's prefix table: the conversion then never sees a row boundary, and nothing at or past 600 * frames[b] of a row is
+// ever read.  (44 + 1200 k) mod 3 = 2: every chunk boundary of form 4 falls inside a base64 group.
+//
+// A request with a rate code (PackReq::rate) was resampled as a whole by resample_requests_kernel below: its stream is then
+// ONE run of n_samples floats at y + y_off, which the staging step copies instead of looking rows up; the forms apply to it
+// exactly as to the model's samples, and the WAV headers carry the chosen rate.  Forms 8 / 9 are G.711 of form 4's 16-bit
+// sample, one byte each.
+constexpr int PACK_THREADS = 256;
+constexpr int PACK_LDS = 4096 + 8;  // samples a workgroup's 4096 output bytes can need: 4096 (G.711), 2048 (PCM16), 1536 + 2 (base64)
+
+__device__ __forceinline__ uint32_t wav_header_dword(int form, long S, int j, int rate_code) {
+    const bool f32 = form == 3;
+    const uint32_t hz = rate_code == 0 ? 24000u : (rate_code == 1 ? 8000u : (rate_code == 2 ? 16000u : 48000u));
+    switch (j) {
+        case 0: return 0x46464952u;                                   // "RIFF"
+        case 1: return f32 ? 0xFFFFFFFFu : (uint32_t)(36 + 2 * S);   // file size - 8 (placeholder in the float form)
+        case 2: return 0x45564157u;                                   // "WAVE"
+        case 3: return 0x20746d66u;                                   // "fmt "
+        case 4: return 16u;
+        case 5: return (f32 ? 3u : 1u) | (1u << 16);                  // format tag (3 = IEEE float, 1 = PCM), 1 channel
+        case 6: return hz;
+        case 7: return f32 ? 4u * hz : 2u * hz;                       // bytes per second
+        case 8: return f32 ? (4u | (32u << 16)) : (2u | (16u << 16));  // block align, bits per sample
+        case 9: return 0x61746164u;                                   // "data"
+        default: return f32 ? 0xFFFFFFFFu : (uint32_t)(2 * S);
+    }
+}
+__device__ __forceinline__ uint32_t base64_char(uint32_t v) {
+    return v < 26u ? 65u + v : (v < 52u ? 71u + v : (v < 62u ? v - 4u : (v == 62u ? 43u : 47u)));
+}
+
+// G.711 of a 16-bit sample, the 16-bit-input algorithms of CPython's audioop.lin2ulaw / lin2alaw (include/kokorox_hip.h)
+__device__ __forceinline__ uint32_t g711_mulaw(int v) {
+    int p = v >> 2;
+    const uint32_t mask = p < 0 ? 0x7Fu : 0xFFu;
+    p = p < 0 ? -p : p;
+    p = (p > 8159 ? 8159 : p) + 33;
+    int seg = 0;
+    while (seg < 8 && p > (0x40 << seg) - 1) ++seg;  // first segment end 0x3F, 0x7F .. 0x1FFF that holds p
+    if (seg == 8) return 0x7Fu ^ mask;
+    return (uint32_t)((seg << 4) | ((p >> (seg + 1)) & 15)) ^ mask;
+}
+__device__ __forceinline__ uint32_t g711_alaw(int v) {
+    const uint32_t mask = v >= 0 ? 0xD5u : 0x55u;
+    const int p = (v >= 0 ? v : -v - 1) >> 3;
+    int seg = 0;
+    while (seg < 7 && p > (0x20 << seg) - 1) ++seg;  // (p <= 0xFFF: segment 7 holds whatever is left)
+    return (uint32_t)((seg << 4) | ((p >> (seg < 2 ? 1 : seg)) & 15)) ^ mask;
+}
+
+// The staging step of the packer and of the resampler: samples [lo, hi) of a request's stream into dst[0 .. hi - lo), lanes
+// along time.  Every lane finds the row of its first sample in the batch's prefix table (cum[row] <= g0 + i < cum[row + 1])
+// and walks on from there.  Plain: the rows appended, sample o of row b is audio[b ld + o].  JOINED (include/kokorox_hip.h,
+// "joins"; host_request.h: JoinRow): cum runs over keep + gap, and offset o of row b is its kept sample skip + o -- times its
+// gain when o lies in one of the two fades, which never overlap -- while o < keep, and +0 in the pause behind it.  A fade is
+// one float64 division, one float64 product and one rounding, computed here: it needs no storage.  Either way nothing at or
+// past 600 * frames[b] of a row is read (skip + keep <= 600 frames[b]), and nothing of a cut region.
+__device__ __forceinline__ float join_fade(float v, long i, int n) {
+    return (float)((double)v * ((double)(2 * i + 1) / (double)(2 * n)));
+}
+template <bool JOINED, int THREADS>
+__device__ __forceinline__ void stage_stream(float* __restrict__ dst, const float* __restrict__ audio, long audio_ld,
+                                             const long* __restrict__ cum, const JoinRow* __restrict__ jrows, int first_row,
+                                             int n_rows, long lo_i, long hi_i) {
+    const long g0 = cum[first_row];
+    const int row_end = first_row + n_rows;
+    long i = lo_i + threadIdx.x;
+    if (i < hi_i) {
+        int lo = first_row, hi = row_end - 1;  // the row of the lane's first sample: cum[row] <= g0 + i < cum[row + 1]
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (cum[mid] <= g0 + i) lo = mid; else hi = mid - 1;
+        }
+        int row = lo;
+        for (; i < hi_i; i += THREADS) {
+            while (row + 1 < row_end && cum[row + 1] <= g0 + i) ++row;
+            const long o = g0 + i - cum[row];
+            if (!JOINED) {
+                dst[i - lo_i] = audio[(long)row * audio_ld + o];
+            } else {
+                const JoinRow jr = jrows[row];
+                float v = 0.0f;
+                if (o < jr.keep) {
+                    v = audio[(long)row * audio_ld + jr.skip + o];
+                    if (o < jr.fade_head) v = join_fade(v, o, jr.fade_head);
+                    else if (jr.keep - 1 - o < jr.fade_tail) v = join_fade(v, jr.keep - 1 - o, jr.fade_tail);
+                }
+                dst[i - lo_i] = v;
+            }
+        }
+    }
+}
+
+template <bool JOINED>
+__device__ __forceinline__ void pack_requests_body(const float* __restrict__ audio, long audio_ld,
+                                                   const PackReq* __restrict__ reqs, const long* __restrict__ cum,
+                                                   const JoinRow* __restrict__ jrows, const float* __restrict__ y,
+                                                   char* __restrict__ out) {
+    __shared__ float smp[PACK_LDS];
+    const PackReq rq = reqs[blockIdx.y];
+    const long mis = rq.out_off & 15;  // the region starts `mis` bytes into its first 16-byte unit
+    const long blk_lo = (long)blockIdx.x * (PACK_THREADS * 16) - mis;
+    if (blk_lo >= rq.out_bytes) return;  // (uniform: the grid covers the largest region of the batch)
+    const long p_lo = blk_lo < 0 ? 0 : blk_lo;
+    const long p_hi = blk_lo + PACK_THREADS * 16 < rq.out_bytes ? blk_lo + PACK_THREADS * 16 : rq.out_bytes;
+    const long S = rq.n_samples;
+    // samples of the request's stream that output bytes [p_lo, p_hi) depend on
+    long s_lo, s_hi;
+    if (rq.form == 0) {
+        s_lo = p_lo >> 2, s_hi = p_hi >> 2;
+    } else if (rq.form == 1) {
+        s_lo = p_lo >> 3, s_hi = (p_hi + 7) >> 3;
+    } else if (rq.form == 2) {
+        s_lo = p_lo >> 1, s_hi = p_hi >> 1;
+    } else if (rq.form == 3) {
+        s_lo = (p_lo < 44 ? 0 : p_lo - 44) >> 2, s_hi = (p_hi < 44 ? 0 : p_hi - 44) >> 2;
+    } else if (rq.form == 4) {
+        const long k_lo = (p_lo >> 2) * 3, k_hi = (p_hi >> 2) * 3;  // stream bytes of its groups
+        s_lo = (k_lo < 44 ? 0 : k_lo - 44) >> 1, s_hi = (k_hi < 44 ? 0 : k_hi - 43) >> 1;
+    } else {
+        s_lo = p_lo, s_hi = p_hi;
+    }
+    s_hi = s_hi > S ? S : s_hi;
+    if (rq.rate) {  // (uniform) a resampled request: one contiguous run
+        const float* __restrict__ src = y + rq.y_off;
+        for (long i = s_lo + threadIdx.x; i < s_hi; i += PACK_THREADS) smp[i - s_lo] = src[i];
+    } else {
+        stage_stream<JOINED, PACK_THREADS>(smp, audio, audio_ld, cum, jrows, rq.first_row, rq.n_rows, s_lo, s_hi);
+    }
+    __syncthreads();
+    const long u_lo = blk_lo + (long)threadIdx.x * 16;  // the lane's unit, as a byte offset in the region (may start before it)
+    if (u_lo >= rq.out_bytes) return;
+    auto sample = [&](long i) { return smp[i - s_lo]; };
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long p = u_lo + 4 * j;
+        uint32_t v = 0;
+        if (p >= 0 && p < rq.out_bytes) {
+            if (rq.form == 0) {
+                v = __float_as_uint(sample(p >> 2));
+            } else if (rq.form == 1) {
+                v = __float_as_uint(sample(p >> 3));
+            } else if (rq.form == 2) {
+                v = ((uint32_t)pcm16_sample(sample(p >> 1), false) & 0xFFFFu) | ((uint32_t)pcm16_sample(sample((p >> 1) + 1), false) << 16);
+            } else if (rq.form == 3) {
+                v = p < 44 ? wav_header_dword(3, S, (int)(p >> 2), rq.rate) : __float_as_uint(sample((p - 44) >> 2));
+            } else if (rq.form >= 8) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {  // (a region of G.711 bytes is a multiple of 4 long: p + 3 is inside it)
+                    const int pcm = pcm16_sample(sample(p + t), true);
+                    v |= (rq.form == 8 ? g711_mulaw(pcm) : g711_alaw(pcm)) << (8 * t);
+                }
+            } else {
+                const long k = (p >> 2) * 3, L = 44 + 2 * S;  // group p / 4 = stream bytes k .. k + 2 of L
+                uint32_t b[3];
+#pragma unroll
+                for (int t = 0; t < 3; ++t) {
+                    const long kk = k + t;
+                    if (kk >= L) {
+                        b[t] = 0;
+                    } else if (kk < 44) {
+                        b[t] = (wav_header_dword(4, S, (int)(kk >> 2), rq.rate) >> (8 * (int)(kk & 3))) & 255u;
+                    } else {
+                        const long d = kk - 44;
+                        b[t] = ((uint32_t)pcm16_sample(sample(d >> 1), true) >> (8 * (int)(d & 1))) & 255u;
+                    }
+                }
+                const long n = L - k;  // bytes of this group: 3, or 2 / 1 in the last one ('=' padding)
+                const uint32_t c0 = base64_char(b[0] >> 2), c1 = base64_char(((b[0] & 3u) << 4) | (b[1] >> 4));
+                const uint32_t c2 = n < 2 ? 61u : base64_char(((b[1] & 15u) << 2) | (b[2] >> 6));
+                const uint32_t c3 = n < 3 ? 61u : base64_char(b[2] & 63u);
+                v = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
+            }
+        }
+        w[j] = v;
+    }
+    char* o = out + rq.out_off + u_lo;  // 16-byte aligned: out_off + u_lo = 16 * (unit index) - mis + out_off
+    if (u_lo >= 0 && u_lo + 16 <= rq.out_bytes) {
+        *reinterpret_cast<uint4*>(o) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long p = u_lo + 4 * j;
+            if (p >= 0 && p < rq.out_bytes) *reinterpret_cast<uint32_t*>(o + 4 * j) = w[j];
+        }
+    }
+}
+// (two kernels, not one with a flag: the plain form keeps its name, its arguments and its registers)
+__global__ __launch_bounds__(PACK_THREADS) void pack_requests_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                     const PackReq* __restrict__ reqs,
+                                                                     const long* __restrict__ cum,
+                                                                     const float* __restrict__ y, char* __restrict__ out) {
+    pack_requests_body<false>(audio, audio_ld, reqs, cum, nullptr, y, out);
+}
+__global__ __launch_bounds__(PACK_THREADS) void pack_requests_joined_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                            const PackReq* __restrict__ reqs,
+                                                                            const long* __restrict__ cum,
+                                                                            const JoinRow* __restrict__ jrows,
+                                                                            const float* __restrict__ y, char* __restrict__ out) {
+    pack_requests_body<true>(audio, audio_ld, reqs, cum, jrows, y, out);
+}
+
+// ---- output sample rates: a request's whole stream through a polyphase FIR, before the packer -----------------------------
+// For rate code c the ratio is L / M ((1, 3), (2, 3), (2, 1)), C = 24 max(L, M), N = 2 C + 1 taps h (resample_taps.h), and
+//     y[n] = f32( sum over j ascending, 0 <= j < S, 0 <= n M - j L + C < N, of f64(h[n M - j L + C]) * f64(x[j]) )
+// with a float64 accumulator from +0, one addition per term and one round-to-nearest-even conversion at the end: a product
+// of two float32 values is exact in float64, so a fused multiply-add and a multiply and an add give the same bits, and a
+// host loop in the same order reproduces y bit for bit (kokorox_amd/voices.py: resample_stream).  x is the request's stream
+// as the packer defines it: a chunk boundary is invisible, and nothing at or past 600 * frames[b] of a row is read.
+//
+// A workgroup owns RS_WINDOW consecutive outputs of one request, lane t the outputs n0 + t + 256 k.  It stages the inputs
+// those outputs touch into LDS with the packer's row lookup, and the taps as float64; every lane then runs its chains out
+// of LDS.  Neighbouring lanes read inputs 3 (8 kHz), 1 or 2 (16 kHz) and 0 or 1 (48 kHz) dwords apart: conflict-free, at
+// most two-way, and pairwise broadcast; the taps are one address per phase.
+constexpr int RS_THREADS = 256;
+constexpr int RS_WINDOW = 1024;
+constexpr int RS_MAX_TAPS = KX_RESAMPLE_NTAPS_8000;
+// inputs of a window: floor(((n0 + 1023) M + C) / L) - ceil((n0 M - C) / L) + 1 <= (1023 M + 2 C) / L + 1 = 3214 at 8 kHz
+constexpr int RS_LDS = 3 * (RS_WINDOW - 1) + (RS_MAX_TAPS - 1) + 1 + 2;
+static_assert(KX_RESAMPLE_NTAPS_16000 <= RS_MAX_TAPS && KX_RESAMPLE_NTAPS_48000 <= RS_MAX_TAPS, "the 8 kHz table is the longest");
+__device__ const uint32_t resample_tap_bits[3][RS_MAX_TAPS] = {{KX_RESAMPLE_TAPS_8000}, {KX_RESAMPLE_TAPS_16000}, {KX_RESAMPLE_TAPS_48000}};
+
+template <bool JOINED>
+__device__ __forceinline__ void resample_requests_body(const float* __restrict__ audio, long audio_ld,
+                                                       const PackReq* __restrict__ reqs, const long* __restrict__ cum,
+                                                       const JoinRow* __restrict__ jrows, float* __restrict__ y) {
+    __shared__ float xs[RS_LDS];
+    __shared__ double hs[RS_MAX_TAPS];
+    const PackReq rq = reqs[blockIdx.y];
+    if (rq.rate == 0) return;  // (uniform) a request at 24 kHz: the packer reads the model's slab
+    const long n0 = (long)blockIdx.x * RS_WINDOW;
+    if (n0 >= rq.n_samples) return;  // (uniform: the grid covers the longest resampled request)
+    const long n1 = n0 + RS_WINDOW < rq.n_samples ? n0 + RS_WINDOW : rq.n_samples;
+    const int L = rq.rate == 1 ? 1 : 2, M = rq.rate == 3 ? 1 : 3, C = rq.rate == 3 ? 48 : 72, N = 2 * C + 1;
+    const long S = rq.src_samples;
+    // inputs some output of [n0, n1) touches: ceil((n0 M - C) / L) .. floor(((n1 - 1) M + C) / L), inside the stream
+    const long a_lo = n0 * M - C;
+    const long j_lo = a_lo <= 0 ? 0 : (a_lo + L - 1) / L;
+    long j_hi = ((n1 - 1) * M + C) / L + 1;
+    j_hi = j_hi > S ? S : j_hi;
+    for (int t = threadIdx.x; t < N; t += RS_THREADS) hs[t] = (double)__uint_as_float(resample_tap_bits[rq.rate - 1][t]);
+    stage_stream<JOINED, RS_THREADS>(xs, audio, audio_ld, cum, jrows, rq.first_row, rq.n_rows, j_lo, j_hi);
+    __syncthreads();
+    float* __restrict__ dst = y + rq.y_off;
+    for (long n = n0 + threadIdx.x; n < n1; n += RS_THREADS) {
+        const long a = n * M - C;
+        const long jl = a <= 0 ? 0 : (a + L - 1) / L;  // >= j_lo, as n >= n0
+        long jh = (n * M + C) / L;                      // < j_hi, as n < n1
+        jh = jh > S - 1 ? S - 1 : jh;
+        int idx = (int)(n * M - jl * L) + C;            // <= 2 C, as jl L >= n M - C; stays >= 0 down to j = jh
+        const float* xp = xs + (jl - j_lo);
+        double acc = 0.0;
+        for (long j = jl; j <= jh; ++j, idx -= L) acc += hs[idx] * (double)*xp++;
+        dst[n] = (float)acc;
+    }
+}
+__global__ __launch_bounds__(RS_THREADS) void resample_requests_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                        const PackReq* __restrict__ reqs,
+                                                                        const long* __restrict__ cum, float* __restrict__ y) {
+    resample_requests_body<false>(audio, audio_ld, reqs, cum, nullptr, y);
+}
+__global__ __launch_bounds__(RS_THREADS) void resample_requests_joined_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                               const PackReq* __restrict__ reqs,
+                                                                               const long* __restrict__ cum,
+                                                                               const JoinRow* __restrict__ jrows,
+                                                                               float* __restrict__ y) {
+    resample_requests_body<true>(audio, audio_ld, reqs, cum, jrows, y);
+}
+
+// The bodies of a plan: its request table, prefixes and (a joined plan) join rows copied into `t`, the resampler when some
+// request carries a rate code, then the packer.  d_y: plan.y_floats floats (may be null when that is 0); out: 16-byte aligned,
+// plan.total_bytes long.  The joined form of the two kernels runs only when the plan says so (OutputPlan::joined).
+void launch_pack_plan(const float* audio, long audio_ld, const OutputPlan& plan, const OutputTables& t, float* d_y, void* out,
+                      hipStream_t s) {
+    if (plan.max_units <= 0) return;
+    const size_t R = plan.req.size(), B = plan.join.size();
+    KX_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0 && R <= 65535, "pack: unaligned output or too many requests");
+    KX_HIP(hipMemcpyAsync(t.req, plan.req.data(), R * sizeof(PackReq), hipMemcpyHostToDevice, s));
+    KX_HIP(hipMemcpyAsync(t.cum, plan.cum.data(), (B + 1) * sizeof(long), hipMemcpyHostToDevice, s));
+    if (plan.joined) KX_HIP(hipMemcpyAsync(t.join, plan.join.data(), B * sizeof(JoinRow), hipMemcpyHostToDevice, s));
+    if (plan.y_floats > 0) {
+        KX_REQUIRE(d_y != nullptr, "pack: no buffer for the resampled streams");
+        const dim3 grid((unsigned)((plan.max_resampled + RS_WINDOW - 1) / RS_WINDOW), (unsigned)R);
+        if (plan.joined)
+            hipLaunchKernelGGL(resample_requests_joined_kernel, grid, dim3(RS_THREADS), 0, s, audio, audio_ld, t.req, t.cum, t.join, d_y);
+        else
+            hipLaunchKernelGGL(resample_requests_kernel, grid, dim3(RS_THREADS), 0, s, audio, audio_ld, t.req, t.cum, d_y);
+        KX_HIP(hipGetLastError());
+    }
+    const dim3 grid((unsigned)((plan.max_units + PACK_THREADS - 1) / PACK_THREADS), (unsigned)R);
+    if (plan.joined)
+        hipLaunchKernelGGL(pack_requests_joined_kernel, grid, dim3(PACK_THREADS), 0, s, audio, audio_ld, t.req, t.cum, t.join, d_y,
+                           static_cast<char*>(out));
+    else
+        hipLaunchKernelGGL(pack_requests_kernel, grid, dim3(PACK_THREADS), 0, s, audio, audio_ld, t.req, t.cum, d_y,
+                           static_cast<char*>(out));
+    KX_HIP(hipGetLastError());
+}
+
+// ---- token timing marks (include/kokorox_hip.h has the definition; host_request.h: MarkRow, build_output_plan) ----------------
+// One workgroup of 512 per row: lane t holds the duration of token t (0 at and beyond lens[b]: the front half leaves those
+// entries of `dur` unwritten, they are never loaded), an exclusive scan in 64 bits, and lane t stores base + K x scan[t] as one
+// 8-byte value, coalesced along t; the lane of the last token stores entry T, the row's end, as well.  The scan is one
+// __shfl_up ladder inside each wave64 and ONE exchange of the eight wave totals through LDS (one barrier).
+// JOINED (a batch with a joined request): the value is (src_base + clamp(600 x scan - skip, 0, keep)) L / M, written as x K / 600
+// -- every term is a multiple of 24 and K of 200, so the division is exact; a plain row (skip 0, keep 600 x its frames) gives
+// base + K x scan as before.
+constexpr int MARK_THREADS = 512;
+template <bool JOINED>
+__device__ __forceinline__ void token_marks_body(const int* __restrict__ dur, const int* __restrict__ lens,
+                                                 const MarkRow* __restrict__ rows, long long* __restrict__ marks) {
+    __shared__ long long wave_total[MARK_THREADS / 64];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const MarkRow mr = rows[b];
+    if (mr.first < 0) return;  // (the whole workgroup: its request wants no marks)
+    const int T = min(lens[b], MARK_THREADS);
+    const long long d = t < T ? (long long)dur[(long)b * 512 + t] : 0;
+    const int lane = t & 63, wave = t >> 6;
+    long long incl = d;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long v = __shfl_up(incl, o);
+        if (lane >= o) incl += v;
+    }
+    if (lane == 63) wave_total[wave] = incl;
+    __syncthreads();
+    long long before = 0;
+#pragma unroll
+    for (int w = 0; w < MARK_THREADS / 64; ++w) before += w < wave ? wave_total[w] : 0;
+    incl += before;
+    auto mark = [&](long long scan) -> long long {
+        if (!JOINED) return mr.base + mr.K * scan;
+        long long u = 600 * scan - mr.skip;
+        u = u < 0 ? 0 : (u > mr.keep ? mr.keep : u);
+        return (mr.src_base + u) * mr.K / 600;
+    };
+    if (t < T) {
+        marks[mr.first + t] = mark(incl - d);
+        if (t == T - 1) marks[mr.first + T] = mark(incl);
+    }
+}
+__global__ __launch_bounds__(MARK_THREADS) void token_marks_kernel(const int* __restrict__ dur, const int* __restrict__ lens,
+                                                                   const MarkRow* __restrict__ rows,
+                                                                   long long* __restrict__ marks) {
+    token_marks_body<false>(dur, lens, rows, marks);
+}
+__global__ __launch_bounds__(MARK_THREADS) void token_marks_joined_kernel(const int* __restrict__ dur, const int* __restrict__ lens,
+                                                                          const MarkRow* __restrict__ rows,
+                                                                          long long* __restrict__ marks) {
+    token_marks_body<true>(dur, lens, rows, marks);
+}
+// The marks of a plan (n_marks > 0): its mark rows copied into `t`, then one launch.  dur [B][512], lens [B]: device; marks: the
+// marks block (8-byte aligned), n_marks values long.  A joined plan: the rows' skip / keep / src_base matter.
+void launch_token_marks(const int* dur, const int* lens, const OutputPlan& plan, const OutputTables& t, void* marks, hipStream_t s) {
+    const size_t B = plan.mark.size();
+    KX_REQUIRE(dur && lens && t.mark && marks && B >= 1 && (reinterpret_cast<uintptr_t>(marks) & 7) == 0, "marks: bad launch argument");
+    KX_HIP(hipMemcpyAsync(t.mark, plan.mark.data(), B * sizeof(MarkRow), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(plan.joined ? token_marks_joined_kernel : token_marks_kernel, dim3((unsigned)B), dim3(MARK_THREADS), 0, s, dur,
+                       lens, t.mark, static_cast<long long*>(marks));
+    KX_HIP(hipGetLastError());
+}
+
+// The output stage of a call whose plan is built, for the model and for the test hook alike: the bodies into d_packed, and the
+// marks of the requests that want them in their block behind the bodies (8-aligned), so one copy to the host brings both.
+void launch_output_plan(const float* audio, long audio_ld, const int* dur, const int* lens, const OutputPlan& plan,
+                        const OutputTables& t, float* d_y, void* d_packed, hipStream_t s) {
+    launch_pack_plan(audio, audio_ld, plan, t, d_y, d_packed, s);
+    if (plan.n_marks > 0) launch_token_marks(dur, lens, plan, t, static_cast<char*>(d_packed) + plan.marks_off, s);
+}
+
+// ---- joins: the used durations of every row's first and last token, for the host's join plan ---------------------------------
+// edges[b] = {dur[b][0], dur[b][lens[b] - 1]}: eight bytes per row behind the duration head, copied to the host beside the
+// frame counts before the forward's one host wait.
+__global__ void edge_durations_kernel(const int* __restrict__ dur, const int* __restrict__ lens, int2* __restrict__ edges, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int T = min(max(lens[b], 1), 512);
+    edges[b] = make_int2(dur[(long)b * 512], dur[(long)b * 512 + T - 1]);
+}
+void launch_edge_durations(const int* dur, const int* lens, int* edges, int B, hipStream_t s) {
+    KX_REQUIRE(dur && lens && edges && B >= 1 && (reinterpret_cast<uintptr_t>(edges) & 7) == 0, "join: bad launch argument");
+    hipLaunchKernelGGL(edge_durations_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, dur, lens,
+                       reinterpret_cast<int2*>(edges), B);
+    KX_HIP(hipGetLastError());
+}
+
+}  // namespace kx

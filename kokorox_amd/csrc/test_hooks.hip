@@ -584,154 +584,81 @@ int kx_test_source(int device_id, const float* f0, int B, int F2, const float* l
     });
 }
 
-int kx_test_pack_requests(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames,
-                          const int32_t* chunks_per_request, int R, const int32_t* formats, void* out, int64_t out_cap,
-                          int64_t* out_bytes, char* err, size_t err_len) {
+int kx_test_output_plan(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames_in, const int32_t* dur,
+                        const int32_t* lens, const int32_t* chunks_per_request, int R, const int32_t* formats, const kx_join* joins,
+                        const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes, int64_t* out_samples,
+                        int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks, char* err, size_t err_len) {
     return guarded_free(err, err_len, [&] {
         check_device(device_id);
-        KX_REQUIRE(audio && frames && formats && out && out_bytes && B > 0 && R > 0, "test_pack_requests: bad argument");
-        for (int b = 0; b < B; ++b) KX_REQUIRE(frames[b] >= 0 && 600L * frames[b] <= audio_ld, "test_pack_requests: a row is shorter than its frames");
-        kx::PackPlan plan;  // the table builder of Model::infer_host_once (null chunks_per_request: R = B single-row requests)
-        kx::build_pack_plan(frames, B, chunks_per_request, R, formats, R, plan);
-        for (int r = 0; r < R; ++r) out_bytes[r] = plan.req[(size_t)r].out_bytes;
-        KX_REQUIRE(plan.total_bytes <= out_cap, "test_pack_requests: out_cap is too small");
-        KX_HIP(hipSetDevice(device_id));
-        DevMem dm;
-        const float* d_audio = dm.up(audio, (size_t)B * (size_t)audio_ld);
-        const kx::PackReq* d_req = dm.up(plan.req.data(), (size_t)R);
-        const long* d_cum = dm.up(plan.cum.data(), (size_t)B + 1);
-        // a sentinel after the last region: the kernel must not write past what the plan says
-        char* d_out = dm.get<char>((size_t)plan.total_bytes + 64);
-        KX_HIP(hipMemset(d_out, 0xA5, (size_t)plan.total_bytes + 64));
-        // (the same sentinel after the resampled streams)
-        float* d_y = plan.y_floats > 0 ? dm.get<float>((size_t)plan.y_floats + 16) : nullptr;
-        if (d_y) KX_HIP(hipMemset(d_y + plan.y_floats, 0xA5, 64));
-        kx::launch_pack_plan(d_audio, (long)audio_ld, d_req, d_cum, R, plan, d_y, d_out, nullptr);
-        KX_HIP(hipDeviceSynchronize());
-        std::vector<unsigned char> tail(64);
-        KX_HIP(hipMemcpy(out, d_out, (size_t)plan.total_bytes, hipMemcpyDeviceToHost));
-        KX_HIP(hipMemcpy(tail.data(), d_out + plan.total_bytes, 64, hipMemcpyDeviceToHost));
-        for (unsigned char c : tail) KX_REQUIRE(c == 0xA5, "test_pack_requests: the kernel wrote past the last region");
-        if (d_y) {
-            KX_HIP(hipMemcpy(tail.data(), d_y + plan.y_floats, 64, hipMemcpyDeviceToHost));
-            for (unsigned char c : tail) KX_REQUIRE(c == 0xA5, "test_pack_requests: the resampler wrote past the last stream");
-        }
-    });
-}
-
-int kx_test_token_marks(int device_id, const int32_t* dur, const int32_t* lens, int B, const int32_t* chunks_per_request, int R,
-                        const int32_t* formats, const uint8_t* want, int64_t* out_marks, int64_t out_cap, int64_t* out_n_marks,
-                        char* err, size_t err_len) {
-    return guarded_free(err, err_len, [&] {
-        check_device(device_id);
-        KX_REQUIRE(dur && lens && chunks_per_request && formats && out_marks && out_n_marks && B > 0 && R > 0, "test_token_marks: bad argument");
-        std::vector<int> frames((size_t)B, 0);  // what duration_kernel would have summed: the row's valid durations
-        for (int b = 0; b < B; ++b) {
-            KX_REQUIRE(lens[b] >= 1 && lens[b] <= 512, "test_token_marks: lens out of range");
-            long f = 0;
-            for (int t = 0; t < lens[b]; ++t) {
-                KX_REQUIRE(dur[(size_t)b * 512 + t] >= 0, "test_token_marks: negative duration");
-                f += dur[(size_t)b * 512 + t];
-            }
-            KX_REQUIRE(f <= 0x7FFFFFFF / 600, "test_token_marks: too many frames in a row");
-            frames[(size_t)b] = (int)f;
-        }
-        kx::PackPlan plan;  // the two table builders of Model::infer_host_once
-        kx::build_pack_plan(frames.data(), B, chunks_per_request, R, formats, R, plan);
-        std::vector<uint8_t> all((size_t)R, 1);  // want = null: every request
-        kx::MarkPlan mp;
-        kx::build_mark_plan(plan, lens, chunks_per_request, R, formats, R, want ? want : all.data(), mp);
-        for (int r = 0; r < R; ++r) out_n_marks[r] = mp.count[(size_t)r];
-        KX_REQUIRE(mp.n_marks <= out_cap, "test_token_marks: out_cap is too small");
-        if (mp.n_marks == 0) return;
-        KX_HIP(hipSetDevice(device_id));
-        DevMem dm;
-        const int* d_dur = dm.up(dur, (size_t)B * 512);
-        const int* d_len = dm.up(lens, (size_t)B);
-        const kx::MarkRow* d_rows = dm.up(mp.row.data(), (size_t)B);
-        // a sentinel after the last mark: the kernel must not write past what the plan says
-        char* d_out = dm.get<char>((size_t)mp.n_marks * 8 + 64);
-        KX_HIP(hipMemset(d_out, 0xA5, (size_t)mp.n_marks * 8 + 64));
-        kx::launch_token_marks(d_dur, d_len, d_rows, B, d_out, nullptr);
-        KX_HIP(hipDeviceSynchronize());
-        std::vector<unsigned char> tail(64);
-        KX_HIP(hipMemcpy(out_marks, d_out, (size_t)mp.n_marks * 8, hipMemcpyDeviceToHost));
-        KX_HIP(hipMemcpy(tail.data(), d_out + mp.n_marks * 8, 64, hipMemcpyDeviceToHost));
-        for (unsigned char c : tail) KX_REQUIRE(c == 0xA5, "test_token_marks: the kernel wrote past the last mark");
-    });
-}
-
-int kx_test_join_requests(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* dur, const int32_t* lens,
-                          const int32_t* chunks_per_request, int R, const int32_t* formats, const kx_join* joins,
-                          const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes, int64_t* out_samples,
-                          int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks, char* err, size_t err_len) {
-    return guarded_free(err, err_len, [&] {
-        check_device(device_id);
-        KX_REQUIRE(dur && lens && chunks_per_request && formats && joins && out_bytes && out_samples && out_n_marks && B > 0 && R > 0 &&
-                       (audio ? out != nullptr : out_cap == 0), "test_join_requests: bad argument");
+        KX_REQUIRE(formats && out_bytes && out_samples && out_n_marks && B > 0 && R > 0 && (frames_in ? !dur : dur && lens) &&
+                       ((!want && !joins) || dur) && (audio ? out != nullptr : out_cap == 0 && dur), "test_output_plan: bad argument");
         // what the forward would have brought back: the rows' frame counts and the durations of their two edge tokens
         std::vector<int> frames((size_t)B, 0), edges((size_t)2 * B, 0);
         for (int b = 0; b < B; ++b) {
-            KX_REQUIRE(lens[b] >= 1 && lens[b] <= 512, "test_join_requests: lens out of range");
-            long f = 0;
-            for (int t = 0; t < lens[b]; ++t) {
-                KX_REQUIRE(dur[(size_t)b * 512 + t] >= 0, "test_join_requests: negative duration");
-                f += dur[(size_t)b * 512 + t];
+            long f = frames_in ? frames_in[b] : 0;
+            if (dur) {
+                KX_REQUIRE(lens[b] >= 1 && lens[b] <= 512, "test_output_plan: lens out of range");
+                for (int t = 0; t < lens[b]; ++t) {
+                    KX_REQUIRE(dur[(size_t)b * 512 + t] >= 0, "test_output_plan: negative duration");
+                    f += dur[(size_t)b * 512 + t];
+                }
+                edges[(size_t)2 * b] = dur[(size_t)b * 512];
+                edges[(size_t)2 * b + 1] = dur[(size_t)b * 512 + lens[b] - 1];
             }
-            KX_REQUIRE(f <= 0x7FFFFFFF / 600 && (!audio || 600L * f <= audio_ld), "test_join_requests: a row is shorter than its frames");
+            KX_REQUIRE(f >= 0 && f <= 0x7FFFFFFF / 600 && (!audio || 600L * f <= audio_ld), "test_output_plan: a row is shorter than its frames");
             frames[(size_t)b] = (int)f;
-            edges[(size_t)2 * b] = dur[(size_t)b * 512];
-            edges[(size_t)2 * b + 1] = dur[(size_t)b * 512 + lens[b] - 1];
         }
-        for (int r = 0; r < R; ++r) KX_REQUIRE(kx::join_spec_ok(kx::JoinSpec{joins[r].flags, joins[r].keep_ms, joins[r].pause_ms, joins[r].fade_ms}), "infer: bad join");
-        kx::PackPlan plan;  // the three table builders of Model::infer_host_once
-        kx::JoinPlan jp;
-        kx::build_join_plan(frames.data(), lens, edges.data(), B, chunks_per_request, R, formats, R,
-                            reinterpret_cast<const kx::JoinSpec*>(joins), R, plan, jp);
-        std::vector<uint8_t> none((size_t)R, 0);  // want = null: no request
-        kx::MarkPlan mp;
-        kx::build_mark_plan(plan, lens, chunks_per_request, R, formats, R, want ? want : none.data(), mp, &jp);
+        static_assert(sizeof(kx_join) == sizeof(kx::JoinSpec), "kx_join is JoinSpec");
+        const kx::JoinSpec* specs = reinterpret_cast<const kx::JoinSpec*>(joins);
+        for (int r = 0; joins && r < R; ++r) KX_REQUIRE(kx::join_spec_ok(specs[r]), "infer: bad join");
+        // the planner and the launcher of Model::infer_host_once
+        const kx::RequestLayout layout{chunks_per_request, R, formats, R, want, specs, R};
+        kx::OutputPlan plan;
+        kx::build_output_plan(frames.data(), lens, joins ? edges.data() : nullptr, B, layout, plan);
         for (int r = 0; r < R; ++r) {
             out_bytes[r] = plan.req[(size_t)r].out_bytes;
             out_samples[r] = plan.req[(size_t)r].n_samples;
-            out_n_marks[r] = mp.count[(size_t)r];
+            out_n_marks[r] = plan.count[(size_t)r];
         }
-        KX_REQUIRE(mp.n_marks <= marks_cap && (mp.n_marks == 0 || out_marks), "test_join_requests: marks_cap is too small");
-        KX_REQUIRE(!audio || plan.total_bytes <= out_cap, "test_join_requests: out_cap is too small");
+        KX_REQUIRE(plan.n_marks <= marks_cap && (plan.n_marks == 0 || out_marks), "test_output_plan: marks_cap is too small");
+        KX_REQUIRE(!audio || plan.total_bytes <= out_cap, "test_output_plan: out_cap is too small");
+        if (!audio && plan.n_marks == 0) return;
         KX_HIP(hipSetDevice(device_id));
         DevMem dm;
-        const kx::JoinRow* d_join = jp.any ? dm.up(jp.row.data(), (size_t)B) : nullptr;
-        std::vector<unsigned char> tail(64);
-        if (audio) {  // (null: the marks alone, as kx_test_token_marks runs them)
+        const kx::OutputTables tables{dm.get<kx::PackReq>((size_t)R), dm.get<long>((size_t)B + 1), dm.get<kx::JoinRow>((size_t)B),
+                                      dm.get<kx::MarkRow>((size_t)B)};
+        const int* d_dur = dur ? dm.up(dur, (size_t)B * 512) : nullptr;
+        const int* d_len = dur ? dm.up(lens, (size_t)B) : nullptr;
+        // sentinels: 64 bytes after the last region, after the resampled streams and after the last mark, which the kernels
+        // must leave alone.  The marks block is moved 64 bytes back for the first of them (the kernel is handed its address,
+        // still 8-aligned; the offset itself is nothing it sees).
+        const long body = audio ? plan.total_bytes : 0, n_mk = plan.n_marks * 8;
+        if (audio) plan.marks_off += 64;
+        const long mk_off = audio ? plan.marks_off : 0;
+        char* d_out = dm.get<char>((size_t)(mk_off + n_mk + 64));
+        KX_HIP(hipMemset(d_out, 0xA5, (size_t)(mk_off + n_mk + 64)));
+        float* d_y = audio && plan.y_floats > 0 ? dm.get<float>((size_t)plan.y_floats + 16) : nullptr;
+        if (d_y) KX_HIP(hipMemset(d_y + plan.y_floats, 0xA5, 64));
+        if (audio) {
             const float* d_audio = dm.up(audio, (size_t)B * (size_t)audio_ld);
-            const kx::PackReq* d_req = dm.up(plan.req.data(), (size_t)R);
-            const long* d_cum = dm.up(plan.cum.data(), (size_t)B + 1);
-            // a sentinel after the last region and after the resampled streams: the kernels must not write past the plan
-            char* d_out = dm.get<char>((size_t)plan.total_bytes + 64);
-            KX_HIP(hipMemset(d_out, 0xA5, (size_t)plan.total_bytes + 64));
-            float* d_y = plan.y_floats > 0 ? dm.get<float>((size_t)plan.y_floats + 16) : nullptr;
-            if (d_y) KX_HIP(hipMemset(d_y + plan.y_floats, 0xA5, 64));
-            kx::launch_pack_plan(d_audio, (long)audio_ld, d_req, d_cum, R, plan, d_y, d_out, nullptr, d_join);
-            KX_HIP(hipDeviceSynchronize());
-            KX_HIP(hipMemcpy(out, d_out, (size_t)plan.total_bytes, hipMemcpyDeviceToHost));
-            KX_HIP(hipMemcpy(tail.data(), d_out + plan.total_bytes, 64, hipMemcpyDeviceToHost));
-            for (unsigned char c : tail) KX_REQUIRE(c == 0xA5, "test_join_requests: the kernel wrote past the last region");
-            if (d_y) {
-                KX_HIP(hipMemcpy(tail.data(), d_y + plan.y_floats, 64, hipMemcpyDeviceToHost));
-                for (unsigned char c : tail) KX_REQUIRE(c == 0xA5, "test_join_requests: the resampler wrote past the last stream");
-            }
+            kx::launch_output_plan(d_audio, (long)audio_ld, d_dur, d_len, plan, tables, d_y, d_out, nullptr);
+        } else {  // (the marks alone: no audio is read, no body written)
+            kx::launch_token_marks(d_dur, d_len, plan, tables, d_out, nullptr);
         }
-        if (mp.n_marks == 0) return;
-        const int* d_dur = dm.up(dur, (size_t)B * 512);
-        const int* d_len = dm.up(lens, (size_t)B);
-        const kx::MarkRow* d_rows = dm.up(mp.row.data(), (size_t)B);
-        char* d_mk = dm.get<char>((size_t)mp.n_marks * 8 + 64);
-        KX_HIP(hipMemset(d_mk, 0xA5, (size_t)mp.n_marks * 8 + 64));
-        kx::launch_token_marks(d_dur, d_len, d_rows, B, d_mk, nullptr, jp.any);
         KX_HIP(hipDeviceSynchronize());
-        KX_HIP(hipMemcpy(out_marks, d_mk, (size_t)mp.n_marks * 8, hipMemcpyDeviceToHost));
-        KX_HIP(hipMemcpy(tail.data(), d_mk + mp.n_marks * 8, 64, hipMemcpyDeviceToHost));
-        for (unsigned char c : tail) KX_REQUIRE(c == 0xA5, "test_join_requests: the kernel wrote past the last mark");
+        std::vector<unsigned char> tail(64);
+        auto untouched = [&](const void* d_at, const char* what) {
+            KX_HIP(hipMemcpy(tail.data(), d_at, 64, hipMemcpyDeviceToHost));
+            for (unsigned char c : tail) KX_REQUIRE(c == 0xA5, what);
+        };
+        if (audio) {
+            KX_HIP(hipMemcpy(out, d_out, (size_t)body, hipMemcpyDeviceToHost));
+            untouched(d_out + body, "test_output_plan: the kernel wrote past the last region");
+            if (d_y) untouched(d_y + plan.y_floats, "test_output_plan: the resampler wrote past the last stream");
+        }
+        if (plan.n_marks == 0) return;
+        KX_HIP(hipMemcpy(out_marks, d_out + mk_off, (size_t)n_mk, hipMemcpyDeviceToHost));
+        untouched(d_out + mk_off + n_mk, "test_output_plan: the kernel wrote past the last mark");
     });
 }
 

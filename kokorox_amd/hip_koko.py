@@ -184,9 +184,7 @@ def load_test_library() -> C.CDLL:
                                       f32, vp, vp, i32, vp, i32, vp, vp, vp, cp, sz]),
         "kx_test_layernorm": (i32, [i32, vp, i32, i32, i32, vp, f32, i32, vp, vp, f32, vp, cp, sz]),
         "kx_test_instance_norm": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, cp, sz]),
-        "kx_test_pack_requests": (i32, [i32, vp, i32, i64, vp, vp, i32, vp, vp, i64, vp, cp, sz]),
-        "kx_test_token_marks": (i32, [i32, vp, vp, i32, vp, i32, vp, vp, vp, i64, vp, cp, sz]),
-        "kx_test_join_requests": (i32, [i32, vp, i32, i64, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, cp, sz]),
+        "kx_test_output_plan": (i32, [i32, vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, cp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -198,7 +196,7 @@ def load_test_library() -> C.CDLL:
 
 TEST_ABI_SYMBOLS = ["kx_test_conv1d", "kx_test_lstm", "kx_test_source", "kx_test_attention", "kx_test_conv1d_epilogue", "kx_test_conv1d_full",
                     "kx_test_conv_transpose", "kx_test_lstm_fault", "kx_test_lstm_parts", "kx_test_conv_plan", "kx_test_conv1d_opts",
-                    "kx_test_layernorm", "kx_test_instance_norm", "kx_test_pack_requests", "kx_test_token_marks", "kx_test_join_requests"]
+                    "kx_test_layernorm", "kx_test_instance_norm", "kx_test_output_plan"]
 
 ABI_SYMBOLS = [
     "kx_version", "kx_init", "kx_create", "kx_import_onnx", "kx_resample_filter", "kx_create_from_device_blob", "kx_create_replicas", "kx_replicas_times", "kx_create_partition", "kx_destroy",
@@ -1016,87 +1014,69 @@ def harmonic_source(f0, lin_w, lin_b, seed=0, utt_base=0, noise_off=False, devic
     return out
 
 
-def pack_requests(audio, frames, chunks_per_request, formats, device=0):
-    """The request packer alone (kx_test_pack_requests): audio [B, audio_ld] with row b valid for 600 * frames[b] samples,
-    request r = chunks_per_request[r] consecutive rows in the format word formats[r] (the resampler runs first where a word
-    has a rate code).  chunks_per_request = None: every row a request of its own (a null pointer to the plan builder, as the
-    per-utterance entries of the model pass it); one word in `formats` then serves all rows.  Returns the R regions as bytes."""
+def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, want, pauses, device):
+    """kx_test_output_plan, the one hook of the output stage: the model's planner and launcher on host arrays (None where the
+    hook takes a null pointer; include/kokorox_hip_test.h).  Returns (bodies as bytes, out_samples, marks as int64 arrays)."""
     lib = load_test_library()
-    audio = _f32(audio)
-    B, ld = audio.shape
-    fr = np.ascontiguousarray(frames, dtype=np.int32)
+    B = len(frames if dur is None else lens)
     fm = np.ascontiguousarray(formats, dtype=np.int32)
-    if chunks_per_request is None:
-        cpr, R = None, B
-        fm = np.repeat(fm, B) if fm.shape == (1,) else fm
+    cpr = None if chunks_per_request is None else np.ascontiguousarray(chunks_per_request, dtype=np.int32)
+    R = B if cpr is None else cpr.shape[0]
+    if dur is None:
+        fr, ln, n_frames, mcap = np.ascontiguousarray(frames, dtype=np.int32), None, int(np.sum(frames)), 0
+        assert fr.shape == (B,)
     else:
-        cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32)
-        R = cpr.shape[0]
-    assert fr.shape == (B,) and fm.shape == (R,)
-    cap = 16 * 600 * int(fr.sum()) + 64 * R  # (stereo f32 at 48 kHz: 16 bytes per sample of the model)
-    out = np.zeros(cap, dtype=np.uint8)
-    nb = np.zeros(R, dtype=np.int64)
-    _err_call(lib.kx_test_pack_requests, device, _ptr(audio), B, ld, _ptr(fr), _ptr(cpr), R, _ptr(fm), _ptr(out), cap, _ptr(nb))
-    raw, res, o = out.tobytes(), [], 0
-    for r in range(R):
-        res.append(raw[o: o + int(nb[r])])
-        o += int(nb[r])
-    return res
-
-
-def token_marks(dur, lens, chunks_per_request, formats, want=None, device=0):
-    """The token marks alone (kx_test_token_marks): dur [B, 512] int32 frames per token, row b valid for lens[b] entries,
-    request r = chunks_per_request[r] consecutive rows in the format word formats[r]; want [R] = which requests get marks
-    (None: all).  Returns one int64 array per request (empty where not wanted): voices.token_marks of the same durations."""
-    lib = load_test_library()
-    dur = np.ascontiguousarray(dur, dtype=np.int32)
-    ln = np.ascontiguousarray(lens, dtype=np.int32)
-    cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32)
-    fm = np.ascontiguousarray(formats, dtype=np.int32)
-    B, R = ln.shape[0], cpr.shape[0]
-    assert dur.shape == (B, 512) and fm.shape == (R,)
+        dur = np.ascontiguousarray(dur, dtype=np.int32)
+        fr, ln = None, np.ascontiguousarray(lens, dtype=np.int32)
+        assert dur.shape == (B, 512)
+        n_frames, mcap = int(sum(int(dur[b, : ln[b]].sum()) for b in range(B))), int(ln.sum()) + B
     wt = None if want is None else np.ascontiguousarray(want, dtype=np.uint8)
-    assert wt is None or wt.shape == (R,)
-    cap = int(ln.sum()) + B
-    out = np.zeros(cap, dtype=np.int64)
-    n = np.zeros(R, dtype=np.int64)
-    _err_call(lib.kx_test_token_marks, device, _ptr(dur), _ptr(ln), B, _ptr(cpr), R, _ptr(fm), _ptr(wt), _ptr(out), cap, _ptr(n))
-    return [m.copy() for m in np.split(out[: int(n.sum())], np.cumsum(n)[:-1])]
-
-
-def join_requests(audio, dur, lens, chunks_per_request, formats, joins, want=None, device=0):
-    """Joined requests alone (kx_test_join_requests): audio [B, audio_ld] (None: the marks alone), dur [B, 512] int32 frames per
-    token with row b valid for lens[b] entries and 600 * their sum samples of audio, request r = chunks_per_request[r]
-    consecutive rows in the format word formats[r] with the join spec joins[r]; want [R] = which requests get marks (None:
-    none).  Returns (bodies as bytes, out_samples, marks): voices.join_stream -> resample_stream -> the form mirrors, and
-    voices.joined_marks (an empty array where not wanted)."""
-    lib = load_test_library()
-    dur = np.ascontiguousarray(dur, dtype=np.int32)
-    ln = np.ascontiguousarray(lens, dtype=np.int32)
-    cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32)
-    fm = np.ascontiguousarray(formats, dtype=np.int32)
-    B, R = ln.shape[0], cpr.shape[0]
-    assert dur.shape == (B, 512) and fm.shape == (R,)
-    j = join_specs(joins, R)
-    wt = None if want is None else np.ascontiguousarray(want, dtype=np.uint8)
-    assert wt is None or wt.shape == (R,)
+    assert fm.shape == (R,) and (wt is None or wt.shape == (R,))
     ld, cap = 0, 0
     if audio is not None:
         audio = _f32(audio)
         assert audio.shape[0] == B
         ld = audio.shape[1]
-        frames = int(sum(int(dur[b, : ln[b]].sum()) for b in range(B)))
-        pauses = sum(24 * int(j["pause_ms"][r]) * (int(cpr[r]) - 1) for r in range(R))
-        cap = 16 * (600 * frames + pauses) + 64 * R  # (stereo f32 at 48 kHz: 16 bytes per sample of the model)
+        cap = 16 * (600 * n_frames + pauses) + 64 * R  # (stereo f32 at 48 kHz: 16 bytes per sample of the model)
     out = np.zeros(max(cap, 1), dtype=np.uint8)
-    mcap = int(ln.sum()) + B
-    mk = np.zeros(mcap, dtype=np.int64)
+    mk = np.zeros(max(mcap, 1), dtype=np.int64)
     nb, ns, nm = np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int64)
-    _err_call(lib.kx_test_join_requests, device, _ptr(audio), B, ld, _ptr(dur), _ptr(ln), _ptr(cpr), R, _ptr(fm), _ptr(j), _ptr(wt),
-              _ptr(out) if audio is not None else None, cap, _ptr(nb), _ptr(ns), _ptr(mk), mcap, _ptr(nm))
+    _err_call(lib.kx_test_output_plan, device, _ptr(audio), B, ld, _ptr(fr), _ptr(dur), _ptr(ln), _ptr(cpr), R, _ptr(fm), _ptr(joins),
+              _ptr(wt), _ptr(out) if audio is not None else None, cap, _ptr(nb), _ptr(ns), _ptr(mk), mcap, _ptr(nm))
     raw, res, o = out.tobytes(), [], 0
     for r in range(R):
         res.append(raw[o: o + int(nb[r])] if audio is not None else b"")
         o += int(nb[r])
     marks = [m.copy() for m in np.split(mk[: int(nm.sum())], np.cumsum(nm)[:-1])]
     return res, [int(v) for v in ns], marks
+
+
+def pack_requests(audio, frames, chunks_per_request, formats, device=0):
+    """The request packer alone: audio [B, audio_ld] with row b valid for 600 * frames[b] samples,
+    request r = chunks_per_request[r] consecutive rows in the format word formats[r] (the resampler runs first where a word
+    has a rate code).  chunks_per_request = None: every row a request of its own (a null pointer to the planner, as the
+    per-utterance entries of the model pass it); one word in `formats` then serves all rows.  Returns the R regions as bytes."""
+    fm = np.ascontiguousarray(formats, dtype=np.int32)
+    if chunks_per_request is None and fm.shape == (1,):
+        fm = np.repeat(fm, len(frames))
+    return _output_plan(audio, frames, None, None, chunks_per_request, fm, None, None, 0, device)[0]
+
+
+def token_marks(dur, lens, chunks_per_request, formats, want=None, device=0):
+    """The token marks alone: dur [B, 512] int32 frames per token, row b valid for lens[b] entries,
+    request r = chunks_per_request[r] consecutive rows in the format word formats[r]; want [R] = which requests get marks
+    (None: all).  Returns one int64 array per request (empty where not wanted): voices.token_marks of the same durations."""
+    want = np.ones(len(chunks_per_request), dtype=np.uint8) if want is None else want
+    return _output_plan(None, None, dur, lens, chunks_per_request, formats, None, want, 0, device)[2]
+
+
+def join_requests(audio, dur, lens, chunks_per_request, formats, joins, want=None, device=0):
+    """Joined requests alone: audio [B, audio_ld] (None: the marks alone), dur [B, 512] int32 frames per
+    token with row b valid for lens[b] entries and 600 * their sum samples of audio, request r = chunks_per_request[r]
+    consecutive rows in the format word formats[r] with the join spec joins[r]; want [R] = which requests get marks (None:
+    none).  Returns (bodies as bytes, out_samples, marks): voices.join_stream -> resample_stream -> the form mirrors, and
+    voices.joined_marks (an empty array where not wanted)."""
+    R = len(chunks_per_request)
+    j = join_specs(joins, R)
+    pauses = sum(24 * int(j["pause_ms"][r]) * (int(chunks_per_request[r]) - 1) for r in range(R))
+    return _output_plan(audio, None, dur, lens, chunks_per_request, formats, j, want, pauses, device)

@@ -200,6 +200,16 @@ static long form_bytes(int form, long n) {  // include/kokorox_hip.h, KX_PACK_*
     }
 }
 
+// the bound of the bodies, written out: the widest word's bytes per sample (forms 0..4 at 24 000 Hz here), 64 per request, 16
+static size_t body_bound(const int* words, int n_words, int R, size_t n_samples) {
+    size_t per_sample = 0;
+    for (int i = 0; i < n_words; ++i) {
+        const size_t w = words[i] == 1 ? 8 : (words[i] == 2 ? 2 : (words[i] == 4 ? 3 : 4));
+        per_sample = w > per_sample ? w : per_sample;
+    }
+    return n_samples * per_sample + (size_t)R * 64 + 16;
+}
+
 static void utterance_layout() {
     // what kx_infer / kx_infer_packed / kx_infer_voices ask of the plan builder: null chunks, one shared form 0..2, R = B
     const int B = 5;
@@ -208,7 +218,7 @@ static void utterance_layout() {
     const int mixed[B] = {0, 1, 2, 2, 1};  // (as a grouped call of single-row requests: the dispatcher's mixed batches)
     const int ones[B] = {1, 1, 1, 1, 1};
     for (int c = 0; c < 4; ++c) {
-        kx::PackPlan plan;
+        kx::OutputPlan plan;
         plan.total_bytes = 77;  // (stale contents must not survive)
         plan.max_units = 77;
         plan.req.resize(9);
@@ -222,14 +232,15 @@ static void utterance_layout() {
             hc.req_formats = mixed;
             hc.n_req_formats = B;
         }
-        CHECK(hc.regions(B) == B && hc.n_words() == (c < 3 ? 1 : B));
-        kx::build_pack_plan(frames, B, hc.chunks_per_request, B, hc.words(), hc.n_words(), plan);
+        const kx::RequestLayout lay = hc.layout(B);
+        CHECK(lay.R == B && lay.n_format == (c < 3 ? 1 : B) && !lay.marks && !lay.joins);
+        kx::build_output_plan(frames, nullptr, nullptr, B, lay, plan);
         CHECK(plan.req.size() == (size_t)B && plan.cum.size() == (size_t)B + 1);
         long sum = 0, n = 0;
         for (int b = 0; b < B; ++b) {
             const int w = width[c < 3 ? c : mixed[b]];
             const kx::PackReq& q = plan.req[(size_t)b];
-            CHECK(q.first_row == b && q.n_rows == 1 && q.form == (c < 3 ? c : mixed[b]) && q.pad_ == 0);
+            CHECK(q.first_row == b && q.n_rows == 1 && q.form == (c < 3 ? c : mixed[b]) && q.rate == 0);
             CHECK(q.n_samples == 600L * frames[b]);
             CHECK(q.out_bytes == 600L * frames[b] * w);
             CHECK(q.out_off == sum);
@@ -241,24 +252,24 @@ static void utterance_layout() {
         // for these frames, and for B rows of one frame each
         const int* words = c < 3 ? &form : mixed;
         const int n_words = c < 3 ? 1 : B;
-        CHECK(kx::packed_bytes_bound(hc, B, 1000) == kx::pack_requests_bound(words, n_words, B, 1000));
-        CHECK(kx::packed_bytes_bound(hc, B, (size_t)n) == kx::pack_requests_bound(words, n_words, B, (size_t)n));
-        CHECK(kx::packed_bytes_bound(hc, B, (size_t)n) >= (size_t)plan.total_bytes);
-        kx::build_pack_plan(ones, B, hc.chunks_per_request, B, hc.words(), hc.n_words(), plan);
+        CHECK(kx::output_bounds(lay, B, 1000, nullptr).packed_bytes == body_bound(words, n_words, B, 1000));
+        CHECK(kx::output_bounds(lay, B, (size_t)n, nullptr).packed_bytes == body_bound(words, n_words, B, (size_t)n));
+        CHECK(kx::output_bounds(lay, B, (size_t)n, nullptr).packed_bytes >= (size_t)plan.total_bytes);
+        kx::build_output_plan(ones, nullptr, nullptr, B, lay, plan);
         CHECK(plan.total_bytes == (c < 3 ? 600L * B * width[c] : 600L * (4 + 8 + 2 + 2 + 8)));
-        CHECK(kx::packed_bytes_bound(hc, B, (size_t)600 * B) >= (size_t)plan.total_bytes);
-        CHECK(kx::resample_floats_bound(hc.words(), hc.n_words(), 1000) == 0);  // (24 kHz: nothing to resample)
+        CHECK(kx::output_bounds(lay, B, (size_t)600 * B, nullptr).packed_bytes >= (size_t)plan.total_bytes);
+        CHECK(kx::output_bounds(lay, B, 1000, nullptr).y_floats == 0);  // (24 kHz: nothing to resample)
     }
     printf("utterance layout: 4 assignments of forms over %d utterances\n", B);
 }
 
 static void check_plan(const std::vector<int>& frames, const std::vector<int>& chunks, const std::vector<int>& forms) {
     const int B = (int)frames.size(), R = (int)chunks.size();
-    kx::PackPlan plan;
+    kx::OutputPlan plan;
     plan.total_bytes = 99;  // (stale contents must not survive)
     plan.max_units = 99;
     plan.req.resize(11);
-    kx::build_pack_plan(frames.data(), B, chunks.data(), R, forms.data(), (int)forms.size(), plan);
+    kx::build_output_plan(frames.data(), nullptr, nullptr, B, {chunks.data(), R, forms.data(), (int)forms.size(), nullptr, nullptr, 0}, plan);
     CHECK(plan.cum.size() == (size_t)B + 1 && plan.cum[0] == 0);
     for (int b = 0; b < B; ++b) CHECK(plan.cum[(size_t)b + 1] == plan.cum[(size_t)b] + 600L * frames[(size_t)b]);
     CHECK(plan.req.size() == (size_t)R);
@@ -269,7 +280,7 @@ static void check_plan(const std::vector<int>& frames, const std::vector<int>& c
         long fr = 0;
         for (int i = 0; i < chunks[(size_t)r]; ++i) fr += frames[(size_t)(row + i)];
         const int form = forms[forms.size() == 1 ? 0 : (size_t)r];
-        CHECK(q.first_row == row && q.n_rows == chunks[(size_t)r] && q.form == form && q.pad_ == 0);
+        CHECK(q.first_row == row && q.n_rows == chunks[(size_t)r] && q.form == form && q.rate == 0);
         CHECK(q.n_samples == 600 * fr);
         CHECK(q.out_bytes == kx::pack_request_bytes(form, q.n_samples));
         CHECK(q.out_bytes == form_bytes(form, q.n_samples) && q.out_bytes % 4 == 0);
@@ -286,8 +297,8 @@ static void check_plan(const std::vector<int>& frames, const std::vector<int>& c
     hc.n_requests = R;
     hc.req_formats = forms.data();
     hc.n_req_formats = (int)forms.size();
-    const size_t bound = kx::pack_requests_bound(forms.data(), (int)forms.size(), R, (size_t)plan.cum[(size_t)B]);
-    CHECK(kx::packed_bytes_bound(hc, B, (size_t)plan.cum[(size_t)B]) == bound);
+    const size_t bound = body_bound(forms.data(), (int)forms.size(), R, (size_t)plan.cum[(size_t)B]);
+    CHECK(kx::output_bounds(hc.layout(B), B, (size_t)plan.cum[(size_t)B], nullptr).packed_bytes == bound);
     CHECK((size_t)plan.total_bytes <= bound);
 }
 
@@ -306,9 +317,9 @@ static void request_plans() {
         ++n;
     }
     // null chunks: every row a request of its own
-    kx::PackPlan plan;
+    kx::OutputPlan plan;
     const int forms[6] = {4, 0, 3, 1, 2, 4};
-    kx::build_pack_plan(frames.data(), 6, nullptr, 6, forms, 6, plan);
+    kx::build_output_plan(frames.data(), nullptr, nullptr, 6, {nullptr, 6, forms, 6, nullptr, nullptr, 0}, plan);
     for (int r = 0; r < 6; ++r) CHECK(plan.req[(size_t)r].first_row == r && plan.req[(size_t)r].n_rows == 1 && plan.req[(size_t)r].n_samples == 600L * frames[(size_t)r]);
     printf("request plans: %d (composition, forms) pairs over 6 rows\n", n);
 }
@@ -336,9 +347,9 @@ static void bounds() {
     const int last_ok = (int)((first_bad - 1) / 600);  // frames
     const int form4 = 4, two = 2, one = 1;
     const int fr[2] = {last_ok, 1};
-    kx::PackPlan plan;
-    CHECK(refused([&] { kx::build_pack_plan(fr, 2, &two, 1, &form4, 1, plan); }, "16-bit WAV"));
-    kx::build_pack_plan(fr, 1, &one, 1, &form4, 1, plan);
+    kx::OutputPlan plan;
+    CHECK(refused([&] { kx::build_output_plan(fr, nullptr, nullptr, 2, {&two, 1, &form4, 1, nullptr, nullptr, 0}, plan); }, "16-bit WAV"));
+    kx::build_output_plan(fr, nullptr, nullptr, 1, {&one, 1, &form4, 1, nullptr, nullptr, 0}, plan);
     CHECK(plan.req[0].n_samples == 600L * last_ok && plan.total_bytes == form_bytes(4, 600L * last_ok));
     printf("bounds: 64 x 5 one-frame batches; form 4 refused from %ld samples\n", first_bad);
 }

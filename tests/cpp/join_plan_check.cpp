@@ -1,5 +1,5 @@
-// CPU driver of the join layout (kokorox_amd/csrc/host_request.cpp: build_join_plan, build_mark_plan with a join plan,
-// join_pause_samples, packed_bytes_bound, resample_floats_bound, check_join_call): built with g++ -fsanitize=address,undefined
+// CPU driver of the join layout (kokorox_amd/csrc/host_request.cpp: build_output_plan with joins and marks,
+// output_bounds, check_join_call): built with g++ -fsanitize=address,undefined
 // together with host_request.cpp by tests/test_joins_cpu.py and run as a child process.  It judges nothing itself: it prints
 // what the unit under test lays out, and the test compares that with the hand-derived answers of tests/golden/joins.json and
 // with the numpy definition (kokorox_amd/voices.py).
@@ -9,7 +9,9 @@
 //       row <b> <skip> <keep> <gap> <fade_head> <fade_tail>
 //       req <r> <out_off> <out_bytes> <n_samples> <src_samples> <n_marks>
 //       marks <r> <values ...>          (from the rows of the mark plan, with token_marks_joined_kernel's arithmetic)
-//       sizes <total_bytes> <end_bytes> <y_floats> <packed_bytes_bound> <resample_floats_bound> <any>
+//       sizes <total_bytes> <end_bytes> <y_floats> <bound of the packed bytes> <bound of the resampled floats> <joined>
+//     (one thing it does judge, in every case: the same rows, grouping, words and want flags with no specs at all and with
+//     all-zero specs give equal plans, field for field, and both select the plain kernels)
 //   join_plan_check refusals           one line per refusal: <name> TAB <code> TAB <message>, or <name> TAB accepted
 //   join_plan_check dispatcher         the same for kx::dispatch::Core::submit_request_joined on a stub model, which records
 //                                      the spec every request reached its batch with
@@ -24,6 +26,51 @@
 #include "host_request.h"
 
 namespace {
+
+#define REQUIRE_SAME(cond)                                                      \
+    do {                                                                        \
+        if (!(cond)) {                                                          \
+            printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);            \
+            exit(1);                                                            \
+        }                                                                       \
+    } while (0)
+
+template <class T>
+bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {  // (vectors of long)
+    return a.size() == b.size() && (a.empty() || !memcmp(a.data(), b.data(), a.size() * sizeof(T)));
+}
+
+// A layout with null joins and the same layout with all-zero specs: equal request tables, prefixes, rows, marks and counts,
+// and the plain kernels for both.
+void plain_specs_equal_no_specs(const std::vector<int>& frames, const std::vector<int>& lens, const std::vector<int>& edges,
+                                const kx::RequestLayout& lay) {
+    const int B = (int)frames.size();
+    const std::vector<kx::JoinSpec> zeros((size_t)lay.R, kx::JoinSpec{0u, 0, 0, 0});
+    kx::RequestLayout none = lay, zero = lay;
+    none.joins = nullptr, none.n_join = 0;
+    zero.joins = zeros.data(), zero.n_join = lay.R;
+    kx::OutputPlan a, b;
+    kx::build_output_plan(frames.data(), lens.data(), nullptr, B, none, a);
+    kx::build_output_plan(frames.data(), lens.data(), edges.data(), B, zero, b);
+    REQUIRE_SAME(!a.joined && !b.joined);
+    REQUIRE_SAME(a.req.size() == (size_t)lay.R && a.cum.size() == (size_t)B + 1 && a.mark.size() == (size_t)B);
+    for (int r = 0; r < lay.R; ++r) {
+        const kx::PackReq &p = a.req[(size_t)r], &q = b.req[(size_t)r];
+        REQUIRE_SAME(p.first_row == q.first_row && p.n_rows == q.n_rows && p.form == q.form && p.rate == q.rate);
+        REQUIRE_SAME(p.out_off == q.out_off && p.out_bytes == q.out_bytes && p.n_samples == q.n_samples);
+        REQUIRE_SAME(p.src_samples == q.src_samples && p.y_off == q.y_off);
+    }
+    for (int i = 0; i < B; ++i) {
+        const kx::JoinRow &j = a.join[(size_t)i], &k = b.join[(size_t)i];
+        REQUIRE_SAME(j.skip == 0 && j.keep == 600L * frames[(size_t)i] && j.gap == 0 && j.fade_head == 0 && j.fade_tail == 0);
+        REQUIRE_SAME(k.skip == j.skip && k.keep == j.keep && k.gap == j.gap && k.fade_head == j.fade_head && k.fade_tail == j.fade_tail);
+        const kx::MarkRow &m = a.mark[(size_t)i], &n = b.mark[(size_t)i];
+        REQUIRE_SAME(m.first == n.first && m.base == n.base && m.K == n.K && m.src_base == n.src_base && m.skip == n.skip && m.keep == n.keep);
+    }
+    REQUIRE_SAME(same_bytes(a.cum, b.cum) && same_bytes(a.count, b.count) && same_bytes(a.first, b.first));
+    REQUIRE_SAME(a.total_bytes == b.total_bytes && a.max_units == b.max_units && a.y_floats == b.y_floats);
+    REQUIRE_SAME(a.max_resampled == b.max_resampled && a.marks_off == b.marks_off && a.n_marks == b.n_marks);
+}
 
 bool read_ints(std::vector<int>& v, size_t n) {
     v.assign(n, 0);
@@ -55,14 +102,14 @@ bool run_case() {
         joins[(size_t)r] = kx::JoinSpec{(uint32_t)jv[(size_t)4 * r], jv[(size_t)4 * r + 1], jv[(size_t)4 * r + 2], jv[(size_t)4 * r + 3]};
         want8[(size_t)r] = (uint8_t)want[(size_t)r];
     }
-    kx::PackPlan plan;
-    kx::JoinPlan jp;
-    kx::MarkPlan mp;
-    kx::build_join_plan(frames.data(), lens.data(), edges.data(), B, cpr.data(), R, words.data(), R, joins.data(), R, plan, jp);
-    kx::build_mark_plan(plan, lens.data(), cpr.data(), R, words.data(), R, want8.data(), mp, &jp);
+    const kx::RequestLayout lay{cpr.data(), R, words.data(), R, want8.data(), joins.data(), R};
+    kx::OutputPlan plan;
+    kx::build_output_plan(frames.data(), lens.data(), edges.data(), B, lay, plan);
+    const kx::OutputPlan &jp = plan, &mp = plan;
+    plain_specs_equal_no_specs(frames, lens, edges, lay);
     printf("case %s\n", name);
     for (int b = 0; b < B; ++b) {
-        const kx::JoinRow& j = jp.row[(size_t)b];
+        const kx::JoinRow& j = jp.join[(size_t)b];
         printf("row %d %ld %ld %ld %d %d\n", b, j.skip, j.keep, j.gap, j.fade_head, j.fade_tail);
     }
     long frames_all = 0;
@@ -73,7 +120,7 @@ bool run_case() {
         if (!mp.count[(size_t)r]) continue;
         printf("marks %d", r);
         for (int b = q.first_row; b < q.first_row + q.n_rows; ++b) {
-            const kx::MarkRow& m = mp.row[(size_t)b];
+            const kx::MarkRow& m = mp.mark[(size_t)b];
             long scan = 0;
             for (int t = 0; t <= lens[(size_t)b]; ++t) {  // (the kernel's value from the row's fields, in 64 bits)
                 long u = 600 * scan - m.skip;
@@ -93,10 +140,9 @@ bool run_case() {
     hc.req_joins = joins.data();
     hc.n_req_joins = R;
     const size_t n_samples = (size_t)600 * (size_t)frames_all;
-    const size_t pauses = kx::join_pause_samples(cpr.data(), R, joins.data(), R);
-    printf("sizes %ld %ld %ld %zu %zu %d\n", plan.total_bytes, mp.end_bytes(), plan.y_floats,
-           kx::packed_bytes_bound(hc, B, n_samples, lens.data()), kx::resample_floats_bound(words.data(), R, n_samples + pauses),
-           jp.any ? 1 : 0);
+    const kx::OutputBounds bound = kx::output_bounds(hc.layout(B), B, n_samples, lens.data());
+    printf("sizes %ld %ld %ld %zu %zu %d\n", plan.total_bytes, mp.end_bytes(), plan.y_floats, bound.packed_bytes, bound.y_floats,
+           jp.joined ? 1 : 0);
     return true;
 }
 

@@ -1,4 +1,4 @@
-// CPU checker of the token-marks layout (kokorox_amd/csrc/host_request.cpp: build_mark_plan, packed_bytes_bound, check_marks_call):
+// CPU checker of the token-marks layout (kokorox_amd/csrc/host_request.cpp: build_output_plan, output_bounds, check_marks_call):
 // built with g++ -fsanitize=address,undefined together with host_request.cpp by tests/test_token_marks_cpu.py and run as a child
 // process.  Every expectation is written out here on its own (plain sums over the rows), not taken from the unit under test.
 #include <cstdint>
@@ -28,11 +28,10 @@ const long kK[4] = {600, 200, 400, 1200};      // rate codes 0..3
 // one grouping, one assignment of words and want flags: the plan against sums written out here
 void check_plan(const std::vector<int>& cpr, const std::vector<int>& words, const std::vector<uint8_t>* want) {
     const int R = (int)cpr.size();
-    kx::PackPlan plan;
-    kx::build_pack_plan(kFrames, 6, cpr.data(), R, words.data(), (int)words.size(), plan);
-    kx::MarkPlan mp;
-    kx::build_mark_plan(plan, kLens, cpr.data(), R, words.data(), (int)words.size(), want ? want->data() : nullptr, mp);
-    CHECK((int)mp.row.size() == 6 && (int)mp.count.size() == R && (int)mp.first.size() == R);
+    kx::OutputPlan plan;
+    kx::build_output_plan(kFrames, kLens, nullptr, 6, {cpr.data(), R, words.data(), (int)words.size(), want ? want->data() : nullptr, nullptr, 0}, plan);
+    const kx::OutputPlan& mp = plan;
+    CHECK((int)mp.mark.size() == 6 && (int)mp.count.size() == R && (int)mp.first.size() == R);
     CHECK(mp.marks_off % 8 == 0 && mp.marks_off >= plan.total_bytes && mp.marks_off < plan.total_bytes + 8);
     long next = 0;
     int row = 0;
@@ -43,7 +42,7 @@ void check_plan(const std::vector<int>& cpr, const std::vector<int>& words, cons
         long frames_before = 0, n = 0;
         CHECK(mp.first[(size_t)r] == next);
         for (int b = row; b < row + cpr[(size_t)r]; ++b) {
-            const kx::MarkRow& m = mp.row[(size_t)b];
+            const kx::MarkRow& m = mp.mark[(size_t)b];
             CHECK(m.K == K);
             CHECK(m.base == K * frames_before);
             CHECK(m.first == (wanted ? next + n : -1));
@@ -91,6 +90,13 @@ void plans() {
     printf("mark plans: %d (grouping, words, want) cases over 6 rows\n", n);
 }
 
+// the bound of the bodies alone, written out: the word's bytes per sample (twice at 48 000 Hz), 64 per request, 16
+size_t body_bound(int word, int R, size_t n_samples) {
+    const int f = word & 255;
+    const size_t w = (f == 1 ? 8 : (f == 2 ? 2 : (f == 4 ? 3 : (f >= 8 ? 1 : 4)))) * (size_t)((word >> 8) == 3 ? 2 : 1);
+    return n_samples * w + (size_t)R * 64 + 16;
+}
+
 void bounds() {
     // without marks: exactly today's value; with marks: 8 + 8 x sum(lens + 1) more, and enough for one frame per token
     int n = 0;
@@ -112,16 +118,14 @@ void bounds() {
                 hc.req_formats = &word;
                 hc.n_req_formats = 1;
                 const size_t n_samples = 600 * (size_t)tokens;
-                const size_t plain = kx::packed_bytes_bound(hc, R, n_samples);
-                CHECK(plain == kx::pack_requests_bound(&word, 1, R, n_samples));
-                CHECK(kx::packed_bytes_bound(hc, R, n_samples, lens.data()) == plain);  // (lens alone asks for nothing)
+                const size_t plain = kx::output_bounds(hc.layout(R), R, n_samples, nullptr).packed_bytes;
+                CHECK(plain == body_bound(word, R, n_samples));
+                CHECK(kx::output_bounds(hc.layout(R), R, n_samples, lens.data()).packed_bytes == plain);  // (lens alone asks for nothing)
                 hc.req_marks = want.data();
-                const size_t with = kx::packed_bytes_bound(hc, R, n_samples, lens.data());
+                const size_t with = kx::output_bounds(hc.layout(R), R, n_samples, lens.data()).packed_bytes;
                 CHECK(with == plain + 8 + 8 * (size_t)(tokens + R));
-                kx::PackPlan plan;
-                kx::build_pack_plan(frames.data(), R, cpr.data(), R, &word, 1, plan);
-                kx::MarkPlan mp;
-                kx::build_mark_plan(plan, lens.data(), cpr.data(), R, &word, 1, want.data(), mp);
+                kx::OutputPlan mp;
+                kx::build_output_plan(frames.data(), lens.data(), nullptr, R, hc.layout(R), mp);
                 CHECK(mp.n_marks == tokens + R);
                 CHECK((size_t)mp.end_bytes() <= with);
                 ++n;
@@ -131,14 +135,13 @@ void bounds() {
     kx::HostCall hc;
     hc.format = 1;
     const int stereo = 1, three[3] = {1, 1, 1};
-    CHECK(kx::packed_bytes_bound(hc, 3, 1800) == kx::pack_requests_bound(&stereo, 1, 3, 1800));
-    CHECK(kx::packed_bytes_bound(hc, 3, 1800, three) == kx::packed_bytes_bound(hc, 3, 1800));
+    CHECK(kx::output_bounds(hc.layout(3), 3, 1800, nullptr).packed_bytes == body_bound(stereo, 3, 1800));
+    CHECK(kx::output_bounds(hc.layout(3), 3, 1800, three).packed_bytes == kx::output_bounds(hc.layout(3), 3, 1800, nullptr).packed_bytes);
     printf("bounds: %d batches of one frame per token\n", n);
 }
 
 void refusals() {
     const int cpr[2] = {1, 2};
-    const int lens[3] = {3, 4, 5}, frames[3] = {3, 4, 5};
     const int word = 0;
     const uint8_t want[2] = {1, 1};
     kx::HostCall hc;
@@ -165,17 +168,6 @@ void refusals() {
     marks = reinterpret_cast<int64_t*>(&hc);
     printf("ok\t%s\n", text(&marks, n, hc).c_str());
     CHECK(marks == nullptr);
-    // a plan of another grouping is refused, not read out of bounds
-    kx::PackPlan plan;
-    kx::build_pack_plan(frames, 3, cpr, 2, &word, 1, plan);
-    kx::MarkPlan mp;
-    const int other[2] = {2, 1};
-    try {
-        kx::build_mark_plan(plan, lens, other, 2, &word, 1, want, mp);
-        printf("other_grouping\taccepted\n");
-    } catch (const kx::Error& e) {
-        printf("other_grouping\t%d\t%s\n", e.code, e.what());
-    }
 }
 
 }  // namespace

@@ -61,13 +61,25 @@ static void filters() {
     printf("filters: 145 145 97 taps\n");
 }
 
+// the bound of the bodies, written out: the widest word's bytes per sample (twice at 48 000 Hz), 64 per request, 16
+static size_t body_bound(const std::vector<int>& words, int R, size_t n_samples) {
+    size_t per_sample = 0;
+    for (int word : words) {
+        const int f = word & 255;
+        const size_t w = (f == 1 ? 8 : (f == 2 ? 2 : (f == 4 ? 3 : (f >= 8 ? 1 : 4)))) * (size_t)((word >> 8) == 3 ? 2 : 1);
+        per_sample = w > per_sample ? w : per_sample;
+    }
+    return n_samples * per_sample + (size_t)R * 64 + 16;
+}
+
 // one request per entry of `chunks` over rows of `frames` frames, request r in words[r]
 static void check_plan(const std::vector<int>& frames, const std::vector<int>& chunks, const std::vector<int>& words) {
     const int B = (int)frames.size(), R = (int)chunks.size();
-    kx::PackPlan plan;
+    kx::OutputPlan plan;
     plan.y_floats = 77;  // (stale contents must not survive)
     plan.max_resampled = 77;
-    kx::build_pack_plan(frames.data(), B, chunks.data(), R, words.data(), (int)words.size(), plan);
+    const kx::RequestLayout lay{chunks.data(), R, words.data(), (int)words.size(), nullptr, nullptr, 0};
+    kx::build_output_plan(frames.data(), nullptr, nullptr, B, lay, plan);
     CHECK(plan.req.size() == (size_t)R);
     long off = 0, units = 0, y = 0, widest = 0, S_all = 0;
     int row = 0;
@@ -77,7 +89,7 @@ static void check_plan(const std::vector<int>& frames, const std::vector<int>& c
         long S = 0;
         for (int i = 0; i < chunks[(size_t)r]; ++i) S += 600L * frames[(size_t)(row + i)];
         const long n = out_samples(rate, S);
-        CHECK(q.first_row == row && q.n_rows == chunks[(size_t)r] && q.form == form && q.pad_ == rate);
+        CHECK(q.first_row == row && q.n_rows == chunks[(size_t)r] && q.form == form && q.rate == rate);
         CHECK(q.src_samples == S && q.n_samples == n && n * RATE_M[rate] == S * RATE_L[rate]);
         CHECK(q.out_off == off && q.out_bytes == region_bytes(form, n) && q.out_bytes % 4 == 0);
         CHECK(q.out_bytes == kx::pack_request_bytes(word, S));
@@ -99,9 +111,11 @@ static void check_plan(const std::vector<int>& frames, const std::vector<int>& c
     hc.n_requests = R;
     hc.req_formats = words.data();
     hc.n_req_formats = (int)words.size();
-    const size_t bound = kx::pack_requests_bound(words.data(), (int)words.size(), R, (size_t)S_all);
-    CHECK(kx::packed_bytes_bound(hc, B, (size_t)S_all) == bound && (size_t)plan.total_bytes <= bound);
-    CHECK((size_t)plan.y_floats <= kx::resample_floats_bound(words.data(), (int)words.size(), (size_t)S_all));
+    const kx::OutputBounds bound = kx::output_bounds(lay, B, (size_t)S_all, nullptr);
+    const kx::OutputBounds same = kx::output_bounds(hc.layout(B), B, (size_t)S_all, nullptr);
+    CHECK(same.packed_bytes == bound.packed_bytes && same.y_floats == bound.y_floats);
+    CHECK(bound.packed_bytes == body_bound(words, R, (size_t)S_all) && (size_t)plan.total_bytes <= bound.packed_bytes);
+    CHECK((size_t)plan.y_floats <= bound.y_floats);
 }
 
 static void plans() {
@@ -125,10 +139,11 @@ static void plans() {
     check_plan({1, 2, 3, 5, 1, 1}, {1, 1, 1, 1, 1, 1}, {0, 2 | 0x200, 3, 9 | 0x100, 1 | 0x300, 4});
     {
         const int frames[3] = {1, 2, 3}, words[3] = {4, 3, 2};
-        kx::PackPlan plan;
-        kx::build_pack_plan(frames, 3, nullptr, 3, words, 3, plan);
+        kx::OutputPlan plan;
+        const kx::RequestLayout lay{nullptr, 3, words, 3, nullptr, nullptr, 0};
+        kx::build_output_plan(frames, nullptr, nullptr, 3, lay, plan);
         CHECK(plan.y_floats == 0 && plan.max_resampled == 0);  // nothing to resample: the resampler is not launched
-        CHECK(kx::resample_floats_bound(words, 3, 3600) == 0);
+        CHECK(kx::output_bounds(lay, 3, 3600, nullptr).y_floats == 0);
     }
     printf("plans: %d (rate, form, frames) triples\n", n);
 }
@@ -156,11 +171,11 @@ static void refusals() {
     const char* RATE = "infer: unknown output sample rate";
     int n = 0;
     const int one = 1, frames = 1;
-    kx::PackPlan plan;
+    kx::OutputPlan plan;
     auto all_refuse = [&](int word, const char* message) {
         CHECK(refused([&] { kx::check_format_word(word); }, message));
         CHECK(refused([&] { (void)kx::pack_request_bytes(word, 600); }, message));
-        CHECK(refused([&] { kx::build_pack_plan(&frames, 1, &one, 1, &word, 1, plan); }, message));
+        CHECK(refused([&] { kx::build_output_plan(&frames, nullptr, nullptr, 1, {&one, 1, &word, 1, nullptr, nullptr, 0}, plan); }, message));
         ++n;
     };
     for (int code = 4; code <= 15; ++code)

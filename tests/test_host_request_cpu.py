@@ -1,6 +1,5 @@
 """CPU: what a call is refused for before it touches the device, and where its output bytes go
-(kokorox_amd/csrc/host_request.cpp: check_host_call, check_device_call, build_pack_plan, pack_requests_bound,
-packed_bytes_bound).
+(kokorox_amd/csrc/host_request.cpp: check_host_call, check_device_call, build_output_plan, output_bounds).
 
 Model::infer_host_once and Model::infer_device take their argument checks and the layout of the compact output from that unit,
 which includes no HIP header: tests/cpp/host_request_check.cpp is built with g++ -fsanitize=address,undefined together with it

@@ -2,7 +2,7 @@
 
 Three layers, none of which needs a GPU: the numpy definition (kokorox_amd/voices.py: join_rows, join_stream, joined_marks)
 against answers worked out by hand (tests/golden/joins.json); the host layout (kokorox_amd/csrc/host_request.cpp:
-build_join_plan, build_mark_plan with a join plan, the two bounds, check_join_call) and the dispatcher's submit-time checks,
+build_output_plan with joins and marks, output_bounds, check_join_call) and the dispatcher's submit-time checks,
 built with g++ -fsanitize=address,undefined into tests/cpp/join_plan_check.cpp and run as a child process, against the golden
 answers and against the numpy definition on 200 seeded random cases; and the ABI (header, Python table, lib.rs).
 """
@@ -220,8 +220,8 @@ def test_plan_builder_gives_the_hand_derived_answers(driver):
 
 def test_plan_builder_equals_the_mirror_on_200_random_cases_and_the_bounds_hold(driver):
     """Rows 1..6, lens 1..6, durations 1..9, every flag set, mixed words, specs and want flags (a plain spec among them): the
-    rows, every request's sizes and offsets, and the marks equal the numpy definition; packed_bytes_bound and
-    resample_floats_bound, taken over the un-joined samples plus the pauses, are upper bounds of what the plan lays out."""
+    rows, every request's sizes and offsets, and the marks equal the numpy definition; the two bounds of
+    output_bounds, taken over the un-joined samples plus the pauses, are upper bounds of what the plan lays out."""
     rng = np.random.default_rng(20240611)
     forms, cases, text = (0, 1, 2, 3, 4, 8, 9), {}, ""
     for i in range(200):
@@ -299,8 +299,8 @@ def test_the_new_entries_are_part_of_the_abi():
     for name in ("kx_infer_requests_joined", "kx_dispatcher_submit_request_joined"):
         assert name in hk.ABI_SYMBOLS and re.search(r"^int %s\(" % name, header, re.M), name
         assert name not in test_header
-    assert "kx_test_join_requests" in hk.TEST_ABI_SYMBOLS and "kx_test_join_requests" not in hk.ABI_SYMBOLS
-    assert re.search(r"^int kx_test_join_requests\(", test_header, re.M) and "kx_test_join_requests" not in header
+    assert "kx_test_output_plan" in hk.TEST_ABI_SYMBOLS and "kx_test_output_plan" not in hk.ABI_SYMBOLS
+    assert re.search(r"^int kx_test_output_plan\(", test_header, re.M) and "kx_test_output_plan" not in header
     for text in ("infer: null join argument", "infer: bad join count", "infer: bad join", "infer: null marks argument",
                  "dispatcher_submit_request: bad join", "dispatcher_submit_request: null marks argument"):
         assert '"%s"' % text in header, text

@@ -1,6 +1,6 @@
 """CPU: token timing marks (include/kokorox_hip.h, "token marks") -- the numpy mirror of kokorox_amd/voices.py against known
-answers written out by hand, the host layout of the marks block (kokorox_amd/csrc/host_request.cpp: build_mark_plan,
-packed_bytes_bound, check_marks_call) through tests/cpp/marks_plan_check.cpp, built with g++ -fsanitize=address,undefined and run
+answers written out by hand, the host layout of the marks block (kokorox_amd/csrc/host_request.cpp: build_output_plan,
+output_bounds, check_marks_call) through tests/cpp/marks_plan_check.cpp, built with g++ -fsanitize=address,undefined and run
 as a child process (nothing is loaded into python), and the names of the new entries in the bindings.
 """
 import os
@@ -78,7 +78,7 @@ def driver(tmp_path_factory):
 
 def test_mark_plans_and_the_packed_bound(driver):
     """Counts, the block's offset (8-aligned, at or after the bodies) and every row's base for the groupings [1]*6, [2,1,3], [6]
-    in every form and rate, with all / none / some / null want flags (rows that are not wanted get -1); packed_bytes_bound
+    in every form and rate, with all / none / some / null want flags (rows that are not wanted get -1); the packed bound (output_bounds)
     unchanged without marks and large enough with them at one frame per token.  The driver compares with sums of its own."""
     out = driver("plans")
     print(out)
@@ -93,7 +93,6 @@ def test_refusals_of_the_marks_arguments(driver):
         "null_out_n_marks": "1\t" + NULL_MARKS,
         "marks_without_requests": "1\tinfer: marks are for requests (chunks_per_request)",
         "ok": "accepted",
-        "other_grouping": "1\tmarks: the grouping is not the plan's",
     }
 
 
@@ -102,14 +101,14 @@ def test_the_new_entries_are_part_of_the_abi():
     from kokorox_amd import hip_koko as hk
     assert "kx_infer_requests_marks" in hk.ABI_SYMBOLS
     assert "kx_dispatcher_submit_request_marks" in hk.ABI_SYMBOLS
-    assert "kx_test_token_marks" in hk.TEST_ABI_SYMBOLS
-    assert "kx_test_token_marks" not in hk.ABI_SYMBOLS  # (the hook lives in the test library only)
+    assert "kx_test_output_plan" in hk.TEST_ABI_SYMBOLS
+    assert "kx_test_output_plan" not in hk.ABI_SYMBOLS  # (the hook lives in the test library only)
     header = open(os.path.join(ROOT, "include", "kokorox_hip.h"), encoding="utf-8").read()
     test_header = open(os.path.join(ROOT, "include", "kokorox_hip_test.h"), encoding="utf-8").read()
     for name in ("kx_infer_requests_marks", "kx_dispatcher_submit_request_marks"):
         assert re.search(r"^int %s\(" % name, header, re.M), name
         assert name not in test_header
-    assert re.search(r"^int kx_test_token_marks\(", test_header, re.M) and "kx_test_token_marks" not in header
+    assert re.search(r"^int kx_test_output_plan\(", test_header, re.M) and "kx_test_output_plan" not in header
     # the refusal texts the GPU suite matches are the ones the header promises
     assert '"%s"' % NULL_MARKS in header and '"dispatcher_submit_request: null marks argument"' in header
 
