@@ -435,6 +435,44 @@ int kx_infer_requests_joined(kx_model* m, const int64_t* ids, int64_t t_stride, 
                              const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
                              int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join);
 
+/* ---- levels: gain, peak normalisation and ceiling of a request on the GPU ----------------------------------------------------
+ * The 16-bit forms (2, 4, and through them 8 and 9) clamp to +-1 without a word, the resampler's steep filter overshoots (a
+ * stream inside +-1 at 24 000 Hz need not stay inside it at the output rate) and a voice mix is un-normalised.  A level spec
+ * sets the level of a request's body where the body is made, behind the join and behind the resampler.
+ *   The stream.  Request r's stream z[0..N) is what form 0 in its format word would hold, N = out_samples[r]: after the join,
+ *   after the resampler, at the request's output rate.  Levels are measured and applied on that stream, the packer's input, so
+ *   a ceiling holds for the samples the body actually carries.
+ *   The peak.  p = the maximum of |z[n]| over all n for which z[n] is not a NaN, as a float32; p = 0 when there is no such n.
+ *   +inf counts.  p is "usable" when 0 < p < +inf.
+ *   The gain.  g is a float64.  Mode 0: g = f64(gain).  Mode 1: g = f64(peak) / f64(p) if p is usable, else 1.0.  Mode 2:
+ *   g = f64(gain); if p is usable and g * f64(p) > f64(peak) (one float64 product), then g = f64(peak) / f64(p).
+ *   The samples.  z'[n] = f32(g * f64(z[n])): one float64 product and one round-to-nearest-even conversion.  A NaN stays a
+ *   NaN.  The form (f32, stereo, PCM16, WAV, base64, G.711) is then applied to z' exactly as it is applied to z without
+ *   levels.  Marks, out_samples, headers and sizes do not change.
+ *   Valid specs.  mode is 0, 1 or 2; 0 <= gain <= 64, and gain is exactly 1.0f in mode 1; peak is +0.0f in mode 0 and
+ *   2^-15 <= peak <= 1 in modes 1 and 2; a NaN fails every one of these.  The plain spec is {0, 1.0f, 0.0f}: z' = z.
+ *   A property.  f32((f64(peak) / f64(p)) * f64(p)) == peak exactly: the quotient is within 2^-53 relative of peak / p, the
+ *   product within 2^-52 relative of the float32 value peak, far inside the half-ulp 2^-25 that rounds back onto it; rounding
+ *   is monotone, so no |z'[n]| exceeds it.  A request that mode 1 or mode 2 normalises therefore has a largest |sample| of
+ *   exactly `peak`, and with peak <= 1 the clamp of the 16-bit forms never engages. */
+#define KX_LEVEL_GAIN      0u  /* multiply by `gain`                                                   */
+#define KX_LEVEL_NORMALIZE 1u  /* scale so that the body's largest |sample| is `peak`                  */
+#define KX_LEVEL_CEILING   2u  /* multiply by `gain`, but never let the largest |sample| exceed `peak` */
+typedef struct kx_level { uint32_t mode; float gain; float peak; } kx_level;   /* 12 bytes */
+/* kx_infer_requests_joined with a level spec per request: levels [n_level], n_level = 1 (shared) or R.  `joins` may be NULL
+ * with n_join == 0 here (no joins); otherwise the join rules and refusals of kx_infer_requests_joined apply.  out_levels may be
+ * NULL; when given it receives [R][2] doubles, f64(p) and g of request r as the GPU computed them.  Through this entry every
+ * request is measured, a plain spec included: a plain spec with out_levels is a peak meter.  Body, marks and levels leave the
+ * device in one copy.  Refused with KX_ERR_INVALID before any device work, after everything kx_infer_requests_joined refuses
+ * (with its texts): a null `levels` ("infer: null level argument"), n_level not 1 or R ("infer: bad level count"), an invalid
+ * spec ("infer: bad level"). */
+int kx_infer_requests_levelled(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                               const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                               const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                               const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                               int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_level* levels,
+                               int n_level, double* out_levels);
+
 /* ---- request dispatcher ----------------------------------------------------
  * Replaces the reference's one-request-at-a-time `Mutex<Session>` (kokorox/src/onn/ort_koko.rs:78; callers
  * kokorox-openai/src/lib.rs:370-439, kokorox-websocket/src/lib.rs:657-668).  Any number of threads submit
@@ -507,6 +545,16 @@ int kx_dispatcher_submit_request_joined(kx_dispatcher* d, const int64_t* ids, co
                                         float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
                                         int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
                                         char* err, size_t err_len);
+/* kx_dispatcher_submit_request_joined with the request's level spec (see "levels" above); `join` may be NULL here (no join).
+ * out_level may be NULL; when given it receives two doubles, f64(p) and g of the request.  A null or invalid `level`:
+ * "dispatcher_submit_request: bad level"; every other refusal as kx_dispatcher_submit_request_joined.  Levelled, joined and
+ * plain requests, with and without marks, share batches; body, marks and levels equal those of kx_infer_requests_levelled
+ * (R = 1, same seed, utterance base 0) whatever the request was batched with. */
+int kx_dispatcher_submit_request_levelled(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                          const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
+                                          float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
+                                          int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
+                                          const kx_level* level, double* out_level, char* err, size_t err_len);
 /* n_requests counts requests, max_batch_seen the largest batch in ROWS (a request of n chunks is n rows). */
 int kx_dispatcher_stats(kx_dispatcher* d, int64_t* n_requests, int64_t* n_batches, int64_t* max_batch_seen);
 /* batches each model (worker) has run so far: per_model[n_models] */

@@ -115,6 +115,15 @@ int kx_test_output_plan(int device_id, const float* audio, int B, int64_t audio_
                         const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes, int64_t* out_samples,
                         int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks, char* err, size_t err_len);
 
+/* kx_test_output_plan with levels (include/kokorox_hip.h, "levels"): levels [R] (one spec per request; needs audio), out_levels
+ * [R][2] doubles = f64(p) and g of every request as request_gain_kernel stored them.  The order is resampler, peak, gain, packer,
+ * marks, through launch_output_plan.  levels = NULL (then out_levels = NULL too) is kx_test_output_plan, which calls this. */
+int kx_test_output_plan_levelled(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames, const int32_t* dur,
+                                 const int32_t* lens, const int32_t* chunks_per_request, int R, const int32_t* formats,
+                                 const kx_join* joins, const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes,
+                                 int64_t* out_samples, int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks,
+                                 const kx_level* levels, double* out_levels, char* err, size_t err_len);
+
 /* Fault injection for the two-CU LSTM recurrence (process-wide, test only): nth > 0 makes the nth following launch of
  * the pair kernel, and every later one, lose the second half of each pair and poll with a short limit, so the call it
  * belongs to must fail with KX_ERR_DEVICE (the bounded wait's error path) and the model must fall back to the one-CU

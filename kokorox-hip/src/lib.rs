@@ -59,6 +59,26 @@ pub struct KxJoin {
     pub fade_ms: i32,
 }
 
+pub const KX_LEVEL_GAIN: u32 = 0;
+pub const KX_LEVEL_NORMALIZE: u32 = 1;
+pub const KX_LEVEL_CEILING: u32 = 2;
+
+/// How a request's level is set on the GPU (`kx_level`; "levels" in kokorox_hip.h): mode 0 multiplies by `gain` (0..64, `peak`
+/// +0.0), mode 1 scales so that the body's largest |sample| is `peak` (2^-15..1, `gain` 1.0), mode 2 multiplies by `gain` but
+/// never lets the largest |sample| exceed `peak`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct KxLevel {
+    pub mode: u32,
+    pub gain: f32,
+    pub peak: f32,
+}
+
+impl KxLevel {
+    /// The plain spec: the samples as they are (through the levelled entries: a peak meter).
+    pub const PLAIN: KxLevel = KxLevel { mode: KX_LEVEL_GAIN, gain: 1.0, peak: 0.0 };
+}
+
 #[repr(C)]
 pub struct KxModel {
     _p: [u8; 0],
@@ -137,6 +157,12 @@ extern "C" {
                                 formats: *const i32, n_format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
                                 out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64, joins: *const KxJoin,
                                 n_join: c_int) -> c_int;
+    fn kx_infer_requests_levelled(m: *mut KxModel, ids: *const i64, t_stride: i64, lens: *const i32, b: c_int,
+                                  chunks_per_request: *const i32, r: c_int, styles: *const f32, voice_ids: *const i32,
+                                  weights: *const f32, max_mix: c_int, speeds: *const f32, n_speed: c_int, seed: u64, flags: u32,
+                                  formats: *const i32, n_format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                                  out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64, joins: *const KxJoin,
+                                  n_join: c_int, levels: *const KxLevel, n_level: c_int, out_levels: *mut f64) -> c_int;
     fn kx_dispatcher_create(models: *mut *mut KxModel, n_models: c_int, max_batch: c_int, max_wait_us: c_int,
                             err: *mut c_char, err_len: usize) -> *mut KxDispatcher;
     fn kx_dispatcher_create_warm(models: *mut *mut KxModel, n_models: c_int, max_batch: c_int, max_wait_us: c_int,
@@ -162,6 +188,12 @@ extern "C" {
                                            speed: f32, seed: u64, format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
                                            out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64,
                                            join: *const KxJoin, err: *mut c_char, err_len: usize) -> c_int;
+    fn kx_dispatcher_submit_request_levelled(d: *mut KxDispatcher, ids: *const i64, chunk_tokens: *const i32, n_chunks: c_int,
+                                             styles: *const f32, voice_ids: *const i32, weights: *const f32, n_mix: c_int,
+                                             speed: f32, seed: u64, format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                                             out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64,
+                                             join: *const KxJoin, level: *const KxLevel, out_level: *mut f64, err: *mut c_char,
+                                             err_len: usize) -> c_int;
     fn kx_dispatcher_stats(d: *mut KxDispatcher, n_requests: *mut i64, n_batches: *mut i64,
                            max_batch_seen: *mut i64) -> c_int;
     fn kx_dispatcher_failures(d: *mut KxDispatcher, n_replayed: *mut i64, n_retried: *mut i64) -> c_int;
@@ -532,6 +564,46 @@ impl HipKoko {
         Ok(res)
     }
 
+    /// `infer_requests_joined` with the level of every request set on the GPU ("levels" in kokorox_hip.h): `levels` holds one
+    /// spec for all requests or one per request, `joins` may be empty (no joins).  Per request: body, marks, and (p, g), the
+    /// peak of its stream and the gain applied, as the GPU computed them.
+    #[allow(clippy::type_complexity)]
+    pub fn infer_requests_levelled(&self, tokens: &[Vec<i64>], chunks_per_request: &[i32], styles: &[Vec<f32>], speeds: &[f32],
+                                   seed: u64, formats: &[c_int], joins: &[KxJoin], levels: &[KxLevel])
+                                   -> Result<Vec<(Vec<u8>, Vec<i64>, (f64, f64))>, Box<dyn Error>> {
+        if tokens.is_empty() || styles.len() != tokens.len() || styles.iter().any(|s| s.len() != KX_STYLE_DIM) {
+            return Err("infer_requests: one style row of 256 floats per chunk is required".into());
+        }
+        let (b, r) = (tokens.len(), chunks_per_request.len());
+        let (ids, lens, stride) = Self::flatten(tokens);
+        let st: Vec<f32> = styles.iter().flatten().copied().collect();
+        let mut out: *mut c_void = ptr::null_mut();
+        let mut mk: *mut i64 = ptr::null_mut();
+        let (mut nbytes, mut nsamp, mut nmarks) = (vec![0i64; r.max(1)], vec![0i64; r.max(1)], vec![0i64; r.max(1)]);
+        let mut lv = vec![0f64; 2 * r.max(1)];
+        let rc = unsafe {
+            kx_infer_requests_levelled(self.h, ids.as_ptr(), stride as i64, lens.as_ptr(), b as c_int, chunks_per_request.as_ptr(),
+                                       r as c_int, st.as_ptr(), ptr::null(), ptr::null(), 0, speeds.as_ptr(), speeds.len() as c_int,
+                                       seed, 0, formats.as_ptr(), formats.len() as c_int, &mut out, nbytes.as_mut_ptr(),
+                                       nsamp.as_mut_ptr(), &mut mk, nmarks.as_mut_ptr(),
+                                       if joins.is_empty() { ptr::null() } else { joins.as_ptr() }, joins.len() as c_int,
+                                       levels.as_ptr(), levels.len() as c_int, lv.as_mut_ptr())
+        };
+        self.check(rc)?;
+        let mut res = Vec::with_capacity(r);
+        let (mut at, mut mat) = (0usize, 0usize);
+        for i in 0..r {
+            // (the marks live in the buffer of `out`: copied before it is released)
+            let body = unsafe { std::slice::from_raw_parts((out as *const u8).add(at), nbytes[i] as usize) }.to_vec();
+            let marks = unsafe { std::slice::from_raw_parts((mk as *const i64).add(mat), nmarks[i] as usize) }.to_vec();
+            at += nbytes[i] as usize;
+            mat += nmarks[i] as usize;
+            res.push((body, marks, (lv[2 * i], lv[2 * i + 1])));
+        }
+        unsafe { kx_free_packed(out) };
+        Ok(res)
+    }
+
     /// Raw device-pointer form (inputs and output stay in HBM).
     ///
     /// # Safety
@@ -851,6 +923,37 @@ impl HipKokoDispatcher {
         let marks = unsafe { std::slice::from_raw_parts(mk as *const i64, nm as usize) }.to_vec();
         unsafe { kx_free_packed(out) };
         Ok((v, marks, ns))
+    }
+
+    /// `submit_request_joined` with the request's level spec ("levels" in kokorox_hip.h; `join` = None: no join): body, marks,
+    /// sample count, and (p, g), the peak of the request's stream and the gain applied.
+    #[allow(clippy::too_many_arguments, clippy::type_complexity)]
+    pub fn submit_request_levelled(&self, chunks: &[Vec<i64>], styles: &[f32], speed: f32, seed: u64, format: i32,
+                                   join: Option<KxJoin>, level: KxLevel) -> Result<(Vec<u8>, Vec<i64>, i64, (f64, f64)), Box<dyn Error>> {
+        if styles.len() != KX_STYLE_DIM * chunks.len() {
+            return Err("submit_request: one style row of 256 floats per chunk is required".into());
+        }
+        let ids: Vec<i64> = chunks.iter().flatten().copied().collect();
+        let lens: Vec<i32> = chunks.iter().map(|c| c.len() as i32).collect();
+        let mut out: *mut c_void = ptr::null_mut();
+        let mut mk: *mut i64 = ptr::null_mut();
+        let (mut nb, mut ns, mut nm) = (0i64, 0i64, 0i64);
+        let mut lv = [0f64; 2];
+        let mut err = vec![0 as c_char; 256];
+        let rc = unsafe {
+            kx_dispatcher_submit_request_levelled(self.d, ids.as_ptr(), lens.as_ptr(), lens.len() as c_int, styles.as_ptr(), ptr::null(),
+                                                  ptr::null(), 0, speed, seed, format, &mut out, &mut nb, &mut ns, &mut mk, &mut nm,
+                                                  join.as_ref().map_or(ptr::null(), |j| j as *const KxJoin), &level, lv.as_mut_ptr(),
+                                                  err.as_mut_ptr(), err.len())
+        };
+        if rc != KX_OK {
+            return Err(format!("kokorox_hip error {}: {}", rc, cstr_buf(&err)).into());
+        }
+        let v = unsafe { std::slice::from_raw_parts(out as *const u8, nb as usize) }.to_vec();
+        // (inside the allocation of `out`: copied before it is released)
+        let marks = unsafe { std::slice::from_raw_parts(mk as *const i64, nm as usize) }.to_vec();
+        unsafe { kx_free_packed(out) };
+        Ok((v, marks, ns, (lv[0], lv[1])))
     }
 
     /// The WebSocket chunk of `encode_audio` (kokorox-websocket/src/lib.rs:696-736) for a request: base64 of its 16-bit WAV

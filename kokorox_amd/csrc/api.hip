@@ -287,14 +287,20 @@ static_assert(sizeof(kx_join) == sizeof(kx::JoinSpec) && offsetof(kx_join, flags
                   KX_JOIN_TRIM_TAIL == kx::JOIN_TRIM_TAIL && KX_JOIN_TRIM_INNER == kx::JOIN_TRIM_INNER,
               "kx_join is the layout of kx::JoinSpec");
 
-// kx_infer_requests, kx_infer_requests_marks and kx_infer_requests_joined are one call: the first asks for no marks, the first
-// two for no joins
+static_assert(sizeof(kx_level) == 12 && sizeof(kx_level) == sizeof(kx::LevelSpec) && offsetof(kx_level, mode) == offsetof(kx::LevelSpec, mode) &&
+                  offsetof(kx_level, gain) == offsetof(kx::LevelSpec, gain) && offsetof(kx_level, peak) == offsetof(kx::LevelSpec, peak) &&
+                  KX_LEVEL_GAIN == kx::LEVEL_GAIN && KX_LEVEL_NORMALIZE == kx::LEVEL_NORMALIZE && KX_LEVEL_CEILING == kx::LEVEL_CEILING,
+              "kx_level is the layout of kx::LevelSpec");
+
+// kx_infer_requests, kx_infer_requests_marks, kx_infer_requests_joined and kx_infer_requests_levelled are one call: the first asks
+// for no marks, the first two for no joins, the first three for no levels
 static int infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
                           const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
                           const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
                           const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
                           bool marks, int64_t** out_marks, int64_t* out_n_marks, bool joined = false, const kx_join* joins = nullptr,
-                          int n_join = 0) {
+                          int n_join = 0, bool levelled = false, const kx_level* levels = nullptr, int n_level = 0,
+                          double* out_levels = nullptr) {
     return guarded(m, [&](Model& M) {
         KX_REQUIRE(chunks_per_request && formats && R >= 1, "infer_requests: null argument");
         KX_REQUIRE((styles != nullptr) != (voice_ids != nullptr), "infer_requests: give the style rows OR voice ids, not both");
@@ -318,7 +324,13 @@ static int infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, con
             hc.req_joins = reinterpret_cast<const kx::JoinSpec*>(joins);
             hc.n_req_joins = n_join;
         }
-        M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks);
+        if (levelled) {  // (a null `levels` is refused with the call's other arguments: check_level_call)
+            hc.level_call = true;
+            hc.req_levels = reinterpret_cast<const kx::LevelSpec*>(levels);
+            hc.n_req_levels = n_level;
+        }
+        M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks,
+                        levelled ? out_levels : nullptr);
     });
 }
 
@@ -347,6 +359,18 @@ int kx_infer_requests_joined(kx_model* m, const int64_t* ids, int64_t t_stride, 
     return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
                           flags, formats, n_format, out, out_bytes, out_samples, out_marks || out_n_marks, out_marks, out_n_marks, true,
                           joins, n_join);
+}
+
+int kx_infer_requests_levelled(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                               const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                               const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                               const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                               int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_level* levels,
+                               int n_level, double* out_levels) {
+    // (joins == NULL with n_join == 0: no joins; anything else goes through the join entry's checks)
+    return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
+                          flags, formats, n_format, out, out_bytes, out_samples, out_marks || out_n_marks, out_marks, out_n_marks,
+                          joins != nullptr || n_join != 0, joins, n_join, true, levels, n_level, out_levels);
 }
 
 int kx_infer_device(kx_model* m, const int64_t* d_ids, int64_t t_stride, const int32_t* lens_host, int B,

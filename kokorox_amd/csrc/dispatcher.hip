@@ -24,6 +24,7 @@ struct ModelBackend {
         // the token marks of the requests that want them: one block in the same buffer, behind the bodies (null: nobody asked)
         int64_t* marks = nullptr;
         std::vector<int64_t> n_marks;
+        std::vector<double> levels;  // [R][2] = {f64(p), g} when some request of the batch came through the levelled entry, else empty
     };
     static int n_voices(kx_model* h) { return h->m->n_voices(); }
     static int n_vocab(kx_model* h) { return h->m->n_vocab(); }
@@ -35,10 +36,11 @@ struct ModelBackend {
         int B = 0;
         size_t stride = 0;
         int mm = 1;
-        bool any_voice = false, any_marks = false, any_join = false;
+        bool any_voice = false, any_marks = false, any_join = false, any_level = false;
         for (Request* r : batch) {
             any_marks = any_marks || r->want_marks;
             any_join = any_join || r->joined();
+            any_level = any_level || r->levelled;
             B += r->rows();
             for (int c = 0; c < r->rows(); ++c) stride = (size_t)r->chunk_len(c) > stride ? (size_t)r->chunk_len(c) : stride;
             mm = r->n_mix > mm ? r->n_mix : mm;
@@ -51,6 +53,7 @@ struct ModelBackend {
         std::vector<uint32_t> uidx(B);
         std::vector<uint8_t> want(R);
         std::vector<kx::JoinSpec> joins(R);  // (a plain request beside a joined one: the all-zero spec, the plain bytes)
+        std::vector<kx::LevelSpec> levels(R);  // (a request without levels beside a levelled one: the plain spec, z' = z)
         int b = 0;
         for (int q = 0; q < R; ++q) {
             const Request& r = *batch[(size_t)q];
@@ -58,6 +61,7 @@ struct ModelBackend {
             formats[q] = r.format;
             want[q] = r.want_marks ? 1 : 0;
             joins[q] = kx::JoinSpec{r.join.flags, r.join.keep_ms, r.join.pause_ms, r.join.fade_ms};
+            levels[q] = kx::LevelSpec{r.level.mode, r.level.gain, r.level.peak};
             size_t at = 0;
             for (int c = 0; c < r.rows(); ++c, ++b) {
                 lens[b] = (int32_t)r.chunk_len(c);
@@ -79,6 +83,7 @@ struct ModelBackend {
         o.samples.assign(R, 0);
         o.marks = nullptr;
         o.n_marks.assign(R, 0);
+        o.levels.assign(any_level ? (size_t)2 * R : 0, 0.0);
         int rc = KX_ERR_DEVICE;
         std::string err;
         {
@@ -100,6 +105,10 @@ struct ModelBackend {
                     hc.req_joins = joins.data();
                     hc.n_req_joins = R;
                 }
+                if (any_level) {
+                    hc.req_levels = levels.data();
+                    hc.n_req_levels = R;
+                }
                 if (any_voice) {
                     hc.voice_ids = vids.data();
                     hc.weights = weights.data();
@@ -110,7 +119,7 @@ struct ModelBackend {
                     hc.styles = styles.data();
                 }
                 M.infer_host_ex(ids.data(), (int64_t)stride, lens.data(), B, speeds.data(), B, 0, 0, hc, &o.buf, o.bytes.data(),
-                                o.samples.data(), &o.marks, o.n_marks.data());
+                                o.samples.data(), &o.marks, o.n_marks.data(), any_level ? o.levels.data() : nullptr);
                 rc = KX_OK;
             } catch (const kx::Error& e) {
                 rc = e.code;
@@ -183,6 +192,10 @@ struct ModelBackend {
             r->out_samples = o.samples[(size_t)b];
             r->marks = r->want_marks ? marks[(size_t)b] : nullptr;
             r->n_marks = r->want_marks ? o.n_marks[(size_t)b] : 0;
+            if (r->levelled && !o.levels.empty()) {
+                r->level_out[0] = o.levels[(size_t)2 * b];
+                r->level_out[1] = o.levels[(size_t)2 * b + 1];
+            }
         }
         o.buf = nullptr;
         o.marks = nullptr;
@@ -305,6 +318,19 @@ int kx_dispatcher_submit_request_joined(kx_dispatcher* d, const int64_t* ids, co
     }
     return d->submit_request_joined(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
                                     out_bytes, out_samples, out_marks, out_n_marks, join, err, err_len);
+}
+
+int kx_dispatcher_submit_request_levelled(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                          const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
+                                          float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
+                                          int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
+                                          const kx_level* level, double* out_level, char* err, size_t err_len) {
+    if (!d) {
+        if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null dispatcher");
+        return KX_ERR_INVALID;
+    }
+    return d->submit_request_levelled(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
+                                      out_bytes, out_samples, out_marks, out_n_marks, join, level, out_level, err, err_len);
 }
 
 int kx_dispatcher_stats(kx_dispatcher* d, int64_t* n_requests, int64_t* n_batches, int64_t* max_batch_seen) {

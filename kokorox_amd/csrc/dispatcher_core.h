@@ -45,7 +45,9 @@
 //                                                                         (and Out on success), returns the batch's status
 //   static void distribute(std::vector<dispatch::Request*>&, Out&);       gives every request its out / out_bytes / out_samples
 //                                                                         (and marks / n_marks where want_marks is set);
-//                                                                         Request::join shapes a request's seams
+//                                                                         Request::join shapes a request's seams;
+//                                                                         Request::level sets its level, and a request
+//                                                                         with `levelled` set gets level_out = {f64(p), g}
 //   static int n_voices(Handle*);                                         rows of the model's voice table (0 = none)
 //   static int n_vocab(Handle*);                                          rows of its embedding tables (token ids are 0 .. n_vocab - 1)
 //   static void free_out(void*);                                          releases a request's `out` (what distribute handed out)
@@ -63,6 +65,7 @@
 #include <vector>
 
 #include "../../include/kokorox_hip.h"
+#include "host_request.h"
 
 namespace kx {
 namespace dispatch {
@@ -85,12 +88,15 @@ struct Request {
     uint64_t seed = 0;
     kx_join join = {0, 0, 0, 0};  // how its seams are shaped (submit_request_joined); all zeros = the chunks appended
     bool joined() const { return join.flags || join.keep_ms || join.pause_ms || join.fade_ms; }
+    kx_level level = {KX_LEVEL_GAIN, 1.0f, 0.0f};  // its level spec (submit_request_levelled); the plain spec = the samples as they are
+    bool levelled = false;    // it came through the levelled entry: it is measured, whatever its spec
     bool want_marks = false;  // the token marks of the request beside its body (submit_request_marks); a batch may mix both kinds
     // result
     void* out = nullptr;
     int64_t out_bytes = 0, out_samples = 0;
     int64_t* marks = nullptr;  // want_marks: into the allocation of `out`, 8-byte aligned behind the body; released with `out`
     int64_t n_marks = 0;
+    double level_out[2] = {0.0, 1.0};  // levelled: f64(p) and g of the request, as the GPU computed them
     int rc = -1;
     std::string err;
     bool done = false;
@@ -462,10 +468,27 @@ struct Core {
         return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
                                   out_samples, out_marks || out_n_marks, out_marks, out_n_marks, err, err_len, join);
     }
+    // ... and with its level spec; `join` may be null here (no join), out_level may be null
+    int submit_request_levelled(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
+                                const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
+                                void** out, int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
+                                const kx_join* join, const kx_level* level, double* out_level, char* err, size_t err_len) {
+        if (join && !join_spec_ok(JoinSpec{join->flags, join->keep_ms, join->pause_ms, join->fade_ms})) {
+            if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: bad join");
+            return KX_ERR_INVALID;
+        }
+        if (!level || !level_spec_ok(LevelSpec{level->mode, level->gain, level->peak})) {
+            if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: bad level");
+            return KX_ERR_INVALID;
+        }
+        return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
+                                  out_samples, out_marks || out_n_marks, out_marks, out_n_marks, err, err_len, join, level, out_level);
+    }
     int submit_request_any(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
                            const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
                            void** out, int64_t* out_bytes, int64_t* out_samples, bool want_marks, int64_t** out_marks,
-                           int64_t* out_n_marks, char* err, size_t err_len, const kx_join* join = nullptr) {
+                           int64_t* out_n_marks, char* err, size_t err_len, const kx_join* join = nullptr,
+                           const kx_level* level = nullptr, double* out_level = nullptr) {
         const char* who = "dispatcher_submit_request";
         if (!out || !out_bytes || !out_samples) {
             if (err && err_len) snprintf(err, err_len, "%s: null output argument", who);
@@ -510,10 +533,18 @@ struct Core {
         r.seed = seed;
         r.want_marks = want_marks;
         if (join) r.join = *join;
+        if (level) {
+            r.level = *level;
+            r.levelled = true;
+        }
         const int rc = submit(r, out, out_bytes, out_samples, err, err_len);
         if (rc == KX_OK && want_marks) {
             *out_marks = r.marks;
             *out_n_marks = r.n_marks;
+        }
+        if (rc == KX_OK && level && out_level) {
+            out_level[0] = r.level_out[0];
+            out_level[1] = r.level_out[1];
         }
         return rc;
     }

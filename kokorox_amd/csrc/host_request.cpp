@@ -108,6 +108,12 @@ void check_join_call(const HostCall& hc) {
     for (int i = 0; i < hc.n_req_joins; ++i) KX_REQUIRE(join_spec_ok(hc.req_joins[i]), "infer: bad join");
 }
 
+void check_level_call(const HostCall& hc) {
+    KX_REQUIRE(hc.req_levels, "infer: null level argument");
+    KX_REQUIRE(hc.grouped() && (hc.n_req_levels == 1 || hc.n_req_levels == hc.n_requests), "infer: bad level count");
+    for (int i = 0; i < hc.n_req_levels; ++i) KX_REQUIRE(level_spec_ok(hc.req_levels[i]), "infer: bad level");
+}
+
 // ---- refusals of the device entry (Model::infer_device) ----------------------------------------------------------------------
 int check_device_call(const void* d_ids, int64_t t_stride, const int32_t* lens_host, int B, const void* d_styles,
                       const float* speeds_host, int n_speed) {
@@ -143,11 +149,16 @@ OutputBounds output_bounds(const RequestLayout& lay, int B, size_t n_samples, co
         per_sample = w > per_sample ? w : per_sample;
         y_per_sample = y > y_per_sample ? y : y_per_sample;
     }
-    OutputBounds bound{n_samples * per_sample + (size_t)lay.R * 64 + 16, n_samples * y_per_sample};
+    OutputBounds bound{n_samples * per_sample + (size_t)lay.R * 64 + 16, n_samples * y_per_sample, 0};
     if (lay.marks) {
         KX_REQUIRE(lens, "infer: marks need the token counts");
         bound.packed_bytes += 8;
         for (int b = 0; b < B; ++b) bound.packed_bytes += 8 * ((size_t)lens[b] + 1);
+    }
+    if (lay.levels) {  // (no request is longer than all the samples at the batch's highest ratio)
+        bound.packed_bytes += 8 + 16 * (size_t)lay.R;
+        const size_t longest = n_samples * (y_per_sample > 1 ? y_per_sample : 1);
+        bound.peak_dwords = (size_t)lay.R * ((longest + (size_t)LEVEL_WINDOW - 1) / (size_t)LEVEL_WINDOW + 1);
     }
     return bound;
 }
@@ -170,7 +181,8 @@ long pack_request_bytes(int form, long n_samples) {
 void build_output_plan(const int* frames, const int* lens, const int* edges, int B, const RequestLayout& lay, OutputPlan& plan) {
     const int R = lay.R;
     KX_REQUIRE(frames && lay.formats && B >= 1 && R >= 1 && (lay.n_format == 1 || lay.n_format == R) &&
-                   (!lay.joins || (edges && (lay.n_join == 1 || lay.n_join == R))) && (lens || (!lay.marks && !lay.joins)),
+                   (!lay.joins || (edges && (lay.n_join == 1 || lay.n_join == R))) && (lens || (!lay.marks && !lay.joins)) &&
+                   (!lay.levels || lay.n_level == 1 || lay.n_level == R),
                "plan: bad argument");
     auto rows_of = [&](int r) { return lay.chunks_per_request ? lay.chunks_per_request[r] : 1; };
     // the rows: what each contributes to its request's stream, and the prefix over it.  (A pass of its own: the refusals of the
@@ -258,6 +270,24 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
         row += n;
     }
     plan.marks_off = (plan.total_bytes + 7) & ~7L;
+    // the levels: every request's spec, the block behind the marks and the grid of the peak pass
+    plan.level.clear();
+    plan.measured = lay.levels != nullptr;
+    plan.levelled = false;
+    plan.levels_off = plan.peak_windows = 0;
+    if (plan.measured) {
+        plan.level.resize((size_t)R);
+        long longest = 0;
+        for (int r = 0; r < R; ++r) {
+            const LevelSpec& ls = lay.levels[lay.n_level == 1 ? 0 : r];
+            KX_REQUIRE(level_spec_ok(ls), "infer: bad level");
+            plan.level[(size_t)r] = ls;
+            plan.levelled = plan.levelled || !level_spec_plain(ls);
+            longest = plan.req[(size_t)r].n_samples > longest ? plan.req[(size_t)r].n_samples : longest;
+        }
+        plan.levels_off = (plan.marks_off + 8 * plan.n_marks + 7) & ~7L;
+        plan.peak_windows = (longest + LEVEL_WINDOW - 1) / LEVEL_WINDOW;
+    }
 }
 
 }  // namespace kx

@@ -4,6 +4,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -25,8 +26,30 @@ inline bool join_spec_ok(const JoinSpec& j) {
 }
 inline bool join_spec_plain(const JoinSpec& j) { return j.flags == 0 && j.keep_ms == 0 && j.pause_ms == 0 && j.fade_ms == 0; }
 
+// A request's level spec: the layout of kx_level (include/kokorox_hip.h, "levels"; api.hip asserts the two agree).
+struct LevelSpec {
+    uint32_t mode;  // LEVEL_GAIN, LEVEL_NORMALIZE or LEVEL_CEILING
+    float gain;     // 0..64; exactly 1 in mode 1
+    float peak;     // +0 in mode 0; 2^-15..1 in modes 1 and 2
+};
+constexpr uint32_t LEVEL_GAIN = 0u, LEVEL_NORMALIZE = 1u, LEVEL_CEILING = 2u;
+inline uint32_t level_float_bits(float v) {
+    uint32_t u;
+    std::memcpy(&u, &v, sizeof u);
+    return u;
+}
+// (every comparison is written so that a NaN fails it)
+inline bool level_spec_ok(const LevelSpec& l) {
+    if (l.mode > LEVEL_CEILING || !(l.gain >= 0.0f && l.gain <= 64.0f)) return false;
+    if (l.mode == LEVEL_GAIN) return level_float_bits(l.peak) == 0u;  // +0.0f and nothing else
+    return (l.mode != LEVEL_NORMALIZE || l.gain == 1.0f) && l.peak >= 0x1p-15f && l.peak <= 1.0f;
+}
+inline bool level_spec_plain(const LevelSpec& l) { return l.mode == LEVEL_GAIN && l.gain == 1.0f && level_float_bits(l.peak) == 0u; }
+// samples of a request's stream (at its output rate) that one workgroup of the peak pass reduces (request_kernels.hip)
+constexpr long LEVEL_WINDOW = 4096;
+
 // What a call asks of the output stage (a view: the arrays are the caller's): how its rows group into requests, and each
-// request's format word, wish for token marks and join spec.  build_output_plan and output_bounds take it.
+// request's format word, wish for token marks, join spec and level spec.  build_output_plan and output_bounds take it.
 struct RequestLayout {
     const int32_t* chunks_per_request;  // [R] rows of each request; null: every row a request of its own, and R = B
     int R;
@@ -35,6 +58,8 @@ struct RequestLayout {
     const uint8_t* marks;               // [R] request r wants token marks when marks[r] != 0; null: none does
     const JoinSpec* joins;              // [n_join] with n_join = 1 (shared) or R; null: the rows are appended as they are
     int n_join;
+    const LevelSpec* levels;            // [n_level] with n_level = 1 (shared) or R; null: nothing is measured or scaled
+    int n_level;
 };
 
 // general host entry behind kx_infer / kx_infer_voices / kx_infer_packed / kx_infer_requests (Model::infer_host_ex)
@@ -61,14 +86,19 @@ struct HostCall {
     bool join_call = false;                       // the entry that takes joins: req_joins must then be there (check_join_call)
     const JoinSpec* req_joins = nullptr;          // host [n_req_joins]
     int n_req_joins = 0;                          // 1 (shared) or n_requests
+    // levels (include/kokorox_hip.h, "levels"): request r is measured and scaled by req_levels[n_req_levels == 1 ? 0 : r]; null = none
+    bool level_call = false;                      // the entry that takes levels: req_levels must then be there (check_level_call)
+    const LevelSpec* req_levels = nullptr;        // host [n_req_levels]
+    int n_req_levels = 0;                         // 1 (shared) or n_requests
 
     bool grouped() const { return chunks_per_request != nullptr; }
     bool by_voice() const { return voice_ids != nullptr; }
     int kind_of(int b) const { return kinds ? kinds[b] : (by_voice() ? (max_mix == 1 ? 1 : 2) : 0); }
     // what the call asks of the output stage: a call without chunks_per_request is B single-row requests sharing `format`
     RequestLayout layout(int B) const {
-        if (!grouped()) return RequestLayout{nullptr, B, &format, 1, nullptr, nullptr, 0};
-        return RequestLayout{chunks_per_request, n_requests, req_formats, n_req_formats, req_marks, req_joins, n_req_joins};
+        if (!grouped()) return RequestLayout{nullptr, B, &format, 1, nullptr, nullptr, 0, nullptr, 0};
+        return RequestLayout{chunks_per_request, n_requests, req_formats, n_req_formats, req_marks, req_joins, n_req_joins, req_levels,
+                             n_req_levels};
     }
 };
 
@@ -87,6 +117,9 @@ void check_marks_call(const HostCall& hc, int64_t** out_marks, int64_t* out_n_ma
 // "infer: bad join" (a stray flag bit or a field outside its range).  Its marks arguments may both be null (no marks); exactly
 // one null is check_marks_call's refusal.
 void check_join_call(const HostCall& hc);
+// The entry that takes levels (HostCall::level_call), checked after everything above.  throws KX_ERR_INVALID: "infer: null level
+// argument", "infer: bad level count" (not 1 or R), "infer: bad level" (level_spec_ok fails).
+void check_level_call(const HostCall& hc);
 // Everything Model::infer_device refuses before hipSetDevice; returns the longest token count.
 int check_device_call(const void* d_ids, int64_t t_stride, const int32_t* lens_host, int B, const void* d_styles,
                       const float* speeds_host, int n_speed);
@@ -161,7 +194,16 @@ struct OutputPlan {
     std::vector<long> first;    // [R] index of request r's first mark in the block
     long marks_off = 0;         // byte offset of the block in the packed buffer (a multiple of 8, >= total_bytes)
     long n_marks = 0;           // int64 values of the block
-    long end_bytes() const { return marks_off + 8 * n_marks; }  // bytes of body + marks: what one copy brings to the host
+    // Levels (include/kokorox_hip.h, "levels"; request_kernels.hip: request_peak_kernel, request_gain_kernel): a third block
+    // behind the marks, [R]{double p, double g}, so body, marks and levels still leave the device in one copy.
+    std::vector<LevelSpec> level;  // [R]; empty when the layout has no levels
+    bool measured = false;         // levels were given: every request's peak is taken and its {p, g} stored
+    bool levelled = false;         // some spec is not the plain one: the levelled packer runs
+    long levels_off = 0;           // byte offset of the block (a multiple of 8, >= marks_off + 8 n_marks); 0 when not measured
+    long peak_windows = 0;         // LEVEL_WINDOW-sample windows of the longest request: the peak pass's grid and table stride
+    long peak_dwords() const { return measured ? (long)req.size() * peak_windows : 0; }  // the partials table [R][peak_windows]
+    // bytes of body + marks (+ levels): what one copy brings to the host
+    long end_bytes() const { return measured ? levels_off + 16 * (long)req.size() : marks_off + 8 * n_marks; }
 };
 // `form` = a format word, n_samples at 24 000 Hz.  throws KX_ERR_INVALID: unknown word, 16-bit WAV past 4 GiB
 long pack_request_bytes(int form, long n_samples);
@@ -176,9 +218,10 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
 // of the layout's words (48 000 Hz doubles the samples; the per-request header and the base64 padding do not scale with the
 // samples); with marks (lens [B] then required) 8 + 8 x the sum over the rows of lens + 1 more: the alignment gap and a block
 // in which every request wants them.  y_floats: the intermediate buffer of the resampled streams, 0 when no word carries a
-// rate code.
+// rate code.  With levels 8 + 16 R bytes more (the alignment gap and the block), and peak_dwords: the partials table of the peak
+// pass, R rows of the windows the longest request can have.
 struct OutputBounds {
-    size_t packed_bytes, y_floats;
+    size_t packed_bytes, y_floats, peak_dwords;
 };
 OutputBounds output_bounds(const RequestLayout& layout, int B, size_t n_samples, const int32_t* lens);
 

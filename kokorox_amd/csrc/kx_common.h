@@ -288,17 +288,22 @@ void launch_style_mix(const float* table, int n_voices, const int* voice_ids, co
 
 // ---- the output stage of a call (request_kernels.hip; host_request.h: OutputPlan, build_output_plan) ----------------------
 // Device memory for a plan's tables, which the launchers copy the plan into: req [R], cum [B + 1], join [B] (used by a joined
-// plan only), mark [B] (used when a request wants marks only)
+// or levelled plan only), mark [B] (used when a request wants marks only); a measured plan (OutputPlan::measured) also level [R]
+// and peak, the partials table of the peak pass (plan.peak_dwords() dwords: scratch, nothing in it outlives a call)
 struct OutputTables {
     PackReq* req;
     long* cum;
     JoinRow* join;
     MarkRow* mark;
+    LevelSpec* level;
+    uint32_t* peak;
 };
 // Everything between "the plan is built" and "copy to the host", for the model and for the test hook: the resampler when
 // plan.y_floats > 0 (d_y: that many floats, null when 0), the packer into d_packed (16-byte aligned, plan.total_bytes long), and
 // when plan.n_marks > 0 the token marks at d_packed + plan.marks_off.  audio [B][audio_ld]; dur [B][512] as duration_kernel
-// wrote it and lens [B], both on the device.  The joined form of the kernels runs only when plan.joined.
+// wrote it and lens [B], both on the device.  The joined form of the kernels runs only when plan.joined.  A measured plan: the peak
+// pass and the gain kernel between resampler and packer, {p, g} of every request at d_packed + plan.levels_off (8-aligned; d_packed
+// is then plan.end_bytes() long), and the levelled packer when plan.levelled.
 void launch_output_plan(const float* audio, long audio_ld, const int* dur, const int* lens, const OutputPlan& plan,
                         const OutputTables& t, float* d_y, void* d_packed, hipStream_t s);
 // its two halves: the bodies, and the marks (n_marks > 0) into a block of their own, 8-byte aligned

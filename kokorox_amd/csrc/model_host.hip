@@ -116,28 +116,33 @@ void Model::infer_host(const int64_t* ids, int64_t t_stride, const int32_t* lens
 // points run the call once more, now on the streaming recurrence (same bits), and the caller sees a result, not an error.
 void Model::infer_host_ex(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
                           int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out,
-                          int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks) {
+                          int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, double* out_levels) {
     try {
-        infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks);
+        infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks,
+                        out_levels);
     } catch (const LstmTimeout&) {
         n_rerun_ += 1;
-        infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks);
+        infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks,
+                        out_levels);
     }
     note_clean_forward();
 }
 
 void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
                             int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out,
-                            int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks) {
+                            int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
+                            double* out_levels) {
     check_host_call(ids, t_stride, lens, B, speeds, hc, out, out_bytes, out_samples, n_vocab_, n_voices_, d_voices_ != nullptr);
     if (hc.join_call) check_join_call(hc);
     if (hc.req_marks) check_marks_call(hc, out_marks, out_n_marks);
+    if (hc.level_call) check_level_call(hc);
     const bool by_voice = hc.by_voice();
     // one way to lay the output out and pack it: a call without chunks_per_request is R = B single-row requests in hc.format
     const RequestLayout layout = hc.layout(B);
     const int R = layout.R;
     const bool joins = layout.joins != nullptr;
     const bool marks = layout.marks != nullptr;  // (with chunks_per_request then: check_marks_call)
+    const bool levels = layout.levels != nullptr;
     KX_HIP(hipSetDevice(device));
     // I/O staging lives in its own arena: ids, styles, frames, noise keys, voice picks, audio, packed audio
     int64_t* d_ids;
@@ -146,6 +151,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     uint64_t* d_seeds;
     uint32_t* d_uidx;
     OutputTables tables{};
+    size_t peak_cap = 0;   // dwords of tables.peak
     float* d_y = nullptr;  // the resampled streams of the requests with a rate code, back to back
     int *d_vid, *d_rows, *d_kinds;
     float* d_w;
@@ -165,7 +171,12 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         tables.cum = static_cast<long*>(A.alloc(((size_t)B + 1) * 8));
         const OutputBounds bound = output_bounds(layout, B, audio_floats, lens);
         d_y = A.f(bound.y_floats);  // (0 floats when no word carries a rate code)
-        if (joins) tables.join = static_cast<JoinRow*>(A.alloc((size_t)B * sizeof(JoinRow)));
+        if (joins || levels) tables.join = static_cast<JoinRow*>(A.alloc((size_t)B * sizeof(JoinRow)));
+        if (levels) {  // (the partials of the peak pass are sized here, before the forward: nothing new on a warm model)
+            tables.level = static_cast<LevelSpec*>(A.alloc((size_t)R * sizeof(LevelSpec)));
+            tables.peak = static_cast<uint32_t*>(A.alloc(bound.peak_dwords * sizeof(uint32_t)));
+            peak_cap = bound.peak_dwords;
+        }
         if (marks) tables.mark = static_cast<MarkRow*>(A.alloc((size_t)B * sizeof(MarkRow)));
         d_packed = A.alloc(bound.packed_bytes);  // compact output: the requests back to back, then the marks
         return A.f(audio_floats);
@@ -212,7 +223,9 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         // frame counts are known (the forward's one host sync): the plan of the output stage, then ONE launch packs every
         // request of the batch back to back on the GPU, whatever its form (one before it, the resampler, when a request asks
         // for another rate; one behind it, the token marks, when a request wants them), then ONE asynchronous copy of bodies
-        // and marks into a page-locked host buffer.  (All-zero join specs: the plain kernels, the plain bytes.)
+        // and marks into a page-locked host buffer.  (All-zero join specs: the plain kernels, the plain bytes.)  A call with
+        // levels: the peak pass and the gain kernel sit between resampler and packer, and {p, g} of every request come back
+        // behind the marks in the same copy.
         OutputPlan& plan = output_plan_;
         build_output_plan(call_.hF.data(), lens, joins ? h_edge_.data() : nullptr, B, layout, plan);
         for (int r = 0; r < R; ++r) {
@@ -220,9 +233,10 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             out_bytes[r] = plan.req[(size_t)r].out_bytes;
             if (marks) out_n_marks[r] = plan.count[(size_t)r];
         }
+        KX_REQUIRE((size_t)plan.peak_dwords() <= peak_cap, "levels: the peak table is too small");
         launch_output_plan(d_audio, ld, call_.d_dur, call_.dT, plan, tables, d_y, d_packed, stream_);
         const int64_t marks_off = plan.marks_off, n_marks = plan.n_marks;
-        const int64_t total = n_marks > 0 ? plan.end_bytes() : plan.total_bytes;
+        const int64_t total = n_marks > 0 || plan.measured ? plan.end_bytes() : plan.total_bytes;
         char* host = static_cast<char*>(host_out_alloc((size_t)(total > 0 ? total : 1)));
         hipError_t e = hipMemcpyAsync(host, d_packed, (size_t)total, hipMemcpyDeviceToHost, stream_);
         if (e == hipSuccess) e = hipStreamSynchronize(stream_);
@@ -240,6 +254,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         }
         *out = host;
         if (marks) *out_marks = n_marks > 0 ? reinterpret_cast<int64_t*>(host + marks_off) : nullptr;
+        if (plan.measured && out_levels) memcpy(out_levels, host + plan.levels_off, (size_t)R * 16);
         return;
     }
 }

@@ -1,6 +1,6 @@
 // The output stage of a call (gfx950): every request of the batch packed as the bytes a server sends -- the packer and its
-// forms (samples, WAV, base64, G.711), the output-rate resampler before it, the token timing marks behind the bodies and the
-// edge durations the host's join plan needs.  host_request.h has the tables these kernels read and the planner that fills
+// forms (samples, WAV, base64, G.711), the output-rate resampler before it, the levels between the two (a request's peak, its
+// gain, the levelled packer), the token timing marks behind the bodies and the edge durations the host's join plan needs.  host_request.h has the tables these kernels read and the planner that fills
 // them (build_output_plan); launch_output_plan below is the one way they are launched, for the model and for the test hook.
 #include "kx_common.h"
 #include "resample_taps.h"
@@ -123,11 +123,13 @@ __device__ __forceinline__ void stage_stream(float* __restrict__ dst, const floa
     }
 }
 
-template <bool JOINED>
+// LEVELLED (include/kokorox_hip.h, "levels"): the staged sample z becomes f32(g * f64(z)) with the request's g from the levels
+// block, which request_gain_kernel wrote before this launch; everything behind the barrier sees z' where it saw z.
+template <bool JOINED, bool LEVELLED = false>
 __device__ __forceinline__ void pack_requests_body(const float* __restrict__ audio, long audio_ld,
                                                    const PackReq* __restrict__ reqs, const long* __restrict__ cum,
                                                    const JoinRow* __restrict__ jrows, const float* __restrict__ y,
-                                                   char* __restrict__ out) {
+                                                   char* __restrict__ out, const double* __restrict__ levels = nullptr) {
     __shared__ float smp[PACK_LDS];
     const PackReq rq = reqs[blockIdx.y];
     const long mis = rq.out_off & 15;  // the region starts `mis` bytes into its first 16-byte unit
@@ -155,9 +157,18 @@ __device__ __forceinline__ void pack_requests_body(const float* __restrict__ aud
     s_hi = s_hi > S ? S : s_hi;
     if (rq.rate) {  // (uniform) a resampled request: one contiguous run
         const float* __restrict__ src = y + rq.y_off;
-        for (long i = s_lo + threadIdx.x; i < s_hi; i += PACK_THREADS) smp[i - s_lo] = src[i];
+        if (LEVELLED) {
+            const double g = levels[2 * blockIdx.y + 1];
+            for (long i = s_lo + threadIdx.x; i < s_hi; i += PACK_THREADS) smp[i - s_lo] = (float)(g * (double)src[i]);
+        } else {
+            for (long i = s_lo + threadIdx.x; i < s_hi; i += PACK_THREADS) smp[i - s_lo] = src[i];
+        }
     } else {
         stage_stream<JOINED, PACK_THREADS>(smp, audio, audio_ld, cum, jrows, rq.first_row, rq.n_rows, s_lo, s_hi);
+        if (LEVELLED) {  // (every lane scales the samples it staged itself: sample i belongs to lane (i - s_lo) mod PACK_THREADS)
+            const double g = levels[2 * blockIdx.y + 1];
+            for (long i = s_lo + threadIdx.x; i < s_hi; i += PACK_THREADS) smp[i - s_lo] = (float)(g * (double)smp[i - s_lo]);
+        }
     }
     __syncthreads();
     const long u_lo = blk_lo + (long)threadIdx.x * 16;  // the lane's unit, as a byte offset in the region (may start before it)
@@ -218,7 +229,7 @@ __device__ __forceinline__ void pack_requests_body(const float* __restrict__ aud
         }
     }
 }
-// (two kernels, not one with a flag: the plain form keeps its name, its arguments and its registers)
+// (three kernels, not one with flags: the plain and the joined form keep their names, their arguments and their registers)
 __global__ __launch_bounds__(PACK_THREADS) void pack_requests_kernel(const float* __restrict__ audio, long audio_ld,
                                                                      const PackReq* __restrict__ reqs,
                                                                      const long* __restrict__ cum,
@@ -231,6 +242,97 @@ __global__ __launch_bounds__(PACK_THREADS) void pack_requests_joined_kernel(cons
                                                                             const JoinRow* __restrict__ jrows,
                                                                             const float* __restrict__ y, char* __restrict__ out) {
     pack_requests_body<true>(audio, audio_ld, reqs, cum, jrows, y, out);
+}
+// (always the joined staging: the plan fills a JoinRow for every row, {0, 600 frames[b], 0, 0, 0} where nothing shapes it)
+__global__ __launch_bounds__(PACK_THREADS) void pack_requests_levelled_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                              const PackReq* __restrict__ reqs,
+                                                                              const long* __restrict__ cum,
+                                                                              const JoinRow* __restrict__ jrows,
+                                                                              const float* __restrict__ y, char* __restrict__ out,
+                                                                              const double* __restrict__ levels) {
+    pack_requests_body<true, true>(audio, audio_ld, reqs, cum, jrows, y, out, levels);
+}
+
+// ---- levels: a request's peak, its gain, and the product in the packer's staging step (include/kokorox_hip.h, "levels") ------
+// The stream z of request r is what the packer stages: the run at y + y_off with a rate code, the rows through stage_stream
+// (joined or plain as the plan says) at 24 000 Hz.  p = the largest |z[n]| over the samples that are no NaN, +inf included, 0 when
+// there is none.  For non-NaN floats the unsigned order of bits(|v|) is the order of |v|, so the maximum is taken on dwords: it
+// does not depend on the order, and 0 is both the empty maximum and +0.
+//
+// request_peak_kernel: a workgroup reduces one window of LEVEL_WINDOW samples -- every lane over its samples, the wave with
+// __shfl_xor, the four waves through LDS with one barrier -- and stores ONE dword into the partials table [R][windows].  No atomic,
+// nothing to zero between calls: request_gain_kernel reads exactly the ceil(N_r / LEVEL_WINDOW) entries this launch wrote.
+constexpr int PEAK_THREADS = 256;
+__device__ __forceinline__ uint32_t peak_take(uint32_t m, float v) {
+    const uint32_t b = __float_as_uint(v) & 0x7FFFFFFFu;
+    return b <= 0x7F800000u && b > m ? b : m;  // (a NaN is above +inf in this order: skipped)
+}
+__global__ __launch_bounds__(PEAK_THREADS) void request_peak_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                     const PackReq* __restrict__ reqs, const long* __restrict__ cum,
+                                                                     const JoinRow* __restrict__ jrows, const float* __restrict__ y,
+                                                                     uint32_t* __restrict__ partials, long windows) {
+    __shared__ float xs[LEVEL_WINDOW];
+    __shared__ uint32_t wave_max[PEAK_THREADS / 64];
+    const PackReq rq = reqs[blockIdx.y];
+    const long n0 = (long)blockIdx.x * LEVEL_WINDOW;
+    if (n0 >= rq.n_samples) return;  // (uniform: the grid covers the longest request)
+    const long n1 = n0 + LEVEL_WINDOW < rq.n_samples ? n0 + LEVEL_WINDOW : rq.n_samples;
+    uint32_t m = 0;
+    if (rq.rate) {  // (uniform) one contiguous run: 16-byte loads where the window starts on a 16-byte address
+        const float* __restrict__ src = y + rq.y_off;
+        long tail = n0;
+        if ((reinterpret_cast<uintptr_t>(src + n0) & 15) == 0) {
+            tail = n0 + ((n1 - n0) & ~3L);
+            for (long i = n0 + 4 * (long)threadIdx.x; i < tail; i += 4 * PEAK_THREADS) {
+                const float4 v = *reinterpret_cast<const float4*>(src + i);
+                m = peak_take(peak_take(peak_take(peak_take(m, v.x), v.y), v.z), v.w);
+            }
+        }
+        for (long i = tail + threadIdx.x; i < n1; i += PEAK_THREADS) m = peak_take(m, src[i]);
+    } else {  // the rows, cut and faded as the packer will see them; every lane reads back the samples it staged itself
+        if (jrows) stage_stream<true, PEAK_THREADS>(xs, audio, audio_ld, cum, jrows, rq.first_row, rq.n_rows, n0, n1);
+        else stage_stream<false, PEAK_THREADS>(xs, audio, audio_ld, cum, jrows, rq.first_row, rq.n_rows, n0, n1);
+        for (long i = n0 + threadIdx.x; i < n1; i += PEAK_THREADS) m = peak_take(m, xs[i - n0]);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const uint32_t v = (uint32_t)__shfl_xor((int)m, o);
+        m = v > m ? v : m;
+    }
+    if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < PEAK_THREADS / 64; ++w) m = wave_max[w] > m ? wave_max[w] : m;
+        partials[(long)blockIdx.y * windows + blockIdx.x] = m;
+    }
+}
+// request_gain_kernel: one wave per request reduces its partials (the windows past its end were never written and are not read),
+// computes g in float64 as the header defines it and stores {f64(p), g} into the levels block of the packed buffer.
+__global__ __launch_bounds__(64) void request_gain_kernel(const PackReq* __restrict__ reqs, const LevelSpec* __restrict__ specs,
+                                                          const uint32_t* __restrict__ partials, long windows,
+                                                          double* __restrict__ levels) {
+    const int r = blockIdx.x;
+    const long n = (reqs[r].n_samples + LEVEL_WINDOW - 1) / LEVEL_WINDOW;
+    uint32_t m = 0;
+    for (long w = threadIdx.x; w < n; w += 64) {
+        const uint32_t v = partials[(long)r * windows + w];
+        m = v > m ? v : m;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const uint32_t v = (uint32_t)__shfl_xor((int)m, o);
+        m = v > m ? v : m;
+    }
+    if (threadIdx.x != 0) return;
+    const LevelSpec ls = specs[r];
+    const double p = (double)__uint_as_float(m), peak = (double)ls.peak;
+    const bool usable = m > 0u && m < 0x7F800000u;
+    double g = (double)ls.gain;
+    if (ls.mode == LEVEL_NORMALIZE) g = usable ? peak / p : 1.0;
+    else if (ls.mode == LEVEL_CEILING && usable && g * p > peak) g = peak / p;
+    levels[2 * r] = p;
+    levels[2 * r + 1] = g;
 }
 
 // ---- output sample rates: a request's whole stream through a polyphase FIR, before the packer -----------------------------
@@ -300,17 +402,23 @@ __global__ __launch_bounds__(RS_THREADS) void resample_requests_joined_kernel(co
     resample_requests_body<true>(audio, audio_ld, reqs, cum, jrows, y);
 }
 
-// The bodies of a plan: its request table, prefixes and (a joined plan) join rows copied into `t`, the resampler when some
-// request carries a rate code, then the packer.  d_y: plan.y_floats floats (may be null when that is 0); out: 16-byte aligned,
-// plan.total_bytes long.  The joined form of the two kernels runs only when the plan says so (OutputPlan::joined).
+// The bodies of a plan: its request table, prefixes and (a joined or levelled plan) join rows copied into `t`, the resampler when
+// some request carries a rate code, then the packer.  d_y: plan.y_floats floats (may be null when that is 0); out: 16-byte aligned,
+// plan.total_bytes long.  The joined form of the two kernels runs only when the plan says so (OutputPlan::joined).  A measured
+// plan (OutputPlan::measured): between the resampler and the packer the peak pass and the gain kernel, which stores every
+// request's {p, g} at out + plan.levels_off; the levelled packer runs only when some spec is not the plain one.
 void launch_pack_plan(const float* audio, long audio_ld, const OutputPlan& plan, const OutputTables& t, float* d_y, void* out,
                       hipStream_t s) {
-    if (plan.max_units <= 0) return;
+    if (plan.max_units <= 0 && !plan.measured) return;
     const size_t R = plan.req.size(), B = plan.join.size();
     KX_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0 && R <= 65535, "pack: unaligned output or too many requests");
     KX_HIP(hipMemcpyAsync(t.req, plan.req.data(), R * sizeof(PackReq), hipMemcpyHostToDevice, s));
     KX_HIP(hipMemcpyAsync(t.cum, plan.cum.data(), (B + 1) * sizeof(long), hipMemcpyHostToDevice, s));
-    if (plan.joined) KX_HIP(hipMemcpyAsync(t.join, plan.join.data(), B * sizeof(JoinRow), hipMemcpyHostToDevice, s));
+    if (plan.joined || plan.levelled) KX_HIP(hipMemcpyAsync(t.join, plan.join.data(), B * sizeof(JoinRow), hipMemcpyHostToDevice, s));
+    if (plan.measured) {
+        KX_REQUIRE(t.level && t.peak && plan.level.size() == R && (plan.levels_off & 7) == 0, "levels: bad launch argument");
+        KX_HIP(hipMemcpyAsync(t.level, plan.level.data(), R * sizeof(LevelSpec), hipMemcpyHostToDevice, s));
+    }
     if (plan.y_floats > 0) {
         KX_REQUIRE(d_y != nullptr, "pack: no buffer for the resampled streams");
         const dim3 grid((unsigned)((plan.max_resampled + RS_WINDOW - 1) / RS_WINDOW), (unsigned)R);
@@ -320,8 +428,22 @@ void launch_pack_plan(const float* audio, long audio_ld, const OutputPlan& plan,
             hipLaunchKernelGGL(resample_requests_kernel, grid, dim3(RS_THREADS), 0, s, audio, audio_ld, t.req, t.cum, d_y);
         KX_HIP(hipGetLastError());
     }
+    double* levels = plan.measured ? reinterpret_cast<double*>(static_cast<char*>(out) + plan.levels_off) : nullptr;
+    if (plan.measured) {
+        if (plan.peak_windows > 0) {
+            hipLaunchKernelGGL(request_peak_kernel, dim3((unsigned)plan.peak_windows, (unsigned)R), dim3(PEAK_THREADS), 0, s, audio, audio_ld,
+                               t.req, t.cum, plan.joined ? t.join : nullptr, d_y, t.peak, plan.peak_windows);
+            KX_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(request_gain_kernel, dim3((unsigned)R), dim3(64), 0, s, t.req, t.level, t.peak, plan.peak_windows, levels);
+        KX_HIP(hipGetLastError());
+    }
+    if (plan.max_units <= 0) return;  // (a measured plan of empty requests: its levels are written, there is no body)
     const dim3 grid((unsigned)((plan.max_units + PACK_THREADS - 1) / PACK_THREADS), (unsigned)R);
-    if (plan.joined)
+    if (plan.levelled)
+        hipLaunchKernelGGL(pack_requests_levelled_kernel, grid, dim3(PACK_THREADS), 0, s, audio, audio_ld, t.req, t.cum, t.join, d_y,
+                           static_cast<char*>(out), levels);
+    else if (plan.joined)
         hipLaunchKernelGGL(pack_requests_joined_kernel, grid, dim3(PACK_THREADS), 0, s, audio, audio_ld, t.req, t.cum, t.join, d_y,
                            static_cast<char*>(out));
     else
@@ -394,7 +516,8 @@ void launch_token_marks(const int* dur, const int* lens, const OutputPlan& plan,
 }
 
 // The output stage of a call whose plan is built, for the model and for the test hook alike: the bodies into d_packed, and the
-// marks of the requests that want them in their block behind the bodies (8-aligned), so one copy to the host brings both.
+// marks of the requests that want them in their block behind the bodies (8-aligned), and behind those the levels of a measured
+// plan, so one copy to the host brings all three.  The order is resampler, peak, gain, packer, marks.
 void launch_output_plan(const float* audio, long audio_ld, const int* dur, const int* lens, const OutputPlan& plan,
                         const OutputTables& t, float* d_y, void* d_packed, hipStream_t s) {
     launch_pack_plan(audio, audio_ld, plan, t, d_y, d_packed, s);

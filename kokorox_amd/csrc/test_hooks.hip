@@ -588,10 +588,21 @@ int kx_test_output_plan(int device_id, const float* audio, int B, int64_t audio_
                         const int32_t* lens, const int32_t* chunks_per_request, int R, const int32_t* formats, const kx_join* joins,
                         const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes, int64_t* out_samples,
                         int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks, char* err, size_t err_len) {
+    return kx_test_output_plan_levelled(device_id, audio, B, audio_ld, frames_in, dur, lens, chunks_per_request, R, formats, joins, want,
+                                        out, out_cap, out_bytes, out_samples, out_marks, marks_cap, out_n_marks, nullptr, nullptr, err,
+                                        err_len);
+}
+
+int kx_test_output_plan_levelled(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames_in,
+                                 const int32_t* dur, const int32_t* lens, const int32_t* chunks_per_request, int R,
+                                 const int32_t* formats, const kx_join* joins, const uint8_t* want, void* out, int64_t out_cap,
+                                 int64_t* out_bytes, int64_t* out_samples, int64_t* out_marks, int64_t marks_cap,
+                                 int64_t* out_n_marks, const kx_level* levels, double* out_levels, char* err, size_t err_len) {
     return guarded_free(err, err_len, [&] {
         check_device(device_id);
         KX_REQUIRE(formats && out_bytes && out_samples && out_n_marks && B > 0 && R > 0 && (frames_in ? !dur : dur && lens) &&
-                       ((!want && !joins) || dur) && (audio ? out != nullptr : out_cap == 0 && dur), "test_output_plan: bad argument");
+                       ((!want && !joins) || dur) && (audio ? out != nullptr : out_cap == 0 && dur) && (levels ? audio && out_levels : !out_levels),
+                   "test_output_plan: bad argument");
         // what the forward would have brought back: the rows' frame counts and the durations of their two edge tokens
         std::vector<int> frames((size_t)B, 0), edges((size_t)2 * B, 0);
         for (int b = 0; b < B; ++b) {
@@ -611,8 +622,11 @@ int kx_test_output_plan(int device_id, const float* audio, int B, int64_t audio_
         static_assert(sizeof(kx_join) == sizeof(kx::JoinSpec), "kx_join is JoinSpec");
         const kx::JoinSpec* specs = reinterpret_cast<const kx::JoinSpec*>(joins);
         for (int r = 0; joins && r < R; ++r) KX_REQUIRE(kx::join_spec_ok(specs[r]), "infer: bad join");
+        static_assert(sizeof(kx_level) == sizeof(kx::LevelSpec), "kx_level is LevelSpec");
+        const kx::LevelSpec* lspecs = reinterpret_cast<const kx::LevelSpec*>(levels);
+        for (int r = 0; levels && r < R; ++r) KX_REQUIRE(kx::level_spec_ok(lspecs[r]), "infer: bad level");
         // the planner and the launcher of Model::infer_host_once
-        const kx::RequestLayout layout{chunks_per_request, R, formats, R, want, specs, R};
+        const kx::RequestLayout layout{chunks_per_request, R, formats, R, want, specs, R, lspecs, levels ? R : 0};
         kx::OutputPlan plan;
         kx::build_output_plan(frames.data(), lens, joins ? edges.data() : nullptr, B, layout, plan);
         for (int r = 0; r < R; ++r) {
@@ -625,18 +639,28 @@ int kx_test_output_plan(int device_id, const float* audio, int B, int64_t audio_
         if (!audio && plan.n_marks == 0) return;
         KX_HIP(hipSetDevice(device_id));
         DevMem dm;
+        // the partials of the peak pass: poisoned with a large finite value (an entry the launch did not write must not be read),
+        // 64 bytes of sentinel behind them
+        const size_t n_peak = (size_t)plan.peak_dwords();
+        uint32_t* d_peak = levels ? dm.get<uint32_t>(n_peak + 16) : nullptr;
+        if (d_peak) {
+            KX_HIP(hipMemset(d_peak, 0x7F, n_peak * 4));
+            KX_HIP(hipMemset(d_peak + n_peak, 0xA5, 64));
+        }
         const kx::OutputTables tables{dm.get<kx::PackReq>((size_t)R), dm.get<long>((size_t)B + 1), dm.get<kx::JoinRow>((size_t)B),
-                                      dm.get<kx::MarkRow>((size_t)B)};
+                                      dm.get<kx::MarkRow>((size_t)B), levels ? dm.get<kx::LevelSpec>((size_t)R) : nullptr, d_peak};
         const int* d_dur = dur ? dm.up(dur, (size_t)B * 512) : nullptr;
         const int* d_len = dur ? dm.up(lens, (size_t)B) : nullptr;
-        // sentinels: 64 bytes after the last region, after the resampled streams and after the last mark, which the kernels
-        // must leave alone.  The marks block is moved 64 bytes back for the first of them (the kernel is handed its address,
-        // still 8-aligned; the offset itself is nothing it sees).
-        const long body = audio ? plan.total_bytes : 0, n_mk = plan.n_marks * 8;
+        // sentinels: 64 bytes after the last region, after the resampled streams, after the last mark and after the levels, which
+        // the kernels must leave alone.  The marks block is moved 64 bytes back for the first of them, the levels block 64 more
+        // for the third (the kernels are handed the addresses, still 8-aligned; the offsets themselves are nothing they see).
+        const long body = audio ? plan.total_bytes : 0, n_mk = plan.n_marks * 8, n_lv = plan.measured ? 16L * R : 0;
         if (audio) plan.marks_off += 64;
-        const long mk_off = audio ? plan.marks_off : 0;
-        char* d_out = dm.get<char>((size_t)(mk_off + n_mk + 64));
-        KX_HIP(hipMemset(d_out, 0xA5, (size_t)(mk_off + n_mk + 64)));
+        if (plan.measured) plan.levels_off += 128;
+        const long mk_off = audio ? plan.marks_off : 0, lv_off = plan.measured ? plan.levels_off : mk_off + n_mk;
+        const long d_out_bytes = plan.measured ? lv_off + n_lv + 64 : mk_off + n_mk + 64;
+        char* d_out = dm.get<char>((size_t)d_out_bytes);
+        KX_HIP(hipMemset(d_out, 0xA5, (size_t)d_out_bytes));
         float* d_y = audio && plan.y_floats > 0 ? dm.get<float>((size_t)plan.y_floats + 16) : nullptr;
         if (d_y) KX_HIP(hipMemset(d_y + plan.y_floats, 0xA5, 64));
         if (audio) {
@@ -655,6 +679,12 @@ int kx_test_output_plan(int device_id, const float* audio, int B, int64_t audio_
             KX_HIP(hipMemcpy(out, d_out, (size_t)body, hipMemcpyDeviceToHost));
             untouched(d_out + body, "test_output_plan: the kernel wrote past the last region");
             if (d_y) untouched(d_y + plan.y_floats, "test_output_plan: the resampler wrote past the last stream");
+        }
+        if (plan.measured) {
+            KX_HIP(hipMemcpy(out_levels, d_out + lv_off, (size_t)n_lv, hipMemcpyDeviceToHost));
+            untouched(d_out + lv_off - 64, "test_output_plan: a kernel wrote in front of the levels");
+            untouched(d_out + lv_off + n_lv, "test_output_plan: the kernel wrote past the last level");
+            untouched(d_peak + n_peak, "test_output_plan: the peak pass wrote past its table");
         }
         if (plan.n_marks == 0) return;
         KX_HIP(hipMemcpy(out_marks, d_out + mk_off, (size_t)n_mk, hipMemcpyDeviceToHost));

@@ -31,6 +31,10 @@ RESAMPLE_MAX_TAPS = 145
 JOIN_TRIM_HEAD, JOIN_TRIM_TAIL, JOIN_TRIM_INNER = 1, 2, 4
 JOIN_DTYPE = np.dtype([("flags", "<u4"), ("keep_ms", "<i4"), ("pause_ms", "<i4"), ("fade_ms", "<i4")])
 JOIN_NONE = (0, 0, 0, 0)
+# levels (include/kokorox_hip.h, "levels"): a spec is (mode, gain, peak), the layout of kx_level
+LEVEL_GAIN, LEVEL_NORMALIZE, LEVEL_CEILING = 0, 1, 2
+LEVEL_DTYPE = np.dtype([("mode", "<u4"), ("gain", "<f4"), ("peak", "<f4")])
+LEVEL_PLAIN = (LEVEL_GAIN, 1.0, 0.0)
 KX_OK, KX_ERR_INVALID, KX_ERR_IO, KX_ERR_DEVICE, KX_ERR_STATE = 0, 1, 2, 3, 4  # include/kokorox_hip.h
 KX_FLAG_NOISE_OFF = 1
 KX_FLAG_TAPS = 2
@@ -129,6 +133,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                            vp, vp, vp, i32]),
         "kx_dispatcher_submit_request_joined": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
                                                       C.POINTER(i64), vp, vp, vp, cp, sz]),
+        "kx_infer_requests_levelled": (i32, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, u64, u32, vp, i32, C.POINTER(vp), vp, vp,
+                                             vp, vp, vp, i32, vp, i32, vp]),
+        "kx_dispatcher_submit_request_levelled": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
+                                                        C.POINTER(i64), vp, vp, vp, vp, vp, cp, sz]),
         "kx_dispatcher_create": (vp, [vp, i32, i32, i32, cp, sz]),
         "kx_dispatcher_create_warm": (vp, [vp, i32, i32, i32, i32, i32, cp, sz]),
         "kx_dispatcher_submit": (i32, [vp, vp, i32, vp, f32, u64, C.POINTER(C.POINTER(f32)), C.POINTER(i64), cp, sz]),
@@ -185,6 +193,8 @@ def load_test_library() -> C.CDLL:
         "kx_test_layernorm": (i32, [i32, vp, i32, i32, i32, vp, f32, i32, vp, vp, f32, vp, cp, sz]),
         "kx_test_instance_norm": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, cp, sz]),
         "kx_test_output_plan": (i32, [i32, vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, cp, sz]),
+        "kx_test_output_plan_levelled": (i32, [i32, vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp,
+                                               cp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -196,7 +206,7 @@ def load_test_library() -> C.CDLL:
 
 TEST_ABI_SYMBOLS = ["kx_test_conv1d", "kx_test_lstm", "kx_test_source", "kx_test_attention", "kx_test_conv1d_epilogue", "kx_test_conv1d_full",
                     "kx_test_conv_transpose", "kx_test_lstm_fault", "kx_test_lstm_parts", "kx_test_conv_plan", "kx_test_conv1d_opts",
-                    "kx_test_layernorm", "kx_test_instance_norm", "kx_test_output_plan"]
+                    "kx_test_layernorm", "kx_test_instance_norm", "kx_test_output_plan", "kx_test_output_plan_levelled"]
 
 ABI_SYMBOLS = [
     "kx_version", "kx_init", "kx_create", "kx_import_onnx", "kx_resample_filter", "kx_create_from_device_blob", "kx_create_replicas", "kx_replicas_times", "kx_create_partition", "kx_destroy",
@@ -204,7 +214,7 @@ ABI_SYMBOLS = [
     "kx_free_audio", "kx_infer_device", "kx_sync", "kx_set_pinned_durations", "kx_warmup", "kx_arena_bytes", "kx_call_times", "kx_model_status", "kx_model_info", "kx_dispatcher_health", "kx_set_utterance_base", "kx_set_lanes",
     "kx_set_conv_mode", "kx_get_conv_mode", "kx_set_stft_variant", "kx_get_stft_variant",
     "kx_profile_enable", "kx_profile_read", "kx_profile_detail", "kx_profile_aux", "kx_diag_enable", "kx_diag_count", "kx_diag_get", "kx_set_act_prescale", "kx_set_voice_table", "kx_infer_voices",
-    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
+    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_infer_requests_levelled", "kx_dispatcher_submit_request_levelled", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
     "kx_dispatcher_stats", "kx_dispatcher_failures", "kx_dispatcher_destroy", "kx_debug_tap",
 ]
 
@@ -229,6 +239,21 @@ def join_specs(joins, n=None) -> np.ndarray:
         a = np.array([tuple(int(v) for v in t) for t in j], dtype=JOIN_DTYPE)
     if n is not None and a.shape[0] != n:
         raise ValueError(f"{n} join specs are required")
+    return a
+
+
+def level_specs(levels, n=None) -> np.ndarray:
+    """Level specs as the array of kx_level the library takes: one (mode, gain, peak) tuple, a list of them, or an array of
+    LEVEL_DTYPE already.  n: the count expected (a single tuple is repeated)."""
+    if isinstance(levels, np.ndarray) and levels.dtype == LEVEL_DTYPE:
+        a = np.ascontiguousarray(levels).reshape(-1)
+    else:
+        lv = list(levels)
+        if lv and not isinstance(lv[0], (tuple, list, np.void)):
+            lv = [tuple(lv)] * (n or 1)
+        a = np.array([(int(m), float(g), float(p)) for m, g, p in lv], dtype=LEVEL_DTYPE)
+    if n is not None and a.shape[0] != n:
+        raise ValueError(f"{n} level specs are required")
     return a
 
 
@@ -458,7 +483,22 @@ class HipKoko:
         out = out + (nsamp,) if with_samples else out
         return out if len(out) > 1 else out[0]
 
-    def _infer_requests(self, tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, want_marks, joins=None):
+    def infer_requests_levelled(self, tokens, chunks_per_request, levels, joins=None, styles=None, voice_ids=None, weights=None,
+                                speeds=(1.0,), seed: int = 0, flags: int = 0, fmt=0, marks: bool = False, with_samples: bool = False):
+        """infer_requests with the level of every request set on the GPU (kx_infer_requests_levelled; the definition is in
+        include/kokorox_hip.h, "levels", the numpy form voices.level_gain / voices.level_stream): `levels` = one spec
+        (mode, gain, peak) for all requests, or a list of one per request; `joins` as infer_requests_joined, or None.  Returns
+        (bodies, levels) with levels a float64 array [R, 2] = the peak p and the gain g of every request as the GPU computed
+        them; marks=True: (bodies, marks, levels).  with_samples: out_samples as a last entry.  LEVEL_PLAIN is a peak meter."""
+        lv = level_specs(levels)
+        j = None if joins is None else join_specs(joins)
+        res, mk, nsamp, out_lv = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, marks,
+                                                      j, lv)
+        out = (res, mk, out_lv) if marks else (res, out_lv)
+        return out + (nsamp,) if with_samples else out
+
+    def _infer_requests(self, tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, want_marks, joins=None,
+                        levels=None):
         ids, lens = self._ids_lens(tokens)
         B = len(tokens)
         cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32).reshape(-1)
@@ -480,7 +520,12 @@ class HipKoko:
         marks = None
         if want_marks:
             mk, n_mk = C.c_void_p(), np.zeros(max(R, 1), np.int64)
-        if joins is not None:
+        if levels is not None:
+            out_lv = np.zeros((max(R, 1), 2), np.float64)
+            self._check(self._lib.kx_infer_requests_levelled(*args, C.byref(mk) if want_marks else None, _ptr(n_mk) if want_marks else None,
+                                                             _ptr(joins), 0 if joins is None else joins.shape[0], _ptr(levels),
+                                                             levels.shape[0], _ptr(out_lv)))
+        elif joins is not None:
             self._check(self._lib.kx_infer_requests_joined(*args, C.byref(mk) if want_marks else None, _ptr(n_mk) if want_marks else None,
                                                            _ptr(joins), joins.shape[0]))
         elif want_marks:
@@ -502,6 +547,8 @@ class HipKoko:
             part = raw[o: o + int(nbytes[r])]
             o += int(nbytes[r])
             res.append(_decode_packed(part, int(fm[r if fm.shape[0] > 1 else 0])))
+        if levels is not None:
+            return res, marks, [int(v) for v in nsamp[:R]], out_lv[:R]
         return res, marks, [int(v) for v in nsamp[:R]]
 
     def infer_device(self, d_ids: int, t_stride: int, lens_host: np.ndarray, d_styles: int, speeds_host: np.ndarray,
@@ -716,13 +763,15 @@ class Dispatcher:
         return arr.reshape(-1, 2) if fmt == 1 else arr
 
     def submit_request(self, chunks: Sequence[Sequence[int]], styles=None, voices=None, speed: float = 1.0, seed: int = 0,
-                       fmt: int = 0, marks: bool = False, join=None):
+                       fmt: int = 0, marks: bool = False, join=None, level=None):
         """A request of 1 .. max_batch chunks (kx_dispatcher_submit_request): `chunks` = the 0-wrapped id lists; `styles` = one
         256-float row per chunk, OR `voices` as in submit_ex (one voice spec for the request); `fmt` = a format word (a PACK_*
         form, optionally | PACK_RATE_*).  Returns what HipKoko.infer_requests returns for one request: an array (forms 0..2, 8, 9)
         or the body as bytes (3, 4).  marks=True (kx_dispatcher_submit_request_marks): returns (body, marks), marks = the
         request's token marks as one int64 array (HipKoko.infer_requests_marks).  join = (flags, keep_ms, pause_ms, fade_ms)
-        (kx_dispatcher_submit_request_joined): the request's seams shaped as HipKoko.infer_requests_joined shapes them."""
+        (kx_dispatcher_submit_request_joined): the request's seams shaped as HipKoko.infer_requests_joined shapes them.
+        level = (mode, gain, peak) (kx_dispatcher_submit_request_levelled): the request's level set as
+        HipKoko.infer_requests_levelled sets it; the result then ends with a float64 pair, the request's peak p and gain g."""
         lens = np.array([len(c) for c in chunks], dtype=np.int32)
         a = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.int64).reshape(-1) for c in chunks])
                                  if len(chunks) else np.zeros(0, np.int64))
@@ -745,7 +794,12 @@ class Dispatcher:
         args = (self._d, _ptr(a), _ptr(lens), len(chunks), _ptr(st), _ptr(vid), _ptr(w), n_mix, float(speed), seed, fmt, C.byref(out),
                 C.byref(nb), C.byref(ns))
         mk, n_mk = C.c_void_p(), C.c_int64(0)
-        if join is not None:
+        lv_out = np.zeros(2, np.float64)
+        if level is not None:
+            j = None if join is None else join_specs(join, 1)
+            rc = self._lib.kx_dispatcher_submit_request_levelled(*args, C.byref(mk) if marks else None, C.byref(n_mk) if marks else None,
+                                                                 _ptr(j), _ptr(level_specs(level, 1)), _ptr(lv_out), err, len(err))
+        elif join is not None:
             j = join_specs(join, 1)
             rc = self._lib.kx_dispatcher_submit_request_joined(*args, C.byref(mk) if marks else None, C.byref(n_mk) if marks else None,
                                                                _ptr(j), err, len(err))
@@ -763,7 +817,9 @@ class Dispatcher:
                 m = np.frombuffer(C.string_at(mk, 8 * n_mk.value), dtype=np.int64).copy()
         finally:
             self._lib.kx_free_packed(out)
-        return (_decode_packed(raw, fmt), m) if marks else _decode_packed(raw, fmt)
+        res = (_decode_packed(raw, fmt), m) if marks else (_decode_packed(raw, fmt),)
+        res = res + (lv_out,) if level is not None else res
+        return res if len(res) > 1 else res[0]
 
     def stats(self):
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
@@ -1014,9 +1070,10 @@ def harmonic_source(f0, lin_w, lin_b, seed=0, utt_base=0, noise_off=False, devic
     return out
 
 
-def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, want, pauses, device):
+def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, want, pauses, device, levels=None):
     """kx_test_output_plan, the one hook of the output stage: the model's planner and launcher on host arrays (None where the
-    hook takes a null pointer; include/kokorox_hip_test.h).  Returns (bodies as bytes, out_samples, marks as int64 arrays)."""
+    hook takes a null pointer; include/kokorox_hip_test.h).  Returns (bodies as bytes, out_samples, marks as int64 arrays).
+    levels (an array of LEVEL_DTYPE, [R]): kx_test_output_plan_levelled, and a fourth entry, the levels as float64 [R, 2]."""
     lib = load_test_library()
     B = len(frames if dur is None else lens)
     fm = np.ascontiguousarray(formats, dtype=np.int32)
@@ -1041,13 +1098,21 @@ def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, w
     out = np.zeros(max(cap, 1), dtype=np.uint8)
     mk = np.zeros(max(mcap, 1), dtype=np.int64)
     nb, ns, nm = np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int64)
-    _err_call(lib.kx_test_output_plan, device, _ptr(audio), B, ld, _ptr(fr), _ptr(dur), _ptr(ln), _ptr(cpr), R, _ptr(fm), _ptr(joins),
-              _ptr(wt), _ptr(out) if audio is not None else None, cap, _ptr(nb), _ptr(ns), _ptr(mk), mcap, _ptr(nm))
+    args = (device, _ptr(audio), B, ld, _ptr(fr), _ptr(dur), _ptr(ln), _ptr(cpr), R, _ptr(fm), _ptr(joins), _ptr(wt),
+            _ptr(out) if audio is not None else None, cap, _ptr(nb), _ptr(ns), _ptr(mk), mcap, _ptr(nm))
+    if levels is None:
+        _err_call(lib.kx_test_output_plan, *args)
+    else:
+        assert levels.dtype == LEVEL_DTYPE and levels.shape == (R,)
+        out_lv = np.zeros((R, 2), dtype=np.float64)
+        _err_call(lib.kx_test_output_plan_levelled, *args, _ptr(levels), _ptr(out_lv))
     raw, res, o = out.tobytes(), [], 0
     for r in range(R):
         res.append(raw[o: o + int(nb[r])] if audio is not None else b"")
         o += int(nb[r])
     marks = [m.copy() for m in np.split(mk[: int(nm.sum())], np.cumsum(nm)[:-1])]
+    if levels is not None:
+        return res, [int(v) for v in ns], marks, out_lv
     return res, [int(v) for v in ns], marks
 
 
@@ -1080,3 +1145,15 @@ def join_requests(audio, dur, lens, chunks_per_request, formats, joins, want=Non
     j = join_specs(joins, R)
     pauses = sum(24 * int(j["pause_ms"][r]) * (int(chunks_per_request[r]) - 1) for r in range(R))
     return _output_plan(audio, None, dur, lens, chunks_per_request, formats, j, want, pauses, device)
+
+
+def level_requests(audio, dur, lens, chunks_per_request, formats, levels, joins=None, want=None, frames=None, device=0):
+    """Levelled requests alone (kx_test_output_plan_levelled): audio, dur, lens, chunks_per_request, formats, joins and want as
+    join_requests takes them (joins = None: the rows appended as they are; dur = lens = None with frames [B]: the frame counts
+    given, then neither joins nor marks), levels = one (mode, gain, peak) spec per request.  Returns (bodies as bytes,
+    out_samples, marks, levels as float64 [R, 2] = p and g of every request): voices.levelled_body and voices.level_gain."""
+    R = len(lens if dur is not None else frames) if chunks_per_request is None else len(chunks_per_request)
+    lv = level_specs(levels, R)
+    j = None if joins is None else join_specs(joins, R)
+    pauses = 0 if j is None else sum(24 * int(j["pause_ms"][r]) * (int(chunks_per_request[r]) - 1) for r in range(R))
+    return _output_plan(audio, frames, dur, lens, chunks_per_request, formats, j, want, pauses, device, lv)

@@ -296,6 +296,59 @@ def joined_body(chunks_samples, durations_per_chunk: Sequence[Sequence[int]], wo
     return stream_body(resample_stream(join_stream(chunks_samples, durations_per_chunk, join), word), word)
 
 
+LEVEL_GAIN, LEVEL_NORMALIZE, LEVEL_CEILING = 0, 1, 2
+LEVEL_PLAIN = (LEVEL_GAIN, 1.0, 0.0)
+
+
+def _level_fields(level):
+    """(mode, gain, peak) of a valid level spec (include/kokorox_hip.h, "levels"), gain and peak as float32; None = the plain
+    spec.  Every comparison is written so that a NaN fails it."""
+    mode, gain, peak = level if level is not None else LEVEL_PLAIN
+    with np.errstate(over="ignore", invalid="ignore"):
+        gain, peak = np.float32(gain), np.float32(peak)
+    ok = isinstance(mode, (int, np.integer)) and not isinstance(mode, bool) and mode in (0, 1, 2) and bool(np.float32(0) <= gain <= np.float32(64))
+    if ok and mode == LEVEL_GAIN:
+        ok = peak.tobytes() == np.float32(0).tobytes()  # +0.0f and nothing else
+    elif ok:
+        ok = (mode != LEVEL_NORMALIZE or gain == np.float32(1)) and bool(np.float32(2.0 ** -15) <= peak <= np.float32(1))
+    if not ok:
+        raise ValueError("level: mode 0..2, gain 0..64 (1 in mode 1), peak +0 in mode 0 and 2^-15..1 in modes 1 and 2")
+    return int(mode), gain, peak
+
+
+def level_gain(z, level):
+    """(p, g) of ONE request's stream z, which is at its output rate already, by the definition of include/kokorox_hip.h,
+    "levels": p = the largest |z[n]| over the samples that are no NaN as a float32 (+inf counts; 0 when there is none), g the
+    float64 gain of `level` = (mode, gain, peak): gain itself (mode 0), peak / p (mode 1, when 0 < p < inf, else 1), or gain
+    unless gain * p > peak, then peak / p (mode 2, when 0 < p < inf) -- one float64 division, one float64 product."""
+    mode, gain, peak = _level_fields(level)
+    z = np.ascontiguousarray(z, dtype=np.float32).reshape(-1)
+    a = np.abs(z[~np.isnan(z)])
+    p = np.float32(a.max()) if a.shape[0] else np.float32(0)
+    usable = bool(np.float32(0) < p < np.float32(np.inf))
+    g = np.float64(gain)
+    if mode == LEVEL_NORMALIZE:
+        g = np.float64(peak) / np.float64(p) if usable else np.float64(1.0)
+    elif mode == LEVEL_CEILING and usable and g * np.float64(p) > np.float64(peak):
+        g = np.float64(peak) / np.float64(p)
+    return p, float(g)
+
+
+def level_stream(z, level) -> np.ndarray:
+    """The levelled stream z'[n] = f32(g * f64(z[n])) with g of level_gain: one float64 product and one round-to-nearest-even
+    conversion per sample; a NaN stays a NaN."""
+    z = np.ascontiguousarray(z, dtype=np.float32).reshape(-1)
+    _, g = level_gain(z, level)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        return (np.float64(g) * z.astype(np.float64)).astype(np.float32)
+
+
+def levelled_body(chunks_samples, durations_per_chunk: Sequence[Sequence[int]], word: int, join, level) -> bytes:
+    """The body of ONE levelled request in the format word `word`, as bytes: join_stream (join = None: the chunks appended),
+    resample_stream, level_stream, then the form."""
+    return stream_body(level_stream(resample_stream(join_stream(chunks_samples, durations_per_chunk, join), word), level), word)
+
+
 def stream_body(y, word: int) -> bytes:
     """The form of a format word applied to a request's stream `y`, which is at the word's rate already, as bytes."""
     y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1)
@@ -349,12 +402,13 @@ def word_spans(spans, words: Sequence[Sequence[int]]):
 
 
 def tts_request(model, styles: Dict[str, np.ndarray], style_name: str, chunk_tokens: Sequence[Sequence[int]],
-                speed: float = 1.0, initial_silence: int = 0, seed: int = 0, fmt: int = 0, join=None):
+                speed: float = 1.0, initial_silence: int = 0, seed: int = 0, fmt: int = 0, join=None, level=None):
     """`tts_chunks` through `model.infer_requests`: the chunks of one text as ONE request of one batched forward, its body
     (header of the form, then the chunks' samples with nothing between them) packed on the GPU.  `fmt` is a format word of
     hip_koko (a PACK_* form, optionally | PACK_RATE_*): 0..2 and 8 / 9 give the samples as an array, 3 (`wav_f32_body`) and 4
     (`wav16_base64`) the bytes a server sends.  `join` = (flags, keep_ms, pause_ms, fade_ms): the seams shaped on the GPU
-    (`model.infer_requests_joined`; trim the pads' silence, pause between sentences, fade the cut edges).  An
+    (`model.infer_requests_joined`; trim the pads' silence, pause between sentences, fade the cut edges).  `level` = (mode, gain,
+    peak): the level set on the GPU (`model.infer_requests_levelled`; a volume, a peak to normalise to, or a ceiling).  An
     empty chunk list and an empty chunk are errors (a request has at least one chunk)."""
     toks, rows = [], []
     for ch in chunk_tokens:
@@ -365,6 +419,9 @@ def tts_request(model, styles: Dict[str, np.ndarray], style_name: str, chunk_tok
         toks.append([0] + t + [0])
     if not toks:
         raise ValueError("tts_request: a request has at least one chunk")
+    if level is not None:
+        return model.infer_requests_levelled(toks, [len(toks)], level, joins=join, styles=np.asarray(rows, dtype=np.float32),
+                                             speeds=[float(speed)], seed=seed, fmt=fmt)[0][0]
     if join is not None:
         return model.infer_requests_joined(toks, [len(toks)], join, styles=np.asarray(rows, dtype=np.float32), speeds=[float(speed)],
                                            seed=seed, fmt=fmt)[0]

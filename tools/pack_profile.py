@@ -9,6 +9,8 @@ the command line; an optional second argument is the batch (1 = one utterance). 
     a word and 'j'       ('2j', '0x108j') kx_infer_requests_joined with marks, the batch as BATCH / 4 requests of 4 chunks, every
                          request with the spec {HEAD | TAIL | INNER, keep 20 ms, pause 150 ms, fade 5 ms}: the joined forms of the
                          three kernels (pack_requests_joined_kernel, resample_requests_joined_kernel, token_marks_joined_kernel);
+    a word and 'l'       ('2l', '0x108l') kx_infer_requests_levelled, every row a request of its own normalised to a peak of 0.5:
+                         request_peak_kernel and request_gain_kernel between resampler and packer, and pack_requests_levelled_kernel;
     a word and 'g'       ('2g') the same grouping without joins (kx_infer_requests_marks): the plain kernels on the same batch.
 Meant to run under the profiler, one mode per run (kernel trace only, no counters in the same run):
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o t -- python tools/pack_profile.py p2
@@ -43,6 +45,10 @@ for it in range(3):
             out, marks = m.infer_requests_marks(toks, [4] * (B // 4), styles=rows, fmt=word)
             assert all(int(k[-1]) == 4 * 422 * 600 * L // M for k in marks)
         assert all(k.shape[0] == 4 * 131 for k in marks)
+    elif which.endswith("l"):
+        word = int(which[:-1], 0)
+        out, lv = m.infer_requests_levelled(toks, [1] * B, (hk.LEVEL_NORMALIZE, 1.0, 0.5), styles=rows, fmt=word)
+        assert lv.shape == (B, 2) and (lv[:, 0] > 0).all() and np.array_equal((lv[:, 0] * lv[:, 1]).astype(np.float32), np.full(B, 0.5, np.float32))
     elif which.endswith("m"):
         word = int(which[:-1], 0)
         out, marks = m.infer_requests_marks(toks, [1] * B, styles=rows, fmt=word)
