@@ -473,6 +473,50 @@ int kx_infer_requests_levelled(kx_model* m, const int64_t* ids, int64_t t_stride
                                int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_level* levels,
                                int n_level, double* out_levels);
 
+/* ---- loudness: ITU-R BS.1770 metering and LUFS normalisation of a request on the GPU -------------------------------------------
+ * Two bodies with the same peak can differ by many LU.  A loudness spec measures the integrated loudness of a request's body
+ * where the body is made, and scales it to a target.
+ *   The stream.  z[0..N) is exactly the stream "levels" defines: what form 0 of the request's format word would hold, after the
+ *   join and after the resampler, at the output rate fs in {24000, 8000, 16000, 48000}.  The peak p keeps its meaning of "levels".
+ *   The input.  x[n] = f64(z[n]) if z[n] is finite, else 0.0: a NaN or an infinity does not poison the recurrence.
+ *   K-weighting.  Two biquads, shelf first, then high-pass, direct form I, float64, zero initial state:
+ *       v[n] = b0 x[n] + b1 x[n-1] + b2 x[n-2] - a1 v[n-1] - a2 v[n-2],   w[n] likewise from v with the high-pass's coefficients.
+ *   With K = tan(pi f0 / fs) -- shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196, Vh = 10^(G/20),
+ *   Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2, b = [(Vh + Vb K/Q + K^2)/a0, 2 (K^2 - Vh)/a0, (Vh - Vb K/Q + K^2)/a0],
+ *   a1 = 2 (K^2 - 1)/a0, a2 = (1 - K/Q + K^2)/a0; high-pass: f0 = 38.13547087602444, Q = 0.5003270373238773, b = [1, -2, 1], a1
+ *   and a2 as for the shelf with this K and Q.  At 48 000 Hz these are the standard's published coefficients.  The four rates'
+ *   coefficients are committed once as float64 bit patterns (kx_loudness_filter hands them out).
+ *   Blocks.  hop = fs / 10 samples.  e[k] = the sum of w[n]^2 over hop k, k < H = floor(N / hop); a trailing partial hop is
+ *   ignored.  Block j covers hops j..j+3: z_j = (e[j] + e[j+1] + e[j+2] + e[j+3]) / (4 hop), j < J = H - 3.
+ *   Gating, in the energy domain.  A block passes the absolute gate when z_j > 10^((-70 + 0.691) / 10); m1 = the mean of z_j over
+ *   those blocks; a block passes the relative gate when it passes the absolute gate and z_j > 0.1 m1; n_g = the number of blocks
+ *   that pass both, m2 their mean.  I = -0.691 + 10 log10(m2) LUFS (mono: channel weight 1).  I is undefined when J < 1 or
+ *   n_g = 0, and then reported as a quiet NaN.
+ *   The gain.  Mode 0 (a meter): g = 1.  Mode 1: g = 10^((f64(target_lufs) - I) / 20) if I is defined, else 1.0; then, if p is
+ *   usable and g * f64(p) > f64(peak), g = f64(peak) / f64(p) -- the ceiling rule of KX_LEVEL_CEILING, so the 16-bit and G.711
+ *   forms cannot clip.
+ *   The samples.  z'[n] = f32(g * f64(z[n])), then the form, as in "levels".  Marks, sizes and headers do not change.
+ *   Valid specs.  Mode 0: target_lufs and peak are +0.0f.  Mode 1: -70 <= target_lufs <= 0 and 2^-15 <= peak <= 1; a NaN fails.
+ *   The GPU's e[k] agree with a sequential float64 evaluation to about 1e-14 relative; I, g and e[k] of a request do not depend on
+ *   what it was batched with. */
+#define KX_LOUDNESS_MEASURE   0u  /* measure only: g = 1                                                        */
+#define KX_LOUDNESS_NORMALIZE 1u  /* scale to `target_lufs`, but never let the largest |sample| exceed `peak`   */
+typedef struct kx_loudness { uint32_t mode; float target_lufs; float peak; } kx_loudness;   /* 12 bytes */
+/* The ten K-weighting coefficients of a format word's rate: shelf b0 b1 b2 a1 a2, then high-pass b0 b1 b2 a1 a2.  Host only;
+ * KX_ERR_INVALID for an unknown word, as kx_resample_filter. */
+int kx_loudness_filter(int format_word, double* out10);
+/* kx_infer_requests_joined with a loudness spec per request: loudness [n_loudness], n_loudness = 1 (shared) or R.  `joins` may
+ * be NULL with n_join == 0 (no joins).  out_loudness may be NULL; when given it receives [R][4] doubles: f64(p), g, I and n_g of
+ * request r as the GPU computed them.  Body, marks, levels and loudness leave the device in one copy.  Refused with
+ * KX_ERR_INVALID before any device work, after everything kx_infer_requests_joined refuses: a null `loudness`
+ * ("infer: null loudness argument"), n_loudness not 1 or R ("infer: bad loudness count"), an invalid spec ("infer: bad loudness"). */
+int kx_infer_requests_loudness(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                               const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                               const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                               const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                               int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join,
+                               const kx_loudness* loudness, int n_loudness, double* out_loudness);
+
 /* ---- request dispatcher ----------------------------------------------------
  * Replaces the reference's one-request-at-a-time `Mutex<Session>` (kokorox/src/onn/ort_koko.rs:78; callers
  * kokorox-openai/src/lib.rs:370-439, kokorox-websocket/src/lib.rs:657-668).  Any number of threads submit
@@ -555,6 +599,16 @@ int kx_dispatcher_submit_request_levelled(kx_dispatcher* d, const int64_t* ids, 
                                           float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
                                           int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
                                           const kx_level* level, double* out_level, char* err, size_t err_len);
+/* kx_dispatcher_submit_request_joined with the request's loudness spec (see "loudness" above); `join` may be NULL here (no
+ * join).  out_loudness may be NULL; when given it receives four doubles, f64(p), g, I and n_g of the request.  A null or invalid
+ * `loudness`: "dispatcher_submit_request: bad loudness"; every other refusal as kx_dispatcher_submit_request_joined.  Loudness,
+ * levelled, joined and plain requests share batches; body, marks and the four values equal those of kx_infer_requests_loudness
+ * (R = 1, same seed, utterance base 0) bit for bit, whatever the request was batched with. */
+int kx_dispatcher_submit_request_loudness(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                          const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
+                                          float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
+                                          int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
+                                          const kx_loudness* loudness, double* out_loudness, char* err, size_t err_len);
 /* n_requests counts requests, max_batch_seen the largest batch in ROWS (a request of n chunks is n rows). */
 int kx_dispatcher_stats(kx_dispatcher* d, int64_t* n_requests, int64_t* n_batches, int64_t* max_batch_seen);
 /* batches each model (worker) has run so far: per_model[n_models] */

@@ -34,6 +34,14 @@ inline ResampleFilter resample_filter(int format_word) {
     return f;
 }
 
+// A request's loudness spec ("loudness" in kokorox_hip.h): {KX_LOUDNESS_MEASURE, 0, 0} measures, {KX_LOUDNESS_NORMALIZE, target_lufs,
+// peak} scales the body to the target under a ceiling; and what comes back: the peak, the gain, the integrated loudness in LUFS
+// (NaN when undefined) and the number of gated blocks.
+using KxLoudness = kx_loudness;
+struct LoudnessResult {
+    double peak, gain, lufs, gated_blocks;
+};
+
 class HipKoko {
   public:
     explicit HipKoko(const std::string& model_path, int device = 0) {
@@ -180,6 +188,49 @@ class HipKoko {
         return bodies;
     }
 
+    // infer_requests with the integrated loudness of every request measured, and set, on the GPU (kx_infer_requests_loudness;
+    // "loudness" in kokorox_hip.h): one spec for every request, no joins, no marks.  loudness[r] = {f64(p), g, I, n_g} of request r.
+    std::vector<std::string> infer_requests_loudness(const std::vector<std::vector<int64_t>>& tokens,
+                                                     const std::vector<int32_t>& chunks_per_request,
+                                                     const std::vector<std::vector<float>>& styles, float speed, uint64_t seed,
+                                                     int format, const KxLoudness& spec, std::vector<LoudnessResult>& loudness) const {
+        if (tokens.empty() || styles.size() != tokens.size()) throw std::invalid_argument("infer_requests: one style row per chunk");
+        const int B = (int)tokens.size(), R = (int)chunks_per_request.size();
+        size_t stride = 1;
+        for (const auto& t : tokens) stride = t.size() > stride ? t.size() : stride;
+        std::vector<int64_t> ids((size_t)B * stride, 0);
+        std::vector<int32_t> tl(B);
+        std::vector<float> st((size_t)B * KX_STYLE_DIM);
+        for (int b = 0; b < B; ++b) {
+            tl[b] = (int32_t)tokens[b].size();
+            for (size_t i = 0; i < tokens[b].size(); ++i) ids[(size_t)b * stride + i] = tokens[b][i];
+            if (styles[b].size() != KX_STYLE_DIM) throw std::invalid_argument("infer_requests: style rows need 256 floats");
+            for (int k = 0; k < KX_STYLE_DIM; ++k) st[(size_t)b * KX_STYLE_DIM + k] = styles[b][k];
+        }
+        void* out = nullptr;
+        std::vector<int64_t> nb(R > 0 ? R : 1), ns(R > 0 ? R : 1);
+        std::vector<double> ld((size_t)4 * (R > 0 ? R : 1));
+        const int32_t fmt = format;
+        const int rc = kx_infer_requests_loudness(h_, ids.data(), (int64_t)stride, tl.data(), B, chunks_per_request.data(), R, st.data(),
+                                                  nullptr, nullptr, 0, &speed, 1, seed, 0, &fmt, 1, &out, nb.data(), ns.data(), nullptr,
+                                                  nullptr, nullptr, 0, &spec, 1, ld.data());
+        if (rc != KX_OK) {
+            char msg[512];
+            kx_last_error_copy(h_, msg, sizeof(msg));
+            throw std::runtime_error(std::string("kokorox_hip error: ") + msg);
+        }
+        std::vector<std::string> bodies;
+        loudness.clear();
+        const char* p = static_cast<const char*>(out);
+        for (int r = 0; r < R; ++r) {
+            bodies.emplace_back(p, p + nb[r]);
+            p += nb[r];
+            loudness.push_back(LoudnessResult{ld[(size_t)4 * r], ld[(size_t)4 * r + 1], ld[(size_t)4 * r + 2], ld[(size_t)4 * r + 3]});
+        }
+        kx_free_packed(out);
+        return bodies;
+    }
+
   private:
     explicit HipKoko(kx_model* adopted) : h_(adopted) {}
     kx_model* h_ = nullptr;
@@ -227,6 +278,30 @@ inline std::string submit_request_marks(kx_dispatcher* d, const std::vector<std:
         throw std::runtime_error(std::string("kokorox_hip error: ") + err);
     std::string body(static_cast<const char*>(out), (size_t)nb);
     marks.assign(mk, mk + nm);  // (inside the allocation of `out`: copied before it is released)
+    kx_free_packed(out);
+    return body;
+}
+
+// ... and with the request's loudness spec (kx_dispatcher_submit_request_loudness; no join, no marks)
+inline std::string submit_request_loudness(kx_dispatcher* d, const std::vector<std::vector<int64_t>>& chunks,
+                                           const std::vector<float>& styles, float speed, uint64_t seed, int format,
+                                           const KxLoudness& spec, LoudnessResult& loudness) {
+    std::vector<int64_t> ids;
+    std::vector<int32_t> lens;
+    for (const auto& c : chunks) {
+        ids.insert(ids.end(), c.begin(), c.end());
+        lens.push_back((int32_t)c.size());
+    }
+    if (styles.size() != chunks.size() * KX_STYLE_DIM) throw std::invalid_argument("submit_request: one style row per chunk");
+    void* out = nullptr;
+    int64_t nb = 0, ns = 0;
+    double ld[4] = {0.0, 1.0, 0.0, 0.0};
+    char err[256] = {0};
+    if (kx_dispatcher_submit_request_loudness(d, ids.data(), lens.data(), (int)lens.size(), styles.data(), nullptr, nullptr, 0, speed,
+                                              seed, format, &out, &nb, &ns, nullptr, nullptr, nullptr, &spec, ld, err, sizeof(err)) != KX_OK)
+        throw std::runtime_error(std::string("kokorox_hip error: ") + err);
+    std::string body(static_cast<const char*>(out), (size_t)nb);
+    loudness = LoudnessResult{ld[0], ld[1], ld[2], ld[3]};
     kx_free_packed(out);
     return body;
 }

@@ -124,6 +124,20 @@ int kx_test_output_plan_levelled(int device_id, const float* audio, int B, int64
                                  int64_t* out_samples, int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks,
                                  const kx_level* levels, double* out_levels, char* err, size_t err_len);
 
+/* kx_test_output_plan_levelled with loudness (include/kokorox_hip.h, "loudness"): loudness [R] (one spec per request; needs audio;
+ * mode 0xFFFFFFFF = that request is not metered, as a plain or levelled request beside metered ones in a batch -- a metered request's
+ * level spec must be the plain one), out_loudness [R][4] doubles = f64(p), g, I and n_g of every request (I and n_g of a request
+ * that is not metered are not written), out_hops [R][hops_cap] doubles whose first out_n_hops[r] entries in row r are the hop
+ * energies e[k] request_loudness_kernel stored.  `levels` may be NULL here (then out_levels too).  The order is resampler, peak,
+ * loudness, gain, packer, marks, through the same build_output_plan and launch_output_plan.  loudness = NULL (then the three
+ * outputs NULL and hops_cap 0) is kx_test_output_plan_levelled, which calls this. */
+int kx_test_output_plan_loudness(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames, const int32_t* dur,
+                                 const int32_t* lens, const int32_t* chunks_per_request, int R, const int32_t* formats,
+                                 const kx_join* joins, const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes,
+                                 int64_t* out_samples, int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks,
+                                 const kx_level* levels, double* out_levels, const kx_loudness* loudness, double* out_loudness,
+                                 double* out_hops, int64_t hops_cap, int64_t* out_n_hops, char* err, size_t err_len);
+
 /* Fault injection for the two-CU LSTM recurrence (process-wide, test only): nth > 0 makes the nth following launch of
  * the pair kernel, and every later one, lose the second half of each pair and poll with a short limit, so the call it
  * belongs to must fail with KX_ERR_DEVICE (the bounded wait's error path) and the model must fall back to the one-CU

@@ -79,6 +79,34 @@ impl KxLevel {
     pub const PLAIN: KxLevel = KxLevel { mode: KX_LEVEL_GAIN, gain: 1.0, peak: 0.0 };
 }
 
+pub const KX_LOUDNESS_MEASURE: u32 = 0;
+pub const KX_LOUDNESS_NORMALIZE: u32 = 1;
+
+/// How a request's loudness is measured and set on the GPU (`kx_loudness`; "loudness" in kokorox_hip.h): mode 0 measures the
+/// integrated loudness of ITU-R BS.1770 (`target_lufs` and `peak` +0.0), mode 1 scales the body to `target_lufs` (-70..0) but
+/// never lets its largest |sample| exceed `peak` (2^-15..1).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct KxLoudness {
+    pub mode: u32,
+    pub target_lufs: f32,
+    pub peak: f32,
+}
+
+impl KxLoudness {
+    /// The meter: the samples as they are, their loudness measured.
+    pub const METER: KxLoudness = KxLoudness { mode: KX_LOUDNESS_MEASURE, target_lufs: 0.0, peak: 0.0 };
+}
+
+/// The ten K-weighting coefficients of a format word's rate: shelf b0 b1 b2 a1 a2, then high-pass b0 b1 b2 a1 a2 (host only).
+pub fn loudness_filter(format_word: c_int) -> Result<[f64; 10], Box<dyn Error>> {
+    let mut c = [0f64; 10];
+    match unsafe { kx_loudness_filter(format_word, c.as_mut_ptr()) } {
+        KX_OK => Ok(c),
+        rc => Err(format!("kokorox_hip error {}: unknown output format or sample rate", rc).into()),
+    }
+}
+
 #[repr(C)]
 pub struct KxModel {
     _p: [u8; 0],
@@ -94,6 +122,19 @@ extern "C" {
     fn kx_create(weights_path: *const c_char, device_id: c_int, err: *mut c_char, err_len: usize) -> *mut KxModel;
     fn kx_import_onnx(onnx_path: *const c_char, out_path: *const c_char, err: *mut c_char, err_len: usize) -> c_int;
     fn kx_resample_filter(format_word: c_int, l: *mut i32, m: *mut i32, n_taps: *mut i32, taps: *mut f32, cap: c_int) -> c_int;
+    fn kx_loudness_filter(format_word: c_int, out10: *mut f64) -> c_int;
+    fn kx_infer_requests_loudness(m: *mut KxModel, ids: *const i64, t_stride: i64, lens: *const i32, b: c_int,
+                                  chunks_per_request: *const i32, r: c_int, styles: *const f32, voice_ids: *const i32,
+                                  weights: *const f32, max_mix: c_int, speeds: *const f32, n_speed: c_int, seed: u64, flags: u32,
+                                  formats: *const c_int, n_format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                                  out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64, joins: *const KxJoin,
+                                  n_join: c_int, loudness: *const KxLoudness, n_loudness: c_int, out_loudness: *mut f64) -> c_int;
+    fn kx_dispatcher_submit_request_loudness(d: *mut KxDispatcher, ids: *const i64, chunk_tokens: *const i32, n_chunks: c_int,
+                                             styles: *const f32, voice_ids: *const i32, weights: *const f32, n_mix: c_int,
+                                             speed: f32, seed: u64, format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                                             out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64,
+                                             join: *const KxJoin, loudness: *const KxLoudness, out_loudness: *mut f64, err: *mut c_char,
+                                             err_len: usize) -> c_int;
     fn kx_create_from_device_blob(d_blob: *const c_void, n_bytes: usize, device_id: c_int, err: *mut c_char,
                                   err_len: usize) -> *mut KxModel;
     fn kx_create_replicas(weights_path: *const c_char, device_ids: *const c_int, n: c_int,
@@ -604,6 +645,47 @@ impl HipKoko {
         Ok(res)
     }
 
+    /// `infer_requests_joined` with the integrated loudness of every request measured, and set, on the GPU ("loudness" in
+    /// kokorox_hip.h): `loudness` holds one spec for all requests or one per request, `joins` may be empty (no joins).  Per
+    /// request: body, marks, and [p, g, I, n_g]: the peak of its stream, the gain applied, its loudness in LUFS (NaN when
+    /// undefined) and the number of gated blocks, as the GPU computed them.
+    #[allow(clippy::type_complexity)]
+    pub fn infer_requests_loudness(&self, tokens: &[Vec<i64>], chunks_per_request: &[i32], styles: &[Vec<f32>], speeds: &[f32],
+                                   seed: u64, formats: &[c_int], joins: &[KxJoin], loudness: &[KxLoudness])
+                                   -> Result<Vec<(Vec<u8>, Vec<i64>, [f64; 4])>, Box<dyn Error>> {
+        if tokens.is_empty() || styles.len() != tokens.len() || styles.iter().any(|s| s.len() != KX_STYLE_DIM) {
+            return Err("infer_requests: one style row of 256 floats per chunk is required".into());
+        }
+        let (b, r) = (tokens.len(), chunks_per_request.len());
+        let (ids, lens, stride) = Self::flatten(tokens);
+        let st: Vec<f32> = styles.iter().flatten().copied().collect();
+        let mut out: *mut c_void = ptr::null_mut();
+        let mut mk: *mut i64 = ptr::null_mut();
+        let (mut nbytes, mut nsamp, mut nmarks) = (vec![0i64; r.max(1)], vec![0i64; r.max(1)], vec![0i64; r.max(1)]);
+        let mut ld = vec![0f64; 4 * r.max(1)];
+        let rc = unsafe {
+            kx_infer_requests_loudness(self.h, ids.as_ptr(), stride as i64, lens.as_ptr(), b as c_int, chunks_per_request.as_ptr(),
+                                       r as c_int, st.as_ptr(), ptr::null(), ptr::null(), 0, speeds.as_ptr(), speeds.len() as c_int,
+                                       seed, 0, formats.as_ptr(), formats.len() as c_int, &mut out, nbytes.as_mut_ptr(),
+                                       nsamp.as_mut_ptr(), &mut mk, nmarks.as_mut_ptr(),
+                                       if joins.is_empty() { ptr::null() } else { joins.as_ptr() }, joins.len() as c_int,
+                                       loudness.as_ptr(), loudness.len() as c_int, ld.as_mut_ptr())
+        };
+        self.check(rc)?;
+        let mut res = Vec::with_capacity(r);
+        let (mut at, mut mat) = (0usize, 0usize);
+        for i in 0..r {
+            // (the marks live in the buffer of `out`: copied before it is released)
+            let body = unsafe { std::slice::from_raw_parts((out as *const u8).add(at), nbytes[i] as usize) }.to_vec();
+            let marks = unsafe { std::slice::from_raw_parts((mk as *const i64).add(mat), nmarks[i] as usize) }.to_vec();
+            at += nbytes[i] as usize;
+            mat += nmarks[i] as usize;
+            res.push((body, marks, [ld[4 * i], ld[4 * i + 1], ld[4 * i + 2], ld[4 * i + 3]]));
+        }
+        unsafe { kx_free_packed(out) };
+        Ok(res)
+    }
+
     /// Raw device-pointer form (inputs and output stay in HBM).
     ///
     /// # Safety
@@ -954,6 +1036,37 @@ impl HipKokoDispatcher {
         let marks = unsafe { std::slice::from_raw_parts(mk as *const i64, nm as usize) }.to_vec();
         unsafe { kx_free_packed(out) };
         Ok((v, marks, ns, (lv[0], lv[1])))
+    }
+
+    /// `submit_request_joined` with the request's loudness spec ("loudness" in kokorox_hip.h; `join` = None: no join): body,
+    /// marks, sample count, and [p, g, I, n_g] of the request.
+    #[allow(clippy::too_many_arguments, clippy::type_complexity)]
+    pub fn submit_request_loudness(&self, chunks: &[Vec<i64>], styles: &[f32], speed: f32, seed: u64, format: i32,
+                                   join: Option<KxJoin>, loudness: KxLoudness) -> Result<(Vec<u8>, Vec<i64>, i64, [f64; 4]), Box<dyn Error>> {
+        if styles.len() != KX_STYLE_DIM * chunks.len() {
+            return Err("submit_request: one style row of 256 floats per chunk is required".into());
+        }
+        let ids: Vec<i64> = chunks.iter().flatten().copied().collect();
+        let lens: Vec<i32> = chunks.iter().map(|c| c.len() as i32).collect();
+        let mut out: *mut c_void = ptr::null_mut();
+        let mut mk: *mut i64 = ptr::null_mut();
+        let (mut nb, mut ns, mut nm) = (0i64, 0i64, 0i64);
+        let mut ld = [0f64; 4];
+        let mut err = vec![0 as c_char; 256];
+        let rc = unsafe {
+            kx_dispatcher_submit_request_loudness(self.d, ids.as_ptr(), lens.as_ptr(), lens.len() as c_int, styles.as_ptr(), ptr::null(),
+                                                  ptr::null(), 0, speed, seed, format, &mut out, &mut nb, &mut ns, &mut mk, &mut nm,
+                                                  join.as_ref().map_or(ptr::null(), |j| j as *const KxJoin), &loudness, ld.as_mut_ptr(),
+                                                  err.as_mut_ptr(), err.len())
+        };
+        if rc != KX_OK {
+            return Err(format!("kokorox_hip error {}: {}", rc, cstr_buf(&err)).into());
+        }
+        let v = unsafe { std::slice::from_raw_parts(out as *const u8, nb as usize) }.to_vec();
+        // (inside the allocation of `out`: copied before it is released)
+        let marks = unsafe { std::slice::from_raw_parts(mk as *const i64, nm as usize) }.to_vec();
+        unsafe { kx_free_packed(out) };
+        Ok((v, marks, ns, ld))
     }
 
     /// The WebSocket chunk of `encode_audio` (kokorox-websocket/src/lib.rs:696-736) for a request: base64 of its 16-bit WAV

@@ -70,6 +70,14 @@ int kx_resample_filter(int format_word, int32_t* L, int32_t* M, int32_t* n_taps,
     });
 }
 
+int kx_loudness_filter(int format_word, double* out10) {
+    return guarded_free(nullptr, 0, [&] {
+        kx::check_format_word(format_word);
+        KX_REQUIRE(out10, "loudness_filter: null argument");
+        std::memcpy(out10, kx::loud_coefs(kx::format_rate(format_word)), 10 * sizeof(double));
+    });
+}
+
 kx_model* kx_create_from_device_blob(const void* d_blob, size_t n_bytes, int device_id, char* err, size_t err_len) {
     kx_model* h = nullptr;
     int rc = guarded_free(err, err_len, [&] {
@@ -292,15 +300,21 @@ static_assert(sizeof(kx_level) == 12 && sizeof(kx_level) == sizeof(kx::LevelSpec
                   KX_LEVEL_GAIN == kx::LEVEL_GAIN && KX_LEVEL_NORMALIZE == kx::LEVEL_NORMALIZE && KX_LEVEL_CEILING == kx::LEVEL_CEILING,
               "kx_level is the layout of kx::LevelSpec");
 
-// kx_infer_requests, kx_infer_requests_marks, kx_infer_requests_joined and kx_infer_requests_levelled are one call: the first asks
-// for no marks, the first two for no joins, the first three for no levels
+static_assert(sizeof(kx_loudness) == 12 && sizeof(kx_loudness) == sizeof(kx::LoudSpec) && offsetof(kx_loudness, mode) == offsetof(kx::LoudSpec, mode) &&
+                  offsetof(kx_loudness, target_lufs) == offsetof(kx::LoudSpec, target_lufs) && offsetof(kx_loudness, peak) == offsetof(kx::LoudSpec, peak) &&
+                  KX_LOUDNESS_MEASURE == kx::LOUD_MEASURE && KX_LOUDNESS_NORMALIZE == kx::LOUD_NORMALIZE,
+              "kx_loudness is the layout of kx::LoudSpec");
+
+// kx_infer_requests, kx_infer_requests_marks, kx_infer_requests_joined, kx_infer_requests_levelled and kx_infer_requests_loudness are
+// one call: the first asks for no marks, the first two for no joins, the first three for no levels, the first four for no loudness
 static int infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
                           const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
                           const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
                           const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
                           bool marks, int64_t** out_marks, int64_t* out_n_marks, bool joined = false, const kx_join* joins = nullptr,
                           int n_join = 0, bool levelled = false, const kx_level* levels = nullptr, int n_level = 0,
-                          double* out_levels = nullptr) {
+                          double* out_levels = nullptr, bool loud = false, const kx_loudness* loudness = nullptr, int n_loudness = 0,
+                          double* out_loudness = nullptr) {
     return guarded(m, [&](Model& M) {
         KX_REQUIRE(chunks_per_request && formats && R >= 1, "infer_requests: null argument");
         KX_REQUIRE((styles != nullptr) != (voice_ids != nullptr), "infer_requests: give the style rows OR voice ids, not both");
@@ -329,8 +343,13 @@ static int infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, con
             hc.req_levels = reinterpret_cast<const kx::LevelSpec*>(levels);
             hc.n_req_levels = n_level;
         }
+        if (loud) {  // (a null `loudness` is refused with the call's other arguments: check_loudness_call)
+            hc.loud_call = true;
+            hc.req_loudness = reinterpret_cast<const kx::LoudSpec*>(loudness);
+            hc.n_req_loudness = n_loudness;
+        }
         M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks,
-                        levelled ? out_levels : nullptr);
+                        levelled ? out_levels : nullptr, loud ? out_loudness : nullptr);
     });
 }
 
@@ -371,6 +390,18 @@ int kx_infer_requests_levelled(kx_model* m, const int64_t* ids, int64_t t_stride
     return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
                           flags, formats, n_format, out, out_bytes, out_samples, out_marks || out_n_marks, out_marks, out_n_marks,
                           joins != nullptr || n_join != 0, joins, n_join, true, levels, n_level, out_levels);
+}
+
+int kx_infer_requests_loudness(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                               const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                               const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                               const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                               int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join,
+                               const kx_loudness* loudness, int n_loudness, double* out_loudness) {
+    return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
+                          flags, formats, n_format, out, out_bytes, out_samples, out_marks || out_n_marks, out_marks, out_n_marks,
+                          joins != nullptr || n_join != 0, joins, n_join, false, nullptr, 0, nullptr, true, loudness, n_loudness,
+                          out_loudness);
 }
 
 int kx_infer_device(kx_model* m, const int64_t* d_ids, int64_t t_stride, const int32_t* lens_host, int B,

@@ -25,6 +25,7 @@ struct ModelBackend {
         int64_t* marks = nullptr;
         std::vector<int64_t> n_marks;
         std::vector<double> levels;  // [R][2] = {f64(p), g} when some request of the batch came through the levelled entry, else empty
+        std::vector<double> loud;    // [R][4] = {f64(p), g, I, n_g} when some request came through the loudness entry, else empty
     };
     static int n_voices(kx_model* h) { return h->m->n_voices(); }
     static int n_vocab(kx_model* h) { return h->m->n_vocab(); }
@@ -36,8 +37,9 @@ struct ModelBackend {
         int B = 0;
         size_t stride = 0;
         int mm = 1;
-        bool any_voice = false, any_marks = false, any_join = false, any_level = false;
+        bool any_voice = false, any_marks = false, any_join = false, any_level = false, any_loud = false;
         for (Request* r : batch) {
+            any_loud = any_loud || r->metered;
             any_marks = any_marks || r->want_marks;
             any_join = any_join || r->joined();
             any_level = any_level || r->levelled;
@@ -54,6 +56,7 @@ struct ModelBackend {
         std::vector<uint8_t> want(R);
         std::vector<kx::JoinSpec> joins(R);  // (a plain request beside a joined one: the all-zero spec, the plain bytes)
         std::vector<kx::LevelSpec> levels(R);  // (a request without levels beside a levelled one: the plain spec, z' = z)
+        std::vector<kx::LoudSpec> louds(R);  // (a request without loudness beside a metered one: LOUD_NONE, the meter passes it by)
         int b = 0;
         for (int q = 0; q < R; ++q) {
             const Request& r = *batch[(size_t)q];
@@ -62,6 +65,7 @@ struct ModelBackend {
             want[q] = r.want_marks ? 1 : 0;
             joins[q] = kx::JoinSpec{r.join.flags, r.join.keep_ms, r.join.pause_ms, r.join.fade_ms};
             levels[q] = kx::LevelSpec{r.level.mode, r.level.gain, r.level.peak};
+            louds[q] = r.metered ? kx::LoudSpec{r.loudness.mode, r.loudness.target_lufs, r.loudness.peak} : kx::LoudSpec{kx::LOUD_NONE, 0.0f, 0.0f};
             size_t at = 0;
             for (int c = 0; c < r.rows(); ++c, ++b) {
                 lens[b] = (int32_t)r.chunk_len(c);
@@ -84,6 +88,7 @@ struct ModelBackend {
         o.marks = nullptr;
         o.n_marks.assign(R, 0);
         o.levels.assign(any_level ? (size_t)2 * R : 0, 0.0);
+        o.loud.assign(any_loud ? (size_t)4 * R : 0, 0.0);
         int rc = KX_ERR_DEVICE;
         std::string err;
         {
@@ -109,6 +114,10 @@ struct ModelBackend {
                     hc.req_levels = levels.data();
                     hc.n_req_levels = R;
                 }
+                if (any_loud) {
+                    hc.req_loudness = louds.data();
+                    hc.n_req_loudness = R;
+                }
                 if (any_voice) {
                     hc.voice_ids = vids.data();
                     hc.weights = weights.data();
@@ -119,7 +128,8 @@ struct ModelBackend {
                     hc.styles = styles.data();
                 }
                 M.infer_host_ex(ids.data(), (int64_t)stride, lens.data(), B, speeds.data(), B, 0, 0, hc, &o.buf, o.bytes.data(),
-                                o.samples.data(), &o.marks, o.n_marks.data(), any_level ? o.levels.data() : nullptr);
+                                o.samples.data(), &o.marks, o.n_marks.data(), any_level ? o.levels.data() : nullptr,
+                                any_loud ? o.loud.data() : nullptr);
                 rc = KX_OK;
             } catch (const kx::Error& e) {
                 rc = e.code;
@@ -196,6 +206,8 @@ struct ModelBackend {
                 r->level_out[0] = o.levels[(size_t)2 * b];
                 r->level_out[1] = o.levels[(size_t)2 * b + 1];
             }
+            if (r->metered && !o.loud.empty())
+                for (int i = 0; i < 4; ++i) r->loud_out[i] = o.loud[(size_t)4 * b + i];
         }
         o.buf = nullptr;
         o.marks = nullptr;
@@ -331,6 +343,19 @@ int kx_dispatcher_submit_request_levelled(kx_dispatcher* d, const int64_t* ids, 
     }
     return d->submit_request_levelled(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
                                       out_bytes, out_samples, out_marks, out_n_marks, join, level, out_level, err, err_len);
+}
+
+int kx_dispatcher_submit_request_loudness(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                          const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
+                                          float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
+                                          int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
+                                          const kx_loudness* loudness, double* out_loudness, char* err, size_t err_len) {
+    if (!d) {
+        if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null dispatcher");
+        return KX_ERR_INVALID;
+    }
+    return d->submit_request_loudness(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
+                                      out_bytes, out_samples, out_marks, out_n_marks, join, loudness, out_loudness, err, err_len);
 }
 
 int kx_dispatcher_stats(kx_dispatcher* d, int64_t* n_requests, int64_t* n_batches, int64_t* max_batch_seen) {

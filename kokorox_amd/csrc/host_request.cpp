@@ -3,6 +3,7 @@
 
 #include <cstring>
 
+#include "kweight_coefs.h"
 #include "resample_taps.h"
 
 namespace kx {
@@ -114,6 +115,65 @@ void check_level_call(const HostCall& hc) {
     for (int i = 0; i < hc.n_req_levels; ++i) KX_REQUIRE(level_spec_ok(hc.req_levels[i]), "infer: bad level");
 }
 
+void check_loudness_call(const HostCall& hc) {
+    KX_REQUIRE(hc.req_loudness, "infer: null loudness argument");
+    KX_REQUIRE(hc.grouped() && (hc.n_req_loudness == 1 || hc.n_req_loudness == hc.n_requests), "infer: bad loudness count");
+    for (int i = 0; i < hc.n_req_loudness; ++i) KX_REQUIRE(loud_spec_ok(hc.req_loudness[i]), "infer: bad loudness");
+}
+
+// ---- the meter's tables (include/kokorox_hip.h, "loudness") ---------------------------------------------------------------------
+namespace {
+// (committed as bit patterns, rate codes 0..3: what the library computes with is what the generator rounded)
+const uint64_t kKweightBits[4][10] = {{KX_KWEIGHT_COEFS_24000}, {KX_KWEIGHT_COEFS_8000}, {KX_KWEIGHT_COEFS_16000}, {KX_KWEIGHT_COEFS_48000}};
+struct LoudTables {
+    double coefs[4][10];
+    double powers[4][LOUD_POWERS][16];
+    LoudTables() {
+        static_assert(sizeof(double) == 8, "float64 bit patterns");
+        std::memcpy(coefs, kKweightBits, sizeof coefs);
+        for (int c = 0; c < 4; ++c) {
+            // one step of the cascade with no input, over s = (v1, v2, w1, w2): v = -a1 v1 - a2 v2, w = c0 v + c1 v1 + c2 v2 - d1 w1 - d2 w2
+            const double* k = coefs[c];
+            const double a1 = k[3], a2 = k[4], c0 = k[5], c1 = k[6], c2 = k[7], d1 = k[8], d2 = k[9];
+            // (the high-pass has a pole pair at radius 0.995 .. 0.97: entries of A^n reach a few hundred, and some 3000 products
+            // in float64 would leave 1e-10 in them, which the scan would carry into every hop; the products run in long double --
+            // 64 bits of mantissa where the host has them -- and each power is rounded to float64 once)
+            typedef long double wide;
+            const wide A[16] = {-(wide)a1, -(wide)a2, 0, 0, 1, 0, 0, 0, (wide)c1 - (wide)c0 * a1, (wide)c2 - (wide)c0 * a2, -(wide)d1, -(wide)d2, 0, 0, 1, 0};
+            auto mul = [](const wide* x, const wide* y, wide* z) {  // z = x y
+                for (int i = 0; i < 4; ++i)
+                    for (int j = 0; j < 4; ++j) {
+                        wide acc = 0;
+                        for (int t = 0; t < 4; ++t) acc += x[4 * i + t] * y[4 * t + j];
+                        z[4 * i + j] = acc;
+                    }
+            };
+            wide step[16], cur[16], next[16];  // A^run, and its powers
+            for (int i = 0; i < 16; ++i) step[i] = cur[i] = (i % 5 == 0) ? 1 : 0;
+            for (int n = 0; n < loud_run(c); ++n) {
+                mul(A, step, next);
+                std::memcpy(step, next, sizeof step);
+            }
+            for (int p = 0; p < LOUD_POWERS; ++p) {
+                for (int i = 0; i < 16; ++i) powers[c][p][i] = (double)cur[i];
+                mul(step, cur, next);
+                std::memcpy(cur, next, sizeof cur);
+            }
+        }
+    }
+};
+const LoudTables& loud_tables() {
+    static const LoudTables t;
+    return t;
+}
+}  // namespace
+
+const double* loud_coefs(int rate_code) {
+    KX_REQUIRE(rate_code >= 0 && rate_code <= 3, "infer: unknown output sample rate");
+    return loud_tables().coefs[rate_code];
+}
+const double* loud_powers() { return &loud_tables().powers[0][0][0]; }
+
 // ---- refusals of the device entry (Model::infer_device) ----------------------------------------------------------------------
 int check_device_call(const void* d_ids, int64_t t_stride, const int32_t* lens_host, int B, const void* d_styles,
                       const float* speeds_host, int n_speed) {
@@ -149,13 +209,17 @@ OutputBounds output_bounds(const RequestLayout& lay, int B, size_t n_samples, co
         per_sample = w > per_sample ? w : per_sample;
         y_per_sample = y > y_per_sample ? y : y_per_sample;
     }
-    OutputBounds bound{n_samples * per_sample + (size_t)lay.R * 64 + 16, n_samples * y_per_sample, 0};
+    OutputBounds bound{n_samples * per_sample + (size_t)lay.R * 64 + 16, n_samples * y_per_sample, 0, 0};
     if (lay.marks) {
         KX_REQUIRE(lens, "infer: marks need the token counts");
         bound.packed_bytes += 8;
         for (int b = 0; b < B; ++b) bound.packed_bytes += 8 * ((size_t)lens[b] + 1);
     }
-    if (lay.levels) {  // (no request is longer than all the samples at the batch's highest ratio)
+    if (lay.loudness) {  // (a hop is 2400 samples at 24 000 Hz, whatever the output rate)
+        bound.packed_bytes += 16 * (size_t)lay.R;
+        bound.hop_doubles = (size_t)lay.R * (n_samples / 2400 + 1);
+    }
+    if (lay.levels || lay.loudness) {  // (no request is longer than all the samples at the batch's highest ratio)
         bound.packed_bytes += 8 + 16 * (size_t)lay.R;
         const size_t longest = n_samples * (y_per_sample > 1 ? y_per_sample : 1);
         bound.peak_dwords = (size_t)lay.R * ((longest + (size_t)LEVEL_WINDOW - 1) / (size_t)LEVEL_WINDOW + 1);
@@ -182,7 +246,7 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
     const int R = lay.R;
     KX_REQUIRE(frames && lay.formats && B >= 1 && R >= 1 && (lay.n_format == 1 || lay.n_format == R) &&
                    (!lay.joins || (edges && (lay.n_join == 1 || lay.n_join == R))) && (lens || (!lay.marks && !lay.joins)) &&
-                   (!lay.levels || lay.n_level == 1 || lay.n_level == R),
+                   (!lay.levels || lay.n_level == 1 || lay.n_level == R) && (!lay.loudness || lay.n_loudness == 1 || lay.n_loudness == R),
                "plan: bad argument");
     auto rows_of = [&](int r) { return lay.chunks_per_request ? lay.chunks_per_request[r] : 1; };
     // the rows: what each contributes to its request's stream, and the prefix over it.  (A pass of its own: the refusals of the
@@ -272,14 +336,15 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
     plan.marks_off = (plan.total_bytes + 7) & ~7L;
     // the levels: every request's spec, the block behind the marks and the grid of the peak pass
     plan.level.clear();
-    plan.measured = lay.levels != nullptr;
+    plan.measured = lay.levels != nullptr || lay.loudness != nullptr;
     plan.levelled = false;
     plan.levels_off = plan.peak_windows = 0;
+    const LevelSpec plain_level{LEVEL_GAIN, 1.0f, 0.0f};
     if (plan.measured) {
         plan.level.resize((size_t)R);
         long longest = 0;
         for (int r = 0; r < R; ++r) {
-            const LevelSpec& ls = lay.levels[lay.n_level == 1 ? 0 : r];
+            const LevelSpec& ls = lay.levels ? lay.levels[lay.n_level == 1 ? 0 : r] : plain_level;
             KX_REQUIRE(level_spec_ok(ls), "infer: bad level");
             plan.level[(size_t)r] = ls;
             plan.levelled = plan.levelled || !level_spec_plain(ls);
@@ -287,6 +352,29 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
         }
         plan.levels_off = (plan.marks_off + 8 * plan.n_marks + 7) & ~7L;
         plan.peak_windows = (longest + LEVEL_WINDOW - 1) / LEVEL_WINDOW;
+    }
+    // the loudness: every request's spec, the block behind the levels and the grid of the meter.  A metered request's {p, g} are the
+    // loudness gain kernel's: its level spec is the plain one.
+    plan.loud.clear();
+    plan.loud_all = false;
+    plan.loud_off = plan.max_hops = 0;
+    if (lay.loudness) {
+        plan.loud.resize((size_t)R);
+        plan.loud_all = true;
+        for (int r = 0; r < R; ++r) {
+            const LoudSpec& ls = lay.loudness[lay.n_loudness == 1 ? 0 : r];
+            KX_REQUIRE(ls.mode == LOUD_NONE || loud_spec_ok(ls), "infer: bad loudness");
+            plan.loud[(size_t)r] = ls;
+            if (ls.mode == LOUD_NONE) {
+                plan.loud_all = false;
+                continue;
+            }
+            KX_REQUIRE(level_spec_plain(plan.level[(size_t)r]), "plan: a request has a level or a loudness, not both");
+            plan.levelled = plan.levelled || ls.mode == LOUD_NORMALIZE;
+            const long hops = plan.req[(size_t)r].n_samples / loud_hop(plan.req[(size_t)r].rate);
+            plan.max_hops = hops > plan.max_hops ? hops : plan.max_hops;
+        }
+        plan.loud_off = plan.levels_off + 16L * R;
     }
 }
 

@@ -48,8 +48,35 @@ inline bool level_spec_plain(const LevelSpec& l) { return l.mode == LEVEL_GAIN &
 // samples of a request's stream (at its output rate) that one workgroup of the peak pass reduces (request_kernels.hip)
 constexpr long LEVEL_WINDOW = 4096;
 
+// A request's loudness spec: the layout of kx_loudness (include/kokorox_hip.h, "loudness"; api.hip asserts the two agree).
+struct LoudSpec {
+    uint32_t mode;      // LOUD_MEASURE or LOUD_NORMALIZE (LOUD_NONE: inside a plan only, a request beside loudness ones that has none)
+    float target_lufs;  // +0 in mode 0; -70..0 in mode 1
+    float peak;         // +0 in mode 0; 2^-15..1 in mode 1
+};
+constexpr uint32_t LOUD_MEASURE = 0u, LOUD_NORMALIZE = 1u, LOUD_NONE = 0xFFFFFFFFu;
+// (every comparison is written so that a NaN fails it)
+inline bool loud_spec_ok(const LoudSpec& l) {
+    if (l.mode == LOUD_MEASURE) return level_float_bits(l.target_lufs) == 0u && level_float_bits(l.peak) == 0u;
+    return l.mode == LOUD_NORMALIZE && l.target_lufs >= -70.0f && l.target_lufs <= 0.0f && l.peak >= 0x1p-15f && l.peak <= 1.0f;
+}
+// The meter's grid at rate code c (request_kernels.hip: request_loudness_kernel): a hop of 100 ms, the warm-up a workgroup runs from
+// zero state before its hop (the tail of sum |h| of the K-weighting beyond it is below 1e-15), and the odd number of samples one of
+// its LOUD_THREADS lanes runs: LOUD_THREADS * loud_run(c) >= loud_warmup(c) + loud_hop(c).
+constexpr int LOUD_THREADS = 256;
+constexpr int LOUD_POWERS = 65;  // A^(run k), k = 0..64, of a rate's 4x4 transition matrix: 16 doubles each, row-major
+constexpr double LOUD_ABS_GATE = 1.1724653045822981e-07;  // 10^((-70 + 0.691) / 10)
+constexpr long loud_rate_hz(int c) { return c == 1 ? 8000 : (c == 2 ? 16000 : (c == 3 ? 48000 : 24000)); }
+constexpr long loud_hop(int c) { return loud_rate_hz(c) / 10; }
+constexpr long loud_warmup(int c) { return c == 1 ? 1536 : (c == 2 ? 3072 : (c == 3 ? 8192 : 4096)); }
+constexpr int loud_run(int c) { return (int)((loud_warmup(c) + loud_hop(c) + LOUD_THREADS - 1) / LOUD_THREADS) | 1; }
+// the ten K-weighting coefficients of rate code 0..3 (kweight_coefs.h: shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2)
+const double* loud_coefs(int rate_code);  // throws KX_ERR_INVALID outside 0..3
+// [4][LOUD_POWERS][16]: the powers of every rate's transition matrix over the state (v[n-1], v[n-2], w[n-1], w[n-2]) of the cascade
+const double* loud_powers();
+
 // What a call asks of the output stage (a view: the arrays are the caller's): how its rows group into requests, and each
-// request's format word, wish for token marks, join spec and level spec.  build_output_plan and output_bounds take it.
+// request's format word, wish for token marks, join spec, level spec and loudness spec.  build_output_plan and output_bounds take it.
 struct RequestLayout {
     const int32_t* chunks_per_request;  // [R] rows of each request; null: every row a request of its own, and R = B
     int R;
@@ -60,6 +87,8 @@ struct RequestLayout {
     int n_join;
     const LevelSpec* levels;            // [n_level] with n_level = 1 (shared) or R; null: nothing is measured or scaled
     int n_level;
+    const LoudSpec* loudness;           // [n_loudness] with n_loudness = 1 (shared) or R; null: no request is metered (a spec of mode
+    int n_loudness;                     // LOUD_NONE: that request is not)
 };
 
 // general host entry behind kx_infer / kx_infer_voices / kx_infer_packed / kx_infer_requests (Model::infer_host_ex)
@@ -90,6 +119,10 @@ struct HostCall {
     bool level_call = false;                      // the entry that takes levels: req_levels must then be there (check_level_call)
     const LevelSpec* req_levels = nullptr;        // host [n_req_levels]
     int n_req_levels = 0;                         // 1 (shared) or n_requests
+    // loudness (include/kokorox_hip.h, "loudness"): request r is metered and scaled by req_loudness[n_req_loudness == 1 ? 0 : r]; null = none
+    bool loud_call = false;                       // the entry that takes loudness: req_loudness must then be there (check_loudness_call)
+    const LoudSpec* req_loudness = nullptr;       // host [n_req_loudness]
+    int n_req_loudness = 0;                       // 1 (shared) or n_requests
 
     bool grouped() const { return chunks_per_request != nullptr; }
     bool by_voice() const { return voice_ids != nullptr; }
@@ -98,7 +131,7 @@ struct HostCall {
     RequestLayout layout(int B) const {
         if (!grouped()) return RequestLayout{nullptr, B, &format, 1, nullptr, nullptr, 0, nullptr, 0};
         return RequestLayout{chunks_per_request, n_requests, req_formats, n_req_formats, req_marks, req_joins, n_req_joins, req_levels,
-                             n_req_levels};
+                             n_req_levels, req_loudness, n_req_loudness};
     }
 };
 
@@ -120,6 +153,9 @@ void check_join_call(const HostCall& hc);
 // The entry that takes levels (HostCall::level_call), checked after everything above.  throws KX_ERR_INVALID: "infer: null level
 // argument", "infer: bad level count" (not 1 or R), "infer: bad level" (level_spec_ok fails).
 void check_level_call(const HostCall& hc);
+// The entry that takes loudness (HostCall::loud_call), checked after everything above.  throws KX_ERR_INVALID: "infer: null loudness
+// argument", "infer: bad loudness count" (not 1 or R), "infer: bad loudness" (loud_spec_ok fails).
+void check_loudness_call(const HostCall& hc);
 // Everything Model::infer_device refuses before hipSetDevice; returns the longest token count.
 int check_device_call(const void* d_ids, int64_t t_stride, const int32_t* lens_host, int B, const void* d_styles,
                       const float* speeds_host, int n_speed);
@@ -202,8 +238,18 @@ struct OutputPlan {
     long levels_off = 0;           // byte offset of the block (a multiple of 8, >= marks_off + 8 n_marks); 0 when not measured
     long peak_windows = 0;         // LEVEL_WINDOW-sample windows of the longest request: the peak pass's grid and table stride
     long peak_dwords() const { return measured ? (long)req.size() * peak_windows : 0; }  // the partials table [R][peak_windows]
-    // bytes of body + marks (+ levels): what one copy brings to the host
-    long end_bytes() const { return measured ? levels_off + 16 * (long)req.size() : marks_off + 8 * n_marks; }
+    // Loudness (include/kokorox_hip.h, "loudness"; request_kernels.hip: request_loudness_kernel, request_loudness_gain_kernel): a
+    // fourth block behind the levels, [R]{double I, double n_g}.  A plan with loudness is measured: the metered requests' {p, g} come
+    // from the loudness gain kernel, the others' from request_gain_kernel (the plain spec where the layout gave no levels).
+    std::vector<LoudSpec> loud;    // [R], LOUD_NONE where a request is not metered; empty when the layout has no loudness
+    bool loud_all = false;         // every request is metered: request_gain_kernel has no slot to write
+    long loud_off = 0;             // byte offset of the block: levels_off + 16 R; 0 without loudness
+    long max_hops = 0;             // whole hops of the metered request that has most: the meter's grid and the stride of its table
+    long hop_doubles() const { return (long)loud.size() * max_hops; }  // the hop energies [R][max_hops]
+    // bytes of body + marks (+ levels (+ loudness)): what one copy brings to the host
+    long end_bytes() const {
+        return !loud.empty() ? loud_off + 16 * (long)req.size() : (measured ? levels_off + 16 * (long)req.size() : marks_off + 8 * n_marks);
+    }
 };
 // `form` = a format word, n_samples at 24 000 Hz.  throws KX_ERR_INVALID: unknown word, 16-bit WAV past 4 GiB
 long pack_request_bytes(int form, long n_samples);
@@ -219,9 +265,10 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
 // samples); with marks (lens [B] then required) 8 + 8 x the sum over the rows of lens + 1 more: the alignment gap and a block
 // in which every request wants them.  y_floats: the intermediate buffer of the resampled streams, 0 when no word carries a
 // rate code.  With levels 8 + 16 R bytes more (the alignment gap and the block), and peak_dwords: the partials table of the peak
-// pass, R rows of the windows the longest request can have.
+// pass, R rows of the windows the longest request can have.  With loudness 16 R bytes more (and the levels' share when the layout
+// has none), and hop_doubles: the hop energies, R rows of the hops all the samples can make (a hop is 100 ms at every rate).
 struct OutputBounds {
-    size_t packed_bytes, y_floats, peak_dwords;
+    size_t packed_bytes, y_floats, peak_dwords, hop_doubles;
 };
 OutputBounds output_bounds(const RequestLayout& layout, int B, size_t n_samples, const int32_t* lens);
 

@@ -297,13 +297,19 @@ struct OutputTables {
     MarkRow* mark;
     LevelSpec* level;
     uint32_t* peak;
+    // a plan with loudness (OutputPlan::loud): loud [R], hops = the hop energies [R][plan.max_hops] (plan.hop_doubles() doubles:
+    // scratch like peak) and loud_pow = the meter's transition powers, 4 * LOUD_POWERS * 16 doubles (host_request.h: loud_powers)
+    LoudSpec* loud;
+    double* hops;
+    double* loud_pow;
 };
 // Everything between "the plan is built" and "copy to the host", for the model and for the test hook: the resampler when
 // plan.y_floats > 0 (d_y: that many floats, null when 0), the packer into d_packed (16-byte aligned, plan.total_bytes long), and
 // when plan.n_marks > 0 the token marks at d_packed + plan.marks_off.  audio [B][audio_ld]; dur [B][512] as duration_kernel
 // wrote it and lens [B], both on the device.  The joined form of the kernels runs only when plan.joined.  A measured plan: the peak
 // pass and the gain kernel between resampler and packer, {p, g} of every request at d_packed + plan.levels_off (8-aligned; d_packed
-// is then plan.end_bytes() long), and the levelled packer when plan.levelled.
+// is then plan.end_bytes() long), and the levelled packer when plan.levelled.  A plan with loudness: request_loudness_kernel behind
+// the peak pass and request_loudness_gain_kernel behind the gain kernel, {I, n_g} of every metered request at d_packed + plan.loud_off.
 void launch_output_plan(const float* audio, long audio_ld, const int* dur, const int* lens, const OutputPlan& plan,
                         const OutputTables& t, float* d_y, void* d_packed, hipStream_t s);
 // its two halves: the bodies, and the marks (n_marks > 0) into a block of their own, 8-byte aligned

@@ -116,14 +116,15 @@ void Model::infer_host(const int64_t* ids, int64_t t_stride, const int32_t* lens
 // points run the call once more, now on the streaming recurrence (same bits), and the caller sees a result, not an error.
 void Model::infer_host_ex(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
                           int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out,
-                          int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, double* out_levels) {
+                          int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, double* out_levels,
+                          double* out_loudness) {
     try {
         infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks,
-                        out_levels);
+                        out_levels, out_loudness);
     } catch (const LstmTimeout&) {
         n_rerun_ += 1;
         infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks,
-                        out_levels);
+                        out_levels, out_loudness);
     }
     note_clean_forward();
 }
@@ -131,18 +132,20 @@ void Model::infer_host_ex(const int64_t* ids, int64_t t_stride, const int32_t* l
 void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
                             int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out,
                             int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
-                            double* out_levels) {
+                            double* out_levels, double* out_loudness) {
     check_host_call(ids, t_stride, lens, B, speeds, hc, out, out_bytes, out_samples, n_vocab_, n_voices_, d_voices_ != nullptr);
     if (hc.join_call) check_join_call(hc);
     if (hc.req_marks) check_marks_call(hc, out_marks, out_n_marks);
     if (hc.level_call) check_level_call(hc);
+    if (hc.loud_call) check_loudness_call(hc);
     const bool by_voice = hc.by_voice();
     // one way to lay the output out and pack it: a call without chunks_per_request is R = B single-row requests in hc.format
     const RequestLayout layout = hc.layout(B);
     const int R = layout.R;
     const bool joins = layout.joins != nullptr;
     const bool marks = layout.marks != nullptr;  // (with chunks_per_request then: check_marks_call)
-    const bool levels = layout.levels != nullptr;
+    const bool loud = layout.loudness != nullptr;
+    const bool levels = layout.levels != nullptr || loud;  // (a call with loudness is measured: its peak pass, its levels block)
     KX_HIP(hipSetDevice(device));
     // I/O staging lives in its own arena: ids, styles, frames, noise keys, voice picks, audio, packed audio
     int64_t* d_ids;
@@ -152,6 +155,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     uint32_t* d_uidx;
     OutputTables tables{};
     size_t peak_cap = 0;   // dwords of tables.peak
+    size_t hop_cap = 0;    // doubles of tables.hops
     float* d_y = nullptr;  // the resampled streams of the requests with a rate code, back to back
     int *d_vid, *d_rows, *d_kinds;
     float* d_w;
@@ -176,6 +180,12 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             tables.level = static_cast<LevelSpec*>(A.alloc((size_t)R * sizeof(LevelSpec)));
             tables.peak = static_cast<uint32_t*>(A.alloc(bound.peak_dwords * sizeof(uint32_t)));
             peak_cap = bound.peak_dwords;
+        }
+        if (loud) {  // (the hop energies of the meter and its transition powers: sized before the forward as well)
+            tables.loud = static_cast<LoudSpec*>(A.alloc((size_t)R * sizeof(LoudSpec)));
+            tables.hops = static_cast<double*>(A.alloc(bound.hop_doubles * sizeof(double)));
+            tables.loud_pow = static_cast<double*>(A.alloc((size_t)4 * LOUD_POWERS * 16 * sizeof(double)));
+            hop_cap = bound.hop_doubles;
         }
         if (marks) tables.mark = static_cast<MarkRow*>(A.alloc((size_t)B * sizeof(MarkRow)));
         d_packed = A.alloc(bound.packed_bytes);  // compact output: the requests back to back, then the marks
@@ -234,6 +244,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             if (marks) out_n_marks[r] = plan.count[(size_t)r];
         }
         KX_REQUIRE((size_t)plan.peak_dwords() <= peak_cap, "levels: the peak table is too small");
+        KX_REQUIRE((size_t)plan.hop_doubles() <= hop_cap, "loudness: the hop table is too small");
         launch_output_plan(d_audio, ld, call_.d_dur, call_.dT, plan, tables, d_y, d_packed, stream_);
         const int64_t marks_off = plan.marks_off, n_marks = plan.n_marks;
         const int64_t total = n_marks > 0 || plan.measured ? plan.end_bytes() : plan.total_bytes;
@@ -255,6 +266,11 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         *out = host;
         if (marks) *out_marks = n_marks > 0 ? reinterpret_cast<int64_t*>(host + marks_off) : nullptr;
         if (plan.measured && out_levels) memcpy(out_levels, host + plan.levels_off, (size_t)R * 16);
+        if (!plan.loud.empty() && out_loudness)
+            for (int r = 0; r < R; ++r) {  // {f64(p), g} of the levels block, {I, n_g} of the loudness block
+                memcpy(out_loudness + 4 * r, host + plan.levels_off + 16 * (size_t)r, 16);
+                memcpy(out_loudness + 4 * r + 2, host + plan.loud_off + 16 * (size_t)r, 16);
+            }
         return;
     }
 }

@@ -1,8 +1,9 @@
 // The output stage of a call (gfx950): every request of the batch packed as the bytes a server sends -- the packer and its
 // forms (samples, WAV, base64, G.711), the output-rate resampler before it, the levels between the two (a request's peak, its
-// gain, the levelled packer), the token timing marks behind the bodies and the edge durations the host's join plan needs.  host_request.h has the tables these kernels read and the planner that fills
+// gain, the levelled packer) and the loudness beside them (the BS.1770 meter and its gain), the token timing marks behind the bodies and the edge durations the host's join plan needs.  host_request.h has the tables these kernels read and the planner that fills
 // them (build_output_plan); launch_output_plan below is the one way they are launched, for the model and for the test hook.
 #include "kx_common.h"
+#include "kweight_coefs.h"
 #include "resample_taps.h"
 
 namespace kx {
@@ -335,6 +336,182 @@ __global__ __launch_bounds__(64) void request_gain_kernel(const PackReq* __restr
     levels[2 * r + 1] = g;
 }
 
+// ---- loudness: BS.1770 K-weighting, hop energies, gating and the gain (include/kokorox_hip.h, "loudness") ---------------------
+// The stream z is the one the peak pass reads; x[n] = f64(z[n]) where z[n] is finite, else 0.  The K-weighting is two biquads in
+// direct form I (kweight_coefs.h), so beside the input the recurrence carries s = (v[n-1], v[n-2], w[n-1], w[n-2]), and with the
+// input switched off one step is s <- A s with a 4x4 matrix A.
+//
+// request_loudness_kernel: workgroup (k, r) owns hop k of request r (loud_hop samples, 100 ms) and stores its energy e[k], the sum
+// of w[n]^2, as ONE double into the table [R][max_hops].  It stages the hop and the loud_warmup samples before it (zeros before the
+// stream's start) into LDS and runs the recurrence over those T samples from zero state as a scan: lane t takes the `run` samples
+// from t * run (run is odd: lanes are run dwords apart, on distinct banks), first from zero state, which leaves q_t; the true end
+// states follow from s_(t+1) = A^run s_t + q_t, one __shfl_up ladder per wave with the host's powers A^(run o) and one exchange of
+// the four wave states through LDS; then every lane runs its samples again from its true start state and sums w^2 over those of
+// the hop.  The sum over the lanes is a __shfl_xor tree and a fixed walk over the four waves.  Every boundary is a function of the
+// request's own sample index, so e[k] does not depend on the batch; no atomic, nothing to zero between calls.
+constexpr int LOUD_LDS = 8192 + 4800;  // loud_warmup + loud_hop at 48 000 Hz, the largest
+static_assert(loud_warmup(0) + loud_hop(0) <= LOUD_LDS && loud_warmup(1) + loud_hop(1) <= LOUD_LDS && loud_warmup(2) + loud_hop(2) <= LOUD_LDS &&
+                  loud_warmup(3) + loud_hop(3) == LOUD_LDS && LOUD_THREADS == 256,
+              "the staged window fits, four waves");
+static_assert((long)LOUD_THREADS * loud_run(0) >= loud_warmup(0) + loud_hop(0) && (long)LOUD_THREADS * loud_run(1) >= loud_warmup(1) + loud_hop(1) &&
+                  (long)LOUD_THREADS * loud_run(2) >= loud_warmup(2) + loud_hop(2) && (long)LOUD_THREADS * loud_run(3) >= loud_warmup(3) + loud_hop(3),
+              "the lanes' runs cover the window");
+__device__ const unsigned long long kweight_bits[4][10] = {{KX_KWEIGHT_COEFS_24000}, {KX_KWEIGHT_COEFS_8000}, {KX_KWEIGHT_COEFS_16000}, {KX_KWEIGHT_COEFS_48000}};
+
+struct KwState {
+    double v1, v2, w1, w2;
+};
+// s += P t, P row-major 4x4
+__device__ __forceinline__ void kw_apply(KwState& s, const double* __restrict__ P, const KwState& t) {
+    s.v1 += P[0] * t.v1 + P[1] * t.v2 + P[2] * t.w1 + P[3] * t.w2;
+    s.v2 += P[4] * t.v1 + P[5] * t.v2 + P[6] * t.w1 + P[7] * t.w2;
+    s.w1 += P[8] * t.v1 + P[9] * t.v2 + P[10] * t.w1 + P[11] * t.w2;
+    s.w2 += P[12] * t.v1 + P[13] * t.v2 + P[14] * t.w1 + P[15] * t.w2;
+}
+// samples [lo, hi) of the staged window through the cascade, from state s (the two inputs before lo are read from the window);
+// returns the sum of w^2 over the samples at or past `from`
+__device__ __forceinline__ double kw_run(const float* __restrict__ xs, long lo, long hi, long from, const double* __restrict__ k, KwState& s) {
+    double x1 = lo >= 1 ? (double)xs[lo - 1] : 0.0, x2 = lo >= 2 ? (double)xs[lo - 2] : 0.0, acc = 0.0;
+    for (long n = lo; n < hi; ++n) {
+        const double x = (double)xs[n];
+        const double v = k[0] * x + k[1] * x1 + k[2] * x2 - k[3] * s.v1 - k[4] * s.v2;
+        const double w = k[5] * v + k[6] * s.v1 + k[7] * s.v2 - k[8] * s.w1 - k[9] * s.w2;
+        x2 = x1, x1 = x;
+        s.v2 = s.v1, s.v1 = v;
+        s.w2 = s.w1, s.w1 = w;
+        if (n >= from) acc += w * w;
+    }
+    return acc;
+}
+__global__ __launch_bounds__(LOUD_THREADS) void request_loudness_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                         const PackReq* __restrict__ reqs, const long* __restrict__ cum,
+                                                                         const JoinRow* __restrict__ jrows, const float* __restrict__ y,
+                                                                         const LoudSpec* __restrict__ specs,
+                                                                         const double* __restrict__ powers, double* __restrict__ hops,
+                                                                         long max_hops) {
+    __shared__ float xs[LOUD_LDS];
+    __shared__ double wave_state[LOUD_THREADS / 64][4];
+    __shared__ double wave_sum[LOUD_THREADS / 64];
+    if (specs[blockIdx.y].mode == LOUD_NONE) return;  // (uniform) a request beside the metered ones
+    const PackReq rq = reqs[blockIdx.y];
+    const long hop = loud_hop(rq.rate), W = loud_warmup(rq.rate), T = W + hop;
+    const int run = loud_run(rq.rate);
+    const long h0 = (long)blockIdx.x * hop;
+    if (h0 + hop > rq.n_samples) return;  // (uniform: the grid covers the request with most hops; a partial hop is ignored)
+    // the window: local index i is sample h0 - W + i of the stream; the first `zeros` of them lie before its start
+    const long zeros = h0 < W ? W - h0 : 0, s_lo = h0 - W + zeros, s_hi = h0 + hop;
+    for (long i = threadIdx.x; i < zeros; i += LOUD_THREADS) xs[i] = 0.0f;
+    float* __restrict__ dst = xs + zeros;
+    auto finite = [](float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; };
+    if (rq.rate) {  // (uniform) one contiguous run
+        const float* __restrict__ src = y + rq.y_off;
+        for (long i = s_lo + threadIdx.x; i < s_hi; i += LOUD_THREADS) {
+            const float v = src[i];
+            dst[i - s_lo] = finite(v) ? v : 0.0f;
+        }
+    } else {  // the rows, cut and faded as the packer will see them; every lane checks the samples it staged itself
+        if (jrows) stage_stream<true, LOUD_THREADS>(dst, audio, audio_ld, cum, jrows, rq.first_row, rq.n_rows, s_lo, s_hi);
+        else stage_stream<false, LOUD_THREADS>(dst, audio, audio_ld, cum, jrows, rq.first_row, rq.n_rows, s_lo, s_hi);
+        for (long i = s_lo + threadIdx.x; i < s_hi; i += LOUD_THREADS)
+            if (!finite(dst[i - s_lo])) dst[i - s_lo] = 0.0f;
+    }
+    __syncthreads();
+    double k[10];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) k[i] = __longlong_as_double((long long)kweight_bits[rq.rate][i]);
+    const double* __restrict__ P = powers + (long)rq.rate * LOUD_POWERS * 16;  // P + 16 o = A^(run o)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long lo = (long)threadIdx.x * run < T ? (long)threadIdx.x * run : T, hi = lo + run < T ? lo + run : T;
+    // first pass, from zero state: q of the lane, then the inclusive scan inside the wave
+    KwState incl{0.0, 0.0, 0.0, 0.0};
+    (void)kw_run(xs, lo, hi, T, k, incl);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const KwState up{__shfl_up(incl.v1, o), __shfl_up(incl.v2, o), __shfl_up(incl.w1, o), __shfl_up(incl.w2, o)};
+        if (lane >= o) kw_apply(incl, P + 16 * o, up);
+    }
+    if (lane == 63) {
+        wave_state[wave][0] = incl.v1, wave_state[wave][1] = incl.v2, wave_state[wave][2] = incl.w1, wave_state[wave][3] = incl.w2;
+    }
+    // the lane's start state inside its wave: the end state of the lane before it
+    KwState start{__shfl_up(incl.v1, 1), __shfl_up(incl.v2, 1), __shfl_up(incl.w1, 1), __shfl_up(incl.w2, 1)};
+    if (lane == 0) start = KwState{0.0, 0.0, 0.0, 0.0};
+    __syncthreads();
+    // the state the wave starts from: c_0 = 0, c_(w+1) = A^(64 run) c_w + the end state of wave w alone; it reaches the lane through A^(run lane)
+    KwState carry{0.0, 0.0, 0.0, 0.0};
+    for (int w = 0; w < wave; ++w) {
+        KwState next{wave_state[w][0], wave_state[w][1], wave_state[w][2], wave_state[w][3]};
+        kw_apply(next, P + 16 * 64, carry);
+        carry = next;
+    }
+    kw_apply(start, P + 16 * lane, carry);
+    // second pass, from the true state: the energy of the hop's samples
+    double acc = kw_run(xs, lo, hi, W, k, start);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+    if (lane == 0) wave_sum[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < LOUD_THREADS / 64; ++w) acc += wave_sum[w];
+        hops[(long)blockIdx.y * max_hops + blockIdx.x] = acc;
+    }
+}
+// request_loudness_gain_kernel: one wave per metered request.  It reduces the peak partials as request_gain_kernel does, forms the
+// 400 ms block means z_j from the hop energies, applies the two gates in the energy domain, every lane over j = lane, lane + 64, ..
+// and the wave with a __shfl_xor tree (a fixed order: the same bits run to run), and stores {f64(p), g} into the request's slot of the
+// levels block and {I, f64(n_g)} into the loudness block behind it.
+__device__ __forceinline__ void loud_gate(const double* __restrict__ e, long J, double scale, double floor_, double& sum, int& count) {
+    double s = 0.0;
+    int c = 0;
+    for (long j = threadIdx.x; j < J; j += 64) {
+        const double z = (e[j] + e[j + 1] + e[j + 2] + e[j + 3]) / scale;
+        if (z > LOUD_ABS_GATE && z > floor_) s += z, c += 1;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o), c += __shfl_xor(c, o);
+    sum = s, count = c;
+}
+__global__ __launch_bounds__(64) void request_loudness_gain_kernel(const PackReq* __restrict__ reqs, const LoudSpec* __restrict__ specs,
+                                                                   const uint32_t* __restrict__ partials, long windows,
+                                                                   const double* __restrict__ hops, long max_hops,
+                                                                   double* __restrict__ levels, double* __restrict__ loud) {
+    const int r = blockIdx.x;
+    const LoudSpec ls = specs[r];
+    if (ls.mode == LOUD_NONE) return;  // (the whole wave: its slot is request_gain_kernel's)
+    const long n = (reqs[r].n_samples + LEVEL_WINDOW - 1) / LEVEL_WINDOW;
+    uint32_t m = 0;
+    for (long w = threadIdx.x; w < n; w += 64) {
+        const uint32_t v = partials[(long)r * windows + w];
+        m = v > m ? v : m;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const uint32_t v = (uint32_t)__shfl_xor((int)m, o);
+        m = v > m ? v : m;
+    }
+    const long hop = loud_hop(reqs[r].rate), J = reqs[r].n_samples / hop - 3;  // (J < 1: no block, nothing of the table is read)
+    const double* __restrict__ e = hops + (long)r * max_hops;
+    const double scale = 4.0 * (double)hop;
+    double s1, s2 = 0.0;
+    int c1, c2 = 0;
+    loud_gate(e, J, scale, 0.0, s1, c1);
+    if (c1 > 0) loud_gate(e, J, scale, 0.1 * (s1 / (double)c1), s2, c2);
+    if (threadIdx.x != 0) return;
+    const double I = c2 > 0 ? -0.691 + 10.0 * log10(s2 / (double)c2) : __longlong_as_double(0x7FF8000000000000LL);
+    const double p = (double)__uint_as_float(m), peak = (double)ls.peak;
+    const bool usable = m > 0u && m < 0x7F800000u;
+    double g = 1.0;
+    if (ls.mode == LOUD_NORMALIZE) {
+        if (c2 > 0) g = pow(10.0, ((double)ls.target_lufs - I) / 20.0);
+        if (usable && g * p > peak) g = peak / p;
+    }
+    levels[2 * r] = p;
+    levels[2 * r + 1] = g;
+    loud[2 * r] = I;
+    loud[2 * r + 1] = (double)c2;
+}
+
 // ---- output sample rates: a request's whole stream through a polyphase FIR, before the packer -----------------------------
 // For rate code c the ratio is L / M ((1, 3), (2, 3), (2, 1)), C = 24 max(L, M), N = 2 C + 1 taps h (resample_taps.h), and
 //     y[n] = f32( sum over j ascending, 0 <= j < S, 0 <= n M - j L + C < N, of f64(h[n M - j L + C]) * f64(x[j]) )
@@ -406,7 +583,9 @@ __global__ __launch_bounds__(RS_THREADS) void resample_requests_joined_kernel(co
 // some request carries a rate code, then the packer.  d_y: plan.y_floats floats (may be null when that is 0); out: 16-byte aligned,
 // plan.total_bytes long.  The joined form of the two kernels runs only when the plan says so (OutputPlan::joined).  A measured
 // plan (OutputPlan::measured): between the resampler and the packer the peak pass and the gain kernel, which stores every
-// request's {p, g} at out + plan.levels_off; the levelled packer runs only when some spec is not the plain one.
+// request's {p, g} at out + plan.levels_off; the levelled packer runs only when some spec is not the plain one.  A plan with
+// loudness (OutputPlan::loud): the meter behind the peak pass, its gain kernel behind request_gain_kernel, {I, n_g} of every
+// metered request at out + plan.loud_off; a plan without loudness launches neither.
 void launch_pack_plan(const float* audio, long audio_ld, const OutputPlan& plan, const OutputTables& t, float* d_y, void* out,
                       hipStream_t s) {
     if (plan.max_units <= 0 && !plan.measured) return;
@@ -418,6 +597,13 @@ void launch_pack_plan(const float* audio, long audio_ld, const OutputPlan& plan,
     if (plan.measured) {
         KX_REQUIRE(t.level && t.peak && plan.level.size() == R && (plan.levels_off & 7) == 0, "levels: bad launch argument");
         KX_HIP(hipMemcpyAsync(t.level, plan.level.data(), R * sizeof(LevelSpec), hipMemcpyHostToDevice, s));
+    }
+    const bool loud = !plan.loud.empty();
+    if (loud) {
+        KX_REQUIRE(t.loud && t.loud_pow && (t.hops || plan.max_hops == 0) && plan.loud.size() == R && plan.loud_off == plan.levels_off + 16 * (long)R,
+                   "loudness: bad launch argument");
+        KX_HIP(hipMemcpyAsync(t.loud, plan.loud.data(), R * sizeof(LoudSpec), hipMemcpyHostToDevice, s));
+        KX_HIP(hipMemcpyAsync(t.loud_pow, loud_powers(), (size_t)4 * LOUD_POWERS * 16 * sizeof(double), hipMemcpyHostToDevice, s));
     }
     if (plan.y_floats > 0) {
         KX_REQUIRE(d_y != nullptr, "pack: no buffer for the resampled streams");
@@ -435,8 +621,22 @@ void launch_pack_plan(const float* audio, long audio_ld, const OutputPlan& plan,
                                t.req, t.cum, plan.joined ? t.join : nullptr, d_y, t.peak, plan.peak_windows);
             KX_HIP(hipGetLastError());
         }
-        hipLaunchKernelGGL(request_gain_kernel, dim3((unsigned)R), dim3(64), 0, s, t.req, t.level, t.peak, plan.peak_windows, levels);
-        KX_HIP(hipGetLastError());
+        if (loud && plan.max_hops > 0) {
+            hipLaunchKernelGGL(request_loudness_kernel, dim3((unsigned)plan.max_hops, (unsigned)R), dim3(LOUD_THREADS), 0, s, audio, audio_ld,
+                               t.req, t.cum, plan.joined ? t.join : nullptr, d_y, t.loud, t.loud_pow, t.hops, plan.max_hops);
+            KX_HIP(hipGetLastError());
+        }
+        // (a metered request's {p, g} slot is the loudness gain kernel's: request_gain_kernel, which runs only when some request is
+        // not metered, leaves the plain spec's {p, 1} there and the later kernel of the same stream stores the request's own)
+        if (!plan.loud_all) {
+            hipLaunchKernelGGL(request_gain_kernel, dim3((unsigned)R), dim3(64), 0, s, t.req, t.level, t.peak, plan.peak_windows, levels);
+            KX_HIP(hipGetLastError());
+        }
+        if (loud) {
+            hipLaunchKernelGGL(request_loudness_gain_kernel, dim3((unsigned)R), dim3(64), 0, s, t.req, t.loud, t.peak, plan.peak_windows,
+                               t.hops, plan.max_hops, levels, reinterpret_cast<double*>(static_cast<char*>(out) + plan.loud_off));
+            KX_HIP(hipGetLastError());
+        }
     }
     if (plan.max_units <= 0) return;  // (a measured plan of empty requests: its levels are written, there is no body)
     const dim3 grid((unsigned)((plan.max_units + PACK_THREADS - 1) / PACK_THREADS), (unsigned)R);
@@ -517,7 +717,8 @@ void launch_token_marks(const int* dur, const int* lens, const OutputPlan& plan,
 
 // The output stage of a call whose plan is built, for the model and for the test hook alike: the bodies into d_packed, and the
 // marks of the requests that want them in their block behind the bodies (8-aligned), and behind those the levels of a measured
-// plan, so one copy to the host brings all three.  The order is resampler, peak, gain, packer, marks.
+// plan (and behind those the loudness of a plan that has it), so one copy to the host brings them all.  The order is resampler,
+// peak, loudness, gain, packer, marks.
 void launch_output_plan(const float* audio, long audio_ld, const int* dur, const int* lens, const OutputPlan& plan,
                         const OutputTables& t, float* d_y, void* d_packed, hipStream_t s) {
     launch_pack_plan(audio, audio_ld, plan, t, d_y, d_packed, s);

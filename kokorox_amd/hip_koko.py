@@ -35,6 +35,11 @@ JOIN_NONE = (0, 0, 0, 0)
 LEVEL_GAIN, LEVEL_NORMALIZE, LEVEL_CEILING = 0, 1, 2
 LEVEL_DTYPE = np.dtype([("mode", "<u4"), ("gain", "<f4"), ("peak", "<f4")])
 LEVEL_PLAIN = (LEVEL_GAIN, 1.0, 0.0)
+# loudness (include/kokorox_hip.h, "loudness"): a spec is (mode, target_lufs, peak), the layout of kx_loudness
+LOUDNESS_MEASURE, LOUDNESS_NORMALIZE = 0, 1
+LOUDNESS_DTYPE = np.dtype([("mode", "<u4"), ("target_lufs", "<f4"), ("peak", "<f4")])
+LOUDNESS_METER = (LOUDNESS_MEASURE, 0.0, 0.0)
+LOUDNESS_NONE = (0xFFFFFFFF, 0.0, 0.0)  # the test hook only: a request beside metered ones that is not metered
 KX_OK, KX_ERR_INVALID, KX_ERR_IO, KX_ERR_DEVICE, KX_ERR_STATE = 0, 1, 2, 3, 4  # include/kokorox_hip.h
 KX_FLAG_NOISE_OFF = 1
 KX_FLAG_TAPS = 2
@@ -137,6 +142,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                              vp, vp, vp, i32, vp, i32, vp]),
         "kx_dispatcher_submit_request_levelled": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
                                                         C.POINTER(i64), vp, vp, vp, vp, vp, cp, sz]),
+        "kx_loudness_filter": (i32, [i32, vp]),
+        "kx_infer_requests_loudness": (i32, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, u64, u32, vp, i32, C.POINTER(vp), vp, vp,
+                                             vp, vp, vp, i32, vp, i32, vp]),
+        "kx_dispatcher_submit_request_loudness": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
+                                                        C.POINTER(i64), vp, vp, vp, vp, vp, cp, sz]),
         "kx_dispatcher_create": (vp, [vp, i32, i32, i32, cp, sz]),
         "kx_dispatcher_create_warm": (vp, [vp, i32, i32, i32, i32, i32, cp, sz]),
         "kx_dispatcher_submit": (i32, [vp, vp, i32, vp, f32, u64, C.POINTER(C.POINTER(f32)), C.POINTER(i64), cp, sz]),
@@ -195,6 +205,8 @@ def load_test_library() -> C.CDLL:
         "kx_test_output_plan": (i32, [i32, vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, cp, sz]),
         "kx_test_output_plan_levelled": (i32, [i32, vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp,
                                                cp, sz]),
+        "kx_test_output_plan_loudness": (i32, [i32, vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp,
+                                               vp, vp, vp, i64, vp, cp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -206,7 +218,7 @@ def load_test_library() -> C.CDLL:
 
 TEST_ABI_SYMBOLS = ["kx_test_conv1d", "kx_test_lstm", "kx_test_source", "kx_test_attention", "kx_test_conv1d_epilogue", "kx_test_conv1d_full",
                     "kx_test_conv_transpose", "kx_test_lstm_fault", "kx_test_lstm_parts", "kx_test_conv_plan", "kx_test_conv1d_opts",
-                    "kx_test_layernorm", "kx_test_instance_norm", "kx_test_output_plan", "kx_test_output_plan_levelled"]
+                    "kx_test_layernorm", "kx_test_instance_norm", "kx_test_output_plan", "kx_test_output_plan_levelled", "kx_test_output_plan_loudness"]
 
 ABI_SYMBOLS = [
     "kx_version", "kx_init", "kx_create", "kx_import_onnx", "kx_resample_filter", "kx_create_from_device_blob", "kx_create_replicas", "kx_replicas_times", "kx_create_partition", "kx_destroy",
@@ -214,7 +226,7 @@ ABI_SYMBOLS = [
     "kx_free_audio", "kx_infer_device", "kx_sync", "kx_set_pinned_durations", "kx_warmup", "kx_arena_bytes", "kx_call_times", "kx_model_status", "kx_model_info", "kx_dispatcher_health", "kx_set_utterance_base", "kx_set_lanes",
     "kx_set_conv_mode", "kx_get_conv_mode", "kx_set_stft_variant", "kx_get_stft_variant",
     "kx_profile_enable", "kx_profile_read", "kx_profile_detail", "kx_profile_aux", "kx_diag_enable", "kx_diag_count", "kx_diag_get", "kx_set_act_prescale", "kx_set_voice_table", "kx_infer_voices",
-    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_infer_requests_levelled", "kx_dispatcher_submit_request_levelled", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
+    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_infer_requests_levelled", "kx_dispatcher_submit_request_levelled", "kx_loudness_filter", "kx_infer_requests_loudness", "kx_dispatcher_submit_request_loudness", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
     "kx_dispatcher_stats", "kx_dispatcher_failures", "kx_dispatcher_destroy", "kx_debug_tap",
 ]
 
@@ -255,6 +267,31 @@ def level_specs(levels, n=None) -> np.ndarray:
     if n is not None and a.shape[0] != n:
         raise ValueError(f"{n} level specs are required")
     return a
+
+
+def loudness_specs(loudness, n=None) -> np.ndarray:
+    """Loudness specs as the array of kx_loudness the library takes: one (mode, target_lufs, peak) tuple, a list of them, or an
+    array of LOUDNESS_DTYPE already.  n: the count expected (a single tuple is repeated)."""
+    if isinstance(loudness, np.ndarray) and loudness.dtype == LOUDNESS_DTYPE:
+        a = np.ascontiguousarray(loudness).reshape(-1)
+    else:
+        ld = list(loudness)
+        if ld and not isinstance(ld[0], (tuple, list, np.void)):
+            ld = [tuple(ld)] * (n or 1)
+        a = np.array([(int(m), float(t), float(p)) for m, t, p in ld], dtype=LOUDNESS_DTYPE)
+    if n is not None and a.shape[0] != n:
+        raise ValueError(f"{n} loudness specs are required")
+    return a
+
+
+def loudness_filter(word: int) -> np.ndarray:
+    """The ten float64 K-weighting coefficients of a format word's rate from the library's one table (kx_loudness_filter; host
+    only, no GPU): shelf b0 b1 b2 a1 a2, then high-pass b0 b1 b2 a1 a2."""
+    out = np.zeros(10, dtype=np.float64)
+    rc = load_library().kx_loudness_filter(int(word), _ptr(out))
+    if rc != KX_OK:
+        raise KokoroxHipError(rc, "unknown output format or sample rate")
+    return out
 
 
 def resample_filter(word: int):
@@ -497,8 +534,23 @@ class HipKoko:
         out = (res, mk, out_lv) if marks else (res, out_lv)
         return out + (nsamp,) if with_samples else out
 
+    def infer_requests_loudness(self, tokens, chunks_per_request, loudness, joins=None, styles=None, voice_ids=None, weights=None,
+                                speeds=(1.0,), seed: int = 0, flags: int = 0, fmt=0, marks: bool = False, with_samples: bool = False):
+        """infer_requests with the integrated loudness of every request measured, and set, on the GPU (kx_infer_requests_loudness;
+        the definition is in include/kokorox_hip.h, "loudness", the numpy form voices.integrated_loudness / voices.loudness_gain):
+        `loudness` = one spec (mode, target_lufs, peak) for all requests, or a list of one per request; `joins` as
+        infer_requests_joined, or None.  Returns (bodies, loudness) with loudness a float64 array [R, 4] = the peak p, the gain g,
+        the integrated loudness I in LUFS (NaN when undefined) and the number of gated blocks n_g of every request as the GPU
+        computed them; marks=True: (bodies, marks, loudness).  with_samples: out_samples as a last entry.  LOUDNESS_METER measures."""
+        ld = loudness_specs(loudness)
+        j = None if joins is None else join_specs(joins)
+        res, mk, nsamp, out_ld = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, marks,
+                                                      j, None, ld)
+        out = (res, mk, out_ld) if marks else (res, out_ld)
+        return out + (nsamp,) if with_samples else out
+
     def _infer_requests(self, tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, want_marks, joins=None,
-                        levels=None):
+                        levels=None, loudness=None):
         ids, lens = self._ids_lens(tokens)
         B = len(tokens)
         cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32).reshape(-1)
@@ -520,7 +572,12 @@ class HipKoko:
         marks = None
         if want_marks:
             mk, n_mk = C.c_void_p(), np.zeros(max(R, 1), np.int64)
-        if levels is not None:
+        if loudness is not None:
+            out_lv = np.zeros((max(R, 1), 4), np.float64)
+            self._check(self._lib.kx_infer_requests_loudness(*args, C.byref(mk) if want_marks else None, _ptr(n_mk) if want_marks else None,
+                                                             _ptr(joins), 0 if joins is None else joins.shape[0], _ptr(loudness),
+                                                             loudness.shape[0], _ptr(out_lv)))
+        elif levels is not None:
             out_lv = np.zeros((max(R, 1), 2), np.float64)
             self._check(self._lib.kx_infer_requests_levelled(*args, C.byref(mk) if want_marks else None, _ptr(n_mk) if want_marks else None,
                                                              _ptr(joins), 0 if joins is None else joins.shape[0], _ptr(levels),
@@ -547,7 +604,7 @@ class HipKoko:
             part = raw[o: o + int(nbytes[r])]
             o += int(nbytes[r])
             res.append(_decode_packed(part, int(fm[r if fm.shape[0] > 1 else 0])))
-        if levels is not None:
+        if levels is not None or loudness is not None:
             return res, marks, [int(v) for v in nsamp[:R]], out_lv[:R]
         return res, marks, [int(v) for v in nsamp[:R]]
 
@@ -763,7 +820,7 @@ class Dispatcher:
         return arr.reshape(-1, 2) if fmt == 1 else arr
 
     def submit_request(self, chunks: Sequence[Sequence[int]], styles=None, voices=None, speed: float = 1.0, seed: int = 0,
-                       fmt: int = 0, marks: bool = False, join=None, level=None):
+                       fmt: int = 0, marks: bool = False, join=None, level=None, loudness=None):
         """A request of 1 .. max_batch chunks (kx_dispatcher_submit_request): `chunks` = the 0-wrapped id lists; `styles` = one
         256-float row per chunk, OR `voices` as in submit_ex (one voice spec for the request); `fmt` = a format word (a PACK_*
         form, optionally | PACK_RATE_*).  Returns what HipKoko.infer_requests returns for one request: an array (forms 0..2, 8, 9)
@@ -771,7 +828,9 @@ class Dispatcher:
         request's token marks as one int64 array (HipKoko.infer_requests_marks).  join = (flags, keep_ms, pause_ms, fade_ms)
         (kx_dispatcher_submit_request_joined): the request's seams shaped as HipKoko.infer_requests_joined shapes them.
         level = (mode, gain, peak) (kx_dispatcher_submit_request_levelled): the request's level set as
-        HipKoko.infer_requests_levelled sets it; the result then ends with a float64 pair, the request's peak p and gain g."""
+        HipKoko.infer_requests_levelled sets it; the result then ends with a float64 pair, the request's peak p and gain g.
+        loudness = (mode, target_lufs, peak) (kx_dispatcher_submit_request_loudness): the request's loudness measured and set as
+        HipKoko.infer_requests_loudness does; the result then ends with four float64 values, p, g, I and n_g."""
         lens = np.array([len(c) for c in chunks], dtype=np.int32)
         a = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.int64).reshape(-1) for c in chunks])
                                  if len(chunks) else np.zeros(0, np.int64))
@@ -795,7 +854,14 @@ class Dispatcher:
                 C.byref(nb), C.byref(ns))
         mk, n_mk = C.c_void_p(), C.c_int64(0)
         lv_out = np.zeros(2, np.float64)
-        if level is not None:
+        ld_out = np.zeros(4, np.float64)
+        if loudness is not None and level is not None:
+            raise ValueError("submit_request: a request has a level or a loudness, not both")
+        if loudness is not None:
+            j = None if join is None else join_specs(join, 1)
+            rc = self._lib.kx_dispatcher_submit_request_loudness(*args, C.byref(mk) if marks else None, C.byref(n_mk) if marks else None,
+                                                                 _ptr(j), _ptr(loudness_specs(loudness, 1)), _ptr(ld_out), err, len(err))
+        elif level is not None:
             j = None if join is None else join_specs(join, 1)
             rc = self._lib.kx_dispatcher_submit_request_levelled(*args, C.byref(mk) if marks else None, C.byref(n_mk) if marks else None,
                                                                  _ptr(j), _ptr(level_specs(level, 1)), _ptr(lv_out), err, len(err))
@@ -819,6 +885,7 @@ class Dispatcher:
             self._lib.kx_free_packed(out)
         res = (_decode_packed(raw, fmt), m) if marks else (_decode_packed(raw, fmt),)
         res = res + (lv_out,) if level is not None else res
+        res = res + (ld_out,) if loudness is not None else res
         return res if len(res) > 1 else res[0]
 
     def stats(self):
@@ -1070,10 +1137,12 @@ def harmonic_source(f0, lin_w, lin_b, seed=0, utt_base=0, noise_off=False, devic
     return out
 
 
-def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, want, pauses, device, levels=None):
+def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, want, pauses, device, levels=None, loudness=None):
     """kx_test_output_plan, the one hook of the output stage: the model's planner and launcher on host arrays (None where the
     hook takes a null pointer; include/kokorox_hip_test.h).  Returns (bodies as bytes, out_samples, marks as int64 arrays).
-    levels (an array of LEVEL_DTYPE, [R]): kx_test_output_plan_levelled, and a fourth entry, the levels as float64 [R, 2]."""
+    levels (an array of LEVEL_DTYPE, [R]): kx_test_output_plan_levelled, and a fourth entry, the levels as float64 [R, 2].
+    loudness (an array of LOUDNESS_DTYPE, [R]; levels may then be None): kx_test_output_plan_loudness, and the fourth entry is
+    the pair (loudness as float64 [R, 4] = p, g, I, n_g; the hop energies e[k] of every request as one float64 array each)."""
     lib = load_test_library()
     B = len(frames if dur is None else lens)
     fm = np.ascontiguousarray(formats, dtype=np.int32)
@@ -1100,7 +1169,15 @@ def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, w
     nb, ns, nm = np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int64)
     args = (device, _ptr(audio), B, ld, _ptr(fr), _ptr(dur), _ptr(ln), _ptr(cpr), R, _ptr(fm), _ptr(joins), _ptr(wt),
             _ptr(out) if audio is not None else None, cap, _ptr(nb), _ptr(ns), _ptr(mk), mcap, _ptr(nm))
-    if levels is None:
+    if loudness is not None:
+        assert loudness.dtype == LOUDNESS_DTYPE and loudness.shape == (R,) and (levels is None or (levels.dtype == LEVEL_DTYPE and levels.shape == (R,)))
+        out_lv = np.zeros((R, 2), dtype=np.float64)
+        out_ld = np.full((R, 4), -1.0, dtype=np.float64)
+        hcap = (600 * n_frames + pauses) // 1200 + 1  # (a hop is 100 ms: 2400 samples of the model, 1200 if everything ran at 48 kHz)
+        hops, n_hops = np.zeros((R, hcap), dtype=np.float64), np.zeros(R, dtype=np.int64)
+        _err_call(lib.kx_test_output_plan_loudness, *args, _ptr(levels), _ptr(out_lv) if levels is not None else None, _ptr(loudness),
+                  _ptr(out_ld), _ptr(hops), hcap, _ptr(n_hops))
+    elif levels is None:
         _err_call(lib.kx_test_output_plan, *args)
     else:
         assert levels.dtype == LEVEL_DTYPE and levels.shape == (R,)
@@ -1111,6 +1188,8 @@ def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, w
         res.append(raw[o: o + int(nb[r])] if audio is not None else b"")
         o += int(nb[r])
     marks = [m.copy() for m in np.split(mk[: int(nm.sum())], np.cumsum(nm)[:-1])]
+    if loudness is not None:
+        return res, [int(v) for v in ns], marks, (out_ld, [hops[r, : int(n_hops[r])].copy() for r in range(R)])
     if levels is not None:
         return res, [int(v) for v in ns], marks, out_lv
     return res, [int(v) for v in ns], marks
@@ -1157,3 +1236,18 @@ def level_requests(audio, dur, lens, chunks_per_request, formats, levels, joins=
     j = None if joins is None else join_specs(joins, R)
     pauses = 0 if j is None else sum(24 * int(j["pause_ms"][r]) * (int(chunks_per_request[r]) - 1) for r in range(R))
     return _output_plan(audio, frames, dur, lens, chunks_per_request, formats, j, want, pauses, device, lv)
+
+
+def loudness_requests(audio, dur, lens, chunks_per_request, formats, loudness, joins=None, want=None, frames=None, levels=None, device=0):
+    """Metered requests alone (kx_test_output_plan_loudness): everything as level_requests takes it, loudness = one (mode,
+    target_lufs, peak) spec per request, LOUDNESS_NONE for a request that is not metered (its level spec, if `levels` is given,
+    then applies; a metered request's level spec is the plain one).  Returns (bodies as bytes, out_samples, marks, loudness as
+    float64 [R, 4] = p, g, I and n_g of every request, the hop energies e[k] of every request): voices.loudness_body,
+    voices.integrated_loudness, voices.loudness_gain and voices.hop_energies."""
+    R = len(lens if dur is not None else frames) if chunks_per_request is None else len(chunks_per_request)
+    ld = loudness_specs(loudness, R)
+    lv = None if levels is None else level_specs(levels, R)
+    j = None if joins is None else join_specs(joins, R)
+    pauses = 0 if j is None else sum(24 * int(j["pause_ms"][r]) * (int(chunks_per_request[r]) - 1) for r in range(R))
+    res, ns, marks, (out_ld, hops) = _output_plan(audio, frames, dur, lens, chunks_per_request, formats, j, want, pauses, device, lv, ld)
+    return res, ns, marks, out_ld, hops

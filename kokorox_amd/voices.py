@@ -349,6 +349,113 @@ def levelled_body(chunks_samples, durations_per_chunk: Sequence[Sequence[int]], 
     return stream_body(level_stream(resample_stream(join_stream(chunks_samples, durations_per_chunk, join), word), level), word)
 
 
+LOUDNESS_MEASURE, LOUDNESS_NORMALIZE = 0, 1
+LOUDNESS_METER = (LOUDNESS_MEASURE, 0.0, 0.0)
+LOUDNESS_ABS_GATE = 10.0 ** ((-70 + 0.691) / 10)  # the absolute gate of BS.1770 as a block energy
+_RATE_WORD = {24000: 0x000, 8000: 0x100, 16000: 0x200, 48000: 0x300}
+
+
+def kweight_coefs(rate: int) -> np.ndarray:
+    """The ten float64 K-weighting coefficients at an output rate (24000, 8000, 16000 or 48000 Hz) from the library's one table
+    (kokorox_amd/csrc/kweight_coefs.h through kx_loudness_filter): shelf b0 b1 b2 a1 a2, then high-pass b0 b1 b2 a1 a2."""
+    from . import hip_koko as hk
+    if int(rate) not in _RATE_WORD:
+        raise ValueError("kweight_coefs: the rate is 24000, 8000, 16000 or 48000")
+    return hk.loudness_filter(_RATE_WORD[int(rate)])
+
+
+def kweight(x, rate: int) -> np.ndarray:
+    """The K-weighted stream w of include/kokorox_hip.h, "loudness", in float64: x[n] = f64(z[n]) where z[n] is finite, else 0;
+    two biquads in direct form I, shelf first, then high-pass, from zero state, one sample after the other."""
+    z = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    xs = np.where(np.isfinite(z), z, np.float32(0)).astype(np.float64).tolist()
+    b0, b1, b2, a1, a2, c0, c1, c2, d1, d2 = (float(v) for v in kweight_coefs(rate))
+    x1 = x2 = v1 = v2 = w1 = w2 = 0.0
+    out = [0.0] * len(xs)
+    for n, xn in enumerate(xs):
+        v = b0 * xn + b1 * x1 + b2 * x2 - a1 * v1 - a2 * v2
+        w = c0 * v + c1 * v1 + c2 * v2 - d1 * w1 - d2 * w2
+        x2, x1, v2, v1, w2, w1 = x1, xn, v1, v, w1, w
+        out[n] = w
+    return np.array(out, dtype=np.float64)
+
+
+def hop_energies(z, rate: int) -> np.ndarray:
+    """e[k] = the sum of w[n]^2 over hop k of rate / 10 samples, k < floor(N / hop): a trailing partial hop is ignored."""
+    w = kweight(z, rate)
+    hop = int(rate) // 10
+    H = w.shape[0] // hop
+    return (w[: H * hop].reshape(H, hop) ** 2).sum(axis=1) if H else np.zeros(0, dtype=np.float64)
+
+
+def gated_loudness(e, rate: int):
+    """(I, n_g, margin) from the hop energies e: the 400 ms block means z_j = (e[j] + e[j+1] + e[j+2] + e[j+3]) / (4 hop), the
+    absolute gate z_j > 10^((-70 + 0.691) / 10), the relative gate z_j > 0.1 m1 with m1 the mean over the absolute gate's blocks,
+    I = -0.691 + 10 log10(the mean over the n_g blocks that pass both), NaN when there is no such block.  margin = the smallest
+    relative distance |z_j - t| / t of any block to either threshold t (inf when there is no block): an input whose margin is
+    large against the rounding of e has the same n_g on every implementation."""
+    e = np.asarray(e, dtype=np.float64).reshape(-1)
+    hop = int(rate) // 10
+    J = e.shape[0] - 3
+    if J < 1:
+        return float("nan"), 0, float("inf")
+    zj = (((e[0:J] + e[1:J + 1]) + e[2:J + 2]) + e[3:J + 3]) / (4.0 * hop)
+    margin = float(np.min(np.abs(zj - LOUDNESS_ABS_GATE) / LOUDNESS_ABS_GATE))
+    above = zj > LOUDNESS_ABS_GATE
+    if not above.any():
+        return float("nan"), 0, margin
+    floor = 0.1 * (float(zj[above].sum()) / int(above.sum()))
+    margin = min(margin, float(np.min(np.abs(zj - floor) / floor)))
+    both = above & (zj > floor)
+    n_g = int(both.sum())
+    if n_g == 0:
+        return float("nan"), 0, margin
+    return -0.691 + 10.0 * float(np.log10(float(zj[both].sum()) / n_g)), n_g, margin
+
+
+def integrated_loudness(z, rate: int):
+    """(I, n_g, margin) of ONE request's stream z, which is at the output rate `rate` already: gated_loudness of hop_energies."""
+    return gated_loudness(hop_energies(z, rate), rate)
+
+
+def _loudness_fields(loudness):
+    """(mode, target_lufs, peak) of a valid loudness spec (include/kokorox_hip.h, "loudness"), the two floats as float32; None =
+    the meter.  Every comparison is written so that a NaN fails it."""
+    mode, target, peak = loudness if loudness is not None else LOUDNESS_METER
+    with np.errstate(over="ignore", invalid="ignore"):
+        target, peak = np.float32(target), np.float32(peak)
+    ok = isinstance(mode, (int, np.integer)) and not isinstance(mode, bool) and mode in (0, 1)
+    if ok and mode == LOUDNESS_MEASURE:
+        ok = target.tobytes() == np.float32(0).tobytes() and peak.tobytes() == np.float32(0).tobytes()
+    elif ok:
+        ok = bool(np.float32(-70) <= target <= np.float32(0)) and bool(np.float32(2.0 ** -15) <= peak <= np.float32(1))
+    if not ok:
+        raise ValueError("loudness: mode 0 with target and peak +0, or mode 1 with -70 <= target_lufs <= 0 and 2^-15 <= peak <= 1")
+    return int(mode), target, peak
+
+
+def loudness_gain(p, I, loudness) -> float:
+    """The float64 gain of a loudness spec for a stream of peak p (level_gain's) and integrated loudness I: 1 for the meter;
+    10^((target - I) / 20) when I is defined, else 1, and then peak / p where p is usable and g p would pass peak."""
+    mode, target, peak = _loudness_fields(loudness)
+    p = np.float32(p)
+    g = np.float64(1.0)
+    if mode == LOUDNESS_NORMALIZE:
+        if not np.isnan(I):
+            g = np.float64(10.0) ** ((np.float64(target) - np.float64(I)) / np.float64(20.0))
+        if bool(np.float32(0) < p < np.float32(np.inf)) and g * np.float64(p) > np.float64(peak):
+            g = np.float64(peak) / np.float64(p)
+    return float(g)
+
+
+def loudness_body(z, g: float, word: int) -> bytes:
+    """The body of a request whose stream z (at the word's rate) is scaled by the gain g: z'[n] = f32(g f64(z[n])), one float64
+    product and one rounding per sample as in level_stream, then the form of `word`."""
+    z = np.ascontiguousarray(z, dtype=np.float32).reshape(-1)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        return stream_body((np.float64(g) * z.astype(np.float64)).astype(np.float32), word)
+
+
 def stream_body(y, word: int) -> bytes:
     """The form of a format word applied to a request's stream `y`, which is at the word's rate already, as bytes."""
     y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1)
@@ -402,13 +509,14 @@ def word_spans(spans, words: Sequence[Sequence[int]]):
 
 
 def tts_request(model, styles: Dict[str, np.ndarray], style_name: str, chunk_tokens: Sequence[Sequence[int]],
-                speed: float = 1.0, initial_silence: int = 0, seed: int = 0, fmt: int = 0, join=None, level=None):
+                speed: float = 1.0, initial_silence: int = 0, seed: int = 0, fmt: int = 0, join=None, level=None, loudness=None):
     """`tts_chunks` through `model.infer_requests`: the chunks of one text as ONE request of one batched forward, its body
     (header of the form, then the chunks' samples with nothing between them) packed on the GPU.  `fmt` is a format word of
     hip_koko (a PACK_* form, optionally | PACK_RATE_*): 0..2 and 8 / 9 give the samples as an array, 3 (`wav_f32_body`) and 4
     (`wav16_base64`) the bytes a server sends.  `join` = (flags, keep_ms, pause_ms, fade_ms): the seams shaped on the GPU
     (`model.infer_requests_joined`; trim the pads' silence, pause between sentences, fade the cut edges).  `level` = (mode, gain,
-    peak): the level set on the GPU (`model.infer_requests_levelled`; a volume, a peak to normalise to, or a ceiling).  An
+    peak): the level set on the GPU (`model.infer_requests_levelled`; a volume, a peak to normalise to, or a ceiling).
+    `loudness` = (mode, target_lufs, peak): the BS.1770 loudness set on the GPU (`model.infer_requests_loudness`).  An
     empty chunk list and an empty chunk are errors (a request has at least one chunk)."""
     toks, rows = [], []
     for ch in chunk_tokens:
@@ -419,6 +527,11 @@ def tts_request(model, styles: Dict[str, np.ndarray], style_name: str, chunk_tok
         toks.append([0] + t + [0])
     if not toks:
         raise ValueError("tts_request: a request has at least one chunk")
+    if loudness is not None:
+        if level is not None:
+            raise ValueError("tts_request: a request has a level or a loudness, not both")
+        return model.infer_requests_loudness(toks, [len(toks)], loudness, joins=join, styles=np.asarray(rows, dtype=np.float32),
+                                             speeds=[float(speed)], seed=seed, fmt=fmt)[0][0]
     if level is not None:
         return model.infer_requests_levelled(toks, [len(toks)], level, joins=join, styles=np.asarray(rows, dtype=np.float32),
                                              speeds=[float(speed)], seed=seed, fmt=fmt)[0][0]

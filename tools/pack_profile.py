@@ -11,6 +11,9 @@ the command line; an optional second argument is the batch (1 = one utterance). 
                          three kernels (pack_requests_joined_kernel, resample_requests_joined_kernel, token_marks_joined_kernel);
     a word and 'l'       ('2l', '0x108l') kx_infer_requests_levelled, every row a request of its own normalised to a peak of 0.5:
                          request_peak_kernel and request_gain_kernel between resampler and packer, and pack_requests_levelled_kernel;
+    a word and 'd'       ('0x300d') kx_infer_requests_loudness, every row a request of its own normalised to -23 LUFS under a peak of 1:
+                         request_peak_kernel, request_loudness_kernel and request_loudness_gain_kernel between resampler and packer, and
+                         pack_requests_levelled_kernel (no request_gain_kernel: every slot is the loudness gain kernel's);
     a word and 'g'       ('2g') the same grouping without joins (kx_infer_requests_marks): the plain kernels on the same batch.
 Meant to run under the profiler, one mode per run (kernel trace only, no counters in the same run):
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o t -- python tools/pack_profile.py p2
@@ -49,6 +52,12 @@ for it in range(3):
         word = int(which[:-1], 0)
         out, lv = m.infer_requests_levelled(toks, [1] * B, (hk.LEVEL_NORMALIZE, 1.0, 0.5), styles=rows, fmt=word)
         assert lv.shape == (B, 2) and (lv[:, 0] > 0).all() and np.array_equal((lv[:, 0] * lv[:, 1]).astype(np.float32), np.full(B, 0.5, np.float32))
+    elif which.endswith("d"):
+        word = int(which[:-1], 0)
+        out, ld = m.infer_requests_loudness(toks, [1] * B, (hk.LOUDNESS_NORMALIZE, -23.0, 1.0), styles=rows, fmt=word)
+        assert ld.shape == (B, 4) and (ld[:, 3] >= 1).all() and np.isfinite(ld[:, 2]).all()
+        if it == 2:
+            print("loudness of the first request: p %.6g g %.6g I %.6f LUFS n_g %d" % tuple(ld[0]))
     elif which.endswith("m"):
         word = int(which[:-1], 0)
         out, marks = m.infer_requests_marks(toks, [1] * B, styles=rows, fmt=word)
