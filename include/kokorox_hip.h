@@ -196,7 +196,14 @@ int kx_arena_bytes(kx_model* m, int64_t* out3);
  * two MFMA-equivalents per product instead of three, ~17 significant bits per product instead of 22 (measured 1e-5 relative per
  * conv output; the waveform moves by < 1e-5 against mode 1), inside the 1e-4 parity band by the same protocol as modes 0 and 1
  * (tests/test_gpu_forward.py::test_ragged_batch_matches_oracle) and far above the bf16 that BASELINE configs[2] names.  Their
- * snake activation takes sin^2 from the hardware cosine there (3e-6 absolute).  The 8-bit weight images are built at create
+ * snake activation v + sin^2(alpha v) / alpha takes sin^2 from the hardware cosine there, 0.5 - 0.5 v_cos_f32(alpha v / pi): at most
+ * 3e-6 absolute in sin^2 for |alpha v| <= 40 and less towards alpha v = 0, so the activation error sin^2-error / alpha is at most
+ * 6e-6 (3e-6 rms) at alpha = 0.01 and below 1e-6 from alpha = 0.2 up: the mode's 1e-5 per conv output holds, measured, for every
+ * alpha from 0.01 to 20 at O(1) activations.  Argument domain: none that matters.  The ISA documents +-256 turns for the
+ * instruction (|alpha v| = 804), but on gfx950 it reduces any finite argument: the sin^2 error grows smoothly as 7e-8 |alpha v|
+ * (the float32 product alpha v / pi in front of it) through that edge and far beyond -- 6e-5 at 800, 7e-4 at 9000 -- which in the
+ * activation is 7e-8 |v| whatever alpha, and a conv at |alpha v| up to 8800 keeps the error it has at O(1) arguments
+ * (tests/test_gpu_snake_range.py; tools/probes/sin_accuracy.hip).  The 8-bit weight images are built at create
  * (or at the first selection of the mode).
  * 4 = reduced precision, opt-in (env KOKOROX_CONV=f16): the decoder / generator convs of the direct-A kernel issue ONE
  * f16 MFMA per product (weights and activations rounded to f16, f32 accumulation) -- the library's counterpart of the

@@ -490,7 +490,10 @@ __global__ __launch_bounds__(256, (NTT == 8 || S16) ? 2 : 3) void conv1d_f16x3_d
         asm volatile("" : "+v"(xt_));
         if (ACT == ACT_SNAKE && HWC) {
             // f16f8: sin^2 t = 0.5 - 0.5 cos 2t on the hardware cosine (v_cos_f32 takes turns: 2t / 2 pi), max error 3.1e-6 absolute
-            // (tools/probes/sin_accuracy.hip) -- under this mode's 1e-5 per product -- for 5 vector-issue slots instead of 12
+            // for |t| <= 40 (tools/probes/sin_accuracy.hip) -- under this mode's 1e-5 per product -- for 5 vector-issue slots instead of
+            // 12.  Less towards t = 0: the activation's sin^2-error / alpha stays below 6.3e-6 down to alpha = 0.01; beyond |t| = 40 it
+            // grows as 7e-8 |t| (the float32 product in front of the instruction, which reduces any finite argument: no edge at its
+            // documented +-256 turns, |t| = 804) -- tests/test_gpu_snake_range.py, DESIGN.md section 4
             const float al = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, al_rcp_x), cq));
             xz_ = (al * xt_) * 0.318309886183790672f;
         } else if (ACT == ACT_SNAKE) {

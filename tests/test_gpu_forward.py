@@ -55,9 +55,9 @@ def test_ragged_batch_matches_oracle(hip_model, oracle, mode):
         hip_model.set_conv_mode(default_mode)
 
 
-def _ragged_batch_vs_oracle(hip_model, oracle):
+def _ragged_batch_vs_oracle(hip_model, oracle, counts=(21, 9, 14)):
     from kokorox_amd import hip_koko as hk
-    counts = [21, 9, 14]
+    counts = list(counts)
     ids, styles = _inputs(counts)
     outs = hip_model.infer_batch([list(x) for x in ids], styles, [1.0], seed=2, flags=hk.KX_FLAG_TAPS)
     for b in range(len(counts)):
@@ -95,6 +95,44 @@ def _ragged_batch_vs_oracle(hip_model, oracle):
               f"waveform max|d| {wave:.2e}")  # (pytest -s: the figures DESIGN.md section 4 quotes)
         assert wave < TOL_WAVE
         assert np.abs(hip_model.tap("audio", b)[0] - outs[b]).max() == 0.0
+
+
+@pytest.fixture(scope="module")
+def wide_alpha(tmp_path_factory):
+    """The synthetic weights with every snake alpha (the 48 alpha1 / alpha2 tensors of the generator's resblocks) redrawn log-uniform
+    on [0.02, 20] -- the synthetic blob draws U(0.5, 2), and the alphas of real weights are unknown: (HipKoko, KokoroOracle) on it."""
+    from kokorox_amd import hip_koko as hk
+    from kokorox_amd import weights as W
+    from oracle import kokoro_ref as R
+    tensors = W.synthetic_tensors(1234)
+    rng = np.random.default_rng(77)
+    names = [n for n in tensors if ".alpha1." in n or ".alpha2." in n]
+    assert len(names) == 48
+    for n in names:
+        tensors[n] = np.exp(rng.uniform(np.log(0.02), np.log(20.0), tensors[n].shape)).astype(np.float32)
+    path = str(tmp_path_factory.mktemp("wide_alpha") / "wide_alpha.kxw")
+    W.write_blob(path, tensors)
+    del tensors
+    m = hk.HipKoko.new(path)
+    try:
+        yield m, R.KokoroOracle(path)
+    finally:
+        m.close()
+        os.remove(path)
+
+
+@pytest.mark.parametrize("mode", [pytest.param(0, id="f32"), pytest.param(1, id="f16x3"), pytest.param(6, id="f16f8")])
+def test_ragged_batch_matches_oracle_on_wide_alpha(wide_alpha, mode):
+    """The parity protocol, same bands, on weights whose snake alphas span three decades: 1 / alpha multiplies whatever absolute error a
+    form's sin^2 has, and alpha v reaches tens of radians.  (The oracle in float32 against itself in float64 is as close on these
+    weights as on the standard ones: the network is no worse conditioned.)"""
+    model, oracle = wide_alpha
+    default_mode = model.get_conv_mode()
+    model.set_conv_mode(mode)
+    try:
+        _ragged_batch_vs_oracle(model, oracle, counts=[9, 5])
+    finally:
+        model.set_conv_mode(default_mode)
 
 
 def test_golden_vectors(hip_model, golden):
