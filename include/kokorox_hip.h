@@ -109,7 +109,9 @@ int kx_last_error_copy(const kx_model* m, char* buf, size_t buf_len);
  *   lens     [B] tokens per utterance incl. the two pads, 1..512 (3..512 for real text).  The reference is
  *            batch-1 (koko.rs:1175); B>1 gives the same result as B separate calls.
  *   styles   [B,256] float32 voice-style rows (mix_styles, koko.rs:1255-1306)
- *   speeds   [n_speed] float32, n_speed = 1 (shared, ort_koko.rs:67-68) or B
+ *   speeds   [n_speed] float32, n_speed = 1 (shared, ort_koko.rs:67-68) or B; each > 0.  A speed so low that an
+ *            utterance's durations add up to more than 50 frames per token of the call's longest utterance is
+ *            KX_ERR_INVALID, "infer: speed too low for utterance b: ..." (speeds >= 1 never are)
  *   seed     Philox key of the harmonic-source noise; utterance b of the call draws the
  *            stream (seed, utt_base + b)
  *   out      *out = a library-owned (pooled, page-locked) float32 buffer holding the B waveforms back to back;

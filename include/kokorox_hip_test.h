@@ -138,6 +138,54 @@ int kx_test_output_plan_loudness(int device_id, const float* audio, int B, int64
                                  const kx_level* levels, double* out_levels, const kx_loudness* loudness, double* out_loudness,
                                  double* out_hops, int64_t hops_cap, int64_t* out_n_hops, char* err, size_t err_len);
 
+/* The token-axis kernels of Model::front_half, alone.  Common to these hooks: rows padded to a multiple of 32 floats as in the
+ * model, NaN in every input column a kernel must not read, -12345.5 (0xA5 bytes in integer buffers) in every output location it
+ * must not write; what the caller cannot see (row padding, guard regions behind a buffer) the hook checks itself after the launch
+ * and fails with KX_ERR_STATE. */
+
+/* kx_test_lstm on a RAGGED batch: x [B,L,n_in] with utterance b valid for lens[b] steps (the rest is never uploaded: NaN) -> y
+ * [B,L,512], where columns >= lens[b] come back as -12345.5.  The input products start as NaN before the input GEMM (the f32
+ * launch of kx_test_lstm, on the ragged lengths), so a recurrence that reads a step past an utterance's length poisons its output.
+ * inplace = 1 (n_in = 640): the output is rows 0..511 of the 640-row input tensor itself, as Model::lstm is called for the duration
+ * encoder; rows 512..639 must come back as they were.  repeat = n (1..16): n launches on ONE exchange buffer whose launch counter
+ * starts at epoch0 (0..0xffff; 0xfffd with repeat = 4 crosses the 16-bit wrap and the clearing that goes with it), the output reset
+ * between them; the last result is returned, and two launches that differ in a bit are KX_ERR_STATE.  kx_test_lstm_parts selects
+ * the form. */
+int kx_test_lstm_ragged(int device_id, const float* x, const int32_t* lens, int B, int L, int n_in, const float* w_ih,
+                        const float* w_hh, const float* b_ih, const float* b_hh, const float* w_ih_r, const float* w_hh_r,
+                        const float* b_ih_r, const float* b_hh_r, int inplace, int repeat, uint32_t epoch0, float* y, char* err,
+                        size_t err_len);
+
+/* Duration head and alignment: launch_duration on logits [B,50,T] (row b valid for lens[b] tokens), speeds [n_speed] (1 or B),
+ * pinned [n_pinned] (0 = none; each 1..50) with rows of idx_ld frames (the model: 50 T), then launch_gather_cols of src [B,C,T]
+ * over Fmax = max(frames).  Out: dur [B,512] (0xA5 bytes past lens[b]), frames [B], idx [B,idx_ld] (0xA5 bytes past frames[b]),
+ * gathered [B,C,Fcap] (-12345.5 in columns >= frames[b]; Fcap >= Fmax), overflow = the sticky word of duration_kernel (0, or
+ * b + 1 of the first row whose durations did not fit idx_ld).  A frame count or an index outside its row is KX_ERR_STATE, and the
+ * gather is then not launched. */
+int kx_test_alignment(int device_id, const float* logits, int B, int T, const int32_t* lens, const float* speeds, int n_speed,
+                      const int32_t* pinned, int n_pinned, const float* src, int C, int idx_ld, int32_t* dur, int32_t* frames,
+                      int32_t* idx, float* gathered, int Fcap, uint32_t* overflow, char* err, size_t err_len);
+
+/* Both embedding kernels on one id buffer ids [B,ids_stride] (ids_stride >= T; row b valid for lens[b] ids): launch_embed with
+ * text_table [n_vocab,512] -> out_text [B,512,T], launch_albert_embed with word [n_vocab,128], type0 [128], pos [T,128] ->
+ * out_albert [B,128,T]; columns >= lens[b] come back as -12345.5.  bad = the sticky word the two share, as in the model (0, or
+ * (b << 16 | t) + 1 of the first id outside 0..n_vocab-1). */
+int kx_test_embed(int device_id, const int64_t* ids, int B, int ids_stride, int T, const int32_t* lens, const float* text_table,
+                  const float* word, const float* type0, const float* pos, int n_vocab, float* out_text, float* out_albert,
+                  uint32_t* bad, char* err, size_t err_len);
+
+/* The style projections of a call in one launch (launch_style_fc): n_desc descriptors, descriptor i with n_out[i] outputs from
+ * half style_off[i] (0 or 128) of styles [B,256]; w = their [n_out[i],128] weights back to back, bias likewise; out
+ * [B, sum n_out], descriptor i at the offset Model::add_fc gives it (the sum of the n_out before it). */
+int kx_test_style_fc(int device_id, const float* styles, int B, const float* w, const float* bias, const int32_t* n_out,
+                     const int32_t* style_off, int n_desc, float* out, char* err, size_t err_len);
+
+/* Row fills and copies.  launch_fill_style_rows as the duration encoder's input is built: rows 512..639 of fill_out [B,640,T] =
+ * styles[b][128 + k] over lens[b] columns, everything else -12345.5.  launch_copy_rows of src [B,rows,Ls] into copy_out
+ * [B,rows,Ld] (another row stride) over lens[b] mul + add columns of every row, the rest -12345.5. */
+int kx_test_rows(int device_id, const float* styles, const int32_t* lens, int B, int T, float* fill_out, const float* src, int rows,
+                 int Ls, int Ld, int mul, int add, float* copy_out, char* err, size_t err_len);
+
 /* Fault injection for the two-CU LSTM recurrence (process-wide, test only): nth > 0 makes the nth following launch of
  * the pair kernel, and every later one, lose the second half of each pair and poll with a short limit, so the call it
  * belongs to must fail with KX_ERR_DEVICE (the bounded wait's error path) and the model must fall back to the one-CU

@@ -643,6 +643,8 @@ __global__ __launch_bounds__(LstmParts<NQ>::THREADS) void lstm_pair_kernel(const
             if (step + 1 < L) gxv = gxp[(long)(dir ? t - 1 : t + 1) * gx_ld];
         }
         __syncthreads();
+        // (step + 1 fits the tag's low 16 bits: a recurrence is at most 50 frames per token long, see duration_kernel)
+        static_assert(50 * 512 + 1 < 65536, "the step field of the hand-off tag is 16 bits wide");
         const unsigned tag = (epoch << 16) | (unsigned)(step + 1);
         const int par = step & 1;
         if (tid < HU) {
@@ -838,9 +840,15 @@ void launch_lstm(const float* gx, long gx_bs, int gx_ld, const float* whhT, floa
 // ---- duration head + alignment ---------------------------------------------------------------
 // dur[t] = clamp(round(sum_c sigmoid(logit[c][t]) / speed), min 1); frames = sum; idx = the
 // repeat_interleave gather index (model.py forward_with_tokens).
+// A row of idx holds idx_ld frames (the model: 50 per token of the call's longest utterance).  At a speed below 1 a row's
+// durations can add up to more: the row is then cut at idx_ld -- the token that crosses the end gets the remainder, the ones
+// behind it 0; dur holds these USED durations, so sum(dur[b][:T]) == frames[b] <= idx_ld always -- and recorded in a sticky
+// device word (first offender: b + 1), as checked_id records a bad token id: the host reads it at the forward's one
+// synchronisation point and turns it into KX_ERR_INVALID.  A row that fits is untouched by any of this.
 __global__ __launch_bounds__(512) void duration_kernel(const float* logits, long bs, int ld, const float* speeds,
                                                        int n_speed, const int* lens, const int* pinned,
-                                                       int n_pinned, int* dur, int* frames, int* idx, int idx_ld) {
+                                                       int n_pinned, int* dur, int* frames, int* idx, int idx_ld,
+                                                       unsigned* overflow) {
     __shared__ int scan[512];
     const int b = blockIdx.x, t = threadIdx.x;
     const int T = lens[b];
@@ -850,9 +858,9 @@ __global__ __launch_bounds__(512) void duration_kernel(const float* logits, long
         for (int c = 0; c < 50; ++c) s += 1.0f / (1.0f + expf(-logits[b * bs + (long)c * ld + t]));
         s = s / speeds[n_speed > 1 ? b : 0];
         s = rintf(s);
-        d = s < 1.f ? 1 : (int)s;
-        if (n_pinned > 0) d = pinned[t % n_pinned];
-        dur[b * 512 + t] = d;
+        // (one token longer than the whole row already overflows it: idx_ld + 1 says so and keeps the sum of 512 inside an int)
+        d = !(s >= 1.f) ? 1 : (s > (float)idx_ld ? idx_ld + 1 : (int)s);
+        if (n_pinned > 0) d = pinned[t % n_pinned];  // (1..50 each: Model::set_pinned)
     }
     scan[t] = d;
     __syncthreads();
@@ -862,17 +870,24 @@ __global__ __launch_bounds__(512) void duration_kernel(const float* logits, long
         scan[t] += v;
         __syncthreads();
     }
-    if (t == 511) frames[b] = scan[511];
+    if (t == 511) {
+        const int total = scan[511];
+        frames[b] = total < idx_ld ? total : idx_ld;
+        if (total > idx_ld && overflow) atomicCAS(overflow, 0u, (unsigned)b + 1u);
+    }
     if (t < T) {
-        const int start = scan[t] - d;
-        for (int f = 0; f < d; ++f) idx[(long)b * idx_ld + start + f] = t;
+        const int end = scan[t] < idx_ld ? scan[t] : idx_ld;
+        const int start = scan[t] - d < idx_ld ? scan[t] - d : idx_ld;
+        dur[b * 512 + t] = end - start;
+        for (int f = start; f < end; ++f) idx[(long)b * idx_ld + f] = t;
     }
 }
 void launch_duration(const float* logits, long bs, int ld, const float* speeds, int n_speed, const int* lens,
-                     const int* pinned, int n_pinned, int* dur, int* frames, int* idx, int idx_ld, int B,
+                     const int* pinned, int n_pinned, int* dur, int* frames, int* idx, int idx_ld, unsigned* overflow, int B,
                      hipStream_t s) {
+    KX_REQUIRE(idx_ld >= 1 && idx_ld <= 50 * 512, "duration: a row of the alignment holds 1 .. 50 x 512 frames");
     hipLaunchKernelGGL(duration_kernel, dim3(B), dim3(512), 0, s, logits, bs, ld, speeds, n_speed, lens, pinned,
-                       n_pinned, dur, frames, idx, idx_ld);
+                       n_pinned, dur, frames, idx, idx_ld, overflow);
     KX_HIP(hipGetLastError());
 }
 

@@ -343,8 +343,8 @@ void lstm_set_parts(int n);       // test hook: 2 / 4 workgroups per (utterance,
 void lstm_set_test_fault(int on);  // test hook: the two-CU kernel's partner never shows up (bounded-poll error path)
 
 void launch_duration(const float* logits, long bs, int ld, const float* speeds, int n_speed, const int* lens,
-                     const int* pinned, int n_pinned, int* dur, int* frames, int* idx, int idx_ld, int B,
-                     hipStream_t s);
+                     const int* pinned, int n_pinned, int* dur, int* frames, int* idx, int idx_ld, unsigned* overflow, int B,
+                     hipStream_t s);  // overflow: sticky word, first row cut at idx_ld frames as b + 1 (see duration_kernel)
 void launch_gather_cols(const float* src, long sbs, int sld, float* dst, long dbs, int dld, int C,
                         const int* idx, int idx_ld, const int* frames, int B, int Fmax, hipStream_t s);
 

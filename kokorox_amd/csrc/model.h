@@ -386,6 +386,7 @@ class Model {
     bool want_edges_ = false;          // the running host call has joins: front_half brings the rows' edge durations back
     std::vector<int> h_edge_;          // [B][2] used durations of every row's first and last token (valid when want_edges_)
     unsigned h_bad_id_ = 0;
+    unsigned h_dur_over_ = 0;
     unsigned* d_dev_err_ = nullptr;
     unsigned* h_words_ = nullptr;    // page-locked: [0] the device error word as read back
     int* h_stage_ = nullptr;         // page-locked scratch of the small per-call host arrays (stage_ints)
@@ -396,6 +397,7 @@ class Model {
     hipStream_t main_stream_ = nullptr;
     void check_dev_err();
     unsigned* d_bad_id_ = nullptr;  // sticky word: first out-of-table token id seen by the embedding kernels
+    unsigned* d_dur_over_ = nullptr;  // sticky word: first utterance whose durations did not fit its row of the alignment (duration_kernel)
     float* gb_ = nullptr;  // [B][gb_total_]
     float *nmean_ = nullptr, *nscale_ = nullptr, *nshift_ = nullptr;
     int n_bs_ = 0;

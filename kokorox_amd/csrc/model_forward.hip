@@ -389,6 +389,7 @@ Model::Front Model::front_half(const int64_t* d_ids, int64_t t_stride, const int
         call_.dF = A.i(B);
         if (want_edges_) d_edge = A.i((size_t)2 * B);  // (a call with joins: every row's two edge durations)
         d_bad_id_ = reinterpret_cast<unsigned*>(A.i(1));
+        d_dur_over_ = reinterpret_cast<unsigned*>(A.i(1));
         d_speeds = A.f(B);
         dur = A.i((size_t)B * 512);
         call_.d_dur = dur;
@@ -424,6 +425,7 @@ Model::Front Model::front_half(const int64_t* d_ids, int64_t t_stride, const int
 
     KX_HIP(hipMemcpyAsync(call_.dT, lens_host, B * sizeof(int), hipMemcpyHostToDevice, stream_));
     KX_HIP(hipMemsetAsync(d_bad_id_, 0, sizeof(unsigned), stream_));
+    KX_HIP(hipMemsetAsync(d_dur_over_, 0, sizeof(unsigned), stream_));
     KX_HIP(hipMemcpyAsync(d_speeds, speeds_host, n_speed * sizeof(float), hipMemcpyHostToDevice, stream_));
     const LenMap LT{call_.dT, 1, 0};
     auto TT = [&](float* p, int C) { return T::of(p, C, Tp, LT, Tmax); };
@@ -506,8 +508,8 @@ Model::Front Model::front_half(const int64_t* d_ids, int64_t t_stride, const int
     lstm(lstms_.at("predictor.lstm"), t_dcat, t_xl, gxT);
     tap("dur.lstm", t_xl);
     conv(convs_.at("duration_proj"), t_xl, t_logits, ConvOpts{});
-    launch_duration(logits, t_logits.bs, Tp, d_speeds, n_speed, call_.dT, d_pinned_, n_pinned_, dur, call_.dF, idx, idx_ld, B,
-                    stream_);
+    launch_duration(logits, t_logits.bs, Tp, d_speeds, n_speed, call_.dT, d_pinned_, n_pinned_, dur, call_.dF, idx, idx_ld, d_dur_over_,
+                    B, stream_);
     KX_HIP(hipMemcpyAsync(call_.hF.data(), call_.dF, B * sizeof(int), hipMemcpyDeviceToHost, stream_));
     if (want_edges_) {
         // a call with joins sizes its regions from the used durations of every row's two pad tokens as well: a gather of
@@ -518,6 +520,8 @@ Model::Front Model::front_half(const int64_t* d_ids, int64_t t_stride, const int
     }
     h_bad_id_ = 0;
     KX_HIP(hipMemcpyAsync(&h_bad_id_, d_bad_id_, sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
+    h_dur_over_ = 0;
+    KX_HIP(hipMemcpyAsync(&h_dur_over_, d_dur_over_, sizeof(unsigned), hipMemcpyDeviceToHost, stream_));
 
     // ===== the one host round trip: predicted frame counts size everything downstream =========
     KX_HIP(hipStreamWaitEvent(stream_, ev_join_, 0));  // the TextEncoder branch joins here
@@ -529,6 +533,10 @@ Model::Front Model::front_half(const int64_t* d_ids, int64_t t_stride, const int
         const unsigned w = h_bad_id_ - 1;
         throw Error(1, "infer: token id outside 0.." + std::to_string(n_vocab_ - 1) + " (utterance " + std::to_string(w >> 16) +
                            ", position " + std::to_string(w & 0xffffu) + ")");
+    }
+    if (h_dur_over_) {  // an utterance slowed down beyond its row of the alignment (cut at idx_ld on the device, never written past it)
+        throw Error(1, "infer: speed too low for utterance " + std::to_string(h_dur_over_ - 1) + ": its durations add up to more than " +
+                           std::to_string(idx_ld) + " frames (50 per token of the call's longest utterance)");
     }
     int Fmax = 0;
     for (int b = 0; b < B; ++b) Fmax = call_.hF[b] > Fmax ? call_.hF[b] : Fmax;

@@ -740,4 +740,308 @@ int kx_test_output_plan_loudness(int device_id, const float* audio, int B, int64
     });
 }
 
+// ---- the token-axis kernels of Model::front_half ---------------------------------------------------------------------------------
+namespace {
+constexpr float FRONT_SENTINEL = -12345.5f;
+inline int pad32(int x) { return (x + 31) & ~31; }
+// [rows][len] -> [rows][ld], the padding filled
+void padded_rows(const float* src, size_t rows, int len, int ld, float fill, std::vector<float>& v) {
+    v.assign(rows * ld, fill);
+    for (size_t r = 0; r < rows; ++r) std::memcpy(&v[r * ld], src + r * len, (size_t)len * 4);
+}
+// [rows][ld] on the device -> [rows][len] on the host; the padding of every row must still hold the sentinel
+void unpad_rows(const float* d_src, size_t rows, int len, int ld, float* dst, const char* what) {
+    std::vector<float> v(rows * ld);
+    KX_HIP(hipMemcpy(v.data(), d_src, v.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < rows; ++r) {
+        std::memcpy(dst + r * len, &v[r * ld], (size_t)len * 4);
+        for (int c = len; c < ld; ++c)
+            if (v[r * ld + c] != FRONT_SENTINEL) throw Error(KX_ERR_STATE, what);
+    }
+}
+// 64 bytes of 0xA5 behind a buffer, as in kx_test_output_plan
+void guard_untouched(const void* d_at, const char* what) {
+    unsigned char tail[64];
+    KX_HIP(hipMemcpy(tail, d_at, 64, hipMemcpyDeviceToHost));
+    for (unsigned char c : tail)
+        if (c != 0xA5) throw Error(KX_ERR_STATE, what);
+}
+}  // namespace
+
+int kx_test_lstm_ragged(int device_id, const float* x, const int32_t* lens, int B, int L, int n_in, const float* w_ih,
+                        const float* w_hh, const float* b_ih, const float* b_hh, const float* w_ih_r, const float* w_hh_r,
+                        const float* b_ih_r, const float* b_hh_r, int inplace, int repeat, uint32_t epoch0, float* y, char* err,
+                        size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        check_device(device_id);
+        KX_REQUIRE(x && lens && y && B > 0 && L > 0 && n_in > 0 && repeat >= 1 && repeat <= 16 && epoch0 <= 0xffffu, "test_lstm_ragged: bad argument");
+        KX_REQUIRE(!inplace || n_in == 640, "test_lstm_ragged: the in-place form is the duration encoder's: 640 input rows");
+        for (int b = 0; b < B; ++b) KX_REQUIRE(lens[b] >= 1 && lens[b] <= L, "test_lstm_ragged: lens out of range");
+        KX_HIP(hipSetDevice(device_id));
+        DevMem dm;
+        const int ld = pad32(L);
+        const float poison = std::nanf("");
+        // [B,L,n_in] -> channel-major [B][n_in][ld]; the row padding and every column >= lens[b] are NaN
+        std::vector<float> xc((size_t)B * n_in * ld, poison);
+        for (int b = 0; b < B; ++b)
+            for (int t = 0; t < lens[b]; ++t)
+                for (int c = 0; c < n_in; ++c) xc[((size_t)b * n_in + c) * ld + t] = x[((size_t)b * L + t) * n_in + c];
+        float* dx = dm.up(xc.data(), xc.size());
+        int* d_len = dm.up(lens, B);
+        const kx::LenMap lm{d_len, 1, 0};
+        // the input GEMM as in kx_test_lstm (f32 kernel, time-major store), on the ragged lengths; gx starts as NaN throughout, so a
+        // recurrence that reads a row past an utterance's length poisons its output
+        const kx::DevAlloc alloc = [&dm](size_t bytes) -> void* { return dm.get<unsigned char>(bytes); };
+        const kx::PackSrc src{{dm.up(w_ih, (size_t)1024 * n_in), dm.up(w_ih_r, (size_t)1024 * n_in), nullptr}, {1024, 1024, 0}};
+        const kx::ConvW ih = kx::pack_conv(src, n_in, 1, nullptr, alloc);
+        float* bias = dm.get<float>(2048);
+        kx::launch_vec_add(dm.up(b_ih, 1024), dm.up(b_hh, 1024), bias, 1024, nullptr);
+        kx::launch_vec_add(dm.up(b_ih_r, 1024), dm.up(b_hh_r, 1024), bias + 1024, 1024, nullptr);
+        float* whhT = dm.get<float>(2 * 256 * 1024);
+        kx::launch_transpose_whh(dm.up(w_hh, 1024 * 256), whhT, nullptr);
+        kx::launch_transpose_whh(dm.up(w_hh_r, 1024 * 256), whhT + 256 * 1024, nullptr);
+        float* gx = dm.get<float>((size_t)B * L * 2048);
+        KX_HIP(hipMemset(gx, 0xFF, (size_t)B * L * 2048 * 4));
+        kx::ConvArgs a{};
+        a.x = dx;
+        a.x_bs = (long)n_in * ld;
+        a.x_ld = ld;
+        a.Cin = n_in;
+        a.in_len = lm;
+        a.out_len = lm;
+        a.n_chunks = ih.n_chunks;
+        a.w = ih.w;
+        a.bias = bias;
+        a.K = 1; a.dil = 1; a.stride = 1; a.pad = 0;
+        a.Cout = ih.rows;
+        a.y = gx;
+        a.y_bs = (long)L * 2048;
+        a.y_ld = 2048;
+        a.out_mul = 1.f; a.out_div = 1.f;
+        a.store = kx::ST_TMAJOR;
+        a.up_cout = 1;
+        kx::launch_conv1d(a, ih.BM, B, L, nullptr);
+        KX_HIP(hipDeviceSynchronize());  // (in place, the rows it read are blanked next)
+        // the output: 512 padded rows per utterance, of a tensor of its own or (in place, as Model::lstm is called for the duration
+        // encoder) rows 0..511 of the 640-row input, whose other 128 rows must come back as they were
+        const long y_bs = inplace ? (long)640 * ld : (long)512 * ld;
+        float* dy = inplace ? dx : dm.get<float>((size_t)B * 512 * ld);
+        const std::vector<float> blank((size_t)512 * ld, FRONT_SENTINEL);
+        unsigned long long* xchg = dm.get<unsigned long long>(kx::lstm_exchange_bytes(B) / sizeof(unsigned long long));
+        KX_HIP(hipMemset(xchg, 0, kx::lstm_exchange_bytes(B)));
+        unsigned* errw = dm.get<unsigned>(1);
+        KX_HIP(hipMemset(errw, 0, sizeof(unsigned)));
+        unsigned epoch_state = epoch0;  // (the exchange buffer's own launch counter, as Model keeps one per buffer)
+        std::vector<float> got((size_t)B * 512 * ld), first;
+        for (int r = 0; r < repeat; ++r) {
+            // (hipMemcpy on the null stream: behind the GEMM that read these rows, and behind the previous launch)
+            for (int b = 0; b < B; ++b) KX_HIP(hipMemcpy(dy + b * y_bs, blank.data(), blank.size() * 4, hipMemcpyHostToDevice));
+            kx::launch_lstm(gx, (long)L * 2048, 2048, whhT, dy, y_bs, ld, lm, B, xchg, errw, nullptr, &epoch_state);
+            KX_HIP(hipDeviceSynchronize());
+            unsigned herr = 0;
+            KX_HIP(hipMemcpy(&herr, errw, sizeof(unsigned), hipMemcpyDeviceToHost));
+            if (herr) throw Error(KX_ERR_DEVICE, "test_lstm_ragged: the two-CU recurrence timed out waiting for its partner");
+            for (int b = 0; b < B; ++b)
+                KX_HIP(hipMemcpy(&got[(size_t)b * 512 * ld], dy + b * y_bs, (size_t)512 * ld * 4, hipMemcpyDeviceToHost));
+            if (r == 0)
+                first = got;
+            else if (std::memcmp(first.data(), got.data(), got.size() * 4) != 0)
+                throw Error(KX_ERR_STATE, "test_lstm_ragged: two launches on one exchange buffer differ");
+        }
+        if (inplace) {
+            std::vector<float> tail((size_t)128 * ld);
+            for (int b = 0; b < B; ++b) {
+                KX_HIP(hipMemcpy(tail.data(), dx + b * y_bs + (long)512 * ld, tail.size() * 4, hipMemcpyDeviceToHost));
+                if (std::memcmp(tail.data(), &xc[((size_t)b * 640 + 512) * ld], tail.size() * 4) != 0)
+                    throw Error(KX_ERR_STATE, "test_lstm_ragged: the recurrence wrote into rows 512..639 of its input");
+            }
+        }
+        // (columns >= lens[b] go back to the caller as they are: the sentinel, if the kernel left them alone)
+        for (int b = 0; b < B; ++b)
+            for (int c = 0; c < 512; ++c) {
+                const float* row = &got[((size_t)b * 512 + c) * ld];
+                for (int t = 0; t < L; ++t) y[((size_t)b * L + t) * 512 + c] = row[t];
+                for (int t = L; t < ld; ++t)
+                    if (row[t] != FRONT_SENTINEL) throw Error(KX_ERR_STATE, "test_lstm_ragged: the kernel wrote into the row padding");
+            }
+    });
+}
+
+int kx_test_alignment(int device_id, const float* logits, int B, int T, const int32_t* lens, const float* speeds, int n_speed,
+                      const int32_t* pinned, int n_pinned, const float* src, int C, int idx_ld, int32_t* dur, int32_t* frames,
+                      int32_t* idx, float* gathered, int Fcap, uint32_t* overflow, char* err, size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        check_device(device_id);
+        KX_REQUIRE(logits && lens && speeds && src && dur && frames && idx && gathered && overflow && B > 0 && T > 0 && T <= 512 && C > 0 &&
+                       idx_ld >= 1 && idx_ld <= 50 * 512 && Fcap >= 1 && (n_speed == 1 || n_speed == B) && n_pinned >= 0 && n_pinned <= 512 &&
+                       (n_pinned == 0 || pinned),
+                   "test_alignment: bad argument");
+        for (int b = 0; b < B; ++b) KX_REQUIRE(lens[b] >= 1 && lens[b] <= T, "test_alignment: lens out of range");
+        for (int i = 0; i < n_speed; ++i) KX_REQUIRE(speeds[i] > 0.f, "test_alignment: speed must be > 0");
+        for (int i = 0; i < n_pinned; ++i) KX_REQUIRE(pinned[i] >= 1 && pinned[i] <= 50, "test_alignment: pinned durations must be in 1..50");
+        KX_HIP(hipSetDevice(device_id));
+        DevMem dm;
+        const int Tp = pad32(T);
+        const float poison = std::nanf("");
+        // logits and src on the model's padded rows: the padding and every column >= lens[b] are NaN
+        auto ragged = [&](const float* p, int rows) {
+            std::vector<float> v((size_t)B * rows * Tp, poison);
+            for (int b = 0; b < B; ++b)
+                for (int r = 0; r < rows; ++r)
+                    std::memcpy(&v[((size_t)b * rows + r) * Tp], p + ((size_t)b * rows + r) * T, (size_t)lens[b] * 4);
+            return v;
+        };
+        const std::vector<float> lg = ragged(logits, 50), sp = ragged(src, C);
+        const float* d_lg = dm.up(lg.data(), lg.size());
+        const float* d_src = dm.up(sp.data(), sp.size());
+        const int* d_len = dm.up(lens, B);
+        const float* d_speed = dm.up(speeds, n_speed);
+        const int* d_pin = n_pinned ? dm.up(pinned, n_pinned) : nullptr;
+        // integer outputs start as 0xA5 bytes; 64 more of them stand guard behind idx
+        int* d_dur = dm.get<int>((size_t)B * 512);
+        int* d_frames = dm.get<int>(B);
+        int* d_idx = dm.get<int>((size_t)B * idx_ld + 16);
+        unsigned* d_over = dm.get<unsigned>(1);
+        KX_HIP(hipMemset(d_dur, 0xA5, (size_t)B * 512 * 4));
+        KX_HIP(hipMemset(d_frames, 0xA5, (size_t)B * 4));
+        KX_HIP(hipMemset(d_idx, 0xA5, ((size_t)B * idx_ld + 16) * 4));
+        KX_HIP(hipMemset(d_over, 0, sizeof(unsigned)));
+        kx::launch_duration(d_lg, (long)50 * Tp, Tp, d_speed, n_speed, d_len, d_pin, n_pinned, d_dur, d_frames, d_idx, idx_ld, d_over, B, nullptr);
+        KX_HIP(hipDeviceSynchronize());
+        KX_HIP(hipMemcpy(dur, d_dur, (size_t)B * 512 * 4, hipMemcpyDeviceToHost));
+        KX_HIP(hipMemcpy(frames, d_frames, (size_t)B * 4, hipMemcpyDeviceToHost));
+        KX_HIP(hipMemcpy(idx, d_idx, (size_t)B * idx_ld * 4, hipMemcpyDeviceToHost));
+        KX_HIP(hipMemcpy(overflow, d_over, sizeof(unsigned), hipMemcpyDeviceToHost));
+        guard_untouched(d_idx + (size_t)B * idx_ld, "test_alignment: the duration kernel wrote past idx");
+        // the gather reads idx[b][0 .. frames[b]): nothing is launched on a frame count or an index outside its row
+        int Fmax = 0;
+        for (int b = 0; b < B; ++b) {
+            if (frames[b] < 0 || frames[b] > idx_ld) throw Error(KX_ERR_STATE, "test_alignment: a frame count outside 0..idx_ld");
+            for (int f = 0; f < frames[b]; ++f)
+                if (idx[(size_t)b * idx_ld + f] < 0 || idx[(size_t)b * idx_ld + f] >= lens[b])
+                    throw Error(KX_ERR_STATE, "test_alignment: an alignment index outside its utterance");
+            Fmax = frames[b] > Fmax ? frames[b] : Fmax;
+        }
+        KX_REQUIRE(Fmax <= Fcap, "test_alignment: Fcap is too small");
+        const int Fp = pad32(Fcap);
+        const size_t n_g = (size_t)B * C * Fp;
+        float* d_g = dm.get<float>(n_g + 16);
+        {
+            const std::vector<float> blank(n_g, FRONT_SENTINEL);
+            KX_HIP(hipMemcpy(d_g, blank.data(), n_g * 4, hipMemcpyHostToDevice));
+            KX_HIP(hipMemset(d_g + n_g, 0xA5, 64));
+        }
+        if (Fmax > 0) kx::launch_gather_cols(d_src, (long)C * Tp, Tp, d_g, (long)C * Fp, Fp, C, d_idx, idx_ld, d_frames, B, Fmax, nullptr);
+        KX_HIP(hipDeviceSynchronize());
+        unpad_rows(d_g, (size_t)B * C, Fcap, Fp, gathered, "test_alignment: the gather wrote into the row padding");
+        guard_untouched(d_g + n_g, "test_alignment: the gather wrote past its tensor");
+    });
+}
+
+int kx_test_embed(int device_id, const int64_t* ids, int B, int ids_stride, int T, const int32_t* lens, const float* text_table,
+                  const float* word, const float* type0, const float* pos, int n_vocab, float* out_text, float* out_albert,
+                  uint32_t* bad, char* err, size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        check_device(device_id);
+        KX_REQUIRE(ids && lens && text_table && word && type0 && pos && out_text && out_albert && bad && B > 0 && T > 0 && T <= 512 &&
+                       ids_stride >= T && n_vocab > 0,
+                   "test_embed: bad argument");
+        for (int b = 0; b < B; ++b) KX_REQUIRE(lens[b] >= 1 && lens[b] <= T, "test_embed: lens out of range");
+        KX_HIP(hipSetDevice(device_id));
+        DevMem dm;
+        const int ld = pad32(T);
+        const int64_t* d_ids = dm.up(ids, (size_t)B * ids_stride);
+        const int* d_len = dm.up(lens, B);
+        const float* d_tab = dm.up(text_table, (size_t)n_vocab * 512);
+        const float* d_word = dm.up(word, (size_t)n_vocab * 128);
+        const float* d_type = dm.up(type0, 128);
+        const float* d_pos = dm.up(pos, (size_t)T * 128);
+        const std::vector<float> blank((size_t)B * 512 * ld, FRONT_SENTINEL);
+        float* d_text = dm.up(blank.data(), (size_t)B * 512 * ld);
+        float* d_alb = dm.up(blank.data(), (size_t)B * 128 * ld);
+        // one sticky word for both kernels, as in the model
+        unsigned* d_bad = dm.get<unsigned>(1);
+        KX_HIP(hipMemset(d_bad, 0, sizeof(unsigned)));
+        kx::launch_embed(d_ids, ids_stride, d_tab, 512, d_text, (long)512 * ld, ld, d_len, B, T, n_vocab, d_bad, nullptr);
+        kx::launch_albert_embed(d_ids, ids_stride, d_word, d_type, d_pos, d_alb, (long)128 * ld, ld, d_len, B, T, n_vocab, d_bad, nullptr);
+        KX_HIP(hipDeviceSynchronize());
+        KX_HIP(hipMemcpy(bad, d_bad, sizeof(unsigned), hipMemcpyDeviceToHost));
+        unpad_rows(d_text, (size_t)B * 512, T, ld, out_text, "test_embed: embed_kernel wrote into the row padding");
+        unpad_rows(d_alb, (size_t)B * 128, T, ld, out_albert, "test_embed: albert_embed_kernel wrote into the row padding");
+    });
+}
+
+int kx_test_style_fc(int device_id, const float* styles, int B, const float* w, const float* bias, const int32_t* n_out,
+                     const int32_t* style_off, int n_desc, float* out, char* err, size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        check_device(device_id);
+        KX_REQUIRE(styles && w && bias && n_out && style_off && out && B > 0 && n_desc > 0, "test_style_fc: bad argument");
+        KX_HIP(hipSetDevice(device_id));
+        DevMem dm;
+        // the descriptors as Model::add_fc packs them: outputs back to back in one row per utterance, every weight tensor an
+        // allocation of its own (a blob's tensors start on 256-byte boundaries: the kernel reads the rows as float4)
+        std::vector<kx::FcDesc> desc((size_t)n_desc);
+        long total = 0;
+        for (int i = 0; i < n_desc; ++i) {
+            KX_REQUIRE(n_out[i] > 0 && (style_off[i] == 0 || style_off[i] == 128), "test_style_fc: bad descriptor");
+            kx::FcDesc& d = desc[(size_t)i];
+            d.w = dm.up(w + (size_t)total * 128, (size_t)n_out[i] * 128);
+            d.b = dm.up(bias + total, (size_t)n_out[i]);
+            d.n_out = n_out[i];
+            d.style_off = style_off[i];
+            d.out_off = total;
+            total += n_out[i];
+        }
+        const kx::FcDesc* d_desc = dm.up(desc.data(), desc.size());
+        const float* d_styles = dm.up(styles, (size_t)B * 256);
+        const size_t n = (size_t)B * total;
+        float* d_out = dm.get<float>(n + 16);
+        const std::vector<float> blank(n, FRONT_SENTINEL);
+        KX_HIP(hipMemcpy(d_out, blank.data(), n * 4, hipMemcpyHostToDevice));
+        KX_HIP(hipMemset(d_out + n, 0xA5, 64));
+        kx::launch_style_fc(d_desc, n_desc, d_styles, d_out, total, B, nullptr);
+        KX_HIP(hipDeviceSynchronize());
+        KX_HIP(hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost));
+        guard_untouched(d_out + n, "test_style_fc: the kernel wrote past the last utterance's row");
+    });
+}
+
+int kx_test_rows(int device_id, const float* styles, const int32_t* lens, int B, int T, float* fill_out, const float* src, int rows,
+                 int Ls, int Ld, int mul, int add, float* copy_out, char* err, size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        check_device(device_id);
+        KX_REQUIRE(styles && lens && fill_out && src && copy_out && B > 0 && T > 0 && rows > 0 && Ls > 0 && Ld > 0, "test_rows: bad argument");
+        for (int b = 0; b < B; ++b) {
+            const long m = (long)lens[b] * mul + add;
+            KX_REQUIRE(lens[b] >= 1 && lens[b] <= T && m >= 0 && m <= Ls && m <= Ld, "test_rows: lens out of range");
+        }
+        KX_HIP(hipSetDevice(device_id));
+        DevMem dm;
+        const int* d_len = dm.up(lens, B);
+        const float* d_styles = dm.up(styles, (size_t)B * 256);
+        // the style rows of the duration encoder's input: rows 512..639 of a 640-row tensor = the second half of the style row
+        const int ld = pad32(T);
+        const std::vector<float> blank((size_t)B * 640 * ld, FRONT_SENTINEL);
+        float* d_fill = dm.up(blank.data(), blank.size());
+        kx::launch_fill_style_rows(d_fill, (long)640 * ld, ld, 512, d_styles, 128, d_len, B, T, nullptr);
+        // a copy between tensors of different row strides over a mapped length (lens[b] mul + add columns of every row)
+        const int sld = pad32(Ls), dld = pad32(Ld) + 32;
+        std::vector<float> sp;
+        padded_rows(src, (size_t)B * rows, Ls, sld, std::nanf(""), sp);
+        const float* d_src = dm.up(sp.data(), sp.size());
+        const size_t n = (size_t)B * rows * dld;
+        float* d_copy = dm.get<float>(n + 16);
+        {
+            const std::vector<float> blank2(n, FRONT_SENTINEL);
+            KX_HIP(hipMemcpy(d_copy, blank2.data(), n * 4, hipMemcpyHostToDevice));
+            KX_HIP(hipMemset(d_copy + n, 0xA5, 64));
+        }
+        kx::launch_copy_rows(d_src, (long)rows * sld, sld, d_copy, (long)rows * dld, dld, rows, kx::LenMap{d_len, mul, add}, B, Ld, nullptr);
+        KX_HIP(hipDeviceSynchronize());
+        unpad_rows(d_fill, (size_t)B * 640, T, ld, fill_out, "test_rows: fill_style_rows_kernel wrote into the row padding");
+        unpad_rows(d_copy, (size_t)B * rows, Ld, dld, copy_out, "test_rows: copy_rows_kernel wrote into the row padding");
+        guard_untouched(d_copy + n, "test_rows: copy_rows_kernel wrote past its tensor");
+    });
+}
+
 }  // extern "C"

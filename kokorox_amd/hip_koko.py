@@ -207,6 +207,11 @@ def load_test_library() -> C.CDLL:
                                                cp, sz]),
         "kx_test_output_plan_loudness": (i32, [i32, vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp,
                                                vp, vp, vp, i64, vp, cp, sz]),
+        "kx_test_lstm_ragged": (i32, [i32, vp, vp, i32, i32, i32] + [vp] * 8 + [i32, i32, u32, vp, cp, sz]),
+        "kx_test_alignment": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, cp, sz]),
+        "kx_test_embed": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, cp, sz]),
+        "kx_test_style_fc": (i32, [i32, vp, i32, vp, vp, vp, vp, i32, vp, cp, sz]),
+        "kx_test_rows": (i32, [i32, vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, cp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -218,7 +223,8 @@ def load_test_library() -> C.CDLL:
 
 TEST_ABI_SYMBOLS = ["kx_test_conv1d", "kx_test_lstm", "kx_test_source", "kx_test_attention", "kx_test_conv1d_epilogue", "kx_test_conv1d_full",
                     "kx_test_conv_transpose", "kx_test_lstm_fault", "kx_test_lstm_parts", "kx_test_conv_plan", "kx_test_conv1d_opts",
-                    "kx_test_layernorm", "kx_test_instance_norm", "kx_test_output_plan", "kx_test_output_plan_levelled", "kx_test_output_plan_loudness"]
+                    "kx_test_layernorm", "kx_test_instance_norm", "kx_test_output_plan", "kx_test_output_plan_levelled", "kx_test_output_plan_loudness",
+                    "kx_test_lstm_ragged", "kx_test_alignment", "kx_test_embed", "kx_test_style_fc", "kx_test_rows"]
 
 ABI_SYMBOLS = [
     "kx_version", "kx_init", "kx_create", "kx_import_onnx", "kx_resample_filter", "kx_create_from_device_blob", "kx_create_replicas", "kx_replicas_times", "kx_create_partition", "kx_destroy",
@@ -1111,6 +1117,95 @@ def lstm(x, params, device=0):
     y = np.zeros((B, L, 512), dtype=np.float32)
     _err_call(lib.kx_test_lstm, device, _ptr(x), B, L, n_in, *[_ptr(p) for p in ps], _ptr(y))
     return y
+
+
+def lstm_ragged(x, lens, params, inplace=False, repeat=1, epoch0=0, device=0):
+    """lstm() on a ragged batch (kx_test_lstm_ragged): x [B,L,n_in] with utterance b valid for lens[b] steps -> [B,L,512], columns
+    >= lens[b] = LN_SENTINEL.  inplace: the output is rows 0..511 of the 640-row input tensor (n_in = 640); repeat launches on one
+    exchange buffer whose launch counter starts at epoch0 (two that differ in a bit raise)."""
+    lib = load_test_library()
+    x = _f32(x)
+    B, L, n_in = x.shape
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    assert ln.shape == (B,)
+    ps = [_f32(p) for p in params]
+    y = np.zeros((B, L, 512), dtype=np.float32)
+    _err_call(lib.kx_test_lstm_ragged, device, _ptr(x), _ptr(ln), B, L, n_in, *[_ptr(p) for p in ps], 1 if inplace else 0, repeat,
+              epoch0, _ptr(y))
+    return y
+
+
+INT_SENTINEL = np.int32(np.uint32(0xA5A5A5A5).astype(np.int32))  # integer buffers of the hooks start as 0xA5 bytes
+
+
+def alignment(logits, lens, speeds, src, pinned=None, idx_ld=None, Fcap=None, device=0):
+    """Duration head and alignment (kx_test_alignment): logits [B,50,T], lens [B], speeds [1 or B], src [B,C,T], pinned (1..50
+    each) or None, rows of idx_ld frames (default 50 T) -> (dur [B,512], frames [B], idx [B,idx_ld], gathered [B,C,Fcap],
+    overflow word).  Untouched entries: INT_SENTINEL / LN_SENTINEL."""
+    lib = load_test_library()
+    logits, src = _f32(logits), _f32(src)
+    B, n50, T = logits.shape
+    assert n50 == 50 and src.shape[0] == B and src.shape[2] == T
+    C_ = src.shape[1]
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    sp = np.ascontiguousarray(speeds, dtype=np.float32).reshape(-1)
+    pin = None if pinned is None else np.ascontiguousarray(pinned, dtype=np.int32)
+    idx_ld = 50 * T if idx_ld is None else idx_ld
+    Fcap = idx_ld if Fcap is None else Fcap
+    dur = np.zeros((B, 512), dtype=np.int32)
+    frames = np.zeros(B, dtype=np.int32)
+    idx = np.zeros((B, idx_ld), dtype=np.int32)
+    g = np.zeros((B, C_, Fcap), dtype=np.float32)
+    over = np.zeros(1, dtype=np.uint32)
+    _err_call(lib.kx_test_alignment, device, _ptr(logits), B, T, _ptr(ln), _ptr(sp), len(sp), _ptr(pin), 0 if pin is None else len(pin),
+              _ptr(src), C_, idx_ld, _ptr(dur), _ptr(frames), _ptr(idx), _ptr(g), Fcap, _ptr(over))
+    return dur, frames, idx, g, int(over[0])
+
+
+def embed(ids, lens, T, text_table, word, type0, pos, device=0):
+    """Both embedding kernels on ids [B,ids_stride] (kx_test_embed) -> (text [B,512,T], albert [B,128,T], sticky bad-id word)."""
+    lib = load_test_library()
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    B, stride = ids.shape
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    text_table, word, type0, pos = _f32(text_table), _f32(word), _f32(type0), _f32(pos)
+    n_vocab = text_table.shape[0]
+    assert text_table.shape == (n_vocab, 512) and word.shape == (n_vocab, 128) and type0.shape == (128,) and pos.shape == (T, 128)
+    out_t = np.zeros((B, 512, T), dtype=np.float32)
+    out_a = np.zeros((B, 128, T), dtype=np.float32)
+    bad = np.zeros(1, dtype=np.uint32)
+    _err_call(lib.kx_test_embed, device, _ptr(ids), B, stride, T, _ptr(ln), _ptr(text_table), _ptr(word), _ptr(type0), _ptr(pos), n_vocab,
+              _ptr(out_t), _ptr(out_a), _ptr(bad))
+    return out_t, out_a, int(bad[0])
+
+
+def style_fc(styles, ws, bs, style_offs, device=0):
+    """The style projections of a call in one launch (kx_test_style_fc): styles [B,256], descriptor i = (ws[i] [n_out,128], bs[i]
+    [n_out], style_offs[i] in (0, 128)) -> [B, sum n_out], descriptor i behind the ones before it."""
+    lib = load_test_library()
+    styles = _f32(styles)
+    B = styles.shape[0]
+    n_out = np.array([w.shape[0] for w in ws], dtype=np.int32)
+    w = _f32(np.concatenate([np.asarray(w, dtype=np.float32).reshape(-1, 128) for w in ws]))
+    b = _f32(np.concatenate([np.asarray(x, dtype=np.float32).reshape(-1) for x in bs]))
+    so = np.ascontiguousarray(style_offs, dtype=np.int32)
+    out = np.zeros((B, int(n_out.sum())), dtype=np.float32)
+    _err_call(lib.kx_test_style_fc, device, _ptr(styles), B, _ptr(w), _ptr(b), _ptr(n_out), _ptr(so), len(n_out), _ptr(out))
+    return out
+
+
+def rows(styles, lens, T, src, Ld, mul=1, add=0, device=0):
+    """launch_fill_style_rows and launch_copy_rows (kx_test_rows): styles [B,256], lens [B] -> (fill [B,640,T] with rows 512..639
+    = styles[b, 128 + k] over lens[b] columns, copy [B,rows,Ld] = src [B,rows,Ls] over lens[b] mul + add columns); the rest
+    LN_SENTINEL."""
+    lib = load_test_library()
+    styles, src = _f32(styles), _f32(src)
+    B, R, Ls = src.shape
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    fill = np.zeros((B, 640, T), dtype=np.float32)
+    cp = np.zeros((B, R, Ld), dtype=np.float32)
+    _err_call(lib.kx_test_rows, device, _ptr(styles), _ptr(ln), B, T, _ptr(fill), _ptr(src), R, Ls, Ld, mul, add, _ptr(cp))
+    return fill, cp
 
 
 def attention(qkv, lens, device=0):

@@ -620,6 +620,27 @@ def test_error_behaviour(hip_model, blob_path, tmp_path):
     assert hip_model.infer([[0, 5, 6, 0]], [style], 1.0).shape[0] % 600 == 0
 
 
+def test_a_speed_too_low_for_the_alignment_is_refused(hip_model):
+    """A row of the alignment holds 50 frames per token of the batch's longest utterance.  A speed that stretches an utterance
+    beyond that is KX_ERR_INVALID naming the utterance (the kernel cuts the row there and writes nothing past it), the utterance
+    beside it is not what is blamed, and the model serves the next call as before."""
+    from kokorox_amd import hip_koko as hk
+    ids, styles = _inputs([12, 20], seed0=60)
+    tokens, st = [list(i) for i in ids], [list(s) for s in styles]
+    before = hip_model.infer_batch(tokens, st, [1.0, 1.0], seed=3)
+    T = len(tokens[1])
+    assert T == max(len(t) for t in tokens)
+    frames = before[1].shape[0] // 600
+    slow = 0.9 * frames / (50.0 * T) / 2  # (at this speed the row is more than twice what fits)
+    assert 0 < slow < 1
+    with pytest.raises(hk.KokoroxHipError, match="speed too low for utterance 1") as e:
+        hip_model.infer_batch(tokens, st, [1.0, slow], seed=3)
+    assert e.value.code == 1  # KX_ERR_INVALID
+    after = hip_model.infer_batch(tokens, st, [1.0, 1.0], seed=3)
+    for a, b in zip(before, after):
+        np.testing.assert_array_equal(a, b)
+
+
 def test_device_blob_constructor_matches_file_constructor(hip_model, blob_path):
     import torch
     from kokorox_amd import hip_koko as hk

@@ -138,7 +138,8 @@ def test_bilstm_two_and_four_workgroups_and_the_streaming_fallback_give_the_same
 
 def test_bilstm_more_pairs_than_cus():
     """The two-CU recurrence at B = 130: 520 workgroups on 256 CUs, so halves wait for partners that are dispatched
-    later (blocks are dispatched in order and every poll is bounded); ragged lengths; no sticky error, f64 parity."""
+    later (blocks are dispatched in order and every poll is bounded); every utterance L steps long (ragged batches:
+    tests/test_gpu_front_kernels.py); no sticky error, f64 parity."""
     from kokorox_amd import hip_koko as hk
     torch.manual_seed(130)
     B, L, n_in = 130, 11, 64
