@@ -463,11 +463,40 @@ int kx_infer_requests_joined(kx_model* m, const int64_t* ids, int64_t t_stride, 
  *   A property.  f32((f64(peak) / f64(p)) * f64(p)) == peak exactly: the quotient is within 2^-53 relative of peak / p, the
  *   product within 2^-52 relative of the float32 value peak, far inside the half-ulp 2^-25 that rounds back onto it; rounding
  *   is monotone, so no |z'[n]| exceeds it.  A request that mode 1 or mode 2 normalises therefore has a largest |sample| of
- *   exactly `peak`, and with peak <= 1 the clamp of the 16-bit forms never engages. */
+ *   exactly `peak`, and with peak <= 1 the clamp of the 16-bit forms never engages.
+ *   True peak.  KX_PEAK_TRUE (0x100) OR-ed into kx_level.mode or kx_loudness.mode replaces p by the true peak tp, in the gain
+ *   rules and in slot 0 of out_levels / out_loudness: a body whose samples stay inside `peak` can still overshoot it between
+ *   the samples, in the next resampler, codec or DAC (EBU R128 pairs -23 LUFS with -1 dBTP).  The valid modes are exactly
+ *   {0, 1, 2} and {0, 1, 2} | 0x100 for levels, {0, 1} and {0, 1} | 0x100 for loudness; the rules on gain, peak and target_lufs
+ *   follow the low byte; every other bit is refused as before.
+ *     Oversampling.  Four times at every output rate (the factor libebur128 uses below 96 kHz), 12 input samples either side:
+ *     U = 4, C = 48, N = 97, w[i] = sinc((i - 48) / 4) * kaiser_97(i; beta = 8) in float64; for phi = 1, 2, 3 and m = 0..23,
+ *     t_phi[m] = w[4 m + phi] / (sum over m of w[4 m + phi]) in float64, rounded once to float32: 72 taps, every phase with DC
+ *     gain 1 (kx_truepeak_filter hands them out).  Phase 0 is the identity (sinc(k) = delta) and is not computed: the samples
+ *     themselves stand for it.
+ *     The input.  x[j] = f64(z[j]) if z[j] is finite and 0 <= j < N, else 0.0 -- z the stream defined above.
+ *     Interpolated values.  For n in [0, N) and phi in 1..3, u_phi[n] = f32(sum over j = n - 11 .. n + 12, ascending, of
+ *     f64(t_phi[n - j + 12]) * x[j]): a float64 accumulator from +0, one addition per term, one round-to-nearest-even
+ *     conversion.  A float32 x float32 product is exact in float64, so fused and unfused forms agree and a host loop in the same
+ *     order equals the GPU bit for bit.
+ *     The result.  tp = max(p, max over n and phi of |u_phi[n]|) as a float32: tp >= p always.  tp is "usable" when
+ *     0 < tp < +inf; a u that overflows to +-inf makes it unusable, as +inf does for p.
+ *     The gain and the property.  The gain rules stand with tp in place of p.  The property becomes an inequality: with
+ *     g = f64(peak) / f64(tp) no |z'[n]| exceeds `peak` (monotone rounding, p <= tp), so the 16-bit and G.711 forms still cannot
+ *     clip.  The true peak of z' equals `peak` only up to the rounding of the interpolation (z' is rounded to float32 before it
+ *     would be interpolated again), not exactly.
+ *     The filter.  A phase's response is within 8.1e-5 of the ideal fractional delay up to half the Nyquist frequency and
+ *     within 1.35e-3 (0.012 dB) up to 0.8 of it.  A 4800-sample fs/4 sine of amplitude 0.5 at phase 0 / 45 / 60 / 67.5 degrees
+ *     reads -6.021 / -5.914 / -5.954 / -5.847 dBTP, inside the -6.0 +0.2 / -0.4 window of EBU Tech 3341 cases 15..18 (what lies
+ *     above -6.02 is the Gibbs transient at the burst's edges, not filter error). */
 #define KX_LEVEL_GAIN      0u  /* multiply by `gain`                                                   */
 #define KX_LEVEL_NORMALIZE 1u  /* scale so that the body's largest |sample| is `peak`                  */
 #define KX_LEVEL_CEILING   2u  /* multiply by `gain`, but never let the largest |sample| exceed `peak` */
+#define KX_PEAK_TRUE   0x100u  /* OR-ed into a kx_level or kx_loudness mode: `peak` bounds the true peak, p is tp */
 typedef struct kx_level { uint32_t mode; float gain; float peak; } kx_level;   /* 12 bytes */
+/* The 72 taps of the true-peak interpolator as [3][24] float32, phase 1 first.  Host only; KX_ERR_INVALID for a null `taps` or
+ * cap < 72. */
+int kx_truepeak_filter(float* taps, int cap);
 /* kx_infer_requests_joined with a level spec per request: levels [n_level], n_level = 1 (shared) or R.  `joins` may be NULL
  * with n_join == 0 here (no joins); otherwise the join rules and refusals of kx_infer_requests_joined apply.  out_levels may be
  * NULL; when given it receives [R][2] doubles, f64(p) and g of request r as the GPU computed them.  Through this entry every
@@ -506,6 +535,7 @@ int kx_infer_requests_levelled(kx_model* m, const int64_t* ids, int64_t t_stride
  *   forms cannot clip.
  *   The samples.  z'[n] = f32(g * f64(z[n])), then the form, as in "levels".  Marks, sizes and headers do not change.
  *   Valid specs.  Mode 0: target_lufs and peak are +0.0f.  Mode 1: -70 <= target_lufs <= 0 and 2^-15 <= peak <= 1; a NaN fails.
+ *   Either mode may carry KX_PEAK_TRUE ("levels", True peak): p is then tp, in the ceiling and in out_loudness.
  *   The GPU's e[k] agree with a sequential float64 evaluation to about 1e-14 relative; I, g and e[k] of a request do not depend on
  *   what it was batched with. */
 #define KX_LOUDNESS_MEASURE   0u  /* measure only: g = 1                                                        */

@@ -34,6 +34,15 @@ inline ResampleFilter resample_filter(int format_word) {
     return f;
 }
 
+// True peak ("levels" in kokorox_hip.h): PEAK_TRUE OR-ed into the mode of a kx_level or a KxLoudness makes `peak` bound the true
+// peak of the body and the reported peak the true peak; truepeak_filter() = the 72 taps of its interpolator, [3][24], phase 1 first.
+constexpr uint32_t PEAK_TRUE = KX_PEAK_TRUE;
+inline std::vector<float> truepeak_filter() {
+    std::vector<float> taps(72);
+    if (kx_truepeak_filter(taps.data(), (int)taps.size()) != KX_OK) throw std::invalid_argument("truepeak_filter: failed");
+    return taps;
+}
+
 // A request's loudness spec ("loudness" in kokorox_hip.h): {KX_LOUDNESS_MEASURE, 0, 0} measures, {KX_LOUDNESS_NORMALIZE, target_lufs,
 // peak} scales the body to the target under a ceiling; and what comes back: the peak, the gain, the integrated loudness in LUFS
 // (NaN when undefined) and the number of gated blocks.

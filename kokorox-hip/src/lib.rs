@@ -79,6 +79,19 @@ impl KxLevel {
     pub const PLAIN: KxLevel = KxLevel { mode: KX_LEVEL_GAIN, gain: 1.0, peak: 0.0 };
 }
 
+/// OR-ed into a `KxLevel` or `KxLoudness` mode: `peak` bounds the true peak of the body (four times oversampled), and the
+/// reported p is that true peak ("levels" in kokorox_hip.h, True peak).
+pub const KX_PEAK_TRUE: u32 = 0x100;
+
+/// The 72 taps of the true-peak interpolator as [3][24], phase 1 first (host only).
+pub fn truepeak_filter() -> Result<[[f32; 24]; 3], Box<dyn Error>> {
+    let mut t = [[0f32; 24]; 3];
+    match unsafe { kx_truepeak_filter(t.as_mut_ptr() as *mut f32, 72) } {
+        KX_OK => Ok(t),
+        rc => Err(format!("kokorox_hip error {}: kx_truepeak_filter", rc).into()),
+    }
+}
+
 pub const KX_LOUDNESS_MEASURE: u32 = 0;
 pub const KX_LOUDNESS_NORMALIZE: u32 = 1;
 
@@ -123,6 +136,7 @@ extern "C" {
     fn kx_import_onnx(onnx_path: *const c_char, out_path: *const c_char, err: *mut c_char, err_len: usize) -> c_int;
     fn kx_resample_filter(format_word: c_int, l: *mut i32, m: *mut i32, n_taps: *mut i32, taps: *mut f32, cap: c_int) -> c_int;
     fn kx_loudness_filter(format_word: c_int, out10: *mut f64) -> c_int;
+    fn kx_truepeak_filter(taps: *mut f32, cap: c_int) -> c_int;
     fn kx_infer_requests_loudness(m: *mut KxModel, ids: *const i64, t_stride: i64, lens: *const i32, b: c_int,
                                   chunks_per_request: *const i32, r: c_int, styles: *const f32, voice_ids: *const i32,
                                   weights: *const f32, max_mix: c_int, speeds: *const f32, n_speed: c_int, seed: u64, flags: u32,

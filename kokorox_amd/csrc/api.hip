@@ -78,6 +78,14 @@ int kx_loudness_filter(int format_word, double* out10) {
     });
 }
 
+int kx_truepeak_filter(float* taps, int cap) {
+    return guarded_free(nullptr, 0, [&] {
+        KX_REQUIRE(taps, "truepeak_filter: null argument");
+        KX_REQUIRE(cap >= kx::TRUEPEAK_PHASES * kx::TRUEPEAK_NTAPS, "truepeak_filter: cap is smaller than the 72 taps");
+        std::memcpy(taps, kx::truepeak_taps(), (size_t)kx::TRUEPEAK_PHASES * kx::TRUEPEAK_NTAPS * sizeof(float));
+    });
+}
+
 kx_model* kx_create_from_device_blob(const void* d_blob, size_t n_bytes, int device_id, char* err, size_t err_len) {
     kx_model* h = nullptr;
     int rc = guarded_free(err, err_len, [&] {
@@ -297,7 +305,7 @@ static_assert(sizeof(kx_join) == sizeof(kx::JoinSpec) && offsetof(kx_join, flags
 
 static_assert(sizeof(kx_level) == 12 && sizeof(kx_level) == sizeof(kx::LevelSpec) && offsetof(kx_level, mode) == offsetof(kx::LevelSpec, mode) &&
                   offsetof(kx_level, gain) == offsetof(kx::LevelSpec, gain) && offsetof(kx_level, peak) == offsetof(kx::LevelSpec, peak) &&
-                  KX_LEVEL_GAIN == kx::LEVEL_GAIN && KX_LEVEL_NORMALIZE == kx::LEVEL_NORMALIZE && KX_LEVEL_CEILING == kx::LEVEL_CEILING,
+                  KX_LEVEL_GAIN == kx::LEVEL_GAIN && KX_LEVEL_NORMALIZE == kx::LEVEL_NORMALIZE && KX_LEVEL_CEILING == kx::LEVEL_CEILING && KX_PEAK_TRUE == kx::PEAK_TRUE,
               "kx_level is the layout of kx::LevelSpec");
 
 static_assert(sizeof(kx_loudness) == 12 && sizeof(kx_loudness) == sizeof(kx::LoudSpec) && offsetof(kx_loudness, mode) == offsetof(kx::LoudSpec, mode) &&

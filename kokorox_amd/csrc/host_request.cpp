@@ -5,6 +5,7 @@
 
 #include "kweight_coefs.h"
 #include "resample_taps.h"
+#include "truepeak_taps.h"
 
 namespace kx {
 
@@ -46,6 +47,17 @@ long resampled_samples(int rate_code, long n_samples) {
     if (rate_code == 0) return n_samples;
     const ResampleFilter& f = resample_filter(rate_code);
     return n_samples * f.L / f.M;
+}
+
+// ---- the true-peak meter's table (include/kokorox_hip.h, "levels") ---------------------------------------------------------------
+const float* truepeak_taps() {
+    static_assert(KX_TRUEPEAK_PHASES == TRUEPEAK_PHASES && KX_TRUEPEAK_NTAPS == TRUEPEAK_NTAPS, "the committed table is [3][24]");
+    static const uint32_t kBits[TRUEPEAK_PHASES * TRUEPEAK_NTAPS] = {KX_TRUEPEAK_TAPS_1, KX_TRUEPEAK_TAPS_2, KX_TRUEPEAK_TAPS_3};
+    static const struct Table {
+        float taps[TRUEPEAK_PHASES * TRUEPEAK_NTAPS];
+        Table() { std::memcpy(taps, kBits, sizeof taps); }
+    } table;
+    return table.taps;
 }
 
 // ---- refusals of the host entry (Model::infer_host_once) ---------------------------------------------------------------------
@@ -209,7 +221,7 @@ OutputBounds output_bounds(const RequestLayout& lay, int B, size_t n_samples, co
         per_sample = w > per_sample ? w : per_sample;
         y_per_sample = y > y_per_sample ? y : y_per_sample;
     }
-    OutputBounds bound{n_samples * per_sample + (size_t)lay.R * 64 + 16, n_samples * y_per_sample, 0, 0};
+    OutputBounds bound{n_samples * per_sample + (size_t)lay.R * 64 + 16, n_samples * y_per_sample, 0, 0, 0};
     if (lay.marks) {
         KX_REQUIRE(lens, "infer: marks need the token counts");
         bound.packed_bytes += 8;
@@ -223,6 +235,12 @@ OutputBounds output_bounds(const RequestLayout& lay, int B, size_t n_samples, co
         bound.packed_bytes += 8 + 16 * (size_t)lay.R;
         const size_t longest = n_samples * (y_per_sample > 1 ? y_per_sample : 1);
         bound.peak_dwords = (size_t)lay.R * ((longest + (size_t)LEVEL_WINDOW - 1) / (size_t)LEVEL_WINDOW + 1);
+        // the second table, when some request's governing spec asks for the true peak (a metered request's level spec is the plain one)
+        bool flagged = false;
+        for (int i = 0; lay.levels && i < lay.n_level; ++i) flagged = flagged || (lay.levels[i].mode & PEAK_TRUE) != 0;
+        for (int i = 0; lay.loudness && i < lay.n_loudness; ++i)
+            flagged = flagged || (lay.loudness[i].mode != LOUD_NONE && (lay.loudness[i].mode & PEAK_TRUE) != 0);
+        if (flagged) bound.truepeak_dwords = bound.peak_dwords;
     }
     return bound;
 }
@@ -337,7 +355,7 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
     // the levels: every request's spec, the block behind the marks and the grid of the peak pass
     plan.level.clear();
     plan.measured = lay.levels != nullptr || lay.loudness != nullptr;
-    plan.levelled = false;
+    plan.levelled = plan.true_peak = false;
     plan.levels_off = plan.peak_windows = 0;
     const LevelSpec plain_level{LEVEL_GAIN, 1.0f, 0.0f};
     if (plan.measured) {
@@ -348,6 +366,7 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
             KX_REQUIRE(level_spec_ok(ls), "infer: bad level");
             plan.level[(size_t)r] = ls;
             plan.levelled = plan.levelled || !level_spec_plain(ls);
+            plan.true_peak = plan.true_peak || (ls.mode & PEAK_TRUE) != 0;
             longest = plan.req[(size_t)r].n_samples > longest ? plan.req[(size_t)r].n_samples : longest;
         }
         plan.levels_off = (plan.marks_off + 8 * plan.n_marks + 7) & ~7L;
@@ -370,7 +389,8 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
                 continue;
             }
             KX_REQUIRE(level_spec_plain(plan.level[(size_t)r]), "plan: a request has a level or a loudness, not both");
-            plan.levelled = plan.levelled || ls.mode == LOUD_NORMALIZE;
+            plan.levelled = plan.levelled || (ls.mode & ~PEAK_TRUE) == LOUD_NORMALIZE;
+            plan.true_peak = plan.true_peak || (ls.mode & PEAK_TRUE) != 0;
             const long hops = plan.req[(size_t)r].n_samples / loud_hop(plan.req[(size_t)r].rate);
             plan.max_hops = hops > plan.max_hops ? hops : plan.max_hops;
         }

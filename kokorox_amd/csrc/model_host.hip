@@ -156,6 +156,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     OutputTables tables{};
     size_t peak_cap = 0;   // dwords of tables.peak
     size_t hop_cap = 0;    // doubles of tables.hops
+    size_t tpeak_cap = 0;  // dwords of tables.tpeak
     float* d_y = nullptr;  // the resampled streams of the requests with a rate code, back to back
     int *d_vid, *d_rows, *d_kinds;
     float* d_w;
@@ -180,6 +181,8 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             tables.level = static_cast<LevelSpec*>(A.alloc((size_t)R * sizeof(LevelSpec)));
             tables.peak = static_cast<uint32_t*>(A.alloc(bound.peak_dwords * sizeof(uint32_t)));
             peak_cap = bound.peak_dwords;
+            if (bound.truepeak_dwords > 0) tables.tpeak = static_cast<uint32_t*>(A.alloc(bound.truepeak_dwords * sizeof(uint32_t)));
+            tpeak_cap = bound.truepeak_dwords;
         }
         if (loud) {  // (the hop energies of the meter and its transition powers: sized before the forward as well)
             tables.loud = static_cast<LoudSpec*>(A.alloc((size_t)R * sizeof(LoudSpec)));
@@ -245,6 +248,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         }
         KX_REQUIRE((size_t)plan.peak_dwords() <= peak_cap, "levels: the peak table is too small");
         KX_REQUIRE((size_t)plan.hop_doubles() <= hop_cap, "loudness: the hop table is too small");
+        KX_REQUIRE((size_t)plan.truepeak_dwords() <= tpeak_cap, "levels: the true-peak table is too small");
         launch_output_plan(d_audio, ld, call_.d_dur, call_.dT, plan, tables, d_y, d_packed, stream_);
         const int64_t marks_off = plan.marks_off, n_marks = plan.n_marks;
         const int64_t total = n_marks > 0 || plan.measured ? plan.end_bytes() : plan.total_bytes;

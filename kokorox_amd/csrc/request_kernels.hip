@@ -5,6 +5,7 @@
 #include "kx_common.h"
 #include "kweight_coefs.h"
 #include "resample_taps.h"
+#include "truepeak_taps.h"
 
 namespace kx {
 
@@ -309,16 +310,25 @@ __global__ __launch_bounds__(PEAK_THREADS) void request_peak_kernel(const float*
     }
 }
 // request_gain_kernel: one wave per request reduces its partials (the windows past its end were never written and are not read),
-// computes g in float64 as the header defines it and stores {f64(p), g} into the levels block of the packed buffer.
+// computes g in float64 as the header defines it and stores {f64(p), g} into the levels block of the packed buffer.  A spec with
+// PEAK_TRUE: the maximum runs over the true-peak partials as well (request_truepeak_kernel wrote that request's row of them), so p
+// is tp from here on; the second table is not read for any other request.
 __global__ __launch_bounds__(64) void request_gain_kernel(const PackReq* __restrict__ reqs, const LevelSpec* __restrict__ specs,
-                                                          const uint32_t* __restrict__ partials, long windows,
+                                                          const uint32_t* __restrict__ partials,
+                                                          const uint32_t* __restrict__ tpartials, long windows,
                                                           double* __restrict__ levels) {
     const int r = blockIdx.x;
+    const LevelSpec ls = specs[r];
+    const bool true_peak = (ls.mode & PEAK_TRUE) != 0;  // (the whole wave)
     const long n = (reqs[r].n_samples + LEVEL_WINDOW - 1) / LEVEL_WINDOW;
     uint32_t m = 0;
     for (long w = threadIdx.x; w < n; w += 64) {
         const uint32_t v = partials[(long)r * windows + w];
         m = v > m ? v : m;
+        if (true_peak) {
+            const uint32_t u = tpartials[(long)r * windows + w];
+            m = u > m ? u : m;
+        }
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
@@ -326,14 +336,119 @@ __global__ __launch_bounds__(64) void request_gain_kernel(const PackReq* __restr
         m = v > m ? v : m;
     }
     if (threadIdx.x != 0) return;
-    const LevelSpec ls = specs[r];
+    const uint32_t mode = ls.mode & ~PEAK_TRUE;
     const double p = (double)__uint_as_float(m), peak = (double)ls.peak;
     const bool usable = m > 0u && m < 0x7F800000u;
     double g = (double)ls.gain;
-    if (ls.mode == LEVEL_NORMALIZE) g = usable ? peak / p : 1.0;
-    else if (ls.mode == LEVEL_CEILING && usable && g * p > peak) g = peak / p;
+    if (mode == LEVEL_NORMALIZE) g = usable ? peak / p : 1.0;
+    else if (mode == LEVEL_CEILING && usable && g * p > peak) g = peak / p;
     levels[2 * r] = p;
     levels[2 * r + 1] = g;
+}
+
+// ---- true peak: the largest value of the stream four times oversampled (include/kokorox_hip.h, "levels": PEAK_TRUE) ------------
+// For phi = 1..3, u_phi[n] = f32(sum over j = n - 11 .. n + 12 ascending of f64(t_phi[n - j + 12]) x[j]), x the stream with zeros
+// outside [0, N) and where z is not finite; tp = max(p, max |u_phi[n]|).  A float32 x float32 product is exact in float64, so the
+// fused and the unfused form give the same bits and a host loop in the same order reproduces every u (voices.py: true_peak).
+//
+// request_truepeak_kernel: workgroup (w, r) owns the samples [4096 w, min(4096 (w + 1), N)) of request r -- the windows of the peak
+// pass -- and stages them with a halo of 11 before and 12 behind into LDS, +0 for every index outside the stream: nothing outside
+// the request's own run of y is read, nothing at or past 600 * frames[b] of a row.  The 72 taps sit beside them as float64.  Lane
+// t takes the samples t + 256 k, eight of them at a time: 24 float64 chains in registers, the tap index running downwards as j
+// runs upwards; a step reads three taps (one address for the wave: a broadcast) and eight inputs (consecutive dwords across the
+// lanes) for 24 multiply-adds.  The three phases of a sample are independent chains, each in its ascending order.  The maximum is
+// taken on dwords as in the peak pass, and ONE dword per workgroup goes into the second partials table: the gain kernels join it
+// with the first.  A request whose governing spec lacks the flag returns at once; its row of the table is neither written nor read.
+constexpr int TP_THREADS = 256;
+constexpr int TP_BEFORE = TRUEPEAK_NTAPS / 2 - 1, TP_BEHIND = TRUEPEAK_NTAPS / 2;  // j = n - 11 .. n + 12
+constexpr int TP_LDS = (int)LEVEL_WINDOW + TP_BEFORE + TP_BEHIND;                    // 4119 floats
+constexpr int TP_GROUP = 8;                                                          // samples of a lane in flight
+static_assert(LEVEL_WINDOW % (TP_THREADS * TP_GROUP) == 0 && KX_TRUEPEAK_PHASES == 3 && KX_TRUEPEAK_NTAPS == 24, "whole groups, [3][24] taps");
+__device__ const uint32_t truepeak_tap_bits[TRUEPEAK_PHASES * TRUEPEAK_NTAPS] = {KX_TRUEPEAK_TAPS_1, KX_TRUEPEAK_TAPS_2, KX_TRUEPEAK_TAPS_3};
+
+__global__ __launch_bounds__(TP_THREADS) void request_truepeak_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                       const PackReq* __restrict__ reqs, const long* __restrict__ cum,
+                                                                       const JoinRow* __restrict__ jrows, const float* __restrict__ y,
+                                                                       const LevelSpec* __restrict__ levels,
+                                                                       const LoudSpec* __restrict__ louds,
+                                                                       uint32_t* __restrict__ tpartials, long windows) {
+    __shared__ float xs[TP_LDS];
+    __shared__ double ts[TRUEPEAK_PHASES * TRUEPEAK_NTAPS];
+    __shared__ uint32_t wave_max[TP_THREADS / 64];
+    // the governing spec: the loudness spec of a metered request (LOUD_NONE has the flag's bit set: asked first), else the level spec
+    const uint32_t lmode = louds ? louds[blockIdx.y].mode : LOUD_NONE;
+    const uint32_t mode = lmode != LOUD_NONE ? lmode : levels[blockIdx.y].mode;
+    if ((mode & PEAK_TRUE) == 0) return;  // (uniform) a request beside the flagged ones
+    const PackReq rq = reqs[blockIdx.y];
+    const long N = rq.n_samples;
+    const long n0 = (long)blockIdx.x * LEVEL_WINDOW;
+    if (n0 >= N) return;  // (uniform: the grid covers the longest request)
+    const long n1 = n0 + LEVEL_WINDOW < N ? n0 + LEVEL_WINDOW : N;
+    // the window: local index i is sample n0 - 11 + i of the stream, i < T; [s_lo, s_hi) of them are inside it, zeros around
+    const long w_lo = n0 - TP_BEFORE, T = n1 - n0 + TP_BEFORE + TP_BEHIND;
+    const long s_lo = w_lo < 0 ? 0 : w_lo, s_hi = n1 + TP_BEHIND < N ? n1 + TP_BEHIND : N;
+    const long front = s_lo - w_lo, back = s_hi - w_lo;  // front <= 11; T - back <= 12
+    for (long i = threadIdx.x; i < front; i += TP_THREADS) xs[i] = 0.0f;
+    for (long i = back + threadIdx.x; i < T; i += TP_THREADS) xs[i] = 0.0f;
+    float* __restrict__ dst = xs + front;
+    auto finite = [](float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; };
+    if (rq.rate) {  // (uniform) one contiguous run
+        const float* __restrict__ src = y + rq.y_off;
+        for (long i = s_lo + threadIdx.x; i < s_hi; i += TP_THREADS) {
+            const float v = src[i];
+            dst[i - s_lo] = finite(v) ? v : 0.0f;
+        }
+    } else {  // the rows, cut and faded as the packer will see them; every lane checks the samples it staged itself
+        if (jrows) stage_stream<true, TP_THREADS>(dst, audio, audio_ld, cum, jrows, rq.first_row, rq.n_rows, s_lo, s_hi);
+        else stage_stream<false, TP_THREADS>(dst, audio, audio_ld, cum, jrows, rq.first_row, rq.n_rows, s_lo, s_hi);
+        for (long i = s_lo + threadIdx.x; i < s_hi; i += TP_THREADS)
+            if (!finite(dst[i - s_lo])) dst[i - s_lo] = 0.0f;
+    }
+    if (threadIdx.x < TRUEPEAK_PHASES * TRUEPEAK_NTAPS) ts[threadIdx.x] = (double)__uint_as_float(truepeak_tap_bits[threadIdx.x]);
+    __syncthreads();
+    const int count = (int)(n1 - n0);
+    uint32_t m = 0;
+    // (a group past the window's end is skipped by the whole wave; inside the last group a lane past the end computes on LDS
+    // that nobody staged, inside xs, and its values are dropped)
+    for (int base = 0; base < (int)LEVEL_WINDOW; base += TP_THREADS * TP_GROUP) {
+        if (base + (int)(threadIdx.x & ~63u) >= count) break;
+        const float* __restrict__ xp = xs + base + threadIdx.x;  // sample n0 + base + t + 256 k reads xp[256 k + 0 .. 23]
+        double acc[TRUEPEAK_PHASES][TP_GROUP];
+#pragma unroll
+        for (int f = 0; f < TRUEPEAK_PHASES; ++f)
+#pragma unroll
+            for (int k = 0; k < TP_GROUP; ++k) acc[f][k] = 0.0;
+#pragma unroll 4
+        for (int jj = 0; jj < TRUEPEAK_NTAPS; ++jj) {  // j = n - 11 + jj ascending: tap n - j + 12 = 23 - jj
+            const double t1 = ts[TRUEPEAK_NTAPS - 1 - jj], t2 = ts[2 * TRUEPEAK_NTAPS - 1 - jj], t3 = ts[3 * TRUEPEAK_NTAPS - 1 - jj];
+#pragma unroll
+            for (int k = 0; k < TP_GROUP; ++k) {
+                const double x = (double)xp[TP_THREADS * k + jj];
+                acc[0][k] += t1 * x;
+                acc[1][k] += t2 * x;
+                acc[2][k] += t3 * x;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < TP_GROUP; ++k) {
+            if (base + (int)threadIdx.x + TP_THREADS * k < count) {
+#pragma unroll
+                for (int f = 0; f < TRUEPEAK_PHASES; ++f) m = peak_take(m, (float)acc[f][k]);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const uint32_t v = (uint32_t)__shfl_xor((int)m, o);
+        m = v > m ? v : m;
+    }
+    if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < TP_THREADS / 64; ++w) m = wave_max[w] > m ? wave_max[w] : m;
+        tpartials[(long)blockIdx.y * windows + blockIdx.x] = m;
+    }
 }
 
 // ---- loudness: BS.1770 K-weighting, hop energies, gating and the gain (include/kokorox_hip.h, "loudness") ---------------------
@@ -457,8 +572,9 @@ __global__ __launch_bounds__(LOUD_THREADS) void request_loudness_kernel(const fl
         hops[(long)blockIdx.y * max_hops + blockIdx.x] = acc;
     }
 }
-// request_loudness_gain_kernel: one wave per metered request.  It reduces the peak partials as request_gain_kernel does, forms the
-// 400 ms block means z_j from the hop energies, applies the two gates in the energy domain, every lane over j = lane, lane + 64, ..
+// request_loudness_gain_kernel: one wave per metered request.  It reduces the peak partials as request_gain_kernel does (with
+// PEAK_TRUE in its spec over both tables, so that p is tp), forms the 400 ms block means z_j from the hop energies, applies the two
+// gates in the energy domain, every lane over j = lane, lane + 64, ..
 // and the wave with a __shfl_xor tree (a fixed order: the same bits run to run), and stores {f64(p), g} into the request's slot of the
 // levels block and {I, f64(n_g)} into the loudness block behind it.
 __device__ __forceinline__ void loud_gate(const double* __restrict__ e, long J, double scale, double floor_, double& sum, int& count) {
@@ -473,17 +589,23 @@ __device__ __forceinline__ void loud_gate(const double* __restrict__ e, long J, 
     sum = s, count = c;
 }
 __global__ __launch_bounds__(64) void request_loudness_gain_kernel(const PackReq* __restrict__ reqs, const LoudSpec* __restrict__ specs,
-                                                                   const uint32_t* __restrict__ partials, long windows,
+                                                                   const uint32_t* __restrict__ partials,
+                                                                   const uint32_t* __restrict__ tpartials, long windows,
                                                                    const double* __restrict__ hops, long max_hops,
                                                                    double* __restrict__ levels, double* __restrict__ loud) {
     const int r = blockIdx.x;
     const LoudSpec ls = specs[r];
     if (ls.mode == LOUD_NONE) return;  // (the whole wave: its slot is request_gain_kernel's)
+    const bool true_peak = (ls.mode & PEAK_TRUE) != 0;  // (the whole wave, and behind LOUD_NONE, which has the bit set)
     const long n = (reqs[r].n_samples + LEVEL_WINDOW - 1) / LEVEL_WINDOW;
     uint32_t m = 0;
     for (long w = threadIdx.x; w < n; w += 64) {
         const uint32_t v = partials[(long)r * windows + w];
         m = v > m ? v : m;
+        if (true_peak) {
+            const uint32_t u = tpartials[(long)r * windows + w];
+            m = u > m ? u : m;
+        }
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
@@ -502,7 +624,7 @@ __global__ __launch_bounds__(64) void request_loudness_gain_kernel(const PackReq
     const double p = (double)__uint_as_float(m), peak = (double)ls.peak;
     const bool usable = m > 0u && m < 0x7F800000u;
     double g = 1.0;
-    if (ls.mode == LOUD_NORMALIZE) {
+    if ((ls.mode & ~PEAK_TRUE) == LOUD_NORMALIZE) {
         if (c2 > 0) g = pow(10.0, ((double)ls.target_lufs - I) / 20.0);
         if (usable && g * p > peak) g = peak / p;
     }
@@ -585,7 +707,8 @@ __global__ __launch_bounds__(RS_THREADS) void resample_requests_joined_kernel(co
 // plan (OutputPlan::measured): between the resampler and the packer the peak pass and the gain kernel, which stores every
 // request's {p, g} at out + plan.levels_off; the levelled packer runs only when some spec is not the plain one.  A plan with
 // loudness (OutputPlan::loud): the meter behind the peak pass, its gain kernel behind request_gain_kernel, {I, n_g} of every
-// metered request at out + plan.loud_off; a plan without loudness launches neither.
+// metered request at out + plan.loud_off; a plan without loudness launches neither.  A plan with a true peak (OutputPlan::true_peak):
+// request_truepeak_kernel behind the resampler and before the gain kernels; a plan without the flag does not launch it.
 void launch_pack_plan(const float* audio, long audio_ld, const OutputPlan& plan, const OutputTables& t, float* d_y, void* out,
                       hipStream_t s) {
     if (plan.max_units <= 0 && !plan.measured) return;
@@ -615,6 +738,7 @@ void launch_pack_plan(const float* audio, long audio_ld, const OutputPlan& plan,
         KX_HIP(hipGetLastError());
     }
     double* levels = plan.measured ? reinterpret_cast<double*>(static_cast<char*>(out) + plan.levels_off) : nullptr;
+    const uint32_t* tpeak = plan.true_peak ? t.tpeak : nullptr;  // (read for a flagged request only)
     if (plan.measured) {
         if (plan.peak_windows > 0) {
             hipLaunchKernelGGL(request_peak_kernel, dim3((unsigned)plan.peak_windows, (unsigned)R), dim3(PEAK_THREADS), 0, s, audio, audio_ld,
@@ -626,14 +750,22 @@ void launch_pack_plan(const float* audio, long audio_ld, const OutputPlan& plan,
                                t.req, t.cum, plan.joined ? t.join : nullptr, d_y, t.loud, t.loud_pow, t.hops, plan.max_hops);
             KX_HIP(hipGetLastError());
         }
+        // the true peak of the flagged requests into the second table, [R][peak_windows] as the first: the gain kernels join the two
+        if (plan.true_peak && plan.peak_windows > 0) {
+            KX_REQUIRE(t.tpeak != nullptr, "levels: no table for the true peak");
+            hipLaunchKernelGGL(request_truepeak_kernel, dim3((unsigned)plan.peak_windows, (unsigned)R), dim3(TP_THREADS), 0, s, audio,
+                               audio_ld, t.req, t.cum, plan.joined ? t.join : nullptr, d_y, t.level, loud ? t.loud : nullptr, t.tpeak,
+                               plan.peak_windows);
+            KX_HIP(hipGetLastError());
+        }
         // (a metered request's {p, g} slot is the loudness gain kernel's: request_gain_kernel, which runs only when some request is
         // not metered, leaves the plain spec's {p, 1} there and the later kernel of the same stream stores the request's own)
         if (!plan.loud_all) {
-            hipLaunchKernelGGL(request_gain_kernel, dim3((unsigned)R), dim3(64), 0, s, t.req, t.level, t.peak, plan.peak_windows, levels);
+            hipLaunchKernelGGL(request_gain_kernel, dim3((unsigned)R), dim3(64), 0, s, t.req, t.level, t.peak, tpeak, plan.peak_windows, levels);
             KX_HIP(hipGetLastError());
         }
         if (loud) {
-            hipLaunchKernelGGL(request_loudness_gain_kernel, dim3((unsigned)R), dim3(64), 0, s, t.req, t.loud, t.peak, plan.peak_windows,
+            hipLaunchKernelGGL(request_loudness_gain_kernel, dim3((unsigned)R), dim3(64), 0, s, t.req, t.loud, t.peak, tpeak, plan.peak_windows,
                                t.hops, plan.max_hops, levels, reinterpret_cast<double*>(static_cast<char*>(out) + plan.loud_off));
             KX_HIP(hipGetLastError());
         }
@@ -718,7 +850,7 @@ void launch_token_marks(const int* dur, const int* lens, const OutputPlan& plan,
 // The output stage of a call whose plan is built, for the model and for the test hook alike: the bodies into d_packed, and the
 // marks of the requests that want them in their block behind the bodies (8-aligned), and behind those the levels of a measured
 // plan (and behind those the loudness of a plan that has it), so one copy to the host brings them all.  The order is resampler,
-// peak, loudness, gain, packer, marks.
+// peak, loudness, true peak, gain, packer, marks.
 void launch_output_plan(const float* audio, long audio_ld, const int* dur, const int* lens, const OutputPlan& plan,
                         const OutputTables& t, float* d_y, void* d_packed, hipStream_t s) {
     launch_pack_plan(audio, audio_ld, plan, t, d_y, d_packed, s);

@@ -670,6 +670,13 @@ int kx_test_output_plan_loudness(int device_id, const float* audio, int B, int64
             KX_HIP(hipMemset(d_peak, 0x7F, n_peak * 4));
             KX_HIP(hipMemset(d_peak + n_peak, 0xA5, 64));
         }
+        // the true-peak partials: poisoned and guarded like the first table
+        const size_t n_tpeak = (size_t)plan.truepeak_dwords();
+        uint32_t* d_tpeak = plan.true_peak ? dm.get<uint32_t>(n_tpeak + 16) : nullptr;
+        if (d_tpeak) {
+            KX_HIP(hipMemset(d_tpeak, 0x7F, n_tpeak * 4));
+            KX_HIP(hipMemset(d_tpeak + n_tpeak, 0xA5, 64));
+        }
         // the hop energies of the meter: poisoned with NaNs (an entry the launch did not write must not be read), a sentinel behind them
         const size_t n_hop = (size_t)plan.hop_doubles();
         double* d_hops = loudness ? dm.get<double>(n_hop + 8) : nullptr;
@@ -680,7 +687,7 @@ int kx_test_output_plan_loudness(int device_id, const float* audio, int B, int64
         const kx::OutputTables tables{dm.get<kx::PackReq>((size_t)R), dm.get<long>((size_t)B + 1), dm.get<kx::JoinRow>((size_t)B),
                                       dm.get<kx::MarkRow>((size_t)B), plan.measured ? dm.get<kx::LevelSpec>((size_t)R) : nullptr, d_peak,
                                       loudness ? dm.get<kx::LoudSpec>((size_t)R) : nullptr, d_hops,
-                                      loudness ? dm.get<double>((size_t)4 * kx::LOUD_POWERS * 16) : nullptr};
+                                      loudness ? dm.get<double>((size_t)4 * kx::LOUD_POWERS * 16) : nullptr, d_tpeak};
         const int* d_dur = dur ? dm.up(dur, (size_t)B * 512) : nullptr;
         const int* d_len = dur ? dm.up(lens, (size_t)B) : nullptr;
         // sentinels: 64 bytes after the last region, after the resampled streams, after the last mark and after the levels, which
@@ -733,6 +740,7 @@ int kx_test_output_plan_loudness(int device_id, const float* audio, int B, int64
             untouched(d_out + lv_off - 64, "test_output_plan: a kernel wrote in front of the levels");
             untouched(d_out + lv_off + n_lv, "test_output_plan: the kernel wrote past the last level");
             untouched(d_peak + n_peak, "test_output_plan: the peak pass wrote past its table");
+            if (d_tpeak) untouched(d_tpeak + n_tpeak, "test_output_plan: the true-peak pass wrote past its table");
         }
         if (plan.n_marks == 0) return;
         KX_HIP(hipMemcpy(out_marks, d_out + mk_off, (size_t)n_mk, hipMemcpyDeviceToHost));

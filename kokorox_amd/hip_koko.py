@@ -35,6 +35,7 @@ JOIN_NONE = (0, 0, 0, 0)
 LEVEL_GAIN, LEVEL_NORMALIZE, LEVEL_CEILING = 0, 1, 2
 LEVEL_DTYPE = np.dtype([("mode", "<u4"), ("gain", "<f4"), ("peak", "<f4")])
 LEVEL_PLAIN = (LEVEL_GAIN, 1.0, 0.0)
+PEAK_TRUE = 0x100  # OR-ed into a level or a loudness mode: p is the true peak tp (KX_PEAK_TRUE)
 # loudness (include/kokorox_hip.h, "loudness"): a spec is (mode, target_lufs, peak), the layout of kx_loudness
 LOUDNESS_MEASURE, LOUDNESS_NORMALIZE = 0, 1
 LOUDNESS_DTYPE = np.dtype([("mode", "<u4"), ("target_lufs", "<f4"), ("peak", "<f4")])
@@ -143,6 +144,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "kx_dispatcher_submit_request_levelled": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
                                                         C.POINTER(i64), vp, vp, vp, vp, vp, cp, sz]),
         "kx_loudness_filter": (i32, [i32, vp]),
+        "kx_truepeak_filter": (i32, [vp, i32]),
         "kx_infer_requests_loudness": (i32, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, u64, u32, vp, i32, C.POINTER(vp), vp, vp,
                                              vp, vp, vp, i32, vp, i32, vp]),
         "kx_dispatcher_submit_request_loudness": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
@@ -232,7 +234,7 @@ ABI_SYMBOLS = [
     "kx_free_audio", "kx_infer_device", "kx_sync", "kx_set_pinned_durations", "kx_warmup", "kx_arena_bytes", "kx_call_times", "kx_model_status", "kx_model_info", "kx_dispatcher_health", "kx_set_utterance_base", "kx_set_lanes",
     "kx_set_conv_mode", "kx_get_conv_mode", "kx_set_stft_variant", "kx_get_stft_variant",
     "kx_profile_enable", "kx_profile_read", "kx_profile_detail", "kx_profile_aux", "kx_diag_enable", "kx_diag_count", "kx_diag_get", "kx_set_act_prescale", "kx_set_voice_table", "kx_infer_voices",
-    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_infer_requests_levelled", "kx_dispatcher_submit_request_levelled", "kx_loudness_filter", "kx_infer_requests_loudness", "kx_dispatcher_submit_request_loudness", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
+    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_infer_requests_levelled", "kx_dispatcher_submit_request_levelled", "kx_loudness_filter", "kx_truepeak_filter", "kx_infer_requests_loudness", "kx_dispatcher_submit_request_loudness", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
     "kx_dispatcher_stats", "kx_dispatcher_failures", "kx_dispatcher_destroy", "kx_debug_tap",
 ]
 
@@ -262,7 +264,8 @@ def join_specs(joins, n=None) -> np.ndarray:
 
 def level_specs(levels, n=None) -> np.ndarray:
     """Level specs as the array of kx_level the library takes: one (mode, gain, peak) tuple, a list of them, or an array of
-    LEVEL_DTYPE already.  n: the count expected (a single tuple is repeated)."""
+    LEVEL_DTYPE already.  n: the count expected (a single tuple is repeated).  A mode may carry PEAK_TRUE (mode | PEAK_TRUE):
+    the peak of that request is then its true peak, four times oversampled on the GPU (voices.true_peak)."""
     if isinstance(levels, np.ndarray) and levels.dtype == LEVEL_DTYPE:
         a = np.ascontiguousarray(levels).reshape(-1)
     else:
@@ -277,7 +280,8 @@ def level_specs(levels, n=None) -> np.ndarray:
 
 def loudness_specs(loudness, n=None) -> np.ndarray:
     """Loudness specs as the array of kx_loudness the library takes: one (mode, target_lufs, peak) tuple, a list of them, or an
-    array of LOUDNESS_DTYPE already.  n: the count expected (a single tuple is repeated)."""
+    array of LOUDNESS_DTYPE already.  n: the count expected (a single tuple is repeated).  A mode may carry PEAK_TRUE, as in
+    level_specs: `peak` is then a true-peak ceiling and the reported p the true peak."""
     if isinstance(loudness, np.ndarray) and loudness.dtype == LOUDNESS_DTYPE:
         a = np.ascontiguousarray(loudness).reshape(-1)
     else:
@@ -297,6 +301,16 @@ def loudness_filter(word: int) -> np.ndarray:
     rc = load_library().kx_loudness_filter(int(word), _ptr(out))
     if rc != KX_OK:
         raise KokoroxHipError(rc, "unknown output format or sample rate")
+    return out
+
+
+def truepeak_filter() -> np.ndarray:
+    """The 72 float32 taps of the true-peak interpolator as [3][24], phase 1 first, from the library's one table
+    (kx_truepeak_filter; host only)."""
+    out = np.zeros((3, 24), dtype=np.float32)
+    rc = load_library().kx_truepeak_filter(_ptr(out), out.size)
+    if rc != KX_OK:
+        raise KokoroxHipError(rc, "kx_truepeak_filter failed")
     return out
 
 

@@ -298,21 +298,53 @@ def joined_body(chunks_samples, durations_per_chunk: Sequence[Sequence[int]], wo
 
 LEVEL_GAIN, LEVEL_NORMALIZE, LEVEL_CEILING = 0, 1, 2
 LEVEL_PLAIN = (LEVEL_GAIN, 1.0, 0.0)
+PEAK_TRUE = 0x100  # OR-ed into a level or loudness mode: the peak is the true peak (include/kokorox_hip.h, "levels")
+
+
+def true_peak_taps() -> np.ndarray:
+    """The 72 taps of the true-peak interpolator as float32 [3][24], phase 1 first, from the library's one table
+    (kokorox_amd/csrc/truepeak_taps.h through kx_truepeak_filter)."""
+    from . import hip_koko as hk
+    return hk.truepeak_filter()
+
+
+def true_peak(z) -> np.float32:
+    """tp of ONE request's stream z, which is at its output rate already, by the definition of include/kokorox_hip.h, "levels":
+    x[j] = f64(z[j]) where z[j] is finite, 0 elsewhere and outside the stream; for phi = 1..3,
+    u_phi[n] = f32(sum over j = n - 11 .. n + 12 ascending of f64(t_phi[n - j + 12]) x[j]), a float64 accumulator from +0;
+    tp = max(p, max |u_phi[n]|) as a float32, with p the sample peak of level_gain.  Vectorised over n, the 24 taps one after
+    the other in ascending j: the order of every chain is the GPU's."""
+    z = np.ascontiguousarray(z, dtype=np.float32).reshape(-1)
+    a = np.abs(z[~np.isnan(z)])
+    tp = np.float32(a.max()) if a.shape[0] else np.float32(0)
+    N = z.shape[0]
+    if N == 0:
+        return tp
+    taps = true_peak_taps().astype(np.float64)
+    x = np.concatenate([np.zeros(11), np.where(np.isfinite(z), z, np.float32(0)).astype(np.float64), np.zeros(12)])
+    with np.errstate(over="ignore"):
+        for phi in range(3):
+            acc = np.zeros(N, dtype=np.float64)
+            for k in range(24):  # j = n - 11 + k, tap n - j + 12 = 23 - k
+                acc = acc + taps[phi, 23 - k] * x[k: k + N]
+            tp = max(tp, np.float32(np.abs(acc.astype(np.float32)).max()))
+    return np.float32(tp)
 
 
 def _level_fields(level):
     """(mode, gain, peak) of a valid level spec (include/kokorox_hip.h, "levels"), gain and peak as float32; None = the plain
-    spec.  Every comparison is written so that a NaN fails it."""
+    spec.  The mode may carry PEAK_TRUE; the rules follow its low byte.  Every comparison is written so that a NaN fails it."""
     mode, gain, peak = level if level is not None else LEVEL_PLAIN
     with np.errstate(over="ignore", invalid="ignore"):
         gain, peak = np.float32(gain), np.float32(peak)
-    ok = isinstance(mode, (int, np.integer)) and not isinstance(mode, bool) and mode in (0, 1, 2) and bool(np.float32(0) <= gain <= np.float32(64))
-    if ok and mode == LEVEL_GAIN:
+    ok = isinstance(mode, (int, np.integer)) and not isinstance(mode, bool) and (mode & ~PEAK_TRUE) in (0, 1, 2) and bool(np.float32(0) <= gain <= np.float32(64))
+    low = mode & ~PEAK_TRUE if ok else 0
+    if ok and low == LEVEL_GAIN:
         ok = peak.tobytes() == np.float32(0).tobytes()  # +0.0f and nothing else
     elif ok:
-        ok = (mode != LEVEL_NORMALIZE or gain == np.float32(1)) and bool(np.float32(2.0 ** -15) <= peak <= np.float32(1))
+        ok = (low != LEVEL_NORMALIZE or gain == np.float32(1)) and bool(np.float32(2.0 ** -15) <= peak <= np.float32(1))
     if not ok:
-        raise ValueError("level: mode 0..2, gain 0..64 (1 in mode 1), peak +0 in mode 0 and 2^-15..1 in modes 1 and 2")
+        raise ValueError("level: mode 0..2 (| PEAK_TRUE), gain 0..64 (1 in mode 1), peak +0 in mode 0 and 2^-15..1 in modes 1 and 2")
     return int(mode), gain, peak
 
 
@@ -320,11 +352,16 @@ def level_gain(z, level):
     """(p, g) of ONE request's stream z, which is at its output rate already, by the definition of include/kokorox_hip.h,
     "levels": p = the largest |z[n]| over the samples that are no NaN as a float32 (+inf counts; 0 when there is none), g the
     float64 gain of `level` = (mode, gain, peak): gain itself (mode 0), peak / p (mode 1, when 0 < p < inf, else 1), or gain
-    unless gain * p > peak, then peak / p (mode 2, when 0 < p < inf) -- one float64 division, one float64 product."""
+    unless gain * p > peak, then peak / p (mode 2, when 0 < p < inf) -- one float64 division, one float64 product.  A mode
+    with PEAK_TRUE: p is true_peak(z), in the rules and in what is returned."""
     mode, gain, peak = _level_fields(level)
     z = np.ascontiguousarray(z, dtype=np.float32).reshape(-1)
-    a = np.abs(z[~np.isnan(z)])
-    p = np.float32(a.max()) if a.shape[0] else np.float32(0)
+    if mode & PEAK_TRUE:
+        p = true_peak(z)
+    else:
+        a = np.abs(z[~np.isnan(z)])
+        p = np.float32(a.max()) if a.shape[0] else np.float32(0)
+    mode &= ~PEAK_TRUE
     usable = bool(np.float32(0) < p < np.float32(np.inf))
     g = np.float64(gain)
     if mode == LEVEL_NORMALIZE:
@@ -420,27 +457,28 @@ def integrated_loudness(z, rate: int):
 
 def _loudness_fields(loudness):
     """(mode, target_lufs, peak) of a valid loudness spec (include/kokorox_hip.h, "loudness"), the two floats as float32; None =
-    the meter.  Every comparison is written so that a NaN fails it."""
+    the meter.  The mode may carry PEAK_TRUE.  Every comparison is written so that a NaN fails it."""
     mode, target, peak = loudness if loudness is not None else LOUDNESS_METER
     with np.errstate(over="ignore", invalid="ignore"):
         target, peak = np.float32(target), np.float32(peak)
-    ok = isinstance(mode, (int, np.integer)) and not isinstance(mode, bool) and mode in (0, 1)
-    if ok and mode == LOUDNESS_MEASURE:
+    ok = isinstance(mode, (int, np.integer)) and not isinstance(mode, bool) and (mode & ~PEAK_TRUE) in (0, 1)
+    if ok and mode & ~PEAK_TRUE == LOUDNESS_MEASURE:
         ok = target.tobytes() == np.float32(0).tobytes() and peak.tobytes() == np.float32(0).tobytes()
     elif ok:
         ok = bool(np.float32(-70) <= target <= np.float32(0)) and bool(np.float32(2.0 ** -15) <= peak <= np.float32(1))
     if not ok:
-        raise ValueError("loudness: mode 0 with target and peak +0, or mode 1 with -70 <= target_lufs <= 0 and 2^-15 <= peak <= 1")
+        raise ValueError("loudness: mode 0 (| PEAK_TRUE) with target and peak +0, or mode 1 (| PEAK_TRUE) with -70 <= target_lufs <= 0 and 2^-15 <= peak <= 1")
     return int(mode), target, peak
 
 
 def loudness_gain(p, I, loudness) -> float:
     """The float64 gain of a loudness spec for a stream of peak p (level_gain's) and integrated loudness I: 1 for the meter;
-    10^((target - I) / 20) when I is defined, else 1, and then peak / p where p is usable and g p would pass peak."""
+    10^((target - I) / 20) when I is defined, else 1, and then peak / p where p is usable and g p would pass peak.  A mode with
+    PEAK_TRUE: the rule is the same and p is the stream's true peak (level_gain with the flag, or true_peak)."""
     mode, target, peak = _loudness_fields(loudness)
     p = np.float32(p)
     g = np.float64(1.0)
-    if mode == LOUDNESS_NORMALIZE:
+    if mode & ~PEAK_TRUE == LOUDNESS_NORMALIZE:
         if not np.isnan(I):
             g = np.float64(10.0) ** ((np.float64(target) - np.float64(I)) / np.float64(20.0))
         if bool(np.float32(0) < p < np.float32(np.inf)) and g * np.float64(p) > np.float64(peak):
@@ -450,7 +488,8 @@ def loudness_gain(p, I, loudness) -> float:
 
 def loudness_body(z, g: float, word: int) -> bytes:
     """The body of a request whose stream z (at the word's rate) is scaled by the gain g: z'[n] = f32(g f64(z[n])), one float64
-    product and one rounding per sample as in level_stream, then the form of `word`."""
+    product and one rounding per sample as in level_stream, then the form of `word`.  (With PEAK_TRUE in the spec g came from the
+    true peak: the body is made the same way.)"""
     z = np.ascontiguousarray(z, dtype=np.float32).reshape(-1)
     with np.errstate(invalid="ignore", over="ignore", under="ignore"):
         return stream_body((np.float64(g) * z.astype(np.float64)).astype(np.float32), word)
@@ -516,7 +555,8 @@ def tts_request(model, styles: Dict[str, np.ndarray], style_name: str, chunk_tok
     (`wav16_base64`) the bytes a server sends.  `join` = (flags, keep_ms, pause_ms, fade_ms): the seams shaped on the GPU
     (`model.infer_requests_joined`; trim the pads' silence, pause between sentences, fade the cut edges).  `level` = (mode, gain,
     peak): the level set on the GPU (`model.infer_requests_levelled`; a volume, a peak to normalise to, or a ceiling).
-    `loudness` = (mode, target_lufs, peak): the BS.1770 loudness set on the GPU (`model.infer_requests_loudness`).  An
+    `loudness` = (mode, target_lufs, peak): the BS.1770 loudness set on the GPU (`model.infer_requests_loudness`).  Either mode
+    may carry PEAK_TRUE: `peak` then bounds the true peak of the body, four times oversampled, not its largest sample.  An
     empty chunk list and an empty chunk are errors (a request has at least one chunk)."""
     toks, rows = [], []
     for ch in chunk_tokens:

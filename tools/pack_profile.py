@@ -14,6 +14,8 @@ the command line; an optional second argument is the batch (1 = one utterance). 
     a word and 'd'       ('0x300d') kx_infer_requests_loudness, every row a request of its own normalised to -23 LUFS under a peak of 1:
                          request_peak_kernel, request_loudness_kernel and request_loudness_gain_kernel between resampler and packer, and
                          pack_requests_levelled_kernel (no request_gain_kernel: every slot is the loudness gain kernel's);
+    'l' or 'd' and 't'   ('0x300lt', '0lt', '0x300dt') the same call with KX_PEAK_TRUE in every spec: request_truepeak_kernel behind the
+                         peak pass (the meter) and before the gain kernel; without the 't' no such kernel may show in the stats;
     a word and 'g'       ('2g') the same grouping without joins (kx_infer_requests_marks): the plain kernels on the same batch.
 Meant to run under the profiler, one mode per run (kernel trace only, no counters in the same run):
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o t -- python tools/pack_profile.py p2
@@ -26,6 +28,8 @@ import torch  # noqa
 from kokorox_amd import hip_koko as hk, weights as W
 from oracle import kokoro_ref as R
 which = sys.argv[1]
+flag = hk.PEAK_TRUE if which.endswith("t") and which[-2:-1] in ("l", "d") else 0
+which = which[:-1] if flag else which
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 m = hk.HipKoko.new(W.ensure_synthetic_blob())
 toks = [list(int(v) for v in R.synthetic_inputs(1, 128, seed=40 + b)[0]) for b in range(B)]
@@ -50,11 +54,11 @@ for it in range(3):
         assert all(k.shape[0] == 4 * 131 for k in marks)
     elif which.endswith("l"):
         word = int(which[:-1], 0)
-        out, lv = m.infer_requests_levelled(toks, [1] * B, (hk.LEVEL_NORMALIZE, 1.0, 0.5), styles=rows, fmt=word)
+        out, lv = m.infer_requests_levelled(toks, [1] * B, (hk.LEVEL_NORMALIZE | flag, 1.0, 0.5), styles=rows, fmt=word)
         assert lv.shape == (B, 2) and (lv[:, 0] > 0).all() and np.array_equal((lv[:, 0] * lv[:, 1]).astype(np.float32), np.full(B, 0.5, np.float32))
     elif which.endswith("d"):
         word = int(which[:-1], 0)
-        out, ld = m.infer_requests_loudness(toks, [1] * B, (hk.LOUDNESS_NORMALIZE, -23.0, 1.0), styles=rows, fmt=word)
+        out, ld = m.infer_requests_loudness(toks, [1] * B, (hk.LOUDNESS_NORMALIZE | flag, -23.0, 1.0), styles=rows, fmt=word)
         assert ld.shape == (B, 4) and (ld[:, 3] >= 1).all() and np.isfinite(ld[:, 2]).all()
         if it == 2:
             print("loudness of the first request: p %.6g g %.6g I %.6f LUFS n_g %d" % tuple(ld[0]))
@@ -66,5 +70,5 @@ for it in range(3):
     else:
         out = m.infer_requests(toks, [1] * B, styles=rows, fmt=int(which, 0))
     n = sum(len(o) if isinstance(o, bytes) else o.nbytes for o in out)
-print("mode", which, "batch", B, "bytes", n, "frames", len(toks[0]))
+print("mode", which + ("t" if flag else ""), "batch", B, "bytes", n, "frames", len(toks[0]))
 m.close()
