@@ -186,6 +186,37 @@ int kx_test_style_fc(int device_id, const float* styles, int B, const float* w, 
 int kx_test_rows(int device_id, const float* styles, const int32_t* lens, int B, int T, float* fill_out, const float* src, int rows,
                  int Ls, int Ld, int mul, int add, float* copy_out, char* err, size_t err_len);
 
+/* The back half's kernels that are no conv.  Conventions of the four hooks: every row on the device is padded as the model pads
+ * it, every input location a kernel must not read holds NaN (the hook writes them: what the caller has there is not uploaded),
+ * every output location it must not write holds -12345.5 and goes back to the caller as it is, and 64 guard bytes stand behind
+ * every buffer; a write into row padding or guard is KX_ERR_STATE.  Arguments the model could not produce are KX_ERR_INVALID
+ * before anything is launched: frames[b] / lens[b] outside 1 .. the row size, B > 64, Fmax > 64 (source: > 2048), C > 1024,
+ * L > 4096.
+ *
+ * kx_test_source_ragged: source_phase_kernel + source_sample_kernel on f0 [B, 2 Fmax], utterance b valid for 2 frames[b] steps, ->
+ * out [B, 600 Fmax], valid for 600 frames[b] samples.  utt_seeds / utt_index [B]: the per-utterance noise keys of the dispatcher;
+ * utt_seeds NULL: (seed, utt_base + b); utt_index NULL beside utt_seeds: utterance 0 of every seed. */
+int kx_test_source_ragged(int device_id, const float* f0, const int32_t* frames, int B, int Fmax, const float* lin_w, float lin_b,
+                          uint64_t seed, uint64_t utt_base, const uint64_t* utt_seeds, const uint32_t* utt_index, int noise_off,
+                          float* out, char* err, size_t err_len);
+
+/* stft_kernel: hs [B, hs_ld] (600 Fmax <= hs_ld <= 600 Fmax + 4096), utterance b valid for 600 frames[b] samples, variant 0 / 1
+ * (kx_set_stft_variant) -> har [B, 22, 120 Fmax + 1] (11 magnitude rows, 11 phase rows), valid for 120 frames[b] + 1 columns. */
+int kx_test_stft(int device_id, const float* hs, int B, int hs_ld, const int32_t* frames, int Fmax, int variant, float* har, char* err,
+                 size_t err_len);
+
+/* istft_spec_kernel + istft_ola_kernel: cp [B, 22, 120 Fmax + 1] (11 rows of log-magnitudes, 11 of phase logits), utterance b
+ * valid for 120 frames[b] + 1 columns -> spec [B, 22, 120 Fmax + 1] (11 real rows, 11 imaginary rows: what the first kernel
+ * stored) and audio [B, 600 Fmax], valid for 600 frames[b] samples. */
+int kx_test_istft_head(int device_id, const float* cp, int B, const int32_t* frames, int Fmax, int variant, float* spec, float* audio,
+                       char* err, size_t err_len);
+
+/* pool_up2_kernel: x [B, C, L], utterance b valid for lens[b] columns; norm [3, B, C] = the mean, scale and shift planes, which
+ * the hook lays out with n_bs > C slots per utterance (the unused ones NaN); w [C, 3], bias [C] -> y [B, C, 2 L], valid for
+ * 2 lens[b] columns, on rows of another stride than x's. */
+int kx_test_pool_up2(int device_id, const float* x, int B, int C, int L, const int32_t* lens, const float* norm, int n_bs, const float* w,
+                     const float* bias, float slope, float* y, char* err, size_t err_len);
+
 /* Fault injection for the two-CU LSTM recurrence (process-wide, test only): nth > 0 makes the nth following launch of
  * the pair kernel, and every later one, lose the second half of each pair and poll with a short limit, so the call it
  * belongs to must fail with KX_ERR_DEVICE (the bounded wait's error path) and the model must fall back to the one-CU

@@ -564,24 +564,12 @@ int kx_test_attention(int device_id, const float* qkv, const int32_t* lens, int 
 
 int kx_test_source(int device_id, const float* f0, int B, int F2, const float* lin_w, float lin_b, uint64_t seed,
                    uint64_t utt_base, int noise_off, float* out, char* err, size_t err_len) {
-    return guarded_free(err, err_len, [&] {
-        check_device(device_id);
-        KX_REQUIRE(f0 && lin_w && out && B > 0 && F2 > 0 && (F2 % 2) == 0, "test_source: bad argument");
-        KX_HIP(hipSetDevice(device_id));
-        kx::init_dft_tables();
-        DevMem dm;
-        const int F = F2 / 2;
-        std::vector<int> fr(B, F);
-        int* d_fr = dm.up(fr.data(), B);
-        const float* d_f0 = dm.up(f0, (size_t)B * F2);
-        const float* d_w = dm.up(lin_w, 9);
-        const float* d_b = dm.up(&lin_b, 1);
-        float* phase = dm.get<float>((size_t)B * 9 * F2);
-        float* har = dm.get<float>((size_t)B * 600 * F);
-        kx::launch_source(d_f0, F2, d_fr, B, F, d_w, d_b, seed, utt_base, nullptr, nullptr, noise_off, phase, har, (long)600 * F, nullptr);
-        KX_HIP(hipDeviceSynchronize());
-        KX_HIP(hipMemcpy(out, har, (size_t)B * 600 * F * 4, hipMemcpyDeviceToHost));
-    });
+    // every row its full length: the ragged hook with frames[b] = F2 / 2 (nothing of `out` is left as the sentinel)
+    if (!(B > 0 && B <= 64 && F2 > 0 && (F2 % 2) == 0))
+        return guarded_free(err, err_len, [] { throw Error(KX_ERR_INVALID, "test_source: bad argument"); });
+    const std::vector<int32_t> fr((size_t)B, F2 / 2);
+    return kx_test_source_ragged(device_id, f0, fr.data(), B, F2 / 2, lin_w, lin_b, seed, utt_base, nullptr, nullptr, noise_off, out, err,
+                                 err_len);
 }
 
 int kx_test_output_plan(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames_in, const int32_t* dur,
@@ -1049,6 +1037,169 @@ int kx_test_rows(int device_id, const float* styles, const int32_t* lens, int B,
         unpad_rows(d_fill, (size_t)B * 640, T, ld, fill_out, "test_rows: fill_style_rows_kernel wrote into the row padding");
         unpad_rows(d_copy, (size_t)B * rows, Ld, dld, copy_out, "test_rows: copy_rows_kernel wrote into the row padding");
         guard_untouched(d_copy + n, "test_rows: copy_rows_kernel wrote past its tensor");
+    });
+}
+
+// ---- the back half's kernels that are no conv: harmonic source, the STFT pair, the up-sampling pool ---------------------------------
+namespace {
+constexpr int HEAD_MAX_B = 64;        // utterances per hook call
+constexpr int HEAD_MAX_F = 64;        // frames per utterance for the STFT hooks (38 400 samples, 7 681 STFT frames)
+constexpr int SOURCE_MAX_F = 2048;    // frames per utterance for the source hook (four chunks of its phase kernel)
+// a device buffer of n floats holding `fill`, 64 bytes of 0xA5 behind it
+float* guarded_buffer(DevMem& dm, size_t n, float fill) {
+    float* d = dm.get<float>(n + 16);
+    const std::vector<float> blank(n, fill);
+    KX_HIP(hipMemcpy(d, blank.data(), n * 4, hipMemcpyHostToDevice));
+    KX_HIP(hipMemset(d + n, 0xA5, 64));
+    return d;
+}
+// a host image uploaded behind which 64 bytes of 0xA5 stand (inputs: a kernel that wrote into one would be caught as well)
+float* guarded_upload(DevMem& dm, const std::vector<float>& v) {
+    float* d = dm.get<float>(v.size() + 16);
+    KX_HIP(hipMemcpy(d, v.data(), v.size() * 4, hipMemcpyHostToDevice));
+    KX_HIP(hipMemset(d + v.size(), 0xA5, 64));
+    return d;
+}
+void check_frames(const int32_t* frames, int B, int Fmax, const char* what) {
+    for (int b = 0; b < B; ++b)
+        if (frames[b] < 1 || frames[b] > Fmax) throw Error(KX_ERR_INVALID, what);
+}
+}  // namespace
+
+int kx_test_source_ragged(int device_id, const float* f0, const int32_t* frames, int B, int Fmax, const float* lin_w, float lin_b,
+                          uint64_t seed, uint64_t utt_base, const uint64_t* utt_seeds, const uint32_t* utt_index, int noise_off,
+                          float* out, char* err, size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        check_device(device_id);
+        KX_REQUIRE(f0 && frames && lin_w && out && B > 0 && B <= HEAD_MAX_B && Fmax > 0 && Fmax <= SOURCE_MAX_F && (utt_seeds || !utt_index),
+                   "test_source_ragged: bad argument");
+        check_frames(frames, B, Fmax, "test_source_ragged: frames out of range");
+        KX_HIP(hipSetDevice(device_id));
+        kx::init_dft_tables();
+        DevMem dm;
+        // f0 on padded rows: NaN in the padding and in every step >= 2 frames[b]
+        const int L2 = 2 * Fmax, f0_ld = pad32(L2);
+        std::vector<float> fp((size_t)B * f0_ld, std::nanf(""));
+        for (int b = 0; b < B; ++b) std::memcpy(&fp[(size_t)b * f0_ld], f0 + (size_t)b * L2, (size_t)2 * frames[b] * 4);
+        const float* d_f0 = guarded_upload(dm, fp);
+        const int* d_fr = dm.up(frames, B);
+        const float* d_w = dm.up(lin_w, 9);
+        const float* d_b = dm.up(&lin_b, 1);
+        const uint64_t* d_seeds = utt_seeds ? dm.up(utt_seeds, B) : nullptr;
+        const uint32_t* d_index = utt_index ? dm.up(utt_index, B) : nullptr;
+        // the phase workspace [B][9][2 Fmax] as the model sizes it, and the output on rows longer than 600 Fmax
+        const size_t n_ph = (size_t)B * 9 * L2;
+        float* phase = guarded_buffer(dm, n_ph, std::nanf(""));
+        const int Ls = 600 * Fmax, har_ld = pad32(Ls) + 32;
+        const size_t n_har = (size_t)B * har_ld;
+        float* har = guarded_buffer(dm, n_har, FRONT_SENTINEL);
+        kx::launch_source(d_f0, f0_ld, d_fr, B, Fmax, d_w, d_b, seed, utt_base, d_seeds, d_index, noise_off, phase, har, har_ld, nullptr);
+        KX_HIP(hipDeviceSynchronize());
+        // (samples >= 600 frames[b] go back as they are: the sentinel, if the kernel left them alone)
+        unpad_rows(har, (size_t)B, Ls, har_ld, out, "test_source_ragged: source_sample_kernel wrote into the row padding");
+        guard_untouched(har + n_har, "test_source_ragged: source_sample_kernel wrote past its tensor");
+        guard_untouched(phase + n_ph, "test_source_ragged: source_phase_kernel wrote past its workspace");
+        guard_untouched(d_f0 + fp.size(), "test_source_ragged: a kernel wrote behind f0");
+    });
+}
+
+int kx_test_stft(int device_id, const float* hs, int B, int hs_ld, const int32_t* frames, int Fmax, int variant, float* har, char* err,
+                 size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        check_device(device_id);
+        KX_REQUIRE(hs && frames && har && B > 0 && B <= HEAD_MAX_B && Fmax > 0 && Fmax <= HEAD_MAX_F && hs_ld >= 600 * Fmax &&
+                       hs_ld <= 600 * Fmax + 4096 && (variant == kx::STFT_ONNX || variant == kx::STFT_TORCH),
+                   "test_stft: bad argument");
+        check_frames(frames, B, Fmax, "test_stft: frames out of range");
+        KX_HIP(hipSetDevice(device_id));
+        kx::init_dft_tables();
+        DevMem dm;
+        // the source rows as the caller strides them: NaN from sample 600 frames[b] on
+        std::vector<float> hp((size_t)B * hs_ld, std::nanf(""));
+        for (int b = 0; b < B; ++b) std::memcpy(&hp[(size_t)b * hs_ld], hs + (size_t)b * hs_ld, (size_t)600 * frames[b] * 4);
+        const float* d_hs = guarded_upload(dm, hp);
+        const int* d_fr = dm.up(frames, B);
+        const int nfmax = 120 * Fmax + 1, ld = pad32(nfmax);
+        const size_t n = (size_t)B * 22 * ld;
+        float* d_har = guarded_buffer(dm, n, FRONT_SENTINEL);
+        kx::launch_stft(d_hs, hs_ld, d_har, (long)22 * ld, ld, d_fr, B, Fmax, variant, nullptr);
+        KX_HIP(hipDeviceSynchronize());
+        unpad_rows(d_har, (size_t)B * 22, nfmax, ld, har, "test_stft: stft_kernel wrote into the row padding");
+        guard_untouched(d_har + n, "test_stft: stft_kernel wrote past its tensor");
+        guard_untouched(d_hs + hp.size(), "test_stft: stft_kernel wrote behind its input");
+    });
+}
+
+int kx_test_istft_head(int device_id, const float* cp, int B, const int32_t* frames, int Fmax, int variant, float* spec, float* audio,
+                       char* err, size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        check_device(device_id);
+        KX_REQUIRE(cp && frames && spec && audio && B > 0 && B <= HEAD_MAX_B && Fmax > 0 && Fmax <= HEAD_MAX_F &&
+                       (variant == kx::STFT_ONNX || variant == kx::STFT_TORCH),
+                   "test_istft_head: bad argument");
+        check_frames(frames, B, Fmax, "test_istft_head: frames out of range");
+        KX_HIP(hipSetDevice(device_id));
+        kx::init_dft_tables();
+        DevMem dm;
+        // conv_post's output on the model's padded rows: NaN in the padding and from frame 120 frames[b] + 1 on
+        const int nfmax = 120 * Fmax + 1, ld = pad32(nfmax);
+        const size_t n = (size_t)B * 22 * ld;
+        std::vector<float> cpp(n, std::nanf(""));
+        for (int b = 0; b < B; ++b)
+            for (int k = 0; k < 22; ++k)
+                std::memcpy(&cpp[((size_t)b * 22 + k) * ld], cp + ((size_t)b * 22 + k) * nfmax, (size_t)(120 * frames[b] + 1) * 4);
+        const float* d_cp = guarded_upload(dm, cpp);
+        const int* d_fr = dm.up(frames, B);
+        float* d_spec = guarded_buffer(dm, n, FRONT_SENTINEL);
+        const int Ls = 600 * Fmax, audio_ld = pad32(Ls) + 32;
+        const size_t n_a = (size_t)B * audio_ld;
+        float* d_audio = guarded_buffer(dm, n_a, FRONT_SENTINEL);
+        kx::launch_istft_head(d_cp, (long)22 * ld, ld, d_spec, d_audio, audio_ld, d_fr, B, Fmax, variant, nullptr);
+        KX_HIP(hipDeviceSynchronize());
+        unpad_rows(d_spec, (size_t)B * 22, nfmax, ld, spec, "test_istft_head: istft_spec_kernel wrote into the row padding");
+        unpad_rows(d_audio, (size_t)B, Ls, audio_ld, audio, "test_istft_head: istft_ola_kernel wrote into the row padding");
+        guard_untouched(d_spec + n, "test_istft_head: istft_spec_kernel wrote past its tensor");
+        guard_untouched(d_audio + n_a, "test_istft_head: istft_ola_kernel wrote past its tensor");
+        guard_untouched(d_cp + n, "test_istft_head: a kernel wrote behind its input");
+    });
+}
+
+int kx_test_pool_up2(int device_id, const float* x, int B, int C, int L, const int32_t* lens, const float* norm, int n_bs, const float* w,
+                     const float* bias, float slope, float* y, char* err, size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        check_device(device_id);
+        KX_REQUIRE(x && lens && norm && w && bias && y && B > 0 && B <= HEAD_MAX_B && C > 0 && C <= 1024 && L > 0 && L <= 4096 && n_bs > C &&
+                       n_bs <= 2048,
+                   "test_pool_up2: bad argument");
+        for (int b = 0; b < B; ++b) KX_REQUIRE(lens[b] >= 1 && lens[b] <= L, "test_pool_up2: lens out of range");
+        KX_HIP(hipSetDevice(device_id));
+        DevMem dm;
+        const float poison = std::nanf("");
+        // x on the model's padded rows: NaN in the padding and in every column >= lens[b]
+        const int x_ld = pad32(L);
+        std::vector<float> xp((size_t)B * C * x_ld, poison);
+        for (int b = 0; b < B; ++b)
+            for (int c = 0; c < C; ++c)
+                std::memcpy(&xp[((size_t)b * C + c) * x_ld], x + ((size_t)b * C + c) * L, (size_t)lens[b] * 4);
+        const float* d_x = guarded_upload(dm, xp);
+        // the (mean, scale, shift) planes [3][B][n_bs]: an utterance's C values at the front of its n_bs slots, the others NaN
+        std::vector<float> pl((size_t)3 * B * n_bs, poison);
+        for (int p = 0; p < 3; ++p)
+            for (int b = 0; b < B; ++b) std::memcpy(&pl[((size_t)p * B + b) * n_bs], norm + ((size_t)p * B + b) * C, (size_t)C * 4);
+        const float* d_pl = dm.up(pl.data(), pl.size());
+        const float* d_w = dm.up(w, (size_t)C * 3);
+        const float* d_bias = dm.up(bias, (size_t)C);
+        const int* d_len = dm.up(lens, B);
+        // y on rows of another stride than x's
+        const int y_ld = pad32(2 * L) + 32;
+        const size_t n = (size_t)B * C * y_ld;
+        float* d_y = guarded_buffer(dm, n, FRONT_SENTINEL);
+        kx::launch_pool_up2(d_x, (long)C * x_ld, x_ld, C, d_pl, d_pl + (size_t)B * n_bs, d_pl + (size_t)2 * B * n_bs, n_bs, slope, d_w, d_bias,
+                            d_y, (long)C * y_ld, y_ld, kx::LenMap{d_len, 1, 0}, B, L, nullptr);
+        KX_HIP(hipDeviceSynchronize());
+        unpad_rows(d_y, (size_t)B * C, 2 * L, y_ld, y, "test_pool_up2: pool_up2_kernel wrote into the row padding");
+        guard_untouched(d_y + n, "test_pool_up2: pool_up2_kernel wrote past its tensor");
+        guard_untouched(d_x + xp.size(), "test_pool_up2: pool_up2_kernel wrote behind its input");
     });
 }
 

@@ -214,6 +214,10 @@ def load_test_library() -> C.CDLL:
         "kx_test_embed": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, cp, sz]),
         "kx_test_style_fc": (i32, [i32, vp, i32, vp, vp, vp, vp, i32, vp, cp, sz]),
         "kx_test_rows": (i32, [i32, vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, cp, sz]),
+        "kx_test_source_ragged": (i32, [i32, vp, vp, i32, i32, vp, f32, u64, u64, vp, vp, i32, vp, cp, sz]),
+        "kx_test_stft": (i32, [i32, vp, i32, i32, vp, i32, i32, vp, cp, sz]),
+        "kx_test_istft_head": (i32, [i32, vp, i32, vp, i32, i32, vp, vp, cp, sz]),
+        "kx_test_pool_up2": (i32, [i32, vp, i32, i32, i32, vp, vp, i32, vp, vp, f32, vp, cp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -226,7 +230,8 @@ def load_test_library() -> C.CDLL:
 TEST_ABI_SYMBOLS = ["kx_test_conv1d", "kx_test_lstm", "kx_test_source", "kx_test_attention", "kx_test_conv1d_epilogue", "kx_test_conv1d_full",
                     "kx_test_conv_transpose", "kx_test_lstm_fault", "kx_test_lstm_parts", "kx_test_conv_plan", "kx_test_conv1d_opts",
                     "kx_test_layernorm", "kx_test_instance_norm", "kx_test_output_plan", "kx_test_output_plan_levelled", "kx_test_output_plan_loudness",
-                    "kx_test_lstm_ragged", "kx_test_alignment", "kx_test_embed", "kx_test_style_fc", "kx_test_rows"]
+                    "kx_test_lstm_ragged", "kx_test_alignment", "kx_test_embed", "kx_test_style_fc", "kx_test_rows", "kx_test_source_ragged",
+                    "kx_test_stft", "kx_test_istft_head", "kx_test_pool_up2"]
 
 ABI_SYMBOLS = [
     "kx_version", "kx_init", "kx_create", "kx_import_onnx", "kx_resample_filter", "kx_create_from_device_blob", "kx_create_replicas", "kx_replicas_times", "kx_create_partition", "kx_destroy",
@@ -1244,6 +1249,73 @@ def harmonic_source(f0, lin_w, lin_b, seed=0, utt_base=0, noise_off=False, devic
     _err_call(lib.kx_test_source, device, _ptr(f0), B, F2, _ptr(lin_w), float(lin_b), seed, utt_base,
               1 if noise_off else 0, _ptr(out))
     return out
+
+
+def harmonic_source_ragged(f0, frames, lin_w, lin_b, seed=0, utt_base=0, utt_seeds=None, utt_index=None, noise_off=False, device=0):
+    """f0 [B,2 Fmax], utterance b valid for 2 frames[b] steps -> har_source [B,600 Fmax], LN_SENTINEL from sample 600 frames[b] on
+    (kx_test_source_ragged).  utt_seeds / utt_index [B]: the dispatcher's per-utterance noise keys (utt_index None beside
+    utt_seeds: utterance 0 of every seed); without utt_seeds row b draws (seed, utt_base + b)."""
+    lib = load_test_library()
+    f0 = _f32(f0)
+    B, F2 = f0.shape
+    assert F2 % 2 == 0
+    fr = np.ascontiguousarray(frames, dtype=np.int32)
+    assert fr.shape == (B,)
+    sd = None if utt_seeds is None else np.ascontiguousarray(utt_seeds, dtype=np.uint64)
+    ix = None if utt_index is None else np.ascontiguousarray(utt_index, dtype=np.uint32)
+    assert (sd is None or sd.shape == (B,)) and (ix is None or ix.shape == (B,))
+    lin_w = _f32(np.asarray(lin_w).reshape(-1))
+    assert lin_w.shape == (9,)
+    out = np.zeros((B, 300 * F2), dtype=np.float32)
+    _err_call(lib.kx_test_source_ragged, device, _ptr(f0), _ptr(fr), B, F2 // 2, _ptr(lin_w), float(lin_b), seed, utt_base, _ptr(sd),
+              _ptr(ix), 1 if noise_off else 0, _ptr(out))
+    return out
+
+
+def stft(hs, frames, variant, device=0):
+    """stft_kernel alone (kx_test_stft): hs [B,hs_ld], utterance b valid for 600 frames[b] samples, hs_ld >= 600 max(frames)
+    -> har [B,22,120 Fmax + 1] (magnitudes | phases), LN_SENTINEL from column 120 frames[b] + 1 on."""
+    lib = load_test_library()
+    hs = _f32(hs)
+    B, hs_ld = hs.shape
+    fr = np.ascontiguousarray(frames, dtype=np.int32)
+    assert fr.shape == (B,)
+    Fmax = int(fr.max())
+    har = np.zeros((B, 22, 120 * Fmax + 1), dtype=np.float32)
+    _err_call(lib.kx_test_stft, device, _ptr(hs), B, hs_ld, _ptr(fr), Fmax, variant, _ptr(har))
+    return har
+
+
+def istft_head(cp, frames, variant, device=0):
+    """istft_spec_kernel and istft_ola_kernel (kx_test_istft_head): cp [B,22,120 Fmax + 1] (log-magnitudes | phase logits),
+    utterance b valid for 120 frames[b] + 1 columns -> (spec [B,22,120 Fmax + 1] = real | imaginary rows as the first kernel
+    stored them, audio [B,600 Fmax]); LN_SENTINEL past an utterance's own length in both."""
+    lib = load_test_library()
+    cp = _f32(cp)
+    B, R, nfmax = cp.shape
+    fr = np.ascontiguousarray(frames, dtype=np.int32)
+    Fmax = int(fr.max())
+    assert R == 22 and nfmax == 120 * Fmax + 1 and fr.shape == (B,)
+    spec = np.zeros((B, 22, nfmax), dtype=np.float32)
+    audio = np.zeros((B, 600 * Fmax), dtype=np.float32)
+    _err_call(lib.kx_test_istft_head, device, _ptr(cp), B, _ptr(fr), Fmax, variant, _ptr(spec), _ptr(audio))
+    return spec, audio
+
+
+def pool_up2(x, lens, norm, w, bias, slope, n_bs=None, device=0):
+    """pool_up2_kernel alone (kx_test_pool_up2): x [B,C,L], utterance b valid for lens[b] columns, norm [3,B,C] = (mean, scale,
+    shift), w [C,3] (or [C,1,3]), bias [C] -> y [B,C,2 L], LN_SENTINEL from column 2 lens[b] on.  n_bs: the planes' slots per
+    utterance (> C; default C + 3)."""
+    lib = load_test_library()
+    x, norm, bias = _f32(x), _f32(norm), _f32(bias)
+    B, C_, L = x.shape
+    w = _f32(np.asarray(w, dtype=np.float32).reshape(C_, 3))
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    assert norm.shape == (3, B, C_) and bias.shape == (C_,) and ln.shape == (B,)
+    y = np.zeros((B, C_, 2 * L), dtype=np.float32)
+    _err_call(lib.kx_test_pool_up2, device, _ptr(x), B, C_, L, _ptr(ln), _ptr(norm), C_ + 3 if n_bs is None else n_bs, _ptr(w), _ptr(bias),
+              float(slope), _ptr(y))
+    return y
 
 
 def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, want, pauses, device, levels=None, loudness=None):

@@ -55,6 +55,22 @@ def test_ragged_batch_matches_oracle(hip_model, oracle, mode):
         hip_model.set_conv_mode(default_mode)
 
 
+def test_ragged_batch_matches_oracle_with_the_torch_stft_pair(hip_model, oracle):
+    """kx_set_stft_variant(1) / KOKOROX_STFT=torch: the same protocol against the oracle's torch.stft / torch.istft variant (plain
+    root and atan2 forward; doubled interior bins and the window envelope inverse), in the default f16x3 mode."""
+    from kokorox_amd import hip_koko as hk
+    from oracle import kokoro_ref as R
+    default_mode, default_variant = hip_model.get_conv_mode(), hip_model.get_stft_variant()
+    hip_model.set_conv_mode(hk.CONV_F16X3)
+    hip_model.set_stft_variant(hk.STFT_TORCH)
+    try:
+        assert hip_model.get_stft_variant() == hk.STFT_TORCH
+        _ragged_batch_vs_oracle(hip_model, R.KokoroOracle(oracle.w, stft_variant="torch"), counts=(21, 9, 14))
+    finally:
+        hip_model.set_stft_variant(default_variant)
+        hip_model.set_conv_mode(default_mode)
+
+
 def _ragged_batch_vs_oracle(hip_model, oracle, counts=(21, 9, 14)):
     from kokorox_amd import hip_koko as hk
     counts = list(counts)
