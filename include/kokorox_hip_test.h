@@ -217,6 +217,18 @@ int kx_test_istft_head(int device_id, const float* cp, int B, const int32_t* fra
 int kx_test_pool_up2(int device_id, const float* x, int B, int C, int L, const int32_t* lens, const float* norm, int n_bs, const float* w,
                      const float* bias, float slope, float* y, char* err, size_t err_len);
 
+/* The weight images of one layer, byte for byte, from the model's own packers (conv_call.hip: pack_conv or pack_convT, then
+ * add_bf16_image and add_f8_image) and nothing else.  n_src = 1..3 float32 sources src[i] [src_rows[i]][Cin][K], row-concatenated
+ * as kx::PackSrc takes them; or, with up_stride = s > 0, one transposed-conv weight src[0] [Cin][src_rows[0] = Cout][K = 2 s].
+ * Out: meta[9] = BM, rows, n_chunks, n_chunks16, K of the kx::ConvW, then the byte lengths of its images w (f32), w16 (split f16),
+ * w16b (bf16) and w8x (e4m3 cross operands), 0 for an image the layer does not get; *unscale = ConvW::unscale; images[4] = host
+ * buffers of cap[4] bytes that receive those images.  Every image is allocated with 64 guard bytes behind it and pre-filled with
+ * the byte 0xC3, so an entry its packer never writes shows; a changed guard is KX_ERR_STATE.  Sizes no layer has are
+ * KX_ERR_INVALID before any launch: rows (all sources; s Cout) outside 1..4096, Cin outside 1..2048, K outside 1..24.  A layer the
+ * packers refuse (non-finite weights, or max|w| 2^ws beyond f16) is their KX_ERR_INVALID and message. */
+int kx_test_weight_images(int device_id, const float* const* src, const int32_t* src_rows, int n_src, int Cin, int K, int up_stride,
+                          int64_t* meta, float* unscale, void* const* images, const int64_t* cap, char* err, size_t err_len);
+
 /* Fault injection for the two-CU LSTM recurrence (process-wide, test only): nth > 0 makes the nth following launch of
  * the pair kernel, and every later one, lose the second half of each pair and poll with a short limit, so the call it
  * belongs to must fail with KX_ERR_DEVICE (the bounded wait's error path) and the model must fall back to the one-CU

@@ -2,7 +2,9 @@
 // (ConvCall), built here once for Model (model.hip) and for the kernel hooks of tests/ (test_hooks.hip), so that the tests
 // launch what the model launches.  The callers keep what needs a resource of theirs: device memory for the images, the
 // pre-split input image, the flat tile table and the statistics slots (model.h: ConvCall).
+#include <cmath>
 #include <cstdlib>
+#include <string>
 
 #include "model.h"
 
@@ -16,9 +18,18 @@ static void pack_sizes(ConvW& c) {
     c.n_chunks16 = (c.Cin + 15) / 16;
 }
 
+// What the pack path carries: a layer whose weights are all finite and whose largest, times the layer's power of two, fits f16.
+// The shift is clamped at -8 (pick_weight_shift), so max|w| 2^ws > 65504 only from 2^24 (65504 / 65536) upwards, where hi would
+// be an infinity and lo = inf - inf a NaN.  Anything else is refused here, at load time, with KX_ERR_INVALID.
+static float max_absmax(float a, float b) { return std::isnan(a) || std::isnan(b) ? std::nanf("") : std::fmax(a, b); }
+
 // the weight shift of the split-f16 image: 2^ws scales the largest weight to f16's upper range, c.unscale undoes it
 static float weight_scale(ConvW& c, float absmax) {
+    if (!std::isfinite(absmax)) throw Error(1, "conv weights: non-finite weight (a NaN or an infinity) in the layer");
     const int ws = pick_weight_shift(absmax);
+    if (std::ldexp(absmax, ws) > 65504.f)
+        throw Error(1, "conv weights: max|w| = " + std::to_string(absmax) + " is beyond the split's range (max|w| 2^" + std::to_string(ws) +
+                           " must fit f16: at most 65504)");
     c.unscale = std::ldexp(1.0f, -ws);
     return std::ldexp(1.0f, ws);
 }
@@ -29,13 +40,13 @@ ConvW pack_conv(const PackSrc& src, int Cin, int K, hipStream_t s, const DevAllo
     c.Cin = Cin;
     c.K = K;
     pack_sizes(c);
+    float amax = 0.f;
+    for (int i = 0; i < 3; ++i)
+        if (src.p[i]) amax = max_absmax(amax, device_absmax(src.p[i], (long)src.rows[i] * Cin * K, s));
+    const float scale = weight_scale(c, amax);  // (throws before anything is allocated for a layer it refuses)
     float* p = static_cast<float*>(alloc(packed_conv_floats(c.rows, Cin, K, c.BM) * sizeof(float)));
     launch_pack_conv(src, p, c.rows, Cin, K, c.BM, s);
     c.w = p;
-    float amax = 0.f;
-    for (int i = 0; i < 3; ++i)
-        if (src.p[i]) amax = std::fmax(amax, device_absmax(src.p[i], (long)src.rows[i] * Cin * K, s));
-    const float scale = weight_scale(c, amax);
     void* p16 = alloc(packed_conv16_halves(c.rows, Cin, K, c.BM) * 2);
     launch_pack_conv16(src, p16, c.rows, Cin, K, c.BM, scale, s);
     c.w16 = p16;
@@ -50,10 +61,10 @@ ConvW pack_convT(const float* w, int Cin, int Cout, int stride, hipStream_t s, c
     c.rows = stride * Cout;
     c.K = 2;
     pack_sizes(c);
+    const float scale = weight_scale(c, device_absmax(w, (long)Cin * Cout * 2 * stride, s));
     float* p = static_cast<float*>(alloc(packed_conv_floats(c.rows, Cin, 2, c.BM) * sizeof(float)));
     launch_pack_convT(w, p, Cin, Cout, stride, c.BM, s);
     c.w = p;
-    const float scale = weight_scale(c, device_absmax(w, (long)Cin * Cout * 2 * stride, s));
     void* p16 = alloc(packed_conv16_halves(c.rows, Cin, 2, c.BM) * 2);
     launch_pack_convT16(w, p16, Cin, Cout, stride, c.BM, scale, s);
     c.w16 = p16;

@@ -502,13 +502,21 @@ size_t packed_conv16_halves(int rows, int Cin, int K, int BM) {
 }
 
 __global__ void absmax_kernel(const float* p, long n, unsigned* out) {
-    float m = 0.f;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-        m = fmaxf(m, fabsf(p[i]));
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o));
-    if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));  // non-negative floats order as uints
+    // the maximum of the bit patterns of |p[i]|: non-negative floats order as uints, an infinity above every finite value and a
+    // NaN above that, so a non-finite weight reaches the host (fmaxf would drop a NaN)
+    unsigned m = 0u;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const unsigned u = __float_as_uint(p[i]) & 0x7fffffffu;
+        m = u > m ? u : m;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned u = (unsigned)__shfl_down((int)m, o);
+        m = u > m ? u : m;
+    }
+    if ((threadIdx.x & 63) == 0) atomicMax(out, m);
 }
 
+// max |p[i]|; an infinity if there is one, a NaN if there is one
 float device_absmax(const float* p, long n, hipStream_t s) {
     unsigned* d;
     KX_HIP(hipMalloc((void**)&d, 4));

@@ -175,10 +175,22 @@ DevAlloc Model::owned_alloc() {
 }
 
 // The layers' weight images come from the shared packers (conv_call.hip); what is left here is finding the tensors and the bias.
+// A layer the packers refuse (non-finite weights, or weights beyond the split's range: KX_ERR_INVALID there) is a load error
+// like any other of the container: KX_ERR_IO, "weight blob: ...", naming the tensor.
+template <class F>
+static ConvW packed_or_load_error(const std::string& tensors, F&& pack) {
+    try {
+        return pack();
+    } catch (const Error& e) {
+        if (e.code != 1) throw;
+        throw Error(2, "weight blob: bad weights " + tensors + ": " + e.what());
+    }
+}
+
 ConvW Model::make_conv(const std::string& name, bool bias) {
     const TensorInfo& ti = info(name + ".weight");
     const PackSrc src{{wt(name + ".weight"), nullptr, nullptr}, {ti.dims[0], 0, 0}};
-    ConvW c = pack_conv(src, ti.dims[1], ti.ndim >= 3 ? ti.dims[2] : 1, stream_, owned_alloc());
+    ConvW c = packed_or_load_error(name + ".weight", [&] { return pack_conv(src, ti.dims[1], ti.ndim >= 3 ? ti.dims[2] : 1, stream_, owned_alloc()); });
     c.bias = (bias && has(name + ".bias")) ? wt(name + ".bias") : nullptr;
     return c;
 }
@@ -187,14 +199,16 @@ ConvW Model::make_conv_cat(const std::vector<std::string>& names) {
     KX_REQUIRE(names.size() <= 3 && !names.empty(), "make_conv_cat");
     PackSrc src{{nullptr, nullptr, nullptr}, {0, 0, 0}};
     int Cin = 0, K = 1;
+    std::string tensors;
     for (size_t i = 0; i < names.size(); ++i) {
         const TensorInfo& ti = info(names[i] + ".weight");
+        tensors += (i ? ", " : "") + names[i] + ".weight";
         src.p[i] = wt(names[i] + ".weight");
         src.rows[i] = ti.dims[0];
         Cin = ti.dims[1];
         K = ti.ndim >= 3 ? ti.dims[2] : 1;
     }
-    ConvW c = pack_conv(src, Cin, K, stream_, owned_alloc());
+    ConvW c = packed_or_load_error(tensors, [&] { return pack_conv(src, Cin, K, stream_, owned_alloc()); });
     float* bias = dev_alloc(c.rows);
     int r0 = 0;
     for (size_t i = 0; i < names.size(); ++i) {
@@ -209,7 +223,7 @@ ConvW Model::make_conv_cat(const std::vector<std::string>& names) {
 ConvW Model::make_convT(const std::string& name, int stride) {
     const TensorInfo& ti = info(name + ".weight");  // [Cin][Cout][k]
     KX_REQUIRE(ti.dims[2] == 2 * stride, "transposed conv: only k == 2*stride is supported");
-    ConvW c = pack_convT(wt(name + ".weight"), ti.dims[0], ti.dims[1], stride, stream_, owned_alloc());
+    ConvW c = packed_or_load_error(name + ".weight", [&] { return pack_convT(wt(name + ".weight"), ti.dims[0], ti.dims[1], stride, stream_, owned_alloc()); });
     c.bias = wt(name + ".bias");
     return c;
 }
@@ -218,7 +232,7 @@ LstmW Model::make_lstm(const std::string& name) {
     LstmW l;
     const TensorInfo& ti = info(name + ".weight_ih_l0");
     const PackSrc src{{wt(name + ".weight_ih_l0"), wt(name + ".weight_ih_l0_reverse"), nullptr}, {1024, 1024, 0}};
-    l.ih = pack_conv(src, ti.dims[1], 1, stream_, owned_alloc());
+    l.ih = packed_or_load_error(name + ".weight_ih_l0, " + name + ".weight_ih_l0_reverse", [&] { return pack_conv(src, ti.dims[1], 1, stream_, owned_alloc()); });
     float* bias = dev_alloc(2048);
     launch_vec_add(wt(name + ".bias_ih_l0"), wt(name + ".bias_hh_l0"), bias, 1024, stream_);
     launch_vec_add(wt(name + ".bias_ih_l0_reverse"), wt(name + ".bias_hh_l0_reverse"), bias + 1024, 1024, stream_);

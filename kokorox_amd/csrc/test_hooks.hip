@@ -1203,4 +1203,72 @@ int kx_test_pool_up2(int device_id, const float* x, int B, int C, int L, const i
     });
 }
 
+// ---- a layer's weight images, byte for byte ---------------------------------------------------------------------------------------
+int kx_test_weight_images(int device_id, const float* const* src, const int32_t* src_rows, int n_src, int Cin, int K, int up_stride,
+                          int64_t* meta, float* unscale, void* const* images, const int64_t* cap, char* err, size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        check_device(device_id);
+        KX_REQUIRE(src && src_rows && meta && unscale && images && cap && n_src >= 1 && n_src <= 3 && up_stride >= 0,
+                   "test_weight_images: bad argument");
+        KX_REQUIRE(up_stride == 0 || (n_src == 1 && K == 2 * up_stride), "test_weight_images: a transposed weight is one source of 2 s taps");
+        // sizes no layer has are refused before anything is launched (a transposed weight's GEMM has stride x Cout rows)
+        long rows = 0;
+        for (int i = 0; i < n_src; ++i) {
+            KX_REQUIRE(src[i] && src_rows[i] >= 1 && src_rows[i] <= 4096, "test_weight_images: rows out of range");
+            rows += src_rows[i];
+        }
+        if (up_stride) rows *= up_stride;
+        KX_REQUIRE(rows <= 4096 && Cin >= 1 && Cin <= 2048 && K >= 1 && K <= 24, "test_weight_images: size out of range");
+        KX_HIP(hipSetDevice(device_id));
+        DevMem dm;
+        // every image behind a guard, and filled with a pattern no packer writes into a padding slot (a padding slot is +0)
+        struct Img { unsigned char* p; size_t bytes; };
+        std::vector<Img> imgs;
+        const kx::DevAlloc alloc = [&](size_t bytes) -> void* {
+            unsigned char* p = dm.get<unsigned char>(bytes + 64);
+            KX_HIP(hipMemset(p, 0xC3, bytes));
+            KX_HIP(hipMemset(p + bytes, 0xA5, 64));
+            imgs.push_back({p, bytes});
+            return p;
+        };
+        kx::ConvW cw;
+        std::vector<const float*> d_src;
+        std::vector<size_t> n_srcf;
+        if (up_stride) {
+            n_srcf.push_back((size_t)Cin * src_rows[0] * K);
+            d_src.push_back(guarded_upload(dm, std::vector<float>(src[0], src[0] + n_srcf[0])));
+            cw = kx::pack_convT(d_src[0], Cin, src_rows[0], up_stride, nullptr, alloc);
+        } else {
+            kx::PackSrc ps{{nullptr, nullptr, nullptr}, {0, 0, 0}};
+            for (int i = 0; i < n_src; ++i) {
+                n_srcf.push_back((size_t)src_rows[i] * Cin * K);
+                d_src.push_back(guarded_upload(dm, std::vector<float>(src[i], src[i] + n_srcf[i])));
+                ps.p[i] = d_src[i];
+                ps.rows[i] = src_rows[i];
+            }
+            cw = kx::pack_conv(ps, Cin, K, nullptr, alloc);
+        }
+        kx::add_bf16_image(cw, nullptr, alloc);
+        kx::add_f8_image(cw, nullptr, alloc);
+        KX_HIP(hipDeviceSynchronize());
+        for (const Img& im : imgs) guard_untouched(im.p + im.bytes, "test_weight_images: a packer wrote past its image");
+        for (size_t i = 0; i < d_src.size(); ++i) guard_untouched(d_src[i] + n_srcf[i], "test_weight_images: a packer wrote behind a source");
+        const int64_t m5[5] = {cw.BM, cw.rows, cw.n_chunks, cw.n_chunks16, cw.K};
+        for (int i = 0; i < 5; ++i) meta[i] = m5[i];
+        *unscale = cw.unscale;
+        const void* which[4] = {cw.w, cw.w16, cw.w16b, cw.w8x};
+        for (int k = 0; k < 4; ++k) {
+            meta[5 + k] = 0;
+            if (!which[k]) continue;  // (an image the layer does not get: length 0)
+            const Img* im = nullptr;
+            for (const Img& c : imgs)
+                if (c.p == which[k]) im = &c;
+            KX_REQUIRE(im, "test_weight_images: an image that did not come from the allocator");
+            KX_REQUIRE(images[k] && cap[k] >= (int64_t)im->bytes, "test_weight_images: image buffer too small");
+            KX_HIP(hipMemcpy(images[k], im->p, im->bytes, hipMemcpyDeviceToHost));
+            meta[5 + k] = (int64_t)im->bytes;
+        }
+    });
+}
+
 }  // extern "C"

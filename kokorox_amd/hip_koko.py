@@ -218,6 +218,7 @@ def load_test_library() -> C.CDLL:
         "kx_test_stft": (i32, [i32, vp, i32, i32, vp, i32, i32, vp, cp, sz]),
         "kx_test_istft_head": (i32, [i32, vp, i32, vp, i32, i32, vp, vp, cp, sz]),
         "kx_test_pool_up2": (i32, [i32, vp, i32, i32, i32, vp, vp, i32, vp, vp, f32, vp, cp, sz]),
+        "kx_test_weight_images": (i32, [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, cp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -231,7 +232,7 @@ TEST_ABI_SYMBOLS = ["kx_test_conv1d", "kx_test_lstm", "kx_test_source", "kx_test
                     "kx_test_conv_transpose", "kx_test_lstm_fault", "kx_test_lstm_parts", "kx_test_conv_plan", "kx_test_conv1d_opts",
                     "kx_test_layernorm", "kx_test_instance_norm", "kx_test_output_plan", "kx_test_output_plan_levelled", "kx_test_output_plan_loudness",
                     "kx_test_lstm_ragged", "kx_test_alignment", "kx_test_embed", "kx_test_style_fc", "kx_test_rows", "kx_test_source_ragged",
-                    "kx_test_stft", "kx_test_istft_head", "kx_test_pool_up2"]
+                    "kx_test_stft", "kx_test_istft_head", "kx_test_pool_up2", "kx_test_weight_images"]
 
 ABI_SYMBOLS = [
     "kx_version", "kx_init", "kx_create", "kx_import_onnx", "kx_resample_filter", "kx_create_from_device_blob", "kx_create_replicas", "kx_replicas_times", "kx_create_partition", "kx_destroy",
@@ -1316,6 +1317,42 @@ def pool_up2(x, lens, norm, w, bias, slope, n_bs=None, device=0):
     _err_call(lib.kx_test_pool_up2, device, _ptr(x), B, C_, L, _ptr(ln), _ptr(norm), C_ + 3 if n_bs is None else n_bs, _ptr(w), _ptr(bias),
               float(slope), _ptr(y))
     return y
+
+
+def weight_images(sources, up_stride=0, device=0):
+    """The weight images of one layer from the model's packers (kx_test_weight_images): `sources` = one to three float32 arrays
+    [rows_i, Cin, K], row-concatenated as the fused layers are, or, with up_stride = s, one transposed-conv weight [Cin, Cout, 2 s].
+    Returns a dict: BM, rows, n_chunks, n_chunks16, K, unscale, and the raw bytes (uint8 arrays) of w, w16, w16b and w8x -- length
+    0 for an image the layer does not get."""
+    lib = load_test_library()
+    if isinstance(sources, np.ndarray):
+        sources = [sources]
+    src = [_f32(a) for a in sources]
+    assert all(a.ndim == 3 for a in src)
+    if up_stride:
+        Cin, rows, K = src[0].shape
+        src_rows = [rows]
+        rows *= up_stride
+    else:
+        _, Cin, K = src[0].shape
+        assert all(a.shape[1:] == (Cin, K) for a in src)
+        src_rows = [a.shape[0] for a in src]
+        rows = sum(src_rows)
+    # (rows padded to at most 128, channels to 16, taps to groups of 4, at most 4 bytes per weight and image)
+    cap = (rows + 127) * (Cin + 15) * (K + 3) * 4
+    bufs = [np.zeros(cap, dtype=np.uint8) for _ in range(4)]
+    ptrs = (C.c_void_p * len(src))(*[a.ctypes.data for a in src])
+    outs = (C.c_void_p * 4)(*[b.ctypes.data for b in bufs])
+    caps = np.full(4, cap, dtype=np.int64)
+    rws = np.array(src_rows, dtype=np.int32)
+    meta = np.zeros(9, dtype=np.int64)
+    unscale = np.zeros(1, dtype=np.float32)
+    _err_call(lib.kx_test_weight_images, device, ptrs, _ptr(rws), len(src), Cin, K, int(up_stride), _ptr(meta), _ptr(unscale), outs, _ptr(caps))
+    out = dict(zip(("BM", "rows", "n_chunks", "n_chunks16", "K"), (int(v) for v in meta[:5])))
+    out["unscale"] = float(unscale[0])
+    for i, name in enumerate(("w", "w16", "w16b", "w8x")):
+        out[name] = bufs[i][: int(meta[5 + i])].copy()
+    return out
 
 
 def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, want, pauses, device, levels=None, loudness=None):

@@ -8,7 +8,11 @@ products; 1 = f16x3 split) with KX_FLAG_TAPS and prints
   * per conv layer: absmax and rms of its input after the AdaIN affine (kx_diag_*), flagging what the split cannot
     carry: |x| > 6e4 (clamped at 65504) and rms < 1e-3 (low half lost to the f16 subnormal quantum), with the
     power-of-two pre-scale that brings the layer back to rms ~ 1 (kx_set_act_prescale); for the 7- / 11-tap convs, whose cross
-    terms the default f16f8 mode carries on e4m3 images, also the narrower window of those (2^-6 .. 448).
+    terms the default f16f8 mode carries on e4m3 images, also the narrower window of those (2^-6 .. 448); and
+  * beside them the SPREAD of the layer's weights: log2(layer absmax / smallest non-zero row absmax), from a plain NumPy pass
+    over the blob's tensors.  A layer has one weight shift (pick_weight_shift), so a row that far below the layer's maximum
+    sits that far below the shift; from 2^-12 on, its f16f8 products run at the one-MFMA class (measured by
+    tests/test_gpu_weight_images.py).
 With --apply the suggested pre-scales are set and the A/B is repeated.  Without a path the seeded synthetic blob is used
 (every layer is then in range: the report is the tool's own smoke test).
 """
@@ -25,6 +29,37 @@ from kokorox_amd import weights as W  # noqa: E402
 # the generator's convs are covered by the per-layer input diagnostics below and by the kernel-level tests.
 TAPS = ["bert.out", "d_en", "dur.lstm", "pred.shared", "pred.F0", "pred.N", "text_enc.out", "dec.encode", "dec.decode.0",
         "dec.decode.1", "dec.decode.2", "dec.decode.3"]
+
+
+# rows this far (log2) below the layer's maximum pass the f16f8 form's asserted class, 3e-5 relative rms
+WEIGHT_SPREAD_F8 = 12
+# the model's layer names whose tensors are not `name + ".weight"` (Model::build)
+_ALBERT = "bert.encoder.albert_layer_groups.0.albert_layers.0."
+LAYER_TENSORS = {"bert.map": ["bert.encoder.embedding_hidden_mapping_in"], "bert.dense": [_ALBERT + "attention.dense"],
+                 "bert.qkv": [_ALBERT + "attention.query", _ALBERT + "attention.key", _ALBERT + "attention.value"],
+                 "bert.ffn": [_ALBERT + "ffn"], "bert.ffn_out": [_ALBERT + "ffn_output"], "duration_proj": ["predictor.duration_proj.linear_layer"]}
+
+
+def weight_spread(tensors, layer):
+    """log2(layer absmax / smallest non-zero row absmax) of a conv layer's weights, or None if its tensors are not found.  A row
+    is an output channel: the first axis of a conv or linear weight, the second of a transposed conv's [Cin][Cout][k]."""
+    if layer.endswith(".ih"):  # an LSTM's input GEMM: both directions' weights, row-concatenated (Model::make_lstm)
+        names = [layer[:-3] + ".weight_ih_l0", layer[:-3] + ".weight_ih_l0_reverse"]
+    else:
+        names = [n + ".weight" for n in LAYER_TENSORS.get(layer) or [layer]]
+    rows = []
+    for n in names:
+        w = tensors.get(n)
+        if w is None:
+            w = tensors.get(n[:-len(".weight")] + ".0.weight")  # (text_encoder.cnn.N: the conv inside a Sequential)
+        if w is None or w.ndim < 2:
+            return None
+        w = np.abs(np.asarray(w, dtype=np.float64))
+        axis = 1 if ".ups." in n else 0
+        rows.append(np.moveaxis(w, axis, 0).reshape(w.shape[axis], -1).max(axis=1))
+    rows = np.concatenate(rows)
+    nz = rows[rows > 0]
+    return float(np.log2(rows.max() / nz.min())) if nz.size else 0.0
 
 
 def synthetic_inputs(n_phonemes, seed):
@@ -78,10 +113,12 @@ def main():
         e[5] = min(e[5], rms)
         e[6] += 1
     print(f"== conv inputs after the AdaIN affine: {len(layers)} layers, {len(recs)} launches")
-    print(f"  {'layer':58s} {'rows':>5s} {'Cin':>5s} {'k':>3s} {'absmax':>10s} {'min rms':>10s}  note")
+    print(f"  {'layer':58s} {'rows':>5s} {'Cin':>5s} {'k':>3s} {'absmax':>10s} {'min rms':>10s} {'w spread':>8s}  note")
     suggest = {}
+    tensors = W.read_blob(blob)
     for name, (rows, cin, k, sh, amax, rms, n) in sorted(layers.items()):
         note = ""
+        spread = weight_spread(tensors, name)
         if amax * 2.0 ** sh > 6e4:
             note = "absmax > 6e4: clamped by the f16 split"
             suggest[name] = sh - int(np.ceil(np.log2(amax * 2.0 ** sh / 1e4)))
@@ -98,7 +135,11 @@ def main():
         elif k in (7, 11) and amax * 2.0 ** sh > 448.0:
             note = ("f16f8: |x| > 448: the cross terms of those elements are clamped (their products keep 2^-12, the rest 2^-17); "
                     "KOKOROX_CONV=f16x3 carries them fully")
-        print(f"  {name:58s} {rows:5d} {cin:5d} {k:3d} {amax:10.3e} {rms:10.3e}  {note}")
+        if spread is not None and spread >= WEIGHT_SPREAD_F8 and k in (3, 7, 11):
+            note = (note + "; " if note else "") + (f"weights: rows 2^-{spread:.1f} below the layer's maximum: rows this far below the layer's "
+                                                     "maximum run at the one-MFMA class in f16f8 mode")
+        sp = "     n/a" if spread is None else f"{spread:8.1f}"
+        print(f"  {name:58s} {rows:5d} {cin:5d} {k:3d} {amax:10.3e} {rms:10.3e} {sp}  {note}")
     if not suggest:
         print("every layer is inside the range the split carries exactly (1e-3 <= rms, absmax <= 6e4)")
     elif apply:
