@@ -54,10 +54,31 @@ int kx_test_conv1d_full(int device_id, const float* x, int B, int Cin, int L, co
  * follow it), tmajor (ST_TMAJOR: y is [B,Lout,Cout]; with pad_ld & 1 its rows of Cout values end in a checked margin), prec1 (0, or
  * 1 / 2 = one f16 / bf16 MFMA per product, 2 on the bf16 weight image built as Model::set_conv_mode builds it), act_shift
  * (x_prescale = 2^act_shift, w_unscale its inverse, as kx_set_act_prescale sets them), epi_stream (ConvArgs::epi_stream), up_stride
- * (s > 0: the polyphase transposed conv of kx_test_conv_transpose instead, w [Cin,Cout,2 s], dense rows, Lout = (L-1) s - 2 (s/2) + 2 s).
+ * (s > 0: the polyphase transposed conv of kx_test_conv_transpose instead, w [Cin,Cout,2 s], Lout = (L-1) s - 2 (s/2) + 2 s; ragged only with the length maps below).
  * norm_gb [B,2 Cout] (gamma | beta) with norm_out [3,B,Cout]: the conv's own fused partial sums go through launch_stats_finalize
  * and come back as the next conv's (mean, scale, shift) planes.  plan_out[17]: the kx::ConvPlan that was launched, fields as in
- * kx_test_conv_plan.  Lout = (in_up2 ? 2 L : L) + 2 pad - dil (k-1). */
+ * kx_test_conv_plan.  Lout = ((in_up2 ? 2 L : L) + 2 pad - dil (k-1) - 1) / stride + 1.
+ *
+ * n_opts = 15 appends the generator's launches; with 8 options, or with all seven appended fields at their defaults, the call is
+ * the one above.  opts[8] = stride (1 by default; plain convs only; a strided conv is refused a merged, in_up2 or time-major
+ * launch: KX_ERR_INVALID).  opts[9 .. 12] = len_mul_in, len_add_in, len_mul_out, len_add_out: with len_mul_in > 0 lens[b] are UNITS
+ * (the model's frames); utterance b stores lens[b] len_mul_in + len_add_in input columns (<= L) and owns lens[b] len_mul_out +
+ * len_add_out output columns, and in.len, out.len and up_len are those LenMaps over one device array, as in Model::back_half.  The
+ * output count must be the conv's own on the input count -- plain (Lin + 2 pad - dil (k-1) - 1) / stride + 1, polyphase s Lin --
+ * or the call is refused before any launch (KX_ERR_INVALID), as are units that overrun L.  A ragged strided or polyphase call states
+ * its maps (len_mul_in = 0 keeps {lens, 1, 0} in and {lens, 1 or 2, Lout - L} out, stride 1 only).  opts[13] = up_off (with up_stride
+ * > 0: the output starts at column 1 of y and column 0 is its reflection, as in kx_test_conv_transpose; y and resid are
+ * [B,Cout,Lout + 1]; KX_ERR_INVALID without up_stride).  opts[14] = view: x and resid each sit 3 rows below the top of a tensor 8
+ * rows taller than they are, y likewise, and the batch strides are those of the taller tensors (x_bs != Cin x_ld); the foreign input
+ * and residual rows hold NaN, the foreign output rows the sentinel, and a changed one is KX_ERR_STATE.
+ * With these fields a ragged batch, padded rows (pad_ld & 1: y_ld rounds Lout + up_off up to 32, the residual is padded from its own
+ * Lout + up_off columns, the checked padding is [Lout + up_off, y_ld)) and the flat tile list go with stride > 1, with up_stride,
+ * with up_off and with the residual of a transposed conv; fused statistics (stats_out, norm_gb / norm_out) go with stride > 1, and
+ * stats_out adds the slots of the row's own output columns.
+ * Every ragged call of the conv hooks (lens given), old or new: the hook writes NaN into every input and residual column at or
+ * past an utterance's own length; what the caller has there is not uploaded.  A call that uses an appended field also gets
+ * -12345.5 back in every output column the utterance does not own (other calls: 0, or the running sum), and has 64 guard bytes
+ * behind x, y, resid and the partial-sum table checked (KX_ERR_STATE). */
 int kx_test_conv1d_opts(int device_id, const float* x, int B, int Cin, int L, const int32_t* lens, int pad_ld, const float* w,
                         const float* bias, int Cout, int k, int pad, int dil, int act, float slope, const float* alpha,
                         const float* norm, const float* resid, int accumulate, float out_mul, float out_div, float* y,

@@ -2,6 +2,7 @@
 // against libkokorox_hip.so -- the production library exports none of them.  The conv hooks take their weight images, launch
 // plan and kernel arguments from conv_call.hip, the code Model runs; what is theirs is the buffers, the tensor views over them
 // and the checks around the launch.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -82,7 +83,14 @@ struct ConvTestExtra {  // epilogue forms beyond bias: residual, accumulate into
     const float* norm_gb = nullptr;  // [B][2 Cout] (gamma | beta): finalize the conv's own partial sums into ...
     float* norm_out = nullptr;       // ... [3][B][Cout] = mean, scale, shift (launch_stats_finalize)
     int64_t* plan_out = nullptr;     // [17] the ConvPlan that was launched, fields as kx_test_conv_plan returns them
+    // the generator's length maps (opts[8 ..] of kx_test_conv1d_opts).  len_mul_in > 0: lens[] are units (the model's frames), utterance
+    // b stores lens[b] * len_mul_in + len_add_in input columns and owns lens[b] * len_mul_out + len_add_out output columns
+    int len_mul_in = 0, len_add_in = 0, len_mul_out = 0, len_add_out = 0;
+    int view = 0;    // x, resid and y are row slices of taller tensors: VIEW_TOP foreign rows above them, VIEW_ROWS - VIEW_TOP below
+    int strict = 0;  // a call that uses one of these fields: unowned output columns hold the sentinel, guard bytes behind the buffers
 };
+constexpr int VIEW_ROWS = 8, VIEW_TOP = 3, GUARD = 16;  // (GUARD floats = 64 bytes)
+const float GUARD_VALUE = 7.25e9f;
 }  // namespace
 
 // a ConvPlan as the 17 integers kx_test_conv_plan and kx_test_conv1d_opts return
@@ -113,11 +121,14 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         KX_REQUIRE(!pre || mode == kx::CONV_F16X3 || mode == kx::CONV_F16X3_DA, "test_conv1d: pre-split images exist for the direct-A kernels only");
         // row strides: the caller's dense rows, or (pad_ld) the model's: a multiple of 32 floats, input padding poisoned
         const int Ly = Lout + ex.up_off;  // columns of y (Lout: the conv's own output length)
-        KX_REQUIRE(ex.up_off == 0 || (transposed && ex.up_off == 1 && !ex.pad_ld), "test_conv1d: an output offset comes with transposed convs");
+        KX_REQUIRE(ex.up_off == 0 || (transposed && ex.up_off == 1), "test_conv1d: an output offset comes with transposed convs");
+        KX_REQUIRE(stride >= 1 && (transposed || stride == 1 || (!ex.merged && !ex.in_up2 && !ex.tmajor)),
+                   "test_conv1d: a strided conv takes no merged, in_up2 or time-major launch");
+        KX_REQUIRE(!ex.view || !ex.tmajor, "test_conv1d: row-slice views of channel-major tensors only");
         // (time-major stores: a row of y is one column's Cout values; padded, it ends in a 32-float margin)
-        const int yr = ex.tmajor ? Lout : Cout, yc = ex.tmajor ? Cout : Lout;  // rows per utterance and columns of y as stored
+        const int yr = ex.tmajor ? Lout : Cout, yc = ex.tmajor ? Cout : Ly;  // rows per utterance and columns of y as stored
         const int x_ld = ex.pad_ld ? (L + 31) & ~31 : L;
-        const int y_ld = ex.tmajor ? (ex.pad_ld ? ((Cout + 31) & ~31) + 32 : Cout) : (ex.pad_ld ? (Lout + 31) & ~31 : Ly);
+        const int y_ld = ex.tmajor ? (ex.pad_ld ? ((Cout + 31) & ~31) + 32 : Cout) : (ex.pad_ld ? (Ly + 31) & ~31 : Ly);
         const int Lv = ex.in_up2 ? 2 * L : L;  // the input length the conv sees
         const bool want_stats = ex.stats_out != nullptr || ex.norm_out != nullptr;
         KX_REQUIRE(!ex.tmajor || (!transposed && !ex.resid && !ex.accum && !want_stats), "test_conv1d: time-major stores are plain stores");
@@ -128,10 +139,56 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         KX_REQUIRE(!transposed || (k == 2 * stride && pad == (k - stride) / 2 && dil == 1), "test_conv1d: transposed needs k=2s, pad=(k-s)/2");
         KX_REQUIRE(act != kx::ACT_SNAKE || alpha, "test_conv1d: snake needs alpha");
         const float poison = std::nanf(""), sentinel = -12345.5f;
-        auto padded = [&](const float* src, int rows_total, int len, int ld, float fill) {
-            std::vector<float> v((size_t)rows_total * ld, fill);
-            for (int r = 0; r < rows_total; ++r) std::memcpy(&v[(size_t)r * ld], src + (size_t)r * len, (size_t)len * 4);
+        // per utterance: the input columns it stores and the output columns it owns (without the offset column)
+        const int up = ex.in_up2 ? 2 : 1;
+        const bool units = ex.len_mul_in > 0;
+        std::vector<int> lin(B, L), lout(B, Lout);
+        KX_REQUIRE(ex.len_mul_in >= 0 && (units || (!ex.len_add_in && !ex.len_mul_out && !ex.len_add_out)), "test_conv1d: bad length map");
+        KX_REQUIRE(!units || (ex.lens && !ex.in_up2 && !ex.merged), "test_conv1d: length maps need lens, and no in_up2 or merged launch");
+        if (ex.lens) {  // ragged batch
+            KX_REQUIRE(units || (!transposed && stride == 1), "test_conv1d: ragged strided and transposed convs state their length maps");
+            for (int b = 0; b < B; ++b) {
+                if (units) {  // utterance b: lens[b] units; the output map must agree with the conv's own formula on the input count
+                    KX_REQUIRE(ex.lens[b] >= 1 && ex.lens[b] <= L, "test_conv1d: lens out of range");
+                    lin[b] = ex.lens[b] * ex.len_mul_in + ex.len_add_in;
+                    lout[b] = ex.lens[b] * ex.len_mul_out + ex.len_add_out;
+                    KX_REQUIRE(lin[b] >= 1 && lin[b] <= L, "test_conv1d: an utterance's input columns overrun L");
+                    const int want = transposed ? stride * lin[b] : (lin[b] + 2 * pad - dil * (k - 1) - 1) / stride + 1;
+                    KX_REQUIRE(lin[b] + 2 * pad - dil * (k - 1) - 1 >= 0 || transposed, "test_conv1d: lens out of range");
+                    KX_REQUIRE(lout[b] == want && lout[b] >= 1 && lout[b] <= Lout, "test_conv1d: the output length map contradicts the conv's own output count");
+                } else {  // utterance b is lens[b] columns long (stride-1 convs: the output shrinks by Lv - Lout)
+                    KX_REQUIRE(ex.lens[b] >= 1 && ex.lens[b] <= L && up * ex.lens[b] + (Lout - Lv) >= 1, "test_conv1d: lens out of range");
+                    lin[b] = ex.lens[b];
+                    lout[b] = up * ex.lens[b] + (Lout - Lv);
+                }
+                lens[b] = ex.lens[b];
+            }
+        } else if (ex.merged)
+            lens.assign(B, L);
+        // A [B][C][len] host tensor as the launch sees it: rows of ld floats (view: VIEW_TOP foreign rows above each utterance's C rows,
+        // VIEW_ROWS in all), with `fill` in the foreign rows, in [len, ld) and - own given - in the columns at or past own[b]; src null
+        // = zeros.  GUARD floats follow.
+        const int vrows = ex.view ? VIEW_ROWS : 0, vtop = ex.view ? VIEW_TOP : 0;
+        auto stage = [&](const float* src, int C, int len, int ld, float fill, const int* own, int own_add) {
+            std::vector<float> v((size_t)B * (C + vrows) * ld + GUARD, fill);
+            for (int b = 0; b < B; ++b)
+                for (int r = 0; r < C; ++r) {
+                    float* d = &v[((size_t)b * (C + vrows) + vtop + r) * ld];
+                    const int n = own ? std::min(len, own[b] + own_add) : len;
+                    if (src)
+                        std::memcpy(d, src + ((size_t)b * C + r) * len, (size_t)n * 4);
+                    else
+                        std::fill(d, d + n, 0.f);
+                }
+            std::fill(v.end() - GUARD, v.end(), GUARD_VALUE);
             return v;
+        };
+        auto guard_ok = [&](const float* d_end) {  // the GUARD floats behind a device buffer
+            float g[GUARD];
+            KX_HIP(hipMemcpy(g, d_end, sizeof g, hipMemcpyDeviceToHost));
+            for (float f : g)
+                if (f != GUARD_VALUE) return false;
+            return true;
         };
         const kx::DevAlloc alloc = [&dm](size_t bytes) -> void* { return dm.get<unsigned char>(bytes); };
 
@@ -151,45 +208,36 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
             KX_REQUIRE(cw.w16b, "test_conv1d: bf16 images exist for 128-row tiles");
         }
 
-        // the input and output views: dense = every utterance L columns ({lens, 0, L}), ragged = its own length
+        // the input and output views: dense = every utterance L columns ({lens, 0, L}), ragged = its own length.  A ragged call
+        // poisons what an utterance does not own: NaN in its input and residual columns at or past its length, whatever the caller has
+        // there; a strict one also starts its unowned output columns from the sentinel
         kx::T in, out, res;
-        if (ex.pad_ld) {
-            const std::vector<float> xp = padded(x, B * Cin, L, x_ld, poison);
-            in.p = dm.up(xp.data(), xp.size());
-        } else
-            in.p = dm.up(x, (size_t)B * Cin * L);
-        in.bs = (long)Cin * x_ld;
+        const std::vector<float> xp = stage(x, Cin, L, x_ld, poison, ex.lens ? lin.data() : nullptr, 0);
+        const size_t x_n = xp.size() - GUARD;
+        float* dx = dm.up(xp.data(), xp.size());
+        in.p = dx + (size_t)vtop * x_ld;
+        in.bs = (long)(Cin + vrows) * x_ld;
         in.ld = x_ld;
         in.C = Cin;
         in.Lmax = L;
-        const int up = ex.in_up2 ? 2 : 1;
         // (the merged kernels read the length array itself: a merged launch always carries real lengths)
         const bool ragged = ex.lens != nullptr || ex.merged;
-        if (ex.lens) {  // ragged batch: utterance b is lens[b] columns long (stride-1 convs: the output shrinks by Lv - Lout)
-            KX_REQUIRE(!transposed && stride == 1, "test_conv1d: ragged lengths with stride-1 convs only");
-            for (int b = 0; b < B; ++b) {
-                KX_REQUIRE(ex.lens[b] >= 1 && ex.lens[b] <= L && up * ex.lens[b] + (Lout - Lv) >= 1, "test_conv1d: lens out of range");
-                lens[b] = ex.lens[b];
-            }
-        } else if (ex.merged)
-            lens.assign(B, L);
         int* d_one = dm.up(lens.data(), B);
-        in.len = ragged ? kx::LenMap{d_one, 1, 0} : kx::LenMap{d_one, 0, L};  // (the stored columns: in_up2 doubles them in the launch)
-        float* dy = dm.get<float>((size_t)B * yr * y_ld);
-        if (ex.pad_ld) {  // y holds the running sum (accumulate) or zeros; the row padding holds a sentinel nobody may touch
-            std::vector<float> y0((size_t)B * yr * yc, 0.f);
-            const std::vector<float> yp = padded(ex.accum ? y : y0.data(), B * yr, yc, y_ld, sentinel);
-            KX_HIP(hipMemcpy(dy, yp.data(), yp.size() * 4, hipMemcpyHostToDevice));
-        } else if (ex.accum)
-            KX_HIP(hipMemcpy(dy, y, (size_t)B * Cout * Lout * 4, hipMemcpyHostToDevice));  // y holds the running sum
-        else
-            KX_HIP(hipMemset(dy, 0, (size_t)B * yr * y_ld * 4));
-        out.p = dy;
-        out.bs = (long)yr * y_ld;
+        // (the stored columns: in_up2 doubles them in the launch)
+        in.len = units ? kx::LenMap{d_one, ex.len_mul_in, ex.len_add_in} : (ragged ? kx::LenMap{d_one, 1, 0} : kx::LenMap{d_one, 0, L});
+        // y holds the running sum (accumulate) or zeros; the row padding holds a sentinel nobody may touch
+        const std::vector<float> y0 = stage(ex.accum ? y : nullptr, yr, yc, y_ld, sentinel, ex.strict && ex.lens ? lout.data() : nullptr, ex.up_off);
+        const size_t y_n = y0.size() - GUARD;
+        float* dy = dm.up(y0.data(), y0.size());
+        out.p = dy + (size_t)vtop * y_ld;
+        out.bs = (long)(yr + vrows) * y_ld;
         out.ld = y_ld;
         out.C = rows;
         out.Lmax = Lout;
-        out.len = ragged ? kx::LenMap{d_one, up, Lout - Lv} : kx::LenMap{d_one, 0, Lout};
+        const kx::LenMap own_len = units ? kx::LenMap{d_one, ex.len_mul_out, ex.len_add_out}
+                                         : (ragged ? kx::LenMap{d_one, up, Lout - Lv} : kx::LenMap{d_one, 0, Lout});
+        out.len = own_len;
+        out.len.add += ex.up_off;  // (the stored columns of y; an up-scattering launch masks with o.up_len)
 
         kx::ConvOpts o;
         if (transposed) {  // the polyphase two-tap GEMM, scattered to the up-sampled axis
@@ -198,7 +246,7 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
             o.up_pad = pad;
             o.up_off = ex.up_off;
             o.up_reflect = ex.up_reflect;
-            o.up_len = out.len;
+            o.up_len = own_len;
         } else {
             o.stride = stride;
             o.pad = pad;
@@ -219,14 +267,15 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         o.out_mul = ex.out_mul;
         o.out_div = ex.out_div;
         o.accum = ex.accum;
+        float* d_res = nullptr;
+        size_t r_n = 0;
         if (ex.resid) {
-            KX_REQUIRE(!transposed || !ex.pad_ld, "test_conv1d: residual of a transposed conv on dense rows only");
-            if (ex.pad_ld) {
-                const std::vector<float> rp = padded(ex.resid, B * Cout, Lout, y_ld, poison);
-                res.p = dm.up(rp.data(), rp.size());
-            } else
-                res.p = dm.up(ex.resid, (size_t)B * Cout * Ly);
-            res.bs = (long)Cout * y_ld;
+            // (laid out as y is: its own Ly columns, NaN behind them and past an utterance's own output)
+            const std::vector<float> rp = stage(ex.resid, Cout, Ly, y_ld, poison, ex.lens ? lout.data() : nullptr, ex.up_off);
+            r_n = rp.size() - GUARD;
+            d_res = dm.up(rp.data(), rp.size());
+            res.p = d_res + (size_t)vtop * y_ld;
+            res.bs = (long)(Cout + vrows) * y_ld;
             res.ld = y_ld;
             o.resid = &res;
         }
@@ -251,10 +300,13 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         const kx::ConvArgs& a = call.a;
         if (ex.plan_out) plan_fields(plan, ex.plan_out);
         float2* d_part = nullptr;
+        size_t part_n = 0;
         if (want_stats) {
             KX_REQUIRE(!transposed && !ex.accum && plan.stat_cols > 0, "test_conv1d: fused statistics come with plain, non-accumulating stores");
-            d_part = dm.get<float2>((size_t)B * rows * plan.stat_tiles);
-            KX_HIP(hipMemset(d_part, 0, (size_t)B * rows * plan.stat_tiles * sizeof(float2)));
+            part_n = (size_t)B * rows * plan.stat_tiles;
+            std::vector<float> p0(2 * part_n + GUARD, 0.f);
+            std::fill(p0.end() - GUARD, p0.end(), GUARD_VALUE);
+            d_part = reinterpret_cast<float2*>(dm.up(p0.data(), p0.size()));
             call.set_stats(d_part);
         }
         if (plan.flat_bn) {
@@ -272,16 +324,25 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         }
         kx::launch_conv(plan, a, B, nullptr);
         KX_HIP(hipDeviceSynchronize());
-        if (ex.pad_ld) {
-            std::vector<float> yp((size_t)B * yr * y_ld);
-            KX_HIP(hipMemcpy(yp.data(), dy, yp.size() * 4, hipMemcpyDeviceToHost));
-            for (int r = 0; r < B * yr; ++r) {
-                std::memcpy(y + (size_t)r * yc, &yp[(size_t)r * y_ld], (size_t)yc * 4);
-                for (int c = yc; c < y_ld; ++c)
-                    if (yp[(size_t)r * y_ld + c] != sentinel) throw Error(KX_ERR_STATE, "test_conv1d: the kernel wrote into the row padding");
-            }
-        } else
-            KX_HIP(hipMemcpy(y, dy, (size_t)B * yr * y_ld * 4, hipMemcpyDeviceToHost));
+        {
+            std::vector<float> yp(y_n);
+            KX_HIP(hipMemcpy(yp.data(), dy, y_n * 4, hipMemcpyDeviceToHost));
+            for (int b = 0; b < B; ++b)
+                for (int r = 0; r < yr + vrows; ++r) {
+                    const float* row = &yp[((size_t)b * (yr + vrows) + r) * y_ld];
+                    const bool foreign = r < vtop || r >= vtop + yr;
+                    if (!foreign) std::memcpy(y + ((size_t)b * yr + (r - vtop)) * yc, row, (size_t)yc * 4);
+                    for (int c = foreign ? 0 : yc; c < y_ld; ++c)
+                        if (row[c] != sentinel)
+                            throw Error(KX_ERR_STATE, foreign ? "test_conv1d: the kernel wrote into a foreign row of the output tensor"
+                                                              : "test_conv1d: the kernel wrote into the row padding");
+                }
+        }
+        if (ex.strict) {
+            const bool ok = guard_ok(dx + x_n) && guard_ok(dy + y_n) && (!d_res || guard_ok(d_res + r_n)) &&
+                            (!d_part || guard_ok(reinterpret_cast<const float*>(d_part) + 2 * part_n));
+            if (!ok) throw Error(KX_ERR_STATE, "test_conv1d: the guard bytes behind a buffer changed");
+        }
         if (ex.norm_out) {  // the model's route from the partial sums to the next conv's AdaIN planes (Model::stats)
             const float* d_gb = dm.up(ex.norm_gb, (size_t)B * 2 * rows);
             float* d_pl = dm.get<float>((size_t)3 * B * rows);
@@ -293,8 +354,9 @@ static int test_conv1d_impl(int device_id, const float* x, int B, int Cin, int L
         if (ex.stats_out) {
             std::vector<float2> part((size_t)B * rows * a.stat_tiles);
             KX_HIP(hipMemcpy(part.data(), d_part, part.size() * sizeof(float2), hipMemcpyDeviceToHost));
-            const int used = (Lout + plan.stat_cols - 1) / plan.stat_cols;
             for (size_t br = 0; br < (size_t)B * rows; ++br) {
+                // (the tiles of the row's own output columns: a ragged row's later slots are never written)
+                const int used = (lout[br / rows] + plan.stat_cols - 1) / plan.stat_cols;
                 double sm = 0.0, sq = 0.0;
                 for (int t = 0; t < used && t < a.stat_tiles; ++t) {
                     sm += part[br * a.stat_tiles + t].x;
@@ -365,8 +427,8 @@ int kx_test_conv1d_opts(int device_id, const float* x, int B, int Cin, int L, co
                         float* stats_out, int mode, const int32_t* opts, int n_opts, const float* norm_gb, float* norm_out,
                         int64_t* plan_out, char* err, size_t err_len) {
     ConvTestExtra ex;
-    if (!opts || n_opts != 8 || !plan_out || opts[7] < 0)
-        return guarded_free(err, err_len, [] { throw Error(KX_ERR_INVALID, "test_conv1d_opts: 8 options in, 17 plan fields out"); });
+    if (!opts || (n_opts != 8 && n_opts != 15) || !plan_out || opts[7] < 0)
+        return guarded_free(err, err_len, [] { throw Error(KX_ERR_INVALID, "test_conv1d_opts: 8 or 15 options in, 17 plan fields out"); });
     ex.resid = resid;
     ex.accum = accumulate;
     ex.out_mul = out_mul;
@@ -385,13 +447,26 @@ int kx_test_conv1d_opts(int device_id, const float* x, int B, int Cin, int L, co
     ex.norm_gb = norm_gb;
     ex.norm_out = norm_out;
     ex.plan_out = plan_out;
+    int stride = 1;
+    if (n_opts == 15) {
+        stride = opts[8];
+        ex.len_mul_in = opts[9];
+        ex.len_add_in = opts[10];
+        ex.len_mul_out = opts[11];
+        ex.len_add_out = opts[12];
+        ex.up_off = ex.up_reflect = opts[13] != 0;
+        ex.view = opts[14] != 0;
+        ex.strict = stride != 1 || ex.len_mul_in || ex.len_add_in || ex.len_mul_out || ex.len_add_out || ex.up_off || ex.view;
+        if (stride < 1 || (stride > 1 && opts[7]))
+            return guarded_free(err, err_len, [] { throw Error(KX_ERR_INVALID, "test_conv1d_opts: stride >= 1, with plain convs only"); });
+    }
     if (const int s = opts[7]) {  // a polyphase transposed conv (kx_test_conv_transpose: k = 2 s, pad = s / 2, w [Cin,Cout,k]) with these options
         const int pd = (k - s) / 2;
         return test_conv1d_impl(device_id, x, B, Cin, L, w, bias, Cout, k, s, pd, 1, 1, act, slope, alpha, norm, y, (L - 1) * s - 2 * pd + k,
                                 mode, ex, err, err_len);
     }
-    const int Lout = (ex.in_up2 ? 2 * L : L) + 2 * pad - dil * (k - 1);
-    return test_conv1d_impl(device_id, x, B, Cin, L, w, bias, Cout, k, 1, pad, dil, 0, act, slope, alpha, norm, y, Lout, mode, ex,
+    const int Lout = ((ex.in_up2 ? 2 * L : L) + 2 * pad - dil * (k - 1) - 1) / stride + 1;
+    return test_conv1d_impl(device_id, x, B, Cin, L, w, bias, Cout, k, stride, pad, dil, 0, act, slope, alpha, norm, y, Lout, mode, ex,
                             err, err_len);
 }
 

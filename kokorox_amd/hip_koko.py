@@ -1062,25 +1062,32 @@ def conv1d_full(x, w, bias=None, pad=0, dil=1, act=0, slope=0.0, alpha=None, nor
 def conv1d_opts(x, w, bias=None, pad=0, dil=1, act=0, slope=0.0, alpha=None, norm=None, resid=None, y_init=None,
                 out_mul=1.0, out_div=1.0, want_stats=False, lens=None, pad_ld=False, flat=False, mode=1, device=0, pre=False,
                 in_up2=False, epi=0, merged=False, tmajor=False, prec1=0, act_shift=0, epi_stream=False, want_norm=None,
-                up_stride=0):
+                up_stride=0, stride=1, len_in=None, len_out=None, up_off=False, view=False):
     """conv1d_full plus the launch options Model::conv sets (include/kokorox_hip_test.h, kx_test_conv1d_opts): in_up2 (x [B,Cin,L]
     read as 2 L columns), epi (1 = gelu_new), merged (the plan may merge the batch's columns), tmajor (y [B,Lout,Cout]), prec1,
     act_shift, epi_stream, up_stride (s > 0: the polyphase transposed conv instead, w [Cin,Cout,2 s]); want_norm = gb [B,2 Cout]: the fused partial sums finalized into (mean, scale, shift) [3,B,Cout].
-    Returns a dict: y, plan (the ConvPlan that ran, as conv_plan returns it), and stats / norm when asked for."""
+    stride (plain convs), len_in / len_out = (mul, add): lens[] are units (the model's frames) and utterance b has lens[b] * mul + add
+    input / output columns, up_off (with up_stride: the output starts at column 1, column 0 is its reflection; y and resid are
+    [B,Cout,Lout + 1]), view (x, resid and y are row slices of taller tensors).  A call that uses one of these five gets unowned output
+    columns back as LN_SENTINEL.
+    Returns a dict: y at its stored shape, plan (the ConvPlan that ran, as conv_plan returns it), and stats / norm when asked for."""
     lib = load_test_library()
     x, w = _f32(x), _f32(w)
     B, Cin, L = x.shape
     Cout, _, k = w.shape
-    Lout = (2 * L if in_up2 else L) + 2 * pad - dil * (k - 1)
+    Lout = ((2 * L if in_up2 else L) + 2 * pad - dil * (k - 1) - 1) // stride + 1
     if up_stride:
         Cout = w.shape[1]
         assert k == 2 * up_stride
-        Lout = (L - 1) * up_stride - 2 * ((k - up_stride) // 2) + k
+        Lout = (L - 1) * up_stride - 2 * ((k - up_stride) // 2) + k + (1 if up_off else 0)
     shape = (B, Lout, Cout) if tmajor else (B, Cout, Lout)
     y = np.zeros(shape, dtype=np.float32) if y_init is None else _f32(y_init).copy()
     st = np.zeros((B, Cout, 2), dtype=np.float32) if want_stats else None
     ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
-    opts = np.array([in_up2, epi, merged, tmajor, prec1, act_shift, epi_stream, up_stride], dtype=np.int32)
+    opts = [in_up2, epi, merged, tmajor, prec1, act_shift, epi_stream, up_stride]
+    if stride != 1 or len_in is not None or len_out is not None or up_off or view:
+        opts += [stride, *(len_in or (0, 0)), *(len_out or (0, 0)), up_off, view]
+    opts = np.array(opts, dtype=np.int32)
     gb = _f32(want_norm)
     planes = None if gb is None else np.zeros((3, B, Cout), dtype=np.float32)
     assert gb is None or gb.shape == (B, 2 * Cout)
