@@ -1,6 +1,7 @@
 /* Test hooks of libkokorox_hip (tests/ only): stand-alone runs of single kernels on host arrays and two process-wide test
- * switches.  They live in a library of their own, libkokorox_hip_test.so (kokorox_amd/csrc/test_hooks.hip), which links against
- * libkokorox_hip.so; the production library exports none of them. */
+ * switches.  They live in a library of their own, libkokorox_hip_test.so (kokorox_amd/csrc/test_hooks_*.hip, one unit per job: conv
+ * launches, the token-axis front half, the back half's other kernels, the output stage), which links against libkokorox_hip.so; the
+ * production library exports none of them. */
 #ifndef KOKOROX_HIP_TEST_H
 #define KOKOROX_HIP_TEST_H
 #include "kokorox_hip.h"
@@ -8,82 +9,70 @@
 extern "C" {
 #endif
 
-/* Stand-alone run of the conv1d MFMA kernel on host arrays (x [B,Cin,L], w [Cout,Cin,k]
- * or, for transposed = 1, [Cin,Cout,k]); y must hold B*Cout*Lout floats.  act: 0 none,
- * 1 leaky(slope), 2 snake(alpha[Cin]); norm = optional [3,B,Cin] (mean, scale, shift);
- * mode as in kx_set_conv_mode, plus 2 = f16x3 on the LDS-DMA kernel forms only (conv_f16x3.hip: what the direct-A
- * kernels are compared with bit for bit) and 3 = f16x3 through the direct-A kernel whatever the grid; + 0x100 (modes 1 and 3,
- * here and in the other conv hooks) = the input staged through a pre-split image (conv_f16x3_pre.hip) whatever the row count;
- * + 0x200 = f16f8 (the layer carries the 8-bit cross image of its weights); + 0x400 = the direct-A conv's 256-column tile with
- * the 4 x 1 wave layout too (not the 2 x 2 one); + 0x800 = no 16x16x32 form. */
-int kx_test_conv1d(int device_id, const float* x, int B, int Cin, int L, const float* w,
-                   const float* bias, int Cout, int k, int stride, int pad, int dil,
-                   int transposed, int act, float slope, const float* alpha,
-                   const float* norm, float* y, int Lout, int mode, char* err, size_t err_len);
+/* One conv launch as the model assembles it (conv_call.hip: the model's packers, plan and kernel arguments), on host arrays.
+ * Fields that are left 0 / NULL are off; out_mul and out_div must be set (1 = off).  Every ragged call (lens given): the hook writes
+ * NaN into every input and residual column at or past an utterance's own length; what the caller has there is not uploaded.  A
+ * STRICT call -- one with stride != 1, a length map, up_off or view -- also gets -12345.5 back in every output column the utterance
+ * does not own (other calls: 0, or the running sum), and has 64 guard bytes behind x, y, resid and the partial-sum table checked
+ * (KX_ERR_STATE).  Contradictory fields are KX_ERR_INVALID before any launch. */
+typedef struct kx_test_conv_args {
+    uint32_t struct_size;   /* sizeof(kx_test_conv_args): any other value is KX_ERR_INVALID, before the device is looked at */
+    int32_t device_id;
+    const float* x;         /* [B,Cin,L] */
+    const float* w;         /* [Cout,Cin,k]; up_stride > 0: [Cin,Cout,k] */
+    const float* bias;      /* [Cout] or NULL */
+    const float* alpha;     /* [Cin], act = 2 */
+    const float* norm;      /* [3,B,Cin] (mean, scale, shift): the fused AdaIN affine on the input, or NULL */
+    const float* resid;     /* [B,Cout,Lout + up_off], added in the store, or NULL */
+    const int32_t* lens;    /* [B]: a RAGGED batch, utterance b is lens[b] columns long (columns past its output length stay as they
+                             * were, its statistics cover its own columns only); with a length map, lens[b] units.  NULL = all L */
+    float* y;               /* [B,Cout,Lout + up_off], tmajor: [B,Lout,Cout].  Lout = ((in_up2 ? 2 L : L) + 2 pad - dil (k-1) - 1) /
+                             * stride + 1, up_stride = s > 0: (L-1) s - 2 pad + k.  Read as the running sum when accumulate != 0 */
+    int64_t y_floats;       /* floats the caller allocated for y: fewer than the stored shape is KX_ERR_INVALID */
+    float* stats_out;       /* [B,Cout,2] or NULL: the fused InstanceNorm partial sums (sum, sum of squares of each stored row; a
+                             * ragged row: the slots of its own output columns) */
+    const float* norm_gb;   /* [B,2 Cout] (gamma | beta), with norm_out: the conv's own partial sums go through launch_stats_finalize */
+    float* norm_out;        /* ... and come back as the next conv's [3,B,Cout] (mean, scale, shift) planes */
+    int64_t* plan_out;      /* [17] or NULL: the kx::ConvPlan that was launched, fields as in kx_test_conv_plan */
+    int32_t B, Cin, L, Cout, k;
+    int32_t stride;         /* >= 1, plain convs; a strided conv is refused a merged, in_up2 or time-major launch */
+    int32_t pad, dil;
+    int32_t up_stride;      /* s > 0: the polyphase transposed conv of the generator's upsamplers (needs k = 2 s, pad = (k - s) / 2,
+                             * dil = 1, stride = 1); ragged only with a length map */
+    int32_t act;            /* on the input: 0 none, 1 leaky(slope), 2 snake(alpha) */
+    float slope;
+    int32_t accumulate;     /* y = (conv + bias + resid [+ y]) * out_mul / out_div */
+    float out_mul, out_div;
+    int32_t mode;           /* as in kx_set_conv_mode, plus 2 = f16x3 on the LDS-DMA kernel forms only (conv_f16x3.hip: what the
+                             * direct-A kernels are compared with bit for bit) and 3 = f16x3 through the direct-A kernel whatever the
+                             * grid; + 0x100 (modes 1 and 3) = the input staged through a pre-split image (conv_f16x3_pre.hip) whatever
+                             * the row count; + 0x200 = f16f8 (the layer carries the 8-bit cross image of its weights); + 0x400 = the
+                             * direct-A conv's 256-column tile with the 4 x 1 wave layout too; + 0x800 = no 16x16x32 form */
+    int32_t pad_ld;         /* rows padded to a multiple of 32 floats as the model lays them out: input and residual padding is NaN,
+                             * the output padding [Lout + up_off, y_ld) holds a sentinel that must survive (KX_ERR_STATE) */
+    int32_t flat;           /* the flat list of live tiles the model hands the direct-A kernels on a batch of more than one utterance */
+    int32_t in_up2;         /* the conv reads x[p >> 1]: x stands for 2 L columns, lens[] are stored lengths */
+    int32_t epi;            /* kx::ConvEpi: 1 = gelu_new */
+    int32_t merged;         /* offer the plan ConvLaunch::merge_T = L, as the model does for every conv whose input and output share
+                             * one plain length array; the plan decides */
+    int32_t tmajor;         /* ST_TMAJOR; with pad_ld its rows of Cout values end in a checked margin */
+    int32_t prec1;          /* 1 / 2 = one f16 / bf16 MFMA per product, 2 on the bf16 weight image of Model::set_conv_mode */
+    int32_t act_shift;      /* x_prescale = 2^act_shift, w_unscale its inverse, as kx_set_act_prescale sets them */
+    int32_t epi_stream;     /* ConvArgs::epi_stream */
+    int32_t len_mul_in, len_add_in, len_mul_out, len_add_out;
+                            /* len_mul_in > 0: lens[b] are UNITS (the model's frames); utterance b stores lens[b] len_mul_in +
+                             * len_add_in input columns (<= L) and owns lens[b] len_mul_out + len_add_out output columns, and in.len,
+                             * out.len and up_len are those LenMaps over one device array, as in Model::back_half.  The output count
+                             * must be the conv's own on the input count.  len_mul_in = 0 keeps {lens, 1, 0} in and {lens, 1 or 2,
+                             * Lout - L} out (stride 1, plain convs only) */
+    int32_t up_off;         /* with up_stride: the output starts at column 1 of y and column 0 is its reflection
+                             * (ReflectionPad1d((1, 0)), the last upsampler) */
+    int32_t view;           /* x and resid each sit 3 rows below the top of a tensor 8 rows taller than they are, y likewise, and the
+                             * batch strides are those of the taller tensors; the foreign input and residual rows hold NaN, the
+                             * foreign output rows the sentinel, and a changed one is KX_ERR_STATE */
+} kx_test_conv_args;
 
-/* A polyphase transposed conv (k = 2 stride, pad = stride / 2) as the generator's upsamplers run it: x [B,Cin,L], w [Cin,Cout,k],
- * fused leaky input activation, residual [B,Cout,Ly] added in the scatter store; up_off = 1: the output starts at column 1 of y
- * and column 0 is its reflection (ReflectionPad1d((1, 0)), the last upsampler), Ly = Lout + up_off, Lout = (L-1) stride - 2 pad + k.
- * mode as kx_test_conv1d, + 0x100 = through a pre-split input image. */
-int kx_test_conv_transpose(int device_id, const float* x, int B, int Cin, int L, const float* w, const float* bias, int Cout,
-                           int stride, int act, float slope, const float* resid, int up_off, float* y, int mode, char* err,
-                           size_t err_len);
-
-/* The epilogue forms of the same kernel on a stride-1 conv: y = (conv + bias + resid [+ y]) * out_mul / out_div
- * with y [B,Cout,Lout] (Lout = L + 2 pad - dil (k-1)) read as the running sum when accumulate != 0, and - when
- * stats_out [B,Cout,2] is given - the fused InstanceNorm partial sums (sum, sum of squares of each stored row). */
-int kx_test_conv1d_epilogue(int device_id, const float* x, int B, int Cin, int L, const float* w,
-                            const float* bias, int Cout, int k, int pad, int dil, const float* resid,
-                            int accumulate, float out_mul, float out_div, float* y, float* stats_out,
-                            int mode, char* err, size_t err_len);
-
-/* Both at once, as the generator's resblock convs run: fused AdaIN affine + activation on the input AND the epilogue forms
- * (residual / running sum / scale / fused statistics), on a RAGGED batch when lens [B] is given (utterance b is lens[b]
- * columns long: columns past its output length stay as they were, its statistics cover its own columns only) and, with
- * pad_ld & 1, on rows padded to a multiple of 32 floats as the model lays them out (input and residual padding is NaN,
- * the output padding holds a sentinel that must survive); pad_ld & 2 = the flat list of live tiles the model hands the
- * direct-A kernels on a batch of more than one utterance instead of a (longest length) x B grid.  Stride 1, not transposed. */
-int kx_test_conv1d_full(int device_id, const float* x, int B, int Cin, int L, const int32_t* lens, int pad_ld,
-                        const float* w, const float* bias, int Cout, int k, int pad, int dil, int act, float slope,
-                        const float* alpha, const float* norm, const float* resid, int accumulate, float out_mul,
-                        float out_div, float* y, float* stats_out, int mode, char* err, size_t err_len);
-
-/* kx_test_conv1d_full plus what Model::conv sets on top of it.  opts[8] = in_up2 (the conv reads x[p >> 1]: x [B,Cin,L] stands for
- * 2 L columns, lens[] are stored lengths), epi (kx::ConvEpi: 1 = gelu_new), merged (offer the plan ConvLaunch::merge_T = L as the
- * model does for every conv whose input and output share one plain length array; the plan decides, ConvArgs::merge_T / merge_B
- * follow it), tmajor (ST_TMAJOR: y is [B,Lout,Cout]; with pad_ld & 1 its rows of Cout values end in a checked margin), prec1 (0, or
- * 1 / 2 = one f16 / bf16 MFMA per product, 2 on the bf16 weight image built as Model::set_conv_mode builds it), act_shift
- * (x_prescale = 2^act_shift, w_unscale its inverse, as kx_set_act_prescale sets them), epi_stream (ConvArgs::epi_stream), up_stride
- * (s > 0: the polyphase transposed conv of kx_test_conv_transpose instead, w [Cin,Cout,2 s], Lout = (L-1) s - 2 (s/2) + 2 s; ragged only with the length maps below).
- * norm_gb [B,2 Cout] (gamma | beta) with norm_out [3,B,Cout]: the conv's own fused partial sums go through launch_stats_finalize
- * and come back as the next conv's (mean, scale, shift) planes.  plan_out[17]: the kx::ConvPlan that was launched, fields as in
- * kx_test_conv_plan.  Lout = ((in_up2 ? 2 L : L) + 2 pad - dil (k-1) - 1) / stride + 1.
- *
- * n_opts = 15 appends the generator's launches; with 8 options, or with all seven appended fields at their defaults, the call is
- * the one above.  opts[8] = stride (1 by default; plain convs only; a strided conv is refused a merged, in_up2 or time-major
- * launch: KX_ERR_INVALID).  opts[9 .. 12] = len_mul_in, len_add_in, len_mul_out, len_add_out: with len_mul_in > 0 lens[b] are UNITS
- * (the model's frames); utterance b stores lens[b] len_mul_in + len_add_in input columns (<= L) and owns lens[b] len_mul_out +
- * len_add_out output columns, and in.len, out.len and up_len are those LenMaps over one device array, as in Model::back_half.  The
- * output count must be the conv's own on the input count -- plain (Lin + 2 pad - dil (k-1) - 1) / stride + 1, polyphase s Lin --
- * or the call is refused before any launch (KX_ERR_INVALID), as are units that overrun L.  A ragged strided or polyphase call states
- * its maps (len_mul_in = 0 keeps {lens, 1, 0} in and {lens, 1 or 2, Lout - L} out, stride 1 only).  opts[13] = up_off (with up_stride
- * > 0: the output starts at column 1 of y and column 0 is its reflection, as in kx_test_conv_transpose; y and resid are
- * [B,Cout,Lout + 1]; KX_ERR_INVALID without up_stride).  opts[14] = view: x and resid each sit 3 rows below the top of a tensor 8
- * rows taller than they are, y likewise, and the batch strides are those of the taller tensors (x_bs != Cin x_ld); the foreign input
- * and residual rows hold NaN, the foreign output rows the sentinel, and a changed one is KX_ERR_STATE.
- * With these fields a ragged batch, padded rows (pad_ld & 1: y_ld rounds Lout + up_off up to 32, the residual is padded from its own
- * Lout + up_off columns, the checked padding is [Lout + up_off, y_ld)) and the flat tile list go with stride > 1, with up_stride,
- * with up_off and with the residual of a transposed conv; fused statistics (stats_out, norm_gb / norm_out) go with stride > 1, and
- * stats_out adds the slots of the row's own output columns.
- * Every ragged call of the conv hooks (lens given), old or new: the hook writes NaN into every input and residual column at or
- * past an utterance's own length; what the caller has there is not uploaded.  A call that uses an appended field also gets
- * -12345.5 back in every output column the utterance does not own (other calls: 0, or the running sum), and has 64 guard bytes
- * behind x, y, resid and the partial-sum table checked (KX_ERR_STATE). */
-int kx_test_conv1d_opts(int device_id, const float* x, int B, int Cin, int L, const int32_t* lens, int pad_ld, const float* w,
-                        const float* bias, int Cout, int k, int pad, int dil, int act, float slope, const float* alpha,
-                        const float* norm, const float* resid, int accumulate, float out_mul, float out_div, float* y,
-                        float* stats_out, int mode, const int32_t* opts, int n_opts, const float* norm_gb, float* norm_out,
-                        int64_t* plan_out, char* err, size_t err_len);
+int kx_test_conv(const kx_test_conv_args* args, char* err, size_t err_len);
 
 /* Stand-alone channel layer norm (launch_layernorm_ch) of x [B,C,T] over C, on rows padded to 32 floats (input padding NaN, output
  * padding checked): mode 0 plain, 1 affine (g, be [C]), 2 adaptive ((1 + g) xhat + be, g, be [B,C]); leaky != 0: leaky ReLU on the

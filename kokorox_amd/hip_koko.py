@@ -173,35 +173,18 @@ TEST_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libkokorox_hip_test.so"
 _test_lib = None
 
 
-def load_test_library() -> C.CDLL:
-    """dlopen libkokorox_hip_test.so: the stand-alone kernel hooks of tests/ (include/kokorox_hip_test.h).  It links against
-    libkokorox_hip.so, which is loaded first (same torch-first rule)."""
-    global _test_lib
-    if _test_lib is not None:
-        return _test_lib
-    load_library()
-    p = os.environ.get("KX_TEST_LIB") or TEST_LIB_PATH
-    if not os.path.exists(p):
-        raise FileNotFoundError(f"{p} is missing: build it with `python -m kokorox_amd.build` (hipcc, gfx950)")
-    lib = C.CDLL(p)
+def _test_signatures():
+    """Every hook of include/kokorox_hip_test.h, once: name -> (result, argument types)."""
     vp, i32, i64, u32, u64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
     cp, sz = C.c_char_p, C.c_size_t
-    sig = {
-        "kx_test_conv1d": (i32, [i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp,
-                                 i32, i32, cp, sz]),
-        "kx_test_conv1d_full": (i32, [i32, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, i32, f32,
-                                      f32, vp, vp, i32, cp, sz]),
-        "kx_test_conv_transpose": (i32, [i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, f32, vp, i32, vp, i32, cp, sz]),
+    return {
+        "kx_test_conv": (i32, [vp, cp, sz]),
         "kx_test_lstm": (i32, [i32, vp, i32, i32, i32] + [vp] * 9 + [cp, sz]),
         "kx_test_source": (i32, [i32, vp, i32, i32, vp, f32, u64, u64, i32, vp, cp, sz]),
         "kx_test_attention": (i32, [i32, vp, vp, i32, i32, vp, cp, sz]),
         "kx_test_lstm_fault": (i32, [i32]),
-        "kx_test_conv1d_epilogue": (i32, [i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, i32, f32, f32, vp, vp,
-                                          i32, cp, sz]),
         "kx_test_lstm_parts": (i32, [i32]),
         "kx_test_conv_plan": (i32, [vp, i32, vp, i32, cp, sz]),
-        "kx_test_conv1d_opts": (i32, [i32, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, i32, f32,
-                                      f32, vp, vp, i32, vp, i32, vp, vp, vp, cp, sz]),
         "kx_test_layernorm": (i32, [i32, vp, i32, i32, i32, vp, f32, i32, vp, vp, f32, vp, cp, sz]),
         "kx_test_instance_norm": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, cp, sz]),
         "kx_test_output_plan": (i32, [i32, vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, cp, sz]),
@@ -220,7 +203,20 @@ def load_test_library() -> C.CDLL:
         "kx_test_pool_up2": (i32, [i32, vp, i32, i32, i32, vp, vp, i32, vp, vp, f32, vp, cp, sz]),
         "kx_test_weight_images": (i32, [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, cp, sz]),
     }
-    for name, (res, args) in sig.items():
+
+
+def load_test_library() -> C.CDLL:
+    """dlopen libkokorox_hip_test.so: the stand-alone kernel hooks of tests/ (include/kokorox_hip_test.h).  It links against
+    libkokorox_hip.so, which is loaded first (same torch-first rule)."""
+    global _test_lib
+    if _test_lib is not None:
+        return _test_lib
+    load_library()
+    p = os.environ.get("KX_TEST_LIB") or TEST_LIB_PATH
+    if not os.path.exists(p):
+        raise FileNotFoundError(f"{p} is missing: build it with `python -m kokorox_amd.build` (hipcc, gfx950)")
+    lib = C.CDLL(p)
+    for name, (res, args) in _test_signatures().items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -228,11 +224,7 @@ def load_test_library() -> C.CDLL:
     return lib
 
 
-TEST_ABI_SYMBOLS = ["kx_test_conv1d", "kx_test_lstm", "kx_test_source", "kx_test_attention", "kx_test_conv1d_epilogue", "kx_test_conv1d_full",
-                    "kx_test_conv_transpose", "kx_test_lstm_fault", "kx_test_lstm_parts", "kx_test_conv_plan", "kx_test_conv1d_opts",
-                    "kx_test_layernorm", "kx_test_instance_norm", "kx_test_output_plan", "kx_test_output_plan_levelled", "kx_test_output_plan_loudness",
-                    "kx_test_lstm_ragged", "kx_test_alignment", "kx_test_embed", "kx_test_style_fc", "kx_test_rows", "kx_test_source_ragged",
-                    "kx_test_stft", "kx_test_istft_head", "kx_test_pool_up2", "kx_test_weight_images"]
+TEST_ABI_SYMBOLS = list(_test_signatures())
 
 ABI_SYMBOLS = [
     "kx_version", "kx_init", "kx_create", "kx_import_onnx", "kx_resample_filter", "kx_create_from_device_blob", "kx_create_replicas", "kx_replicas_times", "kx_create_partition", "kx_destroy",
@@ -963,27 +955,66 @@ CONV_F32, CONV_F16X3, CONV_F16F8 = 0, 1, 6
 STFT_ONNX, STFT_TORCH = 0, 1
 
 
+class ConvArgs(C.Structure):
+    """kx_test_conv_args of include/kokorox_hip_test.h, member for member (tests/test_host_cpu.py compares the two)."""
+    _fields_ = ([("struct_size", C.c_uint32), ("device_id", C.c_int32)]
+                + [(n, C.c_void_p) for n in ("x", "w", "bias", "alpha", "norm", "resid", "lens", "y")]
+                + [("y_floats", C.c_int64)]
+                + [(n, C.c_void_p) for n in ("stats_out", "norm_gb", "norm_out", "plan_out")]
+                + [(n, C.c_int32) for n in ("B", "Cin", "L", "Cout", "k", "stride", "pad", "dil", "up_stride", "act")]
+                + [("slope", C.c_float), ("accumulate", C.c_int32), ("out_mul", C.c_float), ("out_div", C.c_float)]
+                + [(n, C.c_int32) for n in ("mode", "pad_ld", "flat", "in_up2", "epi", "merged", "tmajor", "prec1", "act_shift",
+                                            "epi_stream", "len_mul_in", "len_add_in", "len_mul_out", "len_add_out", "up_off", "view")])
+
+
+def _conv(x, w, bias=None, stride=1, pad=0, dil=1, up_stride=0, act=0, slope=0.0, alpha=None, norm=None, resid=None, y_init=None,
+          out_mul=1.0, out_div=1.0, want_stats=False, lens=None, mode=1, pre=False, want_norm=None, len_in=None, len_out=None,
+          device=0, **flags):
+    """One descriptor, one call of kx_test_conv: what every conv wrapper below maps its arguments onto.  up_stride = s > 0: the
+    polyphase transposed conv (w [Cin,Cout,2 s]) with the pad given; flags: the remaining int fields of ConvArgs by name.
+    Returns a dict: y at its stored shape, the plan that ran, stats and norm when asked for."""
+    lib = load_test_library()
+    x, w = _f32(x), _f32(w)
+    B, Cin, L = x.shape
+    k = w.shape[2]
+    if up_stride:
+        Cout = w.shape[1]
+        Lout = (L - 1) * up_stride - 2 * pad + k + (1 if flags.get("up_off") else 0)
+    else:
+        Cout = w.shape[0]
+        Lout = ((2 * L if flags.get("in_up2") else L) + 2 * pad - dil * (k - 1) - 1) // stride + 1
+    shape = (B, Lout, Cout) if flags.get("tmajor") else (B, Cout, Lout)
+    y = np.zeros(shape, dtype=np.float32) if y_init is None else _f32(y_init).copy()
+    st = np.zeros((B, Cout, 2), dtype=np.float32) if want_stats else None
+    gb = _f32(want_norm)
+    assert gb is None or gb.shape == (B, 2 * Cout)
+    planes = None if gb is None else np.zeros((3, B, Cout), dtype=np.float32)
+    plan = np.zeros(len(CONV_PLAN_FIELDS), dtype=np.int64)
+    ptrs = dict(x=x, w=w, bias=_f32(bias), alpha=_f32(alpha), norm=_f32(norm), resid=_f32(resid),
+                lens=None if lens is None else np.ascontiguousarray(lens, dtype=np.int32), y=y, stats_out=st, norm_gb=gb,
+                norm_out=planes, plan_out=plan)  # (kept alive until the call returns)
+    a = ConvArgs(struct_size=C.sizeof(ConvArgs), device_id=device, y_floats=y.size, B=B, Cin=Cin, L=L, Cout=Cout, k=k, stride=stride,
+                 pad=pad, dil=dil, up_stride=up_stride, act=act, slope=float(slope), accumulate=0 if y_init is None else 1,
+                 out_mul=float(out_mul), out_div=float(out_div), mode=mode | (0x100 if pre else 0), **{n: int(v) for n, v in flags.items()},
+                 **{n: _ptr(p) for n, p in ptrs.items()})
+    (a.len_mul_in, a.len_add_in), (a.len_mul_out, a.len_add_out) = len_in or (0, 0), len_out or (0, 0)
+    _err_call(lib.kx_test_conv, C.byref(a))
+    pl = dict(zip(CONV_PLAN_FIELDS, (int(v) for v in plan)))
+    pl["form"] = CONV_FORMS[pl["form"]]
+    return {"y": y, "plan": pl, "stats": st, "norm": planes}
+
+
 def conv1d(x, w, bias=None, stride=1, pad=0, dil=1, transposed=False, act=0, slope=0.0, alpha=None, norm=None,
            device=0, mode=None, pre=False):
     """Run the MFMA conv kernel alone: x [B,Cin,L], w [Cout,Cin,k] ([Cin,Cout,k] if transposed).  pre: stage the input
     through a pre-split image (conv_f16x3_pre.hip; direct-A kernels only)."""
-    lib = load_test_library()
     if mode is None:
         mode = CONV_F32 if os.environ.get("KOKOROX_CONV", "") == "f32" else CONV_F16X3
-    x, w = _f32(x), _f32(w)
-    B, Cin, L = x.shape
-    k = w.shape[2]
     if transposed:
-        Cout = w.shape[1]
-        Lout = (L - 1) * stride - 2 * pad + k
-    else:
-        Cout = w.shape[0]
-        Lout = (L + 2 * pad - dil * (k - 1) - 1) // stride + 1
-    y = np.zeros((B, Cout, Lout), dtype=np.float32)
-    bias, alpha, norm = _f32(bias), _f32(alpha), _f32(norm)
-    _err_call(lib.kx_test_conv1d, device, _ptr(x), B, Cin, L, _ptr(w), _ptr(bias), Cout, k, stride, pad, dil,
-              1 if transposed else 0, act, float(slope), _ptr(alpha), _ptr(norm), _ptr(y), Lout, mode | (0x100 if pre else 0))
-    return y
+        return _conv(x, w, bias, up_stride=stride, pad=pad, dil=dil, act=act, slope=slope, alpha=alpha, norm=norm, device=device,
+                     mode=mode, pre=pre)["y"]
+    return _conv(x, w, bias, stride=stride, pad=pad, dil=dil, act=act, slope=slope, alpha=alpha, norm=norm, device=device, mode=mode,
+                 pre=pre)["y"]
 
 
 # kx::ConvLaunch and kx::ConvPlan (kokorox_amd/csrc/kx_common.h), field by field in declaration order
@@ -1011,33 +1042,19 @@ def conv_plan(**launch):
 def conv_transpose(x, w, bias=None, stride=6, act=1, slope=0.1, resid=None, up_off=0, mode=1, pre=False, device=0):
     """Polyphase transposed conv as Generator.ups runs it: x [B,Cin,L], w [Cin,Cout,2*stride] -> y [B,Cout,Lout + up_off]
     (+ resid; up_off = 1: output from column 1, column 0 = reflection of column 1)."""
-    lib = load_test_library()
-    x, w = _f32(x), _f32(w)
-    B, Cin, L = x.shape
-    Cout, k = w.shape[1], w.shape[2]
+    k = np.shape(w)[2]
     assert k == 2 * stride
-    pad = (k - stride) // 2
-    Lout = (L - 1) * stride - 2 * pad + k
-    y = np.zeros((B, Cout, Lout + (1 if up_off else 0)), dtype=np.float32)
-    _err_call(lib.kx_test_conv_transpose, device, _ptr(x), B, Cin, L, _ptr(w), _ptr(_f32(bias)), Cout, stride, act, float(slope),
-              _ptr(_f32(resid)), 1 if up_off else 0, _ptr(y), mode | (0x100 if pre else 0))
-    return y
+    return _conv(x, w, bias, up_stride=stride, pad=(k - stride) // 2, act=act, slope=slope, resid=resid, up_off=1 if up_off else 0,
+                 mode=mode, pre=pre, device=device)["y"]
 
 
 def conv1d_epilogue(x, w, bias=None, pad=0, dil=1, resid=None, y_init=None, out_mul=1.0, out_div=1.0, want_stats=False,
                     mode=1, device=0):
     """Stride-1 conv through the epilogue forms: y = (conv + bias + resid [+ y_init]) * out_mul / out_div, and the
     fused per-row (sum, sum of squares) when want_stats.  Returns y or (y, stats[B,Cout,2])."""
-    lib = load_test_library()
-    x, w = _f32(x), _f32(w)
-    B, Cin, L = x.shape
-    Cout, _, k = w.shape
-    Lout = L + 2 * pad - dil * (k - 1)
-    y = np.zeros((B, Cout, Lout), dtype=np.float32) if y_init is None else _f32(y_init).copy()
-    st = np.zeros((B, Cout, 2), dtype=np.float32) if want_stats else None
-    _err_call(lib.kx_test_conv1d_epilogue, device, _ptr(x), B, Cin, L, _ptr(w), _ptr(_f32(bias)), Cout, k, pad, dil,
-              _ptr(_f32(resid)), 0 if y_init is None else 1, float(out_mul), float(out_div), _ptr(y), _ptr(st), mode)
-    return (y, st) if want_stats else y
+    r = _conv(x, w, bias, pad=pad, dil=dil, resid=resid, y_init=y_init, out_mul=out_mul, out_div=out_div, want_stats=want_stats,
+              mode=mode, device=device)
+    return (r["y"], r["stats"]) if want_stats else r["y"]
 
 
 def conv1d_full(x, w, bias=None, pad=0, dil=1, act=0, slope=0.0, alpha=None, norm=None, resid=None, y_init=None,
@@ -1045,25 +1062,16 @@ def conv1d_full(x, w, bias=None, pad=0, dil=1, act=0, slope=0.0, alpha=None, nor
     """Stride-1 conv with the fused input transform (AdaIN affine + leaky / snake) AND the epilogue forms, on a ragged
     batch (lens[b] valid input columns), with pad_ld on the model's padded rows, with flat through the flat list of live
     tiles the model gives the direct-A kernels.  Returns y or (y, stats[B,Cout,2])."""
-    lib = load_test_library()
-    x, w = _f32(x), _f32(w)
-    B, Cin, L = x.shape
-    Cout, _, k = w.shape
-    Lout = L + 2 * pad - dil * (k - 1)
-    y = np.zeros((B, Cout, Lout), dtype=np.float32) if y_init is None else _f32(y_init).copy()
-    st = np.zeros((B, Cout, 2), dtype=np.float32) if want_stats else None
-    ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
-    _err_call(lib.kx_test_conv1d_full, device, _ptr(x), B, Cin, L, _ptr(ln), (1 if pad_ld else 0) | (2 if flat else 0), _ptr(w), _ptr(_f32(bias)),
-              Cout, k, pad, dil, act, float(slope), _ptr(_f32(alpha)), _ptr(_f32(norm)), _ptr(_f32(resid)),
-              0 if y_init is None else 1, float(out_mul), float(out_div), _ptr(y), _ptr(st), mode | (0x100 if pre else 0))
-    return (y, st) if want_stats else y
+    r = _conv(x, w, bias, pad=pad, dil=dil, act=act, slope=slope, alpha=alpha, norm=norm, resid=resid, y_init=y_init, out_mul=out_mul,
+              out_div=out_div, want_stats=want_stats, lens=lens, pad_ld=pad_ld, flat=flat, mode=mode, device=device, pre=pre)
+    return (r["y"], r["stats"]) if want_stats else r["y"]
 
 
 def conv1d_opts(x, w, bias=None, pad=0, dil=1, act=0, slope=0.0, alpha=None, norm=None, resid=None, y_init=None,
                 out_mul=1.0, out_div=1.0, want_stats=False, lens=None, pad_ld=False, flat=False, mode=1, device=0, pre=False,
                 in_up2=False, epi=0, merged=False, tmajor=False, prec1=0, act_shift=0, epi_stream=False, want_norm=None,
                 up_stride=0, stride=1, len_in=None, len_out=None, up_off=False, view=False):
-    """conv1d_full plus the launch options Model::conv sets (include/kokorox_hip_test.h, kx_test_conv1d_opts): in_up2 (x [B,Cin,L]
+    """conv1d_full plus the launch options Model::conv sets (include/kokorox_hip_test.h, kx_test_conv_args): in_up2 (x [B,Cin,L]
     read as 2 L columns), epi (1 = gelu_new), merged (the plan may merge the batch's columns), tmajor (y [B,Lout,Cout]), prec1,
     act_shift, epi_stream, up_stride (s > 0: the polyphase transposed conv instead, w [Cin,Cout,2 s]); want_norm = gb [B,2 Cout]: the fused partial sums finalized into (mean, scale, shift) [3,B,Cout].
     stride (plain convs), len_in / len_out = (mul, add): lens[] are units (the model's frames) and utterance b has lens[b] * mul + add
@@ -1071,34 +1079,14 @@ def conv1d_opts(x, w, bias=None, pad=0, dil=1, act=0, slope=0.0, alpha=None, nor
     [B,Cout,Lout + 1]), view (x, resid and y are row slices of taller tensors).  A call that uses one of these five gets unowned output
     columns back as LN_SENTINEL.
     Returns a dict: y at its stored shape, plan (the ConvPlan that ran, as conv_plan returns it), and stats / norm when asked for."""
-    lib = load_test_library()
-    x, w = _f32(x), _f32(w)
-    B, Cin, L = x.shape
-    Cout, _, k = w.shape
-    Lout = ((2 * L if in_up2 else L) + 2 * pad - dil * (k - 1) - 1) // stride + 1
-    if up_stride:
-        Cout = w.shape[1]
+    if up_stride:  # (k = 2 s taps, pad = (k - s) / 2, no dilation: pad and dil are not the caller's)
+        k = np.shape(w)[2]
         assert k == 2 * up_stride
-        Lout = (L - 1) * up_stride - 2 * ((k - up_stride) // 2) + k + (1 if up_off else 0)
-    shape = (B, Lout, Cout) if tmajor else (B, Cout, Lout)
-    y = np.zeros(shape, dtype=np.float32) if y_init is None else _f32(y_init).copy()
-    st = np.zeros((B, Cout, 2), dtype=np.float32) if want_stats else None
-    ln = None if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
-    opts = [in_up2, epi, merged, tmajor, prec1, act_shift, epi_stream, up_stride]
-    if stride != 1 or len_in is not None or len_out is not None or up_off or view:
-        opts += [stride, *(len_in or (0, 0)), *(len_out or (0, 0)), up_off, view]
-    opts = np.array(opts, dtype=np.int32)
-    gb = _f32(want_norm)
-    planes = None if gb is None else np.zeros((3, B, Cout), dtype=np.float32)
-    assert gb is None or gb.shape == (B, 2 * Cout)
-    plan = np.zeros(len(CONV_PLAN_FIELDS), dtype=np.int64)
-    _err_call(lib.kx_test_conv1d_opts, device, _ptr(x), B, Cin, L, _ptr(ln), (1 if pad_ld else 0) | (2 if flat else 0), _ptr(w),
-              _ptr(_f32(bias)), Cout, k, pad, dil, act, float(slope), _ptr(_f32(alpha)), _ptr(_f32(norm)), _ptr(_f32(resid)),
-              0 if y_init is None else 1, float(out_mul), float(out_div), _ptr(y), _ptr(st), mode | (0x100 if pre else 0), _ptr(opts),
-              len(opts), _ptr(gb), _ptr(planes), _ptr(plan))
-    pl = dict(zip(CONV_PLAN_FIELDS, (int(v) for v in plan)))
-    pl["form"] = CONV_FORMS[pl["form"]]
-    return {"y": y, "plan": pl, "stats": st, "norm": planes}
+        pad, dil = (k - up_stride) // 2, 1
+    return _conv(x, w, bias, stride=stride, pad=pad, dil=dil, up_stride=up_stride, act=act, slope=slope, alpha=alpha, norm=norm,
+                 resid=resid, y_init=y_init, out_mul=out_mul, out_div=out_div, want_stats=want_stats, lens=lens, mode=mode, pre=pre,
+                 want_norm=want_norm, len_in=len_in, len_out=len_out, device=device, pad_ld=pad_ld, flat=flat, in_up2=in_up2, epi=epi,
+                 merged=merged, tmajor=tmajor, prec1=prec1, act_shift=act_shift, epi_stream=epi_stream, up_off=up_off, view=view)
 
 
 LN_PLAIN, LN_AFFINE, LN_ADA = 0, 1, 2

@@ -1,4 +1,4 @@
-"""GPU: the conv launch options the model sets on every forward and no other kernel test reaches, through kx_test_conv1d_opts
+"""GPU: the conv launch options the model sets on every forward and no other kernel test reaches, through kx_test_conv
 (hip_koko.conv1d_opts), against torch CPU float64: in_up2, the gelu_new epilogue, the merged token axis, time-major stores on the
 f16x3 forms, the reduced-precision forms (prec1), the activation pre-scale (act_shift) and the streamed epilogue (epi_stream).
 
@@ -493,3 +493,33 @@ def test_streamed_epilogue_gives_the_same_bits(k, d, mode, form):
             print(f"epi_stream {form} + residual: max err vs float64 {err:.2e}")
             assert err < 3e-5
             assert np.all(np.where(valid, 0.0, r1["y"]) == 0.0)
+
+
+# ---- one descriptor behind every wrapper -------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_every_plain_wrapper_fills_the_same_descriptor(mode):
+    """One plain stride-1 conv through conv1d, conv1d_epilogue, conv1d_full and conv1d_opts: bit-identical y.  The smallest shapes
+    suffice: this is about the wrappers' argument mapping onto kx_test_conv_args, not about a kernel."""
+    from kokorox_amd import hip_koko as hk
+    rng = np.random.default_rng(40 + mode)
+    x = rng.standard_normal((2, 16, 40), dtype=np.float32)
+    w, b = _weights(rng, 32, 16, 3), rng.standard_normal(32, dtype=np.float32)
+    y = hk.conv1d(x, w, b, pad=1, mode=mode)
+    assert y.shape == (2, 32, 40) and np.isfinite(y).all() and np.abs(y).max() > 0.1
+    np.testing.assert_array_equal(hk.conv1d_epilogue(x, w, b, pad=1, mode=mode), y)
+    np.testing.assert_array_equal(hk.conv1d_full(x, w, b, pad=1, mode=mode), y)
+    np.testing.assert_array_equal(hk.conv1d_opts(x, w, b, pad=1, mode=mode)["y"], y)
+
+
+def test_every_transposed_wrapper_fills_the_same_descriptor():
+    """The polyphase transposed conv (stride 6, k = 12, pad = 3, leaky 0.1 on the input) through conv_transpose,
+    conv1d(transposed=True) and conv1d_opts(up_stride=6): bit-identical y."""
+    from kokorox_amd import hip_koko as hk
+    rng = np.random.default_rng(42)
+    x = rng.standard_normal((2, 16, 12), dtype=np.float32)
+    w, b = _weights(rng, 16, 16, 12), rng.standard_normal(16, dtype=np.float32)
+    y = hk.conv_transpose(x, w, b, stride=6, act=1, slope=0.1)
+    assert y.shape == (2, 16, 72) and np.isfinite(y).all() and np.abs(y).max() > 0.1
+    np.testing.assert_array_equal(hk.conv1d(x, w, b, stride=6, pad=3, transposed=True, act=1, slope=0.1, mode=1), y)
+    np.testing.assert_array_equal(hk.conv1d_opts(x, w, b, act=1, slope=0.1, up_stride=6)["y"], y)

@@ -1,4 +1,4 @@
-"""GPU: the generator's conv launches that only the whole forward used to reach, alone through kx_test_conv1d_opts with the model's
+"""GPU: the generator's conv launches that only the whole forward used to reach, alone through kx_test_conv (hip_koko.conv1d_opts) with the model's
 length maps (hip_koko.conv1d_opts: stride, len_in / len_out, up_off, view): the strided noise_convs.0 with fused statistics, the
 1 -> 1 strided F0_conv / N_conv between row slices of taller tensors, the polyphase upsamplers ups.0 / ups.1 ragged on padded rows
 with their residual, output offset and reflected column, and the stride-1 convs of the 120 f + 1 axis.  The batches are ragged

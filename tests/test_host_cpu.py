@@ -111,6 +111,31 @@ def test_test_hooks_live_in_their_own_library():
     assert not [n for n in _header_symbols() if n.startswith("kx_test_")]
 
 
+def test_conv_descriptor_is_described_the_same_twice():
+    """The members of kx_test_conv_args in include/kokorox_hip_test.h, in order, are the fields of its ctypes mirror, in order."""
+    from kokorox_amd import hip_koko as hk
+    txt = open(os.path.join(ROOT, "include", "kokorox_hip_test.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    body = re.search(r"typedef struct kx_test_conv_args \{(.*?)\} kx_test_conv_args;", txt, flags=re.S).group(1)
+    names = []
+    for decl in body.split(";"):  # `type a, b` or `const type* a`: the last identifier of each declarator
+        names += [re.findall(r"[A-Za-z_]\w*", d)[-1] for d in decl.split(",") if d.strip()]
+    assert len(names) >= 40 and names[0] == "struct_size"
+    assert names == [n for n, _ in hk.ConvArgs._fields_]
+
+
+def test_conv_hook_refuses_a_descriptor_of_another_size():
+    """kx_test_conv looks at struct_size before it looks at the device: a descriptor off by 4 bytes is KX_ERR_INVALID, GPU or not."""
+    from kokorox_amd import hip_koko as hk
+    tlib = hk.load_test_library()
+    a = hk.ConvArgs(struct_size=C.sizeof(hk.ConvArgs) - 4)
+    err = C.create_string_buffer(256)
+    assert tlib.kx_test_conv(C.byref(a), err, len(err)) == hk.KX_ERR_INVALID
+    assert b"kx_test_conv_args" in err.value
+    a.struct_size += 8
+    assert tlib.kx_test_conv(C.byref(a), err, len(err)) == hk.KX_ERR_INVALID
+
+
 def _split_args(arglist: str):
     """Top-level comma split of a parameter list (no nested parentheses in this ABI)."""
     a = [x.strip() for x in arglist.replace("\n", " ").split(",")]

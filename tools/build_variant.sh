@@ -6,12 +6,12 @@ ROOT=$(cd $(dirname $0)/.. && pwd)
 NAME=$1; shift
 L=$ROOT/kokorox_amd/lib; mkdir -p $L/variants /tmp/kxv
 /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -fPIC -std=c++17 "$@" -I$ROOT/kokorox_amd/csrc -c $ROOT/kokorox_amd/csrc/conv_f16x3_da.hip -o /tmp/kxv/da_$NAME.o 2>/tmp/kxv/da_$NAME.err || { grep -w error /tmp/kxv/da_$NAME.err | head; exit 1; }
-# every object of the library, conv_f16x3_da.o replaced (test_hooks.o belongs to libkokorox_hip_test.so)
+# every object of the library, conv_f16x3_da.o replaced (the test_hooks*.o belong to libkokorox_hip_test.so)
 OBJS=""
 for o in $L/*.o; do
   case "$(basename $o)" in
     conv_f16x3_da.o) OBJS="$OBJS /tmp/kxv/da_$NAME.o" ;;
-    test_hooks.o) ;;
+    test_hooks*.o) ;;
     *) OBJS="$OBJS $o" ;;
   esac
 done
