@@ -556,6 +556,60 @@ int kx_infer_requests_loudness(kx_model* m, const int64_t* ids, int64_t t_stride
                                int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join,
                                const kx_loudness* loudness, int n_loudness, double* out_loudness);
 
+/* ---- limiter: a look-ahead peak limiter for a request's body on the GPU, sample peak or true peak ------------------------------------
+ * Every other scaling here is one gain per request: where a loudness target meets its ceiling the whole body is pulled down, and
+ * speech, with a crest factor of 15-20 dB, meets it routinely.  A limit spec drives the body to the level asked for and turns down
+ * only the neighbourhood of the samples that would pass `peak`.
+ *   The stream.  z[0..N) at the output rate fs is exactly the stream of "levels": after the join, after the resampler.  p, tp, I and
+ *   n_g keep their meanings of "levels" and "loudness"; with KX_PEAK_TRUE in the mode p is tp.
+ *   The static gain g, float64.  Mode 0: g = f64(gain).  Mode 1: g = 10^((f64(target_lufs) - I) / 20) if I is defined, else 1.0.
+ *   Drive cap: if p is usable and g * f64(p) > 4 f64(peak) (one product; 4 peak is exact), g = 4 f64(peak) / f64(p) -- the ceiling
+ *   rule of KX_LEVEL_CEILING with the ceiling 12 dB up: at most 12.04 dB ever goes into the limiter.  z1[n] = f32(g * f64(z[n])).
+ *   Window and weights.  W = fs / 200 samples: 40, 80, 120, 240 at 8, 16, 24, 48 kHz; 5 ms spans a pitch period down to 100 Hz, so
+ *   the gain does not ride single pitch pulses.  h_W[i], i = 0..2W, is (1 - cos(2 pi (i + 1) / (2 W + 2))) divided by its float64
+ *   sum and rounded once to float32; the four tables are committed as bit patterns (kx_limit_filter hands them out).
+ *   Envelope, float32.  a[n] = |z1[n]| if z1[n] is finite, else 0.  With KX_PEAK_TRUE: a[n] = max(|z1[n]|, |u_phi[n-1]|, |u_phi[n]|)
+ *   over phi = 1..3, u the interpolator of "True peak" applied to z1 -- same taps, same order, non-finite values and values outside
+ *   the stream taken as 0 -- and u_phi[-1] = 0.
+ *   Required gain.  c[n] = 1.0f if a[n] <= peak, else f32(f64(peak) / f64(a[n])); c[k] = 1.0f for k outside [0, N).
+ *   Sliding minimum.  m[j] = the smallest c[k], k in [j - W, j + W], for every j in [-W, N + W): float32, order-free.  An m outside
+ *   the stream still sees the c inside it; without that the gain would rise towards the ends and the bound below would break.
+ *   Smoothing.  s[n] = the sum over j = n - W .. n + W, ascending, of f64(h_W[j - n + W]) * f64(m[j]): a float64 accumulator from
+ *   +0, one addition per term.  A float32 x float32 product is exact in float64, so fused and unfused forms agree and a host loop
+ *   in this order gives the GPU's bits.  Per sample: if every m[j] of the sum is 1.0f, s[n] = 1.0 exactly and the sum is not taken.
+ *   Output.  z2[n] = f32(s[n] * f64(z1[n])); then, if |z2[n]| > peak, z2[n] = copysign(peak, z2[n]).  A NaN stays a NaN, +-inf
+ *   becomes +-peak.  The form is applied to z2 exactly as to z; marks, sizes and headers do not change.
+ *   Sample ceiling.  For j in [n - W, n + W], n lies in j's window, so m[j] <= c[n]; a weighted mean of these stays within rounding
+ *   of c[n], and the final clamp makes |z2[n]| <= peak unconditional.  With KX_PEAK_TRUE the true peak of z2 is bounded only
+ *   approximately, because the gain acts at the sample rate: on voiced, noise and click streams driven to the cap's full 12 dB it
+ *   stayed within 6e-7 of peak at all four rates, where the sample-only limiter leaves 0.5 to 20 per cent; the tests hold it to
+ *   peak (1 + 1e-4).  The loudness of a limited body
+ *   is at or below the target: I is the input's loudness, it is not measured again.
+ *   Valid specs.  Low byte 0 (KX_LIMIT_GAIN): 0 <= gain <= 64 and target_lufs is +0.0f.  Low byte 1 (KX_LIMIT_LOUDNESS): gain is
+ *   exactly 1.0f and -70 <= target_lufs <= 0.  Both: 2^-15 <= peak <= 1.  KX_PEAK_TRUE may be OR-ed in; every other bit is refused
+ *   and a NaN fails every rule.  There is no plain limit spec: a request without a limiter takes the older entries, or sits beside
+ *   limited ones in a dispatcher batch.
+ *   Report.  Five doubles per request: f64(p), g, I, n_g (a quiet NaN and 0 in mode 0) and r = f64(the smallest f32(s[n])), 1.0 for
+ *   a request nothing limited.  Bytes, marks and the five values of a request do not depend on what it was batched with. */
+#define KX_LIMIT_GAIN     0u  /* drive by `gain`, limit at `peak`                                            */
+#define KX_LIMIT_LOUDNESS 1u  /* drive to `target_lufs` (BS.1770, as KX_LOUDNESS_NORMALIZE), limit at `peak` */
+#define KX_LIMIT_MAX_TAPS 481 /* 2 W + 1 at 48 000 Hz                                                        */
+typedef struct kx_limit { uint32_t mode; float gain; float target_lufs; float peak; } kx_limit;   /* 16 bytes */
+/* W and the 2 W + 1 weights h_W of a format word's rate into taps[cap], cap >= 2 W + 1 (KX_LIMIT_MAX_TAPS always does).  Host only;
+ * KX_ERR_INVALID for an unknown word, as kx_resample_filter. */
+int kx_limit_filter(int format_word, int32_t* W, float* taps, int cap);
+/* kx_infer_requests_joined with a limit spec per request: limits [n_limit], n_limit = 1 (shared) or R.  `joins` may be NULL with
+ * n_join == 0 (no joins).  out_limits may be NULL; when given it receives [R][5] doubles, the report above.  Body, marks and all
+ * blocks leave the device in one copy.  Refused with KX_ERR_INVALID before any device work, after everything
+ * kx_infer_requests_joined refuses: a null `limits` ("infer: null limit argument"), n_limit not 1 or R ("infer: bad limit count"),
+ * an invalid spec ("infer: bad limit"). */
+int kx_infer_requests_limited(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                              const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                              const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                              const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                              int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_limit* limits,
+                              int n_limit, double* out_limits);
+
 /* ---- request dispatcher ----------------------------------------------------
  * Replaces the reference's one-request-at-a-time `Mutex<Session>` (kokorox/src/onn/ort_koko.rs:78; callers
  * kokorox-openai/src/lib.rs:370-439, kokorox-websocket/src/lib.rs:657-668).  Any number of threads submit
@@ -648,6 +702,16 @@ int kx_dispatcher_submit_request_loudness(kx_dispatcher* d, const int64_t* ids, 
                                           float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
                                           int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
                                           const kx_loudness* loudness, double* out_loudness, char* err, size_t err_len);
+/* kx_dispatcher_submit_request_joined with the request's limit spec (see "limiter" above); `join` may be NULL here (no join).
+ * out_limit may be NULL; when given it receives five doubles, f64(p), g, I, n_g and r of the request.  A null or invalid `limit`:
+ * "dispatcher_submit_request: bad limit"; every other refusal as kx_dispatcher_submit_request_joined.  Limited, loudness, levelled,
+ * joined and plain requests share batches; body, marks and the five values equal those of kx_infer_requests_limited (R = 1, same
+ * seed, utterance base 0) bit for bit, whatever the request was batched with. */
+int kx_dispatcher_submit_request_limited(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                         const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
+                                         float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
+                                         int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
+                                         const kx_limit* limit, double* out_limit, char* err, size_t err_len);
 /* n_requests counts requests, max_batch_seen the largest batch in ROWS (a request of n chunks is n rows). */
 int kx_dispatcher_stats(kx_dispatcher* d, int64_t* n_requests, int64_t* n_batches, int64_t* max_batch_seen);
 /* batches each model (worker) has run so far: per_model[n_models] */

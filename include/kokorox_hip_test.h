@@ -148,6 +148,20 @@ int kx_test_output_plan_loudness(int device_id, const float* audio, int B, int64
                                  const kx_level* levels, double* out_levels, const kx_loudness* loudness, double* out_loudness,
                                  double* out_hops, int64_t hops_cap, int64_t* out_n_hops, char* err, size_t err_len);
 
+/* kx_test_output_plan_loudness with limits (include/kokorox_hip.h, "limiter"): limits [R] (one spec per request; needs audio; a spec
+ * of mode 0xFFFFFFFF: that request has none, as a request beside limited ones in a dispatcher batch; a limited request's level spec
+ * must be the plain one and its loudness spec, if loudness is given, of mode 0xFFFFFFFF), out_limits [R][5] doubles = f64(p), g, I,
+ * n_g and r of every limited request (the rows of the others are left as they were).  `levels` and `loudness` may be NULL here
+ * (then their outputs too).  The order is resampler, peak, loudness, true peak, gain, limiter, packer, marks, through the same
+ * build_output_plan and launch_output_plan.  limits = NULL (then out_limits too): kx_test_output_plan_loudness. */
+int kx_test_output_plan_limited(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames, const int32_t* dur,
+                                const int32_t* lens, const int32_t* chunks_per_request, int R, const int32_t* formats,
+                                const kx_join* joins, const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes,
+                                int64_t* out_samples, int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks,
+                                const kx_level* levels, double* out_levels, const kx_loudness* loudness, double* out_loudness,
+                                double* out_hops, int64_t hops_cap, int64_t* out_n_hops, const kx_limit* limits, double* out_limits,
+                                char* err, size_t err_len);
+
 /* The token-axis kernels of Model::front_half, alone.  Common to these hooks: rows padded to a multiple of 32 floats as in the
  * model, NaN in every input column a kernel must not read, -12345.5 (0xA5 bytes in integer buffers) in every output location it
  * must not write; what the caller cannot see (row padding, guard regions behind a buffer) the hook checks itself after the launch

@@ -120,6 +120,37 @@ pub fn loudness_filter(format_word: c_int) -> Result<[f64; 10], Box<dyn Error>> 
     }
 }
 
+pub const KX_LIMIT_GAIN: u32 = 0;
+pub const KX_LIMIT_LOUDNESS: u32 = 1;
+pub const KX_LIMIT_MAX_TAPS: usize = 481;
+
+/// How a request's body is driven and peak-limited on the GPU (`kx_limit`; "limiter" in kokorox_hip.h): mode 0 drives it by
+/// `gain` (0..64, `target_lufs` +0.0), mode 1 to `target_lufs` (-70..0, `gain` exactly 1.0) as `KX_LOUDNESS_NORMALIZE` does; a
+/// look-ahead gain of 5 ms either side then keeps every sample at or below `peak` (2^-15..1) by turning down only the
+/// neighbourhood of the samples that would pass it.  `KX_PEAK_TRUE` may be OR-ed into the mode: the limiter then follows the
+/// four-times oversampled envelope.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct KxLimit {
+    pub mode: u32,
+    pub gain: f32,
+    pub target_lufs: f32,
+    pub peak: f32,
+}
+
+/// The limiter's window W = fs / 200 and its 2 W + 1 smoothing weights at a format word's rate (host only).
+pub fn limit_filter(format_word: c_int) -> Result<(usize, Vec<f32>), Box<dyn Error>> {
+    let mut w = 0i32;
+    let mut taps = vec![0f32; KX_LIMIT_MAX_TAPS];
+    match unsafe { kx_limit_filter(format_word, &mut w, taps.as_mut_ptr(), KX_LIMIT_MAX_TAPS as c_int) } {
+        KX_OK => {
+            taps.truncate(2 * w as usize + 1);
+            Ok((w as usize, taps))
+        }
+        rc => Err(format!("kokorox_hip error {}: unknown output format or sample rate", rc).into()),
+    }
+}
+
 #[repr(C)]
 pub struct KxModel {
     _p: [u8; 0],
@@ -149,6 +180,19 @@ extern "C" {
                                              out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64,
                                              join: *const KxJoin, loudness: *const KxLoudness, out_loudness: *mut f64, err: *mut c_char,
                                              err_len: usize) -> c_int;
+    fn kx_limit_filter(format_word: c_int, w: *mut i32, taps: *mut f32, cap: c_int) -> c_int;
+    fn kx_infer_requests_limited(m: *mut KxModel, ids: *const i64, t_stride: i64, lens: *const i32, b: c_int,
+                                 chunks_per_request: *const i32, r: c_int, styles: *const f32, voice_ids: *const i32,
+                                 weights: *const f32, max_mix: c_int, speeds: *const f32, n_speed: c_int, seed: u64, flags: u32,
+                                 formats: *const c_int, n_format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                                 out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64, joins: *const KxJoin,
+                                 n_join: c_int, limits: *const KxLimit, n_limit: c_int, out_limits: *mut f64) -> c_int;
+    fn kx_dispatcher_submit_request_limited(d: *mut KxDispatcher, ids: *const i64, chunk_tokens: *const i32, n_chunks: c_int,
+                                            styles: *const f32, voice_ids: *const i32, weights: *const f32, n_mix: c_int,
+                                            speed: f32, seed: u64, format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                                            out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64,
+                                            join: *const KxJoin, limit: *const KxLimit, out_limit: *mut f64, err: *mut c_char,
+                                            err_len: usize) -> c_int;
     fn kx_create_from_device_blob(d_blob: *const c_void, n_bytes: usize, device_id: c_int, err: *mut c_char,
                                   err_len: usize) -> *mut KxModel;
     fn kx_create_replicas(weights_path: *const c_char, device_ids: *const c_int, n: c_int,
@@ -700,6 +744,47 @@ impl HipKoko {
         Ok(res)
     }
 
+    /// `infer_requests_joined` with every request driven and peak-limited on the GPU ("limiter" in kokorox_hip.h): `limits`
+    /// holds one spec for all requests or one per request, `joins` may be empty (no joins).  Per request: body, marks, and
+    /// [p, g, I, n_g, r]: the peak of its stream, the static gain, its loudness in LUFS and gated blocks (NaN and 0 in mode 0),
+    /// and the smallest smoothed gain (1.0 when nothing was limited), as the GPU computed them.
+    #[allow(clippy::type_complexity)]
+    pub fn infer_requests_limited(&self, tokens: &[Vec<i64>], chunks_per_request: &[i32], styles: &[Vec<f32>], speeds: &[f32],
+                                  seed: u64, formats: &[c_int], joins: &[KxJoin], limits: &[KxLimit])
+                                  -> Result<Vec<(Vec<u8>, Vec<i64>, [f64; 5])>, Box<dyn Error>> {
+        if tokens.is_empty() || styles.len() != tokens.len() || styles.iter().any(|s| s.len() != KX_STYLE_DIM) {
+            return Err("infer_requests: one style row of 256 floats per chunk is required".into());
+        }
+        let (b, r) = (tokens.len(), chunks_per_request.len());
+        let (ids, lens, stride) = Self::flatten(tokens);
+        let st: Vec<f32> = styles.iter().flatten().copied().collect();
+        let mut out: *mut c_void = ptr::null_mut();
+        let mut mk: *mut i64 = ptr::null_mut();
+        let (mut nbytes, mut nsamp, mut nmarks) = (vec![0i64; r.max(1)], vec![0i64; r.max(1)], vec![0i64; r.max(1)]);
+        let mut lm = vec![0f64; 5 * r.max(1)];
+        let rc = unsafe {
+            kx_infer_requests_limited(self.h, ids.as_ptr(), stride as i64, lens.as_ptr(), b as c_int, chunks_per_request.as_ptr(),
+                                      r as c_int, st.as_ptr(), ptr::null(), ptr::null(), 0, speeds.as_ptr(), speeds.len() as c_int,
+                                      seed, 0, formats.as_ptr(), formats.len() as c_int, &mut out, nbytes.as_mut_ptr(),
+                                      nsamp.as_mut_ptr(), &mut mk, nmarks.as_mut_ptr(),
+                                      if joins.is_empty() { ptr::null() } else { joins.as_ptr() }, joins.len() as c_int,
+                                      limits.as_ptr(), limits.len() as c_int, lm.as_mut_ptr())
+        };
+        self.check(rc)?;
+        let mut res = Vec::with_capacity(r);
+        let (mut at, mut mat) = (0usize, 0usize);
+        for i in 0..r {
+            // (the marks live in the buffer of `out`: copied before it is released)
+            let body = unsafe { std::slice::from_raw_parts((out as *const u8).add(at), nbytes[i] as usize) }.to_vec();
+            let marks = unsafe { std::slice::from_raw_parts((mk as *const i64).add(mat), nmarks[i] as usize) }.to_vec();
+            at += nbytes[i] as usize;
+            mat += nmarks[i] as usize;
+            res.push((body, marks, [lm[5 * i], lm[5 * i + 1], lm[5 * i + 2], lm[5 * i + 3], lm[5 * i + 4]]));
+        }
+        unsafe { kx_free_packed(out) };
+        Ok(res)
+    }
+
     /// Raw device-pointer form (inputs and output stay in HBM).
     ///
     /// # Safety
@@ -1081,6 +1166,37 @@ impl HipKokoDispatcher {
         let marks = unsafe { std::slice::from_raw_parts(mk as *const i64, nm as usize) }.to_vec();
         unsafe { kx_free_packed(out) };
         Ok((v, marks, ns, ld))
+    }
+
+    /// `submit_request_joined` with the request's limit spec ("limiter" in kokorox_hip.h; `join` = None: no join): body, marks,
+    /// sample count, and [p, g, I, n_g, r] of the request.
+    #[allow(clippy::too_many_arguments, clippy::type_complexity)]
+    pub fn submit_request_limited(&self, chunks: &[Vec<i64>], styles: &[f32], speed: f32, seed: u64, format: i32,
+                                  join: Option<KxJoin>, limit: KxLimit) -> Result<(Vec<u8>, Vec<i64>, i64, [f64; 5]), Box<dyn Error>> {
+        if styles.len() != KX_STYLE_DIM * chunks.len() {
+            return Err("submit_request: one style row of 256 floats per chunk is required".into());
+        }
+        let ids: Vec<i64> = chunks.iter().flatten().copied().collect();
+        let lens: Vec<i32> = chunks.iter().map(|c| c.len() as i32).collect();
+        let mut out: *mut c_void = ptr::null_mut();
+        let mut mk: *mut i64 = ptr::null_mut();
+        let (mut nb, mut ns, mut nm) = (0i64, 0i64, 0i64);
+        let mut lm = [0f64; 5];
+        let mut err = vec![0 as c_char; 256];
+        let rc = unsafe {
+            kx_dispatcher_submit_request_limited(self.d, ids.as_ptr(), lens.as_ptr(), lens.len() as c_int, styles.as_ptr(), ptr::null(),
+                                                 ptr::null(), 0, speed, seed, format, &mut out, &mut nb, &mut ns, &mut mk, &mut nm,
+                                                 join.as_ref().map_or(ptr::null(), |j| j as *const KxJoin), &limit, lm.as_mut_ptr(),
+                                                 err.as_mut_ptr(), err.len())
+        };
+        if rc != KX_OK {
+            return Err(format!("kokorox_hip error {}: {}", rc, cstr_buf(&err)).into());
+        }
+        let v = unsafe { std::slice::from_raw_parts(out as *const u8, nb as usize) }.to_vec();
+        // (inside the allocation of `out`: copied before it is released)
+        let marks = unsafe { std::slice::from_raw_parts(mk as *const i64, nm as usize) }.to_vec();
+        unsafe { kx_free_packed(out) };
+        Ok((v, marks, ns, lm))
     }
 
     /// The WebSocket chunk of `encode_audio` (kokorox-websocket/src/lib.rs:696-736) for a request: base64 of its 16-bit WAV

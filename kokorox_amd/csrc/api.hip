@@ -70,6 +70,16 @@ int kx_resample_filter(int format_word, int32_t* L, int32_t* M, int32_t* n_taps,
     });
 }
 
+int kx_limit_filter(int format_word, int32_t* W, float* taps, int cap) {
+    return guarded_free(nullptr, 0, [&] {
+        kx::check_format_word(format_word);
+        const int c = kx::format_rate(format_word), n = 2 * kx::limit_window(c) + 1;
+        KX_REQUIRE(W && taps && cap >= n, "limit_filter: null argument or too small a buffer");
+        *W = kx::limit_window(c);
+        std::memcpy(taps, kx::limit_taps(c), (size_t)n * sizeof(float));
+    });
+}
+
 int kx_loudness_filter(int format_word, double* out10) {
     return guarded_free(nullptr, 0, [&] {
         kx::check_format_word(format_word);
@@ -313,6 +323,12 @@ static_assert(sizeof(kx_loudness) == 12 && sizeof(kx_loudness) == sizeof(kx::Lou
                   KX_LOUDNESS_MEASURE == kx::LOUD_MEASURE && KX_LOUDNESS_NORMALIZE == kx::LOUD_NORMALIZE,
               "kx_loudness is the layout of kx::LoudSpec");
 
+static_assert(sizeof(kx_limit) == 16 && sizeof(kx_limit) == sizeof(kx::LimitSpec) && offsetof(kx_limit, mode) == offsetof(kx::LimitSpec, mode) &&
+                  offsetof(kx_limit, gain) == offsetof(kx::LimitSpec, gain) && offsetof(kx_limit, target_lufs) == offsetof(kx::LimitSpec, target_lufs) &&
+                  offsetof(kx_limit, peak) == offsetof(kx::LimitSpec, peak) && KX_LIMIT_GAIN == kx::LIMIT_GAIN && KX_LIMIT_LOUDNESS == kx::LIMIT_LOUDNESS &&
+                  KX_LIMIT_MAX_TAPS == kx::LIMIT_MAX_TAPS,
+              "kx_limit is the layout of kx::LimitSpec");
+
 // kx_infer_requests, kx_infer_requests_marks, kx_infer_requests_joined, kx_infer_requests_levelled and kx_infer_requests_loudness are
 // one call: the first asks for no marks, the first two for no joins, the first three for no levels, the first four for no loudness
 static int infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
@@ -322,7 +338,8 @@ static int infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, con
                           bool marks, int64_t** out_marks, int64_t* out_n_marks, bool joined = false, const kx_join* joins = nullptr,
                           int n_join = 0, bool levelled = false, const kx_level* levels = nullptr, int n_level = 0,
                           double* out_levels = nullptr, bool loud = false, const kx_loudness* loudness = nullptr, int n_loudness = 0,
-                          double* out_loudness = nullptr) {
+                          double* out_loudness = nullptr, bool limited = false, const kx_limit* limits = nullptr, int n_limit = 0,
+                          double* out_limits = nullptr) {
     return guarded(m, [&](Model& M) {
         KX_REQUIRE(chunks_per_request && formats && R >= 1, "infer_requests: null argument");
         KX_REQUIRE((styles != nullptr) != (voice_ids != nullptr), "infer_requests: give the style rows OR voice ids, not both");
@@ -356,8 +373,13 @@ static int infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, con
             hc.req_loudness = reinterpret_cast<const kx::LoudSpec*>(loudness);
             hc.n_req_loudness = n_loudness;
         }
+        if (limited) {  // (a null `limits` is refused with the call's other arguments: check_limit_call)
+            hc.limit_call = true;
+            hc.req_limits = reinterpret_cast<const kx::LimitSpec*>(limits);
+            hc.n_req_limits = n_limit;
+        }
         M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks,
-                        levelled ? out_levels : nullptr, loud ? out_loudness : nullptr);
+                        levelled ? out_levels : nullptr, loud ? out_loudness : nullptr, limited ? out_limits : nullptr);
     });
 }
 
@@ -410,6 +432,18 @@ int kx_infer_requests_loudness(kx_model* m, const int64_t* ids, int64_t t_stride
                           flags, formats, n_format, out, out_bytes, out_samples, out_marks || out_n_marks, out_marks, out_n_marks,
                           joins != nullptr || n_join != 0, joins, n_join, false, nullptr, 0, nullptr, true, loudness, n_loudness,
                           out_loudness);
+}
+
+int kx_infer_requests_limited(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                              const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                              const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                              const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                              int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_limit* limits,
+                              int n_limit, double* out_limits) {
+    return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
+                          flags, formats, n_format, out, out_bytes, out_samples, out_marks || out_n_marks, out_marks, out_n_marks,
+                          joins != nullptr || n_join != 0, joins, n_join, false, nullptr, 0, nullptr, false, nullptr, 0, nullptr, true,
+                          limits, n_limit, out_limits);
 }
 
 int kx_infer_device(kx_model* m, const int64_t* d_ids, int64_t t_stride, const int32_t* lens_host, int B,

@@ -26,6 +26,7 @@ struct ModelBackend {
         std::vector<int64_t> n_marks;
         std::vector<double> levels;  // [R][2] = {f64(p), g} when some request of the batch came through the levelled entry, else empty
         std::vector<double> loud;    // [R][4] = {f64(p), g, I, n_g} when some request came through the loudness entry, else empty
+        std::vector<double> limits;  // [R][5] = {f64(p), g, I, n_g, r} when some request came through the limiter's entry, else empty
     };
     static int n_voices(kx_model* h) { return h->m->n_voices(); }
     static int n_vocab(kx_model* h) { return h->m->n_vocab(); }
@@ -37,8 +38,9 @@ struct ModelBackend {
         int B = 0;
         size_t stride = 0;
         int mm = 1;
-        bool any_voice = false, any_marks = false, any_join = false, any_level = false, any_loud = false;
+        bool any_voice = false, any_marks = false, any_join = false, any_level = false, any_loud = false, any_limit = false;
         for (Request* r : batch) {
+            any_limit = any_limit || r->limited;
             any_loud = any_loud || r->metered;
             any_marks = any_marks || r->want_marks;
             any_join = any_join || r->joined();
@@ -57,9 +59,11 @@ struct ModelBackend {
         std::vector<kx::JoinSpec> joins(R);  // (a plain request beside a joined one: the all-zero spec, the plain bytes)
         std::vector<kx::LevelSpec> levels(R);  // (a request without levels beside a levelled one: the plain spec, z' = z)
         std::vector<kx::LoudSpec> louds(R);  // (a request without loudness beside a metered one: LOUD_NONE, the meter passes it by)
+        std::vector<kx::LimitSpec> limits(R);  // (a request without a limiter beside a limited one: LIMIT_NONE, the limiter passes it by)
         int b = 0;
         for (int q = 0; q < R; ++q) {
             const Request& r = *batch[(size_t)q];
+            limits[q] = r.limited ? kx::LimitSpec{r.limit.mode, r.limit.gain, r.limit.target_lufs, r.limit.peak} : kx::LimitSpec{kx::LIMIT_NONE, 1.0f, 0.0f, 1.0f};
             chunks[q] = r.rows();
             formats[q] = r.format;
             want[q] = r.want_marks ? 1 : 0;
@@ -89,6 +93,7 @@ struct ModelBackend {
         o.n_marks.assign(R, 0);
         o.levels.assign(any_level ? (size_t)2 * R : 0, 0.0);
         o.loud.assign(any_loud ? (size_t)4 * R : 0, 0.0);
+        o.limits.assign(any_limit ? (size_t)5 * R : 0, 0.0);
         int rc = KX_ERR_DEVICE;
         std::string err;
         {
@@ -118,6 +123,10 @@ struct ModelBackend {
                     hc.req_loudness = louds.data();
                     hc.n_req_loudness = R;
                 }
+                if (any_limit) {
+                    hc.req_limits = limits.data();
+                    hc.n_req_limits = R;
+                }
                 if (any_voice) {
                     hc.voice_ids = vids.data();
                     hc.weights = weights.data();
@@ -129,7 +138,7 @@ struct ModelBackend {
                 }
                 M.infer_host_ex(ids.data(), (int64_t)stride, lens.data(), B, speeds.data(), B, 0, 0, hc, &o.buf, o.bytes.data(),
                                 o.samples.data(), &o.marks, o.n_marks.data(), any_level ? o.levels.data() : nullptr,
-                                any_loud ? o.loud.data() : nullptr);
+                                any_loud ? o.loud.data() : nullptr, any_limit ? o.limits.data() : nullptr);
                 rc = KX_OK;
             } catch (const kx::Error& e) {
                 rc = e.code;
@@ -206,6 +215,8 @@ struct ModelBackend {
                 r->level_out[0] = o.levels[(size_t)2 * b];
                 r->level_out[1] = o.levels[(size_t)2 * b + 1];
             }
+            if (r->limited && !o.limits.empty())
+                for (int i = 0; i < 5; ++i) r->limit_out[i] = o.limits[(size_t)5 * b + i];
             if (r->metered && !o.loud.empty())
                 for (int i = 0; i < 4; ++i) r->loud_out[i] = o.loud[(size_t)4 * b + i];
         }
@@ -343,6 +354,19 @@ int kx_dispatcher_submit_request_levelled(kx_dispatcher* d, const int64_t* ids, 
     }
     return d->submit_request_levelled(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
                                       out_bytes, out_samples, out_marks, out_n_marks, join, level, out_level, err, err_len);
+}
+
+int kx_dispatcher_submit_request_limited(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                         const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
+                                         float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
+                                         int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
+                                         const kx_limit* limit, double* out_limit, char* err, size_t err_len) {
+    if (!d) {
+        if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null dispatcher");
+        return KX_ERR_INVALID;
+    }
+    return d->submit_request_limited(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
+                                     out_bytes, out_samples, out_marks, out_n_marks, join, limit, out_limit, err, err_len);
 }
 
 int kx_dispatcher_submit_request_loudness(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,

@@ -93,6 +93,9 @@ struct Request {
     kx_loudness loudness = {KX_LOUDNESS_MEASURE, 0.0f, 0.0f};  // its loudness spec (submit_request_loudness)
     bool metered = false;     // it came through the loudness entry: its loudness is measured, whatever its spec
     double loud_out[4] = {0.0, 1.0, 0.0, 0.0};  // metered: f64(p), g, I and n_g of the request, as the GPU computed them
+    kx_limit limit = {KX_LIMIT_GAIN, 1.0f, 0.0f, 1.0f};  // its limit spec (submit_request_limited)
+    bool limited = false;     // it came through the limiter's entry: its body is driven and limited by `limit`
+    double limit_out[5] = {0.0, 1.0, 0.0, 0.0, 1.0};  // limited: f64(p), g, I, n_g and r of the request, as the GPU computed them
     bool want_marks = false;  // the token marks of the request beside its body (submit_request_marks); a batch may mix both kinds
     // result
     void* out = nullptr;
@@ -504,12 +507,29 @@ struct Core {
                                   out_samples, out_marks || out_n_marks, out_marks, out_n_marks, err, err_len, join, nullptr, nullptr,
                                   loudness, out_loudness);
     }
+    // ... and with its limit spec; `join` may be null here (no join), out_limit may be null
+    int submit_request_limited(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
+                               const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
+                               void** out, int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
+                               const kx_join* join, const kx_limit* limit, double* out_limit, char* err, size_t err_len) {
+        if (join && !join_spec_ok(JoinSpec{join->flags, join->keep_ms, join->pause_ms, join->fade_ms})) {
+            if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: bad join");
+            return KX_ERR_INVALID;
+        }
+        if (!limit || !limit_spec_ok(LimitSpec{limit->mode, limit->gain, limit->target_lufs, limit->peak})) {
+            if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: bad limit");
+            return KX_ERR_INVALID;
+        }
+        return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
+                                  out_samples, out_marks || out_n_marks, out_marks, out_n_marks, err, err_len, join, nullptr, nullptr,
+                                  nullptr, nullptr, limit, out_limit);
+    }
     int submit_request_any(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
                            const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
                            void** out, int64_t* out_bytes, int64_t* out_samples, bool want_marks, int64_t** out_marks,
                            int64_t* out_n_marks, char* err, size_t err_len, const kx_join* join = nullptr,
                            const kx_level* level = nullptr, double* out_level = nullptr, const kx_loudness* loudness = nullptr,
-                           double* out_loudness = nullptr) {
+                           double* out_loudness = nullptr, const kx_limit* limit = nullptr, double* out_limit = nullptr) {
         const char* who = "dispatcher_submit_request";
         if (!out || !out_bytes || !out_samples) {
             if (err && err_len) snprintf(err, err_len, "%s: null output argument", who);
@@ -562,7 +582,13 @@ struct Core {
             r.loudness = *loudness;
             r.metered = true;
         }
+        if (limit) {
+            r.limit = *limit;
+            r.limited = true;
+        }
         const int rc = submit(r, out, out_bytes, out_samples, err, err_len);
+        if (rc == KX_OK && limit && out_limit)
+            for (int i = 0; i < 5; ++i) out_limit[i] = r.limit_out[i];
         if (rc == KX_OK && loudness && out_loudness)
             for (int i = 0; i < 4; ++i) out_loudness[i] = r.loud_out[i];
         if (rc == KX_OK && want_marks) {

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "kweight_coefs.h"
+#include "limit_taps.h"
 #include "resample_taps.h"
 #include "truepeak_taps.h"
 
@@ -58,6 +59,30 @@ const float* truepeak_taps() {
         Table() { std::memcpy(taps, kBits, sizeof taps); }
     } table;
     return table.taps;
+}
+
+// ---- the limiter's weights (include/kokorox_hip.h, "limiter") ---------------------------------------------------------------------
+const float* limit_taps(int rate_code) {
+    KX_REQUIRE(rate_code >= 0 && rate_code <= 3, "infer: unknown output sample rate");
+    static_assert(KX_LIMIT_MAX_NTAPS == LIMIT_MAX_TAPS && KX_LIMIT_NTAPS_48000 == LIMIT_MAX_TAPS && KX_LIMIT_W_24000 == limit_window(0) &&
+                      KX_LIMIT_W_8000 == limit_window(1) && KX_LIMIT_W_16000 == limit_window(2) && KX_LIMIT_W_48000 == limit_window(3),
+                  "the committed tables are those of W = fs / 200");
+    // (committed as bit patterns, rate codes 0..3: what the library computes with is what the generator rounded)
+    static const uint32_t kBits24000[KX_LIMIT_NTAPS_24000] = {KX_LIMIT_TAPS_24000};
+    static const uint32_t kBits8000[KX_LIMIT_NTAPS_8000] = {KX_LIMIT_TAPS_8000};
+    static const uint32_t kBits16000[KX_LIMIT_NTAPS_16000] = {KX_LIMIT_TAPS_16000};
+    static const uint32_t kBits48000[KX_LIMIT_NTAPS_48000] = {KX_LIMIT_TAPS_48000};
+    static const struct Table {
+        float taps[4][LIMIT_MAX_TAPS];
+        Table() {
+            std::memset(taps, 0, sizeof taps);
+            std::memcpy(taps[0], kBits24000, sizeof kBits24000);
+            std::memcpy(taps[1], kBits8000, sizeof kBits8000);
+            std::memcpy(taps[2], kBits16000, sizeof kBits16000);
+            std::memcpy(taps[3], kBits48000, sizeof kBits48000);
+        }
+    } table;
+    return table.taps[rate_code];
 }
 
 // ---- refusals of the host entry (Model::infer_host_once) ---------------------------------------------------------------------
@@ -131,6 +156,12 @@ void check_loudness_call(const HostCall& hc) {
     KX_REQUIRE(hc.req_loudness, "infer: null loudness argument");
     KX_REQUIRE(hc.grouped() && (hc.n_req_loudness == 1 || hc.n_req_loudness == hc.n_requests), "infer: bad loudness count");
     for (int i = 0; i < hc.n_req_loudness; ++i) KX_REQUIRE(loud_spec_ok(hc.req_loudness[i]), "infer: bad loudness");
+}
+
+void check_limit_call(const HostCall& hc) {
+    KX_REQUIRE(hc.req_limits, "infer: null limit argument");
+    KX_REQUIRE(hc.grouped() && (hc.n_req_limits == 1 || hc.n_req_limits == hc.n_requests), "infer: bad limit count");
+    for (int i = 0; i < hc.n_req_limits; ++i) KX_REQUIRE(limit_spec_ok(hc.req_limits[i]), "infer: bad limit");
 }
 
 // ---- the meter's tables (include/kokorox_hip.h, "loudness") ---------------------------------------------------------------------
@@ -221,17 +252,20 @@ OutputBounds output_bounds(const RequestLayout& lay, int B, size_t n_samples, co
         per_sample = w > per_sample ? w : per_sample;
         y_per_sample = y > y_per_sample ? y : y_per_sample;
     }
-    OutputBounds bound{n_samples * per_sample + (size_t)lay.R * 64 + 16, n_samples * y_per_sample, 0, 0, 0};
+    OutputBounds bound{n_samples * per_sample + (size_t)lay.R * 64 + 16, n_samples * y_per_sample, 0, 0, 0, 0, 0};
+    // (a layout whose limit specs are all LIMIT_NONE has no limiter: its bounds are those of the layout without them)
+    bool limited = false;
+    for (int i = 0; lay.limits && i < lay.n_limit; ++i) limited = limited || lay.limits[i].mode != LIMIT_NONE;
     if (lay.marks) {
         KX_REQUIRE(lens, "infer: marks need the token counts");
         bound.packed_bytes += 8;
         for (int b = 0; b < B; ++b) bound.packed_bytes += 8 * ((size_t)lens[b] + 1);
     }
-    if (lay.loudness) {  // (a hop is 2400 samples at 24 000 Hz, whatever the output rate)
+    if (lay.loudness || limited) {  // (a hop is 2400 samples at 24 000 Hz, whatever the output rate)
         bound.packed_bytes += 16 * (size_t)lay.R;
         bound.hop_doubles = (size_t)lay.R * (n_samples / 2400 + 1);
     }
-    if (lay.levels || lay.loudness) {  // (no request is longer than all the samples at the batch's highest ratio)
+    if (lay.levels || lay.loudness || limited) {  // (no request is longer than all the samples at the batch's highest ratio)
         bound.packed_bytes += 8 + 16 * (size_t)lay.R;
         const size_t longest = n_samples * (y_per_sample > 1 ? y_per_sample : 1);
         bound.peak_dwords = (size_t)lay.R * ((longest + (size_t)LEVEL_WINDOW - 1) / (size_t)LEVEL_WINDOW + 1);
@@ -240,7 +274,14 @@ OutputBounds output_bounds(const RequestLayout& lay, int B, size_t n_samples, co
         for (int i = 0; lay.levels && i < lay.n_level; ++i) flagged = flagged || (lay.levels[i].mode & PEAK_TRUE) != 0;
         for (int i = 0; lay.loudness && i < lay.n_loudness; ++i)
             flagged = flagged || (lay.loudness[i].mode != LOUD_NONE && (lay.loudness[i].mode & PEAK_TRUE) != 0);
+        for (int i = 0; limited && i < lay.n_limit; ++i)
+            flagged = flagged || (lay.limits[i].mode != LIMIT_NONE && (lay.limits[i].mode & PEAK_TRUE) != 0);
         if (flagged) bound.truepeak_dwords = bound.peak_dwords;
+        if (limited) {  // (the fifth block; every request limited, at the batch's highest ratio)
+            bound.packed_bytes += 40 * (size_t)lay.R;
+            bound.lim_floats = longest;
+            bound.limit_dwords = bound.peak_dwords;
+        }
     }
     return bound;
 }
@@ -264,7 +305,8 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
     const int R = lay.R;
     KX_REQUIRE(frames && lay.formats && B >= 1 && R >= 1 && (lay.n_format == 1 || lay.n_format == R) &&
                    (!lay.joins || (edges && (lay.n_join == 1 || lay.n_join == R))) && (lens || (!lay.marks && !lay.joins)) &&
-                   (!lay.levels || lay.n_level == 1 || lay.n_level == R) && (!lay.loudness || lay.n_loudness == 1 || lay.n_loudness == R),
+                   (!lay.levels || lay.n_level == 1 || lay.n_level == R) && (!lay.loudness || lay.n_loudness == 1 || lay.n_loudness == R) &&
+                   (!lay.limits || lay.n_limit == 1 || lay.n_limit == R),
                "plan: bad argument");
     auto rows_of = [&](int r) { return lay.chunks_per_request ? lay.chunks_per_request[r] : 1; };
     // the rows: what each contributes to its request's stream, and the prefix over it.  (A pass of its own: the refusals of the
@@ -353,8 +395,18 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
     }
     plan.marks_off = (plan.total_bytes + 7) & ~7L;
     // the levels: every request's spec, the block behind the marks and the grid of the peak pass
+    // (a layout whose limit specs are all LIMIT_NONE has no limiter: its plan is that of the layout without them)
+    plan.limit_spec.clear();
+    plan.limit.clear();
+    plan.limited = false;
+    plan.lim_floats = plan.limits_off = 0;
+    for (int r = 0; lay.limits && r < R; ++r) {
+        const LimitSpec& ms = lay.limits[lay.n_limit == 1 ? 0 : r];
+        KX_REQUIRE(ms.mode == LIMIT_NONE || limit_spec_ok(ms), "infer: bad limit");
+        plan.limited = plan.limited || ms.mode != LIMIT_NONE;
+    }
     plan.level.clear();
-    plan.measured = lay.levels != nullptr || lay.loudness != nullptr;
+    plan.measured = lay.levels != nullptr || lay.loudness != nullptr || plan.limited;
     plan.levelled = plan.true_peak = false;
     plan.levels_off = plan.peak_windows = 0;
     const LevelSpec plain_level{LEVEL_GAIN, 1.0f, 0.0f};
@@ -377,12 +429,37 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
     plan.loud.clear();
     plan.loud_all = false;
     plan.loud_off = plan.max_hops = 0;
-    if (lay.loudness) {
+    // A limited request is driven through the same two kernels: its derived spec is the ceiling rule 12 dB up (4 peak is exact),
+    // LEVEL_CEILING with its gain in mode 0 and LOUD_NORMALIZE with its target in mode 1, the flag carried over.
+    const LoudSpec no_loud{LOUD_NONE, 0.0f, 0.0f};
+    if (plan.limited) {
+        plan.limit_spec.resize((size_t)R);
+        plan.limit.resize((size_t)R);
+        plan.levelled = true;  // (the limited packer stages through the join table and scales the requests beside the limited ones)
+    }
+    if (lay.loudness || plan.limited) {
         plan.loud.resize((size_t)R);
         plan.loud_all = true;
         for (int r = 0; r < R; ++r) {
-            const LoudSpec& ls = lay.loudness[lay.n_loudness == 1 ? 0 : r];
+            LoudSpec ls = lay.loudness ? lay.loudness[lay.n_loudness == 1 ? 0 : r] : no_loud;
             KX_REQUIRE(ls.mode == LOUD_NONE || loud_spec_ok(ls), "infer: bad loudness");
+            if (plan.limited) {
+                const LimitSpec& ms = lay.limits[lay.n_limit == 1 ? 0 : r];
+                plan.limit_spec[(size_t)r] = ms;
+                plan.limit[(size_t)r] = LimitRow{-1, 0.0f, LIMIT_NONE};
+                if (ms.mode != LIMIT_NONE) {
+                    KX_REQUIRE(ls.mode == LOUD_NONE && level_spec_plain(plan.level[(size_t)r]), "plan: a request has a level, a loudness or a limit, not two of them");
+                    const uint32_t flag = ms.mode & PEAK_TRUE;
+                    if ((ms.mode & ~PEAK_TRUE) == LIMIT_LOUDNESS) {
+                        ls = LoudSpec{LOUD_NORMALIZE | flag, ms.target_lufs, LIMIT_DRIVE_CAP * ms.peak};
+                    } else {
+                        plan.level[(size_t)r] = LevelSpec{LEVEL_CEILING | flag, ms.gain, LIMIT_DRIVE_CAP * ms.peak};
+                        plan.true_peak = plan.true_peak || flag != 0;
+                    }
+                    plan.limit[(size_t)r] = LimitRow{plan.lim_floats, ms.peak, ms.mode};
+                    plan.lim_floats += plan.req[(size_t)r].n_samples;
+                }
+            }
             plan.loud[(size_t)r] = ls;
             if (ls.mode == LOUD_NONE) {
                 plan.loud_all = false;
@@ -395,6 +472,7 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
             plan.max_hops = hops > plan.max_hops ? hops : plan.max_hops;
         }
         plan.loud_off = plan.levels_off + 16L * R;
+        if (plan.limited) plan.limits_off = plan.loud_off + 16L * R;
     }
 }
 

@@ -304,6 +304,11 @@ struct OutputTables {
     double* loud_pow;
     // a plan with a true peak (OutputPlan::true_peak): the second partials table, plan.truepeak_dwords() dwords, scratch like peak
     uint32_t* tpeak;
+    // a plan with a limited request (OutputPlan::limited): limit [R], lpart = the partials of r, plan.limit_dwords() dwords, and lim =
+    // the limited streams back to back, plan.lim_floats floats; both scratch like peak
+    LimitRow* limit;
+    uint32_t* lpart;
+    float* lim;
 };
 // Everything between "the plan is built" and "copy to the host", for the model and for the test hook: the resampler when
 // plan.y_floats > 0 (d_y: that many floats, null when 0), the packer into d_packed (16-byte aligned, plan.total_bytes long), and

@@ -192,7 +192,8 @@ class Model {
                        int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out, int64_t* out_bytes,
                        int64_t* out_samples, int64_t** out_marks = nullptr, int64_t* out_n_marks = nullptr,
                        double* out_levels = nullptr,     // [n_requests][2] = {f64(p), g} of a call with levels (may be null)
-                       double* out_loudness = nullptr);  // [n_requests][4] = {f64(p), g, I, n_g} of a call with loudness (may be null)
+                       double* out_loudness = nullptr,   // [n_requests][4] = {f64(p), g, I, n_g} of a call with loudness (may be null)
+                       double* out_limits = nullptr);    // [n_requests][5] = {f64(p), g, I, n_g, r} of a call with limits, the limited requests' rows (may be null)
     // [0] recurrence in use: 0 = resident weights (two / four workgroups), 1 = the streaming fall-back; [1] hand-off time-outs so
     // far; [2] clean forwards left until the resident forms return (0 when they are in use); [3] calls re-run transparently
     void status(int64_t out[4]) const;
@@ -380,7 +381,7 @@ class Model {
     int64_t n_lstm_timeouts_ = 0, n_rerun_ = 0;
     void infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds, int n_speed,
                          uint64_t seed, uint32_t flags, const HostCall& hc, void** out, int64_t* out_bytes, int64_t* out_samples,
-                         int64_t** out_marks, int64_t* out_n_marks, double* out_levels, double* out_loudness);
+                         int64_t** out_marks, int64_t* out_n_marks, double* out_levels, double* out_loudness, double* out_limits);
     // host staging that asynchronous copies read / write: outlives the calling frame
     OutputPlan output_plan_;           // the tables of the running call's output stage: requests, prefixes, joins, marks, levels
     bool want_edges_ = false;          // the running host call has joins: front_half brings the rows' edge durations back

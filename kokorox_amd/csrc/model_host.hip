@@ -117,14 +117,14 @@ void Model::infer_host(const int64_t* ids, int64_t t_stride, const int32_t* lens
 void Model::infer_host_ex(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
                           int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out,
                           int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, double* out_levels,
-                          double* out_loudness) {
+                          double* out_loudness, double* out_limits) {
     try {
         infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks,
-                        out_levels, out_loudness);
+                        out_levels, out_loudness, out_limits);
     } catch (const LstmTimeout&) {
         n_rerun_ += 1;
         infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks,
-                        out_levels, out_loudness);
+                        out_levels, out_loudness, out_limits);
     }
     note_clean_forward();
 }
@@ -132,19 +132,23 @@ void Model::infer_host_ex(const int64_t* ids, int64_t t_stride, const int32_t* l
 void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
                             int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out,
                             int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
-                            double* out_levels, double* out_loudness) {
+                            double* out_levels, double* out_loudness, double* out_limits) {
     check_host_call(ids, t_stride, lens, B, speeds, hc, out, out_bytes, out_samples, n_vocab_, n_voices_, d_voices_ != nullptr);
     if (hc.join_call) check_join_call(hc);
     if (hc.req_marks) check_marks_call(hc, out_marks, out_n_marks);
     if (hc.level_call) check_level_call(hc);
     if (hc.loud_call) check_loudness_call(hc);
+    if (hc.limit_call) check_limit_call(hc);
     const bool by_voice = hc.by_voice();
     // one way to lay the output out and pack it: a call without chunks_per_request is R = B single-row requests in hc.format
     const RequestLayout layout = hc.layout(B);
     const int R = layout.R;
     const bool joins = layout.joins != nullptr;
     const bool marks = layout.marks != nullptr;  // (with chunks_per_request then: check_marks_call)
-    const bool loud = layout.loudness != nullptr;
+    // (a call with a limited request is metered and measured: the limiter's drive comes from the two gain kernels)
+    bool limited = false;
+    for (int i = 0; layout.limits && i < layout.n_limit; ++i) limited = limited || layout.limits[i].mode != LIMIT_NONE;
+    const bool loud = layout.loudness != nullptr || limited;
     const bool levels = layout.levels != nullptr || loud;  // (a call with loudness is measured: its peak pass, its levels block)
     KX_HIP(hipSetDevice(device));
     // I/O staging lives in its own arena: ids, styles, frames, noise keys, voice picks, audio, packed audio
@@ -157,6 +161,8 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     size_t peak_cap = 0;   // dwords of tables.peak
     size_t hop_cap = 0;    // doubles of tables.hops
     size_t tpeak_cap = 0;  // dwords of tables.tpeak
+    size_t lpart_cap = 0;  // dwords of tables.lpart
+    size_t lim_cap = 0;    // floats of tables.lim
     float* d_y = nullptr;  // the resampled streams of the requests with a rate code, back to back
     int *d_vid, *d_rows, *d_kinds;
     float* d_w;
@@ -189,6 +195,13 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             tables.hops = static_cast<double*>(A.alloc(bound.hop_doubles * sizeof(double)));
             tables.loud_pow = static_cast<double*>(A.alloc((size_t)4 * LOUD_POWERS * 16 * sizeof(double)));
             hop_cap = bound.hop_doubles;
+        }
+        if (limited) {  // (the limited streams and the partials of r: sized before the forward as well)
+            tables.limit = static_cast<LimitRow*>(A.alloc((size_t)R * sizeof(LimitRow)));
+            tables.lpart = static_cast<uint32_t*>(A.alloc(bound.limit_dwords * sizeof(uint32_t)));
+            tables.lim = A.f(bound.lim_floats);
+            lpart_cap = bound.limit_dwords;
+            lim_cap = bound.lim_floats;
         }
         if (marks) tables.mark = static_cast<MarkRow*>(A.alloc((size_t)B * sizeof(MarkRow)));
         d_packed = A.alloc(bound.packed_bytes);  // compact output: the requests back to back, then the marks
@@ -249,6 +262,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         KX_REQUIRE((size_t)plan.peak_dwords() <= peak_cap, "levels: the peak table is too small");
         KX_REQUIRE((size_t)plan.hop_doubles() <= hop_cap, "loudness: the hop table is too small");
         KX_REQUIRE((size_t)plan.truepeak_dwords() <= tpeak_cap, "levels: the true-peak table is too small");
+        KX_REQUIRE((size_t)plan.limit_dwords() <= lpart_cap && (size_t)plan.lim_floats <= lim_cap, "limiter: the limit buffer is too small");
         launch_output_plan(d_audio, ld, call_.d_dur, call_.dT, plan, tables, d_y, d_packed, stream_);
         const int64_t marks_off = plan.marks_off, n_marks = plan.n_marks;
         const int64_t total = n_marks > 0 || plan.measured ? plan.end_bytes() : plan.total_bytes;
@@ -270,6 +284,9 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         *out = host;
         if (marks) *out_marks = n_marks > 0 ? reinterpret_cast<int64_t*>(host + marks_off) : nullptr;
         if (plan.measured && out_levels) memcpy(out_levels, host + plan.levels_off, (size_t)R * 16);
+        if (plan.limited && out_limits)
+            for (int r = 0; r < R; ++r)
+                if (plan.limit[(size_t)r].off >= 0) memcpy(out_limits + 5 * r, host + plan.limits_off + 40 * (size_t)r, 40);
         if (!plan.loud.empty() && out_loudness)
             for (int r = 0; r < R; ++r) {  // {f64(p), g} of the levels block, {I, n_g} of the loudness block
                 memcpy(out_loudness + 4 * r, host + plan.levels_off + 16 * (size_t)r, 16);

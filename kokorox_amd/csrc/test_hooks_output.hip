@@ -32,11 +32,24 @@ int kx_test_output_plan_loudness(int device_id, const float* audio, int B, int64
                                  int64_t* out_n_marks, const kx_level* levels, double* out_levels, const kx_loudness* loudness,
                                  double* out_loudness, double* out_hops, int64_t hops_cap, int64_t* out_n_hops, char* err,
                                  size_t err_len) {
+    return kx_test_output_plan_limited(device_id, audio, B, audio_ld, frames_in, dur, lens, chunks_per_request, R, formats, joins, want,
+                                       out, out_cap, out_bytes, out_samples, out_marks, marks_cap, out_n_marks, levels, out_levels,
+                                       loudness, out_loudness, out_hops, hops_cap, out_n_hops, nullptr, nullptr, err, err_len);
+}
+
+int kx_test_output_plan_limited(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames_in,
+                                const int32_t* dur, const int32_t* lens, const int32_t* chunks_per_request, int R,
+                                const int32_t* formats, const kx_join* joins, const uint8_t* want, void* out, int64_t out_cap,
+                                int64_t* out_bytes, int64_t* out_samples, int64_t* out_marks, int64_t marks_cap,
+                                int64_t* out_n_marks, const kx_level* levels, double* out_levels, const kx_loudness* loudness,
+                                double* out_loudness, double* out_hops, int64_t hops_cap, int64_t* out_n_hops, const kx_limit* limits,
+                                double* out_limits, char* err, size_t err_len) {
     return guarded_free(err, err_len, [&] {
         check_device(device_id);
         KX_REQUIRE(formats && out_bytes && out_samples && out_n_marks && B > 0 && R > 0 && (frames_in ? !dur : dur && lens) &&
                        ((!want && !joins) || dur) && (audio ? out != nullptr : out_cap == 0 && dur) && (levels ? audio && out_levels : !out_levels) &&
-                       (loudness ? audio && out_loudness && out_hops && out_n_hops && hops_cap >= 0 : !out_loudness && !out_hops && !out_n_hops),
+                       (loudness ? audio && out_loudness && out_hops && out_n_hops && hops_cap >= 0 : !out_loudness && !out_hops && !out_n_hops) &&
+                       (limits ? audio && out_limits : !out_limits),
                    "test_output_plan: bad argument");
         // what the forward would have brought back: the rows' frame counts and the durations of their two edge tokens
         std::vector<int> frames((size_t)B, 0), edges((size_t)2 * B, 0);
@@ -65,8 +78,14 @@ int kx_test_output_plan_loudness(int device_id, const float* audio, int B, int64
         const kx::LoudSpec* dspecs = reinterpret_cast<const kx::LoudSpec*>(loudness);
         for (int r = 0; loudness && r < R; ++r)
             KX_REQUIRE(dspecs[r].mode == kx::LOUD_NONE || kx::loud_spec_ok(dspecs[r]), "infer: bad loudness");
+        // (a limit spec of mode 0xFFFFFFFF: that request is not limited, as a request beside limited ones in a batch)
+        static_assert(sizeof(kx_limit) == sizeof(kx::LimitSpec), "kx_limit is LimitSpec");
+        const kx::LimitSpec* mspecs = reinterpret_cast<const kx::LimitSpec*>(limits);
+        for (int r = 0; limits && r < R; ++r)
+            KX_REQUIRE(mspecs[r].mode == kx::LIMIT_NONE || kx::limit_spec_ok(mspecs[r]), "infer: bad limit");
         // the planner and the launcher of Model::infer_host_once
-        const kx::RequestLayout layout{chunks_per_request, R, formats, R, want, specs, R, lspecs, levels ? R : 0, dspecs, loudness ? R : 0};
+        const kx::RequestLayout layout{chunks_per_request, R, formats, R, want, specs, R, lspecs, levels ? R : 0, dspecs, loudness ? R : 0,
+                                       mspecs, limits ? R : 0};
         kx::OutputPlan plan;
         kx::build_output_plan(frames.data(), lens, joins ? edges.data() : nullptr, B, layout, plan);
         for (int r = 0; r < R; ++r) {
@@ -91,21 +110,31 @@ int kx_test_output_plan_loudness(int device_id, const float* audio, int B, int64
         uint32_t* d_tpeak = plan.true_peak ? guarded_bytes<uint32_t>(dm, n_tpeak, 0x7F) : nullptr;
         // the hop energies of the meter: poisoned with NaNs (an entry the launch did not write must not be read), the guard behind them
         const size_t n_hop = (size_t)plan.hop_doubles();
-        double* d_hops = loudness ? guarded_bytes<double>(dm, n_hop, 0xFF) : nullptr;
+        const bool metered = !plan.loud.empty();  // (a plan with a limited request has the meter's tables, whatever the call gave)
+        double* d_hops = metered ? guarded_bytes<double>(dm, n_hop, 0xFF) : nullptr;
+        // the limiter's partials, poisoned with zeros (the smallest value of their order: an entry the launch did not write must not
+        // be read), and the limit buffer, poisoned with NaNs; the guards behind them
+        const size_t n_lpart = (size_t)plan.limit_dwords(), n_lim = (size_t)plan.lim_floats;
+        uint32_t* d_lpart = plan.limited ? guarded_bytes<uint32_t>(dm, n_lpart, 0x00) : nullptr;
+        float* d_lim = plan.limited ? guarded_bytes<float>(dm, n_lim, 0xFF) : nullptr;
         const kx::OutputTables tables{dm.get<kx::PackReq>((size_t)R), dm.get<long>((size_t)B + 1), dm.get<kx::JoinRow>((size_t)B),
                                       dm.get<kx::MarkRow>((size_t)B), plan.measured ? dm.get<kx::LevelSpec>((size_t)R) : nullptr, d_peak,
-                                      loudness ? dm.get<kx::LoudSpec>((size_t)R) : nullptr, d_hops,
-                                      loudness ? dm.get<double>((size_t)4 * kx::LOUD_POWERS * 16) : nullptr, d_tpeak};
+                                      metered ? dm.get<kx::LoudSpec>((size_t)R) : nullptr, d_hops,
+                                      metered ? dm.get<double>((size_t)4 * kx::LOUD_POWERS * 16) : nullptr, d_tpeak,
+                                      plan.limited ? dm.get<kx::LimitRow>((size_t)R) : nullptr, d_lpart, d_lim};
         const int* d_dur = dur ? dm.up(dur, (size_t)B * 512) : nullptr;
         const int* d_len = dur ? dm.up(lens, (size_t)B) : nullptr;
         // guards: 64 bytes after the last region, after the resampled streams, after the last mark and after the levels, which
         // the kernels must leave alone.  The marks block is moved 64 bytes back for the first of them, the levels block 64 more
         // for the third (the kernels are handed the addresses, still 8-aligned; the offsets themselves are nothing they see).
         // (the loudness block stays right behind the levels: the two count as one here)
-        const long body = audio ? plan.total_bytes : 0, n_mk = plan.n_marks * 8, n_lv = plan.measured ? (loudness ? 32L : 16L) * R : 0;
+        // (and the limits block right behind the loudness)
+        const long body = audio ? plan.total_bytes : 0, n_mk = plan.n_marks * 8;
+        const long n_lv = plan.measured ? (plan.limited ? 72L : (metered ? 32L : 16L)) * R : 0;
         if (audio) plan.marks_off += GUARD_BYTES;
         if (plan.measured) plan.levels_off += 2 * GUARD_BYTES;
-        if (loudness) plan.loud_off = plan.levels_off + 16L * R;
+        if (metered) plan.loud_off = plan.levels_off + 16L * R;
+        if (plan.limited) plan.limits_off = plan.loud_off + 16L * R;
         const long mk_off = audio ? plan.marks_off : 0, lv_off = plan.measured ? plan.levels_off : mk_off + n_mk;
         const long d_out_bytes = plan.measured ? lv_off + n_lv + GUARD_BYTES : mk_off + n_mk + GUARD_BYTES;
         char* d_out = dm.get<char>((size_t)d_out_bytes);
@@ -138,7 +167,13 @@ int kx_test_output_plan_loudness(int device_id, const float* audio, int B, int64
                     if (out_n_hops[r] > 0)
                         KX_HIP(hipMemcpy(out_hops + (size_t)r * hops_cap, d_hops + (size_t)r * plan.max_hops, (size_t)out_n_hops[r] * 8,
                                          hipMemcpyDeviceToHost));
-                guard_untouched(d_hops + n_hop, "test_output_plan: the meter wrote past its table");
+            }
+            if (metered) guard_untouched(d_hops + n_hop, "test_output_plan: the meter wrote past its table");
+            if (plan.limited) {  // the rows of the limited requests; the others' are left as the caller gave them
+                for (int r = 0; r < R; ++r)
+                    if (plan.limit[(size_t)r].off >= 0) std::memcpy(out_limits + 5 * r, &lv[(size_t)4 * R + 5 * r], 40);
+                guard_untouched(d_lpart + n_lpart, "test_output_plan: the limiter wrote past its partials");
+                guard_untouched(d_lim + n_lim, "test_output_plan: the limiter wrote past the limit buffer");
             }
             guard_untouched(d_out + lv_off - GUARD_BYTES, "test_output_plan: a kernel wrote in front of the levels");
             guard_untouched(d_out + lv_off + n_lv, "test_output_plan: the kernel wrote past the last level");

@@ -41,6 +41,11 @@ LOUDNESS_MEASURE, LOUDNESS_NORMALIZE = 0, 1
 LOUDNESS_DTYPE = np.dtype([("mode", "<u4"), ("target_lufs", "<f4"), ("peak", "<f4")])
 LOUDNESS_METER = (LOUDNESS_MEASURE, 0.0, 0.0)
 LOUDNESS_NONE = (0xFFFFFFFF, 0.0, 0.0)  # the test hook only: a request beside metered ones that is not metered
+# limiter (include/kokorox_hip.h, "limiter"): a spec is (mode, gain, target_lufs, peak), the layout of kx_limit
+LIMIT_GAIN, LIMIT_LOUDNESS = 0, 1
+LIMIT_MAX_TAPS = 481
+LIMIT_DTYPE = np.dtype([("mode", "<u4"), ("gain", "<f4"), ("target_lufs", "<f4"), ("peak", "<f4")])
+LIMIT_NONE = (0xFFFFFFFF, 1.0, 0.0, 1.0)  # the test hook only: a request beside limited ones that has no limiter
 KX_OK, KX_ERR_INVALID, KX_ERR_IO, KX_ERR_DEVICE, KX_ERR_STATE = 0, 1, 2, 3, 4  # include/kokorox_hip.h
 KX_FLAG_NOISE_OFF = 1
 KX_FLAG_TAPS = 2
@@ -149,6 +154,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                              vp, vp, vp, i32, vp, i32, vp]),
         "kx_dispatcher_submit_request_loudness": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
                                                         C.POINTER(i64), vp, vp, vp, vp, vp, cp, sz]),
+        "kx_limit_filter": (i32, [i32, vp, vp, i32]),
+        "kx_infer_requests_limited": (i32, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, u64, u32, vp, i32, C.POINTER(vp), vp, vp,
+                                            vp, vp, vp, i32, vp, i32, vp]),
+        "kx_dispatcher_submit_request_limited": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
+                                                       C.POINTER(i64), vp, vp, vp, vp, vp, cp, sz]),
         "kx_dispatcher_create": (vp, [vp, i32, i32, i32, cp, sz]),
         "kx_dispatcher_create_warm": (vp, [vp, i32, i32, i32, i32, i32, cp, sz]),
         "kx_dispatcher_submit": (i32, [vp, vp, i32, vp, f32, u64, C.POINTER(C.POINTER(f32)), C.POINTER(i64), cp, sz]),
@@ -192,6 +202,8 @@ def _test_signatures():
                                                cp, sz]),
         "kx_test_output_plan_loudness": (i32, [i32, vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp,
                                                vp, vp, vp, i64, vp, cp, sz]),
+        "kx_test_output_plan_limited": (i32, [i32, vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp,
+                                              vp, vp, vp, i64, vp, vp, vp, cp, sz]),
         "kx_test_lstm_ragged": (i32, [i32, vp, vp, i32, i32, i32] + [vp] * 8 + [i32, i32, u32, vp, cp, sz]),
         "kx_test_alignment": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, cp, sz]),
         "kx_test_embed": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, cp, sz]),
@@ -232,7 +244,7 @@ ABI_SYMBOLS = [
     "kx_free_audio", "kx_infer_device", "kx_sync", "kx_set_pinned_durations", "kx_warmup", "kx_arena_bytes", "kx_call_times", "kx_model_status", "kx_model_info", "kx_dispatcher_health", "kx_set_utterance_base", "kx_set_lanes",
     "kx_set_conv_mode", "kx_get_conv_mode", "kx_set_stft_variant", "kx_get_stft_variant",
     "kx_profile_enable", "kx_profile_read", "kx_profile_detail", "kx_profile_aux", "kx_diag_enable", "kx_diag_count", "kx_diag_get", "kx_set_act_prescale", "kx_set_voice_table", "kx_infer_voices",
-    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_infer_requests_levelled", "kx_dispatcher_submit_request_levelled", "kx_loudness_filter", "kx_truepeak_filter", "kx_infer_requests_loudness", "kx_dispatcher_submit_request_loudness", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
+    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_infer_requests_levelled", "kx_dispatcher_submit_request_levelled", "kx_loudness_filter", "kx_truepeak_filter", "kx_infer_requests_loudness", "kx_dispatcher_submit_request_loudness", "kx_limit_filter", "kx_infer_requests_limited", "kx_dispatcher_submit_request_limited", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
     "kx_dispatcher_stats", "kx_dispatcher_failures", "kx_dispatcher_destroy", "kx_debug_tap",
 ]
 
@@ -290,6 +302,33 @@ def loudness_specs(loudness, n=None) -> np.ndarray:
     if n is not None and a.shape[0] != n:
         raise ValueError(f"{n} loudness specs are required")
     return a
+
+
+def limit_specs(limits, n=None) -> np.ndarray:
+    """Limit specs as the array of kx_limit the library takes: one (mode, gain, target_lufs, peak) tuple, a list of them, or an
+    array of LIMIT_DTYPE already.  n: the count expected (a single tuple is repeated).  A mode may carry PEAK_TRUE: the envelope
+    the limiter follows is then the four-times oversampled one and the reported p the true peak."""
+    if isinstance(limits, np.ndarray) and limits.dtype == LIMIT_DTYPE:
+        a = np.ascontiguousarray(limits).reshape(-1)
+    else:
+        lm = list(limits)
+        if lm and not isinstance(lm[0], (tuple, list, np.void)):
+            lm = [tuple(lm)] * (n or 1)
+        a = np.array([(int(m), float(g), float(t), float(p)) for m, g, t, p in lm], dtype=LIMIT_DTYPE)
+    if n is not None and a.shape[0] != n:
+        raise ValueError(f"{n} limit specs are required")
+    return a
+
+
+def limit_filter(word: int):
+    """(W, taps): the limiter's window W = fs / 200 and its 2 W + 1 smoothing weights as float32 at a format word's rate, from
+    the library's one table (kx_limit_filter; host only, no GPU)."""
+    W = C.c_int32(0)
+    taps = np.zeros(LIMIT_MAX_TAPS, dtype=np.float32)
+    rc = load_library().kx_limit_filter(int(word), C.byref(W), _ptr(taps), LIMIT_MAX_TAPS)
+    if rc != KX_OK:
+        raise KokoroxHipError(rc, "unknown output format or sample rate")
+    return int(W.value), taps[: 2 * int(W.value) + 1].copy()
 
 
 def loudness_filter(word: int) -> np.ndarray:
@@ -567,8 +606,23 @@ class HipKoko:
         out = (res, mk, out_ld) if marks else (res, out_ld)
         return out + (nsamp,) if with_samples else out
 
+    def infer_requests_limited(self, tokens, chunks_per_request, limits, joins=None, styles=None, voice_ids=None, weights=None,
+                               speeds=(1.0,), seed: int = 0, flags: int = 0, fmt=0, marks: bool = False, with_samples: bool = False):
+        """infer_requests with every request driven and peak-limited on the GPU (kx_infer_requests_limited; the definition is in
+        include/kokorox_hip.h, "limiter", the numpy form voices.limit_stream): `limits` = one spec (mode, gain, target_lufs, peak)
+        for all requests, or a list of one per request; `joins` as infer_requests_joined, or None.  Returns (bodies, limits) with
+        limits a float64 array [R, 5] = the peak p, the static gain g, the integrated loudness I (NaN in mode 0 and when undefined),
+        the gated blocks n_g and the smallest smoothed gain r of every request as the GPU computed them; marks=True: (bodies,
+        marks, limits).  with_samples: out_samples as a last entry."""
+        lm = limit_specs(limits)
+        j = None if joins is None else join_specs(joins)
+        res, mk, nsamp, out_lm = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, marks,
+                                                      j, None, None, lm)
+        out = (res, mk, out_lm) if marks else (res, out_lm)
+        return out + (nsamp,) if with_samples else out
+
     def _infer_requests(self, tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, want_marks, joins=None,
-                        levels=None, loudness=None):
+                        levels=None, loudness=None, limits=None):
         ids, lens = self._ids_lens(tokens)
         B = len(tokens)
         cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32).reshape(-1)
@@ -590,7 +644,12 @@ class HipKoko:
         marks = None
         if want_marks:
             mk, n_mk = C.c_void_p(), np.zeros(max(R, 1), np.int64)
-        if loudness is not None:
+        if limits is not None:
+            out_lv = np.zeros((max(R, 1), 5), np.float64)
+            self._check(self._lib.kx_infer_requests_limited(*args, C.byref(mk) if want_marks else None, _ptr(n_mk) if want_marks else None,
+                                                            _ptr(joins), 0 if joins is None else joins.shape[0], _ptr(limits),
+                                                            limits.shape[0], _ptr(out_lv)))
+        elif loudness is not None:
             out_lv = np.zeros((max(R, 1), 4), np.float64)
             self._check(self._lib.kx_infer_requests_loudness(*args, C.byref(mk) if want_marks else None, _ptr(n_mk) if want_marks else None,
                                                              _ptr(joins), 0 if joins is None else joins.shape[0], _ptr(loudness),
@@ -622,7 +681,7 @@ class HipKoko:
             part = raw[o: o + int(nbytes[r])]
             o += int(nbytes[r])
             res.append(_decode_packed(part, int(fm[r if fm.shape[0] > 1 else 0])))
-        if levels is not None or loudness is not None:
+        if levels is not None or loudness is not None or limits is not None:
             return res, marks, [int(v) for v in nsamp[:R]], out_lv[:R]
         return res, marks, [int(v) for v in nsamp[:R]]
 
@@ -838,7 +897,7 @@ class Dispatcher:
         return arr.reshape(-1, 2) if fmt == 1 else arr
 
     def submit_request(self, chunks: Sequence[Sequence[int]], styles=None, voices=None, speed: float = 1.0, seed: int = 0,
-                       fmt: int = 0, marks: bool = False, join=None, level=None, loudness=None):
+                       fmt: int = 0, marks: bool = False, join=None, level=None, loudness=None, limit=None):
         """A request of 1 .. max_batch chunks (kx_dispatcher_submit_request): `chunks` = the 0-wrapped id lists; `styles` = one
         256-float row per chunk, OR `voices` as in submit_ex (one voice spec for the request); `fmt` = a format word (a PACK_*
         form, optionally | PACK_RATE_*).  Returns what HipKoko.infer_requests returns for one request: an array (forms 0..2, 8, 9)
@@ -848,7 +907,9 @@ class Dispatcher:
         level = (mode, gain, peak) (kx_dispatcher_submit_request_levelled): the request's level set as
         HipKoko.infer_requests_levelled sets it; the result then ends with a float64 pair, the request's peak p and gain g.
         loudness = (mode, target_lufs, peak) (kx_dispatcher_submit_request_loudness): the request's loudness measured and set as
-        HipKoko.infer_requests_loudness does; the result then ends with four float64 values, p, g, I and n_g."""
+        HipKoko.infer_requests_loudness does; the result then ends with four float64 values, p, g, I and n_g.
+        limit = (mode, gain, target_lufs, peak) (kx_dispatcher_submit_request_limited): the request driven and peak-limited as
+        HipKoko.infer_requests_limited does; the result then ends with five float64 values, p, g, I, n_g and r."""
         lens = np.array([len(c) for c in chunks], dtype=np.int32)
         a = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.int64).reshape(-1) for c in chunks])
                                  if len(chunks) else np.zeros(0, np.int64))
@@ -873,9 +934,15 @@ class Dispatcher:
         mk, n_mk = C.c_void_p(), C.c_int64(0)
         lv_out = np.zeros(2, np.float64)
         ld_out = np.zeros(4, np.float64)
-        if loudness is not None and level is not None:
-            raise ValueError("submit_request: a request has a level or a loudness, not both")
-        if loudness is not None:
+        lm_out = np.zeros(5, np.float64)
+        if (loudness is not None) + (level is not None) + (limit is not None) > 1:
+            raise ValueError("submit_request: a request has a level or a loudness, not both" if limit is None else
+                             "submit_request: a request has a level, a loudness or a limit, not two of them")
+        if limit is not None:
+            j = None if join is None else join_specs(join, 1)
+            rc = self._lib.kx_dispatcher_submit_request_limited(*args, C.byref(mk) if marks else None, C.byref(n_mk) if marks else None,
+                                                                _ptr(j), _ptr(limit_specs(limit, 1)), _ptr(lm_out), err, len(err))
+        elif loudness is not None:
             j = None if join is None else join_specs(join, 1)
             rc = self._lib.kx_dispatcher_submit_request_loudness(*args, C.byref(mk) if marks else None, C.byref(n_mk) if marks else None,
                                                                  _ptr(j), _ptr(loudness_specs(loudness, 1)), _ptr(ld_out), err, len(err))
@@ -904,6 +971,7 @@ class Dispatcher:
         res = (_decode_packed(raw, fmt), m) if marks else (_decode_packed(raw, fmt),)
         res = res + (lv_out,) if level is not None else res
         res = res + (ld_out,) if loudness is not None else res
+        res = res + (lm_out,) if limit is not None else res
         return res if len(res) > 1 else res[0]
 
     def stats(self):
@@ -1350,12 +1418,15 @@ def weight_images(sources, up_stride=0, device=0):
     return out
 
 
-def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, want, pauses, device, levels=None, loudness=None):
+def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, want, pauses, device, levels=None, loudness=None, limits=None):
     """kx_test_output_plan, the one hook of the output stage: the model's planner and launcher on host arrays (None where the
     hook takes a null pointer; include/kokorox_hip_test.h).  Returns (bodies as bytes, out_samples, marks as int64 arrays).
     levels (an array of LEVEL_DTYPE, [R]): kx_test_output_plan_levelled, and a fourth entry, the levels as float64 [R, 2].
     loudness (an array of LOUDNESS_DTYPE, [R]; levels may then be None): kx_test_output_plan_loudness, and the fourth entry is
-    the pair (loudness as float64 [R, 4] = p, g, I, n_g; the hop energies e[k] of every request as one float64 array each)."""
+    the pair (loudness as float64 [R, 4] = p, g, I, n_g; the hop energies e[k] of every request as one float64 array each).
+    limits (an array of LIMIT_DTYPE, [R]; levels and loudness may then be None): kx_test_output_plan_limited, and the fourth entry
+    is the triple (levels [R, 2] or None, loudness [R, 4] or None, limits as float64 [R, 5] = p, g, I, n_g, r, the rows of the
+    requests without a limiter left at -1)."""
     lib = load_test_library()
     B = len(frames if dur is None else lens)
     fm = np.ascontiguousarray(formats, dtype=np.int32)
@@ -1382,7 +1453,17 @@ def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, w
     nb, ns, nm = np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int64)
     args = (device, _ptr(audio), B, ld, _ptr(fr), _ptr(dur), _ptr(ln), _ptr(cpr), R, _ptr(fm), _ptr(joins), _ptr(wt),
             _ptr(out) if audio is not None else None, cap, _ptr(nb), _ptr(ns), _ptr(mk), mcap, _ptr(nm))
-    if loudness is not None:
+    if limits is not None:
+        assert limits.dtype == LIMIT_DTYPE and limits.shape == (R,) and (levels is None or (levels.dtype == LEVEL_DTYPE and levels.shape == (R,)))
+        assert loudness is None or (loudness.dtype == LOUDNESS_DTYPE and loudness.shape == (R,))
+        out_lv = np.zeros((R, 2), dtype=np.float64) if levels is not None else None
+        out_ld = np.full((R, 4), -1.0, dtype=np.float64) if loudness is not None else None
+        out_lm = np.full((R, 5), -1.0, dtype=np.float64)
+        hcap = (600 * n_frames + pauses) // 1200 + 1 if loudness is not None else 0
+        hops, n_hops = (np.zeros((R, hcap), dtype=np.float64), np.zeros(R, dtype=np.int64)) if loudness is not None else (None, None)
+        _err_call(lib.kx_test_output_plan_limited, *args, _ptr(levels), _ptr(out_lv), _ptr(loudness), _ptr(out_ld), _ptr(hops), hcap,
+                  _ptr(n_hops), _ptr(limits), _ptr(out_lm))
+    elif loudness is not None:
         assert loudness.dtype == LOUDNESS_DTYPE and loudness.shape == (R,) and (levels is None or (levels.dtype == LEVEL_DTYPE and levels.shape == (R,)))
         out_lv = np.zeros((R, 2), dtype=np.float64)
         out_ld = np.full((R, 4), -1.0, dtype=np.float64)
@@ -1401,6 +1482,8 @@ def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, w
         res.append(raw[o: o + int(nb[r])] if audio is not None else b"")
         o += int(nb[r])
     marks = [m.copy() for m in np.split(mk[: int(nm.sum())], np.cumsum(nm)[:-1])]
+    if limits is not None:
+        return res, [int(v) for v in ns], marks, (out_lv, out_ld, out_lm)
     if loudness is not None:
         return res, [int(v) for v in ns], marks, (out_ld, [hops[r, : int(n_hops[r])].copy() for r in range(R)])
     if levels is not None:
@@ -1464,3 +1547,21 @@ def loudness_requests(audio, dur, lens, chunks_per_request, formats, loudness, j
     pauses = 0 if j is None else sum(24 * int(j["pause_ms"][r]) * (int(chunks_per_request[r]) - 1) for r in range(R))
     res, ns, marks, (out_ld, hops) = _output_plan(audio, frames, dur, lens, chunks_per_request, formats, j, want, pauses, device, lv, ld)
     return res, ns, marks, out_ld, hops
+
+
+def limit_requests(audio, dur, lens, chunks_per_request, formats, limits, joins=None, want=None, frames=None, levels=None, loudness=None,
+                   device=0):
+    """Limited requests alone (kx_test_output_plan_limited): everything as loudness_requests takes it, limits = one (mode, gain,
+    target_lufs, peak) spec per request, LIMIT_NONE for a request without a limiter (its level or loudness spec, if given, then
+    applies; a limited request's level spec is the plain one and its loudness spec LOUDNESS_NONE).  Returns (bodies as bytes,
+    out_samples, marks, limits as float64 [R, 5] = p, g, I, n_g and r of every limited request, levels [R, 2] or None, loudness
+    [R, 4] or None): voices.limited_body and voices.limit_stream."""
+    R = len(lens if dur is not None else frames) if chunks_per_request is None else len(chunks_per_request)
+    lm = limit_specs(limits, R)
+    ld = None if loudness is None else loudness_specs(loudness, R)
+    lv = None if levels is None else level_specs(levels, R)
+    j = None if joins is None else join_specs(joins, R)
+    pauses = 0 if j is None else sum(24 * int(j["pause_ms"][r]) * (int(chunks_per_request[r]) - 1) for r in range(R))
+    res, ns, marks, (out_lv, out_ld, out_lm) = _output_plan(audio, frames, dur, lens, chunks_per_request, formats, j, want, pauses, device,
+                                                            lv, ld, lm)
+    return res, ns, marks, out_lm, out_lv, out_ld

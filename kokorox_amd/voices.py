@@ -495,6 +495,111 @@ def loudness_body(z, g: float, word: int) -> bytes:
         return stream_body((np.float64(g) * z.astype(np.float64)).astype(np.float32), word)
 
 
+LIMIT_GAIN, LIMIT_LOUDNESS = 0, 1
+_WORD_RATE = {0: 24000, 1: 8000, 2: 16000, 3: 48000}  # rate code of a format word -> Hz
+
+
+def limit_taps(rate: int):
+    """(W, h): the limiter's window W = rate / 200 and its 2 W + 1 smoothing weights as float32 at an output rate (24000, 8000,
+    16000 or 48000 Hz), from the library's one table (kokorox_amd/csrc/limit_taps.h through kx_limit_filter)."""
+    from . import hip_koko as hk
+    if int(rate) not in _RATE_WORD:
+        raise ValueError("limit_taps: the rate is 24000, 8000, 16000 or 48000")
+    return hk.limit_filter(_RATE_WORD[int(rate)])
+
+
+def _limit_fields(limit):
+    """(mode, gain, target_lufs, peak) of a valid limit spec (include/kokorox_hip.h, "limiter"), the three floats as float32.  The
+    mode may carry PEAK_TRUE.  Every comparison is written so that a NaN fails it."""
+    mode, gain, target, peak = limit
+    with np.errstate(over="ignore", invalid="ignore"):
+        gain, target, peak = np.float32(gain), np.float32(target), np.float32(peak)
+    ok = isinstance(mode, (int, np.integer)) and not isinstance(mode, bool) and (mode & ~PEAK_TRUE) in (0, 1)
+    ok = ok and bool(np.float32(2.0 ** -15) <= peak <= np.float32(1))
+    if ok and mode & ~PEAK_TRUE == LIMIT_GAIN:
+        ok = bool(np.float32(0) <= gain <= np.float32(64)) and target.tobytes() == np.float32(0).tobytes()
+    elif ok:
+        ok = bool(gain == np.float32(1)) and bool(np.float32(-70) <= target <= np.float32(0))
+    if not ok:
+        raise ValueError("limit: mode 0 (| PEAK_TRUE) with 0 <= gain <= 64 and target +0, or mode 1 (| PEAK_TRUE) with gain 1 and "
+                         "-70 <= target_lufs <= 0; 2^-15 <= peak <= 1")
+    return int(mode), gain, target, peak
+
+
+def limit_curve(z1, peak, word: int, true_peak_flag: bool = False):
+    """(s, a) of the driven stream z1 (float32, at the rate of the format word `word`) by the definition of include/kokorox_hip.h,
+    "limiter": the envelope a as float32 (|z1|, 0 where z1 is not finite; with true_peak_flag the largest of it and the three
+    interpolated values either side), the required gain c, its sliding minimum m over [j - W, j + W] with c = 1 outside the stream,
+    and the smoothed gain s as float64: the sum over j = n - W .. n + W ascending of f64(h[j - n + W]) f64(m[j]) from +0, and 1.0
+    exactly where every m of the sum is 1.  Vectorised over n, the weights one after the other: the order of every chain is the GPU's."""
+    z1 = np.ascontiguousarray(z1, dtype=np.float32).reshape(-1)
+    peak = np.float32(peak)
+    N = z1.shape[0]
+    W, h = limit_taps(_WORD_RATE[(int(word) >> 8) & 15])
+    x = np.where(np.isfinite(z1), z1, np.float32(0)).astype(np.float32)
+    a = np.abs(x)
+    if N == 0:
+        return np.zeros(0, dtype=np.float64), a
+    if true_peak_flag:
+        taps = true_peak_taps().astype(np.float64)
+        xp = np.concatenate([np.zeros(11), x.astype(np.float64), np.zeros(12)])
+        e = np.zeros(N, dtype=np.float32)
+        with np.errstate(over="ignore"):
+            for phi in range(3):
+                acc = np.zeros(N, dtype=np.float64)
+                for k in range(24):  # j = n - 11 + k, tap n - j + 12 = 23 - k
+                    acc = acc + taps[phi, 23 - k] * xp[k: k + N]
+                e = np.maximum(e, np.abs(acc.astype(np.float32)))
+        a = np.maximum(a, np.maximum(e, np.concatenate([np.zeros(1, dtype=np.float32), e[:-1]])))
+    with np.errstate(divide="ignore", over="ignore", under="ignore"):
+        c = np.where(a <= peak, np.float32(1), (np.float64(peak) / a.astype(np.float64)).astype(np.float32)).astype(np.float32)
+    cp = np.concatenate([np.ones(2 * W, dtype=np.float32), c, np.ones(2 * W, dtype=np.float32)])
+    m = np.lib.stride_tricks.sliding_window_view(cp, 2 * W + 1).min(axis=1)  # m[j], j = -W .. N + W - 1
+    ones = np.lib.stride_tricks.sliding_window_view(m, 2 * W + 1).min(axis=1) == np.float32(1)  # every m of sample n's sum is 1
+    m64, h64 = m.astype(np.float64), h.astype(np.float64)
+    s = np.zeros(N, dtype=np.float64)
+    for i in range(2 * W + 1):
+        s = s + h64[i] * m64[i: i + N]
+    return np.where(ones, np.float64(1.0), s), a
+
+
+def limit_stream(z, limit, word: int, g=None):
+    """(z2, p, g, I, n_g, r) of ONE request's stream z, which is at the rate of `word` already, by the definition of
+    include/kokorox_hip.h, "limiter": limit = (mode, gain, target_lufs, peak).  p = the sample peak, or true_peak(z) with
+    PEAK_TRUE; g = the drive (mode 0: gain; mode 1: 10^((target - I) / 20) where I is defined, else 1), capped where g p would
+    pass 4 peak; z1 = f32(g f64(z)); s of limit_curve; z2 = f32(s f64(z1)) clamped to +-peak; r = the smallest f32(s), 1.0 for an
+    empty stream.  I is NaN and n_g 0 in mode 0.  `g` given: that drive is taken as it is (the GPU's, whose meter agrees with this
+    one to 1e-8 and not to the bit), everything behind it follows."""
+    mode, gain, target, peak = _limit_fields(limit)
+    z = np.ascontiguousarray(z, dtype=np.float32).reshape(-1)
+    flag = bool(mode & PEAK_TRUE)
+    p, _ = level_gain(z, (LEVEL_GAIN | (PEAK_TRUE if flag else 0), 1.0, 0.0))
+    I, n_g = float("nan"), 0
+    if mode & ~PEAK_TRUE == LIMIT_LOUDNESS:
+        I, n_g, _ = integrated_loudness(z, _WORD_RATE[(int(word) >> 8) & 15])
+    if g is None:
+        g = np.float64(gain)
+        if mode & ~PEAK_TRUE == LIMIT_LOUDNESS:
+            g = np.float64(10.0) ** ((np.float64(target) - np.float64(I)) / np.float64(20.0)) if not np.isnan(I) else np.float64(1.0)
+        cap = np.float64(4.0) * np.float64(peak)
+        if bool(np.float32(0) < p < np.float32(np.inf)) and g * np.float64(p) > cap:
+            g = cap / np.float64(p)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        z1 = (np.float64(g) * z.astype(np.float64)).astype(np.float32)
+        s, _ = limit_curve(z1, peak, word, flag)
+        z2 = (s * z1.astype(np.float64)).astype(np.float32)
+        z2 = np.where(np.abs(z2) > peak, np.copysign(peak, z2), z2).astype(np.float32)
+        r = float(s.astype(np.float32).min()) if s.shape[0] else 1.0
+    return z2, p, float(g), float(I), int(n_g), r
+
+
+def limited_body(chunks_samples, durations_per_chunk: Sequence[Sequence[int]], word: int, join, limit, g=None) -> bytes:
+    """The body of ONE limited request in the format word `word`, as bytes: join_stream (join = None: the chunks appended),
+    resample_stream, limit_stream, then the form."""
+    z = resample_stream(join_stream(chunks_samples, durations_per_chunk, join), word)
+    return stream_body(limit_stream(z, limit, word, g)[0], word)
+
+
 def stream_body(y, word: int) -> bytes:
     """The form of a format word applied to a request's stream `y`, which is at the word's rate already, as bytes."""
     y = np.ascontiguousarray(y, dtype=np.float32).reshape(-1)
@@ -548,7 +653,8 @@ def word_spans(spans, words: Sequence[Sequence[int]]):
 
 
 def tts_request(model, styles: Dict[str, np.ndarray], style_name: str, chunk_tokens: Sequence[Sequence[int]],
-                speed: float = 1.0, initial_silence: int = 0, seed: int = 0, fmt: int = 0, join=None, level=None, loudness=None):
+                speed: float = 1.0, initial_silence: int = 0, seed: int = 0, fmt: int = 0, join=None, level=None, loudness=None,
+                limit=None):
     """`tts_chunks` through `model.infer_requests`: the chunks of one text as ONE request of one batched forward, its body
     (header of the form, then the chunks' samples with nothing between them) packed on the GPU.  `fmt` is a format word of
     hip_koko (a PACK_* form, optionally | PACK_RATE_*): 0..2 and 8 / 9 give the samples as an array, 3 (`wav_f32_body`) and 4
@@ -556,7 +662,9 @@ def tts_request(model, styles: Dict[str, np.ndarray], style_name: str, chunk_tok
     (`model.infer_requests_joined`; trim the pads' silence, pause between sentences, fade the cut edges).  `level` = (mode, gain,
     peak): the level set on the GPU (`model.infer_requests_levelled`; a volume, a peak to normalise to, or a ceiling).
     `loudness` = (mode, target_lufs, peak): the BS.1770 loudness set on the GPU (`model.infer_requests_loudness`).  Either mode
-    may carry PEAK_TRUE: `peak` then bounds the true peak of the body, four times oversampled, not its largest sample.  An
+    may carry PEAK_TRUE: `peak` then bounds the true peak of the body, four times oversampled, not its largest sample.
+    `limit` = (mode, gain, target_lufs, peak): the body driven by a gain or to a loudness and peak-limited on the GPU
+    (`model.infer_requests_limited`): only the neighbourhood of the samples that would pass `peak` is turned down.  An
     empty chunk list and an empty chunk are errors (a request has at least one chunk)."""
     toks, rows = [], []
     for ch in chunk_tokens:
@@ -567,6 +675,11 @@ def tts_request(model, styles: Dict[str, np.ndarray], style_name: str, chunk_tok
         toks.append([0] + t + [0])
     if not toks:
         raise ValueError("tts_request: a request has at least one chunk")
+    if limit is not None:
+        if level is not None or loudness is not None:
+            raise ValueError("tts_request: a request has a level, a loudness or a limit, not two of them")
+        return model.infer_requests_limited(toks, [len(toks)], limit, joins=join, styles=np.asarray(rows, dtype=np.float32),
+                                            speeds=[float(speed)], seed=seed, fmt=fmt)[0][0]
     if loudness is not None:
         if level is not None:
             raise ValueError("tts_request: a request has a level or a loudness, not both")

@@ -16,6 +16,10 @@ the command line; an optional second argument is the batch (1 = one utterance). 
                          pack_requests_levelled_kernel (no request_gain_kernel: every slot is the loudness gain kernel's);
     'l' or 'd' and 't'   ('0x300lt', '0lt', '0x300dt') the same call with KX_PEAK_TRUE in every spec: request_truepeak_kernel behind the
                          peak pass (the meter) and before the gain kernel; without the 't' no such kernel may show in the stats;
+    a word and 'x' / 'y' ('0x300x', '0y', '0x300xt') kx_infer_requests_limited, every row a request of its own: 'x' driven by a gain
+                         of 64 and 'y' to -6 LUFS, both into a peak of 2^-6, so the drive cap holds g p at 4 peak and every stretch
+                         within 12 dB of a request's peak is limited: request_limit_kernel and request_limit_report_kernel behind
+                         the gain kernels, and pack_requests_limited_kernel; with 't' the limiter follows the true-peak envelope;
     a word and 'g'       ('2g') the same grouping without joins (kx_infer_requests_marks): the plain kernels on the same batch.
 Meant to run under the profiler, one mode per run (kernel trace only, no counters in the same run):
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o t -- python tools/pack_profile.py p2
@@ -28,7 +32,7 @@ import torch  # noqa
 from kokorox_amd import hip_koko as hk, weights as W
 from oracle import kokoro_ref as R
 which = sys.argv[1]
-flag = hk.PEAK_TRUE if which.endswith("t") and which[-2:-1] in ("l", "d") else 0
+flag = hk.PEAK_TRUE if which.endswith("t") and which[-2:-1] in ("l", "d", "x", "y") else 0
 which = which[:-1] if flag else which
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 m = hk.HipKoko.new(W.ensure_synthetic_blob())
@@ -62,6 +66,13 @@ for it in range(3):
         assert ld.shape == (B, 4) and (ld[:, 3] >= 1).all() and np.isfinite(ld[:, 2]).all()
         if it == 2:
             print("loudness of the first request: p %.6g g %.6g I %.6f LUFS n_g %d" % tuple(ld[0]))
+    elif which[-1] in "xy":
+        word = int(which[:-1], 0)
+        spec = (hk.LIMIT_GAIN | flag, 64.0, 0.0, 2.0 ** -6) if which[-1] == "x" else (hk.LIMIT_LOUDNESS | flag, 1.0, -6.0, 2.0 ** -6)
+        out, lm = m.infer_requests_limited(toks, [1] * B, spec, styles=rows, fmt=word)
+        assert lm.shape == (B, 5) and (lm[:, 4] < 1.0).all() and (lm[:, 4] > 0.24).all()
+        if it == 2:
+            print("limits of the first request: p %.6g g %.6g I %.6f LUFS n_g %d r %.6g" % tuple(lm[0]))
     elif which.endswith("m"):
         word = int(which[:-1], 0)
         out, marks = m.infer_requests_marks(toks, [1] * B, styles=rows, fmt=word)
