@@ -309,9 +309,36 @@ int kx_set_voice_table(kx_model* m, const float* table, int n_voices);
  * Forms 5, 6 and 7 do not exist and are refused ("infer: unknown output format"). */
 #define KX_PACK_MULAW 8
 #define KX_PACK_ALAW 9
+/* FLAC (kx_infer_requests and its siblings, kx_dispatcher_submit_request* only): a lossless body of form 4's 16-bit samples v
+ * (NaN -> 0, +-inf -> +-32767) of the request's stream at its output rate, N of them -- after the join, the resampler and the levels
+ * or the limiter; out_samples[r] and the marks are what they are for any other form.  RFC 9639 gives the meaning of every field;
+ * the choices it leaves open are fixed here, so the body is a function of v and the rate, and the numpy definition
+ * (kokorox_amd/voices.py: flac_body) and the GPU agree on every byte.  All fields MSB first.  F = ceil(N / 4096).
+ *   Body: "fLaC"; a STREAMINFO block, not last: min = max block size 4096, min and max frame size the true ones over the F frames (0
+ *     and 0 when F = 0), the output rate, 1 channel, 16 bits, N samples, the MD5 all zeros ("not computed"); a PADDING block, last,
+ *     of p = (2 - the bytes of all frames) mod 4 zero bytes; frames f = 0 .. F - 1 of n = min(4096, N - 4096 f) samples.  The body is a
+ *     multiple of 4 bytes, as every region of every form.
+ *   Frame header: FF F8 (fixed block size); block-size nibble 1100 for n = 4096, else 0111 and n - 1 as 16 bits behind the frame
+ *     number; rate nibble 0100 / 0101 / 0111 / 1010 for 8000 / 16 000 / 24 000 / 48 000 Hz; 08 (one channel, 16 bits); f in the
+ *     format's UTF-8-like coding; CRC-8 (polynomial 0x07, from 0).  One subframe, zero bits to the byte boundary, CRC-16 (polynomial
+ *     0x8005, from 0, not reflected) over the whole frame.  No wasted bits.
+ *   Subframe: CONSTANT when all n samples are equal.  Else FIXED: for o = 0 .. min(4, n - 1) the residuals e_o[i], i >= o, in int32
+ *     by the binomial forms (e_1 = v[i] - v[i-1], .., e_4 = v[i] - 4 v[i-1] + 6 v[i-2] - 4 v[i-3] + v[i-4]), folded as
+ *     u = (e << 1) ^ (e >> 31); partition order P = 0 .. 6 when n = 4096, else 0; coding method 00 (4-bit parameters), never the
+ *     escape; a partition's Rice parameter is the k in 0 .. 14 with the fewest bits, sum (u >> k) + (k + 1) count, the smaller k on a
+ *     tie; bits(o, P) = 16 o + 6 + the sum over the partitions of 4 + their bits, the first partition holding (n >> P) - o
+ *     residuals; the (o, P) with the fewest bits is taken, the smaller o on a tie, then the smaller P.  VERBATIM when that reaches or
+ *     exceeds 16 n bits.
+ *   A frame is at most 16 + 2 n bytes and a body at most 42 + 7 + the sum of those, rounded up to 4: the bound.  This is the one form
+ *     whose size follows from the samples: out_bytes[r] is the body's true size, and the R bodies lie back to back by those sizes
+ *     like all others (the copy from the device carries the bound; the host closes the gaps).
+ * Not offered: LPC subframes, stereo, other block sizes, an MD5 signature, seek tables.  Forms 10 and 11 do not exist and are
+ * refused like 5, 6 and 7. */
+#define KX_PACK_FLAC 12
+#define KX_FLAC_BLOCK 4096
 
 /* The `format` / `formats[]` value of kx_infer_requests and kx_dispatcher_submit_request is a WORD: bits 0..7 = the form above
- * (0..4, 8, 9), bits 8..11 = the output sample rate, every other bit zero (else "infer: unknown output format").  Rate code 0 =
+ * (0..4, 8, 9, 12), bits 8..11 = the output sample rate, every other bit zero (else "infer: unknown output format").  Rate code 0 =
  * 24 000 Hz, the model's own rate: the bytes of the plain forms, unchanged.  Codes 4..15 are refused with KX_ERR_INVALID,
  * "infer: unknown output sample rate".  Every form combines with every rate.  (kx_infer, kx_infer_packed, kx_infer_voices,
  * kx_dispatcher_submit and kx_dispatcher_submit_ex keep taking the forms 0..2 and nothing else.)

@@ -162,6 +162,21 @@ int kx_test_output_plan_limited(int device_id, const float* audio, int B, int64_
                                 double* out_hops, int64_t hops_cap, int64_t* out_n_hops, const kx_limit* limits, double* out_limits,
                                 char* err, size_t err_len);
 
+/* The same with FLAC requests (form 12; include/kokorox_hip.h, "FLAC"): the limited hook, and out_lengths [R] = the lengths block as
+ * the device wrote it, the true size of every region (may be NULL).  `out` needs room for every FLAC region at its bound,
+ * 52 + 16 ceil(N / 4096) + 2 N bytes; on return the R bodies lie back to back by their true sizes, as kx_infer_requests hands them
+ * out, out_bytes holds those sizes, and the bytes of `out` behind the last body are zero.  The encoder's frame slots, its two
+ * per-frame tables and every byte of a region behind its body are poisoned before the launch and have a guard behind them; the hook
+ * fails with KX_ERR_STATE where a guard or the slack of a region is not as it was filled.  Every pointer of the limited hook may be
+ * NULL as there (limits = NULL: no request is limited); a batch without form 12 is kx_test_output_plan_limited, which calls this. */
+int kx_test_output_plan_flac(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames, const int32_t* dur,
+                             const int32_t* lens, const int32_t* chunks_per_request, int R, const int32_t* formats,
+                             const kx_join* joins, const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes,
+                             int64_t* out_samples, int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks,
+                             const kx_level* levels, double* out_levels, const kx_loudness* loudness, double* out_loudness,
+                             double* out_hops, int64_t hops_cap, int64_t* out_n_hops, const kx_limit* limits, double* out_limits,
+                             int64_t* out_lengths, char* err, size_t err_len);
+
 /* The token-axis kernels of Model::front_half, alone.  Common to these hooks: rows padded to a multiple of 32 floats as in the
  * model, NaN in every input column a kernel must not read, -12345.5 (0xA5 bytes in integer buffers) in every output location it
  * must not write; what the caller cannot see (row padding, guard regions behind a buffer) the hook checks itself after the launch

@@ -37,6 +37,8 @@ pub const KX_PACK_WAV16_BASE64: c_int = 4;
 /// Raw G.711 mu-law / A-law of the 16-bit sample, one byte per sample, no header; requests only.
 pub const KX_PACK_MULAW: c_int = 8;
 pub const KX_PACK_ALAW: c_int = 9;
+/// FLAC of the 16-bit samples, lossless; the body's size follows from the samples (`kokorox_hip.h`, "FLAC").
+pub const KX_PACK_FLAC: c_int = 12;
 /// The output sample rate, or'ed into a request's form (bits 8..11 of the format word; 0 = the model's 24 000 Hz).
 pub const KX_PACK_RATE_24000: c_int = 0x000;
 pub const KX_PACK_RATE_8000: c_int = 0x100;

@@ -13,7 +13,7 @@ namespace kx {
 // ---- the format word and the resampler's tables ------------------------------------------------------------------------------
 void check_format_word(int word) {
     const int form = format_form(word);
-    KX_REQUIRE(word >= 0 && (word & ~0xFFF) == 0 && (form <= 4 || form == 8 || form == 9), "infer: unknown output format");
+    KX_REQUIRE(word >= 0 && (word & ~0xFFF) == 0 && (form <= 4 || form == 8 || form == 9 || form == FORM_FLAC), "infer: unknown output format");
     KX_REQUIRE(format_rate(word) <= 3, "infer: unknown output sample rate");
 }
 
@@ -244,15 +244,21 @@ OutputBounds output_bounds(const RequestLayout& lay, int B, size_t n_samples, co
     // group's padding -- what a one-frame request needs beyond its samples.  Resampled floats per sample: every request at the
     // batch's highest ratio, 2 at 48 000 Hz, below 1 otherwise
     size_t per_sample = 0, y_per_sample = 0;
+    bool flac = false;
     for (int i = 0; i < lay.n_format; ++i) {
         const int f = format_form(lay.formats[i]), c = format_rate(lay.formats[i]);
-        size_t w = f == 1 ? 8 : (f == 2 ? 2 : (f == 4 ? 3 : (f >= 8 ? 1 : 4)));
+        flac = flac || f == FORM_FLAC;
+        size_t w = f == 1 ? 8 : (f == 2 || f == FORM_FLAC ? 2 : (f == 4 ? 3 : (f >= 8 ? 1 : 4)));
         if (c == 3) w *= 2;
         const size_t y = c == 0 ? 0 : (c == 3 ? 2 : 1);
         per_sample = w > per_sample ? w : per_sample;
         y_per_sample = y > y_per_sample ? y : y_per_sample;
     }
-    OutputBounds bound{n_samples * per_sample + (size_t)lay.R * 64 + 16, n_samples * y_per_sample, 0, 0, 0, 0, 0};
+    OutputBounds bound{n_samples * per_sample + (size_t)lay.R * 64 + 16, n_samples * y_per_sample, 0, 0, 0, 0, 0, 0};
+    if (flac) {  // (a FLAC body beyond its samples: 52 <= 64 bytes a request, counted above, and 16 a frame; the lengths block)
+        bound.flac_slots = n_samples * (y_per_sample > 1 ? y_per_sample : 1) / (size_t)FLAC_BLOCK + (size_t)lay.R;
+        bound.packed_bytes += 16 * bound.flac_slots + 8 + 8 * (size_t)lay.R;
+    }
     // (a layout whose limit specs are all LIMIT_NONE has no limiter: its bounds are those of the layout without them)
     bool limited = false;
     for (int i = 0; lay.limits && i < lay.n_limit; ++i) limited = limited || lay.limits[i].mode != LIMIT_NONE;
@@ -297,8 +303,29 @@ long pack_request_bytes(int form, long n_samples) {
         case 4:
             KX_REQUIRE(36 + 2 * n <= 0xFFFFFFFFL, "pack: a 16-bit WAV file cannot hold that many samples (size field of 32 bits)");
             return 4 * ((44 + 2 * n + 2) / 3);
+        case FORM_FLAC: return flac_bound(n);  // (the region; the body's true size is the device's to say)
         default: return n;  // 8, 9: one G.711 byte per sample
     }
+}
+
+long flac_bound(long n_samples) { return (49 + 16 * flac_frames(n_samples) + 2 * n_samples + 3) & ~3L; }
+
+long close_flac_gaps(char* host, const OutputPlan& plan, const int64_t* lengths, int64_t* out_bytes) {
+    KX_REQUIRE(out_bytes && (!plan.has_flac() || (host && lengths)), "flac: bad argument");
+    long at = 0;
+    for (size_t r = 0; r < plan.req.size(); ++r) {
+        const PackReq& q = plan.req[r];
+        long len = q.out_bytes;
+        if (plan.has_flac()) {
+            len = lengths[r];
+            const bool flac = plan.flac[r].frames >= 0;
+            KX_REQUIRE(len >= 0 && (len & 3) == 0 && len <= q.out_bytes && (flac || len == q.out_bytes), "flac: bad length");
+            if (at != q.out_off && len > 0) std::memmove(host + at, host + q.out_off, (size_t)len);
+        }
+        out_bytes[r] = len;
+        at += len;
+    }
+    return at;
 }
 
 void build_output_plan(const int* frames, const int* lens, const int* edges, int B, const RequestLayout& lay, OutputPlan& plan) {
@@ -371,7 +398,7 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
         q.out_off = plan.total_bytes;
         q.out_bytes = pack_request_bytes(word, q.src_samples);
         plan.total_bytes += q.out_bytes;
-        const long units = ((q.out_off & 15) + q.out_bytes + 15) / 16;
+        const long units = q.form == FORM_FLAC ? 0 : ((q.out_off & 15) + q.out_bytes + 15) / 16;  // (the packer writes no FLAC region)
         plan.max_units = units > plan.max_units ? units : plan.max_units;
         plan.first[(size_t)r] = plan.n_marks;
         if (lens) {
@@ -473,6 +500,28 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
         }
         plan.loud_off = plan.levels_off + 16L * R;
         if (plan.limited) plan.limits_off = plan.loud_off + 16L * R;
+    }
+    // FLAC: the packer's table without those requests, the encoder's table, the slots and the lengths block behind everything else
+    plan.pack_req.clear();
+    plan.flac.clear();
+    plan.flac_slots = plan.flac_max_frames = plan.flac_max_bytes = plan.flac_off = 0;
+    bool flac = false;
+    for (int r = 0; r < R; ++r) flac = flac || plan.req[(size_t)r].form == FORM_FLAC;
+    if (flac) {
+        plan.pack_req = plan.req;
+        plan.flac.resize((size_t)R);
+        for (int r = 0; r < R; ++r) {
+            const PackReq& q = plan.req[(size_t)r];
+            FlacRow& f = plan.flac[(size_t)r];
+            f = FlacRow{q.out_off, q.out_bytes, q.n_samples, -1, plan.flac_slots, q.rate};
+            if (q.form != FORM_FLAC) continue;
+            plan.pack_req[(size_t)r].out_off = plan.pack_req[(size_t)r].out_bytes = 0;
+            f.frames = flac_frames(q.n_samples);
+            plan.flac_slots += f.frames;
+            plan.flac_max_frames = f.frames > plan.flac_max_frames ? f.frames : plan.flac_max_frames;
+            plan.flac_max_bytes = q.out_bytes > plan.flac_max_bytes ? q.out_bytes : plan.flac_max_bytes;
+        }
+        plan.flac_off = (plan.blocks_end() + 7) & ~7L;
     }
 }
 

@@ -309,6 +309,13 @@ struct OutputTables {
     LimitRow* limit;
     uint32_t* lpart;
     float* lim;
+    // a plan with FLAC (OutputPlan::has_flac): frow [R], finfo [R], and scratch sized by plan.flac_slots: fslot = the encoded frames,
+    // FLAC_SLOT bytes each (16-byte aligned), flen = their sizes and foff = their offsets behind the request's first frame
+    FlacRow* frow;
+    FlacInfo* finfo;
+    uint32_t* fslot;
+    int* flen;
+    long* foff;
 };
 // Everything between "the plan is built" and "copy to the host", for the model and for the test hook: the resampler when
 // plan.y_floats > 0 (d_y: that many floats, null when 0), the packer into d_packed (16-byte aligned, plan.total_bytes long), and
@@ -317,6 +324,8 @@ struct OutputTables {
 // pass and the gain kernel between resampler and packer, {p, g} of every request at d_packed + plan.levels_off (8-aligned; d_packed
 // is then plan.end_bytes() long), and the levelled packer when plan.levelled.  A plan with loudness: request_loudness_kernel behind
 // the peak pass and request_loudness_gain_kernel behind the gain kernel, {I, n_g} of every metered request at d_packed + plan.loud_off.
+// A plan with a FLAC request (OutputPlan::has_flac): the three FLAC kernels behind the limiter, the body at the front of its region
+// and the true size of every region at d_packed + plan.flac_off; host_request.h: close_flac_gaps moves the regions together.
 void launch_output_plan(const float* audio, long audio_ld, const int* dur, const int* lens, const OutputPlan& plan,
                         const OutputTables& t, float* d_y, void* d_packed, hipStream_t s);
 // its two halves: the bodies, and the marks (n_marks > 0) into a block of their own, 8-byte aligned

@@ -163,6 +163,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     size_t tpeak_cap = 0;  // dwords of tables.tpeak
     size_t lpart_cap = 0;  // dwords of tables.lpart
     size_t lim_cap = 0;    // floats of tables.lim
+    size_t slot_cap = 0;   // frames of tables.fslot, tables.flen and tables.foff
     float* d_y = nullptr;  // the resampled streams of the requests with a rate code, back to back
     int *d_vid, *d_rows, *d_kinds;
     float* d_w;
@@ -204,6 +205,14 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             lim_cap = bound.lim_floats;
         }
         if (marks) tables.mark = static_cast<MarkRow*>(A.alloc((size_t)B * sizeof(MarkRow)));
+        if (bound.flac_slots > 0) {  // (some word has form 12: the encoder's tables and its frame slots, sized before the forward as well)
+            tables.frow = static_cast<FlacRow*>(A.alloc((size_t)R * sizeof(FlacRow)));
+            tables.finfo = static_cast<FlacInfo*>(A.alloc((size_t)R * sizeof(FlacInfo)));
+            tables.fslot = static_cast<uint32_t*>(A.alloc(bound.flac_slots * (size_t)FLAC_SLOT));
+            tables.flen = A.i(bound.flac_slots);
+            tables.foff = static_cast<long*>(A.alloc(bound.flac_slots * sizeof(long)));
+            slot_cap = bound.flac_slots;
+        }
         d_packed = A.alloc(bound.packed_bytes);  // compact output: the requests back to back, then the marks
         return A.f(audio_floats);
     };
@@ -263,9 +272,10 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         KX_REQUIRE((size_t)plan.hop_doubles() <= hop_cap, "loudness: the hop table is too small");
         KX_REQUIRE((size_t)plan.truepeak_dwords() <= tpeak_cap, "levels: the true-peak table is too small");
         KX_REQUIRE((size_t)plan.limit_dwords() <= lpart_cap && (size_t)plan.lim_floats <= lim_cap, "limiter: the limit buffer is too small");
+        KX_REQUIRE((size_t)plan.flac_slots <= slot_cap, "flac: the frame table is too small");
         launch_output_plan(d_audio, ld, call_.d_dur, call_.dT, plan, tables, d_y, d_packed, stream_);
         const int64_t marks_off = plan.marks_off, n_marks = plan.n_marks;
-        const int64_t total = n_marks > 0 || plan.measured ? plan.end_bytes() : plan.total_bytes;
+        const int64_t total = n_marks > 0 || plan.measured || plan.has_flac() ? plan.end_bytes() : plan.total_bytes;
         char* host = static_cast<char*>(host_out_alloc((size_t)(total > 0 ? total : 1)));
         hipError_t e = hipMemcpyAsync(host, d_packed, (size_t)total, hipMemcpyDeviceToHost, stream_);
         if (e == hipSuccess) e = hipStreamSynchronize(stream_);
@@ -280,6 +290,16 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         } catch (...) {
             host_out_free(host);
             throw;
+        }
+        // (FLAC bodies are as long as their samples make them: the device's lengths, then the regions moved together; the blocks
+        // behind the bodies stay where the plan put them)
+        if (plan.has_flac()) {
+            try {
+                close_flac_gaps(host, plan, reinterpret_cast<const int64_t*>(host + plan.flac_off), out_bytes);
+            } catch (...) {
+                host_out_free(host);
+                throw;
+            }
         }
         *out = host;
         if (marks) *out_marks = n_marks > 0 ? reinterpret_cast<int64_t*>(host + marks_off) : nullptr;

@@ -44,6 +44,17 @@ int kx_test_output_plan_limited(int device_id, const float* audio, int B, int64_
                                 int64_t* out_n_marks, const kx_level* levels, double* out_levels, const kx_loudness* loudness,
                                 double* out_loudness, double* out_hops, int64_t hops_cap, int64_t* out_n_hops, const kx_limit* limits,
                                 double* out_limits, char* err, size_t err_len) {
+    return kx_test_output_plan_flac(device_id, audio, B, audio_ld, frames_in, dur, lens, chunks_per_request, R, formats, joins, want, out,
+                                    out_cap, out_bytes, out_samples, out_marks, marks_cap, out_n_marks, levels, out_levels, loudness,
+                                    out_loudness, out_hops, hops_cap, out_n_hops, limits, out_limits, nullptr, err, err_len);
+}
+
+int kx_test_output_plan_flac(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames_in, const int32_t* dur,
+                             const int32_t* lens, const int32_t* chunks_per_request, int R, const int32_t* formats, const kx_join* joins,
+                             const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes, int64_t* out_samples,
+                             int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks, const kx_level* levels, double* out_levels,
+                             const kx_loudness* loudness, double* out_loudness, double* out_hops, int64_t hops_cap, int64_t* out_n_hops,
+                             const kx_limit* limits, double* out_limits, int64_t* out_lengths, char* err, size_t err_len) {
     return guarded_free(err, err_len, [&] {
         check_device(device_id);
         KX_REQUIRE(formats && out_bytes && out_samples && out_n_marks && B > 0 && R > 0 && (frames_in ? !dur : dur && lens) &&
@@ -117,11 +128,20 @@ int kx_test_output_plan_limited(int device_id, const float* audio, int B, int64_
         const size_t n_lpart = (size_t)plan.limit_dwords(), n_lim = (size_t)plan.lim_floats;
         uint32_t* d_lpart = plan.limited ? guarded_bytes<uint32_t>(dm, n_lpart, 0x00) : nullptr;
         float* d_lim = plan.limited ? guarded_bytes<float>(dm, n_lim, 0xFF) : nullptr;
+        // the encoder's scratch, all sized by the plan's frames: the slots poisoned with ones, the sizes with a large negative value and
+        // the offsets with a large one (an entry the launch did not write must not be read), a guard behind each
+        const bool flac = plan.has_flac() && audio;
+        const size_t n_slot = (size_t)plan.flac_slots;
+        uint32_t* d_fslot = flac ? guarded_bytes<uint32_t>(dm, n_slot * (size_t)(kx::FLAC_SLOT / 4), 0xFF) : nullptr;
+        int* d_flen = flac ? guarded_bytes<int>(dm, n_slot, 0x80) : nullptr;
+        long* d_foff = flac ? guarded_bytes<long>(dm, n_slot, 0x7F) : nullptr;
         const kx::OutputTables tables{dm.get<kx::PackReq>((size_t)R), dm.get<long>((size_t)B + 1), dm.get<kx::JoinRow>((size_t)B),
                                       dm.get<kx::MarkRow>((size_t)B), plan.measured ? dm.get<kx::LevelSpec>((size_t)R) : nullptr, d_peak,
                                       metered ? dm.get<kx::LoudSpec>((size_t)R) : nullptr, d_hops,
                                       metered ? dm.get<double>((size_t)4 * kx::LOUD_POWERS * 16) : nullptr, d_tpeak,
-                                      plan.limited ? dm.get<kx::LimitRow>((size_t)R) : nullptr, d_lpart, d_lim};
+                                      plan.limited ? dm.get<kx::LimitRow>((size_t)R) : nullptr, d_lpart, d_lim,
+                                      flac ? dm.get<kx::FlacRow>((size_t)R) : nullptr, flac ? dm.get<kx::FlacInfo>((size_t)R) : nullptr,
+                                      d_fslot, d_flen, d_foff};
         const int* d_dur = dur ? dm.up(dur, (size_t)B * 512) : nullptr;
         const int* d_len = dur ? dm.up(lens, (size_t)B) : nullptr;
         // guards: 64 bytes after the last region, after the resampled streams, after the last mark and after the levels, which
@@ -136,7 +156,10 @@ int kx_test_output_plan_limited(int device_id, const float* audio, int B, int64_
         if (metered) plan.loud_off = plan.levels_off + 16L * R;
         if (plan.limited) plan.limits_off = plan.loud_off + 16L * R;
         const long mk_off = audio ? plan.marks_off : 0, lv_off = plan.measured ? plan.levels_off : mk_off + n_mk;
-        const long d_out_bytes = plan.measured ? lv_off + n_lv + GUARD_BYTES : mk_off + n_mk + GUARD_BYTES;
+        // (the lengths block of a plan with FLAC: behind the guard of the last block, a guard of its own behind it)
+        const long blocks_end = plan.measured ? lv_off + n_lv : mk_off + n_mk;
+        if (flac) plan.flac_off = (blocks_end + GUARD_BYTES + 7) & ~7L;
+        const long d_out_bytes = flac ? plan.flac_off + 8L * R + GUARD_BYTES : blocks_end + GUARD_BYTES;
         char* d_out = dm.get<char>((size_t)d_out_bytes);
         KX_HIP(hipMemset(d_out, GUARD_BYTE, (size_t)d_out_bytes));
         float* d_y = audio && plan.y_floats > 0 ? dm.get<float>((size_t)plan.y_floats + GUARD_BYTES / 4) : nullptr;
@@ -151,6 +174,25 @@ int kx_test_output_plan_limited(int device_id, const float* audio, int B, int64_
         if (audio) {
             KX_HIP(hipMemcpy(out, d_out, (size_t)body, hipMemcpyDeviceToHost));
             guard_untouched(d_out + body, "test_output_plan: the kernel wrote past the last region");
+            if (flac) {  // the slack of every region is as it was filled, then the regions move together as in Model::infer_host_once
+                std::vector<int64_t> lengths((size_t)R);
+                KX_HIP(hipMemcpy(lengths.data(), d_out + plan.flac_off, (size_t)R * 8, hipMemcpyDeviceToHost));
+                if (out_lengths) std::memcpy(out_lengths, lengths.data(), (size_t)R * 8);
+                guard_untouched(d_out + plan.flac_off - GUARD_BYTES, "test_output_plan: a kernel wrote in front of the lengths");
+                guard_untouched(d_out + plan.flac_off + 8L * R, "test_output_plan: the kernel wrote past the last length");
+                guard_untouched(d_fslot + n_slot * (size_t)(kx::FLAC_SLOT / 4), "test_output_plan: the encoder wrote past its slots");
+                guard_untouched(d_flen + n_slot, "test_output_plan: the encoder wrote past its sizes");
+                guard_untouched(d_foff + n_slot, "test_output_plan: the layout wrote past its offsets");
+                const unsigned char* body_bytes = static_cast<const unsigned char*>(out);
+                for (int r = 0; r < R; ++r) {
+                    const kx::PackReq& q = plan.req[(size_t)r];
+                    KX_REQUIRE(lengths[(size_t)r] >= 0 && lengths[(size_t)r] <= q.out_bytes, "flac: bad length");
+                    for (long i = lengths[(size_t)r]; i < q.out_bytes; ++i)
+                        if (body_bytes[q.out_off + i] != GUARD_BYTE) throw Error(KX_ERR_STATE, "test_output_plan: a kernel wrote into a region's slack");
+                }
+                const long closed = kx::close_flac_gaps(static_cast<char*>(out), plan, lengths.data(), out_bytes);
+                std::memset(static_cast<char*>(out) + closed, 0, (size_t)(body - closed));  // (what the moves left behind the last body)
+            }
             if (d_y) guard_untouched(d_y + plan.y_floats, "test_output_plan: the resampler wrote past the last stream");
         }
         if (plan.measured) {

@@ -23,6 +23,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libkokorox_hip.so")
 PACK_F32_MONO, PACK_F32_STEREO, PACK_PCM16_MONO = 0, 1, 2
 PACK_WAV_F32, PACK_WAV16_BASE64 = 3, 4  # the servers' bodies (infer_requests / submit_request only): float WAV, base64 of a 16-bit WAV
 PACK_MULAW, PACK_ALAW = 8, 9  # raw G.711, one byte per sample (infer_requests / submit_request only)
+PACK_FLAC = 12  # a lossless FLAC body of the 16-bit samples (infer_requests / submit_request only); its size follows from the samples
 # the output sample rate, or'ed into the form of infer_requests / submit_request (the format word of include/kokorox_hip.h)
 PACK_RATE_24000, PACK_RATE_8000, PACK_RATE_16000, PACK_RATE_48000 = 0x000, 0x100, 0x200, 0x300
 RATE_HZ = {0: 24000, 1: 8000, 2: 16000, 3: 48000}  # by rate code (bits 8..11 of the word)
@@ -204,6 +205,8 @@ def _test_signatures():
                                                vp, vp, vp, i64, vp, cp, sz]),
         "kx_test_output_plan_limited": (i32, [i32, vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp,
                                               vp, vp, vp, i64, vp, vp, vp, cp, sz]),
+        "kx_test_output_plan_flac": (i32, [i32, vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp,
+                                           vp, vp, vp, i64, vp, vp, vp, vp, cp, sz]),
         "kx_test_lstm_ragged": (i32, [i32, vp, vp, i32, i32, i32] + [vp] * 8 + [i32, i32, u32, vp, cp, sz]),
         "kx_test_alignment": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, cp, sz]),
         "kx_test_embed": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, cp, sz]),
@@ -365,9 +368,9 @@ def resample_filter(word: int):
 
 def _decode_packed(raw: bytes, fmt: int):
     """A request's region as Python hands it out: samples as an array for forms 0..2 and 8 / 9 (uint8), the body as bytes for
-    forms 3 and 4; at the output rate of the word."""
+    forms 3, 4 and 12 (FLAC); at the output rate of the word."""
     fmt = int(fmt) & 0xFF
-    if fmt in (PACK_WAV_F32, PACK_WAV16_BASE64):
+    if fmt in (PACK_WAV_F32, PACK_WAV16_BASE64, PACK_FLAC):
         return raw
     if fmt in (PACK_MULAW, PACK_ALAW):
         return np.frombuffer(raw, dtype=np.uint8).copy()
@@ -550,8 +553,8 @@ class HipKoko:
         request r owns chunks_per_request[r] consecutive ones.  The voice is per chunk: `styles` [B, 256], or `voice_ids` /
         `weights` [B, max_mix] as infer_voices.  `fmt` = one format word (a PACK_* form, optionally | PACK_RATE_*) for all, or one
         per request.  Returns one entry per request: its chunks' samples back to back, at the word's rate, as an array for forms
-        0..2 (float32, [n, 2] float32, int16) and the G.711 forms (uint8), the body as `bytes` for PACK_WAV_F32 and
-        PACK_WAV16_BASE64.  with_samples: also the library's own sample count of every request (out_samples, at the output
+        0..2 (float32, [n, 2] float32, int16) and the G.711 forms (uint8), the body as `bytes` for PACK_WAV_F32,
+        PACK_WAV16_BASE64 and PACK_FLAC (whose size follows from the samples).  with_samples: also the library's own sample count of every request (out_samples, at the output
         rate), as a second list."""
         res, _, nsamp = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, False)
         return (res, nsamp) if with_samples else res
@@ -901,7 +904,7 @@ class Dispatcher:
         """A request of 1 .. max_batch chunks (kx_dispatcher_submit_request): `chunks` = the 0-wrapped id lists; `styles` = one
         256-float row per chunk, OR `voices` as in submit_ex (one voice spec for the request); `fmt` = a format word (a PACK_*
         form, optionally | PACK_RATE_*).  Returns what HipKoko.infer_requests returns for one request: an array (forms 0..2, 8, 9)
-        or the body as bytes (3, 4).  marks=True (kx_dispatcher_submit_request_marks): returns (body, marks), marks = the
+        or the body as bytes (3, 4, 12 = FLAC).  marks=True (kx_dispatcher_submit_request_marks): returns (body, marks), marks = the
         request's token marks as one int64 array (HipKoko.infer_requests_marks).  join = (flags, keep_ms, pause_ms, fade_ms)
         (kx_dispatcher_submit_request_joined): the request's seams shaped as HipKoko.infer_requests_joined shapes them.
         level = (mode, gain, peak) (kx_dispatcher_submit_request_levelled): the request's level set as
@@ -1418,7 +1421,8 @@ def weight_images(sources, up_stride=0, device=0):
     return out
 
 
-def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, want, pauses, device, levels=None, loudness=None, limits=None):
+def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, want, pauses, device, levels=None, loudness=None, limits=None,
+                 flac=False):
     """kx_test_output_plan, the one hook of the output stage: the model's planner and launcher on host arrays (None where the
     hook takes a null pointer; include/kokorox_hip_test.h).  Returns (bodies as bytes, out_samples, marks as int64 arrays).
     levels (an array of LEVEL_DTYPE, [R]): kx_test_output_plan_levelled, and a fourth entry, the levels as float64 [R, 2].
@@ -1426,7 +1430,9 @@ def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, w
     the pair (loudness as float64 [R, 4] = p, g, I, n_g; the hop energies e[k] of every request as one float64 array each).
     limits (an array of LIMIT_DTYPE, [R]; levels and loudness may then be None): kx_test_output_plan_limited, and the fourth entry
     is the triple (levels [R, 2] or None, loudness [R, 4] or None, limits as float64 [R, 5] = p, g, I, n_g, r, the rows of the
-    requests without a limiter left at -1)."""
+    requests without a limiter left at -1).
+    flac = True: kx_test_output_plan_flac whatever else is given, and the fourth entry is (the lengths block as int64 [R], levels
+    [R, 2] or None, loudness [R, 4] or None, limits [R, 5] or None); the bodies are cut by the true sizes."""
     lib = load_test_library()
     B = len(frames if dur is None else lens)
     fm = np.ascontiguousarray(formats, dtype=np.int32)
@@ -1453,7 +1459,17 @@ def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, w
     nb, ns, nm = np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int64)
     args = (device, _ptr(audio), B, ld, _ptr(fr), _ptr(dur), _ptr(ln), _ptr(cpr), R, _ptr(fm), _ptr(joins), _ptr(wt),
             _ptr(out) if audio is not None else None, cap, _ptr(nb), _ptr(ns), _ptr(mk), mcap, _ptr(nm))
-    if limits is not None:
+    if flac:
+        assert audio is not None
+        out_lv = np.zeros((R, 2), dtype=np.float64) if levels is not None else None
+        out_ld = np.full((R, 4), -1.0, dtype=np.float64) if loudness is not None else None
+        out_lm = np.full((R, 5), -1.0, dtype=np.float64) if limits is not None else None
+        hcap = (600 * n_frames + pauses) // 1200 + 1 if loudness is not None else 0
+        hops, n_hops = (np.zeros((R, hcap), dtype=np.float64), np.zeros(R, dtype=np.int64)) if loudness is not None else (None, None)
+        lengths = np.full(R, -1, dtype=np.int64)
+        _err_call(lib.kx_test_output_plan_flac, *args, _ptr(levels), _ptr(out_lv), _ptr(loudness), _ptr(out_ld), _ptr(hops), hcap,
+                  _ptr(n_hops), _ptr(limits), _ptr(out_lm), _ptr(lengths))
+    elif limits is not None:
         assert limits.dtype == LIMIT_DTYPE and limits.shape == (R,) and (levels is None or (levels.dtype == LEVEL_DTYPE and levels.shape == (R,)))
         assert loudness is None or (loudness.dtype == LOUDNESS_DTYPE and loudness.shape == (R,))
         out_lv = np.zeros((R, 2), dtype=np.float64) if levels is not None else None
@@ -1482,6 +1498,8 @@ def _output_plan(audio, frames, dur, lens, chunks_per_request, formats, joins, w
         res.append(raw[o: o + int(nb[r])] if audio is not None else b"")
         o += int(nb[r])
     marks = [m.copy() for m in np.split(mk[: int(nm.sum())], np.cumsum(nm)[:-1])]
+    if flac:
+        return res, [int(v) for v in ns], marks, (lengths, out_lv, out_ld, out_lm)
     if limits is not None:
         return res, [int(v) for v in ns], marks, (out_lv, out_ld, out_lm)
     if loudness is not None:
@@ -1565,3 +1583,20 @@ def limit_requests(audio, dur, lens, chunks_per_request, formats, limits, joins=
     res, ns, marks, (out_lv, out_ld, out_lm) = _output_plan(audio, frames, dur, lens, chunks_per_request, formats, j, want, pauses, device,
                                                             lv, ld, lm)
     return res, ns, marks, out_lm, out_lv, out_ld
+
+
+def flac_requests(audio, dur, lens, chunks_per_request, formats, joins=None, want=None, frames=None, levels=None, loudness=None,
+                  limits=None, device=0):
+    """Requests through kx_test_output_plan_flac: everything as limit_requests takes it, every spec list optional, and any mix of
+    forms, 12 (FLAC) among them.  Returns (bodies as bytes, cut by their true sizes, out_samples, marks, lengths = the lengths block
+    as int64 [R], levels [R, 2] or None, loudness [R, 4] or None, limits [R, 5] or None): voices.flac_body of the 16-bit samples of
+    the same request.  The hook itself checks the guards and the poisoned slack of every region."""
+    R = len(lens if dur is not None else frames) if chunks_per_request is None else len(chunks_per_request)
+    lm = None if limits is None else limit_specs(limits, R)
+    ld = None if loudness is None else loudness_specs(loudness, R)
+    lv = None if levels is None else level_specs(levels, R)
+    j = None if joins is None else join_specs(joins, R)
+    pauses = 0 if j is None else sum(24 * int(j["pause_ms"][r]) * (int(chunks_per_request[r]) - 1) for r in range(R))
+    res, ns, marks, (lengths, out_lv, out_ld, out_lm) = _output_plan(audio, frames, dur, lens, chunks_per_request, formats, j, want, pauses,
+                                                                     device, lv, ld, lm, flac=True)
+    return res, ns, marks, lengths, out_lv, out_ld, out_lm

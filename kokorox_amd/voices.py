@@ -199,6 +199,151 @@ def alaw_bytes(pcm) -> np.ndarray:
     return byte.astype(np.uint8)
 
 
+# ---- FLAC (form 12; include/kokorox_hip.h, "FLAC"): one mono 16-bit stream in fixed blocks of 4096, every choice fixed by rule ----
+FLAC_BLOCK = 4096
+_FLAC_RATE_NIBBLE = {8000: 0b0100, 16000: 0b0101, 24000: 0b0111, 48000: 0b1010}
+_FLAC_FIXED = ((1,), (1, -1), (1, -2, 1), (1, -3, 3, -1), (1, -4, 6, -4, 1))  # e_o = sum over j of c[j] v[i - j]
+
+
+def flac_crc8(data) -> int:
+    """CRC-8 of a frame header: polynomial 0x07, initial value 0, MSB first, no final XOR."""
+    c = 0
+    for b in bytes(data):
+        c ^= b
+        for _ in range(8):
+            c = ((c << 1) ^ 0x07) & 0xFF if c & 0x80 else (c << 1) & 0xFF
+    return c
+
+
+def _flac_crc16_table():
+    t = np.arange(256, dtype=np.uint32) << 8
+    for _ in range(8):
+        t = np.where(t & 0x8000, (t << 1) ^ 0x8005, t << 1) & 0xFFFF
+    return [int(v) for v in t]
+
+
+_FLAC_CRC16 = _flac_crc16_table()
+
+
+def flac_crc16(data) -> int:
+    """CRC-16 of a whole frame: polynomial 0x8005, initial value 0, MSB first, not reflected, no final XOR."""
+    c = 0
+    for b in bytes(data):
+        c = ((c << 8) & 0xFFFF) ^ _FLAC_CRC16[(c >> 8) ^ b]
+    return c
+
+
+def flac_bound(n_samples: int) -> int:
+    """Bytes a body of n_samples samples never exceeds: 42 + 7 + the sum over its frames of 16 + 2 n, rounded up to 4."""
+    n, frames = int(n_samples), (int(n_samples) + FLAC_BLOCK - 1) // FLAC_BLOCK
+    return (49 + 16 * frames + 2 * n + 3) & ~3
+
+
+def _flac_number(f: int) -> bytes:
+    """The frame number in the format's UTF-8-like coding (up to 36 bits; seven bits in one byte)."""
+    if f < 0x80:
+        return bytes([f])
+    n = 2
+    while f >> (5 * n + 1):  # n bytes hold 7 - n + 6 (n - 1) = 5 n + 1 bits
+        n += 1
+    lead = (0xFF << (8 - n)) & 0xFF
+    return bytes([lead | (f >> (6 * (n - 1)))] + [0x80 | ((f >> (6 * k)) & 0x3F) for k in range(n - 2, -1, -1)])
+
+
+def _flac_fold(e):
+    return (e << 1) ^ (e >> 31)  # int64 here: the same value as in int32, |e| < 2^20
+
+
+def _flac_partitions(u, o, n, P):
+    """(ks, bits) of order o at partition order P: u = the folded residuals of samples o .. n - 1."""
+    size, ks, bits, lo = n >> P, [], 0, 0
+    for j in range(1 << P):
+        hi = lo + size - (o if j == 0 else 0)
+        part = u[lo:hi]
+        cost = [int((part >> k).sum()) + (k + 1) * (hi - lo) for k in range(15)]
+        k = int(np.argmin(cost))  # (the first minimum: the smaller k wins a tie)
+        ks.append(k)
+        bits += 4 + cost[k]
+        lo = hi
+    return ks, 16 * o + 6 + bits
+
+
+def flac_frame(v, f: int, rate: int):
+    """Frame f of a stream: `v` = its n <= 4096 samples (int16).  Returns (bytes, (type, o, P, ks)) with type "CONSTANT", "FIXED" or
+    "VERBATIM" (o, P = 0 and ks = () where the type has none): the subframe include/kokorox_hip.h prescribes -- CONSTANT when all
+    samples are equal; else the fixed predictor order o in 0..min(4, n - 1) and the partition order P (0..6 when n = 4096, else 0)
+    with the fewest bits, Rice parameters 0..14 per partition by the same rule, ties to the smaller o, then P, then k; VERBATIM
+    when that reaches 16 n bits."""
+    v = np.asarray(v).astype(np.int64).reshape(-1)
+    n = v.shape[0]
+    if not 1 <= n <= FLAC_BLOCK or np.any(v < -32768) or np.any(v > 32767):
+        raise ValueError("flac_frame: 1..4096 samples of 16 bits")
+    head = bytes([0xFF, 0xF8, ((0b1100 if n == FLAC_BLOCK else 0b0111) << 4) | _FLAC_RATE_NIBBLE[int(rate)], 0x08]) + _flac_number(int(f))
+    if n != FLAC_BLOCK:
+        head += struct.pack(">H", n - 1)
+    head += bytes([flac_crc8(head)])
+    bits = []  # (value, width) pairs, MSB first
+
+    def put(value, width):
+        bits.append((int(value) & ((1 << width) - 1), width))
+
+    choice = ("CONSTANT", 0, 0, ())
+    if np.all(v == v[0]):
+        put(0x00, 8)
+        put(v[0], 16)
+    else:
+        best = None
+        for o in range(min(4, n - 1) + 1):
+            e = sum(c * v[o - j: n - j] for j, c in enumerate(_FLAC_FIXED[o]))
+            u = _flac_fold(e)
+            for P in range(7 if n == FLAC_BLOCK else 1):
+                ks, total = _flac_partitions(u, o, n, P)
+                if best is None or total < best[0]:
+                    best = (total, o, P, ks, u)
+        total, o, P, ks, u = best
+        if total >= 16 * n:
+            choice = ("VERBATIM", 0, 0, ())
+            put(0x02, 8)
+            for s in v:
+                put(s, 16)
+        else:
+            choice = ("FIXED", o, P, tuple(ks))
+            put((8 + o) << 1, 8)
+            for s in v[:o]:
+                put(s, 16)
+            put(0, 2)
+            put(P, 4)
+            size, lo = n >> P, 0
+            for j, k in enumerate(ks):
+                hi = lo + size - (o if j == 0 else 0)
+                put(k, 4)
+                for x in u[lo:hi]:
+                    x = int(x)
+                    put(0, x >> k)
+                    put((1 << k) | (x & ((1 << k) - 1)), k + 1)
+                lo = hi
+    acc, width = 0, 0
+    for value, w in bits:
+        acc, width = (acc << w) | value, width + w
+    pad = -width % 8
+    body = head + ((acc << pad).to_bytes((width + pad) // 8, "big") if width else b"")
+    return body + struct.pack(">H", flac_crc16(body)), choice
+
+
+def flac_body(v_int16, rate: int) -> bytes:
+    """Form 12: "fLaC", STREAMINFO (blocks of 4096, the frames' true smallest and largest size, `rate`, 1 channel, 16 bits, N samples,
+    no MD5), a PADDING block of (2 - the frames' bytes) mod 4 zeros, marked last, and the frames: a multiple of 4 bytes."""
+    v = np.asarray(v_int16).astype(np.int64).reshape(-1)
+    N = v.shape[0]
+    frames = [flac_frame(v[i: i + FLAC_BLOCK], i // FLAC_BLOCK, rate)[0] for i in range(0, N, FLAC_BLOCK)]
+    sizes = [len(fr) for fr in frames]
+    lo, hi = (min(sizes), max(sizes)) if sizes else (0, 0)
+    info = struct.pack(">HH", FLAC_BLOCK, FLAC_BLOCK) + lo.to_bytes(3, "big") + hi.to_bytes(3, "big")
+    info += ((int(rate) << 44) | (0 << 41) | (15 << 36) | N).to_bytes(8, "big") + bytes(16)
+    p = (2 - sum(sizes)) % 4
+    return b"fLaC" + bytes([0x00, 0, 0, 34]) + info + bytes([0x81, 0, 0, p]) + bytes(p) + b"".join(frames)
+
+
 _RATE_LM = {0: (1, 1), 1: (1, 3), 2: (2, 3), 3: (2, 1)}  # rate code of a format word -> (L, M): 24 000, 8000, 16 000, 48 000 Hz
 
 
@@ -618,6 +763,8 @@ def stream_body(y, word: int) -> bytes:
         return wav16_base64(y, rate)
     if form in (8, 9):
         return (mulaw_bytes if form == 8 else alaw_bytes)(pcm16(y)).tobytes()
+    if form == 12:
+        return flac_body(pcm16(y), rate)
     raise ValueError("stream_body: unknown output format")
 
 
@@ -658,7 +805,7 @@ def tts_request(model, styles: Dict[str, np.ndarray], style_name: str, chunk_tok
     """`tts_chunks` through `model.infer_requests`: the chunks of one text as ONE request of one batched forward, its body
     (header of the form, then the chunks' samples with nothing between them) packed on the GPU.  `fmt` is a format word of
     hip_koko (a PACK_* form, optionally | PACK_RATE_*): 0..2 and 8 / 9 give the samples as an array, 3 (`wav_f32_body`) and 4
-    (`wav16_base64`) the bytes a server sends.  `join` = (flags, keep_ms, pause_ms, fade_ms): the seams shaped on the GPU
+    (`wav16_base64`) the bytes a server sends, 12 (`flac_body`) a FLAC stream of the 16-bit samples.  `join` = (flags, keep_ms, pause_ms, fade_ms): the seams shaped on the GPU
     (`model.infer_requests_joined`; trim the pads' silence, pause between sentences, fade the cut edges).  `level` = (mode, gain,
     peak): the level set on the GPU (`model.infer_requests_levelled`; a volume, a peak to normalise to, or a ceiling).
     `loudness` = (mode, target_lufs, peak): the BS.1770 loudness set on the GPU (`model.infer_requests_loudness`).  Either mode

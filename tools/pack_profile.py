@@ -20,6 +20,9 @@ the command line; an optional second argument is the batch (1 = one utterance). 
                          of 64 and 'y' to -6 LUFS, both into a peak of 2^-6, so the drive cap holds g p at 4 peak and every stretch
                          within 12 dB of a request's peak is limited: request_limit_kernel and request_limit_report_kernel behind
                          the gain kernels, and pack_requests_limited_kernel; with 't' the limiter follows the true-peak envelope;
+    '12' / '0x30c'       kx_infer_requests in form 12 (FLAC; '0x30c' = at 48 kHz), every row a request of its own: flac_frames_kernel,
+                         flac_layout_kernel and flac_gather_kernel in the packer's place (pack_requests_kernel does not show: no
+                         request has a region for it); prints the bodies' bytes beside the PCM16 bytes of the same samples;
     a word and 'g'       ('2g') the same grouping without joins (kx_infer_requests_marks): the plain kernels on the same batch.
 Meant to run under the profiler, one mode per run (kernel trace only, no counters in the same run):
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o t -- python tools/pack_profile.py p2
@@ -78,6 +81,11 @@ for it in range(3):
         out, marks = m.infer_requests_marks(toks, [1] * B, styles=rows, fmt=word)
         L, M, _ = hk.resample_filter(word)
         assert all(k.shape[0] == 131 and int(k[-1]) == 422 * 600 * L // M for k in marks)
+    elif int(which, 0) & 0xFF == hk.PACK_FLAC:
+        out, ns = m.infer_requests(toks, [1] * B, styles=rows, fmt=int(which, 0), with_samples=True)
+        assert all(o[:4] == b"fLaC" and len(o) % 4 == 0 for o in out)
+        if it == 2:
+            print("FLAC bytes %d, PCM16 bytes of the same samples %d: ratio %.4f" % (sum(len(o) for o in out), 2 * sum(ns), sum(len(o) for o in out) / (2.0 * sum(ns))))
     else:
         out = m.infer_requests(toks, [1] * B, styles=rows, fmt=int(which, 0))
     n = sum(len(o) if isinstance(o, bytes) else o.nbytes for o in out)
