@@ -637,6 +637,59 @@ int kx_infer_requests_limited(kx_model* m, const int64_t* ids, int64_t t_stride,
                               int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_limit* limits,
                               int n_limit, double* out_limits);
 
+/* ---- prosody: per-token rate, fixed durations, pitch and energy of a call, and what the model chose -----------------------------
+ * The input side of a call beyond ids, style and one speed per row.  Every array of a kx_prosody that is not NULL is
+ * [B, t_stride], laid out as `ids`; only t < lens[b] is read.  A NULL array is neutral; a kx_prosody of four NULLs, or a NULL
+ * kx_prosody*, gives the call without prosody bit for bit.
+ *   Valid values.  0.25 <= rate <= 4, 0 <= frames <= 50, 0.25 <= pitch <= 4, 0 <= energy <= 4; a NaN fails every rule.  Checked on
+ *   the host before any device work: KX_ERR_INVALID "infer: bad prosody" (dispatcher: "dispatcher_submit_request: bad prosody").
+ *   Durations.  Token t of row b: (1) s = the float32 sum of the 50 sigmoids, as without prosody; (2) s = s / speed_b; (3) with
+ *   `rate`, s = s / rate[t], one float32 division (x / 1.0f is x: neutral spans keep their bits); (4) rintf, at least 1, and the
+ *   guard of the row's end, as without prosody; (5) the model's pinned pattern, if set (kx_set_pinned_durations); (6) with `frames`
+ *   and frames[t] >= 1, d = frames[t]: it replaces whatever came before.  A row longer than its alignment is cut and refused as
+ *   without prosody ("infer: speed too low ...").  Marks and joins are defined on these USED durations, so they follow.
+ *   Curves.  The model's F0 and N curves live on 2 F_b steps per row (F_b frames); step j belongs to token tau(j) = the token of
+ *   frame j >> 1.  With a per-token ratio rho (pitch or energy) and cl(i) = min(max(i, 0), 2 F_b - 1):
+ *       r[j] = (sum over k = -2 .. 2, ascending, of f64(w_k) * f64(rho[tau(cl(j + k))])) / 9.0,   w = (1, 2, 3, 2, 1),
+ *   a float64 accumulator from +0, one addition per term, one division.  Five equal ratios of 1 give exactly 1.0; the 5-step
+ *   triangle (62.5 ms wide) keeps a ratio step between two tokens from becoming a pitch jump.
+ *   F0: if !(F0[j] > 10.0f) (unvoiced for the source, or NaN) F0'[j] = F0[j]; otherwise v = f32(f64(F0[j]) * r[j]) and
+ *   F0'[j] = v > 10.0f ? v : the float above 10 (bits 0x41200001): the model's voiced / unvoiced decision never flips.
+ *   N: N'[j] = f32(f64(N[j]) * e[j]) for every j; a NaN stays.  Both readers of the curves, the harmonic source and the decoder,
+ *   take the shaped values.  Under KX_FLAG_TAPS, "pred.F0.raw" / "pred.N.raw" hold the curves before and "pred.F0" / "pred.N" after.
+ *   The API takes ratios, not semitones: exp2 in float64 is not the same bits on every libm.  float32(2 ^ (p / 12)) is the
+ *   caller's to compute (Python: voices.semitones).
+ *   Report.  Four float32 values per token of a request, chunk after chunk: [0] the mean of F0'[j] over the token's steps
+ *   j in [2 start, 2 (start + d)) with F0'[j] > 10 -- a float64 sum in ascending j, divided by the count, rounded once; +0.0f when
+ *   none is voiced (or d = 0); [1] that count; [2] f32(the float64 sum of N'[j] over all its steps, ascending, / (2 d)), +0.0f
+ *   when d = 0; [3] d.  It is the last block of the packed buffer, 8-aligned behind every other block, 16 x the request's tokens
+ *   bytes, present only when asked for, and leaves the device in the one copy.  To aim at a pitch in Hz: measure with neutral
+ *   ratios, then set pitch = target / measured.
+ *   Not offered: prosody together with the levelled, loudness and limited entries; semitone or Hz inputs; per-frame curves;
+ *   silence inside a chunk (a join's pause does that between chunks); SSML parsing. */
+#define KX_PROSODY_MAX_FRAMES 50
+typedef struct kx_prosody {
+    const float*   rate;    /* per token; durations are divided by it, like `speed`   */
+    const int32_t* frames;  /* per token; 0 = as predicted, 1..50 = exactly that many */
+    const float*   pitch;   /* per token; ratio applied to the F0 curve (1 = as is)   */
+    const float*   energy;  /* per token; ratio applied to the N curve  (1 = as is)   */
+} kx_prosody;
+/* kx_infer with a kx_prosody (may be NULL) and the used durations: out_durations [B, t_stride] int32, entries t < lens[b] written,
+ * may be NULL. */
+int kx_infer_prosody(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* styles,
+                     const float* speeds, int n_speed, uint64_t seed, uint32_t flags, float** out, int64_t* out_lens,
+                     const kx_prosody* prosody, int32_t* out_durations);
+/* kx_infer_requests_joined with a kx_prosody (may be NULL) for the call's rows and the report.  `joins` may be NULL with
+ * n_join == 0 (no joins).  out_report and out_n_report are both NULL (no report) or both set, else "infer: null report argument":
+ * *out_report points INTO *out as *out_marks does (never freed on its own), the requests' tokens back to back, and
+ * out_n_report[r] = the tokens of request r (the sum of its chunks' lens). */
+int kx_infer_requests_prosody(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                              const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                              const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                              const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                              int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_prosody* prosody,
+                              float** out_report, int64_t* out_n_report);
+
 /* ---- request dispatcher ----------------------------------------------------
  * Replaces the reference's one-request-at-a-time `Mutex<Session>` (kokorox/src/onn/ort_koko.rs:78; callers
  * kokorox-openai/src/lib.rs:370-439, kokorox-websocket/src/lib.rs:657-668).  Any number of threads submit
@@ -739,6 +792,18 @@ int kx_dispatcher_submit_request_limited(kx_dispatcher* d, const int64_t* ids, c
                                          float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
                                          int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
                                          const kx_limit* limit, double* out_limit, char* err, size_t err_len);
+/* kx_dispatcher_submit_request_joined with the request's prosody (see "prosody" above) and its report; `join` may be NULL here
+ * (no join).  The arrays of `prosody` that are not NULL hold the chunks' values back to back, as `ids` does; a NULL `prosody` is
+ * the neutral one.  out_report and out_n_report are both NULL (no report) or both set, else
+ * "dispatcher_submit_request: null report argument"; *out_report points INTO the allocation of *out, as *out_marks does, and
+ * *out_n_report = the request's tokens.  A value outside its range: "dispatcher_submit_request: bad prosody".  Prosody and plain requests share batches; a request's bytes,
+ * marks and report equal those of kx_infer_requests_prosody (R = 1, same seed, utterance base 0) whatever it was batched with. */
+int kx_dispatcher_submit_request_prosody(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                         const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
+                                         float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
+                                         int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
+                                         const kx_prosody* prosody, float** out_report, int64_t* out_n_report, char* err,
+                                         size_t err_len);
 /* n_requests counts requests, max_batch_seen the largest batch in ROWS (a request of n chunks is n rows). */
 int kx_dispatcher_stats(kx_dispatcher* d, int64_t* n_requests, int64_t* n_batches, int64_t* max_batch_seen);
 /* batches each model (worker) has run so far: per_model[n_models] */

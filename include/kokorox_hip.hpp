@@ -51,6 +51,17 @@ struct LoudnessResult {
     double peak, gain, lufs, gated_blocks;
 };
 
+// A call's per-token prosody ("prosody" in kokorox_hip.h): each field empty (neutral) or one row per chunk with a value per token;
+// and one token of the report: the mean F0 in Hz over its voiced steps (0 when none), their count, the mean of the N curve, its frames.
+struct Prosody {
+    std::vector<std::vector<float>> rate;
+    std::vector<std::vector<int32_t>> frames;
+    std::vector<std::vector<float>> pitch, energy;
+};
+struct ProsodyToken {
+    float f0_hz, voiced_steps, energy, frames;
+};
+
 class HipKoko {
   public:
     explicit HipKoko(const std::string& model_path, int device = 0) {
@@ -192,6 +203,70 @@ class HipKoko {
             p += nb[r];
             marks.emplace_back(mk, mk + nm[r]);
             mk += nm[r];
+        }
+        kx_free_packed(out);
+        return bodies;
+    }
+
+    // infer_requests with per-token prosody and its report (kx_infer_requests_prosody; "prosody" in kokorox_hip.h): each field of
+    // `prosody` is empty (neutral) or holds one row per chunk with a value per token; no joins, no marks.  report[r] = one
+    // ProsodyToken per token of request r, chunk after chunk.
+    std::vector<std::string> infer_requests_prosody(const std::vector<std::vector<int64_t>>& tokens,
+                                                    const std::vector<int32_t>& chunks_per_request,
+                                                    const std::vector<std::vector<float>>& styles, float speed, uint64_t seed,
+                                                    int format, const Prosody& prosody,
+                                                    std::vector<std::vector<ProsodyToken>>& report) const {
+        if (tokens.empty() || styles.size() != tokens.size()) throw std::invalid_argument("infer_requests: one style row per chunk");
+        const int B = (int)tokens.size(), R = (int)chunks_per_request.size();
+        size_t stride = 1;
+        for (const auto& t : tokens) stride = t.size() > stride ? t.size() : stride;
+        std::vector<int64_t> ids((size_t)B * stride, 0);
+        std::vector<int32_t> tl(B);
+        std::vector<float> st((size_t)B * KX_STYLE_DIM);
+        for (int b = 0; b < B; ++b) {
+            tl[b] = (int32_t)tokens[b].size();
+            for (size_t i = 0; i < tokens[b].size(); ++i) ids[(size_t)b * stride + i] = tokens[b][i];
+            if (styles[b].size() != KX_STYLE_DIM) throw std::invalid_argument("infer_requests: style rows need 256 floats");
+            for (int k = 0; k < KX_STYLE_DIM; ++k) st[(size_t)b * KX_STYLE_DIM + k] = styles[b][k];
+        }
+        // the four arrays laid out as the ids, neutral where a row is shorter than the stride
+        auto rows = [&](const auto& given, auto neutral) {
+            std::vector<decltype(neutral)> flat;
+            if (given.empty()) return flat;
+            if (given.size() != tokens.size()) throw std::invalid_argument("infer_requests_prosody: one row per chunk");
+            flat.assign((size_t)B * stride, neutral);
+            for (int b = 0; b < B; ++b) {
+                if (given[b].size() != tokens[b].size()) throw std::invalid_argument("infer_requests_prosody: one value per token");
+                for (size_t i = 0; i < given[b].size(); ++i) flat[(size_t)b * stride + i] = given[b][i];
+            }
+            return flat;
+        };
+        const std::vector<float> rate = rows(prosody.rate, 1.0f), pitch = rows(prosody.pitch, 1.0f), energy = rows(prosody.energy, 1.0f);
+        const std::vector<int32_t> frames = rows(prosody.frames, (int32_t)0);
+        const kx_prosody ps = {rate.empty() ? nullptr : rate.data(), frames.empty() ? nullptr : frames.data(),
+                               pitch.empty() ? nullptr : pitch.data(), energy.empty() ? nullptr : energy.data()};
+        void* out = nullptr;
+        float* rp = nullptr;
+        std::vector<int64_t> nb(R > 0 ? R : 1), ns(R > 0 ? R : 1), nr(R > 0 ? R : 1);
+        const int32_t fmt = format;
+        const int rc = kx_infer_requests_prosody(h_, ids.data(), (int64_t)stride, tl.data(), B, chunks_per_request.data(), R, st.data(),
+                                                 nullptr, nullptr, 0, &speed, 1, seed, 0, &fmt, 1, &out, nb.data(), ns.data(), nullptr,
+                                                 nullptr, nullptr, 0, &ps, &rp, nr.data());
+        if (rc != KX_OK) {
+            char msg[512];
+            kx_last_error_copy(h_, msg, sizeof(msg));
+            throw std::runtime_error(std::string("kokorox_hip error: ") + msg);
+        }
+        std::vector<std::string> bodies;
+        report.clear();
+        const char* p = static_cast<const char*>(out);
+        for (int r = 0; r < R; ++r) {  // (the report lives in the buffer of `out`: copied before it is released)
+            bodies.emplace_back(p, p + nb[r]);
+            p += nb[r];
+            std::vector<ProsodyToken> tok((size_t)nr[r]);
+            for (int64_t i = 0; i < nr[r]; ++i) tok[(size_t)i] = ProsodyToken{rp[4 * i], rp[4 * i + 1], rp[4 * i + 2], rp[4 * i + 3]};
+            rp += 4 * nr[r];
+            report.push_back(std::move(tok));
         }
         kx_free_packed(out);
         return bodies;

@@ -205,6 +205,22 @@ int kx_test_alignment(int device_id, const float* logits, int B, int T, const in
                       const int32_t* pinned, int n_pinned, const float* src, int C, int idx_ld, int32_t* dur, int32_t* frames,
                       int32_t* idx, float* gathered, int Fcap, uint32_t* overflow, char* err, size_t err_len);
 
+/* kx_test_alignment on launch_prosody_duration (include/kokorox_hip.h, "prosody"): rate [B,T] and fixed [B,T] per token (either may
+ * be NULL, not both; entries at or past lens[b] are not read: they go up as NaN / 0xA5 bytes).  Everything else as kx_test_alignment. */
+int kx_test_prosody_durations(int device_id, const float* logits, int B, int T, const int32_t* lens, const float* speeds, int n_speed,
+                              const int32_t* pinned, int n_pinned, const float* rate, const int32_t* fixed, const float* src, int C,
+                              int idx_ld, int32_t* dur, int32_t* frames, int32_t* idx, float* gathered, int Fcap, uint32_t* overflow,
+                              char* err, size_t err_len);
+
+/* launch_prosody_curves on curves [B,2,2 Fcap] (row 0 = F0, row 1 = N; row b valid for 2 frames[b] steps, 1 <= frames[b] <= Fcap),
+ * idx [B,idx_ld] (entries f < frames[b] in 0 .. lens[b] - 1), dur [B,T] (sum over t < lens[b] = frames[b]) and the per-token ratios
+ * pitch / energy [B,T] (either may be NULL).  Out: shaped [B,2,2 Fcap], the whole rows as the kernel left them (what the caller had
+ * past 2 frames[b] must come back), and, when report is not NULL, report [sum of lens,4], the rows' tokens back to back.  The row
+ * padding and the guards behind both buffers are checked here: KX_ERR_STATE. */
+int kx_test_prosody_curves(int device_id, const float* curves, const int32_t* frames, int B, int Fcap, const int32_t* lens, int T,
+                           const int32_t* idx, int idx_ld, const int32_t* dur, const float* pitch, const float* energy, float* shaped,
+                           float* report, char* err, size_t err_len);
+
 /* Both embedding kernels on one id buffer ids [B,ids_stride] (ids_stride >= T; row b valid for lens[b] ids): launch_embed with
  * text_table [n_vocab,512] -> out_text [B,512,T], launch_albert_embed with word [n_vocab,128], type0 [128], pos [T,128] ->
  * out_albert [B,128,T]; columns >= lens[b] come back as -12345.5.  bad = the sticky word the two share, as in the model (0, or

@@ -153,6 +153,48 @@ pub fn limit_filter(format_word: c_int) -> Result<(usize, Vec<f32>), Box<dyn Err
     }
 }
 
+pub const KX_PROSODY_MAX_FRAMES: i32 = 50;
+
+/// Per-token prosody of a call (`kx_prosody`; "prosody" in kokorox_hip.h): every pointer is null (neutral) or `[B, t_stride]`
+/// laid out as the ids.  `rate` 0.25..4 divides the durations, `frames` 0 (as predicted) or 1..50 fixes them, `pitch` 0.25..4 and
+/// `energy` 0..4 are ratios on the F0 and N curves.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct KxProsody {
+    pub rate: *const f32,
+    pub frames: *const i32,
+    pub pitch: *const f32,
+    pub energy: *const f32,
+}
+
+/// The per-token prosody of a call as the safe wrappers take it: each field empty (neutral) or one vector per row with a value
+/// per token.
+#[derive(Clone, Debug, Default)]
+pub struct Prosody {
+    pub rate: Vec<Vec<f32>>,
+    pub frames: Vec<Vec<i32>>,
+    pub pitch: Vec<Vec<f32>>,
+    pub energy: Vec<Vec<f32>>,
+}
+
+/// One token of a request's prosody report: the mean F0 in Hz over its voiced steps (0 when none), their count, the mean of the
+/// N curve over its steps, and its frames.
+pub type ProsodyToken = [f32; 4];
+
+fn prosody_rows<V: Copy>(rows: &[Vec<V>], lens: &[i32], stride: usize, neutral: V) -> Result<Vec<V>, Box<dyn Error>> {
+    if rows.is_empty() {
+        return Ok(Vec::new());
+    }
+    if rows.len() != lens.len() || rows.iter().zip(lens).any(|(r, &n)| r.len() != n as usize) {
+        return Err("prosody: one value per token of every row is required".into());
+    }
+    let mut flat = vec![neutral; lens.len() * stride];
+    for (b, r) in rows.iter().enumerate() {
+        flat[b * stride..b * stride + r.len()].copy_from_slice(r);
+    }
+    Ok(flat)
+}
+
 #[repr(C)]
 pub struct KxModel {
     _p: [u8; 0],
@@ -195,6 +237,21 @@ extern "C" {
                                             out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64,
                                             join: *const KxJoin, limit: *const KxLimit, out_limit: *mut f64, err: *mut c_char,
                                             err_len: usize) -> c_int;
+    fn kx_infer_prosody(m: *mut KxModel, ids: *const i64, t_stride: i64, lens: *const i32, b: c_int, styles: *const f32,
+                        speeds: *const f32, n_speed: c_int, seed: u64, flags: u32, out: *mut *mut f32, out_lens: *mut i64,
+                        prosody: *const KxProsody, out_durations: *mut i32) -> c_int;
+    fn kx_infer_requests_prosody(m: *mut KxModel, ids: *const i64, t_stride: i64, lens: *const i32, b: c_int,
+                                 chunks_per_request: *const i32, r: c_int, styles: *const f32, voice_ids: *const i32,
+                                 weights: *const f32, max_mix: c_int, speeds: *const f32, n_speed: c_int, seed: u64, flags: u32,
+                                 formats: *const c_int, n_format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                                 out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64, joins: *const KxJoin,
+                                 n_join: c_int, prosody: *const KxProsody, out_report: *mut *mut f32, out_n_report: *mut i64) -> c_int;
+    fn kx_dispatcher_submit_request_prosody(d: *mut KxDispatcher, ids: *const i64, chunk_tokens: *const i32, n_chunks: c_int,
+                                            styles: *const f32, voice_ids: *const i32, weights: *const f32, n_mix: c_int,
+                                            speed: f32, seed: u64, format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                                            out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64,
+                                            join: *const KxJoin, prosody: *const KxProsody, out_report: *mut *mut f32,
+                                            out_n_report: *mut i64, err: *mut c_char, err_len: usize) -> c_int;
     fn kx_create_from_device_blob(d_blob: *const c_void, n_bytes: usize, device_id: c_int, err: *mut c_char,
                                   err_len: usize) -> *mut KxModel;
     fn kx_create_replicas(weights_path: *const c_char, device_ids: *const c_int, n: c_int,
@@ -782,6 +839,60 @@ impl HipKoko {
             at += nbytes[i] as usize;
             mat += nmarks[i] as usize;
             res.push((body, marks, [lm[5 * i], lm[5 * i + 1], lm[5 * i + 2], lm[5 * i + 3], lm[5 * i + 4]]));
+        }
+        unsafe { kx_free_packed(out) };
+        Ok(res)
+    }
+
+    /// `infer_requests_joined` with per-token prosody and its report ("prosody" in kokorox_hip.h): `prosody` holds, per field, no
+    /// rows (neutral) or one vector per chunk; `joins` may be empty (no joins).  Per request: body, marks, and the report, one
+    /// `ProsodyToken` per token of its chunks.
+    #[allow(clippy::type_complexity)]
+    pub fn infer_requests_prosody(&self, tokens: &[Vec<i64>], chunks_per_request: &[i32], styles: &[Vec<f32>], speeds: &[f32],
+                                  seed: u64, formats: &[c_int], joins: &[KxJoin], prosody: &Prosody)
+                                  -> Result<Vec<(Vec<u8>, Vec<i64>, Vec<ProsodyToken>)>, Box<dyn Error>> {
+        if tokens.is_empty() || styles.len() != tokens.len() || styles.iter().any(|s| s.len() != KX_STYLE_DIM) {
+            return Err("infer_requests: one style row of 256 floats per chunk is required".into());
+        }
+        let (b, r) = (tokens.len(), chunks_per_request.len());
+        let (ids, lens, stride) = Self::flatten(tokens);
+        let st: Vec<f32> = styles.iter().flatten().copied().collect();
+        let rate = prosody_rows(&prosody.rate, &lens, stride as usize, 1f32)?;
+        let frames = prosody_rows(&prosody.frames, &lens, stride as usize, 0i32)?;
+        let pitch = prosody_rows(&prosody.pitch, &lens, stride as usize, 1f32)?;
+        let energy = prosody_rows(&prosody.energy, &lens, stride as usize, 1f32)?;
+        let ps = KxProsody {
+            rate: if rate.is_empty() { ptr::null() } else { rate.as_ptr() },
+            frames: if frames.is_empty() { ptr::null() } else { frames.as_ptr() },
+            pitch: if pitch.is_empty() { ptr::null() } else { pitch.as_ptr() },
+            energy: if energy.is_empty() { ptr::null() } else { energy.as_ptr() },
+        };
+        let mut out: *mut c_void = ptr::null_mut();
+        let mut mk: *mut i64 = ptr::null_mut();
+        let mut rp: *mut f32 = ptr::null_mut();
+        let (mut nbytes, mut nsamp, mut nmarks) = (vec![0i64; r.max(1)], vec![0i64; r.max(1)], vec![0i64; r.max(1)]);
+        let mut nrep = vec![0i64; r.max(1)];
+        let rc = unsafe {
+            kx_infer_requests_prosody(self.h, ids.as_ptr(), stride as i64, lens.as_ptr(), b as c_int, chunks_per_request.as_ptr(),
+                                      r as c_int, st.as_ptr(), ptr::null(), ptr::null(), 0, speeds.as_ptr(), speeds.len() as c_int,
+                                      seed, 0, formats.as_ptr(), formats.len() as c_int, &mut out, nbytes.as_mut_ptr(),
+                                      nsamp.as_mut_ptr(), &mut mk, nmarks.as_mut_ptr(),
+                                      if joins.is_empty() { ptr::null() } else { joins.as_ptr() }, joins.len() as c_int, &ps,
+                                      &mut rp, nrep.as_mut_ptr())
+        };
+        self.check(rc)?;
+        let mut res = Vec::with_capacity(r);
+        let (mut at, mut mat, mut rat) = (0usize, 0usize, 0usize);
+        for i in 0..r {
+            // (marks and report live in the buffer of `out`: copied before it is released)
+            let body = unsafe { std::slice::from_raw_parts((out as *const u8).add(at), nbytes[i] as usize) }.to_vec();
+            let marks = unsafe { std::slice::from_raw_parts((mk as *const i64).add(mat), nmarks[i] as usize) }.to_vec();
+            let flat = unsafe { std::slice::from_raw_parts((rp as *const f32).add(4 * rat), 4 * nrep[i] as usize) };
+            let report: Vec<ProsodyToken> = flat.chunks_exact(4).map(|c| [c[0], c[1], c[2], c[3]]).collect();
+            at += nbytes[i] as usize;
+            mat += nmarks[i] as usize;
+            rat += nrep[i] as usize;
+            res.push((body, marks, report));
         }
         unsafe { kx_free_packed(out) };
         Ok(res)

@@ -274,6 +274,30 @@ int kx_infer(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* l
     return guarded(m, [&](Model& M) { M.infer_host(ids, t_stride, lens, B, styles, speeds, n_speed, seed, flags, out, out_lens); });
 }
 
+static_assert(sizeof(kx_prosody) == sizeof(kx::ProsodySpec) && offsetof(kx_prosody, rate) == offsetof(kx::ProsodySpec, rate) &&
+                  offsetof(kx_prosody, frames) == offsetof(kx::ProsodySpec, frames) && offsetof(kx_prosody, pitch) == offsetof(kx::ProsodySpec, pitch) &&
+                  offsetof(kx_prosody, energy) == offsetof(kx::ProsodySpec, energy) && KX_PROSODY_MAX_FRAMES == kx::PROSODY_MAX_FRAMES,
+              "kx_prosody is the layout of kx::ProsodySpec");
+
+int kx_infer_prosody(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* styles,
+                     const float* speeds, int n_speed, uint64_t seed, uint32_t flags, float** out, int64_t* out_lens,
+                     const kx_prosody* prosody, int32_t* out_durations) {
+    return guarded(m, [&](Model& M) {
+        KX_REQUIRE(out && out_lens, "infer: null output argument");
+        *out = nullptr;
+        KX_REQUIRE(styles, "infer: null argument");
+        Model::HostCall hc;
+        hc.styles = styles;
+        hc.prosody_call = true;
+        hc.prosody = reinterpret_cast<const kx::ProsodySpec*>(prosody);
+        hc.out_durations = out_durations;
+        void* p = nullptr;
+        std::vector<int64_t> bytes(B > 0 ? B : 1);
+        M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, &p, bytes.data(), out_lens);
+        *out = static_cast<float*>(p);
+    });
+}
+
 void kx_free_audio(float* p) { kx::host_out_free(p); }
 void kx_free_packed(void* p) { kx::host_out_free(p); }
 
@@ -339,7 +363,8 @@ static int infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, con
                           int n_join = 0, bool levelled = false, const kx_level* levels = nullptr, int n_level = 0,
                           double* out_levels = nullptr, bool loud = false, const kx_loudness* loudness = nullptr, int n_loudness = 0,
                           double* out_loudness = nullptr, bool limited = false, const kx_limit* limits = nullptr, int n_limit = 0,
-                          double* out_limits = nullptr) {
+                          double* out_limits = nullptr, bool pros = false, const kx_prosody* prosody = nullptr, float** out_report = nullptr,
+                          int64_t* out_n_report = nullptr) {
     return guarded(m, [&](Model& M) {
         KX_REQUIRE(chunks_per_request && formats && R >= 1, "infer_requests: null argument");
         KX_REQUIRE((styles != nullptr) != (voice_ids != nullptr), "infer_requests: give the style rows OR voice ids, not both");
@@ -378,8 +403,18 @@ static int infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, con
             hc.req_limits = reinterpret_cast<const kx::LimitSpec*>(limits);
             hc.n_req_limits = n_limit;
         }
+        std::vector<uint8_t> want_report;
+        if (pros) {  // (a null `prosody` is the neutral one; the report pair is both there or both null: check_prosody_call)
+            hc.prosody_call = true;
+            hc.prosody = reinterpret_cast<const kx::ProsodySpec*>(prosody);
+            if (out_report && out_n_report) {  // (every request of the call)
+                want_report.assign((size_t)R, 1);
+                hc.req_reports = want_report.data();
+            }
+        }
         M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks,
-                        levelled ? out_levels : nullptr, loud ? out_loudness : nullptr, limited ? out_limits : nullptr);
+                        levelled ? out_levels : nullptr, loud ? out_loudness : nullptr, limited ? out_limits : nullptr,
+                        pros ? out_report : nullptr, pros ? out_n_report : nullptr);
     });
 }
 
@@ -408,6 +443,19 @@ int kx_infer_requests_joined(kx_model* m, const int64_t* ids, int64_t t_stride, 
     return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
                           flags, formats, n_format, out, out_bytes, out_samples, out_marks || out_n_marks, out_marks, out_n_marks, true,
                           joins, n_join);
+}
+
+int kx_infer_requests_prosody(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                              const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                              const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                              const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                              int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_prosody* prosody,
+                              float** out_report, int64_t* out_n_report) {
+    // (joins == NULL with n_join == 0: no joins; anything else goes through the join entry's checks)
+    return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
+                          flags, formats, n_format, out, out_bytes, out_samples, out_marks || out_n_marks, out_marks, out_n_marks,
+                          joins != nullptr || n_join != 0, joins, n_join, false, nullptr, 0, nullptr, false, nullptr, 0, nullptr, false,
+                          nullptr, 0, nullptr, true, prosody, out_report, out_n_report);
 }
 
 int kx_infer_requests_levelled(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,

@@ -27,6 +27,9 @@ struct ModelBackend {
         std::vector<double> levels;  // [R][2] = {f64(p), g} when some request of the batch came through the levelled entry, else empty
         std::vector<double> loud;    // [R][4] = {f64(p), g, I, n_g} when some request came through the loudness entry, else empty
         std::vector<double> limits;  // [R][5] = {f64(p), g, I, n_g, r} when some request came through the limiter's entry, else empty
+        // the prosody report of the requests that want it: the last block of the same buffer (null: nobody asked)
+        float* report = nullptr;
+        std::vector<int64_t> n_report;
     };
     static int n_voices(kx_model* h) { return h->m->n_voices(); }
     static int n_vocab(kx_model* h) { return h->m->n_vocab(); }
@@ -39,7 +42,13 @@ struct ModelBackend {
         size_t stride = 0;
         int mm = 1;
         bool any_voice = false, any_marks = false, any_join = false, any_level = false, any_loud = false, any_limit = false;
+        bool any_rate = false, any_frames = false, any_pitch = false, any_energy = false, any_report = false;
         for (Request* r : batch) {
+            any_rate = any_rate || !r->p_rate.empty();
+            any_frames = any_frames || !r->p_frames.empty();
+            any_pitch = any_pitch || !r->p_pitch.empty();
+            any_energy = any_energy || !r->p_energy.empty();
+            any_report = any_report || r->want_report;
             any_limit = any_limit || r->limited;
             any_loud = any_loud || r->metered;
             any_marks = any_marks || r->want_marks;
@@ -55,7 +64,11 @@ struct ModelBackend {
         std::vector<float> styles((size_t)B * KX_STYLE_DIM, 0.f), speeds(B), weights((size_t)B * mm, 0.f);
         std::vector<uint64_t> seeds(B);
         std::vector<uint32_t> uidx(B);
-        std::vector<uint8_t> want(R);
+        std::vector<uint8_t> want(R), want_report(R);
+        // (a request without prosody beside one that has it: the neutral values, which leave its bits alone)
+        std::vector<float> p_rate(any_rate ? (size_t)B * stride : 0, 1.0f), p_pitch(any_pitch ? (size_t)B * stride : 0, 1.0f),
+            p_energy(any_energy ? (size_t)B * stride : 0, 1.0f);
+        std::vector<int32_t> p_frames(any_frames ? (size_t)B * stride : 0, 0);
         std::vector<kx::JoinSpec> joins(R);  // (a plain request beside a joined one: the all-zero spec, the plain bytes)
         std::vector<kx::LevelSpec> levels(R);  // (a request without levels beside a levelled one: the plain spec, z' = z)
         std::vector<kx::LoudSpec> louds(R);  // (a request without loudness beside a metered one: LOUD_NONE, the meter passes it by)
@@ -67,6 +80,7 @@ struct ModelBackend {
             chunks[q] = r.rows();
             formats[q] = r.format;
             want[q] = r.want_marks ? 1 : 0;
+            want_report[q] = r.want_report ? 1 : 0;
             joins[q] = kx::JoinSpec{r.join.flags, r.join.keep_ms, r.join.pause_ms, r.join.fade_ms};
             levels[q] = kx::LevelSpec{r.level.mode, r.level.gain, r.level.peak};
             louds[q] = r.metered ? kx::LoudSpec{r.loudness.mode, r.loudness.target_lufs, r.loudness.peak} : kx::LoudSpec{kx::LOUD_NONE, 0.0f, 0.0f};
@@ -74,6 +88,10 @@ struct ModelBackend {
             for (int c = 0; c < r.rows(); ++c, ++b) {
                 lens[b] = (int32_t)r.chunk_len(c);
                 memcpy(&ids[(size_t)b * stride], r.ids.data() + at, (size_t)lens[b] * 8);
+                if (!r.p_rate.empty()) memcpy(&p_rate[(size_t)b * stride], r.p_rate.data() + at, (size_t)lens[b] * 4);
+                if (!r.p_frames.empty()) memcpy(&p_frames[(size_t)b * stride], r.p_frames.data() + at, (size_t)lens[b] * 4);
+                if (!r.p_pitch.empty()) memcpy(&p_pitch[(size_t)b * stride], r.p_pitch.data() + at, (size_t)lens[b] * 4);
+                if (!r.p_energy.empty()) memcpy(&p_energy[(size_t)b * stride], r.p_energy.data() + at, (size_t)lens[b] * 4);
                 at += (size_t)lens[b];
                 kinds[b] = r.kind;
                 if (r.kind == 0) memcpy(&styles[(size_t)b * KX_STYLE_DIM], r.style.data() + (size_t)c * KX_STYLE_DIM, KX_STYLE_DIM * 4);
@@ -91,6 +109,8 @@ struct ModelBackend {
         o.samples.assign(R, 0);
         o.marks = nullptr;
         o.n_marks.assign(R, 0);
+        o.report = nullptr;
+        o.n_report.assign(R, 0);
         o.levels.assign(any_level ? (size_t)2 * R : 0, 0.0);
         o.loud.assign(any_loud ? (size_t)4 * R : 0, 0.0);
         o.limits.assign(any_limit ? (size_t)5 * R : 0, 0.0);
@@ -127,6 +147,13 @@ struct ModelBackend {
                     hc.req_limits = limits.data();
                     hc.n_req_limits = R;
                 }
+                const kx::ProsodySpec ps{any_rate ? p_rate.data() : nullptr, any_frames ? p_frames.data() : nullptr,
+                                         any_pitch ? p_pitch.data() : nullptr, any_energy ? p_energy.data() : nullptr};
+                if (any_rate || any_frames || any_pitch || any_energy || any_report) {
+                    hc.prosody_call = true;
+                    hc.prosody = &ps;
+                    if (any_report) hc.req_reports = want_report.data();
+                }
                 if (any_voice) {
                     hc.voice_ids = vids.data();
                     hc.weights = weights.data();
@@ -138,7 +165,8 @@ struct ModelBackend {
                 }
                 M.infer_host_ex(ids.data(), (int64_t)stride, lens.data(), B, speeds.data(), B, 0, 0, hc, &o.buf, o.bytes.data(),
                                 o.samples.data(), &o.marks, o.n_marks.data(), any_level ? o.levels.data() : nullptr,
-                                any_loud ? o.loud.data() : nullptr, any_limit ? o.limits.data() : nullptr);
+                                any_loud ? o.loud.data() : nullptr, any_limit ? o.limits.data() : nullptr,
+                                any_report ? &o.report : nullptr, any_report ? o.n_report.data() : nullptr);
                 rc = KX_OK;
             } catch (const kx::Error& e) {
                 rc = e.code;
@@ -161,10 +189,13 @@ struct ModelBackend {
         const int B = (int)batch.size();
         std::vector<void*> parts((size_t)B);
         std::vector<int64_t*> marks((size_t)B, nullptr);  // a request's marks go with its body: one owner, one pointer to release
-        int64_t off = 0, moff = 0;
+        std::vector<float*> reports((size_t)B, nullptr);  // ... and so does its prosody report
+        int64_t off = 0, moff = 0, roff = 0;
         for (int b = 0; b < B; ++b) {
             parts[(size_t)b] = static_cast<char*>(o.buf) + off;
             off += o.bytes[(size_t)b];
+            if (o.report && o.n_report[(size_t)b] > 0) reports[(size_t)b] = o.report + 4 * roff;
+            roff += o.n_report[(size_t)b];
             if (o.marks && o.n_marks[(size_t)b] > 0) marks[(size_t)b] = o.marks + moff;
             moff += o.n_marks[(size_t)b];
         }
@@ -178,14 +209,20 @@ struct ModelBackend {
             copies.reserve((size_t)B);
             bool ok = true;
             std::vector<int64_t*> mcopies((size_t)B, nullptr);
+            std::vector<float*> rcopies((size_t)B, nullptr);
             for (int b = 0; b < B && ok; ++b) {
-                // body and marks in ONE plain allocation, the marks 8-aligned behind the body: still one pointer to release
+                // body, marks and report in ONE plain allocation, each 8-aligned behind the one before: still one pointer to release
                 const size_t body = (size_t)o.bytes[(size_t)b], mbytes = marks[(size_t)b] ? (size_t)o.n_marks[(size_t)b] * 8 : 0;
+                const size_t rbytes = reports[(size_t)b] ? (size_t)o.n_report[(size_t)b] * 16 : 0;
                 const size_t mat = (body + 7) & ~size_t(7);
-                void* q = malloc(mbytes ? mat + mbytes : (body > 0 ? body : 1));
+                void* q = malloc(mbytes || rbytes ? mat + mbytes + rbytes : (body > 0 ? body : 1));
                 ok = q != nullptr;
                 if (ok) {
                     memcpy(q, parts[(size_t)b], body);
+                    if (rbytes) {
+                        rcopies[(size_t)b] = reinterpret_cast<float*>(static_cast<char*>(q) + mat + mbytes);
+                        memcpy(rcopies[(size_t)b], reports[(size_t)b], rbytes);
+                    }
                     if (mbytes) {
                         mcopies[(size_t)b] = reinterpret_cast<int64_t*>(static_cast<char*>(q) + mat);
                         memcpy(mcopies[(size_t)b], marks[(size_t)b], mbytes);
@@ -196,6 +233,7 @@ struct ModelBackend {
             if (ok) {
                 parts = copies;
                 marks = mcopies;
+                reports = rcopies;
                 kx::host_out_free(o.buf);
             } else {  // (out of pageable memory: share after all)
                 for (void* q : copies) free(q);
@@ -211,6 +249,8 @@ struct ModelBackend {
             r->out_samples = o.samples[(size_t)b];
             r->marks = r->want_marks ? marks[(size_t)b] : nullptr;
             r->n_marks = r->want_marks ? o.n_marks[(size_t)b] : 0;
+            r->report = r->want_report ? reports[(size_t)b] : nullptr;
+            r->n_report = r->want_report ? o.n_report[(size_t)b] : 0;
             if (r->levelled && !o.levels.empty()) {
                 r->level_out[0] = o.levels[(size_t)2 * b];
                 r->level_out[1] = o.levels[(size_t)2 * b + 1];
@@ -222,6 +262,7 @@ struct ModelBackend {
         }
         o.buf = nullptr;
         o.marks = nullptr;
+        o.report = nullptr;
     }
 };
 
@@ -354,6 +395,21 @@ int kx_dispatcher_submit_request_levelled(kx_dispatcher* d, const int64_t* ids, 
     }
     return d->submit_request_levelled(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
                                       out_bytes, out_samples, out_marks, out_n_marks, join, level, out_level, err, err_len);
+}
+
+int kx_dispatcher_submit_request_prosody(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                         const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
+                                         float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
+                                         int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
+                                         const kx_prosody* prosody, float** out_report, int64_t* out_n_report, char* err,
+                                         size_t err_len) {
+    if (!d) {
+        if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null dispatcher");
+        return KX_ERR_INVALID;
+    }
+    return d->submit_request_prosody(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
+                                     out_bytes, out_samples, out_marks, out_n_marks, join, prosody, out_report, out_n_report, err,
+                                     err_len);
 }
 
 int kx_dispatcher_submit_request_limited(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,

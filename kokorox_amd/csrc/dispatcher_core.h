@@ -97,11 +97,17 @@ struct Request {
     bool limited = false;     // it came through the limiter's entry: its body is driven and limited by `limit`
     double limit_out[5] = {0.0, 1.0, 0.0, 0.0, 1.0};  // limited: f64(p), g, I, n_g and r of the request, as the GPU computed them
     bool want_marks = false;  // the token marks of the request beside its body (submit_request_marks); a batch may mix both kinds
+    // its prosody (submit_request_prosody): per token, the chunks back to back as `ids`; an empty vector = that array was not given
+    std::vector<float> p_rate, p_pitch, p_energy;
+    std::vector<int32_t> p_frames;
+    bool want_report = false;  // the prosody report of the request beside its body; a batch may mix both kinds
     // result
     void* out = nullptr;
     int64_t out_bytes = 0, out_samples = 0;
     int64_t* marks = nullptr;  // want_marks: into the allocation of `out`, 8-byte aligned behind the body; released with `out`
     int64_t n_marks = 0;
+    float* report = nullptr;   // want_report: into the allocation of `out`, 8-byte aligned behind body and marks; released with `out`
+    int64_t n_report = 0;      // tokens of it (four float32 values each)
     double level_out[2] = {0.0, 1.0};  // levelled: f64(p) and g of the request, as the GPU computed them
     int rc = -1;
     std::string err;
@@ -524,12 +530,32 @@ struct Core {
                                   out_samples, out_marks || out_n_marks, out_marks, out_n_marks, err, err_len, join, nullptr, nullptr,
                                   nullptr, nullptr, limit, out_limit);
     }
+    // ... and with its prosody (include/kokorox_hip.h, "prosody") and the report; `join` and `prosody` may be null here
+    int submit_request_prosody(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
+                               const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
+                               void** out, int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
+                               const kx_join* join, const kx_prosody* prosody, float** out_report, int64_t* out_n_report, char* err,
+                               size_t err_len) {
+        if (join && !join_spec_ok(JoinSpec{join->flags, join->keep_ms, join->pause_ms, join->fade_ms})) {
+            if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: bad join");
+            return KX_ERR_INVALID;
+        }
+        if ((out_report != nullptr) != (out_n_report != nullptr)) {
+            if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null report argument");
+            return KX_ERR_INVALID;
+        }
+        const kx_prosody neutral = {nullptr, nullptr, nullptr, nullptr};
+        return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
+                                  out_samples, out_marks || out_n_marks, out_marks, out_n_marks, err, err_len, join, nullptr, nullptr,
+                                  nullptr, nullptr, nullptr, nullptr, prosody ? prosody : &neutral, out_report, out_n_report);
+    }
     int submit_request_any(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
                            const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
                            void** out, int64_t* out_bytes, int64_t* out_samples, bool want_marks, int64_t** out_marks,
                            int64_t* out_n_marks, char* err, size_t err_len, const kx_join* join = nullptr,
                            const kx_level* level = nullptr, double* out_level = nullptr, const kx_loudness* loudness = nullptr,
-                           double* out_loudness = nullptr, const kx_limit* limit = nullptr, double* out_limit = nullptr) {
+                           double* out_loudness = nullptr, const kx_limit* limit = nullptr, double* out_limit = nullptr,
+                           const kx_prosody* prosody = nullptr, float** out_report = nullptr, int64_t* out_n_report = nullptr) {
         const char* who = "dispatcher_submit_request";
         if (!out || !out_bytes || !out_samples) {
             if (err && err_len) snprintf(err, err_len, "%s: null output argument", who);
@@ -560,7 +586,22 @@ struct Core {
             total += (size_t)chunk_tokens[c];
             min_tokens = chunk_tokens[c] < min_tokens ? chunk_tokens[c] : min_tokens;
         }
+        if (prosody) {  // (the arrays run over the chunks back to back: one row of `total` tokens as far as the rule goes)
+            const ProsodySpec ps{prosody->rate, prosody->frames, prosody->pitch, prosody->energy};
+            const int32_t all = (int32_t)total;
+            if (!prosody_ok(&ps, &all, 1, (int64_t)total)) {
+                if (err && err_len) snprintf(err, err_len, "%s: bad prosody", who);
+                return KX_ERR_INVALID;
+            }
+        }
         Request r;
+        if (prosody) {
+            if (prosody->rate) r.p_rate.assign(prosody->rate, prosody->rate + total);
+            if (prosody->frames) r.p_frames.assign(prosody->frames, prosody->frames + total);
+            if (prosody->pitch) r.p_pitch.assign(prosody->pitch, prosody->pitch + total);
+            if (prosody->energy) r.p_energy.assign(prosody->energy, prosody->energy + total);
+            r.want_report = out_report != nullptr;
+        }
         if (styles) {
             r.kind = 0;
             r.style.assign(styles, styles + (size_t)n_chunks * KX_STYLE_DIM);
@@ -594,6 +635,10 @@ struct Core {
         if (rc == KX_OK && want_marks) {
             *out_marks = r.marks;
             *out_n_marks = r.n_marks;
+        }
+        if (rc == KX_OK && r.want_report) {
+            *out_report = r.report;
+            *out_n_report = r.n_report;
         }
         if (rc == KX_OK && level && out_level) {
             out_level[0] = r.level_out[0];

@@ -164,6 +164,13 @@ void check_limit_call(const HostCall& hc) {
     for (int i = 0; i < hc.n_req_limits; ++i) KX_REQUIRE(limit_spec_ok(hc.req_limits[i]), "infer: bad limit");
 }
 
+void check_prosody_call(const HostCall& hc, const int32_t* lens, int B, int64_t t_stride, float** out_report, int64_t* out_n_report) {
+    KX_REQUIRE((out_report != nullptr) == (out_n_report != nullptr), "infer: null report argument");
+    if (out_report) *out_report = nullptr;
+    KX_REQUIRE(!hc.req_reports || (hc.grouped() && out_report), "infer: reports are for requests (chunks_per_request)");
+    KX_REQUIRE(prosody_ok(hc.prosody, lens, B, t_stride), "infer: bad prosody");
+}
+
 // ---- the meter's tables (include/kokorox_hip.h, "loudness") ---------------------------------------------------------------------
 namespace {
 // (committed as bit patterns, rate codes 0..3: what the library computes with is what the generator rounded)
@@ -289,6 +296,11 @@ OutputBounds output_bounds(const RequestLayout& lay, int B, size_t n_samples, co
             bound.limit_dwords = bound.peak_dwords;
         }
     }
+    if (lay.reports) {  // (the alignment gap and a block in which every request wants the report)
+        KX_REQUIRE(lens, "infer: reports need the token counts");
+        bound.packed_bytes += 8;
+        for (int b = 0; b < B; ++b) bound.packed_bytes += 16 * (size_t)lens[b];
+    }
     return bound;
 }
 
@@ -328,10 +340,30 @@ long close_flac_gaps(char* host, const OutputPlan& plan, const int64_t* lengths,
     return at;
 }
 
+long report_rows(const RequestLayout& lay, const int32_t* lens, int B, std::vector<long>& rep_first, std::vector<long>* rep_count) {
+    KX_REQUIRE(lay.reports && lens && B >= 1 && lay.R >= 1, "plan: bad argument");
+    rep_first.assign((size_t)B, -1);
+    if (rep_count) rep_count->assign((size_t)lay.R, 0);
+    long tokens = 0;
+    int row = 0;
+    for (int r = 0; r < lay.R; ++r) {
+        const int n = lay.chunks_per_request ? lay.chunks_per_request[r] : 1;
+        KX_REQUIRE(n >= 1 && n <= B - row, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
+        for (int b = row; b < row + n && lay.reports[r]; ++b) {
+            KX_REQUIRE(lens[b] >= 1 && lens[b] <= 512, "infer: token count must be 1..512");
+            rep_first[(size_t)b] = tokens;
+            tokens += lens[b];
+            if (rep_count) (*rep_count)[(size_t)r] += lens[b];
+        }
+        row += n;
+    }
+    return tokens;
+}
+
 void build_output_plan(const int* frames, const int* lens, const int* edges, int B, const RequestLayout& lay, OutputPlan& plan) {
     const int R = lay.R;
     KX_REQUIRE(frames && lay.formats && B >= 1 && R >= 1 && (lay.n_format == 1 || lay.n_format == R) &&
-                   (!lay.joins || (edges && (lay.n_join == 1 || lay.n_join == R))) && (lens || (!lay.marks && !lay.joins)) &&
+                   (!lay.joins || (edges && (lay.n_join == 1 || lay.n_join == R))) && (lens || (!lay.marks && !lay.joins && !lay.reports)) &&
                    (!lay.levels || lay.n_level == 1 || lay.n_level == R) && (!lay.loudness || lay.n_loudness == 1 || lay.n_loudness == R) &&
                    (!lay.limits || lay.n_limit == 1 || lay.n_limit == R),
                "plan: bad argument");
@@ -522,6 +554,14 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
             plan.flac_max_bytes = q.out_bytes > plan.flac_max_bytes ? q.out_bytes : plan.flac_max_bytes;
         }
         plan.flac_off = (plan.blocks_end() + 7) & ~7L;
+    }
+    // the prosody report: the tokens of the requests that want it, behind everything else
+    plan.rep_first.clear();
+    plan.rep_count.clear();
+    plan.report_off = plan.n_report = 0;
+    if (lay.reports) {
+        plan.n_report = report_rows(lay, lens, B, plan.rep_first, &plan.rep_count);
+        if (plan.n_report > 0) plan.report_off = (plan.fixed_end() + 7) & ~7L;
     }
 }
 

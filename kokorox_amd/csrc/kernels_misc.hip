@@ -891,6 +891,144 @@ void launch_duration(const float* logits, long bs, int ld, const float* speeds, 
     KX_HIP(hipGetLastError());
 }
 
+// ---- prosody (include/kokorox_hip.h, "prosody") ------------------------------------------------------------------------------
+// duration_kernel restated with the two per-token controls of a call: s / speed is divided once more by rate[t] (x / 1.0f is x),
+// and frames[t] >= 1 replaces whatever the steps before it gave, the model's pinned pattern included.  rate / frames are
+// [B][p_stride] as the ids (either may be null); everything else, the cut at idx_ld and its sticky word too, is duration_kernel's.
+// Launched only for a call that gives one of the two: the plain call keeps the kernel above.
+__global__ __launch_bounds__(512) void prosody_duration_kernel(const float* logits, long bs, int ld, const float* speeds,
+                                                               int n_speed, const int* lens, const int* pinned, int n_pinned,
+                                                               const float* rate, const int* fixed, long p_stride, int* dur,
+                                                               int* frames, int* idx, int idx_ld, unsigned* overflow) {
+    __shared__ int scan[512];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int T = lens[b];
+    int d = 0;
+    if (t < T) {
+        float s = 0.f;
+        for (int c = 0; c < 50; ++c) s += 1.0f / (1.0f + expf(-logits[b * bs + (long)c * ld + t]));
+        s = s / speeds[n_speed > 1 ? b : 0];
+        if (rate) s = s / rate[b * p_stride + t];
+        s = rintf(s);
+        d = !(s >= 1.f) ? 1 : (s > (float)idx_ld ? idx_ld + 1 : (int)s);
+        if (n_pinned > 0) d = pinned[t % n_pinned];
+        if (fixed) {
+            const int want = fixed[b * p_stride + t];  // (0..50: prosody_ok)
+            if (want >= 1) d = want;
+        }
+    }
+    scan[t] = d;
+    __syncthreads();
+    for (int o = 1; o < 512; o <<= 1) {
+        const int v = (t >= o) ? scan[t - o] : 0;
+        __syncthreads();
+        scan[t] += v;
+        __syncthreads();
+    }
+    if (t == 511) {
+        const int total = scan[511];
+        frames[b] = total < idx_ld ? total : idx_ld;
+        if (total > idx_ld && overflow) atomicCAS(overflow, 0u, (unsigned)b + 1u);
+    }
+    if (t < T) {
+        const int end = scan[t] < idx_ld ? scan[t] : idx_ld;
+        const int start = scan[t] - d < idx_ld ? scan[t] - d : idx_ld;
+        dur[b * 512 + t] = end - start;
+        for (int f = start; f < end; ++f) idx[(long)b * idx_ld + f] = t;
+    }
+}
+void launch_prosody_duration(const float* logits, long bs, int ld, const float* speeds, int n_speed, const int* lens,
+                             const int* pinned, int n_pinned, const float* rate, const int* fixed, long p_stride, int* dur,
+                             int* frames, int* idx, int idx_ld, unsigned* overflow, int B, hipStream_t s) {
+    KX_REQUIRE(idx_ld >= 1 && idx_ld <= 50 * 512, "duration: a row of the alignment holds 1 .. 50 x 512 frames");
+    KX_REQUIRE(rate || fixed, "prosody duration: a rate or a frame count per token");
+    hipLaunchKernelGGL(prosody_duration_kernel, dim3(B), dim3(512), 0, s, logits, bs, ld, speeds, n_speed, lens, pinned,
+                       n_pinned, rate, fixed, p_stride, dur, frames, idx, idx_ld, overflow);
+    KX_HIP(hipGetLastError());
+}
+
+// The F0 / N curves of a row shaped by its per-token ratios, in place on the 2F grid, and the per-token report of what came out.
+// curves: row 0 = F0, row 1 = N ([B][2][ld], bs floats from one utterance to the next).  Step j belongs to token idx[b][j >> 1]; its
+// ratio is the 5-step triangle (1 2 3 2 1) / 9 over the steps around it, clamped to the row, accumulated in float64 from +0 in
+// ascending order: five equal ratios of 1 give exactly 1.0, so a neutral span keeps its bits.  F0 is scaled only where it is voiced
+// (> 10) and stays voiced (never at or below 10: the source's decision does not flip); N is scaled everywhere.  pitch / energy are
+// [B][p_stride] as the ids, either may be null (that curve is left as it is).
+// One workgroup per row, lane t = token t.  Phase 1 walks the grid 512 steps at a time (coalesced); phase 2 is the report, a
+// segmented reduction over the alignment: the lane walks its own token's 2 d steps (d <= 50 unless the speed stretches it) in
+// ascending order, which is the float64 chain the definition states, with no cross-lane step whose order would have to be fixed.
+// The row's curves are L2-resident (8 F bytes each) and a bench row has some 1000 steps, so the walk costs less than a second launch.
+// rep_first[b]: index, in tokens, of the row's first token in `report` ([..][4] float32), or -1; report / rep_first may be null.
+// report[t] = {mean of the voiced F0' of the token's steps (+0 when none), their count, mean of N' over its steps, d}.
+__device__ inline double prosody_ratio(const float* rho, const int* idx_row, int j, int last) {
+    double acc = 0.0;
+#pragma unroll
+    for (int k = -2; k <= 2; ++k) {
+        int i = j + k;
+        i = i < 0 ? 0 : (i > last ? last : i);
+        acc += (double)(3 - (k < 0 ? -k : k)) * (double)rho[idx_row[i >> 1]];
+    }
+    return acc / 9.0;
+}
+__global__ __launch_bounds__(512) void prosody_curves_kernel(float* curves, long bs, int ld, const int* frames, const int* lens,
+                                                             const int* dur, const int* idx, int idx_ld, const float* pitch,
+                                                             const float* energy, long p_stride, const long* rep_first, float* report) {
+    __shared__ int scan[512];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int n = 2 * frames[b], T = lens[b];
+    float* f0 = curves + b * bs;
+    float* nn = f0 + ld;
+    const int* idx_row = idx + (long)b * idx_ld;
+    for (int j = t; j < n; j += 512) {
+        if (pitch) {
+            const float f = f0[j];
+            if (f > 10.0f) {
+                const float v = (float)((double)f * prosody_ratio(pitch + b * p_stride, idx_row, j, n - 1));
+                f0[j] = v > 10.0f ? v : __uint_as_float(0x41200001u);
+            }
+        }
+        if (energy) nn[j] = (float)((double)nn[j] * prosody_ratio(energy + b * p_stride, idx_row, j, n - 1));
+    }
+    if (!report || !rep_first || rep_first[b] < 0) return;  // (uniform over the workgroup)
+    const int d = t < T ? dur[b * 512 + t] : 0;
+    scan[t] = d;
+    __syncthreads();  // (also: the row's shaped curves are visible to every lane of the workgroup)
+    for (int o = 1; o < 512; o <<= 1) {
+        const int v = (t >= o) ? scan[t - o] : 0;
+        __syncthreads();
+        scan[t] += v;
+        __syncthreads();
+    }
+    if (t >= T) return;
+    int end = 2 * scan[t], start = 2 * (scan[t] - d);
+    end = end < n ? end : n;  // (sum(dur) == frames: the clamps never bite, and nothing past 2 F is read whatever dur holds)
+    start = start < end ? start : end;
+    double sf = 0.0, sn = 0.0;
+    int voiced = 0;
+    for (int j = start; j < end; ++j) {
+        const float f = f0[j];
+        if (f > 10.0f) {
+            sf += (double)f;
+            voiced += 1;
+        }
+        sn += (double)nn[j];
+    }
+    float4 r;
+    r.x = voiced ? (float)(sf / (double)voiced) : 0.0f;
+    r.y = (float)voiced;
+    r.z = d > 0 ? (float)(sn / (double)(2 * d)) : 0.0f;
+    r.w = (float)d;
+    reinterpret_cast<float4*>(report)[rep_first[b] + t] = r;
+}
+void launch_prosody_curves(float* curves, long bs, int ld, const int* frames, const int* lens, const int* dur, const int* idx,
+                           int idx_ld, const float* pitch, const float* energy, long p_stride, const long* rep_first, float* report,
+                           int B, hipStream_t s) {
+    KX_REQUIRE(pitch || energy || (rep_first && report), "prosody curves: nothing to shape and nothing to report");
+    KX_REQUIRE((reinterpret_cast<uintptr_t>(report) & 15) == 0, "prosody curves: the report is written 16 bytes at a time");
+    hipLaunchKernelGGL(prosody_curves_kernel, dim3(B), dim3(512), 0, s, curves, bs, ld, frames, lens, dur, idx, idx_ld, pitch, energy,
+                       p_stride, rep_first, report);
+    KX_HIP(hipGetLastError());
+}
+
 __global__ void gather_cols_kernel(const float* src, long sbs, int sld, float* dst, long dbs, int dld,
                                    const int* idx, int idx_ld, const int* frames) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y, b = blockIdx.z;

@@ -361,6 +361,16 @@ void lstm_set_test_fault(int on);  // test hook: the two-CU kernel's partner nev
 void launch_duration(const float* logits, long bs, int ld, const float* speeds, int n_speed, const int* lens,
                      const int* pinned, int n_pinned, int* dur, int* frames, int* idx, int idx_ld, unsigned* overflow, int B,
                      hipStream_t s);  // overflow: sticky word, first row cut at idx_ld frames as b + 1 (see duration_kernel)
+// Prosody (include/kokorox_hip.h, "prosody"; kernels_misc.hip).  launch_duration with a call's per-token rate / fixed frame
+// counts ([B][p_stride] on the device, either may be null, not both): only for a call that gives one.
+void launch_prosody_duration(const float* logits, long bs, int ld, const float* speeds, int n_speed, const int* lens,
+                             const int* pinned, int n_pinned, const float* rate, const int* fixed, long p_stride, int* dur,
+                             int* frames, int* idx, int idx_ld, unsigned* overflow, int B, hipStream_t s);
+// The two curves ([B][2][ld]: F0, N; 2 frames[b] steps each) shaped in place by the per-token pitch / energy ratios ([B][p_stride],
+// either may be null), and, where rep_first[b] >= 0, the report of row b's tokens at report + 4 (rep_first[b] + t) (16-byte aligned).
+void launch_prosody_curves(float* curves, long bs, int ld, const int* frames, const int* lens, const int* dur, const int* idx,
+                           int idx_ld, const float* pitch, const float* energy, long p_stride, const long* rep_first, float* report,
+                           int B, hipStream_t s);
 void launch_gather_cols(const float* src, long sbs, int sld, float* dst, long dbs, int dld, int C,
                         const int* idx, int idx_ld, const int* frames, int B, int Fmax, hipStream_t s);
 

@@ -508,8 +508,12 @@ Model::Front Model::front_half(const int64_t* d_ids, int64_t t_stride, const int
     lstm(lstms_.at("predictor.lstm"), t_dcat, t_xl, gxT);
     tap("dur.lstm", t_xl);
     conv(convs_.at("duration_proj"), t_xl, t_logits, ConvOpts{});
-    launch_duration(logits, t_logits.bs, Tp, d_speeds, n_speed, call_.dT, d_pinned_, n_pinned_, dur, call_.dF, idx, idx_ld, d_dur_over_,
-                    B, stream_);
+    if (pros_.durations())  // (a call with a per-token rate or fixed frame counts: the restated kernel; the plain call keeps its own)
+        launch_prosody_duration(logits, t_logits.bs, Tp, d_speeds, n_speed, call_.dT, d_pinned_, n_pinned_, pros_.rate, pros_.frames,
+                                pros_.stride, dur, call_.dF, idx, idx_ld, d_dur_over_, B, stream_);
+    else
+        launch_duration(logits, t_logits.bs, Tp, d_speeds, n_speed, call_.dT, d_pinned_, n_pinned_, dur, call_.dF, idx, idx_ld, d_dur_over_,
+                        B, stream_);
     KX_HIP(hipMemcpyAsync(call_.hF.data(), call_.dF, B * sizeof(int), hipMemcpyDeviceToHost, stream_));
     if (want_edges_) {
         // a call with joins sizes its regions from the used durations of every row's two pad tokens as well: a gather of
@@ -600,6 +604,13 @@ void Model::back_half(const Front& f, Arena& A) {
         if (br == 1) ev_n = record_here();
     }
     wait_here(ev_n);
+    tap("pred.F0.raw", curves.rows(0, 1));
+    tap("pred.N.raw", curves.rows(1, 1));
+    // prosody: the per-token pitch / energy ratios shape the two curves here, before anything reads them (the source below, F0_conv
+    // and N_conv of the decoder), and the report is taken of what they then hold
+    if (pros_.curves() && !call_.dry)
+        launch_prosody_curves(curves.p, curves.bs, curves.ld, call_.dF, call_.dT, call_.d_dur, f.idx, f.idx_ld, pros_.pitch, pros_.energy,
+                              pros_.stride, pros_.rep_first, pros_.report, B, stream_);
     tap("pred.F0", curves.rows(0, 1));
     tap("pred.N", curves.rows(1, 1));
     // --- Generator, source side: harmonic source -> STFT -> noise_convs / noise_res of both stages.  It depends on the

@@ -117,14 +117,14 @@ void Model::infer_host(const int64_t* ids, int64_t t_stride, const int32_t* lens
 void Model::infer_host_ex(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
                           int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out,
                           int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, double* out_levels,
-                          double* out_loudness, double* out_limits) {
+                          double* out_loudness, double* out_limits, float** out_report, int64_t* out_n_report) {
     try {
         infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks,
-                        out_levels, out_loudness, out_limits);
+                        out_levels, out_loudness, out_limits, out_report, out_n_report);
     } catch (const LstmTimeout&) {
         n_rerun_ += 1;
         infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks,
-                        out_levels, out_loudness, out_limits);
+                        out_levels, out_loudness, out_limits, out_report, out_n_report);
     }
     note_clean_forward();
 }
@@ -132,13 +132,14 @@ void Model::infer_host_ex(const int64_t* ids, int64_t t_stride, const int32_t* l
 void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
                             int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out,
                             int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
-                            double* out_levels, double* out_loudness, double* out_limits) {
+                            double* out_levels, double* out_loudness, double* out_limits, float** out_report, int64_t* out_n_report) {
     check_host_call(ids, t_stride, lens, B, speeds, hc, out, out_bytes, out_samples, n_vocab_, n_voices_, d_voices_ != nullptr);
     if (hc.join_call) check_join_call(hc);
     if (hc.req_marks) check_marks_call(hc, out_marks, out_n_marks);
     if (hc.level_call) check_level_call(hc);
     if (hc.loud_call) check_loudness_call(hc);
     if (hc.limit_call) check_limit_call(hc);
+    if (hc.prosody_call) check_prosody_call(hc, lens, B, t_stride, out_report, out_n_report);
     const bool by_voice = hc.by_voice();
     // one way to lay the output out and pack it: a call without chunks_per_request is R = B single-row requests in hc.format
     const RequestLayout layout = hc.layout(B);
@@ -150,6 +151,12 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     for (int i = 0; layout.limits && i < layout.n_limit; ++i) limited = limited || layout.limits[i].mode != LIMIT_NONE;
     const bool loud = layout.loudness != nullptr || limited;
     const bool levels = layout.levels != nullptr || loud;  // (a call with loudness is measured: its peak pass, its levels block)
+    // prosody: the arrays the call gave go up with the ids; the rows of the report are known from the token counts alone
+    const ProsodySpec no_prosody{nullptr, nullptr, nullptr, nullptr};
+    const ProsodySpec& ps = hc.prosody ? *hc.prosody : no_prosody;
+    const long n_report = layout.reports ? report_rows(layout, lens, B, h_rep_first_, nullptr) : 0;
+    ProsodyDev pd;
+    pd.stride = (long)t_stride;
     KX_HIP(hipSetDevice(device));
     // I/O staging lives in its own arena: ids, styles, frames, noise keys, voice picks, audio, packed audio
     int64_t* d_ids;
@@ -213,6 +220,13 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             tables.foff = static_cast<long*>(A.alloc(bound.flac_slots * sizeof(long)));
             slot_cap = bound.flac_slots;
         }
+        const size_t per_token = (size_t)B * t_stride;  // (laid out as the ids)
+        pd.rate = ps.rate ? A.f(per_token) : nullptr;
+        pd.frames = ps.frames ? A.i(per_token) : nullptr;
+        pd.pitch = ps.pitch ? A.f(per_token) : nullptr;
+        pd.energy = ps.energy ? A.f(per_token) : nullptr;
+        pd.rep_first = n_report > 0 ? static_cast<long*>(A.alloc((size_t)B * sizeof(long))) : nullptr;
+        pd.report = n_report > 0 ? A.f((size_t)4 * n_report) : nullptr;
         d_packed = A.alloc(bound.packed_bytes);  // compact output: the requests back to back, then the marks
         return A.f(audio_floats);
     };
@@ -243,6 +257,16 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         // resets it, and nothing may read them in between)
         if (hc.utt_seeds) KX_HIP(hipMemcpyAsync(d_seeds, hc.utt_seeds, (size_t)B * 8, hipMemcpyHostToDevice, stream_));
         if (hc.utt_index) KX_HIP(hipMemcpyAsync(d_uidx, hc.utt_index, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
+        {
+            const size_t per_token = (size_t)B * t_stride * 4;  // bytes of each array
+            if (ps.rate) KX_HIP(hipMemcpyAsync(const_cast<float*>(pd.rate), ps.rate, per_token, hipMemcpyHostToDevice, stream_));
+            if (ps.frames) KX_HIP(hipMemcpyAsync(const_cast<int*>(pd.frames), ps.frames, per_token, hipMemcpyHostToDevice, stream_));
+            if (ps.pitch) KX_HIP(hipMemcpyAsync(const_cast<float*>(pd.pitch), ps.pitch, per_token, hipMemcpyHostToDevice, stream_));
+            if (ps.energy) KX_HIP(hipMemcpyAsync(const_cast<float*>(pd.energy), ps.energy, per_token, hipMemcpyHostToDevice, stream_));
+            if (pd.rep_first)
+                KX_HIP(hipMemcpyAsync(const_cast<long*>(pd.rep_first), h_rep_first_.data(), (size_t)B * sizeof(long), hipMemcpyHostToDevice, stream_));
+        }
+        Restore<ProsodyDev> prosody(pros_, pd);  // (front_half and back_half read it; the plain call finds it empty)
         int64_t need_ld = 0;
         Restore<bool> edges(want_edges_, joins);  // (the forward brings every row's two edge durations back with its frame counts)
         try {
@@ -267,7 +291,9 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             out_samples[r] = plan.req[(size_t)r].n_samples;
             out_bytes[r] = plan.req[(size_t)r].out_bytes;
             if (marks) out_n_marks[r] = plan.count[(size_t)r];
+            if (out_n_report) out_n_report[r] = layout.reports ? plan.rep_count[(size_t)r] : 0;
         }
+        KX_REQUIRE(plan.n_report == n_report, "prosody: the report's rows changed under the call");
         KX_REQUIRE((size_t)plan.peak_dwords() <= peak_cap, "levels: the peak table is too small");
         KX_REQUIRE((size_t)plan.hop_doubles() <= hop_cap, "loudness: the hop table is too small");
         KX_REQUIRE((size_t)plan.truepeak_dwords() <= tpeak_cap, "levels: the true-peak table is too small");
@@ -275,7 +301,10 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         KX_REQUIRE((size_t)plan.flac_slots <= slot_cap, "flac: the frame table is too small");
         launch_output_plan(d_audio, ld, call_.d_dur, call_.dT, plan, tables, d_y, d_packed, stream_);
         const int64_t marks_off = plan.marks_off, n_marks = plan.n_marks;
-        const int64_t total = n_marks > 0 || plan.measured || plan.has_flac() ? plan.end_bytes() : plan.total_bytes;
+        // (the report was staged by the back half, 16-byte aligned; its block is 8-aligned: one more copy on the device, then the one to the host)
+        if (plan.has_report())
+            KX_HIP(hipMemcpyAsync(static_cast<char*>(d_packed) + plan.report_off, pd.report, (size_t)16 * plan.n_report, hipMemcpyDeviceToDevice, stream_));
+        const int64_t total = n_marks > 0 || plan.measured || plan.has_flac() || plan.has_report() ? plan.end_bytes() : plan.total_bytes;
         char* host = static_cast<char*>(host_out_alloc((size_t)(total > 0 ? total : 1)));
         hipError_t e = hipMemcpyAsync(host, d_packed, (size_t)total, hipMemcpyDeviceToHost, stream_);
         if (e == hipSuccess) e = hipStreamSynchronize(stream_);
@@ -301,7 +330,17 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
                 throw;
             }
         }
+        if (hc.out_durations) {  // (the used durations, [B][512] on the device and alive until the next call, as the caller's ids are laid out)
+            std::vector<int> h_dur((size_t)B * 512);
+            e = hipMemcpy(h_dur.data(), call_.d_dur, h_dur.size() * sizeof(int), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) {
+                host_out_free(host);
+                throw Error(3, std::string("infer: D2H copy failed: ") + hipGetErrorString(e));
+            }
+            for (int b = 0; b < B; ++b) memcpy(hc.out_durations + (size_t)b * t_stride, &h_dur[(size_t)b * 512], (size_t)lens[b] * sizeof(int));
+        }
         *out = host;
+        if (out_report) *out_report = plan.has_report() ? reinterpret_cast<float*>(host + plan.report_off) : nullptr;
         if (marks) *out_marks = n_marks > 0 ? reinterpret_cast<int64_t*>(host + marks_off) : nullptr;
         if (plan.measured && out_levels) memcpy(out_levels, host + plan.levels_off, (size_t)R * 16);
         if (plan.limited && out_limits)

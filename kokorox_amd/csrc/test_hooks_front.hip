@@ -187,9 +187,11 @@ int kx_test_attention(int device_id, const float* qkv, const int32_t* lens, int 
     });
 }
 
-int kx_test_alignment(int device_id, const float* logits, int B, int T, const int32_t* lens, const float* speeds, int n_speed,
-                      const int32_t* pinned, int n_pinned, const float* src, int C, int idx_ld, int32_t* dur, int32_t* frames,
-                      int32_t* idx, float* gathered, int Fcap, uint32_t* overflow, char* err, size_t err_len) {
+// the duration head and the gather; rate / fixed [B][T], both null: launch_duration (kx_test_alignment), else launch_prosody_duration
+static int alignment_hook(int device_id, const float* logits, int B, int T, const int32_t* lens, const float* speeds, int n_speed,
+                          const int32_t* pinned, int n_pinned, const float* rate, const int32_t* fixed, const float* src, int C, int idx_ld,
+                          int32_t* dur, int32_t* frames, int32_t* idx, float* gathered, int Fcap, uint32_t* overflow, char* err,
+                          size_t err_len) {
     return guarded_free(err, err_len, [&] {
         check_device(device_id);
         KX_REQUIRE(logits && lens && speeds && src && dur && frames && idx && gathered && overflow && B > 0 && T > 0 && T <= 512 && C > 0 &&
@@ -217,7 +219,22 @@ int kx_test_alignment(int device_id, const float* logits, int B, int T, const in
         KX_HIP(hipMemset(d_dur, 0xA5, (size_t)B * 512 * 4));
         KX_HIP(hipMemset(d_frames, 0xA5, (size_t)B * 4));
         KX_HIP(hipMemset(d_over, 0, sizeof(unsigned)));
-        kx::launch_duration(d_lg, (long)50 * Tp, Tp, d_speed, n_speed, d_len, d_pin, n_pinned, d_dur, d_frames, d_idx, idx_ld, d_over, B, nullptr);
+        if (rate || fixed) {
+            // (entries at or past lens[b] go up as NaN / 0xA5 bytes: the kernel must not use them)
+            std::vector<float> hr((size_t)B * T, POISON);
+            std::vector<int32_t> hf((size_t)B * T, (int32_t)0xA5A5A5A5u);
+            for (int b = 0; b < B; ++b)
+                for (int t = 0; t < lens[b]; ++t) {
+                    const size_t i = (size_t)b * T + t;
+                    KX_REQUIRE(kx::prosody_value_ok(rate ? rate[i] : 1.0f, fixed ? fixed[i] : 0, 1.0f, 1.0f), "test_prosody_durations: bad prosody");
+                    if (rate) hr[i] = rate[i];
+                    if (fixed) hf[i] = fixed[i];
+                }
+            kx::launch_prosody_duration(d_lg, (long)50 * Tp, Tp, d_speed, n_speed, d_len, d_pin, n_pinned, rate ? dm.up(hr.data(), hr.size()) : nullptr,
+                                        fixed ? dm.up(hf.data(), hf.size()) : nullptr, T, d_dur, d_frames, d_idx, idx_ld, d_over, B, nullptr);
+        } else {
+            kx::launch_duration(d_lg, (long)50 * Tp, Tp, d_speed, n_speed, d_len, d_pin, n_pinned, d_dur, d_frames, d_idx, idx_ld, d_over, B, nullptr);
+        }
         KX_HIP(hipDeviceSynchronize());
         KX_HIP(hipMemcpy(dur, d_dur, (size_t)B * 512 * 4, hipMemcpyDeviceToHost));
         KX_HIP(hipMemcpy(frames, d_frames, (size_t)B * 4, hipMemcpyDeviceToHost));
@@ -241,6 +258,77 @@ int kx_test_alignment(int device_id, const float* logits, int B, int T, const in
         KX_HIP(hipDeviceSynchronize());
         unpad_rows(d_g, (size_t)B * C, Fcap, Fp, gathered, "test_alignment: the gather wrote into the row padding");
         guard_untouched(d_g + n_g, "test_alignment: the gather wrote past its tensor");
+    });
+}
+
+int kx_test_alignment(int device_id, const float* logits, int B, int T, const int32_t* lens, const float* speeds, int n_speed,
+                      const int32_t* pinned, int n_pinned, const float* src, int C, int idx_ld, int32_t* dur, int32_t* frames,
+                      int32_t* idx, float* gathered, int Fcap, uint32_t* overflow, char* err, size_t err_len) {
+    return alignment_hook(device_id, logits, B, T, lens, speeds, n_speed, pinned, n_pinned, nullptr, nullptr, src, C, idx_ld, dur, frames, idx,
+                          gathered, Fcap, overflow, err, err_len);
+}
+
+int kx_test_prosody_durations(int device_id, const float* logits, int B, int T, const int32_t* lens, const float* speeds, int n_speed,
+                              const int32_t* pinned, int n_pinned, const float* rate, const int32_t* fixed, const float* src, int C,
+                              int idx_ld, int32_t* dur, int32_t* frames, int32_t* idx, float* gathered, int Fcap, uint32_t* overflow,
+                              char* err, size_t err_len) {
+    if (!rate && !fixed) return guarded_free(err, err_len, [] { throw Error(KX_ERR_INVALID, "test_prosody_durations: a rate or a frame count per token"); });
+    return alignment_hook(device_id, logits, B, T, lens, speeds, n_speed, pinned, n_pinned, rate, fixed, src, C, idx_ld, dur, frames, idx,
+                          gathered, Fcap, overflow, err, err_len);
+}
+
+int kx_test_prosody_curves(int device_id, const float* curves, const int32_t* frames, int B, int Fcap, const int32_t* lens, int T,
+                           const int32_t* idx, int idx_ld, const int32_t* dur, const float* pitch, const float* energy, float* shaped,
+                           float* report, char* err, size_t err_len) {
+    return guarded_free(err, err_len, [&] {
+        check_device(device_id);
+        KX_REQUIRE(curves && frames && lens && idx && dur && shaped && B > 0 && Fcap >= 1 && T > 0 && T <= 512 && idx_ld >= Fcap &&
+                       idx_ld <= 50 * 512 && (pitch || energy || report),
+                   "test_prosody_curves: bad argument");
+        check_lens(lens, B, T, "test_prosody_curves: lens out of range");
+        // what the kernel indexes with is checked here: frames inside the row, every index a token of its utterance, durations that
+        // add up to the frames
+        long n_tokens = 0;
+        std::vector<long> first((size_t)B);
+        std::vector<int32_t> dur512((size_t)B * 512, (int32_t)0xA5A5A5A5u);
+        std::vector<float> hp((size_t)B * T, POISON), he((size_t)B * T, POISON);
+        for (int b = 0; b < B; ++b) {
+            KX_REQUIRE(frames[b] >= 1 && frames[b] <= Fcap, "test_prosody_curves: frames out of range");
+            long sum = 0;
+            for (int t = 0; t < lens[b]; ++t) {
+                const size_t i = (size_t)b * T + t;
+                KX_REQUIRE(dur[i] >= 0, "test_prosody_curves: negative duration");
+                KX_REQUIRE(kx::prosody_value_ok(1.0f, 0, pitch ? pitch[i] : 1.0f, energy ? energy[i] : 1.0f), "test_prosody_curves: bad prosody");
+                sum += dur[i];
+                dur512[(size_t)b * 512 + t] = dur[i];
+                if (pitch) hp[i] = pitch[i];
+                if (energy) he[i] = energy[i];
+            }
+            KX_REQUIRE(sum == frames[b], "test_prosody_curves: durations do not add up to the frames");
+            for (int f = 0; f < frames[b]; ++f)
+                KX_REQUIRE(idx[(size_t)b * idx_ld + f] >= 0 && idx[(size_t)b * idx_ld + f] < lens[b], "test_prosody_curves: an alignment index outside its utterance");
+            first[(size_t)b] = n_tokens;
+            n_tokens += lens[b];
+        }
+        KX_HIP(hipSetDevice(device_id));
+        DevMem dm;
+        // the curves on the model's padded rows, as the caller gave them (its poison past 2 frames[b] comes back with `shaped`); the
+        // row padding holds the sentinel and the guard stands behind the tensor
+        const int n2 = 2 * Fcap, ld = pad32(n2);
+        const std::vector<float> rows = padded_rows(curves, B, 2, n2, ld, SENTINEL);
+        float* d_curves = guarded_upload(dm, rows);
+        float* d_report = report ? guarded_buffer(dm, (size_t)4 * n_tokens, SENTINEL) : nullptr;
+        kx::launch_prosody_curves(d_curves, (long)2 * ld, ld, dm.up(frames, B), dm.up(lens, B), dm.up(dur512.data(), dur512.size()),
+                                  dm.up(idx, (size_t)B * idx_ld), idx_ld, pitch ? dm.up(hp.data(), hp.size()) : nullptr,
+                                  energy ? dm.up(he.data(), he.size()) : nullptr, T, report ? dm.up(first.data(), first.size()) : nullptr, d_report, B,
+                                  nullptr);
+        KX_HIP(hipDeviceSynchronize());
+        unpad_rows(d_curves, (size_t)B * 2, n2, ld, shaped, "test_prosody_curves: the kernel wrote into the row padding");
+        guard_untouched(d_curves + rows.size(), "test_prosody_curves: the kernel wrote past the curves");
+        if (report) {
+            KX_HIP(hipMemcpy(report, d_report, (size_t)16 * n_tokens, hipMemcpyDeviceToHost));
+            guard_untouched(d_report + (size_t)4 * n_tokens, "test_prosody_curves: the kernel wrote past the report");
+        }
     });
 }
 

@@ -160,6 +160,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                             vp, vp, vp, i32, vp, i32, vp]),
         "kx_dispatcher_submit_request_limited": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
                                                        C.POINTER(i64), vp, vp, vp, vp, vp, cp, sz]),
+        "kx_infer_prosody": (i32, [vp, vp, i64, vp, i32, vp, vp, i32, u64, u32, C.POINTER(C.POINTER(f32)), vp, vp, vp]),
+        "kx_infer_requests_prosody": (i32, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, u64, u32, vp, i32, C.POINTER(vp), vp, vp,
+                                            vp, vp, vp, i32, vp, vp, vp]),
+        "kx_dispatcher_submit_request_prosody": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
+                                                       C.POINTER(i64), vp, vp, vp, vp, vp, vp, cp, sz]),
         "kx_dispatcher_create": (vp, [vp, i32, i32, i32, cp, sz]),
         "kx_dispatcher_create_warm": (vp, [vp, i32, i32, i32, i32, i32, cp, sz]),
         "kx_dispatcher_submit": (i32, [vp, vp, i32, vp, f32, u64, C.POINTER(C.POINTER(f32)), C.POINTER(i64), cp, sz]),
@@ -209,6 +214,8 @@ def _test_signatures():
                                            vp, vp, vp, i64, vp, vp, vp, vp, cp, sz]),
         "kx_test_lstm_ragged": (i32, [i32, vp, vp, i32, i32, i32] + [vp] * 8 + [i32, i32, u32, vp, cp, sz]),
         "kx_test_alignment": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, cp, sz]),
+        "kx_test_prosody_durations": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, cp, sz]),
+        "kx_test_prosody_curves": (i32, [i32, vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, cp, sz]),
         "kx_test_embed": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, cp, sz]),
         "kx_test_style_fc": (i32, [i32, vp, i32, vp, vp, vp, vp, i32, vp, cp, sz]),
         "kx_test_rows": (i32, [i32, vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, cp, sz]),
@@ -247,7 +254,7 @@ ABI_SYMBOLS = [
     "kx_free_audio", "kx_infer_device", "kx_sync", "kx_set_pinned_durations", "kx_warmup", "kx_arena_bytes", "kx_call_times", "kx_model_status", "kx_model_info", "kx_dispatcher_health", "kx_set_utterance_base", "kx_set_lanes",
     "kx_set_conv_mode", "kx_get_conv_mode", "kx_set_stft_variant", "kx_get_stft_variant",
     "kx_profile_enable", "kx_profile_read", "kx_profile_detail", "kx_profile_aux", "kx_diag_enable", "kx_diag_count", "kx_diag_get", "kx_set_act_prescale", "kx_set_voice_table", "kx_infer_voices",
-    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_infer_requests_levelled", "kx_dispatcher_submit_request_levelled", "kx_loudness_filter", "kx_truepeak_filter", "kx_infer_requests_loudness", "kx_dispatcher_submit_request_loudness", "kx_limit_filter", "kx_infer_requests_limited", "kx_dispatcher_submit_request_limited", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
+    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_infer_requests_levelled", "kx_dispatcher_submit_request_levelled", "kx_loudness_filter", "kx_truepeak_filter", "kx_infer_requests_loudness", "kx_dispatcher_submit_request_loudness", "kx_limit_filter", "kx_infer_requests_limited", "kx_dispatcher_submit_request_limited", "kx_infer_prosody", "kx_infer_requests_prosody", "kx_dispatcher_submit_request_prosody", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
     "kx_dispatcher_stats", "kx_dispatcher_failures", "kx_dispatcher_destroy", "kx_debug_tap",
 ]
 
@@ -258,6 +265,35 @@ def _ptr(a: Optional[np.ndarray]):
 
 def _f32(a) -> Optional[np.ndarray]:
     return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+
+
+class Prosody(C.Structure):
+    """kx_prosody (include/kokorox_hip.h, "prosody"): four pointers, each null or [B, t_stride] laid out as the ids."""
+    _fields_ = [("rate", C.c_void_p), ("frames", C.c_void_p), ("pitch", C.c_void_p), ("energy", C.c_void_p)]
+
+
+def prosody_arrays(prosody, lens, stride):
+    """`prosody` = (rate, frames, pitch, energy), each None or one sequence per row (its tokens' values), as the [B, stride] arrays
+    the library takes -- neutral (1, 0, 1, 1) where a row is shorter than the stride -- and the kx_prosody over them.  Returns
+    (struct or None, the arrays): keep the arrays alive for as long as the struct is used."""
+    if prosody is None:
+        return None, ()
+    if len(prosody) != 4:
+        raise ValueError("prosody: (rate, frames, pitch, energy), each None or one sequence per row")
+    arrs = []
+    for k, rows in enumerate(prosody):
+        if rows is None:
+            arrs.append(None)
+            continue
+        if len(rows) != len(lens):
+            raise ValueError("prosody: one sequence per row")
+        a = np.zeros((len(lens), stride), np.int32) if k == 1 else np.ones((len(lens), stride), np.float32)
+        for b, row in enumerate(rows):
+            if len(row) != int(lens[b]):
+                raise ValueError("prosody: one value per token")
+            a[b, : len(row)] = np.asarray(row, dtype=a.dtype)
+        arrs.append(a)
+    return Prosody(*[None if a is None else a.ctypes.data for a in arrs]), tuple(arrs)
 
 
 def join_specs(joins, n=None) -> np.ndarray:
@@ -491,6 +527,46 @@ class HipKoko:
             o += int(out_lens[b])
         return res
 
+    def infer_prosody(self, tokens, styles, speeds, prosody=None, seed: int = 0, flags: int = 0):
+        """infer_batch with per-token prosody (kx_infer_prosody; the definition is in include/kokorox_hip.h, "prosody", the numpy form
+        voices.prosody_durations / voices.shape_curves): `prosody` = (rate, frames, pitch, energy), each None or one sequence per
+        utterance with a value per token; None = no prosody.  Returns (waveforms, durations): the list infer_batch returns and one
+        int32 array per utterance, the frames each token was given."""
+        ids, lens = self._ids_lens(tokens)
+        B = len(tokens)
+        st = _f32(np.asarray(styles, dtype=np.float32).reshape(B, STYLE_DIM))
+        sp = _f32(np.asarray(speeds, dtype=np.float32).reshape(-1))
+        ps, keep = prosody_arrays(prosody, lens, ids.shape[1])
+        out = C.POINTER(C.c_float)()
+        out_lens = np.zeros(max(B, 1), dtype=np.int64)
+        dur = np.zeros(ids.shape, dtype=np.int32)
+        rc = self._lib.kx_infer_prosody(self._h, _ptr(ids), ids.shape[1], _ptr(lens), B, _ptr(st), _ptr(sp), sp.shape[0], seed, flags,
+                                        C.byref(out), _ptr(out_lens), None if ps is None else C.addressof(ps), _ptr(dur))
+        del keep
+        self._check(rc)
+        try:
+            total = int(out_lens[:B].sum())
+            flat = np.ctypeslib.as_array(out, shape=(max(total, 1),))[:total].copy()
+        finally:
+            self._lib.kx_free_audio(out)
+        cuts = np.cumsum(out_lens[:B])[:-1]
+        return [w.copy() for w in np.split(flat, cuts)], [dur[b, : int(lens[b])].copy() for b in range(B)]
+
+    def infer_requests_prosody(self, tokens, chunks_per_request, prosody=None, joins=None, styles=None, voice_ids=None, weights=None,
+                               speeds=(1.0,), seed: int = 0, flags: int = 0, fmt=0, marks: bool = False, report: bool = True,
+                               with_samples: bool = False):
+        """infer_requests with per-token prosody and its report (kx_infer_requests_prosody): `prosody` as infer_prosody, one sequence
+        per chunk; `joins` as infer_requests_joined, or None.  Returns (bodies, report) with report one float32 array [tokens, 4] per
+        request = (mean voiced F0, voiced steps, mean N, frames) of every token, chunk after chunk (voices.prosody_report);
+        marks=True: (bodies, marks, report); report=False leaves it out.  with_samples: out_samples as a last entry."""
+        j = None if joins is None else join_specs(joins)
+        res, mk, nsamp, rep = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, marks, j,
+                                                   prosody=(prosody, report))
+        out = (res, mk) if marks else (res,)
+        out = out + (rep,) if report else out
+        out = out + (nsamp,) if with_samples else out
+        return out if len(out) > 1 else out[0]
+
     # -- SURVEY 8f ranks 2 and 3: device voice table, packed output -----------------------------
     def set_voice_table(self, table: np.ndarray):
         """table [n_voices, 511, 1, 256] (or [n, 511, 256]) as built by load_voices / hf_cache.rs:284-309."""
@@ -625,7 +701,7 @@ class HipKoko:
         return out + (nsamp,) if with_samples else out
 
     def _infer_requests(self, tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, want_marks, joins=None,
-                        levels=None, loudness=None, limits=None):
+                        levels=None, loudness=None, limits=None, prosody=None):
         ids, lens = self._ids_lens(tokens)
         B = len(tokens)
         cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32).reshape(-1)
@@ -647,7 +723,24 @@ class HipKoko:
         marks = None
         if want_marks:
             mk, n_mk = C.c_void_p(), np.zeros(max(R, 1), np.int64)
-        if limits is not None:
+        report = None
+        if prosody is not None:  # (prosody, want the report)
+            ps, keep = prosody_arrays(prosody[0], lens, ids.shape[1])
+            rp, n_rp = C.c_void_p(), np.zeros(max(R, 1), np.int64)
+            rc = self._lib.kx_infer_requests_prosody(*args, C.byref(mk) if want_marks else None, _ptr(n_mk) if want_marks else None,
+                                                     _ptr(joins), 0 if joins is None else joins.shape[0],
+                                                     None if ps is None else C.addressof(ps), C.byref(rp) if prosody[1] else None,
+                                                     _ptr(n_rp) if prosody[1] else None)
+            del keep
+            self._check(rc)
+            if prosody[1]:  # (it lives in the buffer of `out`: read before it is released)
+                n_tok = int(n_rp[:R].sum())
+                if n_tok and ((rp.value or 0) % 8 != 0 or not (out.value <= (rp.value or 0))):
+                    self._lib.kx_free_packed(out)
+                    raise KokoroxHipError(3, "the report is not 8-byte aligned inside the packed buffer")
+                flat_r = np.frombuffer(C.string_at(rp, 16 * n_tok) if n_tok else b"", dtype=np.float32).reshape(-1, 4).copy()
+                report = [x.copy() for x in np.split(flat_r, np.cumsum(n_rp[:R])[:-1])]
+        elif limits is not None:
             out_lv = np.zeros((max(R, 1), 5), np.float64)
             self._check(self._lib.kx_infer_requests_limited(*args, C.byref(mk) if want_marks else None, _ptr(n_mk) if want_marks else None,
                                                             _ptr(joins), 0 if joins is None else joins.shape[0], _ptr(limits),
@@ -686,6 +779,8 @@ class HipKoko:
             res.append(_decode_packed(part, int(fm[r if fm.shape[0] > 1 else 0])))
         if levels is not None or loudness is not None or limits is not None:
             return res, marks, [int(v) for v in nsamp[:R]], out_lv[:R]
+        if prosody is not None:
+            return res, marks, [int(v) for v in nsamp[:R]], report
         return res, marks, [int(v) for v in nsamp[:R]]
 
     def infer_device(self, d_ids: int, t_stride: int, lens_host: np.ndarray, d_styles: int, speeds_host: np.ndarray,
@@ -900,7 +995,8 @@ class Dispatcher:
         return arr.reshape(-1, 2) if fmt == 1 else arr
 
     def submit_request(self, chunks: Sequence[Sequence[int]], styles=None, voices=None, speed: float = 1.0, seed: int = 0,
-                       fmt: int = 0, marks: bool = False, join=None, level=None, loudness=None, limit=None):
+                       fmt: int = 0, marks: bool = False, join=None, level=None, loudness=None, limit=None, prosody=None,
+                       report: bool = False):
         """A request of 1 .. max_batch chunks (kx_dispatcher_submit_request): `chunks` = the 0-wrapped id lists; `styles` = one
         256-float row per chunk, OR `voices` as in submit_ex (one voice spec for the request); `fmt` = a format word (a PACK_*
         form, optionally | PACK_RATE_*).  Returns what HipKoko.infer_requests returns for one request: an array (forms 0..2, 8, 9)
@@ -912,7 +1008,10 @@ class Dispatcher:
         loudness = (mode, target_lufs, peak) (kx_dispatcher_submit_request_loudness): the request's loudness measured and set as
         HipKoko.infer_requests_loudness does; the result then ends with four float64 values, p, g, I and n_g.
         limit = (mode, gain, target_lufs, peak) (kx_dispatcher_submit_request_limited): the request driven and peak-limited as
-        HipKoko.infer_requests_limited does; the result then ends with five float64 values, p, g, I, n_g and r."""
+        HipKoko.infer_requests_limited does; the result then ends with five float64 values, p, g, I, n_g and r.
+        prosody = (rate, frames, pitch, energy), each None or one sequence per chunk (kx_dispatcher_submit_request_prosody), and / or
+        report=True: the request shaped as HipKoko.infer_requests_prosody shapes it; with report=True the result ends with the
+        request's float32 report [tokens, 4].  Not together with level, loudness or limit."""
         lens = np.array([len(c) for c in chunks], dtype=np.int32)
         a = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.int64).reshape(-1) for c in chunks])
                                  if len(chunks) else np.zeros(0, np.int64))
@@ -941,7 +1040,18 @@ class Dispatcher:
         if (loudness is not None) + (level is not None) + (limit is not None) > 1:
             raise ValueError("submit_request: a request has a level or a loudness, not both" if limit is None else
                              "submit_request: a request has a level, a loudness or a limit, not two of them")
-        if limit is not None:
+        rp, n_rp = C.c_void_p(), C.c_int64(0)
+        if prosody is not None or report:
+            if level is not None or loudness is not None or limit is not None:
+                raise ValueError("submit_request: prosody does not go with a level, a loudness or a limit")
+            j = None if join is None else join_specs(join, 1)
+            flat = None if prosody is None else tuple(None if x is None else [np.concatenate([np.asarray(c).reshape(-1) for c in x])] for x in prosody)
+            ps, keep = prosody_arrays(flat, [int(lens.sum())], int(lens.sum()))
+            rc = self._lib.kx_dispatcher_submit_request_prosody(*args, C.byref(mk) if marks else None, C.byref(n_mk) if marks else None,
+                                                                _ptr(j), None if ps is None else C.addressof(ps),
+                                                                C.byref(rp) if report else None, C.byref(n_rp) if report else None, err, len(err))
+            del keep
+        elif limit is not None:
             j = None if join is None else join_specs(join, 1)
             rc = self._lib.kx_dispatcher_submit_request_limited(*args, C.byref(mk) if marks else None, C.byref(n_mk) if marks else None,
                                                                 _ptr(j), _ptr(limit_specs(limit, 1)), _ptr(lm_out), err, len(err))
@@ -969,12 +1079,17 @@ class Dispatcher:
                 if (mk.value or 0) % 8 != 0 or (mk.value or 0) < out.value + nb.value:
                     raise KokoroxHipError(3, "marks are not 8-byte aligned behind the body")
                 m = np.frombuffer(C.string_at(mk, 8 * n_mk.value), dtype=np.int64).copy()
+            if report:  # (inside the allocation of `out` as well)
+                if n_rp.value and ((rp.value or 0) % 8 != 0 or (rp.value or 0) < out.value + nb.value):
+                    raise KokoroxHipError(3, "the report is not 8-byte aligned behind the body")
+                rep_out = np.frombuffer(C.string_at(rp, 16 * n_rp.value) if n_rp.value else b"", dtype=np.float32).reshape(-1, 4).copy()
         finally:
             self._lib.kx_free_packed(out)
         res = (_decode_packed(raw, fmt), m) if marks else (_decode_packed(raw, fmt),)
         res = res + (lv_out,) if level is not None else res
         res = res + (ld_out,) if loudness is not None else res
         res = res + (lm_out,) if limit is not None else res
+        res = res + (rep_out,) if report else res
         return res if len(res) > 1 else res[0]
 
     def stats(self):
@@ -1246,6 +1361,53 @@ def alignment(logits, lens, speeds, src, pinned=None, idx_ld=None, Fcap=None, de
     _err_call(lib.kx_test_alignment, device, _ptr(logits), B, T, _ptr(ln), _ptr(sp), len(sp), _ptr(pin), 0 if pin is None else len(pin),
               _ptr(src), C_, idx_ld, _ptr(dur), _ptr(frames), _ptr(idx), _ptr(g), Fcap, _ptr(over))
     return dur, frames, idx, g, int(over[0])
+
+
+def prosody_durations(logits, lens, speeds, src, rate=None, frames=None, pinned=None, idx_ld=None, Fcap=None, device=0):
+    """`alignment` on the prosody duration kernel (kx_test_prosody_durations): rate / frames [B,T] per token, either may be None (not
+    both).  Returns what `alignment` returns."""
+    lib = load_test_library()
+    logits, src = _f32(logits), _f32(src)
+    B, n50, T = logits.shape
+    assert n50 == 50 and src.shape[0] == B and src.shape[2] == T
+    C_ = src.shape[1]
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    sp = np.ascontiguousarray(speeds, dtype=np.float32).reshape(-1)
+    pin = None if pinned is None else np.ascontiguousarray(pinned, dtype=np.int32)
+    rt = None if rate is None else np.ascontiguousarray(rate, dtype=np.float32).reshape(B, T)
+    fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32).reshape(B, T)
+    idx_ld = 50 * T if idx_ld is None else idx_ld
+    Fcap = idx_ld if Fcap is None else Fcap
+    dur = np.zeros((B, 512), dtype=np.int32)
+    n_frames = np.zeros(B, dtype=np.int32)
+    idx = np.zeros((B, idx_ld), dtype=np.int32)
+    g = np.zeros((B, C_, Fcap), dtype=np.float32)
+    over = np.zeros(1, dtype=np.uint32)
+    _err_call(lib.kx_test_prosody_durations, device, _ptr(logits), B, T, _ptr(ln), _ptr(sp), len(sp), _ptr(pin), 0 if pin is None else len(pin),
+              _ptr(rt), _ptr(fr), _ptr(src), C_, idx_ld, _ptr(dur), _ptr(n_frames), _ptr(idx), _ptr(g), Fcap, _ptr(over))
+    return dur, n_frames, idx, g, int(over[0])
+
+
+def prosody_curves(curves, frames, lens, idx, dur, pitch=None, energy=None, report=True, device=0):
+    """The curve and report kernel (kx_test_prosody_curves): curves [B,2,2 Fcap] (F0, N), frames [B], lens [B], idx [B,idx_ld],
+    dur [B,T], pitch / energy [B,T] or None -> (shaped [B,2,2 Fcap], report [sum(lens),4] or None)."""
+    lib = load_test_library()
+    curves = _f32(curves)
+    B, two, n2 = curves.shape
+    assert two == 2 and n2 % 2 == 0
+    fr = np.ascontiguousarray(frames, dtype=np.int32)
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    ix = np.ascontiguousarray(idx, dtype=np.int32)
+    du = np.ascontiguousarray(dur, dtype=np.int32)
+    T = du.shape[1]
+    assert ix.shape[0] == B and du.shape[0] == B
+    pt = None if pitch is None else np.ascontiguousarray(pitch, dtype=np.float32).reshape(B, T)
+    en = None if energy is None else np.ascontiguousarray(energy, dtype=np.float32).reshape(B, T)
+    shaped = np.zeros_like(curves)
+    rep = np.zeros((int(ln.sum()), 4), dtype=np.float32) if report else None
+    _err_call(lib.kx_test_prosody_curves, device, _ptr(curves), _ptr(fr), B, n2 // 2, _ptr(ln), T, _ptr(ix), ix.shape[1], _ptr(du), _ptr(pt),
+              _ptr(en), _ptr(shaped), _ptr(rep))
+    return shaped, rep
 
 
 def embed(ids, lens, T, text_table, word, type0, pos, device=0):

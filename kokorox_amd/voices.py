@@ -840,3 +840,102 @@ def tts_request(model, styles: Dict[str, np.ndarray], style_name: str, chunk_tok
                                            seed=seed, fmt=fmt)[0]
     return model.infer_requests(toks, [len(toks)], styles=np.asarray(rows, dtype=np.float32), speeds=[float(speed)], seed=seed,
                                 fmt=fmt)[0]
+
+
+# ---- prosody (include/kokorox_hip.h, "prosody"): the numpy form of the per-token controls and of the report -------------------------
+PROSODY_MAX_FRAMES = 50
+_F0_FLOOR = np.float32(10.0)
+_F0_ABOVE_FLOOR = np.array([0x41200001], dtype=np.uint32).view(np.float32)[0]  # the float above 10
+
+
+def semitones(p) -> np.float32:
+    """The pitch ratio of p semitones, float32(2 ** (p / 12)): what a caller puts into `pitch` (the library takes ratios)."""
+    return np.float32(2.0 ** (float(p) / 12.0))
+
+
+def prosody_ok(rate=None, frames=None, pitch=None, energy=None) -> bool:
+    """The validity rule of kx_prosody over the given values: 0.25 <= rate <= 4, 0 <= frames <= 50, 0.25 <= pitch <= 4,
+    0 <= energy <= 4; a NaN fails every rule; None is neutral."""
+    def inside(a, lo, hi):
+        a = np.asarray(a, dtype=np.float32)
+        return bool(np.all((a >= np.float32(lo)) & (a <= np.float32(hi))))
+    ok = rate is None or inside(rate, 0.25, 4)
+    ok = ok and (pitch is None or inside(pitch, 0.25, 4))
+    ok = ok and (energy is None or inside(energy, 0, 4))
+    if frames is not None:
+        f = np.asarray(frames, dtype=np.int64)
+        ok = ok and bool(np.all((f >= 0) & (f <= PROSODY_MAX_FRAMES)))
+    return ok
+
+
+def prosody_durations(s, rate=None, frames=None, pinned=None, idx_ld=None) -> np.ndarray:
+    """The USED durations of one row from its float32 values s[t] = (sum of sigmoids) / speed: divided by rate[t] in float32,
+    rounded half to even, at least 1, the model's pinned pattern over it, frames[t] >= 1 over that, and the row cut at idx_ld frames
+    (default 50 per token) as the duration kernel cuts it."""
+    s = np.asarray(s, dtype=np.float32).reshape(-1)
+    T = s.shape[0]
+    idx_ld = 50 * T if idx_ld is None else int(idx_ld)
+    if rate is not None:
+        s = (s / np.asarray(rate, dtype=np.float32).reshape(-1)).astype(np.float32)
+    r = np.rint(s)
+    d = np.where(~(r >= np.float32(1)), 1, np.where(r > np.float32(idx_ld), idx_ld + 1, np.nan_to_num(r))).astype(np.int64)
+    if pinned is not None and len(pinned):
+        d = np.asarray(pinned, dtype=np.int64)[np.arange(T) % len(pinned)]
+    if frames is not None:
+        f = np.asarray(frames, dtype=np.int64).reshape(-1)
+        d = np.where(f >= 1, f, d)
+    scan = np.cumsum(d)
+    return (np.minimum(scan, idx_ld) - np.minimum(scan - d, idx_ld)).astype(np.int32)
+
+
+def _prosody_ratio(rho, step_token) -> np.ndarray:
+    """r[j] of the definition: the 5-step triangle over the per-token ratio, clamped to the row, float64 in ascending k."""
+    n = step_token.shape[0]
+    rho = np.asarray(rho, dtype=np.float32).astype(np.float64)
+    j = np.arange(n)
+    acc = np.zeros(n, dtype=np.float64)
+    for k, w in zip(range(-2, 3), (1.0, 2.0, 3.0, 2.0, 1.0)):
+        acc = acc + np.float64(w) * rho[step_token[np.clip(j + k, 0, n - 1)]]
+    return acc / np.float64(9.0)
+
+
+def shape_curves(f0, n, durations, pitch=None, energy=None):
+    """One row's F0 and N curves (2 F steps each, F = sum(durations)) shaped by the per-token ratios; None leaves a curve as it is.
+    Returns (F0', N') as float32.  Unvoiced steps (not > 10, NaN included) keep their bits; a voiced step stays above 10."""
+    f0 = np.asarray(f0, dtype=np.float32).reshape(-1)
+    n = np.asarray(n, dtype=np.float32).reshape(-1)
+    d = np.asarray(durations, dtype=np.int64).reshape(-1)
+    steps = 2 * int(d.sum())
+    assert f0.shape[0] == steps and n.shape[0] == steps, "curves: 2 steps per frame"
+    step_token = np.repeat(np.arange(d.shape[0]), 2 * d)
+    f0s, ns = f0.copy(), n.copy()
+    if pitch is not None and steps:
+        with np.errstate(invalid="ignore", over="ignore"):
+            voiced = f0 > _F0_FLOOR
+            v = (f0.astype(np.float64) * _prosody_ratio(pitch, step_token)).astype(np.float32)
+            f0s = np.where(voiced, np.where(v > _F0_FLOOR, v, _F0_ABOVE_FLOOR), f0).astype(np.float32)
+    if energy is not None and steps:
+        with np.errstate(invalid="ignore", over="ignore"):
+            ns = (n.astype(np.float64) * _prosody_ratio(energy, step_token)).astype(np.float32)
+    return f0s, ns
+
+
+def prosody_report(f0s, ns, durations) -> np.ndarray:
+    """The report of one row, [tokens, 4] float32: the mean of the voiced (> 10) steps of F0' of every token (+0 when none), their
+    count, the mean of N' over its steps (+0 when it has none), and its frames.  Float64 sums in ascending order, rounded once."""
+    f0s = np.asarray(f0s, dtype=np.float32).reshape(-1)
+    ns = np.asarray(ns, dtype=np.float32).reshape(-1)
+    d = np.asarray(durations, dtype=np.int64).reshape(-1)
+    out = np.zeros((d.shape[0], 4), dtype=np.float32)
+    at = 0
+    for t, dt in enumerate(d):
+        sf, sn, voiced = 0.0, 0.0, 0
+        for j in range(2 * at, 2 * (at + int(dt))):
+            if f0s[j] > _F0_FLOOR:
+                sf += float(f0s[j])
+                voiced += 1
+            sn += float(ns[j])
+        with np.errstate(invalid="ignore", over="ignore"):
+            out[t] = (np.float32(sf / voiced) if voiced else 0.0, voiced, np.float32(sn / (2 * int(dt))) if dt else 0.0, dt)
+        at += int(dt)
+    return out

@@ -23,6 +23,9 @@ the command line; an optional second argument is the batch (1 = one utterance). 
     '12' / '0x30c'       kx_infer_requests in form 12 (FLAC; '0x30c' = at 48 kHz), every row a request of its own: flac_frames_kernel,
                          flac_layout_kernel and flac_gather_kernel in the packer's place (pack_requests_kernel does not show: no
                          request has a region for it); prints the bodies' bytes beside the PCM16 bytes of the same samples;
+    a word and 'r'       ('2r') kx_infer_requests_prosody with a rate, a pitch and an energy per token and the report, every row a
+                         request of its own: prosody_duration_kernel in duration_kernel's place (the pinned pattern still sets the
+                         frames) and prosody_curves_kernel behind the F0 / N predictors;
     a word and 'g'       ('2g') the same grouping without joins (kx_infer_requests_marks): the plain kernels on the same batch.
 Meant to run under the profiler, one mode per run (kernel trace only, no counters in the same run):
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o t -- python tools/pack_profile.py p2
@@ -76,6 +79,14 @@ for it in range(3):
         assert lm.shape == (B, 5) and (lm[:, 4] < 1.0).all() and (lm[:, 4] > 0.24).all()
         if it == 2:
             print("limits of the first request: p %.6g g %.6g I %.6f LUFS n_g %d r %.6g" % tuple(lm[0]))
+    elif which.endswith("r"):
+        word = int(which[:-1], 0)
+        rng = np.random.default_rng(it)
+        pros = tuple([rng.choice(vals, size=len(t)).astype(np.float32) for t in toks] for vals in ([0.8, 1.0, 1.25], [0.7, 1.0, 1.4], [0.5, 1.0, 1.5]))
+        out, rep = m.infer_requests_prosody(toks, [1] * B, (pros[0], None, pros[1], pros[2]), styles=rows, fmt=word)
+        assert all(k.shape == (130, 4) and int(k[:, 3].sum()) == 422 for k in rep)
+        if it == 2:
+            print("report of the first request: mean voiced F0 %.3f Hz over %d steps" % (float((rep[0][:, 0] * rep[0][:, 1]).sum() / max(rep[0][:, 1].sum(), 1)), int(rep[0][:, 1].sum())))
     elif which.endswith("m"):
         word = int(which[:-1], 0)
         out, marks = m.infer_requests_marks(toks, [1] * B, styles=rows, fmt=word)
