@@ -293,7 +293,7 @@ int kx_infer_prosody(kx_model* m, const int64_t* ids, int64_t t_stride, const in
         hc.out_durations = out_durations;
         void* p = nullptr;
         std::vector<int64_t> bytes(B > 0 ? B : 1);
-        M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, &p, bytes.data(), out_lens);
+        M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, Model::HostResults{&p, bytes.data(), out_lens});
         *out = static_cast<float*>(p);
     });
 }
@@ -315,7 +315,7 @@ int kx_infer_voices(kx_model* m, const int64_t* ids, int64_t t_stride, const int
         hc.weights = weights;
         hc.max_mix = max_mix;
         hc.format = format;
-        M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples);
+        M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, Model::HostResults{out, out_bytes, out_samples});
     });
 }
 
@@ -327,7 +327,7 @@ int kx_infer_packed(kx_model* m, const int64_t* ids, int64_t t_stride, const int
         Model::HostCall hc;
         hc.styles = styles;
         hc.format = format;
-        M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples);
+        M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, Model::HostResults{out, out_bytes, out_samples});
     });
 }
 
@@ -353,68 +353,79 @@ static_assert(sizeof(kx_limit) == 16 && sizeof(kx_limit) == sizeof(kx::LimitSpec
                   KX_LIMIT_MAX_TAPS == kx::LIMIT_MAX_TAPS,
               "kx_limit is the layout of kx::LimitSpec");
 
-// kx_infer_requests, kx_infer_requests_marks, kx_infer_requests_joined, kx_infer_requests_levelled and kx_infer_requests_loudness are
-// one call: the first asks for no marks, the first two for no joins, the first three for no levels, the first four for no loudness
-static int infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
-                          const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
-                          const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
-                          const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
-                          bool marks, int64_t** out_marks, int64_t* out_n_marks, bool joined = false, const kx_join* joins = nullptr,
-                          int n_join = 0, bool levelled = false, const kx_level* levels = nullptr, int n_level = 0,
-                          double* out_levels = nullptr, bool loud = false, const kx_loudness* loudness = nullptr, int n_loudness = 0,
-                          double* out_loudness = nullptr, bool limited = false, const kx_limit* limits = nullptr, int n_limit = 0,
-                          double* out_limits = nullptr, bool pros = false, const kx_prosody* prosody = nullptr, float** out_report = nullptr,
-                          int64_t* out_n_report = nullptr) {
-    return guarded(m, [&](Model& M) {
-        KX_REQUIRE(chunks_per_request && formats && R >= 1, "infer_requests: null argument");
-        KX_REQUIRE((styles != nullptr) != (voice_ids != nullptr), "infer_requests: give the style rows OR voice ids, not both");
-        KX_REQUIRE(styles || weights, "infer_requests: null argument");
+// The seven kx_infer_requests* entries are one call.  What they all take, in the order of their C signatures ...
+struct RequestArgs {
+    kx_model* m;
+    const int64_t* ids; int64_t t_stride; const int32_t* lens; int B;
+    const int32_t* chunks_per_request; int R;
+    const float* styles; const int32_t* voice_ids; const float* weights; int max_mix;
+    const float* speeds; int n_speed;
+    uint64_t seed; uint32_t flags;
+    const int32_t* formats; int n_format;
+    void** out; int64_t* out_bytes; int64_t* out_samples;
+};
+// ... and what each takes beyond that: an entry sets the fields it has, by name.
+struct RequestExtras {
+    int64_t** out_marks = nullptr;  // the marks pair: either of the two asks for marks
+    int64_t* out_n_marks = nullptr;
+    const kx_join* joins = nullptr;
+    int n_join = 0;
+    bool marks_entry = false;  // kx_infer_requests_marks: the pair must be there
+    bool join_entry = false;   // kx_infer_requests_joined: `joins` must be there; elsewhere see infer_requests
+    // the spec list of the levelled, the loudness or the limiter's entry (a null list is refused with the call's other arguments:
+    // check_spec_list) and the array its values come back in
+    kx::SpecList<kx::LevelSpec> levels;
+    kx::SpecList<kx::LoudSpec> loudness;
+    kx::SpecList<kx::LimitSpec> limits;
+    double* out_values = nullptr;
+    bool prosody_entry = false;  // kx_infer_requests_prosody: a null `prosody` is the neutral one; the report pair is both there or
+    const kx_prosody* prosody = nullptr;  // both null (check_prosody_call)
+    float** out_report = nullptr;
+    int64_t* out_n_report = nullptr;
+};
+
+static int infer_requests(const RequestArgs& a, const RequestExtras& x) {
+    return guarded(a.m, [&](Model& M) {
+        KX_REQUIRE(a.chunks_per_request && a.formats && a.R >= 1, "infer_requests: null argument");
+        KX_REQUIRE((a.styles != nullptr) != (a.voice_ids != nullptr), "infer_requests: give the style rows OR voice ids, not both");
+        KX_REQUIRE(a.styles || a.weights, "infer_requests: null argument");
         Model::HostCall hc;
-        hc.styles = styles;
-        hc.voice_ids = voice_ids;
-        hc.weights = weights;
-        hc.max_mix = voice_ids ? max_mix : 0;
-        hc.chunks_per_request = chunks_per_request;
-        hc.n_requests = R;
-        hc.req_formats = formats;
-        hc.n_req_formats = n_format;
+        hc.styles = a.styles;
+        hc.voice_ids = a.voice_ids;
+        hc.weights = a.weights;
+        hc.max_mix = a.voice_ids ? a.max_mix : 0;
+        hc.chunks_per_request = a.chunks_per_request;
+        hc.n_requests = a.R;
+        hc.req_formats = a.formats;
+        hc.n_req_formats = a.n_format;
         std::vector<uint8_t> want;
-        if (marks) {  // (every request of the call)
-            want.assign((size_t)R, 1);
+        if (x.marks_entry || x.out_marks || x.out_n_marks) {  // (every request of the call)
+            want.assign((size_t)a.R, 1);
             hc.req_marks = want.data();
         }
-        if (joined) {  // (a null `joins` is refused with the call's other arguments: check_join_call)
-            hc.join_call = true;
-            hc.req_joins = reinterpret_cast<const kx::JoinSpec*>(joins);
-            hc.n_req_joins = n_join;
-        }
-        if (levelled) {  // (a null `levels` is refused with the call's other arguments: check_level_call)
-            hc.level_call = true;
-            hc.req_levels = reinterpret_cast<const kx::LevelSpec*>(levels);
-            hc.n_req_levels = n_level;
-        }
-        if (loud) {  // (a null `loudness` is refused with the call's other arguments: check_loudness_call)
-            hc.loud_call = true;
-            hc.req_loudness = reinterpret_cast<const kx::LoudSpec*>(loudness);
-            hc.n_req_loudness = n_loudness;
-        }
-        if (limited) {  // (a null `limits` is refused with the call's other arguments: check_limit_call)
-            hc.limit_call = true;
-            hc.req_limits = reinterpret_cast<const kx::LimitSpec*>(limits);
-            hc.n_req_limits = n_limit;
-        }
+        // (joins == NULL with n_join == 0: no joins; anything else goes through the join entry's checks)
+        if (x.join_entry || x.joins || x.n_join != 0) hc.joins = {true, reinterpret_cast<const kx::JoinSpec*>(x.joins), x.n_join};
+        hc.levels = x.levels;
+        hc.loudness = x.loudness;
+        hc.limits = x.limits;
+        Model::HostResults res{a.out, a.out_bytes, a.out_samples};
+        res.out_marks = x.out_marks;
+        res.out_n_marks = x.out_n_marks;
+        res.out_levels = x.levels.call ? x.out_values : nullptr;
+        res.out_loudness = x.loudness.call ? x.out_values : nullptr;
+        res.out_limits = x.limits.call ? x.out_values : nullptr;
         std::vector<uint8_t> want_report;
-        if (pros) {  // (a null `prosody` is the neutral one; the report pair is both there or both null: check_prosody_call)
+        if (x.prosody_entry) {
             hc.prosody_call = true;
-            hc.prosody = reinterpret_cast<const kx::ProsodySpec*>(prosody);
-            if (out_report && out_n_report) {  // (every request of the call)
-                want_report.assign((size_t)R, 1);
+            hc.prosody = reinterpret_cast<const kx::ProsodySpec*>(x.prosody);
+            if (x.out_report && x.out_n_report) {  // (every request of the call)
+                want_report.assign((size_t)a.R, 1);
                 hc.req_reports = want_report.data();
             }
+            res.out_report = x.out_report;
+            res.out_n_report = x.out_n_report;
         }
-        M.infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks,
-                        levelled ? out_levels : nullptr, loud ? out_loudness : nullptr, limited ? out_limits : nullptr,
-                        pros ? out_report : nullptr, pros ? out_n_report : nullptr);
+        M.infer_host_ex(a.ids, a.t_stride, a.lens, a.B, a.speeds, a.n_speed, a.seed, a.flags, hc, res);
     });
 }
 
@@ -422,8 +433,9 @@ int kx_infer_requests(kx_model* m, const int64_t* ids, int64_t t_stride, const i
                       const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
                       const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
                       const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples) {
-    return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
-                          flags, formats, n_format, out, out_bytes, out_samples, false, nullptr, nullptr);
+    return infer_requests({m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
+                           flags, formats, n_format, out, out_bytes, out_samples},
+                          RequestExtras{});
 }
 
 int kx_infer_requests_marks(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
@@ -431,8 +443,11 @@ int kx_infer_requests_marks(kx_model* m, const int64_t* ids, int64_t t_stride, c
                             const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
                             const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
                             int64_t** out_marks, int64_t* out_n_marks) {
-    return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
-                          flags, formats, n_format, out, out_bytes, out_samples, true, out_marks, out_n_marks);
+    RequestExtras x{out_marks, out_n_marks};
+    x.marks_entry = true;
+    return infer_requests({m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
+                           flags, formats, n_format, out, out_bytes, out_samples},
+                          x);
 }
 
 int kx_infer_requests_joined(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
@@ -440,9 +455,11 @@ int kx_infer_requests_joined(kx_model* m, const int64_t* ids, int64_t t_stride, 
                              const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
                              const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
                              int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join) {
-    return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
-                          flags, formats, n_format, out, out_bytes, out_samples, out_marks || out_n_marks, out_marks, out_n_marks, true,
-                          joins, n_join);
+    RequestExtras x{out_marks, out_n_marks, joins, n_join};
+    x.join_entry = true;
+    return infer_requests({m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
+                           flags, formats, n_format, out, out_bytes, out_samples},
+                          x);
 }
 
 int kx_infer_requests_prosody(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
@@ -451,11 +468,13 @@ int kx_infer_requests_prosody(kx_model* m, const int64_t* ids, int64_t t_stride,
                               const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
                               int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_prosody* prosody,
                               float** out_report, int64_t* out_n_report) {
-    // (joins == NULL with n_join == 0: no joins; anything else goes through the join entry's checks)
-    return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
-                          flags, formats, n_format, out, out_bytes, out_samples, out_marks || out_n_marks, out_marks, out_n_marks,
-                          joins != nullptr || n_join != 0, joins, n_join, false, nullptr, 0, nullptr, false, nullptr, 0, nullptr, false,
-                          nullptr, 0, nullptr, true, prosody, out_report, out_n_report);
+    RequestExtras x{out_marks, out_n_marks, joins, n_join};
+    x.prosody_entry = true;
+    x.prosody = prosody;
+    x.out_report = out_report, x.out_n_report = out_n_report;
+    return infer_requests({m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
+                           flags, formats, n_format, out, out_bytes, out_samples},
+                          x);
 }
 
 int kx_infer_requests_levelled(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
@@ -464,10 +483,12 @@ int kx_infer_requests_levelled(kx_model* m, const int64_t* ids, int64_t t_stride
                                const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
                                int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_level* levels,
                                int n_level, double* out_levels) {
-    // (joins == NULL with n_join == 0: no joins; anything else goes through the join entry's checks)
-    return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
-                          flags, formats, n_format, out, out_bytes, out_samples, out_marks || out_n_marks, out_marks, out_n_marks,
-                          joins != nullptr || n_join != 0, joins, n_join, true, levels, n_level, out_levels);
+    RequestExtras x{out_marks, out_n_marks, joins, n_join};
+    x.levels = {true, reinterpret_cast<const kx::LevelSpec*>(levels), n_level};
+    x.out_values = out_levels;
+    return infer_requests({m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
+                           flags, formats, n_format, out, out_bytes, out_samples},
+                          x);
 }
 
 int kx_infer_requests_loudness(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
@@ -476,10 +497,12 @@ int kx_infer_requests_loudness(kx_model* m, const int64_t* ids, int64_t t_stride
                                const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
                                int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join,
                                const kx_loudness* loudness, int n_loudness, double* out_loudness) {
-    return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
-                          flags, formats, n_format, out, out_bytes, out_samples, out_marks || out_n_marks, out_marks, out_n_marks,
-                          joins != nullptr || n_join != 0, joins, n_join, false, nullptr, 0, nullptr, true, loudness, n_loudness,
-                          out_loudness);
+    RequestExtras x{out_marks, out_n_marks, joins, n_join};
+    x.loudness = {true, reinterpret_cast<const kx::LoudSpec*>(loudness), n_loudness};
+    x.out_values = out_loudness;
+    return infer_requests({m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
+                           flags, formats, n_format, out, out_bytes, out_samples},
+                          x);
 }
 
 int kx_infer_requests_limited(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
@@ -488,10 +511,12 @@ int kx_infer_requests_limited(kx_model* m, const int64_t* ids, int64_t t_stride,
                               const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
                               int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_limit* limits,
                               int n_limit, double* out_limits) {
-    return infer_requests(m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
-                          flags, formats, n_format, out, out_bytes, out_samples, out_marks || out_n_marks, out_marks, out_n_marks,
-                          joins != nullptr || n_join != 0, joins, n_join, false, nullptr, 0, nullptr, false, nullptr, 0, nullptr, true,
-                          limits, n_limit, out_limits);
+    RequestExtras x{out_marks, out_n_marks, joins, n_join};
+    x.limits = {true, reinterpret_cast<const kx::LimitSpec*>(limits), n_limit};
+    x.out_values = out_limits;
+    return infer_requests({m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
+                           flags, formats, n_format, out, out_bytes, out_samples},
+                          x);
 }
 
 int kx_infer_device(kx_model* m, const int64_t* d_ids, int64_t t_stride, const int32_t* lens_host, int B,

@@ -14,6 +14,7 @@
 namespace {
 
 using kx::dispatch::Request;
+using kx::dispatch::to_spec;
 
 // One batched forward on a model: requests of every kind / format in one HostCall (per-row kinds and keys, per-request formats).
 struct ModelBackend {
@@ -76,14 +77,14 @@ struct ModelBackend {
         int b = 0;
         for (int q = 0; q < R; ++q) {
             const Request& r = *batch[(size_t)q];
-            limits[q] = r.limited ? kx::LimitSpec{r.limit.mode, r.limit.gain, r.limit.target_lufs, r.limit.peak} : kx::LimitSpec{kx::LIMIT_NONE, 1.0f, 0.0f, 1.0f};
+            limits[q] = r.limited ? to_spec(r.limit) : kx::LimitSpec{kx::LIMIT_NONE, 1.0f, 0.0f, 1.0f};
             chunks[q] = r.rows();
             formats[q] = r.format;
             want[q] = r.want_marks ? 1 : 0;
             want_report[q] = r.want_report ? 1 : 0;
-            joins[q] = kx::JoinSpec{r.join.flags, r.join.keep_ms, r.join.pause_ms, r.join.fade_ms};
-            levels[q] = kx::LevelSpec{r.level.mode, r.level.gain, r.level.peak};
-            louds[q] = r.metered ? kx::LoudSpec{r.loudness.mode, r.loudness.target_lufs, r.loudness.peak} : kx::LoudSpec{kx::LOUD_NONE, 0.0f, 0.0f};
+            joins[q] = to_spec(r.join);
+            levels[q] = to_spec(r.level);
+            louds[q] = r.metered ? to_spec(r.loudness) : kx::LoudSpec{kx::LOUD_NONE, 0.0f, 0.0f};
             size_t at = 0;
             for (int c = 0; c < r.rows(); ++c, ++b) {
                 lens[b] = (int32_t)r.chunk_len(c);
@@ -131,22 +132,11 @@ struct ModelBackend {
                 hc.req_formats = formats.data();
                 hc.n_req_formats = R;
                 if (any_marks) hc.req_marks = want.data();
-                if (any_join) {
-                    hc.req_joins = joins.data();
-                    hc.n_req_joins = R;
-                }
-                if (any_level) {
-                    hc.req_levels = levels.data();
-                    hc.n_req_levels = R;
-                }
-                if (any_loud) {
-                    hc.req_loudness = louds.data();
-                    hc.n_req_loudness = R;
-                }
-                if (any_limit) {
-                    hc.req_limits = limits.data();
-                    hc.n_req_limits = R;
-                }
+                // (the lists go without their `call` flag: every request was checked when it was submitted)
+                if (any_join) hc.joins = {false, joins.data(), R};
+                if (any_level) hc.levels = {false, levels.data(), R};
+                if (any_loud) hc.loudness = {false, louds.data(), R};
+                if (any_limit) hc.limits = {false, limits.data(), R};
                 const kx::ProsodySpec ps{any_rate ? p_rate.data() : nullptr, any_frames ? p_frames.data() : nullptr,
                                          any_pitch ? p_pitch.data() : nullptr, any_energy ? p_energy.data() : nullptr};
                 if (any_rate || any_frames || any_pitch || any_energy || any_report) {
@@ -163,10 +153,13 @@ struct ModelBackend {
                 } else {
                     hc.styles = styles.data();
                 }
-                M.infer_host_ex(ids.data(), (int64_t)stride, lens.data(), B, speeds.data(), B, 0, 0, hc, &o.buf, o.bytes.data(),
-                                o.samples.data(), &o.marks, o.n_marks.data(), any_level ? o.levels.data() : nullptr,
-                                any_loud ? o.loud.data() : nullptr, any_limit ? o.limits.data() : nullptr,
-                                any_report ? &o.report : nullptr, any_report ? o.n_report.data() : nullptr);
+                kx::Model::HostResults res{&o.buf, o.bytes.data(), o.samples.data()};
+                res.out_marks = &o.marks, res.out_n_marks = o.n_marks.data();
+                if (any_level) res.out_levels = o.levels.data();
+                if (any_loud) res.out_loudness = o.loud.data();
+                if (any_limit) res.out_limits = o.limits.data();
+                if (any_report) res.out_report = &o.report, res.out_n_report = o.n_report.data();
+                M.infer_host_ex(ids.data(), (int64_t)stride, lens.data(), B, speeds.data(), B, 0, 0, hc, res);
                 rc = KX_OK;
             } catch (const kx::Error& e) {
                 rc = e.code;
@@ -272,6 +265,12 @@ struct kx_dispatcher : kx::dispatch::Core<ModelBackend> {
     kx_dispatcher(kx_model** ms, int n, int max_b, int wait_us) : kx::dispatch::Core<ModelBackend>(ms, n, max_b, wait_us) {}
 };
 
+// what every submit entry answers to a null dispatcher
+static int no_dispatcher(const char* who, char* err, size_t err_len) {
+    if (err && err_len) snprintf(err, err_len, "%s: null dispatcher", who);
+    return KX_ERR_INVALID;
+}
+
 extern "C" {
 
 kx_dispatcher* kx_dispatcher_create(kx_model** models, int n_models, int max_batch, int max_wait_us, char* err,
@@ -328,20 +327,14 @@ kx_dispatcher* kx_dispatcher_create_warm(kx_model** models, int n_models, int ma
 
 int kx_dispatcher_submit(kx_dispatcher* d, const int64_t* ids, int n_tokens, const float* style, float speed,
                          uint64_t seed, float** out, int64_t* out_len, char* err, size_t err_len) {
-    if (!d) {
-        if (err && err_len) snprintf(err, err_len, "dispatcher_submit: null dispatcher");
-        return KX_ERR_INVALID;
-    }
+    if (!d) return no_dispatcher("dispatcher_submit", err, err_len);
     return d->submit_row(ids, n_tokens, style, speed, seed, out, out_len, err, err_len);
 }
 
 int kx_dispatcher_submit_ex(kx_dispatcher* d, const int64_t* ids, int n_tokens, const float* style,
                             const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed,
                             int format, void** out, int64_t* out_bytes, int64_t* out_samples, char* err, size_t err_len) {
-    if (!d) {
-        if (err && err_len) snprintf(err, err_len, "dispatcher_submit_ex: null dispatcher");
-        return KX_ERR_INVALID;
-    }
+    if (!d) return no_dispatcher("dispatcher_submit_ex", err, err_len);
     return d->submit_ex(ids, n_tokens, style, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes, out_samples, err,
                         err_len);
 }
@@ -350,10 +343,7 @@ int kx_dispatcher_submit_request(kx_dispatcher* d, const int64_t* ids, const int
                                  const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
                                  float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
                                  int64_t* out_samples, char* err, size_t err_len) {
-    if (!d) {
-        if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null dispatcher");
-        return KX_ERR_INVALID;
-    }
+    if (!d) return no_dispatcher("dispatcher_submit_request", err, err_len);
     return d->submit_request(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
                              out_samples, err, err_len);
 }
@@ -363,10 +353,7 @@ int kx_dispatcher_submit_request_marks(kx_dispatcher* d, const int64_t* ids, con
                                        float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
                                        int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, char* err,
                                        size_t err_len) {
-    if (!d) {
-        if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null dispatcher");
-        return KX_ERR_INVALID;
-    }
+    if (!d) return no_dispatcher("dispatcher_submit_request", err, err_len);
     return d->submit_request_marks(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
                                    out_bytes, out_samples, out_marks, out_n_marks, err, err_len);
 }
@@ -376,10 +363,7 @@ int kx_dispatcher_submit_request_joined(kx_dispatcher* d, const int64_t* ids, co
                                         float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
                                         int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
                                         char* err, size_t err_len) {
-    if (!d) {
-        if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null dispatcher");
-        return KX_ERR_INVALID;
-    }
+    if (!d) return no_dispatcher("dispatcher_submit_request", err, err_len);
     return d->submit_request_joined(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
                                     out_bytes, out_samples, out_marks, out_n_marks, join, err, err_len);
 }
@@ -389,10 +373,7 @@ int kx_dispatcher_submit_request_levelled(kx_dispatcher* d, const int64_t* ids, 
                                           float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
                                           int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
                                           const kx_level* level, double* out_level, char* err, size_t err_len) {
-    if (!d) {
-        if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null dispatcher");
-        return KX_ERR_INVALID;
-    }
+    if (!d) return no_dispatcher("dispatcher_submit_request", err, err_len);
     return d->submit_request_levelled(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
                                       out_bytes, out_samples, out_marks, out_n_marks, join, level, out_level, err, err_len);
 }
@@ -403,10 +384,7 @@ int kx_dispatcher_submit_request_prosody(kx_dispatcher* d, const int64_t* ids, c
                                          int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
                                          const kx_prosody* prosody, float** out_report, int64_t* out_n_report, char* err,
                                          size_t err_len) {
-    if (!d) {
-        if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null dispatcher");
-        return KX_ERR_INVALID;
-    }
+    if (!d) return no_dispatcher("dispatcher_submit_request", err, err_len);
     return d->submit_request_prosody(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
                                      out_bytes, out_samples, out_marks, out_n_marks, join, prosody, out_report, out_n_report, err,
                                      err_len);
@@ -417,10 +395,7 @@ int kx_dispatcher_submit_request_limited(kx_dispatcher* d, const int64_t* ids, c
                                          float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
                                          int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
                                          const kx_limit* limit, double* out_limit, char* err, size_t err_len) {
-    if (!d) {
-        if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null dispatcher");
-        return KX_ERR_INVALID;
-    }
+    if (!d) return no_dispatcher("dispatcher_submit_request", err, err_len);
     return d->submit_request_limited(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
                                      out_bytes, out_samples, out_marks, out_n_marks, join, limit, out_limit, err, err_len);
 }
@@ -430,10 +405,7 @@ int kx_dispatcher_submit_request_loudness(kx_dispatcher* d, const int64_t* ids, 
                                           float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
                                           int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
                                           const kx_loudness* loudness, double* out_loudness, char* err, size_t err_len) {
-    if (!d) {
-        if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null dispatcher");
-        return KX_ERR_INVALID;
-    }
+    if (!d) return no_dispatcher("dispatcher_submit_request", err, err_len);
     return d->submit_request_loudness(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
                                       out_bytes, out_samples, out_marks, out_n_marks, join, loudness, out_loudness, err, err_len);
 }

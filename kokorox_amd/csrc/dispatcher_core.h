@@ -116,6 +116,40 @@ struct Request {
     std::chrono::steady_clock::time_point t_submit;
 };
 
+// the public spec structs as their kx:: twins (host_request.h)
+inline JoinSpec to_spec(const kx_join& j) { return JoinSpec{j.flags, j.keep_ms, j.pause_ms, j.fade_ms}; }
+inline LevelSpec to_spec(const kx_level& l) { return LevelSpec{l.mode, l.gain, l.peak}; }
+inline LoudSpec to_spec(const kx_loudness& l) { return LoudSpec{l.mode, l.target_lufs, l.peak}; }
+inline LimitSpec to_spec(const kx_limit& l) { return LimitSpec{l.mode, l.gain, l.target_lufs, l.peak}; }
+// a spec a submit refuses: one that is out of range, or a null one where the entry is the one that takes it
+template <class Pub, class Spec>
+bool spec_bad(const Pub* p, bool needed, bool (*ok)(const Spec&)) {
+    return p ? !ok(to_spec(*p)) : needed;
+}
+
+// What a submit_request* entry takes beyond the arguments they all have (Core::submit_request_any).  A null spec: the request has
+// no such option -- unless the entry is the one named for it (need_*), which refuses a null spec as it refuses a bad one.
+struct RequestOptions {
+    bool want_marks = false;  // the token marks of the request, through the pair
+    int64_t** out_marks = nullptr;
+    int64_t* out_n_marks = nullptr;
+    const kx_join* join = nullptr;
+    const kx_level* level = nullptr;
+    const kx_loudness* loudness = nullptr;
+    const kx_limit* limit = nullptr;
+    double *out_level = nullptr, *out_loudness = nullptr, *out_limit = nullptr;  // [2], [4], [5]: each may be null
+    const kx_prosody* prosody = nullptr;  // (the prosody entry: never null, a request without arrays has the neutral one)
+    float** out_report = nullptr;  // the report pair: both or neither
+    int64_t* out_n_report = nullptr;
+    bool need_join = false, need_level = false, need_loudness = false, need_limit = false;
+    // the entries behind the marks entry: either argument of the pair asks for marks, and then both must be there
+    void set_marks(int64_t** marks, int64_t* n_marks) {
+        want_marks = marks || n_marks;
+        out_marks = marks;
+        out_n_marks = n_marks;
+    }
+};
+
 template <class Backend>
 struct Core {
     using Handle = typename Backend::Handle;
@@ -457,78 +491,65 @@ struct Core {
                        const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
                        void** out, int64_t* out_bytes, int64_t* out_samples, char* err, size_t err_len) {
         return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
-                                  out_samples, false, nullptr, nullptr, err, err_len);
+                                  out_samples, RequestOptions{}, err, err_len);
     }
     // ... and with the request's token marks: *out_marks points into the allocation of *out
     int submit_request_marks(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
                              const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
                              void** out, int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
                              char* err, size_t err_len) {
+        RequestOptions o;
+        o.set_marks(out_marks, out_n_marks);
+        o.want_marks = true;
         return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
-                                  out_samples, true, out_marks, out_n_marks, err, err_len);
+                                  out_samples, o, err, err_len);
     }
     // ... and with its join spec; both marks arguments null = no marks
     int submit_request_joined(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
                               const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
                               void** out, int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
                               const kx_join* join, char* err, size_t err_len) {
-        if (!join || (join->flags & ~7u) || join->keep_ms < 0 || join->keep_ms > 1000 || join->pause_ms < 0 || join->pause_ms > 5000 ||
-            join->fade_ms < 0 || join->fade_ms > 12) {
-            if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: bad join");
-            return KX_ERR_INVALID;
-        }
+        RequestOptions o;
+        o.set_marks(out_marks, out_n_marks);
+        o.join = join, o.need_join = true;
         return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
-                                  out_samples, out_marks || out_n_marks, out_marks, out_n_marks, err, err_len, join);
+                                  out_samples, o, err, err_len);
     }
     // ... and with its level spec; `join` may be null here (no join), out_level may be null
     int submit_request_levelled(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
                                 const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
                                 void** out, int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
                                 const kx_join* join, const kx_level* level, double* out_level, char* err, size_t err_len) {
-        if (join && !join_spec_ok(JoinSpec{join->flags, join->keep_ms, join->pause_ms, join->fade_ms})) {
-            if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: bad join");
-            return KX_ERR_INVALID;
-        }
-        if (!level || !level_spec_ok(LevelSpec{level->mode, level->gain, level->peak})) {
-            if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: bad level");
-            return KX_ERR_INVALID;
-        }
+        RequestOptions o;
+        o.set_marks(out_marks, out_n_marks);
+        o.join = join;
+        o.level = level, o.out_level = out_level, o.need_level = true;
         return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
-                                  out_samples, out_marks || out_n_marks, out_marks, out_n_marks, err, err_len, join, level, out_level);
+                                  out_samples, o, err, err_len);
     }
     // ... and with its loudness spec; `join` may be null here (no join), out_loudness may be null
     int submit_request_loudness(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
                                 const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
                                 void** out, int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
                                 const kx_join* join, const kx_loudness* loudness, double* out_loudness, char* err, size_t err_len) {
-        if (join && !join_spec_ok(JoinSpec{join->flags, join->keep_ms, join->pause_ms, join->fade_ms})) {
-            if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: bad join");
-            return KX_ERR_INVALID;
-        }
-        if (!loudness || !loud_spec_ok(LoudSpec{loudness->mode, loudness->target_lufs, loudness->peak})) {
-            if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: bad loudness");
-            return KX_ERR_INVALID;
-        }
+        RequestOptions o;
+        o.set_marks(out_marks, out_n_marks);
+        o.join = join;
+        o.loudness = loudness, o.out_loudness = out_loudness, o.need_loudness = true;
         return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
-                                  out_samples, out_marks || out_n_marks, out_marks, out_n_marks, err, err_len, join, nullptr, nullptr,
-                                  loudness, out_loudness);
+                                  out_samples, o, err, err_len);
     }
     // ... and with its limit spec; `join` may be null here (no join), out_limit may be null
     int submit_request_limited(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
                                const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
                                void** out, int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
                                const kx_join* join, const kx_limit* limit, double* out_limit, char* err, size_t err_len) {
-        if (join && !join_spec_ok(JoinSpec{join->flags, join->keep_ms, join->pause_ms, join->fade_ms})) {
-            if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: bad join");
-            return KX_ERR_INVALID;
-        }
-        if (!limit || !limit_spec_ok(LimitSpec{limit->mode, limit->gain, limit->target_lufs, limit->peak})) {
-            if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: bad limit");
-            return KX_ERR_INVALID;
-        }
+        RequestOptions o;
+        o.set_marks(out_marks, out_n_marks);
+        o.join = join;
+        o.limit = limit, o.out_limit = out_limit, o.need_limit = true;
         return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
-                                  out_samples, out_marks || out_n_marks, out_marks, out_n_marks, err, err_len, join, nullptr, nullptr,
-                                  nullptr, nullptr, limit, out_limit);
+                                  out_samples, o, err, err_len);
     }
     // ... and with its prosody (include/kokorox_hip.h, "prosody") and the report; `join` and `prosody` may be null here
     int submit_request_prosody(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
@@ -536,71 +557,57 @@ struct Core {
                                void** out, int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
                                const kx_join* join, const kx_prosody* prosody, float** out_report, int64_t* out_n_report, char* err,
                                size_t err_len) {
-        if (join && !join_spec_ok(JoinSpec{join->flags, join->keep_ms, join->pause_ms, join->fade_ms})) {
-            if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: bad join");
-            return KX_ERR_INVALID;
-        }
-        if ((out_report != nullptr) != (out_n_report != nullptr)) {
-            if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null report argument");
-            return KX_ERR_INVALID;
-        }
         const kx_prosody neutral = {nullptr, nullptr, nullptr, nullptr};
+        RequestOptions o;
+        o.set_marks(out_marks, out_n_marks);
+        o.join = join;
+        o.prosody = prosody ? prosody : &neutral;
+        o.out_report = out_report, o.out_n_report = out_n_report;
         return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
-                                  out_samples, out_marks || out_n_marks, out_marks, out_n_marks, err, err_len, join, nullptr, nullptr,
-                                  nullptr, nullptr, nullptr, nullptr, prosody ? prosody : &neutral, out_report, out_n_report);
+                                  out_samples, o, err, err_len);
     }
+    // The submits above are this one.  The request's options are looked at first, a bad join before a bad level, loudness or limit,
+    // then the report pair; the arguments every submit has come after them.
     int submit_request_any(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
                            const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
-                           void** out, int64_t* out_bytes, int64_t* out_samples, bool want_marks, int64_t** out_marks,
-                           int64_t* out_n_marks, char* err, size_t err_len, const kx_join* join = nullptr,
-                           const kx_level* level = nullptr, double* out_level = nullptr, const kx_loudness* loudness = nullptr,
-                           double* out_loudness = nullptr, const kx_limit* limit = nullptr, double* out_limit = nullptr,
-                           const kx_prosody* prosody = nullptr, float** out_report = nullptr, int64_t* out_n_report = nullptr) {
+                           void** out, int64_t* out_bytes, int64_t* out_samples, const RequestOptions& o, char* err, size_t err_len) {
         const char* who = "dispatcher_submit_request";
-        if (!out || !out_bytes || !out_samples) {
-            if (err && err_len) snprintf(err, err_len, "%s: null output argument", who);
-            return KX_ERR_INVALID;
-        }
-        if (want_marks && (!out_marks || !out_n_marks)) {
-            if (err && err_len) snprintf(err, err_len, "%s: null marks argument", who);
-            return KX_ERR_INVALID;
-        }
-        if (!ids || !chunk_tokens || n_chunks < 1 || n_chunks > max_batch) {
-            if (err && err_len) snprintf(err, err_len, "%s: a request has 1..%d chunks (max_batch)", who, max_batch);
-            return KX_ERR_INVALID;
-        }
-        if ((styles != nullptr) == (voice_ids != nullptr)) {
-            if (err && err_len) snprintf(err, err_len, "%s: give the style rows OR voice ids, not both", who);
-            return KX_ERR_INVALID;
-        }
+        // (these texts are written out whole: callers and tests match on them)
+        const char* bad = spec_bad(o.join, o.need_join, join_spec_ok)               ? "dispatcher_submit_request: bad join"
+                          : spec_bad(o.level, o.need_level, level_spec_ok)          ? "dispatcher_submit_request: bad level"
+                          : spec_bad(o.loudness, o.need_loudness, loud_spec_ok)     ? "dispatcher_submit_request: bad loudness"
+                          : spec_bad(o.limit, o.need_limit, limit_spec_ok)          ? "dispatcher_submit_request: bad limit"
+                          : (o.out_report != nullptr) != (o.out_n_report != nullptr) ? "dispatcher_submit_request: null report argument"
+                                                                                     : nullptr;
+        auto refuse = [&](const char* fmt, auto... args) {
+            if (err && err_len) snprintf(err, err_len, fmt, args...);
+            return (int)KX_ERR_INVALID;
+        };
+        if (bad) return refuse("%s", bad);
+        if (!out || !out_bytes || !out_samples) return refuse("%s: null output argument", who);
+        if (o.want_marks && (!o.out_marks || !o.out_n_marks)) return refuse("%s: null marks argument", who);
+        if (!ids || !chunk_tokens || n_chunks < 1 || n_chunks > max_batch) return refuse("%s: a request has 1..%d chunks (max_batch)", who, max_batch);
+        if ((styles != nullptr) == (voice_ids != nullptr)) return refuse("%s: give the style rows OR voice ids, not both", who);
         size_t total = 0;
         int min_tokens = KX_MAX_TOKENS;
         for (int c = 0; c < n_chunks; ++c) {
             // (the count first: check_common reads chunk_tokens[c] ids)
-            if (chunk_tokens[c] < (voice_ids ? 2 : 1) || chunk_tokens[c] > KX_MAX_TOKENS) {
-                if (err && err_len)
-                    snprintf(err, err_len, "%s: chunk %d: 1..512 tokens (with a voice: at least the two 0 pads)", who, c);
-                return KX_ERR_INVALID;
-            }
+            if (chunk_tokens[c] < (voice_ids ? 2 : 1) || chunk_tokens[c] > KX_MAX_TOKENS)
+                return refuse("%s: chunk %d: 1..512 tokens (with a voice: at least the two 0 pads)", who, c);
             if (!check_common(ids + total, chunk_tokens[c], speed, format, who, err, err_len, true)) return KX_ERR_INVALID;
             total += (size_t)chunk_tokens[c];
             min_tokens = chunk_tokens[c] < min_tokens ? chunk_tokens[c] : min_tokens;
         }
-        if (prosody) {  // (the arrays run over the chunks back to back: one row of `total` tokens as far as the rule goes)
-            const ProsodySpec ps{prosody->rate, prosody->frames, prosody->pitch, prosody->energy};
-            const int32_t all = (int32_t)total;
-            if (!prosody_ok(&ps, &all, 1, (int64_t)total)) {
-                if (err && err_len) snprintf(err, err_len, "%s: bad prosody", who);
-                return KX_ERR_INVALID;
-            }
-        }
         Request r;
-        if (prosody) {
-            if (prosody->rate) r.p_rate.assign(prosody->rate, prosody->rate + total);
-            if (prosody->frames) r.p_frames.assign(prosody->frames, prosody->frames + total);
-            if (prosody->pitch) r.p_pitch.assign(prosody->pitch, prosody->pitch + total);
-            if (prosody->energy) r.p_energy.assign(prosody->energy, prosody->energy + total);
-            r.want_report = out_report != nullptr;
+        if (const kx_prosody* p = o.prosody) {  // (the arrays run over the chunks back to back: one row of `total` tokens as far as the rule goes)
+            const ProsodySpec ps{p->rate, p->frames, p->pitch, p->energy};
+            const int32_t all = (int32_t)total;
+            if (!prosody_ok(&ps, &all, 1, (int64_t)total)) return refuse("%s: bad prosody", who);
+            if (p->rate) r.p_rate.assign(p->rate, p->rate + total);
+            if (p->frames) r.p_frames.assign(p->frames, p->frames + total);
+            if (p->pitch) r.p_pitch.assign(p->pitch, p->pitch + total);
+            if (p->energy) r.p_energy.assign(p->energy, p->energy + total);
+            r.want_report = o.out_report != nullptr;
         }
         if (styles) {
             r.kind = 0;
@@ -613,38 +620,39 @@ struct Core {
         r.format = format;
         r.speed = speed;
         r.seed = seed;
-        r.want_marks = want_marks;
-        if (join) r.join = *join;
-        if (level) {
-            r.level = *level;
+        r.want_marks = o.want_marks;
+        if (o.join) r.join = *o.join;
+        if (o.level) {
+            r.level = *o.level;
             r.levelled = true;
         }
-        if (loudness) {
-            r.loudness = *loudness;
+        if (o.loudness) {
+            r.loudness = *o.loudness;
             r.metered = true;
         }
-        if (limit) {
-            r.limit = *limit;
+        if (o.limit) {
+            r.limit = *o.limit;
             r.limited = true;
         }
         const int rc = submit(r, out, out_bytes, out_samples, err, err_len);
-        if (rc == KX_OK && limit && out_limit)
-            for (int i = 0; i < 5; ++i) out_limit[i] = r.limit_out[i];
-        if (rc == KX_OK && loudness && out_loudness)
-            for (int i = 0; i < 4; ++i) out_loudness[i] = r.loud_out[i];
-        if (rc == KX_OK && want_marks) {
-            *out_marks = r.marks;
-            *out_n_marks = r.n_marks;
+        if (rc != KX_OK) return rc;
+        if (o.limit && o.out_limit)
+            for (int i = 0; i < 5; ++i) o.out_limit[i] = r.limit_out[i];
+        if (o.loudness && o.out_loudness)
+            for (int i = 0; i < 4; ++i) o.out_loudness[i] = r.loud_out[i];
+        if (o.want_marks) {
+            *o.out_marks = r.marks;
+            *o.out_n_marks = r.n_marks;
         }
-        if (rc == KX_OK && r.want_report) {
-            *out_report = r.report;
-            *out_n_report = r.n_report;
+        if (r.want_report) {
+            *o.out_report = r.report;
+            *o.out_n_report = r.n_report;
         }
-        if (rc == KX_OK && level && out_level) {
-            out_level[0] = r.level_out[0];
-            out_level[1] = r.level_out[1];
+        if (o.level && o.out_level) {
+            o.out_level[0] = r.level_out[0];
+            o.out_level[1] = r.level_out[1];
         }
-        return rc;
+        return KX_OK;
     }
 };
 

@@ -140,28 +140,28 @@ void check_marks_call(const HostCall& hc, int64_t** out_marks, int64_t* out_n_ma
     KX_REQUIRE(hc.grouped(), "infer: marks are for requests (chunks_per_request)");
 }
 
-void check_join_call(const HostCall& hc) {
-    KX_REQUIRE(hc.req_joins, "infer: null join argument");
-    KX_REQUIRE(hc.grouped() && (hc.n_req_joins == 1 || hc.n_req_joins == hc.n_requests), "infer: bad join count");
-    for (int i = 0; i < hc.n_req_joins; ++i) KX_REQUIRE(join_spec_ok(hc.req_joins[i]), "infer: bad join");
+namespace {
+// (the three texts of a list are written out whole below: callers and tests match on them)
+template <class Spec>
+void check_list(const HostCall& hc, const SpecList<Spec>& list, bool (*ok)(const Spec&), const char* null_list, const char* bad_count,
+                const char* bad_spec) {
+    KX_REQUIRE(list.specs, null_list);
+    KX_REQUIRE(hc.grouped() && (list.n == 1 || list.n == hc.n_requests), bad_count);
+    for (int i = 0; i < list.n; ++i) KX_REQUIRE(ok(list.specs[i]), bad_spec);
 }
+}  // namespace
 
-void check_level_call(const HostCall& hc) {
-    KX_REQUIRE(hc.req_levels, "infer: null level argument");
-    KX_REQUIRE(hc.grouped() && (hc.n_req_levels == 1 || hc.n_req_levels == hc.n_requests), "infer: bad level count");
-    for (int i = 0; i < hc.n_req_levels; ++i) KX_REQUIRE(level_spec_ok(hc.req_levels[i]), "infer: bad level");
+void check_spec_list(const HostCall& hc, const SpecList<JoinSpec>& list) {
+    check_list(hc, list, join_spec_ok, "infer: null join argument", "infer: bad join count", "infer: bad join");
 }
-
-void check_loudness_call(const HostCall& hc) {
-    KX_REQUIRE(hc.req_loudness, "infer: null loudness argument");
-    KX_REQUIRE(hc.grouped() && (hc.n_req_loudness == 1 || hc.n_req_loudness == hc.n_requests), "infer: bad loudness count");
-    for (int i = 0; i < hc.n_req_loudness; ++i) KX_REQUIRE(loud_spec_ok(hc.req_loudness[i]), "infer: bad loudness");
+void check_spec_list(const HostCall& hc, const SpecList<LevelSpec>& list) {
+    check_list(hc, list, level_spec_ok, "infer: null level argument", "infer: bad level count", "infer: bad level");
 }
-
-void check_limit_call(const HostCall& hc) {
-    KX_REQUIRE(hc.req_limits, "infer: null limit argument");
-    KX_REQUIRE(hc.grouped() && (hc.n_req_limits == 1 || hc.n_req_limits == hc.n_requests), "infer: bad limit count");
-    for (int i = 0; i < hc.n_req_limits; ++i) KX_REQUIRE(limit_spec_ok(hc.req_limits[i]), "infer: bad limit");
+void check_spec_list(const HostCall& hc, const SpecList<LoudSpec>& list) {
+    check_list(hc, list, loud_spec_ok, "infer: null loudness argument", "infer: bad loudness count", "infer: bad loudness");
+}
+void check_spec_list(const HostCall& hc, const SpecList<LimitSpec>& list) {
+    check_list(hc, list, limit_spec_ok, "infer: null limit argument", "infer: bad limit count", "infer: bad limit");
 }
 
 void check_prosody_call(const HostCall& hc, const int32_t* lens, int B, int64_t t_stride, float** out_report, int64_t* out_n_report) {

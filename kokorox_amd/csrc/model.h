@@ -188,14 +188,9 @@ class Model {
                     const float* speeds, int n_speed, uint64_t seed, uint32_t flags, float** out,
                     int64_t* out_lens, const uint64_t* utt_seeds = nullptr);
     using HostCall = kx::HostCall;  // (host_request.h)
+    using HostResults = kx::HostResults;
     void infer_host_ex(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
-                       int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out, int64_t* out_bytes,
-                       int64_t* out_samples, int64_t** out_marks = nullptr, int64_t* out_n_marks = nullptr,
-                       double* out_levels = nullptr,     // [n_requests][2] = {f64(p), g} of a call with levels (may be null)
-                       double* out_loudness = nullptr,   // [n_requests][4] = {f64(p), g, I, n_g} of a call with loudness (may be null)
-                       double* out_limits = nullptr,     // [n_requests][5] = {f64(p), g, I, n_g, r} of a call with limits, the limited requests' rows (may be null)
-                       float** out_report = nullptr,     // a call with prosody (HostCall::prosody_call): the report block inside *out and
-                       int64_t* out_n_report = nullptr); // [n_requests] tokens of each request in it (both null: no report)
+                       int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, const HostResults& res);
     // [0] recurrence in use: 0 = resident weights (two / four workgroups), 1 = the streaming fall-back; [1] hand-off time-outs so
     // far; [2] clean forwards left until the resident forms return (0 when they are in use); [3] calls re-run transparently
     void status(int64_t out[4]) const;
@@ -382,9 +377,7 @@ class Model {
     int lstm_rearm_in_ = 0;
     int64_t n_lstm_timeouts_ = 0, n_rerun_ = 0;
     void infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds, int n_speed,
-                         uint64_t seed, uint32_t flags, const HostCall& hc, void** out, int64_t* out_bytes, int64_t* out_samples,
-                         int64_t** out_marks, int64_t* out_n_marks, double* out_levels, double* out_loudness, double* out_limits,
-                         float** out_report, int64_t* out_n_report);
+                         uint64_t seed, uint32_t flags, const HostCall& hc, const HostResults& res);
     // The running host call's prosody on the device (include/kokorox_hip.h, "prosody"): infer_host_once sets it around its forward,
     // front_half and back_half read it.  All null: a plain call, which launches what it always launched.
     struct ProsodyDev {

@@ -40,7 +40,7 @@ void Model::warmup(int B, int n_tokens, int frames_per_token) {
     hc.styles = styles.data();
     void* out = nullptr;
     std::vector<int64_t> bytes((size_t)B), samples((size_t)B);
-    infer_host_ex(ids.data(), n_tokens, lens.data(), B, &speed, 1, 0, 1u /* noise off */, hc, &out, bytes.data(), samples.data());
+    infer_host_ex(ids.data(), n_tokens, lens.data(), B, &speed, 1, 0, 1u /* noise off */, hc, HostResults{&out, bytes.data(), samples.data()});
     host_out_free(out);
 }
 
@@ -108,38 +108,32 @@ void Model::infer_host(const int64_t* ids, int64_t t_stride, const int32_t* lens
     void* p = nullptr;
     *out = nullptr;
     std::vector<int64_t> bytes(B > 0 ? B : 1);
-    infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, &p, bytes.data(), out_lens);
+    infer_host_ex(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, HostResults{&p, bytes.data(), out_lens});
     *out = static_cast<float*>(p);
 }
 
 // A hand-off time-out of the resident-weights recurrence invalidates the call it happened in, not the request: the host entry
 // points run the call once more, now on the streaming recurrence (same bits), and the caller sees a result, not an error.
 void Model::infer_host_ex(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
-                          int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out,
-                          int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, double* out_levels,
-                          double* out_loudness, double* out_limits, float** out_report, int64_t* out_n_report) {
+                          int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, const HostResults& res) {
     try {
-        infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks,
-                        out_levels, out_loudness, out_limits, out_report, out_n_report);
+        infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, res);
     } catch (const LstmTimeout&) {
         n_rerun_ += 1;
-        infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, out, out_bytes, out_samples, out_marks, out_n_marks,
-                        out_levels, out_loudness, out_limits, out_report, out_n_report);
+        infer_host_once(ids, t_stride, lens, B, speeds, n_speed, seed, flags, hc, res);
     }
     note_clean_forward();
 }
 
 void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t* lens, int B, const float* speeds,
-                            int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, void** out,
-                            int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
-                            double* out_levels, double* out_loudness, double* out_limits, float** out_report, int64_t* out_n_report) {
-    check_host_call(ids, t_stride, lens, B, speeds, hc, out, out_bytes, out_samples, n_vocab_, n_voices_, d_voices_ != nullptr);
-    if (hc.join_call) check_join_call(hc);
-    if (hc.req_marks) check_marks_call(hc, out_marks, out_n_marks);
-    if (hc.level_call) check_level_call(hc);
-    if (hc.loud_call) check_loudness_call(hc);
-    if (hc.limit_call) check_limit_call(hc);
-    if (hc.prosody_call) check_prosody_call(hc, lens, B, t_stride, out_report, out_n_report);
+                            int n_speed, uint64_t seed, uint32_t flags, const HostCall& hc, const HostResults& res) {
+    check_host_call(ids, t_stride, lens, B, speeds, hc, res.out, res.out_bytes, res.out_samples, n_vocab_, n_voices_, d_voices_ != nullptr);
+    if (hc.joins.call) check_spec_list(hc, hc.joins);
+    if (hc.req_marks) check_marks_call(hc, res.out_marks, res.out_n_marks);
+    if (hc.levels.call) check_spec_list(hc, hc.levels);
+    if (hc.loudness.call) check_spec_list(hc, hc.loudness);
+    if (hc.limits.call) check_spec_list(hc, hc.limits);
+    if (hc.prosody_call) check_prosody_call(hc, lens, B, t_stride, res.out_report, res.out_n_report);
     const bool by_voice = hc.by_voice();
     // one way to lay the output out and pack it: a call without chunks_per_request is R = B single-row requests in hc.format
     const RequestLayout layout = hc.layout(B);
@@ -288,10 +282,10 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         OutputPlan& plan = output_plan_;
         build_output_plan(call_.hF.data(), lens, joins ? h_edge_.data() : nullptr, B, layout, plan);
         for (int r = 0; r < R; ++r) {
-            out_samples[r] = plan.req[(size_t)r].n_samples;
-            out_bytes[r] = plan.req[(size_t)r].out_bytes;
-            if (marks) out_n_marks[r] = plan.count[(size_t)r];
-            if (out_n_report) out_n_report[r] = layout.reports ? plan.rep_count[(size_t)r] : 0;
+            res.out_samples[r] = plan.req[(size_t)r].n_samples;
+            res.out_bytes[r] = plan.req[(size_t)r].out_bytes;
+            if (marks) res.out_n_marks[r] = plan.count[(size_t)r];
+            if (res.out_n_report) res.out_n_report[r] = layout.reports ? plan.rep_count[(size_t)r] : 0;
         }
         KX_REQUIRE(plan.n_report == n_report, "prosody: the report's rows changed under the call");
         KX_REQUIRE((size_t)plan.peak_dwords() <= peak_cap, "levels: the peak table is too small");
@@ -324,7 +318,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         // behind the bodies stay where the plan put them)
         if (plan.has_flac()) {
             try {
-                close_flac_gaps(host, plan, reinterpret_cast<const int64_t*>(host + plan.flac_off), out_bytes);
+                close_flac_gaps(host, plan, reinterpret_cast<const int64_t*>(host + plan.flac_off), res.out_bytes);
             } catch (...) {
                 host_out_free(host);
                 throw;
@@ -339,17 +333,17 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             }
             for (int b = 0; b < B; ++b) memcpy(hc.out_durations + (size_t)b * t_stride, &h_dur[(size_t)b * 512], (size_t)lens[b] * sizeof(int));
         }
-        *out = host;
-        if (out_report) *out_report = plan.has_report() ? reinterpret_cast<float*>(host + plan.report_off) : nullptr;
-        if (marks) *out_marks = n_marks > 0 ? reinterpret_cast<int64_t*>(host + marks_off) : nullptr;
-        if (plan.measured && out_levels) memcpy(out_levels, host + plan.levels_off, (size_t)R * 16);
-        if (plan.limited && out_limits)
+        *res.out = host;
+        if (res.out_report) *res.out_report = plan.has_report() ? reinterpret_cast<float*>(host + plan.report_off) : nullptr;
+        if (marks) *res.out_marks = n_marks > 0 ? reinterpret_cast<int64_t*>(host + marks_off) : nullptr;
+        if (plan.measured && res.out_levels) memcpy(res.out_levels, host + plan.levels_off, (size_t)R * 16);
+        if (plan.limited && res.out_limits)
             for (int r = 0; r < R; ++r)
-                if (plan.limit[(size_t)r].off >= 0) memcpy(out_limits + 5 * r, host + plan.limits_off + 40 * (size_t)r, 40);
-        if (!plan.loud.empty() && out_loudness)
+                if (plan.limit[(size_t)r].off >= 0) memcpy(res.out_limits + 5 * r, host + plan.limits_off + 40 * (size_t)r, 40);
+        if (!plan.loud.empty() && res.out_loudness)
             for (int r = 0; r < R; ++r) {  // {f64(p), g} of the levels block, {I, n_g} of the loudness block
-                memcpy(out_loudness + 4 * r, host + plan.levels_off + 16 * (size_t)r, 16);
-                memcpy(out_loudness + 4 * r + 2, host + plan.loud_off + 16 * (size_t)r, 16);
+                memcpy(res.out_loudness + 4 * r, host + plan.levels_off + 16 * (size_t)r, 16);
+                memcpy(res.out_loudness + 4 * r + 2, host + plan.loud_off + 16 * (size_t)r, 16);
             }
         return;
     }

@@ -632,7 +632,7 @@ class HipKoko:
         0..2 (float32, [n, 2] float32, int16) and the G.711 forms (uint8), the body as `bytes` for PACK_WAV_F32,
         PACK_WAV16_BASE64 and PACK_FLAC (whose size follows from the samples).  with_samples: also the library's own sample count of every request (out_samples, at the output
         rate), as a second list."""
-        res, _, nsamp = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, False)
+        res, _, nsamp, _ = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, False)
         return (res, nsamp) if with_samples else res
 
     def infer_requests_marks(self, tokens, chunks_per_request, styles=None, voice_ids=None, weights=None, speeds=(1.0,),
@@ -641,7 +641,7 @@ class HipKoko:
         include/kokorox_hip.h, the numpy form voices.token_marks).  Returns (bodies, marks): bodies exactly as infer_requests,
         marks one int64 array per request -- per chunk its tokens + 1 sample offsets in the request's stream at the request's
         output rate, the chunks back to back (voices.token_spans splits them).  with_samples: out_samples as a third entry."""
-        res, marks, nsamp = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, True)
+        res, marks, nsamp, _ = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, True)
         return (res, marks, nsamp) if with_samples else (res, marks)
 
     def infer_requests_joined(self, tokens, chunks_per_request, joins, styles=None, voice_ids=None, weights=None, speeds=(1.0,),
@@ -651,7 +651,7 @@ class HipKoko:
         (flags, keep_ms, pause_ms, fade_ms) for all requests, or a list of one per request.  Returns the bodies as
         infer_requests does; marks=True: (bodies, marks) as infer_requests_marks.  with_samples: out_samples as a last entry."""
         j = join_specs(joins)
-        res, mk, nsamp = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, marks, j)
+        res, mk, nsamp, _ = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, marks, j)
         out = (res, mk) if marks else (res,)
         out = out + (nsamp,) if with_samples else out
         return out if len(out) > 1 else out[0]
@@ -702,6 +702,8 @@ class HipKoko:
 
     def _infer_requests(self, tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, want_marks, joins=None,
                         levels=None, loudness=None, limits=None, prosody=None):
+        """The call behind every infer_requests*: returns (bodies, marks, out_samples, extra) with marks None unless wanted and extra
+        the [R, k] values of the level, loudness or limit list, the reports of a call with prosody that wants them, else None."""
         ids, lens = self._ids_lens(tokens)
         B = len(tokens)
         cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32).reshape(-1)
@@ -720,51 +722,40 @@ class HipKoko:
         nbytes, nsamp = np.zeros(max(R, 1), np.int64), np.zeros(max(R, 1), np.int64)
         args = (self._h, _ptr(ids), ids.shape[1], _ptr(lens), B, _ptr(cpr), R, _ptr(st), _ptr(v), _ptr(w), mm, _ptr(sp), sp.shape[0],
                 seed, flags, _ptr(fm), fm.shape[0], C.byref(out), _ptr(nbytes), _ptr(nsamp))
-        marks = None
-        if want_marks:
-            mk, n_mk = C.c_void_p(), np.zeros(max(R, 1), np.int64)
-        report = None
+        mk, n_mk = C.c_void_p(), np.zeros(max(R, 1), np.int64)
+        # what every entry behind kx_infer_requests_marks takes next: the marks pair (both null: no marks), then the joins
+        tail = (C.byref(mk) if want_marks else None, _ptr(n_mk) if want_marks else None, _ptr(joins), 0 if joins is None else joins.shape[0])
+        # the one spec list that is set picks its entry: (list, entry, float64 values per request that come back)
+        spec = next(((s, fn, k) for s, fn, k in ((limits, self._lib.kx_infer_requests_limited, 5), (loudness, self._lib.kx_infer_requests_loudness, 4),
+                                                  (levels, self._lib.kx_infer_requests_levelled, 2)) if s is not None), None)
+        marks = extra = keep = None
         if prosody is not None:  # (prosody, want the report)
             ps, keep = prosody_arrays(prosody[0], lens, ids.shape[1])
             rp, n_rp = C.c_void_p(), np.zeros(max(R, 1), np.int64)
-            rc = self._lib.kx_infer_requests_prosody(*args, C.byref(mk) if want_marks else None, _ptr(n_mk) if want_marks else None,
-                                                     _ptr(joins), 0 if joins is None else joins.shape[0],
-                                                     None if ps is None else C.addressof(ps), C.byref(rp) if prosody[1] else None,
+            rc = self._lib.kx_infer_requests_prosody(*args, *tail, None if ps is None else C.addressof(ps), C.byref(rp) if prosody[1] else None,
                                                      _ptr(n_rp) if prosody[1] else None)
-            del keep
-            self._check(rc)
-            if prosody[1]:  # (it lives in the buffer of `out`: read before it is released)
-                n_tok = int(n_rp[:R].sum())
-                if n_tok and ((rp.value or 0) % 8 != 0 or not (out.value <= (rp.value or 0))):
-                    self._lib.kx_free_packed(out)
-                    raise KokoroxHipError(3, "the report is not 8-byte aligned inside the packed buffer")
-                flat_r = np.frombuffer(C.string_at(rp, 16 * n_tok) if n_tok else b"", dtype=np.float32).reshape(-1, 4).copy()
-                report = [x.copy() for x in np.split(flat_r, np.cumsum(n_rp[:R])[:-1])]
-        elif limits is not None:
-            out_lv = np.zeros((max(R, 1), 5), np.float64)
-            self._check(self._lib.kx_infer_requests_limited(*args, C.byref(mk) if want_marks else None, _ptr(n_mk) if want_marks else None,
-                                                            _ptr(joins), 0 if joins is None else joins.shape[0], _ptr(limits),
-                                                            limits.shape[0], _ptr(out_lv)))
-        elif loudness is not None:
-            out_lv = np.zeros((max(R, 1), 4), np.float64)
-            self._check(self._lib.kx_infer_requests_loudness(*args, C.byref(mk) if want_marks else None, _ptr(n_mk) if want_marks else None,
-                                                             _ptr(joins), 0 if joins is None else joins.shape[0], _ptr(loudness),
-                                                             loudness.shape[0], _ptr(out_lv)))
-        elif levels is not None:
-            out_lv = np.zeros((max(R, 1), 2), np.float64)
-            self._check(self._lib.kx_infer_requests_levelled(*args, C.byref(mk) if want_marks else None, _ptr(n_mk) if want_marks else None,
-                                                             _ptr(joins), 0 if joins is None else joins.shape[0], _ptr(levels),
-                                                             levels.shape[0], _ptr(out_lv)))
+        elif spec is not None:
+            extra = np.zeros((max(R, 1), spec[2]), np.float64)
+            rc = spec[1](*args, *tail, _ptr(spec[0]), spec[0].shape[0], _ptr(extra))
+            extra = extra[:R]
         elif joins is not None:
-            self._check(self._lib.kx_infer_requests_joined(*args, C.byref(mk) if want_marks else None, _ptr(n_mk) if want_marks else None,
-                                                           _ptr(joins), joins.shape[0]))
+            rc = self._lib.kx_infer_requests_joined(*args, *tail)
         elif want_marks:
-            self._check(self._lib.kx_infer_requests_marks(*args, C.byref(mk), _ptr(n_mk)))
+            rc = self._lib.kx_infer_requests_marks(*args, *tail[:2])
         else:
-            self._check(self._lib.kx_infer_requests(*args))
+            rc = self._lib.kx_infer_requests(*args)
+        del keep
+        self._check(rc)
+        if prosody is not None and prosody[1]:  # (the report lives in the buffer of `out`: read before it is released)
+            n_tok = int(n_rp[:R].sum())
+            if n_tok and ((rp.value or 0) % 8 != 0 or not (out.value <= (rp.value or 0))):
+                self._lib.kx_free_packed(out)
+                raise KokoroxHipError(3, "the report is not 8-byte aligned inside the packed buffer")
+            flat_r = np.frombuffer(C.string_at(rp, 16 * n_tok) if n_tok else b"", dtype=np.float32).reshape(-1, 4).copy()
+            extra = [x.copy() for x in np.split(flat_r, np.cumsum(n_rp[:R])[:-1])]
         total = int(nbytes[:R].sum())
         raw = C.string_at(out, total) if total else b""
-        if want_marks:  # (they live in the buffer of `out`: read before it is released)
+        if want_marks:  # (the marks as well)
             if (mk.value or 0) % 8 != 0 or not (out.value <= mk.value):
                 self._lib.kx_free_packed(out)
                 raise KokoroxHipError(3, "marks are not 8-byte aligned inside the packed buffer")
@@ -777,11 +768,7 @@ class HipKoko:
             part = raw[o: o + int(nbytes[r])]
             o += int(nbytes[r])
             res.append(_decode_packed(part, int(fm[r if fm.shape[0] > 1 else 0])))
-        if levels is not None or loudness is not None or limits is not None:
-            return res, marks, [int(v) for v in nsamp[:R]], out_lv[:R]
-        if prosody is not None:
-            return res, marks, [int(v) for v in nsamp[:R]], report
-        return res, marks, [int(v) for v in nsamp[:R]]
+        return res, marks, [int(v) for v in nsamp[:R]], extra
 
     def infer_device(self, d_ids: int, t_stride: int, lens_host: np.ndarray, d_styles: int, speeds_host: np.ndarray,
                      d_audio: int, audio_ld: int, d_frames: int, seed: int = 0, flags: int = 0) -> int:
@@ -1034,43 +1021,35 @@ class Dispatcher:
         args = (self._d, _ptr(a), _ptr(lens), len(chunks), _ptr(st), _ptr(vid), _ptr(w), n_mix, float(speed), seed, fmt, C.byref(out),
                 C.byref(nb), C.byref(ns))
         mk, n_mk = C.c_void_p(), C.c_int64(0)
-        lv_out = np.zeros(2, np.float64)
-        ld_out = np.zeros(4, np.float64)
-        lm_out = np.zeros(5, np.float64)
         if (loudness is not None) + (level is not None) + (limit is not None) > 1:
             raise ValueError("submit_request: a request has a level or a loudness, not both" if limit is None else
                              "submit_request: a request has a level, a loudness or a limit, not two of them")
+        if (prosody is not None or report) and (level is not None or loudness is not None or limit is not None):
+            raise ValueError("submit_request: prosody does not go with a level, a loudness or a limit")
         rp, n_rp = C.c_void_p(), C.c_int64(0)
+        # what every entry behind kx_dispatcher_submit_request_marks takes next: the marks pair (both null: no marks), then the join
+        j = None if join is None else join_specs(join, 1)
+        tail = (C.byref(mk) if marks else None, C.byref(n_mk) if marks else None, _ptr(j))
+        # the one spec that is set picks its entry: (spec, entry, the float64 values that come back)
+        spec = next(((make(s, 1), fn, np.zeros(k, np.float64)) for s, make, fn, k in
+                     ((limit, limit_specs, self._lib.kx_dispatcher_submit_request_limited, 5),
+                      (loudness, loudness_specs, self._lib.kx_dispatcher_submit_request_loudness, 4),
+                      (level, level_specs, self._lib.kx_dispatcher_submit_request_levelled, 2)) if s is not None), None)
+        keep = None
         if prosody is not None or report:
-            if level is not None or loudness is not None or limit is not None:
-                raise ValueError("submit_request: prosody does not go with a level, a loudness or a limit")
-            j = None if join is None else join_specs(join, 1)
             flat = None if prosody is None else tuple(None if x is None else [np.concatenate([np.asarray(c).reshape(-1) for c in x])] for x in prosody)
             ps, keep = prosody_arrays(flat, [int(lens.sum())], int(lens.sum()))
-            rc = self._lib.kx_dispatcher_submit_request_prosody(*args, C.byref(mk) if marks else None, C.byref(n_mk) if marks else None,
-                                                                _ptr(j), None if ps is None else C.addressof(ps),
+            rc = self._lib.kx_dispatcher_submit_request_prosody(*args, *tail, None if ps is None else C.addressof(ps),
                                                                 C.byref(rp) if report else None, C.byref(n_rp) if report else None, err, len(err))
-            del keep
-        elif limit is not None:
-            j = None if join is None else join_specs(join, 1)
-            rc = self._lib.kx_dispatcher_submit_request_limited(*args, C.byref(mk) if marks else None, C.byref(n_mk) if marks else None,
-                                                                _ptr(j), _ptr(limit_specs(limit, 1)), _ptr(lm_out), err, len(err))
-        elif loudness is not None:
-            j = None if join is None else join_specs(join, 1)
-            rc = self._lib.kx_dispatcher_submit_request_loudness(*args, C.byref(mk) if marks else None, C.byref(n_mk) if marks else None,
-                                                                 _ptr(j), _ptr(loudness_specs(loudness, 1)), _ptr(ld_out), err, len(err))
-        elif level is not None:
-            j = None if join is None else join_specs(join, 1)
-            rc = self._lib.kx_dispatcher_submit_request_levelled(*args, C.byref(mk) if marks else None, C.byref(n_mk) if marks else None,
-                                                                 _ptr(j), _ptr(level_specs(level, 1)), _ptr(lv_out), err, len(err))
+        elif spec is not None:
+            rc = spec[1](*args, *tail, _ptr(spec[0]), _ptr(spec[2]), err, len(err))
         elif join is not None:
-            j = join_specs(join, 1)
-            rc = self._lib.kx_dispatcher_submit_request_joined(*args, C.byref(mk) if marks else None, C.byref(n_mk) if marks else None,
-                                                               _ptr(j), err, len(err))
+            rc = self._lib.kx_dispatcher_submit_request_joined(*args, *tail, err, len(err))
         elif marks:
-            rc = self._lib.kx_dispatcher_submit_request_marks(*args, C.byref(mk), C.byref(n_mk), err, len(err))
+            rc = self._lib.kx_dispatcher_submit_request_marks(*args, *tail[:2], err, len(err))
         else:
             rc = self._lib.kx_dispatcher_submit_request(*args, err, len(err))
+        del keep
         if rc != 0:
             raise KokoroxHipError(rc, err.value.decode())
         try:
@@ -1086,9 +1065,7 @@ class Dispatcher:
         finally:
             self._lib.kx_free_packed(out)
         res = (_decode_packed(raw, fmt), m) if marks else (_decode_packed(raw, fmt),)
-        res = res + (lv_out,) if level is not None else res
-        res = res + (ld_out,) if loudness is not None else res
-        res = res + (lm_out,) if limit is not None else res
+        res = res + (spec[2],) if spec is not None else res
         res = res + (rep_out,) if report else res
         return res if len(res) > 1 else res[0]
 

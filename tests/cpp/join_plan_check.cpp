@@ -1,5 +1,5 @@
 // CPU driver of the join layout (kokorox_amd/csrc/host_request.cpp: build_output_plan with joins and marks,
-// output_bounds, check_join_call): built with g++ -fsanitize=address,undefined
+// output_bounds, check_spec_list): built with g++ -fsanitize=address,undefined
 // together with host_request.cpp by tests/test_joins_cpu.py and run as a child process.  It judges nothing itself: it prints
 // what the unit under test lays out, and the test compares that with the hand-derived answers of tests/golden/joins.json and
 // with the numpy definition (kokorox_amd/voices.py).
@@ -137,8 +137,8 @@ bool run_case() {
     hc.req_formats = words.data();
     hc.n_req_formats = R;
     hc.req_marks = want8.data();
-    hc.req_joins = joins.data();
-    hc.n_req_joins = R;
+    hc.joins.specs = joins.data();
+    hc.joins.n = R;
     const size_t n_samples = (size_t)600 * (size_t)frames_all;
     const kx::OutputBounds bound = kx::output_bounds(hc.layout(B), B, n_samples, lens.data());
     printf("sizes %ld %ld %ld %zu %zu %d\n", plan.total_bytes, mp.end_bytes(), plan.y_floats, bound.packed_bytes, bound.y_floats,
@@ -154,13 +154,13 @@ void refusal(const char* name, const kx::JoinSpec* joins, int n_join, bool marks
     hc.n_requests = 3;
     hc.req_formats = words;
     hc.n_req_formats = 1;
-    hc.join_call = true;
-    hc.req_joins = joins;
-    hc.n_req_joins = n_join;
+    hc.joins.call = true;
+    hc.joins.specs = joins;
+    hc.joins.n = n_join;
     int64_t* mk = nullptr;
     int64_t n_mk[3] = {0, 0, 0};
     try {
-        kx::check_join_call(hc);
+        kx::check_spec_list(hc, hc.joins);
         if (marks) {  // (the entry sets req_marks when either marks argument is there)
             hc.req_marks = want;
             kx::check_marks_call(hc, one_mark_null ? nullptr : &mk, n_mk);

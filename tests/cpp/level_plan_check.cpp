@@ -1,5 +1,5 @@
 // CPU driver of the levels layout (kokorox_amd/csrc/host_request.cpp: build_output_plan with levels, output_bounds,
-// check_level_call) and of the dispatcher's levelled submit: built with g++ -fsanitize=address,undefined together with
+// check_spec_list) and of the dispatcher's levelled submit: built with g++ -fsanitize=address,undefined together with
 // host_request.cpp by tests/test_levels_cpu.py and run as a child process.  It prints what the unit under test lays out, and the
 // test compares that with its own arithmetic.
 //
@@ -140,14 +140,14 @@ bool run_case() {
     hc.n_req_formats = R;
     hc.req_marks = want8.data();
     if (has_joins) {
-        hc.req_joins = joins.data();
-        hc.n_req_joins = R;
+        hc.joins.specs = joins.data();
+        hc.joins.n = R;
     }
     const size_t n_samples = (size_t)600 * (size_t)frames_all;
     const kx::OutputBounds without = kx::output_bounds(hc.layout(B), B, n_samples, lens.data());
     REQUIRE_SAME(without.peak_dwords == 0);
-    hc.req_levels = levels.data();
-    hc.n_req_levels = n_level;
+    hc.levels.specs = levels.data();
+    hc.levels.n = n_level;
     const kx::OutputBounds bound = kx::output_bounds(hc.layout(B), B, n_samples, lens.data());
     printf("bounds %zu %zu %zu %zu\n", bound.packed_bytes, bound.y_floats, bound.peak_dwords, without.packed_bytes);
     return true;
@@ -160,11 +160,11 @@ void refusal(const char* name, const kx::LevelSpec* levels, int n_level) {
     hc.n_requests = 3;
     hc.req_formats = words;
     hc.n_req_formats = 1;
-    hc.level_call = true;
-    hc.req_levels = levels;
-    hc.n_req_levels = n_level;
+    hc.levels.call = true;
+    hc.levels.specs = levels;
+    hc.levels.n = n_level;
     try {
-        kx::check_level_call(hc);
+        kx::check_spec_list(hc, hc.levels);
         printf("%s\taccepted\n", name);
     } catch (const kx::Error& e) {
         printf("%s\t%d\t%s\n", name, e.code, e.what());

@@ -1,4 +1,4 @@
-// CPU driver of the limiter in the host layout (kokorox_amd/csrc/host_request.cpp: limit_spec_ok, limit_taps, check_limit_call,
+// CPU driver of the limiter in the host layout (kokorox_amd/csrc/host_request.cpp: limit_spec_ok, limit_taps, check_spec_list,
 // build_output_plan, output_bounds) and of the dispatcher's submit: built with g++ -fsanitize=address,undefined together with
 // host_request.cpp by tests/test_limit_cpu.py and run as a child process.
 //
@@ -146,15 +146,15 @@ void refusal(const char* name, const kx::LimitSpec* limit, int n_limit, int R = 
     hc.n_requests = R;
     hc.req_formats = words;
     hc.n_req_formats = 1;
-    hc.limit_call = true;
-    hc.req_limits = limit;
-    hc.n_req_limits = n_limit;
-    hc.req_levels = level;
-    hc.n_req_levels = level ? 1 : 0;
-    hc.req_loudness = loud;
-    hc.n_req_loudness = loud ? 1 : 0;
+    hc.limits.call = true;
+    hc.limits.specs = limit;
+    hc.limits.n = n_limit;
+    hc.levels.specs = level;
+    hc.levels.n = level ? 1 : 0;
+    hc.loudness.specs = loud;
+    hc.loudness.n = loud ? 1 : 0;
     try {
-        kx::check_limit_call(hc);
+        kx::check_spec_list(hc, hc.limits);
         // ... and the planner itself, which checks every spec once more and that a request has one kind of spec
         const int frames[2] = {3, 3};
         const kx::RequestLayout lay = hc.layout(R);

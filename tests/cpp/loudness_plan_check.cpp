@@ -1,5 +1,5 @@
 // CPU driver of the loudness layout (kokorox_amd/csrc/host_request.cpp: build_output_plan with loudness, output_bounds,
-// check_loudness_call, the meter's tables) and of the dispatcher's loudness submit: built with g++ -fsanitize=address,undefined
+// check_spec_list, the meter's tables) and of the dispatcher's loudness submit: built with g++ -fsanitize=address,undefined
 // together with host_request.cpp by tests/test_loudness_cpu.py and run as a child process.
 //
 //   loudness_plan_check plans < cases   every case of the input: "name B R", frames [B], chunks_per_request [R], words [R],
@@ -134,11 +134,11 @@ void refusal(const char* name, const kx::LoudSpec* specs, int n) {
     hc.n_requests = 3;
     hc.req_formats = words;
     hc.n_req_formats = 1;
-    hc.loud_call = true;
-    hc.req_loudness = specs;
-    hc.n_req_loudness = n;
+    hc.loudness.call = true;
+    hc.loudness.specs = specs;
+    hc.loudness.n = n;
     try {
-        kx::check_loudness_call(hc);
+        kx::check_spec_list(hc, hc.loudness);
         printf("%s\taccepted\n", name);
     } catch (const kx::Error& e) {
         printf("%s\t%d\t%s\n", name, e.code, e.what());

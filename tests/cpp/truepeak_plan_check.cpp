@@ -140,15 +140,15 @@ void refusal(const char* name, const kx::LevelSpec* level, const kx::LoudSpec* l
     hc.n_requests = 1;
     hc.req_formats = words;
     hc.n_req_formats = 1;
-    hc.level_call = level != nullptr;
-    hc.req_levels = level;
-    hc.n_req_levels = level ? 1 : 0;
-    hc.loud_call = loud != nullptr;
-    hc.req_loudness = loud;
-    hc.n_req_loudness = loud ? 1 : 0;
+    hc.levels.call = level != nullptr;
+    hc.levels.specs = level;
+    hc.levels.n = level ? 1 : 0;
+    hc.loudness.call = loud != nullptr;
+    hc.loudness.specs = loud;
+    hc.loudness.n = loud ? 1 : 0;
     try {
-        if (level) kx::check_level_call(hc);
-        if (loud) kx::check_loudness_call(hc);
+        if (level) kx::check_spec_list(hc, hc.levels);
+        if (loud) kx::check_spec_list(hc, hc.loudness);
         // ... and the planner itself, which checks every spec once more
         const int frames[1] = {3};
         const kx::RequestLayout lay = hc.layout(1);

@@ -2,7 +2,7 @@
 
 Three layers, none of which needs a GPU: the numpy definition (kokorox_amd/voices.py: join_rows, join_stream, joined_marks)
 against answers worked out by hand (tests/golden/joins.json); the host layout (kokorox_amd/csrc/host_request.cpp:
-build_output_plan with joins and marks, output_bounds, check_join_call) and the dispatcher's submit-time checks,
+build_output_plan with joins and marks, output_bounds, check_spec_list) and the dispatcher's submit-time checks,
 built with g++ -fsanitize=address,undefined into tests/cpp/join_plan_check.cpp and run as a child process, against the golden
 answers and against the numpy definition on 200 seeded random cases; and the ABI (header, Python table, lib.rs).
 """

@@ -2,7 +2,7 @@
 
 Three layers, none of which needs a GPU: the numpy definition (kokorox_amd/voices.py: level_gain, level_stream) against answers
 worked out by hand (tests/golden/levels.json) and against exact rational arithmetic; the host layout
-(kokorox_amd/csrc/host_request.cpp: build_output_plan with levels, output_bounds, check_level_call) and the dispatcher's
+(kokorox_amd/csrc/host_request.cpp: build_output_plan with levels, output_bounds, check_spec_list) and the dispatcher's
 submit-time checks, built with g++ -fsanitize=address,undefined into tests/cpp/level_plan_check.cpp and run as a child process;
 and the ABI (header, Python table, lib.rs).
 """

@@ -4,7 +4,7 @@ Layers that need no GPU: the committed K-weighting table against its generator a
 coefficients; the numpy definition (kokorox_amd/voices.py: kweight, hop_energies, gated_loudness, integrated_loudness,
 loudness_gain, loudness_body) against the 997 Hz anchor of EBU Tech 3341 and against answers worked out by hand
 (tests/golden/loudness.json); the host layout (kokorox_amd/csrc/host_request.cpp: build_output_plan with loudness, output_bounds,
-check_loudness_call, the meter's tables) and the dispatcher's submit-time checks, built with g++ -fsanitize=address,undefined into
+check_spec_list, the meter's tables) and the dispatcher's submit-time checks, built with g++ -fsanitize=address,undefined into
 tests/cpp/loudness_plan_check.cpp and run as a child process; and the ABI (header, Python table, C++ wrapper, lib.rs).
 """
 import json
