@@ -690,6 +690,56 @@ int kx_infer_requests_prosody(kx_model* m, const int64_t* ids, int64_t t_stride,
                               int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_prosody* prosody,
                               float** out_report, int64_t* out_n_report);
 
+/* ---- fit: spans of a request's tokens made to last exactly so many frames ----------------------------------------------------
+ * The `duration` attribute of SSML's <prosody>: "this sentence takes exactly 2.4 s".  A frame is 600 samples at 24 000 Hz, 25 ms
+ * (Python: voices.fit_frames(seconds)).  A call carries n_spans spans, sorted by (request, begin) and disjoint; tokens
+ * [begin, end) of request `request` -- positions count the request's tokens with its chunks laid end to end, the two pad tokens of
+ * every chunk included -- get durations that add up to exactly `frames`.  A span may cross chunk boundaries; one span over all
+ * tokens fits the whole request.  For each span the GPU finds the one rate that does it (numpy twin: voices.fit_durations):
+ *   Weights.  Token t of row b has the float32 value s after steps (1) to (3) of "prosody" above (the sum of 50 sigmoids, / speed_b,
+ *   / rate[t] when given), before rintf.  w = s where 2^-20 <= s <= 2^20; below that 2^-20, above it 2^20, and a NaN gives 1.0f.
+ *   Held tokens.  A token whose prosody frames[t] >= 1 is held: it keeps that count and is no part of the fit.  Phi = the sum of
+ *   the held counts inside the span, n = its free tokens, G = frames - Phi = what the free tokens must add up to.
+ *   The fit.  For a float32 lambda > 0: d_t(lambda) = min(max(rintf(f32(w_t * lambda)), 1), 50) (one float32 multiply; an infinite
+ *   product gives 50) and F(lambda) = the sum of d_t(lambda) over the free tokens.  F is non-decreasing in lambda read as its bit
+ *   pattern.  Bisection over the patterns u in 0x00800000 .. 0x7F7FFFFF: while lo < hi, mid = lo + (hi - lo) / 2; F(mid) >= G ?
+ *   hi = mid : lo = mid + 1 (31 steps at most).  lambda = the float of lo, lambda- = the float of lo - 1, E = F(lambda) - G >= 0
+ *   the excess.  Between adjacent floats no d_t moves by more than 1 (DESIGN.md section 7 "Fit"), so at least E tokens have
+ *   d_t(lambda) = d_t(lambda-) + 1: the steppers.  Of them, the E with the highest token position keep d_t(lambda-); every other
+ *   free token gets d_t(lambda).  At lo = 0x00800000, E is 0.  The sum is G exactly.
+ *   The fitted counts are fixed frame counts as in step (6) of "prosody": marks, joins and the prosody report follow them.
+ *   A fit at the natural total need not reproduce the un-fitted durations token for token: every d_t of the span goes through one
+ *   common lambda and the tie rule, and lambda = 1 is only one of the patterns the bisection may end on.
+ *   The fit counts the model's frames.  A join that trims pads afterwards shortens the body as it always does: fit, then join.
+ *   Refusals, on the host before any device work, KX_ERR_INVALID "infer: bad fit" (dispatcher: "dispatcher_submit_request: bad
+ *   fit"): spans unsorted or overlapping; `request` outside 0..R-1; begin >= end or end past the request's tokens; n = 0; G < n or
+ *   G > 50 n; a null span array with n_spans != 0.  A model with a pinned duration pattern (kx_set_pinned_durations) refuses a call
+ *   that has spans: "infer: fit with pinned durations".  n_spans == 0 is the prosody call bit for bit.  Alignment rows hold 50
+ *   frames per token of the longest row; a fitted token has at most 50, so a span adds no overflow path.
+ *   Under KX_FLAG_TAPS, "pred.dur.weights" holds w [B,1,512] and "pred.dur.fitted" the fixed counts the duration kernel took (int32
+ *   bits in the float32 tap): the caller's, the fitted ones, 0 for a token nothing fixes.
+ *   Not offered: fit together with the levelled, loudness and limited entries; targets in samples or at the output rate; fitting the
+ *   stream after a join's trims; silence inside a chunk; SSML parsing. */
+typedef struct kx_fit_span {
+    int32_t request;  /* 0 .. R-1 */
+    int32_t begin;    /* first token of the span, counted over the request's chunks laid end to end */
+    int32_t end;      /* one past its last token */
+    int32_t frames;   /* what its durations add up to: 25 ms each */
+} kx_fit_span;
+typedef struct kx_fit_result {
+    float   lambda;       /* the factor the GPU chose for the span's weights; 1 / lambda is speed-like */
+    int32_t n_free;       /* n: tokens the fit set */
+    int32_t held_frames;  /* Phi */
+    int32_t excess;       /* E */
+} kx_fit_result;
+/* kx_infer_requests_prosody with spans; out_fit [n_spans] may be NULL.  `joins`, `prosody` and the report pair as there. */
+int kx_infer_requests_fitted(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                             const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                             const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                             const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                             int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_prosody* prosody,
+                             float** out_report, int64_t* out_n_report, const kx_fit_span* spans, int n_spans, kx_fit_result* out_fit);
+
 /* ---- request dispatcher ----------------------------------------------------
  * Replaces the reference's one-request-at-a-time `Mutex<Session>` (kokorox/src/onn/ort_koko.rs:78; callers
  * kokorox-openai/src/lib.rs:370-439, kokorox-websocket/src/lib.rs:657-668).  Any number of threads submit
@@ -804,6 +854,16 @@ int kx_dispatcher_submit_request_prosody(kx_dispatcher* d, const int64_t* ids, c
                                          int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
                                          const kx_prosody* prosody, float** out_report, int64_t* out_n_report, char* err,
                                          size_t err_len);
+/* kx_dispatcher_submit_request_prosody with the request's fit spans (see "fit" above): `request` of every span must be 0, positions
+ * count the request's tokens, chunks back to back; out_fit [n_spans] may be NULL.  A refusal of "fit":
+ * "dispatcher_submit_request: bad fit".  Fitted and plain requests share batches; a request's bytes, marks, report and fit results
+ * equal those of kx_infer_requests_fitted (R = 1, same seed, utterance base 0) whatever it was batched with. */
+int kx_dispatcher_submit_request_fitted(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                        const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
+                                        float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
+                                        int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
+                                        const kx_prosody* prosody, float** out_report, int64_t* out_n_report,
+                                        const kx_fit_span* spans, int n_spans, kx_fit_result* out_fit, char* err, size_t err_len);
 /* n_requests counts requests, max_batch_seen the largest batch in ROWS (a request of n chunks is n rows). */
 int kx_dispatcher_stats(kx_dispatcher* d, int64_t* n_requests, int64_t* n_batches, int64_t* max_batch_seen);
 /* batches each model (worker) has run so far: per_model[n_models] */

@@ -62,6 +62,17 @@ struct ProsodyToken {
     float f0_hz, voiced_steps, energy, frames;
 };
 
+// A fit span and what the GPU chose for it ("fit" in kokorox_hip.h): tokens [begin, end) of request `request`, its chunks laid end
+// to end, last exactly `frames` frames of 25 ms; lambda is the factor on the span's weights, 1 / lambda speed-like.
+struct FitSpan {
+    int32_t request, begin, end, frames;
+};
+struct FitResult {
+    float lambda;
+    int32_t n_free, held_frames, excess;
+};
+static_assert(sizeof(FitSpan) == sizeof(kx_fit_span) && sizeof(FitResult) == sizeof(kx_fit_result), "the layouts of kokorox_hip.h");
+
 class HipKoko {
   public:
     explicit HipKoko(const std::string& model_path, int device = 0) {
@@ -267,6 +278,52 @@ class HipKoko {
             for (int64_t i = 0; i < nr[r]; ++i) tok[(size_t)i] = ProsodyToken{rp[4 * i], rp[4 * i + 1], rp[4 * i + 2], rp[4 * i + 3]};
             rp += 4 * nr[r];
             report.push_back(std::move(tok));
+        }
+        kx_free_packed(out);
+        return bodies;
+    }
+
+    // infer_requests with fit spans (kx_infer_requests_fitted; "fit" in kokorox_hip.h): `spans` sorted by (request, begin) and
+    // disjoint; no prosody arrays, no joins, no marks, no report.  fit[i] = what the GPU chose for spans[i].
+    std::vector<std::string> infer_requests_fitted(const std::vector<std::vector<int64_t>>& tokens,
+                                                   const std::vector<int32_t>& chunks_per_request,
+                                                   const std::vector<std::vector<float>>& styles, float speed, uint64_t seed, int format,
+                                                   const std::vector<FitSpan>& spans, std::vector<FitResult>& fit) const {
+        if (tokens.empty() || styles.size() != tokens.size()) throw std::invalid_argument("infer_requests: one style row per chunk");
+        const int B = (int)tokens.size(), R = (int)chunks_per_request.size();
+        size_t stride = 1;
+        for (const auto& t : tokens) stride = t.size() > stride ? t.size() : stride;
+        std::vector<int64_t> ids((size_t)B * stride, 0);
+        std::vector<int32_t> tl(B);
+        std::vector<float> st((size_t)B * KX_STYLE_DIM);
+        for (int b = 0; b < B; ++b) {
+            tl[b] = (int32_t)tokens[b].size();
+            for (size_t i = 0; i < tokens[b].size(); ++i) ids[(size_t)b * stride + i] = tokens[b][i];
+            if (styles[b].size() != KX_STYLE_DIM) throw std::invalid_argument("infer_requests: style rows need 256 floats");
+            for (int k = 0; k < KX_STYLE_DIM; ++k) st[(size_t)b * KX_STYLE_DIM + k] = styles[b][k];
+        }
+        std::vector<kx_fit_span> sp(spans.size());
+        for (size_t i = 0; i < spans.size(); ++i) sp[i] = kx_fit_span{spans[i].request, spans[i].begin, spans[i].end, spans[i].frames};
+        std::vector<kx_fit_result> fr(spans.size() ? spans.size() : 1);
+        void* out = nullptr;
+        std::vector<int64_t> nb(R > 0 ? R : 1), ns(R > 0 ? R : 1);
+        const int32_t fmt = format;
+        const int rc = kx_infer_requests_fitted(h_, ids.data(), (int64_t)stride, tl.data(), B, chunks_per_request.data(), R, st.data(),
+                                                nullptr, nullptr, 0, &speed, 1, seed, 0, &fmt, 1, &out, nb.data(), ns.data(), nullptr,
+                                                nullptr, nullptr, 0, nullptr, nullptr, nullptr, sp.empty() ? nullptr : sp.data(),
+                                                (int)sp.size(), fr.data());
+        if (rc != KX_OK) {
+            char msg[512];
+            kx_last_error_copy(h_, msg, sizeof(msg));
+            throw std::runtime_error(std::string("kokorox_hip error: ") + msg);
+        }
+        fit.clear();
+        for (size_t i = 0; i < spans.size(); ++i) fit.push_back(FitResult{fr[i].lambda, fr[i].n_free, fr[i].held_frames, fr[i].excess});
+        std::vector<std::string> bodies;
+        const char* p = static_cast<const char*>(out);
+        for (int r = 0; r < R; ++r) {
+            bodies.emplace_back(p, p + nb[r]);
+            p += nb[r];
         }
         kx_free_packed(out);
         return bodies;

@@ -212,6 +212,16 @@ int kx_test_prosody_durations(int device_id, const float* logits, int B, int T, 
                               int idx_ld, int32_t* dur, int32_t* frames, int32_t* idx, float* gathered, int Fcap, uint32_t* overflow,
                               char* err, size_t err_len);
 
+/* kx_test_prosody_durations with the fit in front of it (include/kokorox_hip.h, "fit"): launch_fit_weights, launch_fit_spans, then
+ * launch_prosody_duration on the fitted counts.  rate and fixed may both be NULL here; there is no pinned pattern.  spans [n_spans]
+ * (n_spans >= 1) over the R requests of chunks_per_request (NULL: every row a request), checked by fit_ok ("test_fit_durations: bad
+ * fit").  Out, beside kx_test_alignment's: w [B,512] and fitted [B,512] whole as the kernels left them (0 at and past lens[b]), and
+ * results [n_spans].  The three start as sentinel / 0xA5 bytes with a guard behind each, checked here: KX_ERR_STATE. */
+int kx_test_fit_durations(int device_id, const float* logits, int B, int T, const int32_t* lens, const float* speeds, int n_speed,
+                          const float* rate, const int32_t* fixed, const int32_t* chunks_per_request, int R, const kx_fit_span* spans,
+                          int n_spans, const float* src, int C, int idx_ld, int32_t* dur, int32_t* frames, int32_t* idx, float* gathered,
+                          int Fcap, uint32_t* overflow, float* w, int32_t* fitted, kx_fit_result* results, char* err, size_t err_len);
+
 /* launch_prosody_curves on curves [B,2,2 Fcap] (row 0 = F0, row 1 = N; row b valid for 2 frames[b] steps, 1 <= frames[b] <= Fcap),
  * idx [B,idx_ld] (entries f < frames[b] in 0 .. lens[b] - 1), dur [B,T] (sum over t < lens[b] = frames[b]) and the per-token ratios
  * pitch / energy [B,T] (either may be NULL).  Out: shaped [B,2,2 Fcap], the whole rows as the kernel left them (what the caller had

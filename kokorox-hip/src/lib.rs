@@ -195,6 +195,28 @@ fn prosody_rows<V: Copy>(rows: &[Vec<V>], lens: &[i32], stride: usize, neutral: 
     Ok(flat)
 }
 
+/// A fit span (`kx_fit_span`; "fit" in kokorox_hip.h): tokens `[begin, end)` of request `request`, its chunks laid end to end,
+/// get durations that add up to exactly `frames` frames of 25 ms.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct KxFitSpan {
+    pub request: i32,
+    pub begin: i32,
+    pub end: i32,
+    pub frames: i32,
+}
+
+/// What the GPU chose for a span (`kx_fit_result`): the factor on its weights (`1 / lambda` is speed-like), its free tokens, the
+/// frames of its held tokens and the excess E.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct KxFitResult {
+    pub lambda: f32,
+    pub n_free: i32,
+    pub held_frames: i32,
+    pub excess: i32,
+}
+
 #[repr(C)]
 pub struct KxModel {
     _p: [u8; 0],
@@ -246,6 +268,20 @@ extern "C" {
                                  formats: *const c_int, n_format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
                                  out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64, joins: *const KxJoin,
                                  n_join: c_int, prosody: *const KxProsody, out_report: *mut *mut f32, out_n_report: *mut i64) -> c_int;
+    fn kx_infer_requests_fitted(m: *mut KxModel, ids: *const i64, t_stride: i64, lens: *const i32, b: c_int,
+                                chunks_per_request: *const i32, r: c_int, styles: *const f32, voice_ids: *const i32,
+                                weights: *const f32, max_mix: c_int, speeds: *const f32, n_speed: c_int, seed: u64, flags: u32,
+                                formats: *const c_int, n_format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                                out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64, joins: *const KxJoin,
+                                n_join: c_int, prosody: *const KxProsody, out_report: *mut *mut f32, out_n_report: *mut i64,
+                                spans: *const KxFitSpan, n_spans: c_int, out_fit: *mut KxFitResult) -> c_int;
+    fn kx_dispatcher_submit_request_fitted(d: *mut KxDispatcher, ids: *const i64, chunk_tokens: *const i32, n_chunks: c_int,
+                                           styles: *const f32, voice_ids: *const i32, weights: *const f32, n_mix: c_int,
+                                           speed: f32, seed: u64, format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                                           out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64,
+                                           join: *const KxJoin, prosody: *const KxProsody, out_report: *mut *mut f32,
+                                           out_n_report: *mut i64, spans: *const KxFitSpan, n_spans: c_int,
+                                           out_fit: *mut KxFitResult, err: *mut c_char, err_len: usize) -> c_int;
     fn kx_dispatcher_submit_request_prosody(d: *mut KxDispatcher, ids: *const i64, chunk_tokens: *const i32, n_chunks: c_int,
                                             styles: *const f32, voice_ids: *const i32, weights: *const f32, n_mix: c_int,
                                             speed: f32, seed: u64, format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
@@ -896,6 +932,57 @@ impl HipKoko {
         }
         unsafe { kx_free_packed(out) };
         Ok(res)
+    }
+
+    /// `infer_requests_prosody` with fit spans ("fit" in kokorox_hip.h): `spans` sorted by (request, begin) and disjoint.  Per
+    /// request: body and marks; then one `KxFitResult` per span.
+    #[allow(clippy::type_complexity, clippy::too_many_arguments)]
+    pub fn infer_requests_fitted(&self, tokens: &[Vec<i64>], chunks_per_request: &[i32], styles: &[Vec<f32>], speeds: &[f32],
+                                 seed: u64, formats: &[c_int], joins: &[KxJoin], prosody: &Prosody, spans: &[KxFitSpan])
+                                 -> Result<(Vec<(Vec<u8>, Vec<i64>)>, Vec<KxFitResult>), Box<dyn Error>> {
+        if tokens.is_empty() || styles.len() != tokens.len() || styles.iter().any(|s| s.len() != KX_STYLE_DIM) {
+            return Err("infer_requests: one style row of 256 floats per chunk is required".into());
+        }
+        let (b, r) = (tokens.len(), chunks_per_request.len());
+        let (ids, lens, stride) = Self::flatten(tokens);
+        let st: Vec<f32> = styles.iter().flatten().copied().collect();
+        let rate = prosody_rows(&prosody.rate, &lens, stride as usize, 1f32)?;
+        let frames = prosody_rows(&prosody.frames, &lens, stride as usize, 0i32)?;
+        let pitch = prosody_rows(&prosody.pitch, &lens, stride as usize, 1f32)?;
+        let energy = prosody_rows(&prosody.energy, &lens, stride as usize, 1f32)?;
+        let ps = KxProsody {
+            rate: if rate.is_empty() { ptr::null() } else { rate.as_ptr() },
+            frames: if frames.is_empty() { ptr::null() } else { frames.as_ptr() },
+            pitch: if pitch.is_empty() { ptr::null() } else { pitch.as_ptr() },
+            energy: if energy.is_empty() { ptr::null() } else { energy.as_ptr() },
+        };
+        let mut out: *mut c_void = ptr::null_mut();
+        let mut mk: *mut i64 = ptr::null_mut();
+        let (mut nbytes, mut nsamp, mut nmarks) = (vec![0i64; r.max(1)], vec![0i64; r.max(1)], vec![0i64; r.max(1)]);
+        let mut fit = vec![KxFitResult::default(); spans.len().max(1)];
+        let rc = unsafe {
+            kx_infer_requests_fitted(self.h, ids.as_ptr(), stride as i64, lens.as_ptr(), b as c_int, chunks_per_request.as_ptr(),
+                                     r as c_int, st.as_ptr(), ptr::null(), ptr::null(), 0, speeds.as_ptr(), speeds.len() as c_int,
+                                     seed, 0, formats.as_ptr(), formats.len() as c_int, &mut out, nbytes.as_mut_ptr(),
+                                     nsamp.as_mut_ptr(), &mut mk, nmarks.as_mut_ptr(),
+                                     if joins.is_empty() { ptr::null() } else { joins.as_ptr() }, joins.len() as c_int, &ps,
+                                     ptr::null_mut(), ptr::null_mut(), if spans.is_empty() { ptr::null() } else { spans.as_ptr() },
+                                     spans.len() as c_int, fit.as_mut_ptr())
+        };
+        self.check(rc)?;
+        fit.truncate(spans.len());
+        let mut res = Vec::with_capacity(r);
+        let (mut at, mut mat) = (0usize, 0usize);
+        for i in 0..r {
+            // (the marks live in the buffer of `out`: copied before it is released)
+            let body = unsafe { std::slice::from_raw_parts((out as *const u8).add(at), nbytes[i] as usize) }.to_vec();
+            let marks = unsafe { std::slice::from_raw_parts((mk as *const i64).add(mat), nmarks[i] as usize) }.to_vec();
+            at += nbytes[i] as usize;
+            mat += nmarks[i] as usize;
+            res.push((body, marks));
+        }
+        unsafe { kx_free_packed(out) };
+        Ok((res, fit))
     }
 
     /// Raw device-pointer form (inputs and output stay in HBM).

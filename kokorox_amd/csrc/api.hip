@@ -382,6 +382,10 @@ struct RequestExtras {
     const kx_prosody* prosody = nullptr;  // both null (check_prosody_call)
     float** out_report = nullptr;
     int64_t* out_n_report = nullptr;
+    bool fit_entry = false;  // kx_infer_requests_fitted: the spans (n_spans == 0: none) and where their results go (may be null)
+    const kx_fit_span* spans = nullptr;
+    int n_spans = 0;
+    kx_fit_result* out_fit = nullptr;
 };
 
 static int infer_requests(const RequestArgs& a, const RequestExtras& x) {
@@ -424,6 +428,12 @@ static int infer_requests(const RequestArgs& a, const RequestExtras& x) {
             }
             res.out_report = x.out_report;
             res.out_n_report = x.out_n_report;
+        }
+        if (x.fit_entry) {
+            hc.fit_call = true;
+            hc.fit_spans = reinterpret_cast<const kx::FitSpan*>(x.spans);
+            hc.n_fit_spans = x.n_spans;
+            res.out_fit = reinterpret_cast<kx::FitResult*>(x.out_fit);
         }
         M.infer_host_ex(a.ids, a.t_stride, a.lens, a.B, a.speeds, a.n_speed, a.seed, a.flags, hc, res);
     });
@@ -472,6 +482,33 @@ int kx_infer_requests_prosody(kx_model* m, const int64_t* ids, int64_t t_stride,
     x.prosody_entry = true;
     x.prosody = prosody;
     x.out_report = out_report, x.out_n_report = out_n_report;
+    return infer_requests({m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
+                           flags, formats, n_format, out, out_bytes, out_samples},
+                          x);
+}
+
+static_assert(sizeof(kx_fit_span) == 16 && sizeof(kx_fit_span) == sizeof(kx::FitSpan) && offsetof(kx_fit_span, request) == offsetof(kx::FitSpan, request) &&
+                  offsetof(kx_fit_span, begin) == offsetof(kx::FitSpan, begin) && offsetof(kx_fit_span, end) == offsetof(kx::FitSpan, end) &&
+                  offsetof(kx_fit_span, frames) == offsetof(kx::FitSpan, frames),
+              "kx_fit_span is the layout of kx::FitSpan");
+static_assert(sizeof(kx_fit_result) == 16 && sizeof(kx_fit_result) == sizeof(kx::FitResult) &&
+                  offsetof(kx_fit_result, lambda) == offsetof(kx::FitResult, lambda) && offsetof(kx_fit_result, n_free) == offsetof(kx::FitResult, n_free) &&
+                  offsetof(kx_fit_result, held_frames) == offsetof(kx::FitResult, held_frames) &&
+                  offsetof(kx_fit_result, excess) == offsetof(kx::FitResult, excess),
+              "kx_fit_result is the layout of kx::FitResult");
+
+int kx_infer_requests_fitted(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                             const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                             const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                             const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                             int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_prosody* prosody,
+                             float** out_report, int64_t* out_n_report, const kx_fit_span* spans, int n_spans, kx_fit_result* out_fit) {
+    RequestExtras x{out_marks, out_n_marks, joins, n_join};
+    x.prosody_entry = true;
+    x.prosody = prosody;
+    x.out_report = out_report, x.out_n_report = out_n_report;
+    x.fit_entry = true;
+    x.spans = spans, x.n_spans = n_spans, x.out_fit = out_fit;
     return infer_requests({m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
                            flags, formats, n_format, out, out_bytes, out_samples},
                           x);

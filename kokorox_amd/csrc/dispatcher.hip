@@ -74,6 +74,12 @@ struct ModelBackend {
         std::vector<kx::LevelSpec> levels(R);  // (a request without levels beside a levelled one: the plain spec, z' = z)
         std::vector<kx::LoudSpec> louds(R);  // (a request without loudness beside a metered one: LOUD_NONE, the meter passes it by)
         std::vector<kx::LimitSpec> limits(R);  // (a request without a limiter beside a limited one: LIMIT_NONE, the limiter passes it by)
+        // the fit spans of the batch: every request's own, renumbered to its index in the batch (sorted by (request, begin) as the
+        // requests' own lists are); a request without spans adds none, and its tokens get zeros in the fitted counts
+        std::vector<kx::FitSpan> spans;
+        for (int q = 0; q < R; ++q)
+            for (const kx::FitSpan& f : batch[(size_t)q]->fit) spans.push_back(kx::FitSpan{q, f.begin, f.end, f.frames});
+        std::vector<kx::FitResult> fit_out(spans.size());
         int b = 0;
         for (int q = 0; q < R; ++q) {
             const Request& r = *batch[(size_t)q];
@@ -144,6 +150,11 @@ struct ModelBackend {
                     hc.prosody = &ps;
                     if (any_report) hc.req_reports = want_report.data();
                 }
+                if (!spans.empty()) {
+                    hc.fit_call = true;
+                    hc.fit_spans = spans.data();
+                    hc.n_fit_spans = (int)spans.size();
+                }
                 if (any_voice) {
                     hc.voice_ids = vids.data();
                     hc.weights = weights.data();
@@ -159,8 +170,14 @@ struct ModelBackend {
                 if (any_loud) res.out_loudness = o.loud.data();
                 if (any_limit) res.out_limits = o.limits.data();
                 if (any_report) res.out_report = &o.report, res.out_n_report = o.n_report.data();
+                if (!spans.empty()) res.out_fit = fit_out.data();
                 M.infer_host_ex(ids.data(), (int64_t)stride, lens.data(), B, speeds.data(), B, 0, 0, hc, res);
                 rc = KX_OK;
+                size_t at = 0;  // (the results come back in the order the spans went in)
+                for (Request* r : batch) {
+                    r->fit_out.assign(fit_out.begin() + (long)at, fit_out.begin() + (long)(at + r->fit.size()));
+                    at += r->fit.size();
+                }
             } catch (const kx::Error& e) {
                 rc = e.code;
                 err = e.what();
@@ -388,6 +405,21 @@ int kx_dispatcher_submit_request_prosody(kx_dispatcher* d, const int64_t* ids, c
     return d->submit_request_prosody(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
                                      out_bytes, out_samples, out_marks, out_n_marks, join, prosody, out_report, out_n_report, err,
                                      err_len);
+}
+
+int kx_dispatcher_submit_request_fitted(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                        const float* styles, const int32_t* voice_ids, const float* weights, int n_mix,
+                                        float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
+                                        int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
+                                        const kx_prosody* prosody, float** out_report, int64_t* out_n_report,
+                                        const kx_fit_span* spans, int n_spans, kx_fit_result* out_fit, char* err, size_t err_len) {
+    if (!d) {
+        if (err && err_len) snprintf(err, err_len, "dispatcher_submit_request: null dispatcher");
+        return KX_ERR_INVALID;
+    }
+    return d->submit_request_fitted(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
+                                    out_bytes, out_samples, out_marks, out_n_marks, join, prosody, out_report, out_n_report, spans,
+                                    n_spans, out_fit, err, err_len);
 }
 
 int kx_dispatcher_submit_request_limited(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,

@@ -101,6 +101,10 @@ struct Request {
     std::vector<float> p_rate, p_pitch, p_energy;
     std::vector<int32_t> p_frames;
     bool want_report = false;  // the prosody report of the request beside its body; a batch may mix both kinds
+    // its fit spans (submit_request_fitted): `request` 0, positions over its chunks back to back; empty = none.  A batch may mix both
+    // kinds.  fit_out [fit.size()]: what the GPU chose for each span
+    std::vector<FitSpan> fit;
+    std::vector<FitResult> fit_out;
     // result
     void* out = nullptr;
     int64_t out_bytes = 0, out_samples = 0;
@@ -141,6 +145,9 @@ struct RequestOptions {
     const kx_prosody* prosody = nullptr;  // (the prosody entry: never null, a request without arrays has the neutral one)
     float** out_report = nullptr;  // the report pair: both or neither
     int64_t* out_n_report = nullptr;
+    const kx_fit_span* spans = nullptr;  // the fit entry: the request's spans (n_spans == 0: none) and where their results go (may be null)
+    int n_spans = 0;
+    kx_fit_result* out_fit = nullptr;
     bool need_join = false, need_level = false, need_loudness = false, need_limit = false;
     // the entries behind the marks entry: either argument of the pair asks for marks, and then both must be there
     void set_marks(int64_t** marks, int64_t* n_marks) {
@@ -566,6 +573,22 @@ struct Core {
         return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
                                   out_samples, o, err, err_len);
     }
+    // ... and with its fit spans (include/kokorox_hip.h, "fit") and their results
+    int submit_request_fitted(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
+                              const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
+                              void** out, int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
+                              const kx_join* join, const kx_prosody* prosody, float** out_report, int64_t* out_n_report,
+                              const kx_fit_span* spans, int n_spans, kx_fit_result* out_fit, char* err, size_t err_len) {
+        const kx_prosody neutral = {nullptr, nullptr, nullptr, nullptr};
+        RequestOptions o;
+        o.set_marks(out_marks, out_n_marks);
+        o.join = join;
+        o.prosody = prosody ? prosody : &neutral;
+        o.out_report = out_report, o.out_n_report = out_n_report;
+        o.spans = spans, o.n_spans = n_spans, o.out_fit = out_fit;
+        return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
+                                  out_samples, o, err, err_len);
+    }
     // The submits above are this one.  The request's options are looked at first, a bad join before a bad level, loudness or limit,
     // then the report pair; the arguments every submit has come after them.
     int submit_request_any(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
@@ -609,6 +632,15 @@ struct Core {
             if (p->energy) r.p_energy.assign(p->energy, p->energy + total);
             r.want_report = o.out_report != nullptr;
         }
+        if (o.n_spans != 0) {  // (`request` must be 0: the request is the only one of its call as far as the rule goes)
+            static_assert(sizeof(kx_fit_span) == sizeof(FitSpan) && sizeof(kx_fit_result) == sizeof(FitResult), "the layouts of host_request.h");
+            FitPlan plan;
+            const int32_t one = n_chunks;
+            if (!fit_ok(reinterpret_cast<const FitSpan*>(o.spans), o.n_spans, &one, 1, chunk_tokens, n_chunks,
+                        o.prosody ? o.prosody->frames : nullptr, 0, plan, true))
+                return refuse("%s: bad fit", who);
+            r.fit.assign(reinterpret_cast<const FitSpan*>(o.spans), reinterpret_cast<const FitSpan*>(o.spans) + o.n_spans);
+        }
         if (styles) {
             r.kind = 0;
             r.style.assign(styles, styles + (size_t)n_chunks * KX_STYLE_DIM);
@@ -644,6 +676,7 @@ struct Core {
             *o.out_marks = r.marks;
             *o.out_n_marks = r.n_marks;
         }
+        if (o.out_fit && !r.fit.empty() && r.fit_out.size() == r.fit.size()) memcpy(o.out_fit, r.fit_out.data(), r.fit.size() * sizeof(FitResult));
         if (r.want_report) {
             *o.out_report = r.report;
             *o.out_n_report = r.n_report;

@@ -171,6 +171,21 @@ void check_prosody_call(const HostCall& hc, const int32_t* lens, int B, int64_t 
     KX_REQUIRE(prosody_ok(hc.prosody, lens, B, t_stride), "infer: bad prosody");
 }
 
+void check_fit_call(const HostCall& hc, const int32_t* lens, int B, int64_t t_stride, FitPlan& plan) {
+    if (!hc.fit_call) {  // (an entry without spans: nothing to check, nothing planned)
+        plan.prefix.clear();
+        plan.flat.clear();
+        return;
+    }
+    const bool ok = fit_ok(hc.fit_spans, hc.n_fit_spans, hc.chunks_per_request, hc.n_requests, lens, B,
+                           hc.prosody ? hc.prosody->frames : nullptr, t_stride, plan);
+    if (!ok) {
+        plan.prefix.clear();
+        plan.flat.clear();
+    }
+    KX_REQUIRE(ok, "infer: bad fit");
+}
+
 // ---- the meter's tables (include/kokorox_hip.h, "loudness") ---------------------------------------------------------------------
 namespace {
 // (committed as bit patterns, rate codes 0..3: what the library computes with is what the generator rounded)

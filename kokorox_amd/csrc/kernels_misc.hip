@@ -1029,6 +1029,190 @@ void launch_prosody_curves(float* curves, long bs, int ld, const int* frames, co
     KX_HIP(hipGetLastError());
 }
 
+// ---- fit (include/kokorox_hip.h, "fit") ------------------------------------------------------------------------------------------
+// Steps (1) to (3) of prosody_duration_kernel, the same expression in the same order so that the sum has the same bits, stopped
+// before rintf and clamped to 2^-20 .. 2^20 (a NaN: 1.0f): the weight of a token in a fit.  w and fitted are [B][512]; every entry
+// is written, 0 at and past lens[b].  fitted starts as the caller's fixed counts (fixed [B][f_stride], may be null: zeros), which
+// fit_spans_kernel below then reads as "held" and completes.  rate is [B][r_stride], may be null.
+__global__ __launch_bounds__(512) void fit_weights_kernel(const float* logits, long bs, int ld, const float* speeds, int n_speed,
+                                                          const int* lens, const float* rate, long r_stride, const int* fixed,
+                                                          long f_stride, float* w, int* fitted) {
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int T = lens[b];
+    float wt = 0.f;
+    int keep = 0;
+    if (t < T) {
+        float s = 0.f;
+        for (int c = 0; c < 50; ++c) s += 1.0f / (1.0f + expf(-logits[b * bs + (long)c * ld + t]));
+        s = s / speeds[n_speed > 1 ? b : 0];
+        if (rate) s = s / rate[b * r_stride + t];
+        wt = s >= 0x1p-20f ? (s <= 0x1p20f ? s : 0x1p20f) : (s < 0x1p-20f ? 0x1p-20f : 1.0f);  // (a NaN fails both: 1.0f)
+        if (fixed) {
+            const int want = fixed[b * f_stride + t];
+            keep = want >= 1 ? want : 0;
+        }
+    }
+    w[b * 512 + t] = wt;
+    fitted[b * 512 + t] = keep;
+}
+void launch_fit_weights(const float* logits, long bs, int ld, const float* speeds, int n_speed, const int* lens, const float* rate,
+                        long r_stride, const int* fixed, long f_stride, float* w, int* fitted, int B, hipStream_t s) {
+    KX_REQUIRE(w && fitted && B >= 1, "fit weights: bad argument");
+    hipLaunchKernelGGL(fit_weights_kernel, dim3(B), dim3(512), 0, s, logits, bs, ld, speeds, n_speed, lens, rate, r_stride, fixed,
+                       f_stride, w, fitted);
+    KX_HIP(hipGetLastError());
+}
+
+// One workgroup of 256 (four waves) per span.  prefix [B + 1] = the running sum of lens; a span is [begin, end) in that flat token
+// space and `frames` its wanted total.  Lane l owns the contiguous run of per = ceil(n / 256) positions from begin + l per, so
+// position order is lane order.  The run's row is found once, by bisection over prefix (as flac_gather_kernel finds its frame), and
+// walked from there.  Weights are staged once: slot k of lane l lives at sw[k * 256 + l] (a lane reads only its own column: no bank
+// conflict whatever per is) for k < FIT_LDS_RUN = 16, which holds spans of up to 4096 tokens in 16 KiB; a longer run reads the rest
+// from w in global memory (L2-resident: 2 KiB a row).  A held token (fitted >= 1 as fit_weights_kernel left it) is staged as 0.0f,
+// which no clamped weight is, and takes no part.
+// The bisection walks the bit patterns of lambda (F is non-decreasing in them): 31 steps at most, each one __fmul_rn, rintf and a
+// clamp per token and an integer sum over the workgroup -- __shfl_xor inside a wave, four wave totals through LDS.  Integer sums:
+// the order cannot show.  The last step takes d(lambda), d(lambda-) and the stepper flag; a scan of the lanes' stepper counts gives
+// every stepper its rank from the span's end, and the E = F(lambda) - G last ones keep d(lambda-).
+constexpr int FIT_LDS_RUN = 16;
+__device__ inline int fit_block_sum(int v, int* red) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const int s = red[0] + red[1] + red[2] + red[3];
+    __syncthreads();
+    return s;
+}
+__device__ inline int fit_count(float wv, float lambda) {
+    return (int)fminf(fmaxf(rintf(__fmul_rn(wv, lambda)), 1.0f), 50.0f);  // (an infinite product: 50)
+}
+__global__ __launch_bounds__(256) void fit_spans_kernel(const int* prefix, int B, const FitFlat* spans, const float* w, int* fitted,
+                                                        FitResult* results) {
+    __shared__ float sw[FIT_LDS_RUN * 256];
+    __shared__ int red[4];
+    __shared__ int scan[256];
+    const int l = threadIdx.x;
+    const FitFlat sp = spans[blockIdx.x];
+    const int total = prefix[B];
+    const int begin = sp.begin < 0 ? 0 : sp.begin, end = sp.end > total ? total : sp.end;
+    const int n = end > begin ? end - begin : 0;
+    const int per = (n + 255) / 256;
+    const int first = begin + l * per < end ? begin + l * per : end;
+    const int cnt = first + per <= end ? per : end - first;  // (0 for the lanes past the span)
+    // the row of `first`: the last row with prefix[row] <= first
+    int row0 = 0;
+    {
+        int lo = 0, hi = B - 1;
+        while (lo < hi) {
+            const int mid = lo + (hi - lo + 1) / 2;
+            if (prefix[mid] <= first) lo = mid; else hi = mid - 1;
+        }
+        row0 = lo;
+    }
+    // stage, and count the free tokens and the held frames
+    int n_free = 0, held = 0;
+    {
+        int row = row0, next = prefix[row0 + 1];
+        for (int k = 0; k < cnt; ++k) {
+            const int pos = first + k;
+            while (pos >= next && row < B - 1) next = prefix[++row + 1];
+            const int at = row * 512 + (pos - prefix[row]);
+            const int h = fitted[at];
+            if (k < FIT_LDS_RUN) sw[k * 256 + l] = h >= 1 ? 0.0f : w[at];
+            if (h >= 1) held += h; else n_free += 1;
+        }
+    }
+    n_free = fit_block_sum(n_free, red);
+    held = fit_block_sum(held, red);
+    const int G = sp.frames - held;
+    // F(lambda) over the lane's run
+    auto run_sum = [&](float lambda) {
+        int acc = 0;
+        int row = row0, next = prefix[row0 + 1];
+        for (int k = 0; k < cnt; ++k) {
+            float wv;
+            if (k < FIT_LDS_RUN) {
+                wv = sw[k * 256 + l];
+            } else {
+                const int pos = first + k;
+                while (pos >= next && row < B - 1) next = prefix[++row + 1];
+                const int at = row * 512 + (pos - prefix[row]);
+                wv = fitted[at] >= 1 ? 0.0f : w[at];
+            }
+            if (wv != 0.0f) acc += fit_count(wv, lambda);
+        }
+        return acc;
+    };
+    unsigned lo = 0x00800000u, hi = 0x7F7FFFFFu;
+    while (lo < hi) {  // (lo and hi are the same in every lane: the sums are the workgroup's)
+        const unsigned mid = lo + (hi - lo) / 2;
+        if (fit_block_sum(run_sum(__uint_as_float(mid)), red) >= G) hi = mid; else lo = mid + 1;
+    }
+    const float lambda = __uint_as_float(lo), below = __uint_as_float(lo - 1);
+    const int E = fit_block_sum(run_sum(lambda), red) - G;
+    // the steppers of the lane's run, then their ranks from the span's end
+    int mine = 0;
+    {
+        int row = row0, next = prefix[row0 + 1];
+        for (int k = 0; k < cnt; ++k) {
+            float wv;
+            if (k < FIT_LDS_RUN) {
+                wv = sw[k * 256 + l];
+            } else {
+                const int pos = first + k;
+                while (pos >= next && row < B - 1) next = prefix[++row + 1];
+                const int at = row * 512 + (pos - prefix[row]);
+                wv = fitted[at] >= 1 ? 0.0f : w[at];
+            }
+            if (wv != 0.0f && fit_count(wv, lambda) == fit_count(wv, below) + 1) mine += 1;
+        }
+    }
+    scan[l] = mine;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const int v = (l >= o) ? scan[l - o] : 0;
+        __syncthreads();
+        scan[l] += v;
+        __syncthreads();
+    }
+    const int after = scan[255] - scan[l];  // steppers of the lanes behind this one
+    {
+        int row = row0, next = prefix[row0 + 1];
+        int seen = 0;
+        for (int k = 0; k < cnt; ++k) {
+            const int pos = first + k;
+            while (pos >= next && row < B - 1) next = prefix[++row + 1];
+            const int at = row * 512 + (pos - prefix[row]);
+            const float wv = k < FIT_LDS_RUN ? sw[k * 256 + l] : (fitted[at] >= 1 ? 0.0f : w[at]);
+            if (wv == 0.0f) continue;  // (held: the caller's count stays)
+            int d = fit_count(wv, lambda);
+            if (E > 0) {
+                const int dm = fit_count(wv, below);
+                if (d == dm + 1) {
+                    seen += 1;
+                    if (after + (mine - seen + 1) <= E) d = dm;  // (rank from the end, 1-based)
+                }
+            }
+            fitted[at] = d;
+        }
+    }
+    if (l == 0) {
+        FitResult r;
+        r.lambda = lambda;
+        r.n_free = n_free;
+        r.held_frames = held;
+        r.excess = E;
+        results[blockIdx.x] = r;
+    }
+}
+void launch_fit_spans(const int* prefix, int B, const FitFlat* spans, int n_spans, const float* w, int* fitted, FitResult* results,
+                      hipStream_t s) {
+    KX_REQUIRE(prefix && spans && w && fitted && results && B >= 1 && n_spans >= 1, "fit spans: bad argument");
+    hipLaunchKernelGGL(fit_spans_kernel, dim3(n_spans), dim3(256), 0, s, prefix, B, spans, w, fitted, results);
+    KX_HIP(hipGetLastError());
+}
+
 __global__ void gather_cols_kernel(const float* src, long sbs, int sld, float* dst, long dbs, int dld,
                                    const int* idx, int idx_ld, const int* frames) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y, b = blockIdx.z;

@@ -371,6 +371,15 @@ void launch_prosody_duration(const float* logits, long bs, int ld, const float* 
 void launch_prosody_curves(float* curves, long bs, int ld, const int* frames, const int* lens, const int* dur, const int* idx,
                            int idx_ld, const float* pitch, const float* energy, long p_stride, const long* rep_first, float* report,
                            int B, hipStream_t s);
+// Fit (include/kokorox_hip.h, "fit"; kernels_misc.hip).  launch_fit_weights: w [B][512] = every token's duration before rintf,
+// clamped, and fitted [B][512] = the caller's fixed counts (fixed [B][f_stride], may be null) or 0; rate [B][r_stride] may be null.
+// launch_fit_spans: prefix [B + 1] = the running sum of lens, spans [n_spans] in that flat token space (fit_ok made them); the free
+// tokens of every span get their fitted count in `fitted`, and results [n_spans] what the fit chose.  launch_prosody_duration then
+// takes `fitted` as its fixed array, stride 512.
+void launch_fit_weights(const float* logits, long bs, int ld, const float* speeds, int n_speed, const int* lens, const float* rate,
+                        long r_stride, const int* fixed, long f_stride, float* w, int* fitted, int B, hipStream_t s);
+void launch_fit_spans(const int* prefix, int B, const FitFlat* spans, int n_spans, const float* w, int* fitted, FitResult* results,
+                      hipStream_t s);
 void launch_gather_cols(const float* src, long sbs, int sld, float* dst, long dbs, int dld, int C,
                         const int* idx, int idx_ld, const int* frames, int B, int Fmax, hipStream_t s);
 

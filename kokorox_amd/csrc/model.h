@@ -388,11 +388,22 @@ class Model {
         long stride = 0;
         const long* rep_first = nullptr;  // [B] first token of row b in `report`, -1: none (null with report)
         float* report = nullptr;          // [tokens][4], staged in the I/O arena and copied behind the packed blocks
-        bool durations() const { return rate || frames; }
+        // a call with fit spans (include/kokorox_hip.h, "fit"): then `rate` is [B][512] (dur_stride), `frames` stays [B][stride]
+        long dur_stride = 0;                  // stride of `rate`, and of `frames` as the duration kernel reads it
+        int n_spans = 0;
+        const int* fit_prefix = nullptr;      // [B + 1] running sum of lens
+        const FitFlat* fit_spans = nullptr;   // [n_spans] in that flat token space
+        float* fit_w = nullptr;               // [B][512] weights
+        int* fit_fitted = nullptr;            // [B][512] fixed counts of the call: the caller's, then the fitted ones
+        FitResult* fit_results = nullptr;     // [n_spans]
+        bool durations() const { return rate || frames || n_spans > 0; }
         bool curves() const { return pitch || energy || report; }
     };
     ProsodyDev pros_;
     std::vector<long> h_rep_first_;  // host side of ProsodyDev::rep_first (outlives the asynchronous copy)
+    FitPlan fit_plan_;                    // host side of the running call's fit (outlives the asynchronous copies)
+    std::vector<float> h_fit_rate_;       // the call's rate laid out [B][512]
+    std::vector<FitResult> h_fit_results_;  // what front_half brings back in front of its host wait
     // host staging that asynchronous copies read / write: outlives the calling frame
     OutputPlan output_plan_;           // the tables of the running call's output stage: requests, prefixes, joins, marks, levels
     bool want_edges_ = false;          // the running host call has joins: front_half brings the rows' edge durations back

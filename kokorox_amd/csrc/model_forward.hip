@@ -508,9 +508,22 @@ Model::Front Model::front_half(const int64_t* d_ids, int64_t t_stride, const int
     lstm(lstms_.at("predictor.lstm"), t_dcat, t_xl, gxT);
     tap("dur.lstm", t_xl);
     conv(convs_.at("duration_proj"), t_xl, t_logits, ConvOpts{});
-    if (pros_.durations())  // (a call with a per-token rate or fixed frame counts: the restated kernel; the plain call keeps its own)
+    if (pros_.n_spans > 0) {
+        // a call with fit spans: every token's weight, then one workgroup a span finds the span's lambda and writes the fitted counts
+        // beside the caller's fixed ones; the duration kernel takes them as its fixed array and everything downstream follows
+        launch_fit_weights(logits, t_logits.bs, Tp, d_speeds, n_speed, call_.dT, pros_.rate, pros_.dur_stride, pros_.frames, pros_.stride,
+                           pros_.fit_w, pros_.fit_fitted, B, stream_);
+        launch_fit_spans(pros_.fit_prefix, B, pros_.fit_spans, pros_.n_spans, pros_.fit_w, pros_.fit_fitted, pros_.fit_results, stream_);
+        launch_prosody_duration(logits, t_logits.bs, Tp, d_speeds, n_speed, call_.dT, d_pinned_, n_pinned_, pros_.rate, pros_.fit_fitted,
+                                pros_.dur_stride, dur, call_.dF, idx, idx_ld, d_dur_over_, B, stream_);
+        h_fit_results_.assign((size_t)pros_.n_spans, FitResult{});
+        KX_HIP(hipMemcpyAsync(h_fit_results_.data(), pros_.fit_results, (size_t)pros_.n_spans * sizeof(FitResult), hipMemcpyDeviceToHost,
+                              stream_));
+        tap("pred.dur.weights", T::of(pros_.fit_w, 1, 512, LT, Tmax));
+        tap("pred.dur.fitted", T::of(reinterpret_cast<float*>(pros_.fit_fitted), 1, 512, LT, Tmax));  // (int32 bits)
+    } else if (pros_.durations())  // (a call with a per-token rate or fixed frame counts: the restated kernel; the plain call keeps its own)
         launch_prosody_duration(logits, t_logits.bs, Tp, d_speeds, n_speed, call_.dT, d_pinned_, n_pinned_, pros_.rate, pros_.frames,
-                                pros_.stride, dur, call_.dF, idx, idx_ld, d_dur_over_, B, stream_);
+                                pros_.dur_stride, dur, call_.dF, idx, idx_ld, d_dur_over_, B, stream_);
     else
         launch_duration(logits, t_logits.bs, Tp, d_speeds, n_speed, call_.dT, d_pinned_, n_pinned_, dur, call_.dF, idx, idx_ld, d_dur_over_,
                         B, stream_);

@@ -134,6 +134,9 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     if (hc.loudness.call) check_spec_list(hc, hc.loudness);
     if (hc.limits.call) check_spec_list(hc, hc.limits);
     if (hc.prosody_call) check_prosody_call(hc, lens, B, t_stride, res.out_report, res.out_n_report);
+    check_fit_call(hc, lens, B, t_stride, fit_plan_);  // (the empty plan unless the call came through the entry that takes spans)
+    const int n_spans = (int)fit_plan_.flat.size();
+    KX_REQUIRE(n_spans == 0 || n_pinned_ == 0, "infer: fit with pinned durations");
     const bool by_voice = hc.by_voice();
     // one way to lay the output out and pack it: a call without chunks_per_request is R = B single-row requests in hc.format
     const RequestLayout layout = hc.layout(B);
@@ -151,6 +154,12 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     const long n_report = layout.reports ? report_rows(layout, lens, B, h_rep_first_, nullptr) : 0;
     ProsodyDev pd;
     pd.stride = (long)t_stride;
+    pd.dur_stride = n_spans > 0 ? 512 : (long)t_stride;  // (a call with spans: the duration kernel reads rate and the fitted counts [B][512])
+    pd.n_spans = n_spans;
+    if (n_spans > 0 && ps.rate) {
+        h_fit_rate_.assign((size_t)B * 512, 1.0f);
+        for (int b = 0; b < B; ++b) memcpy(&h_fit_rate_[(size_t)b * 512], ps.rate + (size_t)b * t_stride, (size_t)lens[b] * 4);
+    }
     KX_HIP(hipSetDevice(device));
     // I/O staging lives in its own arena: ids, styles, frames, noise keys, voice picks, audio, packed audio
     int64_t* d_ids;
@@ -215,7 +224,14 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             slot_cap = bound.flac_slots;
         }
         const size_t per_token = (size_t)B * t_stride;  // (laid out as the ids)
-        pd.rate = ps.rate ? A.f(per_token) : nullptr;
+        pd.rate = ps.rate ? A.f(n_spans > 0 ? (size_t)B * 512 : per_token) : nullptr;
+        if (n_spans > 0) {
+            pd.fit_prefix = A.i((size_t)B + 1);
+            pd.fit_spans = static_cast<FitFlat*>(A.alloc((size_t)n_spans * sizeof(FitFlat)));
+            pd.fit_w = A.f((size_t)B * 512);
+            pd.fit_fitted = A.i((size_t)B * 512);
+            pd.fit_results = static_cast<FitResult*>(A.alloc((size_t)n_spans * sizeof(FitResult)));
+        }
         pd.frames = ps.frames ? A.i(per_token) : nullptr;
         pd.pitch = ps.pitch ? A.f(per_token) : nullptr;
         pd.energy = ps.energy ? A.f(per_token) : nullptr;
@@ -253,7 +269,15 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         if (hc.utt_index) KX_HIP(hipMemcpyAsync(d_uidx, hc.utt_index, (size_t)B * 4, hipMemcpyHostToDevice, stream_));
         {
             const size_t per_token = (size_t)B * t_stride * 4;  // bytes of each array
-            if (ps.rate) KX_HIP(hipMemcpyAsync(const_cast<float*>(pd.rate), ps.rate, per_token, hipMemcpyHostToDevice, stream_));
+            if (ps.rate && n_spans > 0)
+                KX_HIP(hipMemcpyAsync(const_cast<float*>(pd.rate), h_fit_rate_.data(), (size_t)B * 512 * 4, hipMemcpyHostToDevice, stream_));
+            else if (ps.rate)
+                KX_HIP(hipMemcpyAsync(const_cast<float*>(pd.rate), ps.rate, per_token, hipMemcpyHostToDevice, stream_));
+            if (n_spans > 0) {
+                KX_HIP(hipMemcpyAsync(const_cast<int*>(pd.fit_prefix), fit_plan_.prefix.data(), ((size_t)B + 1) * 4, hipMemcpyHostToDevice, stream_));
+                KX_HIP(hipMemcpyAsync(const_cast<FitFlat*>(pd.fit_spans), fit_plan_.flat.data(), (size_t)n_spans * sizeof(FitFlat),
+                                      hipMemcpyHostToDevice, stream_));
+            }
             if (ps.frames) KX_HIP(hipMemcpyAsync(const_cast<int*>(pd.frames), ps.frames, per_token, hipMemcpyHostToDevice, stream_));
             if (ps.pitch) KX_HIP(hipMemcpyAsync(const_cast<float*>(pd.pitch), ps.pitch, per_token, hipMemcpyHostToDevice, stream_));
             if (ps.energy) KX_HIP(hipMemcpyAsync(const_cast<float*>(pd.energy), ps.energy, per_token, hipMemcpyHostToDevice, stream_));
@@ -333,6 +357,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
             }
             for (int b = 0; b < B; ++b) memcpy(hc.out_durations + (size_t)b * t_stride, &h_dur[(size_t)b * 512], (size_t)lens[b] * sizeof(int));
         }
+        if (res.out_fit && n_spans > 0) memcpy(res.out_fit, h_fit_results_.data(), (size_t)n_spans * sizeof(FitResult));
         *res.out = host;
         if (res.out_report) *res.out_report = plan.has_report() ? reinterpret_cast<float*>(host + plan.report_off) : nullptr;
         if (marks) *res.out_marks = n_marks > 0 ? reinterpret_cast<int64_t*>(host + marks_off) : nullptr;

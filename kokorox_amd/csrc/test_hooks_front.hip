@@ -187,11 +187,23 @@ int kx_test_attention(int device_id, const float* qkv, const int32_t* lens, int 
     });
 }
 
-// the duration head and the gather; rate / fixed [B][T], both null: launch_duration (kx_test_alignment), else launch_prosody_duration
+// the fit in front of the duration head (kx_test_fit_durations): the spans as the caller gave them and where w, the fitted counts
+// and the results go
+struct FitHook {
+    const int32_t* chunks_per_request;
+    int R;
+    const kx_fit_span* spans;
+    int n_spans;
+    float* w;                // [B][512]
+    int32_t* fitted;         // [B][512]
+    kx_fit_result* results;  // [n_spans]
+};
+// the duration head and the gather; rate / fixed [B][T], both null: launch_duration (kx_test_alignment), else launch_prosody_duration;
+// fit given: the two fit kernels first, and launch_prosody_duration on what they wrote
 static int alignment_hook(int device_id, const float* logits, int B, int T, const int32_t* lens, const float* speeds, int n_speed,
                           const int32_t* pinned, int n_pinned, const float* rate, const int32_t* fixed, const float* src, int C, int idx_ld,
                           int32_t* dur, int32_t* frames, int32_t* idx, float* gathered, int Fcap, uint32_t* overflow, char* err,
-                          size_t err_len) {
+                          size_t err_len, const FitHook* fit = nullptr) {
     return guarded_free(err, err_len, [&] {
         check_device(device_id);
         KX_REQUIRE(logits && lens && speeds && src && dur && frames && idx && gathered && overflow && B > 0 && T > 0 && T <= 512 && C > 0 &&
@@ -219,7 +231,37 @@ static int alignment_hook(int device_id, const float* logits, int B, int T, cons
         KX_HIP(hipMemset(d_dur, 0xA5, (size_t)B * 512 * 4));
         KX_HIP(hipMemset(d_frames, 0xA5, (size_t)B * 4));
         KX_HIP(hipMemset(d_over, 0, sizeof(unsigned)));
-        if (rate || fixed) {
+        float* d_w = nullptr;
+        int* d_fitted = nullptr;
+        kx::FitResult* d_res = nullptr;
+        if (fit) {
+            KX_REQUIRE(fit->spans && fit->n_spans >= 1 && fit->w && fit->fitted && fit->results && n_pinned == 0, "test_fit_durations: bad argument");
+            // (rate as the duration kernel then reads it, [B][512]; fixed as the caller laid it out; poison past lens[b] in both)
+            std::vector<float> hr((size_t)B * 512, POISON);
+            std::vector<int32_t> hf((size_t)B * T, (int32_t)0xA5A5A5A5u);
+            for (int b = 0; b < B; ++b)
+                for (int t = 0; t < lens[b]; ++t) {
+                    const size_t i = (size_t)b * T + t;
+                    KX_REQUIRE(kx::prosody_value_ok(rate ? rate[i] : 1.0f, fixed ? fixed[i] : 0, 1.0f, 1.0f), "test_fit_durations: bad prosody");
+                    if (rate) hr[(size_t)b * 512 + t] = rate[i];
+                    if (fixed) hf[i] = fixed[i];
+                }
+            kx::FitPlan plan;
+            KX_REQUIRE(kx::fit_ok(reinterpret_cast<const kx::FitSpan*>(fit->spans), fit->n_spans, fit->chunks_per_request, fit->R, lens, B, fixed, T, plan),
+                       "test_fit_durations: bad fit");
+            const float* d_rate = rate ? dm.up(hr.data(), hr.size()) : nullptr;
+            const int* d_fixed = fixed ? dm.up(hf.data(), hf.size()) : nullptr;
+            const int* d_prefix = dm.up(plan.prefix.data(), plan.prefix.size());
+            const kx::FitFlat* d_spans = dm.up(plan.flat.data(), plan.flat.size());
+            // outputs start as the sentinel / 0xA5 bytes, a guard behind each
+            d_w = guarded_buffer(dm, (size_t)B * 512, SENTINEL);
+            d_fitted = guarded_bytes<int>(dm, (size_t)B * 512, 0xA5);
+            d_res = guarded_bytes<kx::FitResult>(dm, (size_t)fit->n_spans, 0xA5);
+            kx::launch_fit_weights(d_lg, (long)50 * Tp, Tp, d_speed, n_speed, d_len, d_rate, 512, d_fixed, T, d_w, d_fitted, B, nullptr);
+            kx::launch_fit_spans(d_prefix, B, d_spans, fit->n_spans, d_w, d_fitted, d_res, nullptr);
+            kx::launch_prosody_duration(d_lg, (long)50 * Tp, Tp, d_speed, n_speed, d_len, d_pin, n_pinned, d_rate, d_fitted, 512, d_dur, d_frames,
+                                        d_idx, idx_ld, d_over, B, nullptr);
+        } else if (rate || fixed) {
             // (entries at or past lens[b] go up as NaN / 0xA5 bytes: the kernel must not use them)
             std::vector<float> hr((size_t)B * T, POISON);
             std::vector<int32_t> hf((size_t)B * T, (int32_t)0xA5A5A5A5u);
@@ -241,6 +283,14 @@ static int alignment_hook(int device_id, const float* logits, int B, int T, cons
         KX_HIP(hipMemcpy(idx, d_idx, (size_t)B * idx_ld * 4, hipMemcpyDeviceToHost));
         KX_HIP(hipMemcpy(overflow, d_over, sizeof(unsigned), hipMemcpyDeviceToHost));
         guard_untouched(d_idx + (size_t)B * idx_ld, "test_alignment: the duration kernel wrote past idx");
+        if (fit) {
+            KX_HIP(hipMemcpy(fit->w, d_w, (size_t)B * 512 * 4, hipMemcpyDeviceToHost));
+            KX_HIP(hipMemcpy(fit->fitted, d_fitted, (size_t)B * 512 * 4, hipMemcpyDeviceToHost));
+            KX_HIP(hipMemcpy(fit->results, d_res, (size_t)fit->n_spans * sizeof(kx::FitResult), hipMemcpyDeviceToHost));
+            guard_untouched(d_w + (size_t)B * 512, "test_fit_durations: a fit kernel wrote past w");
+            guard_untouched(d_fitted + (size_t)B * 512, "test_fit_durations: a fit kernel wrote past the fitted counts");
+            guard_untouched(d_res + fit->n_spans, "test_fit_durations: the fit kernel wrote past its results");
+        }
         // the gather reads idx[b][0 .. frames[b]): nothing is launched on a frame count or an index outside its row
         int Fmax = 0;
         for (int b = 0; b < B; ++b) {
@@ -275,6 +325,15 @@ int kx_test_prosody_durations(int device_id, const float* logits, int B, int T, 
     if (!rate && !fixed) return guarded_free(err, err_len, [] { throw Error(KX_ERR_INVALID, "test_prosody_durations: a rate or a frame count per token"); });
     return alignment_hook(device_id, logits, B, T, lens, speeds, n_speed, pinned, n_pinned, rate, fixed, src, C, idx_ld, dur, frames, idx,
                           gathered, Fcap, overflow, err, err_len);
+}
+
+int kx_test_fit_durations(int device_id, const float* logits, int B, int T, const int32_t* lens, const float* speeds, int n_speed,
+                          const float* rate, const int32_t* fixed, const int32_t* chunks_per_request, int R, const kx_fit_span* spans,
+                          int n_spans, const float* src, int C, int idx_ld, int32_t* dur, int32_t* frames, int32_t* idx, float* gathered,
+                          int Fcap, uint32_t* overflow, float* w, int32_t* fitted, kx_fit_result* results, char* err, size_t err_len) {
+    const FitHook fit{chunks_per_request, R, spans, n_spans, w, fitted, results};
+    return alignment_hook(device_id, logits, B, T, lens, speeds, n_speed, nullptr, 0, rate, fixed, src, C, idx_ld, dur, frames, idx, gathered,
+                          Fcap, overflow, err, err_len, &fit);
 }
 
 int kx_test_prosody_curves(int device_id, const float* curves, const int32_t* frames, int B, int Fcap, const int32_t* lens, int T,

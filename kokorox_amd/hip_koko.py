@@ -165,6 +165,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                             vp, vp, vp, i32, vp, vp, vp]),
         "kx_dispatcher_submit_request_prosody": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
                                                        C.POINTER(i64), vp, vp, vp, vp, vp, vp, cp, sz]),
+        "kx_infer_requests_fitted": (i32, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, u64, u32, vp, i32, C.POINTER(vp), vp, vp,
+                                           vp, vp, vp, i32, vp, vp, vp, vp, i32, vp]),
+        "kx_dispatcher_submit_request_fitted": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
+                                                      C.POINTER(i64), vp, vp, vp, vp, vp, vp, vp, i32, vp, cp, sz]),
         "kx_dispatcher_create": (vp, [vp, i32, i32, i32, cp, sz]),
         "kx_dispatcher_create_warm": (vp, [vp, i32, i32, i32, i32, i32, cp, sz]),
         "kx_dispatcher_submit": (i32, [vp, vp, i32, vp, f32, u64, C.POINTER(C.POINTER(f32)), C.POINTER(i64), cp, sz]),
@@ -215,6 +219,8 @@ def _test_signatures():
         "kx_test_lstm_ragged": (i32, [i32, vp, vp, i32, i32, i32] + [vp] * 8 + [i32, i32, u32, vp, cp, sz]),
         "kx_test_alignment": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, cp, sz]),
         "kx_test_prosody_durations": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, cp, sz]),
+        "kx_test_fit_durations": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp,
+                                        cp, sz]),
         "kx_test_prosody_curves": (i32, [i32, vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, cp, sz]),
         "kx_test_embed": (i32, [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, cp, sz]),
         "kx_test_style_fc": (i32, [i32, vp, i32, vp, vp, vp, vp, i32, vp, cp, sz]),
@@ -254,7 +260,7 @@ ABI_SYMBOLS = [
     "kx_free_audio", "kx_infer_device", "kx_sync", "kx_set_pinned_durations", "kx_warmup", "kx_arena_bytes", "kx_call_times", "kx_model_status", "kx_model_info", "kx_dispatcher_health", "kx_set_utterance_base", "kx_set_lanes",
     "kx_set_conv_mode", "kx_get_conv_mode", "kx_set_stft_variant", "kx_get_stft_variant",
     "kx_profile_enable", "kx_profile_read", "kx_profile_detail", "kx_profile_aux", "kx_diag_enable", "kx_diag_count", "kx_diag_get", "kx_set_act_prescale", "kx_set_voice_table", "kx_infer_voices",
-    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_infer_requests_levelled", "kx_dispatcher_submit_request_levelled", "kx_loudness_filter", "kx_truepeak_filter", "kx_infer_requests_loudness", "kx_dispatcher_submit_request_loudness", "kx_limit_filter", "kx_infer_requests_limited", "kx_dispatcher_submit_request_limited", "kx_infer_prosody", "kx_infer_requests_prosody", "kx_dispatcher_submit_request_prosody", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
+    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_infer_requests_levelled", "kx_dispatcher_submit_request_levelled", "kx_loudness_filter", "kx_truepeak_filter", "kx_infer_requests_loudness", "kx_dispatcher_submit_request_loudness", "kx_limit_filter", "kx_infer_requests_limited", "kx_dispatcher_submit_request_limited", "kx_infer_prosody", "kx_infer_requests_prosody", "kx_dispatcher_submit_request_prosody", "kx_infer_requests_fitted", "kx_dispatcher_submit_request_fitted", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
     "kx_dispatcher_stats", "kx_dispatcher_failures", "kx_dispatcher_destroy", "kx_debug_tap",
 ]
 
@@ -294,6 +300,22 @@ def prosody_arrays(prosody, lens, stride):
             a[b, : len(row)] = np.asarray(row, dtype=a.dtype)
         arrs.append(a)
     return Prosody(*[None if a is None else a.ctypes.data for a in arrs]), tuple(arrs)
+
+
+# kx_fit_span / kx_fit_result (include/kokorox_hip.h, "fit")
+FIT_SPAN_DTYPE = np.dtype([("request", np.int32), ("begin", np.int32), ("end", np.int32), ("frames", np.int32)])
+FIT_RESULT_DTYPE = np.dtype([("lambda", np.float32), ("n_free", np.int32), ("held_frames", np.int32), ("excess", np.int32)])
+
+
+def fit_spans(spans) -> np.ndarray:
+    """Fit spans as the array of kx_fit_span the library takes: a list of (request, begin, end, frames), or an array of
+    FIT_SPAN_DTYPE already."""
+    if isinstance(spans, np.ndarray) and spans.dtype == FIT_SPAN_DTYPE:
+        return np.ascontiguousarray(spans).reshape(-1)
+    a = np.zeros(len(spans), FIT_SPAN_DTYPE)
+    for i, s in enumerate(spans):
+        a[i] = tuple(int(v) for v in s)
+    return a
 
 
 def join_specs(joins, n=None) -> np.ndarray:
@@ -567,6 +589,23 @@ class HipKoko:
         out = out + (nsamp,) if with_samples else out
         return out if len(out) > 1 else out[0]
 
+    def infer_requests_fitted(self, tokens, chunks_per_request, fit, prosody=None, joins=None, styles=None, voice_ids=None, weights=None,
+                              speeds=(1.0,), seed: int = 0, flags: int = 0, fmt=0, marks: bool = False, report: bool = False,
+                              with_samples: bool = False):
+        """infer_requests_prosody with fit spans (kx_infer_requests_fitted; the definition is in include/kokorox_hip.h, "fit", the numpy
+        form voices.fit_durations): `fit` = a list of (request, begin, end, frames), sorted by (request, begin) and disjoint; tokens
+        [begin, end) of that request, its chunks laid end to end, then last exactly `frames` frames of 25 ms (voices.fit_frames).
+        Returns what infer_requests_prosody returns, then the fit results, one FIT_RESULT_DTYPE record per span."""
+        j = None if joins is None else join_specs(joins)
+        sp = fit_spans(fit)
+        fr = np.zeros(max(len(sp), 1), FIT_RESULT_DTYPE)
+        res, mk, nsamp, rep = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, marks, j,
+                                                   prosody=(prosody, report, sp, fr))
+        out = (res, mk) if marks else (res,)
+        out = out + (rep,) if report else out
+        out = out + (fr[: len(sp)],)
+        return out + (nsamp,) if with_samples else out
+
     # -- SURVEY 8f ranks 2 and 3: device voice table, packed output -----------------------------
     def set_voice_table(self, table: np.ndarray):
         """table [n_voices, 511, 1, 256] (or [n, 511, 256]) as built by load_voices / hf_cache.rs:284-309."""
@@ -729,11 +768,15 @@ class HipKoko:
         spec = next(((s, fn, k) for s, fn, k in ((limits, self._lib.kx_infer_requests_limited, 5), (loudness, self._lib.kx_infer_requests_loudness, 4),
                                                   (levels, self._lib.kx_infer_requests_levelled, 2)) if s is not None), None)
         marks = extra = keep = None
-        if prosody is not None:  # (prosody, want the report)
+        if prosody is not None:  # (prosody, want the report) or, through the fitted entry, (..., the fit spans, their results)
             ps, keep = prosody_arrays(prosody[0], lens, ids.shape[1])
             rp, n_rp = C.c_void_p(), np.zeros(max(R, 1), np.int64)
-            rc = self._lib.kx_infer_requests_prosody(*args, *tail, None if ps is None else C.addressof(ps), C.byref(rp) if prosody[1] else None,
-                                                     _ptr(n_rp) if prosody[1] else None)
+            ptail = (None if ps is None else C.addressof(ps), C.byref(rp) if prosody[1] else None, _ptr(n_rp) if prosody[1] else None)
+            if len(prosody) > 2:  # (..., the spans, their results)
+                rc = self._lib.kx_infer_requests_fitted(*args, *tail, *ptail, _ptr(prosody[2]) if len(prosody[2]) else None, len(prosody[2]),
+                                                        _ptr(prosody[3]))
+            else:
+                rc = self._lib.kx_infer_requests_prosody(*args, *tail, *ptail)
         elif spec is not None:
             extra = np.zeros((max(R, 1), spec[2]), np.float64)
             rc = spec[1](*args, *tail, _ptr(spec[0]), spec[0].shape[0], _ptr(extra))
@@ -983,7 +1026,7 @@ class Dispatcher:
 
     def submit_request(self, chunks: Sequence[Sequence[int]], styles=None, voices=None, speed: float = 1.0, seed: int = 0,
                        fmt: int = 0, marks: bool = False, join=None, level=None, loudness=None, limit=None, prosody=None,
-                       report: bool = False):
+                       report: bool = False, fit=None):
         """A request of 1 .. max_batch chunks (kx_dispatcher_submit_request): `chunks` = the 0-wrapped id lists; `styles` = one
         256-float row per chunk, OR `voices` as in submit_ex (one voice spec for the request); `fmt` = a format word (a PACK_*
         form, optionally | PACK_RATE_*).  Returns what HipKoko.infer_requests returns for one request: an array (forms 0..2, 8, 9)
@@ -998,7 +1041,10 @@ class Dispatcher:
         HipKoko.infer_requests_limited does; the result then ends with five float64 values, p, g, I, n_g and r.
         prosody = (rate, frames, pitch, energy), each None or one sequence per chunk (kx_dispatcher_submit_request_prosody), and / or
         report=True: the request shaped as HipKoko.infer_requests_prosody shapes it; with report=True the result ends with the
-        request's float32 report [tokens, 4].  Not together with level, loudness or limit."""
+        request's float32 report [tokens, 4].  Not together with level, loudness or limit.
+        fit = [(begin, end, frames), ...] (kx_dispatcher_submit_request_fitted): spans of the request's tokens, chunks laid end to end,
+        fitted as HipKoko.infer_requests_fitted fits them; the result then ends with the FIT_RESULT_DTYPE records of the spans.  It goes
+        with prosody and report, not with level, loudness or limit."""
         lens = np.array([len(c) for c in chunks], dtype=np.int32)
         a = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.int64).reshape(-1) for c in chunks])
                                  if len(chunks) else np.zeros(0, np.int64))
@@ -1024,7 +1070,7 @@ class Dispatcher:
         if (loudness is not None) + (level is not None) + (limit is not None) > 1:
             raise ValueError("submit_request: a request has a level or a loudness, not both" if limit is None else
                              "submit_request: a request has a level, a loudness or a limit, not two of them")
-        if (prosody is not None or report) and (level is not None or loudness is not None or limit is not None):
+        if (prosody is not None or report or fit is not None) and (level is not None or loudness is not None or limit is not None):
             raise ValueError("submit_request: prosody does not go with a level, a loudness or a limit")
         rp, n_rp = C.c_void_p(), C.c_int64(0)
         # what every entry behind kx_dispatcher_submit_request_marks takes next: the marks pair (both null: no marks), then the join
@@ -1036,11 +1082,19 @@ class Dispatcher:
                       (loudness, loudness_specs, self._lib.kx_dispatcher_submit_request_loudness, 4),
                       (level, level_specs, self._lib.kx_dispatcher_submit_request_levelled, 2)) if s is not None), None)
         keep = None
-        if prosody is not None or report:
+        fit_sp = fit_res = None
+        if fit is not None:
+            fit_sp = fit_spans([(0,) + tuple(f) for f in fit])
+            fit_res = np.zeros(max(len(fit_sp), 1), FIT_RESULT_DTYPE)
+        if prosody is not None or report or fit is not None:
             flat = None if prosody is None else tuple(None if x is None else [np.concatenate([np.asarray(c).reshape(-1) for c in x])] for x in prosody)
             ps, keep = prosody_arrays(flat, [int(lens.sum())], int(lens.sum()))
-            rc = self._lib.kx_dispatcher_submit_request_prosody(*args, *tail, None if ps is None else C.addressof(ps),
-                                                                C.byref(rp) if report else None, C.byref(n_rp) if report else None, err, len(err))
+            ptail = (None if ps is None else C.addressof(ps), C.byref(rp) if report else None, C.byref(n_rp) if report else None)
+            if fit is not None:
+                rc = self._lib.kx_dispatcher_submit_request_fitted(*args, *tail, *ptail, _ptr(fit_sp) if len(fit_sp) else None, len(fit_sp),
+                                                                   _ptr(fit_res), err, len(err))
+            else:
+                rc = self._lib.kx_dispatcher_submit_request_prosody(*args, *tail, *ptail, err, len(err))
         elif spec is not None:
             rc = spec[1](*args, *tail, _ptr(spec[0]), _ptr(spec[2]), err, len(err))
         elif join is not None:
@@ -1067,6 +1121,7 @@ class Dispatcher:
         res = (_decode_packed(raw, fmt), m) if marks else (_decode_packed(raw, fmt),)
         res = res + (spec[2],) if spec is not None else res
         res = res + (rep_out,) if report else res
+        res = res + (fit_res[: len(fit_sp)],) if fit is not None else res
         return res if len(res) > 1 else res[0]
 
     def stats(self):
@@ -1363,6 +1418,37 @@ def prosody_durations(logits, lens, speeds, src, rate=None, frames=None, pinned=
     _err_call(lib.kx_test_prosody_durations, device, _ptr(logits), B, T, _ptr(ln), _ptr(sp), len(sp), _ptr(pin), 0 if pin is None else len(pin),
               _ptr(rt), _ptr(fr), _ptr(src), C_, idx_ld, _ptr(dur), _ptr(n_frames), _ptr(idx), _ptr(g), Fcap, _ptr(over))
     return dur, n_frames, idx, g, int(over[0])
+
+
+def fit_durations(logits, lens, speeds, src, spans, chunks_per_request=None, rate=None, frames=None, idx_ld=None, Fcap=None, device=0):
+    """`prosody_durations` with the fit in front of it (kx_test_fit_durations): spans = [(request, begin, end, frames), ...] over the
+    requests of chunks_per_request (None: every row a request).  Returns what `alignment` returns, then w [B,512], fitted [B,512]
+    and the FIT_RESULT_DTYPE records of the spans."""
+    lib = load_test_library()
+    logits, src = _f32(logits), _f32(src)
+    B, n50, T = logits.shape
+    assert n50 == 50 and src.shape[0] == B and src.shape[2] == T
+    C_ = src.shape[1]
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    sp = np.ascontiguousarray(speeds, dtype=np.float32).reshape(-1)
+    rt = None if rate is None else np.ascontiguousarray(rate, dtype=np.float32).reshape(B, T)
+    fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32).reshape(B, T)
+    cpr = None if chunks_per_request is None else np.ascontiguousarray(chunks_per_request, dtype=np.int32).reshape(-1)
+    fs = fit_spans(spans)
+    idx_ld = 50 * T if idx_ld is None else idx_ld
+    Fcap = idx_ld if Fcap is None else Fcap
+    dur = np.zeros((B, 512), dtype=np.int32)
+    n_frames = np.zeros(B, dtype=np.int32)
+    idx = np.zeros((B, idx_ld), dtype=np.int32)
+    g = np.zeros((B, C_, Fcap), dtype=np.float32)
+    over = np.zeros(1, dtype=np.uint32)
+    w = np.zeros((B, 512), dtype=np.float32)
+    fitted = np.zeros((B, 512), dtype=np.int32)
+    res = np.zeros(max(len(fs), 1), FIT_RESULT_DTYPE)
+    _err_call(lib.kx_test_fit_durations, device, _ptr(logits), B, T, _ptr(ln), _ptr(sp), len(sp), _ptr(rt), _ptr(fr), _ptr(cpr),
+              B if cpr is None else len(cpr), _ptr(fs) if len(fs) else None, len(fs), _ptr(src), C_, idx_ld, _ptr(dur), _ptr(n_frames),
+              _ptr(idx), _ptr(g), Fcap, _ptr(over), _ptr(w), _ptr(fitted), _ptr(res))
+    return dur, n_frames, idx, g, int(over[0]), w, fitted, res[: len(fs)]
 
 
 def prosody_curves(curves, frames, lens, idx, dur, pitch=None, energy=None, report=True, device=0):

@@ -888,6 +888,67 @@ def prosody_durations(s, rate=None, frames=None, pinned=None, idx_ld=None) -> np
     return (np.minimum(scan, idx_ld) - np.minimum(scan - d, idx_ld)).astype(np.int32)
 
 
+FIT_FRAME_SECONDS = 0.025  # a frame: 600 samples at 24 000 Hz
+
+
+def fit_frames(seconds) -> int:
+    """The frame count closest to `seconds` (a frame is 25 ms): what a caller puts into a fit span."""
+    return int(round(float(seconds) / FIT_FRAME_SECONDS))
+
+
+def fit_weights(s) -> np.ndarray:
+    """The weights of a fit from the float32 values s[t] before rintf: s inside 2^-20 .. 2^20, clamped to it outside, 1 for a NaN."""
+    s = np.asarray(s, dtype=np.float32).reshape(-1)
+    lo, hi = np.float32(2.0 ** -20), np.float32(2.0 ** 20)
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isnan(s), np.float32(1), np.minimum(np.maximum(s, lo), hi)).astype(np.float32)
+
+
+def fit_counts(w, lam_bits) -> np.ndarray:
+    """d_t(lambda) of the definition for the float32 lambda with the bit pattern lam_bits: min(max(rint(f32(w lambda)), 1), 50)."""
+    lam = np.array([lam_bits], dtype=np.uint32).view(np.float32)[0]
+    with np.errstate(over="ignore", under="ignore"):
+        p = (np.asarray(w, dtype=np.float32) * lam).astype(np.float32)
+    return np.minimum(np.maximum(np.rint(p), np.float32(1)), np.float32(50)).astype(np.int64)
+
+
+def fit_durations(w, frames, held=None):
+    """The fit of one span (include/kokorox_hip.h, "fit"): w = the float32 values of its tokens before rintf (clamped here as the
+    GPU clamps them), frames = the wanted total, held = None or one count per token, >= 1 where the token is held.  Returns
+    (d, lam_bits, excess): the durations of all its tokens (int32; a held token keeps its count), the bit pattern of lambda and E.
+    Raises ValueError where the library refuses the span (no free token, G outside n .. 50 n)."""
+    w = fit_weights(w)
+    h = np.zeros(w.shape[0], dtype=np.int64) if held is None else np.asarray(held, dtype=np.int64).reshape(-1)
+    if h.shape[0] != w.shape[0]:
+        raise ValueError("fit: one held count per token")
+    free = h < 1
+    n = int(free.sum())
+    G = int(frames) - int(h[~free].sum())
+    if n == 0 or G < n or G > 50 * n:
+        raise ValueError("fit: bad fit")
+    wf = w[free]
+    lo, hi = 0x00800000, 0x7F7FFFFF
+    while lo < hi:
+        mid = lo + (hi - lo) // 2
+        if int(fit_counts(wf, mid).sum()) >= G:
+            hi = mid
+        else:
+            lo = mid + 1
+    d_hi = fit_counts(wf, lo)
+    E = int(d_hi.sum()) - G
+    df = d_hi.copy()
+    if E > 0:
+        d_lo = fit_counts(wf, lo - 1)
+        steppers = np.flatnonzero(d_hi == d_lo + 1)
+        if steppers.shape[0] < E:
+            raise AssertionError("fit: fewer steppers than the excess")
+        keep = steppers[steppers.shape[0] - E:]  # (the E with the highest position)
+        df[keep] = d_lo[keep]
+    d = h.copy()
+    d[free] = df
+    return d.astype(np.int32), int(lo), E
+
+
 def _prosody_ratio(rho, step_token) -> np.ndarray:
     """r[j] of the definition: the 5-step triangle over the per-token ratio, clamped to the row, float64 in ascending k."""
     n = step_token.shape[0]

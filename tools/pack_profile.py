@@ -26,6 +26,9 @@ the command line; an optional second argument is the batch (1 = one utterance). 
     a word and 'r'       ('2r') kx_infer_requests_prosody with a rate, a pitch and an energy per token and the report, every row a
                          request of its own: prosody_duration_kernel in duration_kernel's place (the pinned pattern still sets the
                          frames) and prosody_curves_kernel behind the F0 / N predictors;
+    a word and 'f'       ('2f') kx_infer_requests_fitted, every row a request of its own with one span over all its 130 tokens fitted
+                         to 422 frames (what the pinned pattern gives the other modes; a fit refuses a pinned model, so this mode
+                         runs without the pattern): fit_weights_kernel and fit_spans_kernel in front of prosody_duration_kernel;
     a word and 'g'       ('2g') the same grouping without joins (kx_infer_requests_marks): the plain kernels on the same batch.
 Meant to run under the profiler, one mode per run (kernel trace only, no counters in the same run):
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o t -- python tools/pack_profile.py p2
@@ -44,7 +47,8 @@ B = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 m = hk.HipKoko.new(W.ensure_synthetic_blob())
 toks = [list(int(v) for v in R.synthetic_inputs(1, 128, seed=40 + b)[0]) for b in range(B)]
 rows = [W.synthetic_voices(1)[0, 128, 0]] * B
-m.set_pinned_durations([3, 3, 3, 4])
+if not which.endswith("f"):
+    m.set_pinned_durations([3, 3, 3, 4])
 for it in range(3):
     if which == "i":
         out = m.infer_batch(toks, rows, [1.0])
@@ -87,6 +91,13 @@ for it in range(3):
         assert all(k.shape == (130, 4) and int(k[:, 3].sum()) == 422 for k in rep)
         if it == 2:
             print("report of the first request: mean voiced F0 %.3f Hz over %d steps" % (float((rep[0][:, 0] * rep[0][:, 1]).sum() / max(rep[0][:, 1].sum(), 1)), int(rep[0][:, 1].sum())))
+    elif which.endswith("f"):
+        word = int(which[:-1], 0)
+        out, fit, ns = m.infer_requests_fitted(toks, [1] * B, [(b, 0, len(toks[b]), 422) for b in range(B)], styles=rows, fmt=word, with_samples=True)
+        L, M, _ = hk.resample_filter(word)
+        assert all(int(k) == 422 * 600 * L // M for k in ns) and all(int(f["n_free"]) == 130 for f in fit)
+        if it == 2:
+            print("fit of the first request: lambda %.6f, excess %d" % (float(fit[0]["lambda"]), int(fit[0]["excess"])))
     elif which.endswith("m"):
         word = int(which[:-1], 0)
         out, marks = m.infer_requests_marks(toks, [1] * B, styles=rows, fmt=word)
