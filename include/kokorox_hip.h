@@ -336,9 +336,43 @@ int kx_set_voice_table(kx_model* m, const float* table, int n_voices);
  * refused like 5, 6 and 7. */
 #define KX_PACK_FLAC 12
 #define KX_FLAC_BLOCK 4096
+/* IMA ADPCM in a WAV file (kx_infer_requests and its siblings, kx_dispatcher_submit_request* only): 4 bits per sample, the body a
+ * telephone, an IVR or a small device decodes (WAVE_FORMAT_IMA_ADPCM, tag 0x0011, which is the form's number), a quarter of the
+ * 16-bit size.  v[0..N) are form 4's 16-bit samples (NaN -> 0, +-inf -> +-32767, truncation toward zero) of the request's stream at
+ * its output rate -- after the join, the resampler and the levels or the limiter; out_samples[r] and the marks are what they are
+ * for any other form.  Every choice is fixed here, so the body is a function of v and the rate, and the numpy definition
+ * (kokorox_amd/voices.py: adpcm_wav_body) and the GPU agree on every byte.  All fields little-endian.
+ *   Block size by rate: A = 256 bytes at 8000 Hz, 512 at 16 000 and 24 000 Hz, 1024 at 48 000 Hz; a block holds P = 1 + 2 (A - 4)
+ *     samples (505, 1017, 2041).  F = ceil(N / P) blocks; the samples past N in the last block repeat v[N - 1].
+ *   Header, 60 bytes: "RIFF", 52 + A F, "WAVE"; "fmt ", 20: tag 0x0011, 1 channel, the rate, floor(rate A / P) bytes per second,
+ *     block align A, 4 bits per sample, cbSize 2, wSamplesPerBlock P; "fact", 4: N; "data", A F.  The body is 60 + A F bytes, a
+ *     multiple of 4 as every region.  A body whose N (the fact chunk) or RIFF size would pass 0xFFFFFFFF is refused with
+ *     KX_ERR_INVALID, as form 4's is.
+ *   Block: int16 predictor = the block's first sample; uint8 index i0; uint8 0; then A - 4 bytes of two codes each, the earlier
+ *     sample in the LOW nibble.
+ *   Start index: i0 = the smallest i with STEP[i] >= max over t = 0..7 of |v[t + 1] - v[t]|, the block's own (padded) samples
+ *     counted from its first, 88 when there is none.  (Eight differences, not the first alone: a block that begins near an extremum
+ *     of the waveform would otherwise start with far too small a step; DESIGN.md section 7 has the measurements.)
+ *     A block is thereby a function of its own samples: all blocks of all requests are encoded at once, and a body is the same
+ *     bytes whatever it was batched with.
+ *   Per sample s (the standard IMA / DVI step, the algorithm of CPython's audioop.lin2adpcm), with the 89 steps STEP = 7, 8, 9, ..
+ *     29794, 32767 (kokorox_amd/csrc/adpcm_steps.h) and the index steps -1, -1, -1, -1, 2, 4, 6, 8: d = s - pred; the code's bit 8
+ *     is set when d < 0, and d = |d|; vp = step >> 3; three compare-subtract rounds at step, step >> 1 and step >> 2 set bits
+ *     4, 2 and 1, each subtracting the compared value from d and adding it to vp; pred -= vp or += vp by the sign, clamped to
+ *     [-32768, 32767]; index += the index step of the code's low three bits, clamped to [0, 88]; step = STEP[index].
+ * Not offered: stereo, other block sizes, raw DVI4 without a container, G.726.  Forms 13..16 do not exist and are refused. */
+#define KX_PACK_ADPCM_WAV 17
+#define KX_ADPCM_MAX_BLOCK 1024
+/* The plain 16-bit WAV file, as bytes: what form 4 encodes as base64 -- the 44-byte header with its true sizes, then the 16-bit
+ * samples with form 4's meaning; 44 + 2 N bytes, padded with zero bytes to a multiple of 4 as every region is (out_bytes[r]
+ * counts the padding; the header's sizes do not).  Refused where form 4 is (a RIFF size past 0xFFFFFFFF).  Requests only. */
+#define KX_PACK_WAV16 18
+/* The block of form 17 at the rate of `format_word` (only bits 8..11 are read): *block_bytes = A, *samples_per_block = P (either
+ * may be NULL).  Host only, touches no GPU; KX_ERR_INVALID for a rate code above 3. */
+int kx_adpcm_block(int format_word, int32_t* block_bytes, int32_t* samples_per_block);
 
 /* The `format` / `formats[]` value of kx_infer_requests and kx_dispatcher_submit_request is a WORD: bits 0..7 = the form above
- * (0..4, 8, 9, 12), bits 8..11 = the output sample rate, every other bit zero (else "infer: unknown output format").  Rate code 0 =
+ * (0..4, 8, 9, 12, 17, 18), bits 8..11 = the output sample rate, every other bit zero (else "infer: unknown output format").  Rate code 0 =
  * 24 000 Hz, the model's own rate: the bytes of the plain forms, unchanged.  Codes 4..15 are refused with KX_ERR_INVALID,
  * "infer: unknown output sample rate".  Every form combines with every rate.  (kx_infer, kx_infer_packed, kx_infer_voices,
  * kx_dispatcher_submit and kx_dispatcher_submit_ex keep taking the forms 0..2 and nothing else.)

@@ -15,7 +15,8 @@ namespace kokorox {
 // The format word of infer_requests / submit_request: a form, optionally or'ed with an output rate (kokorox_hip.h, KX_PACK_*).
 constexpr int PACK_F32_MONO = KX_PACK_F32_MONO, PACK_F32_STEREO = KX_PACK_F32_STEREO, PACK_PCM16_MONO = KX_PACK_PCM16_MONO,
               PACK_WAV_F32 = KX_PACK_WAV_F32, PACK_WAV16_BASE64 = KX_PACK_WAV16_BASE64, PACK_MULAW = KX_PACK_MULAW,
-              PACK_ALAW = KX_PACK_ALAW, PACK_FLAC = KX_PACK_FLAC;
+              PACK_ALAW = KX_PACK_ALAW, PACK_FLAC = KX_PACK_FLAC, PACK_ADPCM_WAV = KX_PACK_ADPCM_WAV,
+              PACK_WAV16 = KX_PACK_WAV16;
 constexpr int PACK_RATE_24000 = KX_PACK_RATE_24000, PACK_RATE_8000 = KX_PACK_RATE_8000, PACK_RATE_16000 = KX_PACK_RATE_16000,
               PACK_RATE_48000 = KX_PACK_RATE_48000;
 

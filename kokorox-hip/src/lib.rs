@@ -39,6 +39,13 @@ pub const KX_PACK_MULAW: c_int = 8;
 pub const KX_PACK_ALAW: c_int = 9;
 /// FLAC of the 16-bit samples, lossless; the body's size follows from the samples (`kokorox_hip.h`, "FLAC").
 pub const KX_PACK_FLAC: c_int = 12;
+/// IMA ADPCM in a WAV file, 4 bits per sample, blocks encoded on the GPU (`kokorox_hip.h`, "IMA ADPCM"); the form's number is the
+/// WAV format tag it carries.
+pub const KX_PACK_ADPCM_WAV: c_int = 17;
+/// The largest block of `KX_PACK_ADPCM_WAV`, at 48 000 Hz.
+pub const KX_ADPCM_MAX_BLOCK: c_int = 1024;
+/// The plain 16-bit WAV file as bytes: what `KX_PACK_WAV16_BASE64` encodes, padded with zeros to a multiple of 4.
+pub const KX_PACK_WAV16: c_int = 18;
 /// The output sample rate, or'ed into a request's form (bits 8..11 of the format word; 0 = the model's 24 000 Hz).
 pub const KX_PACK_RATE_24000: c_int = 0x000;
 pub const KX_PACK_RATE_8000: c_int = 0x100;
@@ -91,6 +98,15 @@ pub fn truepeak_filter() -> Result<[[f32; 24]; 3], Box<dyn Error>> {
     match unsafe { kx_truepeak_filter(t.as_mut_ptr() as *mut f32, 72) } {
         KX_OK => Ok(t),
         rc => Err(format!("kokorox_hip error {}: kx_truepeak_filter", rc).into()),
+    }
+}
+
+/// The block of `KX_PACK_ADPCM_WAV` at the rate of a format word: (bytes of a block, samples of a block); host only.
+pub fn adpcm_block(format_word: c_int) -> Result<(i32, i32), Box<dyn Error>> {
+    let (mut a, mut p) = (0i32, 0i32);
+    match unsafe { kx_adpcm_block(format_word, &mut a, &mut p) } {
+        KX_OK => Ok((a, p)),
+        rc => Err(format!("kokorox_hip error {}: kx_adpcm_block", rc).into()),
     }
 }
 
@@ -234,6 +250,7 @@ extern "C" {
     fn kx_resample_filter(format_word: c_int, l: *mut i32, m: *mut i32, n_taps: *mut i32, taps: *mut f32, cap: c_int) -> c_int;
     fn kx_loudness_filter(format_word: c_int, out10: *mut f64) -> c_int;
     fn kx_truepeak_filter(taps: *mut f32, cap: c_int) -> c_int;
+    fn kx_adpcm_block(format_word: c_int, block_bytes: *mut i32, samples_per_block: *mut i32) -> c_int;
     fn kx_infer_requests_loudness(m: *mut KxModel, ids: *const i64, t_stride: i64, lens: *const i32, b: c_int,
                                   chunks_per_request: *const i32, r: c_int, styles: *const f32, voice_ids: *const i32,
                                   weights: *const f32, max_mix: c_int, speeds: *const f32, n_speed: c_int, seed: u64, flags: u32,

@@ -22,7 +22,7 @@ _PUB_TEST = os.path.join("..", "..", "include", "kokorox_hip_test.h")
 # (model.h includes kxw_file.h, which includes onnx_import.h)
 _MODEL_H = ["model.h", "kxw_file.h", "onnx_import.h"]
 EXTRA_DEPS = {"model.hip": [*_MODEL_H, _PUB], "model_forward.hip": [*_MODEL_H, _PUB], "model_host.hip": [*_MODEL_H, "host_pool.h", _PUB],
-              "host_pool.cpp": ["host_pool.h"], "host_request.cpp": ["resample_taps.h", "kweight_coefs.h", "truepeak_taps.h", "limit_taps.h"], "request_kernels.hip": ["resample_taps.h", "kweight_coefs.h", "truepeak_taps.h", "limit_taps.h"], "conv_call.hip": _MODEL_H, "api.hip": [*_MODEL_H, "kx_handle.h", "api_guard.h", "check_device.h", _PUB],
+              "host_pool.cpp": ["host_pool.h"], "host_request.cpp": ["resample_taps.h", "kweight_coefs.h", "truepeak_taps.h", "limit_taps.h", "adpcm_steps.h"], "request_kernels.hip": ["resample_taps.h", "kweight_coefs.h", "truepeak_taps.h", "limit_taps.h", "adpcm_steps.h"], "conv_call.hip": _MODEL_H, "api.hip": [*_MODEL_H, "kx_handle.h", "api_guard.h", "check_device.h", _PUB],
               "dispatcher.hip": [*_MODEL_H, "kx_handle.h", "dispatcher_core.h", _PUB],
               **{t: [*_MODEL_H, "test_hooks.h", "api_guard.h", "check_device.h", _PUB, _PUB_TEST] for t in TEST_SOURCES}, "onnx_import.cpp": ["onnx_import.h"],
               "kxw_file.cpp": ["kxw_file.h", "onnx_import.h"], "conv_f16x3_da_p1.hip": ["conv_f16x3_da.hip"], "conv_f16x3_da_w2.hip": ["conv_f16x3_da.hip"], "conv_f16x3_da_s16.hip": ["conv_f16x3_da.hip"], "conv_f16x3_da_f8.hip": ["conv_f16x3_da.hip"], "conv_f16x3_da_pre.hip": ["conv_f16x3_da.hip"]}

@@ -96,6 +96,14 @@ int kx_truepeak_filter(float* taps, int cap) {
     });
 }
 
+int kx_adpcm_block(int format_word, int32_t* block_bytes, int32_t* samples_per_block) {
+    return guarded_free(nullptr, 0, [&] {
+        const long A = kx::adpcm_block_bytes(kx::format_rate(format_word));
+        if (block_bytes) *block_bytes = (int32_t)A;
+        if (samples_per_block) *samples_per_block = (int32_t)kx::adpcm_block_samples(A);
+    });
+}
+
 kx_model* kx_create_from_device_blob(const void* d_blob, size_t n_bytes, int device_id, char* err, size_t err_len) {
     kx_model* h = nullptr;
     int rc = guarded_free(err, err_len, [&] {

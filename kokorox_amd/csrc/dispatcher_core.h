@@ -376,16 +376,17 @@ struct Core {
         return n < 0 ? 0 : n;
     }
 
-    // format_word: `format` is the word of the request entries (include/kokorox_hip.h: a form 0..4, 8, 9 or 12 in bits 0..7, a
+    // format_word: `format` is the word of the request entries (include/kokorox_hip.h: a form 0..4, 8, 9, 12, 17 or 18 in bits 0..7, a
     // rate code 0..3 in bits 8..11, nothing else); otherwise one of the three forms 0..2 of the single-utterance submits
     bool check_common(const int64_t* ids, int n_tokens, float speed, int format, const char* who, char* err,
                       size_t err_len, bool format_word = false) {
         const int form = format_word ? (format & 0xFF) : format;
-        const bool form_ok = format_word ? (format >= 0 && (format & ~0xFFF) == 0 && (form <= KX_PACK_WAV16_BASE64 || form == KX_PACK_MULAW || form == KX_PACK_ALAW || form == KX_PACK_FLAC))
+        const bool form_ok = format_word ? (format >= 0 && (format & ~0xFFF) == 0 && (form <= KX_PACK_WAV16_BASE64 || form == KX_PACK_MULAW || form == KX_PACK_ALAW || form == KX_PACK_FLAC ||
+                                                         form == KX_PACK_ADPCM_WAV || form == KX_PACK_WAV16))
                                          : (format >= 0 && format <= KX_PACK_PCM16_MONO);
         if (!ids || n_tokens < 1 || n_tokens > KX_MAX_TOKENS || !(speed > 0.f) || !form_ok) {
             if (err && err_len)
-                snprintf(err, err_len, "%s: bad argument (1..512 tokens, speed > 0, format %s)", who, format_word ? "0..4, 8, 9, 12 | rate code << 8" : "0..2");
+                snprintf(err, err_len, "%s: bad argument (1..512 tokens, speed > 0, format %s)", who, format_word ? "0..4, 8, 9, 12, 17, 18 | rate code << 8" : "0..2");
             return false;
         }
         if (format_word && ((format >> 8) & 15) > 3) {

@@ -3,6 +3,7 @@
 
 #include <cstring>
 
+#include "adpcm_steps.h"
 #include "kweight_coefs.h"
 #include "limit_taps.h"
 #include "resample_taps.h"
@@ -13,7 +14,8 @@ namespace kx {
 // ---- the format word and the resampler's tables ------------------------------------------------------------------------------
 void check_format_word(int word) {
     const int form = format_form(word);
-    KX_REQUIRE(word >= 0 && (word & ~0xFFF) == 0 && (form <= 4 || form == 8 || form == 9 || form == FORM_FLAC), "infer: unknown output format");
+    KX_REQUIRE(word >= 0 && (word & ~0xFFF) == 0 && (form <= 4 || form == 8 || form == 9 || form == FORM_FLAC || form == FORM_ADPCM_WAV || form == FORM_WAV16),
+               "infer: unknown output format");
     KX_REQUIRE(format_rate(word) <= 3, "infer: unknown output sample rate");
 }
 
@@ -266,17 +268,21 @@ OutputBounds output_bounds(const RequestLayout& lay, int B, size_t n_samples, co
     // group's padding -- what a one-frame request needs beyond its samples.  Resampled floats per sample: every request at the
     // batch's highest ratio, 2 at 48 000 Hz, below 1 otherwise
     size_t per_sample = 0, y_per_sample = 0;
-    bool flac = false;
+    bool flac = false, adpcm = false;
     for (int i = 0; i < lay.n_format; ++i) {
         const int f = format_form(lay.formats[i]), c = format_rate(lay.formats[i]);
         flac = flac || f == FORM_FLAC;
-        size_t w = f == 1 ? 8 : (f == 2 || f == FORM_FLAC ? 2 : (f == 4 ? 3 : (f >= 8 ? 1 : 4)));
+        adpcm = adpcm || f == FORM_ADPCM_WAV;
+        // (ADPCM: A bytes for P = 2 A - 7 samples, below 1 byte a sample from A = 256 on; its last block is counted below)
+        size_t w = f == 1 ? 8 : (f == 2 || f == FORM_FLAC || f == FORM_WAV16 ? 2 : (f == 4 ? 3 : (f >= 8 ? 1 : 4)));
         if (c == 3) w *= 2;
         const size_t y = c == 0 ? 0 : (c == 3 ? 2 : 1);
         per_sample = w > per_sample ? w : per_sample;
         y_per_sample = y > y_per_sample ? y : y_per_sample;
     }
     OutputBounds bound{n_samples * per_sample + (size_t)lay.R * 64 + 16, n_samples * y_per_sample, 0, 0, 0, 0, 0, 0};
+    // (an ADPCM body beyond its samples: 60 header bytes and a last block padded to its full size, at most 1024 bytes)
+    if (adpcm) bound.packed_bytes += (size_t)lay.R * (size_t)(ADPCM_HEADER + ADPCM_MAX_BLOCK);
     if (flac) {  // (a FLAC body beyond its samples: 52 <= 64 bytes a request, counted above, and 16 a frame; the lengths block)
         bound.flac_slots = n_samples * (y_per_sample > 1 ? y_per_sample : 1) / (size_t)FLAC_BLOCK + (size_t)lay.R;
         bound.packed_bytes += 16 * bound.flac_slots + 8 + 8 * (size_t)lay.R;
@@ -331,8 +337,28 @@ long pack_request_bytes(int form, long n_samples) {
             KX_REQUIRE(36 + 2 * n <= 0xFFFFFFFFL, "pack: a 16-bit WAV file cannot hold that many samples (size field of 32 bits)");
             return 4 * ((44 + 2 * n + 2) / 3);
         case FORM_FLAC: return flac_bound(n);  // (the region; the body's true size is the device's to say)
+        case FORM_ADPCM_WAV: {
+            // (both size fields of 32 bits: the RIFF size 52 + A F, and N itself in the fact chunk, which is the first to overflow)
+            const long A = adpcm_block_bytes(format_rate(form));
+            KX_REQUIRE(n <= 0xFFFFFFFFL && 52 + A * adpcm_blocks(n, A) <= 0xFFFFFFFFL,
+                       "pack: an ADPCM WAV file cannot hold that many samples (size field of 32 bits)");
+            return ADPCM_HEADER + A * adpcm_blocks(n, A);
+        }
+        case FORM_WAV16:
+            KX_REQUIRE(36 + 2 * n <= 0xFFFFFFFFL, "pack: a 16-bit WAV file cannot hold that many samples (size field of 32 bits)");
+            return (44 + 2 * n + 3) & ~3L;
         default: return n;  // 8, 9: one G.711 byte per sample
     }
+}
+
+long adpcm_block_bytes(int rate_code) {
+    static const long bytes[4] = {KX_ADPCM_BLOCK_BYTES};
+    KX_REQUIRE(rate_code >= 0 && rate_code <= 3, "infer: unknown output sample rate");
+    return bytes[rate_code];
+}
+const int* adpcm_steps() {
+    static const int steps[KX_ADPCM_NSTEPS] = {KX_ADPCM_STEPS};
+    return steps;
 }
 
 long flac_bound(long n_samples) { return (49 + 16 * flac_frames(n_samples) + 2 * n_samples + 3) & ~3L; }
@@ -419,7 +445,7 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
     KX_REQUIRE(row == B, "infer: chunks_per_request entries must be >= 1 and add up to the batch");
     // the requests: the table of the packer and the resampler over that prefix, and the rows' marks behind the bodies
     plan.req.assign((size_t)R, PackReq{});
-    plan.total_bytes = plan.max_units = plan.y_floats = plan.max_resampled = 0;
+    plan.total_bytes = plan.max_units = plan.y_floats = plan.max_resampled = plan.adpcm_groups = 0;
     plan.mark.assign(lens ? (size_t)B : 0, MarkRow{-1, 0, 0});
     plan.count.assign((size_t)R, 0);
     plan.first.assign((size_t)R, 0);
@@ -445,7 +471,14 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
         q.out_off = plan.total_bytes;
         q.out_bytes = pack_request_bytes(word, q.src_samples);
         plan.total_bytes += q.out_bytes;
-        const long units = q.form == FORM_FLAC ? 0 : ((q.out_off & 15) + q.out_bytes + 15) / 16;  // (the packer writes no FLAC region)
+        // (the packer writes no FLAC region and no ADPCM region)
+        const long units = q.form == FORM_FLAC || q.form == FORM_ADPCM_WAV ? 0 : ((q.out_off & 15) + q.out_bytes + 15) / 16;
+        if (q.form == FORM_ADPCM_WAV) {  // (the workgroup of block 0 writes the header: one group even where there is no block)
+            const long A = adpcm_block_bytes(q.rate), per_group = ADPCM_GROUP_BYTES / A;
+            const long groups = (adpcm_blocks(q.n_samples, A) + per_group - 1) / per_group;
+            const long wanted = groups > 1 ? groups : 1;
+            plan.adpcm_groups = wanted > plan.adpcm_groups ? wanted : plan.adpcm_groups;
+        }
         plan.max_units = units > plan.max_units ? units : plan.max_units;
         plan.first[(size_t)r] = plan.n_marks;
         if (lens) {

@@ -326,6 +326,8 @@ struct OutputTables {
 // the peak pass and request_loudness_gain_kernel behind the gain kernel, {I, n_g} of every metered request at d_packed + plan.loud_off.
 // A plan with a FLAC request (OutputPlan::has_flac): the three FLAC kernels behind the limiter, the body at the front of its region
 // and the true size of every region at d_packed + plan.flac_off; host_request.h: close_flac_gaps moves the regions together.
+// A plan with an ADPCM request (OutputPlan::adpcm_groups > 0): adpcm_blocks_kernel at the same place writes those regions, header and
+// blocks, where the plan put them; the packer leaves them alone.
 void launch_output_plan(const float* audio, long audio_ld, const int* dur, const int* lens, const OutputPlan& plan,
                         const OutputTables& t, float* d_y, void* d_packed, hipStream_t s);
 // its two halves: the bodies, and the marks (n_marks > 0) into a block of their own, 8-byte aligned

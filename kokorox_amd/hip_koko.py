@@ -24,6 +24,10 @@ PACK_F32_MONO, PACK_F32_STEREO, PACK_PCM16_MONO = 0, 1, 2
 PACK_WAV_F32, PACK_WAV16_BASE64 = 3, 4  # the servers' bodies (infer_requests / submit_request only): float WAV, base64 of a 16-bit WAV
 PACK_MULAW, PACK_ALAW = 8, 9  # raw G.711, one byte per sample (infer_requests / submit_request only)
 PACK_FLAC = 12  # a lossless FLAC body of the 16-bit samples (infer_requests / submit_request only); its size follows from the samples
+# (infer_requests / submit_request only) a WAV file of 4-bit IMA ADPCM, the form's number being the WAV tag it carries, and the plain
+# 16-bit WAV file that PACK_WAV16_BASE64 encodes, as bytes
+PACK_ADPCM_WAV, PACK_WAV16 = 17, 18
+ADPCM_MAX_BLOCK = 1024
 # the output sample rate, or'ed into the form of infer_requests / submit_request (the format word of include/kokorox_hip.h)
 PACK_RATE_24000, PACK_RATE_8000, PACK_RATE_16000, PACK_RATE_48000 = 0x000, 0x100, 0x200, 0x300
 RATE_HZ = {0: 24000, 1: 8000, 2: 16000, 3: 48000}  # by rate code (bits 8..11 of the word)
@@ -151,6 +155,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                                         C.POINTER(i64), vp, vp, vp, vp, vp, cp, sz]),
         "kx_loudness_filter": (i32, [i32, vp]),
         "kx_truepeak_filter": (i32, [vp, i32]),
+        "kx_adpcm_block": (i32, [i32, vp, vp]),
         "kx_infer_requests_loudness": (i32, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, u64, u32, vp, i32, C.POINTER(vp), vp, vp,
                                              vp, vp, vp, i32, vp, i32, vp]),
         "kx_dispatcher_submit_request_loudness": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
@@ -260,7 +265,7 @@ ABI_SYMBOLS = [
     "kx_free_audio", "kx_infer_device", "kx_sync", "kx_set_pinned_durations", "kx_warmup", "kx_arena_bytes", "kx_call_times", "kx_model_status", "kx_model_info", "kx_dispatcher_health", "kx_set_utterance_base", "kx_set_lanes",
     "kx_set_conv_mode", "kx_get_conv_mode", "kx_set_stft_variant", "kx_get_stft_variant",
     "kx_profile_enable", "kx_profile_read", "kx_profile_detail", "kx_profile_aux", "kx_diag_enable", "kx_diag_count", "kx_diag_get", "kx_set_act_prescale", "kx_set_voice_table", "kx_infer_voices",
-    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_infer_requests_levelled", "kx_dispatcher_submit_request_levelled", "kx_loudness_filter", "kx_truepeak_filter", "kx_infer_requests_loudness", "kx_dispatcher_submit_request_loudness", "kx_limit_filter", "kx_infer_requests_limited", "kx_dispatcher_submit_request_limited", "kx_infer_prosody", "kx_infer_requests_prosody", "kx_dispatcher_submit_request_prosody", "kx_infer_requests_fitted", "kx_dispatcher_submit_request_fitted", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
+    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_infer_requests_levelled", "kx_dispatcher_submit_request_levelled", "kx_loudness_filter", "kx_truepeak_filter", "kx_adpcm_block", "kx_infer_requests_loudness", "kx_dispatcher_submit_request_loudness", "kx_limit_filter", "kx_infer_requests_limited", "kx_dispatcher_submit_request_limited", "kx_infer_prosody", "kx_infer_requests_prosody", "kx_dispatcher_submit_request_prosody", "kx_infer_requests_fitted", "kx_dispatcher_submit_request_fitted", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
     "kx_dispatcher_stats", "kx_dispatcher_failures", "kx_dispatcher_destroy", "kx_debug_tap",
 ]
 
@@ -424,11 +429,24 @@ def resample_filter(word: int):
     return L.value, M.value, taps[: n.value].copy()
 
 
+def adpcm_block(word: int = 0):
+    """(A, P) of PACK_ADPCM_WAV at the rate of a format word: the bytes of a block and the samples it holds (kx_adpcm_block; host
+    only)."""
+    a, p = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+    rc = load_library().kx_adpcm_block(int(word), _ptr(a), _ptr(p))
+    if rc != KX_OK:
+        raise KokoroxHipError(rc, "kx_adpcm_block: unknown output sample rate")
+    return int(a[0]), int(p[0])
+
+
 def _decode_packed(raw: bytes, fmt: int):
     """A request's region as Python hands it out: samples as an array for forms 0..2 and 8 / 9 (uint8), the body as bytes for
-    forms 3, 4 and 12 (FLAC); at the output rate of the word."""
+    forms 3, 4, 12 (FLAC), 17 (ADPCM WAV) and 18 (16-bit WAV, its zero padding to a multiple of 4 cut off); at the output rate of
+    the word."""
     fmt = int(fmt) & 0xFF
-    if fmt in (PACK_WAV_F32, PACK_WAV16_BASE64, PACK_FLAC):
+    if fmt == PACK_WAV16:  # (the file is as long as its RIFF size says: 8 + that)
+        return raw[: 8 + int.from_bytes(raw[4:8], "little")]
+    if fmt in (PACK_WAV_F32, PACK_WAV16_BASE64, PACK_FLAC, PACK_ADPCM_WAV):
         return raw
     if fmt in (PACK_MULAW, PACK_ALAW):
         return np.frombuffer(raw, dtype=np.uint8).copy()
@@ -669,7 +687,7 @@ class HipKoko:
         `weights` [B, max_mix] as infer_voices.  `fmt` = one format word (a PACK_* form, optionally | PACK_RATE_*) for all, or one
         per request.  Returns one entry per request: its chunks' samples back to back, at the word's rate, as an array for forms
         0..2 (float32, [n, 2] float32, int16) and the G.711 forms (uint8), the body as `bytes` for PACK_WAV_F32,
-        PACK_WAV16_BASE64 and PACK_FLAC (whose size follows from the samples).  with_samples: also the library's own sample count of every request (out_samples, at the output
+        PACK_WAV16_BASE64, PACK_FLAC (whose size follows from the samples), PACK_ADPCM_WAV and PACK_WAV16.  with_samples: also the library's own sample count of every request (out_samples, at the output
         rate), as a second list."""
         res, _, nsamp, _ = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, False)
         return (res, nsamp) if with_samples else res
@@ -1030,7 +1048,7 @@ class Dispatcher:
         """A request of 1 .. max_batch chunks (kx_dispatcher_submit_request): `chunks` = the 0-wrapped id lists; `styles` = one
         256-float row per chunk, OR `voices` as in submit_ex (one voice spec for the request); `fmt` = a format word (a PACK_*
         form, optionally | PACK_RATE_*).  Returns what HipKoko.infer_requests returns for one request: an array (forms 0..2, 8, 9)
-        or the body as bytes (3, 4, 12 = FLAC).  marks=True (kx_dispatcher_submit_request_marks): returns (body, marks), marks = the
+        or the body as bytes (3, 4, 12 = FLAC, 17 = ADPCM WAV, 18 = 16-bit WAV).  marks=True (kx_dispatcher_submit_request_marks): returns (body, marks), marks = the
         request's token marks as one int64 array (HipKoko.infer_requests_marks).  join = (flags, keep_ms, pause_ms, fade_ms)
         (kx_dispatcher_submit_request_joined): the request's seams shaped as HipKoko.infer_requests_joined shapes them.
         level = (mode, gain, peak) (kx_dispatcher_submit_request_levelled): the request's level set as

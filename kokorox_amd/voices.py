@@ -17,6 +17,8 @@ only ever sees ids and one 256-float row per utterance.
 from __future__ import annotations
 
 import base64
+import os
+import re
 import struct
 from typing import Dict, List, Sequence
 
@@ -342,6 +344,118 @@ def flac_body(v_int16, rate: int) -> bytes:
     info += ((int(rate) << 44) | (0 << 41) | (15 << 36) | N).to_bytes(8, "big") + bytes(16)
     p = (2 - sum(sizes)) % 4
     return b"fLaC" + bytes([0x00, 0, 0, 34]) + info + bytes([0x81, 0, 0, p]) + bytes(p) + b"".join(frames)
+
+
+# ---- IMA ADPCM in a WAV file and the 16-bit WAV file (forms 17 and 18; include/kokorox_hip.h, "IMA ADPCM") ----------------------
+ADPCM_INDEX_STEPS = (-1, -1, -1, -1, 2, 4, 6, 8)
+ADPCM_START_DIFFS = 8  # a block's start index looks at its first so many differences (KX_ADPCM_START_DIFFS of adpcm_steps.h)
+ADPCM_BLOCK_BYTES = {8000: 256, 16000: 512, 24000: 512, 48000: 1024}  # A by rate; a block holds P = 1 + 2 (A - 4) samples
+
+
+def adpcm_steps() -> np.ndarray:
+    """The 89 steps, from the one table the kernel and the host are compiled with (kokorox_amd/csrc/adpcm_steps.h)."""
+    text = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "adpcm_steps.h"), encoding="utf-8").read()
+    body = re.search(r"#define KX_ADPCM_STEPS((?:.*\\\n)*.*)\n", text).group(1)
+    steps = np.array([int(v) for v in re.findall(r"\d+", body)], dtype=np.int64)
+    if steps.shape[0] != 89:
+        raise ValueError("adpcm_steps: adpcm_steps.h does not hold 89 steps")
+    return steps
+
+
+def adpcm_blocks(v_int16, rate: int) -> np.ndarray:
+    """The F = ceil(N / P) blocks of form 17 as uint8 [F, A]: every block the int16 predictor (its first sample), the start index
+    i0 = the smallest i with STEP[i] >= the largest of |v[t + 1] - v[t]|, t = 0..7, over the block's own samples (88 when none; the
+    samples past N repeat v[N - 1]), a zero byte, and the codes of its other P - 1 samples by the standard IMA / DVI step, two a byte, the earlier one
+    in the low nibble.  All blocks advance together, one sample per pass: a block depends on nothing outside it."""
+    v = np.asarray(v_int16).astype(np.int64).reshape(-1)
+    A = ADPCM_BLOCK_BYTES[int(rate)]
+    P = 1 + 2 * (A - 4)
+    N = v.shape[0]
+    F = (N + P - 1) // P
+    out = np.zeros((F, A), dtype=np.uint8)
+    if F == 0:
+        return out
+    steps = adpcm_steps()
+    x = np.concatenate([v, np.full(F * P - N, v[-1], dtype=np.int64)]).reshape(F, P)
+    pred = x[:, 0].copy()
+    index = np.minimum(np.searchsorted(steps, np.abs(np.diff(x[:, : ADPCM_START_DIFFS + 1], axis=1)).max(axis=1), side="left"), 88)
+    out[:, 0:2] = pred.astype("<i2").view(np.uint8).reshape(F, 2)
+    out[:, 2] = index
+    table = np.asarray(ADPCM_INDEX_STEPS, dtype=np.int64)
+    codes = np.zeros((F, P - 1), dtype=np.int64)
+    for t in range(1, P):
+        step = steps[index]
+        d = x[:, t] - pred
+        sign = d < 0
+        d = np.abs(d)
+        code = np.zeros(F, dtype=np.int64)
+        vp = step >> 3
+        for bit, shift in ((4, 0), (2, 1), (1, 2)):
+            s = step >> shift
+            take = d >= s
+            code |= np.where(take, bit, 0)
+            d = np.where(take, d - s, d)
+            vp = np.where(take, vp + s, vp)
+        pred = np.clip(np.where(sign, pred - vp, pred + vp), -32768, 32767)
+        index = np.clip(index + table[code], 0, 88)
+        codes[:, t - 1] = code | np.where(sign, 8, 0)
+    out[:, 4:] = (codes[:, 0::2] | (codes[:, 1::2] << 4)).astype(np.uint8)
+    return out
+
+
+def adpcm_wav_body(v_int16, rate: int) -> bytes:
+    """Form 17: the 60-byte header (RIFF, fmt of 20 bytes with tag 0x11, fact = N, data) and the blocks of `adpcm_blocks`."""
+    v = np.asarray(v_int16).reshape(-1)
+    A = ADPCM_BLOCK_BYTES[int(rate)]
+    P = 1 + 2 * (A - 4)
+    N = v.shape[0]
+    F = (N + P - 1) // P
+    if N > 0xFFFFFFFF or 52 + A * F > 0xFFFFFFFF:
+        raise ValueError("adpcm_wav_body: an ADPCM WAV file cannot hold that many samples")
+    hdr = struct.pack("<4sI4s4sIHHIIHHHH4sII4sI", b"RIFF", 52 + A * F, b"WAVE", b"fmt ", 20, 0x11, 1, rate, rate * A // P, A, 4, 2, P,
+                      b"fact", 4, N, b"data", A * F)
+    return hdr + adpcm_blocks(v, rate).tobytes()
+
+
+def adpcm_wav_decode(body: bytes):
+    """(int16 samples, rate) of a form-17 body: the header read field by field, every block decoded from its own header state by
+    the standard step (the inverse of `adpcm_blocks`: the decoder follows the encoder's predictor exactly), cut to the N of the
+    fact chunk.  Raises ValueError for anything that is not this project's layout."""
+    if len(body) < 60:
+        raise ValueError("adpcm_wav_decode: shorter than the header")
+    (riff, size, wave, fmt_, fmt_size, tag, ch, rate, bps, A, bits, cb, P, fact, fact_size, N, data, n_data) = struct.unpack(
+        "<4sI4s4sIHHIIHHHH4sII4sI", body[:60])
+    ok = (riff, wave, fmt_, fact, data) == (b"RIFF", b"WAVE", b"fmt ", b"fact", b"data") and (fmt_size, tag, ch, bits, cb, fact_size) == (20, 0x11, 1, 4, 2, 4)
+    ok = ok and A >= 8 and P == 1 + 2 * (A - 4) and bps == rate * A // P and n_data % A == 0 and size == 52 + n_data and len(body) == 60 + n_data
+    F = n_data // A if ok else 0
+    if not ok or F != (N + P - 1) // P:
+        raise ValueError("adpcm_wav_decode: not an IMA ADPCM WAV body of this layout")
+    blocks = np.frombuffer(body, dtype=np.uint8, offset=60).reshape(F, A).astype(np.int64)
+    if F and (blocks[:, 2].max() > 88 or blocks[:, 3].any()):
+        raise ValueError("adpcm_wav_decode: bad block header")
+    steps = adpcm_steps()
+    table = np.asarray(ADPCM_INDEX_STEPS, dtype=np.int64)
+    out = np.zeros((F, P), dtype=np.int64)
+    pred = blocks[:, 0:2].astype(np.uint8).reshape(-1).view("<i2").astype(np.int64)
+    index = blocks[:, 2].copy()
+    out[:, 0] = pred
+    codes = np.empty((F, P - 1), dtype=np.int64)
+    codes[:, 0::2] = blocks[:, 4:] & 15
+    codes[:, 1::2] = blocks[:, 4:] >> 4
+    for t in range(1, P):
+        step = steps[index]
+        c = codes[:, t - 1]
+        vp = (step >> 3) + np.where(c & 4, step, 0) + np.where(c & 2, step >> 1, 0) + np.where(c & 1, step >> 2, 0)
+        pred = np.clip(np.where(c & 8, pred - vp, pred + vp), -32768, 32767)
+        index = np.clip(index + table[c & 7], 0, 88)
+        out[:, t] = pred
+    return out.reshape(-1)[:N].astype(np.int16), int(rate)
+
+
+def wav16_body(samples, rate: int = SAMPLE_RATE) -> bytes:
+    """Form 18, the file itself: the bytes `wav16_base64` encodes -- the 44-byte header with its true sizes and the samples
+    through `pcm16`; 44 + 2 N bytes.  (A request's region holds it padded with zero bytes to a multiple of 4: `stream_body`.)"""
+    return base64.b64decode(wav16_base64(samples, rate))
 
 
 _RATE_LM = {0: (1, 1), 1: (1, 3), 2: (2, 3), 3: (2, 1)}  # rate code of a format word -> (L, M): 24 000, 8000, 16 000, 48 000 Hz
@@ -765,6 +879,11 @@ def stream_body(y, word: int) -> bytes:
         return (mulaw_bytes if form == 8 else alaw_bytes)(pcm16(y)).tobytes()
     if form == 12:
         return flac_body(pcm16(y), rate)
+    if form == 17:
+        return adpcm_wav_body(pcm16(y), rate)
+    if form == 18:  # (the region: the file and its zero padding to a multiple of 4)
+        body = wav16_body(y, rate)
+        return body + bytes(-len(body) % 4)
     raise ValueError("stream_body: unknown output format")
 
 

@@ -23,6 +23,9 @@ the command line; an optional second argument is the batch (1 = one utterance). 
     '12' / '0x30c'       kx_infer_requests in form 12 (FLAC; '0x30c' = at 48 kHz), every row a request of its own: flac_frames_kernel,
                          flac_layout_kernel and flac_gather_kernel in the packer's place (pack_requests_kernel does not show: no
                          request has a region for it); prints the bodies' bytes beside the PCM16 bytes of the same samples;
+    '17' / '0x111'       kx_infer_requests in form 17 (IMA ADPCM in a WAV file; '0x111' = at 8 kHz), every row a request of its own:
+                         adpcm_blocks_kernel in the packer's place (pack_requests_kernel does not show); '18' = the 16-bit WAV file,
+                         a branch of pack_requests_kernel;
     a word and 'r'       ('2r') kx_infer_requests_prosody with a rate, a pitch and an energy per token and the report, every row a
                          request of its own: prosody_duration_kernel in duration_kernel's place (the pinned pattern still sets the
                          frames) and prosody_curves_kernel behind the F0 / N predictors;
@@ -108,6 +111,12 @@ for it in range(3):
         assert all(o[:4] == b"fLaC" and len(o) % 4 == 0 for o in out)
         if it == 2:
             print("FLAC bytes %d, PCM16 bytes of the same samples %d: ratio %.4f" % (sum(len(o) for o in out), 2 * sum(ns), sum(len(o) for o in out) / (2.0 * sum(ns))))
+    elif int(which, 0) & 0xFF == hk.PACK_ADPCM_WAV:
+        out, ns = m.infer_requests(toks, [1] * B, styles=rows, fmt=int(which, 0), with_samples=True)
+        A, P = hk.adpcm_block(int(which, 0))
+        assert all(o[:4] == b"RIFF" and len(o) == 60 + A * -(-n // P) for o, n in zip(out, ns))
+        if it == 2:
+            print("ADPCM bytes %d, PCM16 bytes of the same samples %d: ratio %.4f" % (sum(len(o) for o in out), 2 * sum(ns), sum(len(o) for o in out) / (2.0 * sum(ns))))
     else:
         out = m.infer_requests(toks, [1] * B, styles=rows, fmt=int(which, 0))
     n = sum(len(o) if isinstance(o, bytes) else o.nbytes for o in out)
