@@ -774,6 +774,70 @@ int kx_infer_requests_fitted(kx_model* m, const int64_t* ids, int64_t t_stride, 
                              int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_prosody* prosody,
                              float** out_report, int64_t* out_n_report, const kx_fit_span* spans, int n_spans, kx_fit_result* out_fit);
 
+/* ---- pieces: a request delivered in several calls whose payloads join byte for byte ---------------------------------------------
+ * A request's body is complete only when all its chunks have been through the forward.  A *piece* is a run of consecutive chunks
+ * of a request, submitted as one request of a call, with a flag word and a carry record; the caller sends the chunks it has, gets
+ * the bytes that are final, and hands the carry it got back to the next piece.  The invariant:
+ *
+ *     the payloads of a request's pieces, laid end to end, ARE the body of the same request run whole -- every byte -- and
+ *     their marks are its marks.
+ *
+ * KX_PIECE_FIRST marks the first piece of a request, KX_PIECE_LAST the last; a request run whole is the single piece with both
+ * flags, and is planned and launched exactly as through kx_infer_requests_levelled (its carry-out is all zeros).
+ *
+ * Let x[0..A) be the whole request's stream at 24 000 Hz after the join, y[0..N) that stream at the output rate after the
+ * resampler and the gain, A_k the joined source samples of pieces 0..k, and (L, M, C) the rate's filter of 2 C + 1 taps
+ * (kx_resample_filter).  Output n is *final* once its window lies inside the data, n M + C <= A_k L - 1:
+ *     F_k = clamp(floor((A_k L - 1 - C) / M) + 1, 0, N)      final outputs after piece k
+ *     E_k = 4 floor(F_k / 4)                                  emitted after piece k (every region stays a multiple of 4 bytes)
+ * with E_k = A_k at rate code 0 and E_k = N for the last piece.  Piece k's payload is the bytes of samples [E_{k-1}, E_k) in the
+ * request's form, behind the form's header in the FIRST piece only; out_samples is E_k - E_{k-1}.  It may be 0, and a piece of 0
+ * bytes is a good result.  The accumulation of every output is the whole request's: float64 from +0, j ascending over the terms
+ * that exist (no source sample before x[0] and none at or past A), one rounding -- the same bits.
+ *
+ * Joins: a piece's rows get the join rows they have in the whole request.  Head rules apply only under KX_PIECE_FIRST, tail rules
+ * only under KX_PIECE_LAST; a piece that is not last keeps the pause behind its final chunk; every boundary between pieces is an
+ * inner boundary.  Marks are the whole request's ("joins"), positions in the whole body's sample stream, their base from the carry.
+ *
+ * A piece may ask for forms 0, 1, 2, 3, 8 and 9, any rate, any join spec, marks, and a level of mode KX_LEVEL_GAIN (a product per
+ * sample; the p it reports is the piece's).  What needs the whole body before the first byte is refused with KX_ERR_INVALID before
+ * any device work, "infer: a piece cannot carry <noun>": `a measured level` (modes NORMALIZE and CEILING, KX_PEAK_TRUE), `loudness`,
+ * `a limiter`, `a sized form` (4, 12, 17 and 18: their headers hold sizes).  Prosody and fit spans are per call.  Out of scope:
+ * ADPCM and FLAC pieces (block and frame alignment need a larger hold-back, STREAMINFO holds totals), a streaming limiter or
+ * loudness, MP3, text segmentation.
+ *
+ * The carry is a POD the caller owns, one per request in and one out.  `tail` holds the last n_tail = min(KX_PIECE_TAIL, A_k)
+ * samples of the joined 24 000 Hz stream so far (n_tail = 0 at rate code 0) and zeros behind them: every source sample an output
+ * not yet emitted reads -- at most (2 C + 3 M) / L = 153 of them, at 8000 Hz.  The GPU writes the carry-out into a block of its own
+ * behind every other block of the packed buffer, so body, marks and carry leave the device in one copy.  A FIRST piece ignores its
+ * carry-in.  Any other piece is refused with "infer: bad piece carry" when its carry has another magic, a format word other than
+ * the piece's, or fields that do not belong together (n_tail, out_samples = E of src_samples, src_samples a multiple of 24).  The
+ * model keeps no state between calls and the dispatcher none between submissions. */
+#define KX_PIECE_FIRST 1u
+#define KX_PIECE_LAST  2u
+#define KX_PIECE_TAIL  256
+#define KX_PIECE_MAGIC 0x4350584Bu
+typedef struct kx_piece_carry {
+    uint32_t magic;        /* KX_PIECE_MAGIC */
+    uint32_t format_word;  /* the request's format word */
+    int64_t src_samples;   /* A_k */
+    int64_t out_samples;   /* E_k */
+    int32_t n_tail;
+    int32_t reserved;      /* chunks of the pieces so far (the dispatcher numbers a later piece's rows from it) */
+    float tail[KX_PIECE_TAIL];
+} kx_piece_carry;   /* 1056 bytes */
+/* kx_infer_requests_levelled with pieces: piece_flags [R], carry_in [R] (entry r is read unless request r has KX_PIECE_FIRST; may
+ * be NULL when none is read), carry_out [R].  `levels` may be NULL with n_level == 0 here (no levels), `joins` with n_join == 0.
+ * Refused after everything kx_infer_requests_levelled refuses: a null piece_flags or carry_out ("infer: null piece argument"), a
+ * flag word with a bit beyond the two ("infer: bad piece flags"; 0 is a piece that is neither the first nor the last), and the refusals above. */
+int kx_infer_requests_pieces(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                             const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                             const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                             const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                             int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_level* levels,
+                             int n_level, double* out_levels, const uint32_t* piece_flags, const kx_piece_carry* carry_in,
+                             kx_piece_carry* carry_out);
+
 /* ---- request dispatcher ----------------------------------------------------
  * Replaces the reference's one-request-at-a-time `Mutex<Session>` (kokorox/src/onn/ort_koko.rs:78; callers
  * kokorox-openai/src/lib.rs:370-439, kokorox-websocket/src/lib.rs:657-668).  Any number of threads submit
@@ -856,6 +920,19 @@ int kx_dispatcher_submit_request_levelled(kx_dispatcher* d, const int64_t* ids, 
                                           float speed, uint64_t seed, int format, void** out, int64_t* out_bytes,
                                           int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks, const kx_join* join,
                                           const kx_level* level, double* out_level, char* err, size_t err_len);
+/* kx_dispatcher_submit_request_levelled as a piece of a request (see "pieces" above): piece_flags = KX_PIECE_FIRST and / or
+ * KX_PIECE_LAST, carry_in the record the piece before left (NULL with KX_PIECE_FIRST), carry_out where this one's goes.  `join` and
+ * `level` may both be NULL here.  The rows of a later piece draw the noise they draw in the request run whole (the carry counts the
+ * chunks so far).  Refusals as kx_infer_requests_pieces names them, under "dispatcher_submit_request: " ("... a piece cannot carry a
+ * sized form", "... bad piece carry", "... bad piece flags", "... null piece argument").  Pieces of different requests, and pieces
+ * beside whole requests of every kind, share batches; payload, marks and carry equal those of kx_infer_requests_pieces whatever
+ * the piece was batched with. */
+int kx_dispatcher_submit_request_piece(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                       const float* styles, const int32_t* voice_ids, const float* weights, int n_mix, float speed,
+                                       uint64_t seed, int format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                                       int64_t** out_marks, int64_t* out_n_marks, const kx_join* join, const kx_level* level,
+                                       double* out_level, uint32_t piece_flags, const kx_piece_carry* carry_in,
+                                       kx_piece_carry* carry_out, char* err, size_t err_len);
 /* kx_dispatcher_submit_request_joined with the request's loudness spec (see "loudness" above); `join` may be NULL here (no
  * join).  out_loudness may be NULL; when given it receives four doubles, f64(p), g, I and n_g of the request.  A null or invalid
  * `loudness`: "dispatcher_submit_request: bad loudness"; every other refusal as kx_dispatcher_submit_request_joined.  Loudness,

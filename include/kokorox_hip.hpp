@@ -74,6 +74,10 @@ struct FitResult {
 };
 static_assert(sizeof(FitSpan) == sizeof(kx_fit_span) && sizeof(FitResult) == sizeof(kx_fit_result), "the layouts of kokorox_hip.h");
 
+// A request run in pieces ("pieces" in kokorox_hip.h): the flag bits, and the carry a piece leaves for the next one.
+constexpr uint32_t PIECE_FIRST = KX_PIECE_FIRST, PIECE_LAST = KX_PIECE_LAST;
+using PieceCarry = kx_piece_carry;
+
 class HipKoko {
   public:
     explicit HipKoko(const std::string& model_path, int device = 0) {
@@ -174,6 +178,42 @@ class HipKoko {
         }
         kx_free_packed(out);
         return bodies;
+    }
+
+    // One piece of ONE request (kx_infer_requests_pieces; "pieces" in kokorox_hip.h): tokens = the piece's chunks, flags = PIECE_FIRST
+    // and / or PIECE_LAST, carry = the record the piece before left (ignored with PIECE_FIRST) and, on return, the one this piece
+    // leaves.  Returns the piece's payload: the payloads of a request's pieces, end to end, are the body of the request run whole.
+    std::string infer_request_piece(const std::vector<std::vector<int64_t>>& tokens, const std::vector<std::vector<float>>& styles,
+                                    float speed, uint64_t seed, int format, uint32_t flags, PieceCarry& carry) const {
+        if (tokens.empty() || styles.size() != tokens.size()) throw std::invalid_argument("infer_requests: one style row per chunk");
+        const int B = (int)tokens.size();
+        size_t stride = 1;
+        for (const auto& t : tokens) stride = t.size() > stride ? t.size() : stride;
+        std::vector<int64_t> ids((size_t)B * stride, 0);
+        std::vector<int32_t> tl(B);
+        std::vector<float> st((size_t)B * KX_STYLE_DIM);
+        for (int b = 0; b < B; ++b) {
+            tl[b] = (int32_t)tokens[b].size();
+            for (size_t i = 0; i < tokens[b].size(); ++i) ids[(size_t)b * stride + i] = tokens[b][i];
+            if (styles[b].size() != KX_STYLE_DIM) throw std::invalid_argument("infer_requests: style rows need 256 floats");
+            for (int k = 0; k < KX_STYLE_DIM; ++k) st[(size_t)b * KX_STYLE_DIM + k] = styles[b][k];
+        }
+        void* out = nullptr;
+        int64_t nb = 0, ns = 0;
+        const int32_t fmt = format, rows = B;
+        PieceCarry next{};
+        const int rc = kx_infer_requests_pieces(h_, ids.data(), (int64_t)stride, tl.data(), B, &rows, 1, st.data(), nullptr, nullptr, 0,
+                                                &speed, 1, seed, 0, &fmt, 1, &out, &nb, &ns, nullptr, nullptr, nullptr, 0, nullptr, 0,
+                                                nullptr, &flags, &carry, &next);
+        if (rc != KX_OK) {
+            char msg[512];
+            kx_last_error_copy(h_, msg, sizeof(msg));
+            throw std::runtime_error(std::string("kokorox_hip error: ") + msg);
+        }
+        std::string body(static_cast<const char*>(out), static_cast<const char*>(out) + nb);
+        kx_free_packed(out);
+        carry = next;
+        return body;
     }
 
     // infer_requests with the token marks of every request (kx_infer_requests_marks; "token marks" in kokorox_hip.h): marks[r]

@@ -177,6 +177,19 @@ int kx_test_output_plan_flac(int device_id, const float* audio, int B, int64_t a
                              double* out_hops, int64_t hops_cap, int64_t* out_n_hops, const kx_limit* limits, double* out_limits,
                              int64_t* out_lengths, char* err, size_t err_len);
 
+/* The same with pieces (include/kokorox_hip.h, "pieces"): the levelled hook, `loudness` / out_loudness [R][4] as in the loudness hook
+ * (may both be NULL; the hop energies are not handed out) for a metered request run whole beside the pieces, and piece_flags [R],
+ * carry_in [R] (may be NULL when every piece has KX_PIECE_FIRST), carry_out [R] as kx_infer_requests_pieces takes them, host arrays
+ * in and out, through build_output_plan and launch_output_plan.  The carry block sits behind a guard of its own and has one behind
+ * it, as have the carried tails; the hook fails with KX_ERR_STATE where one is not as it was filled.  Needs audio. */
+int kx_test_output_plan_pieces(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames, const int32_t* dur,
+                               const int32_t* lens, const int32_t* chunks_per_request, int R, const int32_t* formats,
+                               const kx_join* joins, const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes,
+                               int64_t* out_samples, int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks,
+                               const kx_level* levels, double* out_levels, const kx_loudness* loudness, double* out_loudness,
+                               const uint32_t* piece_flags, const kx_piece_carry* carry_in, kx_piece_carry* carry_out, char* err,
+                               size_t err_len);
+
 /* The token-axis kernels of Model::front_half, alone.  Common to these hooks: rows padded to a multiple of 32 floats as in the
  * model, NaN in every input column a kernel must not read, -12345.5 (0xA5 bytes in integer buffers) in every output location it
  * must not write; what the caller cannot see (row padding, guard regions behind a buffer) the hook checks itself after the launch

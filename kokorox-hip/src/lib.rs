@@ -83,6 +83,29 @@ pub struct KxLevel {
     pub peak: f32,
 }
 
+/// A request run in pieces ("pieces" in kokorox_hip.h): the flag bits of a piece, and the record one piece leaves for the next
+/// (`kx_piece_carry`, 1056 bytes).  The payloads of a request's pieces, end to end, are the body of the request run whole.
+pub const KX_PIECE_FIRST: u32 = 1;
+pub const KX_PIECE_LAST: u32 = 2;
+pub const KX_PIECE_TAIL: usize = 256;
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct KxPieceCarry {
+    pub magic: u32,
+    pub format_word: u32,
+    pub src_samples: i64,
+    pub out_samples: i64,
+    pub n_tail: i32,
+    pub reserved: i32,
+    pub tail: [f32; KX_PIECE_TAIL],
+}
+
+impl KxPieceCarry {
+    /// What a first piece is given: nothing of it is read.
+    pub const EMPTY: KxPieceCarry =
+        KxPieceCarry { magic: 0, format_word: 0, src_samples: 0, out_samples: 0, n_tail: 0, reserved: 0, tail: [0.0; KX_PIECE_TAIL] };
+}
+
 impl KxLevel {
     /// The plain spec: the samples as they are (through the levelled entries: a peak meter).
     pub const PLAIN: KxLevel = KxLevel { mode: KX_LEVEL_GAIN, gain: 1.0, peak: 0.0 };
@@ -405,6 +428,20 @@ extern "C" {
                                              out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64,
                                              join: *const KxJoin, level: *const KxLevel, out_level: *mut f64, err: *mut c_char,
                                              err_len: usize) -> c_int;
+    fn kx_infer_requests_pieces(m: *mut KxModel, ids: *const i64, t_stride: i64, lens: *const i32, b: c_int,
+                                chunks_per_request: *const i32, r: c_int, styles: *const f32, voice_ids: *const i32,
+                                weights: *const f32, max_mix: c_int, speeds: *const f32, n_speed: c_int, seed: u64, flags: u32,
+                                formats: *const i32, n_format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                                out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64, joins: *const KxJoin,
+                                n_join: c_int, levels: *const KxLevel, n_level: c_int, out_levels: *mut f64,
+                                piece_flags: *const u32, carry_in: *const KxPieceCarry, carry_out: *mut KxPieceCarry) -> c_int;
+    fn kx_dispatcher_submit_request_piece(d: *mut KxDispatcher, ids: *const i64, chunk_tokens: *const i32, n_chunks: c_int,
+                                          styles: *const f32, voice_ids: *const i32, weights: *const f32, n_mix: c_int,
+                                          speed: f32, seed: u64, format: c_int, out: *mut *mut c_void, out_bytes: *mut i64,
+                                          out_samples: *mut i64, out_marks: *mut *mut i64, out_n_marks: *mut i64,
+                                          join: *const KxJoin, level: *const KxLevel, out_level: *mut f64, piece_flags: u32,
+                                          carry_in: *const KxPieceCarry, carry_out: *mut KxPieceCarry, err: *mut c_char,
+                                          err_len: usize) -> c_int;
     fn kx_dispatcher_stats(d: *mut KxDispatcher, n_requests: *mut i64, n_batches: *mut i64,
                            max_batch_seen: *mut i64) -> c_int;
     fn kx_dispatcher_failures(d: *mut KxDispatcher, n_replayed: *mut i64, n_retried: *mut i64) -> c_int;
@@ -1321,6 +1358,35 @@ impl HipKokoDispatcher {
         let marks = unsafe { std::slice::from_raw_parts(mk as *const i64, nm as usize) }.to_vec();
         unsafe { kx_free_packed(out) };
         Ok((v, marks, ns))
+    }
+
+    /// One piece of a request ("pieces" in kokorox_hip.h): `flags` = KX_PIECE_FIRST and / or KX_PIECE_LAST, `carry` the record the
+    /// piece before left (ignored with KX_PIECE_FIRST).  Returns the payload, its sample count and the carry for the next piece.
+    #[allow(clippy::too_many_arguments, clippy::type_complexity)]
+    pub fn submit_request_piece(&self, chunks: &[Vec<i64>], styles: &[f32], speed: f32, seed: u64, format: i32, join: Option<KxJoin>,
+                                flags: u32, carry: &KxPieceCarry) -> Result<(Vec<u8>, i64, KxPieceCarry), Box<dyn Error>> {
+        if styles.len() != KX_STYLE_DIM * chunks.len() {
+            return Err("submit_request: one style row of 256 floats per chunk is required".into());
+        }
+        let ids: Vec<i64> = chunks.iter().flatten().copied().collect();
+        let lens: Vec<i32> = chunks.iter().map(|c| c.len() as i32).collect();
+        let mut out: *mut c_void = ptr::null_mut();
+        let (mut nb, mut ns) = (0i64, 0i64);
+        let mut next = KxPieceCarry::EMPTY;
+        let mut err = vec![0 as c_char; 256];
+        let rc = unsafe {
+            kx_dispatcher_submit_request_piece(self.d, ids.as_ptr(), lens.as_ptr(), lens.len() as c_int, styles.as_ptr(), ptr::null(),
+                                               ptr::null(), 0, speed, seed, format, &mut out, &mut nb, &mut ns, ptr::null_mut(),
+                                               ptr::null_mut(), join.as_ref().map_or(ptr::null(), |j| j as *const KxJoin), ptr::null(),
+                                               ptr::null_mut(), flags, carry as *const KxPieceCarry, &mut next, err.as_mut_ptr(),
+                                               err.len())
+        };
+        if rc != KX_OK {
+            return Err(format!("kokorox_hip error {}: {}", rc, cstr_buf(&err)).into());
+        }
+        let v = unsafe { std::slice::from_raw_parts(out as *const u8, nb as usize) }.to_vec();
+        unsafe { kx_free_packed(out) };
+        Ok((v, ns, next))
     }
 
     /// `submit_request_joined` with the request's level spec ("levels" in kokorox_hip.h; `join` = None: no join): body, marks,

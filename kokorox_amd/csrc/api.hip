@@ -394,6 +394,10 @@ struct RequestExtras {
     const kx_fit_span* spans = nullptr;
     int n_spans = 0;
     kx_fit_result* out_fit = nullptr;
+    bool piece_entry = false;  // kx_infer_requests_pieces: the flags and the carry-out must be there (check_piece_call)
+    const uint32_t* piece_flags = nullptr;
+    const kx_piece_carry* carry_in = nullptr;
+    kx_piece_carry* carry_out = nullptr;
 };
 
 static int infer_requests(const RequestArgs& a, const RequestExtras& x) {
@@ -442,6 +446,12 @@ static int infer_requests(const RequestArgs& a, const RequestExtras& x) {
             hc.fit_spans = reinterpret_cast<const kx::FitSpan*>(x.spans);
             hc.n_fit_spans = x.n_spans;
             res.out_fit = reinterpret_cast<kx::FitResult*>(x.out_fit);
+        }
+        if (x.piece_entry) {
+            hc.piece_call = true;
+            hc.piece_flags = x.piece_flags;
+            hc.carry_in = reinterpret_cast<const kx::PieceCarry*>(x.carry_in);
+            hc.carry_out = reinterpret_cast<kx::PieceCarry*>(x.carry_out);
         }
         M.infer_host_ex(a.ids, a.t_stride, a.lens, a.B, a.speeds, a.n_speed, a.seed, a.flags, hc, res);
     });
@@ -531,6 +541,34 @@ int kx_infer_requests_levelled(kx_model* m, const int64_t* ids, int64_t t_stride
     RequestExtras x{out_marks, out_n_marks, joins, n_join};
     x.levels = {true, reinterpret_cast<const kx::LevelSpec*>(levels), n_level};
     x.out_values = out_levels;
+    return infer_requests({m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
+                           flags, formats, n_format, out, out_bytes, out_samples},
+                          x);
+}
+
+static_assert(sizeof(kx_piece_carry) == 1056 && sizeof(kx_piece_carry) == sizeof(kx::PieceCarry) &&
+                  offsetof(kx_piece_carry, magic) == offsetof(kx::PieceCarry, magic) &&
+                  offsetof(kx_piece_carry, format_word) == offsetof(kx::PieceCarry, format_word) &&
+                  offsetof(kx_piece_carry, src_samples) == offsetof(kx::PieceCarry, src_samples) &&
+                  offsetof(kx_piece_carry, out_samples) == offsetof(kx::PieceCarry, out_samples) &&
+                  offsetof(kx_piece_carry, n_tail) == offsetof(kx::PieceCarry, n_tail) && offsetof(kx_piece_carry, tail) == offsetof(kx::PieceCarry, tail) &&
+                  KX_PIECE_FIRST == kx::PIECE_FIRST && KX_PIECE_LAST == kx::PIECE_LAST && KX_PIECE_TAIL == kx::PIECE_TAIL &&
+                  KX_PIECE_MAGIC == kx::PIECE_MAGIC,
+              "kx_piece_carry is the layout of kx::PieceCarry");
+
+int kx_infer_requests_pieces(kx_model* m, const int64_t* ids, int64_t t_stride, const int32_t* lens, int B,
+                             const int32_t* chunks_per_request, int R, const float* styles, const int32_t* voice_ids,
+                             const float* weights, int max_mix, const float* speeds, int n_speed, uint64_t seed, uint32_t flags,
+                             const int32_t* formats, int n_format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                             int64_t** out_marks, int64_t* out_n_marks, const kx_join* joins, int n_join, const kx_level* levels,
+                             int n_level, double* out_levels, const uint32_t* piece_flags, const kx_piece_carry* carry_in,
+                             kx_piece_carry* carry_out) {
+    RequestExtras x{out_marks, out_n_marks, joins, n_join};
+    // (levels == NULL with n_level == 0: no levels; anything else goes through the levelled entry's checks)
+    if (levels || n_level != 0) x.levels = {true, reinterpret_cast<const kx::LevelSpec*>(levels), n_level};
+    x.out_values = out_levels;
+    x.piece_entry = true;
+    x.piece_flags = piece_flags, x.carry_in = carry_in, x.carry_out = carry_out;
     return infer_requests({m, ids, t_stride, lens, B, chunks_per_request, R, styles, voice_ids, weights, max_mix, speeds, n_speed, seed,
                            flags, formats, n_format, out, out_bytes, out_samples},
                           x);

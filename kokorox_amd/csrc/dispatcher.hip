@@ -28,6 +28,7 @@ struct ModelBackend {
         std::vector<double> levels;  // [R][2] = {f64(p), g} when some request of the batch came through the levelled entry, else empty
         std::vector<double> loud;    // [R][4] = {f64(p), g, I, n_g} when some request came through the loudness entry, else empty
         std::vector<double> limits;  // [R][5] = {f64(p), g, I, n_g, r} when some request came through the limiter's entry, else empty
+        std::vector<kx::PieceCarry> carries;  // [R] the carries the pieces of the batch leave, when it has one, else empty
         // the prosody report of the requests that want it: the last block of the same buffer (null: nobody asked)
         float* report = nullptr;
         std::vector<int64_t> n_report;
@@ -43,6 +44,7 @@ struct ModelBackend {
         size_t stride = 0;
         int mm = 1;
         bool any_voice = false, any_marks = false, any_join = false, any_level = false, any_loud = false, any_limit = false;
+        bool any_piece = false;
         bool any_rate = false, any_frames = false, any_pitch = false, any_energy = false, any_report = false;
         for (Request* r : batch) {
             any_rate = any_rate || !r->p_rate.empty();
@@ -50,6 +52,7 @@ struct ModelBackend {
             any_pitch = any_pitch || !r->p_pitch.empty();
             any_energy = any_energy || !r->p_energy.empty();
             any_report = any_report || r->want_report;
+            any_piece = any_piece || r->piece();
             any_limit = any_limit || r->limited;
             any_loud = any_loud || r->metered;
             any_marks = any_marks || r->want_marks;
@@ -73,6 +76,9 @@ struct ModelBackend {
         std::vector<kx::JoinSpec> joins(R);  // (a plain request beside a joined one: the all-zero spec, the plain bytes)
         std::vector<kx::LevelSpec> levels(R);  // (a request without levels beside a levelled one: the plain spec, z' = z)
         std::vector<kx::LoudSpec> louds(R);  // (a request without loudness beside a metered one: LOUD_NONE, the meter passes it by)
+        // (a request run whole beside a piece: PIECE_WHOLE, planned and launched as ever)
+        std::vector<uint32_t> piece_flags(any_piece ? (size_t)R : 0, kx::PIECE_WHOLE);
+        std::vector<kx::PieceCarry> carry_in(any_piece ? (size_t)R : 0);
         std::vector<kx::LimitSpec> limits(R);  // (a request without a limiter beside a limited one: LIMIT_NONE, the limiter passes it by)
         // the fit spans of the batch: every request's own, renumbered to its index in the batch (sorted by (request, begin) as the
         // requests' own lists are); a request without spans adds none, and its tokens get zeros in the fitted counts
@@ -91,6 +97,10 @@ struct ModelBackend {
             joins[q] = to_spec(r.join);
             levels[q] = to_spec(r.level);
             louds[q] = r.metered ? to_spec(r.loudness) : kx::LoudSpec{kx::LOUD_NONE, 0.0f, 0.0f};
+            if (r.piece()) {
+                piece_flags[(size_t)q] = r.piece_flags;
+                carry_in[(size_t)q] = r.carry_in;
+            }
             size_t at = 0;
             for (int c = 0; c < r.rows(); ++c, ++b) {
                 lens[b] = (int32_t)r.chunk_len(c);
@@ -108,7 +118,7 @@ struct ModelBackend {
                 }
                 speeds[b] = r.speed;
                 seeds[b] = r.seed;
-                uidx[b] = (uint32_t)c;
+                uidx[b] = (uint32_t)(r.chunk_base() + c);  // (a later piece's rows: numbered as in the request run whole)
             }
         }
         o.buf = nullptr;
@@ -121,6 +131,7 @@ struct ModelBackend {
         o.levels.assign(any_level ? (size_t)2 * R : 0, 0.0);
         o.loud.assign(any_loud ? (size_t)4 * R : 0, 0.0);
         o.limits.assign(any_limit ? (size_t)5 * R : 0, 0.0);
+        o.carries.assign(any_piece ? (size_t)R : 0, kx::PieceCarry{});
         int rc = KX_ERR_DEVICE;
         std::string err;
         {
@@ -143,6 +154,7 @@ struct ModelBackend {
                 if (any_level) hc.levels = {false, levels.data(), R};
                 if (any_loud) hc.loudness = {false, louds.data(), R};
                 if (any_limit) hc.limits = {false, limits.data(), R};
+                if (any_piece) hc.piece_flags = piece_flags.data(), hc.carry_in = carry_in.data(), hc.carry_out = o.carries.data();
                 const kx::ProsodySpec ps{any_rate ? p_rate.data() : nullptr, any_frames ? p_frames.data() : nullptr,
                                          any_pitch ? p_pitch.data() : nullptr, any_energy ? p_energy.data() : nullptr};
                 if (any_rate || any_frames || any_pitch || any_energy || any_report) {
@@ -265,6 +277,7 @@ struct ModelBackend {
                 r->level_out[0] = o.levels[(size_t)2 * b];
                 r->level_out[1] = o.levels[(size_t)2 * b + 1];
             }
+            if (r->piece() && !o.carries.empty()) r->carry_out = o.carries[(size_t)b];
             if (r->limited && !o.limits.empty())
                 for (int i = 0; i < 5; ++i) r->limit_out[i] = o.limits[(size_t)5 * b + i];
             if (r->metered && !o.loud.empty())
@@ -430,6 +443,18 @@ int kx_dispatcher_submit_request_limited(kx_dispatcher* d, const int64_t* ids, c
     if (!d) return no_dispatcher("dispatcher_submit_request", err, err_len);
     return d->submit_request_limited(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out,
                                      out_bytes, out_samples, out_marks, out_n_marks, join, limit, out_limit, err, err_len);
+}
+
+int kx_dispatcher_submit_request_piece(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,
+                                       const float* styles, const int32_t* voice_ids, const float* weights, int n_mix, float speed,
+                                       uint64_t seed, int format, void** out, int64_t* out_bytes, int64_t* out_samples,
+                                       int64_t** out_marks, int64_t* out_n_marks, const kx_join* join, const kx_level* level,
+                                       double* out_level, uint32_t piece_flags, const kx_piece_carry* carry_in,
+                                       kx_piece_carry* carry_out, char* err, size_t err_len) {
+    if (!d) return no_dispatcher("dispatcher_submit_request", err, err_len);
+    return d->submit_request_piece(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
+                                   out_samples, out_marks, out_n_marks, join, level, out_level, piece_flags, carry_in, carry_out, err,
+                                   err_len);
 }
 
 int kx_dispatcher_submit_request_loudness(kx_dispatcher* d, const int64_t* ids, const int32_t* chunk_tokens, int n_chunks,

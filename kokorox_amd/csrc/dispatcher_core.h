@@ -97,6 +97,13 @@ struct Request {
     bool limited = false;     // it came through the limiter's entry: its body is driven and limited by `limit`
     double limit_out[5] = {0.0, 1.0, 0.0, 0.0, 1.0};  // limited: f64(p), g, I, n_g and r of the request, as the GPU computed them
     bool want_marks = false;  // the token marks of the request beside its body (submit_request_marks); a batch may mix both kinds
+    // a piece of a request (submit_request_piece; include/kokorox_hip.h, "pieces"): its flags, the carry it came with and the one it
+    // leaves.  PIECE_WHOLE = a request run whole, as through every other entry; a batch may mix both kinds
+    uint32_t piece_flags = PIECE_WHOLE;
+    PieceCarry carry_in = {}, carry_out = {};
+    bool piece() const { return piece_flags != PIECE_WHOLE; }
+    // the index of its first chunk in the whole request: the rows of a later piece draw the noise they draw in the request run whole
+    int chunk_base() const { return piece() && !(piece_flags & PIECE_FIRST) ? carry_in.reserved : 0; }
     // its prosody (submit_request_prosody): per token, the chunks back to back as `ids`; an empty vector = that array was not given
     std::vector<float> p_rate, p_pitch, p_energy;
     std::vector<int32_t> p_frames;
@@ -148,6 +155,11 @@ struct RequestOptions {
     const kx_fit_span* spans = nullptr;  // the fit entry: the request's spans (n_spans == 0: none) and where their results go (may be null)
     int n_spans = 0;
     kx_fit_result* out_fit = nullptr;
+    // the piece entry: the flag word, the carry before (null with KX_PIECE_FIRST) and where the carry goes
+    bool need_piece = false;
+    uint32_t piece_flags = PIECE_WHOLE;
+    const kx_piece_carry* carry_in = nullptr;
+    kx_piece_carry* carry_out = nullptr;
     bool need_join = false, need_level = false, need_loudness = false, need_limit = false;
     // the entries behind the marks entry: either argument of the pair asks for marks, and then both must be there
     void set_marks(int64_t** marks, int64_t* n_marks) {
@@ -590,6 +602,20 @@ struct Core {
         return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
                                   out_samples, o, err, err_len);
     }
+    // ... and as a piece of a request (include/kokorox_hip.h, "pieces"); `join` and `level` may be null here, out_level may be null
+    int submit_request_piece(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
+                             const int32_t* voice_ids, const float* weights, int n_mix, float speed, uint64_t seed, int format,
+                             void** out, int64_t* out_bytes, int64_t* out_samples, int64_t** out_marks, int64_t* out_n_marks,
+                             const kx_join* join, const kx_level* level, double* out_level, uint32_t piece_flags,
+                             const kx_piece_carry* carry_in, kx_piece_carry* carry_out, char* err, size_t err_len) {
+        RequestOptions o;
+        o.set_marks(out_marks, out_n_marks);
+        o.join = join;
+        o.level = level, o.out_level = out_level;
+        o.need_piece = true, o.piece_flags = piece_flags, o.carry_in = carry_in, o.carry_out = carry_out;
+        return submit_request_any(ids, chunk_tokens, n_chunks, styles, voice_ids, weights, n_mix, speed, seed, format, out, out_bytes,
+                                  out_samples, o, err, err_len);
+    }
     // The submits above are this one.  The request's options are looked at first, a bad join before a bad level, loudness or limit,
     // then the report pair; the arguments every submit has come after them.
     int submit_request_any(const int64_t* ids, const int32_t* chunk_tokens, int n_chunks, const float* styles,
@@ -608,6 +634,17 @@ struct Core {
             return (int)KX_ERR_INVALID;
         };
         if (bad) return refuse("%s", bad);
+        if (o.need_piece) {  // (the model's refusals of a piece, under the dispatcher's name: "infer: ..." becomes "dispatcher_submit_request: ...")
+            static_assert(sizeof(kx_piece_carry) == sizeof(PieceCarry), "the layout of host_request.h");
+            if (!o.carry_out) return refuse("%s: null piece argument", who);
+            const LevelSpec ls = o.level ? to_spec(*o.level) : LevelSpec{LEVEL_GAIN, 1.0f, 0.0f};
+            RequestLayout lay{};
+            lay.R = 1, lay.formats = &format, lay.n_format = 1;
+            lay.levels = &ls, lay.n_level = 1;
+            lay.piece_flags = &o.piece_flags;
+            lay.carry_in = reinterpret_cast<const PieceCarry*>(o.carry_in);
+            if (const char* why = piece_refusal(lay)) return refuse("%s: %s", who, strncmp(why, "infer: ", 7) == 0 ? why + 7 : why);
+        }
         if (!out || !out_bytes || !out_samples) return refuse("%s: null output argument", who);
         if (o.want_marks && (!o.out_marks || !o.out_n_marks)) return refuse("%s: null marks argument", who);
         if (!ids || !chunk_tokens || n_chunks < 1 || n_chunks > max_batch) return refuse("%s: a request has 1..%d chunks (max_batch)", who, max_batch);
@@ -667,8 +704,13 @@ struct Core {
             r.limit = *o.limit;
             r.limited = true;
         }
+        if (o.need_piece) {
+            r.piece_flags = o.piece_flags;
+            if (r.piece() && !(r.piece_flags & PIECE_FIRST)) r.carry_in = *reinterpret_cast<const PieceCarry*>(o.carry_in);
+        }
         const int rc = submit(r, out, out_bytes, out_samples, err, err_len);
         if (rc != KX_OK) return rc;
+        if (o.need_piece) memcpy(o.carry_out, &r.carry_out, sizeof(PieceCarry));
         if (o.limit && o.out_limit)
             for (int i = 0; i < 5; ++i) o.out_limit[i] = r.limit_out[i];
         if (o.loudness && o.out_loudness)

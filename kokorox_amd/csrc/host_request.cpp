@@ -52,6 +52,22 @@ long resampled_samples(int rate_code, long n_samples) {
     return n_samples * f.L / f.M;
 }
 
+// ---- pieces (include/kokorox_hip.h, "pieces") ---------------------------------------------------------------------------------------
+static_assert(PIECE_TAIL >= piece_tail_need(1, 3, KX_RESAMPLE_NTAPS_8000) && PIECE_TAIL >= piece_tail_need(2, 3, KX_RESAMPLE_NTAPS_16000) &&
+                  PIECE_TAIL >= piece_tail_need(2, 1, KX_RESAMPLE_NTAPS_48000),
+              "a carry holds every source sample an output still to come reads");
+
+static_assert(KX_RESAMPLE_NTAPS_8000 == 2 * 72 + 1 && KX_RESAMPLE_NTAPS_16000 == 2 * 72 + 1 && KX_RESAMPLE_NTAPS_48000 == 2 * 48 + 1,
+              "piece_emitted has the three filters' C written out");
+
+void check_piece_call(const HostCall& hc) {
+    if (!hc.piece_call) return;  // (an entry without pieces; the dispatcher's pieces were checked when they were submitted)
+    KX_REQUIRE(hc.piece_flags && hc.carry_out, "infer: null piece argument");
+    KX_REQUIRE(hc.grouped(), "infer: pieces are for requests (chunks_per_request)");
+    const char* refusal = piece_refusal(hc.layout(0));
+    KX_REQUIRE(!refusal, refusal);
+}
+
 // ---- the true-peak meter's table (include/kokorox_hip.h, "levels") ---------------------------------------------------------------
 const float* truepeak_taps() {
     static_assert(KX_TRUEPEAK_PHASES == TRUEPEAK_PHASES && KX_TRUEPEAK_NTAPS == TRUEPEAK_NTAPS, "the committed table is [3][24]");
@@ -260,9 +276,11 @@ int check_device_call(const void* d_ids, int64_t t_stride, const int32_t* lens_h
 // ---- layout of the compact output ----------------------------------------------------------------------------------------------
 OutputBounds output_bounds(const RequestLayout& lay, int B, size_t n_samples, const int32_t* lens) {
     if (lay.joins && lay.chunks_per_request)
-        for (int r = 0; r < lay.R; ++r)
-            if (lay.chunks_per_request[r] > 1)
-                n_samples += (size_t)24 * (size_t)lay.joins[lay.n_join == 1 ? 0 : r].pause_ms * (size_t)(lay.chunks_per_request[r] - 1);
+        for (int r = 0; r < lay.R; ++r) {
+            // (a piece that is not the last keeps the pause behind its final chunk)
+            const int pauses = lay.chunks_per_request[r] - (lay.piece_flags && !(lay.piece_flags[r] & PIECE_LAST) ? 0 : 1);
+            if (pauses > 0) n_samples += (size_t)24 * (size_t)lay.joins[lay.n_join == 1 ? 0 : r].pause_ms * (size_t)pauses;
+        }
     // bytes per sample: 8 (stereo), 4 (f32, float WAV), 3 >= 8 / 3 (base64 of 16 bits), 2 (PCM16), 1 (G.711), twice that at 48 000 Hz
     // (the lower rates are counted as 24 000 Hz); per request: the 44-byte header, or its 60 base64 characters and the last
     // group's padding -- what a one-frame request needs beyond its samples.  Resampled floats per sample: every request at the
@@ -316,6 +334,13 @@ OutputBounds output_bounds(const RequestLayout& lay, int B, size_t n_samples, co
             bound.lim_floats = longest;
             bound.limit_dwords = bound.peak_dwords;
         }
+    }
+    if (lay.piece_flags) {
+        // (a piece also emits what the pieces before it held back: fewer than C / M + 4 <= 52 outputs, 8 bytes each at the most;
+        // then the alignment gap and the carry block)
+        bound.packed_bytes += (size_t)lay.R * 512;
+        if (y_per_sample > 0) bound.y_floats += (size_t)lay.R * 64;
+        bound.packed_bytes += 8 + (size_t)lay.R * sizeof(PieceCarry);
     }
     if (lay.reports) {  // (the alignment gap and a block in which every request wants the report)
         KX_REQUIRE(lens, "infer: reports need the token counts");
@@ -409,6 +434,10 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
                    (!lay.limits || lay.n_limit == 1 || lay.n_limit == R),
                "plan: bad argument");
     auto rows_of = [&](int r) { return lay.chunks_per_request ? lay.chunks_per_request[r] : 1; };
+    // (a request run in pieces: its head rules only in its first piece, its tail rules only in its last; PIECE_WHOLE where none is given)
+    const char* refusal = piece_refusal(lay);
+    KX_REQUIRE(!refusal, refusal);
+    auto flags_of = [&](int r) { return lay.piece_flags ? lay.piece_flags[r] : PIECE_WHOLE; };
     // the rows: what each contributes to its request's stream, and the prefix over it.  (A pass of its own: the refusals of the
     // rows speak before those of the request table below, whichever request they are in, and callers match on the text.)
     const JoinSpec as_it_is{};
@@ -425,7 +454,8 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
         const long k = 24L * js.keep_ms, fade = 24L * js.fade_ms;
         for (int b = row; b < row + n; ++b) {
             KX_REQUIRE(frames[b] >= 0 && (!lay.joins || (edges[2 * b] >= 0 && edges[2 * b + 1] >= 0)), "pack: negative frame count");
-            const bool first = b == row, last = b == row + n - 1, long_enough = js.flags != 0 && lens[b] >= 3;  // (shorter rows are pads only)
+            const bool first = b == row && (flags_of(r) & PIECE_FIRST) != 0, last = b == row + n - 1 && (flags_of(r) & PIECE_LAST) != 0;
+            const bool long_enough = js.flags != 0 && lens[b] >= 3;  // (shorter rows are pads only)
             const bool head = long_enough && (js.flags & (first ? JOIN_TRIM_HEAD : JOIN_TRIM_INNER)) != 0;
             const bool tail = long_enough && (js.flags & (last ? JOIN_TRIM_TAIL : JOIN_TRIM_INNER)) != 0;
             JoinRow& j = plan.join[(size_t)b];
@@ -450,6 +480,12 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
     plan.count.assign((size_t)R, 0);
     plan.first.assign((size_t)R, 0);
     plan.n_marks = 0;
+    // (a layout whose flags are all PIECE_WHOLE has no piece: its plan is that of the layout without them)
+    bool pieces = false;
+    for (int r = 0; r < R; ++r) pieces = pieces || flags_of(r) != PIECE_WHOLE;
+    plan.piece.assign(pieces ? (size_t)R : 0, PieceRow{});
+    plan.tail_in.clear();
+    plan.carry_off = 0;
     row = 0;
     for (int r = 0; r < R; ++r) {
         const int n = rows_of(r);
@@ -462,6 +498,28 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
         q.rate = format_rate(word);
         q.src_samples = plan.cum[(size_t)(row + n)] - plan.cum[(size_t)row];
         q.n_samples = resampled_samples(q.rate, q.src_samples);
+        const bool piece = flags_of(r) != PIECE_WHOLE;
+        long src_before = 0;  // A_{k-1}: the marks of a later piece start from it
+        if (pieces) {
+            PieceRow& pr = plan.piece[(size_t)r];
+            pr = PieceRow{0, q.n_samples, 0, q.src_samples, 0, 0, 0, 0, flags_of(r), (uint32_t)word, n, 0};
+            if (piece) {
+                if (!(pr.flags & PIECE_FIRST)) {
+                    const PieceCarry& c = lay.carry_in[r];
+                    pr.src_before = src_before = (long)c.src_samples;
+                    pr.emit_lo = (long)c.out_samples;
+                    pr.n_tail_in = c.n_tail;
+                    pr.chunks_end = c.reserved + n;
+                    pr.tail_in = (long)plan.tail_in.size();
+                    plan.tail_in.insert(plan.tail_in.end(), c.tail, c.tail + c.n_tail);
+                }
+                pr.src_end = pr.src_before + q.src_samples;
+                pr.emit_hi = piece_emitted(q.rate, pr.src_end, (pr.flags & PIECE_LAST) != 0);
+                pr.n_tail_out = q.rate == 0 ? 0 : (int)(pr.src_end < PIECE_TAIL ? pr.src_end : PIECE_TAIL);
+                KX_REQUIRE(pr.emit_hi >= pr.emit_lo, "infer: bad piece carry");
+                q.n_samples = pr.emit_hi - pr.emit_lo;
+            }
+        }
         q.y_off = 0;
         if (q.rate) {
             q.y_off = plan.y_floats;
@@ -470,6 +528,11 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
         }
         q.out_off = plan.total_bytes;
         q.out_bytes = pack_request_bytes(word, q.src_samples);
+        if (piece) {  // (its samples in the form, behind the header only in a first piece: a later piece of a float WAV is bare floats)
+            const bool bare = q.form == 3 && !(flags_of(r) & PIECE_FIRST);
+            if (bare) q.form = 0;
+            q.out_bytes = (q.form == 3 ? 44 : 0) + (q.form == 1 ? 8 : (q.form == 2 ? 2 : (q.form >= 8 ? 1 : 4))) * q.n_samples;
+        }
         plan.total_bytes += q.out_bytes;
         // (the packer writes no FLAC region and no ADPCM region)
         const long units = q.form == FORM_FLAC || q.form == FORM_ADPCM_WAV ? 0 : ((q.out_off & 15) + q.out_bytes + 15) / 16;
@@ -487,7 +550,7 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
                 KX_REQUIRE(lens[b] >= 1 && lens[b] <= 512, "infer: token count must be 1..512");
                 MarkRow& m = plan.mark[(size_t)b];
                 m.K = K;
-                m.src_base = plan.cum[(size_t)b] - plan.cum[(size_t)row];
+                m.src_base = src_before + plan.cum[(size_t)b] - plan.cum[(size_t)row];
                 m.base = m.src_base * K / 600;  // (exact: cum counts multiples of 24 samples)
                 m.skip = plan.join[(size_t)b].skip;
                 m.keep = plan.join[(size_t)b].keep;
@@ -610,6 +673,11 @@ void build_output_plan(const int* frames, const int* lens, const int* edges, int
     if (lay.reports) {
         plan.n_report = report_rows(lay, lens, B, plan.rep_first, &plan.rep_count);
         if (plan.n_report > 0) plan.report_off = (plan.fixed_end() + 7) & ~7L;
+    }
+    // the carries of a plan with pieces: one record per request, behind everything else
+    if (pieces) {
+        plan.carry_off = (plan.report_end() + 7) & ~7L;
+        for (int r = 0; r < R; ++r) plan.piece[(size_t)r].carry_off = plan.carry_off + (long)sizeof(PieceCarry) * r;
     }
 }
 

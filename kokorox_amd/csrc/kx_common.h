@@ -316,6 +316,10 @@ struct OutputTables {
     uint32_t* fslot;
     int* flen;
     long* foff;
+    // a plan with pieces (OutputPlan::has_pieces): piece [R], and piece_tail = the carried tails back to back, at most R * PIECE_TAIL
+    // floats; `join` is then used whatever the plan's other flags say
+    PieceRow* piece;
+    float* piece_tail;
 };
 // Everything between "the plan is built" and "copy to the host", for the model and for the test hook: the resampler when
 // plan.y_floats > 0 (d_y: that many floats, null when 0), the packer into d_packed (16-byte aligned, plan.total_bytes long), and
@@ -328,6 +332,9 @@ struct OutputTables {
 // and the true size of every region at d_packed + plan.flac_off; host_request.h: close_flac_gaps moves the regions together.
 // A plan with an ADPCM request (OutputPlan::adpcm_groups > 0): adpcm_blocks_kernel at the same place writes those regions, header and
 // blocks, where the plan put them; the packer leaves them alone.
+// A plan with pieces (OutputPlan::has_pieces): resample_pieces_kernel in the resampler's place, for every request of the plan, and
+// piece_carry_kernel behind it, every request's carry record at d_packed + plan.carry_off (8-aligned; d_packed is then
+// plan.end_bytes() long).  The gain, the packer and the marks run on the emitted range as they run on a whole request.
 void launch_output_plan(const float* audio, long audio_ld, const int* dur, const int* lens, const OutputPlan& plan,
                         const OutputTables& t, float* d_y, void* d_packed, hipStream_t s);
 // its two halves: the bodies, and the marks (n_marks > 0) into a block of their own, 8-byte aligned

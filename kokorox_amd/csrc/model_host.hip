@@ -134,6 +134,7 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     if (hc.loudness.call) check_spec_list(hc, hc.loudness);
     if (hc.limits.call) check_spec_list(hc, hc.limits);
     if (hc.prosody_call) check_prosody_call(hc, lens, B, t_stride, res.out_report, res.out_n_report);
+    check_piece_call(hc);  // (nothing to check unless the call came through the entry that takes pieces)
     check_fit_call(hc, lens, B, t_stride, fit_plan_);  // (the empty plan unless the call came through the entry that takes spans)
     const int n_spans = (int)fit_plan_.flat.size();
     KX_REQUIRE(n_spans == 0 || n_pinned_ == 0, "infer: fit with pinned durations");
@@ -143,6 +144,9 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
     const int R = layout.R;
     const bool joins = layout.joins != nullptr;
     const bool marks = layout.marks != nullptr;  // (with chunks_per_request then: check_marks_call)
+    // (a call whose flags are all PIECE_WHOLE has no piece: it is planned and launched as the call without them)
+    bool pieces = false;
+    for (int r = 0; layout.piece_flags && r < R; ++r) pieces = pieces || layout.piece_flags[r] != PIECE_WHOLE;
     // (a call with a limited request is metered and measured: the limiter's drive comes from the two gain kernels)
     bool limited = false;
     for (int i = 0; layout.limits && i < layout.n_limit; ++i) limited = limited || layout.limits[i].mode != LIMIT_NONE;
@@ -193,7 +197,11 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         tables.cum = static_cast<long*>(A.alloc(((size_t)B + 1) * 8));
         const OutputBounds bound = output_bounds(layout, B, audio_floats, lens);
         d_y = A.f(bound.y_floats);  // (0 floats when no word carries a rate code)
-        if (joins || levels) tables.join = static_cast<JoinRow*>(A.alloc((size_t)B * sizeof(JoinRow)));
+        if (joins || levels || pieces) tables.join = static_cast<JoinRow*>(A.alloc((size_t)B * sizeof(JoinRow)));
+        if (pieces) {  // (the table of the piece kernels and room for every request's carried tail)
+            tables.piece = static_cast<PieceRow*>(A.alloc((size_t)R * sizeof(PieceRow)));
+            tables.piece_tail = A.f((size_t)R * PIECE_TAIL);
+        }
         if (levels) {  // (the partials of the peak pass are sized here, before the forward: nothing new on a warm model)
             tables.level = static_cast<LevelSpec*>(A.alloc((size_t)R * sizeof(LevelSpec)));
             tables.peak = static_cast<uint32_t*>(A.alloc(bound.peak_dwords * sizeof(uint32_t)));
@@ -322,7 +330,8 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         // (the report was staged by the back half, 16-byte aligned; its block is 8-aligned: one more copy on the device, then the one to the host)
         if (plan.has_report())
             KX_HIP(hipMemcpyAsync(static_cast<char*>(d_packed) + plan.report_off, pd.report, (size_t)16 * plan.n_report, hipMemcpyDeviceToDevice, stream_));
-        const int64_t total = n_marks > 0 || plan.measured || plan.has_flac() || plan.has_report() ? plan.end_bytes() : plan.total_bytes;
+        const int64_t total =
+            n_marks > 0 || plan.measured || plan.has_flac() || plan.has_report() || plan.has_pieces() ? plan.end_bytes() : plan.total_bytes;
         char* host = static_cast<char*>(host_out_alloc((size_t)(total > 0 ? total : 1)));
         hipError_t e = hipMemcpyAsync(host, d_packed, (size_t)total, hipMemcpyDeviceToHost, stream_);
         if (e == hipSuccess) e = hipStreamSynchronize(stream_);
@@ -361,6 +370,10 @@ void Model::infer_host_once(const int64_t* ids, int64_t t_stride, const int32_t*
         *res.out = host;
         if (res.out_report) *res.out_report = plan.has_report() ? reinterpret_cast<float*>(host + plan.report_off) : nullptr;
         if (marks) *res.out_marks = n_marks > 0 ? reinterpret_cast<int64_t*>(host + marks_off) : nullptr;
+        if (hc.carry_out) {  // (a call without a piece: every request was run whole, and its record is all zeros)
+            if (plan.has_pieces()) memcpy(hc.carry_out, host + plan.carry_off, (size_t)R * sizeof(PieceCarry));
+            else memset(hc.carry_out, 0, (size_t)R * sizeof(PieceCarry));
+        }
         if (plan.measured && res.out_levels) memcpy(res.out_levels, host + plan.levels_off, (size_t)R * 16);
         if (plan.limited && res.out_limits)
             for (int r = 0; r < R; ++r)

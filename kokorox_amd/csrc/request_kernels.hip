@@ -739,6 +739,109 @@ __global__ __launch_bounds__(RS_THREADS) void resample_requests_joined_kernel(co
     resample_requests_body<true>(audio, audio_ld, reqs, cum, jrows, y);
 }
 
+// ---- pieces: a request resampled in several calls (include/kokorox_hip.h, "pieces"; host_request.h: PieceRow, PieceCarry) --------
+// The resampler of a plan with pieces, for every request of it.  A piece's source is tail_in ++ its joined rows: samples
+// [A' - n_tail_in, A') and [A', A) of the whole request's stream x, and it writes the outputs [E', E) of the whole request's y to
+// y + y_off.  Every index below is one of the whole request's, so the taps an output meets, their order (j ascending over the terms
+// that exist: no sample before x[0], none at or past A), the float64 accumulator from +0 and the one rounding are those of
+// resample_requests_body on the whole stream: the same bits.  A request run whole is the piece [0, N) of [0, S) without a tail.
+// The window is staged as there, the carried tail first and the rows behind it through the row lookup, plain or JOINED as the plan
+// says; PIECE_TAIL guarantees that no output of [E', E) reads before A' - n_tail_in, and an index that did would read +0, never
+// outside the tail buffer.
+template <bool JOINED>
+__device__ __forceinline__ void resample_pieces_body(const float* __restrict__ audio, long audio_ld,
+                                                                      const PackReq* __restrict__ reqs,
+                                                                      const PieceRow* __restrict__ pieces,
+                                                                      const long* __restrict__ cum,
+                                                                      const JoinRow* __restrict__ jrows,
+                                                                      const float* __restrict__ tails, float* __restrict__ y) {
+    __shared__ float xs[RS_LDS];
+    __shared__ double hs[RS_MAX_TAPS];
+    const PackReq rq = reqs[blockIdx.y];
+    if (rq.rate == 0) return;  // (uniform) a request at 24 kHz: the packer reads the model's slab
+    const PieceRow pr = pieces[blockIdx.y];
+    const long n0 = pr.emit_lo + (long)blockIdx.x * RS_WINDOW;
+    if (n0 >= pr.emit_hi) return;  // (uniform: the grid covers the request with most outputs in this call)
+    const long n1 = n0 + RS_WINDOW < pr.emit_hi ? n0 + RS_WINDOW : pr.emit_hi;
+    const int L = rq.rate == 1 ? 1 : 2, M = rq.rate == 3 ? 1 : 3, C = rq.rate == 3 ? 48 : 72, N = 2 * C + 1;
+    const long S = pr.src_end;  // the stream so far: a term at or past it does not exist (no final output has one)
+    const long a_lo = n0 * M - C;
+    const long j_lo = a_lo <= 0 ? 0 : (a_lo + L - 1) / L;
+    long j_hi = ((n1 - 1) * M + C) / L + 1;
+    j_hi = j_hi > S ? S : j_hi;
+    for (int t = threadIdx.x; t < N; t += RS_THREADS) hs[t] = (double)__uint_as_float(resample_tap_bits[rq.rate - 1][t]);
+    // the carried tail: x[base .. A'), then the piece's own rows: x[A' .. A)
+    const long base = pr.src_before - pr.n_tail_in;
+    const long t_hi = j_hi < pr.src_before ? j_hi : pr.src_before;
+    for (long j = j_lo + threadIdx.x; j < t_hi; j += RS_THREADS) xs[j - j_lo] = j >= base ? tails[pr.tail_in + (j - base)] : 0.0f;
+    const long r_lo = j_lo > pr.src_before ? j_lo : pr.src_before;
+    if (r_lo < j_hi)
+        stage_stream<JOINED, RS_THREADS>(xs + (r_lo - j_lo), audio, audio_ld, cum, jrows, rq.first_row, rq.n_rows, r_lo - pr.src_before,
+                                         j_hi - pr.src_before);
+    __syncthreads();
+    float* __restrict__ dst = y + rq.y_off;
+    for (long n = n0 + threadIdx.x; n < n1; n += RS_THREADS) {
+        const long a = n * M - C;
+        const long jl = a <= 0 ? 0 : (a + L - 1) / L;  // >= j_lo, as n >= n0
+        long jh = (n * M + C) / L;                      // < j_hi, as n < n1
+        jh = jh > S - 1 ? S - 1 : jh;
+        int idx = (int)(n * M - jl * L) + C;
+        const float* xp = xs + (jl - j_lo);
+        double acc = 0.0;
+        for (long j = jl; j <= jh; ++j, idx -= L) acc += hs[idx] * (double)*xp++;
+        dst[n - pr.emit_lo] = (float)acc;
+    }
+}
+__global__ __launch_bounds__(RS_THREADS) void resample_pieces_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                      const PackReq* __restrict__ reqs,
+                                                                      const PieceRow* __restrict__ pieces,
+                                                                      const long* __restrict__ cum, const float* __restrict__ tails,
+                                                                      float* __restrict__ y) {
+    resample_pieces_body<false>(audio, audio_ld, reqs, pieces, cum, nullptr, tails, y);
+}
+__global__ __launch_bounds__(RS_THREADS) void resample_pieces_joined_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                             const PackReq* __restrict__ reqs,
+                                                                             const PieceRow* __restrict__ pieces,
+                                                                             const long* __restrict__ cum,
+                                                                             const JoinRow* __restrict__ jrows,
+                                                                             const float* __restrict__ tails, float* __restrict__ y) {
+    resample_pieces_body<true>(audio, audio_ld, reqs, pieces, cum, jrows, tails, y);
+}
+// The carry a piece leaves, one workgroup of PIECE_TAIL lanes per request: lane t stores sample t of the new tail, the last
+// n_tail_out samples of tail_in ++ joined rows -- the last of the piece's own kept samples, staged through the joined row lookup, and
+// in front of them, where the piece kept fewer than n_tail_out, the last of the old tail -- and +0 behind them; lane 0 the record's
+// head.  A request run whole gets the all-zero record.
+__global__ __launch_bounds__(PIECE_TAIL) void piece_carry_kernel(const float* __restrict__ audio, long audio_ld,
+                                                                  const PackReq* __restrict__ reqs,
+                                                                  const PieceRow* __restrict__ pieces, const long* __restrict__ cum,
+                                                                  const JoinRow* __restrict__ jrows,
+                                                                  const float* __restrict__ tails, char* __restrict__ out) {
+    __shared__ float xs[PIECE_TAIL];
+    const PackReq rq = reqs[blockIdx.x];
+    const PieceRow pr = pieces[blockIdx.x];
+    PieceCarry* __restrict__ c = reinterpret_cast<PieceCarry*>(out + pr.carry_off);
+    const bool piece = pr.flags != PIECE_WHOLE;
+    const int t = threadIdx.x;
+    const long own = pr.src_end - pr.src_before;                       // the piece's joined samples
+    const int n_out = piece ? pr.n_tail_out : 0;
+    const int from_rows = own < (long)n_out ? (int)own : n_out;        // (uniform)
+    const int from_tail = n_out - from_rows;                           // <= n_tail_in: A' >= n_out - own
+    if (from_rows > 0) stage_stream<true, PIECE_TAIL>(xs, audio, audio_ld, cum, jrows, rq.first_row, rq.n_rows, own - from_rows, own);
+    __syncthreads();
+    float v = 0.0f;
+    if (t < from_tail) v = pr.n_tail_in - from_tail + t >= 0 ? tails[pr.tail_in + pr.n_tail_in - from_tail + t] : 0.0f;
+    else if (t < n_out) v = xs[t - from_tail];
+    c->tail[t] = v;
+    if (t == 0) {
+        c->magic = piece ? PIECE_MAGIC : 0u;
+        c->format_word = piece ? pr.word : 0u;
+        c->src_samples = piece ? pr.src_end : 0;
+        c->out_samples = piece ? pr.emit_hi : 0;
+        c->n_tail = n_out;
+        c->reserved = piece ? pr.chunks_end : 0;
+    }
+}
+
 // ---- limiter: a look-ahead gain that keeps every sample at or below the request's peak (include/kokorox_hip.h, "limiter") ------
 // The stream z is the one the peak pass reads and g its drive from the levels block (the gain kernels ran before: a limited request's
 // derived spec carries the drive cap).  z1[n] = f32(g f64(z[n])); a[n] = |z1[n]|, with PEAK_TRUE the largest of it and the three
@@ -1583,7 +1686,7 @@ __global__ __launch_bounds__(ADPCM_THREADS) void adpcm_blocks_kernel(const float
 // A plan with an ADPCM request (OutputPlan::adpcm_groups > 0): adpcm_blocks_kernel at the same place, which needs no table of its own.
 void launch_pack_plan(const float* audio, long audio_ld, const OutputPlan& plan, const OutputTables& t, float* d_y, void* out,
                       hipStream_t s) {
-    if (plan.max_units <= 0 && !plan.measured && !plan.has_flac() && plan.adpcm_groups <= 0) return;
+    if (plan.max_units <= 0 && !plan.measured && !plan.has_flac() && plan.adpcm_groups <= 0 && !plan.has_pieces()) return;
     const size_t R = plan.req.size(), B = plan.join.size();
     KX_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0 && R <= 65535, "pack: unaligned output or too many requests");
     // (a plan with FLAC: the packer's table has those requests emptied; every other kernel reads the fields the two tables share)
@@ -1596,7 +1699,16 @@ void launch_pack_plan(const float* audio, long audio_ld, const OutputPlan& plan,
         KX_HIP(hipMemcpyAsync(t.frow, plan.flac.data(), R * sizeof(FlacRow), hipMemcpyHostToDevice, s));
     }
     KX_HIP(hipMemcpyAsync(t.cum, plan.cum.data(), (B + 1) * sizeof(long), hipMemcpyHostToDevice, s));
-    if (plan.joined || plan.levelled) KX_HIP(hipMemcpyAsync(t.join, plan.join.data(), B * sizeof(JoinRow), hipMemcpyHostToDevice, s));
+    if (plan.joined || plan.levelled || plan.has_pieces())
+        KX_HIP(hipMemcpyAsync(t.join, plan.join.data(), B * sizeof(JoinRow), hipMemcpyHostToDevice, s));
+    if (plan.has_pieces()) {  // (the table of the two piece kernels and the carried tails; both always stage through the join table)
+        KX_REQUIRE(t.piece && t.join && (t.piece_tail || plan.tail_in.empty()) && plan.piece.size() == R && (plan.carry_off & 7) == 0 &&
+                       plan.carry_off >= plan.report_end() && plan.tail_in.size() <= R * (size_t)PIECE_TAIL,
+                   "pieces: bad launch argument");
+        KX_HIP(hipMemcpyAsync(t.piece, plan.piece.data(), R * sizeof(PieceRow), hipMemcpyHostToDevice, s));
+        if (!plan.tail_in.empty())
+            KX_HIP(hipMemcpyAsync(t.piece_tail, plan.tail_in.data(), plan.tail_in.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    }
     if (plan.measured) {
         KX_REQUIRE(t.level && t.peak && plan.level.size() == R && (plan.levels_off & 7) == 0, "levels: bad launch argument");
         KX_HIP(hipMemcpyAsync(t.level, plan.level.data(), R * sizeof(LevelSpec), hipMemcpyHostToDevice, s));
@@ -1617,10 +1729,22 @@ void launch_pack_plan(const float* audio, long audio_ld, const OutputPlan& plan,
     if (plan.y_floats > 0) {
         KX_REQUIRE(d_y != nullptr, "pack: no buffer for the resampled streams");
         const dim3 grid((unsigned)((plan.max_resampled + RS_WINDOW - 1) / RS_WINDOW), (unsigned)R);
-        if (plan.joined)
+        if (plan.has_pieces() && plan.joined)  // (every request of the plan, the ones run whole included: the same bits)
+            hipLaunchKernelGGL(resample_pieces_joined_kernel, grid, dim3(RS_THREADS), 0, s, audio, audio_ld, t.req, t.piece, t.cum, t.join,
+                               t.piece_tail, d_y);
+        else if (plan.has_pieces())
+            hipLaunchKernelGGL(resample_pieces_kernel, grid, dim3(RS_THREADS), 0, s, audio, audio_ld, t.req, t.piece, t.cum, t.piece_tail,
+                               d_y);
+        else if (plan.joined)
             hipLaunchKernelGGL(resample_requests_joined_kernel, grid, dim3(RS_THREADS), 0, s, audio, audio_ld, t.req, t.cum, t.join, d_y);
         else
             hipLaunchKernelGGL(resample_requests_kernel, grid, dim3(RS_THREADS), 0, s, audio, audio_ld, t.req, t.cum, d_y);
+        KX_HIP(hipGetLastError());
+    }
+    // the carries of a plan with pieces, into their block behind everything else: they depend on the rows and the old tails alone
+    if (plan.has_pieces()) {
+        hipLaunchKernelGGL(piece_carry_kernel, dim3((unsigned)R), dim3(PIECE_TAIL), 0, s, audio, audio_ld, t.req, t.piece, t.cum, t.join,
+                           t.piece_tail, static_cast<char*>(out));
         KX_HIP(hipGetLastError());
     }
     double* levels = plan.measured ? reinterpret_cast<double*>(static_cast<char*>(out) + plan.levels_off) : nullptr;

@@ -49,14 +49,20 @@ int kx_test_output_plan_limited(int device_id, const float* audio, int B, int64_
                                     out_loudness, out_hops, hops_cap, out_n_hops, limits, out_limits, nullptr, err, err_len);
 }
 
-int kx_test_output_plan_flac(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames_in, const int32_t* dur,
-                             const int32_t* lens, const int32_t* chunks_per_request, int R, const int32_t* formats, const kx_join* joins,
-                             const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes, int64_t* out_samples,
-                             int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks, const kx_level* levels, double* out_levels,
-                             const kx_loudness* loudness, double* out_loudness, double* out_hops, int64_t hops_cap, int64_t* out_n_hops,
-                             const kx_limit* limits, double* out_limits, int64_t* out_lengths, char* err, size_t err_len) {
+}  // extern "C"
+
+// The one body of the hooks above and of kx_test_output_plan_pieces: the FLAC hook's arguments, and a call's pieces (all three null:
+// every request is run whole).
+static int output_plan_hook(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames_in, const int32_t* dur,
+                            const int32_t* lens, const int32_t* chunks_per_request, int R, const int32_t* formats, const kx_join* joins,
+                            const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes, int64_t* out_samples,
+                            int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks, const kx_level* levels, double* out_levels,
+                            const kx_loudness* loudness, double* out_loudness, double* out_hops, int64_t hops_cap, int64_t* out_n_hops,
+                            const kx_limit* limits, double* out_limits, int64_t* out_lengths, const uint32_t* piece_flags,
+                            const kx_piece_carry* carry_in, kx_piece_carry* carry_out, char* err, size_t err_len) {
     return guarded_free(err, err_len, [&] {
         check_device(device_id);
+        KX_REQUIRE((piece_flags ? audio && carry_out : !carry_in && !carry_out), "test_output_plan: bad argument");
         KX_REQUIRE(formats && out_bytes && out_samples && out_n_marks && B > 0 && R > 0 && (frames_in ? !dur : dur && lens) &&
                        ((!want && !joins) || dur) && (audio ? out != nullptr : out_cap == 0 && dur) && (levels ? audio && out_levels : !out_levels) &&
                        (loudness ? audio && out_loudness && out_hops && out_n_hops && hops_cap >= 0 : !out_loudness && !out_hops && !out_n_hops) &&
@@ -95,8 +101,11 @@ int kx_test_output_plan_flac(int device_id, const float* audio, int B, int64_t a
         for (int r = 0; limits && r < R; ++r)
             KX_REQUIRE(mspecs[r].mode == kx::LIMIT_NONE || kx::limit_spec_ok(mspecs[r]), "infer: bad limit");
         // the planner and the launcher of Model::infer_host_once
-        const kx::RequestLayout layout{chunks_per_request, R, formats, R, want, specs, R, lspecs, levels ? R : 0, dspecs, loudness ? R : 0,
-                                       mspecs, limits ? R : 0};
+        kx::RequestLayout layout{chunks_per_request, R, formats, R, want, specs, R, lspecs, levels ? R : 0, dspecs, loudness ? R : 0,
+                                 mspecs, limits ? R : 0};
+        static_assert(sizeof(kx_piece_carry) == sizeof(kx::PieceCarry), "kx_piece_carry is PieceCarry");
+        layout.piece_flags = piece_flags;
+        layout.carry_in = reinterpret_cast<const kx::PieceCarry*>(carry_in);
         kx::OutputPlan plan;
         kx::build_output_plan(frames.data(), lens, joins ? edges.data() : nullptr, B, layout, plan);
         for (int r = 0; r < R; ++r) {
@@ -135,13 +144,17 @@ int kx_test_output_plan_flac(int device_id, const float* audio, int B, int64_t a
         uint32_t* d_fslot = flac ? guarded_bytes<uint32_t>(dm, n_slot * (size_t)(kx::FLAC_SLOT / 4), 0xFF) : nullptr;
         int* d_flen = flac ? guarded_bytes<int>(dm, n_slot, 0x80) : nullptr;
         long* d_foff = flac ? guarded_bytes<long>(dm, n_slot, 0x7F) : nullptr;
+        // the carried tails of a plan with pieces: a guard behind them (the kernels only read them)
+        const bool pieces = plan.has_pieces();
+        const size_t n_tail = plan.tail_in.size();
+        float* d_tail = pieces ? guarded_bytes<float>(dm, n_tail, 0xFF) : nullptr;
         const kx::OutputTables tables{dm.get<kx::PackReq>((size_t)R), dm.get<long>((size_t)B + 1), dm.get<kx::JoinRow>((size_t)B),
                                       dm.get<kx::MarkRow>((size_t)B), plan.measured ? dm.get<kx::LevelSpec>((size_t)R) : nullptr, d_peak,
                                       metered ? dm.get<kx::LoudSpec>((size_t)R) : nullptr, d_hops,
                                       metered ? dm.get<double>((size_t)4 * kx::LOUD_POWERS * 16) : nullptr, d_tpeak,
                                       plan.limited ? dm.get<kx::LimitRow>((size_t)R) : nullptr, d_lpart, d_lim,
                                       flac ? dm.get<kx::FlacRow>((size_t)R) : nullptr, flac ? dm.get<kx::FlacInfo>((size_t)R) : nullptr,
-                                      d_fslot, d_flen, d_foff};
+                                      d_fslot, d_flen, d_foff, pieces ? dm.get<kx::PieceRow>((size_t)R) : nullptr, d_tail};
         const int* d_dur = dur ? dm.up(dur, (size_t)B * 512) : nullptr;
         const int* d_len = dur ? dm.up(lens, (size_t)B) : nullptr;
         // guards: 64 bytes after the last region, after the resampled streams, after the last mark and after the levels, which
@@ -159,7 +172,13 @@ int kx_test_output_plan_flac(int device_id, const float* audio, int B, int64_t a
         // (the lengths block of a plan with FLAC: behind the guard of the last block, a guard of its own behind it)
         const long blocks_end = plan.measured ? lv_off + n_lv : mk_off + n_mk;
         if (flac) plan.flac_off = (blocks_end + GUARD_BYTES + 7) & ~7L;
-        const long d_out_bytes = flac ? plan.flac_off + 8L * R + GUARD_BYTES : blocks_end + GUARD_BYTES;
+        // (the carry block of a plan with pieces: behind the guard of the last block, a guard of its own behind it)
+        const long carries = (long)sizeof(kx::PieceCarry) * R, before_carry = flac ? plan.flac_off + 8L * R : blocks_end;
+        if (pieces) {
+            plan.carry_off = (before_carry + GUARD_BYTES + 7) & ~7L;
+            for (int r = 0; r < R; ++r) plan.piece[(size_t)r].carry_off = plan.carry_off + (long)sizeof(kx::PieceCarry) * r;
+        }
+        const long d_out_bytes = (pieces ? plan.carry_off + carries : before_carry) + GUARD_BYTES;
         char* d_out = dm.get<char>((size_t)d_out_bytes);
         KX_HIP(hipMemset(d_out, GUARD_BYTE, (size_t)d_out_bytes));
         float* d_y = audio && plan.y_floats > 0 ? dm.get<float>((size_t)plan.y_floats + GUARD_BYTES / 4) : nullptr;
@@ -195,6 +214,12 @@ int kx_test_output_plan_flac(int device_id, const float* audio, int B, int64_t a
             }
             if (d_y) guard_untouched(d_y + plan.y_floats, "test_output_plan: the resampler wrote past the last stream");
         }
+        if (pieces) {
+            KX_HIP(hipMemcpy(carry_out, d_out + plan.carry_off, (size_t)carries, hipMemcpyDeviceToHost));
+            guard_untouched(d_out + plan.carry_off - GUARD_BYTES, "test_output_plan: a kernel wrote in front of the carries");
+            guard_untouched(d_out + plan.carry_off + carries, "test_output_plan: the kernel wrote past the last carry");
+            guard_untouched(d_tail + n_tail, "test_output_plan: a kernel wrote past the carried tails");
+        }
         if (plan.measured) {
             std::vector<double> lv((size_t)n_lv / 8);
             KX_HIP(hipMemcpy(lv.data(), d_out + lv_off, (size_t)n_lv, hipMemcpyDeviceToHost));
@@ -226,6 +251,39 @@ int kx_test_output_plan_flac(int device_id, const float* audio, int B, int64_t a
         KX_HIP(hipMemcpy(out_marks, d_out + mk_off, (size_t)n_mk, hipMemcpyDeviceToHost));
         guard_untouched(d_out + mk_off + n_mk, "test_output_plan: the kernel wrote past the last mark");
     });
+}
+
+extern "C" {
+
+int kx_test_output_plan_flac(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames_in, const int32_t* dur,
+                             const int32_t* lens, const int32_t* chunks_per_request, int R, const int32_t* formats, const kx_join* joins,
+                             const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes, int64_t* out_samples,
+                             int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks, const kx_level* levels, double* out_levels,
+                             const kx_loudness* loudness, double* out_loudness, double* out_hops, int64_t hops_cap, int64_t* out_n_hops,
+                             const kx_limit* limits, double* out_limits, int64_t* out_lengths, char* err, size_t err_len) {
+    return output_plan_hook(device_id, audio, B, audio_ld, frames_in, dur, lens, chunks_per_request, R, formats, joins, want, out, out_cap,
+                            out_bytes, out_samples, out_marks, marks_cap, out_n_marks, levels, out_levels, loudness, out_loudness, out_hops,
+                            hops_cap, out_n_hops, limits, out_limits, out_lengths, nullptr, nullptr, nullptr, err, err_len);
+}
+
+int kx_test_output_plan_pieces(int device_id, const float* audio, int B, int64_t audio_ld, const int32_t* frames_in, const int32_t* dur,
+                               const int32_t* lens, const int32_t* chunks_per_request, int R, const int32_t* formats, const kx_join* joins,
+                               const uint8_t* want, void* out, int64_t out_cap, int64_t* out_bytes, int64_t* out_samples,
+                               int64_t* out_marks, int64_t marks_cap, int64_t* out_n_marks, const kx_level* levels, double* out_levels,
+                               const kx_loudness* loudness, double* out_loudness, const uint32_t* piece_flags,
+                               const kx_piece_carry* carry_in, kx_piece_carry* carry_out, char* err, size_t err_len) {
+    // (the hop energies of a metered request beside the pieces are not handed out: room for a hop per frame, which is 25 ms)
+    long total = 1 + 51L * (B > 0 ? B : 0);  // (and the longest pause behind every row)
+    for (int b = 0; b < B && (frames_in || (dur && lens)); ++b) {
+        if (frames_in) total += frames_in[b] > 0 ? frames_in[b] : 0;
+        else for (int t = 0; t < lens[b] && t < 512; ++t) total += dur[(size_t)b * 512 + t] > 0 ? dur[(size_t)b * 512 + t] : 0;
+    }
+    std::vector<double> hops(loudness && R > 0 ? (size_t)R * (size_t)total : 0);
+    std::vector<int64_t> n_hops(loudness && R > 0 ? (size_t)R : 0);
+    return output_plan_hook(device_id, audio, B, audio_ld, frames_in, dur, lens, chunks_per_request, R, formats, joins, want, out, out_cap,
+                            out_bytes, out_samples, out_marks, marks_cap, out_n_marks, levels, out_levels, loudness, out_loudness,
+                            loudness ? hops.data() : nullptr, loudness ? total : 0, loudness ? n_hops.data() : nullptr, nullptr, nullptr,
+                            nullptr, piece_flags, carry_in, carry_out, err, err_len);
 }
 
 }  // extern "C"

@@ -41,6 +41,12 @@ LEVEL_GAIN, LEVEL_NORMALIZE, LEVEL_CEILING = 0, 1, 2
 LEVEL_DTYPE = np.dtype([("mode", "<u4"), ("gain", "<f4"), ("peak", "<f4")])
 LEVEL_PLAIN = (LEVEL_GAIN, 1.0, 0.0)
 PEAK_TRUE = 0x100  # OR-ed into a level or a loudness mode: p is the true peak tp (KX_PEAK_TRUE)
+# pieces (include/kokorox_hip.h, "pieces"): the flag bits of a piece, and the layout of kx_piece_carry
+PIECE_FIRST, PIECE_LAST, PIECE_WHOLE = 1, 2, 3
+PIECE_TAIL = 256
+PIECE_MAGIC = 0x4350584B
+PIECE_CARRY_DTYPE = np.dtype([("magic", "<u4"), ("format_word", "<u4"), ("src_samples", "<i8"), ("out_samples", "<i8"), ("n_tail", "<i4"),
+                              ("reserved", "<i4"), ("tail", "<f4", (PIECE_TAIL,))])
 # loudness (include/kokorox_hip.h, "loudness"): a spec is (mode, target_lufs, peak), the layout of kx_loudness
 LOUDNESS_MEASURE, LOUDNESS_NORMALIZE = 0, 1
 LOUDNESS_DTYPE = np.dtype([("mode", "<u4"), ("target_lufs", "<f4"), ("peak", "<f4")])
@@ -153,6 +159,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                              vp, vp, vp, i32, vp, i32, vp]),
         "kx_dispatcher_submit_request_levelled": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
                                                         C.POINTER(i64), vp, vp, vp, vp, vp, cp, sz]),
+        "kx_infer_requests_pieces": (i32, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, u64, u32, vp, i32, C.POINTER(vp), vp, vp,
+                                           vp, vp, vp, i32, vp, i32, vp, vp, vp, vp]),
+        "kx_dispatcher_submit_request_piece": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, f32, u64, i32, C.POINTER(vp), C.POINTER(i64),
+                                                     C.POINTER(i64), vp, vp, vp, vp, vp, u32, vp, vp, cp, sz]),
         "kx_loudness_filter": (i32, [i32, vp]),
         "kx_truepeak_filter": (i32, [vp, i32]),
         "kx_adpcm_block": (i32, [i32, vp, vp]),
@@ -221,6 +231,8 @@ def _test_signatures():
                                               vp, vp, vp, i64, vp, vp, vp, cp, sz]),
         "kx_test_output_plan_flac": (i32, [i32, vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp,
                                            vp, vp, vp, i64, vp, vp, vp, vp, cp, sz]),
+        "kx_test_output_plan_pieces": (i32, [i32, vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp,
+                                             vp, vp, vp, vp, vp, cp, sz]),
         "kx_test_lstm_ragged": (i32, [i32, vp, vp, i32, i32, i32] + [vp] * 8 + [i32, i32, u32, vp, cp, sz]),
         "kx_test_alignment": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, cp, sz]),
         "kx_test_prosody_durations": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, cp, sz]),
@@ -265,7 +277,7 @@ ABI_SYMBOLS = [
     "kx_free_audio", "kx_infer_device", "kx_sync", "kx_set_pinned_durations", "kx_warmup", "kx_arena_bytes", "kx_call_times", "kx_model_status", "kx_model_info", "kx_dispatcher_health", "kx_set_utterance_base", "kx_set_lanes",
     "kx_set_conv_mode", "kx_get_conv_mode", "kx_set_stft_variant", "kx_get_stft_variant",
     "kx_profile_enable", "kx_profile_read", "kx_profile_detail", "kx_profile_aux", "kx_diag_enable", "kx_diag_count", "kx_diag_get", "kx_set_act_prescale", "kx_set_voice_table", "kx_infer_voices",
-    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_infer_requests_levelled", "kx_dispatcher_submit_request_levelled", "kx_loudness_filter", "kx_truepeak_filter", "kx_adpcm_block", "kx_infer_requests_loudness", "kx_dispatcher_submit_request_loudness", "kx_limit_filter", "kx_infer_requests_limited", "kx_dispatcher_submit_request_limited", "kx_infer_prosody", "kx_infer_requests_prosody", "kx_dispatcher_submit_request_prosody", "kx_infer_requests_fitted", "kx_dispatcher_submit_request_fitted", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
+    "kx_infer_packed", "kx_free_packed", "kx_infer_requests", "kx_dispatcher_submit_request", "kx_infer_requests_marks", "kx_dispatcher_submit_request_marks", "kx_infer_requests_joined", "kx_dispatcher_submit_request_joined", "kx_infer_requests_levelled", "kx_dispatcher_submit_request_levelled", "kx_infer_requests_pieces", "kx_dispatcher_submit_request_piece", "kx_loudness_filter", "kx_truepeak_filter", "kx_adpcm_block", "kx_infer_requests_loudness", "kx_dispatcher_submit_request_loudness", "kx_limit_filter", "kx_infer_requests_limited", "kx_dispatcher_submit_request_limited", "kx_infer_prosody", "kx_infer_requests_prosody", "kx_dispatcher_submit_request_prosody", "kx_infer_requests_fitted", "kx_dispatcher_submit_request_fitted", "kx_dispatcher_create", "kx_dispatcher_create_warm", "kx_dispatcher_submit", "kx_dispatcher_submit_ex", "kx_dispatcher_model_batches",
     "kx_dispatcher_stats", "kx_dispatcher_failures", "kx_dispatcher_destroy", "kx_debug_tap",
 ]
 
@@ -437,6 +449,21 @@ def adpcm_block(word: int = 0):
     if rc != KX_OK:
         raise KokoroxHipError(rc, "kx_adpcm_block: unknown output sample rate")
     return int(a[0]), int(p[0])
+
+
+def piece_carries(carries, n) -> np.ndarray:
+    """n carries as the array of kx_piece_carry the library takes: None (all zeros: what first pieces are given), one record, a list
+    of records (None = zeros), or an array of PIECE_CARRY_DTYPE already."""
+    if isinstance(carries, np.ndarray) and carries.dtype == PIECE_CARRY_DTYPE:
+        a = np.ascontiguousarray(carries).reshape(-1)
+    else:
+        a = np.zeros(n, PIECE_CARRY_DTYPE)
+        for i, c in enumerate([] if carries is None else carries):
+            if c is not None:
+                a[i] = np.asarray(c, dtype=PIECE_CARRY_DTYPE).reshape(())
+    if a.shape[0] != n:
+        raise ValueError(f"{n} piece carries are required")
+    return a
 
 
 def _decode_packed(raw: bytes, fmt: int):
@@ -757,8 +784,36 @@ class HipKoko:
         out = (res, mk, out_lm) if marks else (res, out_lm)
         return out + (nsamp,) if with_samples else out
 
+    def infer_requests_pieces(self, tokens, chunks_per_request, piece_flags, carries=None, levels=None, joins=None, styles=None,
+                              voice_ids=None, weights=None, speeds=(1.0,), seed: int = 0, flags: int = 0, fmt=0, marks: bool = False,
+                              with_samples: bool = False):
+        """Pieces of requests in one forward (kx_infer_requests_pieces; the definition is in include/kokorox_hip.h, "pieces", the
+        numpy form voices.piece_bodies / voices.piece_carry): request r of the call is a piece with the flag word piece_flags[r]
+        (PIECE_FIRST, PIECE_LAST, both = a request run whole) and the carry carries[r] that the piece before it left (None, or
+        anything for a first piece).  `levels` (mode LEVEL_GAIN for a piece) and `joins` as infer_requests_levelled, or None.
+        Returns (payloads, carries): every payload as bytes -- the payloads of a request's pieces, end to end, are the body of the
+        request run whole -- and the carries as an array of PIECE_CARRY_DTYPE, one per request, to hand to the next pieces;
+        marks=True: (payloads, marks, carries), the marks positions in the whole request's stream.  With levels the result ends
+        with the float64 [R, 2] array of p and g; with_samples: out_samples as a last entry.  Row b of the call draws the noise of
+        utterance (utterance base + b): a later piece must run at the utterance base of its first row in the whole request
+        (set_utterance_base; RequestStream does it)."""
+        cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32).reshape(-1)
+        R = cpr.shape[0]
+        pf = np.ascontiguousarray(piece_flags, dtype=np.uint32).reshape(-1)
+        if pf.shape[0] != R:
+            raise ValueError(f"{R} piece flag words are required")
+        cin = piece_carries(carries, R)
+        cout = np.zeros(R, PIECE_CARRY_DTYPE)
+        lv = None if levels is None else level_specs(levels)
+        j = None if joins is None else join_specs(joins)
+        res, mk, nsamp, out_lv = self._infer_requests(tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, marks,
+                                                      j, lv, pieces=(pf, cin, cout))
+        out = (res, mk, cout) if marks else (res, cout)
+        out = out + (out_lv,) if lv is not None else out
+        return out + (nsamp,) if with_samples else out
+
     def _infer_requests(self, tokens, chunks_per_request, styles, voice_ids, weights, speeds, seed, flags, fmt, want_marks, joins=None,
-                        levels=None, loudness=None, limits=None, prosody=None):
+                        levels=None, loudness=None, limits=None, prosody=None, pieces=None):
         """The call behind every infer_requests*: returns (bodies, marks, out_samples, extra) with marks None unless wanted and extra
         the [R, k] values of the level, loudness or limit list, the reports of a call with prosody that wants them, else None."""
         ids, lens = self._ids_lens(tokens)
@@ -786,7 +841,13 @@ class HipKoko:
         spec = next(((s, fn, k) for s, fn, k in ((limits, self._lib.kx_infer_requests_limited, 5), (loudness, self._lib.kx_infer_requests_loudness, 4),
                                                   (levels, self._lib.kx_infer_requests_levelled, 2)) if s is not None), None)
         marks = extra = keep = None
-        if prosody is not None:  # (prosody, want the report) or, through the fitted entry, (..., the fit spans, their results)
+        if pieces is not None:  # (the flag words, the carries before, the carries behind): the levelled entry's list, which may be null
+            if levels is not None:
+                extra = np.zeros((max(R, 1), 2), np.float64)
+            rc = self._lib.kx_infer_requests_pieces(*args, *tail, _ptr(levels), 0 if levels is None else levels.shape[0], _ptr(extra),
+                                                    _ptr(pieces[0]), _ptr(pieces[1]), _ptr(pieces[2]))
+            extra = None if extra is None else extra[:R]
+        elif prosody is not None:  # (prosody, want the report) or, through the fitted entry, (..., the fit spans, their results)
             ps, keep = prosody_arrays(prosody[0], lens, ids.shape[1])
             rp, n_rp = C.c_void_p(), np.zeros(max(R, 1), np.int64)
             ptail = (None if ps is None else C.addressof(ps), C.byref(rp) if prosody[1] else None, _ptr(n_rp) if prosody[1] else None)
@@ -828,7 +889,7 @@ class HipKoko:
         for r in range(R):
             part = raw[o: o + int(nbytes[r])]
             o += int(nbytes[r])
-            res.append(_decode_packed(part, int(fm[r if fm.shape[0] > 1 else 0])))
+            res.append(part if pieces is not None else _decode_packed(part, int(fm[r if fm.shape[0] > 1 else 0])))
         return res, marks, [int(v) for v in nsamp[:R]], extra
 
     def infer_device(self, d_ids: int, t_stride: int, lens_host: np.ndarray, d_styles: int, speeds_host: np.ndarray,
@@ -1044,7 +1105,7 @@ class Dispatcher:
 
     def submit_request(self, chunks: Sequence[Sequence[int]], styles=None, voices=None, speed: float = 1.0, seed: int = 0,
                        fmt: int = 0, marks: bool = False, join=None, level=None, loudness=None, limit=None, prosody=None,
-                       report: bool = False, fit=None):
+                       report: bool = False, fit=None, piece=None):
         """A request of 1 .. max_batch chunks (kx_dispatcher_submit_request): `chunks` = the 0-wrapped id lists; `styles` = one
         256-float row per chunk, OR `voices` as in submit_ex (one voice spec for the request); `fmt` = a format word (a PACK_*
         form, optionally | PACK_RATE_*).  Returns what HipKoko.infer_requests returns for one request: an array (forms 0..2, 8, 9)
@@ -1062,7 +1123,11 @@ class Dispatcher:
         request's float32 report [tokens, 4].  Not together with level, loudness or limit.
         fit = [(begin, end, frames), ...] (kx_dispatcher_submit_request_fitted): spans of the request's tokens, chunks laid end to end,
         fitted as HipKoko.infer_requests_fitted fits them; the result then ends with the FIT_RESULT_DTYPE records of the spans.  It goes
-        with prosody and report, not with level, loudness or limit."""
+        with prosody and report, not with level, loudness or limit.
+        piece = (flags, carry) (kx_dispatcher_submit_request_piece; include/kokorox_hip.h, "pieces"): `chunks` are a piece of a request,
+        flags = PIECE_FIRST and / or PIECE_LAST, carry = the record the piece before left (None for a first piece).  The body comes
+        back as bytes -- the payloads of a request's pieces, end to end, are the body of the request run whole -- and the result ends
+        with the carry for the next piece, a PIECE_CARRY_DTYPE record.  It goes with marks, join and a level of mode LEVEL_GAIN."""
         lens = np.array([len(c) for c in chunks], dtype=np.int32)
         a = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.int64).reshape(-1) for c in chunks])
                                  if len(chunks) else np.zeros(0, np.int64))
@@ -1099,6 +1164,9 @@ class Dispatcher:
                      ((limit, limit_specs, self._lib.kx_dispatcher_submit_request_limited, 5),
                       (loudness, loudness_specs, self._lib.kx_dispatcher_submit_request_loudness, 4),
                       (level, level_specs, self._lib.kx_dispatcher_submit_request_levelled, 2)) if s is not None), None)
+        if piece is not None and (loudness is not None or limit is not None or prosody is not None or report or fit is not None):
+            raise ValueError("submit_request: a piece goes with marks, a join and a level only")
+        carry_out = None
         keep = None
         fit_sp = fit_res = None
         if fit is not None:
@@ -1113,6 +1181,12 @@ class Dispatcher:
                                                                    _ptr(fit_res), err, len(err))
             else:
                 rc = self._lib.kx_dispatcher_submit_request_prosody(*args, *tail, *ptail, err, len(err))
+        elif piece is not None:
+            carry_in = None if piece[1] is None else piece_carries([piece[1]], 1)
+            carry_out = np.zeros(1, PIECE_CARRY_DTYPE)
+            rc = self._lib.kx_dispatcher_submit_request_piece(*args, *tail, None if spec is None else _ptr(spec[0]),
+                                                              None if spec is None else _ptr(spec[2]), int(piece[0]), _ptr(carry_in),
+                                                              _ptr(carry_out), err, len(err))
         elif spec is not None:
             rc = spec[1](*args, *tail, _ptr(spec[0]), _ptr(spec[2]), err, len(err))
         elif join is not None:
@@ -1136,8 +1210,10 @@ class Dispatcher:
                 rep_out = np.frombuffer(C.string_at(rp, 16 * n_rp.value) if n_rp.value else b"", dtype=np.float32).reshape(-1, 4).copy()
         finally:
             self._lib.kx_free_packed(out)
-        res = (_decode_packed(raw, fmt), m) if marks else (_decode_packed(raw, fmt),)
+        body = raw if piece is not None else _decode_packed(raw, fmt)
+        res = (body, m) if marks else (body,)
         res = res + (spec[2],) if spec is not None else res
+        res = res + (carry_out[0].copy(),) if piece is not None else res
         res = res + (rep_out,) if report else res
         res = res + (fit_res[: len(fit_sp)],) if fit is not None else res
         return res if len(res) > 1 else res[0]
@@ -1166,6 +1242,48 @@ class Dispatcher:
             self.close()
         except Exception:
             pass
+
+
+class RequestStream:
+    """One request sent in pieces (include/kokorox_hip.h, "pieces"): holds the carry between `send` calls, so that the payloads
+    that come back, end to end, are the body of the request run whole -- the header of the form first, every byte.  `backend` is a
+    HipKoko or a Dispatcher; fmt, join, level, speed and seed are the request's and stay the same for every piece.  With a HipKoko
+    the rows of a later piece run at the utterance base of their place in the whole request (`utterance_base` + the chunks so far),
+    and the model's utterance base is put back to `utterance_base` after every call."""
+
+    def __init__(self, backend, fmt: int = PACK_WAV_F32, join=None, level=None, speed: float = 1.0, seed: int = 0, marks: bool = False,
+                 utterance_base: int = 0):
+        self._be, self._fmt, self._join, self._level, self._speed, self._seed, self._marks = backend, fmt, join, level, speed, seed, marks
+        self._base = utterance_base
+        self._carry = None
+        self._chunks = 0
+        self.closed = False
+
+    def send(self, chunks, styles, last: bool = False):
+        """The next chunks of the request (0-wrapped id lists) with one style row each; last=True closes the request.  Returns the
+        payload as bytes (possibly empty); with marks, (payload, marks) with the marks positions in the whole request's stream."""
+        if self.closed:
+            raise ValueError("RequestStream: the request has had its last piece")
+        flags = (PIECE_FIRST if self._carry is None else 0) | (PIECE_LAST if last else 0)
+        if isinstance(self._be, Dispatcher):
+            res = self._be.submit_request(chunks, styles=styles, speed=self._speed, seed=self._seed, fmt=self._fmt, marks=self._marks,
+                                          join=self._join, level=self._level, piece=(flags, self._carry))
+            body, carry = res[0], res[-1]
+            mk = res[1] if self._marks else None
+        else:
+            self._be.set_utterance_base(self._base + self._chunks)
+            try:
+                res = self._be.infer_requests_pieces(chunks, [len(chunks)], [flags], None if self._carry is None else [self._carry],
+                                                     levels=self._level, joins=self._join, styles=styles, speeds=(self._speed,),
+                                                     seed=self._seed, fmt=self._fmt, marks=self._marks)
+            finally:
+                self._be.set_utterance_base(self._base)
+            body, carry = res[0][0], res[2 if self._marks else 1][0]
+            mk = res[1][0] if self._marks else None
+        self._carry = carry
+        self._chunks += len(chunks)
+        self.closed = last
+        return (body, mk) if self._marks else body
 
 
 # ---- stand-alone kernel hooks (tests) -----------------------------------------------------
@@ -1843,3 +1961,44 @@ def flac_requests(audio, dur, lens, chunks_per_request, formats, joins=None, wan
     res, ns, marks, (lengths, out_lv, out_ld, out_lm) = _output_plan(audio, frames, dur, lens, chunks_per_request, formats, j, want, pauses,
                                                                      device, lv, ld, lm, flac=True)
     return res, ns, marks, lengths, out_lv, out_ld, out_lm
+
+
+def piece_requests(audio, dur, lens, chunks_per_request, formats, piece_flags, carries=None, joins=None, want=None, levels=None,
+                   loudness=None, device=0):
+    """Pieces through kx_test_output_plan_pieces: audio, dur, lens, chunks_per_request, formats, joins, want and levels as
+    level_requests takes them (levels and joins may be None), piece_flags = one flag word per request (PIECE_WHOLE: run whole),
+    carries = what the pieces before left (None = zeros; see piece_carries), loudness = one spec per request or None (LOUDNESS_NONE
+    for every piece).  Returns (payloads as bytes, out_samples, marks, carries as an array of PIECE_CARRY_DTYPE, levels [R, 2] or None,
+    loudness [R, 4] or None): voices.piece_bodies, voices.joined_marks and voices.piece_carry.  The hook itself checks the guards
+    around the carry block and behind the bodies."""
+    lib = load_test_library()
+    cpr = np.ascontiguousarray(chunks_per_request, dtype=np.int32)
+    R, B = cpr.shape[0], len(lens)
+    fm = np.ascontiguousarray(formats, dtype=np.int32)
+    pf = np.ascontiguousarray(piece_flags, dtype=np.uint32)
+    assert fm.shape == (R,) and pf.shape == (R,)
+    lv = None if levels is None else level_specs(levels, R)
+    ld = None if loudness is None else loudness_specs(loudness, R)
+    j = None if joins is None else join_specs(joins, R)
+    cin, cout = piece_carries(carries, R), np.zeros(R, PIECE_CARRY_DTYPE)
+    audio = _f32(audio)
+    dur, ln = np.ascontiguousarray(dur, dtype=np.int32), np.ascontiguousarray(lens, dtype=np.int32)
+    assert dur.shape == (B, 512) and audio.shape[0] == B
+    n_frames = int(sum(int(dur[b, : ln[b]].sum()) for b in range(B)))
+    pauses = 0 if j is None else sum(24 * int(j["pause_ms"][r]) * int(cpr[r]) for r in range(R))
+    cap = 16 * (600 * n_frames + pauses) + 1024 * R  # (stereo f32 at 48 kHz; a piece also emits what the ones before held back)
+    mcap = int(ln.sum()) + B
+    wt = None if want is None else np.ascontiguousarray(want, dtype=np.uint8)
+    out, mk = np.zeros(cap, dtype=np.uint8), np.zeros(mcap, dtype=np.int64)
+    nb, ns, nm = np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int64)
+    out_lv = None if lv is None else np.zeros((R, 2), dtype=np.float64)
+    out_ld = None if ld is None else np.full((R, 4), -1.0, dtype=np.float64)
+    _err_call(lib.kx_test_output_plan_pieces, device, _ptr(audio), B, audio.shape[1], None, _ptr(dur), _ptr(ln), _ptr(cpr), R, _ptr(fm),
+              _ptr(j), _ptr(wt), _ptr(out), cap, _ptr(nb), _ptr(ns), _ptr(mk), mcap, _ptr(nm), _ptr(lv), _ptr(out_lv), _ptr(ld),
+              _ptr(out_ld), _ptr(pf), _ptr(cin), _ptr(cout))
+    raw, res, o = out.tobytes(), [], 0
+    for r in range(R):
+        res.append(raw[o: o + int(nb[r])])
+        o += int(nb[r])
+    marks = [m.copy() for m in np.split(mk[: int(nm.sum())], np.cumsum(nm)[:-1])]
+    return res, [int(v) for v in ns], marks, cout, out_lv, out_ld

@@ -645,6 +645,86 @@ def levelled_body(chunks_samples, durations_per_chunk: Sequence[Sequence[int]], 
     return stream_body(level_stream(resample_stream(join_stream(chunks_samples, durations_per_chunk, join), word), level), word)
 
 
+_FORM_SAMPLE_BYTES = {0: 4, 1: 8, 2: 2, 3: 4, 8: 1, 9: 1}  # the forms a piece may have: bytes per sample (form 3: behind 44 header bytes)
+
+
+def piece_ranges(lengths: Sequence[int], word: int) -> List[int]:
+    """E_k of a request run in pieces (the definition of include/kokorox_hip.h, "pieces"): `lengths[k]` = the joined source
+    samples at 24 kHz of piece k (600 x its frames where nothing joins the chunks; `piece_lengths` with a join), `word` the request's
+    format word (only its rate code matters).  With A_k their running sum, N = A L / M and (L, M, C) the rate's filter, output n is
+    final after piece k when n M + C <= A_k L - 1: F_k = clamp(floor((A_k L - 1 - C) / M) + 1, 0, N), E_k = 4 floor(F_k / 4); E_k = A_k
+    at rate code 0, and N for the last piece.  Piece k's payload is samples [E_{k-1}, E_k) of the whole body."""
+    from . import hip_koko as hk
+    code = (int(word) >> 8) & 15
+    if code not in _RATE_LM or not len(lengths):
+        raise ValueError("piece_ranges: unknown output sample rate, or a request without pieces")
+    L, M = _RATE_LM[code]
+    A = np.cumsum(np.asarray(lengths, dtype=np.int64))
+    if int(np.min(np.asarray(lengths, dtype=np.int64))) < 0 or (int(A[-1]) * L) % M:
+        raise ValueError("piece_ranges: negative length, or a stream that gives no whole number of output samples")
+    N = int(A[-1]) * L // M
+    if code == 0:
+        return [int(a) for a in A]
+    C = (hk.resample_filter(word)[2].shape[0] - 1) // 2
+    out = []
+    for k, a in enumerate(int(v) for v in A):
+        q = a * L - 1 - C
+        F = min(max(q // M + 1, 0), N) if q >= 0 else 0
+        out.append(N if k == len(A) - 1 else 4 * (F // 4))
+    return out
+
+
+def piece_lengths(durations_per_chunk: Sequence[Sequence[int]], join, cuts: Sequence[int]) -> List[int]:
+    """The joined source samples of every piece of ONE request: `cuts[k]` = chunks of piece k (they add up to the request's chunks).
+    A piece's rows have the join rows they have in the whole request (`join_rows`): a piece that is not the last keeps the pause
+    behind its final chunk, and every boundary between pieces is an inner boundary."""
+    rows = join_rows(durations_per_chunk, join)
+    if sum(int(c) for c in cuts) != len(rows) or any(int(c) < 1 for c in cuts):
+        raise ValueError("piece_lengths: every piece has a chunk, and the pieces add up to the request")
+    out, at = [], 0
+    for c in cuts:
+        out.append(sum(keep + gap for _, keep, gap, _, _ in rows[at: at + int(c)]))
+        at += int(c)
+    return out
+
+
+def piece_bodies(chunks_samples, durations_per_chunk: Sequence[Sequence[int]], word: int, join, level, cuts: Sequence[int]) -> List[bytes]:
+    """The payloads of ONE request run in pieces of cuts[k] chunks each, as slices of `levelled_body` of the request run whole (level a
+    spec of mode LEVEL_GAIN, or None): piece k is the bytes of samples [E_{k-1}, E_k) in the word's form, behind the form's header in
+    piece 0 only.  Laid end to end they are the whole body, every byte."""
+    form = int(word) & 0xFF
+    if form not in _FORM_SAMPLE_BYTES:
+        raise ValueError("piece_bodies: a piece cannot carry a sized form")
+    if level is not None and _level_fields(level)[0] != LEVEL_GAIN:
+        raise ValueError("piece_bodies: a piece cannot carry a measured level")
+    body = levelled_body(chunks_samples, durations_per_chunk, word, join, level)
+    E = piece_ranges(piece_lengths(durations_per_chunk, join, cuts), word)
+    w, hdr = _FORM_SAMPLE_BYTES[form], 44 if form == 3 else 0
+    edges = [0] + [hdr + w * e for e in E]
+    assert edges[-1] == len(body)
+    return [body[a: b] for a, b in zip(edges[:-1], edges[1:])]
+
+
+def piece_carry(chunks_samples, durations_per_chunk: Sequence[Sequence[int]], word: int, join, cuts: Sequence[int]) -> np.ndarray:
+    """The carry every piece of ONE request leaves, an array of hip_koko.PIECE_CARRY_DTYPE: A_k and E_k, the chunks so far, and the
+    last n_tail = min(PIECE_TAIL, A_k) samples of the joined 24 kHz stream so far (n_tail = 0 at rate code 0), zeros behind them.
+    A request run whole (one piece) leaves the all-zero record."""
+    from . import hip_koko as hk
+    out = np.zeros(len(cuts), hk.PIECE_CARRY_DTYPE)
+    if len(cuts) == 1:
+        return out
+    x = join_stream(chunks_samples, durations_per_chunk, join)
+    lengths = piece_lengths(durations_per_chunk, join, cuts)
+    A, E, code = np.cumsum(lengths), piece_ranges(lengths, word), (int(word) >> 8) & 15
+    for k in range(len(cuts)):
+        n_tail = 0 if code == 0 else min(hk.PIECE_TAIL, int(A[k]))
+        out[k]["magic"], out[k]["format_word"] = hk.PIECE_MAGIC, int(word)
+        out[k]["src_samples"], out[k]["out_samples"] = int(A[k]), int(E[k])
+        out[k]["n_tail"], out[k]["reserved"] = n_tail, sum(int(c) for c in cuts[: k + 1])
+        out[k]["tail"][:n_tail] = x[int(A[k]) - n_tail: int(A[k])]
+    return out
+
+
 LOUDNESS_MEASURE, LOUDNESS_NORMALIZE = 0, 1
 LOUDNESS_METER = (LOUDNESS_MEASURE, 0.0, 0.0)
 LOUDNESS_ABS_GATE = 10.0 ** ((-70 + 0.691) / 10)  # the absolute gate of BS.1770 as a block energy

@@ -32,6 +32,9 @@ the command line; an optional second argument is the batch (1 = one utterance). 
     a word and 'f'       ('2f') kx_infer_requests_fitted, every row a request of its own with one span over all its 130 tokens fitted
                          to 422 frames (what the pinned pattern gives the other modes; a fit refuses a pinned model, so this mode
                          runs without the pattern): fit_weights_kernel and fit_spans_kernel in front of prosody_duration_kernel;
+    a word and 'q'       ('0x108q') kx_infer_requests_pieces, every row a one-chunk piece of a request of its own: the first call the
+                         FIRST pieces, the second middle pieces with the carries of the first, the third the LAST pieces:
+                         resample_pieces_kernel in the resampler's place and piece_carry_kernel behind it, the packer as ever;
     a word and 'g'       ('2g') the same grouping without joins (kx_infer_requests_marks): the plain kernels on the same batch.
 Meant to run under the profiler, one mode per run (kernel trace only, no counters in the same run):
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o t -- python tools/pack_profile.py p2
@@ -101,6 +104,14 @@ for it in range(3):
         assert all(int(k) == 422 * 600 * L // M for k in ns) and all(int(f["n_free"]) == 130 for f in fit)
         if it == 2:
             print("fit of the first request: lambda %.6f, excess %d" % (float(fit[0]["lambda"]), int(fit[0]["excess"])))
+    elif which.endswith("q"):
+        word = int(which[:-1], 0)
+        L, M, _ = hk.resample_filter(word)
+        out, carries, ns = m.infer_requests_pieces(toks, [1] * B, [[hk.PIECE_FIRST, 0, hk.PIECE_LAST][it]] * B, carries if it else None,
+                                                   styles=rows, fmt=word, with_samples=True)
+        assert (carries["src_samples"] == 422 * 600 * (it + 1)).all() and (carries["reserved"] == it + 1).all()
+        assert it < 2 or (carries["out_samples"] == 3 * 422 * 600 * L // M).all()
+        print("call", it, "samples of the first piece", ns[0], "of", 422 * 600 * L // M, "a chunk")
     elif which.endswith("m"):
         word = int(which[:-1], 0)
         out, marks = m.infer_requests_marks(toks, [1] * B, styles=rows, fmt=word)
