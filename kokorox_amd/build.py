@@ -13,7 +13,17 @@ LIB_PATH = os.path.join(LIB_DIR, "libkokorox_hip.so")
 TEST_LIB_PATH = os.path.join(LIB_DIR, "libkokorox_hip_test.so")
 # one unit per job: conv launches, the token-axis front half (with the two LSTM switches), the back half's other kernels, the output stage
 TEST_SOURCES = ["test_hooks_conv.hip", "test_hooks_front.hip", "test_hooks_head.hip", "test_hooks_output.hip"]
-SOURCES = ["conv_plan.hip", "conv_call.hip", "conv_mfma.hip", "conv_f16x3.hip", "conv_f16x3_da.hip", "conv_f16x3_da_p1.hip", "conv_f16x3_da_w2.hip", "conv_f16x3_da_s16.hip", "conv_f16x3_da_f8.hip", "conv_f16x3_da_pre.hip", "conv_f16x3_pre.hip", "conv_f16x3_dapn.hip", "conv_f16x3_dag.hip", "kernels_misc.hip", "request_kernels.hip", "model.hip", "model_forward.hip", "model_host.hip", "api.hip", "dispatcher.hip", "onnx_import.cpp", "kxw_file.cpp",
+# the output stage, one unit per job, each with the headers of its own that it includes (request_units.h: the stages the launcher
+# calls; request_stream.h: a request's stream on the device; request_truepeak.h: what the true-peak meter and the limiter share)
+_REQUEST_DEPS = {"request_pack.hip": ["request_stream.h", "request_units.h"],
+                 "request_resample.hip": ["request_stream.h", "request_units.h", "resample_taps.h"],
+                 "request_levels.hip": ["request_stream.h", "request_units.h", "request_truepeak.h", "truepeak_taps.h", "kweight_coefs.h"],
+                 "request_limit.hip": ["request_stream.h", "request_units.h", "request_truepeak.h", "truepeak_taps.h", "limit_taps.h"],
+                 "request_flac.hip": ["request_stream.h", "request_units.h"],
+                 "request_adpcm.hip": ["request_stream.h", "request_units.h", "adpcm_steps.h"],
+                 "request_marks.hip": ["request_units.h"], "request_launch.hip": ["request_units.h"]}
+REQUEST_SOURCES = list(_REQUEST_DEPS)
+SOURCES = ["conv_plan.hip", "conv_call.hip", "conv_mfma.hip", "conv_f16x3.hip", "conv_f16x3_da.hip", "conv_f16x3_da_p1.hip", "conv_f16x3_da_w2.hip", "conv_f16x3_da_s16.hip", "conv_f16x3_da_f8.hip", "conv_f16x3_da_pre.hip", "conv_f16x3_pre.hip", "conv_f16x3_dapn.hip", "conv_f16x3_dag.hip", "kernels_misc.hip", *REQUEST_SOURCES, "model.hip", "model_forward.hip", "model_host.hip", "api.hip", "dispatcher.hip", "onnx_import.cpp", "kxw_file.cpp",
            "host_request.cpp", "host_pool.cpp"]
 HEADERS = ["kx_common.h", "kx_error.h", "host_request.h", "conv_epilogue.h", "conv_f16x3_common.h"]  # (kx_common.h includes host_request.h)
 _PUB = os.path.join("..", "..", "include", "kokorox_hip.h")
@@ -22,7 +32,7 @@ _PUB_TEST = os.path.join("..", "..", "include", "kokorox_hip_test.h")
 # (model.h includes kxw_file.h, which includes onnx_import.h)
 _MODEL_H = ["model.h", "kxw_file.h", "onnx_import.h"]
 EXTRA_DEPS = {"model.hip": [*_MODEL_H, _PUB], "model_forward.hip": [*_MODEL_H, _PUB], "model_host.hip": [*_MODEL_H, "host_pool.h", _PUB],
-              "host_pool.cpp": ["host_pool.h"], "host_request.cpp": ["resample_taps.h", "kweight_coefs.h", "truepeak_taps.h", "limit_taps.h", "adpcm_steps.h"], "request_kernels.hip": ["resample_taps.h", "kweight_coefs.h", "truepeak_taps.h", "limit_taps.h", "adpcm_steps.h"], "conv_call.hip": _MODEL_H, "api.hip": [*_MODEL_H, "kx_handle.h", "api_guard.h", "check_device.h", _PUB],
+              "host_pool.cpp": ["host_pool.h"], "host_request.cpp": ["resample_taps.h", "kweight_coefs.h", "truepeak_taps.h", "limit_taps.h", "adpcm_steps.h"], **_REQUEST_DEPS, "conv_call.hip": _MODEL_H, "api.hip": [*_MODEL_H, "kx_handle.h", "api_guard.h", "check_device.h", _PUB],
               "dispatcher.hip": [*_MODEL_H, "kx_handle.h", "dispatcher_core.h", _PUB],
               **{t: [*_MODEL_H, "test_hooks.h", "api_guard.h", "check_device.h", _PUB, _PUB_TEST] for t in TEST_SOURCES}, "onnx_import.cpp": ["onnx_import.h"],
               "kxw_file.cpp": ["kxw_file.h", "onnx_import.h"], "conv_f16x3_da_p1.hip": ["conv_f16x3_da.hip"], "conv_f16x3_da_w2.hip": ["conv_f16x3_da.hip"], "conv_f16x3_da_s16.hip": ["conv_f16x3_da.hip"], "conv_f16x3_da_f8.hip": ["conv_f16x3_da.hip"], "conv_f16x3_da_pre.hip": ["conv_f16x3_da.hip"]}

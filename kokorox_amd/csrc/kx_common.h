@@ -286,7 +286,7 @@ void launch_diag_stats(const float* x, long bs, int ld, int C, LenMap len, int B
 void launch_style_mix(const float* table, int n_voices, const int* voice_ids, const float* weights, int max_mix,
                       const int* rows, const int* kinds, float* styles, int B, hipStream_t s);
 
-// ---- the output stage of a call (request_kernels.hip; host_request.h: OutputPlan, build_output_plan) ----------------------
+// ---- the output stage of a call (request_launch.hip and the request_*.hip units it launches; host_request.h: OutputPlan, build_output_plan) ----------------------
 // Device memory for a plan's tables, which the launchers copy the plan into: req [R], cum [B + 1], join [B] (used by a joined
 // or levelled plan only), mark [B] (used when a request wants marks only); a measured plan (OutputPlan::measured) also level [R]
 // and peak, the partials table of the peak pass (plan.peak_dwords() dwords: scratch, nothing in it outlives a call)

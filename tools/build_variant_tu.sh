@@ -1,5 +1,5 @@
 #!/bin/bash
-# build_variant_tu.sh NAME TU ALT_SOURCE [extra flags]: a library variant in which translation unit TU (e.g. kernels_misc, or request_kernels for the packer, the resampler and the marks) is compiled
+# build_variant_tu.sh NAME TU ALT_SOURCE [extra flags]: a library variant in which translation unit TU (e.g. kernels_misc, or request_pack / request_resample / request_marks for the packer, the resampler and the marks) is compiled
 # from ALT_SOURCE (e.g. an older revision written to /tmp by `git show REV:kokorox_amd/csrc/TU.hip`), every other object reused
 # from kokorox_amd/lib -> kokorox_amd/lib/variants/lib_NAME.so (select with KX_LIB; tools/ab_variants.sh)
 set -e
